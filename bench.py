@@ -17,13 +17,20 @@ through: ring_rows()), inputs resident before the timed region.  Multi-GPU = ind
 on the step path (weak scaling); the only communication is the timing barrier / MAX.
 
 Timing.  The step launches are captured once into a hipGraph and the graph is replayed: after the
-W warm-up steps it is replayed for >= 0.3 s (clocks up, the graph uploaded -- a first replay is
-several times slower than a steady one), then the timed region runs the K steps R times back to
-back between barrier + synchronize on both sides; R ("repeats") is 1 for K >= 2000 and
-ceil(2000 / K) below that, so that one graph-launch latency (~15-40 us) is not smeared over a
-handful of 5 us steps.  A graph holds up to --chunk (200) consecutive steps -- a divisor of K, or,
-for a short K, several repetitions of the K steps (`steps_per_graph` in the line).  `ms_per_step`,
-`value` and `roofline` are means over the K * R timed steps (`timed_steps`).
+W warm-up steps and SETTLE_STEPS more (the episodes started together by reset() drift apart until
+the in-step reset rate is the steady one), the state is kept aside, the graph is replayed for
+>= 0.3 s (clocks up, the graph uploaded -- a first replay is several times slower than a steady
+one), the state is put back, and the timed region runs exactly the K steps between barrier +
+synchronize on both sides.  The timed steps therefore compute the same thing on every run with the
+same arguments, however many replays the spin fitted in.  A graph holds up to --chunk (200)
+consecutive steps -- a divisor of K where one exists, the rest of K eagerly (`steps_per_graph` in
+the line).  `ms_per_step`, `value` and `roofline` are means over the K timed steps; for a short K
+they include one graph-launch latency (~15-40 us).
+
+--dump-outputs DIR: after the timed steps, what the last one returned to its caller -- obs, reward,
+done and the infos of the envs that finished (outcome, episode return / length, terminal
+observation; zero for the others) -- as DIR/<name>.npy in float32 / float64, rank 0's shard, under
+64 MB (above that, the same seeded sample of env rows in every array, `sample_index.npy`).
 
 One JSON line on rank 0 with `roofline` (HBM bound; algorithmic bytes B(N,s) = s(16+9N)+9 per
 env-step / average launch duration measured with HIP events on the launch stream) and
@@ -33,7 +40,6 @@ configs[0] and the batch of the headline workload).
 """
 import argparse
 import json
-import math
 import os
 import socket
 import subprocess
@@ -46,6 +52,9 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.3 TB/s achievable copy)
 METRIC = "env-steps/sec at 65536 envs x N_TRAFFIC=8; achieved HBM GB/s vs peak"
+SETTLE_STEPS = 8000          # after reset() (N_TRAFFIC = 8): 100-step means of the reset rate are down to their noise by ~6 000
+DUMP_LIMIT_BYTES = 60_000_000   # --dump-outputs: under 64 MB with the .npy headers
+INFO_FIELDS = ("outcome", "terminal_observation", "episode_return", "episode_steps")    # written only where done
 
 
 def parse(argv=None):
@@ -64,8 +73,9 @@ def parse(argv=None):
     ap.add_argument("--action-rows", type=int, default=0,
                     help="distinct pre-generated action rows the steps cycle through (0 = the largest divisor <= 32 of the "
                          "steps of one graph; see ring_rows)")
-    ap.add_argument("--repeats", type=int, default=0, help="timed repetitions of the K steps (0 = auto: ceil(2000 / K))")
     ap.add_argument("--spin-seconds", type=float, default=0.3, help="graph replays before the timed region")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (rank 0, under 64 MB)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--device", type=int, default=None, help="rehearsal only: force this GPU index on every rank")
     ap.add_argument("--rehearsal", action="store_true",
@@ -333,6 +343,44 @@ class RehearsalEnv:
     def step_from(self, row):
         self.acc.add_(row)
 
+    @property
+    def outputs(self):
+        return {"acc": self.acc}
+
+
+def pick_graph_steps(k, chunk, cap):
+    """Steps per captured graph: a multiple of the `chunk` action rows, at most min(cap, K), even where one is (an odd
+    graph turns double buffering off, StepRunner) -- the largest that divides K, else the largest, the rest of the K
+    steps eagerly."""
+    sizes = [chunk * d for d in range(1, max(1, min(cap, k) // chunk) + 1)]
+    sizes = [n for n in sizes if n % 2 == 0] or sizes
+    return max([n for n in sizes if k % n == 0] or sizes)
+
+
+def dump_outputs(outputs, dirname, limit=DUMP_LIMIT_BYTES):
+    """Write the tensors of `outputs` (dim 0 = env) as dirname/<name>.npy, float64 where the engine computed float64,
+    float32 otherwise.  The infos are zeroed where `done` is false (stale there); above `limit` bytes every array
+    keeps the same seeded sample of rows, whose indices go to sample_index.npy."""
+    import numpy as np
+    host = {n: t.detach().cpu().numpy() for n, t in outputs.items() if t is not None}
+    if "done" in host:
+        done = host["done"].astype(bool)
+        for n in INFO_FIELDS:
+            if n in host:
+                host[n] = np.where(done.reshape((-1,) + (1,) * (host[n].ndim - 1)), host[n], 0)
+    host = {n: a.astype(np.float64 if a.dtype == np.float64 else np.float32) for n, a in host.items()}
+    rows = len(next(iter(host.values())))
+    total = sum(a.nbytes for a in host.values())
+    if total > limit:
+        keep = limit // (total // rows + 8)
+        idx = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        host = {n: a[idx] for n, a in host.items()}
+        host["sample_index"] = idx.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for n, a in host.items():
+        np.save(os.path.join(dirname, n + ".npy"), a)
+    return sorted(host)
+
 
 def main():
     args = parse()
@@ -371,22 +419,24 @@ def main():
     gen = torch.Generator(device=dev).manual_seed(1000 + rank)
     actions = torch.rand(chunk, E, generator=gen, device=dev, dtype=dtype) * 2 - 1
     use_graph = args.launch == "graph" and not args.rehearsal
-    repeats = args.repeats if args.repeats > 0 else (1 if K >= 2000 else min(400, math.ceil(2000 / K)))
-    # the timed region is `repeats` x K consecutive steps; a short K is captured several times over per graph (the
-    # actions repeat every `chunk` steps either way), so that a small --steps does not time graph-launch gaps instead
-    m = max(d for d in range(1, max(1, args.chunk // chunk) + 1) if (K * repeats) % (chunk * d) == 0)
-    graph_steps = chunk * m
+    graph_steps = pick_graph_steps(K, chunk, args.chunk)
     runner = StepRunner(env, actions, use_graph, graph_steps)
 
     def barrier():
         if world > 1:
             torch.distributed.barrier()
 
-    # ---- warm-up: the W steps asked for, then the captured graphs replayed for spin-seconds ----
+    # ---- warm-up: the W steps asked for and the settling steps, then the captured graphs replayed for spin-seconds
+    #      from a copy of that state, which the timed steps start from again ----
     runner.run(W)
-    sync()
-    spin_replays = runner.spin(args.spin_seconds) if not args.rehearsal else 0
-    # ---- timed region: the K steps, R times, between barrier + synchronize on both sides ----
+    spin_replays = 0
+    if not args.rehearsal:
+        runner.run(SETTLE_STEPS)
+        start = env.state_dict()
+        spin_replays = runner.spin(args.spin_seconds)
+        env.load_state_dict(start)
+        del start
+    # ---- timed region: the K steps between barrier + synchronize on both sides ----
     sync()
     barrier()
     sync()
@@ -395,7 +445,7 @@ def main():
     t0 = time.perf_counter()
     if not args.rehearsal:
         ev0.record()                   # same stream as the kernel launches (torch's current stream)
-    runner.run(K * repeats)
+    runner.run(K)
     if not args.rehearsal:
         ev1.record()
     sync()
@@ -407,7 +457,9 @@ def main():
     wall = g.sharding.max_over_ranks(wall, device=red_dev)
     dev_ms = g.sharding.max_over_ranks(dev_ms, device=red_dev)
     episodes = g.sharding.sum_over_ranks(float(env.episode.to(torch.int64).sum().item()), device=red_dev)
-    timed_steps = K * repeats
+    timed_steps = K
+    if args.dump_outputs and rank == 0:
+        dump_outputs(env.outputs, args.dump_outputs)
 
     # ---- secondary: the same workload through acas2d_rollout_* (T steps fused per launch) ----
     fused = None
@@ -464,7 +516,7 @@ def main():
             "metric": METRIC,
             "value": E * world * timed_steps / wall,
             "unit": "env-steps/s",
-            "n_gpus": world, "steps": K, "warmup": W, "repeats": repeats, "timed_steps": timed_steps,
+            "n_gpus": world, "steps": K, "warmup": W, "timed_steps": timed_steps,
             "ms_per_step": wall * 1e3 / timed_steps,
             "higher_is_better": True,
             "scaling": "weak",
@@ -492,7 +544,7 @@ def main():
                                               else "in place",
                              "state_layout": "consecutive rows (all loads through preloaded base pointers)"
                                              if getattr(env, "consecutive_layout", False) else "separate arrays",
-                             "warmup_graph_replays": spin_replays,
+                             "settle_steps": SETTLE_STEPS, "warmup_graph_replays": spin_replays,
                              "lanes_per_env": geo["lanes_per_env"], "traffic_per_lane": geo["traffic_per_lane"],
                              "grid_blocks": geo["grid_blocks"],
                              "parallelism": "env-index shards x%d, no collective on the step path" % world,
