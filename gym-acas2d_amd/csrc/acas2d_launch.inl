@@ -85,10 +85,39 @@ static int write_offsets(const Acas2dState* st, const Acas2dState* out, bool aut
     }
     const int64_t lim = 0x7fffffffLL - n_envs * (int64_t)n_traffic - 64;
     const int64_t ad = d < 0 ? -d : d, adt = dt < 0 ? -dt : dt;
-    if ((ad != 0 && ad < n_envs) || (adt != 0 && adt < n_envs * (int64_t)n_traffic) || ad > lim || adt > lim) {   // (either group may stay in place)
-        set_error("acas2d_step: state_out overlaps state, or lies more than 2^31 elements away");
+    if (ad > lim || adt > lim) {
+        set_error("acas2d_step: state_out lies more than 2^31 elements away from state");
         return ACAS2D_EINVAL;
     }
+    // No byte a moved group writes may be one the step reads: any array of `st` (trace aside), the shared ones
+    // written in place at a reset included.  (A group at offset 0 is stepped in place, as without a state_out.)
+    // Compared in bytes: steps is int32 while T may be 8 bytes wide.
+    const int64_t E = n_envs, EN = n_envs * (int64_t)n_traffic, sT = (int64_t)sizeof(T);
+    struct Range { const char* name; const void* p; int64_t bytes; };
+    const Range reads[] = {{"own_x", st->own_x, E * sT}, {"own_y", st->own_y, E * sT}, {"own_psi", st->own_psi, E * sT},
+                           {"own_v", st->own_v, E * sT}, {"goal_x", st->goal_x, E * sT}, {"goal_y", st->goal_y, E * sT},
+                           {"trf_x", st->trf_x, EN * sT}, {"trf_y", st->trf_y, EN * sT}, {"trf_psi", st->trf_psi, EN * sT},
+                           {"trf_v", st->trf_v, EN * sT}, {"steps", st->steps, E * 4}, {"total_reward", st->total_reward, E * sT},
+                           {"status", st->status, E}, {"episode", st->episode, E * 4}};
+    const Range env_writes[] = {{"own_x", out->own_x, E * sT}, {"own_y", out->own_y, E * sT}, {"own_psi", out->own_psi, E * sT},
+                                {"total_reward", out->total_reward, E * sT}, {"steps", out->steps, E * 4}};
+    const Range trf_writes[] = {{"trf_x", out->trf_x, EN * sT}, {"trf_y", out->trf_y, EN * sT}};
+    const auto overlap = [&](const Range& w) -> bool {
+        const uintptr_t w0 = (uintptr_t)w.p, w1 = w0 + (uintptr_t)w.bytes;
+        for (const Range& r : reads) {
+            const uintptr_t r0 = (uintptr_t)r.p, r1 = r0 + (uintptr_t)r.bytes;
+            if (w0 < r1 && r0 < w1) {
+                set_error("acas2d_step: state_out's %s overlaps state's %s (a double-buffered array must not share a byte "
+                          "with any array the step reads)", w.name, r.name);
+                return true;
+            }
+        }
+        return false;
+    };
+    if (d != 0)
+        for (const Range& w : env_writes) if (overlap(w)) return ACAS2D_EINVAL;
+    if (dt != 0)
+        for (const Range& w : trf_writes) if (overlap(w)) return ACAS2D_EINVAL;
     *w_env = (int32_t)d; *w_trf = (int32_t)dt;
     return ACAS2D_OK;
 }

@@ -389,7 +389,7 @@ class ACAS2DVecEnv:
         MlpPolicy actor (`policy.SB3ActorPolicy` / `ppo.ActorCritic`) evaluated inside the kernel on
         the observation the previous step left -- `self.outputs["obs"]` at the start, so call
         reset() / step() / set_state(observe=True) first.  One lane per env: n_traffic in
-        {1, 2, 3, 4, 8} for float32, {1, 2, 3} for float64.  Returns rollout()'s dict plus
+        {1, 2, 3, 4, 8} for float32, {1, 2, 3, 4} for float64.  Returns rollout()'s dict plus
         "actions" [T, E] (the actions taken); VecEnv auto-reset semantics."""
         if not self.auto_reset:
             raise RuntimeError("rollout_policy() has VecEnv auto-reset semantics; construct with auto_reset=True")

@@ -159,7 +159,8 @@ const char *acas2d_last_error(void);  /* thread-local; valid until the next fail
  *   whereas stores to the other generation stream out during it (65 536 x 8 float32: 4.23 vs 4.65 us per launch).
  *   Layout contract: state_out's own_x, own_y, own_psi, steps and total_reward lie at ONE element offset from
  *   state's, its trf_x and trf_y at one (e.g. every such array allocated as [2][E] / [2][E][N], the two structs
- *   pointing at the two halves), without overlap and less than 2^31 elements away; every other field (own_v,
+ *   pointing at the two halves), less than 2^31 elements away, and not one byte of them inside any array of
+ *   `state` (trace aside) -- the arrays shared between the two included; every other field (own_v,
  *   goal_*, trf_psi, trf_v, status, episode, trace: changed at a reset only, in place) is the SAME buffer in
  *   both structs.  Needs ACAS2D_AUTO_RESET.  A hipGraph that captures an odd number of steps must not be
  *   replayed twice in a row (each replay would read the generation the previous one also read).

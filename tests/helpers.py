@@ -8,6 +8,7 @@ interface so that both are checked by the same code against the same fixtures.
 """
 import os
 import random
+from collections import namedtuple
 
 import numpy as np
 
@@ -135,3 +136,53 @@ def assert_matches_reference_policy_eval(total_reward, steps, path_length, tol=2
     for col, want in REF_POLICY_EVAL.items():
         for k, w in want.items():
             assert abs(got[col][k] - w) <= tol * max(1.0, abs(w)), (col, k, got[col][k], w)
+
+
+# ---- work-shape coverage ------------------------------------------------------------------------------------------
+# step_kernel is instantiated once per work shape: C traffic aircraft per lane as one vector, G lanes per env (the
+# packed shapes of ACAS2D_PACKED_SHAPES in gym-acas2d_amd/csrc/acas2d_f32.hip / acas2d_f64.hip), or the generic
+# strided walk with G in {1, 4, 16, 64} lanes per env (any N).  One row per shape and build -- float32 (FAST), and the
+# float64 build in each of its formulations -- with the N that reaches it, through choose_shape() (override None) or
+# ACAS2D_SHAPE.  C is None for the generic walk.  tests/test_host.py holds this table to the .hip lists; the GPU
+# tests of tests/test_gpu_parity.py run every row.
+class Shape(namedtuple("Shape", "dtype math n_traffic override C G")):
+    """dtype "float32" / "float64"; math "fast" / "exact" (float32 has FAST only); override: ACAS2D_SHAPE, or None
+    for the default choice."""
+    __slots__ = ()
+    packed = property(lambda s: s.C is not None)
+    elem = property(lambda s: 4 if s.dtype == "float32" else 8)
+    dtype_name = property(lambda s: "float64fast" if (s.dtype == "float64" and s.math == "fast") else s.dtype)
+
+    @property
+    def id(self):
+        shape = "%d,%d" % (self.C, self.G) if self.packed else "generic,%d" % self.G
+        return "%s-N%d-%s%s" % (self.dtype_name, self.n_traffic, shape, "" if self.override is None else "-override")
+
+    @property
+    def envs_per_wave(self):
+        return 64 // self.G
+
+    @property
+    def reset_slots(self):
+        """Envs one pass of the in-step reset takes (geometry_for() / ResetSlots in the kernels): a packed shape with
+        N + 1 <= 32 has 64 / stride slots, stride the power of two >= max(2, N + 1); the others reset one env per pass."""
+        if not self.packed or self.n_traffic + 1 > 32:
+            return 1
+        stride = 2
+        while stride < self.n_traffic + 1:
+            stride *= 2
+        return 64 // stride
+
+
+def _rows(dtype, math, rows):
+    return [Shape(dtype, math, n, ov, c, gl) for n, ov, c, gl in rows]
+
+
+_F32 = [(1, None, 1, 1), (2, None, 2, 1), (3, None, 3, 1), (4, None, 4, 1), (8, "8,1", 8, 1), (8, None, 4, 2),
+        (8, "2,4", 2, 4), (16, None, 4, 4), (32, None, 4, 8), (64, None, 4, 16), (64, "8,8", 8, 8), (64, "2,32", 2, 32),
+        (8, "generic,1", None, 1), (5, None, None, 4), (33, None, None, 16), (100, None, None, 64)]
+_F64 = [(1, None, 1, 1), (2, None, 2, 1), (3, None, 3, 1), (4, None, 4, 1), (8, "2,4", 2, 4), (8, None, 4, 2),
+        (16, None, 4, 4), (32, None, 4, 8), (64, "2,32", 2, 32), (64, None, 4, 16),
+        (3, "generic,1", None, 1), (5, None, None, 4), (17, None, None, 16), (100, None, None, 64)]
+SHAPES = _rows("float32", "fast", _F32) + _rows("float64", "exact", _F64) + _rows("float64", "fast", _F64)
+GENERIC_G = (1, 4, 16, 64)

@@ -165,6 +165,124 @@ def test_c_abi_argument_validation_needs_no_gpu(g):
         g.native.launch_geometry(16, 5000)
 
 
+_READ_ARRAYS = ("own_x", "own_y", "own_psi", "own_v", "goal_x", "goal_y", "trf_x", "trf_y", "trf_psi", "trf_v", "steps",
+                "total_reward", "status", "episode")
+
+
+class _SyntheticF64State:
+    """A float64 state of E envs x N traffic on host memory: array k of _READ_ARRAYS in slot k (SLOT bytes apart).
+    Every case built from it must be rejected by acas2d_step's validation BEFORE any launch: the addresses are not
+    device memory."""
+    E, N, SLOT = 4, 2, 1024
+
+    def __init__(self, g):
+        self.g, self.L = g, g.native.lib()
+        self.buf = (C.c_char * (self.SLOT * 64))()
+        self.base = C.addressof(self.buf) + 16 * self.SLOT          # room below for negative offsets
+        self.cfg = g.ACAS2DConfig(n_traffic=self.N).to_c()
+        self.at = {n: self.base + k * self.SLOT for k, n in enumerate(_READ_ARRAYS)}
+        self.st = g.native.CState(*[self.at.get(n) for n, _ in g.native.CState._fields_])      # trace stays NULL
+        self.io = g.native.CStepIO(*([self.base + 40 * self.SLOT] * 5 + [None] * 3))
+        E, N = self.E, self.N
+        self.bytes = {n: E * N * 8 if n.startswith("trf") else E * {"steps": 4, "status": 1, "episode": 4}.get(n, 8)
+                      for n in _READ_ARRAYS}
+
+    def out(self, d=0, dt=0):
+        """state_out: own_x, own_y, own_psi, total_reward (float64) and steps (int32) d ELEMENTS from state's, trf_x and
+        trf_y dt elements; everything else shared."""
+        f = dict(self.at)
+        for n in ("own_x", "own_y", "own_psi", "total_reward"):
+            f[n] += 8 * d
+        f["steps"] += 4 * d
+        for n in ("trf_x", "trf_y"):
+            f[n] += 8 * dt
+        return self.g.native.CState(*[f.get(n) for n, _ in self.g.native.CState._fields_])
+
+    def step(self, out):
+        return self.L.acas2d_step_f64(C.byref(self.cfg), C.byref(self.st), C.byref(out), C.byref(self.io),
+                                      self.g.native.AUTO_RESET, 0, 0, self.E, self.N, None)
+
+
+def test_state_out_writing_into_another_array_of_state_is_rejected(g):
+    """write_offsets(): each double-buffered array only clearing ITSELF is not enough -- state_out.own_x == state.own_y
+    (one element offset of E, as far as own_x alone can tell a clean second generation) would stream one env's stores
+    over rows other wavefronts are still reading."""
+    s = _SyntheticF64State(g)
+    d = s.SLOT // 8                                                  # out.own_x == st.own_y, out.own_y == st.own_psi ...
+    assert s.out(d=d).own_x == s.st.own_y
+    assert s.step(s.out(d=d)) == -22
+    assert b"state_out's own_x overlaps state's own_y" in s.L.acas2d_last_error()
+    # the same for the traffic pair: out.trf_x == st.trf_y
+    dt = s.SLOT // 8
+    assert s.step(s.out(dt=dt)) == -22 and b"state_out's trf_x overlaps state's trf_y" in s.L.acas2d_last_error()
+
+
+@pytest.mark.parametrize("group", ("env", "trf"))
+@pytest.mark.parametrize("target", _READ_ARRAYS)
+def test_state_out_overlap_with_each_array_of_state_is_rejected(g, group, target):
+    """One written group (own_x .. steps, or trf_x / trf_y) moved so that its first array's first element lies on the
+    LAST element of one array the step reads -- a one-element overlap, from above or below -- for every array of state:
+    the double-buffered ones and the ones shared between the two structs (written in place at a reset)."""
+    s = _SyntheticF64State(g)
+    first = "own_x" if group == "env" else "trf_x"
+    last = s.at[target] + (s.bytes[target] - 1) // 8 * 8             # the float64-aligned word holding its last byte
+    off = (last - s.at[first]) // 8
+    out = s.out(d=off) if group == "env" else s.out(dt=off)
+    assert s.step(out) == -22, target
+    assert (b"state_out's %s overlaps state's %s" % (first.encode(), target.encode())) in s.L.acas2d_last_error()
+
+
+def test_state_out_overlap_is_checked_in_bytes(g):
+    """steps is int32 while the float64 arrays are 8 bytes wide: one element offset d moves steps by 4 d bytes and the
+    others by 8 d.  Here only the written steps row lands inside state's total_reward -- in its SECOND half, which a
+    check that counted every array as E 4-byte elements would not see."""
+    s = _SyntheticF64State(g)
+    d = (s.at["total_reward"] + 4 * s.E - s.at["steps"]) // 4
+    out = s.out(d=d)
+    assert out.steps == s.at["total_reward"] + 4 * s.E
+    for n in ("own_x", "own_y", "own_psi", "total_reward"):          # the float64 rows land right behind other arrays
+        w0 = getattr(out, n)
+        assert all(w0 >= s.at[r] + s.bytes[r] or w0 + 8 * s.E <= s.at[r] for r in _READ_ARRAYS), n
+    assert s.step(out) == -22
+    assert b"state_out's steps overlaps state's total_reward" in s.L.acas2d_last_error()
+
+
+def _packed_shapes(build):
+    src = open(os.path.join(ROOT, "gym-acas2d_amd", "csrc", "acas2d_%s.hip" % build)).read()
+    line = re.search(r"^#define ACAS2D_PACKED_SHAPES\(X\)(.*)$", src, re.M).group(1)
+    return {(int(c), int(gl)) for c, gl in re.findall(r"X\(\s*(\d+)\s*,\s*(\d+)\s*\)", line)}
+
+
+def test_shape_table_is_exactly_the_compiled_set():
+    """helpers.SHAPES (the rows the GPU tests run) against the instantiations: a shape added to ACAS2D_PACKED_SHAPES
+    without a row, or a row whose shape is no longer compiled, fails here -- for float32 and for each float64
+    formulation (one instantiation per formulation)."""
+    builds = {"float32": _packed_shapes("f32"), "float64": _packed_shapes("f64")}
+    assert (4, 2) in builds["float32"] and (4, 2) in builds["float64"] and len(builds["float32"]) >= 10
+    for dtype, math in (("float32", "fast"), ("float64", "exact"), ("float64", "fast")):
+        rows = [s for s in H.SHAPES if (s.dtype, s.math) == (dtype, math)]
+        assert {(s.C, s.G) for s in rows if s.packed} == builds[dtype], (dtype, math)
+        assert {s.G for s in rows if not s.packed} == set(H.GENERIC_G), (dtype, math)
+        assert len(rows) == len(builds[dtype]) + len(H.GENERIC_G), (dtype, math)        # one row per shape
+    assert all(s.math == "fast" for s in H.SHAPES if s.dtype == "float32")
+
+
+@pytest.mark.parametrize("shape", H.SHAPES, ids=[s.id for s in H.SHAPES])
+def test_shape_table_rows_resolve_to_their_shape(g, monkeypatch, shape):
+    """Each row's N (and ACAS2D_SHAPE, where it has one) resolves to the row's (C, G) in launch_geometry() -- the
+    same resolve_shape() the step / reset / rollout launches call -- so a GPU test run on that row runs that kernel.
+    (An override that named a shape no longer compiled would fall back to the generic walk and fail here.)"""
+    if shape.override is None:
+        monkeypatch.delenv("ACAS2D_SHAPE", raising=False)
+    else:
+        monkeypatch.setenv("ACAS2D_SHAPE", shape.override)
+    geo = g.native.launch_geometry(1000, shape.n_traffic, shape.elem)
+    assert geo["lanes_per_env"] == shape.G
+    assert geo["traffic_per_lane"] == (shape.C if shape.packed else -1)
+    if shape.packed:
+        assert shape.C * shape.G == shape.n_traffic
+
+
 def test_no_cpu_fallback(g, monkeypatch):
     import torch
     if torch.cuda.is_available():
