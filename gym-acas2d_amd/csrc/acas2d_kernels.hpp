@@ -1426,10 +1426,13 @@ __device__ __forceinline__ float policy_mlp(const float* w1t_, const float* b1_,
     for (int i = 0; i < H2; ++i) acc = __builtin_elementwise_fma(w3[i], F2{tanh_hw(g[i].x), tanh_hw(g[i].y)}, acc);
     return (acc.x + acc.y) + b3[0];
 }
-// the deterministic action = clip(mean, -1, 1) (SB3 policies.py predict())
+// the deterministic action = clip(mean, -1, 1) (SB3 policies.py predict()).  np.clip / torch.clamp keep a NaN mean
+// (a NaN observation: the reference's d_cpa in exact parallel flight, kinematics.py:48) NaN, while fminf / fmaxf
+// (IEEE maxNum) would turn it into a bound: the select keeps it.
 template <int D>
 __device__ __forceinline__ float policy_action(const PolicyW& pw, const float (&x)[D]) {
-    return fminf(fmaxf(policy_mlp<D>(pw.w1t, pw.b1, pw.w2t, pw.b2, pw.w3, pw.b3, x), -1.0f), 1.0f);
+    const float m = policy_mlp<D>(pw.w1t, pw.b1, pw.w2t, pw.b2, pw.w3, pw.b3, x);
+    return m != m ? m : fminf(fmaxf(m, -1.0f), 1.0f);
 }
 
 // ---- kernels ------------------------------------------------------------------------------------------

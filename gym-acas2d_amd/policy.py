@@ -99,7 +99,8 @@ def evaluate_policy_fused(policy, own, traffic, goal=None, dtype=torch.float64, 
     `own` [E,4] / `traffic` [E,N,4] / `goal` are run with the deterministic SB3 actor evaluated inside
     the rollout kernel; results are those of each env's FIRST episode (the launch has VecEnv
     auto-reset semantics and keeps stepping the envs that finish early).  Thread-per-env shapes only
-    (N in {1,2,3,4,8} float32, {1,2,3} float64)."""
+    (N in {1,2,3,4,8} float32, {1,2,3,4} float64).  A NaN observation (the reference's d_cpa in exact parallel
+    flight) gives a NaN action, as policy.predict() does in evaluate_policy()."""
     from .vec_env import ACAS2DVecEnv
     own, traffic = np.asarray(own), np.asarray(traffic)
     E, N = own.shape[0], traffic.shape[1]

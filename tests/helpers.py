@@ -186,3 +186,31 @@ _F64 = [(1, None, 1, 1), (2, None, 2, 1), (3, None, 3, 1), (4, None, 4, 1), (8, 
         (3, "generic,1", None, 1), (5, None, None, 4), (17, None, None, 16), (100, None, None, 64)]
 SHAPES = _rows("float32", "fast", _F32) + _rows("float64", "exact", _F64) + _rows("float64", "fast", _F64)
 GENERIC_G = (1, 4, 16, 64)
+
+
+# ---- the fused collector ----------------------------------------------------------------------------------------------
+def bits_equal(x, y):
+    """torch.equal on the bit patterns (a NaN d_cpa -- exact parallel flight, kinematics.py:48 -- equals itself)."""
+    import torch
+    if x.is_floating_point():
+        bits = torch.int32 if x.dtype == torch.float32 else torch.int64
+        return x.shape == y.shape and torch.equal(x.contiguous().view(bits), y.contiguous().view(bits))
+    return torch.equal(x, y)
+
+
+def replay_collect_on_twin(env, twin, out):
+    """A twin of `env` (same construction, same state before collect()) stepped with the clipped actions of the
+    collect() dict `out` reproduces every observation, reward and mask bit for bit, some episodes end on the way, and
+    both envs end in the same state.  Returns the number of finished episodes."""
+    import torch
+    T = out["actions"].shape[0]
+    act = out["actions"].to(torch.float32)
+    dones = 0
+    for t in range(T):
+        o, r, d, _ = twin.step(act[t].clamp(-1, 1).to(twin.dtype))
+        assert bits_equal(o, out["obs"][t + 1]) and bits_equal(r, out["reward"][t]) and bits_equal(d, out["done"][t]), t
+        dones += int(d.sum())
+    assert dones > 0 and bits_equal(env.outputs["obs"], out["obs"][T])
+    for name in ("own_x", "trf_x", "steps", "episode", "total_reward"):
+        assert torch.equal(getattr(env, name), getattr(twin, name)), name
+    return dones

@@ -318,3 +318,109 @@ def test_spaces_and_sharding(g):
         assert bl[0][0] == 0 and sum(c for _, c in bl) == 1000
         assert all(bl[i][0] + bl[i][1] == bl[i + 1][0] for i in range(world - 1))
         assert max(c for _, c in bl) - min(c for _, c in bl) <= 1
+
+
+# ---- the learner's kernels: compiled sets, workspace layout, argument validation ------------------------------------
+def _ppo_widths():
+    src = open(os.path.join(ROOT, "gym-acas2d_amd", "csrc", "acas2d_ppo.hip")).read()
+    body = re.search(r"switch \(D\) \{(.*?)default:", src, re.S).group(1)
+    return [int(d) for d in re.findall(r"case (\d+): rc = launch_grad<\1>", body)]
+
+
+def test_learner_kernel_lists_are_exactly_the_compiled_set():
+    """learner_ref.UPDATE_WIDTHS (the widths tests/test_learner_kernels.py runs acas2d_ppo_update_f32 at) against the
+    obs_dim switch of acas2d_ppo.hip, and learner_ref.POLICY_KERNELS (the collector / rollout-policy instantiations it
+    runs) against the G = 1 packed shapes of each build -- float32 FAST, float64 EXACT and FAST.  An instantiation added
+    or removed on either side fails here."""
+    import learner_ref as R
+    widths = _ppo_widths()
+    assert len(widths) == len(set(widths)) and 8 in widths
+    assert tuple(sorted(widths)) == tuple(R.UPDATE_WIDTHS)
+    want = [("float32", True, c) for c, gl in sorted(_packed_shapes("f32")) if gl == 1]
+    want += [("float64", fast, c) for fast in (False, True) for c, gl in sorted(_packed_shapes("f64")) if gl == 1]
+    assert len(want) >= 13 and sorted(want) == sorted(R.POLICY_KERNELS) and len(set(R.POLICY_KERNELS)) == len(R.POLICY_KERNELS)
+
+
+def test_ppo_workspace_is_the_13_parameter_tensors(g):
+    """acas2d_ppo_workspace_floats(D) == the total numel of FusedUpdate's 13 parameter tensors of ActorCritic(D), in
+    learner_ref.PARAM_NAMES order (the flat layout the float64 references unflatten)."""
+    import torch
+
+    import learner_ref as R
+    L = g.native.lib()
+    for D in _ppo_widths():
+        pol = g.ActorCritic(D)
+        z = lambda *s: torch.zeros(*s)  # noqa: E731
+        fu = g.FusedUpdate(pol, g.PPOConfig(), z(4, D), z(4), z(4), z(4), z(4))      # host only: nothing is launched
+        assert len(fu._params) == 13 and all(p is pol.get_parameter(n) for p, n in zip(fu._params, R.PARAM_NAMES))
+        total = sum(p.numel() for p in fu._params)
+        assert L.acas2d_ppo_workspace_floats(D) == total == fu.grad.numel() == R.segments(pol)[-1][2], D
+
+
+def _ppo_struct(g, **over):
+    """An Acas2dPpoUpdate whose pointers are host addresses: every case built from it must be rejected before any
+    launch."""
+    buf = (C.c_char * 64)()
+    f = {n: C.addressof(buf) for n, t in g.native.CPpoUpdate._fields_ if t is C.c_void_p}
+    f.update(n_rows=64, obs_dim=8, clip_range=0.2, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, learning_rate=3e-4,
+             beta1=0.9, beta2=0.999, adam_eps=1e-5)
+    f.update(over)
+    return g.native.CPpoUpdate(**f), buf
+
+
+def test_ppo_update_validation_needs_no_gpu(g):
+    L = g.native.lib()
+    assert L.acas2d_ppo_update_f32(None, None) == -22 and b"NULL argument" in L.acas2d_last_error()
+    pointers = [n for n, t in g.native.CPpoUpdate._fields_ if t is C.c_void_p]
+    assert len(pointers) == 24
+    for name in pointers:
+        u, _keep = _ppo_struct(g, **{name: None})
+        assert L.acas2d_ppo_update_f32(C.byref(u), None) == -22, name
+        assert b"every pointer is required" in L.acas2d_last_error(), name
+    for n_rows in (1, 0, -5):
+        u, _keep = _ppo_struct(g, n_rows=n_rows)
+        assert L.acas2d_ppo_update_f32(C.byref(u), None) == -22
+        assert (b"n_rows = %d" % n_rows) in L.acas2d_last_error()
+    for D in (0, 5, 7, 9, 20, 30, -8, 53):
+        u, _keep = _ppo_struct(g, obs_dim=D)
+        assert L.acas2d_ppo_update_f32(C.byref(u), None) == -22
+        assert (b"obs_dim = %d" % D) in L.acas2d_last_error()
+
+
+def test_collect_and_rollout_policy_validation_needs_no_gpu(g):
+    """acas2d_collect_* / acas2d_rollout_policy_* reject, before any launch: a traffic count with no thread-per-env
+    shape (float32 N = 5, float64 N = 8), hidden != 64, and (collect) a missing value net, log_std or output."""
+    L = g.native.lib()
+    buf = (C.c_double * 4096)()
+    a = C.addressof(buf)
+    st = g.native.CState(*([a] * 14))
+    io = g.native.CStepIO(*([a] * 5 + [None] * 3))
+
+    def pol(hidden=64):
+        return g.native.CPolicy(*([a] * 6), hidden, 0)
+
+    def ac(hidden=64, **none):
+        f = {n: a for n, _ in g.native.CActorCritic._fields_[1:10]}
+        f.update(none)
+        return g.native.CActorCritic(pol(hidden), **f, noise_seed=7, noise_step=0)
+
+    for dt, N in (("f32", 5), ("f64", 8)):
+        cfg = g.ACAS2DConfig(n_traffic=N).to_c()
+        rp, cl = getattr(L, "acas2d_rollout_policy_" + dt), getattr(L, "acas2d_collect_" + dt)
+        assert rp(C.byref(cfg), C.byref(st), C.byref(io), C.byref(pol()), a, 4, 13, 0, 64, N, None) == -22
+        assert b"no thread-per-env shape" in L.acas2d_last_error()
+        assert cl(C.byref(cfg), C.byref(st), C.byref(io), C.byref(ac()), a, 4, 13, 0, 64, N, None) == -22
+        assert b"no thread-per-env shape" in L.acas2d_last_error()
+    for dt, N in (("f32", 8), ("f64", 4), ("f32", 1)):
+        cfg = g.ACAS2DConfig(n_traffic=N).to_c()
+        rp, cl = getattr(L, "acas2d_rollout_policy_" + dt), getattr(L, "acas2d_collect_" + dt)
+        for hidden in (32, 0, 65):
+            assert rp(C.byref(cfg), C.byref(st), C.byref(io), C.byref(pol(hidden)), a, 4, 13, 0, 64, N, None) == -22
+            assert (b"got hidden = %d" % hidden) in L.acas2d_last_error()
+            assert cl(C.byref(cfg), C.byref(st), C.byref(io), C.byref(ac(hidden)), a, 4, 13, 0, 64, N, None) == -22
+            assert (b"got hidden = %d" % hidden) in L.acas2d_last_error()
+        for name in ("v1t", "vb1", "v2t", "vb2", "v3", "vb3", "log_std", "values", "logp"):
+            assert cl(C.byref(cfg), C.byref(st), C.byref(io), C.byref(ac(**{name: None})), a, 4, 13, 0, 64, N, None) == -22, name
+            assert b"the value net, log_std, values and logp are required" in L.acas2d_last_error(), name
+        assert cl(C.byref(cfg), C.byref(st), C.byref(io), None, a, 4, 13, 0, 64, N, None) == -22
+        assert b"NULL actor-critic" in L.acas2d_last_error()

@@ -10,12 +10,7 @@ import torch
 import helpers as H
 
 
-def bits_equal(x, y):
-    """torch.equal on the bit patterns (a NaN d_cpa -- exact parallel flight, kinematics.py:48 -- equals itself)."""
-    if x.is_floating_point():
-        bits = torch.int32 if x.dtype == torch.float32 else torch.int64
-        return x.shape == y.shape and torch.equal(x.contiguous().view(bits), y.contiguous().view(bits))
-    return torch.equal(x, y)
+bits_equal = H.bits_equal
 
 
 def test_gae_matches_scalar_recursion():
@@ -127,6 +122,54 @@ def test_one_minibatch_update_against_a_float64_numpy_restatement():
     assert (sb3.n_steps, sb3.batch_size, sb3.n_epochs, sb3.max_grad_norm, sb3.learning_rate) == (2048, 64, 10, 0.5, 3e-4)
 
 
+@pytest.mark.parametrize("D", (8, 11, 14, 17, 29))
+def test_float64_reference_update_against_central_differences_at_every_width(D):
+    """tests/learner_ref.py's float64 references, at every width the fused update is compiled for (the GPU tests of
+    tests/test_learner_kernels.py hold the kernel to them): grad64 (ppo_loss() with float64 autograd) against central
+    differences of the NumPy restatement _np_loss, entry for entry; adam64 against clip_grad_norm_ + torch.optim.Adam
+    (float64) for three steps with the clip active."""
+    import gym_acas2d_amd as g
+    import learner_ref as R
+    assert D in R.UPDATE_WIDTHS
+    torch.manual_seed(D)
+    rng = np.random.default_rng(D)
+    B = 24
+    cfg = g.PPOConfig(ent_coef=0.01, max_grad_norm=0.5)
+    pol = g.ActorCritic(D).double()
+    with torch.no_grad():
+        pol.action_net.weight.mul_(30.0)
+        pol.log_std.fill_(-0.3)
+    obs = rng.uniform(-1, 1, (B, D)).astype(np.float32).astype(np.float64)
+    act, adv, ret = rng.normal(0, 0.7, B), rng.normal(0, 2, B), rng.normal(0, 1, B)
+    theta = R.flat_params(pol)
+    old_logp = R.logp64(g.ActorCritic, D, theta, obs, act) + rng.normal(0, 0.4, B)
+    grad, pg, vf, ratio = R.grad64(g.ActorCritic, cfg, D, theta, obs, act, old_logp, adv, ret)
+    assert ((ratio < 0.8) | (ratio > 1.2)).sum() >= 3 and ((ratio > 0.8) & (ratio < 1.2)).sum() >= 3
+    names = [(n, tuple(pol.get_parameter(n).shape)) for n in R.PARAM_NAMES]
+    args = (cfg, obs, act[:, None], old_logp, adv, ret)
+    fd, h = np.zeros_like(theta), 1e-6
+    for i in range(theta.size):
+        tp, tm = theta.copy(), theta.copy()
+        tp[i] += h
+        tm[i] -= h
+        fd[i] = (_np_loss(tp, names, *args) - _np_loss(tm, names, *args)) / (2 * h)
+    assert np.abs(grad - fd).max() < 1e-7 * max(1.0, np.abs(fd).max()), np.abs(grad - fd).max()
+    opt = torch.optim.Adam(pol.parameters(), lr=cfg.learning_rate, eps=1e-5)
+    m, v = np.zeros_like(theta), np.zeros_like(theta)
+    for step in range(3):
+        th = R.flat_params(pol)
+        gr, _, _, _ = R.grad64(g.ActorCritic, cfg, D, th, obs, act, old_logp, adv, ret)
+        want, m, v, norm = R.adam64(th, gr, m, v, step, cfg.max_grad_norm, cfg.learning_rate, 0.9, 0.999, 1e-5)
+        assert norm > cfg.max_grad_norm
+        opt.zero_grad()
+        loss, _, _ = g.ppo_loss(pol, cfg, torch.as_tensor(obs), torch.as_tensor(act[:, None]), torch.as_tensor(old_logp),
+                                torch.as_tensor(adv), torch.as_tensor(ret))
+        loss.backward()
+        torch.nn.utils.clip_grad_norm_(pol.parameters(), cfg.max_grad_norm)
+        opt.step()
+        assert np.abs(R.flat_params(pol) - want).max() < 1e-12, (step, np.abs(R.flat_params(pol) - want).max())
+
+
 def _eval_on_reference_episodes(g, policy):
     own, trf, goal = H.parity_reset_states(g.ACAS2DConfig(), 13, 0, 100)
     ev = g.ACAS2DVecEnv(100, 1, device="cuda:0", dtype=torch.float64, auto_reset=False)
@@ -235,14 +278,7 @@ def test_fused_collector_against_torch_and_a_twin_env(g_mod, dtype_name, N, E, T
     assert abs(e.mean()) < 5 / np.sqrt(n) and abs(e.var() - 1) < 8 / np.sqrt(n) and abs((e ** 4).mean() - 3) < 0.15
     assert abs(np.corrcoef(e[:-1].ravel(), e[1:].ravel())[0, 1]) < 5 / np.sqrt(n)          # step to step
     assert abs(np.corrcoef(e[:, :-1].ravel(), e[:, 1:].ravel())[0, 1]) < 5 / np.sqrt(n)    # env to env
-    dones = 0
-    for t in range(T):
-        o, r, d, _ = twin.step(act[t].clamp(-1, 1).to(dtype))
-        assert bits_equal(o, out["obs"][t + 1]) and bits_equal(r, out["reward"][t]) and bits_equal(d, out["done"][t]), t
-        dones += int(d.sum())
-    assert dones > 0 and bits_equal(env.outputs["obs"], out["obs"][T])
-    for name in ("own_x", "trf_x", "steps", "episode", "total_reward"):
-        assert torch.equal(getattr(env, name), getattr(twin, name)), name
+    H.replay_collect_on_twin(env, twin, out)
     # (d)
     again = mk(E); again.reset()
     o2 = again.collect(pol, T, noise_seed=7, noise_step=1000)
