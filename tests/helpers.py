@@ -214,3 +214,111 @@ def replay_collect_on_twin(env, twin, out):
     for name in ("own_x", "trf_x", "steps", "episode", "total_reward"):
         assert torch.equal(getattr(env, name), getattr(twin, name)), name
     return dones
+
+
+# ---- non-default configurations ---------------------------------------------------------------------------------------
+# ACAS2DConfig keyword sets in which every tunable differs from settings.py (tests/test_host.py checks that, field by
+# field of to_c()).  "wide": a larger, slower-framed airspace with an airspeed-factor range and short episodes -- no goal
+# is reachable within its 120 steps; "small": a small airspace in which goals, collisions and timeouts all occur within
+# a few dozen steps after step 80, so the goal bonus and the step-reward decay are covered too.
+NONDEFAULT_CONFIGS = {
+    "wide": dict(max_steps=120, width=2000, height=1200, fps=50, aircraft_size=20, airspeed=180, airspeed_factor_min=0.8,
+                 airspeed_factor_max=1.3, acc_lat_limit=150.0, player_initial_heading_lim=10,
+                 traffic_initial_heading_lim=25, reward_goal=500, reward_collision=-750),
+    "small": dict(max_steps=82, width=700, height=500, fps=40, aircraft_size=16, airspeed=240, airspeed_factor_min=0.7,
+                  airspeed_factor_max=1.2, acc_lat_limit=120, player_initial_heading_lim=5,
+                  traffic_initial_heading_lim=20, reward_goal=400, reward_collision=-600),
+}
+
+
+def oracle_config(O, cfg):
+    """OracleConfig carrying the product configuration `cfg` (same field names)."""
+    cc, oc = cfg.to_c(), O.OracleConfig()
+    for name, _ in O.OracleConfig._fields_:
+        if name != "_pad":                      # (the product's `math` selector: the oracle has one formulation)
+            setattr(oc, name, getattr(cc, name))
+    return oc
+
+
+def f32_oracle_steps(O, E, N, T, seed=13, env_offset=0, warmup=None, config=None):
+    """The oracle side of a float32-vs-oracle window: a free-running float64 oracle trajectory `ref` with auto-reset and
+    actions from default_rng(7), `warmup` steps first (None: 3 at N = 64, where episodes last ~8 steps, else 15..29 drawn
+    from the same stream), then T steps.  For each of those it yields (t, own, trf, steps, episode, act, chk, stepped):
+    ref's state rounded to float32 (the state both sides start the step from), the float32-representable action, and the
+    oracle `chk` stepped once from that state -- stepped = chk.step()'s (o, r, d, oc).  `config`: an OracleConfig, None
+    for the default one."""
+    f32 = lambda a: a.astype(np.float32).astype(np.float64)  # noqa: E731
+    ref = O.OracleEnvs(E, N, seed=seed, env_offset=env_offset, auto_reset=True, config=config)
+    ref.reset()
+    rng = np.random.default_rng(7)
+    if warmup is None:
+        warmup = 3 if N == 64 else int(rng.integers(15, 30))
+    for _ in range(warmup):
+        ref.step(rng.uniform(-1, 1, E))
+    chk = O.OracleEnvs(E, N, seed=seed, env_offset=env_offset, auto_reset=True, config=config)
+    for t in range(T):
+        own = f32(np.stack([ref.own_x, ref.own_y, ref.own_psi, ref.own_v], 1))
+        trf = f32(np.stack([ref.trf_x, ref.trf_y, ref.trf_psi, ref.trf_v], -1))
+        steps, act = ref.steps.copy(), f32(rng.uniform(-1, 1, E))
+        chk.set_state(own, trf, None, steps)
+        chk.episode[:] = ref.episode
+        o, r, d, oc, _ = chk.step(act)
+        yield t, own, trf, steps, ref.episode.copy(), act, chk, (o, r, d, oc)
+        ref.step(act)
+
+
+# The float32 bounds of tests/test_gpu_parity.py (_check_f32_step_vs_oracle), derived from the configuration -- `cfgc`,
+# an OracleConfig -- by the rules its docstring states.  For the default configuration each evaluates to the fixed number
+# the tests used before it was derived (tests/test_host.py holds them to those numbers).
+def ulp32(x):
+    return float(np.spacing(np.float32(abs(x))))
+
+
+def f32_pos_bound(m):
+    """Positions after one step, |coordinates| up to m: 1 float32 ulp -- 1.3e-4 below 2048 px (ulp 1.22e-4)."""
+    return max(1.3e-4, ulp32(m))
+
+
+def f32_bounds(cfgc, dflt):
+    """dflt: the default OracleConfig (the reward bound scales with the configuration's d_cpa amplification over the
+    default's).  speed None: the speed factor is a single value, the fresh speeds must be bit-equal."""
+    extent = max(cfgc.t0_x, cfgc.tn_x_max, cfgc.t0_y_base + cfgc.t0_y_span, cfgc.tn_y_max)
+    amp = (cfgc.d_cpa_max / cfgc.safe_distance) / (dflt.d_cpa_max / dflt.safe_distance)
+    density = (cfgc.collision_dist / (cfgc.tn_x_max * cfgc.tn_y_max)) / (dflt.collision_dist / (dflt.tn_x_max * dflt.tn_y_max))
+    fmin, fmax = cfgc.speed_factor_min, cfgc.speed_factor_max
+    return dict(
+        # the fraction of envs a step may leave inside the 1e-3 px band around the thresholds: the chance that an aircraft
+        # lies in the band grows with the collision distance over the area the traffic is drawn in
+        band=1e-3 * max(1.0, density),
+        # terminal reward / episode return (total_reward starts each checked step at 0): 1 ulp of the bonus, + 1e-5 for
+        # the shaped part
+        ret=max(1.3e-4, ulp32(max(abs(cfgc.reward_goal), abs(cfgc.reward_collision)))) + 1e-5,
+        # the non-terminal reward: (d_cpa / safe_distance)^4 amplifies the d_cpa entry's error (a fraction of d_cpa_max)
+        # by up to 4 d_cpa_max / safe_distance -- 39x by default, where 5e-5 holds
+        rew=5e-5 * max(1.0, amp),
+        # fresh episode (float32 draws from 24 random bits): 2 ulp of the largest drawn coordinate, headings 2 ulp of 360
+        reset_pos=max(2.5e-4, 2 * ulp32(extent)),
+        reset_psi=6e-5,
+        # fresh speeds: 24 random bits against 32 move the factor by < 2^-24 of the range, plus the float32 rounding
+        speed=None if fmin == fmax else (fmax - fmin) * cfgc.airspeed * 2.0 ** -24 + 2 * ulp32(fmax * cfgc.airspeed))
+
+
+# Where the non-default windows of tests/test_gpu_parity.py run (seed, env_offset, oracle warm-up steps, checked steps)
+# and which outcomes the CPU oracle produces there -- the outcomes each test asserts it compared.  tests/test_host.py
+# runs the oracle over every window and holds these sets to what really occurs.
+GOAL, COLLISION, TIMEOUT = 1, 2, 3
+NONDEFAULT_SHAPE_WINDOW = dict(wide=dict(seed=3, env_offset=37, warmup=100, T=30),
+                               small=dict(seed=3, env_offset=37, warmup=75, T=40))
+# (N, E, T) of the odd-traffic-count tests of tests/test_gpu_parity.py.  The float32 one runs "wide" in a window that starts
+# at step 100, so the episodes that last reach their timeout at step 121 inside it
+ODD_TRAFFIC = ((2, 1500, 80), (5, 777, 90), (6, 1024, 60), (7, 333, 60), (12, 640, 50), (33, 200, 30))
+NONDEFAULT_ODD_WINDOW = dict(seed=3, env_offset=17, warmup=100)
+
+
+def nondefault_outcomes(name, N):
+    """The outcomes the CPU oracle produces at least 5 times in the shape window NONDEFAULT_SHAPE_WINDOW[name] at N
+    traffic (measured; tests/test_host.py re-measures them): crowded airspaces end every episode in a collision before
+    its goal or timeout, and "wide" with one aircraft collides nowhere."""
+    if name == "wide":
+        return {TIMEOUT} if N == 1 else {COLLISION, TIMEOUT}
+    return {GOAL, COLLISION, TIMEOUT} if N <= 16 else {GOAL, COLLISION} if N <= 33 else {COLLISION}

@@ -10,6 +10,11 @@ Tolerances (north star: masks bit-exact, 1e-5 abs on float positions / rewards):
       identical (float32-representable) states are held to: observations 1e-5 abs (2e-5 for the
       signed d_cpa entry), non-terminal rewards 1e-5 abs, positions / terminal rewards 1 float32
       ulp (1.3e-4); masks exact outside a 1e-3 band around the thresholds.
+  float32 under a non-default configuration (helpers.NONDEFAULT_CONFIGS: "wide", "small") -- the same criteria with the
+      bounds derived from the configuration (helpers.f32_bounds): positions 1 ulp of the largest coordinate (2.44e-4
+      beyond 2048 px: worst 1.22e-4), fresh speeds (max - min) airspeed 2^-24 + 2 ulp (worst 2.2e-5 of 3.6e-5 under
+      "wide", 3.4e-5 of 6.8e-5 under "small"), and the d_cpa entry 2e-5 plus, where speeds differ, the reference's own
+      conditioning d (max airspeed 2^-20) / (|v12| d_cpa_max) (worst 2.8e-5, 0.35 of its bound).
 """
 import os
 import types
@@ -429,14 +434,10 @@ def test_f64_auto_reset_vs_oracle(g, O, N, E, T, math):
 
 def _oracle_config_from(O, cfg):
     """OracleConfig carrying a NON-default product configuration (same field names)."""
-    cc, oc = cfg.to_c(), O.OracleConfig()
-    for name, _ in O.OracleConfig._fields_:
-        if name != "_pad":                      # (the product's `math` selector: the oracle has one formulation)
-            setattr(oc, name, getattr(cc, name))
-    return oc
+    return H.oracle_config(O, cfg)
 
 
-_ODD_TRAFFIC = ((2, 1500, 80), (5, 777, 90), (6, 1024, 60), (7, 333, 60), (12, 640, 50), (33, 200, 30))
+_ODD_TRAFFIC = H.ODD_TRAFFIC
 
 
 @pytest.mark.parametrize("N,E,T", _ODD_TRAFFIC)
@@ -456,10 +457,7 @@ def test_f64_fast_odd_traffic_counts_and_nondefault_config_vs_oracle(g, O, N, E,
 
 
 def _odd_traffic_and_nondefault_config_vs_oracle(g, O, N, E, T, math):
-    cfg = g.ACAS2DConfig(n_traffic=N, max_steps=120, width=2000, height=1200, fps=50, aircraft_size=20,
-                         airspeed=180, airspeed_factor_min=0.8, airspeed_factor_max=1.3,
-                         acc_lat_limit=150.0, player_initial_heading_lim=10, traffic_initial_heading_lim=25,
-                         reward_goal=500, reward_collision=-750, fast_math=(math == "fast"))
+    cfg = g.ACAS2DConfig(n_traffic=N, fast_math=(math == "fast"), **H.NONDEFAULT_CONFIGS["wide"])
     ref = O.OracleEnvs(E, N, seed=3, env_offset=17, auto_reset=True, config=_oracle_config_from(O, cfg))
     env = GpuEngine.__new__(GpuEngine)
     env.v = g.ACAS2DVecEnv(E, device="cuda:0", dtype=torch.float64, seed=3, env_offset=17, config=cfg)
@@ -1012,8 +1010,15 @@ def test_full_size_f64_vs_oracle(g, O, E, N, T):
     assert np.array_equal(env.steps, ref.steps) and np.array_equal(env.episode, ref.episode)
 
 
+def _default_oracle_config():
+    from oracle import oracle
+    return oracle.default_config()
+
+
 def _new_f32_totals():
-    return dict(steps=0, mask_mismatch=0, in_band=0, finished=0, e_obs=0.0, e_cpa=0.0, e_rew=0.0, e_term=0.0, e_fresh_obs=0.0)
+    return dict(steps=0, mask_mismatch=0, in_band=0, finished=0, e_obs=0.0, e_cpa=0.0, e_rew=0.0, e_term=0.0, e_fresh_obs=0.0,
+                outcomes=set(), cpa_ratio=0.0, e_pos=0.0, pos_bound=0.0, e_ret=0.0, e_reset_pos=0.0, e_reset_psi=0.0, e_speed=0.0,
+                bounds=None)
 
 
 def _check_f32_step_vs_oracle(env, chk, stepped, got, N, tot, t=0):
@@ -1021,13 +1026,26 @@ def _check_f32_step_vs_oracle(env, chk, stepped, got, N, tot, t=0):
     stepped = chk.step()'s (o, r, d, oc), got = the engine's (obs, rew, done, outcome).  done / outcome masks equal
     outside a 1e-3 px band around the thresholds; observations, rewards and positions of the envs that go on within the
     tolerances of test_f32_statistical_single_step_vs_f64_oracle; for the envs that finish: the terminal observation,
-    the episode return and length, and the freshly drawn episode (the float32 build draws in float32: positions 2.5e-4,
-    headings 6e-5 from the float64 draw) with its first observation.  Accumulates the counts / worst errors in `tot`;
-    returns the envs that went on and those that finished, both outside the band."""
+    the episode return and length, and the freshly drawn episode with its first observation.  Accumulates the counts,
+    the worst errors and the outcomes compared in `tot`; returns the envs that went on and those that finished, both
+    outside the band.
+
+    The bounds that depend on the configuration are derived from chk.cfg (the oracle's copy of it) by helpers.f32_bounds
+    and f32_pos_bound; for the default configuration they are the fixed numbers below in brackets.  Positions: 1 float32
+    ulp of the largest |coordinate| M of the compared envs, at least 1.3e-4 (M < 2048 px; [1.3e-4]).  Episode return:
+    1 ulp of the larger terminal bonus, at least 1.3e-4, + 1e-5 [1.4e-4].  Non-terminal reward: 5e-5 times the d_cpa
+    amplification 4 d_cpa_max / safe_distance over the default's, at least 1 [5e-5].  The fresh episode (the float32
+    build draws in float32 from 24 random bits): positions 2 ulp of the largest drawn coordinate, at least 2.5e-4
+    [2.5e-4], headings 6e-5 (2 ulp of 360); speeds bit-equal when the speed factor is a single value [always], else
+    within (max - min) airspeed 2^-24 + 2 ulp of max airspeed.  The d_cpa entry: 2e-5 [2e-5], plus under a speed range
+    d (max airspeed 2^-20) / (|v12| d_cpa_max) per entry (see below).  At most a fraction 1e-3 [1e-3] of the envs in the
+    band, times the collision distance over the traffic's draw area relative to the default's."""
     o, r, d, oc = stepped
     obs, rew, done, outcome = got
     E = len(d)
     cfgc = chk.cfg
+    bnd = H.f32_bounds(cfgc, _default_oracle_config())
+    tot["bounds"] = bnd
     col = np.arange(5 + 3 * N)
     cpa, vcl = (col >= 5) & ((col - 5) % 3 == 1), (col >= 5) & ((col - 5) % 3 == 2)
     d = d.astype(bool)
@@ -1036,10 +1054,11 @@ def _check_f32_step_vs_oracle(env, chk, stepped, got, N, tot, t=0):
     mism = (done.astype(bool) != d) | (outcome != oc)
     tot["mask_mismatch"] += int((mism & ok).sum()); tot["in_band"] += int((~ok).sum()); tot["steps"] += E
     assert not (mism & ok).any(), (t, int((mism & ok).sum()))
-    assert ok.mean() > 0.999
+    assert ok.mean() > 1 - bnd["band"], (t, ok.mean(), bnd["band"])
     same = ok & ~mism
     go, fin = same & ~d, same & d
     tot["finished"] += int(fin.sum())
+    tot["outcomes"] |= set(int(k) for k in np.unique(oc[fin]))
     # ---- envs that go on: the step itself
     v12x = (chk.own_v * np.cos(np.deg2rad(chk.own_psi)))[:, None] - chk.trf_v * np.cos(np.deg2rad(chk.trf_psi))
     v12y = (chk.own_v * np.sin(np.deg2rad(chk.own_psi)))[:, None] - chk.trf_v * np.sin(np.deg2rad(chk.trf_psi))
@@ -1047,21 +1066,36 @@ def _check_f32_step_vs_oracle(env, chk, stepped, got, N, tot, t=0):
     near = (o[:, 5::3] * cfgc.d_sep_max) < 16.0
     err = np.abs(obs - o)
     err[:, [1, 4]] = np.minimum(err[:, [1, 4]], 1.0 - err[:, [1, 4]])
+    # d_cpa: 2e-5, plus -- when speeds differ -- the reference's own conditioning d |dv12| / |v12| (kinematics.py:40-49):
+    # the float32 velocity components carry a relative error of order 2^-21 (a heading rounded to float32 near 360
+    # degrees, the hardware sin / cos) that equal speeds cancel in v12 and unequal ones do not (measured: 5.5e-7 v)
+    cpa_tol = 2e-5
+    if bnd["speed"] is not None:
+        dv12 = cfgc.speed_factor_max * cfgc.airspeed * 2.0 ** -20
+        cpa_tol = 2e-5 + (o[:, 5::3] * cfgc.d_sep_max) * dv12 / (np.hypot(v12x, v12y) * cfgc.d_cpa_max)
     if go.any():
         e_plain = err[:, ~(cpa | vcl)][go]
         e_vc, e_cpa = err[:, vcl][go][~near[go]], err[:, cpa][go][well[go]]
+        cpa_excess = (err[:, cpa] - cpa_tol)[go][well[go]]
         tot["e_obs"] = max(tot["e_obs"], float(e_plain.max()), float(e_vc.max(initial=0.0)))
         tot["e_cpa"] = max(tot["e_cpa"], float(e_cpa.max(initial=0.0)))
-        assert e_plain.max() < 1e-5 and e_vc.max(initial=0.0) < 1e-5 and e_cpa.max(initial=0.0) < 2e-5, \
+        tot["cpa_ratio"] = max(tot["cpa_ratio"], float((err[:, cpa] / cpa_tol)[go][well[go]].max(initial=0.0)))
+        assert e_plain.max() < 1e-5 and e_vc.max(initial=0.0) < 1e-5 and cpa_excess.max(initial=-1.0) < 0, \
             (t, e_plain.max(), e_vc.max(initial=0.0), e_cpa.max(initial=0.0))
         nt = go & well[:, 0] & ~near[:, 0]
         e_rew = np.abs(rew[nt] - r[nt])
         tot["e_rew"] = max(tot["e_rew"], float(e_rew.max(initial=0.0)))
         # (1e-5 for 99.99 % of the env-steps, the worst below 5e-5: the reward amplifies the d_cpa error up to 39 x --
         #  see test_f32_statistical_single_step_vs_f64_oracle; a percentile needs the samples to carry it)
-        assert e_rew.max(initial=0.0) < 5e-5 and (e_rew.size < 50000 or np.quantile(e_rew, 0.9999) < 1e-5), (t, e_rew.max())
-        assert max(np.abs(env.own_x - chk.own_x)[go].max(), np.abs(env.trf_x - chk.trf_x)[go].max(),
-                   np.abs(env.trf_y - chk.trf_y)[go].max()) <= 1.3e-4
+        assert e_rew.max(initial=0.0) < bnd["rew"] and (e_rew.size < 50000 or np.quantile(e_rew, 0.9999) < 1e-5), \
+            (t, e_rew.max(), bnd["rew"])
+        m = max(np.abs(chk.own_x)[go].max(), np.abs(chk.own_y)[go].max(), np.abs(chk.trf_x)[go].max(),
+                np.abs(chk.trf_y)[go].max())
+        pos_bound = H.f32_pos_bound(m)
+        e_pos = max(np.abs(env.own_x - chk.own_x)[go].max(), np.abs(env.trf_x - chk.trf_x)[go].max(),
+                    np.abs(env.trf_y - chk.trf_y)[go].max())
+        tot["e_pos"], tot["pos_bound"] = max(tot["e_pos"], float(e_pos)), max(tot["pos_bound"], pos_bound)
+        assert e_pos <= pos_bound, (t, e_pos, pos_bound)
         assert np.array_equal(env.steps[go], chk.steps[go])
     # ---- envs that finish: side channels of the finished episode, then the fresh one
     if fin.any():
@@ -1071,11 +1105,22 @@ def _check_f32_step_vs_oracle(env, chk, stepped, got, N, tot, t=0):
         tot["e_term"] = max(tot["e_term"], float(tw.max()))
         assert tw.max() < 1e-5
         assert np.array_equal(env.ep_steps[fin], chk.ep_steps[fin]) and np.array_equal(env.episode[fin], chk.episode[fin])
-        assert np.abs(env.ep_return - chk.ep_return)[fin].max() <= 1.3e-4 + 1e-5          # one float32 ulp of the +-1000 bonus
-        assert max(np.abs(env.trf_x - chk.trf_x)[fin].max(), np.abs(env.trf_y - chk.trf_y)[fin].max()) < 2.5e-4
+        e_ret = np.abs(env.ep_return - chk.ep_return)[fin].max()
+        tot["e_ret"] = max(tot["e_ret"], float(e_ret))
+        assert e_ret <= bnd["ret"], (t, e_ret, bnd["ret"])             # one float32 ulp of the terminal bonus
+        e_rp = max(np.abs(env.trf_x - chk.trf_x)[fin].max(), np.abs(env.trf_y - chk.trf_y)[fin].max())
+        tot["e_reset_pos"] = max(tot["e_reset_pos"], float(e_rp))
+        assert e_rp < bnd["reset_pos"], (t, e_rp, bnd["reset_pos"])
         for name in ("trf_psi", "own_psi"):
             dpsi = np.abs(getattr(env, name) - getattr(chk, name))[fin]
-            assert np.minimum(dpsi, 360 - dpsi).max() < 6e-5, name
+            tot["e_reset_psi"] = max(tot["e_reset_psi"], float(np.minimum(dpsi, 360 - dpsi).max()))
+            assert np.minimum(dpsi, 360 - dpsi).max() < bnd["reset_psi"], name
+        if bnd["speed"] is None:
+            assert np.array_equal(env.trf_v[fin], chk.trf_v[fin])
+        else:
+            e_v = np.abs(env.trf_v - chk.trf_v)[fin].max()
+            tot["e_speed"] = max(tot["e_speed"], float(e_v))
+            assert e_v <= bnd["speed"], (t, e_v, bnd["speed"])
         assert np.array_equal(env.steps[fin], chk.steps[fin]) and (env.steps[fin] == 1).all()
         fe = np.abs(obs - o)
         fe[:, [1, 4]] = np.minimum(fe[:, [1, 4]], 1.0 - fe[:, [1, 4]])
@@ -1086,37 +1131,35 @@ def _check_f32_step_vs_oracle(env, chk, stepped, got, N, tot, t=0):
 
 
 def _print_f32_totals(what, tot):
-    print("f32 vs f64 oracle %s: %d env-steps, %d finished; mask mismatches outside the 1e-3 band %d (%d env-steps inside "
-          "it); max |obs| %.2e, d_cpa %.2e, reward %.2e, terminal obs %.2e, first obs of a fresh episode %.2e"
-          % (what, tot["steps"], tot["finished"], tot["mask_mismatch"], tot["in_band"], tot["e_obs"], tot["e_cpa"],
-             tot["e_rew"], tot["e_term"], tot["e_fresh_obs"]))
+    b = tot["bounds"]
+    print("f32 vs f64 oracle %s: %d env-steps, %d finished (outcomes compared %s); mask mismatches outside the 1e-3 band %d "
+          "(%d env-steps inside it); max |obs| %.2e, d_cpa %.2e (%.2f of its bound), reward %.2e (bound %.2e), terminal obs %.2e, first obs of "
+          "a fresh episode %.2e; positions %.2e (bound %.2e), return %.2e (bound %.2e), fresh positions %.2e (bound %.2e), "
+          "fresh headings %.2e (bound %.0e), fresh speeds %s"
+          % (what, tot["steps"], tot["finished"], sorted(tot["outcomes"]), tot["mask_mismatch"], tot["in_band"], tot["e_obs"],
+             tot["e_cpa"], tot["cpa_ratio"], tot["e_rew"], b["rew"], tot["e_term"], tot["e_fresh_obs"], tot["e_pos"], tot["pos_bound"],
+             tot["e_ret"], b["ret"], tot["e_reset_pos"], b["reset_pos"], tot["e_reset_psi"], b["reset_psi"],
+             "bit-equal" if b["speed"] is None else "%.2e (bound %.2e)" % (tot["e_speed"], b["speed"])))
 
 
-def _f32_steps_vs_oracle(g, O, E, N, T, seed=13, env_offset=0):
+def _f32_steps_vs_oracle(g, O, E, N, T, seed=13, env_offset=0, config=None, warmup=None):
     """T float32 steps WITH auto-reset, each from the oracle trajectory's state rounded to float32 (so that both sides
     start every step from the identical state and the comparison is the step's, not the accumulated drift's), checked
-    by _check_f32_step_vs_oracle.  Returns the totals."""
-    f32 = lambda a: a.astype(np.float32).astype(np.float64)  # noqa: E731
-    ref = O.OracleEnvs(E, N, seed=seed, env_offset=env_offset, auto_reset=True)
-    ref.reset()
-    rng = np.random.default_rng(7)
-    for _ in range(3 if N == 64 else int(rng.integers(15, 30))):        # mid-episode states (N = 64: episodes last ~8 steps)
-        ref.step(rng.uniform(-1, 1, E))
-    chk = O.OracleEnvs(E, N, seed=seed, env_offset=env_offset, auto_reset=True)
-    env = GpuEngine(g, E, N, dtype=torch.float32, auto_reset=True, seed=seed, env_offset=env_offset)
+    by _check_f32_step_vs_oracle.  config: ACAS2DConfig keywords other than n_traffic (None: the default configuration);
+    warmup: oracle steps before the first checked one (helpers.f32_oracle_steps).  Returns the totals."""
+    cfg = g.ACAS2DConfig(n_traffic=N, **(config or {}))
+    ocfg = None if config is None else _oracle_config_from(O, cfg)
+    env = _engine(g.ACAS2DVecEnv(E, device="cuda:0", dtype=torch.float32, auto_reset=True, seed=seed,
+                                 env_offset=env_offset, config=cfg))
     tot = _new_f32_totals()
-    for t in range(T):
-        own = f32(np.stack([ref.own_x, ref.own_y, ref.own_psi, ref.own_v], 1))
-        trf = f32(np.stack([ref.trf_x, ref.trf_y, ref.trf_psi, ref.trf_v], -1))
-        steps, act = ref.steps.copy(), f32(rng.uniform(-1, 1, E))
-        chk.set_state(own, trf, None, steps)
-        chk.episode[:] = ref.episode
+    for t, own, trf, steps, episode, act, chk, stepped in H.f32_oracle_steps(O, E, N, T, seed, env_offset, warmup, ocfg):
         env.set_state(own, trf, None, steps)
-        env.v.episode.copy_(torch.as_tensor(ref.episode.view(np.int32), device="cuda:0"))
-        o, r, d, oc, _ = chk.step(act)
+        env.v.episode.copy_(torch.as_tensor(episode.view(np.int32), device="cuda:0"))
         obs, rew, done, outcome, _ = env.step(act)
-        _check_f32_step_vs_oracle(env, chk, (o, r, d, oc), (obs, rew, done, outcome), N, tot, t)
-        ref.step(act)
+        _check_f32_step_vs_oracle(env, chk, stepped, (obs, rew, done, outcome), N, tot, t)
+    tot["speeds"] = len(np.unique(env.trf_v))
+    if config is None:       # the default configuration's windows stay below 2048 px: the fixed 1.3e-4
+        assert tot["pos_bound"] == 1.3e-4, tot["pos_bound"]
     return tot
 
 
@@ -1328,10 +1371,14 @@ def test_every_f32_shape_vs_f64_oracle(g, O, monkeypatch, shape):
 def test_every_packed_shape_rollout_equals_steps(g, monkeypatch, shape):
     """acas2d_rollout_* == the same number of acas2d_step_* calls, bit for bit, on every packed work shape (the fused
     rollout has no generic walk): outputs, side channels where done, the final state."""
+    _rollout_equals_steps(g, monkeypatch, shape, _SHORT)
+
+
+def _rollout_equals_steps(g, monkeypatch, shape, config):
     _use_shape(g, monkeypatch, shape)
     E, T = 1001, 90
-    a = _shape_env(g, shape, E, config=_SHORT)
-    b = _shape_env(g, shape, E, config=_SHORT, double_buffer=False)
+    a = _shape_env(g, shape, E, config=config)
+    b = _shape_env(g, shape, E, config=config, double_buffer=False)
     assert bits_equal(a.reset(), b.reset())
     gen = torch.Generator(device="cuda:0").manual_seed(3)
     actions = torch.rand(T, E, generator=gen, device="cuda:0", dtype=a.dtype) * 2 - 1
@@ -1380,10 +1427,14 @@ _F32_PACKED = [s for s in _PACKED if s.dtype == "float32"]
 def test_every_f32_packed_shape_arena_equals_general(g, monkeypatch, shape):
     """The consecutive-layout ("arena") step kernel == the general kernel (ACAS2D_NO_ARENA, read per launch), bit for
     bit, on every float32 packed shape; E = 32 waves, a whole multiple of eight workgroups (the arena kernel's size)."""
+    _arena_equals_general(g, monkeypatch, shape, _SHORT)
+
+
+def _arena_equals_general(g, monkeypatch, shape, config):
     E, T = 32 * shape.envs_per_wave, 90
     _use_shape(g, monkeypatch, shape, E)
-    a = _shape_env(g, shape, E, config=_SHORT)
-    b = _shape_env(g, shape, E, config=_SHORT)
+    a = _shape_env(g, shape, E, config=config)
+    b = _shape_env(g, shape, E, config=config)
     assert a.consecutive_layout
     assert bits_equal(a.reset(), b.reset())
     gen = torch.Generator(device="cuda:0").manual_seed(5)
@@ -1433,6 +1484,106 @@ def test_every_f64_shape_reset_masked_vs_oracle(g, O, monkeypatch, shape):
         np.testing.assert_allclose(obs[mask], o_ref[mask], rtol=0, atol=1e-9)
         assert np.array_equal(env.steps[mask], ref.steps[mask])
         ref.steps[~mask] = before["steps"][~mask]
+
+
+# ---- the float32 build under non-default configurations (helpers.NONDEFAULT_CONFIGS) ---------------------------------
+# Under the default configuration every aircraft flies at exactly `airspeed`: the float32 speed draw, the kinematics.py:74
+# quirk of the paired float2 path (v2y from the PLAYER's speed), the float32 rounding of the configuration and its
+# reciprocals, and timeouts / the step-reward decay at another max_steps are seen by the tests above only at their
+# default values.
+_F32_SHAPES = [s for s in H.SHAPES if s.dtype == "float32"]
+
+
+@pytest.mark.parametrize("name", tuple(H.NONDEFAULT_CONFIGS))
+@pytest.mark.parametrize("shape", _F32_SHAPES, ids=_ids(_F32_SHAPES))
+def test_every_f32_shape_nondefault_config_vs_f64_oracle(g, O, monkeypatch, shape, name):
+    """Every float32 work shape under each non-default configuration against the float64 oracle, step by step from the
+    oracle's state rounded to float32 (_f32_steps_vs_oracle; bounds derived from the configuration); E = 1001, env_offset
+    37, the window of helpers.NONDEFAULT_SHAPE_WINDOW: it covers timeouts, and under "small" goals -- every outcome the
+    oracle produces there (helpers.nondefault_outcomes) must have been compared."""
+    _use_shape(g, monkeypatch, shape)
+    w = H.NONDEFAULT_SHAPE_WINDOW[name]
+    tot = _f32_steps_vs_oracle(g, O, 1001, shape.n_traffic, w["T"], seed=w["seed"], env_offset=w["env_offset"],
+                               config=H.NONDEFAULT_CONFIGS[name], warmup=w["warmup"])
+    _print_f32_totals('"%s" on %s, 1001 envs x %d steps after %d' % (name, shape.id, w["T"], w["warmup"]), tot)
+    assert tot["speeds"] > 10                                          # speeds really vary
+    assert tot["outcomes"] >= H.nondefault_outcomes(name, shape.n_traffic), tot["outcomes"]
+
+
+@pytest.mark.parametrize("N,E,T", _ODD_TRAFFIC)
+def test_f32_odd_traffic_counts_and_nondefault_config_vs_f64_oracle(g, O, N, E, T):
+    """The float32 twin of test_f64_odd_traffic_counts_and_nondefault_config_vs_oracle: the same traffic counts, env
+    counts and "wide" configuration, stepped from the oracle's state rounded to float32 (_f32_steps_vs_oracle) in a window
+    that starts at step 100, so that both collisions and timeouts are compared."""
+    tot = _f32_steps_vs_oracle(g, O, E, N, T, config=H.NONDEFAULT_CONFIGS["wide"], **H.NONDEFAULT_ODD_WINDOW)
+    _print_f32_totals('"wide" at %d x %d over %d steps' % (E, N, T), tot)
+    assert tot["speeds"] > 10
+    assert tot["outcomes"] >= {H.COLLISION, H.TIMEOUT}, tot["outcomes"]
+
+
+@pytest.mark.parametrize("name", tuple(H.NONDEFAULT_CONFIGS))
+def test_f32_reset_names_the_same_episodes_nondefault(g, O, name):
+    """test_f32_reset_names_the_same_episodes under a non-default configuration with an airspeed-factor range: the draws
+    of reset() and of the in-step reset within the bounds of helpers.f32_bounds (speeds included), and reset_kernel on a
+    twin env bit for bit what the step drew."""
+    E, N = 4096, 8
+    cfg = g.ACAS2DConfig(n_traffic=N, **H.NONDEFAULT_CONFIGS[name])
+    ref = O.OracleEnvs(E, N, seed=5, auto_reset=True, config=_oracle_config_from(O, cfg))
+    bnd = H.f32_bounds(ref.cfg, _default_oracle_config())
+    assert bnd["speed"] is not None
+    worst = dict(pos=0.0, psi=0.0, speed=0.0)
+
+    def close_to_oracle(env, sel):
+        e = max(np.abs(env.trf_x[sel] - ref.trf_x[sel]).max(), np.abs(env.trf_y[sel] - ref.trf_y[sel]).max())
+        worst["pos"] = max(worst["pos"], float(e))
+        assert e < bnd["reset_pos"], e
+        for k in ("trf_psi", "own_psi"):
+            dpsi = np.abs(getattr(env, k)[sel] - getattr(ref, k)[sel])
+            worst["psi"] = max(worst["psi"], float(np.minimum(dpsi, 360 - dpsi).max()))
+            assert np.minimum(dpsi, 360 - dpsi).max() < bnd["reset_psi"], k
+        e = np.abs(env.trf_v[sel] - ref.trf_v[sel]).max()
+        worst["speed"] = max(worst["speed"], float(e))
+        assert e <= bnd["speed"], e
+
+    ref.reset()
+    env = _engine(g.ACAS2DVecEnv(E, device="cuda:0", dtype=torch.float32, auto_reset=True, seed=5, config=cfg))
+    env.reset()
+    close_to_oracle(env, np.ones(E, bool))
+    assert len(np.unique(env.trf_v)) > 10                       # speeds really vary
+    rng = np.random.default_rng(3)
+    checked = 0
+    twin = g.ACAS2DVecEnv(E, device="cuda:0", dtype=torch.float32, auto_reset=True, seed=5, config=cfg)
+    for _ in range(40):
+        a = rng.uniform(-1, 1, E).astype(np.float32).astype(np.float64)
+        _, _, d1, _, _ = ref.step(a)
+        _, _, d2, _, _ = env.step(a)
+        both = (d1 != 0) & (d2 != 0) & (env.episode == ref.episode)
+        if both.any():
+            checked += int(both.sum())
+            close_to_oracle(env, both)
+        fresh = torch.as_tensor(d2 != 0, device="cuda:0")
+        if fresh.any():
+            twin.episode.copy_(env.v.episode)
+            twin._launch_reset(fresh.to(torch.uint8), do_init=1)
+            for k in _STATE:
+                assert torch.equal(getattr(twin, k)[fresh], getattr(env.v, k)[fresh]), k
+            assert bits_equal(twin.outputs["obs"][fresh], env.v.outputs["obs"][fresh])
+    print('f32 reset draws under "%s": %d in-step resets checked; worst positions %.2e (bound %.2e), headings %.2e (bound '
+          '%.0e), speeds %.2e (bound %.2e)' % (name, checked, worst["pos"], bnd["reset_pos"], worst["psi"], bnd["reset_psi"],
+                                             worst["speed"], bnd["speed"]))
+    assert checked > 50
+
+
+@pytest.mark.parametrize("shape", _F32_PACKED, ids=_ids(_F32_PACKED))
+def test_every_f32_packed_shape_rollout_equals_steps_nondefault(g, monkeypatch, shape):
+    """test_every_packed_shape_rollout_equals_steps on the float32 packed shapes under the "small" configuration."""
+    _rollout_equals_steps(g, monkeypatch, shape, H.NONDEFAULT_CONFIGS["small"])
+
+
+@pytest.mark.parametrize("shape", _F32_PACKED, ids=_ids(_F32_PACKED))
+def test_every_f32_packed_shape_arena_equals_general_nondefault(g, monkeypatch, shape):
+    """test_every_f32_packed_shape_arena_equals_general under the "small" configuration."""
+    _arena_equals_general(g, monkeypatch, shape, H.NONDEFAULT_CONFIGS["small"])
 
 
 # ---- waves whose envs finish together -----------------------------------------------------------------------------

@@ -424,3 +424,69 @@ def test_collect_and_rollout_policy_validation_needs_no_gpu(g):
             assert b"the value net, log_std, values and logp are required" in L.acas2d_last_error(), name
         assert cl(C.byref(cfg), C.byref(st), C.byref(io), None, a, 4, 13, 0, 64, N, None) == -22
         assert b"NULL actor-critic" in L.acas2d_last_error()
+
+
+# ---- the non-default configurations of the GPU tests (helpers.NONDEFAULT_CONFIGS) ------------------------------------
+# to_c() fields no ACAS2DConfig can move: the first traffic aircraft's heading base and step are constants of game.py:105,
+# and the player starts at the goal's height (own_y0 == goal_y == height / 2, game.py:80-87), so the heading from start
+# to goal is always 0.  `math` selects the float64 build's formulation and is not part of the environment.
+_FIXED_BY_CONSTRUCTION = ("t0_heading_base", "t0_heading_step", "own_heading0", "math")
+
+
+def _window_outcomes(O, cfg, E, N, T, seed, env_offset, warmup):
+    """Occurrences of each outcome, and the distinct traffic speeds, in the oracle side of a float32 window."""
+    counts, speeds = {}, set()
+    for _, _, _, _, _, _, chk, (_, _, d, oc) in H.f32_oracle_steps(O, E, N, T, seed, env_offset, warmup,
+                                                                   H.oracle_config(O, cfg)):
+        for k in oc[d != 0]:
+            counts[int(k)] = counts.get(int(k), 0) + 1
+        speeds |= set(np.unique(chk.trf_v).tolist())
+    return counts, len(speeds)
+
+
+@pytest.mark.parametrize("name", tuple(H.NONDEFAULT_CONFIGS))
+def test_nondefault_configs_move_every_tunable_and_cover_the_outcomes_the_gpu_tests_claim(g, oracle_mod, name):
+    """Each non-default configuration differs from the default in every to_c() field that a configuration can move, and
+    the CPU oracle, run over the windows of the GPU tests that use it (same seed, env_offset, warm-up and actions),
+    produces there the outcomes those tests assert they compared (at least 5 times each: helpers.nondefault_outcomes
+    lists exactly these) with more than 10 distinct traffic speeds.  A later edit of a configuration or a window that
+    drops goals or timeouts from a GPU test fails here, without a GPU."""
+    O = oracle_mod
+    kw = H.NONDEFAULT_CONFIGS[name]
+    c, d = g.ACAS2DConfig(**kw).to_c(), g.ACAS2DConfig().to_c()
+    for field, _ in type(c)._fields_:
+        if field in _FIXED_BY_CONSTRUCTION:
+            assert getattr(c, field) == getattr(d, field), field
+        else:
+            assert getattr(c, field) != getattr(d, field), field
+    assert c.own_y0 == c.goal_y and c.own_heading0 == 0
+    w = H.NONDEFAULT_SHAPE_WINDOW[name]
+    for N in sorted({s.n_traffic for s in H.SHAPES if s.dtype == "float32"}):
+        counts, speeds = _window_outcomes(O, g.ACAS2DConfig(n_traffic=N, **kw), 1001, N, w["T"], w["seed"],
+                                          w["env_offset"], w["warmup"])
+        assert {k for k, n in counts.items() if n >= 5} == H.nondefault_outcomes(name, N), (N, counts)
+        assert speeds > 10, (N, speeds)
+    if name == "wide":
+        for N, E, T in H.ODD_TRAFFIC:
+            counts, speeds = _window_outcomes(O, g.ACAS2DConfig(n_traffic=N, **kw), E, N, T, **H.NONDEFAULT_ODD_WINDOW)
+            assert min(counts.get(H.COLLISION, 0), counts.get(H.TIMEOUT, 0)) >= 5 and speeds > 10, (N, counts, speeds)
+    # test_f32_reset_names_the_same_episodes_nondefault: 40 steps from reset() (seed 5) end enough episodes
+    E, N = 4096, 8
+    ref = O.OracleEnvs(E, N, seed=5, auto_reset=True, config=H.oracle_config(O, g.ACAS2DConfig(n_traffic=N, **kw)))
+    ref.reset()
+    rng = np.random.default_rng(3)
+    assert sum(int(ref.step(rng.uniform(-1, 1, E).astype(np.float32).astype(np.float64))[4]) for _ in range(40)) > 200
+
+
+def test_f32_bounds_of_the_default_configuration_are_the_fixed_ones(oracle_mod):
+    """helpers.f32_bounds / f32_pos_bound evaluate, for the default configuration, to exactly the numbers the float32
+    tests held before the bounds were derived from the configuration; the non-default ones are at least as large."""
+    dflt = oracle_mod.default_config()
+    assert H.f32_bounds(dflt, dflt) == dict(band=1e-3, ret=1.3e-4 + 1e-5, rew=5e-5, reset_pos=2.5e-4,
+                                                reset_psi=6e-5, speed=None)
+    assert 1 - H.f32_bounds(dflt, dflt)["band"] == 0.999
+    assert H.f32_pos_bound(1600) == H.f32_pos_bound(2047.9) == 1.3e-4 and H.f32_pos_bound(2514) == 2 ** -12
+    import gym_acas2d_amd as g
+    for kw in H.NONDEFAULT_CONFIGS.values():
+        b = H.f32_bounds(H.oracle_config(oracle_mod, g.ACAS2DConfig(**kw)), dflt)
+        assert all(b[k] >= v for k, v in H.f32_bounds(dflt, dflt).items() if v is not None) and b["speed"] > 0

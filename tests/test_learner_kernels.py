@@ -275,6 +275,65 @@ def test_fused_collector_vs_float64(g, kern):
     H.replay_collect_on_twin(env, twin, out)
 
 
+# one paired (float32 C = 8: the float2 traffic path) and one unpaired (float32 C = 3) instantiation under the "small"
+# configuration (helpers.NONDEFAULT_CONFIGS): unequal speeds, another frame rate, airspace and max_steps
+_NONDEFAULT_KERNELS = (("float32", True, 8), ("float32", True, 3))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kern", _NONDEFAULT_KERNELS, ids=[R.kernel_id(k) for k in _NONDEFAULT_KERNELS])
+def test_fused_collector_nondefault_config_replays_on_a_twin(g, kern):
+    """collect() under the "small" configuration, 100 steps (past its 82-step timeout): a twin env stepped with the
+    clipped actions reproduces every observation, reward and mask bit for bit (helpers.replay_collect_on_twin)."""
+    dtype, fast, N = kern
+    D, E, T = 5 + 3 * N, 1001, 100
+    pol = _actor_critic(g, D)
+    env, twin = (_env(g, kern, E, seed=3, env_offset=37, cfg=H.NONDEFAULT_CONFIGS["small"]) for _ in range(2))
+    env.reset()
+    twin.reset()
+    assert len(torch.unique(env.trf_v)) > 10                           # speeds really vary
+    out = env.collect(pol, T, noise_seed=11, noise_step=0)
+    dones = H.replay_collect_on_twin(env, twin, out)
+    outcomes = set(out["outcome"][out["done"]].unique().tolist())
+    print("collector %s under \"small\": %d episodes finished, outcomes %s" % (R.kernel_id(kern), dones, sorted(outcomes)))
+    assert outcomes >= {H.COLLISION, H.TIMEOUT}, outcomes
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kern", _NONDEFAULT_KERNELS, ids=[R.kernel_id(k) for k in _NONDEFAULT_KERNELS])
+def test_fused_policy_rollout_nondefault_config_replays_on_a_twin(g, kern):
+    """rollout_policy() under the "small" configuration, 100 steps: every action against clip(mean64, -1, 1) on the
+    observation the kernel stepped from (1e-5, NaN at the same places), and a twin env stepped with those actions
+    reproduces every observation, reward and mask bit for bit and ends in the same state."""
+    dtype, fast, N = kern
+    D, E, T = 5 + 3 * N, 1001, 100
+    pol = _actor_critic(g, D)
+    env, twin = (_env(g, kern, E, seed=3, env_offset=37, cfg=H.NONDEFAULT_CONFIGS["small"]) for _ in range(2))
+    env.reset()
+    obs0 = twin.reset().double().cpu().numpy()
+    out = env.rollout_policy(pol, T)
+    torch.cuda.synchronize()
+    obs = np.concatenate([obs0[None], out["obs"][:T - 1].double().cpu().numpy()])
+    ref = R.actor64(pol.actor_weights(), obs.reshape(T * E, D)).reshape(T, E)
+    got = out["actions"].double().cpu().numpy()
+    assert np.array_equal(np.isnan(got), np.isnan(ref))
+    fin = ~np.isnan(ref)
+    worst = float(np.abs(got[fin] - ref[fin]).max())
+    dones, outcomes = 0, set()
+    for t in range(T):
+        o, r, d, infos = twin.step(out["actions"][t])
+        assert H.bits_equal(out["obs"][t], o) and H.bits_equal(out["reward"][t], r), t
+        assert torch.equal(out["done"][t], d) and torch.equal(out["outcome"][t], infos.outcome), t
+        dones += int(d.sum())
+        outcomes |= set(infos.outcome[d].unique().tolist())
+    for name in ("own_x", "own_y", "own_psi", "trf_x", "trf_y", "trf_v", "steps", "total_reward", "episode"):
+        assert torch.equal(getattr(env, name), getattr(twin, name)), name
+    print("rollout_policy %s under \"small\": worst |action - clip(mean64)| %.2e (bound 1e-5); %d episodes finished, "
+          "outcomes %s" % (R.kernel_id(kern), worst, dones, sorted(outcomes)))
+    assert worst < 1e-5
+    assert outcomes >= {H.COLLISION, H.TIMEOUT}, outcomes
+
+
 # ---- acas2d_rollout_policy_* ----------------------------------------------------------------------------------------
 def _scaled_actor(g, D, kind, obs0):
     """An SB3 actor whose hidden pre-activations reach |z| = 60 on obs0 in both layers ("saturating": v_exp_f32 in
