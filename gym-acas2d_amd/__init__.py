@@ -11,7 +11,8 @@ from .spaces import Box                                              # noqa: F40
 from . import native, records, render, reset_parity, sharding        # noqa: F401
 from .vec_env import ACAS2DVecEnv, LazyInfos                         # noqa: F401
 from .env import ACAS2DEnv, GameView, register_with_gym              # noqa: F401
-from .policy import SB3ActorPolicy, load_sb3_policy, evaluate_policy, evaluate_policy_fused  # noqa: F401
+from .policy import (SB3ActorPolicy, load_sb3_policy, save_sb3_policy, evaluate_policy, evaluate_policy_fused,  # noqa: F401
+                     evaluate_policies_fused)
 from .ppo import ActorCritic, FusedUpdate, PPOConfig, PPOTrainer, compute_gae, ppo_loss   # noqa: F401
 
 register_with_gym()

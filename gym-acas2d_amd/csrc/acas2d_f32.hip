@@ -11,6 +11,7 @@ template int launch_step<float>(const Acas2dConfig*, const Acas2dState*, const A
 template int launch_rollout<float>(const Acas2dConfig*, const Acas2dState*, const Acas2dStepIO*, int32_t, uint64_t, int64_t, int64_t, int32_t, hipStream_t);
 template int launch_rollout_policy<float>(const Acas2dConfig*, const Acas2dState*, const Acas2dStepIO*, const Acas2dPolicy*, const void*, int32_t, uint64_t, int64_t, int64_t, int32_t, hipStream_t);
 template int launch_collect<float>(const Acas2dConfig*, const Acas2dState*, const Acas2dStepIO*, const Acas2dActorCritic*, const void*, int32_t, uint64_t, int64_t, int64_t, int32_t, hipStream_t);
+template int launch_evaluate_policies<float>(const Acas2dConfig*, const Acas2dState*, int64_t, const Acas2dPolicy*, int32_t, int32_t, const void*, int32_t, uint64_t, int64_t, int32_t, uint8_t*, int32_t*, void*, hipStream_t);
 template int launch_reset<float>(const Acas2dConfig*, const Acas2dState*, const uint8_t*, void*, int32_t, uint64_t, int64_t, int64_t, int32_t, hipStream_t);
 template int shape_geometry<float>(int64_t, int32_t, int32_t*, int32_t*, int64_t*);
 template int state_consecutive<float>(const Acas2dState*, int64_t, int32_t);

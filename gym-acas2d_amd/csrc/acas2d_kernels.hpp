@@ -1384,6 +1384,20 @@ struct PolicyW {
 };
 constexpr int kPolicyHidden = 64;
 
+// EVAL (acas2d_evaluate_policies_*): K policies scored on the same episodes in one launch.  The actor pointers name
+// [K][...] stacks; env e plays episode e % ep_stride for policy e / ep_stride (ep_stride = n_episodes rounded up to a
+// whole wave, so the policy is wave-uniform and its weights stay scalar operands).  Each lane keeps its FIRST episode
+// only: at its first done it writes outcome / steps / total_reward to [K][n_episodes] and stops; a lane that never
+// finishes within n_steps writes 0 / 0 / 0.
+struct PolicyEvalW : PolicyW {
+    uint8_t* res_outcome;                            // [K][n_episodes]
+    int32_t* res_steps;                              // [K][n_episodes]: game.steps at done
+    void* res_return;                                // T[K][n_episodes]
+    int32_t n_episodes, ep_stride;
+};
+template <bool EVAL>
+using PolicyArg = typename std::conditional<EVAL, PolicyEvalW, PolicyW>::type;
+
 // tanh(x) = 1 - 2 / (exp(2x) + 1) on v_exp_f32 / v_rcp_f32: abs error < 2e-7 over the reals
 // (saturates cleanly: exp -> inf gives 1, exp -> 0 gives -1).
 __device__ __forceinline__ float tanh_hw(float x) {
@@ -1447,16 +1461,20 @@ __device__ __forceinline__ float policy_action(const PolicyW& pw, const float (&
 // eps, eps ~ N(0, 1) from a Philox block per env and step (Box-Muller); the raw action, the critic's value of the
 // observation and the log-probability of the draw are stored per step, the env is stepped with the clipped action, and
 // a non-finite observation entry reaches the networks as 0 (the reference's NaN d_cpa in exact parallel flight).
+// With EVAL on top of POLICY (acas2d_evaluate_policies_*; PolicyEvalW) the launch scores K stacked policies: no per-step
+// outputs, no in-step resets, no state write-back; each lane latches the result of its first episode and the wave leaves
+// the step loop once none of its lanes is still running.
 template <typename T, int C, int G, bool PACKED, bool AUTO_RESET, bool FAST, bool ROLLOUT, bool POLICY = false,
-          bool SAMPLE = false, bool ARENA = false>
+          bool SAMPLE = false, bool ARENA = false, bool EVAL = false>
 __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, const T* a2, const T* a3, const T* a4,
                                                       const T* a5, int32_t e_n_envs, int32_t tile_elems,
                                                       Params<T> p_arg, StepResetParams<T, ROLLOUT> rp_arg, State<T> s_arg,
                                                       StepIO<T> io_arg, uint32_t k0, uint32_t k1,
-                                                      int64_t env_offset, int N_arg, int n_steps, PolicyW pw) {
+                                                      int64_t env_offset, int N_arg, int n_steps, PolicyArg<EVAL> pw) {
     static_assert(!ROLLOUT || (AUTO_RESET && PACKED), "rollout: auto-reset semantics, packed shapes");
     static_assert(!POLICY || (ROLLOUT && G == 1), "in-kernel policy: rollout mode, one lane per env");
     static_assert(!SAMPLE || POLICY, "sampling needs the in-kernel policy");
+    static_assert(!EVAL || (POLICY && !SAMPLE), "evaluation: the deterministic in-kernel policy");
     constexpr int NS = PACKED ? C * G : 0;         // packed shapes: n_traffic is a compile-time constant
     const int N = PACKED ? NS : N_arg;
     constexpr int EPW = 64 / G;                    // envs per wavefront
@@ -1619,6 +1637,21 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
         const T* obs_in = static_cast<const T*>(pw.obs_in) + e_wave * D;
         if (active) { for (int i = 0; i < D; ++i) row[i] = obs_in[el * D + i]; }
     }
+    // EVAL: this wave's policy (ep_stride is a multiple of the wave, so one per wave: its weights stay SGPR operands), the
+    // lane's episode, and whether it is still playing it (padding lanes past n_episodes never are)
+    bool running = false;
+    int64_t res_i = 0;
+    if constexpr (EVAL) {
+        const uint32_t kp = __builtin_amdgcn_readfirstlane(e_wave32 / (uint32_t)pw.ep_stride);
+        const uint32_t ep = e_wave32 - kp * (uint32_t)pw.ep_stride + (uint32_t)el;
+        running = active && ep < (uint32_t)pw.n_episodes;
+        res_i = (int64_t)kp * pw.n_episodes + ep;
+        constexpr int DP = 5 + 3 * NS;
+        pw.w1t += (size_t)kp * (DP * kPolicyHidden); pw.b1 += (size_t)kp * kPolicyHidden;
+        pw.w2t += (size_t)kp * (kPolicyHidden * kPolicyHidden); pw.b2 += (size_t)kp * kPolicyHidden;
+        pw.w3 += (size_t)kp * kPolicyHidden; pw.b3 += kp;
+    }
+    (void)running; (void)res_i;
     for (int t = 0; t < T_steps; ++t) {
         // outputs of step t: [t][E] / [t][E][D] slices (t == 0 for the per-step launch)
         const int64_t te = ROLLOUT ? (int64_t)t * n_envs : 0;
@@ -1665,7 +1698,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
                 action = (T)fminf(fmaxf(raw, -1.0f), 1.0f);
             } else {
                 action = (T)policy_action<DP>(pw_t, x);
-                if (active) (static_cast<T*>(pw.actions_out) + e_wave + te)[el] = action;
+                if constexpr (!EVAL) { if (active) (static_cast<T*>(pw.actions_out) + e_wave + te)[el] = action; }
             }
         } else {
             if (ROLLOUT && active && t + 1 < T_steps) action_next = io.actions[n_envs + el];
@@ -1698,7 +1731,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
             auto before_traffic = [&](const OwnCtx<T>&) {
                 if constexpr (!AUTO_RESET) { if (s.trace) d_sep = minimum_separation<T, C, G, PACKED>(s, o, tr, el, j, N); }
             };
-            Seen<T> r = observe<T, C, G, PACKED, FAST>(p, s, o, el, j, N, steps, !frozen, tr, row, last && active,
+            Seen<T> r = observe<T, C, G, PACKED, FAST>(p, s, o, el, j, N, steps, !frozen, tr, row, !EVAL && last && active,
                                                        ROLLOUT ? &trig : nullptr, before_traffic);
 
             // game.py:249-292 evaluate()
@@ -1717,7 +1750,14 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
             oc = (steps > p.max_steps) ? 3 : (r.collided ? 2 : (at_goal ? 1 : 0));
             total = total + rw;                                               // :287
             if (!active) oc = 0;                          // a padding lane never finishes anything
-            if (j == 0 && active) {
+            if constexpr (EVAL) {
+                if (running && oc != 0) {                 // the first episode's result, then the lane stops for good
+                    pw.res_outcome[res_i] = oc;
+                    pw.res_steps[res_i] = steps;
+                    static_cast<T*>(pw.res_return)[res_i] = total;
+                    running = false;
+                }
+            } else if (j == 0 && active) {
                 io.reward[el] = rw;                       // (plain stores: non-temporal measured the same, 0.6 MB)
                 io.done[el] = (uint8_t)(oc != 0);
                 io.outcome[el] = oc;
@@ -1734,7 +1774,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
 
         if (t == 0) ACAS2D_STAMP(3, wave, lane, false);
         T* const obs_wave = io.obs;
-        if constexpr (HANDOFF) {
+        if constexpr (HANDOFF && !EVAL) {
             // ---- finished envs (one bit per env: its group's lane 0) are reset by the whole wave NOW,
             // before anything but reward / done / outcome has been stored: the new episode's state
             // reaches the owner lanes through LDS and leaves with the coalesced state stores and the
@@ -1851,12 +1891,14 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
             }
         }
         // Flush the tile (generic walk: now, the stores drain while finished envs are reset below).
-        wave_lds_fence();
-        if constexpr (PACKED) {
-            constexpr int kChunks = (EPW * (5 + 3 * NS) * (int)sizeof(T) / 16 + 63) / 64;
-            flush_tile_unrolled<T, kChunks>(tile, obs_wave, n_rows * D, lane);
-        } else {
-            flush_tile<T>(tile, obs_wave, n_rows * D, lane);
+        if constexpr (!EVAL) {
+            wave_lds_fence();
+            if constexpr (PACKED) {
+                constexpr int kChunks = (EPW * (5 + 3 * NS) * (int)sizeof(T) / 16 + 63) / 64;
+                flush_tile_unrolled<T, kChunks>(tile, obs_wave, n_rows * D, lane);
+            } else {
+                flush_tile<T>(tile, obs_wave, n_rows * D, lane);
+            }
         }
         if (t == 0) ACAS2D_STAMP(4, wave, lane, false);
         if constexpr (AUTO_RESET && !HANDOFF) {
@@ -1875,6 +1917,16 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
             }
         }
         if constexpr (ROLLOUT) wave_lds_fence();          // tile reads precede the next step's row writes
+        // EVAL: the wave is done once every lane has latched its result (a wave-uniform exit: the loop body has no
+        // workgroup barrier, only the wave's own LDS tile and fences)
+        if constexpr (EVAL) { if (__ballot(running) == 0ull) break; }
+    }
+    if constexpr (EVAL) {
+        if (running) {                                    // no done within n_steps
+            pw.res_outcome[res_i] = 0;
+            pw.res_steps[res_i] = 0;
+            static_cast<T*>(pw.res_return)[res_i] = T(0);
+        }
     }
     ACAS2D_STAMP(5, wave, lane, false);
     ACAS2D_STAMP(6, wave, lane, true);
@@ -1956,6 +2008,11 @@ template <typename T>
 int launch_collect(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
                    const void* obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset, int64_t n_envs,
                    int32_t n_traffic, hipStream_t stream);
+template <typename T>
+int launch_evaluate_policies(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
+                             int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
+                             int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
+                             hipStream_t stream);
 template <typename T>
 int launch_reset(const Acas2dConfig* cfg, const Acas2dState* st, const uint8_t* mask, void* obs,
                  int32_t do_init, uint64_t seed, int64_t env_offset, int64_t n_envs, int32_t n_traffic,

@@ -223,6 +223,16 @@ static void policy_shape(const Geometry& g, hipStream_t stream, const Params<T>&
                            stream, ACAS2D_EARLY_ARGS(s, n_envs, g), p, rp, s, io, k0, k1, env_offset, N, n_steps, pw);
 }
 
+// K stacked policies scored on shared episodes (acas2d_evaluate_policies_*): the policy rollout with EVAL
+template <typename T, bool FAST, int C>
+static void eval_shape(const Geometry& g, hipStream_t stream, const Params<T>& p, const StepResetParams<T, true>& rp,
+                       const State<T>& s, uint32_t k0, uint32_t k1, int64_t env_offset, int64_t n_envs, int N, int n_steps,
+                       const PolicyEvalW& pw) {
+    hipLaunchKernelGGL((step_kernel<T, C, 1, true, true, FAST, true, true, false, false, true>), dim3(g.grid), dim3(kBlock),
+                       g.lds_bytes, stream, ACAS2D_EARLY_ARGS(s, n_envs, g), p, rp, s, StepIO<T>{}, k0, k1, env_offset, N,
+                       n_steps, pw);
+}
+
 template <typename T, bool FAST, int C, int G, bool PACKED>
 static void reset_shape(const Geometry& g, hipStream_t stream, const Params<T>& p, const StepResetParams<T, true>& rp,
                         const State<T>& s, const uint8_t* mask, T* obs, int do_init, uint32_t k0, uint32_t k1,
@@ -377,6 +387,56 @@ static int launch_rollout_policy_impl(const Acas2dConfig* cfg, const Acas2dState
 }
 
 template <typename T, bool FAST>
+static int launch_evaluate_policies_impl(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
+                                         int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps,
+                                         uint64_t seed, int64_t env_offset, int32_t n_traffic, uint8_t* outcome,
+                                         int32_t* steps, void* total_reward, hipStream_t stream) {
+    if (!cfg || !pol) { set_error("acas2d_evaluate_policies: NULL cfg / policies"); return ACAS2D_EINVAL; }
+    if (!state_complete(st)) { set_error("acas2d_evaluate_policies: NULL state or a NULL state buffer"); return ACAS2D_EINVAL; }
+    if (!obs_in || !outcome || !steps || !total_reward) {
+        set_error("acas2d_evaluate_policies: obs_in and the outcome, steps and total_reward outputs are required"); return ACAS2D_EINVAL; }
+    if (!pol->w1t || !pol->b1 || !pol->w2t || !pol->b2 || !pol->w3 || !pol->b3 || pol->hidden != kPolicyHidden) {
+        set_error("acas2d_evaluate_policies: six weight buffers and hidden == %d are required (got hidden = %d)", kPolicyHidden, pol->hidden);
+        return ACAS2D_EINVAL; }
+    if (n_policies < 1 || n_episodes < 1) {
+        set_error("acas2d_evaluate_policies: n_policies = %d, n_episodes = %d (at least 1 each)", n_policies, n_episodes); return ACAS2D_EINVAL; }
+    if (n_traffic < 1 || n_steps < 1) { set_error("acas2d_evaluate_policies: n_traffic = %d, n_steps = %d", n_traffic, n_steps); return ACAS2D_EINVAL; }
+    if (env_offset < 0) { set_error("acas2d_evaluate_policies: negative env_offset"); return ACAS2D_EINVAL; }
+    bool ok = false;
+#define X(C_, G_) if (G_ == 1 && C_ == n_traffic) ok = true;
+    ACAS2D_PACKED_SHAPES(X)
+#undef X
+    if (!ok) {
+        set_error("acas2d_evaluate_policies: n_traffic = %d has no thread-per-env shape for this element type", n_traffic);
+        return ACAS2D_EINVAL;
+    }
+    // policy k plays envs [k EP, (k + 1) EP): EP = n_episodes rounded up to a whole wave
+    const int64_t ep = ((int64_t)n_episodes + 63) / 64 * 64, total = (int64_t)n_policies * ep;
+    if (n_envs < total) {
+        set_error("acas2d_evaluate_policies: the state holds n_envs = %lld envs, %d policies x %lld (n_episodes = %d rounded up "
+                  "to 64) need %lld", (long long)n_envs, n_policies, (long long)ep, n_episodes, (long long)total);
+        return ACAS2D_EINVAL;
+    }
+    const Shape sh{n_traffic, 1, true};
+    Geometry g;
+    if (int rc = geometry_for<T>(sh, total, n_traffic, &g)) return rc;
+    const Params<T> p = make_params<T>(*cfg);
+    const StepResetParams<T, true> rp = make_reset_params<double, T>(*cfg);
+    const State<T> s = make_state<T>(*st);
+    PolicyEvalW pw{};
+    pw.w1t = (const float*)pol->w1t; pw.b1 = (const float*)pol->b1; pw.w2t = (const float*)pol->w2t;
+    pw.b2 = (const float*)pol->b2; pw.w3 = (const float*)pol->w3; pw.b3 = (const float*)pol->b3;
+    pw.obs_in = obs_in;
+    pw.res_outcome = outcome; pw.res_steps = steps; pw.res_return = total_reward;
+    pw.n_episodes = n_episodes; pw.ep_stride = (int32_t)ep;
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#define X(C_, G_) if constexpr (G_ == 1) { if (C_ == n_traffic) eval_shape<T, FAST, C_>(g, stream, p, rp, s, k0, k1, env_offset, total, n_traffic, n_steps, pw); }
+    ACAS2D_PACKED_SHAPES(X)
+#undef X
+    return check_launch("acas2d_evaluate_policies launch");
+}
+
+template <typename T, bool FAST>
 static int launch_reset_impl(const Acas2dConfig* cfg, const Acas2dState* st, const uint8_t* mask, void* obs,
                  int32_t do_init, uint64_t seed, int64_t env_offset, int64_t n_envs, int32_t n_traffic,
                  hipStream_t stream) {
@@ -443,6 +503,17 @@ int launch_collect(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dS
     return fast_math<T>(cfg)
                ? launch_rollout_policy_impl<T, true>(cfg, st, io, &ac->actor, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream, ac)
                : launch_rollout_policy_impl<T, kFast>(cfg, st, io, &ac->actor, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream, ac);
+}
+template <typename T>
+int launch_evaluate_policies(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
+                             int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
+                             int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
+                             hipStream_t stream) {
+    return fast_math<T>(cfg)
+               ? launch_evaluate_policies_impl<T, true>(cfg, st, n_envs, pol, n_policies, n_episodes, obs_in, n_steps, seed,
+                                                        env_offset, n_traffic, outcome, steps, total_reward, stream)
+               : launch_evaluate_policies_impl<T, kFast>(cfg, st, n_envs, pol, n_policies, n_episodes, obs_in, n_steps, seed,
+                                                         env_offset, n_traffic, outcome, steps, total_reward, stream);
 }
 template <typename T>
 int launch_reset(const Acas2dConfig* cfg, const Acas2dState* st, const uint8_t* mask, void* obs,

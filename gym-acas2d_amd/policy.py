@@ -11,7 +11,9 @@ not required here: the zip's `policy.pth` is a state dict of 13 float32 tensors,
 space without squashing: observation -> float32, two tanh layers of 64, linear action head, the
 mean action clipped to [-1, 1].
 """
+import ctypes as C
 import io
+import os
 import zipfile
 
 import numpy as np
@@ -62,6 +64,31 @@ def load_sb3_policy(path, device="cpu"):
         with zipfile.ZipFile(path) as z:
             sd = torch.load(io.BytesIO(z.read("policy.pth")), map_location="cpu", weights_only=True)
     return SB3ActorPolicy(sd).to(device)
+
+
+SB3_VERSION = "1.1.0"
+
+
+def save_sb3_policy(actor_critic, path):
+    """Write `actor_critic` (a `ppo.ActorCritic`) as the policy half of an SB3 1.1.0 PPO zip: `policy.pth`, the
+    state dict of its 13 float32 tensors under SB3's MlpPolicy keys (ActorCritic's own parameter names), and
+    `_stable_baselines3_version`.  `load_sb3_policy` / `ActorCritic.load_sb3_state_dict` read it back bit for bit.
+    SB3's pickled `data` member (the class, spaces and hyper-parameters) is NOT written, so loading the file with
+    SB3 itself is parity unpinned."""
+    sd = {k: v.detach().to(device="cpu", dtype=torch.float32).contiguous().clone()
+          for k, v in actor_critic.state_dict().items()}
+    buf = io.BytesIO()
+    torch.save(sd, buf)
+    path = str(path)
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    tmp = path + ".tmp"
+    with zipfile.ZipFile(tmp, "w", zipfile.ZIP_DEFLATED) as z:
+        z.writestr("policy.pth", buf.getvalue())
+        z.writestr("_stable_baselines3_version", SB3_VERSION)
+    os.replace(tmp, path)
+    return path
 
 
 def evaluate_policy(venv, policy, max_steps=None):
@@ -116,3 +143,54 @@ def evaluate_policy_fused(policy, own, traffic, goal=None, dtype=torch.float64, 
     return {"outcome": np.where(fin, out["outcome"].cpu().numpy()[t0, e], 0).astype(np.uint8), "steps": steps,
             "total_reward": np.where(fin, out["episode_return"].cpu().numpy()[t0, e], 0.0).astype(np.float64),
             "path_length": step_len * (steps - 1), "unfinished": int((~fin).sum())}
+
+
+def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float64, device="cuda:0", config=None,
+                            max_steps=None):
+    """evaluate_policy_fused() for K policies on the SAME E episodes in ONE launch (acas2d_evaluate_policies_*):
+    scoring the checkpoints of a run, or the policies of a seed sweep, together.  `policies`: `SB3ActorPolicy` /
+    `ppo.ActorCritic` objects or paths of SB3 zips / .npz exports.  The episodes `own` [E,4] / `traffic` [E,N,4] /
+    `goal` are replicated into K blocks of EP = round_up(E, 64) envs (block k: policy k; the padding repeats episode 0
+    and is not scored).  Each env stops at the end of its first episode, and nothing per step is stored.
+    Returns evaluate_policy_fused()'s keys as [K, E] numpy arrays (outcome, steps, total_reward, path_length) and
+    `unfinished` [K]; row k equals evaluate_policy_fused(policies[k], ...) bit for bit."""
+    from . import native
+    from .vec_env import ACAS2DVecEnv
+    if not policies:
+        raise ValueError("evaluate_policies_fused needs at least one policy")
+    own, traffic = np.asarray(own), np.asarray(traffic)
+    E, N = own.shape[0], traffic.shape[1]
+    K, EP = len(policies), (own.shape[0] + 63) // 64 * 64
+    idx = np.concatenate([np.arange(E), np.zeros(EP - E, np.int64)])
+    idx = np.tile(idx, K)
+    if goal is not None and np.asarray(goal).ndim == 2:
+        goal = np.asarray(goal)[idx]
+    v = ACAS2DVecEnv(K * EP, N, device=device, dtype=dtype, auto_reset=True, config=config)
+    D, dev = v.obs_dim, v.device
+    v.set_state(own[idx], traffic[idx], goal, np.zeros(K * EP, np.int32), observe=True)
+    ws = []
+    for pol in policies:
+        if isinstance(pol, (str, os.PathLike)):
+            pol = load_sb3_policy(pol)
+        w = pol.actor_weights() if hasattr(pol, "actor_weights") else pol
+        w1, b1, w2, b2, w3, b3 = (torch.as_tensor(t, dtype=torch.float32).to(dev) for t in w)
+        if w1.shape != (64, D) or w2.shape != (64, 64) or w3.numel() != 64 or b3.numel() != 1:
+            raise ValueError("policy must be the SB3 MlpPolicy actor %d -> 64 -> 64 -> 1, got %s %s %s"
+                             % (D, tuple(w1.shape), tuple(w2.shape), tuple(w3.shape)))
+        ws.append((w1.t(), b1.reshape(64), w2.t(), b2.reshape(64), w3.reshape(64), b3.reshape(1)))
+    keep = [torch.stack([w[i] for w in ws]).contiguous() for i in range(6)]      # [K][D][64], [K][64], ...
+    T = (max_steps or v.config.max_steps) + 1
+    outcome = torch.empty(K, E, dtype=torch.uint8, device=dev)
+    steps = torch.empty(K, E, dtype=torch.int32, device=dev)
+    ret = torch.empty(K, E, dtype=dtype, device=dev)
+    pw = native.CPolicy(*[t.data_ptr() for t in keep], 64, 0)
+    L = native.lib()
+    fn = L.acas2d_evaluate_policies_f32 if dtype == torch.float32 else L.acas2d_evaluate_policies_f64
+    with torch.cuda.device(dev):
+        native.check(fn(C.byref(v._ccfg), C.byref(v._cstate), K * EP, C.byref(pw), K, E, v.outputs["obs"].data_ptr(), T,
+                        v.seed_value, v.env_offset, N, outcome.data_ptr(), steps.data_ptr(), ret.data_ptr(),
+                        v._stream()))
+    oc, st = outcome.cpu().numpy(), steps.cpu().numpy()
+    step_len = v.config.airspeed * v.config.dt
+    return {"outcome": oc, "steps": st, "total_reward": ret.cpu().numpy().astype(np.float64),
+            "path_length": step_len * (st - 1), "unfinished": (oc == 0).sum(1)}

@@ -27,6 +27,8 @@ statistics are read once per iteration from the [T, E] side-channel buffers.
 """
 import dataclasses
 import math
+import os
+import random
 import time
 
 import numpy as np
@@ -491,11 +493,47 @@ class PPOTrainer:
                 "goal": float((o == 1).float().mean()), "collision": float((o == 2).float().mean()),
                 "timeout": float((o == 3).float().mean())}
 
-    def learn(self, total_timesteps, log=print):
+    def evaluate(self, n_episodes, rng):
+        """Score the current actor deterministically on `n_episodes` fresh episodes drawn from `rng` (a `random.Random`
+        fed to reset_parity, like the reference's eval env) in one launch (policy.evaluate_policies_fused, K = 1).
+        Touches neither the training env, nor the captured graphs, nor any torch random stream."""
+        from . import reset_parity
+        from .policy import evaluate_policies_fused
+        own, trf, goal = reset_parity.draw_episodes(self.venv.config, n_episodes, rng)
+        out = evaluate_policies_fused([self.policy], own, trf, goal, dtype=self.venv.dtype, device=self.device,
+                                      config=self.venv.config)
+        return {k: (v[0] if k != "unfinished" else int(v[0])) for k, v in out.items()}
+
+    def learn(self, total_timesteps, log=print, eval_every=None, eval_episodes=10, eval_seed=None, save_dir=None,
+              checkpoint_every=None):
+        """Run PPO iterations until `total_timesteps` env steps.  Off by default, SB3's callbacks as training_main.py
+        sets them up:
+          eval_every        EvalCallback: at each iteration boundary that crosses a multiple of `eval_every` timesteps,
+                            score the deterministic actor on `eval_episodes` fresh episodes from ONE
+                            random.Random(eval_seed) (default: the config's seed) kept for the whole run; the record
+                            joins the history, and with `save_dir` the scores are appended to
+                            save_dir/results/evaluations.npz (timesteps [n], results [n, eval_episodes] returns,
+                            ep_lengths [n, eval_episodes] = steps - 1) and save_dir/best_model.zip is written whenever
+                            the mean return beats the best so far
+          checkpoint_every  CheckpointCallback: save_dir/checkpoints/model_<num_timesteps>_steps.zip at each boundary
+                            that crosses a multiple of `checkpoint_every` timesteps
+        Neither changes the training: the evaluation runs on an env of its own and draws no torch random numbers."""
+        if checkpoint_every and not save_dir:
+            raise ValueError("checkpoint_every needs save_dir")
+        if eval_every:
+            f32 = self.venv.dtype == torch.float32
+            if self.venv.n_traffic not in ((1, 2, 3, 4, 8) if f32 else (1, 2, 3, 4)):
+                raise ValueError("eval_every needs a thread-per-env work shape: n_traffic in {1, 2, 3, 4, 8} (float32) / "
+                                 "{1, 2, 3, 4} (float64), got %d" % self.venv.n_traffic)
+            eval_rng = random.Random(self.cfg.seed if eval_seed is None else eval_seed)
+        from .policy import save_sb3_policy
+        evals = {"timesteps": [], "results": [], "ep_lengths": []}
+        best = -math.inf
         t0 = time.time()
         it = 0
         history = []
         while self.num_timesteps < total_timesteps:
+            before = self.num_timesteps
             batch = self.collect()
             stats = self.update() if batch is None else self.update(*batch)
             it += 1
@@ -506,4 +544,30 @@ class PPOTrainer:
             history.append(rec)
             if log:
                 log(rec)
+            crossed = lambda every: bool(every) and before // every < self.num_timesteps // every  # noqa: E731
+            if crossed(eval_every):
+                out = self.evaluate(eval_episodes, eval_rng)
+                mean = float(out["total_reward"].mean())
+                new_best = mean > best
+                best = max(best, mean)
+                erec = {"eval": True, "timesteps": self.num_timesteps, "mean_reward": mean,
+                        "std_reward": float(out["total_reward"].std()), "mean_ep_length": float((out["steps"] - 1).mean()),
+                        "goal": float((out["outcome"] == 1).mean()), "collision": float((out["outcome"] == 2).mean()),
+                        "timeout": float((out["outcome"] == 3).mean()), "unfinished": out["unfinished"],
+                        "new_best": new_best}
+                if save_dir:
+                    evals["timesteps"].append(self.num_timesteps)
+                    evals["results"].append(out["total_reward"].astype(np.float64))
+                    evals["ep_lengths"].append(out["steps"].astype(np.int64) - 1)
+                    os.makedirs(os.path.join(save_dir, "results"), exist_ok=True)
+                    np.savez(os.path.join(save_dir, "results", "evaluations.npz"),
+                             timesteps=np.asarray(evals["timesteps"], np.int64),
+                             results=np.stack(evals["results"]), ep_lengths=np.stack(evals["ep_lengths"]))
+                    if new_best:
+                        save_sb3_policy(self.policy, os.path.join(save_dir, "best_model.zip"))
+                history.append(erec)
+                if log:
+                    log(erec)
+            if crossed(checkpoint_every):
+                save_sb3_policy(self.policy, os.path.join(save_dir, "checkpoints", "model_%d_steps.zip" % self.num_timesteps))
         return history

@@ -269,7 +269,33 @@ int acas2d_collect_f64(const Acas2dConfig *cfg, const Acas2dState *state, const 
                        int64_t env_offset, int64_t n_envs, int32_t n_traffic, void *stream);
 
 /*
- * acas2d_ppo_update_f32: ONE minibatch update of SB3 1.1.0's PPO.train() for the MlpPolicy actor-critic (the update
+ * acas2d_evaluate_policies_*: K deterministic policies scored on the same n_episodes episodes in ONE launch -- the
+ * evaluation of testing_main.py / SB3's EvalCallback for a set of checkpoints.  Additive to ABI 7.
+ *   state, n_envs     the envs; the first K * EP are used, EP = n_episodes rounded up to a multiple of 64: env
+ *                     k * EP + i holds episode i for policy k (i >= n_episodes: padding, never scored)
+ *   policies          ONE Acas2dPolicy whose pointers name the K actors stacked: w1t float[K][D][64], b1 float[K][64],
+ *                     w2t float[K][64][64], b2 float[K][64], w3 float[K][64], b3 float[K][1]
+ *   obs_in            T[K * EP][D]  the observation each env's first action is taken on
+ *   n_steps           the step budget (max_steps + 1 covers every episode)
+ *   outcome, steps    uint8 / int32 [K][n_episodes]: each env's FIRST episode -- its outcome and game.steps at done,
+ *   total_reward      T[K][n_episodes]  and its return; 0 / 0 / 0 where the episode is not done within n_steps
+ * Per step the arithmetic of acas2d_rollout_policy_*, so row k equals that rollout of policy k on the same episodes
+ * bit for bit.  Nothing else is written: no per-step outputs, and the state is left as it was given.  A lane stops at
+ * its episode's end and a wavefront once all its lanes have.  Work shapes as acas2d_rollout_policy_*.
+ */
+int acas2d_evaluate_policies_f32(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                                 const Acas2dPolicy *policies, int32_t n_policies, int32_t n_episodes,
+                                 const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
+                                 int32_t n_traffic, uint8_t *outcome, int32_t *steps, void *total_reward,
+                                 void *stream);
+int acas2d_evaluate_policies_f64(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                                 const Acas2dPolicy *policies, int32_t n_policies, int32_t n_episodes,
+                                 const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
+                                 int32_t n_traffic, uint8_t *outcome, int32_t *steps, void *total_reward,
+                                 void *stream);
+
+/*
+ * acas2d_ppo_update_f32:ONE minibatch update of SB3 1.1.0's PPO.train() for the MlpPolicy actor-critic (the update
  * half of `PPO('MlpPolicy', env).learn()`, training_main.py:44-52) as two launches: forward + PPO loss + backward of
  * both 2 x 64 tanh networks on the rows idx[0 .. n_rows) of the rollout buffer (advantages normalised over the
  * minibatch, clipped surrogate, MSE value loss without clipping, entropy of the state-independent Gaussian), then

@@ -1,0 +1,44 @@
+#!/usr/bin/env python3
+"""checkpoint_testing_main.py for a whole training run: every `model_<n>_steps.zip` under DIR (and DIR/checkpoints)
+plus `best_model.zip`, scored deterministically on the reference's 100 test episodes (the first 100 games of the
+seed-13 MT19937 stream, as testing_main.py and tools/train_ppo.py draw them) in ONE launch (evaluate_policies_fused).
+One JSON line per checkpoint, in timestep order, best_model.zip last.
+
+    python tools/evaluate_checkpoints.py DIR [--dtype float64|float32] [--episodes 100]
+"""
+import argparse
+import glob
+import json
+import os
+import random
+import re
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import gym_acas2d_amd as g  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("dir")
+ap.add_argument("--dtype", choices=("float64", "float32"), default="float64")
+ap.add_argument("--episodes", type=int, default=100)
+args = ap.parse_args()
+
+steps_of = lambda p: int(re.search(r"model_(\d+)_steps\.zip$", p).group(1))  # noqa: E731
+ckpts = sorted({p for d in (args.dir, os.path.join(args.dir, "checkpoints"))
+                for p in glob.glob(os.path.join(d, "model_*_steps.zip"))}, key=steps_of)
+best = os.path.join(args.dir, "best_model.zip")
+paths = ckpts + ([best] if os.path.exists(best) else [])
+if not paths:
+    sys.exit("no model_*_steps.zip or best_model.zip under %s" % args.dir)
+
+own, trf, goal = g.reset_parity.draw_episodes(g.ACAS2DConfig(), args.episodes, random.Random(13))
+out = g.evaluate_policies_fused(paths, own, trf, goal, dtype=getattr(torch, args.dtype))
+for k, p in enumerate(paths):
+    r, s, oc = out["total_reward"][k], out["steps"][k], out["outcome"][k]
+    print(json.dumps({"checkpoint": os.path.relpath(p, args.dir), "timesteps": steps_of(p) if p != best else None,
+                      "mean_return": float(r.mean()), "std_return": float(r.std()), "mean_steps": float(s.mean()),
+                      "goal": int((oc == 1).sum()), "collision": int((oc == 2).sum()), "timeout": int((oc == 3).sum()),
+                      "unfinished": int(out["unfinished"][k])}), flush=True)

@@ -15,7 +15,10 @@ SB3's own stream of random numbers is unpinned*: initial weights, action noise a
 other generators, and the evaluation episodes are drawn from the reference's reset distribution (reset_parity.py)
 by a stream of their own.  PPO on this task is seed-sensitive (the reference's own curve swings between 50 and 1200
 from one evaluation to the next), so what is compared is the SHAPE of the learning curve and the level it reaches:
---seeds runs several seeds.  One JSON line per evaluation, one summary line per seed.
+--seeds runs several seeds.  The evaluations are PPOTrainer.learn()'s own (eval_every / save_dir: EvalCallback's
+evaluations.npz and best_model.zip under --save-dir/seed_<s>); like the reference, which ships its BEST checkpoint, the
+summary scores best_model.zip on the reference's 100 test episodes (testing_main.py) next to the reference policy's
+1 210.07 / 100 goals.  One JSON line per evaluation, one summary line per seed.
 
     python tools/replay_reference_recipe.py [--seeds 13 14 15] [--envs 1] [--out profiles/r03_recipe.jsonl]
 """
@@ -24,6 +27,7 @@ import json
 import os
 import random
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -42,6 +46,8 @@ ap.add_argument("--eval-episodes", type=int, default=10)          # settings.py:
 ap.add_argument("--collector", default="fused")
 ap.add_argument("--updater", default="fused")
 ap.add_argument("--out", default=None)
+ap.add_argument("--save-dir", default=None, help="keep evaluations.npz / best_model.zip per seed here (default: a temporary "
+                                                 "directory)")
 args = ap.parse_args()
 
 ref = np.load(os.path.join(ROOT, "tests", "golden", "ref_training_evaluations.npz"))
@@ -57,44 +63,47 @@ def emit(rec):
         sink.flush()
 
 
-def evaluate(policy, rng, n):
-    """EvalCallback: n deterministic episodes on fresh draws of the reference's reset distribution (game.py:80-116)."""
-    own, trf, goal = g.reset_parity.draw_episodes(g.ACAS2DConfig(), n, rng)
-    out = g.evaluate_policy_fused(policy, own, trf, goal, dtype=torch.float32)
-    return out["total_reward"], out["steps"] - 1, out["outcome"]
-
-
 emit({"recipe": "training_main.py:28-52", "config": "PPOConfig.sb3(): n_steps 2048, batch 64, 10 epochs, gamma 0.99, lambda 0.95, "
       "clip 0.2, lr 3e-4, ent 0, vf 0.5, max_grad_norm 0.5", "envs": args.envs, "timesteps": args.timesteps,
       "eval_every": args.eval_every, "eval_episodes": args.eval_episodes, "collector": args.collector, "updater": args.updater,
       "parity": "unpinned (SB3 1.1.0 is not in the reference tree nor in this image: its PPO is restated, its random streams are not)",
       "reference_final_eval": {"mean_reward": 1198.22, "std": 85.34, "mean_ep_length": 771.6,
                                "source": "models/logs/training_ACAS2D_PPO_1048576_11.txt:13001-13002"}})
+test_eps = g.reset_parity.draw_episodes(g.ACAS2DConfig(), 100, random.Random(13))   # testing_main.py
 for seed in args.seeds:
     venv = g.ACAS2DVecEnv(args.envs, 1, device="cuda:0", dtype=torch.float32, seed=seed)
     trainer = g.PPOTrainer(venv, g.PPOConfig.sb3(seed=seed), collector=args.collector, updater=args.updater)
-    eval_rng = random.Random(1000 + seed)
-    t0, next_eval, evals = time.time(), args.eval_every, []
+    save_dir = os.path.join(args.save_dir, "seed_%d" % seed) if args.save_dir else tempfile.mkdtemp(prefix="recipe_")
+    t0, evals, last = time.time(), [], {}
 
     def log(rec):
-        global next_eval
-        while rec["timesteps"] >= next_eval and next_eval <= args.timesteps:
-            r, l, oc = evaluate(trainer.policy, eval_rng, args.eval_episodes)
-            rr = ref_at.get(next_eval)
-            ev = {"seed": seed, "eval_at": next_eval, "mean_reward": float(r.mean()), "std_reward": float(r.std()),
-                  "mean_ep_length": float(l.mean()), "goal": int((oc == 1).sum()), "collision": int((oc == 2).sum()),
-                  "timeout": int((oc == 3).sum()), "train_ep_rew_mean": rec.get("ep_rew_mean"), "std": rec.get("std"),
-                  "reference_mean_reward": rr[0] if rr else None, "reference_mean_ep_length": rr[2] if rr else None,
-                  "wall_s": time.time() - t0}
-            evals.append(ev)
-            emit(ev)
-            next_eval += args.eval_every
+        if not rec.get("eval"):
+            last.update(rec)
+            return
+        rr = ref_at.get(rec["timesteps"])
+        ev = {"seed": seed, "eval_at": rec["timesteps"], "mean_reward": rec["mean_reward"], "std_reward": rec["std_reward"],
+              "mean_ep_length": rec["mean_ep_length"], "goal": round(rec["goal"] * args.eval_episodes),
+              "collision": round(rec["collision"] * args.eval_episodes), "timeout": round(rec["timeout"] * args.eval_episodes),
+              "new_best": rec["new_best"], "train_ep_rew_mean": last.get("ep_rew_mean"), "std": last.get("std"),
+              "reference_mean_reward": rr[0] if rr else None, "reference_mean_ep_length": rr[2] if rr else None,
+              "wall_s": time.time() - t0}
+        evals.append(ev)
+        emit(ev)
 
-    trainer.learn(args.timesteps, log=log)
+    trainer.learn(args.timesteps, log=log, eval_every=args.eval_every, eval_episodes=args.eval_episodes,
+                  eval_seed=1000 + seed, save_dir=save_dir)
+    wall = time.time() - t0
+    best = g.evaluate_policies_fused([os.path.join(save_dir, "best_model.zip")], *test_eps)     # float64, as testing_main.py
     last4 = evals[-4:]
-    emit({"seed": seed, "summary": True, "wall_s": time.time() - t0, "steps_per_s": args.timesteps / (time.time() - t0),
+    emit({"seed": seed, "summary": True, "wall_s": wall, "steps_per_s": args.timesteps / wall,
           "final_eval_mean_reward": evals[-1]["mean_reward"], "final_eval_goals": evals[-1]["goal"],
           "mean_of_last_4_evals": float(np.mean([e["mean_reward"] for e in last4])),
-          "best_eval": max(e["mean_reward"] for e in evals),
+          "best_eval": max(e["mean_reward"] for e in evals), "save_dir": save_dir,
+          "best_model_100_test_episodes": {"mean_return": float(best["total_reward"][0].mean()),
+                                           "mean_steps": float(best["steps"][0].mean()),
+                                           "goal": int((best["outcome"][0] == 1).sum()),
+                                           "collision": int((best["outcome"][0] == 2).sum()),
+                                           "timeout": int((best["outcome"][0] == 3).sum())},
           "reference": {"final_eval": 1198.22, "mean_of_last_4_evals": float(ref["results"][-4:].mean()),
-                        "best_eval": float(ref["results"].mean(1).max()), "wall_s": 14688.0, "steps_per_s": 71.0}})
+                        "best_eval": float(ref["results"].mean(1).max()), "wall_s": 14688.0, "steps_per_s": 71.0,
+                        "best_model_100_test_episodes": {"mean_return": 1210.07, "goal": 100}}})
