@@ -240,16 +240,18 @@ def oracle_config(O, cfg):
     return oc
 
 
-def f32_oracle_steps(O, E, N, T, seed=13, env_offset=0, warmup=None, config=None):
+def f32_oracle_steps(O, E, N, T, seed=13, env_offset=0, warmup=None, config=None, episode=None):
     """The oracle side of a float32-vs-oracle window: a free-running float64 oracle trajectory `ref` with auto-reset and
     actions from default_rng(7), `warmup` steps first (None: 3 at N = 64, where episodes last ~8 steps, else 15..29 drawn
     from the same stream), then T steps.  For each of those it yields (t, own, trf, steps, episode, act, chk, stepped):
     ref's state rounded to float32 (the state both sides start the step from), the float32-representable action, and the
     oracle `chk` stepped once from that state -- stepped = chk.step()'s (o, r, d, oc).  `config`: an OracleConfig, None
-    for the default one."""
+    for the default one; `episode`: the episode counters [E] after reset() (None: 0)."""
     f32 = lambda a: a.astype(np.float32).astype(np.float64)  # noqa: E731
     ref = O.OracleEnvs(E, N, seed=seed, env_offset=env_offset, auto_reset=True, config=config)
     ref.reset()
+    if episode is not None:
+        ref.episode[:] = episode
     rng = np.random.default_rng(7)
     if warmup is None:
         warmup = 3 if N == 64 else int(rng.integers(15, 30))
@@ -322,3 +324,48 @@ def nondefault_outcomes(name, N):
     if name == "wide":
         return {TIMEOUT} if N == 1 else {COLLISION, TIMEOUT}
     return {GOAL, COLLISION, TIMEOUT} if N <= 16 else {GOAL, COLLISION} if N <= 33 else {COLLISION}
+
+
+# ---- wide reset keys --------------------------------------------------------------------------------------------------
+# Every episode is the Philox4x32-7 block of counter (global env index lo, hi, episode, entity) under key (seed lo, hi).
+# These keys make every one of those words matter: a seed whose halves are non-zero and distinct, an env_offset that puts
+# the 2^32 crossing of the global env index inside a wave (and so inside a workgroup) of WIDE_E envs -- "mid" -- or in
+# the last, partial wave of the shapes with >= 16 envs per wave -- "tail" --, and episode counters at 2^32 - 2 on the
+# even envs (WIDE_PRESET), so that their second reset wraps the counter to 0.  tests/test_host.py holds every shape of
+# SHAPES to these claims; the GPU tests of tests/test_gpu_parity.py run at these keys.
+WIDE_SEED = 0x9E3779B97F4A7C15
+WIDE_E = 1001
+WIDE_CROSSING = dict(mid=501, tail=999)            # the local env whose global index is 2^32
+WIDE_OFFSET = {k: 2 ** 32 - c for k, c in WIDE_CROSSING.items()}
+WIDE_EPISODE = 2 ** 32 - 2
+
+
+def wide_preset(E):
+    """The envs whose episode counter starts at WIDE_EPISODE: the even ones (every wave holds both kinds)."""
+    return np.arange(E) % 2 == 0
+
+
+def wide_crossing_offset(E, wave):
+    """An env_offset for a launch of E envs in waves of `wave` envs: the 2^32 crossing at the middle wave's lane
+    max(1, wave / 2 - 1) -- inside it unless a wave holds one env (then at its lane 0)."""
+    return 2 ** 32 - ((E // wave) // 2 * wave + (max(1, wave // 2 - 1) if wave > 1 else 0))
+
+
+def wide_f32_window(N):
+    """(oracle warm-up steps, checked steps) of the float32 wide-key windows (max_steps = 40): wraps of the preset
+    counters happen inside them -- at the first collisions of crowded airspaces, at the second timeout (step 80) of one
+    aircraft, at the first timeouts (step 40, the collisions before it took the first reset) of a few."""
+    return (75, 8) if N == 1 else (36, 8) if N <= 5 else (0, 8)
+
+
+# ---- 32-bit offset limits ---------------------------------------------------------------------------------------------
+# The float32 "arena" step kernel addresses its state through 32-bit byte offsets (acas2d_launch.inl arena_layout):
+# it takes E envs x N traffic only while 8 E N < 2^32 (the [2][E][N] traffic blocks) and 20 E < 2^32 (the [5][E] block).
+# (N, largest admitted E, first rejected whole-workgroup E) at the bound -- N = 2: the 20 E term binds.
+ARENA_BOUND = ((8, 67107840, 67108864), (64, 8388480, 8388608), (2, 214747136, 214749184))
+
+
+def obs_row_crossing(D, elem):
+    """The env whose observation row [E][D] of `elem`-byte elements straddles byte 2^32."""
+    return (2 ** 32) // (D * elem)
+

@@ -1142,21 +1142,26 @@ def _print_f32_totals(what, tot):
              "bit-equal" if b["speed"] is None else "%.2e (bound %.2e)" % (tot["e_speed"], b["speed"])))
 
 
-def _f32_steps_vs_oracle(g, O, E, N, T, seed=13, env_offset=0, config=None, warmup=None):
+def _f32_steps_vs_oracle(g, O, E, N, T, seed=13, env_offset=0, config=None, warmup=None, episode0=None):
     """T float32 steps WITH auto-reset, each from the oracle trajectory's state rounded to float32 (so that both sides
     start every step from the identical state and the comparison is the step's, not the accumulated drift's), checked
     by _check_f32_step_vs_oracle.  config: ACAS2DConfig keywords other than n_traffic (None: the default configuration);
-    warmup: oracle steps before the first checked one (helpers.f32_oracle_steps).  Returns the totals."""
+    warmup: oracle steps before the first checked one (helpers.f32_oracle_steps); episode0: the episode counters after
+    reset() (None: 0).  Returns the totals; "wrapped" counts the envs whose reset in a checked step wrapped the counter
+    to 0."""
     cfg = g.ACAS2DConfig(n_traffic=N, **(config or {}))
     ocfg = None if config is None else _oracle_config_from(O, cfg)
     env = _engine(g.ACAS2DVecEnv(E, device="cuda:0", dtype=torch.float32, auto_reset=True, seed=seed,
                                  env_offset=env_offset, config=cfg))
     tot = _new_f32_totals()
-    for t, own, trf, steps, episode, act, chk, stepped in H.f32_oracle_steps(O, E, N, T, seed, env_offset, warmup, ocfg):
+    tot["wrapped"] = 0
+    for t, own, trf, steps, episode, act, chk, stepped in H.f32_oracle_steps(O, E, N, T, seed, env_offset, warmup, ocfg,
+                                                                             episode0):
         env.set_state(own, trf, None, steps)
         env.v.episode.copy_(torch.as_tensor(episode.view(np.int32), device="cuda:0"))
         obs, rew, done, outcome, _ = env.step(act)
         _check_f32_step_vs_oracle(env, chk, stepped, (obs, rew, done, outcome), N, tot, t)
+        tot["wrapped"] += int(((done != 0) & (env.episode == 0)).sum())
     tot["speeds"] = len(np.unique(env.trf_v))
     if config is None:       # the default configuration's windows stay below 2048 px: the fixed 1.3e-4
         assert tot["pos_bound"] == 1.3e-4, tot["pos_bound"]
@@ -1374,12 +1379,17 @@ def test_every_packed_shape_rollout_equals_steps(g, monkeypatch, shape):
     _rollout_equals_steps(g, monkeypatch, shape, _SHORT)
 
 
-def _rollout_equals_steps(g, monkeypatch, shape, config):
+def _rollout_equals_steps(g, monkeypatch, shape, config, **keys):
+    """keys: seed / env_offset of both envs (_shape_env's by default) and `episode0`, the episode counters after reset()."""
     _use_shape(g, monkeypatch, shape)
     E, T = 1001, 90
-    a = _shape_env(g, shape, E, config=config)
-    b = _shape_env(g, shape, E, config=config, double_buffer=False)
+    episode0 = keys.pop("episode0", None)
+    a = _shape_env(g, shape, E, config=config, **keys)
+    b = _shape_env(g, shape, E, config=config, double_buffer=False, **keys)
     assert bits_equal(a.reset(), b.reset())
+    if episode0 is not None:
+        for v in (a, b):
+            v.episode.copy_(torch.as_tensor(episode0.view(np.int32), device="cuda:0"))
     gen = torch.Generator(device="cuda:0").manual_seed(3)
     actions = torch.rand(T, E, generator=gen, device="cuda:0", dtype=a.dtype) * 2 - 1
     out = a.rollout(actions, keep_terminal_obs=True)
@@ -1395,6 +1405,8 @@ def _rollout_equals_steps(g, monkeypatch, shape, config):
                 assert bits_equal(out[k][t][done], want[done]), (t, k)
     assert dones >= E
     _same_state(a, b)
+    if episode0 is not None:                               # preset counters wrapped inside the window
+        assert int((a.episode[torch.as_tensor(episode0 != 0, device="cuda:0")] >= 0).sum()) >= 50
 
 
 @pytest.mark.parametrize("shape", H.SHAPES, ids=_ids(H.SHAPES))
@@ -1598,10 +1610,13 @@ def _wave_variants(shape):
 _WAVE_CASES = [c for s in H.SHAPES for c in _wave_variants(s)]
 # injected own_v / goal other than the configuration's: the reset must write the configuration's back
 _CONSTS_CASES = [(s, "consts") for s in H.SHAPES if s.override is None and s.n_traffic in (5, 8, 64)]
+# at the wide reset keys (helpers.WIDE_SEED, the 2^32 crossing of the global env index inside the middle wave, which
+# finishes whole; episode counters at 2^32 - 2 .. 2): the in-place step (float32: both kernels) and the rollout
+_WIDE_WAVE_CASES = [(s, "wide-" + v) for s, v in _WAVE_CASES if not v.startswith("double")]
 
 
-@pytest.mark.parametrize("shape,variant", _WAVE_CASES + _CONSTS_CASES,
-                         ids=["%s-%s" % (s.id, v) for s, v in _WAVE_CASES + _CONSTS_CASES])
+@pytest.mark.parametrize("shape,variant", _WAVE_CASES + _CONSTS_CASES + _WIDE_WAVE_CASES,
+                         ids=["%s-%s" % (s.id, v) for s, v in _WAVE_CASES + _CONSTS_CASES + _WIDE_WAVE_CASES])
 def test_waves_finishing_together_vs_oracle(g, O, monkeypatch, shape, variant):
     """The in-step reset takes a wave's finished envs SLOTS at a time (a packed shape with N + 1 <= 32: SLOTS = 64 /
     the power of two >= max(2, N + 1), geometry_for() / ResetSlots; otherwise one per pass).  A step where a chosen
@@ -1611,7 +1626,11 @@ def test_waves_finishing_together_vs_oracle(g, O, monkeypatch, shape, variant):
     (1e-9, masks and reset states bit for bit) or the float32 ones (_check_f32_step_vs_oracle): the terminal
     observation, return and length, the fresh episode and its first observation, and the untouched envs -- for the
     step kernel in place and double-buffered (float32: the arena kernel and the general one) and for rollout().
-    "consts": the injected states fly at own_v = 190 towards goal (1400, 520); the reset restores 200 / (1456, 500)."""
+    "consts": the injected states fly at own_v = 190 towards goal (1400, 520); the reset restores 200 / (1456, 500).
+    "wide-*": at helpers.WIDE_SEED, the global env index crossing 2^32 inside the middle wave, whose envs all finish,
+    and episode counters 2^32 - 2 .. 2 (the resets from 2^32 - 1 wrap to 0)."""
+    wide = variant.startswith("wide-")
+    variant = variant[5:] if wide else variant
     f32 = shape.dtype == "float32"
     wave = shape.envs_per_wave
     E, N = 32 * wave, shape.n_traffic                          # a whole multiple of eight workgroups (the arena kernel)
@@ -1646,16 +1665,23 @@ def test_waves_finishing_together_vs_oracle(g, O, monkeypatch, shape, variant):
     for w in range(E // wave):
         k = counts[(w + len(counts) // 2) % len(counts)]          # every count, at different waves
         chosen[w * wave + rng.choice(wave, k, replace=False)] = True
+    seed, off = 21, 37
+    if wide:
+        seed, off = H.WIDE_SEED, H.wide_crossing_offset(E, wave)
+        w = (2 ** 32 - off) // wave
+        chosen[w * wave:(w + 1) * wave] = True
     steps[chosen] = cfgc.max_steps
     episode = rng.integers(0, 5, E).astype(np.uint32)
-    chk = O.OracleEnvs(E, N, seed=21, env_offset=37, auto_reset=True, config=cfgc)
+    if wide:
+        episode = ((episode.astype(np.int64) + H.WIDE_EPISODE) % 2 ** 32).astype(np.uint32)
+    chk = O.OracleEnvs(E, N, seed=seed, env_offset=off, auto_reset=True, config=cfgc)
     chk.set_state(own, trf, goal, steps)
     chk.episode[:] = episode
     o, r, d, oc, _ = chk.step(act)
     assert np.array_equal(oc == 3, chosen) and np.array_equal(d != 0, chosen)      # the setup: exactly the chosen envs
     # ---- the engine
     kind = variant.split("-")[0]
-    v = g.ACAS2DVecEnv(E, device="cuda:0", dtype=getattr(torch, shape.dtype), seed=21, env_offset=37, config=cfg,
+    v = g.ACAS2DVecEnv(E, device="cuda:0", dtype=getattr(torch, shape.dtype), seed=seed, env_offset=off, config=cfg,
                        double_buffer=(kind == "double"))
     if variant.endswith("general"):
         monkeypatch.setenv("ACAS2D_NO_ARENA", "1")
@@ -1673,7 +1699,18 @@ def test_waves_finishing_together_vs_oracle(g, O, monkeypatch, shape, variant):
         v.step(a)
         got = {k: env._np(t) for k, t in v.outputs.items()}
     monkeypatch.delenv("ACAS2D_NO_ARENA", raising=False)
-    snap = types.SimpleNamespace(**{n: getattr(env, n) for n in _STATE + ("steps", "total_reward", "episode")})
+    if wide and variant == "inplace-arena":                 # the arena kernel == the general one, bit for bit
+        twin = g.ACAS2DVecEnv(E, device="cuda:0", dtype=v.dtype, seed=seed, env_offset=off, config=cfg, double_buffer=False)
+        twin.set_state(own, trf, goal, steps, observe=False)
+        twin.episode.copy_(torch.as_tensor(episode.view(np.int32), device="cuda:0"))
+        monkeypatch.setenv("ACAS2D_NO_ARENA", "1")
+        assert not twin.consecutive_layout
+        twin.step(a)
+        monkeypatch.delenv("ACAS2D_NO_ARENA")
+        for k in v.outputs:
+            assert bits_equal(v.outputs[k], twin.outputs[k]), k
+        _same_state(v, twin, _STATE + ("steps", "total_reward", "episode", "status"))
+    snap =types.SimpleNamespace(**{n: getattr(env, n) for n in _STATE + ("steps", "total_reward", "episode")})
     snap.term_obs, snap.ep_return, snap.ep_steps = got["terminal_observation"], got["episode_return"], got["episode_steps"]
     obs, rew, done, outcome = got["obs"], got["reward"], got["done"].astype(np.uint8), got["outcome"]
     print("%s %s: %d envs, %d finish (per wave: %s; SLOTS %d)" % (shape.id, variant, E, chosen.sum(), counts,
@@ -1709,6 +1746,8 @@ def test_waves_finishing_together_vs_oracle(g, O, monkeypatch, shape, variant):
     assert np.array_equal(snap.own_v[~chosen], own[~chosen, 3]) and np.array_equal(snap.goal_x[~chosen], goal[~chosen, 0])
     assert np.array_equal(snap.goal_y[~chosen], goal[~chosen, 1])
     assert np.array_equal(snap.episode, (episode + chosen).astype(np.uint32))
+    if wide:
+        assert ((snap.episode == 0) & chosen).sum() >= (2 if wave >= 4 else 0) and (off + E) >> 32 == 1
 
 
 # ---- the headline configuration as bench.py measures it ------------------------------------------------------------
@@ -1781,3 +1820,373 @@ def test_arena_kernel_in_place_at_the_per_rank_shard_size(g, monkeypatch):
         dones += int(da.sum())
     _same_state(a, b, _STATE + ("steps", "total_reward", "episode", "status"))
     assert dones > 1000
+
+
+# ---- wide reset keys (helpers.WIDE_*) ---------------------------------------------------------------------------------
+# Every episode is the Philox block of counter (global env index lo, hi, episode, entity) under key (seed lo, hi).  With
+# small seeds, offsets and counters the high words are all 0, and a kernel that dropped one -- or added a lane's env to
+# its wave's first global index in 32 bits -- would pass every test above.  These run at a seed whose halves differ, the
+# 2^32 crossing of the global index inside a wave, and counters that wrap through 2^32 - 1 to 0.
+# Both formulations share the reset code and the launchers: every row auto-resets at the "mid" keys; the "tail" keys and
+# the latching step (whose draws are reset()'s) run in the reference formulation's rows.
+_F64_EXACT = [s for s in _F64 if s.math == "exact"]
+_WIDE_F64_CASES = [(s, True, "mid") for s in _F64] + [(s, True, "tail") for s in _F64_EXACT] + \
+                  [(s, False, "mid") for s in _F64_EXACT]
+_WIDE_MASKED_CASES = [(s, "mid") for s in _F64] + [(s, "tail") for s in _F64_EXACT]
+
+
+def _wide_episode0(E):
+    return np.where(H.wide_preset(E), H.WIDE_EPISODE, 0).astype(np.uint32)
+
+
+@pytest.mark.parametrize("shape,auto_reset,key", _WIDE_F64_CASES,
+                         ids=["%s-%s-%s" % (s.id, "auto_reset" if ar else "latching", k) for s, ar, k in _WIDE_F64_CASES])
+def test_every_f64_shape_at_wide_keys_vs_oracle(g, O, monkeypatch, shape, auto_reset, key):
+    """test_every_f64_shape_vs_oracle at the wide keys: reset() bit for bit, then the even envs' counters set to
+    2^32 - 2 and 90 steps of max_steps 40, so that their second reset wraps the counter to 0 (auto-reset; latching: the
+    reset() draws, then the latching step).  Fresh episodes bit for bit, observations 1e-9, episode counters equal."""
+    _use_shape(g, monkeypatch, shape)
+    E, N, T, off = H.WIDE_E, shape.n_traffic, 90, H.WIDE_OFFSET[key]
+    v = _shape_env(g, shape, E, seed=H.WIDE_SEED, env_offset=off, auto_reset=auto_reset, config=_SHORT)
+    ref = O.OracleEnvs(E, N, seed=H.WIDE_SEED, env_offset=off, auto_reset=auto_reset, config=_oracle_config_from(O, v.config))
+    env = _engine(v)
+    o_ref, o_gpu = ref.reset(), env.reset()
+    for name in _STATE:
+        assert np.array_equal(getattr(env, name), getattr(ref, name)), name
+    np.testing.assert_allclose(o_gpu, o_ref, rtol=0, atol=1e-9)
+    ref.episode[:] = _wide_episode0(E)
+    v.episode.copy_(torch.as_tensor(ref.episode.view(np.int32), device="cuda:0"))
+    rng = np.random.default_rng(1)
+    wrapped = 0
+    for t in range(T):
+        a = rng.uniform(-1, 1, E)
+        o1, r1, d1, oc1, _ = ref.step(a)
+        o2, r2, d2, oc2, _ = env.step(a)
+        assert np.array_equal(d1, d2) and np.array_equal(oc1, oc2), t
+        np.testing.assert_allclose(o2, o1, rtol=0, atol=1e-9, equal_nan=True)
+        np.testing.assert_allclose(r2, r1, rtol=0, atol=1e-9, equal_nan=True)
+        assert np.array_equal(env.steps, ref.steps) and np.array_equal(env.episode, ref.episode), t
+        d = d1.astype(bool)
+        if auto_reset and d.any():
+            wrapped += int((d & (ref.episode == 0)).sum())
+            np.testing.assert_allclose(env.term_obs[d], ref.term_obs[d], rtol=0, atol=1e-9, equal_nan=True)
+            for name in _STATE:
+                assert np.array_equal(getattr(env, name)[d], getattr(ref, name)[d]), (t, name)
+        if not auto_reset:
+            assert np.array_equal(env.status, ref.status), t
+    if auto_reset:
+        print("%s at %s keys: %d resets wrapped the episode counter" % (shape.id, key, wrapped))
+        assert wrapped >= 50
+    else:
+        assert (ref.status != 0).all()
+
+
+@pytest.mark.parametrize("shape,key", _WIDE_MASKED_CASES, ids=["%s-%s" % (s.id, k) for s, k in _WIDE_MASKED_CASES])
+def test_every_f64_shape_reset_masked_at_wide_keys_vs_oracle(g, O, monkeypatch, shape, key):
+    """reset_masked() at the wide keys: three masked resets, the first two covering every even env (counters preset to
+    2^32 - 2: the second wraps them to 0); re-drawn envs bit for bit, first observations 1e-9, the rest untouched."""
+    _use_shape(g, monkeypatch, shape)
+    E, N, off = H.WIDE_E, shape.n_traffic, H.WIDE_OFFSET[key]
+    v = _shape_env(g, shape, E, seed=H.WIDE_SEED, env_offset=off)
+    ref = O.OracleEnvs(E, N, seed=H.WIDE_SEED, env_offset=off, auto_reset=True)
+    env = _engine(v)
+    ref.reset()
+    env.reset()
+    pre = H.wide_preset(E)
+    ref.episode[:] = _wide_episode0(E)
+    v.episode.copy_(torch.as_tensor(ref.episode.view(np.int32), device="cuda:0"))
+    rng = np.random.default_rng(6)
+    for k, frac in enumerate((0.5, 0.2, 0.9)):
+        mask = (rng.random(E) < frac) | (pre if k < 2 else False)
+        before = {name: getattr(env, name).copy() for name in _STATE + ("steps",)}
+        obs = env._np(v.reset_masked(torch.as_tensor(mask, device="cuda:0")))
+        ref.episode[mask] += np.uint32(1)
+        ref.reset_philox(mask.astype(np.uint8))
+        for name in _STATE:
+            got = getattr(env, name)
+            assert np.array_equal(got[mask], getattr(ref, name)[mask]), (k, name)
+            assert np.array_equal(got[~mask], before[name][~mask]), (k, name)
+        assert np.array_equal(env.episode, ref.episode), k
+        o_ref = ref.observe()
+        np.testing.assert_allclose(obs[mask], o_ref[mask], rtol=0, atol=1e-9)
+        ref.steps[~mask] = before["steps"][~mask]
+        if k == 1:
+            assert (env.episode[pre] == 0).all()
+
+
+@pytest.mark.parametrize("key", tuple(H.WIDE_OFFSET))
+@pytest.mark.parametrize("shape", _F32_SHAPES, ids=_ids(_F32_SHAPES))
+def test_every_f32_shape_at_wide_keys_vs_f64_oracle(g, O, monkeypatch, shape, key):
+    """Every float32 work shape at the wide keys against the float64 oracle (_f32_steps_vs_oracle, max_steps 40), in the
+    window of helpers.wide_f32_window where resets wrap the preset counters: the fresh episodes within the float32
+    bounds, the counters equal."""
+    _use_shape(g, monkeypatch, shape)
+    warmup, T = H.wide_f32_window(shape.n_traffic)
+    tot = _f32_steps_vs_oracle(g, O, H.WIDE_E, shape.n_traffic, T, seed=H.WIDE_SEED, env_offset=H.WIDE_OFFSET[key],
+                               config=_SHORT, warmup=warmup, episode0=_wide_episode0(H.WIDE_E))
+    _print_f32_totals("at %s keys on %s, %d envs x %d steps after %d" % (key, shape.id, H.WIDE_E, T, warmup), tot)
+    assert tot["finished"] > 0 and tot["wrapped"] >= 5, tot["wrapped"]
+
+
+def test_f32_reset_names_the_same_episodes_at_wide_keys(g, O):
+    """test_f32_reset_names_the_same_episodes at the wide keys (4096 envs x 8, the 2^32 crossing at env 2049, the even
+    envs' counters at 2^32 - 2, max_steps 40 so that they wrap within 85 steps): reset() and the in-step reset within the
+    float32 reset bounds of the oracle's draws, and reset_kernel on a twin bit for bit what the step drew."""
+    E, N, T, off = 4096, 8, 85, 2 ** 32 - 2049
+    cfg = g.ACAS2DConfig(n_traffic=N, **_SHORT)
+    ref = O.OracleEnvs(E, N, seed=H.WIDE_SEED, env_offset=off, auto_reset=True, config=_oracle_config_from(O, cfg))
+    bnd = H.f32_bounds(ref.cfg, _default_oracle_config())
+    worst = dict(pos=0.0, psi=0.0)
+
+    def close_to_oracle(env, sel):
+        e = max(np.abs(env.trf_x[sel] - ref.trf_x[sel]).max(), np.abs(env.trf_y[sel] - ref.trf_y[sel]).max())
+        worst["pos"] = max(worst["pos"], float(e))
+        assert e < bnd["reset_pos"], e
+        for k in ("trf_psi", "own_psi"):
+            dpsi = np.abs(getattr(env, k)[sel] - getattr(ref, k)[sel])
+            worst["psi"] = max(worst["psi"], float(np.minimum(dpsi, 360 - dpsi).max()))
+            assert np.minimum(dpsi, 360 - dpsi).max() < bnd["reset_psi"], k
+        assert np.array_equal(env.trf_v[sel], ref.trf_v[sel])
+
+    kw = dict(device="cuda:0", dtype=torch.float32, auto_reset=True, seed=H.WIDE_SEED, env_offset=off, config=cfg)
+    ref.reset()
+    env = _engine(g.ACAS2DVecEnv(E, **kw))
+    env.reset()
+    close_to_oracle(env, np.ones(E, bool))
+    ref.episode[:] = _wide_episode0(E)
+    env.v.episode.copy_(torch.as_tensor(ref.episode.view(np.int32), device="cuda:0"))
+    rng = np.random.default_rng(3)
+    checked = wrapped = 0
+    twin = g.ACAS2DVecEnv(E, **kw)
+    for _ in range(T):
+        a = rng.uniform(-1, 1, E).astype(np.float32).astype(np.float64)
+        _, _, d1, _, _ = ref.step(a)
+        _, _, d2, _, _ = env.step(a)
+        both = (d1 != 0) & (d2 != 0) & (env.episode == ref.episode)
+        if both.any():
+            checked += int(both.sum())
+            wrapped += int((both & (ref.episode == 0)).sum())
+            close_to_oracle(env, both)
+        fresh = torch.as_tensor(d2 != 0, device="cuda:0")
+        if fresh.any():
+            twin.episode.copy_(env.v.episode)
+            twin._launch_reset(fresh.to(torch.uint8), do_init=1)
+            for k in _STATE:
+                assert torch.equal(getattr(twin, k)[fresh], getattr(env.v, k)[fresh]), k
+            assert bits_equal(twin.outputs["obs"][fresh], env.v.outputs["obs"][fresh])
+    print("f32 reset draws at wide keys: %d in-step resets checked (%d wrapped the counter); worst positions %.2e (bound "
+          "%.2e), headings %.2e (bound %.0e)" % (checked, wrapped, worst["pos"], bnd["reset_pos"], worst["psi"],
+                                                 bnd["reset_psi"]))
+    assert checked > 500 and wrapped > 50
+
+
+@pytest.mark.parametrize("shape", _PACKED, ids=_ids(_PACKED))
+def test_every_packed_shape_rollout_equals_steps_at_wide_keys(g, monkeypatch, shape):
+    """test_every_packed_shape_rollout_equals_steps at the wide keys ("mid" crossing, the even envs' counters at
+    2^32 - 2: their second reset inside the 90 steps wraps them)."""
+    _rollout_equals_steps(g, monkeypatch, shape, _SHORT, seed=H.WIDE_SEED, env_offset=H.WIDE_OFFSET["mid"],
+                          episode0=_wide_episode0(H.WIDE_E))
+
+
+# ---- 32-bit offset limits at scale ------------------------------------------------------------------------------------
+# The float32 arena kernel addresses its state through 32-bit byte offsets and is admitted up to helpers.ARENA_BOUND;
+# observation rows [E][D] and rollout outputs [T][E][D] pass 2^32 bytes and 2^31 elements at ordinary sizes.  These run
+# there.  Device memory is checked first: a card without room skips, naming the bytes needed.
+def _env_bytes(E, N, elem, term_obs=True, generations=1):
+    """Device bytes of one ACAS2DVecEnv: state (`generations` of the per-step arrays), status, actions, step outputs."""
+    D = 5 + 3 * N
+    per_step = elem * (4 + 2 * N) + 4                     # own_x, own_y, own_psi, total_reward, trf_x, trf_y; steps
+    return E * (generations * per_step + elem * (4 + 2 * N + 3 + D * (2 if term_obs else 1)) + 4 * 2 + 1 + 2)
+
+
+def _need_device_bytes(n):
+    torch.cuda.empty_cache()                              # (blocks an earlier test left in torch's cache count as free)
+    free, _ = torch.cuda.mem_get_info()
+    if free < n * 1.05:
+        pytest.skip("needs %d bytes of free device memory, %d free" % (n * 1.05, free))
+    torch.cuda.reset_peak_memory_stats()
+
+
+def _print_peak(what):
+    print("%s: peak device memory %.1f GB" % (what, torch.cuda.max_memory_allocated() / 1e9))
+
+
+def _window_state(v, lo, hi):
+    """The envs [lo, hi) of a float32 env as float64 numpy: what _check_f32_step_vs_oracle reads of its engine."""
+    f = lambda t: t[lo:hi].double().cpu().numpy() if t.is_floating_point() else t[lo:hi].cpu().numpy()  # noqa: E731
+    ns = types.SimpleNamespace(**{n: f(getattr(v, n)) for n in _STATE + ("steps", "total_reward")})
+    ns.episode = v.episode[lo:hi].cpu().numpy().view(np.uint32)
+    ns.term_obs = f(v.outputs["terminal_observation"])
+    ns.ep_return, ns.ep_steps = f(v.outputs["episode_return"]), f(v.outputs["episode_steps"])
+    return ns
+
+
+def _f32_window_step_vs_oracle(O, v, before, lo, act, tot, t):
+    """The float32 step just taken, over envs [lo, lo + len) of `v`, against the oracle stepped from `before` (their
+    state before it) with env_offset = lo: _check_f32_step_vs_oracle."""
+    n = len(before.steps)
+    chk = O.OracleEnvs(n, v.n_traffic, seed=v.seed_value, env_offset=v.env_offset + lo, auto_reset=True,
+                       config=_oracle_config_from(O, v.config))
+    chk.set_state(np.stack([before.own_x, before.own_y, before.own_psi, before.own_v], 1),
+                  np.stack([before.trf_x, before.trf_y, before.trf_psi, before.trf_v], -1),
+                  np.stack([before.goal_x, before.goal_y], 1), before.steps)
+    chk.total_reward[:] = before.total_reward
+    chk.episode[:] = before.episode
+    o, r, d, oc, _ = chk.step(act)
+    after = _window_state(v, lo, lo + n)
+    got = tuple(v.outputs[k][lo:lo + n].cpu().numpy() for k in ("obs", "reward", "done", "outcome"))
+    got = (got[0].astype(np.float64), got[1].astype(np.float64), got[2].astype(np.uint8), got[3])
+    _check_f32_step_vs_oracle(after, chk, (o, r, d, oc), got, v.n_traffic, tot, t)
+
+
+_ARENA_SCALE = [(N, e_yes, True) for N, e_yes, _ in H.ARENA_BOUND if N != 2] + [(H.ARENA_BOUND[0][0], H.ARENA_BOUND[0][2], False)]
+
+
+@pytest.mark.parametrize("N,E,admitted", _ARENA_SCALE, ids=["N%d-E%d" % (n, e) for n, e, _ in _ARENA_SCALE])
+def test_arena_kernel_at_its_32_bit_size_bound(g, O, monkeypatch, N, E, admitted):
+    """float32 at the arena kernel's largest admitted size (and, N = 8, the first rejected one, which takes the general
+    kernel): 24 steps from reset() with episodes of 20 steps.  Against the general kernel (ACAS2D_NO_ARENA), every
+    element of the state and the outputs bit for bit after every step: envs are independent and their episodes depend on
+    (seed, global index, counter) only, so a twin of E / 4 envs at env_offset = lo steps envs [lo, lo + E / 4) exactly as
+    the full launch does; the full env is re-run from reset() once per quarter, which keeps the two envs within ~36 GB.
+    Against the float64 oracle (_check_f32_step_vs_oracle), in the first pass, over windows of 4 096 envs -- the first,
+    those around the observation row that straddles byte 2^32, the last -- in every step."""
+    monkeypatch.delenv("ACAS2D_SHAPE", raising=False)
+    monkeypatch.delenv("ACAS2D_NO_ARENA", raising=False)
+    Q = E // 4
+    assert Q * 4 == E
+    _need_device_bytes(_env_bytes(E, N, 4) + _env_bytes(Q, N, 4) + 4 * E)
+    cfg = g.ACAS2DConfig(n_traffic=N, max_steps=20)
+    a = g.ACAS2DVecEnv(E, device="cuda:0", dtype=torch.float32, seed=13, config=cfg, double_buffer=False)
+    assert a.consecutive_layout == admitted
+    D, W, T = a.obs_dim, 4096, 24
+    cross = H.obs_row_crossing(D, 4)
+    assert cross + W // 2 < E and E * D * 4 > 2 ** 32
+    windows = (0, cross - W // 2, E - W)
+    tot = _new_f32_totals()
+    dones = 0
+    for lo in range(0, E, Q):
+        sl = slice(lo, lo + Q)
+        b = g.ACAS2DVecEnv(Q, device="cuda:0", dtype=torch.float32, seed=13, env_offset=lo, config=cfg,
+                           double_buffer=False)
+        assert bits_equal(a.reset()[sl], b.reset())
+        for k in ("terminal_observation", "episode_return", "episode_steps"):   # written where done only: start as b's
+            a.outputs[k].zero_()
+        gen = torch.Generator(device="cuda:0").manual_seed(12)
+        for t in range(T):
+            act = torch.rand(E, generator=gen, device="cuda:0") * 2 - 1
+            before = [_window_state(a, w, w + W) for w in windows] if lo == 0 else None
+            a.step(act)
+            monkeypatch.setenv("ACAS2D_NO_ARENA", "1")
+            assert not b.consecutive_layout
+            b.step(act[sl])
+            monkeypatch.delenv("ACAS2D_NO_ARENA")
+            for k in ("obs", "reward", "done", "outcome", "terminal_observation", "episode_return", "episode_steps"):
+                assert bits_equal(a.outputs[k][sl], b.outputs[k]), (lo, t, k)
+            for name in _STATE + ("steps", "total_reward", "episode", "status"):
+                assert bits_equal(getattr(a, name)[sl], getattr(b, name)), (lo, t, name)
+            dones += int(b.outputs["done"].sum())
+            if lo == 0:
+                for w, bf in zip(windows, before):
+                    _f32_window_step_vs_oracle(O, a, bf, w, act[w:w + W].double().cpu().numpy(), tot, t)
+        del b
+    _print_f32_totals("at %d x %d (%s kernel), 3 windows of %d envs over %d steps" %
+                      (E, N, "arena" if admitted else "general", W, T), tot)
+    _print_peak("arena bound %d x %d" % (E, N))
+    assert dones > E and tot["finished"] > 2 * W
+
+
+def test_f64_obs_past_4_gib_vs_oracle(g, O, monkeypatch):
+    """float64, 20 000 000 envs x 8 (observations [E][29] of 4.6 GB), 45 auto-reset steps of episodes of 20 steps from
+    reset(): the oracle over the 4 096 envs around the observation row that straddles byte 2^32 (env 18 512 790) and the
+    last 4 096 (the last wave), env_offset = the window's start -- drawn states bit for bit, observations and rewards
+    1e-9, masks and counters equal."""
+    monkeypatch.delenv("ACAS2D_SHAPE", raising=False)
+    E, N, T, W = 20_000_000, 8, 45, 4096
+    _need_device_bytes(_env_bytes(E, N, 8) + 8 * E)
+    cfg = g.ACAS2DConfig(n_traffic=N, max_steps=20)
+    v = g.ACAS2DVecEnv(E, device="cuda:0", dtype=torch.float64, seed=13, config=cfg, double_buffer=False)
+    cross = H.obs_row_crossing(v.obs_dim, 8)
+    assert cross == 18512790 and E * v.obs_dim * 8 > 2 ** 32
+    windows = (cross - W // 2, E - W)
+    refs = [O.OracleEnvs(W, N, seed=13, env_offset=lo, auto_reset=True, config=_oracle_config_from(O, cfg))
+            for lo in windows]
+    obs = v.reset()
+    for lo, ref in zip(windows, refs):
+        o = ref.reset()
+        np.testing.assert_allclose(obs[lo:lo + W].cpu().numpy(), o, rtol=0, atol=1e-9)
+    gen = torch.Generator(device="cuda:0").manual_seed(13)
+    dones = 0
+    for t in range(T):
+        act = torch.rand(E, generator=gen, device="cuda:0", dtype=torch.float64) * 2 - 1
+        obs, rew, done, _ = v.step(act)
+        for lo, ref in zip(windows, refs):
+            sl = slice(lo, lo + W)
+            o, r, d, oc, _ = ref.step(act[sl].cpu().numpy())
+            assert np.array_equal(done[sl].cpu().numpy(), d != 0) and np.array_equal(v.outputs["outcome"][sl].cpu().numpy(), oc), t
+            np.testing.assert_allclose(obs[sl].cpu().numpy(), o, rtol=0, atol=1e-9, equal_nan=True)
+            np.testing.assert_allclose(rew[sl].cpu().numpy(), r, rtol=0, atol=1e-9, equal_nan=True)
+            assert np.array_equal(v.steps[sl].cpu().numpy(), ref.steps) and np.array_equal(v.episode[sl].cpu().numpy().view(np.uint32), ref.episode)
+            fin = d != 0
+            dones += int(fin.sum())
+            for name in _STATE:                                     # the fresh episodes: bit for bit
+                assert np.array_equal(getattr(v, name)[sl].cpu().numpy()[fin], getattr(ref, name)[fin]), (t, name)
+            for name in ("own_x", "own_y", "own_psi", "trf_x", "trf_y"):
+                np.testing.assert_allclose(getattr(v, name)[sl].cpu().numpy(), getattr(ref, name), rtol=0, atol=1e-9)
+    _print_peak("float64 obs past 4 GiB")
+    assert dones > 2 * W
+
+
+@pytest.mark.parametrize("dtype_name", ("float32", "float64"))
+def test_rollout_outputs_past_2_to_the_31_elements_equal_steps(g, monkeypatch, dtype_name):
+    """rollout() of 65 536 envs x 8 over 1 200 steps: its [T][E][29] observations pass 2^32 bytes (float32: step 565)
+    and 2^31 elements (step 1 130); float32 also keeps the terminal observations.  Against a twin stepped 1 200 times,
+    bit for bit at every step -- compared on the device, no second [T][E][D] copy -- and in the final state."""
+    monkeypatch.delenv("ACAS2D_SHAPE", raising=False)
+    dtype = getattr(torch, dtype_name)
+    E, N, T = 65536, 8, 1200
+    elem = 4 if dtype == torch.float32 else 8
+    keep = dtype == torch.float32
+    D = 5 + 3 * N
+    _need_device_bytes(T * E * (D * elem * (2 if keep else 1) + elem * 3 + 6) + 2 * _env_bytes(E, N, elem, generations=2))
+    assert T * E * D >= 2 ** 31 and (2 ** 31) // (E * D) < T
+    a, b = (g.ACAS2DVecEnv(E, N, device="cuda:0", dtype=dtype, seed=13) for _ in range(2))
+    assert bits_equal(a.reset(), b.reset())
+    gen = torch.Generator(device="cuda:0").manual_seed(14)
+    actions = torch.rand(T, E, generator=gen, device="cuda:0", dtype=dtype) * 2 - 1
+    out = a.rollout(actions, keep_terminal_obs=keep)
+    dones = late = 0
+    for t in range(T):
+        obs, rew, done, infos = b.step(actions[t])
+        assert bits_equal(out["obs"][t], obs) and bits_equal(out["reward"][t], rew), t
+        assert torch.equal(out["done"][t], done) and torch.equal(out["outcome"][t], infos.outcome), t
+        assert bits_equal(out["episode_return"][t][done], infos.episode_return[done]), t
+        assert bits_equal(out["episode_steps"][t][done], infos.episode_steps[done]), t
+        if keep:
+            assert bits_equal(out["terminal_observation"][t][done], infos.terminal_observation[done]), t
+        n = int(done.sum())
+        dones += n
+        late += n if t * E * D >= 2 ** 31 else 0
+    _print_peak("rollout %s past 2^31 elements" % dtype_name)
+    assert late > 0 and dones > E
+    _same_state(a, b)
+
+
+def test_collector_outputs_past_2_to_the_31_elements_replay_on_a_twin(g, monkeypatch):
+    """collect() of 65 536 envs x 8 float32 over 1 200 steps ([T + 1][E][29] observations past 2^31 elements): a twin
+    stepped with its clipped actions reproduces every observation, reward and mask (helpers.replay_collect_on_twin)."""
+    monkeypatch.delenv("ACAS2D_SHAPE", raising=False)
+    E, N, T = 65536, 8, 1200
+    D = 5 + 3 * N
+    _need_device_bytes((T + 1) * E * D * 4 + T * E * 24 + 2 * _env_bytes(E, N, 4, generations=2))
+    torch.manual_seed(1)
+    pol = g.ActorCritic(D).to("cuda:0")
+    with torch.no_grad():
+        pol.action_net.weight.mul_(40.0)
+    env, twin = (g.ACAS2DVecEnv(E, N, device="cuda:0", seed=13) for _ in range(2))
+    env.reset()
+    twin.reset()
+    out = env.collect(pol, T, noise_seed=5, noise_step=0)
+    assert out["obs"].numel() >= 2 ** 31
+    assert H.replay_collect_on_twin(env, twin, out) > E
+    _print_peak("collector past 2^31 elements")

@@ -490,3 +490,81 @@ def test_f32_bounds_of_the_default_configuration_are_the_fixed_ones(oracle_mod):
     for kw in H.NONDEFAULT_CONFIGS.values():
         b = H.f32_bounds(H.oracle_config(oracle_mod, g.ACAS2DConfig(**kw)), dflt)
         assert all(b[k] >= v for k, v in H.f32_bounds(dflt, dflt).items() if v is not None) and b["speed"] > 0
+
+
+def test_wide_keys_cross_2_to_the_32_where_the_gpu_tests_claim(g, oracle_mod):
+    """helpers.WIDE_*: the seed's halves are non-zero and distinct; for every work shape of helpers.SHAPES the global
+    env index crosses 2^32 inside a wave and a workgroup at both env_offsets ("tail": inside the last, partial wave
+    wherever it holds more than one env), every wave holds preset and plain episode counters, and the GPU tests' runs
+    really wrap preset counters through 2^32 - 1 to 0: the float64 shape runs (90 steps, max_steps 40) and the float32
+    windows of helpers.wide_f32_window -- re-measured on the oracle here."""
+    O = oracle_mod
+    lo, hi = H.WIDE_SEED & 0xFFFFFFFF, H.WIDE_SEED >> 32
+    assert 0 < lo != hi > 0 and hi < 2 ** 32
+    E, block = H.WIDE_E, 256 // 64                       # waves per workgroup (kWavesPerBlock)
+    pre = H.wide_preset(E)
+    for shape in H.SHAPES:
+        wave = shape.envs_per_wave
+        for key, off in H.WIDE_OFFSET.items():
+            c = 2 ** 32 - off
+            assert 0 < c < E and off + c == 2 ** 32 and (off + c - 1) >> 32 == 0, (shape.id, key)
+            if wave > 1:
+                assert c % wave != 0 and c % (wave * block) != 0, (shape.id, key)     # not on a wave / workgroup start
+                w0 = c - c % wave
+                assert pre[w0:w0 + wave].any() and (~pre[w0:w0 + wave]).any(), shape.id
+            if key == "tail" and E % wave > 1:
+                assert c >= E - E % wave, shape.id                                   # the last, partial wave
+        # test_waves_finishing_together_vs_oracle's wide cases: E = 32 waves, the crossing inside the middle one
+        c = 2 ** 32 - H.wide_crossing_offset(32 * wave, wave)
+        assert c // wave == 16 and (wave == 1 or c % wave != 0), shape.id
+    assert sum(s.envs_per_wave > 1 and E % s.envs_per_wave > 1 for s in H.SHAPES) >= 10
+    for N in sorted({s.n_traffic for s in H.SHAPES}):
+        cfg = g.ACAS2DConfig(n_traffic=N, max_steps=40)
+        ocfg = H.oracle_config(O, cfg)
+        for key, off in H.WIDE_OFFSET.items():
+            ref = O.OracleEnvs(E, N, seed=H.WIDE_SEED, env_offset=off, auto_reset=True, config=ocfg)
+            ref.reset()
+            ref.episode[pre] = H.WIDE_EPISODE
+            rng = np.random.default_rng(1)
+            wrapped = 0
+            for _ in range(90):
+                _, _, d, _, _ = ref.step(rng.uniform(-1, 1, E))
+                wrapped += int(((d != 0) & (ref.episode == 0)).sum())
+            assert wrapped >= 50 and (ref.episode[pre] < 2 ** 31).sum() >= 50, (N, key, wrapped)
+            warmup, T = H.wide_f32_window(N)
+            episode = np.where(pre, H.WIDE_EPISODE, 0).astype(np.uint32)
+            wrapped = 0
+            for _, _, _, _, _, _, chk, (_, _, d, _) in H.f32_oracle_steps(O, E, N, T, H.WIDE_SEED, off, warmup, ocfg,
+                                                                         episode):
+                wrapped += int(((d != 0) & (chk.episode == 0)).sum())
+            assert wrapped >= 5, (N, key, wrapped)
+
+
+def test_arena_layout_size_bound_at_the_32_bit_limit(g):
+    """acas2d_state_is_consecutive at its size bound (helpers.ARENA_BOUND): the largest whole-workgroup env count with
+    8 E N < 2^32 and 20 E < 2^32 is admitted, the next one is not (N = 8 and 64: the traffic term; N = 2: the [5][E]
+    term).  Synthetic addresses, as in test_c_abi_argument_validation_needs_no_gpu."""
+    L = g.native.lib()
+
+    def arena(E, N):
+        b = 1 << 40
+        f = {n: 0 for n, _ in g.native.CState._fields_}
+        for k, n in enumerate(("own_x", "own_y", "own_psi", "total_reward", "steps")):
+            f[n] = b + k * E * 4
+        for k, n in enumerate(("own_v", "goal_x", "goal_y", "episode")):
+            f[n] = 2 * b + k * E * 4
+        f["trf_x"], f["trf_y"] = 3 * b, 3 * b + E * N * 4
+        f["trf_psi"], f["trf_v"] = 4 * b, 4 * b + E * N * 4
+        f["status"], f["trace"] = 5 * b, None
+        return g.native.CState(*[f[n] for n, _ in g.native.CState._fields_])
+
+    for N, e_yes, e_no in H.ARENA_BOUND:
+        geo = g.native.launch_geometry(e_yes, N, 4)
+        unit = (64 // geo["lanes_per_env"]) * 4 * 8                # whole multiples of eight workgroups
+        assert e_yes % unit == 0 and e_no == e_yes + unit, N
+        assert 8 * e_yes * N < 2 ** 32 and 20 * e_yes < 2 ** 32, N
+        assert 8 * e_no * N >= 2 ** 32 or 20 * e_no >= 2 ** 32, N
+        assert (20 * e_no >= 2 ** 32) == (N <= 2) and (8 * e_no * N < 2 ** 32) == (N <= 2), N   # which term binds
+        assert L.acas2d_state_is_consecutive(C.byref(arena(e_yes, N)), e_yes, N, 4) == 1, N
+        assert L.acas2d_state_is_consecutive(C.byref(arena(e_no, N)), e_no, N, 4) == 0, N
+        assert L.acas2d_state_is_consecutive(C.byref(arena(e_yes - unit, N)), e_yes - unit, N, 4) == 1, N

@@ -440,3 +440,60 @@ def test_nan_observation_evaluations_agree(g, N):
           % (slow["outcome"][rows], slow["steps"][rows], fused["outcome"][rows], fused["steps"][rows]))
     assert slow["unfinished"] == 0 and fused["unfinished"] == 0
     assert np.array_equal(slow["outcome"], fused["outcome"]) and np.array_equal(slow["steps"], fused["steps"])
+
+
+# ---- at the wide reset keys (helpers.WIDE_*) --------------------------------------------------------------------------
+def _wide_pair(g, kern, E):
+    """Two envs at helpers.WIDE_SEED with the 2^32 crossing inside a wave ("mid"), max_steps 40, reset, the even envs'
+    episode counters set to 2^32 - 2 (their second in-kernel reset wraps them to 0)."""
+    env, twin = (_env(g, kern, E, seed=H.WIDE_SEED, env_offset=H.WIDE_OFFSET["mid"], cfg={"max_steps": 40})
+                 for _ in range(2))
+    pre = torch.as_tensor(H.wide_preset(E), device=DEV)
+    for v in (env, twin):
+        v.reset()
+        v.episode[pre] = H.WIDE_EPISODE - 2 ** 32                  # the counter's int32 bit pattern
+    return env, twin, pre
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kern", R.POLICY_KERNELS, ids=[R.kernel_id(k) for k in R.POLICY_KERNELS])
+def test_fused_collector_at_wide_keys_replays_on_a_twin(g, kern):
+    """collect() at the wide keys, 90 steps: its in-kernel resets -- wrapping the preset counters -- are the ones a twin
+    stepped with the clipped actions draws (helpers.replay_collect_on_twin, bit for bit); the twin's step is held to the
+    oracle at these keys by tests/test_gpu_parity.py."""
+    dtype, fast, N = kern
+    E, T = H.WIDE_E, 90
+    env, twin, pre = _wide_pair(g, kern, E)
+    out = env.collect(_actor_critic(g, 5 + 3 * N), T, noise_seed=H.WIDE_SEED, noise_step=0)
+    H.replay_collect_on_twin(env, twin, out)
+    assert int((env.episode[pre] >= 0).sum()) >= 50                    # wrapped through 2^32 - 1 to 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kern", R.POLICY_KERNELS, ids=[R.kernel_id(k) for k in R.POLICY_KERNELS])
+def test_fused_policy_rollout_at_wide_keys_replays_on_a_twin(g, kern):
+    """rollout_policy() at the wide keys, 90 steps: every action against clip(mean64, -1, 1) of the observation the
+    kernel stepped from (1e-5, NaN at the same places); a twin stepped with those actions reproduces every output bit for
+    bit and ends in the same state, the preset counters wrapped."""
+    dtype, fast, N = kern
+    D, E, T = 5 + 3 * N, H.WIDE_E, 90
+    pol = _actor_critic(g, D)
+    env, twin, pre = _wide_pair(g, kern, E)
+    obs0 = twin.outputs["obs"].double().cpu().numpy()
+    out = env.rollout_policy(pol, T)
+    torch.cuda.synchronize()
+    obs = np.concatenate([obs0[None], out["obs"][:T - 1].double().cpu().numpy()])
+    ref = R.actor64(pol.actor_weights(), obs.reshape(T * E, D)).reshape(T, E)
+    got = out["actions"].double().cpu().numpy()
+    assert np.array_equal(np.isnan(got), np.isnan(ref))
+    fin = ~np.isnan(ref)
+    worst = float(np.abs(got[fin] - ref[fin]).max())
+    for t in range(T):
+        o, r, d, infos = twin.step(out["actions"][t])
+        assert H.bits_equal(out["obs"][t], o) and H.bits_equal(out["reward"][t], r), t
+        assert torch.equal(out["done"][t], d) and torch.equal(out["outcome"][t], infos.outcome), t
+    for name in ("own_x", "own_y", "own_psi", "trf_x", "trf_y", "trf_psi", "trf_v", "steps", "total_reward", "episode"):
+        assert torch.equal(getattr(env, name), getattr(twin, name)), name
+    print("rollout_policy %s at wide keys: worst |action - clip(mean64)| %.2e (bound 1e-5)" % (R.kernel_id(kern), worst))
+    assert worst < 1e-5
+    assert int((env.episode[pre] >= 0).sum()) >= 50

@@ -238,3 +238,42 @@ def test_oracle_threads_do_not_change_a_bit(oracle_mod):
     assert runs[0][4] == runs[1][4] > 0
     for a, b in zip(runs[0][:4], runs[1][:4]):
         assert np.array_equal(a, b)
+
+
+def test_reset_draws_restated_from_philox_at_wide_keys(O):
+    """OracleEnvs.reset_philox assembles counter (gid lo, gid hi, episode, entity) and key (seed lo, seed hi) around the
+    KAT-pinned philox4x32: three one-line draws restated from O.philox4x32 alone -- own_psi from word 2 of entity 0,
+    trf_v from word 3, trf_x of traffic n >= 1 from word 0 -- at helpers.WIDE_SEED, for global env indices just below
+    and above 2^32 and episode counters around the wrap, bit for bit.  Changing only the seed's high word, or only the
+    global index's high word, changes the draws."""
+    E, N, off = 6, 3, 2 ** 32 - 3                         # gids 2^32 - 3 .. 2^32 + 2
+    cfg = O.default_config()
+    cfg.speed_factor_min, cfg.speed_factor_max = 0.8, 1.3  # (the default draws no speed)
+    L = O.lib()
+    rel = L.acas2d_oracle_relative_angle(cfg.own_x0, cfg.own_y0, cfg.goal_x, cfg.goal_y)
+    u01 = lambda w: (float(w) + 0.5) * 2.0 ** -32          # noqa: E731
+    uniform = lambda a, b, w: a + (b - a) * u01(w)          # noqa: E731  (random.uniform)
+    episode = np.array([2 ** 32 - 2, 2 ** 32 - 1, 0, 2 ** 32 - 1, 2 ** 32 - 2, 1], np.uint32)
+
+    def draw(seed, env_offset):
+        ref = O.OracleEnvs(E, N, seed=seed, env_offset=env_offset, config=cfg)
+        ref.episode[:] = episode
+        ref.reset_philox()
+        return ref
+
+    ref = draw(H.WIDE_SEED, off)
+    key = [H.WIDE_SEED & 0xFFFFFFFF, H.WIDE_SEED >> 32]
+    for e in range(E):
+        gid = off + e
+        ctr = lambda ent: [gid & 0xFFFFFFFF, gid >> 32, int(episode[e]), ent]  # noqa: E731
+        w0 = O.philox4x32(ctr(0), key)
+        assert ref.own_psi[e] == (rel + uniform(-cfg.own_heading_jitter, cfg.own_heading_jitter, w0[2])) % 360.0, e
+        for n in range(N):
+            w = O.philox4x32(ctr(1 + n), key)
+            assert ref.trf_v[e, n] == uniform(cfg.speed_factor_min, cfg.speed_factor_max, w[3]) * cfg.airspeed, (e, n)
+            if n >= 1:
+                assert ref.trf_x[e, n] == uniform(0.0, cfg.tn_x_max, w[0]), (e, n)
+    assert ((off + np.arange(E)) >> 32).tolist() == [0, 0, 0, 1, 1, 1]
+    for other in (draw(H.WIDE_SEED ^ (1 << 45), off), draw(H.WIDE_SEED, off + 2 ** 32)):   # one high word changed
+        assert (other.own_psi != ref.own_psi).all() and (other.trf_x[:, 1:] != ref.trf_x[:, 1:]).all()
+        assert (other.trf_psi != ref.trf_psi).all() and (other.trf_v != ref.trf_v).all()
