@@ -1450,6 +1450,20 @@ __device__ __forceinline__ float policy_action(const PolicyW& pw, const float (&
 }
 
 // ---- kernels ------------------------------------------------------------------------------------------
+// The launch modes of step_kernel, one per C entry point / launch path (DESIGN.md 4.1 lists them with the
+// flags each one implies).  The values are part of the kernels' names: keep them stable, append new ones.
+enum class Mode {
+    Latch,      // acas2d_step_* without ACAS2D_AUTO_RESET: a finished env latches
+    Step,       // acas2d_step_* with ACAS2D_AUTO_RESET
+    Arena,      // the same, float32, the state in the consecutive layout (arena_layout())
+    Rollout,    // acas2d_rollout_*
+    Policy,     // acas2d_rollout_policy_*
+    Collect,    // acas2d_collect_*
+    Eval,       // acas2d_evaluate_policies_*
+};
+constexpr bool policy_mode(Mode m) { return m == Mode::Policy || m == Mode::Collect || m == Mode::Eval; }
+constexpr bool rollout_mode(Mode m) { return m == Mode::Rollout || policy_mode(m); }
+
 // ACAS2DEnv.step(), environment.py:29-42 -- and, with ROLLOUT, n_steps of them fused in one launch:
 // the state stays in registers, step t reads actions[t][E] and writes obs[t][E][D], reward[t][E],
 // done[t][E], outcome[t][E] (and the optional auto-reset side channels [t][E]...), finished envs
@@ -1464,17 +1478,17 @@ __device__ __forceinline__ float policy_action(const PolicyW& pw, const float (&
 // With EVAL on top of POLICY (acas2d_evaluate_policies_*; PolicyEvalW) the launch scores K stacked policies: no per-step
 // outputs, no in-step resets, no state write-back; each lane latches the result of its first episode and the wave leaves
 // the step loop once none of its lanes is still running.
-template <typename T, int C, int G, bool PACKED, bool AUTO_RESET, bool FAST, bool ROLLOUT, bool POLICY = false,
-          bool SAMPLE = false, bool ARENA = false, bool EVAL = false>
+template <typename T, int C, int G, bool PACKED, bool FAST, Mode M>
 __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, const T* a2, const T* a3, const T* a4,
                                                       const T* a5, int32_t e_n_envs, int32_t tile_elems,
-                                                      Params<T> p_arg, StepResetParams<T, ROLLOUT> rp_arg, State<T> s_arg,
+                                                      Params<T> p_arg, StepResetParams<T, rollout_mode(M)> rp_arg, State<T> s_arg,
                                                       StepIO<T> io_arg, uint32_t k0, uint32_t k1,
-                                                      int64_t env_offset, int N_arg, int n_steps, PolicyArg<EVAL> pw) {
-    static_assert(!ROLLOUT || (AUTO_RESET && PACKED), "rollout: auto-reset semantics, packed shapes");
-    static_assert(!POLICY || (ROLLOUT && G == 1), "in-kernel policy: rollout mode, one lane per env");
-    static_assert(!SAMPLE || POLICY, "sampling needs the in-kernel policy");
-    static_assert(!EVAL || (POLICY && !SAMPLE), "evaluation: the deterministic in-kernel policy");
+                                                      int64_t env_offset, int N_arg, int n_steps, PolicyArg<M == Mode::Eval> pw) {
+    constexpr bool AUTO_RESET = M != Mode::Latch, ROLLOUT = rollout_mode(M);
+    constexpr bool POLICY = policy_mode(M), SAMPLE = M == Mode::Collect;
+    constexpr bool ARENA = M == Mode::Arena, EVAL = M == Mode::Eval;
+    static_assert(!ROLLOUT || PACKED, "rollout modes: packed shapes");
+    static_assert(!POLICY || G == 1, "in-kernel policy: one lane per env");
     constexpr int NS = PACKED ? C * G : 0;         // packed shapes: n_traffic is a compile-time constant
     const int N = PACKED ? NS : N_arg;
     constexpr int EPW = 64 / G;                    // envs per wavefront
@@ -1483,12 +1497,12 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
     // instructions instead of behind a scalar-load round trip to the argument segment (~0.27 us, all waves of a launch
     // miss together).  The grid size follows from the env count (geometry_for), so nothing of the launch geometry is
     // fetched either.  Six pointers do not name fourteen input arrays, so:
-    //   ARENA   (launch_step_impl found the state laid out as consecutive [k][E] rows, as the Python host allocates it)
+    //   ARENA   (launch_step found the state laid out as consecutive [k][E] rows, as the Python host allocates it)
     //           a0 = own_x (then own_y, own_psi, total_reward, steps), a1 = own_v (then goal_x, goal_y, episode),
     //           a2 = trf_x (then trf_y), a3 = trf_psi (then trf_v), a4 = actions: EVERY load leaves at once;
     //   else    a0 .. a5 = trf_x, trf_y, trf_psi, trf_v, own_x, own_y: the bulk of the bytes leaves at once, the rest
     //           behind the round trip.
-    static_assert(!ARENA || (sizeof(T) == 4 && PACKED && AUTO_RESET && !ROLLOUT), "arena launches: the float32 per-step auto-reset kernel");
+    static_assert(!ARENA || (sizeof(T) == 4 && PACKED), "arena launches: float32, packed shapes");
     // A wavefront issues one instruction per four cycles whatever its kind, and every instruction in front of the first
     // load is on the launch's critical path: env indices are 32-bit here (n_envs < 2^31, geometry_for).
     const uint32_t E32 = (uint32_t)e_n_envs;
@@ -1497,7 +1511,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
     const int wib = wave_in_block();
     extern __shared__ __align__(16) unsigned char lds_raw[];
     constexpr uint32_t kEnvsPerBlock = EPW * kWavesPerBlock;
-    // Arena launches come in whole multiples of eight workgroups (launch_step_impl): every wave is full and the XCD remap
+    // Arena launches come in whole multiples of eight workgroups (launch_step): every wave is full and the XCD remap
     // unconditional -- no bounds check, no clamped load index, no lane guards on the stores, fifteen instructions less
     // in front of the first load.
     constexpr bool FULL = ARENA;
@@ -1542,12 +1556,12 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
         s_in.trf_x = const_cast<T*>(a0); s_in.trf_y = const_cast<T*>(a1); s_in.trf_psi = const_cast<T*>(a2);
         s_in.trf_v = const_cast<T*>(a3); s_in.own_x = const_cast<T*>(a4); s_in.own_y = const_cast<T*>(a5);
     }
-    // only the per-step auto-reset launch takes a second state generation (launch_step_impl); elsewhere the offsets are
+    // only the per-step auto-reset launch takes a second state generation (launch_step); elsewhere the offsets are
     // compile-time zeros and cost no registers
     if constexpr (ROLLOUT || !AUTO_RESET) { s_in.w_env = 0; s_in.w_trf = 0; }
     T ox = T(0), oy = T(0);
     if constexpr (ARENA) {
-        // Unmodified preloaded bases + 32-bit per-lane byte offsets (launch_step_impl checked that they fit): one VALU add
+        // Unmodified preloaded bases + 32-bit per-lane byte offsets (launch_step checked that they fit): one VALU add
         // per array instead of four scalar ones.  The player's scalars and the action first, the traffic vectors (the
         // bulk) last: loads return in order, so the player-side arithmetic can start while the vectors are landing.
         if (run) {

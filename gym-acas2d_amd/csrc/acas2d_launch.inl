@@ -1,10 +1,11 @@
 // acas2d_launch.inl -- host-side launchers, included by acas2d_f32.hip and acas2d_f64.hip which
-// define ACAS2D_PACKED_SHAPES(X) (the (C, G) pairs to instantiate for their element type) and
-// kFast, then instantiate launch_step<T> / launch_reset<T>.  (Two translation units: each element
-// type is compiled with its own flags.  Both use -ffp-contract=off today, so only the fma()s written
-// in the source fuse.)
+// define ACAS2D_PACKED_SHAPES(X) (the (C, G) pairs to instantiate for their element type), Elem (that
+// type) and kFast (its own formulation); the launchers are instantiated for Elem at the end.  (Two
+// translation units: each element type is compiled with its own flags.  Both use -ffp-contract=off
+// today, so only the fma()s written in the source fuse.)
 #include <stdlib.h>
 #include <cmath>
+#include <type_traits>
 
 #include "acas2d_kernels.hpp"
 
@@ -28,18 +29,19 @@ static Params<T> make_params(const Acas2dConfig& c) {
     return p;
 }
 
-template <typename R, typename GT = R>
-static ResetParamsT<R, GT> make_reset_params(const Acas2dConfig& c) {
+template <typename T, bool ROLLOUT>
+static StepResetParams<T, ROLLOUT> make_reset_params(const Acas2dConfig& c) {
+    using R = typename std::conditional<ROLLOUT, double, T>::type;
     // the goal terms of a fresh episode (own_context_fresh()): game.py:168-180 at the start position
     const double gdx = c.goal_x - c.own_x0, gdy = c.goal_y - c.own_y0;
     double bearing = std::atan2(gdy, gdx);
     if (bearing < 0) bearing += 6.283185307179586476925;
     else if (bearing == 0) bearing = 0;
-    return ResetParamsT<R, GT>{(R)c.own_x0, (R)c.own_y0, (R)c.own_v, (R)c.own_heading0, (R)c.own_heading_jitter,
-                           (R)c.goal_x, (R)c.goal_y, (R)c.t0_x, (R)c.t0_y_base, (R)c.t0_y_span,
-                           (R)c.t0_heading_base, (R)c.t0_heading_step, (R)c.t0_heading_jitter, (R)c.tn_x_max,
-                           (R)c.tn_y_max, (R)c.speed_factor_min, (R)c.speed_factor_max, (R)c.airspeed,
-                           (GT)std::sqrt(std::fma(gdy, gdy, gdx * gdx)), (GT)(bearing * 57.29577951308232087680), (GT)gdy};
+    return StepResetParams<T, ROLLOUT>{(R)c.own_x0, (R)c.own_y0, (R)c.own_v, (R)c.own_heading0, (R)c.own_heading_jitter,
+                                       (R)c.goal_x, (R)c.goal_y, (R)c.t0_x, (R)c.t0_y_base, (R)c.t0_y_span,
+                                       (R)c.t0_heading_base, (R)c.t0_heading_step, (R)c.t0_heading_jitter, (R)c.tn_x_max,
+                                       (R)c.tn_y_max, (R)c.speed_factor_min, (R)c.speed_factor_max, (R)c.airspeed,
+                                       (T)std::sqrt(std::fma(gdy, gdy, gdx * gdx)), (T)(bearing * 57.29577951308232087680), (T)gdy};
 }
 
 template <typename T>
@@ -122,9 +124,9 @@ static int write_offsets(const Acas2dState* st, const Acas2dState* out, bool aut
     return ACAS2D_OK;
 }
 
-static int check_launch(const char* what) {
+static int check_launch(const char* name) {
     hipError_t err = hipGetLastError();
-    if (err != hipSuccess) { set_error("%s: %s", what, hipGetErrorString(err)); return ACAS2D_EHIP; }
+    if (err != hipSuccess) { set_error("%s launch: %s", name, hipGetErrorString(err)); return ACAS2D_EHIP; }
     return ACAS2D_OK;
 }
 
@@ -158,15 +160,10 @@ static int geometry_for(const Shape& sh, int64_t n_envs, int n_traffic, Geometry
     return ACAS2D_OK;
 }
 
-// The step kernel's first 14 argument dwords are what the command processor preloads into SGPRs (see step_kernel):
-// six pointers, the env count, the tile size.
-#define ACAS2D_EARLY_ARGS(s, n_envs, g) \
-    (s).trf_x, (s).trf_y, (s).trf_psi, (s).trf_v, (s).own_x, (s).own_y, (int32_t)(n_envs), (int32_t)(g).tile_elems
-
 // "Arena" layout of a float32 state: the per-env arrays a step reads are consecutive [k][E] rows -- own_x, own_y,
 // own_psi, total_reward, steps / own_v, goal_x, goal_y, episode -- and so are the traffic arrays -- trf_x, trf_y /
 // trf_psi, trf_v ([k][E][N]).  Five preloaded base pointers (the four blocks and the actions) then name every input of
-// the step, and ALL of a wavefront's loads leave before its first scalar-load round trip (step_kernel<..., ARENA>).
+// the step, and ALL of a wavefront's loads leave before its first scalar-load round trip (Mode::Arena).
 // `ACAS2DVecEnv` allocates its float32 state this way.  The kernel also assumes full waves in whole multiples of eight
 // workgroups (n_envs a multiple of 1 024 at n_traffic = 8); any other layout or size takes the general kernel, same results.
 template <typename T>
@@ -181,72 +178,34 @@ static bool arena_layout(const State<T>& s, int64_t E, int N, int G) {
            s.trf_y == s.trf_x + EN && s.trf_v == s.trf_psi + EN;
 }
 
-template <typename T, bool FAST, int C, int G, bool PACKED>
-static void step_shape(bool auto_reset, const Geometry& g, hipStream_t stream, const Params<T>& p,
-                       const ResetParamsT<T>& rp, const State<T>& s, const StepIO<T>& io, uint32_t k0, uint32_t k1,
-                       int64_t env_offset, int64_t n_envs, int N) {
-    if constexpr (PACKED && sizeof(T) == 4) {
-        if (auto_reset && arena_layout<T>(s, n_envs, N, G)) {
-            hipLaunchKernelGGL((step_kernel<T, C, G, true, true, FAST, false, false, false, true>), dim3(g.grid), dim3(g.block),
-                               g.lds_bytes, stream, (const T*)s.own_x, (const T*)s.own_v, (const T*)s.trf_x, (const T*)s.trf_psi,
-                               io.actions, (const T*)nullptr, (int32_t)n_envs, (int32_t)g.tile_elems,
-                               p, rp, s, io, k0, k1, env_offset, N, 1, PolicyW{});
-            return;
-        }
-    }
-    if (auto_reset)
-        hipLaunchKernelGGL((step_kernel<T, C, G, PACKED, true, FAST, false>), dim3(g.grid), dim3(g.block), g.lds_bytes, stream,
-                           ACAS2D_EARLY_ARGS(s, n_envs, g), p, rp, s, io, k0, k1, env_offset, N, 1, PolicyW{});
-    else
-        hipLaunchKernelGGL((step_kernel<T, C, G, PACKED, false, FAST, false>), dim3(g.grid), dim3(g.block), g.lds_bytes, stream,
-                           ACAS2D_EARLY_ARGS(s, n_envs, g), p, rp, s, io, k0, k1, env_offset, N, 1, PolicyW{});
-}
-
-template <typename T, bool FAST, int C, int G>
-static void rollout_shape(const Geometry& g, hipStream_t stream, const Params<T>& p, const StepResetParams<T, true>& rp,
-                          const State<T>& s, const StepIO<T>& io, uint32_t k0, uint32_t k1, int64_t env_offset,
-                          int64_t n_envs, int N, int n_steps) {
-    hipLaunchKernelGGL((step_kernel<T, C, G, true, true, FAST, true>), dim3(g.grid), dim3(kBlock), g.lds_bytes, stream,
-                       ACAS2D_EARLY_ARGS(s, n_envs, g), p, rp, s, io, k0, k1, env_offset, N, n_steps, PolicyW{});
-}
-
-// the same with the SB3 actor evaluated in the kernel (thread-per-env shapes only)
-template <typename T, bool FAST, int C>
-static void policy_shape(const Geometry& g, hipStream_t stream, const Params<T>& p, const StepResetParams<T, true>& rp,
-                         const State<T>& s, const StepIO<T>& io, uint32_t k0, uint32_t k1, int64_t env_offset,
-                         int64_t n_envs, int N, int n_steps, const PolicyW& pw, bool sample) {
-    if (sample)
-        hipLaunchKernelGGL((step_kernel<T, C, 1, true, true, FAST, true, true, true>), dim3(g.grid), dim3(kBlock), g.lds_bytes,
-                           stream, ACAS2D_EARLY_ARGS(s, n_envs, g), p, rp, s, io, k0, k1, env_offset, N, n_steps, pw);
-    else
-        hipLaunchKernelGGL((step_kernel<T, C, 1, true, true, FAST, true, true>), dim3(g.grid), dim3(kBlock), g.lds_bytes,
-                           stream, ACAS2D_EARLY_ARGS(s, n_envs, g), p, rp, s, io, k0, k1, env_offset, N, n_steps, pw);
-}
-
-// K stacked policies scored on shared episodes (acas2d_evaluate_policies_*): the policy rollout with EVAL
-template <typename T, bool FAST, int C>
-static void eval_shape(const Geometry& g, hipStream_t stream, const Params<T>& p, const StepResetParams<T, true>& rp,
-                       const State<T>& s, uint32_t k0, uint32_t k1, int64_t env_offset, int64_t n_envs, int N, int n_steps,
-                       const PolicyEvalW& pw) {
-    hipLaunchKernelGGL((step_kernel<T, C, 1, true, true, FAST, true, true, false, false, true>), dim3(g.grid), dim3(kBlock),
-                       g.lds_bytes, stream, ACAS2D_EARLY_ARGS(s, n_envs, g), p, rp, s, StepIO<T>{}, k0, k1, env_offset, N,
-                       n_steps, pw);
-}
-
-template <typename T, bool FAST, int C, int G, bool PACKED>
-static void reset_shape(const Geometry& g, hipStream_t stream, const Params<T>& p, const StepResetParams<T, true>& rp,
-                        const State<T>& s, const uint8_t* mask, T* obs, int do_init, uint32_t k0, uint32_t k1,
-                        int64_t env_offset, int64_t n_envs, int N) {
-    hipLaunchKernelGGL((reset_kernel<T, C, G, PACKED, FAST>), dim3(g.grid), dim3(kBlock),
-                       g.lds_bytes, stream, p, rp, s, mask, obs, do_init, k0, k1, env_offset, n_envs, N, g.tile_elems);
-}
-
-static bool shape_instantiated(const Shape& sh) {
-    if (!sh.packed) return sh.C == 1 && (sh.G == 1 || sh.G == 4 || sh.G == 16 || sh.G == 64);
-#define X(C_, G_) if (sh.C == C_ && sh.G == G_) return true;
+// The one map from a runtime Shape to an instantiation: calls f(C, G, PACKED), as integral_constants, for the shape of
+// ACAS2D_PACKED_SHAPES or of the generic walk (C = 1, G lanes per env) that sh names; false when none does.
+template <typename F>
+static bool visit_shape(const Shape& sh, F f) {
+    bool found = false;
+    const auto at = [&](auto C, auto G, auto packed) {
+        if (sh.packed == packed && sh.C == C && sh.G == G) { f(C, G, packed); found = true; }
+    };
+#define X(C_, G_) at(std::integral_constant<int, C_>{}, std::integral_constant<int, G_>{}, std::true_type{});
     ACAS2D_PACKED_SHAPES(X)
 #undef X
-    return false;
+#define X(G_) at(std::integral_constant<int, 1>{}, std::integral_constant<int, G_>{}, std::false_type{});
+    X(1) X(4) X(16) X(64)                                   // the generic walk
+#undef X
+    return found;
+}
+
+static bool shape_instantiated(const Shape& sh) { return visit_shape(sh, [](auto, auto, auto) {}); }
+
+// Formulation (DESIGN.md 4.1): the element type's own -- FAST for float32, EXACT for float64 -- unless the
+// configuration asks for ACAS2D_MATH_FAST, which gives the float64 entry points the algebraic formulation in
+// float64 arithmetic (float32 has no other).  Chosen per call; nothing is cached between calls.  Calls
+// f(FAST, C, G, PACKED) for that formulation and the instantiated shape sh.
+template <typename F>
+static void dispatch(const Acas2dConfig& cfg, const Shape& sh, F f) {
+    const auto with = [&](auto fast) { visit_shape(sh, [&](auto C, auto G, auto packed) { f(fast, C, G, packed); }); };
+    if (kFast || cfg.math == ACAS2D_MATH_FAST) with(std::true_type{});
+    else with(std::integral_constant<bool, kFast>{});
 }
 
 // Shape for (n_traffic, element type): the tuned default of choose_shape(), or the override
@@ -268,259 +227,225 @@ static int resolve_shape(int n_traffic, Shape* out) {
     return ACAS2D_OK;
 }
 
-template <typename T, bool FAST>
-static int launch_step_impl(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dState* st_out, const Acas2dStepIO* io_,
-                uint32_t flags, uint64_t seed, int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream) {
-    if (!cfg || !io_) { set_error("acas2d_step: NULL cfg / io"); return ACAS2D_EINVAL; }
-    if (!state_complete(st)) { set_error("acas2d_step: NULL state or a NULL state buffer"); return ACAS2D_EINVAL; }
-    if (!io_->actions || !io_->obs || !io_->reward || !io_->done || !io_->outcome) {
-        set_error("acas2d_step: actions, obs, reward, done and outcome are required"); return ACAS2D_EINVAL; }
-    if (n_traffic < 1) { set_error("acas2d_step: n_traffic = %d (the reference needs traffic[0], game.py:254)", n_traffic); return ACAS2D_EINVAL; }
-    if (n_envs < 0 || env_offset < 0) { set_error("acas2d_step: negative n_envs / env_offset"); return ACAS2D_EINVAL; }
-    if (n_envs == 0) return ACAS2D_OK;
-    Shape sh;
-    if (int rc = resolve_shape<T>(n_traffic, &sh)) return rc;
-    const bool ar = (flags & ACAS2D_AUTO_RESET) != 0;
-    Geometry g;
-    if (int rc = geometry_for<T>(sh, n_envs, n_traffic, &g)) return rc;
-    const Params<T> p = make_params<T>(*cfg);
-    const ResetParamsT<T> rp = make_reset_params<T>(*cfg);
-    State<T> s = make_state<T>(*st);
-    if (int rc = write_offsets<T>(st, st_out, ar, n_envs, n_traffic, &s.w_env, &s.w_trf)) return rc;
-    const StepIO<T> io{(const T*)io_->actions, (T*)io_->obs, (T*)io_->reward, io_->done, io_->outcome,
-                       (T*)io_->term_obs, (T*)io_->ep_return, io_->ep_steps};
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    if (sh.packed) {
-#define X(C_, G_) if (sh.C == C_ && sh.G == G_) step_shape<T, FAST, C_, G_, true>(ar, g, stream, p, rp, s, io, k0, k1, env_offset, n_envs, n_traffic);
-        ACAS2D_PACKED_SHAPES(X)
-#undef X
-    } else {
-        switch (sh.G) {
-            case 1:  step_shape<T, FAST, 1, 1, false>(ar, g, stream, p, rp, s, io, k0, k1, env_offset, n_envs, n_traffic); break;
-            case 4:  step_shape<T, FAST, 1, 4, false>(ar, g, stream, p, rp, s, io, k0, k1, env_offset, n_envs, n_traffic); break;
-            case 16: step_shape<T, FAST, 1, 16, false>(ar, g, stream, p, rp, s, io, k0, k1, env_offset, n_envs, n_traffic); break;
-            default: step_shape<T, FAST, 1, 64, false>(ar, g, stream, p, rp, s, io, k0, k1, env_offset, n_envs, n_traffic); break;
-        }
-    }
-    return check_launch("acas2d_step launch");
+template <typename... A>
+static int fail(const char* fmt, A... a) {
+    set_error(fmt, a...);
+    return ACAS2D_EINVAL;
 }
 
-template <typename T, bool FAST>
-static int launch_rollout_impl(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io_, int32_t n_steps,
-                   uint64_t seed, int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream) {
-    if (!cfg || !io_) { set_error("acas2d_rollout: NULL cfg / io"); return ACAS2D_EINVAL; }
-    if (!state_complete(st)) { set_error("acas2d_rollout: NULL state or a NULL state buffer"); return ACAS2D_EINVAL; }
-    if (!io_->actions || !io_->obs || !io_->reward || !io_->done || !io_->outcome) {
-        set_error("acas2d_rollout: actions, obs, reward, done and outcome are required"); return ACAS2D_EINVAL; }
-    if (n_traffic < 1 || n_steps < 1) { set_error("acas2d_rollout: n_traffic = %d, n_steps = %d", n_traffic, n_steps); return ACAS2D_EINVAL; }
-    if (n_envs < 0 || env_offset < 0) { set_error("acas2d_rollout: negative n_envs / env_offset"); return ACAS2D_EINVAL; }
-    if (n_envs == 0) return ACAS2D_OK;
-    Shape sh;
-    if (int rc = resolve_shape<T>(n_traffic, &sh)) return rc;
-    if (!sh.packed) {
-        set_error("acas2d_rollout: n_traffic = %d has no packed work shape for this element type "
-                  "(needs n_traffic in {1,2,3} or a multiple of %d tiling a wave); use acas2d_step", n_traffic,
-                  16 / (int)sizeof(T));
-        return ACAS2D_EINVAL;
-    }
-    Geometry g;
-    if (int rc = geometry_for<T>(sh, n_envs, n_traffic, &g)) return rc;
-    const Params<T> p = make_params<T>(*cfg);
-    const StepResetParams<T, true> rp = make_reset_params<double, T>(*cfg);
-    const State<T> s = make_state<T>(*st);
-    const StepIO<T> io{(const T*)io_->actions, (T*)io_->obs, (T*)io_->reward, io_->done, io_->outcome,
-                       (T*)io_->term_obs, (T*)io_->ep_return, io_->ep_steps};
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#define X(C_, G_) if (sh.C == C_ && sh.G == G_) rollout_shape<T, FAST, C_, G_>(g, stream, p, rp, s, io, k0, k1, env_offset, n_envs, n_traffic, n_steps);
-    ACAS2D_PACKED_SHAPES(X)
-#undef X
-    return check_launch("acas2d_rollout launch");
-}
-
-template <typename T, bool FAST>
-static int launch_rollout_policy_impl(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io_,
-                          const Acas2dPolicy* pol, const void* obs_in, int32_t n_steps, uint64_t seed,
-                          int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream,
-                          const Acas2dActorCritic* ac = nullptr) {
-    if (!cfg || !io_ || !pol) { set_error("acas2d_rollout_policy: NULL cfg / io / policy"); return ACAS2D_EINVAL; }
-    if (!state_complete(st)) { set_error("acas2d_rollout_policy: NULL state or a NULL state buffer"); return ACAS2D_EINVAL; }
-    if (!io_->actions || !io_->obs || !io_->reward || !io_->done || !io_->outcome || !obs_in) {
-        set_error("acas2d_rollout_policy: obs_in, actions (output), obs, reward, done and outcome are required"); return ACAS2D_EINVAL; }
-    if (!pol->w1t || !pol->b1 || !pol->w2t || !pol->b2 || !pol->w3 || !pol->b3 || pol->hidden != kPolicyHidden) {
-        set_error("acas2d_rollout_policy: six weight buffers and hidden == %d are required (got hidden = %d)", kPolicyHidden, pol->hidden);
-        return ACAS2D_EINVAL; }
-    if (n_traffic < 1 || n_steps < 1) { set_error("acas2d_rollout_policy: n_traffic = %d, n_steps = %d", n_traffic, n_steps); return ACAS2D_EINVAL; }
-    if (n_envs < 0 || env_offset < 0) { set_error("acas2d_rollout_policy: negative n_envs / env_offset"); return ACAS2D_EINVAL; }
-    if (n_envs == 0) return ACAS2D_OK;
-    const Shape sh{n_traffic, 1, true};                      // one lane per env, its traffic as one vector
-    bool ok = false;
-#define X(C_, G_) if (G_ == 1 && C_ == n_traffic) ok = true;
-    ACAS2D_PACKED_SHAPES(X)
-#undef X
-    if (!ok) {
-        set_error("acas2d_rollout_policy: n_traffic = %d has no thread-per-env shape for this element type", n_traffic);
-        return ACAS2D_EINVAL;
-    }
-    Geometry g;
-    if (int rc = geometry_for<T>(sh, n_envs, n_traffic, &g)) return rc;
-    const Params<T> p = make_params<T>(*cfg);
-    const StepResetParams<T, true> rp = make_reset_params<double, T>(*cfg);
-    const State<T> s = make_state<T>(*st);
-    const StepIO<T> io{(const T*)io_->actions, (T*)io_->obs, (T*)io_->reward, io_->done, io_->outcome,
-                       (T*)io_->term_obs, (T*)io_->ep_return, io_->ep_steps};
-    PolicyW pw{(const float*)pol->w1t, (const float*)pol->b1, (const float*)pol->w2t, (const float*)pol->b2,
-               (const float*)pol->w3, (const float*)pol->b3, const_cast<void*>(io_->actions), obs_in,
-               nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0u, 0u, 0u};
-    if (ac) {
-        if (!ac->v1t || !ac->vb1 || !ac->v2t || !ac->vb2 || !ac->v3 || !ac->vb3 || !ac->log_std || !ac->values || !ac->logp) {
-            set_error("acas2d_collect: the value net, log_std, values and logp are required"); return ACAS2D_EINVAL; }
-        pw.v1t = (const float*)ac->v1t; pw.vb1 = (const float*)ac->vb1; pw.v2t = (const float*)ac->v2t;
-        pw.vb2 = (const float*)ac->vb2; pw.v3 = (const float*)ac->v3; pw.vb3 = (const float*)ac->vb3;
-        pw.log_std = (const float*)ac->log_std; pw.values_out = ac->values; pw.logp_out = ac->logp;
-        pw.nk0 = (uint32_t)ac->noise_seed; pw.nk1 = (uint32_t)(ac->noise_seed >> 32); pw.noise_step = ac->noise_step;
-    }
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#define X(C_, G_) if constexpr (G_ == 1) { if (C_ == n_traffic) policy_shape<T, FAST, C_>(g, stream, p, rp, s, io, k0, k1, env_offset, n_envs, n_traffic, n_steps, pw, ac != nullptr); }
-    ACAS2D_PACKED_SHAPES(X)
-#undef X
-    return check_launch("acas2d_rollout_policy launch");
-}
-
-template <typename T, bool FAST>
-static int launch_evaluate_policies_impl(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
-                                         int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps,
-                                         uint64_t seed, int64_t env_offset, int32_t n_traffic, uint8_t* outcome,
-                                         int32_t* steps, void* total_reward, hipStream_t stream) {
-    if (!cfg || !pol) { set_error("acas2d_evaluate_policies: NULL cfg / policies"); return ACAS2D_EINVAL; }
-    if (!state_complete(st)) { set_error("acas2d_evaluate_policies: NULL state or a NULL state buffer"); return ACAS2D_EINVAL; }
-    if (!obs_in || !outcome || !steps || !total_reward) {
-        set_error("acas2d_evaluate_policies: obs_in and the outcome, steps and total_reward outputs are required"); return ACAS2D_EINVAL; }
-    if (!pol->w1t || !pol->b1 || !pol->w2t || !pol->b2 || !pol->w3 || !pol->b3 || pol->hidden != kPolicyHidden) {
-        set_error("acas2d_evaluate_policies: six weight buffers and hidden == %d are required (got hidden = %d)", kPolicyHidden, pol->hidden);
-        return ACAS2D_EINVAL; }
-    if (n_policies < 1 || n_episodes < 1) {
-        set_error("acas2d_evaluate_policies: n_policies = %d, n_episodes = %d (at least 1 each)", n_policies, n_episodes); return ACAS2D_EINVAL; }
-    if (n_traffic < 1 || n_steps < 1) { set_error("acas2d_evaluate_policies: n_traffic = %d, n_steps = %d", n_traffic, n_steps); return ACAS2D_EINVAL; }
-    if (env_offset < 0) { set_error("acas2d_evaluate_policies: negative env_offset"); return ACAS2D_EINVAL; }
-    bool ok = false;
-#define X(C_, G_) if (G_ == 1 && C_ == n_traffic) ok = true;
-    ACAS2D_PACKED_SHAPES(X)
-#undef X
-    if (!ok) {
-        set_error("acas2d_evaluate_policies: n_traffic = %d has no thread-per-env shape for this element type", n_traffic);
-        return ACAS2D_EINVAL;
-    }
-    // policy k plays envs [k EP, (k + 1) EP): EP = n_episodes rounded up to a whole wave
-    const int64_t ep = ((int64_t)n_episodes + 63) / 64 * 64, total = (int64_t)n_policies * ep;
-    if (n_envs < total) {
-        set_error("acas2d_evaluate_policies: the state holds n_envs = %lld envs, %d policies x %lld (n_episodes = %d rounded up "
-                  "to 64) need %lld", (long long)n_envs, n_policies, (long long)ep, n_episodes, (long long)total);
-        return ACAS2D_EINVAL;
-    }
-    const Shape sh{n_traffic, 1, true};
-    Geometry g;
-    if (int rc = geometry_for<T>(sh, total, n_traffic, &g)) return rc;
-    const Params<T> p = make_params<T>(*cfg);
-    const StepResetParams<T, true> rp = make_reset_params<double, T>(*cfg);
-    const State<T> s = make_state<T>(*st);
-    PolicyEvalW pw{};
-    pw.w1t = (const float*)pol->w1t; pw.b1 = (const float*)pol->b1; pw.w2t = (const float*)pol->w2t;
-    pw.b2 = (const float*)pol->b2; pw.w3 = (const float*)pol->w3; pw.b3 = (const float*)pol->b3;
-    pw.obs_in = obs_in;
-    pw.res_outcome = outcome; pw.res_steps = steps; pw.res_return = total_reward;
-    pw.n_episodes = n_episodes; pw.ep_stride = (int32_t)ep;
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#define X(C_, G_) if constexpr (G_ == 1) { if (C_ == n_traffic) eval_shape<T, FAST, C_>(g, stream, p, rp, s, k0, k1, env_offset, total, n_traffic, n_steps, pw); }
-    ACAS2D_PACKED_SHAPES(X)
-#undef X
-    return check_launch("acas2d_evaluate_policies launch");
-}
-
-template <typename T, bool FAST>
-static int launch_reset_impl(const Acas2dConfig* cfg, const Acas2dState* st, const uint8_t* mask, void* obs,
-                 int32_t do_init, uint64_t seed, int64_t env_offset, int64_t n_envs, int32_t n_traffic,
-                 hipStream_t stream) {
-    if (!cfg) { set_error("acas2d_reset: NULL cfg"); return ACAS2D_EINVAL; }
-    if (!state_complete(st)) { set_error("acas2d_reset: NULL state or a NULL state buffer"); return ACAS2D_EINVAL; }
-    if (n_traffic < 1) { set_error("acas2d_reset: n_traffic = %d", n_traffic); return ACAS2D_EINVAL; }
-    if (n_envs < 0 || env_offset < 0) { set_error("acas2d_reset: negative n_envs / env_offset"); return ACAS2D_EINVAL; }
-    if (n_envs == 0) return ACAS2D_OK;
-    Shape sh;
-    if (int rc = resolve_shape<T>(n_traffic, &sh)) return rc;
-    Geometry g;
-    if (int rc = geometry_for<T>(sh, n_envs, n_traffic, &g)) return rc;
-    const Params<T> p = make_params<T>(*cfg);
-    const StepResetParams<T, true> rp = make_reset_params<double, T>(*cfg);
-    const State<T> s = make_state<T>(*st);
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    if (do_init < 0) { set_error("acas2d_reset: do_init = %d", do_init); return ACAS2D_EINVAL; }
-    if (sh.packed) {
-#define X(C_, G_) if (sh.C == C_ && sh.G == G_) reset_shape<T, FAST, C_, G_, true>(g, stream, p, rp, s, mask, (T*)obs, do_init, k0, k1, env_offset, n_envs, n_traffic);
-        ACAS2D_PACKED_SHAPES(X)
-#undef X
-    } else {
-        switch (sh.G) {
-            case 1:  reset_shape<T, FAST, 1, 1, false>(g, stream, p, rp, s, mask, (T*)obs, do_init, k0, k1, env_offset, n_envs, n_traffic); break;
-            case 4:  reset_shape<T, FAST, 1, 4, false>(g, stream, p, rp, s, mask, (T*)obs, do_init, k0, k1, env_offset, n_envs, n_traffic); break;
-            case 16: reset_shape<T, FAST, 1, 16, false>(g, stream, p, rp, s, mask, (T*)obs, do_init, k0, k1, env_offset, n_envs, n_traffic); break;
-            default: reset_shape<T, FAST, 1, 64, false>(g, stream, p, rp, s, mask, (T*)obs, do_init, k0, k1, env_offset, n_envs, n_traffic); break;
-        }
-    }
-    return check_launch("acas2d_reset launch");
-}
-
-// Formulation (DESIGN.md 4.1): the element type's own -- FAST for float32, EXACT for float64 -- unless the
-// configuration asks for ACAS2D_MATH_FAST, which gives the float64 entry points the algebraic formulation in
-// float64 arithmetic (float32 has no other).  Chosen per call; nothing is cached between calls.
+// One entry point's launch: its arguments (the first block, set by the entry point), then what prepare() derives.
 template <typename T>
-static bool fast_math(const Acas2dConfig* cfg) { return kFast || (cfg && cfg->math == ACAS2D_MATH_FAST); }
+struct Launch {
+    const char* name;                         // the entry point, as its messages name it
+    const Acas2dConfig* cfg;
+    const Acas2dState* st;
+    const Acas2dStepIO* step_io;              // NULL where the entry point takes no StepIO
+    uint64_t seed;
+    int64_t env_offset, n_envs;
+    int32_t N, n_steps;                       // n_steps = 1 for the per-step entry points
+    hipStream_t stream;
+    Shape sh;
+    Geometry g;
+    Params<T> p;
+    State<T> s;
+    StepIO<T> io;
+    uint32_t k0, k1;
+};
+
+// The entry points' words for the rejections they share (each has always said them its own way)
+struct Words {
+    const char* nulls;                        // the pointers the first check names next to cfg
+    const char* sizes;                        // n_traffic or n_steps < 1 (printf: name, n_traffic, n_steps)
+    const char* negative;                     // a negative n_envs / env_offset
+};
+static const char kSizes[] = "%s: n_traffic = %d, n_steps = %d", kNegative[] = "%s: negative n_envs / env_offset";
+
+// The checks every entry point shares, in the order each one runs them, and the launch arguments they share.  The
+// entry point's own parts: `given` (the pointers of words.nulls are there), inputs() (its buffers), shape() (its work
+// shape; its own shape checks) and go() (its checks that need the launch arguments, then the launch).
+template <typename T, typename Inputs, typename PickShape, typename Go>
+static int prepare(Launch<T>& L, const Words& words, bool given, Inputs inputs, PickShape shape, Go go) {
+    if (!L.cfg || !given) return fail("%s: NULL %s", L.name, words.nulls);
+    if (!state_complete(L.st)) return fail("%s: NULL state or a NULL state buffer", L.name);
+    if (int rc = inputs()) return rc;
+    if (L.N < 1 || L.n_steps < 1) return fail(words.sizes, L.name, L.N, L.n_steps);
+    if (L.n_envs < 0 || L.env_offset < 0) return fail(words.negative, L.name);
+    if (L.n_envs == 0) return ACAS2D_OK;
+    if (int rc = shape(&L.sh)) return rc;
+    if (int rc = geometry_for<T>(L.sh, L.n_envs, L.N, &L.g)) return rc;
+    L.p = make_params<T>(*L.cfg);
+    L.s = make_state<T>(*L.st);
+    if (const Acas2dStepIO* io = L.step_io)
+        L.io = StepIO<T>{(const T*)io->actions, (T*)io->obs, (T*)io->reward, io->done, io->outcome, (T*)io->term_obs,
+                         (T*)io->ep_return, io->ep_steps};
+    L.k0 = (uint32_t)L.seed; L.k1 = (uint32_t)(L.seed >> 32);
+    if (int rc = go()) return rc;
+    return check_launch(L.name);
+}
+
+static int require_io(const char* name, const Acas2dStepIO* io) {
+    if (io->actions && io->obs && io->reward && io->done && io->outcome) return ACAS2D_OK;
+    return fail("%s: actions, obs, reward, done and outcome are required", name);
+}
+static int require_actor(const char* name, const Acas2dPolicy* pol) {
+    if (pol->w1t && pol->b1 && pol->w2t && pol->b2 && pol->w3 && pol->b3 && pol->hidden == kPolicyHidden) return ACAS2D_OK;
+    return fail("%s: six weight buffers and hidden == %d are required (got hidden = %d)", name, kPolicyHidden, pol->hidden);
+}
+// the in-kernel policy's work shape: one lane per env, its traffic as one vector
+static int thread_per_env(const char* name, int n_traffic, Shape* sh) {
+    *sh = Shape{n_traffic, 1, true};
+    if (shape_instantiated(*sh)) return ACAS2D_OK;
+    return fail("%s: n_traffic = %d has no thread-per-env shape for this element type", name, n_traffic);
+}
+
+// One step_kernel launch in mode M for L's shape and formulation.  The six preloaded pointers (see step_kernel): the
+// arena mode's four state blocks and the actions, else the traffic arrays, own_x and own_y.
+template <Mode M, typename T, typename PW>
+static int launch_mode(const Launch<T>& L, const PW& pw) {
+    const StepResetParams<T, rollout_mode(M)> rp = make_reset_params<T, rollout_mode(M)>(*L.cfg);
+    const State<T>& s = L.s;
+    const T* const general[6] = {s.trf_x, s.trf_y, s.trf_psi, s.trf_v, s.own_x, s.own_y};
+    const T* const arena[6] = {s.own_x, s.own_v, s.trf_x, s.trf_psi, L.io.actions, nullptr};
+    const T* const* a = M == Mode::Arena ? arena : general;
+    dispatch(*L.cfg, L.sh, [&](auto fast, auto C, auto G, auto packed) {
+        if constexpr ((M != Mode::Arena || (packed && sizeof(T) == 4)) && (!rollout_mode(M) || packed) &&
+                      (!policy_mode(M) || G == 1))
+            hipLaunchKernelGGL((step_kernel<T, C, G, packed, fast, M>), dim3(L.g.grid), dim3(L.g.block), L.g.lds_bytes,
+                               L.stream, a[0], a[1], a[2], a[3], a[4], a[5], (int32_t)L.n_envs, (int32_t)L.g.tile_elems,
+                               L.p, rp, s, L.io, L.k0, L.k1, L.env_offset, L.N, L.n_steps, pw);
+    });
+    return ACAS2D_OK;
+}
 
 template <typename T>
 int launch_step(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dState* st_out, const Acas2dStepIO* io, uint32_t flags,
                 uint64_t seed, int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream) {
-    return fast_math<T>(cfg) ? launch_step_impl<T, true>(cfg, st, st_out, io, flags, seed, env_offset, n_envs, n_traffic, stream)
-                             : launch_step_impl<T, kFast>(cfg, st, st_out, io, flags, seed, env_offset, n_envs, n_traffic, stream);
+    Launch<T> L{"acas2d_step", cfg, st, io, seed, env_offset, n_envs, n_traffic, 1, stream};
+    const auto go = [&] {
+        const bool ar = (flags & ACAS2D_AUTO_RESET) != 0;
+        if (int rc = write_offsets<T>(st, st_out, ar, n_envs, n_traffic, &L.s.w_env, &L.s.w_trf)) return rc;
+        if (!ar) return launch_mode<Mode::Latch>(L, PolicyW{});
+        if (L.sh.packed && arena_layout<T>(L.s, n_envs, n_traffic, L.sh.G)) return launch_mode<Mode::Arena>(L, PolicyW{});
+        return launch_mode<Mode::Step>(L, PolicyW{});
+    };
+    return prepare(L, Words{"cfg / io", "%s: n_traffic = %d (the reference needs traffic[0], game.py:254)", kNegative},
+                   io != nullptr, [&] { return require_io(L.name, io); },
+                   [&](Shape* sh) { return resolve_shape<T>(n_traffic, sh); }, go);
 }
+
 template <typename T>
 int launch_rollout(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, int32_t n_steps,
                    uint64_t seed, int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream) {
-    return fast_math<T>(cfg) ? launch_rollout_impl<T, true>(cfg, st, io, n_steps, seed, env_offset, n_envs, n_traffic, stream)
-                             : launch_rollout_impl<T, kFast>(cfg, st, io, n_steps, seed, env_offset, n_envs, n_traffic, stream);
+    Launch<T> L{"acas2d_rollout", cfg, st, io, seed, env_offset, n_envs, n_traffic, n_steps, stream};
+    const auto shape = [&](Shape* sh) {
+        if (int rc = resolve_shape<T>(n_traffic, sh)) return rc;
+        if (sh->packed) return ACAS2D_OK;
+        return fail("acas2d_rollout: n_traffic = %d has no packed work shape for this element type "
+                    "(needs n_traffic in {1,2,3} or a multiple of %d tiling a wave); use acas2d_step", n_traffic,
+                    16 / (int)sizeof(T));
+    };
+    return prepare(L, Words{"cfg / io", kSizes, kNegative}, io != nullptr, [&] { return require_io(L.name, io); }, shape,
+                   [&] { return launch_mode<Mode::Rollout>(L, PolicyW{}); });
+}
+
+// the actor's weights and the observation its first action is taken on (policy and evaluation launches)
+template <typename PW>
+static PW actor(const Acas2dPolicy* pol, const void* obs_in) {
+    PW pw{};
+    pw.w1t = (const float*)pol->w1t; pw.b1 = (const float*)pol->b1; pw.w2t = (const float*)pol->w2t;
+    pw.b2 = (const float*)pol->b2; pw.w3 = (const float*)pol->w3; pw.b3 = (const float*)pol->b3;
+    pw.obs_in = obs_in;
+    return pw;
+}
+
+// acas2d_rollout_policy_* and, with the actor-critic, acas2d_collect_* (which words most rejections as the former)
+template <typename T>
+static int launch_policy(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dPolicy* pol,
+                         const void* obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset, int64_t n_envs,
+                         int32_t n_traffic, hipStream_t stream, const Acas2dActorCritic* ac) {
+    Launch<T> L{"acas2d_rollout_policy", cfg, st, io, seed, env_offset, n_envs, n_traffic, n_steps, stream};
+    const auto inputs = [&] {
+        if (!io->actions || !io->obs || !io->reward || !io->done || !io->outcome || !obs_in)
+            return fail("%s: obs_in, actions (output), obs, reward, done and outcome are required", L.name);
+        return require_actor(L.name, pol);
+    };
+    const auto go = [&] {
+        PolicyW pw = actor<PolicyW>(pol, obs_in);
+        pw.actions_out = const_cast<void*>(io->actions);
+        if (!ac) return launch_mode<Mode::Policy>(L, pw);
+        if (!ac->v1t || !ac->vb1 || !ac->v2t || !ac->vb2 || !ac->v3 || !ac->vb3 || !ac->log_std || !ac->values || !ac->logp)
+            return fail("acas2d_collect: the value net, log_std, values and logp are required");
+        pw.v1t = (const float*)ac->v1t; pw.vb1 = (const float*)ac->vb1; pw.v2t = (const float*)ac->v2t;
+        pw.vb2 = (const float*)ac->vb2; pw.v3 = (const float*)ac->v3; pw.vb3 = (const float*)ac->vb3;
+        pw.log_std = (const float*)ac->log_std; pw.values_out = ac->values; pw.logp_out = ac->logp;
+        pw.nk0 = (uint32_t)ac->noise_seed; pw.nk1 = (uint32_t)(ac->noise_seed >> 32); pw.noise_step = ac->noise_step;
+        return launch_mode<Mode::Collect>(L, pw);
+    };
+    return prepare(L, Words{"cfg / io / policy", kSizes, kNegative}, io && pol, inputs,
+                   [&](Shape* sh) { return thread_per_env(L.name, n_traffic, sh); }, go);
 }
 template <typename T>
 int launch_rollout_policy(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io,
                           const Acas2dPolicy* pol, const void* obs_in, int32_t n_steps, uint64_t seed,
                           int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream) {
-    return fast_math<T>(cfg)
-               ? launch_rollout_policy_impl<T, true>(cfg, st, io, pol, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream)
-               : launch_rollout_policy_impl<T, kFast>(cfg, st, io, pol, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream);
+    return launch_policy<T>(cfg, st, io, pol, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream, nullptr);
 }
 template <typename T>
 int launch_collect(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
                    const void* obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset, int64_t n_envs,
                    int32_t n_traffic, hipStream_t stream) {
-    if (!ac) { set_error("acas2d_collect: NULL actor-critic"); return ACAS2D_EINVAL; }
-    return fast_math<T>(cfg)
-               ? launch_rollout_policy_impl<T, true>(cfg, st, io, &ac->actor, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream, ac)
-               : launch_rollout_policy_impl<T, kFast>(cfg, st, io, &ac->actor, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream, ac);
+    if (!ac) return fail("acas2d_collect: NULL actor-critic");
+    return launch_policy<T>(cfg, st, io, &ac->actor, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream, ac);
 }
+
+// K stacked policies scored on shared episodes: policy k plays envs [k EP, (k + 1) EP) of the state, EP = n_episodes
+// rounded up to a whole wave; the launch covers those n_policies x EP envs
 template <typename T>
 int launch_evaluate_policies(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
                              int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
                              int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
                              hipStream_t stream) {
-    return fast_math<T>(cfg)
-               ? launch_evaluate_policies_impl<T, true>(cfg, st, n_envs, pol, n_policies, n_episodes, obs_in, n_steps, seed,
-                                                        env_offset, n_traffic, outcome, steps, total_reward, stream)
-               : launch_evaluate_policies_impl<T, kFast>(cfg, st, n_envs, pol, n_policies, n_episodes, obs_in, n_steps, seed,
-                                                         env_offset, n_traffic, outcome, steps, total_reward, stream);
+    const int64_t ep = ((int64_t)n_episodes + 63) / 64 * 64, total = (int64_t)n_policies * ep;
+    Launch<T> L{"acas2d_evaluate_policies", cfg, st, nullptr, seed, env_offset, total, n_traffic, n_steps, stream};
+    const auto inputs = [&] {
+        if (!obs_in || !outcome || !steps || !total_reward)
+            return fail("%s: obs_in and the outcome, steps and total_reward outputs are required", L.name);
+        if (int rc = require_actor(L.name, pol)) return rc;
+        if (n_policies < 1 || n_episodes < 1)
+            return fail("%s: n_policies = %d, n_episodes = %d (at least 1 each)", L.name, n_policies, n_episodes);
+        return ACAS2D_OK;
+    };
+    const auto shape = [&](Shape* sh) {
+        if (int rc = thread_per_env(L.name, n_traffic, sh)) return rc;
+        if (n_envs >= total) return ACAS2D_OK;
+        return fail("acas2d_evaluate_policies: the state holds n_envs = %lld envs, %d policies x %lld (n_episodes = %d rounded up "
+                    "to 64) need %lld", (long long)n_envs, n_policies, (long long)ep, n_episodes, (long long)total);
+    };
+    const auto go = [&] {
+        PolicyEvalW pw = actor<PolicyEvalW>(pol, obs_in);
+        pw.res_outcome = outcome; pw.res_steps = steps; pw.res_return = total_reward;
+        pw.n_episodes = n_episodes; pw.ep_stride = (int32_t)ep;
+        return launch_mode<Mode::Eval>(L, pw);
+    };
+    return prepare(L, Words{"cfg / policies", kSizes, "%s: negative env_offset"}, pol != nullptr, inputs, shape, go);
 }
+
 template <typename T>
 int launch_reset(const Acas2dConfig* cfg, const Acas2dState* st, const uint8_t* mask, void* obs,
                  int32_t do_init, uint64_t seed, int64_t env_offset, int64_t n_envs, int32_t n_traffic,
                  hipStream_t stream) {
-    return fast_math<T>(cfg) ? launch_reset_impl<T, true>(cfg, st, mask, obs, do_init, seed, env_offset, n_envs, n_traffic, stream)
-                             : launch_reset_impl<T, kFast>(cfg, st, mask, obs, do_init, seed, env_offset, n_envs, n_traffic, stream);
+    Launch<T> L{"acas2d_reset", cfg, st, nullptr, seed, env_offset, n_envs, n_traffic, 1, stream};
+    const auto go = [&] {
+        if (do_init < 0) return fail("%s: do_init = %d", L.name, do_init);
+        const StepResetParams<T, true> rp = make_reset_params<T, true>(*cfg);
+        dispatch(*cfg, L.sh, [&](auto fast, auto C, auto G, auto packed) {
+            hipLaunchKernelGGL((reset_kernel<T, C, G, packed, fast>), dim3(L.g.grid), dim3(kBlock), L.g.lds_bytes, stream,
+                               L.p, rp, L.s, mask, (T*)obs, do_init, L.k0, L.k1, env_offset, n_envs, n_traffic, L.g.tile_elems);
+        });
+        return ACAS2D_OK;
+    };
+    return prepare(L, Words{"cfg", "%s: n_traffic = %d", kNegative}, true, [] { return ACAS2D_OK; },
+                   [&](Shape* sh) { return resolve_shape<T>(n_traffic, sh); }, go);
 }
 
 // 1 when acas2d_step_* (auto-reset) would take the kernel whose loads all go through preloaded base pointers for this
@@ -542,5 +467,15 @@ int shape_geometry(int64_t n_envs, int32_t n_traffic, int32_t* lanes, int32_t* p
     *lanes = sh.G; *per_lane = sh.packed ? sh.C : -1; *grid = g.grid;
     return ACAS2D_OK;
 }
+
+// the launchers of this unit's element type (acas2d_kernels.hpp declares them, acas2d_api.hip calls them)
+template decltype(launch_step<Elem>) launch_step<Elem>;
+template decltype(launch_rollout<Elem>) launch_rollout<Elem>;
+template decltype(launch_rollout_policy<Elem>) launch_rollout_policy<Elem>;
+template decltype(launch_collect<Elem>) launch_collect<Elem>;
+template decltype(launch_evaluate_policies<Elem>) launch_evaluate_policies<Elem>;
+template decltype(launch_reset<Elem>) launch_reset<Elem>;
+template decltype(shape_geometry<Elem>) shape_geometry<Elem>;
+template decltype(state_consecutive<Elem>) state_consecutive<Elem>;
 
 }  // namespace acas2d

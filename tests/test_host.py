@@ -123,6 +123,35 @@ def test_c_abi_argument_validation_needs_no_gpu(g):
     assert step(gen2(steps=base + 4 * (E - 1), **near)) == -22 and b"overlaps" in L.acas2d_last_error()
     assert L.acas2d_reset_f32(C.byref(cfg), C.byref(st), None, None, 1, 0, 0, 4, 1, None) == -22
     assert L.acas2d_reset_f32(C.byref(cfg), C.byref(full), None, None, 1, 0, 0, 0, 1, None) == 0
+    reset = lambda do_init=1, off=0, n=4, N=1: L.acas2d_reset_f64(C.byref(cfg), C.byref(full), None, None, do_init, 0, off,  # noqa: E731
+                                                                 n, N, None)
+    assert reset(N=0) == -22 and L.acas2d_last_error() == b"acas2d_reset: n_traffic = 0"
+    assert reset(off=-1) == -22 and L.acas2d_last_error() == b"acas2d_reset: negative n_envs / env_offset"
+    assert reset(do_init=-1) == -22 and L.acas2d_last_error() == b"acas2d_reset: do_init = -1"
+    assert reset(do_init=-1, n=0) == 0                         # no envs: done before do_init is looked at
+    # acas2d_rollout_*: the shared rejections in its own words, and the packed-only work shape
+    roll = lambda T=4, N=8, n=4, off=0, io=C.byref(io_ok), c=C.byref(cfg): L.acas2d_rollout_f32(c, C.byref(full), io, T, 0,  # noqa: E731
+                                                                                               off, n, N, None)
+    assert roll(c=None) == -22 and L.acas2d_last_error() == b"acas2d_rollout: NULL cfg / io"
+    assert roll(io=None) == -22 and L.acas2d_last_error() == b"acas2d_rollout: NULL cfg / io"
+    assert roll(io=C.byref(g.native.CStepIO(*([base] * 4)))) == -22 and b"outcome are required" in L.acas2d_last_error()
+    assert roll(T=0) == -22 and L.acas2d_last_error() == b"acas2d_rollout: n_traffic = 8, n_steps = 0"
+    assert roll(N=0) == -22 and L.acas2d_last_error() == b"acas2d_rollout: n_traffic = 0, n_steps = 4"
+    assert roll(n=-1) == -22 and L.acas2d_last_error() == b"acas2d_rollout: negative n_envs / env_offset"
+    assert roll(n=0) == 0
+    assert roll(N=5) == -22 and b"acas2d_rollout: n_traffic = 5 has no packed work shape" in L.acas2d_last_error()
+    # acas2d_rollout_policy_* / acas2d_collect_* (which words these as the former): NULL pointers and obs_in
+    pol = g.native.CPolicy(*([base] * 6), 64, 0)
+    ac = g.native.CActorCritic(pol, *([base] * 9), 7, 0)
+    policy = lambda p=C.byref(pol), io=C.byref(io_ok), obs=base: L.acas2d_rollout_policy_f64(C.byref(cfg), C.byref(full), io,  # noqa: E731
+                                                                                              p, obs, 4, 0, 0, 4, 4, None)
+    assert policy(p=None) == -22 and L.acas2d_last_error() == b"acas2d_rollout_policy: NULL cfg / io / policy"
+    assert policy(io=None) == -22 and L.acas2d_last_error() == b"acas2d_rollout_policy: NULL cfg / io / policy"
+    assert policy(obs=None) == -22 and b"rollout_policy: obs_in, actions (output), obs" in L.acas2d_last_error()
+    assert L.acas2d_collect_f32(None, C.byref(full), C.byref(io_ok), C.byref(ac), base, 4, 0, 0, 4, 4, None) == -22
+    assert L.acas2d_last_error() == b"acas2d_rollout_policy: NULL cfg / io / policy"
+    assert L.acas2d_collect_f32(C.byref(cfg), C.byref(full), C.byref(io_ok), C.byref(ac), None, 4, 0, 0, 4, 4, None) == -22
+    assert b"acas2d_rollout_policy: obs_in, actions (output)" in L.acas2d_last_error()
     with pytest.raises(RuntimeError, match="acas2d: error -22"):
         g.native.check(L.acas2d_launch_geometry(-1, 1, 4, None, None, None, None))
     # headline config: 4 traffic per lane as one 16-byte vector, 2 lanes per env, 32 envs per wave

@@ -80,8 +80,8 @@ def test_evaluate_policies_validation_needs_no_gpu(g):
         cfg = g.ACAS2DConfig(n_traffic=N).to_c()
 
         def call(cfg_=C.byref(cfg), state=C.byref(st), n_envs=256, p=None, K=2, E=100, obs=a, T=10, n=N,
-                 outcome=a, steps=a, ret=a):
-            return fn(cfg_, state, n_envs, C.byref(p or pol()), K, E, obs, T, 13, 0, n, outcome, steps, ret, None)
+                 outcome=a, steps=a, ret=a, off=0):
+            return fn(cfg_, state, n_envs, C.byref(p or pol()), K, E, obs, T, 13, off, n, outcome, steps, ret, None)
 
         def rejects(msg, **kw):
             assert call(**kw) == -22, (dt, kw)
@@ -101,6 +101,7 @@ def test_evaluate_policies_validation_needs_no_gpu(g):
         rejects("n_episodes = 0", E=0)
         rejects("n_steps = 0", T=0)
         rejects("n_traffic = 0", n=0)
+        rejects("acas2d_evaluate_policies: negative env_offset", off=-1)
         rejects("no thread-per-env shape", n=badN)
         # K x round_up(E, 64) envs: 2 x 128 = 256 fit, 255 do not; 3 x 64 = 192 at E = 37
         rejects("need 256", n_envs=255)

@@ -6,7 +6,8 @@ python3 - "$f" <<'PY'
 import csv,sys,statistics,re
 agg={}
 for r in csv.DictReader(open(sys.argv[1])):
-    if re.search(r"step_kernel<float, 4, 2, true, true, true(, false)+>", r["Kernel_Name"]):
+    # the per-step auto-reset kernel of the headline shape: Mode::Step or Mode::Arena
+    if re.search(r"step_kernel<float, 4, 2, true, true, \(acas2d::Mode\)[12]>", r["Kernel_Name"]):
         agg.setdefault(r["Counter_Name"],[]).append(float(r["Counter_Value"]))
 for k,v in agg.items(): print(k, len(v), statistics.mean(v[len(v)//4:]))
 PY

@@ -8,7 +8,12 @@ python3 $R/bench.py --steps 2000 --warmup 200 --no-extra --no-cpu-baseline --no-
 for i in 1 2; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace$i -- python3 $R/bench.py --steps 2000 --warmup 200 --no-extra --no-cpu-baseline --no-rollout 2>/dev/null | grep "^{" > $O/bench_traced$i.json
   f=$(find $O/trace$i -name '*kernel_stats.csv' | head -1); cp "$f" $O/kernel_stats$i.csv; rm -rf $O/trace$i
-  grep "step_kernel<float, 4, 2" $O/kernel_stats$i.csv | cut -d, -f1-12 | rev | cut -d'"' -f1 | rev
+  python3 - $O/kernel_stats$i.csv <<'PY'
+import csv, sys
+for r in csv.DictReader(open(sys.argv[1])):      # step_kernel<float, 4, 2, true, true, (acas2d::Mode)M>: every mode
+    if r["Name"].startswith("void acas2d::step_kernel<float, 4, 2,"):
+        print(r["Name"][:r["Name"].index(">(") + 1], r["Calls"], r["AverageNs"], r["MinNs"], r["MaxNs"], r["StdDev"])
+PY
 done
 python3 - $O <<'PY'
 import json, sys
