@@ -913,9 +913,13 @@ __device__ __forceinline__ Seen<T> observe(const Params<T>& p, const State<T>& s
                     psi_changed |= (ps.x != ps_in.x) | (ps.y != ps_in.y);
                 }
                 if (tc != nullptr) {
+                    // The window maps a heading a hair below 0 to exactly 360.0f (-tiny + 360 rounds up), which the next
+                    // step's wrap turns into 0: such a heading is no fixed point of the wrap, so its lane recomputes
+                    // next step as a per-step launch does, instead of keeping 360 in registers for the rest of the rollout.
+                    bool fixed = true;
 #pragma unroll
-                    for (int k = 0; k < C; ++k) { tc->st[k] = st[k]; tc->ct[k] = ct[k]; }
-                    tc->valid = true;
+                    for (int k = 0; k < C; ++k) { tc->st[k] = st[k]; tc->ct[k] = ct[k]; fixed &= tr.psi.v[k] != T(360); }
+                    tc->valid = fixed;
                 }
             }
 #pragma unroll

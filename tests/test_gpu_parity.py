@@ -112,9 +112,19 @@ def grazing(fx_obs, N, cfg, band):
         return (np.abs(d_sep - cfg.collision_dist) < band).any(1) | (np.abs(d_goal - cfg.goal_radius) < band)
 
 
+def _fixture_shapes(dtype):
+    """(N, shape) of every work shape with an edge fixture (N in 1, 3, 8, 64); the default shape keeps the id "N".  The
+    float64 rows are the same in both formulations: the `math` fixture picks one."""
+    rows = [s for s in H.SHAPES if s.dtype == dtype and s.math == ("fast" if dtype == "float32" else "exact")
+            and s.n_traffic in (1, 3, 8, 64)]
+    return [pytest.param(s.n_traffic, s, id=str(s.n_traffic) if s.override is None else "%d-%s" % (s.n_traffic, s.override))
+            for s in rows]
+
+
 # ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("N", (1, 3, 8, 64))
-def test_f64_edge_vectors(g, O, N, math):
+@pytest.mark.parametrize("N,shape", _fixture_shapes("float64"))
+def test_f64_edge_vectors(g, O, monkeypatch, N, shape, math):
+    _use_shape(g, monkeypatch, shape)
     fx = H.load("ref_edge_n%d.npz" % N)
     E = len(fx["action"])
     env = GpuEngine(g, E, N, math=math)
@@ -292,8 +302,9 @@ def test_testing_main_record_columns_vs_reference(g, N, tmp_path):
 
 
 # ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("N", (1, 3, 8, 64))
-def test_f32_single_step_vs_f64_oracle(g, O, N):
+@pytest.mark.parametrize("N,shape", _fixture_shapes("float32"))
+def test_f32_single_step_vs_f64_oracle(g, O, monkeypatch, N, shape):
+    _use_shape(g, monkeypatch, shape)
     fx = H.load("ref_edge_n%d.npz" % N)
     sel = ~np.isnan(fx["obs"]).any(1)
     own = fx["own"][sel].astype(np.float32).astype(np.float64)        # float32-representable inputs
@@ -334,11 +345,12 @@ def test_f32_single_step_vs_f64_oracle(g, O, N):
     assert np.abs(env.own_psi - ref.own_psi).max() <= 3.1e-5             # 1 ulp of float32(360)
 
 
-@pytest.mark.parametrize("N", (1, 3, 8, 64))
-def test_f32_reproduces_the_reference_nan_pattern(g, N):
+@pytest.mark.parametrize("N,shape", _fixture_shapes("float32"))
+def test_f32_reproduces_the_reference_nan_pattern(g, monkeypatch, N, shape):
     """Parallel flight (identical heading and speed) makes the reference's relative velocity 0/0:
     d_cpa is NaN (kinematics.py:48) and so is the reward whenever it reads traffic[0]'s d_cpa.  The
     algebraic float32 formulation (0 * inf) must put NaN in exactly the same places."""
+    _use_shape(g, monkeypatch, shape)
     fx = H.load("ref_edge_n%d.npz" % N)
     rows = np.isnan(fx["obs"]).any(1)
     assert rows.sum() >= 8
@@ -1021,7 +1033,7 @@ def _new_f32_totals():
                 bounds=None)
 
 
-def _check_f32_step_vs_oracle(env, chk, stepped, got, N, tot, t=0):
+def _check_f32_step_vs_oracle(env, chk, stepped, got, N, tot, t=0, in_band=None):
     """One float32 step against the float64 oracle `chk` stepped from the identical (float32-representable) state:
     stepped = chk.step()'s (o, r, d, oc), got = the engine's (obs, rew, done, outcome).  done / outcome masks equal
     outside a 1e-3 px band around the thresholds; observations, rewards and positions of the envs that go on within the
@@ -1039,7 +1051,10 @@ def _check_f32_step_vs_oracle(env, chk, stepped, got, N, tot, t=0):
     [2.5e-4], headings 6e-5 (2 ulp of 360); speeds bit-equal when the speed factor is a single value [always], else
     within (max - min) airspeed 2^-24 + 2 ulp of max airspeed.  The d_cpa entry: 2e-5 [2e-5], plus under a speed range
     d (max airspeed 2^-20) / (|v12| d_cpa_max) per entry (see below).  At most a fraction 1e-3 [1e-3] of the envs in the
-    band, times the collision distance over the traffic's draw area relative to the default's."""
+    band, times the collision distance over the traffic's draw area relative to the default's -- or, with `in_band` (bool [E]),
+    exactly the envs it names (hand-placed states, tests/edge_states.py).  With a latching `chk` (auto_reset off) the
+    finished envs are checked like the others: their state latches, nothing is reset; the terminal reward to the return's
+    bound."""
     o, r, d, oc = stepped
     obs, rew, done, outcome = got
     E = len(d)
@@ -1050,13 +1065,20 @@ def _check_f32_step_vs_oracle(env, chk, stepped, got, N, tot, t=0):
     cpa, vcl = (col >= 5) & ((col - 5) % 3 == 1), (col >= 5) & ((col - 5) % 3 == 2)
     d = d.astype(bool)
     # ---- masks: bit-exact outside the band
-    ok = ~grazing(np.where(d[:, None], chk.term_obs, o), N, cfgc, 1e-3)
+    ok = ~grazing(np.where(d[:, None] & chk.auto_reset, chk.term_obs, o), N, cfgc, 1e-3)
     mism = (done.astype(bool) != d) | (outcome != oc)
     tot["mask_mismatch"] += int((mism & ok).sum()); tot["in_band"] += int((~ok).sum()); tot["steps"] += E
     assert not (mism & ok).any(), (t, int((mism & ok).sum()))
-    assert ok.mean() > 1 - bnd["band"], (t, ok.mean(), bnd["band"])
+    if in_band is None:
+        assert ok.mean() > 1 - bnd["band"], (t, ok.mean(), bnd["band"])
+    else:
+        assert np.array_equal(~ok, in_band), (t, int((~ok).sum()), int(in_band.sum()))
     same = ok & ~mism
     go, fin = same & ~d, same & d
+    latch = same & d if not chk.auto_reset else np.zeros_like(d)
+    if latch.any():
+        assert np.array_equal(env.status[same], chk.status[same])
+        go, fin = same, np.zeros_like(d)
     tot["finished"] += int(fin.sum())
     tot["outcomes"] |= set(int(k) for k in np.unique(oc[fin]))
     # ---- envs that go on: the step itself
@@ -1082,8 +1104,12 @@ def _check_f32_step_vs_oracle(env, chk, stepped, got, N, tot, t=0):
         tot["cpa_ratio"] = max(tot["cpa_ratio"], float((err[:, cpa] / cpa_tol)[go][well[go]].max(initial=0.0)))
         assert e_plain.max() < 1e-5 and e_vc.max(initial=0.0) < 1e-5 and cpa_excess.max(initial=-1.0) < 0, \
             (t, e_plain.max(), e_vc.max(initial=0.0), e_cpa.max(initial=0.0))
-        nt = go & well[:, 0] & ~near[:, 0]
+        nt = go & ~latch & well[:, 0] & ~near[:, 0]
         e_rew = np.abs(rew[nt] - r[nt])
+        lt = latch & well[:, 0] & ~near[:, 0]
+        e_lret = np.abs(rew[lt] - r[lt])
+        tot["e_ret"] = max(tot["e_ret"], float(e_lret.max(initial=0.0)))
+        assert e_lret.max(initial=0.0) <= bnd["ret"], (t, e_lret.max(), bnd["ret"])
         tot["e_rew"] = max(tot["e_rew"], float(e_rew.max(initial=0.0)))
         # (1e-5 for 99.99 % of the env-steps, the worst below 5e-5: the reward amplifies the d_cpa error up to 39 x --
         #  see test_f32_statistical_single_step_vs_f64_oracle; a percentile needs the samples to carry it)
@@ -2190,3 +2216,249 @@ def test_collector_outputs_past_2_to_the_31_elements_replay_on_a_twin(g, monkeyp
     assert out["obs"].numel() >= 2 ** 31
     assert H.replay_collect_on_twin(env, twin, out) > E
     _print_peak("collector past 2^31 elements")
+
+
+# ---- hand-placed edge states on every work shape (tests/edge_states.py; tests/test_edge_states.py holds the batch to its
+# labels on the CPU oracle) ------------------------------------------------------------------------------------------------
+def _edge_config(O, name):
+    """(ACAS2DConfig keywords, OracleConfig) of the configuration `name`: "default" or one of helpers.NONDEFAULT_CONFIGS."""
+    import gym_acas2d_amd as g
+    kw = {} if name == "default" else H.NONDEFAULT_CONFIGS[name]
+    return kw, H.oracle_config(O, g.ACAS2DConfig(n_traffic=1, **kw))
+
+
+_EDGE_BATCHES = {}
+
+
+def _edge_batch(O, N, name):
+    import edge_states as ES
+    if (N, name) not in _EDGE_BATCHES:
+        _EDGE_BATCHES[(N, name)] = ES.edge_batch(N, _edge_config(O, name)[1], seed=N)
+    return _EDGE_BATCHES[(N, name)]
+
+
+def _f32r(a):
+    return np.asarray(a).astype(np.float32).astype(np.float64)
+
+
+class _RolloutView:
+    """Step t of a rollout() dict behind the engine attributes the checkers read (the state is the env's own)."""
+
+    def __init__(self, env, out, t=0):
+        self.env, self.out, self.t = env, out, t
+
+    def __getattr__(self, name):
+        key = {"term_obs": "terminal_observation", "ep_return": "episode_return", "ep_steps": "episode_steps"}.get(name)
+        if key is None:
+            return getattr(self.env, name)
+        return GpuEngine._np(self.out[key][self.t])
+
+
+def _rollout_outputs(out, t=0):
+    d = out["done"][t].cpu().numpy().astype(np.uint8)
+    return (GpuEngine._np(out["obs"][t]), GpuEngine._np(out["reward"][t]), d, out["outcome"][t].cpu().numpy())
+
+
+def _check_f64_edge_step(b, env, ref, got, stepped, auto_reset, tot):
+    """One float64 step of the edge batch against the oracle stepped from the same state: obs, reward, positions and
+    headings to 1e-9, NaN exactly where the oracle has it (obs, reward, terminal observation, return), masks and outcome
+    bit-exact outside the 1e-9 band -- in which exactly the placed envs lie --, the fresh episode of every finished env bit
+    for bit.  At the mirror-heading slots only, the sign of d_cpa is exempt (its magnitude is not): v12x is an exact 0 or
+    +-1 ulp there, a coin toss of the host's cos that the device's sincos -- in either formulation -- need not repeat
+    (test_f64_edge_vectors)."""
+    import edge_states as ES
+    obs, rew, done, outcome = got
+    o, r, d, oc = stepped
+    band = ES.placed_in_band(b, ES.F64_BAND)
+    assert not (((done != d) | (outcome != oc)) & ~band).any()
+    same = (done == d) & (outcome == oc)
+    tot["band"] += int(band.sum()); tot["band_differs"] += int((~same).sum())
+    want = o.copy()
+    ms = ES.labels(b, "mirror_slot").astype(int)
+    coin = np.nonzero(ms >= 0)[0]
+    col = 5 + 3 * ms[coin] + 1
+    flip = (d[coin] == 0) & (np.sign(obs[coin, col]) != np.sign(want[coin, col]))
+    want[coin[flip], col[flip]] *= -1.0
+    tot["sign_flips"] = tot.get("sign_flips", 0) + int(flip.sum())
+    assert np.array_equal(np.isnan(obs[same]), np.isnan(o[same])) and np.array_equal(np.isnan(rew), np.isnan(r))
+    tot["nan"] += int(np.isnan(o[same]).sum())
+    np.testing.assert_allclose(obs[same], want[same], rtol=0, atol=1e-9, equal_nan=True)
+    np.testing.assert_allclose(rew[same], r[same], rtol=0, atol=1e-9, equal_nan=True)
+    go = same & ((d == 0) | (not auto_reset))
+    for name in ("own_x", "own_y", "own_psi", "trf_x", "trf_y", "trf_psi"):
+        np.testing.assert_allclose(getattr(env, name)[go], getattr(ref, name)[go], rtol=0, atol=1e-9, err_msg=name)
+    assert np.array_equal(env.steps[same], ref.steps[same]) and np.array_equal(env.episode[same], ref.episode[same])
+    if not auto_reset:
+        assert np.array_equal(env.status[same], ref.status[same])
+        return
+    fin = same & (d != 0)
+    tot["finished"] += int(fin.sum())
+    if fin.any():
+        assert np.array_equal(np.isnan(env.term_obs[fin]), np.isnan(ref.term_obs[fin]))
+        assert np.array_equal(np.isnan(env.ep_return[fin]), np.isnan(ref.ep_return[fin]))
+        tot["nan"] += int(np.isnan(ref.term_obs[fin]).sum())
+        np.testing.assert_allclose(env.term_obs[fin], ref.term_obs[fin], rtol=0, atol=1e-9, equal_nan=True)
+        np.testing.assert_allclose(env.ep_return[fin], ref.ep_return[fin], rtol=0, atol=1e-9, equal_nan=True)
+        assert np.array_equal(env.ep_steps[fin], ref.ep_steps[fin])
+        for name in _STATE:
+            assert np.array_equal(getattr(env, name)[fin], getattr(ref, name)[fin]), name
+
+
+def _check_f32_edge_step(b, env, chk, got, stepped, tot, t=0):
+    """_check_f32_step_vs_oracle with the float32 band (1e-3) holding exactly the placed envs, and on top: the NaN pattern
+    of every slot exact (obs, reward; terminal observation and return where finished), every traffic heading the oracle's
+    wrapped heading rounded to float32 (a hair below 0 wraps to 360 - 2^-40 in float64: 360.0f, what the float32 wrap
+    gives), the player's within one float32 ulp of 360."""
+    import edge_states as ES
+    obs, rew, done, outcome = got
+    o, r, d, oc = stepped
+    go, fin = _check_f32_step_vs_oracle(env, chk, stepped, got, b.N, tot, t, in_band=ES.placed_in_band(b, ES.F32_BAND))
+    same = go | fin
+    assert np.array_equal(np.isnan(obs[same]), np.isnan(o[same])) and np.array_equal(np.isnan(rew[same]), np.isnan(r[same]))
+    tot["nan"] = tot.get("nan", 0) + int(np.isnan(o[same]).sum())
+    if chk.auto_reset and fin.any():
+        assert np.array_equal(np.isnan(env.term_obs[fin]), np.isnan(chk.term_obs[fin]))
+        assert np.array_equal(np.isnan(env.ep_return[fin]), np.isnan(chk.ep_return[fin]))
+        tot["nan"] += int(np.isnan(chk.term_obs[fin]).sum())
+    assert np.array_equal(env.trf_psi[go], _f32r(chk.trf_psi[go]))
+    dpsi = np.abs(env.own_psi[go] - chk.own_psi[go])
+    assert np.minimum(dpsi, 360 - dpsi).max() <= 3.1e-5
+
+
+def _edge_rollout_equals_steps(g, shape, b, kw, state, T=3):
+    """rollout(T) from the injected edge state == T step() calls bit for bit, the written-back headings included."""
+    a = _shape_env(g, shape, len(b.case), config=kw, double_buffer=False)
+    c = _shape_env(g, shape, len(b.case), config=kw, double_buffer=False)
+    for v in (a, c):
+        v.set_state(*state[:4], observe=False)
+    gen = torch.Generator(device="cuda:0").manual_seed(6)
+    actions = torch.rand(T, len(b.case), generator=gen, device="cuda:0", dtype=a.dtype) * 2 - 1
+    actions[0] = torch.as_tensor(state[4], device="cuda:0", dtype=a.dtype)
+    out = a.rollout(actions, keep_terminal_obs=True)
+    for t in range(T):
+        obs, rew, done, infos = c.step(actions[t])
+        assert bits_equal(out["obs"][t], obs) and bits_equal(out["reward"][t], rew), t
+        assert torch.equal(out["done"][t], done) and torch.equal(out["outcome"][t], infos.outcome), t
+        for k, want in (("episode_return", infos.episode_return), ("episode_steps", infos.episode_steps),
+                        ("terminal_observation", infos.terminal_observation)):
+            assert bits_equal(out[k][t][done], want[done]), (t, k)
+    _same_state(a, c)
+
+
+_EDGE_CASES = [(s, "default") for s in H.SHAPES] + [(s, "small") for s in H.SHAPES if s.override is None]
+
+
+@pytest.mark.parametrize("shape,config", _EDGE_CASES, ids=["%s-%s" % (s.id, c) for s, c in _EDGE_CASES])
+def test_every_shape_on_edge_states_vs_oracle(g, O, monkeypatch, shape, config):
+    """The edge batch of tests/edge_states.py -- a collision at every slot at +-1e-8 / 1e-2 / 5 px of the threshold (and
+    0, +-1e-10: in the band), parallel flight (NaN d_cpa) and mirror headings at every slot, injected headings at every
+    slot, goal thresholds, timeout precedence, heading wraps, off-plan states and odd speeds, each case at the first and
+    the last env of a wave and in a partial last wave -- through every path of the work shape against the oracle: the
+    latching step, the auto-reset step in place and double-buffered, float32 packed shapes in the consecutive-layout
+    kernel and in the general one, and the fused rollout (T = 1 against the oracle, T = 3 bit for bit against steps)."""
+    import edge_states as ES
+    _use_shape(g, monkeypatch, shape)
+    N = shape.n_traffic
+    kw, ocfg = _edge_config(O, config)
+    b = _edge_batch(O, N, config)
+    E = len(b.case)
+    f32 = shape.dtype == "float32"
+    rnd = _f32r if f32 else (lambda a: np.asarray(a, np.float64))
+    state = (rnd(b.own), rnd(b.trf), rnd(b.goal), b.steps)
+    act = rnd(b.action)
+    tot = dict(band=0, band_differs=0, nan=0, finished=0) if not f32 else _new_f32_totals()
+    paths = []
+
+    def oracle(auto_reset, n=E):
+        ref = O.OracleEnvs(n, N, seed=21, env_offset=37, auto_reset=auto_reset, config=ocfg)
+        ref.set_state(state[0][:n], state[1][:n], state[2][:n], state[3][:n])
+        return ref, ref.step(act[:n])[:4]
+
+    def check(env, ref, got, stepped, auto_reset, n=E):
+        sub = b._replace(own=b.own[:n], case=b.case[:n]) if n != E else b
+        if f32:
+            _check_f32_edge_step(sub, env, ref, got, stepped, tot)
+        else:
+            _check_f64_edge_step(sub, env, ref, got, stepped, auto_reset, tot)
+
+    for auto_reset, db in ((False, False), (True, False), (True, True)):
+        ref, stepped = oracle(auto_reset)
+        v = _shape_env(g, shape, E, auto_reset=auto_reset, config=kw, double_buffer=db)
+        assert not v.consecutive_layout                   # E is not whole workgroups: the general kernel
+        env = _engine(v)
+        env.set_state(*state)
+        check(env, ref, env.step(act)[:4], stepped, auto_reset)
+        paths.append("latching" if not auto_reset else "double-buffered" if db else "in place")
+    if f32 and shape.packed:                               # whole eight-workgroup groups: arena kernel and general kernel
+        n = b.whole
+        ref, stepped = oracle(True, n)
+        for arena in (True, False):
+            v = _shape_env(g, shape, n, config=kw)
+            if arena:
+                monkeypatch.delenv("ACAS2D_NO_ARENA", raising=False)
+            else:
+                monkeypatch.setenv("ACAS2D_NO_ARENA", "1")
+            assert v.consecutive_layout == arena
+            env = _engine(v)
+            env.set_state(state[0][:n], state[1][:n], state[2][:n], state[3][:n])
+            check(env, ref, env.step(act[:n])[:4], stepped, True, n)
+            paths.append("arena" if arena else "general, whole groups")
+        monkeypatch.delenv("ACAS2D_NO_ARENA", raising=False)
+    if shape.packed:
+        ref, stepped = oracle(True)
+        v = _shape_env(g, shape, E, config=kw, double_buffer=False)
+        env = _engine(v)
+        env.set_state(*state)
+        out = v.rollout(torch.as_tensor(act, device="cuda:0", dtype=v.dtype)[None], keep_terminal_obs=True)
+        check(_RolloutView(env, out), ref, _rollout_outputs(out), stepped, True)
+        _edge_rollout_equals_steps(g, shape, b, kw, state + (act,))
+        paths.append("rollout")
+    placed = ES.placed_in_band(b, ES.F32_BAND if f32 else ES.F64_BAND)
+    print("edge states on %s (%s): %d envs, %d cases, paths %s; in-band rows %d per path (placed %d); NaN entries matched %d; "
+          "mirror d_cpa signs exempted %d" % (shape.id, config, E, len(b.cases), ", ".join(paths),
+                                              (tot["in_band"] if f32 else tot["band"]) // len(paths), int(placed.sum()),
+                                              tot["nan"], tot.get("sign_flips", 0)))
+    if f32:
+        _print_f32_totals("edge states on %s (%s)" % (shape.id, config), tot)
+    assert tot["nan"] > 0 and tot["finished"] > 0
+
+
+def _edge_shape_groups():
+    """(dtype_name, N, ACAS2D_SHAPE values) of every (dtype, formulation, N) with more than one work shape, plus the
+    generic overrides of test_results_do_not_depend_on_the_work_shape (N = 8 and 64)."""
+    extra = {("float32", 8): ("generic,4",), ("float32", 64): ("generic,16", "generic,64"),
+             ("float64", 8): ("generic,4",), ("float64fast", 8): ("generic,4",)}
+    groups = {}
+    for s in H.SHAPES:
+        groups.setdefault((s.dtype_name, s.n_traffic), []).append(s.override)
+    return [(k[0], k[1], tuple(v) + extra.get(k, ())) for k, v in groups.items() if len(v) + len(extra.get(k, ())) > 1]
+
+
+@pytest.mark.parametrize("dtype_name,N,shapes", _edge_shape_groups(), ids=["%s-N%d" % k[:2] for k in _edge_shape_groups()])
+def test_edge_states_do_not_depend_on_the_work_shape(g, O, monkeypatch, dtype_name, N, shapes):
+    """test_results_do_not_depend_on_the_work_shape on the edge batch: the latching and the auto-reset step of every work
+    shape of (dtype, formulation, N) leave the same outputs and state, bit for bit."""
+    dtype, cfg = _dtype_and_config(g, dtype_name, N)
+    b = _edge_batch(O, N, "default")
+    E = len(b.case)
+    f = _f32r if dtype == torch.float32 else (lambda a: np.asarray(a, np.float64))
+    ref = None
+    for sh in shapes:
+        if sh is None:
+            monkeypatch.delenv("ACAS2D_SHAPE", raising=False)
+        else:
+            monkeypatch.setenv("ACAS2D_SHAPE", sh)
+        got = []
+        for auto_reset in (False, True):
+            v = g.ACAS2DVecEnv(E, N, device="cuda:0", dtype=dtype, seed=21, env_offset=37, auto_reset=auto_reset, config=cfg)
+            v.set_state(f(b.own), f(b.trf), f(b.goal), b.steps, observe=False)
+            obs, rew, done, infos = v.step(torch.as_tensor(f(b.action), device="cuda:0", dtype=dtype))
+            got += [obs.clone(), rew.clone(), done.clone(), infos.outcome.clone()]
+            if auto_reset:
+                got += [v.outputs[k].clone() for k in ("terminal_observation", "episode_return", "episode_steps")]
+            got += [getattr(v, n).clone() for n in _STATE + ("steps", "total_reward", "episode", "status")]
+        if ref is None:
+            ref = got
+        else:
+            for k, (x, y) in enumerate(zip(ref, got)):
+                assert bits_equal(x, y), (sh, k)
