@@ -102,6 +102,25 @@ int acas2d_evaluate_policies_f64(const Acas2dConfig* cfg, const Acas2dState* sta
     return launch_evaluate_policies<double>(cfg, state, n_envs, policies, n_policies, n_episodes, obs_in, n_steps, seed, env_offset,
                                             n_traffic, outcome, steps, total_reward, (hipStream_t)stream);
 }
+// the group-cooperative policy (float32, n_traffic in {8, 16, 32, 64}): the siblings' launches at the packed shapes
+int acas2d_rollout_policy_group_f32(const Acas2dConfig* cfg, const Acas2dState* state, const Acas2dStepIO* io,
+                                    const Acas2dPolicy* policy, const void* obs_in, int32_t n_steps, uint64_t seed,
+                                    int64_t env_offset, int64_t n_envs, int32_t n_traffic, void* stream) {
+    return launch_rollout_policy_group<float>(cfg, state, io, policy, obs_in, n_steps, seed, env_offset, n_envs, n_traffic,
+                                              (hipStream_t)stream);
+}
+int acas2d_collect_group_f32(const Acas2dConfig* cfg, const Acas2dState* state, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
+                             const void* obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset, int64_t n_envs,
+                             int32_t n_traffic, void* stream) {
+    return launch_collect_group<float>(cfg, state, io, ac, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, (hipStream_t)stream);
+}
+int acas2d_evaluate_policies_group_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs,
+                                       const Acas2dPolicy* policies, int32_t n_policies, int32_t n_episodes, const void* obs_in,
+                                       int32_t n_steps, uint64_t seed, int64_t env_offset, int32_t n_traffic, uint8_t* outcome,
+                                       int32_t* steps, void* total_reward, void* stream) {
+    return launch_evaluate_policies<float>(cfg, state, n_envs, policies, n_policies, n_episodes, obs_in, n_steps, seed, env_offset,
+                                           n_traffic, outcome, steps, total_reward, (hipStream_t)stream, true);
+}
 int acas2d_reset_f32(const Acas2dConfig* cfg, const Acas2dState* state, const uint8_t* mask, void* obs,
                      int32_t do_init, uint64_t seed, int64_t env_offset, int64_t n_envs, int32_t n_traffic,
                      void* stream) {

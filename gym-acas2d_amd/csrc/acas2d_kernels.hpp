@@ -46,6 +46,10 @@ constexpr int kWavesPerBlock = kBlock / 64;
 
 // constant address space: wave-uniform loads through it are scalar loads (s_load_*)
 #define ACAS2D_AS4 __attribute__((address_space(4)))
+// global address space: a pointer that went through an empty asm (the per-step laundering of the policy's weights) is
+// a generic one to the compiler, and loads through it are FLAT loads, which count against the LDS queue as well and are
+// issued one at a time between the LDS reads of the same loop
+#define ACAS2D_AS1 __attribute__((address_space(1)))
 
 #include "acas2d_diag.hpp"   // ACAS2D_STAMP(): empty in the product build
 
@@ -1453,6 +1457,150 @@ __device__ __forceinline__ float policy_action(const PolicyW& pw, const float (&
     return m != m ? m : fminf(fmaxf(m, -1.0f), 1.0f);
 }
 
+// ---- the same network shared by the G lanes of an env (packed shapes with G > 1, float32: N = 8 .. 64) ----
+// Lane j of the group owns the hidden units [j U, (j + 1) U), U = 64 / G, of both hidden layers.  Its inputs come from
+// LDS -- the env's observation row in the wave's tile, then the hidden vector the group assembles in `hid` (64 floats
+// per env behind the tile and the reset slots, geometry_for()) -- as same-address broadcast reads; its weights are no
+// longer wave-uniform, so they come through vector memory: the lane's U-wide slice of row k as 16-byte loads (G = 2,
+// 4, 8; G = 16 splits the work differently, policy_mlp_wave() below).  Per unit the fma sequence is policy_mlp()'s --
+// h = b; h = fma(w[k][unit], x[k], h), k ascending -- and the head is evaluated by every lane of the group in
+// policy_mlp()'s order (even units into one accumulator, odd units into the other, ascending), so the result is the
+// thread-per-env kernel's bit for bit and uniform over the group.  `hid` is reused for both layers; the tile is
+// private to the wave, so compiler-only fences order its writes and reads (wave_lds_fence()).
+// ZERO_NONFINITE: the collector's "a non-finite observation entry reaches the networks as 0".
+typedef float F4 __attribute__((ext_vector_type(4)));
+constexpr bool group_policy_shape(int C, int G) { return C == 4 && (G == 2 || G == 4 || G == 8 || G == 16); }
+
+template <int U>
+__device__ __forceinline__ void group_layer(const F4 ACAS2D_AS1* __restrict__ w, const float* __restrict__ x, int n_in,
+                                            bool zero_nonfinite, F2 (&h)[U / 2]) {
+    constexpr int V4 = U / 4;
+    constexpr int UNROLL = U >= 32 ? 2 : (U >= 16 ? 4 : 8);       // ~16 weight vectors of a lane in flight
+#pragma unroll UNROLL
+    for (int k = 0; k < n_in; ++k) {
+        float xk = x[k];
+        if (zero_nonfinite) xk = (xk == xk && fabsf(xk) < __builtin_inff()) ? xk : 0.0f;
+        const F2 x2 = F2{xk, xk};
+#pragma unroll
+        for (int q = 0; q < V4; ++q) {
+            const F4 wq = w[k * (kPolicyHidden / 4) + q];
+            h[2 * q] = __builtin_elementwise_fma(F2{wq.x, wq.y}, x2, h[2 * q]);
+            h[2 * q + 1] = __builtin_elementwise_fma(F2{wq.z, wq.w}, x2, h[2 * q + 1]);
+        }
+    }
+}
+
+template <int D, int G, bool ZERO_NONFINITE>
+__device__ __forceinline__ float policy_mlp_group(const float* w1t_, const float* b1_, const float* w2t_, const float* b2_,
+                                                  const float* w3_, const float* b3_, const float* __restrict__ x,
+                                                  float* __restrict__ hid, int j) {
+    constexpr int U = kPolicyHidden / G, V4 = U / 4, H2 = kPolicyHidden / 2;
+    static_assert(G > 1 && U % 4 == 0, "a lane's slice of a weight row is whole 16-byte vectors");
+    const F4 ACAS2D_AS1* w1 = (const F4 ACAS2D_AS1*)w1t_ + j * V4;
+    const F4 ACAS2D_AS1* w2 = (const F4 ACAS2D_AS1*)w2t_ + j * V4;
+    const F4 ACAS2D_AS1* b1 = (const F4 ACAS2D_AS1*)b1_ + j * V4;
+    const F4 ACAS2D_AS1* b2 = (const F4 ACAS2D_AS1*)b2_ + j * V4;
+    const F2 ACAS2D_AS4* w3 = (const F2 ACAS2D_AS4*)w3_;      // the head's weights are wave-uniform: scalar loads
+    const float ACAS2D_AS4* b3 = (const float ACAS2D_AS4*)b3_;
+    F4* mine = reinterpret_cast<F4*>(hid) + j * V4;
+    F2 h[U / 2];
+    const auto bias = [&](const F4 ACAS2D_AS1* b) {
+#pragma unroll
+        for (int q = 0; q < V4; ++q) { const F4 bq = b[q]; h[2 * q] = F2{bq.x, bq.y}; h[2 * q + 1] = F2{bq.z, bq.w}; }
+    };
+    const auto publish = [&] {                                 // tanh of my units into the group's hidden vector
+#pragma unroll
+        for (int q = 0; q < V4; ++q)
+            mine[q] = F4{tanh_hw(h[2 * q].x), tanh_hw(h[2 * q].y), tanh_hw(h[2 * q + 1].x), tanh_hw(h[2 * q + 1].y)};
+    };
+    bias(b1);
+    group_layer<U>(w1, x, D, ZERO_NONFINITE, h);
+    wave_lds_fence();                                         // whoever read `hid` last is done with it
+    publish();
+    wave_lds_fence();                                         // layer 1 of the whole group is in `hid`
+    bias(b2);
+    group_layer<U>(w2, hid, kPolicyHidden, false, h);
+    wave_lds_fence();                                         // every lane has read layer 1
+    publish();
+    wave_lds_fence();                                         // layer 2 of the whole group is in `hid`
+    F2 acc = F2{0.0f, 0.0f};
+#pragma unroll
+    for (int i = 0; i < H2; ++i) acc = __builtin_elementwise_fma(w3[i], reinterpret_cast<const F2*>(hid)[i], acc);
+    return (acc.x + acc.y) + b3[0];
+}
+
+// G = 16 (N = 64): the four envs of a wave read the SAME weights, and with the split above every lane fetches its
+// 16-byte slice of every row again for its own env -- 261 vector loads of 1 KiB per wave and step.  Here the wave's 64
+// lanes take ONE hidden unit each, for all EPW envs of the wave: one 4-byte load per lane and row (256 bytes per wave)
+// feeds EPW fmas, the inputs are same-address LDS reads of the envs' rows.  The fma sequence per (env, unit) and the
+// head are unchanged, hence the same bits.  Measured at 65 536 x 64, T = 200: 15.7 ms per launch
+// against 24.2 ms for the per-group split there.
+template <int D, int EPW, bool ZERO_NONFINITE>
+__device__ __forceinline__ float policy_mlp_wave(const float* w1t, const float* b1, const float* w2t, const float* b2,
+                                                 const float* w3_, const float* b3_, const float* __restrict__ rows,
+                                                 float* __restrict__ hid, int lane, int el) {
+    constexpr int H2 = kPolicyHidden / 2, UN = 8;             // UN rows of weights in flight per lane
+    typedef const float ACAS2D_AS1 GF;
+    const F2 ACAS2D_AS4* w3 = (const F2 ACAS2D_AS4*)w3_;      // the head's weights are wave-uniform: scalar loads
+    const float ACAS2D_AS4* b3 = (const float ACAS2D_AS4*)b3_;
+    float h[EPW];
+    const auto layer = [&](GF* __restrict__ w, GF* __restrict__ b, const float* __restrict__ x, int stride, auto n_in_c,
+                           bool zero_nonfinite) {
+        constexpr int n_in = decltype(n_in_c)::value;
+        const float bias = b[lane];
+#pragma unroll
+        for (int e = 0; e < EPW; ++e) h[e] = bias;
+        const auto rows_of = [&](int k0, auto un_c) {         // rows [k0, k0 + un) of the layer: the loads first
+            constexpr int un = decltype(un_c)::value;
+            float wk[un > 0 ? un : 1];
+#pragma unroll
+            for (int u = 0; u < un; ++u) wk[u] = w[(k0 + u) * kPolicyHidden + lane];
+#pragma unroll
+            for (int u = 0; u < un; ++u) {
+#pragma unroll
+                for (int e = 0; e < EPW; ++e) {
+                    float xe = x[e * stride + k0 + u];
+                    if (zero_nonfinite) xe = (xe == xe && fabsf(xe) < __builtin_inff()) ? xe : 0.0f;
+                    h[e] = fmaf(wk[u], xe, h[e]);
+                }
+            }
+        };
+#pragma unroll 1
+        for (int k0 = 0; k0 + UN <= n_in; k0 += UN) rows_of(k0, std::integral_constant<int, UN>{});
+        rows_of(n_in / UN * UN, std::integral_constant<int, n_in % UN>{});
+    };
+    const auto publish = [&] {                                 // tanh of my unit, for every env of the wave
+#pragma unroll
+        for (int e = 0; e < EPW; ++e) hid[e * kPolicyHidden + lane] = tanh_hw(h[e]);
+    };
+    layer((GF*)w1t, (GF*)b1, rows, D, std::integral_constant<int, D>{}, ZERO_NONFINITE);
+    wave_lds_fence();                                         // whoever read `hid` last is done with it
+    publish();
+    wave_lds_fence();                                         // layer 1 of every env is in `hid`
+    layer((GF*)w2t, (GF*)b2, hid, kPolicyHidden, std::integral_constant<int, kPolicyHidden>{}, false);
+    wave_lds_fence();                                         // every lane has read layer 1
+    publish();
+    wave_lds_fence();                                         // layer 2 of every env is in `hid`
+    F2 acc = F2{0.0f, 0.0f};
+#pragma unroll
+    for (int i = 0; i < H2; ++i)
+        acc = __builtin_elementwise_fma(w3[i], reinterpret_cast<const F2*>(hid + el * kPolicyHidden)[i], acc);
+    return (acc.x + acc.y) + b3[0];
+}
+
+// One head for the env of `lane` at a shape with G > 1: `tile` is the wave's observation tile (rows of D values),
+// `hid` its EPW x 64 hidden values.
+template <int D, int G, bool ZERO_NONFINITE>
+__device__ __forceinline__ float policy_mlp_shared(const float* w1t, const float* b1, const float* w2t, const float* b2,
+                                                   const float* w3, const float* b3, const float* __restrict__ tile,
+                                                   float* __restrict__ hid, int lane) {
+    const int j = lane & (G - 1), el = lane / G;
+    if constexpr (G == 16)
+        return policy_mlp_wave<D, 64 / G, ZERO_NONFINITE>(w1t, b1, w2t, b2, w3, b3, tile, hid, lane, el);
+    else
+        return policy_mlp_group<D, G, ZERO_NONFINITE>(w1t, b1, w2t, b2, w3, b3, tile + el * D, hid + el * kPolicyHidden, j);
+}
+
 // ---- kernels ------------------------------------------------------------------------------------------
 // The launch modes of step_kernel, one per C entry point / launch path (DESIGN.md 4.1 lists them with the
 // flags each one implies).  The values are part of the kernels' names: keep them stable, append new ones.
@@ -1473,8 +1621,9 @@ constexpr bool rollout_mode(Mode m) { return m == Mode::Rollout || policy_mode(m
 // done[t][E], outcome[t][E] (and the optional auto-reset side channels [t][E]...), finished envs
 // are reset on the fly (ROLLOUT implies AUTO_RESET semantics and a packed shape).  The per-step
 // arithmetic is this same code, so rollout(T) == T x step() bit for bit.
-// With POLICY (rollout, one lane per env) the action of every step comes from policy_action() on the
-// previous observation instead of from actions[t][E], which becomes an output.
+// With POLICY (rollout; one lane per env, or at the float32 shapes (4,2) (4,4) (4,8) (4,16) the env's lanes together:
+// policy_mlp_shared()) the action of every step comes from policy_action() on the previous observation instead of from
+// actions[t][E], which becomes an output.
 // With SAMPLE on top (the collector of a PPO iteration, SB3's collect_rollouts) the action is drawn: mean + exp(log_std)
 // eps, eps ~ N(0, 1) from a Philox block per env and step (Box-Muller); the raw action, the critic's value of the
 // observation and the log-probability of the draw are stored per step, the env is stepped with the clipped action, and
@@ -1492,7 +1641,8 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
     constexpr bool POLICY = policy_mode(M), SAMPLE = M == Mode::Collect;
     constexpr bool ARENA = M == Mode::Arena, EVAL = M == Mode::Eval;
     static_assert(!ROLLOUT || PACKED, "rollout modes: packed shapes");
-    static_assert(!POLICY || G == 1, "in-kernel policy: one lane per env");
+    static_assert(!POLICY || G == 1 || (PACKED && sizeof(T) == 4 && group_policy_shape(C, G)),
+                  "in-kernel policy: one lane per env, or the group-cooperative float32 shapes");
     constexpr int NS = PACKED ? C * G : 0;         // packed shapes: n_traffic is a compile-time constant
     const int N = PACKED ? NS : N_arg;
     constexpr int EPW = 64 / G;                    // envs per wavefront
@@ -1653,7 +1803,12 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
     if constexpr (POLICY) {
         // the observation the first action is taken on (reset()'s / the previous step's) into the lane's row
         const T* obs_in = static_cast<const T*>(pw.obs_in) + e_wave * D;
-        if (active) { for (int i = 0; i < D; ++i) row[i] = obs_in[el * D + i]; }
+        if constexpr (G == 1) {
+            if (active) { for (int i = 0; i < D; ++i) row[i] = obs_in[el * D + i]; }
+        } else {                                           // the group shares the row: each lane a G-th of it
+            if (active) { for (int i = j; i < D; i += G) row[i] = obs_in[el * D + i]; }
+            wave_lds_fence();
+        }
     }
     // EVAL: this wave's policy (ep_stride is a multiple of the wave, so one per wave: its weights stay SGPR operands), the
     // lane's episode, and whether it is still playing it (padding lanes past n_episodes never are)
@@ -1682,9 +1837,17 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
         T action = action_next;
         if constexpr (POLICY) {
             constexpr int DP = 5 + 3 * NS;                // compile-time obs width (packed shapes)
-            float x[DP];
+            float x[G == 1 ? DP : 1];
+            (void)x;
+            if constexpr (G == 1) {
 #pragma unroll
-            for (int i = 0; i < DP; ++i) x[i] = (float)row[i];
+                for (int i = 0; i < DP; ++i) x[i] = (float)row[i];
+            }
+            // G > 1: the group evaluates the network together (policy_mlp_group()); its hidden vector lies behind
+            // the wave's tile and reset slots (geometry_for())
+            float* hid = nullptr;
+            if constexpr (G > 1) hid = reinterpret_cast<float*>(tile) + (tile_elems - EPW * kPolicyHidden);
+            (void)hid;
             // The weights must be RE-READ every step (scalar cache hits): they are loop-invariant, and
             // hoisted out of the step loop hipcc tries to keep all 4 700 of them in SGPRs, spills them
             // to VGPR lanes and reads them back one v_readlane at a time (7x slower).  Laundering the
@@ -1692,12 +1855,23 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
             PolicyW pw_t = pw;
             asm volatile("" : "+s"(pw_t.w1t), "+s"(pw_t.b1), "+s"(pw_t.w2t), "+s"(pw_t.b2), "+s"(pw_t.w3), "+s"(pw_t.b3));
             if constexpr (SAMPLE) {
+                float mean, value;
+                if constexpr (G == 1) {
 #pragma unroll
-                for (int i = 0; i < DP; ++i) x[i] = (x[i] == x[i] && fabsf(x[i]) < __builtin_inff()) ? x[i] : 0.0f;
-                const float mean = policy_mlp<DP>(pw_t.w1t, pw_t.b1, pw_t.w2t, pw_t.b2, pw_t.w3, pw_t.b3, x);
-                asm volatile("" : "+s"(pw_t.v1t), "+s"(pw_t.vb1), "+s"(pw_t.v2t), "+s"(pw_t.vb2), "+s"(pw_t.v3), "+s"(pw_t.vb3),
-                                  "+s"(pw_t.log_std));
-                const float value = policy_mlp<DP>(pw_t.v1t, pw_t.vb1, pw_t.v2t, pw_t.vb2, pw_t.v3, pw_t.vb3, x);
+                    for (int i = 0; i < DP; ++i) x[i] = (x[i] == x[i] && fabsf(x[i]) < __builtin_inff()) ? x[i] : 0.0f;
+                    mean = policy_mlp<DP>(pw_t.w1t, pw_t.b1, pw_t.w2t, pw_t.b2, pw_t.w3, pw_t.b3, x);
+                    asm volatile("" : "+s"(pw_t.v1t), "+s"(pw_t.vb1), "+s"(pw_t.v2t), "+s"(pw_t.vb2), "+s"(pw_t.v3), "+s"(pw_t.vb3),
+                                      "+s"(pw_t.log_std));
+                    value = policy_mlp<DP>(pw_t.v1t, pw_t.vb1, pw_t.v2t, pw_t.vb2, pw_t.v3, pw_t.vb3, x);
+                } else {
+                    mean = policy_mlp_shared<DP, G, true>(pw_t.w1t, pw_t.b1, pw_t.w2t, pw_t.b2, pw_t.w3, pw_t.b3,
+                                                          reinterpret_cast<const float*>(tile), hid, lane);
+                    asm volatile("" : "+s"(pw_t.v1t), "+s"(pw_t.vb1), "+s"(pw_t.v2t), "+s"(pw_t.vb2), "+s"(pw_t.v3), "+s"(pw_t.vb3),
+                                      "+s"(pw_t.log_std));
+                    value = policy_mlp_shared<DP, G, true>(pw_t.v1t, pw_t.vb1, pw_t.v2t, pw_t.vb2, pw_t.v3, pw_t.vb3,
+                                                           reinterpret_cast<const float*>(tile), hid, lane);
+                    wave_lds_fence();                     // the row has been read: observe() rewrites it below
+                }
                 const float log_std = ((const float ACAS2D_AS4*)pw_t.log_std)[0];
                 // eps ~ N(0, 1): one Philox block per (global env, noise step + t), Box-Muller on two 24-bit uniforms
                 const uint64_t gid = (uint64_t)(env_offset + e_wave + el);
@@ -1708,15 +1882,22 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
                                   __builtin_amdgcn_cosf(u2);                                                    // cos(2 pi u2)
                 const float raw = fmaf(__builtin_amdgcn_exp2f(log_std * 1.4426950408889634f), eps, mean);
                 const float logp = fmaf(-0.5f * eps, eps, -log_std) - 0.9189385332046727f;                      // - log sqrt(2 pi)
-                if (active) {
+                if (active && j == 0) {                   // (group-uniform values: the group's first lane stores them)
                     (static_cast<T*>(pw.actions_out) + e_wave + te)[el] = (T)raw;      // the buffer keeps the RAW action,
                     (static_cast<T*>(pw.values_out) + e_wave + te)[el] = (T)value;     // the env sees the clipped one
                     (static_cast<T*>(pw.logp_out) + e_wave + te)[el] = (T)logp;
                 }
                 action = (T)fminf(fmaxf(raw, -1.0f), 1.0f);
             } else {
-                action = (T)policy_action<DP>(pw_t, x);
-                if constexpr (!EVAL) { if (active) (static_cast<T*>(pw.actions_out) + e_wave + te)[el] = action; }
+                if constexpr (G == 1) {
+                    action = (T)policy_action<DP>(pw_t, x);
+                } else {                                  // policy_action() with the group's network
+                    const float m = policy_mlp_shared<DP, G, false>(pw_t.w1t, pw_t.b1, pw_t.w2t, pw_t.b2, pw_t.w3, pw_t.b3,
+                                                                    reinterpret_cast<const float*>(tile), hid, lane);
+                    wave_lds_fence();                     // the row has been read: observe() rewrites it below
+                    action = (T)(m != m ? m : fminf(fmaxf(m, -1.0f), 1.0f));
+                }
+                if constexpr (!EVAL) { if (active && j == 0) (static_cast<T*>(pw.actions_out) + e_wave + te)[el] = action; }
             }
         } else {
             if (ROLLOUT && active && t + 1 < T_steps) action_next = io.actions[n_envs + el];
@@ -1770,9 +1951,11 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
             if (!active) oc = 0;                          // a padding lane never finishes anything
             if constexpr (EVAL) {
                 if (running && oc != 0) {                 // the first episode's result, then the lane stops for good
-                    pw.res_outcome[res_i] = oc;
-                    pw.res_steps[res_i] = steps;
-                    static_cast<T*>(pw.res_return)[res_i] = total;
+                    if (j == 0) {                         // (a group latches together: its first lane writes)
+                        pw.res_outcome[res_i] = oc;
+                        pw.res_steps[res_i] = steps;
+                        static_cast<T*>(pw.res_return)[res_i] = total;
+                    }
                     running = false;
                 }
             } else if (j == 0 && active) {
@@ -1940,7 +2123,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
         if constexpr (EVAL) { if (__ballot(running) == 0ull) break; }
     }
     if constexpr (EVAL) {
-        if (running) {                                    // no done within n_steps
+        if (running && j == 0) {                          // no done within n_steps
             pw.res_outcome[res_i] = 0;
             pw.res_steps[res_i] = 0;
             static_cast<T*>(pw.res_return)[res_i] = T(0);
@@ -2030,7 +2213,16 @@ template <typename T>
 int launch_evaluate_policies(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
                              int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
                              int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
-                             hipStream_t stream);
+                             hipStream_t stream, bool group = false);
+// the *_group entry points (float32: the double instantiations reject every traffic count)
+template <typename T>
+int launch_rollout_policy_group(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io,
+                                const Acas2dPolicy* pol, const void* obs_in, int32_t n_steps, uint64_t seed,
+                                int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream);
+template <typename T>
+int launch_collect_group(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
+                         const void* obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset, int64_t n_envs,
+                         int32_t n_traffic, hipStream_t stream);
 template <typename T>
 int launch_reset(const Acas2dConfig* cfg, const Acas2dState* st, const uint8_t* mask, void* obs,
                  int32_t do_init, uint64_t seed, int64_t env_offset, int64_t n_envs, int32_t n_traffic,

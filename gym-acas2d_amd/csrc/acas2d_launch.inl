@@ -5,6 +5,7 @@
 // today, so only the fma()s written in the source fuse.)
 #include <stdlib.h>
 #include <cmath>
+#include <initializer_list>
 #include <type_traits>
 
 #include "acas2d_kernels.hpp"
@@ -131,11 +132,13 @@ static int check_launch(const char* name) {
 }
 
 // Launch geometry for a shape: one env per G lanes, 64 / G envs per wavefront, 4 wavefronts per
-// workgroup, one LDS observation tile per wavefront.
+// workgroup, one LDS observation tile per wavefront.  `group_policy`: the launch evaluates the in-kernel policy
+// with the G lanes of an env together and keeps each env's 64 hidden activations behind the wave's tile and reset
+// slots (policy_mlp_group(); the kernel finds them at the END of the wave's tile_elems).
 struct Geometry { unsigned grid, block; int tile_elems; size_t lds_bytes; };
 
 template <typename T>
-static int geometry_for(const Shape& sh, int64_t n_envs, int n_traffic, Geometry* g) {
+static int geometry_for(const Shape& sh, int64_t n_envs, int n_traffic, Geometry* g, bool group_policy = false) {
     const int64_t epw = 64 / sh.G, envs_per_block = epw * kWavesPerBlock;
     const int64_t blocks = (n_envs + envs_per_block - 1) / envs_per_block;
     if (blocks > 0x7fffffffLL || n_envs > 0x7fffffffLL) { set_error("n_envs = %lld exceeds the launch limit", (long long)n_envs); return ACAS2D_EINVAL; }
@@ -150,10 +153,12 @@ static int geometry_for(const Shape& sh, int64_t n_envs, int n_traffic, Geometry
     } else if (sh.packed) {
         scratch = 4 * (int64_t)n_traffic + 1;
     }
-    const int64_t elems = ((tile + scratch + 3) / 4) * 4;
+    const int64_t hidden = group_policy ? epw * kPolicyHidden : 0;
+    const int64_t elems = ((tile + scratch + 3) / 4) * 4 + hidden;
     const int64_t bytes = elems * kWavesPerBlock * (int64_t)sizeof(T);
     if (bytes > 64 * 1024) {
-        set_error("n_traffic = %d needs a %lld-byte LDS observation tile per workgroup (limit 65536)", n_traffic, (long long)bytes);
+        set_error("n_traffic = %d needs a %lld-byte LDS observation tile%s per workgroup (limit 65536)", n_traffic, (long long)bytes,
+                  group_policy ? " and hidden vectors" : "");
         return ACAS2D_EINVAL;
     }
     g->grid = (unsigned)blocks; g->block = (unsigned)kBlock; g->tile_elems = (int)elems; g->lds_bytes = (size_t)bytes;
@@ -250,6 +255,7 @@ struct Launch {
     State<T> s;
     StepIO<T> io;
     uint32_t k0, k1;
+    bool group_policy;                        // the *_group entry points: geometry_for()'s hidden vectors
 };
 
 // The entry points' words for the rejections they share (each has always said them its own way)
@@ -272,7 +278,7 @@ static int prepare(Launch<T>& L, const Words& words, bool given, Inputs inputs, 
     if (L.n_envs < 0 || L.env_offset < 0) return fail(words.negative, L.name);
     if (L.n_envs == 0) return ACAS2D_OK;
     if (int rc = shape(&L.sh)) return rc;
-    if (int rc = geometry_for<T>(L.sh, L.n_envs, L.N, &L.g)) return rc;
+    if (int rc = geometry_for<T>(L.sh, L.n_envs, L.N, &L.g, L.group_policy)) return rc;
     L.p = make_params<T>(*L.cfg);
     L.s = make_state<T>(*L.st);
     if (const Acas2dStepIO* io = L.step_io)
@@ -297,6 +303,26 @@ static int thread_per_env(const char* name, int n_traffic, Shape* sh) {
     if (shape_instantiated(*sh)) return ACAS2D_OK;
     return fail("%s: n_traffic = %d has no thread-per-env shape for this element type", name, n_traffic);
 }
+// the *_group entry points' work shape: the default of resolve_shape(), which must be one of the four shapes the
+// group-cooperative policy is built for.  `sibling`: the entry point that serves the thread-per-env counts.
+template <typename T>
+static int group_shape(const char* name, const char* sibling, int n_traffic, Shape* sh) {
+    static const char kBuilt[] = "the group-cooperative policy is built for n_traffic in {8, 16, 32, 64}, float32 "
+                                 "(work shapes (4,2) (4,4) (4,8) (4,16))";
+    if (int rc = resolve_shape<T>(n_traffic, sh)) return rc;
+    if (sizeof(T) == 4 && sh->packed && group_policy_shape(sh->C, sh->G)) return ACAS2D_OK;
+    if (sizeof(T) == 4 && sh->packed && sh->G == 1)
+        return fail("%s: n_traffic = %d takes the thread-per-env shape C=%d G=1: use %s; %s", name, n_traffic, sh->C, sibling, kBuilt);
+    if (!sh->packed) return fail("%s: n_traffic = %d has no packed work shape; %s", name, n_traffic, kBuilt);
+    return fail("%s: n_traffic = %d takes the work shape C=%d G=%d; %s", name, n_traffic, sh->C, sh->G, kBuilt);
+}
+// ... and its weights: a lane reads its slice of a weight row as 16-byte vectors
+static int require_aligned(const char* name, std::initializer_list<const void*> ptrs) {
+    for (const void* q : ptrs)
+        if (reinterpret_cast<uintptr_t>(q) & 15u)
+            return fail("%s: the first two layers' weights and biases must be 16-byte aligned", name);
+    return ACAS2D_OK;
+}
 
 // One step_kernel launch in mode M for L's shape and formulation.  The six preloaded pointers (see step_kernel): the
 // arena mode's four state blocks and the actions, else the traffic arrays, own_x and own_y.
@@ -309,7 +335,7 @@ static int launch_mode(const Launch<T>& L, const PW& pw) {
     const T* const* a = M == Mode::Arena ? arena : general;
     dispatch(*L.cfg, L.sh, [&](auto fast, auto C, auto G, auto packed) {
         if constexpr ((M != Mode::Arena || (packed && sizeof(T) == 4)) && (!rollout_mode(M) || packed) &&
-                      (!policy_mode(M) || G == 1))
+                      (!policy_mode(M) || G == 1 || (sizeof(T) == 4 && packed && group_policy_shape(C, G))))
             hipLaunchKernelGGL((step_kernel<T, C, G, packed, fast, M>), dim3(L.g.grid), dim3(L.g.block), L.g.lds_bytes,
                                L.stream, a[0], a[1], a[2], a[3], a[4], a[5], (int32_t)L.n_envs, (int32_t)L.g.tile_elems,
                                L.p, rp, s, L.io, L.k0, L.k1, L.env_offset, L.N, L.n_steps, pw);
@@ -362,8 +388,10 @@ static PW actor(const Acas2dPolicy* pol, const void* obs_in) {
 template <typename T>
 static int launch_policy(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dPolicy* pol,
                          const void* obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset, int64_t n_envs,
-                         int32_t n_traffic, hipStream_t stream, const Acas2dActorCritic* ac) {
-    Launch<T> L{"acas2d_rollout_policy", cfg, st, io, seed, env_offset, n_envs, n_traffic, n_steps, stream};
+                         int32_t n_traffic, hipStream_t stream, const Acas2dActorCritic* ac, bool group = false) {
+    Launch<T> L{group ? "acas2d_rollout_policy_group" : "acas2d_rollout_policy", cfg, st, io, seed, env_offset, n_envs, n_traffic,
+                n_steps, stream};
+    L.group_policy = group;
     const auto inputs = [&] {
         if (!io->actions || !io->obs || !io->reward || !io->done || !io->outcome || !obs_in)
             return fail("%s: obs_in, actions (output), obs, reward, done and outcome are required", L.name);
@@ -372,17 +400,24 @@ static int launch_policy(const Acas2dConfig* cfg, const Acas2dState* st, const A
     const auto go = [&] {
         PolicyW pw = actor<PolicyW>(pol, obs_in);
         pw.actions_out = const_cast<void*>(io->actions);
+        if (group)
+            if (int rc = require_aligned(L.name, {pol->w1t, pol->b1, pol->w2t, pol->b2})) return rc;
         if (!ac) return launch_mode<Mode::Policy>(L, pw);
         if (!ac->v1t || !ac->vb1 || !ac->v2t || !ac->vb2 || !ac->v3 || !ac->vb3 || !ac->log_std || !ac->values || !ac->logp)
             return fail("acas2d_collect: the value net, log_std, values and logp are required");
+        if (group)
+            if (int rc = require_aligned(L.name, {ac->v1t, ac->vb1, ac->v2t, ac->vb2})) return rc;
         pw.v1t = (const float*)ac->v1t; pw.vb1 = (const float*)ac->vb1; pw.v2t = (const float*)ac->v2t;
         pw.vb2 = (const float*)ac->vb2; pw.v3 = (const float*)ac->v3; pw.vb3 = (const float*)ac->vb3;
         pw.log_std = (const float*)ac->log_std; pw.values_out = ac->values; pw.logp_out = ac->logp;
         pw.nk0 = (uint32_t)ac->noise_seed; pw.nk1 = (uint32_t)(ac->noise_seed >> 32); pw.noise_step = ac->noise_step;
         return launch_mode<Mode::Collect>(L, pw);
     };
-    return prepare(L, Words{"cfg / io / policy", kSizes, kNegative}, io && pol, inputs,
-                   [&](Shape* sh) { return thread_per_env(L.name, n_traffic, sh); }, go);
+    const auto shape = [&](Shape* sh) {
+        if (group) return group_shape<T>(L.name, ac ? "acas2d_collect_f32" : "acas2d_rollout_policy_f32", n_traffic, sh);
+        return thread_per_env(L.name, n_traffic, sh);
+    };
+    return prepare(L, Words{"cfg / io / policy", kSizes, kNegative}, io && pol, inputs, shape, go);
 }
 template <typename T>
 int launch_rollout_policy(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io,
@@ -397,6 +432,20 @@ int launch_collect(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dS
     if (!ac) return fail("acas2d_collect: NULL actor-critic");
     return launch_policy<T>(cfg, st, io, &ac->actor, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream, ac);
 }
+// the *_group entry points: the same launches at the shapes whose G lanes evaluate an env's policy together
+template <typename T>
+int launch_rollout_policy_group(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io,
+                                const Acas2dPolicy* pol, const void* obs_in, int32_t n_steps, uint64_t seed,
+                                int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream) {
+    return launch_policy<T>(cfg, st, io, pol, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream, nullptr, true);
+}
+template <typename T>
+int launch_collect_group(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
+                         const void* obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset, int64_t n_envs,
+                         int32_t n_traffic, hipStream_t stream) {
+    if (!ac) return fail("acas2d_collect: NULL actor-critic");
+    return launch_policy<T>(cfg, st, io, &ac->actor, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream, ac, true);
+}
 
 // K stacked policies scored on shared episodes: policy k plays envs [k EP, (k + 1) EP) of the state, EP = n_episodes
 // rounded up to a whole wave; the launch covers those n_policies x EP envs
@@ -404,9 +453,11 @@ template <typename T>
 int launch_evaluate_policies(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
                              int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
                              int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
-                             hipStream_t stream) {
+                             hipStream_t stream, bool group) {
     const int64_t ep = ((int64_t)n_episodes + 63) / 64 * 64, total = (int64_t)n_policies * ep;
-    Launch<T> L{"acas2d_evaluate_policies", cfg, st, nullptr, seed, env_offset, total, n_traffic, n_steps, stream};
+    Launch<T> L{group ? "acas2d_evaluate_policies_group" : "acas2d_evaluate_policies", cfg, st, nullptr, seed, env_offset, total,
+                n_traffic, n_steps, stream};
+    L.group_policy = group;
     const auto inputs = [&] {
         if (!obs_in || !outcome || !steps || !total_reward)
             return fail("%s: obs_in and the outcome, steps and total_reward outputs are required", L.name);
@@ -416,12 +467,15 @@ int launch_evaluate_policies(const Acas2dConfig* cfg, const Acas2dState* st, int
         return ACAS2D_OK;
     };
     const auto shape = [&](Shape* sh) {
-        if (int rc = thread_per_env(L.name, n_traffic, sh)) return rc;
+        if (int rc = group ? group_shape<T>(L.name, "acas2d_evaluate_policies_f32", n_traffic, sh)
+                           : thread_per_env(L.name, n_traffic, sh)) return rc;
         if (n_envs >= total) return ACAS2D_OK;
         return fail("acas2d_evaluate_policies: the state holds n_envs = %lld envs, %d policies x %lld (n_episodes = %d rounded up "
                     "to 64) need %lld", (long long)n_envs, n_policies, (long long)ep, n_episodes, (long long)total);
     };
     const auto go = [&] {
+        if (group)
+            if (int rc = require_aligned(L.name, {pol->w1t, pol->b1, pol->w2t, pol->b2})) return rc;
         PolicyEvalW pw = actor<PolicyEvalW>(pol, obs_in);
         pw.res_outcome = outcome; pw.res_steps = steps; pw.res_return = total_reward;
         pw.n_episodes = n_episodes; pw.ep_stride = (int32_t)ep;
@@ -473,6 +527,8 @@ template decltype(launch_step<Elem>) launch_step<Elem>;
 template decltype(launch_rollout<Elem>) launch_rollout<Elem>;
 template decltype(launch_rollout_policy<Elem>) launch_rollout_policy<Elem>;
 template decltype(launch_collect<Elem>) launch_collect<Elem>;
+template decltype(launch_rollout_policy_group<Elem>) launch_rollout_policy_group<Elem>;
+template decltype(launch_collect_group<Elem>) launch_collect_group<Elem>;
 template decltype(launch_evaluate_policies<Elem>) launch_evaluate_policies<Elem>;
 template decltype(launch_reset<Elem>) launch_reset<Elem>;
 template decltype(shape_geometry<Elem>) shape_geometry<Elem>;

@@ -52,7 +52,8 @@ EXPORTS = ("acas2d_abi_version", "acas2d_config_size", "acas2d_state_size", "aca
            "acas2d_step_f64", "acas2d_rollout_f32", "acas2d_rollout_f64", "acas2d_rollout_policy_f32",
            "acas2d_rollout_policy_f64", "acas2d_collect_f32", "acas2d_collect_f64", "acas2d_ppo_workspace_floats",
            "acas2d_ppo_update_f32", "acas2d_reset_f32", "acas2d_reset_f64", "acas2d_launch_geometry",
-           "acas2d_state_is_consecutive", "acas2d_evaluate_policies_f32", "acas2d_evaluate_policies_f64")
+           "acas2d_state_is_consecutive", "acas2d_evaluate_policies_f32", "acas2d_evaluate_policies_f64",
+           "acas2d_rollout_policy_group_f32", "acas2d_collect_group_f32", "acas2d_evaluate_policies_group_f32")
 
 
 class NativeLibraryError(RuntimeError):
@@ -104,17 +105,17 @@ def lib():
         f.restype = C.c_int
         f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.POINTER(CStepIO), C.c_int32,
                       C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
-    for name in ("acas2d_rollout_policy_f32", "acas2d_rollout_policy_f64"):
+    for name in ("acas2d_rollout_policy_f32", "acas2d_rollout_policy_f64", "acas2d_rollout_policy_group_f32"):
         f = getattr(L, name)
         f.restype = C.c_int
         f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.POINTER(CStepIO), C.POINTER(CPolicy), C.c_void_p,
                       C.c_int32, C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
-    for name in ("acas2d_collect_f32", "acas2d_collect_f64"):
+    for name in ("acas2d_collect_f32", "acas2d_collect_f64", "acas2d_collect_group_f32"):
         f = getattr(L, name)
         f.restype = C.c_int
         f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.POINTER(CStepIO), C.POINTER(CActorCritic), C.c_void_p,
                       C.c_int32, C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
-    for name in ("acas2d_evaluate_policies_f32", "acas2d_evaluate_policies_f64"):
+    for name in ("acas2d_evaluate_policies_f32", "acas2d_evaluate_policies_f64", "acas2d_evaluate_policies_group_f32"):
         f = getattr(L, name)
         f.restype = C.c_int
         f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.c_int64, C.POINTER(CPolicy), C.c_int32, C.c_int32,

@@ -121,20 +121,23 @@ def evaluate_policy(venv, policy, max_steps=None):
 
 
 def evaluate_policy_fused(policy, own, traffic, goal=None, dtype=torch.float64, device="cuda:0", config=None,
-                          max_steps=None):
+                          max_steps=None, group=False):
     """evaluate_policy() as ONE kernel launch (ACAS2DVecEnv.rollout_policy): the episodes given by
     `own` [E,4] / `traffic` [E,N,4] / `goal` are run with the deterministic SB3 actor evaluated inside
     the rollout kernel; results are those of each env's FIRST episode (the launch has VecEnv
     auto-reset semantics and keeps stepping the envs that finish early).  Thread-per-env shapes only
-    (N in {1,2,3,4,8} float32, {1,2,3,4} float64).  A NaN observation (the reference's d_cpa in exact parallel
-    flight) gives a NaN action, as policy.predict() does in evaluate_policy()."""
+    (N in {1,2,3,4,8} float32, {1,2,3,4} float64), or with group=True the group-cooperative float32 launch
+    (N in {8,16,32,64}, ACAS2DVecEnv.rollout_policy(group=True)).  A NaN observation (the reference's d_cpa in
+    exact parallel flight) gives a NaN action, as policy.predict() does in evaluate_policy()."""
     from .vec_env import ACAS2DVecEnv
+    if group and dtype != torch.float32:
+        raise ValueError("evaluate_policy_fused(group=True) is float32 only, got %s" % (dtype,))
     own, traffic = np.asarray(own), np.asarray(traffic)
     E, N = own.shape[0], traffic.shape[1]
     v = ACAS2DVecEnv(E, N, device=device, dtype=dtype, auto_reset=True, config=config)
     v.set_state(own, traffic, goal, np.zeros(E, np.int32), observe=True)
     T = (max_steps or v.config.max_steps) + 1
-    out = v.rollout_policy(policy, T)
+    out = v.rollout_policy(policy, T, group=group)
     done = out["done"].cpu().numpy()
     fin = done.any(0)
     t0, e = done.argmax(0), np.arange(E)
@@ -146,18 +149,21 @@ def evaluate_policy_fused(policy, own, traffic, goal=None, dtype=torch.float64, 
 
 
 def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float64, device="cuda:0", config=None,
-                            max_steps=None):
+                            max_steps=None, group=False):
     """evaluate_policy_fused() for K policies on the SAME E episodes in ONE launch (acas2d_evaluate_policies_*):
     scoring the checkpoints of a run, or the policies of a seed sweep, together.  `policies`: `SB3ActorPolicy` /
     `ppo.ActorCritic` objects or paths of SB3 zips / .npz exports.  The episodes `own` [E,4] / `traffic` [E,N,4] /
     `goal` are replicated into K blocks of EP = round_up(E, 64) envs (block k: policy k; the padding repeats episode 0
     and is not scored).  Each env stops at the end of its first episode, and nothing per step is stored.
     Returns evaluate_policy_fused()'s keys as [K, E] numpy arrays (outcome, steps, total_reward, path_length) and
-    `unfinished` [K]; row k equals evaluate_policy_fused(policies[k], ...) bit for bit."""
+    `unfinished` [K]; row k equals evaluate_policy_fused(policies[k], ...) bit for bit.  group=True: the
+    group-cooperative float32 launch (acas2d_evaluate_policies_group_f32, N in {8, 16, 32, 64})."""
     from . import native
     from .vec_env import ACAS2DVecEnv
     if not policies:
         raise ValueError("evaluate_policies_fused needs at least one policy")
+    if group and dtype != torch.float32:
+        raise ValueError("evaluate_policies_fused(group=True) is float32 only, got %s" % (dtype,))
     own, traffic = np.asarray(own), np.asarray(traffic)
     E, N = own.shape[0], traffic.shape[1]
     K, EP = len(policies), (own.shape[0] + 63) // 64 * 64
@@ -185,7 +191,10 @@ def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float
     ret = torch.empty(K, E, dtype=dtype, device=dev)
     pw = native.CPolicy(*[t.data_ptr() for t in keep], 64, 0)
     L = native.lib()
-    fn = L.acas2d_evaluate_policies_f32 if dtype == torch.float32 else L.acas2d_evaluate_policies_f64
+    if group:
+        fn = L.acas2d_evaluate_policies_group_f32
+    else:
+        fn = L.acas2d_evaluate_policies_f32 if dtype == torch.float32 else L.acas2d_evaluate_policies_f64
     with torch.cuda.device(dev):
         native.check(fn(C.byref(v._ccfg), C.byref(v._cstate), K * EP, C.byref(pw), K, E, v.outputs["obs"].data_ptr(), T,
                         v.seed_value, v.env_offset, N, outcome.data_ptr(), steps.data_ptr(), ret.data_ptr(),

@@ -199,12 +199,19 @@ class FusedUpdate:
         return {"pg_loss": s[4], "value_loss": s[5], "grad_norm": s[2]}
 
 
+# traffic counts at which PPOTrainer takes the group-cooperative launches by itself (float32; at 8 the thread-per-env
+# kernel exists and is the better design: its weights are scalar operands)
+GROUP_TRAFFIC = (16, 32, 64)
+
+
 class PPOTrainer:
     """collector: "graphs" (default on a GPU: one captured env step replayed n_steps times), "fused" (the whole
     collection of an iteration in ONE hand-written launch, ACAS2DVecEnv.collect(): actor, critic, Gaussian sampling
     and the env step inside the kernel; its noise comes from the kernel's own Philox stream instead of torch's
-    generator) or "eager" (op by op).  updater: "graphs" (default with `use_graphs`: one captured minibatch update of
-    torch ops) or "fused" (FusedUpdate: the minibatch update as two hand-written launches, its own Adam state)."""
+    generator; float32 envs with 16, 32 or 64 traffic aircraft take the launch whose lanes share an env's network,
+    ACAS2DVecEnv.collect(group=True), and so does evaluate()) or "eager" (op by op).  updater: "graphs" (default with
+    `use_graphs`: one captured minibatch update of torch ops) or "fused" (FusedUpdate: the minibatch update as two
+    hand-written launches, its own Adam state; obs_dim <= 29)."""
 
     def __init__(self, venv, config=None, policy=None, use_graphs=None, collector=None, updater=None):
         self.venv = venv
@@ -228,9 +235,12 @@ class PPOTrainer:
         # the hand-written launches exist for the observation widths / traffic counts below: say so HERE, not at the
         # first collect() / update() of a run
         f32 = getattr(venv, "dtype", torch.float32) == torch.float32
-        if self.collector == "fused" and venv.n_traffic not in ((1, 2, 3, 4, 8) if f32 else (1, 2, 3)):
+        # float32 at 16, 32 or 64 traffic aircraft: the launches whose lanes share an env's network (group=True)
+        self._group = f32 and venv.n_traffic in GROUP_TRAFFIC
+        if self.collector == "fused" and not self._group and venv.n_traffic not in ((1, 2, 3, 4, 8) if f32 else (1, 2, 3)):
             raise ValueError("collector='fused' needs a thread-per-env work shape: n_traffic in {1, 2, 3, 4, 8} (float32) / "
-                             "{1, 2, 3} (float64), got %d -- use collector='graphs'" % venv.n_traffic)
+                             "{1, 2, 3} (float64), or the group-cooperative float32 launch: n_traffic in {16, 32, 64}; "
+                             "got %d -- use collector='graphs'" % venv.n_traffic)
         if self.updater == "fused" and venv.obs_dim not in (8, 11, 14, 17, 29):
             raise ValueError("updater='fused' is built for obs_dim in {8, 11, 14, 17, 29} (n_traffic 1, 2, 3, 4, 8), got %d "
                              "-- use updater='graphs'" % venv.obs_dim)
@@ -372,7 +382,7 @@ class PPOTrainer:
             if self.collector == "fused":
                 # one launch: rows t = 0 .. T-1 of the static buffers, then the captured GAE as usual
                 out = self.venv.collect(self.policy, T, noise_seed=cfg.seed, noise_step=self.num_timesteps // E,
-                                        out=self._fused_out)
+                                        out=self._fused_out, group=self._group)
                 self._fused_out = out
                 obs_all, rew = out["obs"].to(torch.float32), out["reward"].to(torch.float32)
                 self.nan_events.add_(torch.isnan(rew).sum() + torch.isnan(obs_all[1:]).any(-1).sum())
@@ -501,7 +511,7 @@ class PPOTrainer:
         from .policy import evaluate_policies_fused
         own, trf, goal = reset_parity.draw_episodes(self.venv.config, n_episodes, rng)
         out = evaluate_policies_fused([self.policy], own, trf, goal, dtype=self.venv.dtype, device=self.device,
-                                      config=self.venv.config)
+                                      config=self.venv.config, group=self._group)
         return {k: (v[0] if k != "unfinished" else int(v[0])) for k, v in out.items()}
 
     def learn(self, total_timesteps, log=print, eval_every=None, eval_episodes=10, eval_seed=None, save_dir=None,
@@ -522,9 +532,10 @@ class PPOTrainer:
             raise ValueError("checkpoint_every needs save_dir")
         if eval_every:
             f32 = self.venv.dtype == torch.float32
-            if self.venv.n_traffic not in ((1, 2, 3, 4, 8) if f32 else (1, 2, 3, 4)):
+            if not self._group and self.venv.n_traffic not in ((1, 2, 3, 4, 8) if f32 else (1, 2, 3, 4)):
                 raise ValueError("eval_every needs a thread-per-env work shape: n_traffic in {1, 2, 3, 4, 8} (float32) / "
-                                 "{1, 2, 3, 4} (float64), got %d" % self.venv.n_traffic)
+                                 "{1, 2, 3, 4} (float64), or the group-cooperative float32 launch: n_traffic in "
+                                 "{16, 32, 64}; got %d" % self.venv.n_traffic)
             eval_rng = random.Random(self.cfg.seed if eval_seed is None else eval_seed)
         from .policy import save_sb3_policy
         evals = {"timesteps": [], "results": [], "ep_lengths": []}

@@ -383,16 +383,29 @@ class ACAS2DVecEnv:
         out["_actions"] = a          # keep the (possibly re-laid-out) input alive until the launch ran
         return out
 
-    def rollout_policy(self, policy, n_steps, out=None, keep_terminal_obs=False):
+    def _group_entry(self, what, name):
+        """The *_group entry point `name` (float32 only: the group-cooperative policy has no float64 kernels)."""
+        if self.dtype != torch.float32:
+            raise ValueError("%s(group=True) is float32 only (n_traffic in {8, 16, 32, 64}), this env is %s"
+                             % (what, self.dtype))
+        return getattr(self._lib, name)
+
+    def rollout_policy(self, policy, n_steps, out=None, keep_terminal_obs=False, group=False):
         """testing_main.py:69-105 in ONE kernel launch (acas2d_rollout_policy_*): for n_steps steps,
         `action = policy.predict(obs, deterministic=True)` then `env.step(action)`, with the SB3
         MlpPolicy actor (`policy.SB3ActorPolicy` / `ppo.ActorCritic`) evaluated inside the kernel on
         the observation the previous step left -- `self.outputs["obs"]` at the start, so call
         reset() / step() / set_state(observe=True) first.  One lane per env: n_traffic in
-        {1, 2, 3, 4, 8} for float32, {1, 2, 3, 4} for float64.  Returns rollout()'s dict plus
-        "actions" [T, E] (the actions taken); VecEnv auto-reset semantics."""
+        {1, 2, 3, 4, 8} for float32, {1, 2, 3, 4} for float64.  group=True (float32, n_traffic in {8, 16, 32, 64}:
+        acas2d_rollout_policy_group_f32): the lanes that share an env evaluate the network together, same results.
+        Returns rollout()'s dict plus "actions" [T, E] (the actions taken); VecEnv auto-reset semantics."""
         if not self.auto_reset:
             raise RuntimeError("rollout_policy() has VecEnv auto-reset semantics; construct with auto_reset=True")
+        if group:
+            fn = self._group_entry("rollout_policy", "acas2d_rollout_policy_group_f32")
+        else:
+            fn = (self._lib.acas2d_rollout_policy_f32 if self.dtype == torch.float32
+                  else self._lib.acas2d_rollout_policy_f64)
         T, E, D, dev = int(n_steps), self.num_envs, self.obs_dim, self.device
         w = policy.actor_weights() if hasattr(policy, "actor_weights") else policy
         w1, b1, w2, b2, w3, b3 = (torch.as_tensor(t, dtype=torch.float32).to(dev) for t in w)
@@ -418,8 +431,6 @@ class ACAS2DVecEnv:
                             ptr(out["outcome"]), ptr(out.get("terminal_observation")), ptr(out["episode_return"]),
                             ptr(out["episode_steps"]))
         pol = native.CPolicy(*[ptr(t) for t in keep], 64, 0)
-        fn = (self._lib.acas2d_rollout_policy_f32 if self.dtype == torch.float32
-              else self._lib.acas2d_rollout_policy_f64)
         with torch.cuda.device(dev):
             native.check(fn(C.byref(self._ccfg), C.byref(self._cstate), C.byref(io), C.byref(pol), ptr(self._obs),
                             T, self.seed_value, self.env_offset, E, self.n_traffic, self._stream()))
@@ -427,7 +438,7 @@ class ACAS2DVecEnv:
         out["_weights"] = keep       # keep the transposed copies alive until the launch ran
         return out
 
-    def collect(self, policy, n_steps, noise_seed=0, noise_step=0, out=None):
+    def collect(self, policy, n_steps, noise_seed=0, noise_step=0, out=None, group=False):
         """The collector of one PPO iteration in ONE kernel launch (acas2d_collect_*; SB3 `collect_rollouts` as
         training_main.py:44-52 runs it): for n_steps steps draw `a ~ N(actor(obs), exp(log_std))`, record the raw
         action, `critic(obs)` and the draw's log-probability, step the env with `clip(a, -1, 1)`.  `policy` is a
@@ -435,9 +446,14 @@ class ACAS2DVecEnv:
         Returns a dict of device tensors: obs [T + 1, E, D] (obs[t] is what action t was drawn on, obs[T] the
         observation the next iteration starts from), actions / values / logp / reward [T, E], done [T, E] bool,
         outcome, episode_return, episode_steps [T, E].  The noise stream depends on (noise_seed, global env index,
-        noise_step + t) only.  One lane per env: n_traffic in {1, 2, 3, 4, 8} (float32), {1, 2, 3, 4} (float64)."""
+        noise_step + t) only.  One lane per env: n_traffic in {1, 2, 3, 4, 8} (float32), {1, 2, 3, 4} (float64);
+        group=True (float32, n_traffic in {8, 16, 32, 64}: acas2d_collect_group_f32) as in rollout_policy()."""
         if not self.auto_reset:
             raise RuntimeError("collect() has VecEnv auto-reset semantics; construct with auto_reset=True")
+        if group:
+            fn = self._group_entry("collect", "acas2d_collect_group_f32")
+        else:
+            fn = self._lib.acas2d_collect_f32 if self.dtype == torch.float32 else self._lib.acas2d_collect_f64
         T, E, D, dev = int(n_steps), self.num_envs, self.obs_dim, self.device
         f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32)  # noqa: E731
         pn, vn = policy.mlp_extractor.policy_net, policy.mlp_extractor.value_net
@@ -464,7 +480,6 @@ class ACAS2DVecEnv:
             ac = native.CActorCritic(native.CPolicy(*[ptr(t) for t in keep[:6]], 64, 0), *[ptr(t) for t in keep[6:]],
                                      ptr(out["values"]), ptr(out["logp"]), int(noise_seed) & (2 ** 64 - 1),
                                      int(noise_step) & 0xFFFFFFFF, 0)
-            fn = self._lib.acas2d_collect_f32 if self.dtype == torch.float32 else self._lib.acas2d_collect_f64
             native.check(fn(C.byref(self._ccfg), C.byref(self._cstate), C.byref(io), C.byref(ac), ptr(out["obs"][0]), T,
                             self.seed_value, self.env_offset, E, self.n_traffic, self._stream()))
             self._obs.copy_(out["obs"][T])            # the observation the NEXT action would be drawn on

@@ -215,7 +215,9 @@ int acas2d_rollout_f64(const Acas2dConfig *cfg, const Acas2dState *state, const 
  *   obs_in          T[E][D]  the observation the first action is taken on (reset()'s / the last step's)
  *   io->actions     T[n_steps][E]  OUTPUT here: the action each step took
  *   everything else as acas2d_rollout_*.
- * Needs a thread-per-env work shape: n_traffic in {1, 2, 3, 4, 8} (f32) / {1, 2, 3} (f64).
+ * Needs a thread-per-env work shape: n_traffic in {1, 2, 3, 4, 8} (f32) / {1, 2, 3} (f64); float32 with 8, 16, 32
+ * or 64 traffic aircraft: acas2d_rollout_policy_group_f32 below (likewise for acas2d_collect_* and
+ * acas2d_evaluate_policies_*).
  */
 typedef struct Acas2dPolicy {
     const void *w1t, *b1;    /* float[D][64]  = policy_net.0.weight TRANSPOSED, float[64] */
@@ -293,6 +295,29 @@ int acas2d_evaluate_policies_f64(const Acas2dConfig *cfg, const Acas2dState *sta
                                  const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
                                  int32_t n_traffic, uint8_t *outcome, int32_t *steps, void *total_reward,
                                  void *stream);
+
+/*
+ * acas2d_rollout_policy_group_f32 / acas2d_collect_group_f32 / acas2d_evaluate_policies_group_f32: the three launches
+ * above for n_traffic in {8, 16, 32, 64}, float32 -- arguments, outputs and rejections as their siblings'.  Additive
+ * to ABI 7.  The env's G lanes of the packed work shapes (4,2) (4,4) (4,8) (4,16) evaluate the network together:
+ * each lane 64 / G hidden units (at (4,16) one unit for the four envs of its wavefront), with the same fma sequence per
+ * unit and the same order in the head as the thread-per-env kernels, so that at n_traffic = 8 (where both exist) the results are equal bit for bit.  A lane reads
+ * its slice of a weight row as 16-byte vectors: w1t, b1, w2t, b2 (v1t, vb1, v2t, vb2) must be 16-byte aligned.
+ * Any other traffic count is rejected (ACAS2D_EINVAL; n_traffic in {1, 2, 3, 4} belongs to the siblings).  There are
+ * no float64 variants: the float64 policy kernels stay at n_traffic <= 4.
+ */
+int acas2d_rollout_policy_group_f32(const Acas2dConfig *cfg, const Acas2dState *state, const Acas2dStepIO *io,
+                                    const Acas2dPolicy *policy, const void *obs_in, int32_t n_steps,
+                                    uint64_t seed, int64_t env_offset, int64_t n_envs, int32_t n_traffic,
+                                    void *stream);
+int acas2d_collect_group_f32(const Acas2dConfig *cfg, const Acas2dState *state, const Acas2dStepIO *io,
+                             const Acas2dActorCritic *ac, const void *obs_in, int32_t n_steps, uint64_t seed,
+                             int64_t env_offset, int64_t n_envs, int32_t n_traffic, void *stream);
+int acas2d_evaluate_policies_group_f32(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                                       const Acas2dPolicy *policies, int32_t n_policies, int32_t n_episodes,
+                                       const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
+                                       int32_t n_traffic, uint8_t *outcome, int32_t *steps, void *total_reward,
+                                       void *stream);
 
 /*
  * acas2d_ppo_update_f32:ONE minibatch update of SB3 1.1.0's PPO.train() for the MlpPolicy actor-critic (the update
