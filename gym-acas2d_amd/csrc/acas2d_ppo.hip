@@ -17,35 +17,12 @@
 //   ppo_apply_kernel   one workgroup: the global gradient norm, torch.nn.utils.clip_grad_norm_'s coefficient, Adam
 //                      (torch.optim.Adam's bias-corrected form) on the 13 parameter tensors in place, gradient zeroed
 //                      for the next minibatch.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "acas2d.h"
+#include "acas2d_ppo.hpp"
 
 namespace acas2d {
-void set_error(const char* fmt, ...);
+using namespace ppo;
 
 namespace {
-
-constexpr int kH = 64;               // hidden width of SB3's MlpPolicy
-constexpr int kRow = 65;             // LDS row stride of a per-sample 64-vector (conflict-free rows AND columns)
-#define ACAS2D_C4 __attribute__((address_space(4)))
-
-// gradient / moment block of one network, in floats: w1 [64][D], b1 [64], w2 [64][64], b2 [64], w3 [64], b3 [1]
-__host__ __device__ constexpr int net_size(int D) { return kH * D + kH + kH * kH + kH + kH + 1; }
-__host__ __device__ constexpr int off_b1(int D) { return kH * D; }
-__host__ __device__ constexpr int off_w2(int D) { return kH * D + kH; }
-__host__ __device__ constexpr int off_b2(int D) { return kH * D + kH + kH * kH; }
-__host__ __device__ constexpr int off_w3(int D) { return kH * D + kH + kH * kH + kH; }
-__host__ __device__ constexpr int off_b3(int D) { return kH * D + kH + kH * kH + kH + kH; }
-
-struct NetW { const float *w1, *b1, *w2, *b2, *w3, *b3; };      // torch layouts: [out][in]
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
 
 template <int D>
 __global__ __launch_bounds__(64) void ppo_grad_kernel(NetW actor, NetW critic, const float* log_std_p, const float* obs,
@@ -267,9 +244,29 @@ int launch_grad(const Acas2dPpoUpdate& u, hipStream_t stream) {
 }
 
 }  // namespace
+
+int launch_ppo_apply(const Acas2dPpoUpdate& u, hipStream_t stream) {
+    const int D = u.obs_dim;
+    Segments seg;
+    float* ptrs[13] = {(float*)u.actor_w1, (float*)u.actor_b1, (float*)u.actor_w2, (float*)u.actor_b2, (float*)u.actor_w3,
+                       (float*)u.actor_b3, (float*)u.critic_w1, (float*)u.critic_b1, (float*)u.critic_w2, (float*)u.critic_b2,
+                       (float*)u.critic_w3, (float*)u.critic_b3, (float*)u.log_std};
+    const int cnt[6] = {kH * D, kH, kH * kH, kH, kH, 1};
+    int off = 0;
+    for (int k = 0; k < 12; ++k) { seg.s[k] = Segment{ptrs[k], off, cnt[k % 6]}; off += cnt[k % 6]; }
+    seg.s[12] = Segment{ptrs[12], off, 1};
+    hipLaunchKernelGGL(ppo_apply_kernel, dim3(1), dim3(1024), 0, stream, seg, off + 1, (float*)u.grad, (float*)u.adam_m,
+                       (float*)u.adam_v, (int32_t*)u.adam_step, u.ent_coef, u.max_grad_norm, u.learning_rate, u.beta1,
+                       u.beta2, u.adam_eps, (float*)u.stats);
+    hipError_t err = hipGetLastError();
+    if (err != hipSuccess) { set_error("acas2d_ppo_update launch: %s", hipGetErrorString(err)); return ACAS2D_EHIP; }
+    return ACAS2D_OK;
+}
+
 }  // namespace acas2d
 
 using namespace acas2d;
+using namespace acas2d::ppo;
 
 extern "C" int acas2d_ppo_workspace_floats(int32_t obs_dim) { return 2 * net_size(obs_dim) + 1; }
 
@@ -293,18 +290,5 @@ extern "C" int acas2d_ppo_update_f32(const Acas2dPpoUpdate* u, void* stream_) {
     }
     if (rc != ACAS2D_OK) return rc;                      // (a failed gradient launch must not read as a zero gradient)
     if (u->max_grad_norm < 0.0f) return ACAS2D_OK;      // tests: the raw gradient stays in `grad`, nothing is applied
-    Segments seg;
-    float* ptrs[13] = {(float*)u->actor_w1, (float*)u->actor_b1, (float*)u->actor_w2, (float*)u->actor_b2, (float*)u->actor_w3,
-                       (float*)u->actor_b3, (float*)u->critic_w1, (float*)u->critic_b1, (float*)u->critic_w2, (float*)u->critic_b2,
-                       (float*)u->critic_w3, (float*)u->critic_b3, (float*)u->log_std};
-    const int cnt[6] = {kH * D, kH, kH * kH, kH, kH, 1};
-    int off = 0;
-    for (int k = 0; k < 12; ++k) { seg.s[k] = Segment{ptrs[k], off, cnt[k % 6]}; off += cnt[k % 6]; }
-    seg.s[12] = Segment{ptrs[12], off, 1};
-    hipLaunchKernelGGL(ppo_apply_kernel, dim3(1), dim3(1024), 0, stream, seg, off + 1, (float*)u->grad, (float*)u->adam_m,
-                       (float*)u->adam_v, (int32_t*)u->adam_step, u->ent_coef, u->max_grad_norm, u->learning_rate, u->beta1,
-                       u->beta2, u->adam_eps, (float*)u->stats);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) { set_error("acas2d_ppo_update launch: %s", hipGetErrorString(err)); return ACAS2D_EHIP; }
-    return ACAS2D_OK;
+    return launch_ppo_apply(*u, stream);
 }

@@ -53,7 +53,8 @@ EXPORTS = ("acas2d_abi_version", "acas2d_config_size", "acas2d_state_size", "aca
            "acas2d_rollout_policy_f64", "acas2d_collect_f32", "acas2d_collect_f64", "acas2d_ppo_workspace_floats",
            "acas2d_ppo_update_f32", "acas2d_reset_f32", "acas2d_reset_f64", "acas2d_launch_geometry",
            "acas2d_state_is_consecutive", "acas2d_evaluate_policies_f32", "acas2d_evaluate_policies_f64",
-           "acas2d_rollout_policy_group_f32", "acas2d_collect_group_f32", "acas2d_evaluate_policies_group_f32")
+           "acas2d_rollout_policy_group_f32", "acas2d_collect_group_f32", "acas2d_evaluate_policies_group_f32",
+           "acas2d_ppo_update_wide_f32", "acas2d_ppo_wide_lds_bytes")
 
 
 class NativeLibraryError(RuntimeError):
@@ -123,8 +124,12 @@ def lib():
                       C.c_void_p]
     L.acas2d_ppo_workspace_floats.restype = C.c_int
     L.acas2d_ppo_workspace_floats.argtypes = [C.c_int32]
-    L.acas2d_ppo_update_f32.restype = C.c_int
-    L.acas2d_ppo_update_f32.argtypes = [C.POINTER(CPpoUpdate), C.c_void_p]
+    for name in ("acas2d_ppo_update_f32", "acas2d_ppo_update_wide_f32"):
+        f = getattr(L, name)
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(CPpoUpdate), C.c_void_p]
+    L.acas2d_ppo_wide_lds_bytes.restype = C.c_int
+    L.acas2d_ppo_wide_lds_bytes.argtypes = [C.c_int32]
     for name in ("acas2d_reset_f32", "acas2d_reset_f64"):
         f = getattr(L, name)
         f.restype = C.c_int

@@ -155,8 +155,15 @@ def ppo_loss(policy, cfg, obs, act, old_logp, adv, ret):
     return pg + cfg.ent_coef * ent + cfg.vf_coef * vf, pg, vf
 
 
+# observation widths the fused minibatch update is built for: acas2d_ppo_update_f32 (a lane holds its observation row in
+# registers; n_traffic 1, 2, 3, 4, 8) and acas2d_ppo_update_wide_f32 (four waves tile it through LDS; n_traffic 16, 32, 64)
+FUSED_UPDATE_WIDTHS = (8, 11, 14, 17, 29)
+FUSED_UPDATE_WIDE_WIDTHS = (53, 101, 197)
+
+
 class FusedUpdate:
-    """One PPO minibatch update as two hand-written launches (acas2d_ppo_update_f32, csrc/acas2d_ppo.hip): forward,
+    """One PPO minibatch update as two hand-written launches (acas2d_ppo_update_f32, csrc/acas2d_ppo.hip; for obs_dim
+    53, 101, 197 acas2d_ppo_update_wide_f32, csrc/acas2d_ppo_wide.hip -- `entry` names the one chosen): forward,
     ppo_loss(), backward, clip_grad_norm_ and Adam for the SB3 MlpPolicy actor-critic, on the parameter tensors in
     place.  `obs` [n, D], `act` / `old_logp` / `adv` / `ret` [n] are the flat float32 rollout buffers (their storage
     must stay put), `idx` an int64 device tensor naming the minibatch's rows (rewritten by the caller between
@@ -165,9 +172,18 @@ class FusedUpdate:
     def __init__(self, policy, cfg, obs, act, old_logp, adv, ret, beta1=0.9, beta2=0.999, adam_eps=1e-5):
         import ctypes as C
         from . import native
-        self._C, self._native, self._lib = C, native, native.lib()
-        dev = obs.device
         D = obs.shape[-1]
+        if D in FUSED_UPDATE_WIDTHS:
+            self.entry = "acas2d_ppo_update_f32"
+        elif D in FUSED_UPDATE_WIDE_WIDTHS:
+            self.entry = "acas2d_ppo_update_wide_f32"
+        else:
+            raise ValueError("FusedUpdate is built for obs_dim in {8, 11, 14, 17, 29} (n_traffic 1, 2, 3, 4, 8: "
+                             "acas2d_ppo_update_f32) and {53, 101, 197} (n_traffic 16, 32, 64: acas2d_ppo_update_wide_f32), "
+                             "got %d" % D)
+        self._C, self._native, self._lib = C, native, native.lib()
+        self._update = getattr(self._lib, self.entry)
+        dev = obs.device
         n = int(self._lib.acas2d_ppo_workspace_floats(D))
         z = lambda k, dt=torch.float32: torch.zeros(k, dtype=dt, device=dev)  # noqa: E731
         self.grad, self.m, self.v, self.step_count, self.stats = z(n), z(n), z(n), z(1, torch.int32), z(8)
@@ -191,7 +207,7 @@ class FusedUpdate:
 
     def step(self, idx):
         u = self._struct(idx)
-        self._native.check(self._lib.acas2d_ppo_update_f32(
+        self._native.check(self._update(
             self._C.byref(u), self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
 
     def last_losses(self):
@@ -211,7 +227,8 @@ class PPOTrainer:
     generator; float32 envs with 16, 32 or 64 traffic aircraft take the launch whose lanes share an env's network,
     ACAS2DVecEnv.collect(group=True), and so does evaluate()) or "eager" (op by op).  updater: "graphs" (default with
     `use_graphs`: one captured minibatch update of torch ops) or "fused" (FusedUpdate: the minibatch update as two
-    hand-written launches, its own Adam state; obs_dim <= 29)."""
+    hand-written launches, its own Adam state; obs_dim in {8, 11, 14, 17, 29} or {53, 101, 197}, i.e. n_traffic 1, 2, 3,
+    4, 8 or 16, 32, 64)."""
 
     def __init__(self, venv, config=None, policy=None, use_graphs=None, collector=None, updater=None):
         self.venv = venv
@@ -241,9 +258,9 @@ class PPOTrainer:
             raise ValueError("collector='fused' needs a thread-per-env work shape: n_traffic in {1, 2, 3, 4, 8} (float32) / "
                              "{1, 2, 3} (float64), or the group-cooperative float32 launch: n_traffic in {16, 32, 64}; "
                              "got %d -- use collector='graphs'" % venv.n_traffic)
-        if self.updater == "fused" and venv.obs_dim not in (8, 11, 14, 17, 29):
-            raise ValueError("updater='fused' is built for obs_dim in {8, 11, 14, 17, 29} (n_traffic 1, 2, 3, 4, 8), got %d "
-                             "-- use updater='graphs'" % venv.obs_dim)
+        if self.updater == "fused" and venv.obs_dim not in FUSED_UPDATE_WIDTHS + FUSED_UPDATE_WIDE_WIDTHS:
+            raise ValueError("updater='fused' is built for obs_dim in {8, 11, 14, 17, 29} (n_traffic 1, 2, 3, 4, 8) and "
+                             "{53, 101, 197} (n_traffic 16, 32, 64), got %d -- use updater='graphs'" % venv.obs_dim)
         # (fused: one multi-tensor kernel for the 13 parameter tensors instead of ~10 foreach launches)
         self.opt = torch.optim.Adam(self.policy.parameters(), lr=self.cfg.learning_rate, eps=1e-5,
                                     capturable=self.use_graphs, **({"fused": True} if self.use_graphs else {}))

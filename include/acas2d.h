@@ -354,6 +354,26 @@ int acas2d_ppo_workspace_floats(int32_t obs_dim);
 int acas2d_ppo_update_f32(const Acas2dPpoUpdate *u, void *stream);
 
 /*
+ * acas2d_ppo_update_wide_f32: acas2d_ppo_update_f32 for obs_dim in {53, 101, 197} (n_traffic 16, 32, 64), float32.
+ * Additive to ABI 7.  The same struct, the same semantics (SB3 1.1.0's PPO.train() minibatch, advantages normalised over
+ * the rows idx[0 .. n_rows), clip_grad_norm_ + Adam on the 13 parameter tensors IN PLACE), the same flat layout of
+ * grad / adam_m / adam_v (acas2d_ppo_workspace_floats(obs_dim) floats each: actor w1 b1 w2 b2 w3 b3, critic likewise,
+ * log_std; zero before the first call, grad left zero by every call), adam_step int32[1], stats float[8] ([2] gradient
+ * norm, [4] policy loss, [5] value loss of the last minibatch), and the same probe mode: max_grad_norm < 0 leaves the raw
+ * gradient in `grad` and applies nothing.  Every pointer is required and n_rows >= 2; any other obs_dim is rejected
+ * (ACAS2D_EINVAL; {8, 11, 14, 17, 29} belong to the sibling), before anything is launched.
+ * The gradient launch runs four waves per 64 samples and network, each wave a quarter of the hidden units, and tiles the
+ * obs_dim-sized operands through LDS; no observation column >= obs_dim of any row is read.  The apply launch is the
+ * sibling's.  Run-to-run: as for the sibling, the per-workgroup partial gradients are added to `grad` with float
+ * atomics, whose order is not fixed, so two runs of the same update agree to float32 rounding of the sums (~1e-7
+ * relative), not bit for bit.  The gradient kernel asks for acas2d_ppo_wide_lds_bytes(obs_dim) bytes of LDS per workgroup
+ * (79 / 91 / 115 KB; gfx950 has 160 KB), checked against the device at the first call (ACAS2D_EINVAL where it does not
+ * fit).  acas2d_ppo_wide_lds_bytes answers ACAS2D_EINVAL for an obs_dim outside the three.
+ */
+int acas2d_ppo_update_wide_f32(const Acas2dPpoUpdate *u, void *stream);
+int acas2d_ppo_wide_lds_bytes(int32_t obs_dim);
+
+/*
  * acas2d_reset_*: replaces ACAS2DEnv.reset() (environment.py:44-48 -> ACAS2DGame.__init__,
  * game.py:28-41,80-116, then observe()).  For every env with mask[e] != 0 (mask == NULL: all):
  *   do_init != 0: draw a fresh episode from the Philox stream described above

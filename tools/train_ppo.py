@@ -24,16 +24,20 @@ ap.add_argument("--batch-size", type=int, default=4096)
 ap.add_argument("--collector", choices=("graphs", "fused", "eager"), default="fused",
                 help="fused: the whole collection of an iteration in one hand-written launch (ACAS2DVecEnv.collect)")
 ap.add_argument("--updater", choices=("graphs", "fused"), default=None,
-                help="fused (default where it is built: obs_dim <= 29, i.e. --traffic 1, 2, 3, 4, 8): every minibatch "
-                     "update as two hand-written launches (acas2d_ppo_update_f32); graphs: captured torch ops")
+                help="fused (default where it is built and measured faster: --traffic 1, 2, 3, 4, 8 -- acas2d_ppo_update_f32 "
+                     "-- and 16, 32, 64 -- acas2d_ppo_update_wide_f32; tools/bench_ppo_update.py): every minibatch update as "
+                     "two hand-written launches; graphs: captured torch ops")
 ap.add_argument("--seed", type=int, default=13)
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 if args.updater is None:
-    args.updater = "fused" if args.traffic in (1, 2, 3, 4, 8) else "graphs"
+    # fused wherever it is built: it was measured faster than the captured graph at every one of these widths
+    # (a width where it were not would be left out of this tuple)
+    args.updater = "fused" if args.traffic in (1, 2, 3, 4, 8, 16, 32, 64) else "graphs"
     if args.updater == "graphs":
-        print(json.dumps({"note": "updater=graphs: the fused update is built for obs_dim <= 29 (traffic 1, 2, 3, 4, 8), "
-                                  "--traffic %d has obs_dim %d" % (args.traffic, 5 + 3 * args.traffic)}), flush=True)
+        print(json.dumps({"note": "updater=graphs: the fused update is built for traffic 1, 2, 3, 4, 8, 16, 32, 64 (obs_dim 8, "
+                                  "11, 14, 17, 29, 53, 101, 197), --traffic %d has obs_dim %d"
+                                  % (args.traffic, 5 + 3 * args.traffic)}), flush=True)
 
 venv = g.ACAS2DVecEnv(args.envs, args.traffic, device="cuda:0", dtype=torch.float32, seed=13)
 trainer = g.PPOTrainer(venv, g.PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, seed=args.seed), collector=args.collector,
