@@ -8,6 +8,11 @@ constexpr bool kFast = true;
 }
 #include "acas2d_launch.inl"
 
+// the set collector exists in float32 only
+namespace acas2d {
+template decltype(launch_collect_set<float>) launch_collect_set<float>;
+}
+
 #ifdef ACAS2D_STAMPS
 extern "C" int acas2d_debug_set_stamps_f32(unsigned long long* buf) {
     return (int)hipMemcpyToSymbol(HIP_SYMBOL(acas2d::g_stamps), &buf, sizeof(buf));

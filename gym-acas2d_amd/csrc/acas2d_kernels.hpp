@@ -1389,6 +1389,11 @@ struct PolicyW {
     const float* log_std;                            // [1]
     void *values_out, *logp_out;                     // T[n_steps][E]
     uint32_t nk0, nk1, noise_step;
+    // Mode::CollectSet (acas2d_collect_set_f32): K actor-critics side by side, member k on the envs
+    // [k member_stride, (k + 1) member_stride).  Every weight pointer above then names a [K][...] stack, log_std is
+    // float[K], and (nk0, nk1) hold the two halves of the ADDRESS of the K 64-bit noise keys: a wave loads its member's key
+    // into them before the first step.  (The field lies in what was the struct's tail padding: no layout changes.)
+    uint32_t member_stride;
 };
 constexpr int kPolicyHidden = 64;
 
@@ -1612,8 +1617,10 @@ enum class Mode {
     Policy,     // acas2d_rollout_policy_*
     Collect,    // acas2d_collect_*
     Eval,       // acas2d_evaluate_policies_*
+    CollectSet, // acas2d_collect_set_f32: Collect for K stacked actor-critics (float32, one lane per env)
 };
-constexpr bool policy_mode(Mode m) { return m == Mode::Policy || m == Mode::Collect || m == Mode::Eval; }
+constexpr bool sample_mode(Mode m) { return m == Mode::Collect || m == Mode::CollectSet; }
+constexpr bool policy_mode(Mode m) { return m == Mode::Policy || sample_mode(m) || m == Mode::Eval; }
 constexpr bool rollout_mode(Mode m) { return m == Mode::Rollout || policy_mode(m); }
 
 // ACAS2DEnv.step(), environment.py:29-42 -- and, with ROLLOUT, n_steps of them fused in one launch:
@@ -1638,8 +1645,9 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
                                                       StepIO<T> io_arg, uint32_t k0, uint32_t k1,
                                                       int64_t env_offset, int N_arg, int n_steps, PolicyArg<M == Mode::Eval> pw) {
     constexpr bool AUTO_RESET = M != Mode::Latch, ROLLOUT = rollout_mode(M);
-    constexpr bool POLICY = policy_mode(M), SAMPLE = M == Mode::Collect;
-    constexpr bool ARENA = M == Mode::Arena, EVAL = M == Mode::Eval;
+    constexpr bool POLICY = policy_mode(M), SAMPLE = sample_mode(M);
+    constexpr bool ARENA = M == Mode::Arena, EVAL = M == Mode::Eval, SET = M == Mode::CollectSet;
+    static_assert(!SET || (G == 1 && PACKED && sizeof(T) == 4), "set collection: float32, one lane per env");
     static_assert(!ROLLOUT || PACKED, "rollout modes: packed shapes");
     static_assert(!POLICY || G == 1 || (PACKED && sizeof(T) == 4 && group_policy_shape(C, G)),
                   "in-kernel policy: one lane per env, or the group-cooperative float32 shapes");
@@ -1825,6 +1833,22 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
         pw.w3 += (size_t)kp * kPolicyHidden; pw.b3 += kp;
     }
     (void)running; (void)res_i;
+    // SET: this wave's member (member_stride is a multiple of the wave, so one per wave: its weights stay SGPR operands),
+    // its slices of the stacks and its noise key -- one scalar load; everything below is Mode::Collect's step
+    if constexpr (SET) {
+        const uint32_t km = __builtin_amdgcn_readfirstlane(e_wave32 / pw.member_stride);
+        constexpr int DP = 5 + 3 * NS;
+        pw.w1t += (size_t)km * (DP * kPolicyHidden); pw.b1 += (size_t)km * kPolicyHidden;
+        pw.w2t += (size_t)km * (kPolicyHidden * kPolicyHidden); pw.b2 += (size_t)km * kPolicyHidden;
+        pw.w3 += (size_t)km * kPolicyHidden; pw.b3 += km;
+        pw.v1t += (size_t)km * (DP * kPolicyHidden); pw.vb1 += (size_t)km * kPolicyHidden;
+        pw.v2t += (size_t)km * (kPolicyHidden * kPolicyHidden); pw.vb2 += (size_t)km * kPolicyHidden;
+        pw.v3 += (size_t)km * kPolicyHidden; pw.vb3 += km;
+        pw.log_std += km;
+        const uint64_t* keys = reinterpret_cast<const uint64_t*>((uintptr_t)pw.nk0 | ((uintptr_t)pw.nk1 << 32));
+        const uint64_t key = ((const uint64_t ACAS2D_AS4*)keys)[km];
+        pw.nk0 = (uint32_t)key; pw.nk1 = (uint32_t)(key >> 32);
+    }
     for (int t = 0; t < T_steps; ++t) {
         // outputs of step t: [t][E] / [t][E][D] slices (t == 0 for the per-step launch)
         const int64_t te = ROLLOUT ? (int64_t)t * n_envs : 0;
@@ -2214,6 +2238,11 @@ int launch_evaluate_policies(const Acas2dConfig* cfg, const Acas2dState* st, int
                              int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
                              int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
                              hipStream_t stream, bool group = false);
+// acas2d_collect_set_f32 (float32 only: acas2d_f32.hip instantiates it)
+template <typename T>
+int launch_collect_set(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
+                       int32_t n_members, const uint64_t* noise_seeds, const void* obs_in, int32_t n_steps, uint64_t seed,
+                       int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream);
 // the *_group entry points (float32: the double instantiations reject every traffic count)
 template <typename T>
 int launch_rollout_policy_group(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io,

@@ -335,7 +335,8 @@ static int launch_mode(const Launch<T>& L, const PW& pw) {
     const T* const* a = M == Mode::Arena ? arena : general;
     dispatch(*L.cfg, L.sh, [&](auto fast, auto C, auto G, auto packed) {
         if constexpr ((M != Mode::Arena || (packed && sizeof(T) == 4)) && (!rollout_mode(M) || packed) &&
-                      (!policy_mode(M) || G == 1 || (sizeof(T) == 4 && packed && group_policy_shape(C, G))))
+                      (!policy_mode(M) || G == 1 || (sizeof(T) == 4 && packed && group_policy_shape(C, G))) &&
+                      (M != Mode::CollectSet || (G == 1 && sizeof(T) == 4)))
             hipLaunchKernelGGL((step_kernel<T, C, G, packed, fast, M>), dim3(L.g.grid), dim3(L.g.block), L.g.lds_bytes,
                                L.stream, a[0], a[1], a[2], a[3], a[4], a[5], (int32_t)L.n_envs, (int32_t)L.g.tile_elems,
                                L.p, rp, s, L.io, L.k0, L.k1, L.env_offset, L.N, L.n_steps, pw);
@@ -445,6 +446,48 @@ int launch_collect_group(const Acas2dConfig* cfg, const Acas2dState* st, const A
                          int32_t n_traffic, hipStream_t stream) {
     if (!ac) return fail("acas2d_collect: NULL actor-critic");
     return launch_policy<T>(cfg, st, io, &ac->actor, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream, ac, true);
+}
+
+// acas2d_collect_set_f32: acas2d_collect_* for K stacked actor-critics, member k on the envs [k EM, (k + 1) EM) with
+// EM = n_envs / K a multiple of the wave, so that the member is wave-uniform.  float32, one lane per env.
+template <typename T>
+int launch_collect_set(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
+                       int32_t n_members, const uint64_t* noise_seeds, const void* obs_in, int32_t n_steps, uint64_t seed,
+                       int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream) {
+    static_assert(sizeof(T) == 4, "acas2d_collect_set: float32 only");
+    static const char kScope[] = "float32, n_traffic in {1, 2, 3, 4, 8}; float64 and the group-cooperative launches of "
+                                 "n_traffic 16 / 32 / 64 collect one learner per call";
+    Launch<T> L{"acas2d_collect_set", cfg, st, io, seed, env_offset, n_envs, n_traffic, n_steps, stream};
+    const auto inputs = [&] {
+        if (!io->actions || !io->obs || !io->reward || !io->done || !io->outcome || !obs_in)
+            return fail("%s: obs_in, actions (output), obs, reward, done and outcome are required", L.name);
+        if (int rc = require_actor(L.name, &ac->actor)) return rc;
+        if (!ac->v1t || !ac->vb1 || !ac->v2t || !ac->vb2 || !ac->v3 || !ac->vb3 || !ac->log_std || !ac->values || !ac->logp)
+            return fail("%s: the value net's stacks, log_std, values and logp are required", L.name);
+        if (!noise_seeds) return fail("%s: NULL noise_seeds (one 64-bit key per member, on the device)", L.name);
+        if (n_members < 1) return fail("%s: n_members = %d (at least 1)", L.name, n_members);
+        if (n_envs >= 0 && (n_envs % n_members != 0 || (n_envs / n_members) % 64 != 0))
+            return fail("%s: n_envs = %lld is not n_members = %d x a multiple of 64 (a wavefront's envs belong to ONE member)",
+                        L.name, (long long)n_envs, n_members);
+        return ACAS2D_OK;
+    };
+    const auto shape = [&](Shape* sh) {
+        *sh = Shape{n_traffic, 1, true};
+        if (shape_instantiated(*sh)) return ACAS2D_OK;
+        return fail("%s: n_traffic = %d has no thread-per-env shape (%s)", L.name, n_traffic, kScope);
+    };
+    const auto go = [&] {
+        PolicyW pw = actor<PolicyW>(&ac->actor, obs_in);
+        pw.actions_out = const_cast<void*>(io->actions);
+        pw.v1t = (const float*)ac->v1t; pw.vb1 = (const float*)ac->vb1; pw.v2t = (const float*)ac->v2t;
+        pw.vb2 = (const float*)ac->vb2; pw.v3 = (const float*)ac->v3; pw.vb3 = (const float*)ac->vb3;
+        pw.log_std = (const float*)ac->log_std; pw.values_out = ac->values; pw.logp_out = ac->logp;
+        const uint64_t keys = (uint64_t)reinterpret_cast<uintptr_t>(noise_seeds);     // the kernel loads its member's key
+        pw.nk0 = (uint32_t)keys; pw.nk1 = (uint32_t)(keys >> 32); pw.noise_step = ac->noise_step;
+        pw.member_stride = (uint32_t)(n_envs / n_members);
+        return launch_mode<Mode::CollectSet>(L, pw);
+    };
+    return prepare(L, Words{"cfg / io / actor-critic", kSizes, kNegative}, io && ac, inputs, shape, go);
 }
 
 // K stacked policies scored on shared episodes: policy k plays envs [k EP, (k + 1) EP) of the state, EP = n_episodes

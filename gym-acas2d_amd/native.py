@@ -48,13 +48,22 @@ class CPpoUpdate(C.Structure):
         [(n, C.c_void_p) for n in ("grad", "adam_m", "adam_v", "adam_step", "stats")]
 
 
+class CPpoUpdateSet(C.Structure):
+    """struct Acas2dPpoUpdateSet: one PPO minibatch update of K stacked learners (include/acas2d.h)."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "actor_w1", "actor_b1", "actor_w2", "actor_b2", "actor_w3", "actor_b3", "critic_w1", "critic_b1", "critic_w2",
+        "critic_b2", "critic_w3", "critic_b3", "log_std", "obs", "act", "old_logp", "adv", "ret", "idx")] + \
+        [(n, C.c_int32) for n in ("n_members", "n_rows", "obs_dim", "apply")] + \
+        [(n, C.c_void_p) for n in ("hyper", "grad", "adam_m", "adam_v", "adam_step", "stats")]
+
+
 EXPORTS = ("acas2d_abi_version", "acas2d_config_size", "acas2d_state_size", "acas2d_last_error", "acas2d_step_f32",
            "acas2d_step_f64", "acas2d_rollout_f32", "acas2d_rollout_f64", "acas2d_rollout_policy_f32",
            "acas2d_rollout_policy_f64", "acas2d_collect_f32", "acas2d_collect_f64", "acas2d_ppo_workspace_floats",
            "acas2d_ppo_update_f32", "acas2d_reset_f32", "acas2d_reset_f64", "acas2d_launch_geometry",
            "acas2d_state_is_consecutive", "acas2d_evaluate_policies_f32", "acas2d_evaluate_policies_f64",
            "acas2d_rollout_policy_group_f32", "acas2d_collect_group_f32", "acas2d_evaluate_policies_group_f32",
-           "acas2d_ppo_update_wide_f32", "acas2d_ppo_wide_lds_bytes")
+           "acas2d_ppo_update_wide_f32", "acas2d_ppo_wide_lds_bytes", "acas2d_collect_set_f32", "acas2d_ppo_update_set_f32")
 
 
 class NativeLibraryError(RuntimeError):
@@ -122,6 +131,12 @@ def lib():
         f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.c_int64, C.POINTER(CPolicy), C.c_int32, C.c_int32,
                       C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                       C.c_void_p]
+    L.acas2d_collect_set_f32.restype = C.c_int
+    L.acas2d_collect_set_f32.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.POINTER(CStepIO), C.POINTER(CActorCritic),
+                                         C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int64,
+                                         C.c_int32, C.c_void_p]
+    L.acas2d_ppo_update_set_f32.restype = C.c_int
+    L.acas2d_ppo_update_set_f32.argtypes = [C.POINTER(CPpoUpdateSet), C.c_void_p]
     L.acas2d_ppo_workspace_floats.restype = C.c_int
     L.acas2d_ppo_workspace_floats.argtypes = [C.c_int32]
     for name in ("acas2d_ppo_update_f32", "acas2d_ppo_update_wide_f32"):

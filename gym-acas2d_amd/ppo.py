@@ -599,3 +599,367 @@ class PPOTrainer:
             if crossed(checkpoint_every):
                 save_sb3_policy(self.policy, os.path.join(save_dir, "checkpoints", "model_%d_steps.zip" % self.num_timesteps))
         return history
+
+
+# ---- K learners at once: the seeds or hyper-parameter sets of a sweep as ONE population ---------------------------------
+# the 13 parameter tensors in FusedUpdate's order (the flat grad / moment layout of include/acas2d.h)
+PARAM_NAMES = ("mlp_extractor.policy_net.0.weight", "mlp_extractor.policy_net.0.bias",
+               "mlp_extractor.policy_net.2.weight", "mlp_extractor.policy_net.2.bias", "action_net.weight", "action_net.bias",
+               "mlp_extractor.value_net.0.weight", "mlp_extractor.value_net.0.bias",
+               "mlp_extractor.value_net.2.weight", "mlp_extractor.value_net.2.bias", "value_net.weight", "value_net.bias",
+               "log_std")
+# what may differ between the members of a population, and what the shared launches need equal
+MEMBER_FIELDS = ("seed", "learning_rate", "clip_range", "ent_coef", "vf_coef", "max_grad_norm", "gamma", "gae_lambda")
+SHARED_FIELDS = ("n_steps", "batch_size", "n_epochs")
+# hyper[k]: the row acas2d_ppo_update_set_f32 reads for member k
+HYPER_SLOTS = ("clip_range", "vf_coef", "ent_coef", "max_grad_norm", "learning_rate", "beta1", "beta2", "adam_eps")
+
+
+class ActorCriticSet:
+    """K `ActorCritic`s held as [K, ...] stacks: `params[name]` is the float32 tensor of the K members' `name`
+    (PARAM_NAMES, torch layouts) -- what acas2d_ppo_update_set_f32 updates in place and, transposed,
+    acas2d_collect_set_f32 reads."""
+
+    def __init__(self, n_members, obs_dim, device="cpu"):
+        self.n_members, self.obs_dim = int(n_members), int(obs_dim)
+        like = ActorCritic(obs_dim)
+        self.params = {n: torch.zeros((self.n_members,) + tuple(like.get_parameter(n).shape), dtype=torch.float32,
+                                      device=device) for n in PARAM_NAMES}
+
+    @classmethod
+    def from_members(cls, members, device=None):
+        members = list(members)
+        if not members:
+            raise ValueError("ActorCriticSet.from_members needs at least one member")
+        D = members[0].mlp_extractor.policy_net[0].in_features
+        dev = members[0].log_std.device if device is None else device
+        out = cls(len(members), D, dev)
+        with torch.no_grad():
+            for k, m in enumerate(members):
+                if m.mlp_extractor.policy_net[0].in_features != D:
+                    raise ValueError("every member must have obs_dim %d" % D)
+                for n in PARAM_NAMES:
+                    out.params[n][k].copy_(m.get_parameter(n).detach().to(torch.float32))
+        return out
+
+    @property
+    def device(self):
+        return self.params["log_std"].device
+
+    def to(self, device):
+        self.params = {n: t.to(device) for n, t in self.params.items()}
+        return self
+
+    def member(self, k):
+        """A fresh `ActorCritic` holding a copy of member k's parameters, bit for bit."""
+        m = ActorCritic(self.obs_dim)
+        with torch.no_grad():
+            for n in PARAM_NAMES:
+                m.get_parameter(n).copy_(self.params[n][k].cpu())
+        return m.to(self.device)
+
+    def actor_weights(self):
+        """K tuples (w1 [64,D], b1, w2 [64,64], b2, w3 [1,64], b3): the `policies` of evaluate_policies_fused()."""
+        return [tuple(self.params[n][k].detach() for n in PARAM_NAMES[:6]) for k in range(self.n_members)]
+
+    def collector_weights(self):
+        """The 13 stacks as acas2d_collect_set_f32 takes them: the first two layers of each net transposed
+        ([K][D][64], [K][64][64]), the heads and biases flat, log_std [K]."""
+        p, K = self.params, self.n_members
+        t = lambda n: p[n].detach().transpose(1, 2).contiguous()  # noqa: E731
+        f = lambda n: p[n].detach().reshape(K, -1).contiguous()  # noqa: E731
+        out = []
+        for net, head in (("policy_net", "action_net"), ("value_net", "value_net")):
+            pre = "mlp_extractor.%s." % net
+            out += [t(pre + "0.weight"), f(pre + "0.bias"), t(pre + "2.weight"), f(pre + "2.bias"), f(head + ".weight"),
+                    f(head + ".bias")]
+        return out + [f("log_std").reshape(K)]
+
+    @torch.no_grad()
+    def values(self, obs):
+        """The K critics on their own envs: obs [K * EM, D] (member k's rows [k EM, (k + 1) EM)) -> [K * EM]."""
+        p, K = self.params, self.n_members
+        x = obs.to(torch.float32).reshape(K, -1, self.obs_dim)
+        pre = "mlp_extractor.value_net."
+        h = torch.tanh(torch.baddbmm(p[pre + "0.bias"].unsqueeze(1), x, p[pre + "0.weight"].transpose(1, 2)))
+        h = torch.tanh(torch.baddbmm(p[pre + "2.bias"].unsqueeze(1), h, p[pre + "2.weight"].transpose(1, 2)))
+        return torch.baddbmm(p["value_net.bias"].unsqueeze(1), h, p["value_net.weight"].transpose(1, 2)).reshape(-1)
+
+
+class FusedUpdateSet:
+    """FusedUpdate for the K members of an `ActorCriticSet` in two launches whatever K is (acas2d_ppo_update_set_f32,
+    csrc/acas2d_ppo_set.hip).  `obs` [n, D], `act` / `old_logp` / `adv` / `ret` [n] are ONE flat float32 rollout buffer
+    shared by the members (their storage must stay put); `step(idx)` takes an int64 device tensor [K, B]: row k names
+    member k's minibatch as rows of that buffer.  `hyper` is a float32 device tensor [K, 8] (HYPER_SLOTS) the kernels
+    read at every call: rewrite it between calls to change a member's learning rate, clip range, ...  Keeps the
+    members' Adam moments and step counts ([K, ...]).  float32, obs_dim in {8, 11, 14, 17, 29}."""
+
+    def __init__(self, policy_set, configs, obs, act, old_logp, adv, ret, beta1=0.9, beta2=0.999, adam_eps=1e-5):
+        import ctypes as C
+        from . import native
+        D, K = obs.shape[-1], policy_set.n_members
+        if D not in FUSED_UPDATE_WIDTHS:
+            raise ValueError("FusedUpdateSet is built for obs_dim in {8, 11, 14, 17, 29} (n_traffic 1, 2, 3, 4, 8), float32; "
+                             "got %d (the wide update of n_traffic 16 / 32 / 64 takes one learner per call: FusedUpdate)" % D)
+        if len(configs) != K or policy_set.obs_dim != D:
+            raise ValueError("FusedUpdateSet needs one config per member and members of obs_dim %d" % D)
+        self._C, self._native, self._lib = C, native, native.lib()
+        dev = obs.device
+        n = int(self._lib.acas2d_ppo_workspace_floats(D))
+        z = lambda *k, dt=torch.float32: torch.zeros(*k, dtype=dt, device=dev)  # noqa: E731
+        self.grad, self.m, self.v, self.step_count, self.stats = z(K, n), z(K, n), z(K, n), z(K, dt=torch.int32), z(K, 8)
+        self.hyper = torch.tensor([[c.clip_range, c.vf_coef, c.ent_coef, c.max_grad_norm, c.learning_rate, beta1, beta2,
+                                    adam_eps] for c in configs], dtype=torch.float32).to(dev)
+        self._params = [policy_set.params[name] for name in PARAM_NAMES]
+        assert all(p.dtype == torch.float32 and p.is_contiguous() and p.device == dev for p in self._params)
+        self._bufs = [t.reshape(-1) if i else t.reshape(-1, D) for i, t in enumerate((obs, act, old_logp, adv, ret))]
+        assert all(t.dtype == torch.float32 and t.is_contiguous() for t in self._bufs)
+        self.policy_set, self.D, self.K, self.device = policy_set, D, K, dev
+
+    def step(self, idx, apply=True):
+        """One minibatch update of every member; apply=False leaves the raw gradients in `grad` and applies nothing."""
+        assert idx.dtype == torch.int64 and idx.is_contiguous() and idx.dim() == 2 and idx.shape[0] == self.K
+        p = lambda t: t.data_ptr()  # noqa: E731
+        u = self._native.CPpoUpdateSet(*[p(t) for t in self._params], *[p(t) for t in self._bufs], p(idx), self.K,
+                                       idx.shape[1], self.D, 1 if apply else 0, p(self.hyper), p(self.grad), p(self.m),
+                                       p(self.v), p(self.step_count), p(self.stats))
+        self._native.check(self._lib.acas2d_ppo_update_set_f32(
+            self._C.byref(u), self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def last_losses(self):
+        s = self.stats.cpu()
+        return [{"pg_loss": float(r[4]), "value_loss": float(r[5]), "grad_norm": float(r[2])} for r in s]
+
+
+class PopulationTrainer:
+    """K independent PPO learners trained side by side on ONE env: member k owns the envs [k EM, (k + 1) EM) of `venv`
+    (EM = num_envs / K), collects with its own actor-critic and noise key, and is updated on its own rows with its own
+    hyper-parameters -- one collection launch (ACAS2DVecEnv.collect_set), two launches per minibatch (FusedUpdateSet) and
+    one evaluation launch (evaluate_policies_fused) for all K, where K PPOTrainer(collector="fused", updater="fused") runs
+    take K times as many.  There is no exchange between members: no exploit / explore step, K separate runs.
+
+    `configs`: K PPOConfig.  MEMBER_FIELDS may differ; n_steps, batch_size and n_epochs must be equal (the members share
+    every launch).  Member k starts from the weights PPOTrainer(PPOConfig(seed=s_k)) constructs, draws its minibatch
+    permutations from its own torch.Generator and its collection noise with the key s_k.  `num_timesteps` counts ONE
+    member's env steps (n_steps x EM per iteration), so learn()'s arguments mean per member what PPOTrainer.learn()'s do.
+    With per-member gamma / gae_lambda GAE takes them as per-env float32 vectors (the product gamma x lambda is then
+    rounded in float32); equal values are passed as the numbers they are.
+    Out of scope: float64, n_traffic 16 / 32 / 64 (the group-cooperative launches and the wide update), members with
+    different n_steps / batch_size / n_epochs, more than one GPU."""
+
+    def __init__(self, venv, configs):
+        configs = list(configs)
+        if not configs:
+            raise ValueError("PopulationTrainer needs at least one PPOConfig")
+        for f in SHARED_FIELDS:
+            if len({getattr(c, f) for c in configs}) != 1:
+                raise ValueError("every member of a population needs the same %s (the members share every launch), got %s"
+                                 % (f, [getattr(c, f) for c in configs]))
+        if getattr(venv, "dtype", torch.float32) != torch.float32:
+            raise ValueError("PopulationTrainer is float32 only (float64 trains one learner per process: PPOTrainer), this "
+                             "env is %s" % (venv.dtype,))
+        if venv.n_traffic not in (1, 2, 3, 4, 8) or venv.obs_dim not in FUSED_UPDATE_WIDTHS:
+            raise ValueError("PopulationTrainer needs n_traffic in {1, 2, 3, 4, 8}, got %d (the group-cooperative launches "
+                             "and the wide update of n_traffic 16 / 32 / 64 train one learner per process: PPOTrainer)"
+                             % venv.n_traffic)
+        K = len(configs)
+        if venv.num_envs % K or (venv.num_envs // K) % 64:
+            raise ValueError("PopulationTrainer needs num_envs = K x a multiple of 64, got num_envs = %d for K = %d members"
+                             % (venv.num_envs, K))
+        self.venv, self.configs, self.K, self.EM = venv, configs, K, venv.num_envs // K
+        self.cfg = configs[0]                           # the shared fields
+        self.device = venv.device
+        members = []
+        for c in configs:                               # PPOTrainer.__init__'s construction, member by member
+            torch.manual_seed(c.seed)
+            members.append(ActorCritic(venv.obs_dim))
+        self.policy_set = ActorCriticSet.from_members(members, device=self.device)
+        self.generators = []
+        for c in configs:
+            gen = torch.Generator(device=self.device)
+            gen.manual_seed(c.seed)
+            self.generators.append(gen)
+        self.noise_seeds = torch.as_tensor(np.asarray([c.seed & (2 ** 64 - 1) for c in configs], np.uint64).view(np.int64)
+                                           ).to(self.device)
+        per_env = lambda f: (getattr(configs[0], f) if len({getattr(c, f) for c in configs}) == 1 else  # noqa: E731
+                             torch.tensor([getattr(c, f) for c in configs], dtype=torch.float32, device=self.device
+                                          ).repeat_interleave(self.EM))
+        self.gamma, self.gae_lambda = per_env("gamma"), per_env("gae_lambda")
+        self.obs = venv.reset().to(torch.float32).clone()
+        self.nan_events = torch.zeros(K, dtype=torch.int64, device=self.device)
+        self.num_timesteps = 0
+        self.ep_returns, self.ep_lengths, self.ep_outcomes = ([[] for _ in range(K)] for _ in range(3))
+        self.history = []
+        self._fused_out = self._fused_update = None
+        E, T, D, dev = venv.num_envs, self.cfg.n_steps, venv.obs_dim, self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.b_obs = torch.zeros(T, E, D, **f32)
+        self.b_act = torch.zeros(T, E, 1, **f32)
+        self.b_logp, self.b_val, self.b_rew = (torch.zeros(T, E, **f32) for _ in range(3))
+        self.b_adv, self.b_ret, self.b_epret = (torch.zeros(T, E, **f32) for _ in range(3))
+        self.b_done = torch.zeros(T, E, dtype=torch.bool, device=dev)
+        self.b_eplen = torch.zeros(T, E, dtype=torch.int32, device=dev)
+        self.b_outcome = torch.zeros(T, E, dtype=torch.uint8, device=dev)
+        self.last_value = torch.zeros(E, **f32)
+        # member k's rows of the flat [T * E] buffer, in the order its own [T * EM] buffer would have them
+        t_ = torch.arange(T, device=dev).unsqueeze(1) * E + torch.arange(self.EM, device=dev).unsqueeze(0)
+        self.member_rows = (torch.arange(K, device=dev).view(K, 1, 1) * self.EM + t_.unsqueeze(0)).reshape(K, T * self.EM)
+        n = T * self.EM
+        B = min(self.cfg.batch_size, n)
+        self.mb_idx = torch.zeros(K, B, dtype=torch.int64, device=dev)
+        # the partial last minibatch of an epoch, as PPOTrainer takes it (not a single row: no standard deviation)
+        self.mb_tail = torch.zeros(K, n % B, dtype=torch.int64, device=dev) if n % B > 1 else None
+
+    def member(self, k):
+        """Member k's current actor-critic (a copy)."""
+        return self.policy_set.member(k)
+
+    def collect(self):
+        T, E, K, EM = self.cfg.n_steps, self.venv.num_envs, self.K, self.EM
+        out = self.venv.collect_set(self.policy_set, T, self.noise_seeds, noise_step=self.num_timesteps // EM,
+                                    out=self._fused_out)
+        self._fused_out = out
+        obs_all, rew = out["obs"], out["reward"]
+        nan = torch.isnan(rew).view(T, K, EM).sum((0, 2)) + torch.isnan(obs_all[1:]).any(-1).view(T, K, EM).sum((0, 2))
+        self.nan_events.add_(nan)
+        obs_all = torch.nan_to_num(obs_all, nan=0.0, posinf=0.0, neginf=0.0)    # what the kernel fed the networks
+        self.b_obs.copy_(obs_all[:T])
+        self.obs.copy_(obs_all[T])
+        self.b_act.copy_(out["actions"].unsqueeze(-1))
+        self.b_val.copy_(out["values"])
+        self.b_logp.copy_(out["logp"])
+        self.b_rew.copy_(torch.nan_to_num(rew, nan=0.0))
+        self.b_done.copy_(out["done"])
+        self.b_epret.copy_(out["episode_return"])
+        self.b_eplen.copy_(out["episode_steps"])
+        self.b_outcome.copy_(out["outcome"])
+        self.last_value.copy_(self.policy_set.values(self.obs))
+        adv, ret = compute_gae(self.b_rew, self.b_val, self.b_done, self.last_value, self.gamma, self.gae_lambda)
+        self.b_adv.copy_(adv)
+        self.b_ret.copy_(ret)
+        done = self.b_done
+        if bool(done.any()):                              # the iteration's one host synchronisation
+            member_of = (torch.arange(E, device=self.device) // EM).expand(T, E)[done].cpu()
+            r, l, o = self.b_epret[done].cpu(), (self.b_eplen[done] - 1).cpu(), self.b_outcome[done].cpu()
+            for k in range(K):
+                sel = member_of == k
+                if bool(sel.any()):
+                    self.ep_returns[k].append(r[sel])
+                    self.ep_lengths[k].append(l[sel])
+                    self.ep_outcomes[k].append(o[sel])
+        self.num_timesteps += T * EM
+
+    def update(self):
+        cfg, K = self.cfg, self.K
+        n, B = cfg.n_steps * self.EM, self.mb_idx.shape[1]
+        if self._fused_update is None:
+            self._fused_update = FusedUpdateSet(self.policy_set, self.configs, self.b_obs, self.b_act, self.b_logp, self.b_adv,
+                                                self.b_ret)
+        fu = self._fused_update
+        for _ in range(cfg.n_epochs):
+            perm = torch.stack([torch.randperm(n, device=self.device, generator=g) for g in self.generators])
+            rows = self.member_rows.gather(1, perm)       # [K, n]: each member's permutation, as rows of the shared buffer
+            for i in range(0, n - B + 1, B):
+                self.mb_idx.copy_(rows[:, i:i + B])
+                fu.step(self.mb_idx)
+            if self.mb_tail is not None:
+                self.mb_tail.copy_(rows[:, n - n % B:])
+                fu.step(self.mb_tail)
+        std = self.policy_set.params["log_std"].detach().exp().reshape(K).cpu().tolist()
+        return [{"pg_loss": st["pg_loss"], "value_loss": st["value_loss"], "std": std[k]}
+                for k, st in enumerate(fu.last_losses())]
+
+    def optimizer_state(self):
+        """The members' Adam state: step [K], exp_avg / exp_avg_sq [K, n] in the flat layout of include/acas2d.h."""
+        fu = self._fused_update
+        if fu is None:
+            return {"updater": "fused", "step": [0] * self.K, "exp_avg": None, "exp_avg_sq": None}
+        return {"updater": "fused", "step": fu.step_count.cpu().tolist(), "exp_avg": fu.m, "exp_avg_sq": fu.v}
+
+    def recent_episodes(self, clear=True):
+        """One PPOTrainer.recent_episodes() dict per member (None where no episode ended)."""
+        out = []
+        for k in range(self.K):
+            if not self.ep_returns[k]:
+                out.append(None)
+                continue
+            r, l, o = torch.cat(self.ep_returns[k]), torch.cat(self.ep_lengths[k]), torch.cat(self.ep_outcomes[k])
+            out.append({"episodes": int(r.numel()), "ep_rew_mean": float(r.mean()), "ep_len_mean": float(l.float().mean()),
+                        "goal": float((o == 1).float().mean()), "collision": float((o == 2).float().mean()),
+                        "timeout": float((o == 3).float().mean())})
+            if clear:
+                self.ep_returns[k], self.ep_lengths[k], self.ep_outcomes[k] = [], [], []
+        return out
+
+    def evaluate(self, n_episodes, rng):
+        """Score the K current actors deterministically on the SAME `n_episodes` fresh episodes drawn from `rng` in ONE
+        launch (policy.evaluate_policies_fused): its dict, rows = members."""
+        from . import reset_parity
+        from .policy import evaluate_policies_fused
+        own, trf, goal = reset_parity.draw_episodes(self.venv.config, n_episodes, rng)
+        return evaluate_policies_fused(self.policy_set.actor_weights(), own, trf, goal, dtype=self.venv.dtype,
+                                       device=self.device, config=self.venv.config)
+
+    def learn(self, total_timesteps, log=print, eval_every=None, eval_episodes=10, eval_seed=None, save_dir=None,
+              checkpoint_every=None):
+        """PPOTrainer.learn() for every member at once; every count of timesteps is ONE member's.  Records carry a
+        "member" key; `history` (returned, and kept as self.history) holds one record per member and iteration, plus one
+        per member and evaluation.  Evaluations score all members on the same episodes (one random.Random(eval_seed),
+        default the first member's seed, kept for the run).  Files go under save_dir/member_<k>/ as PPOTrainer writes them
+        under save_dir: results/evaluations.npz, best_model.zip (per member: its own best), checkpoints/."""
+        if checkpoint_every and not save_dir:
+            raise ValueError("checkpoint_every needs save_dir")
+        from .policy import save_sb3_policy
+        K = self.K
+        eval_rng = random.Random(self.configs[0].seed if eval_seed is None else eval_seed) if eval_every else None
+        evals = [{"timesteps": [], "results": [], "ep_lengths": []} for _ in range(K)]
+        best = [-math.inf] * K
+        mdir = lambda k: os.path.join(save_dir, "member_%d" % k)  # noqa: E731
+        t0 = time.time()
+        it = 0
+        history = self.history
+        while self.num_timesteps < total_timesteps:
+            before = self.num_timesteps
+            self.collect()
+            stats = self.update()
+            it += 1
+            eps = self.recent_episodes()
+            nan = self.nan_events.cpu().tolist()
+            for k in range(K):
+                rec = {"member": k, "iteration": it, "timesteps": self.num_timesteps,
+                       "fps": self.num_timesteps / max(time.time() - t0, 1e-9), **(eps[k] or {}), **stats[k],
+                       "nan_events": int(nan[k])}
+                history.append(rec)
+                if log:
+                    log(rec)
+            crossed = lambda every: bool(every) and before // every < self.num_timesteps // every  # noqa: E731
+            if crossed(eval_every):
+                out = self.evaluate(eval_episodes, eval_rng)
+                for k in range(K):
+                    ret, steps, oc = out["total_reward"][k], out["steps"][k], out["outcome"][k]
+                    mean = float(ret.mean())
+                    new_best = mean > best[k]
+                    best[k] = max(best[k], mean)
+                    erec = {"member": k, "eval": True, "timesteps": self.num_timesteps, "mean_reward": mean,
+                            "std_reward": float(ret.std()), "mean_ep_length": float((steps - 1).mean()),
+                            "goal": float((oc == 1).mean()), "collision": float((oc == 2).mean()),
+                            "timeout": float((oc == 3).mean()), "unfinished": int(out["unfinished"][k]), "new_best": new_best}
+                    if save_dir:
+                        ev = evals[k]
+                        ev["timesteps"].append(self.num_timesteps)
+                        ev["results"].append(ret.astype(np.float64))
+                        ev["ep_lengths"].append(steps.astype(np.int64) - 1)
+                        os.makedirs(os.path.join(mdir(k), "results"), exist_ok=True)
+                        np.savez(os.path.join(mdir(k), "results", "evaluations.npz"),
+                                 timesteps=np.asarray(ev["timesteps"], np.int64), results=np.stack(ev["results"]),
+                                 ep_lengths=np.stack(ev["ep_lengths"]))
+                        if new_best:
+                            save_sb3_policy(self.member(k), os.path.join(mdir(k), "best_model.zip"))
+                    history.append(erec)
+                    if log:
+                        log(erec)
+            if crossed(checkpoint_every):
+                for k in range(K):
+                    save_sb3_policy(self.member(k),
+                                    os.path.join(mdir(k), "checkpoints", "model_%d_steps.zip" % self.num_timesteps))
+        return history

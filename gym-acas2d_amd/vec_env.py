@@ -486,6 +486,68 @@ class ACAS2DVecEnv:
         out["_weights"] = keep       # keep the transposed copies alive until the launch ran
         return out
 
+    # traffic counts with a float32 thread-per-env kernel: what acas2d_collect_set_f32 is built for
+    SET_TRAFFIC = (1, 2, 3, 4, 8)
+
+    def check_member_split(self, n_members):
+        """Envs per member for a set of `n_members` learners on this env, or a ValueError saying what
+        acas2d_collect_set_f32 cannot take: float32, n_traffic in {1, 2, 3, 4, 8}, num_envs = K x a multiple of 64."""
+        K = int(n_members)
+        if self.dtype != torch.float32:
+            raise ValueError("collect_set() is float32 only (float64 collects one learner per launch: collect()), this env "
+                             "is %s" % (self.dtype,))
+        if self.n_traffic not in self.SET_TRAFFIC:
+            raise ValueError("collect_set() needs a thread-per-env work shape: n_traffic in {1, 2, 3, 4, 8}, got %d (the "
+                             "group-cooperative launches of n_traffic 16 / 32 / 64 collect one learner per launch: "
+                             "collect(group=True))" % self.n_traffic)
+        if K < 1 or self.num_envs % K or (self.num_envs // K) % 64:
+            raise ValueError("collect_set() needs num_envs = K x a multiple of 64 (a wavefront's envs belong to one member), "
+                             "got num_envs = %d, K = %d" % (self.num_envs, K))
+        return self.num_envs // K
+
+    def collect_set(self, policy_set, n_steps, noise_seeds, noise_step=0, out=None):
+        """collect() for K independent actor-critics in ONE kernel launch (acas2d_collect_set_f32).  `policy_set` is a
+        `ppo.ActorCriticSet` of K members; member k owns the envs [k EM, (k + 1) EM), EM = num_envs / K a multiple of 64,
+        and draws its noise with the key noise_seeds[k] (K ints, or an int64 device tensor holding the keys' bit
+        patterns) on collect()'s counter (global env index, noise_step + t).  Returns collect()'s dict, in the same
+        [T, E] layout: the columns of member k equal what collect(member k, noise_seed=noise_seeds[k]) returns on an env
+        of EM envs at env_offset + k EM with the same seed, bit for bit.  float32, n_traffic in {1, 2, 3, 4, 8}."""
+        if not self.auto_reset:
+            raise RuntimeError("collect_set() has VecEnv auto-reset semantics; construct with auto_reset=True")
+        K = int(policy_set.n_members)
+        self.check_member_split(K)
+        T, E, D, dev = int(n_steps), self.num_envs, self.obs_dim, self.device
+        if policy_set.obs_dim != D:
+            raise ValueError("the set's members must be SB3 MlpPolicy actor-critics %d -> 64 -> 64 -> 1, got obs_dim %d"
+                             % (D, policy_set.obs_dim))
+        keep = [t.to(dev) for t in policy_set.collector_weights()]
+        if torch.is_tensor(noise_seeds):
+            keys = noise_seeds.to(device=dev, dtype=torch.int64).contiguous()
+        else:
+            keys = torch.as_tensor(np.asarray([int(s) & (2 ** 64 - 1) for s in noise_seeds], np.uint64).view(np.int64)).to(dev)
+        if keys.numel() != K:
+            raise ValueError("collect_set() needs one noise seed per member: %d for %d members" % (keys.numel(), K))
+        if out is None:
+            z = lambda *shape, dt=self.dtype: torch.zeros(*shape, dtype=dt, device=dev)  # noqa: E731
+            out = {"obs": z(T + 1, E, D), "actions": z(T, E), "values": z(T, E), "logp": z(T, E), "reward": z(T, E),
+                   "done_u8": z(T, E, dt=torch.uint8), "outcome": z(T, E, dt=torch.uint8), "episode_return": z(T, E),
+                   "episode_steps": z(T, E, dt=torch.int32)}
+            out["done"] = out["done_u8"].view(torch.bool)
+        assert out["obs"].shape == (T + 1, E, D)
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        with torch.cuda.device(dev):
+            out["obs"][0].copy_(self._obs)
+            io = native.CStepIO(ptr(out["actions"]), ptr(out["obs"][1:]), ptr(out["reward"]), ptr(out["done_u8"]),
+                                ptr(out["outcome"]), None, ptr(out["episode_return"]), ptr(out["episode_steps"]))
+            ac = native.CActorCritic(native.CPolicy(*[ptr(t) for t in keep[:6]], 64, 0), *[ptr(t) for t in keep[6:]],
+                                     ptr(out["values"]), ptr(out["logp"]), 0, int(noise_step) & 0xFFFFFFFF, 0)
+            native.check(self._lib.acas2d_collect_set_f32(
+                C.byref(self._ccfg), C.byref(self._cstate), C.byref(io), C.byref(ac), K, ptr(keys), ptr(out["obs"][0]), T,
+                self.seed_value, self.env_offset, E, self.n_traffic, self._stream()))
+            self._obs.copy_(out["obs"][T])            # the observation the NEXT actions would be drawn on
+        out["_weights"] = keep + [keys]   # keep the transposed copies and the keys alive until the launch ran
+        return out
+
     # the per-step arrays: views of the live generation
     own_x = property(lambda self: self._gen["own_x"][self._cur if "own_x" in self._db else 0])
     own_y = property(lambda self: self._gen["own_y"][self._cur if "own_y" in self._db else 0])

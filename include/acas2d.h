@@ -271,6 +271,29 @@ int acas2d_collect_f64(const Acas2dConfig *cfg, const Acas2dState *state, const 
                        int64_t env_offset, int64_t n_envs, int32_t n_traffic, void *stream);
 
 /*
+ * acas2d_collect_set_f32: acas2d_collect_f32 for K independent actor-critics ("members": the seeds or hyper-parameter
+ * sets of a sweep) in ONE launch.  Additive to ABI 7.
+ *   ac                ONE Acas2dActorCritic whose weight pointers name K stacks, in the layouts acas2d_evaluate_policies_*
+ *                     documents for the actor: w1t float[K][D][64], b1 float[K][64], w2t float[K][64][64], b2 float[K][64],
+ *                     w3 float[K][64], b3 float[K][1]; v1t .. vb3 likewise; log_std float[K].  ac->noise_seed is ignored.
+ *   n_members         K >= 1
+ *   noise_seeds       DEVICE uint64[K]: member k's noise key.  The counter is acas2d_collect_*'s: (global env index,
+ *                     ac->noise_step + t)
+ *   n_envs            K * EM with EM a multiple of 64: member k owns the envs [k EM, (k + 1) EM), so that a wavefront's
+ *                     envs belong to one member and its weights stay scalar operands
+ *   io, values, logp  the collector's [n_steps][n_envs] layout
+ * The slice of member k equals acas2d_collect_f32 run alone on those envs -- policy k, noise_seed = noise_seeds[k],
+ * env_offset + k EM, the same env seed -- bit for bit: per step it is that launch's code.  Rejected with ACAS2D_EINVAL
+ * before anything is launched: n_members < 1, an n_envs that is not K x a multiple of 64, a NULL stack or noise_seeds,
+ * and any n_traffic outside {1, 2, 3, 4, 8}.  Out of scope: float64, and the group-cooperative launches of n_traffic
+ * 16 / 32 / 64 (acas2d_collect_group_f32 collects one learner per call).
+ */
+int acas2d_collect_set_f32(const Acas2dConfig *cfg, const Acas2dState *state, const Acas2dStepIO *io,
+                           const Acas2dActorCritic *ac, int32_t n_members, const uint64_t *noise_seeds,
+                           const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset, int64_t n_envs,
+                           int32_t n_traffic, void *stream);
+
+/*
  * acas2d_evaluate_policies_*: K deterministic policies scored on the same n_episodes episodes in ONE launch -- the
  * evaluation of testing_main.py / SB3's EvalCallback for a set of checkpoints.  Additive to ABI 7.
  *   state, n_envs     the envs; the first K * EP are used, EP = n_episodes rounded up to a multiple of 64: env
@@ -372,6 +395,40 @@ int acas2d_ppo_update_f32(const Acas2dPpoUpdate *u, void *stream);
  */
 int acas2d_ppo_update_wide_f32(const Acas2dPpoUpdate *u, void *stream);
 int acas2d_ppo_wide_lds_bytes(int32_t obs_dim);
+
+/*
+ * acas2d_ppo_update_set_f32: acas2d_ppo_update_f32 for K independent learners ("members") in TWO launches, whatever K
+ * is.  Additive to ABI 7.  Every parameter pointer names a [K][...] stack of the sibling's tensor (torch layouts);
+ * grad / adam_m / adam_v are float[K][acas2d_ppo_workspace_floats(obs_dim)], adam_step int32[K], stats float[K][8] (slots
+ * as the sibling's), all zero before the first call.  The rollout buffer is ONE flat buffer shared by all members --
+ * obs float[n_total][obs_dim], act / old_logp / adv / ret float[n_total] -- and idx int64[K][n_rows] holds member k's
+ * minibatch as rows of that buffer, so the [T][K * EM] output of acas2d_collect_set_f32 feeds the update as it lies.
+ * hyper is a DEVICE float[K][8]: clip_range, vf_coef, ent_coef, max_grad_norm, learning_rate, beta1, beta2, adam_eps of
+ * member k, read by the kernels (the caller may rewrite it between calls).  apply == 0 (tests): only the gradients are
+ * computed and left in grad[k]; nothing is applied and adam_step is untouched.
+ * The gradient launch has the grid (ceil(n_rows / 64), 2, K) and runs the sibling's arithmetic per member; the apply
+ * launch has one 1 024-thread workgroup per member.  Run-to-run: as for the sibling, the per-wave partial gradients are
+ * added to grad[k] with float atomics, whose order is not fixed, so two runs agree to float32 rounding of the sums (~1e-7
+ * relative), not bit for bit.  LDS as the sibling's (70 - 75 KB per gradient workgroup), checked against each device at
+ * its first call.  Every pointer is required, n_members in [1, 65535], n_rows >= 2, obs_dim in {8, 11, 14, 17, 29}
+ * (n_traffic 1, 2, 3, 4, 8); anything else is ACAS2D_EINVAL before a launch.  Out of scope: float64, the wide widths
+ * (acas2d_ppo_update_wide_f32 takes one learner per call), members with different n_rows.
+ */
+typedef struct Acas2dPpoUpdateSet {
+    void *actor_w1, *actor_b1, *actor_w2, *actor_b2, *actor_w3, *actor_b3;       /* [K][...] stacks */
+    void *critic_w1, *critic_b1, *critic_w2, *critic_b2, *critic_w3, *critic_b3;
+    void *log_std;                      /* float[K] */
+    const void *obs;                    /* float[n_total][obs_dim]: ONE shared flat rollout buffer */
+    const void *act, *old_logp, *adv, *ret;   /* float[n_total] */
+    const int64_t *idx;                 /* int64[K][n_rows]: member k's minibatch, rows of the shared buffer */
+    int32_t n_members, n_rows, obs_dim, apply;  /* apply == 0: raw gradients only */
+    const void *hyper;                  /* device float[K][8] */
+    void *grad, *adam_m, *adam_v;       /* float[K][acas2d_ppo_workspace_floats(obs_dim)] */
+    int32_t *adam_step;                 /* int32[K] */
+    void *stats;                        /* float[K][8] */
+} Acas2dPpoUpdateSet;
+
+int acas2d_ppo_update_set_f32(const Acas2dPpoUpdateSet *u, void *stream);
 
 /*
  * acas2d_reset_*: replaces ACAS2DEnv.reset() (environment.py:44-48 -> ACAS2DGame.__init__,

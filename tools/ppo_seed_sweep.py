@@ -5,6 +5,11 @@ on the reference's 100 test episodes (testing_main.py; the reference's own polic
 1210.07).  One JSON line per run, one summary line per set.
 
     python tools/ppo_seed_sweep.py --sets default lr1e-4 --seeds 13 14 15 --timesteps 3e7
+
+--population trains the seeds of a set as ONE population (ppo.PopulationTrainer: member k on its own --envs envs of one
+env of len(seeds) x --envs) and scores them in one launch.  Opt-in: the sequential path is the default (DESIGN.md 4.2e
+says what was measured).  Member k plays the envs at offset k x --envs, so its episodes are not the solo run's: the
+runs compare as seeds do, not bit for bit.
 """
 import argparse
 import json
@@ -41,6 +46,7 @@ ap.add_argument("--seeds", type=int, nargs="+", default=[13, 14, 15])
 ap.add_argument("--envs", type=int, default=1024)
 ap.add_argument("--timesteps", type=float, default=3.0e7)
 ap.add_argument("--out", default=None)
+ap.add_argument("--population", action="store_true", help="one PopulationTrainer per set over the seeds")
 args = ap.parse_args()
 sink = open(args.out, "a") if args.out else None
 
@@ -57,7 +63,25 @@ own, trf, goal = H.parity_reset_states(g.ACAS2DConfig(), 13, 0, 100)
 for name in args.sets:
     kw = {**dict(n_steps=256, batch_size=4096), **SETS[name]}
     goals = []
-    for seed in args.seeds:
+    if args.population:
+        t0 = time.time()
+        K = len(args.seeds)
+        venv = g.ACAS2DVecEnv(K * args.envs, 1, device="cuda:0", dtype=torch.float32, seed=13)
+        pop = g.PopulationTrainer(venv, [g.PPOConfig(seed=seed, **kw) for seed in args.seeds])
+        hist = pop.learn(int(args.timesteps), log=None)
+        out = g.evaluate_policies_fused(pop.policy_set.actor_weights(), own, trf, goal)
+        wall = time.time() - t0
+        for k, seed in enumerate(args.seeds):
+            last = [r for r in hist if r["member"] == k and not r.get("eval")][-1]
+            rec = {"set": name, "config": kw, "seed": seed, "population": K, "member": k, "timesteps": int(args.timesteps),
+                   "wall_s": wall, "train_ep_rew_mean_last": last.get("ep_rew_mean"), "std": last.get("std"),
+                   "eval_mean_return": float(out["total_reward"][k].mean()), "eval_mean_steps": float(out["steps"][k].mean()),
+                   "goal": int((out["outcome"][k] == 1).sum()), "collision": int((out["outcome"][k] == 2).sum()),
+                   "timeout": int((out["outcome"][k] == 3).sum())}
+            goals.append(rec["goal"])
+            emit(rec)
+        del pop, venv
+    for seed in ([] if args.population else args.seeds):
         t0 = time.time()
         venv = g.ACAS2DVecEnv(args.envs, 1, device="cuda:0", dtype=torch.float32, seed=13)
         tr = g.PPOTrainer(venv, g.PPOConfig(seed=seed, **kw), collector="fused", updater="fused")

@@ -28,6 +28,10 @@ ap.add_argument("--updater", choices=("graphs", "fused"), default=None,
                      "-- and 16, 32, 64 -- acas2d_ppo_update_wide_f32; tools/bench_ppo_update.py): every minibatch update as "
                      "two hand-written launches; graphs: captured torch ops")
 ap.add_argument("--seed", type=int, default=13)
+ap.add_argument("--population", type=int, default=0, metavar="K",
+                help="train K learners with the seeds --seed ... --seed + K - 1 side by side in one process "
+                     "(ppo.PopulationTrainer: one collection launch and two launches per minibatch for all K; each member gets "
+                     "--envs envs; float32, --traffic 1, 2, 3, 4, 8, fused collector and update)")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 if args.updater is None:
@@ -38,6 +42,25 @@ if args.updater is None:
         print(json.dumps({"note": "updater=graphs: the fused update is built for traffic 1, 2, 3, 4, 8, 16, 32, 64 (obs_dim 8, "
                                   "11, 14, 17, 29, 53, 101, 197), --traffic %d has obs_dim %d"
                                   % (args.traffic, 5 + 3 * args.traffic)}), flush=True)
+
+if args.population:
+    import helpers as H
+    K = args.population
+    venv = g.ACAS2DVecEnv(K * args.envs, args.traffic, device="cuda:0", dtype=torch.float32, seed=13)
+    pop = g.PopulationTrainer(venv, [g.PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, seed=args.seed + k)
+                                     for k in range(K)])
+    pop.learn(int(args.timesteps), log=lambda r: print(json.dumps(r), flush=True))
+    if args.traffic == 1:
+        own, trf, goal = H.parity_reset_states(g.ACAS2DConfig(), 13, 0, 100)
+        out = g.evaluate_policies_fused(pop.policy_set.actor_weights(), own, trf, goal)
+        for k in range(K):
+            print(json.dumps({"member": k, "seed": args.seed + k, "eval_100_reference_episodes": {
+                "mean_return": float(out["total_reward"][k].mean()), "mean_steps": float(out["steps"][k].mean()),
+                "goal": int((out["outcome"][k] == 1).sum()), "collision": int((out["outcome"][k] == 2).sum()),
+                "timeout": int((out["outcome"][k] == 3).sum())}}))
+    if args.out:
+        torch.save({n: t.cpu() for n, t in pop.policy_set.params.items()}, args.out)      # the [K, ...] stacks
+    sys.exit(0)
 
 venv = g.ACAS2DVecEnv(args.envs, args.traffic, device="cuda:0", dtype=torch.float32, seed=13)
 trainer = g.PPOTrainer(venv, g.PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, seed=args.seed), collector=args.collector,
