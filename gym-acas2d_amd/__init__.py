@@ -14,7 +14,7 @@ from .env import ACAS2DEnv, GameView, register_with_gym              # noqa: F40
 from .policy import (SB3ActorPolicy, load_sb3_policy, save_sb3_policy, evaluate_policy, evaluate_policy_fused,  # noqa: F401
                      evaluate_policies_fused)
 from .ppo import (ActorCritic, ActorCriticSet, FusedUpdate, FusedUpdateSet, PopulationTrainer, PPOConfig, PPOTrainer,  # noqa: F401
-                  compute_gae, ppo_loss)
+                  compute_gae, gae_constants, gae_fused, ppo_loss)
 
 register_with_gym()
 

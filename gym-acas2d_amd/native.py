@@ -57,13 +57,22 @@ class CPpoUpdateSet(C.Structure):
         [(n, C.c_void_p) for n in ("hyper", "grad", "adam_m", "adam_v", "adam_step", "stats")]
 
 
+class CGae(C.Structure):
+    """struct Acas2dGae: the bootstrap value and GAE over the collector's [T][E] buffers (include/acas2d.h)."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "reward", "value", "done", "last_value", "obs_last", "v1t", "vb1", "v2t", "vb2", "v3", "vb3", "gamma",
+        "gamma_lambda", "adv", "ret", "last_value_out", "nan_count")] + \
+        [("n_envs", C.c_int64)] + [(n, C.c_int32) for n in ("n_steps", "n_members", "obs_dim", "_pad")]
+
+
 EXPORTS = ("acas2d_abi_version", "acas2d_config_size", "acas2d_state_size", "acas2d_last_error", "acas2d_step_f32",
            "acas2d_step_f64", "acas2d_rollout_f32", "acas2d_rollout_f64", "acas2d_rollout_policy_f32",
            "acas2d_rollout_policy_f64", "acas2d_collect_f32", "acas2d_collect_f64", "acas2d_ppo_workspace_floats",
            "acas2d_ppo_update_f32", "acas2d_reset_f32", "acas2d_reset_f64", "acas2d_launch_geometry",
            "acas2d_state_is_consecutive", "acas2d_evaluate_policies_f32", "acas2d_evaluate_policies_f64",
            "acas2d_rollout_policy_group_f32", "acas2d_collect_group_f32", "acas2d_evaluate_policies_group_f32",
-           "acas2d_ppo_update_wide_f32", "acas2d_ppo_wide_lds_bytes", "acas2d_collect_set_f32", "acas2d_ppo_update_set_f32")
+           "acas2d_ppo_update_wide_f32", "acas2d_ppo_wide_lds_bytes", "acas2d_collect_set_f32", "acas2d_ppo_update_set_f32",
+           "acas2d_gae_f32", "acas2d_gae_size", "acas2d_gae_pipeline_depth")
 
 
 class NativeLibraryError(RuntimeError):
@@ -137,6 +146,10 @@ def lib():
                                          C.c_int32, C.c_void_p]
     L.acas2d_ppo_update_set_f32.restype = C.c_int
     L.acas2d_ppo_update_set_f32.argtypes = [C.POINTER(CPpoUpdateSet), C.c_void_p]
+    L.acas2d_gae_f32.restype = C.c_int
+    L.acas2d_gae_f32.argtypes = [C.POINTER(CGae), C.c_void_p]
+    L.acas2d_gae_size.restype = C.c_size_t
+    L.acas2d_gae_pipeline_depth.restype = C.c_int
     L.acas2d_ppo_workspace_floats.restype = C.c_int
     L.acas2d_ppo_workspace_floats.argtypes = [C.c_int32]
     for name in ("acas2d_ppo_update_f32", "acas2d_ppo_update_wide_f32"):
@@ -162,6 +175,8 @@ def lib():
                                  (L.acas2d_config_size(), C.sizeof(CConfig)))
     if L.acas2d_state_size() != C.sizeof(CState):
         raise NativeLibraryError("Acas2dState layout mismatch: %d != %d" % (L.acas2d_state_size(), C.sizeof(CState)))
+    if L.acas2d_gae_size() != C.sizeof(CGae):
+        raise NativeLibraryError("Acas2dGae layout mismatch: %d != %d" % (L.acas2d_gae_size(), C.sizeof(CGae)))
     _lib = L
     return L
 

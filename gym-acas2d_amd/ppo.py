@@ -132,6 +132,113 @@ def compute_gae(rewards, values, dones, last_value, gamma, lam):
     return adv, adv + values
 
 
+# observation widths the in-kernel bootstrap value of acas2d_gae_f32 is built for (n_traffic 1, 2, 3, 4, 8)
+GAE_BOOTSTRAP_WIDTHS = (8, 11, 14, 17, 29)
+
+
+def gae_constants(gamma, gae_lambda, n_members, device):
+    """The two float32 [K] device tensors acas2d_gae_f32 reads, in compute_gae's semantics: Python numbers give
+    float32(gamma) and float32(gamma * gae_lambda) with the product taken in double (what torch does with a Python scalar);
+    if either is a tensor ([K], or one element), both are rounded to float32 first and multiplied in float32."""
+    K = int(n_members)
+    if torch.is_tensor(gamma) or torch.is_tensor(gae_lambda):
+        g, l = (torch.as_tensor(x, dtype=torch.float32, device=device).reshape(-1) for x in (gamma, gae_lambda))
+        if g.numel() not in (1, K) or l.numel() not in (1, K):
+            raise ValueError("gamma / gae_lambda tensors need one element per member (%d), got %d / %d"
+                             % (K, g.numel(), l.numel()))
+        g, l = g.expand(K), l.expand(K)
+        return g.contiguous(), (g * l).contiguous()
+    g = torch.full((K,), float(gamma), dtype=torch.float32, device=device)
+    return g, torch.full((K,), float(gamma) * float(gae_lambda), dtype=torch.float32, device=device)
+
+
+def _critic_stacks(critic, n_members, obs_dim, device):
+    """The six value-net tensors in Acas2dActorCritic's layout: from an ActorCritic (K = 1), an ActorCriticSet, or a
+    sequence of six tensors already in that layout."""
+    if isinstance(critic, ActorCriticSet):
+        if critic.n_members != n_members or critic.obs_dim != obs_dim:
+            raise ValueError("critic: a set of %d members of obs_dim %d, needed %d of %d"
+                             % (critic.n_members, critic.obs_dim, n_members, obs_dim))
+        w = critic.collector_weights()[6:12]
+    elif isinstance(critic, nn.Module):
+        if n_members != 1:
+            raise ValueError("critic: one ActorCritic serves n_members = 1; pass an ActorCriticSet for %d" % n_members)
+        vn = critic.mlp_extractor.value_net
+        w = [vn[0].weight.detach().t(), vn[0].bias.detach(), vn[2].weight.detach().t(), vn[2].bias.detach(),
+             critic.value_net.weight.detach().reshape(-1), critic.value_net.bias.detach().reshape(-1)]
+    else:
+        w = list(critic)
+    w = [t.to(device=device, dtype=torch.float32).contiguous() for t in w]
+    want = (n_members * obs_dim * 64, n_members * 64, n_members * 64 * 64, n_members * 64, n_members * 64, n_members)
+    if len(w) != 6 or tuple(t.numel() for t in w) != want:
+        raise ValueError("critic must be the SB3 MlpPolicy value net %d -> 64 -> 64 -> 1 of %d member(s)" % (obs_dim, n_members))
+    return w
+
+
+@torch.no_grad()
+def gae_fused(rewards, values, dones, last_value=None, gamma=0.99, gae_lambda=0.95, n_members=1, critic=None,
+              obs_last=None, out=None, nan_count=None, constants=None):
+    """compute_gae() as ONE hand-written launch (acas2d_gae_f32, csrc/acas2d_gae.hip), equal to it bit for bit.
+    rewards / values [T, E] float32 and dones [T, E] bool or uint8 are the collector's buffers on the GPU; a NaN reward
+    counts as 0 and an infinite one as +-FLT_MAX (torch.nan_to_num), so the raw rewards may be passed.
+      last_value      [E] float32, or None: the kernel evaluates `critic` on obs_last [E, D] itself (a non-finite entry fed
+                      as 0; D in {8, 11, 14, 17, 29}) with the collector's arithmetic, and the value is returned as well
+      gamma, gae_lambda   Python numbers, or float32 tensors with one element per member: see gae_constants() for how
+                      each form rounds gamma x lambda (as compute_gae does); `constants` = gae_constants(...) kept by the
+                      caller saves forming them at every call
+      n_members       K: member k owns the envs [k E / K, (k + 1) E / K); for K > 1, E / K must be a multiple of 64
+      critic          an ActorCritic (K = 1), an ActorCriticSet, or the six value-net tensors in the collector's layout
+      out             optional dict of preallocated outputs: "adv", "ret" [T, E] and "last_value" [E]
+      nan_count       optional int32 [K] device tensor: the NaN rewards of member k are ADDED to nan_count[k]
+    Returns (adv, ret), or (adv, ret, last_value) when the kernel computed the bootstrap value."""
+    import ctypes as C
+    from . import native
+    if rewards.dim() != 2 or values.shape != rewards.shape or dones.shape != rewards.shape:
+        raise ValueError("gae_fused takes rewards, values and dones of one shape [T, E]")
+    T, E = rewards.shape
+    K, dev = int(n_members), rewards.device
+    if dev.type != "cuda":
+        raise ValueError("gae_fused runs on the GPU (there is no CPU path: compute_gae is the torch one)")
+    if rewards.dtype != torch.float32 or values.dtype != torch.float32 or dones.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("gae_fused takes float32 rewards / values and bool or uint8 dones")
+    if K < 1 or (K > 1 and (E % K or (E // K) % 64)):
+        raise ValueError("gae_fused needs E = K x a multiple of 64 for K > 1 members, got E = %d, K = %d" % (E, K))
+    rewards, values, dones = rewards.contiguous(), values.contiguous(), dones.contiguous()
+    out = {} if out is None else out
+    adv = out["adv"] if "adv" in out else torch.empty_like(rewards)
+    ret = out["ret"] if "ret" in out else torch.empty_like(rewards)
+    for t in (adv, ret):
+        if t.shape != rewards.shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+            raise ValueError("out['adv'] / out['ret'] must be contiguous float32 [T, E] tensors on the inputs' device")
+    g_t, gl_t = constants if constants is not None else gae_constants(gamma, gae_lambda, K, dev)
+    keep, lv_out, D = [], None, 0
+    if last_value is None:
+        if critic is None or obs_last is None:
+            raise ValueError("gae_fused needs last_value, or critic and obs_last for the in-kernel bootstrap value")
+        D = obs_last.shape[-1]
+        if D not in GAE_BOOTSTRAP_WIDTHS:
+            raise ValueError("the in-kernel bootstrap value is built for obs_dim in {8, 11, 14, 17, 29} (n_traffic 1, 2, 3, 4, "
+                             "8), got %d -- pass last_value" % D)
+        obs_last = obs_last.to(device=dev, dtype=torch.float32).contiguous()
+        if obs_last.shape != (E, D):
+            raise ValueError("obs_last must be [E, D] = [%d, %d]" % (E, D))
+        keep = _critic_stacks(critic, K, D, dev)
+        lv_out = out["last_value"] if "last_value" in out else torch.empty(E, dtype=torch.float32, device=dev)
+    else:
+        last_value = last_value.to(device=dev, dtype=torch.float32).contiguous()
+        if last_value.shape != (E,):
+            raise ValueError("last_value must be [E] = [%d]" % E)
+    if nan_count is not None and (nan_count.dtype != torch.int32 or nan_count.numel() != K or nan_count.device != dev):
+        raise ValueError("nan_count must be an int32 device tensor of %d element(s)" % K)
+    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    g = native.CGae(p(rewards), p(values), p(dones), p(last_value), p(obs_last) if last_value is None else None,
+                    *([p(t) for t in keep] if keep else [None] * 6), p(g_t), p(gl_t), p(adv), p(ret), p(lv_out), p(nan_count),
+                    E, T, K, D, 0)
+    with torch.cuda.device(dev):
+        native.check(native.lib().acas2d_gae_f32(C.byref(g), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return (adv, ret) if last_value is not None else (adv, ret, lv_out)
+
+
 LOG_SQRT_2PI = 0.5 * math.log(2.0 * math.pi)
 
 
@@ -228,9 +335,11 @@ class PPOTrainer:
     ACAS2DVecEnv.collect(group=True), and so does evaluate()) or "eager" (op by op).  updater: "graphs" (default with
     `use_graphs`: one captured minibatch update of torch ops) or "fused" (FusedUpdate: the minibatch update as two
     hand-written launches, its own Adam state; obs_dim in {8, 11, 14, 17, 29} or {53, 101, 197}, i.e. n_traffic 1, 2, 3,
-    4, 8 or 16, 32, 64)."""
+    4, 8 or 16, 32, 64).  gae: None / "torch" (compute_gae: captured with `use_graphs`) or "kernel" (gae_fused: one
+    hand-written launch on the static buffers, the bootstrap value still torch's forward, so the run is the "torch" run
+    bit for bit; with `use_graphs` and collector="fused" only)."""
 
-    def __init__(self, venv, config=None, policy=None, use_graphs=None, collector=None, updater=None):
+    def __init__(self, venv, config=None, policy=None, use_graphs=None, collector=None, updater=None, gae=None):
         self.venv = venv
         self.cfg = config or PPOConfig()
         torch.manual_seed(self.cfg.seed)
@@ -249,6 +358,14 @@ class PPOTrainer:
         if self.updater not in ("graphs", "fused") or (self.updater == "fused" and not self.use_graphs):
             raise ValueError("updater %r needs use_graphs" % (self.updater,))
         self._fused_update = None
+        self.gae = gae or "torch"
+        if self.gae not in ("torch", "kernel"):
+            raise ValueError("gae must be None, 'torch' or 'kernel', got %r" % (gae,))
+        if self.gae == "kernel" and not (self.use_graphs and self.collector == "fused"):
+            raise ValueError("gae='kernel' (gae_fused on the static rollout buffers) is supported with use_graphs and "
+                             "collector='fused' only; got use_graphs=%r, collector=%r -- use gae='torch'"
+                             % (self.use_graphs, self.collector))
+        self._gae_constants = None
         # the hand-written launches exist for the observation widths / traffic counts below: say so HERE, not at the
         # first collect() / update() of a run
         f32 = getattr(venv, "dtype", torch.float32) == torch.float32
@@ -418,7 +535,15 @@ class PPOTrainer:
                 self.t_idx.zero_()
                 for _ in range(T):
                     self._graphs[0].replay()
-            self._graphs[1].replay()
+            if self.gae == "kernel":
+                if self._gae_constants is None:
+                    self._gae_constants = gae_constants(cfg.gamma, cfg.gae_lambda, 1, self.device)
+                with torch.no_grad():
+                    _, last_value = self.policy.forward(self.obs)
+                gae_fused(self.b_rew, self.b_val, self.b_done, last_value, constants=self._gae_constants,
+                          out={"adv": self.b_adv, "ret": self.b_ret})
+            else:
+                self._graphs[1].replay()
             done = self.b_done
             if bool(done.any()):                          # the iteration's one host synchronisation
                 self.ep_returns.append(self.b_epret[done].cpu())
@@ -745,10 +870,14 @@ class PopulationTrainer:
     With per-member gamma / gae_lambda GAE takes them as per-env float32 vectors (the product gamma x lambda is then
     rounded in float32); equal values are passed as the numbers they are.
     Out of scope: float64, n_traffic 16 / 32 / 64 (the group-cooperative launches and the wide update), members with
-    different n_steps / batch_size / n_epochs, more than one GPU."""
+    different n_steps / batch_size / n_epochs, more than one GPU.
+    gae: None / "torch" (compute_gae, op by op) or "kernel" (gae_fused: one launch for all members, the same bits)."""
 
-    def __init__(self, venv, configs):
+    def __init__(self, venv, configs, gae=None):
         configs = list(configs)
+        self.gae = gae or "torch"
+        if self.gae not in ("torch", "kernel"):
+            raise ValueError("gae must be None, 'torch' or 'kernel', got %r" % (gae,))
         if not configs:
             raise ValueError("PopulationTrainer needs at least one PPOConfig")
         for f in SHARED_FIELDS:
@@ -785,6 +914,10 @@ class PopulationTrainer:
                              torch.tensor([getattr(c, f) for c in configs], dtype=torch.float32, device=self.device
                                           ).repeat_interleave(self.EM))
         self.gamma, self.gae_lambda = per_env("gamma"), per_env("gae_lambda")
+        # gae="kernel": the same two hyper-parameters per MEMBER, rounded as compute_gae rounds the per-env forms above
+        per_member = lambda f: (getattr(configs[0], f) if len({getattr(c, f) for c in configs}) == 1 else  # noqa: E731
+                                torch.tensor([getattr(c, f) for c in configs], dtype=torch.float32, device=self.device))
+        self._gae_constants = gae_constants(per_member("gamma"), per_member("gae_lambda"), K, self.device)
         self.obs = venv.reset().to(torch.float32).clone()
         self.nan_events = torch.zeros(K, dtype=torch.int64, device=self.device)
         self.num_timesteps = 0
@@ -834,9 +967,13 @@ class PopulationTrainer:
         self.b_eplen.copy_(out["episode_steps"])
         self.b_outcome.copy_(out["outcome"])
         self.last_value.copy_(self.policy_set.values(self.obs))
-        adv, ret = compute_gae(self.b_rew, self.b_val, self.b_done, self.last_value, self.gamma, self.gae_lambda)
-        self.b_adv.copy_(adv)
-        self.b_ret.copy_(ret)
+        if self.gae == "kernel":
+            gae_fused(self.b_rew, self.b_val, self.b_done, self.last_value, n_members=K, constants=self._gae_constants,
+                      out={"adv": self.b_adv, "ret": self.b_ret})
+        else:
+            adv, ret = compute_gae(self.b_rew, self.b_val, self.b_done, self.last_value, self.gamma, self.gae_lambda)
+            self.b_adv.copy_(adv)
+            self.b_ret.copy_(ret)
         done = self.b_done
         if bool(done.any()):                              # the iteration's one host synchronisation
             member_of = (torch.arange(E, device=self.device) // EM).expand(T, E)[done].cpu()

@@ -431,6 +431,60 @@ typedef struct Acas2dPpoUpdateSet {
 int acas2d_ppo_update_set_f32(const Acas2dPpoUpdateSet *u, void *stream);
 
 /*
+ * acas2d_gae_f32: what lies between acas2d_collect_* and acas2d_ppo_update_* in a PPO iteration, in ONE launch -- the
+ * critic's value of the last observation (optional) and SB3 1.1.0's RolloutBuffer.compute_returns_and_advantage (GAE)
+ * over the collector's [T][E] buffers (`PPO.learn()`, training_main.py:44-52).  Additive to ABI 7.  float32.
+ * One lane per env sweeps t = T-1 ... 0; per (t, e), every operation its own float32 rounding, in this order:
+ *     r     = reward[t][e], NaN -> 0, +inf -> FLT_MAX, -inf -> -FLT_MAX          (torch.nan_to_num(x, nan=0.0))
+ *     nt    = done[t][e] ? 0.0f : 1.0f
+ *     nv    = (t == T-1) ? last_value[e] : value[t+1][e]
+ *     delta = ((r + ((gamma_k * nv) * nt)) - value[t][e])
+ *     last  = delta + ((gl_k * nt) * last)                                       last starts at 0
+ *     adv[t][e] = last;  ret[t][e] = last + value[t][e]
+ * which is the sequence of torch operations of the Python host's compute_gae(): the outputs are equal to its bit for bit.
+ * The sweep keeps acas2d_gae_pipeline_depth() rows of loads in flight below the row it computes on.
+ *   gamma, gamma_lambda   DEVICE float[K]: member k's gamma_k and gl_k.  The CALLER forms gl_k, so both conventions exist:
+ *                         (float)(gamma * lambda) with the product taken in double (scalar hyper-parameters), or
+ *                         (float)gamma * (float)lambda rounded in float32 (float32 tensors of hyper-parameters)
+ *   n_members             K >= 1: member k owns the envs [k EM, (k + 1) EM), EM = n_envs / K -- for K > 1 a multiple of 64,
+ *                         so that a wavefront's envs belong to one member and its constants and critic stay scalar
+ *                         operands, as for acas2d_collect_set_f32; K == 1 takes any n_envs >= 1 (< 2^31)
+ *   last_value            float[E], or NULL: the kernel then evaluates the critic on obs_last float[E][obs_dim] itself, with
+ *                         the value-net stacks v1t .. vb3 in Acas2dActorCritic's layout ([K][D][64], [K][64], [K][64][64],
+ *                         [K][64], [K][64], [K][1]).  A non-finite observation entry is fed as 0, and the arithmetic is the
+ *                         collector's, so the value has the bits `values` of a collection started on that observation
+ *                         holds.  The in-kernel critic exists for obs_dim in {8, 11, 14, 17, 29} (n_traffic 1, 2, 3, 4, 8)
+ *                         only: the wide widths (53, 101, 197) must pass last_value.  obs_dim and v1t .. vb3 are ignored
+ *                         when last_value is given
+ *   last_value_out        optional float[E]: the bootstrap value used
+ *   nan_count             optional int32[K]: the number of NaN rewards of member k is ADDED to nan_count[k] (one integer
+ *                         atomic per wavefront that saw one; zero it before the call)
+ * Rejected with ACAS2D_EINVAL before any HIP call: a NULL reward, value, done, adv, ret, gamma or gamma_lambda; n_steps,
+ * n_envs or n_members < 1; K > 1 with n_envs not K x a multiple of 64; last_value and obs_last both NULL; without
+ * last_value an obs_dim outside the five or a NULL critic stack; adv or ret equal to any other buffer of the struct or to
+ * each other.
+ */
+typedef struct Acas2dGae {
+    const void *reward, *value;      /* float[n_steps][n_envs]: the collector's reward / values */
+    const uint8_t *done;             /* u8[n_steps][n_envs] */
+    const void *last_value;          /* float[n_envs] or NULL */
+    const void *obs_last;            /* float[n_envs][obs_dim]; read only when last_value is NULL */
+    const void *v1t, *vb1;           /* the critic, as Acas2dActorCritic's: read only when last_value is NULL */
+    const void *v2t, *vb2;
+    const void *v3, *vb3;
+    const void *gamma, *gamma_lambda;   /* device float[n_members] */
+    void *adv, *ret;                 /* float[n_steps][n_envs] outputs */
+    void *last_value_out;            /* float[n_envs] or NULL */
+    int32_t *nan_count;              /* int32[n_members] or NULL */
+    int64_t n_envs;
+    int32_t n_steps, n_members, obs_dim, _pad;
+} Acas2dGae;
+
+int acas2d_gae_f32(const Acas2dGae *g, void *stream);
+size_t acas2d_gae_size(void);         /* sizeof(Acas2dGae): layout check for bindings */
+int acas2d_gae_pipeline_depth(void);  /* rows of loads in flight per lane (16) */
+
+/*
  * acas2d_reset_*: replaces ACAS2DEnv.reset() (environment.py:44-48 -> ACAS2DGame.__init__,
  * game.py:28-41,80-116, then observe()).  For every env with mask[e] != 0 (mask == NULL: all):
  *   do_init != 0: draw a fresh episode from the Philox stream described above

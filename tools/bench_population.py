@@ -37,6 +37,8 @@ ap.add_argument("--batch-size", type=int, default=4096)
 ap.add_argument("--iters", type=int, default=1, help="iterations per timed window")
 ap.add_argument("--windows", type=int, default=7)
 ap.add_argument("--reps", type=int, default=7)
+ap.add_argument("--gae", choices=("torch", "kernel"), default="torch",
+                help="GAE of BOTH variants: torch's compute_gae or the one-launch kernel (ppo.gae_fused); the same bits")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 DEV = "cuda:0"
@@ -66,19 +68,19 @@ def spread(xs):
 cfg = lambda seed: g.PPOConfig(seed=seed, n_steps=args.n_steps, batch_size=args.batch_size)  # noqa: E731
 per_it = args.n_steps * args.envs                     # one member's env steps per iteration
 shape = {"envs_per_member": args.envs, "n_traffic": args.traffic, "n_steps": args.n_steps, "batch_size": args.batch_size,
-         "iters_per_window": args.iters, "windows": args.windows, "device": torch.cuda.get_device_name(0)}
+         "gae": args.gae, "iters_per_window": args.iters, "windows": args.windows, "device": torch.cuda.get_device_name(0)}
 
 # the baseline's solo trainers: the parent path, one learner each, built once and reused for every K
 solos = []
 for k in range(max(args.members)):
     venv = g.ACAS2DVecEnv(args.envs, args.traffic, device=DEV, seed=13)
-    tr = g.PPOTrainer(venv, cfg(13 + k), collector="fused", updater="fused")
+    tr = g.PPOTrainer(venv, cfg(13 + k), collector="fused", updater="fused", gae=args.gae)
     tr.learn(per_it, log=None)                        # warm-up: graph capture, first launches
     solos.append(tr)
 
 for K in args.members:
     venv = g.ACAS2DVecEnv(K * args.envs, args.traffic, device=DEV, seed=13)
-    pop = g.PopulationTrainer(venv, [cfg(13 + k) for k in range(K)])
+    pop = g.PopulationTrainer(venv, [cfg(13 + k) for k in range(K)], gae=args.gae)
     pop.learn(per_it, log=None)                       # warm-up
 
     def run_population():

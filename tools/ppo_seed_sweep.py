@@ -47,7 +47,15 @@ ap.add_argument("--envs", type=int, default=1024)
 ap.add_argument("--timesteps", type=float, default=3.0e7)
 ap.add_argument("--out", default=None)
 ap.add_argument("--population", action="store_true", help="one PopulationTrainer per set over the seeds")
+ap.add_argument("--gae", choices=("torch", "kernel"), default=None,
+                help="kernel: GAE as one hand-written launch (ppo.gae_fused), the same bits as torch's compute_gae; the default "
+                     "follows tools/bench_gae.py's measurement (DESIGN.md 4.2f): GAE_DEFAULT below")
 args = ap.parse_args()
+# "kernel" where learn() with it beat gae="torch" by more than both variants' spreads (the fused-collector
+# PPOTrainer by 2 % at 512 steps and 13 % at 128, the population by 3 %); a trainer that were not faster would say "torch"
+GAE_DEFAULT = {"population": "kernel", "solo": "kernel"}
+if args.gae is None:
+    args.gae = GAE_DEFAULT["population" if args.population else "solo"]
 sink = open(args.out, "a") if args.out else None
 
 
@@ -67,7 +75,7 @@ for name in args.sets:
         t0 = time.time()
         K = len(args.seeds)
         venv = g.ACAS2DVecEnv(K * args.envs, 1, device="cuda:0", dtype=torch.float32, seed=13)
-        pop = g.PopulationTrainer(venv, [g.PPOConfig(seed=seed, **kw) for seed in args.seeds])
+        pop = g.PopulationTrainer(venv, [g.PPOConfig(seed=seed, **kw) for seed in args.seeds], gae=args.gae)
         hist = pop.learn(int(args.timesteps), log=None)
         out = g.evaluate_policies_fused(pop.policy_set.actor_weights(), own, trf, goal)
         wall = time.time() - t0
@@ -84,7 +92,7 @@ for name in args.sets:
     for seed in ([] if args.population else args.seeds):
         t0 = time.time()
         venv = g.ACAS2DVecEnv(args.envs, 1, device="cuda:0", dtype=torch.float32, seed=13)
-        tr = g.PPOTrainer(venv, g.PPOConfig(seed=seed, **kw), collector="fused", updater="fused")
+        tr = g.PPOTrainer(venv, g.PPOConfig(seed=seed, **kw), collector="fused", updater="fused", gae=args.gae)
         hist = tr.learn(int(args.timesteps), log=None)
         out = g.evaluate_policy_fused(tr.policy, own, trf, goal)
         rec = {"set": name, "config": kw, "seed": seed, "timesteps": int(args.timesteps), "wall_s": time.time() - t0,

@@ -27,6 +27,10 @@ ap.add_argument("--updater", choices=("graphs", "fused"), default=None,
                 help="fused (default where it is built and measured faster: --traffic 1, 2, 3, 4, 8 -- acas2d_ppo_update_f32 "
                      "-- and 16, 32, 64 -- acas2d_ppo_update_wide_f32; tools/bench_ppo_update.py): every minibatch update as "
                      "two hand-written launches; graphs: captured torch ops")
+ap.add_argument("--gae", choices=("torch", "kernel"), default=None,
+                help="kernel: the GAE of an iteration as one hand-written launch (ppo.gae_fused: acas2d_gae_f32; the same bits "
+                     "as torch's compute_gae; needs --collector fused); the default follows tools/bench_gae.py's measurement "
+                     "(DESIGN.md 4.2f): GAE_DEFAULT below")
 ap.add_argument("--seed", type=int, default=13)
 ap.add_argument("--population", type=int, default=0, metavar="K",
                 help="train K learners with the seeds --seed ... --seed + K - 1 side by side in one process "
@@ -34,6 +38,11 @@ ap.add_argument("--population", type=int, default=0, metavar="K",
                      "--envs envs; float32, --traffic 1, 2, 3, 4, 8, fused collector and update)")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
+# "kernel" where learn() with it beat gae="torch" by more than both variants' spreads (the fused-collector
+# PPOTrainer by 2 % at 512 steps and 13 % at 128, the population by 3 %); a trainer that were not faster would say "torch"
+GAE_DEFAULT = {"population": "kernel", "solo": "kernel"}
+if args.gae is None:
+    args.gae = GAE_DEFAULT["population"] if args.population else (GAE_DEFAULT["solo"] if args.collector == "fused" else "torch")
 if args.updater is None:
     # fused wherever it is built: it was measured faster than the captured graph at every one of these widths
     # (a width where it were not would be left out of this tuple)
@@ -48,7 +57,7 @@ if args.population:
     K = args.population
     venv = g.ACAS2DVecEnv(K * args.envs, args.traffic, device="cuda:0", dtype=torch.float32, seed=13)
     pop = g.PopulationTrainer(venv, [g.PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, seed=args.seed + k)
-                                     for k in range(K)])
+                                     for k in range(K)], gae=args.gae)
     pop.learn(int(args.timesteps), log=lambda r: print(json.dumps(r), flush=True))
     if args.traffic == 1:
         own, trf, goal = H.parity_reset_states(g.ACAS2DConfig(), 13, 0, 100)
@@ -64,7 +73,7 @@ if args.population:
 
 venv = g.ACAS2DVecEnv(args.envs, args.traffic, device="cuda:0", dtype=torch.float32, seed=13)
 trainer = g.PPOTrainer(venv, g.PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, seed=args.seed), collector=args.collector,
-                       use_graphs=args.collector != "eager", updater=args.updater if args.collector != "eager" else "graphs")
+                       use_graphs=args.collector != "eager", updater=args.updater if args.collector != "eager" else "graphs", gae=args.gae)
 hist = trainer.learn(int(args.timesteps), log=lambda r: print(json.dumps(r), flush=True))
 
 if args.traffic == 1:
