@@ -14,7 +14,8 @@
 //                      as conflict-free rows, q ascending.  The 64 lanes of one atomic instruction then hit 64
 //                      CONSECUTIVE floats of `grad` (the narrow kernel's lanes are D floats apart).
 //   the advantage statistics of the whole minibatch are taken by the actor workgroup's 256 threads together.
-// ppo_apply_kernel (norm, clip_grad_norm_, Adam) does not depend on the width: launch_ppo_apply of acas2d_ppo.hip.
+// d loss / d output is loss_grad of acas2d_ppo.hpp, the narrow kernels' own.  ppo_apply_kernel (norm, clip_grad_norm_,
+// Adam) does not depend on the width: launch_ppo_apply of acas2d_ppo.hip.
 #include "acas2d_ppo.hpp"
 
 namespace acas2d {
@@ -34,8 +35,6 @@ __host__ __device__ constexpr int x_stride(int D) { return D | 1; }
 __host__ __device__ constexpr size_t lds_bytes(int D) {
     return 64 * sizeof(int64_t) + (size_t)(4 * 64 * kRow + 64 * x_stride(D) + 64 + 2 * kWaves) * sizeof(float);
 }
-
-struct Nets { NetW n[2]; };                 // actor, critic: a workgroup reads the one it works on (blockIdx.y)
 
 template <int D>
 __global__ __launch_bounds__(kThreads) void ppo_grad_wide_kernel(Nets nets, const float* log_std_p,
@@ -141,26 +140,9 @@ __global__ __launch_bounds__(kThreads) void ppo_grad_wide_kernel(Nets nets, cons
     float out = b3[0];                                                 // (every wave: all of them need d loss / d output)
     for (int i = 0; i < kH; ++i) out = fmaf(w3[i], l_h2[lane * kRow + i], out);
 
-    // ---- d loss / d output (SB3 PPO.train(): clipped surrogate on minibatch-normalised advantages, MSE value loss)
-    float dout = 0.0f, dls = 0.0f, pg_s = 0.0f, vf_s = 0.0f;
-    if (live) {
-        if (is_actor) {
-            const float ls = log_std_p[0], inv_var = expf(-2.0f * ls);
-            const float diff = act[s] - out;
-            const float logp = -0.5f * diff * diff * inv_var - ls - 0.9189385332046727f;
-            const float a = (adv[s] - a_mean) / (a_std + 1e-8f);
-            const float ratio = expf(logp - old_logp[s]);
-            const float surr1 = a * ratio, surr2 = a * fminf(fmaxf(ratio, 1.0f - clip_range), 1.0f + clip_range);
-            pg_s = -fminf(surr1, surr2) / (float)B;
-            const float dlogp = (surr1 <= surr2) ? -(a * ratio) / (float)B : 0.0f;     // torch.min: ties go to the first operand
-            dout = dlogp * diff * inv_var;                       // d logp / d mean
-            dls = dlogp * (diff * diff * inv_var - 1.0f);        // d logp / d log_std
-        } else {
-            const float e = out - ret[s];
-            vf_s = e * e / (float)B;
-            dout = vf_coef * 2.0f * e / (float)B;
-        }
-    }
+    float dout, dls, pg_s, vf_s;
+    loss_grad(is_actor, live, out, act + s, old_logp + s, adv + s, ret + s, a_mean, a_std, log_std_p, B, clip_range, vf_coef,
+              dout, dls, pg_s, vf_s);
     if (w == 0) l_do[lane] = dout;
 
     // ---- backward to the pre-activations: dz2 = dout w3 (1 - h2^2), dh1 = W2^T dz2, dz1 = dh1 (1 - h1^2)
@@ -244,37 +226,18 @@ __global__ __launch_bounds__(kThreads) void ppo_grad_wide_kernel(Nets nets, cons
     }
 }
 
-// The dynamic LDS (79 - 115 KB) is more than the 64 KB a HIP launch gets without asking: the attribute raises the
-// kernel's limit, and the size is checked against what the device reports (gfx950: 160 KB per workgroup).
+// The dynamic LDS is 79 - 115 KB: ensure_dynamic_lds raises the kernel's limit on the current device and checks the size.
 template <int D>
 int launch_grad_wide(const Acas2dPpoUpdate& u, hipStream_t stream) {
-    const Nets nets{{{(const float*)u.actor_w1, (const float*)u.actor_b1, (const float*)u.actor_w2, (const float*)u.actor_b2,
-                      (const float*)u.actor_w3, (const float*)u.actor_b3},
-                     {(const float*)u.critic_w1, (const float*)u.critic_b1, (const float*)u.critic_w2, (const float*)u.critic_b2,
-                      (const float*)u.critic_w3, (const float*)u.critic_b3}}};
     constexpr size_t bytes = lds_bytes(D);
-    static int lds_limit = -1;                               // per instantiation, set once
-    if (lds_limit < 0) {
-        int dev = 0, optin = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&optin, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) {
-            set_error("acas2d_ppo_update_wide: cannot query the device's LDS size"); return ACAS2D_EHIP; }
-        if ((size_t)optin >= bytes)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&ppo_grad_wide_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        (void)hipGetLastError();
-        lds_limit = optin;
-    }
-    if ((size_t)lds_limit < bytes) {
-        set_error("acas2d_ppo_update_wide: the gradient kernel needs %zu bytes of LDS per workgroup, this device offers %d "
-                  "(built for gfx950's 160 KB)", bytes, lds_limit);
-        return ACAS2D_EINVAL;
-    }
+    const int rc = ensure_dynamic_lds<&ppo_grad_wide_kernel<D>>(bytes, "acas2d_ppo_update_wide");
+    if (rc != ACAS2D_OK) return rc;
+    const Nets nets = nets_of(u);
     hipLaunchKernelGGL((ppo_grad_wide_kernel<D>), dim3((unsigned)((u.n_rows + 63) / 64), 2), dim3(kThreads), bytes, stream, nets,
                        (const float*)u.log_std, (const float*)u.obs, (const float*)u.act, (const float*)u.old_logp,
                        (const float*)u.adv, (const float*)u.ret, (const int64_t*)u.idx, u.n_rows, u.clip_range, u.vf_coef,
                        (float*)u.grad, (float*)u.stats);
-    const hipError_t err = hipGetLastError();
-    if (err != hipSuccess) { set_error("acas2d_ppo_update_wide gradient launch: %s", hipGetErrorString(err)); return ACAS2D_EHIP; }
-    return ACAS2D_OK;
+    return launched("acas2d_ppo_update_wide gradient launch");
 }
 
 }  // namespace
@@ -294,13 +257,8 @@ extern "C" int acas2d_ppo_wide_lds_bytes(int32_t obs_dim) {
 
 extern "C" int acas2d_ppo_update_wide_f32(const Acas2dPpoUpdate* u, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    if (!u) { set_error("acas2d_ppo_update_wide: NULL argument"); return ACAS2D_EINVAL; }
-    const void* need[] = {u->actor_w1, u->actor_b1, u->actor_w2, u->actor_b2, u->actor_w3, u->actor_b3, u->critic_w1, u->critic_b1,
-                          u->critic_w2, u->critic_b2, u->critic_w3, u->critic_b3, u->log_std, u->obs, u->act, u->old_logp, u->adv,
-                          u->ret, u->idx, u->grad, u->adam_m, u->adam_v, u->adam_step, u->stats};
-    for (const void* p : need) if (!p) { set_error("acas2d_ppo_update_wide: every pointer is required"); return ACAS2D_EINVAL; }
-    if (u->n_rows < 2) { set_error("acas2d_ppo_update_wide: n_rows = %d (the advantage normalisation needs 2)", u->n_rows); return ACAS2D_EINVAL; }
-    int rc;
+    int rc = check_update(u, "acas2d_ppo_update_wide", u, "");
+    if (rc != ACAS2D_OK) return rc;
     switch (u->obs_dim) {
         case 53: rc = launch_grad_wide<53>(*u, stream); break;
         case 101: rc = launch_grad_wide<101>(*u, stream); break;

@@ -266,6 +266,19 @@ def ppo_loss(policy, cfg, obs, act, old_logp, adv, ret):
 # registers; n_traffic 1, 2, 3, 4, 8) and acas2d_ppo_update_wide_f32 (four waves tile it through LDS; n_traffic 16, 32, 64)
 FUSED_UPDATE_WIDTHS = (8, 11, 14, 17, 29)
 FUSED_UPDATE_WIDE_WIDTHS = (53, 101, 197)
+# the 13 parameter tensors in FusedUpdate's order (the flat grad / moment layout of include/acas2d.h)
+PARAM_NAMES = ("mlp_extractor.policy_net.0.weight", "mlp_extractor.policy_net.0.bias",
+               "mlp_extractor.policy_net.2.weight", "mlp_extractor.policy_net.2.bias", "action_net.weight", "action_net.bias",
+               "mlp_extractor.value_net.0.weight", "mlp_extractor.value_net.0.bias",
+               "mlp_extractor.value_net.2.weight", "mlp_extractor.value_net.2.bias", "value_net.weight", "value_net.bias",
+               "log_std")
+
+
+def _flat_rollout(obs, act, old_logp, adv, ret):
+    """The five rollout buffers as the update kernels take them: obs [n, D], the others [n] (views of the storage)."""
+    bufs = [t.reshape(-1) if i else t.reshape(-1, obs.shape[-1]) for i, t in enumerate((obs, act, old_logp, adv, ret))]
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in bufs)
+    return bufs
 
 
 class FusedUpdate:
@@ -294,13 +307,9 @@ class FusedUpdate:
         n = int(self._lib.acas2d_ppo_workspace_floats(D))
         z = lambda k, dt=torch.float32: torch.zeros(k, dtype=dt, device=dev)  # noqa: E731
         self.grad, self.m, self.v, self.step_count, self.stats = z(n), z(n), z(n), z(1, torch.int32), z(8)
-        pn, vn = policy.mlp_extractor.policy_net, policy.mlp_extractor.value_net
-        self._params = [pn[0].weight, pn[0].bias, pn[2].weight, pn[2].bias, policy.action_net.weight, policy.action_net.bias,
-                        vn[0].weight, vn[0].bias, vn[2].weight, vn[2].bias, policy.value_net.weight, policy.value_net.bias,
-                        policy.log_std]
+        self._params = [policy.get_parameter(name) for name in PARAM_NAMES]
         assert all(p.dtype == torch.float32 and p.is_contiguous() and p.device == dev for p in self._params)
-        self._bufs = [t.reshape(-1) if i else t.reshape(-1, D) for i, t in enumerate((obs, act, old_logp, adv, ret))]
-        assert all(t.dtype == torch.float32 and t.is_contiguous() for t in self._bufs)
+        self._bufs = _flat_rollout(obs, act, old_logp, adv, ret)
         self.cfg, self.D, self.betas, self.adam_eps, self.device = cfg, D, (beta1, beta2), adam_eps, dev
 
     def _struct(self, idx):
@@ -325,6 +334,52 @@ class FusedUpdate:
 # traffic counts at which PPOTrainer takes the group-cooperative launches by itself (float32; at 8 the thread-per-env
 # kernel exists and is the better design: its weights are scalar operands)
 GROUP_TRAFFIC = (16, 32, 64)
+
+
+def episode_summary(returns, lengths, outcomes):
+    """recent_episodes() for one learner, from its lists of per-collection tensors (None where no episode ended)."""
+    if not returns:
+        return None
+    r, l, o = torch.cat(returns), torch.cat(lengths), torch.cat(outcomes)
+    return {"episodes": int(r.numel()), "ep_rew_mean": float(r.mean()), "ep_len_mean": float(l.float().mean()),
+            "goal": float((o == 1).float().mean()), "collision": float((o == 2).float().mean()),
+            "timeout": float((o == 3).float().mean())}
+
+
+class _Callbacks:
+    """learn()'s EvalCallback / CheckpointCallback bookkeeping for ONE learner, whose files go under `save_dir` and whose
+    ActorCritic `policy()` gives when one is saved; `head` opens every record (a population's {"member": k})."""
+
+    def __init__(self, save_dir, policy, head=()):
+        self.save_dir, self.policy, self.head = save_dir, policy, dict(head)
+        self.evals = {"timesteps": [], "results": [], "ep_lengths": []}
+        self.best = -math.inf
+
+    def evaluated(self, timesteps, ret, steps, outcome, unfinished):
+        from .policy import save_sb3_policy
+        mean = float(ret.mean())
+        new_best = mean > self.best
+        self.best = max(self.best, mean)
+        rec = {**self.head, "eval": True, "timesteps": timesteps, "mean_reward": mean, "std_reward": float(ret.std()),
+               "mean_ep_length": float((steps - 1).mean()), "goal": float((outcome == 1).mean()),
+               "collision": float((outcome == 2).mean()), "timeout": float((outcome == 3).mean()),
+               "unfinished": int(unfinished), "new_best": new_best}
+        if self.save_dir:
+            ev = self.evals
+            ev["timesteps"].append(timesteps)
+            ev["results"].append(ret.astype(np.float64))
+            ev["ep_lengths"].append(steps.astype(np.int64) - 1)
+            os.makedirs(os.path.join(self.save_dir, "results"), exist_ok=True)
+            np.savez(os.path.join(self.save_dir, "results", "evaluations.npz"),
+                     timesteps=np.asarray(ev["timesteps"], np.int64), results=np.stack(ev["results"]),
+                     ep_lengths=np.stack(ev["ep_lengths"]))
+            if new_best:
+                save_sb3_policy(self.policy(), os.path.join(self.save_dir, "best_model.zip"))
+        return rec
+
+    def checkpoint(self, timesteps):
+        from .policy import save_sb3_policy
+        save_sb3_policy(self.policy(), os.path.join(self.save_dir, "checkpoints", "model_%d_steps.zip" % timesteps))
 
 
 class PPOTrainer:
@@ -636,14 +691,10 @@ class PPOTrainer:
         return {"updater": self.updater, **self.opt.state_dict()}
 
     def recent_episodes(self, clear=True):
-        if not self.ep_returns:
-            return None
-        r, l, o = torch.cat(self.ep_returns), torch.cat(self.ep_lengths), torch.cat(self.ep_outcomes)
+        out = episode_summary(self.ep_returns, self.ep_lengths, self.ep_outcomes)
         if clear:
             self.ep_returns, self.ep_lengths, self.ep_outcomes = [], [], []
-        return {"episodes": int(r.numel()), "ep_rew_mean": float(r.mean()), "ep_len_mean": float(l.float().mean()),
-                "goal": float((o == 1).float().mean()), "collision": float((o == 2).float().mean()),
-                "timeout": float((o == 3).float().mean())}
+        return out
 
     def evaluate(self, n_episodes, rng):
         """Score the current actor deterministically on `n_episodes` fresh episodes drawn from `rng` (a `random.Random`
@@ -679,9 +730,7 @@ class PPOTrainer:
                                  "{1, 2, 3, 4} (float64), or the group-cooperative float32 launch: n_traffic in "
                                  "{16, 32, 64}; got %d" % self.venv.n_traffic)
             eval_rng = random.Random(self.cfg.seed if eval_seed is None else eval_seed)
-        from .policy import save_sb3_policy
-        evals = {"timesteps": [], "results": [], "ep_lengths": []}
-        best = -math.inf
+        book = _Callbacks(save_dir, lambda: self.policy)
         t0 = time.time()
         it = 0
         history = []
@@ -700,39 +749,16 @@ class PPOTrainer:
             crossed = lambda every: bool(every) and before // every < self.num_timesteps // every  # noqa: E731
             if crossed(eval_every):
                 out = self.evaluate(eval_episodes, eval_rng)
-                mean = float(out["total_reward"].mean())
-                new_best = mean > best
-                best = max(best, mean)
-                erec = {"eval": True, "timesteps": self.num_timesteps, "mean_reward": mean,
-                        "std_reward": float(out["total_reward"].std()), "mean_ep_length": float((out["steps"] - 1).mean()),
-                        "goal": float((out["outcome"] == 1).mean()), "collision": float((out["outcome"] == 2).mean()),
-                        "timeout": float((out["outcome"] == 3).mean()), "unfinished": out["unfinished"],
-                        "new_best": new_best}
-                if save_dir:
-                    evals["timesteps"].append(self.num_timesteps)
-                    evals["results"].append(out["total_reward"].astype(np.float64))
-                    evals["ep_lengths"].append(out["steps"].astype(np.int64) - 1)
-                    os.makedirs(os.path.join(save_dir, "results"), exist_ok=True)
-                    np.savez(os.path.join(save_dir, "results", "evaluations.npz"),
-                             timesteps=np.asarray(evals["timesteps"], np.int64),
-                             results=np.stack(evals["results"]), ep_lengths=np.stack(evals["ep_lengths"]))
-                    if new_best:
-                        save_sb3_policy(self.policy, os.path.join(save_dir, "best_model.zip"))
+                erec = book.evaluated(self.num_timesteps, out["total_reward"], out["steps"], out["outcome"], out["unfinished"])
                 history.append(erec)
                 if log:
                     log(erec)
             if crossed(checkpoint_every):
-                save_sb3_policy(self.policy, os.path.join(save_dir, "checkpoints", "model_%d_steps.zip" % self.num_timesteps))
+                book.checkpoint(self.num_timesteps)
         return history
 
 
 # ---- K learners at once: the seeds or hyper-parameter sets of a sweep as ONE population ---------------------------------
-# the 13 parameter tensors in FusedUpdate's order (the flat grad / moment layout of include/acas2d.h)
-PARAM_NAMES = ("mlp_extractor.policy_net.0.weight", "mlp_extractor.policy_net.0.bias",
-               "mlp_extractor.policy_net.2.weight", "mlp_extractor.policy_net.2.bias", "action_net.weight", "action_net.bias",
-               "mlp_extractor.value_net.0.weight", "mlp_extractor.value_net.0.bias",
-               "mlp_extractor.value_net.2.weight", "mlp_extractor.value_net.2.bias", "value_net.weight", "value_net.bias",
-               "log_std")
 # what may differ between the members of a population, and what the shared launches need equal
 MEMBER_FIELDS = ("seed", "learning_rate", "clip_range", "ent_coef", "vf_coef", "max_grad_norm", "gamma", "gae_lambda")
 SHARED_FIELDS = ("n_steps", "batch_size", "n_epochs")
@@ -837,8 +863,7 @@ class FusedUpdateSet:
                                     adam_eps] for c in configs], dtype=torch.float32).to(dev)
         self._params = [policy_set.params[name] for name in PARAM_NAMES]
         assert all(p.dtype == torch.float32 and p.is_contiguous() and p.device == dev for p in self._params)
-        self._bufs = [t.reshape(-1) if i else t.reshape(-1, D) for i, t in enumerate((obs, act, old_logp, adv, ret))]
-        assert all(t.dtype == torch.float32 and t.is_contiguous() for t in self._bufs)
+        self._bufs = _flat_rollout(obs, act, old_logp, adv, ret)
         self.policy_set, self.D, self.K, self.device = policy_set, D, K, dev
 
     def step(self, idx, apply=True):
@@ -1015,17 +1040,9 @@ class PopulationTrainer:
 
     def recent_episodes(self, clear=True):
         """One PPOTrainer.recent_episodes() dict per member (None where no episode ended)."""
-        out = []
-        for k in range(self.K):
-            if not self.ep_returns[k]:
-                out.append(None)
-                continue
-            r, l, o = torch.cat(self.ep_returns[k]), torch.cat(self.ep_lengths[k]), torch.cat(self.ep_outcomes[k])
-            out.append({"episodes": int(r.numel()), "ep_rew_mean": float(r.mean()), "ep_len_mean": float(l.float().mean()),
-                        "goal": float((o == 1).float().mean()), "collision": float((o == 2).float().mean()),
-                        "timeout": float((o == 3).float().mean())})
-            if clear:
-                self.ep_returns[k], self.ep_lengths[k], self.ep_outcomes[k] = [], [], []
+        out = [episode_summary(self.ep_returns[k], self.ep_lengths[k], self.ep_outcomes[k]) for k in range(self.K)]
+        if clear:
+            self.ep_returns, self.ep_lengths, self.ep_outcomes = ([[] for _ in range(self.K)] for _ in range(3))
         return out
 
     def evaluate(self, n_episodes, rng):
@@ -1046,12 +1063,10 @@ class PopulationTrainer:
         under save_dir: results/evaluations.npz, best_model.zip (per member: its own best), checkpoints/."""
         if checkpoint_every and not save_dir:
             raise ValueError("checkpoint_every needs save_dir")
-        from .policy import save_sb3_policy
         K = self.K
         eval_rng = random.Random(self.configs[0].seed if eval_seed is None else eval_seed) if eval_every else None
-        evals = [{"timesteps": [], "results": [], "ep_lengths": []} for _ in range(K)]
-        best = [-math.inf] * K
-        mdir = lambda k: os.path.join(save_dir, "member_%d" % k)  # noqa: E731
+        books = [_Callbacks(save_dir and os.path.join(save_dir, "member_%d" % k), lambda k=k: self.member(k), {"member": k})
+                 for k in range(K)]
         t0 = time.time()
         it = 0
         history = self.history
@@ -1073,30 +1088,12 @@ class PopulationTrainer:
             if crossed(eval_every):
                 out = self.evaluate(eval_episodes, eval_rng)
                 for k in range(K):
-                    ret, steps, oc = out["total_reward"][k], out["steps"][k], out["outcome"][k]
-                    mean = float(ret.mean())
-                    new_best = mean > best[k]
-                    best[k] = max(best[k], mean)
-                    erec = {"member": k, "eval": True, "timesteps": self.num_timesteps, "mean_reward": mean,
-                            "std_reward": float(ret.std()), "mean_ep_length": float((steps - 1).mean()),
-                            "goal": float((oc == 1).mean()), "collision": float((oc == 2).mean()),
-                            "timeout": float((oc == 3).mean()), "unfinished": int(out["unfinished"][k]), "new_best": new_best}
-                    if save_dir:
-                        ev = evals[k]
-                        ev["timesteps"].append(self.num_timesteps)
-                        ev["results"].append(ret.astype(np.float64))
-                        ev["ep_lengths"].append(steps.astype(np.int64) - 1)
-                        os.makedirs(os.path.join(mdir(k), "results"), exist_ok=True)
-                        np.savez(os.path.join(mdir(k), "results", "evaluations.npz"),
-                                 timesteps=np.asarray(ev["timesteps"], np.int64), results=np.stack(ev["results"]),
-                                 ep_lengths=np.stack(ev["ep_lengths"]))
-                        if new_best:
-                            save_sb3_policy(self.member(k), os.path.join(mdir(k), "best_model.zip"))
+                    erec = books[k].evaluated(self.num_timesteps, out["total_reward"][k], out["steps"][k], out["outcome"][k],
+                                              out["unfinished"][k])
                     history.append(erec)
                     if log:
                         log(erec)
             if crossed(checkpoint_every):
                 for k in range(K):
-                    save_sb3_policy(self.member(k),
-                                    os.path.join(mdir(k), "checkpoints", "model_%d_steps.zip" % self.num_timesteps))
+                    books[k].checkpoint(self.num_timesteps)
         return history

@@ -356,7 +356,7 @@ int acas2d_evaluate_policies_group_f32(const Acas2dConfig *cfg, const Acas2dStat
  * Run-to-run: the per-wave partial gradients are added to `grad` with float atomics, whose order is not fixed, so two
  * runs of the same update agree to float32 rounding of the sums (~1e-7 relative), not bit for bit -- unlike the env
  * kernels, which are bitwise deterministic.  The gradient kernel uses 70 - 75 KB of LDS per workgroup (gfx950 has 160 KB;
- * checked against the device at the first call, ACAS2D_EINVAL where it does not fit).
+ * checked against each device at its first call, ACAS2D_EINVAL where it does not fit).
  */
 typedef struct Acas2dPpoUpdate {
     void *actor_w1, *actor_b1, *actor_w2, *actor_b2, *actor_w3, *actor_b3;       /* mlp_extractor.policy_net.{0,2}, action_net */
@@ -390,7 +390,7 @@ int acas2d_ppo_update_f32(const Acas2dPpoUpdate *u, void *stream);
  * sibling's.  Run-to-run: as for the sibling, the per-workgroup partial gradients are added to `grad` with float
  * atomics, whose order is not fixed, so two runs of the same update agree to float32 rounding of the sums (~1e-7
  * relative), not bit for bit.  The gradient kernel asks for acas2d_ppo_wide_lds_bytes(obs_dim) bytes of LDS per workgroup
- * (79 / 91 / 115 KB; gfx950 has 160 KB), checked against the device at the first call (ACAS2D_EINVAL where it does not
+ * (79 / 91 / 115 KB; gfx950 has 160 KB), checked against each device at its first call (ACAS2D_EINVAL where it does not
  * fit).  acas2d_ppo_wide_lds_bytes answers ACAS2D_EINVAL for an obs_dim outside the three.
  */
 int acas2d_ppo_update_wide_f32(const Acas2dPpoUpdate *u, void *stream);

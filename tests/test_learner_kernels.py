@@ -213,6 +213,37 @@ def test_fused_update_applied_steps_vs_float64(g, D, B):
           % (D, B, worst["param"], worst["m"], TAU_M, worst["v"], TAU_V, worst["norm"], worst["pg"], worst["vf"]))
 
 
+@pytest.mark.gpu
+def test_narrow_and_wide_update_on_a_second_device(g):
+    """The gradient kernels use more LDS than a launch gets without asking, and the attribute that raises the limit
+    belongs to a (kernel, device) pair: one process runs a raw-gradient call at D = 8 and at D = 53 (B = 64) on device 0
+    and then the same on device 1.  Every call returns ACAS2D_OK (FusedUpdate.step raises otherwise) and meets the
+    float64 reference with the criterion of test_fused_update_raw_gradient_per_tensor_vs_float64."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two devices")
+    B = 64
+    for dev in ("cuda:0", "cuda:1"):
+        for D in (8, 53):
+            n = 2 * B + 17
+            bt = _Batch(g, D, n, seed=1000 + 7 * D + B)
+            cfg = g.PPOConfig(ent_coef=0.01, max_grad_norm=-1.0, clip_range=0.2)
+            bt.set_old_logp("mixed", cfg.clip_range)
+            idx = torch.randperm(n, device=DEV)[:B].contiguous()
+            theta = R.flat_params(bt.pol)
+            host = bt.host(idx)
+            with torch.cuda.device(dev):
+                fu = g.FusedUpdate(bt.pol.to(dev), cfg, *(t.to(dev) for t in (bt.obs, bt.act, bt.old_logp, bt.adv, bt.ret)))
+                assert fu.grad.device == torch.device(dev)
+                fu.step(idx.to(dev))
+                torch.cuda.synchronize()
+            got = fu.grad.double().cpu().numpy()
+            got[-1] -= cfg.ent_coef
+            ref, pg, vf, _ = R.grad64(bt.ac_cls, cfg, D, theta, *host)
+            _assert_per_tensor("raw gradient D=%d B=%d on %s" % (D, B, dev), got, ref, R.segments(bt.pol), TAU)
+            st = fu.stats.double().cpu().numpy()
+            assert abs(st[0] - pg) <= 1e-5 * max(1.0, abs(pg)) and abs(st[1] - vf) <= 1e-5 * max(1.0, vf)
+
+
 # ---- acas2d_collect_* -------------------------------------------------------------------------------------------------
 def _actor_critic(g, D, seed=1):
     torch.manual_seed(seed)

@@ -5,8 +5,9 @@
        member round trip and the population's config rules.
   GPU  a set collection equals K solo collections bit for bit; raw gradients and applied steps per member against the
        float64 references of tests/learner_ref.py, with the criteria and bounds of tests/test_learner_kernels.py (the set
-       kernels run the same chains per member, so the same bounds apply); the trainer's first iteration against K solo
-       PPOTrainer runs; a few iterations with the callbacks.
+       kernels run the solo kernels' body per member, so the same bounds apply), and against the solo update bit for bit
+       where there is one wave per network; the trainer's first iteration against K solo PPOTrainer runs; a few iterations
+       with the callbacks.
 Every criterion prints what it observed."""
 import ctypes as C
 import os
@@ -480,6 +481,71 @@ def test_update_set_applied_steps_per_member_vs_float64(gpu, D, B):
     print("applied steps D=%d B=%d: worst param excess %.2e lr (bound 1e-2), m tau %.2e (bound %.0e), v tau %.2e (bound "
           "%.0e), norm / pg / vf at %.2f / %.2f / %.2f of their 1e-5 bounds"
           % (D, B, worst["param"], worst["m"], TAU_M, worst["v"], TAU_V, worst["norm"], worst["pg"], worst["vf"]))
+
+
+BITWISE_CASES = [(D, B) for D in R.UPDATE_WIDTHS for B in (2, 63, 64)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("D,B", BITWISE_CASES, ids=["D%d-B%d" % c for c in BITWISE_CASES])
+def test_update_set_single_wave_equals_solo_bitwise(gpu, D, B):
+    """The set kernels and the solo kernels run ONE body (csrc/acas2d_ppo.hpp: grad_narrow, apply_body), so where the
+    result does not depend on the order of the atomics it is the same bits: with B <= 64 there is one wave per network,
+    every gradient entry receives exactly one atomic add onto zero, and the apply kernel's reduction order is fixed.
+    K = 3 members with different weights, minibatches and hyper-rows (and Adam step counts) on one shared buffer, through
+    FusedUpdateSet; the same member by member through FusedUpdate on the same buffer.  First the raw gradient (apply=False
+    against the solo probe max_grad_norm < 0), then three applied steps, compared after each: grad, the 13 parameters, m,
+    v, step_count, stats[2] / [4] / [5] with torch.equal.  B = 2 and 63 leave dead lanes, B = 64 fills the wave."""
+    g = gpu
+    K = 3
+    hyper = dict(clip_range=(0.1, 0.2, 0.3), vf_coef=(0.5, 0.25, 1.0), ent_coef=(0.01, 0.0, 0.02),
+                 max_grad_norm=(0.5, 1e6, 0.3), learning_rate=(3e-4, 1e-3, 1e-4))
+    cfgs = [g.PPOConfig(**{f: v[k] for f, v in hyper.items()}) for k in range(K)]
+    probes = [g.PPOConfig(**{**{f: v[k] for f, v in hyper.items()}, "max_grad_norm": -1.0}) for k in range(K)]
+    n = K * B + 317
+    bt = _SharedBatch(g, D, K, n, seed=5000 + 7 * D + B)
+    idx = torch.randperm(n, device=DEV)[:K * B].reshape(K, B).contiguous()           # disjoint rows
+    for k in range(K):
+        bt.set_old_logp(k, idx[k], "mixed", hyper["clip_range"][k])
+    solo = [bt.pset.member(k) for k in range(K)]                                     # copies, before anything is applied
+    bufs = (bt.obs, bt.act, bt.old_logp, bt.adv, bt.ret)
+
+    def same(what, a, b):
+        assert a.shape == b.shape and torch.equal(a, b), (what, D, B, float((a.double() - b.double()).abs().max()))
+
+    fs = g.FusedUpdateSet(bt.pset, cfgs, *bufs)
+    fs.step(idx, apply=False)
+    for k in range(K):
+        fu = g.FusedUpdate(solo[k], probes[k], *bufs)
+        fu.step(idx[k].contiguous())
+        assert float(fu.grad.abs().max()) > 0.0
+        same("raw gradient, member %d" % k, fs.grad[k], fu.grad)
+        same("raw losses, member %d" % k, fs.stats[k, 0:2], fu.stats[0:2])
+
+    fs = g.FusedUpdateSet(bt.pset, cfgs, *bufs)
+    fus = [g.FusedUpdate(solo[k], cfgs[k], *bufs) for k in range(K)]
+    starts = (0, 5, 9999)
+    fs.step_count.copy_(torch.tensor(starts, dtype=torch.int32))
+    for k in range(K):
+        fus[k].step_count.fill_(starts[k])
+    for step in range(3):
+        rows = idx[:, torch.randperm(B, device=DEV)].contiguous()                   # the same rows on other lanes
+        fs.step(rows)
+        for k in range(K):
+            fus[k].step(rows[k].contiguous())
+            what = "member %d, applied step %d: " % (k, step + 1)
+            same(what + "grad", fs.grad[k], fus[k].grad)
+            for name in R.PARAM_NAMES:
+                same(what + name, bt.pset.params[name][k], solo[k].get_parameter(name).detach())
+            same(what + "m", fs.m[k], fus[k].m)
+            same(what + "v", fs.v[k], fus[k].v)
+            same(what + "step_count", fs.step_count[k:k + 1], fus[k].step_count)
+            for slot in (2, 4, 5):
+                same(what + "stats[%d]" % slot, fs.stats[k, slot], fus[k].stats[slot])
+    assert fs.step_count.cpu().tolist() == [s + 3 for s in starts]
+    moved = max(float((bt.pset.params[R.PARAM_NAMES[2]][k] - bt.pols[k].get_parameter(R.PARAM_NAMES[2]).detach()).abs().max())
+                for k in range(K))
+    assert moved > 0.0                                                               # the steps were taken
 
 
 # ---- GPU: the trainer --------------------------------------------------------------------------------------------------
