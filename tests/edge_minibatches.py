@@ -1,0 +1,330 @@
+"""Hand-placed edge minibatches for the PPO update kernels (acas2d_ppo_update_f32, acas2d_ppo_update_wide_f32,
+acas2d_ppo_update_set_f32): the cases of tests/test_learner_edges.py, admitted on the CPU by tests/test_edge_minibatches.py.
+No GPU is needed here: everything is NumPy and CPU torch.
+
+make(D, B, case, seed, K=1, clips=(0.2,)) returns an EdgeBatch: float32 rollout buffers obs [n, D], act, old_logp, adv,
+ret [n] with n = K B + 317 > K B, an int64 idx [K, B] of rows into them (member k's minibatch; the members' rows are
+disjoint), K float32 ActorCritic(D) on the CPU with the head x 40 (test_learner_kernels._Batch), and `labels`: the
+measured quantities that make the case the case it claims to be, taken on the minibatch rows (check_labels asserts
+them).  old_logp is _Batch.set_old_logp's "mixed" mode from the case's own policy on every row of the member's pool:
+float64 log-prob + N(0, 0.5) noise (cut at 5 sigma = 2.5: no row has logp - old_logp > 3; float32 expf overflow of the
+ratio is not a case), ratios within 1e-4 of a clip edge moved off it.
+
+CASES:
+  saturated    the hidden weight matrices of both networks scaled so that max |z1| and max |z2| over the minibatch are
+               22 (inside [15, 30]): a share of the float32 activations is exactly +-1 (1 - h * h == 0) and a share has
+               |z| in [2, 6], where 1 - h * h cancels.  One factor PER MATRIX: a single common factor cannot place both
+               layers in [15, 30] at D = 8, where SB3's initialisation gives max |z1| ~ 1.3 but max |z2| ~ 6 once the
+               first layer saturates (test_edge_minibatches.test_one_common_factor_cannot_place_both_layers).
+  wide_obs     observation values of magnitude 10 to 30 in columns 0, D - 1 and, where they exist, 63, 64, 127, 128, 191,
+               192 (the borders of the wide kernel's 64-column dW1 tiles; D - 1 is in the tail of D % 4, D - 1 - D % 4
+               ends the last whole chunk), every loud column at its own scale; the rest in [-1, 1].
+  grid_adv     adv = c + k q on the minibatch rows, integer |k| <= 32, sum k = 0, c and q powers of two with
+               B (c + 32 q) / q < 2^24 and B 32^2 < 2^24: every partial sum of adv and of (adv - mean)^2 is exact in
+               float32 in ANY order, so mean and Bessel-corrected std are the same bits however the kernel sums.  c = 128
+               (64 above B = 4 096); q is the largest power of two <= 1 / 8 at which a float32 one-pass variance
+               (sum x^2 - (sum x)^2 / B, accumulated in order) is more than 2e-3 off on this very data -- at q = 1 / 8
+               and B < 8 even sum x^2 is exact, so small minibatches get a finer grid.
+  const_adv    every advantage 0.5: std == 0, a = 0 / 1e-8 = 0, the actor's gradient is exactly the entropy term.
+  log_std-2.5, log_std+1.0   log_std at -2.5 and +1.0, actions within 4 sigma of the case's own mean.
+  dup_rows     idx drawn with replacement: it contains row 0 and row n - 1 and, from B = 65, one row repeated in 64
+               consecutive wave-aligned positions (a whole wave on one sample; at B = 65 that row is n - 1, and the one
+               other row's advantage is -64 x the run's: the minibatch mean is an exact 0).
+  underflow    max(2, B // 10) rows (1 at B < 4) have logp - old_logp = -110: the ratio is 0 in float32, 1e-48 in
+               float64; they carry both signs of the normalised advantage.  The other rows are "mixed".
+"mixed" is _Batch's own minibatch (the large-B tests use it beside grid_adv)."""
+import numpy as np
+import torch
+
+import learner_ref as R
+
+CASES = ("saturated", "wide_obs", "grid_adv", "const_adv", "log_std-2.5", "log_std+1.0", "dup_rows", "underflow")
+Z_TARGET, Z_RANGE = 22.0, (15.0, 30.0)
+TILE_BORDERS = (63, 64, 127, 128, 191, 192)
+GRID_KMAX = 32
+UNDERFLOW_SHIFT = 110.0
+ONE_PASS_MIN = 1e-3                  # the label's requirement; the grid is chosen with 2x room
+# the three-member batches of the set update: each member its own policy, clip_range and vf_coef
+# (test_update_set_raw_gradients_per_member_vs_float64)
+SET_LAYOUT = dict(K=3, clips=(0.1, 0.2, 0.3))
+VF_COEFS = (0.5, 0.25, 1.0)
+
+
+def seed_of(D, B, case):
+    """The seed of the batch that tests/test_learner_edges.py runs and tests/test_edge_minibatches.py admits."""
+    return 7000 + 7 * D + B + 1000 * (CASES + ("mixed",)).index(case)
+
+
+class EdgeBatch:
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def theta(self, k=0):
+        return R.flat_params(self.pols[k])
+
+    def rows(self, k=0):
+        """The float64 minibatch of member k: obs, act, old_logp, adv, ret on idx[k]."""
+        i = self.idx[k]
+        return [a.astype(np.float64)[i] for a in (self.obs, self.act, self.old_logp, self.adv, self.ret)]
+
+
+def _policy(ac_cls, D, seed, log_std):
+    torch.manual_seed(seed)
+    pol = ac_cls(D)
+    with torch.no_grad():
+        pol.action_net.weight.mul_(40.0)        # away from SB3's near-zero init: ratios spread, some clip
+        pol.log_std.fill_(log_std)
+    return pol
+
+
+def loud_columns(D):
+    return [c for c in sorted({0, D - 1} | set(TILE_BORDERS)) if c < D]
+
+
+def loud_scales(D):
+    """One scale per loud column, 30 down to 40 / 3: with the U(0.75, 1) factor the magnitudes stay within [10, 30]."""
+    cols = loud_columns(D)
+    return np.linspace(30.0, 40.0 / 3.0, len(cols))
+
+
+def hidden_stats(pol, x):
+    """max |z1|, max |z2|, the share of float32 activations that are exactly +-1 and the share with |z| in [2, 6], over
+    both networks and both hidden layers on the float32-rounded rows x."""
+    p, x = R.params64(pol), R.obs32(x)
+    zs = [z for net in ("policy", "value") for z in R.preactivations64(p, x, net)]
+    z = np.abs(np.concatenate([a.reshape(-1) for a in zs]))
+    h = np.tanh(z).astype(np.float32)
+    return {"z1_max": [float(np.abs(zs[0]).max()), float(np.abs(zs[2]).max())],
+            "z2_max": [float(np.abs(zs[1]).max()), float(np.abs(zs[3]).max())],
+            "share_exactly_one": float((h == 1.0).mean()), "share_cancelling": float(((z >= 2) & (z <= 6)).mean())}
+
+
+def scale_hidden(pol, x, target=Z_TARGET):
+    """Scale each hidden weight matrix of both networks so that max |z| of its layer on the rows x is `target`."""
+    x = R.obs32(x)
+    with torch.no_grad():
+        for net, mod in (("policy", pol.mlp_extractor.policy_net), ("value", pol.mlp_extractor.value_net)):
+            for layer, lin in ((0, mod[0]), (1, mod[2])):
+                z = R.preactivations64(R.params64(pol), x, net)[layer]
+                lin.weight.mul_(float(target / np.abs(z).max()))
+
+
+def one_pass_variance_error(x):
+    """Relative error of the float32 one-pass Bessel-corrected variance (sum x^2 - (sum x)^2 / B) / (B - 1), both sums
+    accumulated in index order, against float64."""
+    x = np.asarray(x, np.float32)
+    B = np.float32(len(x))
+    s1 = np.add.accumulate(x, dtype=np.float32)[-1]
+    s2 = np.add.accumulate(x * x, dtype=np.float32)[-1]
+    one = (s2 - s1 * s1 / B) / np.float32(len(x) - 1)
+    ref = x.astype(np.float64).var(ddof=1)
+    return float(abs(float(one) - ref) / ref)
+
+
+def grid_advantages(B, rng):
+    """(adv [B] float32, c, q, k) of the grid_adv case."""
+    j = rng.integers(1, GRID_KMAX + 1, B // 2)
+    k = np.concatenate([j, -j, np.zeros(B % 2, np.int64)])
+    k = k[rng.permutation(B)]
+    c = 128.0 if B <= 4096 else 64.0
+    q = 0.125
+    while q >= 2.0 ** -20:
+        adv = (c + k * q).astype(np.float32)
+        if B * (c + GRID_KMAX * q) / q < 2 ** 24 and one_pass_variance_error(adv) > 2 * ONE_PASS_MIN:
+            return adv, c, q, k
+        q /= 2
+    raise AssertionError(("no exact grid exposes a one-pass variance", B, k))
+
+
+def dup_idx(B, pool, first, last, rng):
+    """B draws with replacement from `pool` that contain `first` and `last` (row 0 and row n - 1 of the buffer where the
+    pool holds them) and, from B = 65, one row in 64 consecutive positions that start at a multiple of 64."""
+    if B < 65:
+        idx = rng.choice(pool[:max(2, B // 2)], B)            # a small pool: duplicates are certain from B = 4
+        idx[0], idx[-1] = first, last
+        return idx, None
+    idx = rng.choice(pool, B)
+    start = 64 * int(rng.integers(0, (B - 65) // 64 + 1))
+    free = [i for i in range(B) if not start <= i < start + 64]
+    run = last if len(free) < 2 else int(rng.choice(pool))
+    idx[start:start + 64] = run
+    idx[free[0]] = first
+    if len(free) >= 2:
+        idx[free[-1]] = last
+    return idx, start
+
+
+def mixed_old_logp(ac_cls, D, theta, obs, act, clip, rng):
+    """_Batch.set_old_logp("mixed") for the rows given: float32 old log-probs, and how many were moved off a clip edge."""
+    lp = R.logp64(ac_cls, D, theta, obs, act)
+    old = (lp + np.clip(rng.normal(0, 0.5, len(lp)), -2.5, 2.5)).astype(np.float32).astype(np.float64)
+    return nudge_off_edges(lp, old, clip)
+
+
+def nudge_off_edges(lp, old, clip):
+    r = np.exp(lp - old)
+    edge = (np.abs(r - (1 - clip)) < 1e-4) | (np.abs(r - (1 + clip)) < 1e-4)
+    old = old.copy()
+    old[edge] -= 1e-3
+    return old.astype(np.float32), int(edge.sum())
+
+
+def make(D, B, case, seed, K=1, clips=(0.2,), ac_cls=None):
+    assert case in CASES + ("mixed",) and len(clips) == K
+    if ac_cls is None:
+        from gym_acas2d_amd import ActorCritic as ac_cls
+    rng = np.random.default_rng(seed)
+    n = K * B + 317
+    f32 = lambda a: np.ascontiguousarray(np.asarray(a, np.float32))  # noqa: E731
+    obs = f32(rng.uniform(-1, 1, (n, D)))
+    act = f32(rng.normal(0, 0.7, n))
+    adv, ret = f32(rng.normal(0, 2, n)), f32(rng.normal(2, 3, n))
+    old_logp = np.zeros(n, np.float32)
+    labels = {}
+
+    # ---- disjoint row pools, one per member; row 0 lies in the first and row n - 1 in the last
+    perm = rng.permutation(np.arange(1, n - 1))
+    cut = [len(perm) * k // K for k in range(K + 1)]
+    pools = [perm[cut[k]:cut[k + 1]] for k in range(K)]
+    pools[0] = np.concatenate([[0], pools[0]])
+    pools[-1] = np.concatenate([pools[-1], [n - 1]])
+    idx = np.stack([p[:B] for p in pools]).astype(np.int64)
+    if case == "dup_rows":
+        runs = []
+        for k in range(K):
+            idx[k], start = dup_idx(B, pools[k], pools[k][0], pools[k][-1], rng)
+            runs.append(start)
+            if B == 65:
+                # 64 of the 65 rows are one sample: adv - mean of that sample is a cancellation amplified 65 times, which
+                # float32 torch itself does not clear (admission measured tau 6e-6 at D = 29).  The one other row
+                # balances the run exactly, so the mean is an exact 0 and nothing cancels.
+                a_run = float(np.round(adv[pools[k][-1]] * 8) / 8) or 0.125
+                adv[pools[k][-1]], adv[pools[k][0]] = a_run, -64.0 * a_run
+        labels.update(distinct_rows=[int(len(np.unique(r))) for r in idx], run_start=runs,
+                      has_row_0=bool((idx == 0).any()), has_row_last=bool((idx == n - 1).any()),
+                      longest_run=[int(max(np.diff(np.flatnonzero(np.concatenate(([True], r[1:] != r[:-1], [True]))))))
+                                   for r in idx])
+
+    # ---- observations and advantages
+    if case == "wide_obs":
+        cols, scales = loud_columns(D), loud_scales(D)
+        for c, s in zip(cols, scales):
+            obs[:, c] = f32(rng.choice([-1.0, 1.0], n) * rng.uniform(0.75, 1.0, n) * s)
+    if case == "grid_adv":
+        grids = []
+        for k in range(K):
+            a, c, q, kk = grid_advantages(B, rng)
+            adv[idx[k]] = a
+            grids.append((c, q, kk))
+    if case == "const_adv":
+        adv[:] = 0.5
+
+    # ---- the policies
+    log_std = {"log_std-2.5": -2.5, "log_std+1.0": 1.0}.get(case)
+    pols = []
+    for k in range(K):
+        pol = _policy(ac_cls, D, seed + 17 * k, (-0.7 + 0.2 * k) if log_std is None else log_std)
+        if case == "saturated":
+            scale_hidden(pol, obs[idx[k]])
+        pols.append(pol)
+    if log_std is not None:                                  # actions within 4 sigma of the member's own mean
+        for k in range(K):
+            mean, _ = R.forward64(R.params64(pols[k]), obs[pools[k]])
+            act[pools[k]] = f32(mean + np.exp(log_std) * np.clip(rng.normal(0, 1, len(mean)), -4, 4))
+
+    # ---- old_logp: "mixed" on every row of the member's pool, from the member's own policy and clip range
+    moved = 0
+    for k in range(K):
+        old_logp[pools[k]], e = mixed_old_logp(ac_cls, D, R.flat_params(pols[k]), obs[pools[k]], act[pools[k]], clips[k], rng)
+        moved += e
+    if case == "underflow":
+        n_under = max(2, B // 10) if B >= 4 else 1
+        for k in range(K):
+            rows = idx[k][rng.permutation(B)[:n_under]]
+            lp = R.logp64(ac_cls, D, R.flat_params(pols[k]), obs[rows], act[rows])
+            old_logp[rows] = f32(lp + UNDERFLOW_SHIFT)
+            adv[rows] = f32(np.where(np.arange(n_under) % 2 == 0, 1.0, -1.0) * rng.uniform(2.0, 4.0, n_under))
+
+    bt = EdgeBatch(D=D, B=B, K=K, n=n, case=case, seed=seed, clips=tuple(clips), obs=obs, act=act, old_logp=old_logp,
+                   adv=adv, ret=ret, idx=idx, pools=pools, pols=pols, ac_cls=ac_cls, labels=labels)
+
+    # ---- labels, on the minibatch rows of every member
+    labels["edge_ratios_moved"] = moved
+    dlogp = []
+    for k in range(K):
+        o, a, old, ad, _ = bt.rows(k)
+        d = R.logp64(ac_cls, D, bt.theta(k), o, a) - old
+        dlogp.append(d)
+        r = np.exp(d)
+        assert not ((np.abs(r - (1 - clips[k])) < 1e-4) | (np.abs(r - (1 + clips[k])) < 1e-4)).any()
+    labels["max_logp_minus_old"] = float(max(d.max() for d in dlogp))
+    labels["adv_std"] = [float(bt.rows(k)[3].std(ddof=1)) for k in range(K)]
+    if case == "saturated":
+        labels["hidden"] = [hidden_stats(pols[k], obs[idx[k]]) for k in range(K)]
+    if case == "wide_obs":
+        labels["column_max"] = np.abs(obs[idx.reshape(-1)]).max(0)
+    if case == "grid_adv":
+        labels["grid"] = [dict(c=c, q=q, sum_k=int(kk.sum()), k_max=int(np.abs(kk).max()),
+                               sums_exact=B * (c + GRID_KMAX * q) / q, squares_exact=B * GRID_KMAX ** 2,
+                               one_pass_error=one_pass_variance_error(adv[idx[k]]),
+                               offset_over_std=c / float(adv[idx[k]].astype(np.float64).std(ddof=1)))
+                          for k, (c, q, kk) in enumerate(grids)]
+    if log_std is not None:
+        labels["log_std"] = log_std
+        labels["max_sigmas_off_mean"] = float(max(
+            np.abs(bt.rows(k)[1] - R.forward64(R.params64(pols[k]), obs[idx[k]])[0]).max() for k in range(K)) / np.exp(log_std))
+    if case == "underflow":
+        under = [d < -100 for d in dlogp]
+        a_n = [bt.rows(k)[3] - bt.rows(k)[3].mean() for k in range(K)]
+        labels["underflow"] = [dict(rows=int(u.sum()), positive=int((a[u] > 0).sum()), negative=int((a[u] < 0).sum()),
+                                    ratio32=float(np.exp(d[u].astype(np.float32)).max()), ratio64=float(np.exp(d[u]).max()),
+                                    others_min=float(d[~u].min()) if (~u).any() else 0.0)
+                               for u, a, d in zip(under, a_n, dlogp)]
+    return bt
+
+
+def check_labels(bt):
+    """The labels say the case is the case it claims to be."""
+    L, B, D, K = bt.labels, bt.B, bt.D, bt.K
+    assert L["max_logp_minus_old"] <= 3.0, L["max_logp_minus_old"]
+    assert bt.n > K * B and bt.idx.shape == (K, B) and bt.idx.min() >= 0 and bt.idx.max() < bt.n
+    if bt.case != "dup_rows":
+        assert len(np.unique(bt.idx)) == K * B
+    if bt.case == "saturated":
+        for h in L["hidden"]:
+            for z in h["z1_max"] + h["z2_max"]:
+                assert Z_RANGE[0] <= z <= Z_RANGE[1], h
+            assert h["share_exactly_one"] > 0.05 and h["share_cancelling"] > 0.05, h
+    if bt.case == "wide_obs":
+        cols, cm = loud_columns(D), L["column_max"]
+        assert {0, D - 1} <= set(cols) and all((c in cols) == (c < D) for c in TILE_BORDERS)
+        assert all(10.0 <= cm[c] <= 30.0 for c in cols), cm[cols]
+        assert len(set(np.round(loud_scales(D), 3))) == len(cols)              # every loud column at its own scale
+        if B >= 65:                                                            # ... and its own observed maximum
+            assert all(cm[a] > cm[b] for a, b in zip(cols[:-1], cols[1:])), cm[cols]
+        assert np.delete(cm, cols).max(initial=0.0) <= 1.0
+    if bt.case == "grid_adv":
+        for gl, std in zip(L["grid"], L["adv_std"]):
+            assert gl["sum_k"] == 0 and 1 <= gl["k_max"] <= GRID_KMAX, gl
+            assert gl["sums_exact"] < 2 ** 24 and gl["squares_exact"] < 2 ** 24, gl
+            assert gl["one_pass_error"] > ONE_PASS_MIN, gl
+            assert gl["offset_over_std"] > 20, gl
+    if bt.case == "const_adv":
+        assert L["adv_std"] == [0.0] * K and bool((bt.adv == 0.5).all())
+    if bt.case.startswith("log_std"):
+        assert L["log_std"] in (-2.5, 1.0) and L["max_sigmas_off_mean"] <= 4.0 + 1e-3, L
+        assert all(float(p.log_std.detach()) == L["log_std"] for p in bt.pols)
+    if bt.case == "dup_rows":
+        assert L["has_row_0"] and L["has_row_last"], L
+        for k in range(K):
+            if B >= 65:
+                assert L["run_start"][k] % 64 == 0 and L["longest_run"][k] >= 64, L
+            if B >= 4:
+                assert L["distinct_rows"][k] < B, L
+    if bt.case == "underflow":
+        for u in L["underflow"]:
+            assert u["rows"] == (max(2, B // 10) if B >= 4 else 1), u
+            assert u["ratio32"] == 0.0 and 0.0 < u["ratio64"] < 1e-46, u
+            assert u["others_min"] > -4.0, u
+            if u["rows"] >= 2:
+                assert u["positive"] >= 1 and u["negative"] >= 1, u
