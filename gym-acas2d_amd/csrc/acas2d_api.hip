@@ -120,6 +120,12 @@ int acas2d_collect_group_f32(const Acas2dConfig* cfg, const Acas2dState* state, 
                              int32_t n_traffic, void* stream) {
     return launch_collect_group<float>(cfg, state, io, ac, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, (hipStream_t)stream);
 }
+int acas2d_collect_set_group_f32(const Acas2dConfig* cfg, const Acas2dState* state, const Acas2dStepIO* io,
+                                 const Acas2dActorCritic* ac, int32_t n_members, const uint64_t* noise_seeds, const void* obs_in,
+                                 int32_t n_steps, uint64_t seed, int64_t env_offset, int64_t n_envs, int32_t n_traffic, void* stream) {
+    return launch_collect_set_group<float>(cfg, state, io, ac, n_members, noise_seeds, obs_in, n_steps, seed, env_offset, n_envs,
+                                           n_traffic, (hipStream_t)stream);
+}
 int acas2d_evaluate_policies_group_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs,
                                        const Acas2dPolicy* policies, int32_t n_policies, int32_t n_episodes, const void* obs_in,
                                        int32_t n_steps, uint64_t seed, int64_t env_offset, int32_t n_traffic, uint8_t* outcome,

@@ -8,9 +8,10 @@ constexpr bool kFast = true;
 }
 #include "acas2d_launch.inl"
 
-// the set collector exists in float32 only
+// the set collectors exist in float32 only
 namespace acas2d {
 template decltype(launch_collect_set<float>) launch_collect_set<float>;
+template decltype(launch_collect_set_group<float>) launch_collect_set_group<float>;
 }
 
 #ifdef ACAS2D_STAMPS

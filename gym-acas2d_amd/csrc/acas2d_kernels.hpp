@@ -1389,7 +1389,7 @@ struct PolicyW {
     const float* log_std;                            // [1]
     void *values_out, *logp_out;                     // T[n_steps][E]
     uint32_t nk0, nk1, noise_step;
-    // Mode::CollectSet (acas2d_collect_set_f32): K actor-critics side by side, member k on the envs
+    // Mode::CollectSet (acas2d_collect_set_f32, acas2d_collect_set_group_f32): K actor-critics side by side, member k on the envs
     // [k member_stride, (k + 1) member_stride).  Every weight pointer above then names a [K][...] stack, log_std is
     // float[K], and (nk0, nk1) hold the two halves of the ADDRESS of the K 64-bit noise keys: a wave loads its member's key
     // into them before the first step.  (The field lies in what was the struct's tail padding: no layout changes.)
@@ -1617,7 +1617,7 @@ enum class Mode {
     Policy,     // acas2d_rollout_policy_*
     Collect,    // acas2d_collect_*
     Eval,       // acas2d_evaluate_policies_*
-    CollectSet, // acas2d_collect_set_f32: Collect for K stacked actor-critics (float32, one lane per env)
+    CollectSet, // acas2d_collect_set_f32, acas2d_collect_set_group_f32: Collect for K stacked actor-critics (float32)
 };
 constexpr bool sample_mode(Mode m) { return m == Mode::Collect || m == Mode::CollectSet; }
 constexpr bool policy_mode(Mode m) { return m == Mode::Policy || sample_mode(m) || m == Mode::Eval; }
@@ -1647,7 +1647,8 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
     constexpr bool AUTO_RESET = M != Mode::Latch, ROLLOUT = rollout_mode(M);
     constexpr bool POLICY = policy_mode(M), SAMPLE = sample_mode(M);
     constexpr bool ARENA = M == Mode::Arena, EVAL = M == Mode::Eval, SET = M == Mode::CollectSet;
-    static_assert(!SET || (G == 1 && PACKED && sizeof(T) == 4), "set collection: float32, one lane per env");
+    static_assert(!SET || (PACKED && sizeof(T) == 4 && (G == 1 || group_policy_shape(C, G))),
+                  "set collection: float32, one lane per env or the group-cooperative shapes");
     static_assert(!ROLLOUT || PACKED, "rollout modes: packed shapes");
     static_assert(!POLICY || G == 1 || (PACKED && sizeof(T) == 4 && group_policy_shape(C, G)),
                   "in-kernel policy: one lane per env, or the group-cooperative float32 shapes");
@@ -2238,11 +2239,15 @@ int launch_evaluate_policies(const Acas2dConfig* cfg, const Acas2dState* st, int
                              int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
                              int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
                              hipStream_t stream, bool group = false);
-// acas2d_collect_set_f32 (float32 only: acas2d_f32.hip instantiates it)
+// acas2d_collect_set_f32 and acas2d_collect_set_group_f32 (float32 only: acas2d_f32.hip instantiates them)
 template <typename T>
 int launch_collect_set(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
                        int32_t n_members, const uint64_t* noise_seeds, const void* obs_in, int32_t n_steps, uint64_t seed,
                        int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream);
+template <typename T>
+int launch_collect_set_group(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
+                             int32_t n_members, const uint64_t* noise_seeds, const void* obs_in, int32_t n_steps, uint64_t seed,
+                             int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream);
 // the *_group entry points (float32: the double instantiations reject every traffic count)
 template <typename T>
 int launch_rollout_policy_group(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io,

@@ -336,7 +336,7 @@ static int launch_mode(const Launch<T>& L, const PW& pw) {
     dispatch(*L.cfg, L.sh, [&](auto fast, auto C, auto G, auto packed) {
         if constexpr ((M != Mode::Arena || (packed && sizeof(T) == 4)) && (!rollout_mode(M) || packed) &&
                       (!policy_mode(M) || G == 1 || (sizeof(T) == 4 && packed && group_policy_shape(C, G))) &&
-                      (M != Mode::CollectSet || (G == 1 && sizeof(T) == 4)))
+                      (M != Mode::CollectSet || sizeof(T) == 4))
             hipLaunchKernelGGL((step_kernel<T, C, G, packed, fast, M>), dim3(L.g.grid), dim3(L.g.block), L.g.lds_bytes,
                                L.stream, a[0], a[1], a[2], a[3], a[4], a[5], (int32_t)L.n_envs, (int32_t)L.g.tile_elems,
                                L.p, rp, s, L.io, L.k0, L.k1, L.env_offset, L.N, L.n_steps, pw);
@@ -449,15 +449,19 @@ int launch_collect_group(const Acas2dConfig* cfg, const Acas2dState* st, const A
 }
 
 // acas2d_collect_set_f32: acas2d_collect_* for K stacked actor-critics, member k on the envs [k EM, (k + 1) EM) with
-// EM = n_envs / K a multiple of the wave, so that the member is wave-uniform.  float32, one lane per env.
+// EM = n_envs / K a multiple of the wave, so that the member is wave-uniform.  float32, one lane per env -- or, `group`
+// (acas2d_collect_set_group_f32), the env's G lanes together at the shapes of group_shape(): a wave then holds 64 / G envs,
+// and the same rule for EM keeps them one member's.
 template <typename T>
-int launch_collect_set(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
+static int collect_set(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
                        int32_t n_members, const uint64_t* noise_seeds, const void* obs_in, int32_t n_steps, uint64_t seed,
-                       int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream) {
+                       int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream, bool group) {
     static_assert(sizeof(T) == 4, "acas2d_collect_set: float32 only");
-    static const char kScope[] = "float32, n_traffic in {1, 2, 3, 4, 8}; float64 and the group-cooperative launches of "
-                                 "n_traffic 16 / 32 / 64 collect one learner per call";
-    Launch<T> L{"acas2d_collect_set", cfg, st, io, seed, env_offset, n_envs, n_traffic, n_steps, stream};
+    static const char kScope[] = "float32, n_traffic in {1, 2, 3, 4, 8}; n_traffic 16 / 32 / 64 is acas2d_collect_set_group_f32, "
+                                 "float64 collects one learner per call";
+    Launch<T> L{group ? "acas2d_collect_set_group" : "acas2d_collect_set", cfg, st, io, seed, env_offset, n_envs, n_traffic,
+                n_steps, stream};
+    L.group_policy = group;
     const auto inputs = [&] {
         if (!io->actions || !io->obs || !io->reward || !io->done || !io->outcome || !obs_in)
             return fail("%s: obs_in, actions (output), obs, reward, done and outcome are required", L.name);
@@ -472,6 +476,7 @@ int launch_collect_set(const Acas2dConfig* cfg, const Acas2dState* st, const Aca
         return ACAS2D_OK;
     };
     const auto shape = [&](Shape* sh) {
+        if (group) return group_shape<T>(L.name, "acas2d_collect_set_f32", n_traffic, sh);
         *sh = Shape{n_traffic, 1, true};
         if (shape_instantiated(*sh)) return ACAS2D_OK;
         return fail("%s: n_traffic = %d has no thread-per-env shape (%s)", L.name, n_traffic, kScope);
@@ -479,6 +484,9 @@ int launch_collect_set(const Acas2dConfig* cfg, const Acas2dState* st, const Aca
     const auto go = [&] {
         PolicyW pw = actor<PolicyW>(&ac->actor, obs_in);
         pw.actions_out = const_cast<void*>(io->actions);
+        if (group)      // (a member's slice lies a multiple of 256 bytes behind the stack's base: the base decides)
+            if (int rc = require_aligned(L.name, {ac->actor.w1t, ac->actor.b1, ac->actor.w2t, ac->actor.b2, ac->v1t, ac->vb1,
+                                                  ac->v2t, ac->vb2})) return rc;
         pw.v1t = (const float*)ac->v1t; pw.vb1 = (const float*)ac->vb1; pw.v2t = (const float*)ac->v2t;
         pw.vb2 = (const float*)ac->vb2; pw.v3 = (const float*)ac->v3; pw.vb3 = (const float*)ac->vb3;
         pw.log_std = (const float*)ac->log_std; pw.values_out = ac->values; pw.logp_out = ac->logp;
@@ -488,6 +496,18 @@ int launch_collect_set(const Acas2dConfig* cfg, const Acas2dState* st, const Aca
         return launch_mode<Mode::CollectSet>(L, pw);
     };
     return prepare(L, Words{"cfg / io / actor-critic", kSizes, kNegative}, io && ac, inputs, shape, go);
+}
+template <typename T>
+int launch_collect_set(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
+                       int32_t n_members, const uint64_t* noise_seeds, const void* obs_in, int32_t n_steps, uint64_t seed,
+                       int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream) {
+    return collect_set<T>(cfg, st, io, ac, n_members, noise_seeds, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream, false);
+}
+template <typename T>
+int launch_collect_set_group(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
+                             int32_t n_members, const uint64_t* noise_seeds, const void* obs_in, int32_t n_steps, uint64_t seed,
+                             int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream) {
+    return collect_set<T>(cfg, st, io, ac, n_members, noise_seeds, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream, true);
 }
 
 // K stacked policies scored on shared episodes: policy k plays envs [k EP, (k + 1) EP) of the state, EP = n_episodes

@@ -1,8 +1,9 @@
-// acas2d_ppo.hpp -- what the three translation units of the PPO minibatch update share, each thing written once: the flat
+// acas2d_ppo.hpp -- what the translation units of the PPO minibatch update share, each thing written once: the flat
 // gradient / moment layout, the d loss / d output block (loss_grad), the one-wave gradient body of the narrow widths
 // (grad_narrow<D>), the apply body (apply_body: norm, clip_grad_norm_, Adam), and the host helpers of the entry points
-// (pointer check, NetW pair, per-device LDS opt-in).  The __global__ kernels of acas2d_ppo.hip, acas2d_ppo_wide.hip and
-// acas2d_ppo_set.hip are prologues in front of these bodies.
+// (pointer check, NetW pair, per-device LDS opt-in).  The __global__ kernels of acas2d_ppo.hip and acas2d_ppo_set.hip are
+// prologues in front of these bodies; those of acas2d_ppo_wide.hip and acas2d_ppo_wide_set.hip in front of grad_wide<D>
+// (acas2d_ppo_wide.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -324,5 +325,7 @@ inline int launched(const char* what) {
 
 // ppo_apply_kernel on the 13 parameter tensors of `u` (acas2d_ppo.hip); ACAS2D_OK or ACAS2D_EHIP with the error set
 int launch_ppo_apply(const Acas2dPpoUpdate& u, hipStream_t stream);
+// ppo_apply_set_kernel on the K members of `u`, whatever its obs_dim (acas2d_ppo_set.hip); likewise
+int launch_ppo_apply_set(const Acas2dPpoUpdateSet& u, hipStream_t stream);
 
 }  // namespace acas2d

@@ -12,8 +12,8 @@
 //                         k's slices with hyper[k] and adam_step[k].
 //
 // With one wave per network (n_rows <= 64) every gradient entry receives one atomic add, and the set and the solo update
-// agree in every bit.  Out of scope (rejected): float64, the wide widths (obs_dim 53 / 101 / 197: acas2d_ppo_update_wide_f32, one
-// learner per call), members with different n_rows.
+// agree in every bit.  Out of scope (rejected): float64, members with different n_rows, and the wide widths (obs_dim 53 /
+// 101 / 197): those are acas2d_ppo_update_wide_set_f32 (acas2d_ppo_wide_set.hip), which shares ppo_apply_set_kernel.
 #include "acas2d_ppo.hpp"
 
 namespace acas2d {
@@ -70,6 +70,15 @@ int launch_grad_set(const Acas2dPpoUpdateSet& u, hipStream_t stream) {
 }
 
 }  // namespace
+
+// ppo_apply_set_kernel on the K members of `u`; the wide set update (acas2d_ppo_wide_set.hip) ends with it too
+int launch_ppo_apply_set(const Acas2dPpoUpdateSet& u, hipStream_t stream) {
+    hipLaunchKernelGGL(ppo_apply_set_kernel, dim3((unsigned)u.n_members), dim3(1024), 0, stream, param_ptrs(u), u.obs_dim,
+                       (const float*)u.hyper, (float*)u.grad, (float*)u.adam_m, (float*)u.adam_v, u.adam_step,
+                       (float*)u.stats);
+    return launched("acas2d_ppo_update_set launch");
+}
+
 }  // namespace acas2d
 
 using namespace acas2d;
@@ -90,13 +99,10 @@ extern "C" int acas2d_ppo_update_set_f32(const Acas2dPpoUpdateSet* u, void* stre
         case 29: rc = launch_grad_set<29>(*u, stream); break;
         default:
             set_error("acas2d_ppo_update_set: obs_dim = %d (float32, built for n_traffic in {1, 2, 3, 4, 8}: obs_dim 8, 11, 14, "
-                      "17, 29; the wide update of n_traffic 16 / 32 / 64 takes one learner per call)", D);
+                      "17, 29; n_traffic 16 / 32 / 64 is acas2d_ppo_update_wide_set_f32)", D);
             return ACAS2D_EINVAL;
     }
     if (rc != ACAS2D_OK) return rc;                      // (a failed gradient launch must not read as a zero gradient)
     if (u->apply == 0) return ACAS2D_OK;                 // tests: the raw gradients stay in `grad`, nothing is applied
-    hipLaunchKernelGGL(ppo_apply_set_kernel, dim3((unsigned)u->n_members), dim3(1024), 0, stream, param_ptrs(*u), D,
-                       (const float*)u->hyper, (float*)u->grad, (float*)u->adam_m, (float*)u->adam_v, u->adam_step,
-                       (float*)u->stats);
-    return launched("acas2d_ppo_update_set launch");
+    return launch_ppo_apply_set(*u, stream);
 }

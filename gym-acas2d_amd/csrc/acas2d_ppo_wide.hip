@@ -2,8 +2,10 @@
 // aircraft): acas2d_ppo_update_wide_f32, same struct, same flat gradient / moment layout, same `stats`, same probe mode.
 //
 // ppo_grad_kernel<D> keeps x[D] and a D-wide gradient row per lane in registers; at these widths that does not fit.
-// ppo_grad_wide_kernel<D> keeps the scheme -- one lane per sample, weights as scalar operands, the per-sample vectors in
-// LDS with row stride 65 -- and tiles what is D-sized, with FOUR waves per 64 samples and network:
+// ppo_grad_wide_kernel<D> is a prologue in front of grad_wide<D> (acas2d_ppo_wide.hpp), the body it shares with the
+// K-learner kernel of acas2d_ppo_wide_set.hip.  That body keeps the scheme -- one lane per sample, weights as scalar
+// operands, the per-sample vectors in LDS with row stride 65 -- and tiles what is D-sized, with FOUR waves per 64 samples
+// and network:
 //
 //   forward / backward to the pre-activations   every wave holds the same 64 samples (lane = sample) and takes 16 of the
 //                      64 hidden units of each layer: layer 1 accumulates its 16 pre-activations in registers over
@@ -16,25 +18,30 @@
 //   the advantage statistics of the whole minibatch are taken by the actor workgroup's 256 threads together.
 // d loss / d output is loss_grad of acas2d_ppo.hpp, the narrow kernels' own.  ppo_apply_kernel (norm, clip_grad_norm_,
 // Adam) does not depend on the width: launch_ppo_apply of acas2d_ppo.hip.
-#include "acas2d_ppo.hpp"
+#include "acas2d_ppo_wide.hpp"
 
 namespace acas2d {
 using namespace ppo;
+using namespace ppo::wide;
 
 namespace {
 
-constexpr int kWaves = 4;                   // per workgroup: one per SIMD
-constexpr int kThreads = 64 * kWaves;
-constexpr int kU = kH / kWaves;             // hidden units (rows of a weight gradient) per wave
-constexpr int kChunk = 4;                   // observation entries per layer-1 step (8: the weights in flight spill SGPRs)
-
-// LDS row stride of the observation tile: odd, so that "every lane reads entry k of its own row" is conflict-free
-__host__ __device__ constexpr int x_stride(int D) { return D | 1; }
-// dynamic LDS in bytes: the 64 gathered row indices, 4 x [64][65] per-sample vectors, the observations, d loss / d
-// output per sample, the two cross-wave partial sums
-__host__ __device__ constexpr size_t lds_bytes(int D) {
-    return 64 * sizeof(int64_t) + (size_t)(4 * 64 * kRow + 64 * x_stride(D) + 64 + 2 * kWaves) * sizeof(float);
-}
+// one learner: the kernel's own arguments, no offsets
+struct OneLearner {
+    const Nets& nets;
+    const float* log_std_p;
+    const int64_t* idx_p;
+    float clip, vf;
+    float *grad_p, *stats_p;
+    __device__ __forceinline__ NetW net() const { return nets.n[blockIdx.y]; }
+    __device__ __forceinline__ static constexpr int at(int) { return 0; }
+    __device__ __forceinline__ const int64_t* idx() const { return idx_p; }
+    __device__ __forceinline__ const float* log_std() const { return log_std_p; }
+    __device__ __forceinline__ float clip_range() const { return clip; }
+    __device__ __forceinline__ float vf_coef() const { return vf; }
+    __device__ __forceinline__ float* grad() const { return grad_p; }
+    __device__ __forceinline__ float* stats() const { return stats_p; }
+};
 
 template <int D>
 __global__ __launch_bounds__(kThreads) void ppo_grad_wide_kernel(Nets nets, const float* log_std_p,
@@ -42,188 +49,7 @@ __global__ __launch_bounds__(kThreads) void ppo_grad_wide_kernel(Nets nets, cons
                                                                  const float* adv, const float* ret, const int64_t* idx,
                                                                  int B, float clip_range, float vf_coef, float* grad,
                                                                  float* stats) {
-    constexpr int XS = x_stride(D);
-    extern __shared__ __align__(16) unsigned char lds_raw[];
-    int64_t* l_idx = reinterpret_cast<int64_t*>(lds_raw);             // [64]
-    float* l_h1 = reinterpret_cast<float*>(l_idx + 64);                // [64][65]
-    float* l_h2 = l_h1 + 64 * kRow;
-    float* l_dz1 = l_h2 + 64 * kRow;
-    float* l_dz2 = l_dz1 + 64 * kRow;
-    float* l_x = l_dz2 + 64 * kRow;                                    // [64][XS], columns < D only
-    float* l_do = l_x + 64 * XS;                                       // [64]
-    float* l_red = l_do + 64;                                          // [2][kWaves]
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);           // wave-uniform: weight addresses stay scalar
-    const int u0 = w * kU;
-    const int u0v = (tid >> 6) * kU;                                   // the same in a VGPR: the atomics' addresses
-    const bool is_actor = blockIdx.y == 0;
-    const NetW net = nets.n[blockIdx.y];
-    const int row = blockIdx.x * 64 + lane;
-    const bool live = row < B;
-    const int64_t s = idx[live ? row : 0];
-    if (w == 0) l_idx[lane] = s;
-
-    // ---- the minibatch's advantage statistics (SB3 normalises per minibatch; torch.std is Bessel-corrected)
-    float a_mean = 0.0f, a_std = 1.0f;
-    if (is_actor) {                                                    // (uniform over the workgroup)
-        float sum = 0.0f;
-        for (int i = tid; i < B; i += kThreads) sum += adv[idx[i]];
-        sum = wave_sum(sum);
-        if (lane == 0) l_red[w] = sum;
-        __syncthreads();
-        a_mean = (l_red[0] + l_red[1] + l_red[2] + l_red[3]) / (float)B;
-        float sq = 0.0f;
-        for (int i = tid; i < B; i += kThreads) { const float d = adv[idx[i]] - a_mean; sq = fmaf(d, d, sq); }
-        sq = wave_sum(sq);
-        if (lane == 0) l_red[kWaves + w] = sq;
-        __syncthreads();
-        a_std = sqrtf((l_red[kWaves] + l_red[kWaves + 1] + l_red[kWaves + 2] + l_red[kWaves + 3]) / (float)(B > 1 ? B - 1 : 1));
-    }
-    __syncthreads();
-
-    // ---- the 64 observation rows into LDS, coalesced along a row; nothing past column D - 1 of a row is read
-    for (int e = tid; e < 64 * D; e += kThreads) {
-        const int r = e / D, k = e - r * D;
-        l_x[r * XS + k] = obs[l_idx[r] * D + k];
-    }
-    __syncthreads();
-
-    // ---- forward: obs -> Linear(D, 64) tanh -> Linear(64, 64) tanh -> Linear(64, 1), weights by scalar loads
-    const float ACAS2D_C4* w1 = (const float ACAS2D_C4*)net.w1;
-    const float ACAS2D_C4* b1 = (const float ACAS2D_C4*)net.b1;
-    const float ACAS2D_C4* w2 = (const float ACAS2D_C4*)net.w2;
-    const float ACAS2D_C4* b2 = (const float ACAS2D_C4*)net.b2;
-    const float ACAS2D_C4* w3 = (const float ACAS2D_C4*)net.w3;
-    const float ACAS2D_C4* b3 = (const float ACAS2D_C4*)net.b3;
-    {
-        float z[kU];
-#pragma unroll
-        for (int j = 0; j < kU; ++j) z[j] = b1[u0 + j];
-        const float* xr = l_x + lane * XS;
-        for (int k0 = 0; k0 + kChunk <= D; k0 += kChunk) {
-            float xv[kChunk];
-#pragma unroll
-            for (int kk = 0; kk < kChunk; ++kk) xv[kk] = xr[k0 + kk];
-#pragma unroll
-            for (int j = 0; j < kU; ++j)
-#pragma unroll
-                for (int kk = 0; kk < kChunk; ++kk) z[j] = fmaf(w1[(u0 + j) * D + k0 + kk], xv[kk], z[j]);
-        }
-        constexpr int kTail = D % kChunk, kT0 = D - kTail;
-        if (kTail > 0) {
-            float xv[kTail > 0 ? kTail : 1];
-#pragma unroll
-            for (int kk = 0; kk < kTail; ++kk) xv[kk] = xr[kT0 + kk];
-#pragma unroll
-            for (int j = 0; j < kU; ++j)
-#pragma unroll
-                for (int kk = 0; kk < kTail; ++kk) z[j] = fmaf(w1[(u0 + j) * D + kT0 + kk], xv[kk], z[j]);
-        }
-#pragma unroll
-        for (int j = 0; j < kU; ++j) l_h1[lane * kRow + u0 + j] = tanhf(z[j]);
-    }
-    __syncthreads();
-    {
-        float h1[kH];
-#pragma unroll
-        for (int k = 0; k < kH; ++k) h1[k] = l_h1[lane * kRow + k];
-#pragma unroll 1
-        for (int j = 0; j < kU; ++j) {
-            const int i = u0 + j;
-            float z = b2[i];
-#pragma unroll
-            for (int k = 0; k < kH; ++k) z = fmaf(w2[i * kH + k], h1[k], z);
-            l_h2[lane * kRow + i] = tanhf(z);
-        }
-    }
-    __syncthreads();
-    float out = b3[0];                                                 // (every wave: all of them need d loss / d output)
-    for (int i = 0; i < kH; ++i) out = fmaf(w3[i], l_h2[lane * kRow + i], out);
-
-    float dout, dls, pg_s, vf_s;
-    loss_grad(is_actor, live, out, act + s, old_logp + s, adv + s, ret + s, a_mean, a_std, log_std_p, B, clip_range, vf_coef,
-              dout, dls, pg_s, vf_s);
-    if (w == 0) l_do[lane] = dout;
-
-    // ---- backward to the pre-activations: dz2 = dout w3 (1 - h2^2), dh1 = W2^T dz2, dz1 = dh1 (1 - h1^2)
-#pragma unroll
-    for (int j = 0; j < kU; ++j) {
-        const float h2 = l_h2[lane * kRow + u0 + j];
-        l_dz2[lane * kRow + u0 + j] = dout * w3[u0 + j] * (1.0f - h2 * h2);
-    }
-    __syncthreads();
-    {
-        float dh1[kU];
-#pragma unroll
-        for (int j = 0; j < kU; ++j) dh1[j] = 0.0f;
-#pragma unroll 1
-        for (int i = 0; i < kH; ++i) {
-            const float dz2 = l_dz2[lane * kRow + i];
-#pragma unroll
-            for (int j = 0; j < kU; ++j) dh1[j] = fmaf(w2[i * kH + u0 + j], dz2, dh1[j]);
-        }
-#pragma unroll
-        for (int j = 0; j < kU; ++j) {
-            const float h1 = l_h1[lane * kRow + u0 + j];
-            l_dz1[lane * kRow + u0 + j] = dh1[j] * (1.0f - h1 * h1);
-        }
-    }
-    __syncthreads();
-
-    // ---- weight gradients: the lane takes a column, the wave rows u0 .. u0 + 15, summed over the 64 samples
-    float* g = grad + (is_actor ? 0 : net_size(D));
-    {
-        float acc[kU];
-#pragma unroll
-        for (int j = 0; j < kU; ++j) acc[j] = 0.0f;
-#pragma unroll 2
-        for (int q = 0; q < 64; ++q) {
-            const float h1 = l_h1[q * kRow + lane];
-#pragma unroll
-            for (int j = 0; j < kU; ++j) acc[j] = fmaf(l_dz2[q * kRow + u0 + j], h1, acc[j]);
-        }
-#pragma unroll
-        for (int j = 0; j < kU; ++j) atomicAdd(g + off_w2(D) + (u0v + j) * kH + lane, acc[j]);
-    }
-    for (int c0 = 0; c0 < D; c0 += 64) {
-        const int c = c0 + lane;
-        const bool col = c < D;
-        const float* xc = l_x + (col ? c : D - 1);                    // (a lane past the last column re-reads it, adds nothing)
-        float acc[kU];
-#pragma unroll
-        for (int j = 0; j < kU; ++j) acc[j] = 0.0f;
-#pragma unroll 2
-        for (int q = 0; q < 64; ++q) {
-            const float x = xc[q * XS];
-#pragma unroll
-            for (int j = 0; j < kU; ++j) acc[j] = fmaf(l_dz1[q * kRow + u0 + j], x, acc[j]);
-        }
-        if (col) {
-#pragma unroll
-            for (int j = 0; j < kU; ++j) atomicAdd(g + (u0v + j) * D + c, acc[j]);
-        }
-    }
-    // ---- the vectors, one wave each: b2, b1, w3, and the scalars
-    if (w == 0) {
-        float bsum = 0.0f;
-        for (int q = 0; q < 64; ++q) bsum += l_dz2[q * kRow + lane];
-        atomicAdd(g + off_b2(D) + lane, bsum);
-    } else if (w == 1) {
-        float bsum = 0.0f;
-        for (int q = 0; q < 64; ++q) bsum += l_dz1[q * kRow + lane];
-        atomicAdd(g + off_b1(D) + lane, bsum);
-    } else if (w == 2) {
-        float w3sum = 0.0f;
-        for (int q = 0; q < 64; ++q) w3sum = fmaf(l_do[q], l_h2[q * kRow + lane], w3sum);
-        atomicAdd(g + off_w3(D) + lane, w3sum);
-    } else {
-        const float dsum = wave_sum(dout), lsum = wave_sum(dls), pgsum = wave_sum(pg_s), vfsum = wave_sum(vf_s);
-        if (lane == 0) {
-            atomicAdd(g + off_b3(D), dsum);
-            if (is_actor) { atomicAdd(grad + 2 * net_size(D), lsum); atomicAdd(stats + 0, pgsum); }
-            else atomicAdd(stats + 1, vfsum);
-        }
-    }
+    grad_wide<D>(OneLearner{nets, log_std_p, idx, clip_range, vf_coef, grad, stats}, obs, act, old_logp, adv, ret, B);
 }
 
 // The dynamic LDS is 79 - 115 KB: ensure_dynamic_lds raises the kernel's limit on the current device and checks the size.
@@ -245,6 +71,7 @@ int launch_grad_wide(const Acas2dPpoUpdate& u, hipStream_t stream) {
 
 using namespace acas2d;
 using namespace acas2d::ppo;
+using namespace acas2d::ppo::wide;
 
 extern "C" int acas2d_ppo_wide_lds_bytes(int32_t obs_dim) {
     switch (obs_dim) {

@@ -72,7 +72,8 @@ EXPORTS = ("acas2d_abi_version", "acas2d_config_size", "acas2d_state_size", "aca
            "acas2d_state_is_consecutive", "acas2d_evaluate_policies_f32", "acas2d_evaluate_policies_f64",
            "acas2d_rollout_policy_group_f32", "acas2d_collect_group_f32", "acas2d_evaluate_policies_group_f32",
            "acas2d_ppo_update_wide_f32", "acas2d_ppo_wide_lds_bytes", "acas2d_collect_set_f32", "acas2d_ppo_update_set_f32",
-           "acas2d_gae_f32", "acas2d_gae_size", "acas2d_gae_pipeline_depth")
+           "acas2d_gae_f32", "acas2d_gae_size", "acas2d_gae_pipeline_depth", "acas2d_collect_set_group_f32",
+           "acas2d_ppo_update_wide_set_f32")
 
 
 class NativeLibraryError(RuntimeError):
@@ -140,12 +141,15 @@ def lib():
         f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.c_int64, C.POINTER(CPolicy), C.c_int32, C.c_int32,
                       C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                       C.c_void_p]
-    L.acas2d_collect_set_f32.restype = C.c_int
-    L.acas2d_collect_set_f32.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.POINTER(CStepIO), C.POINTER(CActorCritic),
-                                         C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int64,
-                                         C.c_int32, C.c_void_p]
-    L.acas2d_ppo_update_set_f32.restype = C.c_int
-    L.acas2d_ppo_update_set_f32.argtypes = [C.POINTER(CPpoUpdateSet), C.c_void_p]
+    for name in ("acas2d_collect_set_f32", "acas2d_collect_set_group_f32"):
+        f = getattr(L, name)
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.POINTER(CStepIO), C.POINTER(CActorCritic), C.c_int32,
+                      C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
+    for name in ("acas2d_ppo_update_set_f32", "acas2d_ppo_update_wide_set_f32"):
+        f = getattr(L, name)
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(CPpoUpdateSet), C.c_void_p]
     L.acas2d_gae_f32.restype = C.c_int
     L.acas2d_gae_f32.argtypes = [C.POINTER(CGae), C.c_void_p]
     L.acas2d_gae_size.restype = C.c_size_t

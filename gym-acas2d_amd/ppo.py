@@ -839,22 +839,29 @@ class ActorCriticSet:
 
 class FusedUpdateSet:
     """FusedUpdate for the K members of an `ActorCriticSet` in two launches whatever K is (acas2d_ppo_update_set_f32,
-    csrc/acas2d_ppo_set.hip).  `obs` [n, D], `act` / `old_logp` / `adv` / `ret` [n] are ONE flat float32 rollout buffer
+    csrc/acas2d_ppo_set.hip; for obs_dim 53, 101, 197 acas2d_ppo_update_wide_set_f32, csrc/acas2d_ppo_wide_set.hip --
+    `entry` names the one chosen).  `obs` [n, D], `act` / `old_logp` / `adv` / `ret` [n] are ONE flat float32 rollout buffer
     shared by the members (their storage must stay put); `step(idx)` takes an int64 device tensor [K, B]: row k names
     member k's minibatch as rows of that buffer.  `hyper` is a float32 device tensor [K, 8] (HYPER_SLOTS) the kernels
     read at every call: rewrite it between calls to change a member's learning rate, clip range, ...  Keeps the
-    members' Adam moments and step counts ([K, ...]).  float32, obs_dim in {8, 11, 14, 17, 29}."""
+    members' Adam moments and step counts ([K, ...]).  float32."""
 
     def __init__(self, policy_set, configs, obs, act, old_logp, adv, ret, beta1=0.9, beta2=0.999, adam_eps=1e-5):
         import ctypes as C
         from . import native
         D, K = obs.shape[-1], policy_set.n_members
-        if D not in FUSED_UPDATE_WIDTHS:
-            raise ValueError("FusedUpdateSet is built for obs_dim in {8, 11, 14, 17, 29} (n_traffic 1, 2, 3, 4, 8), float32; "
-                             "got %d (the wide update of n_traffic 16 / 32 / 64 takes one learner per call: FusedUpdate)" % D)
+        if D in FUSED_UPDATE_WIDTHS:
+            self.entry = "acas2d_ppo_update_set_f32"
+        elif D in FUSED_UPDATE_WIDE_WIDTHS:
+            self.entry = "acas2d_ppo_update_wide_set_f32"
+        else:
+            raise ValueError("FusedUpdateSet is built for obs_dim in {8, 11, 14, 17, 29} (n_traffic 1, 2, 3, 4, 8: "
+                             "acas2d_ppo_update_set_f32) and {53, 101, 197} (n_traffic 16, 32, 64: "
+                             "acas2d_ppo_update_wide_set_f32), float32; got %d" % D)
         if len(configs) != K or policy_set.obs_dim != D:
             raise ValueError("FusedUpdateSet needs one config per member and members of obs_dim %d" % D)
         self._C, self._native, self._lib = C, native, native.lib()
+        self._update = getattr(self._lib, self.entry)
         dev = obs.device
         n = int(self._lib.acas2d_ppo_workspace_floats(D))
         z = lambda *k, dt=torch.float32: torch.zeros(*k, dtype=dt, device=dev)  # noqa: E731
@@ -873,7 +880,7 @@ class FusedUpdateSet:
         u = self._native.CPpoUpdateSet(*[p(t) for t in self._params], *[p(t) for t in self._bufs], p(idx), self.K,
                                        idx.shape[1], self.D, 1 if apply else 0, p(self.hyper), p(self.grad), p(self.m),
                                        p(self.v), p(self.step_count), p(self.stats))
-        self._native.check(self._lib.acas2d_ppo_update_set_f32(
+        self._native.check(self._update(
             self._C.byref(u), self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
 
     def last_losses(self):
@@ -887,6 +894,8 @@ class PopulationTrainer:
     hyper-parameters -- one collection launch (ACAS2DVecEnv.collect_set), two launches per minibatch (FusedUpdateSet) and
     one evaluation launch (evaluate_policies_fused) for all K, where K PPOTrainer(collector="fused", updater="fused") runs
     take K times as many.  There is no exchange between members: no exploit / explore step, K separate runs.
+    n_traffic in {1, 2, 3, 4, 8}; group=True: n_traffic in {8, 16, 32, 64}, with the group-cooperative launches
+    (collect_set(group=True), evaluate_policies_fused(group=True)) and, at 16 / 32 / 64, the wide update.
 
     `configs`: K PPOConfig.  MEMBER_FIELDS may differ; n_steps, batch_size and n_epochs must be equal (the members share
     every launch).  Member k starts from the weights PPOTrainer(PPOConfig(seed=s_k)) constructs, draws its minibatch
@@ -894,12 +903,12 @@ class PopulationTrainer:
     member's env steps (n_steps x EM per iteration), so learn()'s arguments mean per member what PPOTrainer.learn()'s do.
     With per-member gamma / gae_lambda GAE takes them as per-env float32 vectors (the product gamma x lambda is then
     rounded in float32); equal values are passed as the numbers they are.
-    Out of scope: float64, n_traffic 16 / 32 / 64 (the group-cooperative launches and the wide update), members with
-    different n_steps / batch_size / n_epochs, more than one GPU.
+    Out of scope: float64, members with different n_steps / batch_size / n_epochs, more than one GPU.
     gae: None / "torch" (compute_gae, op by op) or "kernel" (gae_fused: one launch for all members, the same bits)."""
 
-    def __init__(self, venv, configs, gae=None):
+    def __init__(self, venv, configs, gae=None, group=False):
         configs = list(configs)
+        self.group = bool(group)
         self.gae = gae or "torch"
         if self.gae not in ("torch", "kernel"):
             raise ValueError("gae must be None, 'torch' or 'kernel', got %r" % (gae,))
@@ -912,10 +921,13 @@ class PopulationTrainer:
         if getattr(venv, "dtype", torch.float32) != torch.float32:
             raise ValueError("PopulationTrainer is float32 only (float64 trains one learner per process: PPOTrainer), this "
                              "env is %s" % (venv.dtype,))
-        if venv.n_traffic not in (1, 2, 3, 4, 8) or venv.obs_dim not in FUSED_UPDATE_WIDTHS:
+        if self.group:
+            if venv.n_traffic not in (8, 16, 32, 64) or venv.obs_dim not in FUSED_UPDATE_WIDTHS + FUSED_UPDATE_WIDE_WIDTHS:
+                raise ValueError("PopulationTrainer(group=True) needs n_traffic in {8, 16, 32, 64}, got %d (n_traffic in "
+                                 "{1, 2, 3, 4}: group=False)" % venv.n_traffic)
+        elif venv.n_traffic not in (1, 2, 3, 4, 8) or venv.obs_dim not in FUSED_UPDATE_WIDTHS:
             raise ValueError("PopulationTrainer needs n_traffic in {1, 2, 3, 4, 8}, got %d (the group-cooperative launches "
-                             "and the wide update of n_traffic 16 / 32 / 64 train one learner per process: PPOTrainer)"
-                             % venv.n_traffic)
+                             "and the wide update of n_traffic 16 / 32 / 64: pass group=True)" % venv.n_traffic)
         K = len(configs)
         if venv.num_envs % K or (venv.num_envs // K) % 64:
             raise ValueError("PopulationTrainer needs num_envs = K x a multiple of 64, got num_envs = %d for K = %d members"
@@ -975,7 +987,7 @@ class PopulationTrainer:
     def collect(self):
         T, E, K, EM = self.cfg.n_steps, self.venv.num_envs, self.K, self.EM
         out = self.venv.collect_set(self.policy_set, T, self.noise_seeds, noise_step=self.num_timesteps // EM,
-                                    out=self._fused_out)
+                                    out=self._fused_out, **({"group": True} if self.group else {}))
         self._fused_out = out
         obs_all, rew = out["obs"], out["reward"]
         nan = torch.isnan(rew).view(T, K, EM).sum((0, 2)) + torch.isnan(obs_all[1:]).any(-1).view(T, K, EM).sum((0, 2))
@@ -1052,7 +1064,7 @@ class PopulationTrainer:
         from .policy import evaluate_policies_fused
         own, trf, goal = reset_parity.draw_episodes(self.venv.config, n_episodes, rng)
         return evaluate_policies_fused(self.policy_set.actor_weights(), own, trf, goal, dtype=self.venv.dtype,
-                                       device=self.device, config=self.venv.config)
+                                       device=self.device, config=self.venv.config, group=self.group)
 
     def learn(self, total_timesteps, log=print, eval_every=None, eval_episodes=10, eval_seed=None, save_dir=None,
               checkpoint_every=None):

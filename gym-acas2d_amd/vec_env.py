@@ -488,34 +488,45 @@ class ACAS2DVecEnv:
 
     # traffic counts with a float32 thread-per-env kernel: what acas2d_collect_set_f32 is built for
     SET_TRAFFIC = (1, 2, 3, 4, 8)
+    # ... and those of the group-cooperative policy: what acas2d_collect_set_group_f32 is built for
+    SET_GROUP_TRAFFIC = (8, 16, 32, 64)
 
-    def check_member_split(self, n_members):
+    def check_member_split(self, n_members, group=False):
         """Envs per member for a set of `n_members` learners on this env, or a ValueError saying what
-        acas2d_collect_set_f32 cannot take: float32, n_traffic in {1, 2, 3, 4, 8}, num_envs = K x a multiple of 64."""
+        acas2d_collect_set_f32 cannot take: float32, n_traffic in {1, 2, 3, 4, 8}, num_envs = K x a multiple of 64.
+        group=True: the same for acas2d_collect_set_group_f32, n_traffic in {8, 16, 32, 64}."""
         K = int(n_members)
-        if self.dtype != torch.float32:
+        if group:
+            self._group_entry("collect_set", "acas2d_collect_set_group_f32")
+            if self.n_traffic not in self.SET_GROUP_TRAFFIC:
+                raise ValueError("collect_set(group=True) needs a group-cooperative work shape: n_traffic in {8, 16, 32, 64}, "
+                                 "got %d (n_traffic in {1, 2, 3, 4}: collect_set())" % self.n_traffic)
+        elif self.dtype != torch.float32:
             raise ValueError("collect_set() is float32 only (float64 collects one learner per launch: collect()), this env "
                              "is %s" % (self.dtype,))
-        if self.n_traffic not in self.SET_TRAFFIC:
+        elif self.n_traffic not in self.SET_TRAFFIC:
             raise ValueError("collect_set() needs a thread-per-env work shape: n_traffic in {1, 2, 3, 4, 8}, got %d (the "
-                             "group-cooperative launches of n_traffic 16 / 32 / 64 collect one learner per launch: "
-                             "collect(group=True))" % self.n_traffic)
+                             "group-cooperative launches of n_traffic 16 / 32 / 64: collect_set(group=True))"
+                             % self.n_traffic)
         if K < 1 or self.num_envs % K or (self.num_envs // K) % 64:
             raise ValueError("collect_set() needs num_envs = K x a multiple of 64 (a wavefront's envs belong to one member), "
                              "got num_envs = %d, K = %d" % (self.num_envs, K))
         return self.num_envs // K
 
-    def collect_set(self, policy_set, n_steps, noise_seeds, noise_step=0, out=None):
+    def collect_set(self, policy_set, n_steps, noise_seeds, noise_step=0, out=None, group=False):
         """collect() for K independent actor-critics in ONE kernel launch (acas2d_collect_set_f32).  `policy_set` is a
         `ppo.ActorCriticSet` of K members; member k owns the envs [k EM, (k + 1) EM), EM = num_envs / K a multiple of 64,
         and draws its noise with the key noise_seeds[k] (K ints, or an int64 device tensor holding the keys' bit
         patterns) on collect()'s counter (global env index, noise_step + t).  Returns collect()'s dict, in the same
         [T, E] layout: the columns of member k equal what collect(member k, noise_seed=noise_seeds[k]) returns on an env
-        of EM envs at env_offset + k EM with the same seed, bit for bit.  float32, n_traffic in {1, 2, 3, 4, 8}."""
+        of EM envs at env_offset + k EM with the same seed, bit for bit.  float32, n_traffic in {1, 2, 3, 4, 8};
+        group=True (n_traffic in {8, 16, 32, 64}: acas2d_collect_set_group_f32) as in collect(): the columns of member k
+        then equal collect(member k, group=True)."""
         if not self.auto_reset:
             raise RuntimeError("collect_set() has VecEnv auto-reset semantics; construct with auto_reset=True")
         K = int(policy_set.n_members)
-        self.check_member_split(K)
+        self.check_member_split(K, group=group)
+        fn = self._lib.acas2d_collect_set_group_f32 if group else self._lib.acas2d_collect_set_f32
         T, E, D, dev = int(n_steps), self.num_envs, self.obs_dim, self.device
         if policy_set.obs_dim != D:
             raise ValueError("the set's members must be SB3 MlpPolicy actor-critics %d -> 64 -> 64 -> 1, got obs_dim %d"
@@ -541,7 +552,7 @@ class ACAS2DVecEnv:
                                 ptr(out["outcome"]), None, ptr(out["episode_return"]), ptr(out["episode_steps"]))
             ac = native.CActorCritic(native.CPolicy(*[ptr(t) for t in keep[:6]], 64, 0), *[ptr(t) for t in keep[6:]],
                                      ptr(out["values"]), ptr(out["logp"]), 0, int(noise_step) & 0xFFFFFFFF, 0)
-            native.check(self._lib.acas2d_collect_set_f32(
+            native.check(fn(
                 C.byref(self._ccfg), C.byref(self._cstate), C.byref(io), C.byref(ac), K, ptr(keys), ptr(out["obs"][0]), T,
                 self.seed_value, self.env_offset, E, self.n_traffic, self._stream()))
             self._obs.copy_(out["obs"][T])            # the observation the NEXT actions would be drawn on

@@ -285,8 +285,8 @@ int acas2d_collect_f64(const Acas2dConfig *cfg, const Acas2dState *state, const 
  * The slice of member k equals acas2d_collect_f32 run alone on those envs -- policy k, noise_seed = noise_seeds[k],
  * env_offset + k EM, the same env seed -- bit for bit: per step it is that launch's code.  Rejected with ACAS2D_EINVAL
  * before anything is launched: n_members < 1, an n_envs that is not K x a multiple of 64, a NULL stack or noise_seeds,
- * and any n_traffic outside {1, 2, 3, 4, 8}.  Out of scope: float64, and the group-cooperative launches of n_traffic
- * 16 / 32 / 64 (acas2d_collect_group_f32 collects one learner per call).
+ * and any n_traffic outside {1, 2, 3, 4, 8}: the group-cooperative launches of n_traffic 16 / 32 / 64 are
+ * acas2d_collect_set_group_f32, below.  Out of scope: float64.
  */
 int acas2d_collect_set_f32(const Acas2dConfig *cfg, const Acas2dState *state, const Acas2dStepIO *io,
                            const Acas2dActorCritic *ac, int32_t n_members, const uint64_t *noise_seeds,
@@ -341,6 +341,24 @@ int acas2d_evaluate_policies_group_f32(const Acas2dConfig *cfg, const Acas2dStat
                                        const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
                                        int32_t n_traffic, uint8_t *outcome, int32_t *steps, void *total_reward,
                                        void *stream);
+
+/*
+ * acas2d_collect_set_group_f32: acas2d_collect_set_f32 for n_traffic in {8, 16, 32, 64}, float32 -- the same arguments,
+ * layouts and outputs.  Additive to ABI 7.  The launch is acas2d_collect_group_f32's (the env's G lanes of the packed work
+ * shapes (4,2) (4,4) (4,8) (4,16) evaluate the two networks together) with the member found per wavefront: a wavefront
+ * holds 64 / G envs, and the rule n_envs = K x a multiple of 64 is kept as it stands (64 / G would do for this kernel;
+ * acas2d_gae_f32 and the trainers need 64 for K > 1, and one rule is easier to state).
+ * The columns of member k equal acas2d_collect_group_f32 run alone on those envs -- policy k, noise_seed = noise_seeds[k],
+ * env_offset + k EM, the same env seed -- bit for bit; at n_traffic = 8 they also equal acas2d_collect_set_f32's.
+ * The stacks w1t, b1, w2t, b2, v1t, vb1, v2t, vb2 must be 16-byte aligned (a member's slice then is: the member strides are
+ * multiples of 256 bytes).  Rejected with ACAS2D_EINVAL before anything is launched: what the sibling rejects, a misaligned
+ * stack, and any n_traffic outside the four (n_traffic in {1, 2, 3, 4} belongs to acas2d_collect_set_f32).  There is no
+ * float64 variant.
+ */
+int acas2d_collect_set_group_f32(const Acas2dConfig *cfg, const Acas2dState *state, const Acas2dStepIO *io,
+                                 const Acas2dActorCritic *ac, int32_t n_members, const uint64_t *noise_seeds,
+                                 const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset, int64_t n_envs,
+                                 int32_t n_traffic, void *stream);
 
 /*
  * acas2d_ppo_update_f32:ONE minibatch update of SB3 1.1.0's PPO.train() for the MlpPolicy actor-critic (the update
@@ -411,8 +429,8 @@ int acas2d_ppo_wide_lds_bytes(int32_t obs_dim);
  * added to grad[k] with float atomics, whose order is not fixed, so two runs agree to float32 rounding of the sums (~1e-7
  * relative), not bit for bit.  LDS as the sibling's (70 - 75 KB per gradient workgroup), checked against each device at
  * its first call.  Every pointer is required, n_members in [1, 65535], n_rows >= 2, obs_dim in {8, 11, 14, 17, 29}
- * (n_traffic 1, 2, 3, 4, 8); anything else is ACAS2D_EINVAL before a launch.  Out of scope: float64, the wide widths
- * (acas2d_ppo_update_wide_f32 takes one learner per call), members with different n_rows.
+ * (n_traffic 1, 2, 3, 4, 8); anything else is ACAS2D_EINVAL before a launch (the wide widths 53, 101, 197 are
+ * acas2d_ppo_update_wide_set_f32, below).  Out of scope: float64, members with different n_rows.
  */
 typedef struct Acas2dPpoUpdateSet {
     void *actor_w1, *actor_b1, *actor_w2, *actor_b2, *actor_w3, *actor_b3;       /* [K][...] stacks */
@@ -429,6 +447,25 @@ typedef struct Acas2dPpoUpdateSet {
 } Acas2dPpoUpdateSet;
 
 int acas2d_ppo_update_set_f32(const Acas2dPpoUpdateSet *u, void *stream);
+
+/*
+ * acas2d_ppo_update_wide_set_f32: acas2d_ppo_update_set_f32 for obs_dim in {53, 101, 197} (n_traffic 16, 32, 64), float32.
+ * Additive to ABI 7.  The same struct and the same layouts: [K][...] parameter stacks in torch layouts, grad / adam_m /
+ * adam_v float[K][acas2d_ppo_workspace_floats(obs_dim)], adam_step int32[K], stats float[K][8], hyper DEVICE float[K][8],
+ * ONE flat rollout buffer shared by all members with idx int64[K][n_rows] naming member k's rows of it, apply == 0 for the
+ * raw gradients.  The gradient launch has the grid (ceil(n_rows / 64), 2, K) with 256 threads and runs
+ * acas2d_ppo_update_wide_f32's arithmetic per member (four waves per 64 samples and network); the apply launch is
+ * acas2d_ppo_update_set_f32's, one 1 024-thread workgroup per member.  With one workgroup per network (n_rows <= 64) every
+ * gradient entry receives one atomic add, and member k's result equals acas2d_ppo_update_wide_f32 on that member bit for bit.
+ * Run-to-run: otherwise, as for the siblings, the per-workgroup partial gradients are added to grad[k] with float atomics,
+ * whose order is not fixed, so two runs agree to float32 rounding of the sums (~1e-7 relative), not bit for bit.  The
+ * gradient kernel asks for acas2d_ppo_wide_lds_bytes(obs_dim) bytes of LDS per workgroup (79 / 91 / 115 KB; gfx950 has
+ * 160 KB), checked against each device at its first call (ACAS2D_EINVAL where it does not fit).
+ * Every pointer is required, n_members in [1, 65535], n_rows >= 2; any other obs_dim is ACAS2D_EINVAL before a launch
+ * ({8, 11, 14, 17, 29} belong to acas2d_ppo_update_set_f32, and the message says so).  Out of scope: float64, members with
+ * different n_rows.
+ */
+int acas2d_ppo_update_wide_set_f32(const Acas2dPpoUpdateSet *u, void *stream);
 
 /*
  * acas2d_gae_f32: what lies between acas2d_collect_* and acas2d_ppo_update_* in a PPO iteration, in ONE launch -- the

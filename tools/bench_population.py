@@ -5,7 +5,9 @@ process: aggregate env-steps per second of learn(), and where an iteration's tim
 Per K: both variants are constructed and warmed up (one iteration each), then timed in ALTERNATING windows of --iters
 iterations, host clock around work that ends in a synchronise; reported: the median of --windows windows and their
 spread (min, max).  Each member / solo run has --envs envs x --traffic aircraft, --n-steps steps per iteration and
-minibatches of --batch-size; fused collector and fused update in both variants.
+minibatches of --batch-size; fused collector and fused update in both variants.  At --traffic 16, 32, 64 the population
+is PopulationTrainer(group=True) (the group-cooperative set collector, the wide set update); the sequential PPOTrainer
+takes the group and wide launches by itself.
 
 Then, per K, three single operations (median of --reps timings, each ended by a synchronise):
   collect_set   one ACAS2DVecEnv.collect_set() launch of --n-steps steps (with the copy of the first observation)
@@ -34,6 +36,7 @@ ap.add_argument("--envs", type=int, default=1024, help="envs per member / solo r
 ap.add_argument("--traffic", type=int, default=1)
 ap.add_argument("--n-steps", type=int, default=512)
 ap.add_argument("--batch-size", type=int, default=4096)
+ap.add_argument("--n-epochs", type=int, default=None, help="epochs per iteration (default: PPOConfig's)")
 ap.add_argument("--iters", type=int, default=1, help="iterations per timed window")
 ap.add_argument("--windows", type=int, default=7)
 ap.add_argument("--reps", type=int, default=7)
@@ -65,10 +68,13 @@ def spread(xs):
     return {"median": statistics.median(xs), "min": min(xs), "max": max(xs)}
 
 
-cfg = lambda seed: g.PPOConfig(seed=seed, n_steps=args.n_steps, batch_size=args.batch_size)  # noqa: E731
+epochs_kw = {} if args.n_epochs is None else {"n_epochs": args.n_epochs}
+cfg = lambda seed: g.PPOConfig(seed=seed, n_steps=args.n_steps, batch_size=args.batch_size, **epochs_kw)  # noqa: E731
 per_it = args.n_steps * args.envs                     # one member's env steps per iteration
+GROUP = args.traffic in g.ppo.GROUP_TRAFFIC
+group_kw = {"group": True} if GROUP else {}
 shape = {"envs_per_member": args.envs, "n_traffic": args.traffic, "n_steps": args.n_steps, "batch_size": args.batch_size,
-         "gae": args.gae, "iters_per_window": args.iters, "windows": args.windows, "device": torch.cuda.get_device_name(0)}
+         "n_epochs": cfg(0).n_epochs, "gae": args.gae, "iters_per_window": args.iters, "windows": args.windows, "device": torch.cuda.get_device_name(0)}
 
 # the baseline's solo trainers: the parent path, one learner each, built once and reused for every K
 solos = []
@@ -80,7 +86,7 @@ for k in range(max(args.members)):
 
 for K in args.members:
     venv = g.ACAS2DVecEnv(K * args.envs, args.traffic, device=DEV, seed=13)
-    pop = g.PopulationTrainer(venv, [cfg(13 + k) for k in range(K)], gae=args.gae)
+    pop = g.PopulationTrainer(venv, [cfg(13 + k) for k in range(K)], gae=args.gae, **group_kw)
     pop.learn(per_it, log=None)                       # warm-up
 
     def run_population():
@@ -104,7 +110,7 @@ for K in args.members:
 
     # ---- the single operations
     out = pop._fused_out
-    t_collect = [timed(lambda: venv.collect_set(pop.policy_set, args.n_steps, pop.noise_seeds, noise_step=0, out=out))
+    t_collect = [timed(lambda: venv.collect_set(pop.policy_set, args.n_steps, pop.noise_seeds, noise_step=0, out=out, **group_kw))
                  for _ in range(args.reps)]
     fu = pop._fused_update
     n = args.n_steps * args.envs

@@ -7,7 +7,8 @@ on the reference's 100 test episodes (testing_main.py; the reference's own polic
     python tools/ppo_seed_sweep.py --sets default lr1e-4 --seeds 13 14 15 --timesteps 3e7
 
 --population trains the seeds of a set as ONE population (ppo.PopulationTrainer: member k on its own --envs envs of one
-env of len(seeds) x --envs) and scores them in one launch.  Opt-in: the sequential path is the default (DESIGN.md 4.2e
+env of len(seeds) x --envs; at --traffic 16, 32, 64 with group=True: the group-cooperative collector and the wide update)
+and scores them in one launch.  Opt-in: the sequential path is the default (DESIGN.md 4.2e
 says what was measured).  Member k plays the envs at offset k x --envs, so its episodes are not the solo run's: the
 runs compare as seeds do, not bit for bit.
 """
@@ -44,6 +45,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--sets", nargs="+", default=["default"])
 ap.add_argument("--seeds", type=int, nargs="+", default=[13, 14, 15])
 ap.add_argument("--envs", type=int, default=1024)
+ap.add_argument("--traffic", type=int, default=1, help="traffic aircraft (the 100 scored episodes are then drawn for that count)")
 ap.add_argument("--timesteps", type=float, default=3.0e7)
 ap.add_argument("--out", default=None)
 ap.add_argument("--population", action="store_true", help="one PopulationTrainer per set over the seeds")
@@ -67,17 +69,20 @@ def emit(rec):
         sink.flush()
 
 
-own, trf, goal = H.parity_reset_states(g.ACAS2DConfig(), 13, 0, 100)
+N = args.traffic
+GROUP = N in g.ppo.GROUP_TRAFFIC                       # the group-cooperative launches, in every trainer and evaluation
+own, trf, goal = H.parity_reset_states(g.ACAS2DConfig(n_traffic=N), 13, 0, 100)
+score = dict(dtype=torch.float32, config=g.ACAS2DConfig(n_traffic=N), group=True) if GROUP else {}
 for name in args.sets:
     kw = {**dict(n_steps=256, batch_size=4096), **SETS[name]}
     goals = []
     if args.population:
         t0 = time.time()
         K = len(args.seeds)
-        venv = g.ACAS2DVecEnv(K * args.envs, 1, device="cuda:0", dtype=torch.float32, seed=13)
-        pop = g.PopulationTrainer(venv, [g.PPOConfig(seed=seed, **kw) for seed in args.seeds], gae=args.gae)
+        venv = g.ACAS2DVecEnv(K * args.envs, N, device="cuda:0", dtype=torch.float32, seed=13)
+        pop = g.PopulationTrainer(venv, [g.PPOConfig(seed=seed, **kw) for seed in args.seeds], gae=args.gae, group=GROUP)
         hist = pop.learn(int(args.timesteps), log=None)
-        out = g.evaluate_policies_fused(pop.policy_set.actor_weights(), own, trf, goal)
+        out = g.evaluate_policies_fused(pop.policy_set.actor_weights(), own, trf, goal, **score)
         wall = time.time() - t0
         for k, seed in enumerate(args.seeds):
             last = [r for r in hist if r["member"] == k and not r.get("eval")][-1]
@@ -91,10 +96,10 @@ for name in args.sets:
         del pop, venv
     for seed in ([] if args.population else args.seeds):
         t0 = time.time()
-        venv = g.ACAS2DVecEnv(args.envs, 1, device="cuda:0", dtype=torch.float32, seed=13)
+        venv = g.ACAS2DVecEnv(args.envs, N, device="cuda:0", dtype=torch.float32, seed=13)
         tr = g.PPOTrainer(venv, g.PPOConfig(seed=seed, **kw), collector="fused", updater="fused", gae=args.gae)
         hist = tr.learn(int(args.timesteps), log=None)
-        out = g.evaluate_policy_fused(tr.policy, own, trf, goal)
+        out = g.evaluate_policy_fused(tr.policy, own, trf, goal, **score)
         rec = {"set": name, "config": kw, "seed": seed, "timesteps": int(args.timesteps), "wall_s": time.time() - t0,
                "train_ep_rew_mean_last": hist[-1].get("ep_rew_mean"), "std": hist[-1].get("std"),
                "eval_mean_return": float(out["total_reward"].mean()), "eval_mean_steps": float(out["steps"].mean()),

@@ -35,7 +35,8 @@ ap.add_argument("--seed", type=int, default=13)
 ap.add_argument("--population", type=int, default=0, metavar="K",
                 help="train K learners with the seeds --seed ... --seed + K - 1 side by side in one process "
                      "(ppo.PopulationTrainer: one collection launch and two launches per minibatch for all K; each member gets "
-                     "--envs envs; float32, --traffic 1, 2, 3, 4, 8, fused collector and update)")
+                     "--envs envs; float32, --traffic 1, 2, 3, 4, 8 and -- PopulationTrainer(group=True): the group-cooperative "
+                     "collector and the wide update -- 16, 32, 64; fused collector and update)")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 # "kernel" where learn() with it beat gae="torch" by more than both variants' spreads (the fused-collector
@@ -57,7 +58,7 @@ if args.population:
     K = args.population
     venv = g.ACAS2DVecEnv(K * args.envs, args.traffic, device="cuda:0", dtype=torch.float32, seed=13)
     pop = g.PopulationTrainer(venv, [g.PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, seed=args.seed + k)
-                                     for k in range(K)], gae=args.gae)
+                                     for k in range(K)], gae=args.gae, group=args.traffic in g.ppo.GROUP_TRAFFIC)
     pop.learn(int(args.timesteps), log=lambda r: print(json.dumps(r), flush=True))
     if args.traffic == 1:
         own, trf, goal = H.parity_reset_states(g.ACAS2DConfig(), 13, 0, 100)
