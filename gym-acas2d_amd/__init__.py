@@ -13,8 +13,8 @@ from .vec_env import ACAS2DVecEnv, LazyInfos                         # noqa: F40
 from .env import ACAS2DEnv, GameView, register_with_gym              # noqa: F401
 from .policy import (SB3ActorPolicy, load_sb3_policy, save_sb3_policy, evaluate_policy, evaluate_policy_fused,  # noqa: F401
                      evaluate_policies_fused)
-from .ppo import (ActorCritic, ActorCriticSet, FusedUpdate, FusedUpdateSet, PopulationTrainer, PPOConfig, PPOTrainer,  # noqa: F401
-                  compute_gae, gae_constants, gae_fused, ppo_loss)
+from .ppo import (ActorCritic, ActorCriticSet, FusedUpdate, FusedUpdateSet, PBTConfig, PBTTrainer, PopulationTrainer,  # noqa: F401
+                  PPOConfig, PPOTrainer, compute_gae, gae_constants, gae_fused, member_episodes, population_exploit, ppo_loss)
 
 register_with_gym()
 

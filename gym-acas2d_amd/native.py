@@ -65,6 +65,24 @@ class CGae(C.Structure):
         [("n_envs", C.c_int64)] + [(n, C.c_int32) for n in ("n_steps", "n_members", "obs_dim", "_pad")]
 
 
+class CMemberEpisodes(C.Structure):
+    """struct Acas2dMemberEpisodes: per-member episode statistics of a collection (include/acas2d.h)."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "done", "outcome", "ep_return", "ep_steps", "ep_count", "ep_outcomes", "ep_steps_sum", "ep_return_sum", "score")] + \
+        [("n_envs", C.c_int64), ("n_steps", C.c_int32), ("n_members", C.c_int32)]
+
+
+class CPopulationExploit(C.Structure):
+    """struct Acas2dPopulationExploit: truncation selection, copy and perturbation among K stacked learners
+    (include/acas2d.h)."""
+    _fields_ = [(n, C.c_void_p) for n in (
+        "actor_w1", "actor_b1", "actor_w2", "actor_b2", "actor_w3", "actor_b3", "critic_w1", "critic_b1", "critic_w2",
+        "critic_b2", "critic_w3", "critic_b3", "log_std", "adam_m", "adam_v", "adam_step", "hyper", "score", "donor")] + \
+        [(n, C.c_int32) for n in ("n_members", "obs_dim", "n_replace")] + \
+        [("generation", C.c_uint32), ("seed", C.c_uint64), ("perturb_mask", C.c_uint32), ("factor_lo", C.c_float),
+         ("factor_hi", C.c_float), ("lo", C.c_float * 8), ("hi", C.c_float * 8), ("_pad", C.c_uint32)]
+
+
 EXPORTS = ("acas2d_abi_version", "acas2d_config_size", "acas2d_state_size", "acas2d_last_error", "acas2d_step_f32",
            "acas2d_step_f64", "acas2d_rollout_f32", "acas2d_rollout_f64", "acas2d_rollout_policy_f32",
            "acas2d_rollout_policy_f64", "acas2d_collect_f32", "acas2d_collect_f64", "acas2d_ppo_workspace_floats",
@@ -73,7 +91,8 @@ EXPORTS = ("acas2d_abi_version", "acas2d_config_size", "acas2d_state_size", "aca
            "acas2d_rollout_policy_group_f32", "acas2d_collect_group_f32", "acas2d_evaluate_policies_group_f32",
            "acas2d_ppo_update_wide_f32", "acas2d_ppo_wide_lds_bytes", "acas2d_collect_set_f32", "acas2d_ppo_update_set_f32",
            "acas2d_gae_f32", "acas2d_gae_size", "acas2d_gae_pipeline_depth", "acas2d_collect_set_group_f32",
-           "acas2d_ppo_update_wide_set_f32")
+           "acas2d_ppo_update_wide_set_f32", "acas2d_member_episodes_f32", "acas2d_member_episodes_size",
+           "acas2d_population_exploit_f32", "acas2d_population_exploit_size")
 
 
 class NativeLibraryError(RuntimeError):
@@ -154,6 +173,12 @@ def lib():
     L.acas2d_gae_f32.argtypes = [C.POINTER(CGae), C.c_void_p]
     L.acas2d_gae_size.restype = C.c_size_t
     L.acas2d_gae_pipeline_depth.restype = C.c_int
+    L.acas2d_member_episodes_f32.restype = C.c_int
+    L.acas2d_member_episodes_f32.argtypes = [C.POINTER(CMemberEpisodes), C.c_void_p]
+    L.acas2d_member_episodes_size.restype = C.c_size_t
+    L.acas2d_population_exploit_f32.restype = C.c_int
+    L.acas2d_population_exploit_f32.argtypes = [C.POINTER(CPopulationExploit), C.c_void_p]
+    L.acas2d_population_exploit_size.restype = C.c_size_t
     L.acas2d_ppo_workspace_floats.restype = C.c_int
     L.acas2d_ppo_workspace_floats.argtypes = [C.c_int32]
     for name in ("acas2d_ppo_update_f32", "acas2d_ppo_update_wide_f32"):
@@ -181,6 +206,10 @@ def lib():
         raise NativeLibraryError("Acas2dState layout mismatch: %d != %d" % (L.acas2d_state_size(), C.sizeof(CState)))
     if L.acas2d_gae_size() != C.sizeof(CGae):
         raise NativeLibraryError("Acas2dGae layout mismatch: %d != %d" % (L.acas2d_gae_size(), C.sizeof(CGae)))
+    for name, twin in (("member_episodes", CMemberEpisodes), ("population_exploit", CPopulationExploit)):
+        size = getattr(L, "acas2d_%s_size" % name)()
+        if size != C.sizeof(twin):
+            raise NativeLibraryError("%s layout mismatch: %d != %d" % (twin.__name__, size, C.sizeof(twin)))
     _lib = L
     return L
 

@@ -893,7 +893,8 @@ class PopulationTrainer:
     (EM = num_envs / K), collects with its own actor-critic and noise key, and is updated on its own rows with its own
     hyper-parameters -- one collection launch (ACAS2DVecEnv.collect_set), two launches per minibatch (FusedUpdateSet) and
     one evaluation launch (evaluate_policies_fused) for all K, where K PPOTrainer(collector="fused", updater="fused") runs
-    take K times as many.  There is no exchange between members: no exploit / explore step, K separate runs.
+    take K times as many.  There is no exchange between members: no exploit / explore step, K separate runs
+    (PBTTrainer, below, adds one).
     n_traffic in {1, 2, 3, 4, 8}; group=True: n_traffic in {8, 16, 32, 64}, with the group-cooperative launches
     (collect_set(group=True), evaluate_policies_fused(group=True)) and, at 16 / 32 / 64, the wide update.
 
@@ -1109,3 +1110,181 @@ class PopulationTrainer:
                 for k in range(K):
                     books[k].checkpoint(self.num_timesteps)
         return history
+
+
+# ---- population-based training: score, exploit and explore on the device (csrc/acas2d_pbt.hip) -------------------------
+def member_episodes(done, outcome, episode_return, episode_steps, n_members, acc=None):
+    """The episodes that ended in a collection, summed per member in ONE launch (acas2d_member_episodes_f32).  `done`
+    (bool or uint8), `outcome` (uint8), `episode_return` (float32) and `episode_steps` (int32) are the collector's [T, E]
+    outputs as they lie, member k owning the columns [k EM, (k + 1) EM); what lies where `done` is 0 reaches nothing.
+    ADDS to `acc` -- {"count": int64 [K], "outcomes": int64 [K, 4], "steps": int64 [K] (step() calls), "return_sum":
+    float64 [K]} -- and overwrites acc["score"], float32 [K]: the mean return of everything added so far, NaN where no
+    episode has ended.  acc=None starts a zeroed window.  Returns acc.  No host synchronisation; the same inputs give the
+    same bits."""
+    import ctypes as C
+    from . import native
+    K = int(n_members)
+    dev = done.device
+    if done.dtype == torch.bool:
+        done = done.view(torch.uint8)
+    want = ((done, torch.uint8), (outcome, torch.uint8), (episode_return, torch.float32), (episode_steps, torch.int32))
+    if done.dim() != 2 or any(t.shape != done.shape or t.dtype != dt or not t.is_contiguous() or t.device != dev
+                              for t, dt in want):
+        raise ValueError("member_episodes takes contiguous [T, E] tensors on one device: done bool / uint8, outcome uint8, "
+                         "episode_return float32, episode_steps int32")
+    if acc is None:
+        z = lambda *shape, dt=torch.int64: torch.zeros(*shape, dtype=dt, device=dev)  # noqa: E731
+        acc = {"count": z(K), "outcomes": z(K, 4), "steps": z(K), "return_sum": z(K, dt=torch.float64),
+               "score": torch.full((K,), float("nan"), dtype=torch.float32, device=dev)}
+    shapes = {"count": (K,), "outcomes": (K, 4), "steps": (K,), "return_sum": (K,), "score": (K,)}
+    if any(tuple(acc[n].shape) != s or not acc[n].is_contiguous() or acc[n].device != dev for n, s in shapes.items()):
+        raise ValueError("member_episodes: acc does not hold the accumulators of %d members on %s" % (K, dev))
+    p = lambda t: t.data_ptr()  # noqa: E731
+    T, E = done.shape
+    m = native.CMemberEpisodes(p(done), p(outcome), p(episode_return), p(episode_steps), p(acc["count"]), p(acc["outcomes"]),
+                               p(acc["steps"]), p(acc["return_sum"]), p(acc["score"]), E, T, K)
+    native.check(native.lib().acas2d_member_episodes_f32(C.byref(m), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return acc
+
+
+PBT_PERTURB = ("learning_rate", "clip_range", "ent_coef")
+PBT_BOUNDS = {"learning_rate": (1e-6, 1e-2), "clip_range": (0.02, 0.5), "ent_coef": (0.0, 0.1)}
+
+
+def _hyper_slots(names):
+    unknown = [n for n in names if n not in HYPER_SLOTS]
+    if unknown:
+        raise ValueError("%s: not a slot of the hyper row %s" % (unknown, HYPER_SLOTS))
+    return [HYPER_SLOTS.index(n) for n in names]
+
+
+def population_exploit(policy_set, fused_update_set, score, n_replace, generation, seed, perturb=PBT_PERTURB,
+                       factors=(0.8, 1.2), bounds=PBT_BOUNDS):
+    """The exploit / explore step of population-based training in ONE launch (acas2d_population_exploit_f32): each of the
+    `n_replace` members with the worst `score` (float32 device tensor [K]; NaN is worst, ties go to the smaller index)
+    draws one of the `n_replace` best and, where that one is strictly better, becomes a bit copy of it -- the 13
+    parameter stacks of `policy_set`, the Adam moments and step of `fused_update_set` -- with its `hyper` row, the slots
+    named in `perturb` multiplied by one of `factors` (one random bit per slot) and clamped into `bounds[name]`.
+    (generation, seed) key the draws.  Returns `donor`, int32 device tensor [K]: whom member k was copied from, k where
+    nothing changed.  No host decision and no synchronisation."""
+    import ctypes as C
+    from . import native
+    fu, K = fused_update_set, policy_set.n_members
+    if fu.policy_set is not policy_set:
+        raise ValueError("population_exploit: fused_update_set updates another ActorCriticSet")
+    if score.dtype != torch.float32 or tuple(score.shape) != (K,) or not score.is_contiguous() or score.device != fu.device:
+        raise ValueError("population_exploit: score must be a contiguous float32 tensor [%d] on %s" % (K, fu.device))
+    mask, lo, hi = 0, [-math.inf] * 8, [math.inf] * 8
+    for name, s in zip(perturb, _hyper_slots(perturb)):
+        if name not in bounds:
+            raise ValueError("population_exploit: no bounds for the perturbed %r" % name)
+        mask |= 1 << s
+        lo[s], hi[s] = (float(b) for b in bounds[name])
+    donor = torch.empty(K, dtype=torch.int32, device=fu.device)
+    p = lambda t: t.data_ptr()  # noqa: E731
+    x = native.CPopulationExploit(*[p(policy_set.params[n]) for n in PARAM_NAMES], p(fu.m), p(fu.v), p(fu.step_count),
+                                  p(fu.hyper), p(score), p(donor), K, policy_set.obs_dim, int(n_replace),
+                                  int(generation) & 0xffffffff, int(seed) & (2 ** 64 - 1), mask, float(factors[0]),
+                                  float(factors[1]), (C.c_float * 8)(*lo), (C.c_float * 8)(*hi), 0)
+    native.check(native.lib().acas2d_population_exploit_f32(
+        C.byref(x), C.c_void_p(torch.cuda.current_stream(fu.device).cuda_stream)))
+    return donor
+
+
+@dataclasses.dataclass
+class PBTConfig:
+    """When and how a PBTTrainer exchanges between its members (Jaderberg et al. 2017, truncation selection): every
+    `ready_every` iterations the floor(fraction x K) members with the worst mean return of the window each copy one of
+    the equally many best and perturb the copied `perturb` hyper-parameters by one of `factors` (the paper's 0.8 / 1.2),
+    clamped into `bounds`."""
+    ready_every: int
+    fraction: float = 0.25
+    factors: tuple = (0.8, 1.2)
+    perturb: tuple = PBT_PERTURB
+    bounds: dict = dataclasses.field(default_factory=lambda: dict(PBT_BOUNDS))
+    seed: int = 0
+
+    def __post_init__(self):
+        if int(self.ready_every) != self.ready_every or self.ready_every < 1:
+            raise ValueError("PBTConfig.ready_every counts iterations: an integer >= 1, got %r" % (self.ready_every,))
+        if not 0.0 <= self.fraction <= 1.0:
+            raise ValueError("PBTConfig.fraction is a share of the population, in [0, 1], got %r" % (self.fraction,))
+        if len(self.factors) != 2 or not all(math.isfinite(f) and f > 0 for f in self.factors):
+            raise ValueError("PBTConfig.factors must be two finite positive numbers, got %r" % (self.factors,))
+        for name, s in zip(self.perturb, _hyper_slots(self.perturb)):
+            if name not in self.bounds or not self.bounds[name][0] <= self.bounds[name][1]:
+                raise ValueError("PBTConfig.bounds needs lo <= hi for the perturbed %r" % name)
+
+    def n_replace(self, n_members):
+        """floor(fraction x K); a ValueError where 2 x n_replace > K."""
+        R = int(math.floor(self.fraction * n_members))
+        if 2 * R > n_members:
+            raise ValueError("PBTConfig: 2 x n_replace <= K is the rule (donors and recipients are disjoint); fraction = %r "
+                             "gives n_replace = %d of K = %d" % (self.fraction, R, n_members))
+        return R
+
+
+class PBTTrainer(PopulationTrainer):
+    """PopulationTrainer with the exchange between members that makes a population more than a seed sweep
+    (population-based training, Jaderberg et al. 2017), scored and decided on the device:
+      collect()   the parent's, followed by ONE member_episodes launch on the b_* buffers: `window` accumulates every
+                  member's ended episodes, window["score"] is its mean return;
+      update()    the parent's; every `pbt.ready_every`-th call is followed by exploit();
+      exploit()   ONE population_exploit launch with the window's score, generation = the number of exploits so far and
+                  pbt.seed; zeroes the window and appends one record per member to `history`:
+                  {"member", "exploit": donor or None, "hyper": the member's row (HYPER_SLOTS), "score", "timesteps",
+                  "generation"}.  The read-back of donor and hyper (K x 9 numbers) follows update()'s own read of the
+                  losses.
+    learn() is the parent's.  A recipient takes parameters, Adam state and hyper row; it keeps its envs, its noise key and
+    its minibatch generator, so twins diverge.  gamma and gae_lambda live outside the hyper row and are not exchanged:
+    they must be equal across members.  fraction = 0 is PopulationTrainer bit for bit.  group=True and gae="kernel" as
+    the parent's."""
+
+    def __init__(self, venv, configs, pbt, gae=None, group=False):
+        configs = list(configs)
+        for f in ("gamma", "gae_lambda"):
+            if len({getattr(c, f) for c in configs}) > 1:
+                raise ValueError("PBTTrainer needs the same %s for every member: it lives outside the hyper row and is not "
+                                 "exchanged by an exploit step, got %s" % (f, [getattr(c, f) for c in configs]))
+        self.pbt = pbt
+        self.n_replace = pbt.n_replace(len(configs))
+        super().__init__(venv, configs, gae=gae, group=group)
+        # built now, not at the first update: an exploit before it must find the moments and the hyper row
+        self._fused_update = FusedUpdateSet(self.policy_set, self.configs, self.b_obs, self.b_act, self.b_logp, self.b_adv,
+                                            self.b_ret)
+        self.window = None
+        self.generation = 0
+        self._updates = 0
+
+    @property
+    def hyper(self):
+        """The members' current hyper rows: float32 device tensor [K, 8] (HYPER_SLOTS)."""
+        return self._fused_update.hyper
+
+    def collect(self):
+        super().collect()
+        self.window = member_episodes(self.b_done, self.b_outcome, self.b_epret, self.b_eplen, self.K, acc=self.window)
+
+    def update(self):
+        stats = super().update()
+        self._updates += 1
+        if self._updates % self.pbt.ready_every == 0:
+            self.exploit()
+        return stats
+
+    def exploit(self):
+        """One exploit / explore step on the window's score; returns the members' records (also appended to history)."""
+        if self.window is None:
+            raise RuntimeError("PBTTrainer.exploit() needs a collect() first: there is no score yet")
+        pbt, w = self.pbt, self.window
+        donor = population_exploit(self.policy_set, self._fused_update, w["score"], self.n_replace, self.generation,
+                                   pbt.seed, perturb=pbt.perturb, factors=pbt.factors, bounds=pbt.bounds)
+        donor, hyper, score = donor.cpu().tolist(), self.hyper.cpu().tolist(), w["score"].cpu().tolist()
+        for n in ("count", "outcomes", "steps", "return_sum"):
+            w[n].zero_()
+        w["score"].fill_(float("nan"))
+        recs = [{"member": k, "exploit": None if donor[k] == k else donor[k], "hyper": hyper[k], "score": score[k],
+                 "timesteps": self.num_timesteps, "generation": self.generation} for k in range(self.K)]
+        self.history.extend(recs)
+        self.generation += 1
+        return recs

@@ -522,6 +522,85 @@ size_t acas2d_gae_size(void);         /* sizeof(Acas2dGae): layout check for bin
 int acas2d_gae_pipeline_depth(void);  /* rows of loads in flight per lane (16) */
 
 /*
+ * acas2d_member_episodes_f32: the episodes that ended during a collection of K members, summed per member in ONE launch
+ * -- the score of population-based training (Jaderberg et al. 2017).  Additive to ABI 7.  Inputs are the [T][E] outputs of
+ * acas2d_collect_* as they lie, member k owning the columns [k EM, (k + 1) EM), EM = n_envs / K.  ep_return and ep_steps
+ * are defined only where done != 0; whatever lies at the other positions (NaN, inf, INT32_MIN) reaches no result.
+ * The launch ADDS to the accumulators (device memory; zero them to start a new window):
+ *   ep_count       int64[K]      episodes ended
+ *   ep_outcomes    int64[K][4]   of these, by outcome code 0 .. 3
+ *   ep_steps_sum   int64[K]      the sum of ep_steps - 1 (ep_steps counts step() calls + 1)
+ *   ep_return_sum  double[K]     the sum of the float returns, each widened to double and added as it is (a NaN return
+ *                                at a done position propagates, to that member's sum only)
+ * and OVERWRITES score float[K] = (float)(ep_return_sum[k] / ep_count[k]) from the totals after adding: the mean return of
+ * the window, NaN where no episode has ended.
+ * One 1 024-thread workgroup per member adds in a fixed order (in the lane, in the wave, across the waves) without
+ * atomics: the same inputs and shapes give the same bits on every run.
+ * Rejected with ACAS2D_EINVAL before any HIP call: a NULL pointer; n_steps or n_envs < 1; n_members outside [1, 65535];
+ * K > 1 with n_envs not K x a multiple of 64 (K == 1 takes any n_envs >= 1); n_envs >= 2^31.
+ */
+typedef struct Acas2dMemberEpisodes {
+    const uint8_t *done, *outcome;   /* u8[n_steps][n_envs] */
+    const void *ep_return;           /* float[n_steps][n_envs] */
+    const int32_t *ep_steps;         /* int32[n_steps][n_envs] */
+    int64_t *ep_count, *ep_outcomes, *ep_steps_sum;   /* int64[K], int64[K][4], int64[K]: added to */
+    double *ep_return_sum;           /* double[K]: added to */
+    void *score;                     /* float[K]: overwritten */
+    int64_t n_envs;
+    int32_t n_steps, n_members;
+} Acas2dMemberEpisodes;
+
+int acas2d_member_episodes_f32(const Acas2dMemberEpisodes *m, void *stream);
+size_t acas2d_member_episodes_size(void);     /* sizeof(Acas2dMemberEpisodes): layout check for bindings */
+
+/*
+ * acas2d_population_exploit_f32: the exploit / explore step of population-based training for the K stacked learners of
+ * acas2d_ppo_update_set_f32 / acas2d_ppo_update_wide_set_f32, in ONE launch with no host decision: truncation selection on
+ * `score`, a bit copy of a better member into each of the worst, and the perturbation of the copied hyper row.  Additive
+ * to ABI 7.  The layouts are Acas2dPpoUpdateSet's at every width: obs_dim in {8, 11, 14, 17, 29, 53, 101, 197}.
+ * With K = n_members and R = n_replace (0 <= 2R <= K):
+ *   key_j   = -inf where score[j] is NaN, else score[j]
+ *   rank_k  = #{j : key_j > key_k} + #{j < k : key_j == key_k}       (a total order: ties go to the smaller index, +0 == -0)
+ *   member k is a recipient iff rank_k >= K - R; every other member gets donor[k] = k and is not touched
+ *   w       = the seven-round philox4x32 of the reset stream on counter (k, generation, 0, 0x70627431), key (seed lo, seed hi)
+ *   d       = the member with rank_d == (uint64(w.x) * R) >> 32                         (one of the R best, uniformly)
+ *   if not key_d > key_k: donor[k] = k and nothing of member k changes                  (a NaN score never donates)
+ *   else    the 13 parameter tensors, adam_m[k], adam_v[k] and adam_step[k] become member d's, bit for bit;
+ *           hyper[k][s] = hyper[d][s], and where bit s of perturb_mask is set instead
+ *           fminf(fmaxf(hyper[d][s] * f, lo[s]), hi[s]) with f = ((w.y >> s) & 1) ? factor_hi : factor_lo (one float32
+ *           multiplication; slots in the order of the hyper row: clip_range, vf_coef, ent_coef, max_grad_norm,
+ *           learning_rate, beta1, beta2, adam_eps; bits 8 .. 31 are ignored); donor[k] = d
+ * grad and stats of the update are not touched.  Donors are only read and a recipient is written by its own workgroups
+ * only, so the launch (grid 16 x K, every workgroup ranking the K scores in LDS) is race-free in place.  A member's row
+ * of adam_m / adam_v is an odd number of floats: rows are copied as 16-byte words where source and destination allow,
+ * as dwords otherwise, and nothing beyond 4-byte alignment is assumed.
+ * Rejected with ACAS2D_EINVAL before any HIP call: a NULL pointer; obs_dim outside the eight widths; n_members outside
+ * [1, 1024]; n_replace < 0 or 2 x n_replace > n_members; a factor that is not finite and positive; lo[s] > hi[s] (or a
+ * NaN bound) on a slot of perturb_mask; donor or score equal to another buffer of the struct.  n_replace == 0 launches
+ * and writes donor[k] = k only.
+ */
+typedef struct Acas2dPopulationExploit {
+    void *actor_w1, *actor_b1, *actor_w2, *actor_b2, *actor_w3, *actor_b3;       /* [K][...] stacks, as Acas2dPpoUpdateSet's */
+    void *critic_w1, *critic_b1, *critic_w2, *critic_b2, *critic_w3, *critic_b3;
+    void *log_std;                      /* float[K] */
+    void *adam_m, *adam_v;              /* float[K][acas2d_ppo_workspace_floats(obs_dim)] */
+    int32_t *adam_step;                 /* int32[K] */
+    void *hyper;                        /* device float[K][8] */
+    const void *score;                  /* float[K]: greater is better, NaN is worst */
+    int32_t *donor;                     /* int32[K] output: whom member k was copied from, k where it was not */
+    int32_t n_members, obs_dim, n_replace;
+    uint32_t generation;
+    uint64_t seed;
+    uint32_t perturb_mask;
+    float factor_lo, factor_hi;
+    float lo[8], hi[8];
+    uint32_t _pad;
+} Acas2dPopulationExploit;
+
+int acas2d_population_exploit_f32(const Acas2dPopulationExploit *x, void *stream);
+size_t acas2d_population_exploit_size(void);  /* sizeof(Acas2dPopulationExploit): layout check for bindings */
+
+/*
  * acas2d_reset_*: replaces ACAS2DEnv.reset() (environment.py:44-48 -> ACAS2DGame.__init__,
  * game.py:28-41,80-116, then observe()).  For every env with mask[e] != 0 (mask == NULL: all):
  *   do_init != 0: draw a fresh episode from the Philox stream described above

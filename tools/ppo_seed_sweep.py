@@ -11,6 +11,9 @@ env of len(seeds) x --envs; at --traffic 16, 32, 64 with group=True: the group-c
 and scores them in one launch.  Opt-in: the sequential path is the default (DESIGN.md 4.2e
 says what was measured).  Member k plays the envs at offset k x --envs, so its episodes are not the solo run's: the
 runs compare as seeds do, not bit for bit.
+--pbt (with --population) makes the population a ppo.PBTTrainer: every --pbt-every iterations the --pbt-fraction worst
+members by training return copy one of the best and perturb its learning rate, clip range and entropy coefficient
+(DESIGN.md 4.2g).  Opt-in; the members are then no longer independent seeds.
 """
 import argparse
 import json
@@ -49,10 +52,15 @@ ap.add_argument("--traffic", type=int, default=1, help="traffic aircraft (the 10
 ap.add_argument("--timesteps", type=float, default=3.0e7)
 ap.add_argument("--out", default=None)
 ap.add_argument("--population", action="store_true", help="one PopulationTrainer per set over the seeds")
+ap.add_argument("--pbt", action="store_true", help="with --population: exploit / explore between the members (ppo.PBTTrainer)")
+ap.add_argument("--pbt-every", type=int, default=8, help="iterations between two exploit steps")
+ap.add_argument("--pbt-fraction", type=float, default=0.25, help="the share of members replaced at an exploit step")
 ap.add_argument("--gae", choices=("torch", "kernel"), default=None,
                 help="kernel: GAE as one hand-written launch (ppo.gae_fused), the same bits as torch's compute_gae; the default "
                      "follows tools/bench_gae.py's measurement (DESIGN.md 4.2f): GAE_DEFAULT below")
 args = ap.parse_args()
+if args.pbt and not args.population:
+    ap.error("--pbt needs --population")
 # "kernel" where learn() with it beat gae="torch" by more than both variants' spreads (the fused-collector
 # PPOTrainer by 2 % at 512 steps and 13 % at 128, the population by 3 %); a trainer that were not faster would say "torch"
 GAE_DEFAULT = {"population": "kernel", "solo": "kernel"}
@@ -80,17 +88,26 @@ for name in args.sets:
         t0 = time.time()
         K = len(args.seeds)
         venv = g.ACAS2DVecEnv(K * args.envs, N, device="cuda:0", dtype=torch.float32, seed=13)
-        pop = g.PopulationTrainer(venv, [g.PPOConfig(seed=seed, **kw) for seed in args.seeds], gae=args.gae, group=GROUP)
+        cfgs = [g.PPOConfig(seed=seed, **kw) for seed in args.seeds]
+        if args.pbt:
+            pop = g.PBTTrainer(venv, cfgs, g.PBTConfig(ready_every=args.pbt_every, fraction=args.pbt_fraction), gae=args.gae,
+                               group=GROUP)
+        else:
+            pop = g.PopulationTrainer(venv, cfgs, gae=args.gae, group=GROUP)
         hist = pop.learn(int(args.timesteps), log=None)
         out = g.evaluate_policies_fused(pop.policy_set.actor_weights(), own, trf, goal, **score)
         wall = time.time() - t0
         for k, seed in enumerate(args.seeds):
-            last = [r for r in hist if r["member"] == k and not r.get("eval")][-1]
+            last = [r for r in hist if r["member"] == k and not r.get("eval") and "exploit" not in r][-1]
             rec = {"set": name, "config": kw, "seed": seed, "population": K, "member": k, "timesteps": int(args.timesteps),
                    "wall_s": wall, "train_ep_rew_mean_last": last.get("ep_rew_mean"), "std": last.get("std"),
                    "eval_mean_return": float(out["total_reward"][k].mean()), "eval_mean_steps": float(out["steps"][k].mean()),
                    "goal": int((out["outcome"][k] == 1).sum()), "collision": int((out["outcome"][k] == 2).sum()),
                    "timeout": int((out["outcome"][k] == 3).sum())}
+            if args.pbt:
+                steps = [r for r in hist if r["member"] == k and "exploit" in r]
+                rec.update(pbt={"every": args.pbt_every, "fraction": args.pbt_fraction, "hyper": steps[-1]["hyper"] if steps else None,
+                                "copied_from": [r["exploit"] for r in steps if r["exploit"] is not None]})
             goals.append(rec["goal"])
             emit(rec)
         del pop, venv

@@ -37,8 +37,16 @@ ap.add_argument("--population", type=int, default=0, metavar="K",
                      "(ppo.PopulationTrainer: one collection launch and two launches per minibatch for all K; each member gets "
                      "--envs envs; float32, --traffic 1, 2, 3, 4, 8 and -- PopulationTrainer(group=True): the group-cooperative "
                      "collector and the wide update -- 16, 32, 64; fused collector and update)")
+ap.add_argument("--pbt", action="store_true",
+                help="with --population: population-based training (ppo.PBTTrainer) -- every --pbt-every iterations the "
+                     "--pbt-fraction worst members by training return copy one of the best and perturb its learning rate, clip "
+                     "range and entropy coefficient, scored and decided on the device (DESIGN.md 4.2g)")
+ap.add_argument("--pbt-every", type=int, default=8, help="iterations between two exploit steps")
+ap.add_argument("--pbt-fraction", type=float, default=0.25, help="the share of members replaced at an exploit step")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
+if args.pbt and not args.population:
+    ap.error("--pbt needs --population K")
 # "kernel" where learn() with it beat gae="torch" by more than both variants' spreads (the fused-collector
 # PPOTrainer by 2 % at 512 steps and 13 % at 128, the population by 3 %); a trainer that were not faster would say "torch"
 GAE_DEFAULT = {"population": "kernel", "solo": "kernel"}
@@ -57,8 +65,12 @@ if args.population:
     import helpers as H
     K = args.population
     venv = g.ACAS2DVecEnv(K * args.envs, args.traffic, device="cuda:0", dtype=torch.float32, seed=13)
-    pop = g.PopulationTrainer(venv, [g.PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, seed=args.seed + k)
-                                     for k in range(K)], gae=args.gae, group=args.traffic in g.ppo.GROUP_TRAFFIC)
+    cfgs = [g.PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, seed=args.seed + k) for k in range(K)]
+    if args.pbt:
+        pop = g.PBTTrainer(venv, cfgs, g.PBTConfig(ready_every=args.pbt_every, fraction=args.pbt_fraction, seed=args.seed),
+                           gae=args.gae, group=args.traffic in g.ppo.GROUP_TRAFFIC)
+    else:
+        pop = g.PopulationTrainer(venv, cfgs, gae=args.gae, group=args.traffic in g.ppo.GROUP_TRAFFIC)
     pop.learn(int(args.timesteps), log=lambda r: print(json.dumps(r), flush=True))
     if args.traffic == 1:
         own, trf, goal = H.parity_reset_states(g.ACAS2DConfig(), 13, 0, 100)
