@@ -3,7 +3,8 @@
 // (grad_narrow<D>), the apply body (apply_body: norm, clip_grad_norm_, Adam), and the host helpers of the entry points
 // (pointer check, NetW pair, per-device LDS opt-in).  The __global__ kernels of acas2d_ppo.hip and acas2d_ppo_set.hip are
 // prologues in front of these bodies; those of acas2d_ppo_wide.hip and acas2d_ppo_wide_set.hip in front of grad_wide<D>
-// (acas2d_ppo_wide.hpp).
+// (acas2d_ppo_wide.hpp).  acas2d_ppo_guard.hip (target_kl) instantiates the gradient bodies with Guard = true; with the
+// default, false, they are the code they were before the guard existed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -57,23 +58,32 @@ __device__ __forceinline__ float wave_sum(float v) {
 // d loss / d output of one sample (SB3 PPO.train(): clipped surrogate on minibatch-normalised advantages, MSE value
 // loss).  act_s ... ret_s point at the sample's entries and log_std_p at the scalar: each is read only on the branch
 // that needs it.  A dead lane (row >= B) contributes zeros.
+// Guard (the target_kl kernels of acas2d_ppo_guard.hip): a live actor sample also gives its terms of SB3's approx_kl,
+// (ratio - 1) - log ratio, and of its clip_fraction, |ratio - 1| > clip_range, from the log ratio and the ratio the
+// surrogate is formed from; without it `kl_s` and `cf_s` are zeros nobody reads.
+template <bool Guard = false>
 __device__ __forceinline__ void loss_grad(bool is_actor, bool live, float out, const float* act_s, const float* old_logp_s,
                                           const float* adv_s, const float* ret_s, float a_mean, float a_std,
                                           const float* log_std_p, int B, float clip_range, float vf_coef, float& dout,
-                                          float& dls, float& pg_s, float& vf_s) {
-    dout = 0.0f; dls = 0.0f; pg_s = 0.0f; vf_s = 0.0f;
+                                          float& dls, float& pg_s, float& vf_s, float& kl_s, float& cf_s) {
+    dout = 0.0f; dls = 0.0f; pg_s = 0.0f; vf_s = 0.0f; kl_s = 0.0f; cf_s = 0.0f;
     if (live) {
         if (is_actor) {
             const float ls = log_std_p[0], inv_var = expf(-2.0f * ls);
             const float diff = act_s[0] - out;
             const float logp = -0.5f * diff * diff * inv_var - ls - 0.9189385332046727f;
             const float a = (adv_s[0] - a_mean) / (a_std + 1e-8f);
-            const float ratio = expf(logp - old_logp_s[0]);
+            const float log_ratio = logp - old_logp_s[0];
+            const float ratio = expf(log_ratio);
             const float surr1 = a * ratio, surr2 = a * fminf(fmaxf(ratio, 1.0f - clip_range), 1.0f + clip_range);
             pg_s = -fminf(surr1, surr2) / (float)B;
             const float dlogp = (surr1 <= surr2) ? -(a * ratio) / (float)B : 0.0f;     // torch.min: ties go to the first operand
             dout = dlogp * diff * inv_var;                       // d logp / d mean
             dls = dlogp * (diff * diff * inv_var - 1.0f);        // d logp / d log_std
+            if constexpr (Guard) {
+                kl_s = (ratio - 1.0f) - log_ratio;
+                cf_s = fabsf(ratio - 1.0f) > clip_range ? 1.0f : 0.0f;
+            }
         } else {
             const float e = out - ret_s[0];
             vf_s = e * e / (float)B;
@@ -89,12 +99,14 @@ __device__ __forceinline__ void loss_grad(bool is_actor, bool live, float out, c
 // dz2) live in LDS (narrow_lds_bytes(D) at `lds`), row stride 65 so that "every lane writes its own row's element i" and
 // "every lane reads column t of row s" are both conflict-free; the weight gradients are then sums over the 64 samples
 // of outer products, taken by thread t for row t of each weight matrix, and added to `grad` with float atomics.
-template <int D>
+// Guard: an actor wave also adds its samples' KL and clipped-count terms (loss_grad) to diag[0] and diag[1].
+template <int D, bool Guard = false>
 __device__ __forceinline__ void grad_narrow(const float ACAS2D_C4* w1, const float ACAS2D_C4* b1, const float ACAS2D_C4* w2,
                                             const float ACAS2D_C4* b2, const float ACAS2D_C4* w3, const float ACAS2D_C4* b3,
                                             const float* log_std_p, const float* obs, const float* act,
                                             const float* old_logp, const float* adv, const float* ret, const int64_t* idx,
-                                            int B, float clip_range, float vf_coef, float* grad, float* stats, float* lds) {
+                                            int B, float clip_range, float vf_coef, float* grad, float* stats, float* lds,
+                                            float* diag = nullptr) {
     float* l_h1 = lds;                       // [64][65]
     float* l_h2 = l_h1 + 64 * kRow;
     float* l_dz1 = l_h2 + 64 * kRow;
@@ -141,10 +153,16 @@ __device__ __forceinline__ void grad_narrow(const float ACAS2D_C4* w1, const flo
         out = fmaf(w3[i], h2, out);
     }
 
-    float dout, dls, pg_s, vf_s;
-    loss_grad(is_actor, live, out, act + s, old_logp + s, adv + s, ret + s, a_mean, a_std, log_std_p, B, clip_range, vf_coef,
-              dout, dls, pg_s, vf_s);
+    float dout, dls, pg_s, vf_s, kl_s, cf_s;
+    loss_grad<Guard>(is_actor, live, out, act + s, old_logp + s, adv + s, ret + s, a_mean, a_std, log_std_p, B, clip_range,
+                     vf_coef, dout, dls, pg_s, vf_s, kl_s, cf_s);
     l_do[lane] = dout;
+    if constexpr (Guard) {                                   // (here, not beside the stats atomics: the two terms die at once)
+        if (is_actor) {                                      // (uniform over the wave)
+            const float klsum = wave_sum(kl_s), cfsum = wave_sum(cf_s);
+            if (lane == 0) { atomicAdd(diag + 0, klsum); atomicAdd(diag + 1, cfsum); }
+        }
+    }
 
     // ---- backward to the pre-activations: dz2 = dout w3 (1 - h2^2), dh1 = W2^T dz2, dz1 = dh1 (1 - h1^2)
     float dh1[kH];

@@ -30,10 +30,14 @@ __host__ __device__ constexpr size_t lds_bytes(int D) {
 //   lr.net()                        the six weight pointers of network blockIdx.y ([K][...] stacks for a member)
 //   lr.at(n)                        the learner's element offset into a stack of n floats per learner (0 for one learner)
 //   lr.idx()  lr.log_std()  lr.grad()  lr.stats()  lr.clip_range()  lr.vf_coef()       the learner's own
+//   lr.diag()                       Guard only (acas2d_ppo_guard.hip): the learner's float[8] of KL / clip statistics
 // Each is asked for WHERE IT IS USED, not up front: a member's pointers are sums, and sums formed at the top stay in
 // SGPRs across layer 1, whose 64 weights in flight leave no room for them (20 SGPR spills); the stack pointers and the
 // member number they are formed from are live anyway.
-template <int D, class Learner>
+// Guard: the wave that adds the scalars also adds the 64 samples' KL and clipped-count terms (loss_grad) to lr.diag()[0]
+// and [1], right after loss_grad: lr.diag() is asked for there, next to lr.clip_range(), and is dead again before the
+// weight gradients (held to the end beside lr.stats() it costs the widest kernel an SGPR spill).
+template <int D, class Learner, bool Guard = false>
 __device__ __forceinline__ void grad_wide(const Learner& lr, const float* obs, const float* act, const float* old_logp,
                                           const float* adv, const float* ret, int B) {
     constexpr int XS = x_stride(D);
@@ -142,11 +146,16 @@ __device__ __forceinline__ void grad_wide(const Learner& lr, const float* obs, c
     float out = b3[0];                                              // (every wave: all of them need d loss / d output)
     for (int i = 0; i < kH; ++i) out = fmaf(w3[i], l_h2[lane * kRow + i], out);
 
-    float dout, dls, pg_s, vf_s;
-    loss_grad(is_actor, live, out, act + s, old_logp + s, adv + s, ret + s, a_mean, a_std, lr.log_std(), B, lr.clip_range(),
-              lr.vf_coef(),
-              dout, dls, pg_s, vf_s);
+    float dout, dls, pg_s, vf_s, kl_s, cf_s;
+    loss_grad<Guard>(is_actor, live, out, act + s, old_logp + s, adv + s, ret + s, a_mean, a_std, lr.log_std(), B,
+                     lr.clip_range(), lr.vf_coef(), dout, dls, pg_s, vf_s, kl_s, cf_s);
     if (w == 0) l_do[lane] = dout;
+    if constexpr (Guard) {
+        if (is_actor && w == kWaves - 1) {                             // (uniform over the wave)
+            const float klsum = wave_sum(kl_s), cfsum = wave_sum(cf_s);
+            if (lane == 0) { atomicAdd(lr.diag() + 0, klsum); atomicAdd(lr.diag() + 1, cfsum); }
+        }
+    }
 
     // ---- backward to the pre-activations: dz2 = dout w3 (1 - h2^2), dh1 = W2^T dz2, dz1 = dh1 (1 - h1^2)
 #pragma unroll

@@ -57,6 +57,12 @@ class CPpoUpdateSet(C.Structure):
         [(n, C.c_void_p) for n in ("hyper", "grad", "adam_m", "adam_v", "adam_step", "stats")]
 
 
+class CPpoGuard(C.Structure):
+    """struct Acas2dPpoGuard: the target_kl limits, stop flags and KL / clip statistics of K stacked learners
+    (include/acas2d.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("target_kl", "stopped", "diag")]
+
+
 class CGae(C.Structure):
     """struct Acas2dGae: the bootstrap value and GAE over the collector's [T][E] buffers (include/acas2d.h)."""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -92,7 +98,8 @@ EXPORTS = ("acas2d_abi_version", "acas2d_config_size", "acas2d_state_size", "aca
            "acas2d_ppo_update_wide_f32", "acas2d_ppo_wide_lds_bytes", "acas2d_collect_set_f32", "acas2d_ppo_update_set_f32",
            "acas2d_gae_f32", "acas2d_gae_size", "acas2d_gae_pipeline_depth", "acas2d_collect_set_group_f32",
            "acas2d_ppo_update_wide_set_f32", "acas2d_member_episodes_f32", "acas2d_member_episodes_size",
-           "acas2d_population_exploit_f32", "acas2d_population_exploit_size")
+           "acas2d_population_exploit_f32", "acas2d_population_exploit_size", "acas2d_ppo_update_guarded_set_f32",
+           "acas2d_ppo_guard_size")
 
 
 class NativeLibraryError(RuntimeError):
@@ -169,6 +176,9 @@ def lib():
         f = getattr(L, name)
         f.restype = C.c_int
         f.argtypes = [C.POINTER(CPpoUpdateSet), C.c_void_p]
+    L.acas2d_ppo_update_guarded_set_f32.restype = C.c_int
+    L.acas2d_ppo_update_guarded_set_f32.argtypes = [C.POINTER(CPpoUpdateSet), C.POINTER(CPpoGuard), C.c_void_p]
+    L.acas2d_ppo_guard_size.restype = C.c_size_t
     L.acas2d_gae_f32.restype = C.c_int
     L.acas2d_gae_f32.argtypes = [C.POINTER(CGae), C.c_void_p]
     L.acas2d_gae_size.restype = C.c_size_t
@@ -206,7 +216,8 @@ def lib():
         raise NativeLibraryError("Acas2dState layout mismatch: %d != %d" % (L.acas2d_state_size(), C.sizeof(CState)))
     if L.acas2d_gae_size() != C.sizeof(CGae):
         raise NativeLibraryError("Acas2dGae layout mismatch: %d != %d" % (L.acas2d_gae_size(), C.sizeof(CGae)))
-    for name, twin in (("member_episodes", CMemberEpisodes), ("population_exploit", CPopulationExploit)):
+    for name, twin in (("member_episodes", CMemberEpisodes), ("population_exploit", CPopulationExploit),
+                       ("ppo_guard", CPpoGuard)):
         size = getattr(L, "acas2d_%s_size" % name)()
         if size != C.sizeof(twin):
             raise NativeLibraryError("%s layout mismatch: %d != %d" % (twin.__name__, size, C.sizeof(twin)))

@@ -30,6 +30,7 @@ import math
 import os
 import random
 import time
+from typing import Optional
 
 import numpy as np
 import torch
@@ -54,6 +55,9 @@ class PPOConfig:
     vf_coef: float = 0.5
     max_grad_norm: float = 0.5
     seed: int = 13                # settings.py:28
+    # SB3's target_kl: PPO.train() abandons the rest of an update as soon as one minibatch's approx_kl exceeds 1.5 x
+    # target_kl, before that minibatch's optimizer step.  None (SB3's default, and sb3()'s): no limit.
+    target_kl: Optional[float] = None
 
     @classmethod
     def sb3(cls, **overrides):
@@ -262,6 +266,64 @@ def ppo_loss(policy, cfg, obs, act, old_logp, adv, ret):
     return pg + cfg.ent_coef * ent + cfg.vf_coef * vf, pg, vf
 
 
+@torch.no_grad()
+def approx_kl_and_clip_fraction(policy, cfg, obs, act, old_logp):
+    """What SB3 1.1.0's PPO.train() measures on a minibatch beside its loss, under no_grad: approx_kl = mean((ratio - 1)
+    - log ratio) (Schulman's low-variance estimator, the one `target_kl` is compared with) and clip_fraction =
+    mean(|ratio - 1| > clip_range), with ppo_loss()'s log-prob.  Returns two 0-d tensors."""
+    mean, _ = policy.forward(obs)
+    log_ratio = _normal_logp(mean, policy.log_std, act) - old_logp
+    ratio = log_ratio.exp()
+    return ((ratio - 1.0) - log_ratio).mean(), ((ratio - 1.0).abs() > cfg.clip_range).to(log_ratio.dtype).mean()
+
+
+def explained_variance(values, returns):
+    """SB3's train/explained_variance, 1 - Var(returns - values) / Var(returns) (population variances, as np.var), over
+    the LAST dimension: flat buffers give a 0-d tensor, [K, n] per-member rows give [K].  NaN where Var(returns) == 0."""
+    var_ret = returns.var(dim=-1, unbiased=False)
+    ev = 1.0 - (returns - values).var(dim=-1, unbiased=False) / var_ret
+    return torch.where(var_ret == 0, torch.full_like(ev, float("nan")), ev)
+
+
+def _target_kl(cfg):
+    """A config's target_kl as the kernels take it: None is 0, no limit."""
+    return 0.0 if cfg.target_kl is None else float(cfg.target_kl)
+
+
+class _KlGuard:
+    """What FusedUpdate and FusedUpdateSet share of the guarded update (acas2d_ppo_update_guarded_set_f32,
+    csrc/acas2d_ppo_guard.hip): the per-member `target_kl` limits, the `stopped` flags and the `diag` rows the kernels
+    keep, as ONE device buffer so that begin_update() is one memset."""
+
+    def _init_guard(self, configs, diagnostics, dev):
+        K = len(configs)
+        self.guarded = bool(diagnostics) or any(c.target_kl is not None for c in configs)
+        if not self.guarded:
+            return
+        self.target_kl = torch.tensor([_target_kl(c) for c in configs], dtype=torch.float32).to(dev)
+        self._guard_state = torch.zeros(K * 9, dtype=torch.float32, device=dev)
+        self.diag = self._guard_state[:K * 8].view(K, 8)
+        self.stopped = self._guard_state[K * 8:].view(torch.int32)
+        self._guarded_update = self._lib.acas2d_ppo_update_guarded_set_f32
+        p = lambda t: t.data_ptr()  # noqa: E731
+        self._guard = self._native.CPpoGuard(p(self.target_kl), p(self.stopped), p(self.diag))
+
+    def begin_update(self):
+        """Where SB3 enters train(): every member runs again and the statistics start over.  One memset on the current
+        stream, no synchronisation; nothing to do for an update that is not guarded."""
+        if self.guarded:
+            self._guard_state.zero_()
+
+    def _diagnostics(self):
+        if not self.guarded:
+            raise RuntimeError("diagnostics() needs the guarded update: a target_kl in the config, or diagnostics=True")
+        d, stopped = self.diag.cpu().tolist(), self.stopped.cpu().tolist()
+        nan = float("nan")
+        return [{"approx_kl": r[4] / r[6] if r[6] else nan, "clip_fraction": r[5] / r[6] if r[6] else nan,
+                 "n_minibatches": int(r[6]), "n_applied": int(r[7]), "early_stop": bool(f),
+                 "last_approx_kl": r[2], "last_clip_fraction": r[3]} for r, f in zip(d, stopped)]
+
+
 # observation widths the fused minibatch update is built for: acas2d_ppo_update_f32 (a lane holds its observation row in
 # registers; n_traffic 1, 2, 3, 4, 8) and acas2d_ppo_update_wide_f32 (four waves tile it through LDS; n_traffic 16, 32, 64)
 FUSED_UPDATE_WIDTHS = (8, 11, 14, 17, 29)
@@ -281,15 +343,20 @@ def _flat_rollout(obs, act, old_logp, adv, ret):
     return bufs
 
 
-class FusedUpdate:
+class FusedUpdate(_KlGuard):
     """One PPO minibatch update as two hand-written launches (acas2d_ppo_update_f32, csrc/acas2d_ppo.hip; for obs_dim
     53, 101, 197 acas2d_ppo_update_wide_f32, csrc/acas2d_ppo_wide.hip -- `entry` names the one chosen): forward,
     ppo_loss(), backward, clip_grad_norm_ and Adam for the SB3 MlpPolicy actor-critic, on the parameter tensors in
     place.  `obs` [n, D], `act` / `old_logp` / `adv` / `ret` [n] are the flat float32 rollout buffers (their storage
     must stay put), `idx` an int64 device tensor naming the minibatch's rows (rewritten by the caller between
-    calls).  Keeps its own Adam moments (torch.optim.Adam's arithmetic, eps 1e-5 as SB3 sets it)."""
+    calls).  Keeps its own Adam moments (torch.optim.Adam's arithmetic, eps 1e-5 as SB3 sets it).
+    With `cfg.target_kl` or `diagnostics=True` every step goes through acas2d_ppo_update_guarded_set_f32 instead, as a
+    population of one (`guarded`; the hyper-parameters are then the config's at construction): call begin_update() once
+    per PPO update, step() for every minibatch whether the learner has stopped or not, and read diagnostics()
+    afterwards.  Otherwise the calls are the ones above and begin_update() does nothing."""
 
-    def __init__(self, policy, cfg, obs, act, old_logp, adv, ret, beta1=0.9, beta2=0.999, adam_eps=1e-5):
+    def __init__(self, policy, cfg, obs, act, old_logp, adv, ret, beta1=0.9, beta2=0.999, adam_eps=1e-5,
+                 diagnostics=False):
         import ctypes as C
         from . import native
         D = obs.shape[-1]
@@ -311,6 +378,10 @@ class FusedUpdate:
         assert all(p.dtype == torch.float32 and p.is_contiguous() and p.device == dev for p in self._params)
         self._bufs = _flat_rollout(obs, act, old_logp, adv, ret)
         self.cfg, self.D, self.betas, self.adam_eps, self.device = cfg, D, (beta1, beta2), adam_eps, dev
+        self._init_guard([cfg], diagnostics, dev)
+        if self.guarded:
+            self.hyper = torch.tensor([[cfg.clip_range, cfg.vf_coef, cfg.ent_coef, cfg.max_grad_norm, cfg.learning_rate,
+                                        beta1, beta2, adam_eps]], dtype=torch.float32).to(dev)
 
     def _struct(self, idx):
         assert idx.dtype == torch.int64 and idx.is_contiguous()
@@ -322,13 +393,27 @@ class FusedUpdate:
                                        p(self.step_count), p(self.stats))
 
     def step(self, idx):
+        stream = self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        if self.guarded:                                  # the learner's tensors are K = 1 stacks
+            assert idx.dtype == torch.int64 and idx.is_contiguous()
+            p = lambda t: t.data_ptr()  # noqa: E731
+            u = self._native.CPpoUpdateSet(*[p(t) for t in self._params], *[p(t) for t in self._bufs], p(idx), 1, idx.numel(),
+                                           self.D, 1, p(self.hyper), p(self.grad), p(self.m), p(self.v), p(self.step_count),
+                                           p(self.stats))
+            self._native.check(self._guarded_update(self._C.byref(u), self._C.byref(self._guard), stream))
+            return
         u = self._struct(idx)
-        self._native.check(self._update(
-            self._C.byref(u), self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        self._native.check(self._update(self._C.byref(u), stream))
 
     def last_losses(self):
         s = self.stats.cpu().tolist()
         return {"pg_loss": s[4], "value_loss": s[5], "grad_norm": s[2]}
+
+    def diagnostics(self):
+        """Since begin_update(): approx_kl and clip_fraction (SB3's train/ values: means over the minibatches the learner
+        took, the stopping one included), n_minibatches, n_applied (optimizer steps), early_stop, and the last minibatch's
+        own last_approx_kl / last_clip_fraction.  One read-back."""
+        return self._diagnostics()[0]
 
 
 # traffic counts at which PPOTrainer takes the group-cooperative launches by itself (float32; at 8 the thread-per-env
@@ -392,9 +477,15 @@ class PPOTrainer:
     hand-written launches, its own Adam state; obs_dim in {8, 11, 14, 17, 29} or {53, 101, 197}, i.e. n_traffic 1, 2, 3,
     4, 8 or 16, 32, 64).  gae: None / "torch" (compute_gae: captured with `use_graphs`) or "kernel" (gae_fused: one
     hand-written launch on the static buffers, the bootstrap value still torch's forward, so the run is the "torch" run
-    bit for bit; with `use_graphs` and collector="fused" only)."""
+    bit for bit; with `use_graphs` and collector="fused" only).
+    config.target_kl (SB3's early stop): with updater="fused" the decision is taken on the device (FusedUpdate's guarded
+    entry: every minibatch is still launched, the host learns of a stop from update()'s statistics), op by op it is
+    SB3's break before the optimizer step; the captured torch-op updater cannot stop and rejects it.  diagnostics=True
+    (updater="fused"): the guarded entry without a limit.  Either adds approx_kl, clip_fraction, n_applied, early_stop and
+    explained_variance to update()'s statistics; without both, update() issues the launches it always did."""
 
-    def __init__(self, venv, config=None, policy=None, use_graphs=None, collector=None, updater=None, gae=None):
+    def __init__(self, venv, config=None, policy=None, use_graphs=None, collector=None, updater=None, gae=None,
+                 diagnostics=False):
         self.venv = venv
         self.cfg = config or PPOConfig()
         torch.manual_seed(self.cfg.seed)
@@ -413,6 +504,13 @@ class PPOTrainer:
         if self.updater not in ("graphs", "fused") or (self.updater == "fused" and not self.use_graphs):
             raise ValueError("updater %r needs use_graphs" % (self.updater,))
         self._fused_update = None
+        self.diagnostics = bool(diagnostics)
+        if (self.cfg.target_kl is not None and self.use_graphs or self.diagnostics) and not (
+                self.use_graphs and self.updater == "fused"):
+            raise ValueError("target_kl and diagnostics=True need updater='fused' (the stop is decided inside its kernels) "
+                             "or use_graphs=False (target_kl only: SB3's break, op by op); the captured torch-op updater "
+                             "replays a fixed graph and cannot stop -- got use_graphs=%r, updater=%r"
+                             % (self.use_graphs, self.updater))
         self.gae = gae or "torch"
         if self.gae not in ("torch", "kernel"):
             raise ValueError("gae must be None, 'torch' or 'kernel', got %r" % (gae,))
@@ -639,8 +737,10 @@ class PPOTrainer:
         if self.use_graphs and self.updater == "fused":
             n, B = cfg.n_steps * self.venv.num_envs, self.mb_idx.numel()
             if self._fused_update is None:
-                self._fused_update = FusedUpdate(self.policy, cfg, self.b_obs, self.b_act, self.b_logp, self.b_adv, self.b_ret)
+                self._fused_update = FusedUpdate(self.policy, cfg, self.b_obs, self.b_act, self.b_logp, self.b_adv, self.b_ret,
+                                                 diagnostics=self.diagnostics)
             fu = self._fused_update
+            fu.begin_update()
             for _ in range(cfg.n_epochs):
                 perm = torch.randperm(n, device=self.device)
                 for i in range(0, n - B + 1, B):
@@ -650,7 +750,12 @@ class PPOTrainer:
                     self.mb_tail.copy_(perm[n - n % B:])
                     fu.step(self.mb_tail)
             st = fu.last_losses()
-            return {"pg_loss": st["pg_loss"], "value_loss": st["value_loss"], "std": self.policy.log_std.detach().exp().item()}
+            out = {"pg_loss": st["pg_loss"], "value_loss": st["value_loss"], "std": self.policy.log_std.detach().exp().item()}
+            if fu.guarded:
+                d = fu.diagnostics()
+                out.update({k: d[k] for k in ("approx_kl", "clip_fraction", "n_applied", "early_stop")})
+                out["explained_variance"] = explained_variance(self.b_val.reshape(-1), self.b_ret.reshape(-1)).item()
+            return out
         if self.use_graphs:
             n, B = cfg.n_steps * self.venv.num_envs, self.mb_idx.numel()
             for _ in range(cfg.n_epochs):
@@ -665,6 +770,7 @@ class PPOTrainer:
                     "std": self.policy.log_std.detach().exp().item()}
         n = obs.shape[0]
         stats = {}
+        kls, cfs, n_applied, go_on = [], [], 0, True
         for _ in range(cfg.n_epochs):
             perm = torch.randperm(n, device=self.device)
             for i in range(0, n, cfg.batch_size):
@@ -672,11 +778,26 @@ class PPOTrainer:
                 if idx.numel() < 2:
                     continue                              # a one-row tail has no advantage standard deviation
                 loss, pg, vf = ppo_loss(self.policy, cfg, obs[idx], act[idx], old_logp[idx], adv[idx], ret[idx])
+                if cfg.target_kl is not None:             # SB3: measured under no_grad, the break before the optimizer step
+                    kl, cf = approx_kl_and_clip_fraction(self.policy, cfg, obs[idx], act[idx], old_logp[idx])
+                    kls.append(kl.item())
+                    cfs.append(cf.item())
+                    if kls[-1] > 1.5 * cfg.target_kl:
+                        go_on = False
+                        break
                 self.opt.zero_grad(set_to_none=True)
                 loss.backward()
                 nn.utils.clip_grad_norm_(self.policy.parameters(), cfg.max_grad_norm)
                 self.opt.step()
+                n_applied += 1
             stats = {"pg_loss": pg.item(), "value_loss": vf.item(), "std": self.policy.log_std.detach().exp().item()}
+            if not go_on:
+                break
+        if cfg.target_kl is not None:
+            stats.update({"approx_kl": float(np.mean(kls)), "clip_fraction": float(np.mean(cfs)), "n_applied": n_applied,
+                          "early_stop": not go_on})
+            if old_val is not None:
+                stats["explained_variance"] = explained_variance(old_val.reshape(-1), ret.reshape(-1)).item()
         return stats
 
     def optimizer_state(self):
@@ -760,9 +881,10 @@ class PPOTrainer:
 
 # ---- K learners at once: the seeds or hyper-parameter sets of a sweep as ONE population ---------------------------------
 # what may differ between the members of a population, and what the shared launches need equal
-MEMBER_FIELDS = ("seed", "learning_rate", "clip_range", "ent_coef", "vf_coef", "max_grad_norm", "gamma", "gae_lambda")
+MEMBER_FIELDS = ("seed", "learning_rate", "clip_range", "ent_coef", "vf_coef", "max_grad_norm", "gamma", "gae_lambda",
+                 "target_kl")
 SHARED_FIELDS = ("n_steps", "batch_size", "n_epochs")
-# hyper[k]: the row acas2d_ppo_update_set_f32 reads for member k
+# hyper[k]: the row acas2d_ppo_update_set_f32 reads for member k (target_kl is not in it: FusedUpdateSet.target_kl)
 HYPER_SLOTS = ("clip_range", "vf_coef", "ent_coef", "max_grad_norm", "learning_rate", "beta1", "beta2", "adam_eps")
 
 
@@ -837,16 +959,22 @@ class ActorCriticSet:
         return torch.baddbmm(p["value_net.bias"].unsqueeze(1), h, p["value_net.weight"].transpose(1, 2)).reshape(-1)
 
 
-class FusedUpdateSet:
+class FusedUpdateSet(_KlGuard):
     """FusedUpdate for the K members of an `ActorCriticSet` in two launches whatever K is (acas2d_ppo_update_set_f32,
     csrc/acas2d_ppo_set.hip; for obs_dim 53, 101, 197 acas2d_ppo_update_wide_set_f32, csrc/acas2d_ppo_wide_set.hip --
     `entry` names the one chosen).  `obs` [n, D], `act` / `old_logp` / `adv` / `ret` [n] are ONE flat float32 rollout buffer
     shared by the members (their storage must stay put); `step(idx)` takes an int64 device tensor [K, B]: row k names
     member k's minibatch as rows of that buffer.  `hyper` is a float32 device tensor [K, 8] (HYPER_SLOTS) the kernels
     read at every call: rewrite it between calls to change a member's learning rate, clip range, ...  Keeps the
-    members' Adam moments and step counts ([K, ...]).  float32."""
+    members' Adam moments and step counts ([K, ...]).  float32.
+    Where a member's config has a `target_kl`, or with `diagnostics=True`, every step goes through
+    acas2d_ppo_update_guarded_set_f32 instead (`guarded`; csrc/acas2d_ppo_guard.hip): `target_kl` is a float32 device
+    tensor [K] (0: no limit) beside `hyper`, `stopped` int32 [K] and `diag` float32 [K, 8] are the kernels'.  Call
+    begin_update() once per PPO update, step() for every minibatch -- a stopped member's share of the two launches
+    returns at once -- and read diagnostics() afterwards.  Otherwise the calls are the ones above."""
 
-    def __init__(self, policy_set, configs, obs, act, old_logp, adv, ret, beta1=0.9, beta2=0.999, adam_eps=1e-5):
+    def __init__(self, policy_set, configs, obs, act, old_logp, adv, ret, beta1=0.9, beta2=0.999, adam_eps=1e-5,
+                 diagnostics=False):
         import ctypes as C
         from . import native
         D, K = obs.shape[-1], policy_set.n_members
@@ -872,20 +1000,29 @@ class FusedUpdateSet:
         assert all(p.dtype == torch.float32 and p.is_contiguous() and p.device == dev for p in self._params)
         self._bufs = _flat_rollout(obs, act, old_logp, adv, ret)
         self.policy_set, self.D, self.K, self.device = policy_set, D, K, dev
+        self._init_guard(list(configs), diagnostics, dev)
 
     def step(self, idx, apply=True):
-        """One minibatch update of every member; apply=False leaves the raw gradients in `grad` and applies nothing."""
+        """One minibatch update of every member; apply=False leaves the raw gradients in `grad` and applies nothing (the
+        unguarded entry: a probe has no stop to decide)."""
         assert idx.dtype == torch.int64 and idx.is_contiguous() and idx.dim() == 2 and idx.shape[0] == self.K
         p = lambda t: t.data_ptr()  # noqa: E731
         u = self._native.CPpoUpdateSet(*[p(t) for t in self._params], *[p(t) for t in self._bufs], p(idx), self.K,
                                        idx.shape[1], self.D, 1 if apply else 0, p(self.hyper), p(self.grad), p(self.m),
                                        p(self.v), p(self.step_count), p(self.stats))
-        self._native.check(self._update(
-            self._C.byref(u), self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+        stream = self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        if self.guarded and apply:
+            self._native.check(self._guarded_update(self._C.byref(u), self._C.byref(self._guard), stream))
+        else:
+            self._native.check(self._update(self._C.byref(u), stream))
 
     def last_losses(self):
         s = self.stats.cpu()
         return [{"pg_loss": float(r[4]), "value_loss": float(r[5]), "grad_norm": float(r[2])} for r in s]
+
+    def diagnostics(self):
+        """FusedUpdate.diagnostics(), one dict per member."""
+        return self._diagnostics()
 
 
 class PopulationTrainer:
@@ -905,11 +1042,16 @@ class PopulationTrainer:
     With per-member gamma / gae_lambda GAE takes them as per-env float32 vectors (the product gamma x lambda is then
     rounded in float32); equal values are passed as the numbers they are.
     Out of scope: float64, members with different n_steps / batch_size / n_epochs, more than one GPU.
-    gae: None / "torch" (compute_gae, op by op) or "kernel" (gae_fused: one launch for all members, the same bits)."""
+    gae: None / "torch" (compute_gae, op by op) or "kernel" (gae_fused: one launch for all members, the same bits).
+    target_kl may differ between members (None: no limit): a member whose minibatch exceeds 1.5 x its target_kl sits out
+    the rest of that update() while the others go on in the same launches, decided on the device (FusedUpdateSet's
+    guarded entry).  With a target_kl anywhere, or diagnostics=True, update() adds approx_kl, clip_fraction, n_applied,
+    early_stop and explained_variance per member; without both it issues the launches it always did."""
 
-    def __init__(self, venv, configs, gae=None, group=False):
+    def __init__(self, venv, configs, gae=None, group=False, diagnostics=False):
         configs = list(configs)
         self.group = bool(group)
+        self.diagnostics = bool(diagnostics)
         self.gae = gae or "torch"
         if self.gae not in ("torch", "kernel"):
             raise ValueError("gae must be None, 'torch' or 'kernel', got %r" % (gae,))
@@ -1029,8 +1171,9 @@ class PopulationTrainer:
         n, B = cfg.n_steps * self.EM, self.mb_idx.shape[1]
         if self._fused_update is None:
             self._fused_update = FusedUpdateSet(self.policy_set, self.configs, self.b_obs, self.b_act, self.b_logp, self.b_adv,
-                                                self.b_ret)
+                                                self.b_ret, diagnostics=self.diagnostics)
         fu = self._fused_update
+        fu.begin_update()
         for _ in range(cfg.n_epochs):
             perm = torch.stack([torch.randperm(n, device=self.device, generator=g) for g in self.generators])
             rows = self.member_rows.gather(1, perm)       # [K, n]: each member's permutation, as rows of the shared buffer
@@ -1041,8 +1184,15 @@ class PopulationTrainer:
                 self.mb_tail.copy_(rows[:, n - n % B:])
                 fu.step(self.mb_tail)
         std = self.policy_set.params["log_std"].detach().exp().reshape(K).cpu().tolist()
-        return [{"pg_loss": st["pg_loss"], "value_loss": st["value_loss"], "std": std[k]}
-                for k, st in enumerate(fu.last_losses())]
+        out = [{"pg_loss": st["pg_loss"], "value_loss": st["value_loss"], "std": std[k]}
+               for k, st in enumerate(fu.last_losses())]
+        if fu.guarded:
+            rows = lambda b: b.view(cfg.n_steps, K, self.EM).transpose(0, 1).reshape(K, -1)  # noqa: E731
+            ev = explained_variance(rows(self.b_val), rows(self.b_ret)).cpu().tolist()
+            for k, d in enumerate(fu.diagnostics()):
+                out[k].update({n: d[n] for n in ("approx_kl", "clip_fraction", "n_applied", "early_stop")})
+                out[k]["explained_variance"] = ev[k]
+        return out
 
     def optimizer_state(self):
         """The members' Adam state: step [K], exp_avg / exp_avg_sq [K, n] in the flat layout of include/acas2d.h."""
@@ -1237,10 +1387,12 @@ class PBTTrainer(PopulationTrainer):
                   losses.
     learn() is the parent's.  A recipient takes parameters, Adam state and hyper row; it keeps its envs, its noise key and
     its minibatch generator, so twins diverge.  gamma and gae_lambda live outside the hyper row and are not exchanged:
-    they must be equal across members.  fraction = 0 is PopulationTrainer bit for bit.  group=True and gae="kernel" as
-    the parent's."""
+    they must be equal across members.  A member's target_kl is not in the hyper row either and belongs to its SLOT:
+    an exploit step neither copies nor perturbs it, so a recipient keeps its own limit under the donor's weights and
+    learning rate -- the guard against what the x 1.2 steps can build up.  fraction = 0 is PopulationTrainer bit for bit.
+    group=True, gae="kernel" and diagnostics=True as the parent's."""
 
-    def __init__(self, venv, configs, pbt, gae=None, group=False):
+    def __init__(self, venv, configs, pbt, gae=None, group=False, diagnostics=False):
         configs = list(configs)
         for f in ("gamma", "gae_lambda"):
             if len({getattr(c, f) for c in configs}) > 1:
@@ -1248,10 +1400,10 @@ class PBTTrainer(PopulationTrainer):
                                  "exchanged by an exploit step, got %s" % (f, [getattr(c, f) for c in configs]))
         self.pbt = pbt
         self.n_replace = pbt.n_replace(len(configs))
-        super().__init__(venv, configs, gae=gae, group=group)
+        super().__init__(venv, configs, gae=gae, group=group, diagnostics=diagnostics)
         # built now, not at the first update: an exploit before it must find the moments and the hyper row
         self._fused_update = FusedUpdateSet(self.policy_set, self.configs, self.b_obs, self.b_act, self.b_logp, self.b_adv,
-                                            self.b_ret)
+                                            self.b_ret, diagnostics=self.diagnostics)
         self.window = None
         self.generation = 0
         self._updates = 0

@@ -468,6 +468,42 @@ int acas2d_ppo_update_set_f32(const Acas2dPpoUpdateSet *u, void *stream);
 int acas2d_ppo_update_wide_set_f32(const Acas2dPpoUpdateSet *u, void *stream);
 
 /*
+ * acas2d_ppo_update_guarded_set_f32: acas2d_ppo_update_set_f32 / acas2d_ppo_update_wide_set_f32 with SB3 1.1.0's target_kl
+ * early stop and its train/approx_kl and train/clip_fraction, decided on the device.  Additive to ABI 7.  float32.
+ * ONE entry for obs_dim in {8, 11, 14, 17, 29, 53, 101, 197}; `u` is the siblings' struct with the siblings' layouts, K =
+ * 1 serves a single learner (its tensors are K = 1 stacks).  The same two launches, no read-back:
+ *   gradient launch   the sibling's arithmetic; each live row of an actor workgroup also adds (ratio - 1) - log(ratio)
+ *                     to diag[k][0] and (|ratio - 1| > clip_range ? 1 : 0) to diag[k][1], ratio being the one the
+ *                     clipped surrogate is formed from.  A member with stopped[k] != 0 does nothing.
+ *   apply launch      a member with stopped[k] != 0 does nothing.  Otherwise kl = diag[k][0] / n_rows and cf =
+ *                     diag[k][1] / n_rows (SB3's approx_kl and clip_fraction of this minibatch), and
+ *                       diag[k][2] = kl, diag[k][3] = cf              the last minibatch's
+ *                       diag[k][4] += kl, diag[k][5] += cf, diag[k][6] += 1   sums and count over the update
+ *                       diag[k][0] = diag[k][1] = 0
+ *                     then, if target_kl[k] > 0 and kl > 1.5f * target_kl[k], the member STOPS: stopped[k] = 1, stats[k][0]
+ *                     and [1] move to stats[k][4] and [5] (SB3 logs the stopping minibatch's losses), grad[k] is zeroed,
+ *                     and nothing is applied -- the parameters, adam_m, adam_v, adam_step[k] and stats[k][2] stay as they
+ *                     were, the entropy term is not added.  Otherwise the sibling's apply, and diag[k][7] += 1.
+ * The caller zeroes `stopped` and `diag` where SB3 enters train() and keeps calling for every minibatch of the update;
+ * afterwards diag[k][4] / diag[k][6] is SB3's train/approx_kl, diag[k][5] / diag[k][6] its train/clip_fraction and
+ * diag[k][7] the number of minibatches applied (SB3 appends the stopping minibatch to both lists before it breaks, so it
+ * counts in [4], [5], [6] and not in [7]).  target_kl[k] <= 0: no limit for member k, only the statistics.
+ * With the limit off the parameters, moments and step counts are the siblings': bit for bit where n_rows <= 64 (one atomic
+ * add per gradient entry), to the siblings' run-to-run rounding otherwise.  LDS as the siblings', checked against each
+ * device at its first call.  ACAS2D_EINVAL before any launch: what the siblings reject, a NULL `g` or a NULL pointer in it,
+ * an obs_dim outside the eight, and apply == 0 (the probe mode has no decision to make: the raw gradients are the
+ * unguarded entries').  Out of scope: float64, members with different n_rows.
+ */
+typedef struct Acas2dPpoGuard {
+    const void *target_kl;              /* device float[K]; <= 0: no limit */
+    int32_t *stopped;                   /* device int32[K]; the caller zeroes it where SB3 enters train() */
+    void *diag;                         /* device float[K][8], slots as above; zeroed with `stopped` */
+} Acas2dPpoGuard;
+
+int acas2d_ppo_update_guarded_set_f32(const Acas2dPpoUpdateSet *u, const Acas2dPpoGuard *g, void *stream);
+size_t acas2d_ppo_guard_size(void);     /* sizeof(Acas2dPpoGuard): layout check for bindings */
+
+/*
  * acas2d_gae_f32: what lies between acas2d_collect_* and acas2d_ppo_update_* in a PPO iteration, in ONE launch -- the
  * critic's value of the last observation (optional) and SB3 1.1.0's RolloutBuffer.compute_returns_and_advantage (GAE)
  * over the collector's [T][E] buffers (`PPO.learn()`, training_main.py:44-52).  Additive to ABI 7.  float32.

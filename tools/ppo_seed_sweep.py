@@ -58,6 +58,9 @@ ap.add_argument("--pbt-fraction", type=float, default=0.25, help="the share of m
 ap.add_argument("--gae", choices=("torch", "kernel"), default=None,
                 help="kernel: GAE as one hand-written launch (ppo.gae_fused), the same bits as torch's compute_gae; the default "
                      "follows tools/bench_gae.py's measurement (DESIGN.md 4.2f): GAE_DEFAULT below")
+ap.add_argument("--target-kl", type=float, default=None,
+                help="SB3's target_kl for every run of the sweep (decided inside the fused update's launches, DESIGN.md 4.2h): "
+                     "the records then carry the last update's approx_kl, clip_fraction and n_applied")
 args = ap.parse_args()
 if args.pbt and not args.population:
     ap.error("--pbt needs --population")
@@ -82,7 +85,7 @@ GROUP = N in g.ppo.GROUP_TRAFFIC                       # the group-cooperative l
 own, trf, goal = H.parity_reset_states(g.ACAS2DConfig(n_traffic=N), 13, 0, 100)
 score = dict(dtype=torch.float32, config=g.ACAS2DConfig(n_traffic=N), group=True) if GROUP else {}
 for name in args.sets:
-    kw = {**dict(n_steps=256, batch_size=4096), **SETS[name]}
+    kw = {**dict(n_steps=256, batch_size=4096), **SETS[name], **({} if args.target_kl is None else {"target_kl": args.target_kl})}
     goals = []
     if args.population:
         t0 = time.time()
@@ -101,6 +104,7 @@ for name in args.sets:
             last = [r for r in hist if r["member"] == k and not r.get("eval") and "exploit" not in r][-1]
             rec = {"set": name, "config": kw, "seed": seed, "population": K, "member": k, "timesteps": int(args.timesteps),
                    "wall_s": wall, "train_ep_rew_mean_last": last.get("ep_rew_mean"), "std": last.get("std"),
+                   **{n: last[n] for n in ("approx_kl", "clip_fraction", "n_applied") if n in last},
                    "eval_mean_return": float(out["total_reward"][k].mean()), "eval_mean_steps": float(out["steps"][k].mean()),
                    "goal": int((out["outcome"][k] == 1).sum()), "collision": int((out["outcome"][k] == 2).sum()),
                    "timeout": int((out["outcome"][k] == 3).sum())}
@@ -119,6 +123,7 @@ for name in args.sets:
         out = g.evaluate_policy_fused(tr.policy, own, trf, goal, **score)
         rec = {"set": name, "config": kw, "seed": seed, "timesteps": int(args.timesteps), "wall_s": time.time() - t0,
                "train_ep_rew_mean_last": hist[-1].get("ep_rew_mean"), "std": hist[-1].get("std"),
+               **{n: hist[-1][n] for n in ("approx_kl", "clip_fraction", "n_applied") if n in hist[-1]},
                "eval_mean_return": float(out["total_reward"].mean()), "eval_mean_steps": float(out["steps"].mean()),
                "goal": int((out["outcome"] == 1).sum()), "collision": int((out["outcome"] == 2).sum()),
                "timeout": int((out["outcome"] == 3).sum())}

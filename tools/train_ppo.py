@@ -32,6 +32,11 @@ ap.add_argument("--gae", choices=("torch", "kernel"), default=None,
                      "as torch's compute_gae; needs --collector fused); the default follows tools/bench_gae.py's measurement "
                      "(DESIGN.md 4.2f): GAE_DEFAULT below")
 ap.add_argument("--seed", type=int, default=13)
+ap.add_argument("--target-kl", type=float, default=None,
+                help="SB3's target_kl: a learner whose minibatch approx_kl exceeds 1.5 x this sits out the rest of that update "
+                     "(fused updater: decided inside the update's own launches, DESIGN.md 4.2h; --collector eager: SB3's break); "
+                     "the log then carries approx_kl, clip_fraction, n_applied, early_stop and explained_variance.  Not with "
+                     "--updater graphs")
 ap.add_argument("--population", type=int, default=0, metavar="K",
                 help="train K learners with the seeds --seed ... --seed + K - 1 side by side in one process "
                      "(ppo.PopulationTrainer: one collection launch and two launches per minibatch for all K; each member gets "
@@ -65,7 +70,8 @@ if args.population:
     import helpers as H
     K = args.population
     venv = g.ACAS2DVecEnv(K * args.envs, args.traffic, device="cuda:0", dtype=torch.float32, seed=13)
-    cfgs = [g.PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, seed=args.seed + k) for k in range(K)]
+    cfgs = [g.PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, seed=args.seed + k, target_kl=args.target_kl)
+            for k in range(K)]
     if args.pbt:
         pop = g.PBTTrainer(venv, cfgs, g.PBTConfig(ready_every=args.pbt_every, fraction=args.pbt_fraction, seed=args.seed),
                            gae=args.gae, group=args.traffic in g.ppo.GROUP_TRAFFIC)
@@ -85,7 +91,8 @@ if args.population:
     sys.exit(0)
 
 venv = g.ACAS2DVecEnv(args.envs, args.traffic, device="cuda:0", dtype=torch.float32, seed=13)
-trainer = g.PPOTrainer(venv, g.PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, seed=args.seed), collector=args.collector,
+trainer = g.PPOTrainer(venv, g.PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, seed=args.seed, target_kl=args.target_kl),
+                       collector=args.collector,
                        use_graphs=args.collector != "eager", updater=args.updater if args.collector != "eager" else "graphs", gae=args.gae)
 hist = trainer.learn(int(args.timesteps), log=lambda r: print(json.dumps(r), flush=True))
 
