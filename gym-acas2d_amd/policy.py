@@ -24,6 +24,16 @@ _ACTOR_KEYS = ("mlp_extractor.policy_net.0.weight", "mlp_extractor.policy_net.0.
                "action_net.weight", "action_net.bias")
 
 
+def kernel_layout(w1, b1, w2, b2, w3, b3, device=None):
+    """One SB3 MlpPolicy net (actor or critic) as the kernels read it (CPolicy / Acas2dActorCritic, include/acas2d.h):
+    from (w1 [64, D], b1, w2 [64, 64], b2, w3 [1, 64], b3) in torch's layout, each with an optional leading [K], six
+    contiguous float32 tensors -- w1 and w2 transposed on their last two dimensions ([D][64], [64][64]), the head and
+    the biases flat per member.  Checks no shape: every caller has its own message."""
+    w = [torch.as_tensor(t).detach().to(device=device, dtype=torch.float32) for t in (w1, b1, w2, b2, w3, b3)]
+    flat = (lambda t: t.reshape(t.shape[0], -1)) if w[0].dim() == 3 else (lambda t: t.reshape(-1))  # noqa: E731
+    return [(t.transpose(-2, -1) if i in (0, 2) else flat(t)).contiguous() for i, t in enumerate(w)]
+
+
 class SB3ActorPolicy(torch.nn.Module):
     def __init__(self, state_dict):
         super().__init__()
@@ -183,8 +193,8 @@ def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float
         if w1.shape != (64, D) or w2.shape != (64, 64) or w3.numel() != 64 or b3.numel() != 1:
             raise ValueError("policy must be the SB3 MlpPolicy actor %d -> 64 -> 64 -> 1, got %s %s %s"
                              % (D, tuple(w1.shape), tuple(w2.shape), tuple(w3.shape)))
-        ws.append((w1.t(), b1.reshape(64), w2.t(), b2.reshape(64), w3.reshape(64), b3.reshape(1)))
-    keep = [torch.stack([w[i] for w in ws]).contiguous() for i in range(6)]      # [K][D][64], [K][64], ...
+        ws.append(kernel_layout(w1, b1, w2, b2, w3, b3))
+    keep = [torch.stack(ts) for ts in zip(*ws)]                                  # [K][D][64], [K][64], ...
     T = (max_steps or v.config.max_steps) + 1
     outcome = torch.empty(K, E, dtype=torch.uint8, device=dev)
     steps = torch.empty(K, E, dtype=torch.int32, device=dev)

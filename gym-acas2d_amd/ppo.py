@@ -24,6 +24,13 @@ buffer writes -- the time index is a device counter, so the same graph is replay
 the GAE recursion, and ONE minibatch update (gather by a static index buffer, losses, backward,
 gradient clipping, capturable Adam).  No host synchronisation inside an iteration; episode
 statistics are read once per iteration from the [T, E] side-channel buffers.
+
+One learner (PPOTrainer) and K learners in the same launches (PopulationTrainer, PBTTrainer) differ in their random
+streams and in the kernels they call, not in their host code, which is written once: `_Trainer` holds the static rollout
+buffers, the intake of a fused collection and learn()'s loop; minibatch_buffers() / minibatch_schedule() the static index
+buffers and an epoch's walk through them; `_FusedUpdater` what FusedUpdate and FusedUpdateSet share (the entry by width,
+the workspace, hyper_row(), the struct of the set entries, the target_kl guard); policy.kernel_layout() the network as
+every kernel reads it.
 """
 import dataclasses
 import math
@@ -35,6 +42,8 @@ from typing import Optional
 import numpy as np
 import torch
 from torch import nn
+
+from .policy import kernel_layout
 
 
 @dataclasses.dataclass
@@ -168,8 +177,7 @@ def _critic_stacks(critic, n_members, obs_dim, device):
         if n_members != 1:
             raise ValueError("critic: one ActorCritic serves n_members = 1; pass an ActorCriticSet for %d" % n_members)
         vn = critic.mlp_extractor.value_net
-        w = [vn[0].weight.detach().t(), vn[0].bias.detach(), vn[2].weight.detach().t(), vn[2].bias.detach(),
-             critic.value_net.weight.detach().reshape(-1), critic.value_net.bias.detach().reshape(-1)]
+        w = kernel_layout(vn[0].weight, vn[0].bias, vn[2].weight, vn[2].bias, critic.value_net.weight, critic.value_net.bias)
     else:
         w = list(critic)
     w = [t.to(device=device, dtype=torch.float32).contiguous() for t in w]
@@ -285,28 +293,90 @@ def explained_variance(values, returns):
     return torch.where(var_ret == 0, torch.full_like(ev, float("nan")), ev)
 
 
-def _target_kl(cfg):
-    """A config's target_kl as the kernels take it: None is 0, no limit."""
-    return 0.0 if cfg.target_kl is None else float(cfg.target_kl)
+# observation widths the fused minibatch update is built for: acas2d_ppo_update_f32 (a lane holds its observation row in
+# registers; n_traffic 1, 2, 3, 4, 8) and acas2d_ppo_update_wide_f32 (four waves tile it through LDS; n_traffic 16, 32, 64)
+FUSED_UPDATE_WIDTHS = (8, 11, 14, 17, 29)
+FUSED_UPDATE_WIDE_WIDTHS = (53, 101, 197)
+# the 13 parameter tensors in FusedUpdate's order (the flat grad / moment layout of include/acas2d.h)
+PARAM_NAMES = ("mlp_extractor.policy_net.0.weight", "mlp_extractor.policy_net.0.bias",
+               "mlp_extractor.policy_net.2.weight", "mlp_extractor.policy_net.2.bias", "action_net.weight", "action_net.bias",
+               "mlp_extractor.value_net.0.weight", "mlp_extractor.value_net.0.bias",
+               "mlp_extractor.value_net.2.weight", "mlp_extractor.value_net.2.bias", "value_net.weight", "value_net.bias",
+               "log_std")
+# hyper[k]: the row acas2d_ppo_update_set_f32 reads for member k (target_kl is not in it: FusedUpdateSet.target_kl)
+HYPER_SLOTS = ("clip_range", "vf_coef", "ent_coef", "max_grad_norm", "learning_rate", "beta1", "beta2", "adam_eps")
 
 
-class _KlGuard:
-    """What FusedUpdate and FusedUpdateSet share of the guarded update (acas2d_ppo_update_guarded_set_f32,
-    csrc/acas2d_ppo_guard.hip): the per-member `target_kl` limits, the `stopped` flags and the `diag` rows the kernels
-    keep, as ONE device buffer so that begin_update() is one memset."""
+def hyper_row(cfg, beta1=0.9, beta2=0.999, adam_eps=1e-5):
+    """One learner's hyper-parameters as the update kernels take them, in HYPER_SLOTS order."""
+    return [cfg.clip_range, cfg.vf_coef, cfg.ent_coef, cfg.max_grad_norm, cfg.learning_rate, beta1, beta2, adam_eps]
 
-    def _init_guard(self, configs, diagnostics, dev):
-        K = len(configs)
+
+def _flat_rollout(obs, act, old_logp, adv, ret):
+    """The five rollout buffers as the update kernels take them: obs [n, D], the others [n] (views of the storage)."""
+    bufs = [t.reshape(-1) if i else t.reshape(-1, obs.shape[-1]) for i, t in enumerate((obs, act, old_logp, adv, ret))]
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in bufs)
+    return bufs
+
+
+class _FusedUpdater:
+    """What FusedUpdate and FusedUpdateSet share: the choice of the entry by width, the workspace (`grad`, `m`, `v`,
+    `step_count`, `stats`) with a leading [K] for a set, the flat rollout, the `hyper` rows, the struct of the set entries
+    and the guarded update (acas2d_ppo_update_guarded_set_f32, csrc/acas2d_ppo_guard.hip): the per-member `target_kl`
+    limits, the `stopped` flags and the `diag` rows the kernels keep, as ONE device buffer so that begin_update() is one
+    memset."""
+    # one row per width class: the widths, the solo symbol, the set symbol (`_symbol` names a subclass's column)
+    _ENTRIES = ((FUSED_UPDATE_WIDTHS, "acas2d_ppo_update_f32", "acas2d_ppo_update_set_f32"),
+                (FUSED_UPDATE_WIDE_WIDTHS, "acas2d_ppo_update_wide_f32", "acas2d_ppo_update_wide_set_f32"))
+
+    @classmethod
+    def _entry_for(cls, D):
+        for row in cls._ENTRIES:
+            if D in row[0]:
+                return row[cls._symbol]
+        built = " and ".join("{%s} (n_traffic %s: %s)" % (", ".join(map(str, row[0])), ", ".join(str((d - 5) // 3) for d in row[0]),
+                                                          row[cls._symbol]) for row in cls._ENTRIES)
+        raise ValueError("%s is built for obs_dim in %s%s %d" % (cls.__name__, built, cls._got, D))
+
+    def __init__(self, params, configs, rollout, lead, beta1, beta2, adam_eps, diagnostics):
+        import ctypes as C
+        from . import native
+        self.D, K, dev = rollout[0].shape[-1], len(configs), rollout[0].device
+        self.entry = self._entry_for(self.D)
+        self._C, self._native, self._lib, self.device = C, native, native.lib(), dev
+        self._update = getattr(self._lib, self.entry)
+        n = int(self._lib.acas2d_ppo_workspace_floats(self.D))
+        z = lambda *shape, dt=torch.float32: torch.zeros(*shape, dtype=dt, device=dev)  # noqa: E731
+        self.grad, self.m, self.v, self.step_count, self.stats = z(*lead, n), z(*lead, n), z(*lead, n), z(K, dt=torch.int32), z(*lead, 8)
+        self.hyper = torch.tensor([hyper_row(c, beta1, beta2, adam_eps) for c in configs], dtype=torch.float32).to(dev)
+        self._params = params
+        assert all(p.dtype == torch.float32 and p.is_contiguous() and p.device == dev for p in params)
+        self._bufs = _flat_rollout(*rollout)
         self.guarded = bool(diagnostics) or any(c.target_kl is not None for c in configs)
-        if not self.guarded:
-            return
-        self.target_kl = torch.tensor([_target_kl(c) for c in configs], dtype=torch.float32).to(dev)
-        self._guard_state = torch.zeros(K * 9, dtype=torch.float32, device=dev)
-        self.diag = self._guard_state[:K * 8].view(K, 8)
-        self.stopped = self._guard_state[K * 8:].view(torch.int32)
-        self._guarded_update = self._lib.acas2d_ppo_update_guarded_set_f32
+        if self.guarded:
+            # a config's target_kl as the kernels take it: None is 0, no limit
+            self.target_kl = torch.tensor([0.0 if c.target_kl is None else float(c.target_kl) for c in configs],
+                                          dtype=torch.float32).to(dev)
+            self._guard_state = torch.zeros(K * 9, dtype=torch.float32, device=dev)
+            self.diag = self._guard_state[:K * 8].view(K, 8)
+            self.stopped = self._guard_state[K * 8:].view(torch.int32)
+            self._guarded_update = self._lib.acas2d_ppo_update_guarded_set_f32
+            self._guard = native.CPpoGuard(self.target_kl.data_ptr(), self.stopped.data_ptr(), self.diag.data_ptr())
+
+    def _stream(self):
+        return self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _set_struct(self, idx, K, B, apply=True):
+        """The Acas2dPpoUpdateSet of one minibatch: `idx` names B rows for each of the K members."""
+        assert idx.dtype == torch.int64 and idx.is_contiguous()
         p = lambda t: t.data_ptr()  # noqa: E731
-        self._guard = self._native.CPpoGuard(p(self.target_kl), p(self.stopped), p(self.diag))
+        return self._native.CPpoUpdateSet(*[p(t) for t in self._params], *[p(t) for t in self._bufs], p(idx), K, B, self.D,
+                                          1 if apply else 0, p(self.hyper), p(self.grad), p(self.m), p(self.v),
+                                          p(self.step_count), p(self.stats))
+
+    def _step_guarded(self, idx, K, B):
+        u = self._set_struct(idx, K, B)
+        self._native.check(self._guarded_update(self._C.byref(u), self._C.byref(self._guard), self._stream()))
 
     def begin_update(self):
         """Where SB3 enters train(): every member runs again and the statistics start over.  One memset on the current
@@ -324,26 +394,7 @@ class _KlGuard:
                  "last_approx_kl": r[2], "last_clip_fraction": r[3]} for r, f in zip(d, stopped)]
 
 
-# observation widths the fused minibatch update is built for: acas2d_ppo_update_f32 (a lane holds its observation row in
-# registers; n_traffic 1, 2, 3, 4, 8) and acas2d_ppo_update_wide_f32 (four waves tile it through LDS; n_traffic 16, 32, 64)
-FUSED_UPDATE_WIDTHS = (8, 11, 14, 17, 29)
-FUSED_UPDATE_WIDE_WIDTHS = (53, 101, 197)
-# the 13 parameter tensors in FusedUpdate's order (the flat grad / moment layout of include/acas2d.h)
-PARAM_NAMES = ("mlp_extractor.policy_net.0.weight", "mlp_extractor.policy_net.0.bias",
-               "mlp_extractor.policy_net.2.weight", "mlp_extractor.policy_net.2.bias", "action_net.weight", "action_net.bias",
-               "mlp_extractor.value_net.0.weight", "mlp_extractor.value_net.0.bias",
-               "mlp_extractor.value_net.2.weight", "mlp_extractor.value_net.2.bias", "value_net.weight", "value_net.bias",
-               "log_std")
-
-
-def _flat_rollout(obs, act, old_logp, adv, ret):
-    """The five rollout buffers as the update kernels take them: obs [n, D], the others [n] (views of the storage)."""
-    bufs = [t.reshape(-1) if i else t.reshape(-1, obs.shape[-1]) for i, t in enumerate((obs, act, old_logp, adv, ret))]
-    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in bufs)
-    return bufs
-
-
-class FusedUpdate(_KlGuard):
+class FusedUpdate(_FusedUpdater):
     """One PPO minibatch update as two hand-written launches (acas2d_ppo_update_f32, csrc/acas2d_ppo.hip; for obs_dim
     53, 101, 197 acas2d_ppo_update_wide_f32, csrc/acas2d_ppo_wide.hip -- `entry` names the one chosen): forward,
     ppo_loss(), backward, clip_grad_norm_ and Adam for the SB3 MlpPolicy actor-critic, on the parameter tensors in
@@ -351,59 +402,30 @@ class FusedUpdate(_KlGuard):
     must stay put), `idx` an int64 device tensor naming the minibatch's rows (rewritten by the caller between
     calls).  Keeps its own Adam moments (torch.optim.Adam's arithmetic, eps 1e-5 as SB3 sets it).
     With `cfg.target_kl` or `diagnostics=True` every step goes through acas2d_ppo_update_guarded_set_f32 instead, as a
-    population of one (`guarded`; the hyper-parameters are then the config's at construction): call begin_update() once
-    per PPO update, step() for every minibatch whether the learner has stopped or not, and read diagnostics()
-    afterwards.  Otherwise the calls are the ones above and begin_update() does nothing."""
+    population of one (`guarded`; the hyper-parameters are then `hyper`, the config's at construction): call
+    begin_update() once per PPO update, step() for every minibatch whether the learner has stopped or not, and read
+    diagnostics() afterwards.  Otherwise the calls are the ones above and begin_update() does nothing."""
+    _symbol, _got = 1, ", got"
 
     def __init__(self, policy, cfg, obs, act, old_logp, adv, ret, beta1=0.9, beta2=0.999, adam_eps=1e-5,
                  diagnostics=False):
-        import ctypes as C
-        from . import native
-        D = obs.shape[-1]
-        if D in FUSED_UPDATE_WIDTHS:
-            self.entry = "acas2d_ppo_update_f32"
-        elif D in FUSED_UPDATE_WIDE_WIDTHS:
-            self.entry = "acas2d_ppo_update_wide_f32"
-        else:
-            raise ValueError("FusedUpdate is built for obs_dim in {8, 11, 14, 17, 29} (n_traffic 1, 2, 3, 4, 8: "
-                             "acas2d_ppo_update_f32) and {53, 101, 197} (n_traffic 16, 32, 64: acas2d_ppo_update_wide_f32), "
-                             "got %d" % D)
-        self._C, self._native, self._lib = C, native, native.lib()
-        self._update = getattr(self._lib, self.entry)
-        dev = obs.device
-        n = int(self._lib.acas2d_ppo_workspace_floats(D))
-        z = lambda k, dt=torch.float32: torch.zeros(k, dtype=dt, device=dev)  # noqa: E731
-        self.grad, self.m, self.v, self.step_count, self.stats = z(n), z(n), z(n), z(1, torch.int32), z(8)
-        self._params = [policy.get_parameter(name) for name in PARAM_NAMES]
-        assert all(p.dtype == torch.float32 and p.is_contiguous() and p.device == dev for p in self._params)
-        self._bufs = _flat_rollout(obs, act, old_logp, adv, ret)
-        self.cfg, self.D, self.betas, self.adam_eps, self.device = cfg, D, (beta1, beta2), adam_eps, dev
-        self._init_guard([cfg], diagnostics, dev)
-        if self.guarded:
-            self.hyper = torch.tensor([[cfg.clip_range, cfg.vf_coef, cfg.ent_coef, cfg.max_grad_norm, cfg.learning_rate,
-                                        beta1, beta2, adam_eps]], dtype=torch.float32).to(dev)
+        super().__init__([policy.get_parameter(name) for name in PARAM_NAMES], [cfg], (obs, act, old_logp, adv, ret), (),
+                         beta1, beta2, adam_eps, diagnostics)
+        self.cfg, self.betas, self.adam_eps = cfg, (beta1, beta2), adam_eps
 
     def _struct(self, idx):
         assert idx.dtype == torch.int64 and idx.is_contiguous()
         p = lambda t: t.data_ptr()  # noqa: E731
-        cfg = self.cfg
         return self._native.CPpoUpdate(*[p(t) for t in self._params], *[p(t) for t in self._bufs], p(idx), idx.numel(), self.D,
-                                       cfg.clip_range, cfg.vf_coef, cfg.ent_coef, cfg.max_grad_norm, cfg.learning_rate,
-                                       self.betas[0], self.betas[1], self.adam_eps, p(self.grad), p(self.m), p(self.v),
+                                       *hyper_row(self.cfg, *self.betas, self.adam_eps), p(self.grad), p(self.m), p(self.v),
                                        p(self.step_count), p(self.stats))
 
     def step(self, idx):
-        stream = self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         if self.guarded:                                  # the learner's tensors are K = 1 stacks
-            assert idx.dtype == torch.int64 and idx.is_contiguous()
-            p = lambda t: t.data_ptr()  # noqa: E731
-            u = self._native.CPpoUpdateSet(*[p(t) for t in self._params], *[p(t) for t in self._bufs], p(idx), 1, idx.numel(),
-                                           self.D, 1, p(self.hyper), p(self.grad), p(self.m), p(self.v), p(self.step_count),
-                                           p(self.stats))
-            self._native.check(self._guarded_update(self._C.byref(u), self._C.byref(self._guard), stream))
+            self._step_guarded(idx, 1, idx.numel())
             return
         u = self._struct(idx)
-        self._native.check(self._update(self._C.byref(u), stream))
+        self._native.check(self._update(self._C.byref(u), self._stream()))
 
     def last_losses(self):
         s = self.stats.cpu().tolist()
@@ -467,7 +489,104 @@ class _Callbacks:
         save_sb3_policy(self.policy(), os.path.join(self.save_dir, "checkpoints", "model_%d_steps.zip" % timesteps))
 
 
-class PPOTrainer:
+def minibatch_buffers(n, batch_size, device, lead=()):
+    """The static index buffers of an update over n rows (each with the leading shape `lead`: a population's (K,)):
+    `mb_idx` for the whole minibatches of B = min(batch_size, n) rows and `mb_tail` for the partial last one of an epoch,
+    as SB3 takes it -- None if there is none or it is ONE row: the advantage normalisation divides by the standard
+    deviation of the minibatch, which one row does not have (NaN in SB3 as well)."""
+    B = min(batch_size, n)
+    mb_idx = torch.zeros(*lead, B, dtype=torch.int64, device=device)
+    return mb_idx, (torch.zeros(*lead, n % B, dtype=torch.int64, device=device) if n % B > 1 else None)
+
+
+def minibatch_schedule(rows, mb_idx, mb_tail):
+    """One epoch: `rows` ([n], or [K, n]) is its permutation; every whole minibatch is copied into `mb_idx` and that
+    buffer yielded, then the partial one through `mb_tail` where there is one."""
+    n, B = rows.shape[-1], mb_idx.shape[-1]
+    for i in range(0, n - B + 1, B):
+        mb_idx.copy_(rows[..., i:i + B])
+        yield mb_idx
+    if mb_tail is not None:
+        mb_tail.copy_(rows[..., n - n % B:])
+        yield mb_tail
+
+
+class _Trainer:
+    """What PPOTrainer and PopulationTrainer share: the static [T, E] rollout buffers `b_*`, the intake of a fused
+    collection into them, and learn()'s loop."""
+
+    def _alloc_rollout(self):
+        E, T, D, dev = self.venv.num_envs, self.cfg.n_steps, self.venv.obs_dim, self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        # zeros, not empty: PPOTrainer's capture warm-up runs GAE and two updates over the whole buffer
+        self.b_obs = torch.zeros(T, E, D, **f32)
+        self.b_act = torch.zeros(T, E, 1, **f32)
+        self.b_logp, self.b_val, self.b_rew = (torch.zeros(T, E, **f32) for _ in range(3))
+        self.b_adv, self.b_ret, self.b_epret = (torch.zeros(T, E, **f32) for _ in range(3))
+        self.b_done = torch.zeros(T, E, dtype=torch.bool, device=dev)
+        self.b_eplen = torch.zeros(T, E, dtype=torch.int32, device=dev)
+        self.b_outcome = torch.zeros(T, E, dtype=torch.uint8, device=dev)
+
+    def _store_collection(self, out):
+        """A fused collector's dict (ACAS2DVecEnv.collect / collect_set) into the buffers and `self.obs`, cast to float32
+        first and then cleaned of NaN.  Returns the NaN events per sample, int64 [T, E]."""
+        T = self.b_obs.shape[0]
+        obs_all, rew = out["obs"].to(torch.float32), out["reward"].to(torch.float32)
+        nan = torch.isnan(rew).to(torch.int64) + torch.isnan(obs_all[1:]).any(-1)
+        obs_all = torch.nan_to_num(obs_all, nan=0.0, posinf=0.0, neginf=0.0)    # what the kernel fed the networks
+        self.b_obs.copy_(obs_all[:T])
+        self.obs.copy_(obs_all[T])
+        self.b_act.copy_(out["actions"].to(torch.float32).unsqueeze(-1))
+        self.b_val.copy_(out["values"].to(torch.float32))
+        self.b_logp.copy_(out["logp"].to(torch.float32))
+        self.b_rew.copy_(torch.nan_to_num(rew, nan=0.0))
+        self.b_done.copy_(out["done"])
+        self.b_epret.copy_(out["episode_return"].to(torch.float32))
+        self.b_eplen.copy_(out["episode_steps"])
+        self.b_outcome.copy_(out["outcome"])
+        return nan
+
+    def _evaluate_rows(self, policies, group, n_episodes, rng):
+        """evaluate_policies_fused() of `policies` on `n_episodes` fresh episodes drawn from `rng`: rows = policies."""
+        from . import reset_parity
+        from .policy import evaluate_policies_fused
+        own, trf, goal = reset_parity.draw_episodes(self.venv.config, n_episodes, rng)
+        return evaluate_policies_fused(policies, own, trf, goal, dtype=self.venv.dtype, device=self.device,
+                                       config=self.venv.config, group=group)
+
+    def _learn(self, total_timesteps, log, books, history, iterate, evaluate, eval_every, checkpoint_every):
+        """learn() for the learners whose bookkeeping `books` holds (one _Callbacks each): iterate() runs one iteration
+        and returns per learner the update's statistics, the recent episodes and the NaN events so far; evaluate() gives
+        evaluate_policies_fused()'s dict, one row per learner."""
+        t0 = time.time()
+        it = 0
+        while self.num_timesteps < total_timesteps:
+            before = self.num_timesteps
+            stats, eps, nan = iterate()
+            it += 1
+            for k, book in enumerate(books):
+                rec = {**book.head, "iteration": it, "timesteps": self.num_timesteps,
+                       "fps": self.num_timesteps / max(time.time() - t0, 1e-9), **(eps[k] or {}), **stats[k],
+                       "nan_events": int(nan[k])}
+                history.append(rec)
+                if log:
+                    log(rec)
+            crossed = lambda every: bool(every) and before // every < self.num_timesteps // every  # noqa: E731
+            if crossed(eval_every):
+                out = evaluate()
+                for k, book in enumerate(books):
+                    erec = book.evaluated(self.num_timesteps, out["total_reward"][k], out["steps"][k], out["outcome"][k],
+                                          out["unfinished"][k])
+                    history.append(erec)
+                    if log:
+                        log(erec)
+            if crossed(checkpoint_every):
+                for book in books:
+                    book.checkpoint(self.num_timesteps)
+        return history
+
+
+class PPOTrainer(_Trainer):
     """collector: "graphs" (default on a GPU: one captured env step replayed n_steps times), "fused" (the whole
     collection of an iteration in ONE hand-written launch, ACAS2DVecEnv.collect(): actor, critic, Gaussian sampling
     and the env step inside the kernel; its noise comes from the kernel's own Philox stream instead of torch's
@@ -545,19 +664,10 @@ class PPOTrainer:
         self.ep_returns, self.ep_lengths, self.ep_outcomes = [], [], []
         self._graphs = None
 
-    # ---- rollout buffers (static: the graphs write into them) ------------------------------------
     def _alloc(self):
-        E, T, D, dev = self.venv.num_envs, self.cfg.n_steps, self.venv.obs_dim, self.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        # zeros, not empty: the capture warm-up below runs GAE and two updates over the whole buffer
-        self.b_obs = torch.zeros(T, E, D, **f32)
-        self.b_act = torch.zeros(T, E, 1, **f32)
-        self.b_logp, self.b_val, self.b_rew = (torch.zeros(T, E, **f32) for _ in range(3))
-        self.b_adv, self.b_ret, self.b_epret = (torch.zeros(T, E, **f32) for _ in range(3))
-        self.b_done = torch.zeros(T, E, dtype=torch.bool, device=dev)
-        self.b_eplen = torch.zeros(T, E, dtype=torch.int32, device=dev)
-        self.b_outcome = torch.zeros(T, E, dtype=torch.uint8, device=dev)
-        self.t_idx = torch.zeros(1, dtype=torch.int64, device=dev)
+        """The rollout buffers (static: the graphs write into them) and the collector graph's row counter."""
+        self._alloc_rollout()
+        self.t_idx = torch.zeros(1, dtype=torch.int64, device=self.device)
 
     def _collect_step(self):
         """One env step of SB3's collect_rollouts into row t_idx of the buffers (graph-capturable:
@@ -610,12 +720,7 @@ class PPOTrainer:
         observation, the parameters and the Adam state are put back IN PLACE afterwards (the graphs
         hold their addresses), so training starts from exactly the state it was constructed in."""
         self._alloc()
-        n = self.cfg.n_steps * self.venv.num_envs
-        B = min(self.cfg.batch_size, n)
-        self.mb_idx = torch.zeros(B, dtype=torch.int64, device=self.device)
-        # the partial last minibatch of an epoch, as SB3 takes it -- unless it is ONE row: the advantage normalisation
-        # divides by the standard deviation of the minibatch, which one row does not have (NaN in SB3 as well)
-        self.mb_tail = torch.zeros(n % B, dtype=torch.int64, device=self.device) if n % B > 1 else None
+        self.mb_idx, self.mb_tail = minibatch_buffers(self.cfg.n_steps * self.venv.num_envs, self.cfg.batch_size, self.device)
         env_before = self.venv.state_dict()
         obs_before, env_obs_before = self.obs.clone(), self.venv.outputs["obs"].clone()
         params_before = [p.detach().clone() for p in self.policy.parameters()]
@@ -671,19 +776,7 @@ class PPOTrainer:
                 out = self.venv.collect(self.policy, T, noise_seed=cfg.seed, noise_step=self.num_timesteps // E,
                                         out=self._fused_out, group=self._group)
                 self._fused_out = out
-                obs_all, rew = out["obs"].to(torch.float32), out["reward"].to(torch.float32)
-                self.nan_events.add_(torch.isnan(rew).sum() + torch.isnan(obs_all[1:]).any(-1).sum())
-                obs_all = torch.nan_to_num(obs_all, nan=0.0, posinf=0.0, neginf=0.0)    # what the kernel fed the networks
-                self.b_obs.copy_(obs_all[:T])
-                self.obs.copy_(obs_all[T])
-                self.b_act.copy_(out["actions"].to(torch.float32).unsqueeze(-1))
-                self.b_val.copy_(out["values"].to(torch.float32))
-                self.b_logp.copy_(out["logp"].to(torch.float32))
-                self.b_rew.copy_(torch.nan_to_num(rew, nan=0.0))
-                self.b_done.copy_(out["done"])
-                self.b_epret.copy_(out["episode_return"].to(torch.float32))
-                self.b_eplen.copy_(out["episode_steps"])
-                self.b_outcome.copy_(out["outcome"])
+                self.nan_events.add_(self._store_collection(out).sum())
             else:
                 self.t_idx.zero_()
                 for _ in range(T):
@@ -735,20 +828,15 @@ class PPOTrainer:
     def update(self, obs=None, act=None, old_logp=None, adv=None, ret=None, old_val=None):
         cfg = self.cfg
         if self.use_graphs and self.updater == "fused":
-            n, B = cfg.n_steps * self.venv.num_envs, self.mb_idx.numel()
+            n = cfg.n_steps * self.venv.num_envs
             if self._fused_update is None:
                 self._fused_update = FusedUpdate(self.policy, cfg, self.b_obs, self.b_act, self.b_logp, self.b_adv, self.b_ret,
                                                  diagnostics=self.diagnostics)
             fu = self._fused_update
             fu.begin_update()
             for _ in range(cfg.n_epochs):
-                perm = torch.randperm(n, device=self.device)
-                for i in range(0, n - B + 1, B):
-                    self.mb_idx.copy_(perm[i:i + B])
-                    fu.step(self.mb_idx)
-                if self.mb_tail is not None:
-                    self.mb_tail.copy_(perm[n - n % B:])
-                    fu.step(self.mb_tail)
+                for idx in minibatch_schedule(torch.randperm(n, device=self.device), self.mb_idx, self.mb_tail):
+                    fu.step(idx)
             st = fu.last_losses()
             out = {"pg_loss": st["pg_loss"], "value_loss": st["value_loss"], "std": self.policy.log_std.detach().exp().item()}
             if fu.guarded:
@@ -757,15 +845,11 @@ class PPOTrainer:
                 out["explained_variance"] = explained_variance(self.b_val.reshape(-1), self.b_ret.reshape(-1)).item()
             return out
         if self.use_graphs:
-            n, B = cfg.n_steps * self.venv.num_envs, self.mb_idx.numel()
+            n = cfg.n_steps * self.venv.num_envs
             for _ in range(cfg.n_epochs):
-                perm = torch.randperm(n, device=self.device)
-                for i in range(0, n - B + 1, B):          # whole minibatches: one static shape
-                    self.mb_idx.copy_(perm[i:i + B])
-                    self._graphs[2].replay()
-                if self.mb_tail is not None:              # ... and the partial one SB3 also takes, its own graph
-                    self.mb_tail.copy_(perm[n - n % B:])
-                    self._graphs[3].replay()
+                for idx in minibatch_schedule(torch.randperm(n, device=self.device), self.mb_idx, self.mb_tail):
+                    # whole minibatches: one static shape; the partial one SB3 also takes: its own graph
+                    self._graphs[2 if idx is self.mb_idx else 3].replay()
             return {"pg_loss": self._pg.item(), "value_loss": self._vf.item(),
                     "std": self.policy.log_std.detach().exp().item()}
         n = obs.shape[0]
@@ -821,11 +905,7 @@ class PPOTrainer:
         """Score the current actor deterministically on `n_episodes` fresh episodes drawn from `rng` (a `random.Random`
         fed to reset_parity, like the reference's eval env) in one launch (policy.evaluate_policies_fused, K = 1).
         Touches neither the training env, nor the captured graphs, nor any torch random stream."""
-        from . import reset_parity
-        from .policy import evaluate_policies_fused
-        own, trf, goal = reset_parity.draw_episodes(self.venv.config, n_episodes, rng)
-        out = evaluate_policies_fused([self.policy], own, trf, goal, dtype=self.venv.dtype, device=self.device,
-                                      config=self.venv.config, group=self._group)
+        out = self._evaluate_rows([self.policy], self._group, n_episodes, rng)
         return {k: (v[0] if k != "unfinished" else int(v[0])) for k, v in out.items()}
 
     def learn(self, total_timesteps, log=print, eval_every=None, eval_episodes=10, eval_seed=None, save_dir=None,
@@ -851,32 +931,15 @@ class PPOTrainer:
                                  "{1, 2, 3, 4} (float64), or the group-cooperative float32 launch: n_traffic in "
                                  "{16, 32, 64}; got %d" % self.venv.n_traffic)
             eval_rng = random.Random(self.cfg.seed if eval_seed is None else eval_seed)
-        book = _Callbacks(save_dir, lambda: self.policy)
-        t0 = time.time()
-        it = 0
-        history = []
-        while self.num_timesteps < total_timesteps:
-            before = self.num_timesteps
+
+        def iterate():
             batch = self.collect()
             stats = self.update() if batch is None else self.update(*batch)
-            it += 1
-            ep = self.recent_episodes() or {}
-            rec = {"iteration": it, "timesteps": self.num_timesteps,
-                   "fps": self.num_timesteps / max(time.time() - t0, 1e-9), **ep, **stats,
-                   "nan_events": int(self.nan_events)}
-            history.append(rec)
-            if log:
-                log(rec)
-            crossed = lambda every: bool(every) and before // every < self.num_timesteps // every  # noqa: E731
-            if crossed(eval_every):
-                out = self.evaluate(eval_episodes, eval_rng)
-                erec = book.evaluated(self.num_timesteps, out["total_reward"], out["steps"], out["outcome"], out["unfinished"])
-                history.append(erec)
-                if log:
-                    log(erec)
-            if crossed(checkpoint_every):
-                book.checkpoint(self.num_timesteps)
-        return history
+            return [stats], [self.recent_episodes()], [self.nan_events]
+
+        return self._learn(total_timesteps, log, [_Callbacks(save_dir, lambda: self.policy)], [], iterate,
+                           lambda: self._evaluate_rows([self.policy], self._group, eval_episodes, eval_rng), eval_every,
+                           checkpoint_every)
 
 
 # ---- K learners at once: the seeds or hyper-parameter sets of a sweep as ONE population ---------------------------------
@@ -884,8 +947,7 @@ class PPOTrainer:
 MEMBER_FIELDS = ("seed", "learning_rate", "clip_range", "ent_coef", "vf_coef", "max_grad_norm", "gamma", "gae_lambda",
                  "target_kl")
 SHARED_FIELDS = ("n_steps", "batch_size", "n_epochs")
-# hyper[k]: the row acas2d_ppo_update_set_f32 reads for member k (target_kl is not in it: FusedUpdateSet.target_kl)
-HYPER_SLOTS = ("clip_range", "vf_coef", "ent_coef", "max_grad_norm", "learning_rate", "beta1", "beta2", "adam_eps")
+# (HYPER_SLOTS, the row a member's hyper-parameters travel in, is defined beside hyper_row() above)
 
 
 class ActorCriticSet:
@@ -938,15 +1000,9 @@ class ActorCriticSet:
     def collector_weights(self):
         """The 13 stacks as acas2d_collect_set_f32 takes them: the first two layers of each net transposed
         ([K][D][64], [K][64][64]), the heads and biases flat, log_std [K]."""
-        p, K = self.params, self.n_members
-        t = lambda n: p[n].detach().transpose(1, 2).contiguous()  # noqa: E731
-        f = lambda n: p[n].detach().reshape(K, -1).contiguous()  # noqa: E731
-        out = []
-        for net, head in (("policy_net", "action_net"), ("value_net", "value_net")):
-            pre = "mlp_extractor.%s." % net
-            out += [t(pre + "0.weight"), f(pre + "0.bias"), t(pre + "2.weight"), f(pre + "2.bias"), f(head + ".weight"),
-                    f(head + ".bias")]
-        return out + [f("log_std").reshape(K)]
+        p = self.params
+        return (kernel_layout(*(p[n] for n in PARAM_NAMES[:6])) + kernel_layout(*(p[n] for n in PARAM_NAMES[6:12]))
+                + [p["log_std"].detach().reshape(self.n_members).contiguous()])
 
     @torch.no_grad()
     def values(self, obs):
@@ -959,7 +1015,7 @@ class ActorCriticSet:
         return torch.baddbmm(p["value_net.bias"].unsqueeze(1), h, p["value_net.weight"].transpose(1, 2)).reshape(-1)
 
 
-class FusedUpdateSet(_KlGuard):
+class FusedUpdateSet(_FusedUpdater):
     """FusedUpdate for the K members of an `ActorCriticSet` in two launches whatever K is (acas2d_ppo_update_set_f32,
     csrc/acas2d_ppo_set.hip; for obs_dim 53, 101, 197 acas2d_ppo_update_wide_set_f32, csrc/acas2d_ppo_wide_set.hip --
     `entry` names the one chosen).  `obs` [n, D], `act` / `old_logp` / `adv` / `ret` [n] are ONE flat float32 rollout buffer
@@ -973,48 +1029,27 @@ class FusedUpdateSet(_KlGuard):
     begin_update() once per PPO update, step() for every minibatch -- a stopped member's share of the two launches
     returns at once -- and read diagnostics() afterwards.  Otherwise the calls are the ones above."""
 
+    _symbol, _got = 2, ", float32; got"
+
     def __init__(self, policy_set, configs, obs, act, old_logp, adv, ret, beta1=0.9, beta2=0.999, adam_eps=1e-5,
                  diagnostics=False):
-        import ctypes as C
-        from . import native
         D, K = obs.shape[-1], policy_set.n_members
-        if D in FUSED_UPDATE_WIDTHS:
-            self.entry = "acas2d_ppo_update_set_f32"
-        elif D in FUSED_UPDATE_WIDE_WIDTHS:
-            self.entry = "acas2d_ppo_update_wide_set_f32"
-        else:
-            raise ValueError("FusedUpdateSet is built for obs_dim in {8, 11, 14, 17, 29} (n_traffic 1, 2, 3, 4, 8: "
-                             "acas2d_ppo_update_set_f32) and {53, 101, 197} (n_traffic 16, 32, 64: "
-                             "acas2d_ppo_update_wide_set_f32), float32; got %d" % D)
+        self._entry_for(D)
         if len(configs) != K or policy_set.obs_dim != D:
             raise ValueError("FusedUpdateSet needs one config per member and members of obs_dim %d" % D)
-        self._C, self._native, self._lib = C, native, native.lib()
-        self._update = getattr(self._lib, self.entry)
-        dev = obs.device
-        n = int(self._lib.acas2d_ppo_workspace_floats(D))
-        z = lambda *k, dt=torch.float32: torch.zeros(*k, dtype=dt, device=dev)  # noqa: E731
-        self.grad, self.m, self.v, self.step_count, self.stats = z(K, n), z(K, n), z(K, n), z(K, dt=torch.int32), z(K, 8)
-        self.hyper = torch.tensor([[c.clip_range, c.vf_coef, c.ent_coef, c.max_grad_norm, c.learning_rate, beta1, beta2,
-                                    adam_eps] for c in configs], dtype=torch.float32).to(dev)
-        self._params = [policy_set.params[name] for name in PARAM_NAMES]
-        assert all(p.dtype == torch.float32 and p.is_contiguous() and p.device == dev for p in self._params)
-        self._bufs = _flat_rollout(obs, act, old_logp, adv, ret)
-        self.policy_set, self.D, self.K, self.device = policy_set, D, K, dev
-        self._init_guard(list(configs), diagnostics, dev)
+        super().__init__([policy_set.params[name] for name in PARAM_NAMES], list(configs), (obs, act, old_logp, adv, ret),
+                         (K,), beta1, beta2, adam_eps, diagnostics)
+        self.policy_set, self.K = policy_set, K
 
     def step(self, idx, apply=True):
         """One minibatch update of every member; apply=False leaves the raw gradients in `grad` and applies nothing (the
         unguarded entry: a probe has no stop to decide)."""
-        assert idx.dtype == torch.int64 and idx.is_contiguous() and idx.dim() == 2 and idx.shape[0] == self.K
-        p = lambda t: t.data_ptr()  # noqa: E731
-        u = self._native.CPpoUpdateSet(*[p(t) for t in self._params], *[p(t) for t in self._bufs], p(idx), self.K,
-                                       idx.shape[1], self.D, 1 if apply else 0, p(self.hyper), p(self.grad), p(self.m),
-                                       p(self.v), p(self.step_count), p(self.stats))
-        stream = self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        assert idx.dim() == 2 and idx.shape[0] == self.K
         if self.guarded and apply:
-            self._native.check(self._guarded_update(self._C.byref(u), self._C.byref(self._guard), stream))
-        else:
-            self._native.check(self._update(self._C.byref(u), stream))
+            self._step_guarded(idx, self.K, idx.shape[1])
+            return
+        u = self._set_struct(idx, self.K, idx.shape[1], apply)
+        self._native.check(self._update(self._C.byref(u), self._stream()))
 
     def last_losses(self):
         s = self.stats.cpu()
@@ -1025,7 +1060,7 @@ class FusedUpdateSet(_KlGuard):
         return self._diagnostics()
 
 
-class PopulationTrainer:
+class PopulationTrainer(_Trainer):
     """K independent PPO learners trained side by side on ONE env: member k owns the envs [k EM, (k + 1) EM) of `venv`
     (EM = num_envs / K), collects with its own actor-critic and noise key, and is updated on its own rows with its own
     hyper-parameters -- one collection launch (ACAS2DVecEnv.collect_set), two launches per minibatch (FusedUpdateSet) and
@@ -1104,24 +1139,13 @@ class PopulationTrainer:
         self.ep_returns, self.ep_lengths, self.ep_outcomes = ([[] for _ in range(K)] for _ in range(3))
         self.history = []
         self._fused_out = self._fused_update = None
-        E, T, D, dev = venv.num_envs, self.cfg.n_steps, venv.obs_dim, self.device
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.b_obs = torch.zeros(T, E, D, **f32)
-        self.b_act = torch.zeros(T, E, 1, **f32)
-        self.b_logp, self.b_val, self.b_rew = (torch.zeros(T, E, **f32) for _ in range(3))
-        self.b_adv, self.b_ret, self.b_epret = (torch.zeros(T, E, **f32) for _ in range(3))
-        self.b_done = torch.zeros(T, E, dtype=torch.bool, device=dev)
-        self.b_eplen = torch.zeros(T, E, dtype=torch.int32, device=dev)
-        self.b_outcome = torch.zeros(T, E, dtype=torch.uint8, device=dev)
-        self.last_value = torch.zeros(E, **f32)
+        E, T, dev = venv.num_envs, self.cfg.n_steps, self.device
+        self._alloc_rollout()
+        self.last_value = torch.zeros(E, dtype=torch.float32, device=dev)
         # member k's rows of the flat [T * E] buffer, in the order its own [T * EM] buffer would have them
         t_ = torch.arange(T, device=dev).unsqueeze(1) * E + torch.arange(self.EM, device=dev).unsqueeze(0)
         self.member_rows = (torch.arange(K, device=dev).view(K, 1, 1) * self.EM + t_.unsqueeze(0)).reshape(K, T * self.EM)
-        n = T * self.EM
-        B = min(self.cfg.batch_size, n)
-        self.mb_idx = torch.zeros(K, B, dtype=torch.int64, device=dev)
-        # the partial last minibatch of an epoch, as PPOTrainer takes it (not a single row: no standard deviation)
-        self.mb_tail = torch.zeros(K, n % B, dtype=torch.int64, device=dev) if n % B > 1 else None
+        self.mb_idx, self.mb_tail = minibatch_buffers(T * self.EM, self.cfg.batch_size, dev, lead=(K,))
 
     def member(self, k):
         """Member k's current actor-critic (a copy)."""
@@ -1132,20 +1156,7 @@ class PopulationTrainer:
         out = self.venv.collect_set(self.policy_set, T, self.noise_seeds, noise_step=self.num_timesteps // EM,
                                     out=self._fused_out, **({"group": True} if self.group else {}))
         self._fused_out = out
-        obs_all, rew = out["obs"], out["reward"]
-        nan = torch.isnan(rew).view(T, K, EM).sum((0, 2)) + torch.isnan(obs_all[1:]).any(-1).view(T, K, EM).sum((0, 2))
-        self.nan_events.add_(nan)
-        obs_all = torch.nan_to_num(obs_all, nan=0.0, posinf=0.0, neginf=0.0)    # what the kernel fed the networks
-        self.b_obs.copy_(obs_all[:T])
-        self.obs.copy_(obs_all[T])
-        self.b_act.copy_(out["actions"].unsqueeze(-1))
-        self.b_val.copy_(out["values"])
-        self.b_logp.copy_(out["logp"])
-        self.b_rew.copy_(torch.nan_to_num(rew, nan=0.0))
-        self.b_done.copy_(out["done"])
-        self.b_epret.copy_(out["episode_return"])
-        self.b_eplen.copy_(out["episode_steps"])
-        self.b_outcome.copy_(out["outcome"])
+        self.nan_events.add_(self._store_collection(out).view(T, K, EM).sum((0, 2)))
         self.last_value.copy_(self.policy_set.values(self.obs))
         if self.gae == "kernel":
             gae_fused(self.b_rew, self.b_val, self.b_done, self.last_value, n_members=K, constants=self._gae_constants,
@@ -1166,23 +1177,22 @@ class PopulationTrainer:
                     self.ep_outcomes[k].append(o[sel])
         self.num_timesteps += T * EM
 
+    def _make_fused_update(self):
+        return FusedUpdateSet(self.policy_set, self.configs, self.b_obs, self.b_act, self.b_logp, self.b_adv, self.b_ret,
+                              diagnostics=self.diagnostics)
+
     def update(self):
         cfg, K = self.cfg, self.K
-        n, B = cfg.n_steps * self.EM, self.mb_idx.shape[1]
+        n = cfg.n_steps * self.EM
         if self._fused_update is None:
-            self._fused_update = FusedUpdateSet(self.policy_set, self.configs, self.b_obs, self.b_act, self.b_logp, self.b_adv,
-                                                self.b_ret, diagnostics=self.diagnostics)
+            self._fused_update = self._make_fused_update()
         fu = self._fused_update
         fu.begin_update()
         for _ in range(cfg.n_epochs):
             perm = torch.stack([torch.randperm(n, device=self.device, generator=g) for g in self.generators])
             rows = self.member_rows.gather(1, perm)       # [K, n]: each member's permutation, as rows of the shared buffer
-            for i in range(0, n - B + 1, B):
-                self.mb_idx.copy_(rows[:, i:i + B])
-                fu.step(self.mb_idx)
-            if self.mb_tail is not None:
-                self.mb_tail.copy_(rows[:, n - n % B:])
-                fu.step(self.mb_tail)
+            for idx in minibatch_schedule(rows, self.mb_idx, self.mb_tail):
+                fu.step(idx)
         std = self.policy_set.params["log_std"].detach().exp().reshape(K).cpu().tolist()
         out = [{"pg_loss": st["pg_loss"], "value_loss": st["value_loss"], "std": std[k]}
                for k, st in enumerate(fu.last_losses())]
@@ -1211,11 +1221,7 @@ class PopulationTrainer:
     def evaluate(self, n_episodes, rng):
         """Score the K current actors deterministically on the SAME `n_episodes` fresh episodes drawn from `rng` in ONE
         launch (policy.evaluate_policies_fused): its dict, rows = members."""
-        from . import reset_parity
-        from .policy import evaluate_policies_fused
-        own, trf, goal = reset_parity.draw_episodes(self.venv.config, n_episodes, rng)
-        return evaluate_policies_fused(self.policy_set.actor_weights(), own, trf, goal, dtype=self.venv.dtype,
-                                       device=self.device, config=self.venv.config, group=self.group)
+        return self._evaluate_rows(self.policy_set.actor_weights(), self.group, n_episodes, rng)
 
     def learn(self, total_timesteps, log=print, eval_every=None, eval_episodes=10, eval_seed=None, save_dir=None,
               checkpoint_every=None):
@@ -1226,40 +1232,17 @@ class PopulationTrainer:
         under save_dir: results/evaluations.npz, best_model.zip (per member: its own best), checkpoints/."""
         if checkpoint_every and not save_dir:
             raise ValueError("checkpoint_every needs save_dir")
-        K = self.K
         eval_rng = random.Random(self.configs[0].seed if eval_seed is None else eval_seed) if eval_every else None
         books = [_Callbacks(save_dir and os.path.join(save_dir, "member_%d" % k), lambda k=k: self.member(k), {"member": k})
-                 for k in range(K)]
-        t0 = time.time()
-        it = 0
-        history = self.history
-        while self.num_timesteps < total_timesteps:
-            before = self.num_timesteps
+                 for k in range(self.K)]
+
+        def iterate():
             self.collect()
             stats = self.update()
-            it += 1
-            eps = self.recent_episodes()
-            nan = self.nan_events.cpu().tolist()
-            for k in range(K):
-                rec = {"member": k, "iteration": it, "timesteps": self.num_timesteps,
-                       "fps": self.num_timesteps / max(time.time() - t0, 1e-9), **(eps[k] or {}), **stats[k],
-                       "nan_events": int(nan[k])}
-                history.append(rec)
-                if log:
-                    log(rec)
-            crossed = lambda every: bool(every) and before // every < self.num_timesteps // every  # noqa: E731
-            if crossed(eval_every):
-                out = self.evaluate(eval_episodes, eval_rng)
-                for k in range(K):
-                    erec = books[k].evaluated(self.num_timesteps, out["total_reward"][k], out["steps"][k], out["outcome"][k],
-                                              out["unfinished"][k])
-                    history.append(erec)
-                    if log:
-                        log(erec)
-            if crossed(checkpoint_every):
-                for k in range(K):
-                    books[k].checkpoint(self.num_timesteps)
-        return history
+            return stats, self.recent_episodes(), self.nan_events.cpu().tolist()
+
+        return self._learn(total_timesteps, log, books, self.history, iterate,
+                           lambda: self.evaluate(eval_episodes, eval_rng), eval_every, checkpoint_every)
 
 
 # ---- population-based training: score, exploit and explore on the device (csrc/acas2d_pbt.hip) -------------------------
@@ -1402,8 +1385,7 @@ class PBTTrainer(PopulationTrainer):
         self.n_replace = pbt.n_replace(len(configs))
         super().__init__(venv, configs, gae=gae, group=group, diagnostics=diagnostics)
         # built now, not at the first update: an exploit before it must find the moments and the hyper row
-        self._fused_update = FusedUpdateSet(self.policy_set, self.configs, self.b_obs, self.b_act, self.b_logp, self.b_adv,
-                                            self.b_ret, diagnostics=self.diagnostics)
+        self._fused_update = self._make_fused_update()
         self.window = None
         self.generation = 0
         self._updates = 0

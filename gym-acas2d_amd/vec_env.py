@@ -20,6 +20,7 @@ import torch
 
 from . import native
 from .config import ACAS2DConfig
+from .policy import kernel_layout
 from .spaces import Box
 
 _STATE_FIELDS = ("own_x", "own_y", "own_psi", "own_v", "goal_x", "goal_y",
@@ -341,6 +342,41 @@ class ACAS2DVecEnv:
         io.actions = a.data_ptr()
         self._launch_step(io)
 
+    def _launch_out(self, obs_rows, T, extra=(), keep_terminal_obs=None, new=torch.empty):
+        """The dict of device tensors a whole-rollout launch writes: obs [obs_rows, E, D], the `extra` [T, E] tensors of
+        this env's dtype, reward, done_u8 / done, outcome, episode_return, episode_steps [T, E] and, unless
+        keep_terminal_obs is None, terminal_observation ([T, E, D], or None when False).  What a launch writes only
+        where an episode ended is zeroed; the rest comes from `new`."""
+        E, D = self.num_envs, self.obs_dim
+        te = lambda make, dt=self.dtype: make(T, E, dtype=dt, device=self.device)  # noqa: E731
+        out = {"obs": new(obs_rows, E, D, dtype=self.dtype, device=self.device), **{k: te(new) for k in extra},
+               "reward": te(new), "done_u8": te(new, torch.uint8), "outcome": te(new, torch.uint8),
+               "episode_return": te(torch.zeros), "episode_steps": te(torch.zeros, torch.int32)}
+        if keep_terminal_obs is not None:
+            out["terminal_observation"] = (torch.zeros(T, E, D, dtype=self.dtype, device=self.device)
+                                           if keep_terminal_obs else None)
+        out["done"] = out["done_u8"].view(torch.bool)
+        return out
+
+    def _launch_collect(self, fn, keep, T, out, noise_seed, noise_step, set_args=()):
+        """collect() and collect_set() from the output dict to the launch: `fn` reads the 13 weight tensors `keep`;
+        set_args is collect_set's (K, pointer to the members' noise keys)."""
+        if out is None:
+            out = self._launch_out(T + 1, T, ("actions", "values", "logp"), new=torch.zeros)
+        assert out["obs"].shape == (T + 1, self.num_envs, self.obs_dim)
+        ptr = lambda t: t.data_ptr()  # noqa: E731
+        with torch.cuda.device(self.device):
+            out["obs"][0].copy_(self._obs)
+            io = native.CStepIO(ptr(out["actions"]), ptr(out["obs"][1:]), ptr(out["reward"]), ptr(out["done_u8"]),
+                                ptr(out["outcome"]), None, ptr(out["episode_return"]), ptr(out["episode_steps"]))
+            ac = native.CActorCritic(native.CPolicy(*[ptr(t) for t in keep[:6]], 64, 0), *[ptr(t) for t in keep[6:]],
+                                     ptr(out["values"]), ptr(out["logp"]), noise_seed, int(noise_step) & 0xFFFFFFFF, 0)
+            native.check(fn(C.byref(self._ccfg), C.byref(self._cstate), C.byref(io), C.byref(ac), *set_args,
+                            ptr(out["obs"][0]), T, self.seed_value, self.env_offset, self.num_envs, self.n_traffic,
+                            self._stream()))
+            self._obs.copy_(out["obs"][T])            # the observation the NEXT action(s) would be drawn on
+        return out
+
     def rollout(self, actions, out=None, keep_terminal_obs=False):
         """T consecutive step() calls fused into ONE kernel launch (acas2d_rollout_*): the inner loop
         of a rollout collector when the actions are known up front (scripted / random policies:
@@ -361,15 +397,7 @@ class ACAS2DVecEnv:
         a = a.contiguous()
         dev = self.device
         if out is None:
-            out = {"obs": torch.empty(T, E, D, dtype=self.dtype, device=dev),
-                   "reward": torch.empty(T, E, dtype=self.dtype, device=dev),
-                   "done_u8": torch.empty(T, E, dtype=torch.uint8, device=dev),
-                   "outcome": torch.empty(T, E, dtype=torch.uint8, device=dev),
-                   "episode_return": torch.zeros(T, E, dtype=self.dtype, device=dev),
-                   "episode_steps": torch.zeros(T, E, dtype=torch.int32, device=dev),
-                   "terminal_observation": (torch.zeros(T, E, D, dtype=self.dtype, device=dev)
-                                            if keep_terminal_obs else None)}
-            out["done"] = out["done_u8"].view(torch.bool)
+            out = self._launch_out(T, T, keep_terminal_obs=keep_terminal_obs)
         assert out["obs"].shape == (T, E, D)
         ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         io = native.CStepIO(ptr(a), ptr(out["obs"]), ptr(out["reward"]), ptr(out["done_u8"]), ptr(out["outcome"]),
@@ -412,19 +440,9 @@ class ACAS2DVecEnv:
         if w1.shape != (64, D) or w2.shape != (64, 64) or w3.numel() != 64:
             raise ValueError("policy must be the SB3 MlpPolicy actor %d -> 64 -> 64 -> 1, got %s %s %s"
                              % (D, tuple(w1.shape), tuple(w2.shape), tuple(w3.shape)))
-        keep = [w1.t().contiguous(), b1.contiguous(), w2.t().contiguous(), b2.contiguous(),
-                w3.reshape(-1).contiguous(), b3.reshape(-1).contiguous()]
+        keep = kernel_layout(w1, b1, w2, b2, w3, b3)
         if out is None:
-            out = {"obs": torch.empty(T, E, D, dtype=self.dtype, device=dev),
-                   "actions": torch.empty(T, E, dtype=self.dtype, device=dev),
-                   "reward": torch.empty(T, E, dtype=self.dtype, device=dev),
-                   "done_u8": torch.empty(T, E, dtype=torch.uint8, device=dev),
-                   "outcome": torch.empty(T, E, dtype=torch.uint8, device=dev),
-                   "episode_return": torch.zeros(T, E, dtype=self.dtype, device=dev),
-                   "episode_steps": torch.zeros(T, E, dtype=torch.int32, device=dev),
-                   "terminal_observation": (torch.zeros(T, E, D, dtype=self.dtype, device=dev)
-                                            if keep_terminal_obs else None)}
-            out["done"] = out["done_u8"].view(torch.bool)
+            out = self._launch_out(T, T, ("actions",), keep_terminal_obs)
         assert out["obs"].shape == (T, E, D) and out["actions"].shape == (T, E)
         ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         io = native.CStepIO(ptr(out["actions"]), ptr(out["obs"]), ptr(out["reward"]), ptr(out["done_u8"]),
@@ -454,35 +472,16 @@ class ACAS2DVecEnv:
             fn = self._group_entry("collect", "acas2d_collect_group_f32")
         else:
             fn = self._lib.acas2d_collect_f32 if self.dtype == torch.float32 else self._lib.acas2d_collect_f64
-        T, E, D, dev = int(n_steps), self.num_envs, self.obs_dim, self.device
-        f32 = lambda t: t.detach().to(device=dev, dtype=torch.float32)  # noqa: E731
+        T, D, dev = int(n_steps), self.obs_dim, self.device
         pn, vn = policy.mlp_extractor.policy_net, policy.mlp_extractor.value_net
-        keep = [f32(pn[0].weight).t().contiguous(), f32(pn[0].bias).contiguous(), f32(pn[2].weight).t().contiguous(),
-                f32(pn[2].bias).contiguous(), f32(policy.action_net.weight).reshape(-1).contiguous(),
-                f32(policy.action_net.bias).reshape(-1).contiguous(),
-                f32(vn[0].weight).t().contiguous(), f32(vn[0].bias).contiguous(), f32(vn[2].weight).t().contiguous(),
-                f32(vn[2].bias).contiguous(), f32(policy.value_net.weight).reshape(-1).contiguous(),
-                f32(policy.value_net.bias).reshape(-1).contiguous(), f32(policy.log_std).reshape(-1).contiguous()]
+        keep = (kernel_layout(pn[0].weight, pn[0].bias, pn[2].weight, pn[2].bias, policy.action_net.weight,
+                              policy.action_net.bias, device=dev)
+                + kernel_layout(vn[0].weight, vn[0].bias, vn[2].weight, vn[2].bias, policy.value_net.weight,
+                                policy.value_net.bias, device=dev)
+                + [policy.log_std.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()])
         if keep[0].shape != (D, 64) or keep[2].shape != (64, 64) or keep[4].numel() != 64:
             raise ValueError("policy must be the SB3 MlpPolicy actor-critic %d -> 64 -> 64 -> 1" % D)
-        if out is None:
-            z = lambda *shape, dt=self.dtype: torch.zeros(*shape, dtype=dt, device=dev)  # noqa: E731
-            out = {"obs": z(T + 1, E, D), "actions": z(T, E), "values": z(T, E), "logp": z(T, E), "reward": z(T, E),
-                   "done_u8": z(T, E, dt=torch.uint8), "outcome": z(T, E, dt=torch.uint8), "episode_return": z(T, E),
-                   "episode_steps": z(T, E, dt=torch.int32)}
-            out["done"] = out["done_u8"].view(torch.bool)
-        assert out["obs"].shape == (T + 1, E, D)
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        with torch.cuda.device(dev):
-            out["obs"][0].copy_(self._obs)
-            io = native.CStepIO(ptr(out["actions"]), ptr(out["obs"][1:]), ptr(out["reward"]), ptr(out["done_u8"]),
-                                ptr(out["outcome"]), None, ptr(out["episode_return"]), ptr(out["episode_steps"]))
-            ac = native.CActorCritic(native.CPolicy(*[ptr(t) for t in keep[:6]], 64, 0), *[ptr(t) for t in keep[6:]],
-                                     ptr(out["values"]), ptr(out["logp"]), int(noise_seed) & (2 ** 64 - 1),
-                                     int(noise_step) & 0xFFFFFFFF, 0)
-            native.check(fn(C.byref(self._ccfg), C.byref(self._cstate), C.byref(io), C.byref(ac), ptr(out["obs"][0]), T,
-                            self.seed_value, self.env_offset, E, self.n_traffic, self._stream()))
-            self._obs.copy_(out["obs"][T])            # the observation the NEXT action would be drawn on
+        out = self._launch_collect(fn, keep, T, out, int(noise_seed) & (2 ** 64 - 1), noise_step)
         out["_weights"] = keep       # keep the transposed copies alive until the launch ran
         return out
 
@@ -527,7 +526,7 @@ class ACAS2DVecEnv:
         K = int(policy_set.n_members)
         self.check_member_split(K, group=group)
         fn = self._lib.acas2d_collect_set_group_f32 if group else self._lib.acas2d_collect_set_f32
-        T, E, D, dev = int(n_steps), self.num_envs, self.obs_dim, self.device
+        T, D, dev = int(n_steps), self.obs_dim, self.device
         if policy_set.obs_dim != D:
             raise ValueError("the set's members must be SB3 MlpPolicy actor-critics %d -> 64 -> 64 -> 1, got obs_dim %d"
                              % (D, policy_set.obs_dim))
@@ -538,24 +537,7 @@ class ACAS2DVecEnv:
             keys = torch.as_tensor(np.asarray([int(s) & (2 ** 64 - 1) for s in noise_seeds], np.uint64).view(np.int64)).to(dev)
         if keys.numel() != K:
             raise ValueError("collect_set() needs one noise seed per member: %d for %d members" % (keys.numel(), K))
-        if out is None:
-            z = lambda *shape, dt=self.dtype: torch.zeros(*shape, dtype=dt, device=dev)  # noqa: E731
-            out = {"obs": z(T + 1, E, D), "actions": z(T, E), "values": z(T, E), "logp": z(T, E), "reward": z(T, E),
-                   "done_u8": z(T, E, dt=torch.uint8), "outcome": z(T, E, dt=torch.uint8), "episode_return": z(T, E),
-                   "episode_steps": z(T, E, dt=torch.int32)}
-            out["done"] = out["done_u8"].view(torch.bool)
-        assert out["obs"].shape == (T + 1, E, D)
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        with torch.cuda.device(dev):
-            out["obs"][0].copy_(self._obs)
-            io = native.CStepIO(ptr(out["actions"]), ptr(out["obs"][1:]), ptr(out["reward"]), ptr(out["done_u8"]),
-                                ptr(out["outcome"]), None, ptr(out["episode_return"]), ptr(out["episode_steps"]))
-            ac = native.CActorCritic(native.CPolicy(*[ptr(t) for t in keep[:6]], 64, 0), *[ptr(t) for t in keep[6:]],
-                                     ptr(out["values"]), ptr(out["logp"]), 0, int(noise_step) & 0xFFFFFFFF, 0)
-            native.check(fn(
-                C.byref(self._ccfg), C.byref(self._cstate), C.byref(io), C.byref(ac), K, ptr(keys), ptr(out["obs"][0]), T,
-                self.seed_value, self.env_offset, E, self.n_traffic, self._stream()))
-            self._obs.copy_(out["obs"][T])            # the observation the NEXT actions would be drawn on
+        out = self._launch_collect(fn, keep, T, out, 0, noise_step, (K, keys.data_ptr()))
         out["_weights"] = keep + [keys]   # keep the transposed copies and the keys alive until the launch ran
         return out
 
