@@ -9,10 +9,14 @@ ppo.explained_variance), against the float64 restatement of tests/kl_guard_ref.p
        a float32 log-prob error of ~1e-6 enters (r - 1) - log r times |r - 1| -- and the clipped fraction exactly); the
        decision over three calls of K = 3 members; guard off == the unguarded entries bit for bit where one workgroup
        adds each gradient entry; begin_update(); the three trainers.
+The statistics, the bitwise identity and the decision over three calls run at every compiled width (8, 11, 14, 17, 29, 53,
+101, 197: all eight guarded instantiations are launched); tests/test_kl_guard_edges.py takes the same entry to the
+hand-placed edge minibatches, to B = 8 193, to the float32 boundary of the decision and through sentinels.
 Every criterion prints what it observed.
 
-Observed (MI355X): approx_kl at most 0.020 of its bound over the 40 statistics cases (2.0e-7 absolute, D = 53, K = 3,
-B = 2; at most 0.006 elsewhere); the clipped fraction exact in every case."""
+Observed (MI355X): approx_kl at most 0.081 of its bound over the 80 statistics cases (8.1e-7 absolute, D = 17, K = 3,
+B = 2; 0.055 at D = 17, K = 1, B = 2; 0.020 at D = 53, K = 3, B = 2; at most 0.006 elsewhere); the clipped fraction exact
+in every case.  The 141 GPU tests of this file take 9.7 s."""
 import ctypes as C
 import dataclasses
 import os
@@ -34,7 +38,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gym-acas2d_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 NARROW, WIDE = (8, 11, 14, 17, 29), (53, 101, 197)
-WIDTHS = (8, 29, 53, 197)              # both gradient bodies, the smallest and the largest width of each
+WIDTHS = NARROW + WIDE                 # every compiled guarded instantiation: what n_traffic 1, 2, 3, 4, 8, 16, 32, 64 take
 # bounds of tests/test_learner_kernels.py, unchanged
 TAU, TAU0, TAU_M, TAU_V = 2e-5, 1e-6, 2e-5, 5e-5
 GUARDED = "acas2d_ppo_update_guarded_set_f32"
@@ -267,8 +271,8 @@ def test_guarded_statistics_vs_float64(gpu, D, K, B):
     closed, the step applied.  Then a first-epoch minibatch (ratio ~ 1): approx_kl < 1e-6, clip_fraction == 0.
     B = 2 and 63 leave dead lanes, 64 fills one workgroup, 65 and 130 add a second (and third) whose atomics land in the
     same accumulator.
-    Observed on an MI355X: approx_kl at most 0.020 of the bound (2.0e-7 absolute; D = 53, K = 3, B = 2), at most 0.006 in
-    the other 39 cases."""
+    Observed on an MI355X: approx_kl at most 0.081 of the bound (8.1e-7 absolute; D = 17, K = 3, B = 2), 0.055 and 0.020 at
+    D = 17, K = 1 and D = 53, K = 3 (both B = 2), at most 0.006 in the other 77 cases."""
     g = gpu
     bt = KR.SharedBatch(g, D, K, K * B + 317, seed=6000 + 7 * D + 31 * K + B, device=DEV)
     cfgs = _cfgs(g, K)
@@ -419,11 +423,14 @@ IDENTITY_CASES = [(D, K, B) for D in WIDTHS for K in (1, 3) for B in (2, 63, 64)
 def test_guard_off_equals_the_unguarded_entries_bitwise(gpu, D, K, B):
     """B <= 64: every gradient entry receives one atomic add, so the result does not depend on their order.  With every
     target_kl zero, two guarded calls leave the parameters, moments, step counts and logged statistics of
-    acas2d_ppo_update_set_f32 (D = 8, 29) / acas2d_ppo_update_wide_set_f32 (D = 53, 197) on a twin, bit for bit; at K = 1
+    acas2d_ppo_update_set_f32 (D <= 29) / acas2d_ppo_update_wide_set_f32 (D >= 53) on a twin, bit for bit; at K = 1
     also those of the solo entries (FusedUpdate as it always was), through FusedUpdateSet's and FusedUpdate's guarded
     paths alike.  A difference here means the guard changed the shared arithmetic."""
     g = gpu
-    bt = KR.SharedBatch(g, D, K, K * B + 317, seed=8000 + 7 * D + 31 * K + B, device=DEV)
+    # (seeds from 8500: with the earlier 8000 the two minibatches of D = 101, K = 1, B = 2 hold four rows that the surrogate
+    # clips on the side where its gradient is exactly 0 -- float64 autograd gives no actor gradient either, and the
+    # `moved > 0` below, which looks at an actor matrix, cannot hold for any correct kernel; about 1 draw in 70 at B = 2)
+    bt = KR.SharedBatch(g, D, K, K * B + 317, seed=8500 + 7 * D + 31 * K + B, device=DEV)
     cfgs = _cfgs(g, K)
     twins = {"plain": bt.policy_set(), "guarded": bt.policy_set()}
     fus = {"plain": g.FusedUpdateSet(twins["plain"], cfgs, *bt.bufs),

@@ -1,10 +1,10 @@
 """The PPO update kernels -- acas2d_ppo_update_f32 (narrow), acas2d_ppo_update_wide_f32 (wide), acas2d_ppo_update_set_f32
-(set), which share the body of csrc/acas2d_ppo.hpp -- against float64 on the hand-placed edge minibatches of
+(set), acas2d_ppo_update_wide_set_f32 (wide set), which share the body of csrc/acas2d_ppo.hpp -- against float64 on the hand-placed edge minibatches of
 tests/edge_minibatches.py (admitted on the CPU by tests/test_edge_minibatches.py: plain float32 autograd clears a quarter
 of every bound used here), through FusedUpdate and FusedUpdateSet:
 
-  a  every case x family (narrow D = 8, 29; wide D = 53, 197; set D = 8, 29 with K = 3 members of their own policy,
-     clip_range and vf_coef) x B in (2, 65, 130): the raw gradient per tensor and one applied step from the kernel's own
+  a  every case x family (narrow D = 8, 29; wide D = 53, 197; set D = 8, 29 and wide set D = 53, 197 with K = 3 members of
+     their own policy, clip_range and vf_coef; `entry` is asserted) x B in (2, 65, 130): the raw gradient per tensor and one applied step from the kernel's own
      state; const_adv gives an exactly zero actor gradient and keeps every actor bit
   b  B = 8 193 (above anything a trainer here asks for): grid_adv and "mixed", D = 8 and 197, raw gradient
   c  Adam constants other than 0.9 / 0.999 / 1e-5, per member in the set, and a step count of 10 000 000
@@ -14,7 +14,7 @@ of every bound used here), through FusedUpdate and FusedUpdateSet:
 Criteria and bounds are test_learner_kernels.py's (TAU, TAU0, TAU_M, TAU_V, parameter excess 1e-2 lr, losses 1e-5),
 unchanged; every test prints what it observed.
 
-Observed on an MI355X (one run of this file: 161 passed in 8.7 s; the slowest test 0.39 s -- the first, which loads
+Observed on an MI355X (one run of this file: 161 passed in 8.7 s, 209 in 13.7 s with the wide set cases; the slowest test 0.39 s -- the first, which loads
 the library -- every other under 0.1 s; the two 8.6 GB cases ran, 0.07 s each).  No case exposed a fault in the kernels.
 Worst per-tensor tau over D and B, raw gradient / m / v (bounds 2e-5 / 2e-5 / 5e-5; negative: within the 1e-6 max |ref|
 term alone), and worst parameter excess in lr (bound 1e-2):
@@ -29,9 +29,21 @@ term alone), and worst parameter excess in lr (bound 1e-2):
   dup_rows      -3.2e-7 / -2.5e-7 / 1.26e-5, 5.6e-4  -1.3e-7 / -1.5e-7 / 1.30e-5, 1.7e-4  -3.0e-7 / -1.4e-7 / 1.31e-5, 3.9e-4
   underflow     -9.4e-7 / -6.5e-7 / 1.20e-5, 3.4e-5  -7.6e-7 / -5.8e-7 / 1.21e-5, 1.7e-4  -6.9e-7 / -5.7e-7 / 1.24e-5, 7.0e-5
 
+The set update at D = 53, 197 (acas2d_ppo_update_wide_set_f32; worst member, the same four figures):
+
+  case          wide set
+  saturated      2.6e-6 /  2.6e-6 / 1.22e-5, 1.4e-3
+  wide_obs       2.8e-7 /  4.8e-8 / 1.34e-5, 2.3e-3
+  grid_adv      -4.5e-7 / -4.6e-7 / 1.23e-5, 1.7e-4
+  const_adv     -6.5e-7 / -5.8e-7 / 1.21e-5, 1.8e-4
+  log_std-2.5    4.6e-7 /  5.1e-7 / 1.30e-5, 4.8e-4
+  log_std+1.0   -5.8e-7 / -6.1e-7 / 1.22e-5, 1.6e-4
+  dup_rows       1.7e-7 / -1.3e-7 / 1.32e-5, 2.1e-4
+  underflow      1.6e-7 /  5.9e-8 / 1.27e-5, 1.7e-4
+
 (v sits at 1.2e-5 everywhere: the float32 0.999, as in test_learner_kernels.py.)  The worst raw gradient is wide_obs at
 D = 197, B = 65, 3.0e-6 -- the case float32 torch autograd itself clears by least on the CPU (3.3e-6).  const_adv: actor
-tensors, log_std entry and pg exactly 0 in all 18 runs, every actor bit kept by the applied step.  B = 8 193: tau -8.0e-7
+tensors, log_std entry and pg exactly 0 in all 24 runs, every actor bit kept by the applied step.  B = 8 193: tau -8.0e-7
 (grid_adv) and -8.1e-7 (mixed) at worst.  Adam constants: (0.5, 0.9, 1e-3) m -8.5e-7, v -5.1e-7 (bound 3.7e-5), excess
 1.1e-6 lr; (0.8, 0.99, 1e-4) v 4.0e-8, excess 2.3e-6 lr; the defaults v 1.19e-5, excess 3.5e-5 lr -- the steps from
 10 000 000 included.  Shared rows: bit-equal in all four cases; overlapping rows and the rows past 2^31 floats -7.9e-7 at
@@ -115,7 +127,7 @@ def _check_applied(K, what, segs, theta1, m1, v1, theta_ref, m_ref, v_ref, lr, t
 
 # ---- a. every case, raw gradient and one applied step -------------------------------------------------------------------
 SOLO_CASES = [(D, B, case) for D in (8, 29, 53, 197) for B in (2, 65, 130) for case in E.CASES]
-SET_CASES = [(D, B, case) for D in (8, 29) for B in (2, 65, 130) for case in E.CASES]
+SET_CASES = [(D, B, case) for D in (8, 29, 53, 197) for B in (2, 65, 130) for case in E.CASES]
 _ID = lambda c: "D%d-B%d-%s" % c  # noqa: E731
 
 
@@ -186,7 +198,8 @@ def _theta_set(pset, k):
 @pytest.mark.parametrize("D,B,case", SET_CASES, ids=[_ID(c) for c in SET_CASES])
 def test_set_update_on_edge_minibatches_vs_float64(g, K, D, B, case):
     """The solo test for K = 3 members with their own policy, clip_range 0.1 / 0.2 / 0.3 and vf_coef 0.5 / 0.25 / 1.0 on
-    disjoint rows of one buffer: apply=False for the raw gradients, then one applied step of a fresh FusedUpdateSet."""
+    disjoint rows of one buffer: apply=False for the raw gradients, then one applied step of a fresh FusedUpdateSet.
+    D = 8, 29 take acas2d_ppo_update_set_f32, D = 53, 197 acas2d_ppo_update_wide_set_f32 (asserted on fu.entry)."""
     bt = _batch("set", D, B, case)
     idx = _dev(bt.idx)
     segs = R.segments(bt.pols[0])
@@ -199,6 +212,7 @@ def test_set_update_on_edge_minibatches_vs_float64(g, K, D, B, case):
 
     cf = cfgs(0.01, 0.5)
     pset, fu = _set_update(g, bt, cf)
+    assert fu.entry == ("acas2d_ppo_update_set_f32" if D < 53 else "acas2d_ppo_update_wide_set_f32")
     fu.step(idx, apply=False)
     torch.cuda.synchronize()
     assert fu.step_count.cpu().tolist() == [0] * bt.K and float(fu.m.abs().max()) == 0.0 and float(fu.v.abs().max()) == 0.0
