@@ -1,10 +1,12 @@
 // acas2d_ppo.hpp -- what the translation units of the PPO minibatch update share, each thing written once: the flat
 // gradient / moment layout, the d loss / d output block (loss_grad), the one-wave gradient body of the narrow widths
-// (grad_narrow<D>), the apply body (apply_body: norm, clip_grad_norm_, Adam), and the host helpers of the entry points
-// (pointer check, NetW pair, per-device LDS opt-in).  The __global__ kernels of acas2d_ppo.hip and acas2d_ppo_set.hip are
-// prologues in front of these bodies; those of acas2d_ppo_wide.hip and acas2d_ppo_wide_set.hip in front of grad_wide<D>
-// (acas2d_ppo_wide.hpp).  acas2d_ppo_guard.hip (target_kl) instantiates the gradient bodies with Guard = true; with the
-// default, false, they are the code they were before the guard existed.
+// (grad_narrow<D>), the prologue that takes member blockIdx.z of a [K][...] set in front of it (grad_narrow_member<D>),
+// the apply body (apply_body: norm, clip_grad_norm_, Adam), and the host helpers of the entry points (pointer check,
+// set check, NetW pair, per-device LDS opt-in).  ppo_grad_kernel<D> (acas2d_ppo.hip) is a prologue of its own in front of
+// grad_narrow<D>; ppo_grad_set_kernel<D> (acas2d_ppo_set.hip) and ppo_grad_guarded_set_kernel<D> (acas2d_ppo_guard.hip,
+// target_kl) are grad_narrow_member<D> with Guard = false and true.  The wide kernels stand likewise in front of
+// grad_wide<D> (acas2d_ppo_wide.hpp).  With Guard at its default, false, the gradient bodies are the code they were
+// before the guard existed.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -222,6 +224,35 @@ __device__ __forceinline__ void grad_narrow(const float ACAS2D_C4* w1, const flo
     }
 }
 
+// Member blockIdx.z of a set in front of grad_narrow: its slices of the [K][...] parameter stacks, its minibatch
+// idx[k][.], its gradient block grad[k], its stats[k], its clip_range and vf_coef from hyper[k] by scalar load (hyper[k]:
+// clip_range, vf_coef, ent_coef, max_grad_norm, learning_rate, beta1, beta2, adam_eps) and, Guard only, its diag[k].  The
+// rollout buffer (obs ... ret) is ONE flat buffer shared by all members; idx holds its global row numbers.
+template <int D, bool Guard = false>
+__device__ __forceinline__ void grad_narrow_member(const ParamPtrs& prm, const float* obs, const float* act,
+                                                   const float* old_logp, const float* adv, const float* ret,
+                                                   const int64_t* idx_all, int B, const float* hyper, float* grad_all,
+                                                   float* stats_all, float* lds, float* diag_all = nullptr) {
+    const bool is_actor = blockIdx.y == 0;
+    const size_t m = blockIdx.z;
+    const auto net = [&](int i) -> const float* { return is_actor ? prm.p[i] : prm.p[6 + i]; };
+    const float ACAS2D_C4* w1 = (const float ACAS2D_C4*)(net(0) + m * (kH * D));
+    const float ACAS2D_C4* b1 = (const float ACAS2D_C4*)(net(1) + m * kH);
+    const float ACAS2D_C4* w2 = (const float ACAS2D_C4*)(net(2) + m * (kH * kH));
+    const float ACAS2D_C4* b2 = (const float ACAS2D_C4*)(net(3) + m * kH);
+    const float ACAS2D_C4* w3 = (const float ACAS2D_C4*)(net(4) + m * kH);
+    const float ACAS2D_C4* b3 = (const float ACAS2D_C4*)(net(5) + m);
+    const float* log_std_p = prm.p[12] + m;
+    const int64_t* idx = idx_all + m * (size_t)B;
+    float* grad = grad_all + m * (size_t)(2 * net_size(D) + 1);
+    float* stats = stats_all + m * 8;
+    const float ACAS2D_C4* hy = (const float ACAS2D_C4*)(hyper + m * 8);
+    const float clip_range = hy[0], vf_coef = hy[1];
+
+    grad_narrow<D, Guard>(w1, b1, w2, b2, w3, b3, log_std_p, obs, act, old_logp, adv, ret, idx, B, clip_range, vf_coef, grad,
+                          stats, lds, Guard ? diag_all + m * 8 : nullptr);
+}
+
 // One 1 024-thread workgroup: the global gradient norm, torch.nn.utils.clip_grad_norm_'s coefficient, Adam
 // (torch.optim.Adam's bias-corrected form) on the 13 tensors prm.p[k] + member * seg_count(D, k) in place, gradient
 // zeroed for the next minibatch.  grad / m / v / step / stats are the learner's own; the gradient and the statistics
@@ -299,6 +330,15 @@ int check_update(const U* u, const char* entry, const void* more, const char* ro
     if (!ok) { set_error("%s: every pointer is required", entry); return ACAS2D_EINVAL; }
     if (u->n_rows >= 2) return ACAS2D_OK;
     set_error("%s: n_rows = %d (the advantage normalisation needs 2%s)", entry, u->n_rows, rows_note);
+    return ACAS2D_EINVAL;
+}
+
+// check_update for a set (hyper is required too), and 1 to 65535 members
+inline int check_set(const Acas2dPpoUpdateSet* u, const char* entry) {
+    const int rc = check_update(u, entry, u ? u->hyper : nullptr, "; every member takes the same number of rows");
+    if (rc != ACAS2D_OK) return rc;
+    if (u->n_members >= 1 && u->n_members <= 65535) return ACAS2D_OK;
+    set_error("%s: n_members = %d (1 to 65535 members, one grid plane each)", entry, u->n_members);
     return ACAS2D_EINVAL;
 }
 

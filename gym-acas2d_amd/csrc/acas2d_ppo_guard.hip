@@ -2,8 +2,10 @@
 // updates, decided on the device: acas2d_ppo_update_guarded_set_f32, the two launches of acas2d_ppo_update_set_f32 /
 // acas2d_ppo_update_wide_set_f32 at all eight widths, with no launch and no read-back added.
 //
-//   ppo_grad_guarded_set_kernel<D>        ppo_grad_set_kernel<D>'s prologue in front of grad_narrow<D, true>
-//   ppo_grad_wide_guarded_set_kernel<D>   ppo_grad_wide_set_kernel<D>'s in front of grad_wide<D, ., true>
+//   ppo_grad_guarded_set_kernel<D>        grad_narrow_member<D, true> (acas2d_ppo.hpp): ppo_grad_set_kernel<D>'s prologue,
+//                                         and the member's diag row, in front of grad_narrow<D, true>
+//   ppo_grad_wide_guarded_set_kernel<D>   a SetMember with the diag rows (acas2d_ppo_wide.hpp): ppo_grad_wide_set_kernel<D>'s
+//                                         prologue in front of grad_wide<D, ., true>
 //                         A workgroup of a member with stopped[k] != 0 returns at its top (uniform, the flag by scalar
 //                         load, before any LDS use or barrier).  Otherwise the arithmetic is the unguarded kernel's, and
 //                         an actor workgroup also adds its rows' (ratio - 1) - log ratio to diag[k][0] and its count of
@@ -44,50 +46,9 @@ __global__ __launch_bounds__(64) void ppo_grad_guarded_set_kernel(ParamPtrs prm,
                                                                   const float* hyper, float* grad_all, float* stats_all,
                                                                   const int32_t* stopped, float* diag_all) {
     extern __shared__ float lds[];
-    const size_t m = blockIdx.z;
     if (member_stopped(stopped, blockIdx.z)) return;
-    const bool is_actor = blockIdx.y == 0;
-    // ---- the member, as ppo_grad_set_kernel takes it (acas2d_ppo_set.hip), and its diag row
-    const auto net = [&](int i) -> const float* { return is_actor ? prm.p[i] : prm.p[6 + i]; };
-    const float ACAS2D_C4* w1 = (const float ACAS2D_C4*)(net(0) + m * (kH * D));
-    const float ACAS2D_C4* b1 = (const float ACAS2D_C4*)(net(1) + m * kH);
-    const float ACAS2D_C4* w2 = (const float ACAS2D_C4*)(net(2) + m * (kH * kH));
-    const float ACAS2D_C4* b2 = (const float ACAS2D_C4*)(net(3) + m * kH);
-    const float ACAS2D_C4* w3 = (const float ACAS2D_C4*)(net(4) + m * kH);
-    const float ACAS2D_C4* b3 = (const float ACAS2D_C4*)(net(5) + m);
-    const float* log_std_p = prm.p[12] + m;
-    const int64_t* idx = idx_all + m * (size_t)B;
-    float* grad = grad_all + m * (size_t)(2 * net_size(D) + 1);
-    float* stats = stats_all + m * 8;
-    const float ACAS2D_C4* hy = (const float ACAS2D_C4*)(hyper + m * 8);
-    const float clip_range = hy[0], vf_coef = hy[1];
-
-    grad_narrow<D, true>(w1, b1, w2, b2, w3, b3, log_std_p, obs, act, old_logp, adv, ret, idx, B, clip_range, vf_coef, grad,
-                         stats, lds, diag_all + m * 8);
+    grad_narrow_member<D, true>(prm, obs, act, old_logp, adv, ret, idx_all, B, hyper, grad_all, stats_all, lds, diag_all);
 }
-
-// the 13 [K][...] stacks as the two networks' rows and log_std: a workgroup reads the row it works on (blockIdx.y)
-struct SetNets { NetW n[2]; const float* log_std; };
-
-// member blockIdx.z of the set for grad_wide: acas2d_ppo_wide_set.hip's Member and the diag rows.  Every pointer of the
-// member is a sum formed where grad_wide asks for it (acas2d_ppo_wide.hpp says why), diag() among them.
-struct GuardedMember {
-    const SetNets& nets;
-    const int64_t* idx_all;
-    const float* hyper;                      // hyper[k]: clip_range, vf_coef, ... (acas2d_ppo_set.hip)
-    float *grad_all, *stats_all, *diag_all;
-    int B, total;                            // rows of a minibatch, floats of a gradient block
-    __device__ __forceinline__ size_t m() const { return blockIdx.z; }
-    __device__ __forceinline__ NetW net() const { return nets.n[blockIdx.y]; }
-    __device__ __forceinline__ size_t at(int per_member) const { return m() * (size_t)per_member; }
-    __device__ __forceinline__ const int64_t* idx() const { return idx_all + m() * (size_t)B; }
-    __device__ __forceinline__ const float* log_std() const { return nets.log_std + m(); }
-    __device__ __forceinline__ float clip_range() const { return ((const float ACAS2D_C4*)hyper)[m() * 8]; }
-    __device__ __forceinline__ float vf_coef() const { return ((const float ACAS2D_C4*)hyper)[m() * 8 + 1]; }
-    __device__ __forceinline__ float* grad() const { return grad_all + m() * (size_t)total; }
-    __device__ __forceinline__ float* stats() const { return stats_all + m() * 8; }
-    __device__ __forceinline__ float* diag() const { return diag_all + m() * 8; }
-};
 
 // `stopped` stands beside idx_all and B, the arguments the top of the kernel reads anyway: at the end of the list its
 // load takes hyper, grad_all and stats_all with it into SGPRs that layer 1 has no room for (12 to 15 spills).
@@ -99,8 +60,8 @@ __global__ __launch_bounds__(kThreads) void ppo_grad_wide_guarded_set_kernel(Set
                                                                              const float* hyper, float* grad_all,
                                                                              float* stats_all, float* diag_all) {
     if (member_stopped(stopped, blockIdx.z)) return;
-    grad_wide<D, GuardedMember, true>(GuardedMember{nets, idx_all, hyper, grad_all, stats_all, diag_all, B, 2 * net_size(D) + 1},
-                                      obs, act, old_logp, adv, ret, B);
+    grad_wide<D, SetMember, true>(SetMember{nets, idx_all, hyper, grad_all, stats_all, B, 2 * net_size(D) + 1, diag_all}, obs,
+                                  act, old_logp, adv, ret, B);
 }
 
 // hyper[k] as ppo_apply_set_kernel reads it; B: the rows of the minibatch the gradient launch summed over
@@ -157,13 +118,10 @@ int launch_grad_guarded(const Acas2dPpoUpdateSet& u, const Acas2dPpoGuard& g, hi
         constexpr size_t bytes = lds_bytes(D);
         const int rc = ensure_dynamic_lds<&ppo_grad_wide_guarded_set_kernel<D>>(bytes, kEntry);
         if (rc != ACAS2D_OK) return rc;
-        const ParamPtrs q = param_ptrs(u);
-        const SetNets nets{{{q.p[0], q.p[1], q.p[2], q.p[3], q.p[4], q.p[5]}, {q.p[6], q.p[7], q.p[8], q.p[9], q.p[10], q.p[11]}},
-                           q.p[12]};
-        hipLaunchKernelGGL((ppo_grad_wide_guarded_set_kernel<D>), grid, dim3(kThreads), bytes, stream, nets, (const float*)u.obs,
-                           (const float*)u.act, (const float*)u.old_logp, (const float*)u.adv, (const float*)u.ret,
-                           (const int64_t*)u.idx, (const int32_t*)g.stopped, u.n_rows, (const float*)u.hyper, (float*)u.grad,
-                           (float*)u.stats, (float*)g.diag);
+        hipLaunchKernelGGL((ppo_grad_wide_guarded_set_kernel<D>), grid, dim3(kThreads), bytes, stream, set_nets_of(u),
+                           (const float*)u.obs, (const float*)u.act, (const float*)u.old_logp, (const float*)u.adv,
+                           (const float*)u.ret, (const int64_t*)u.idx, (const int32_t*)g.stopped, u.n_rows,
+                           (const float*)u.hyper, (float*)u.grad, (float*)u.stats, (float*)g.diag);
     }
     return launched("acas2d_ppo_update_guarded_set gradient launch");
 }
@@ -178,12 +136,10 @@ extern "C" size_t acas2d_ppo_guard_size(void) { return sizeof(Acas2dPpoGuard); }
 
 extern "C" int acas2d_ppo_update_guarded_set_f32(const Acas2dPpoUpdateSet* u, const Acas2dPpoGuard* g, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    int rc = check_update(u, kEntry, u ? u->hyper : nullptr, "; every member takes the same number of rows");
+    int rc = check_set(u, kEntry);
     if (rc != ACAS2D_OK) return rc;
     if (!g || !g->target_kl || !g->stopped || !g->diag) {
         set_error("%s: the guard and its three pointers (target_kl, stopped, diag) are required", kEntry); return ACAS2D_EINVAL; }
-    if (u->n_members < 1 || u->n_members > 65535) {
-        set_error("%s: n_members = %d (1 to 65535 members, one grid plane each)", kEntry, u->n_members); return ACAS2D_EINVAL; }
     const int D = u->obs_dim;
     const bool known = D == 8 || D == 11 || D == 14 || D == 17 || D == 29 || D == 53 || D == 101 || D == 197;
     if (!known) {

@@ -3,11 +3,11 @@
 // 128 single-wave workgroups at a minibatch of 4 096 and one workgroup for Adam on a device with 256 CUs; here the K
 // learners lie side by side in the same two launches.
 //
-//   ppo_grad_set_kernel   grid (ceil(n_rows / 64), 2, K): blockIdx.z is the member.  The prologue takes the member's slices
-//                         of the [K][...] parameter stacks, its minibatch idx[k][.], its gradient block grad[k], and its
-//                         clip_range and vf_coef from hyper[k] by scalar load; the rest is grad_narrow<D> (acas2d_ppo.hpp),
-//                         the body ppo_grad_kernel<D> runs.  The rollout buffer is ONE flat buffer shared by all members;
-//                         idx holds its global row numbers.
+//   ppo_grad_set_kernel   grid (ceil(n_rows / 64), 2, K): blockIdx.z is the member.  It is grad_narrow_member<D>
+//                         (acas2d_ppo.hpp): the prologue that takes the member's slices of the [K][...] parameter stacks,
+//                         its minibatch idx[k][.], its gradient block grad[k], and its clip_range and vf_coef from
+//                         hyper[k] by scalar load, in front of grad_narrow<D>, the body ppo_grad_kernel<D> runs.  The
+//                         rollout buffer is ONE flat buffer shared by all members; idx holds its global row numbers.
 //   ppo_apply_set_kernel  grid (K), 1 024 threads: apply_body (acas2d_ppo.hpp), the body ppo_apply_kernel runs, on member
 //                         k's slices with hyper[k] and adam_step[k].
 //
@@ -27,25 +27,7 @@ __global__ __launch_bounds__(64) void ppo_grad_set_kernel(ParamPtrs prm, const f
                                                           const int64_t* idx_all, int B, const float* hyper, float* grad_all,
                                                           float* stats_all) {
     extern __shared__ float lds[];
-    const bool is_actor = blockIdx.y == 0;
-    // ---- the member: its slices of the stacks, its minibatch, its gradient block, its two hyper-parameters
-    const size_t m = blockIdx.z;
-    const auto net = [&](int i) -> const float* { return is_actor ? prm.p[i] : prm.p[6 + i]; };
-    const float ACAS2D_C4* w1 = (const float ACAS2D_C4*)(net(0) + m * (kH * D));
-    const float ACAS2D_C4* b1 = (const float ACAS2D_C4*)(net(1) + m * kH);
-    const float ACAS2D_C4* w2 = (const float ACAS2D_C4*)(net(2) + m * (kH * kH));
-    const float ACAS2D_C4* b2 = (const float ACAS2D_C4*)(net(3) + m * kH);
-    const float ACAS2D_C4* w3 = (const float ACAS2D_C4*)(net(4) + m * kH);
-    const float ACAS2D_C4* b3 = (const float ACAS2D_C4*)(net(5) + m);
-    const float* log_std_p = prm.p[12] + m;
-    const int64_t* idx = idx_all + m * (size_t)B;
-    float* grad = grad_all + m * (size_t)(2 * net_size(D) + 1);
-    float* stats = stats_all + m * 8;
-    const float ACAS2D_C4* hy = (const float ACAS2D_C4*)(hyper + m * 8);
-    const float clip_range = hy[0], vf_coef = hy[1];
-
-    grad_narrow<D>(w1, b1, w2, b2, w3, b3, log_std_p, obs, act, old_logp, adv, ret, idx, B, clip_range, vf_coef, grad, stats,
-                   lds);
+    grad_narrow_member<D>(prm, obs, act, old_logp, adv, ret, idx_all, B, hyper, grad_all, stats_all, lds);
 }
 
 // hyper[k]: clip_range, vf_coef, ent_coef, max_grad_norm, learning_rate, beta1, beta2, adam_eps
@@ -86,10 +68,8 @@ using namespace acas2d::ppo;
 
 extern "C" int acas2d_ppo_update_set_f32(const Acas2dPpoUpdateSet* u, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    int rc = check_update(u, "acas2d_ppo_update_set", u ? u->hyper : nullptr, "; every member takes the same number of rows");
+    int rc = check_set(u, "acas2d_ppo_update_set");
     if (rc != ACAS2D_OK) return rc;
-    if (u->n_members < 1 || u->n_members > 65535) {
-        set_error("acas2d_ppo_update_set: n_members = %d (1 to 65535 members, one grid plane each)", u->n_members); return ACAS2D_EINVAL; }
     const int D = u->obs_dim;
     switch (D) {
         case 8: rc = launch_grad_set<8>(*u, stream); break;

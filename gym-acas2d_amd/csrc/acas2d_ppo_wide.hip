@@ -3,7 +3,7 @@
 //
 // ppo_grad_kernel<D> keeps x[D] and a D-wide gradient row per lane in registers; at these widths that does not fit.
 // ppo_grad_wide_kernel<D> is a prologue in front of grad_wide<D> (acas2d_ppo_wide.hpp), the body it shares with the
-// K-learner kernel of acas2d_ppo_wide_set.hip.  That body keeps the scheme -- one lane per sample, weights as scalar
+// K-learner kernels of acas2d_ppo_wide_set.hip and acas2d_ppo_guard.hip.  That body keeps the scheme -- one lane per sample, weights as scalar
 // operands, the per-sample vectors in LDS with row stride 65 -- and tiles what is D-sized, with FOUR waves per 64 samples
 // and network:
 //

@@ -1,8 +1,9 @@
 // acas2d_ppo_wide.hpp -- the gradient body of the PPO minibatch update at obs_dim 53, 101, 197 (16, 32, 64 traffic
 // aircraft), written once: grad_wide<D>, four waves per 64 samples and network (acas2d_ppo_wide.hip describes the
-// tiling), its constants and its LDS size.  ppo_grad_wide_kernel<D> (acas2d_ppo_wide.hip, one learner) and
-// ppo_grad_wide_set_kernel<D> (acas2d_ppo_wide_set.hip, K learners, blockIdx.z the member) are prologues in front of it,
-// as the narrow kernels are in front of grad_narrow<D>.
+// tiling), its constants and its LDS size, and the learner it works for when that is member blockIdx.z of a [K][...] set
+// (SetNets, SetMember, set_nets_of).  ppo_grad_wide_kernel<D> (acas2d_ppo_wide.hip, one learner: OneLearner),
+// ppo_grad_wide_set_kernel<D> (acas2d_ppo_wide_set.hip) and ppo_grad_wide_guarded_set_kernel<D> (acas2d_ppo_guard.hip,
+// target_kl; both a SetMember) are prologues in front of it, as the narrow kernels are in front of grad_narrow<D>.
 #pragma once
 #include "acas2d_ppo.hpp"
 
@@ -26,11 +27,11 @@ __host__ __device__ constexpr size_t lds_bytes(int D) {
 // The gradient of one workgroup: 64 samples (one per lane, the same 64 in each of the four waves) of the network
 // blockIdx.y names (0 actor, 1 critic), whose weights are wave-uniform and come through scalar loads.  `lds_raw` is
 // lds_bytes(D) of dynamic LDS, 16-byte aligned.  `lr` names the learner the workgroup works for (OneLearner in
-// acas2d_ppo_wide.hip, a member of a set in acas2d_ppo_wide_set.hip):
+// acas2d_ppo_wide.hip, SetMember below for a member of a set):
 //   lr.net()                        the six weight pointers of network blockIdx.y ([K][...] stacks for a member)
 //   lr.at(n)                        the learner's element offset into a stack of n floats per learner (0 for one learner)
 //   lr.idx()  lr.log_std()  lr.grad()  lr.stats()  lr.clip_range()  lr.vf_coef()       the learner's own
-//   lr.diag()                       Guard only (acas2d_ppo_guard.hip): the learner's float[8] of KL / clip statistics
+//   lr.diag()                       Guard only (target_kl): the learner's float[8] of KL / clip statistics
 // Each is asked for WHERE IT IS USED, not up front: a member's pointers are sums, and sums formed at the top stay in
 // SGPRs across layer 1, whose 64 weights in flight leave no room for them (20 SGPR spills); the stack pointers and the
 // member number they are formed from are live anyway.
@@ -239,6 +240,37 @@ __device__ __forceinline__ void grad_wide(const Learner& lr, const float* obs, c
         }
     }
 }
+
+// the 13 [K][...] stacks as the two networks' rows and log_std: a workgroup reads the row it works on (blockIdx.y)
+struct SetNets { NetW n[2]; const float* log_std; };
+
+inline SetNets set_nets_of(const Acas2dPpoUpdateSet& u) {
+    const ParamPtrs q = param_ptrs(u);
+    return SetNets{{{q.p[0], q.p[1], q.p[2], q.p[3], q.p[4], q.p[5]}, {q.p[6], q.p[7], q.p[8], q.p[9], q.p[10], q.p[11]}},
+                   q.p[12]};
+}
+
+// member blockIdx.z of the set as grad_wide's Learner: the [K][...] stacks and what moves them to the member.  Every
+// pointer of the member is a sum formed where grad_wide asks for it (the comment above grad_wide says why), diag() among
+// them; diag_all is the guarded kernel's alone.
+struct SetMember {
+    const SetNets& nets;
+    const int64_t* idx_all;
+    const float* hyper;                      // hyper[k]: clip_range, vf_coef, ... (grad_narrow_member, acas2d_ppo.hpp)
+    float *grad_all, *stats_all;
+    int B, total;                            // rows of a minibatch, floats of a gradient block
+    float* diag_all = nullptr;               // diag[k], the KL / clip statistics: Guard only
+    __device__ __forceinline__ size_t m() const { return blockIdx.z; }
+    __device__ __forceinline__ NetW net() const { return nets.n[blockIdx.y]; }
+    __device__ __forceinline__ size_t at(int per_member) const { return m() * (size_t)per_member; }
+    __device__ __forceinline__ const int64_t* idx() const { return idx_all + m() * (size_t)B; }
+    __device__ __forceinline__ const float* log_std() const { return nets.log_std + m(); }
+    __device__ __forceinline__ float clip_range() const { return ((const float ACAS2D_C4*)hyper)[m() * 8]; }
+    __device__ __forceinline__ float vf_coef() const { return ((const float ACAS2D_C4*)hyper)[m() * 8 + 1]; }
+    __device__ __forceinline__ float* grad() const { return grad_all + m() * (size_t)total; }
+    __device__ __forceinline__ float* stats() const { return stats_all + m() * 8; }
+    __device__ __forceinline__ float* diag() const { return diag_all + m() * 8; }
+};
 
 }  // namespace wide
 }  // namespace ppo

@@ -3,13 +3,14 @@
 // learner ceil(n_rows / 64) x 2 workgroups -- 128 at a minibatch of 4 096, on 256 CUs -- and one workgroup for Adam;
 // here the K learners lie side by side.
 //
-//   ppo_grad_wide_set_kernel   grid (ceil(n_rows / 64), 2, K), 256 threads: blockIdx.z is the member.  The prologue takes
-//                              the member's slices of the [K][...] parameter stacks, its minibatch idx[k][.], its gradient
-//                              block grad[k], its stats[k], and its clip_range and vf_coef from hyper[k] by scalar load;
-//                              the rest is grad_wide<D> (acas2d_ppo_wide.hpp), the body ppo_grad_wide_kernel<D> runs.
+//   ppo_grad_wide_set_kernel   grid (ceil(n_rows / 64), 2, K), 256 threads: blockIdx.z is the member.  The prologue is a
+//                              SetMember (acas2d_ppo_wide.hpp): the member's slices of the [K][...] parameter stacks, its
+//                              minibatch idx[k][.], its gradient block grad[k], its stats[k], and its clip_range and
+//                              vf_coef from hyper[k] by scalar load; the rest is grad_wide<D> (the same header), the body
+//                              ppo_grad_wide_kernel<D> runs.
 //   ppo_apply_set_kernel       acas2d_ppo_set.hip's, through launch_ppo_apply_set: it takes D at run time.
 //
-// grad_wide<D> asks for each of the member's pointers where it uses it (acas2d_ppo_wide.hpp says why): the prologue
+// grad_wide<D> asks for each of the member's pointers where it uses it (acas2d_ppo_wide.hpp says why): the SetMember
 // hands it the stacks and the member number, not six sums.
 #include "acas2d_ppo_wide.hpp"
 
@@ -19,33 +20,12 @@ using namespace ppo::wide;
 
 namespace {
 
-// the 13 [K][...] stacks as the two networks' rows and log_std: a workgroup reads the row it works on (blockIdx.y)
-struct SetNets { NetW n[2]; const float* log_std; };
-
-// member blockIdx.z of the set: the [K][...] stacks and what moves them to the member
-struct Member {
-    const SetNets& nets;
-    const int64_t* idx_all;
-    const float* hyper;                      // hyper[k]: clip_range, vf_coef, ... (acas2d_ppo_set.hip)
-    float *grad_all, *stats_all;
-    int B, total;                            // rows of a minibatch, floats of a gradient block
-    __device__ __forceinline__ size_t m() const { return blockIdx.z; }
-    __device__ __forceinline__ NetW net() const { return nets.n[blockIdx.y]; }
-    __device__ __forceinline__ size_t at(int per_member) const { return m() * (size_t)per_member; }
-    __device__ __forceinline__ const int64_t* idx() const { return idx_all + m() * (size_t)B; }
-    __device__ __forceinline__ const float* log_std() const { return nets.log_std + m(); }
-    __device__ __forceinline__ float clip_range() const { return ((const float ACAS2D_C4*)hyper)[m() * 8]; }
-    __device__ __forceinline__ float vf_coef() const { return ((const float ACAS2D_C4*)hyper)[m() * 8 + 1]; }
-    __device__ __forceinline__ float* grad() const { return grad_all + m() * (size_t)total; }
-    __device__ __forceinline__ float* stats() const { return stats_all + m() * 8; }
-};
-
 template <int D>
 __global__ __launch_bounds__(kThreads) void ppo_grad_wide_set_kernel(SetNets nets, const float* obs, const float* act,
                                                                      const float* old_logp, const float* adv,
                                                                      const float* ret, const int64_t* idx_all, int B,
                                                                      const float* hyper, float* grad_all, float* stats_all) {
-    grad_wide<D>(Member{nets, idx_all, hyper, grad_all, stats_all, B, 2 * net_size(D) + 1}, obs, act, old_logp, adv, ret, B);
+    grad_wide<D>(SetMember{nets, idx_all, hyper, grad_all, stats_all, B, 2 * net_size(D) + 1}, obs, act, old_logp, adv, ret, B);
 }
 
 // The dynamic LDS is 79 - 115 KB: ensure_dynamic_lds raises the kernel's limit on the current device and checks the size.
@@ -54,12 +34,10 @@ int launch_grad_wide_set(const Acas2dPpoUpdateSet& u, hipStream_t stream) {
     constexpr size_t bytes = lds_bytes(D);
     const int rc = ensure_dynamic_lds<&ppo_grad_wide_set_kernel<D>>(bytes, "acas2d_ppo_update_wide_set");
     if (rc != ACAS2D_OK) return rc;
-    const ParamPtrs q = param_ptrs(u);
-    const SetNets nets{{{q.p[0], q.p[1], q.p[2], q.p[3], q.p[4], q.p[5]}, {q.p[6], q.p[7], q.p[8], q.p[9], q.p[10], q.p[11]}}, q.p[12]};
     hipLaunchKernelGGL((ppo_grad_wide_set_kernel<D>), dim3((unsigned)((u.n_rows + 63) / 64), 2, (unsigned)u.n_members),
-                       dim3(kThreads), bytes, stream, nets, (const float*)u.obs, (const float*)u.act, (const float*)u.old_logp,
-                       (const float*)u.adv, (const float*)u.ret, (const int64_t*)u.idx, u.n_rows, (const float*)u.hyper,
-                       (float*)u.grad, (float*)u.stats);
+                       dim3(kThreads), bytes, stream, set_nets_of(u), (const float*)u.obs, (const float*)u.act,
+                       (const float*)u.old_logp, (const float*)u.adv, (const float*)u.ret, (const int64_t*)u.idx, u.n_rows,
+                       (const float*)u.hyper, (float*)u.grad, (float*)u.stats);
     return launched("acas2d_ppo_update_wide_set gradient launch");
 }
 
@@ -71,10 +49,8 @@ using namespace acas2d::ppo;
 
 extern "C" int acas2d_ppo_update_wide_set_f32(const Acas2dPpoUpdateSet* u, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
-    int rc = check_update(u, "acas2d_ppo_update_wide_set", u ? u->hyper : nullptr, "; every member takes the same number of rows");
+    int rc = check_set(u, "acas2d_ppo_update_wide_set");
     if (rc != ACAS2D_OK) return rc;
-    if (u->n_members < 1 || u->n_members > 65535) {
-        set_error("acas2d_ppo_update_wide_set: n_members = %d (1 to 65535 members, one grid plane each)", u->n_members); return ACAS2D_EINVAL; }
     switch (u->obs_dim) {
         case 53: rc = launch_grad_wide_set<53>(*u, stream); break;
         case 101: rc = launch_grad_wide_set<101>(*u, stream); break;

@@ -34,7 +34,7 @@ four counts exact on both paths.  No case exposed a fault in the kernels.  Run t
 0.6 s (the first, which loads the library).
 With one arithmetic line of a kernel changed, the 110 GPU tests of this file fail as follows (each build run once): kl_s
 formed from the clamped ratio, 105; the guarded apply kernel dividing by the row count rounded up to 64, 103;
-GuardedMember::clip_range() reading member 0's row (the wide kernels only), 49.
+SetMember::clip_range() (csrc/acas2d_ppo_wide.hpp) reading member 0's row (the wide kernels only), 49.
 """
 import numpy as np
 import pytest
