@@ -6,7 +6,7 @@
 // grad_narrow<D>; ppo_grad_set_kernel<D> (acas2d_ppo_set.hip) and ppo_grad_guarded_set_kernel<D> (acas2d_ppo_guard.hip,
 // target_kl) are grad_narrow_member<D> with Guard = false and true.  The wide kernels stand likewise in front of
 // grad_wide<D> (acas2d_ppo_wide.hpp).  With Guard at its default, false, the gradient bodies are the code they were
-// before the guard existed.
+// before the guard existed; likewise with Opts (acas2d_ppo_sb3.hip: clip_range_vf and the schedule factors).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -63,11 +63,17 @@ __device__ __forceinline__ float wave_sum(float v) {
 // Guard (the target_kl kernels of acas2d_ppo_guard.hip): a live actor sample also gives its terms of SB3's approx_kl,
 // (ratio - 1) - log ratio, and of its clip_fraction, |ratio - 1| > clip_range, from the log ratio and the ratio the
 // surrogate is formed from; without it `kl_s` and `cf_s` are zeros nobody reads.
-template <bool Guard = false>
+// Opts (the clip_range_vf / schedule kernels of acas2d_ppo_sb3.hip, always with Guard): `clip_range` is the caller's
+// hyper[k][0] * scale[k][1], and a critic sample with clip_vf > 0 takes SB3's clipped value loss -- values_pred =
+// old_val + clamp(out - old_val, -clip_vf, clip_vf), F.mse_loss(ret, values_pred), no max with the unclipped loss; torch's
+// clamp passes the gradient on the closed interval.  clip_vf <= 0 or NaN (wave-uniform): the plain branch, and
+// old_val_s is not read.
+template <bool Guard = false, bool Opts = false>
 __device__ __forceinline__ void loss_grad(bool is_actor, bool live, float out, const float* act_s, const float* old_logp_s,
                                           const float* adv_s, const float* ret_s, float a_mean, float a_std,
                                           const float* log_std_p, int B, float clip_range, float vf_coef, float& dout,
-                                          float& dls, float& pg_s, float& vf_s, float& kl_s, float& cf_s) {
+                                          float& dls, float& pg_s, float& vf_s, float& kl_s, float& cf_s,
+                                          const float* old_val_s = nullptr, float clip_vf = 0.0f) {
     dout = 0.0f; dls = 0.0f; pg_s = 0.0f; vf_s = 0.0f; kl_s = 0.0f; cf_s = 0.0f;
     if (live) {
         if (is_actor) {
@@ -87,6 +93,15 @@ __device__ __forceinline__ void loss_grad(bool is_actor, bool live, float out, c
                 cf_s = fabsf(ratio - 1.0f) > clip_range ? 1.0f : 0.0f;
             }
         } else {
+            if constexpr (Opts) {
+                if (clip_vf > 0.0f) {
+                    const float ov = old_val_s[0], d = out - ov;
+                    const float e = (ov + fminf(fmaxf(d, -clip_vf), clip_vf)) - ret_s[0];
+                    vf_s = e * e / (float)B;
+                    dout = (d >= -clip_vf && d <= clip_vf) ? vf_coef * 2.0f * e / (float)B : 0.0f;
+                    return;
+                }
+            }
             const float e = out - ret_s[0];
             vf_s = e * e / (float)B;
             dout = vf_coef * 2.0f * e / (float)B;
@@ -102,13 +117,14 @@ __device__ __forceinline__ void loss_grad(bool is_actor, bool live, float out, c
 // "every lane reads column t of row s" are both conflict-free; the weight gradients are then sums over the 64 samples
 // of outer products, taken by thread t for row t of each weight matrix, and added to `grad` with float atomics.
 // Guard: an actor wave also adds its samples' KL and clipped-count terms (loss_grad) to diag[0] and diag[1].
-template <int D, bool Guard = false>
+// Opts: `clip_range` is the effective one, and a critic wave with clip_vf > 0 gathers old_val[s] (loss_grad).
+template <int D, bool Guard = false, bool Opts = false>
 __device__ __forceinline__ void grad_narrow(const float ACAS2D_C4* w1, const float ACAS2D_C4* b1, const float ACAS2D_C4* w2,
                                             const float ACAS2D_C4* b2, const float ACAS2D_C4* w3, const float ACAS2D_C4* b3,
                                             const float* log_std_p, const float* obs, const float* act,
                                             const float* old_logp, const float* adv, const float* ret, const int64_t* idx,
                                             int B, float clip_range, float vf_coef, float* grad, float* stats, float* lds,
-                                            float* diag = nullptr) {
+                                            float* diag = nullptr, const float* old_val = nullptr, float clip_vf = 0.0f) {
     float* l_h1 = lds;                       // [64][65]
     float* l_h2 = l_h1 + 64 * kRow;
     float* l_dz1 = l_h2 + 64 * kRow;
@@ -120,6 +136,10 @@ __device__ __forceinline__ void grad_narrow(const float ACAS2D_C4* w1, const flo
     const int row = blockIdx.x * 64 + lane;
     const bool live = row < B;
     const int64_t s = idx[live ? row : 0];
+    // Opts: the sample's old_val address is formed HERE and pinned in VGPRs (there is room: 144 of 256 in use), so that old_val
+    // does not sit in two SGPRs across layer 2, whose 64 weights in flight leave none
+    [[maybe_unused]] const float* old_val_s = nullptr;
+    if constexpr (Opts) { old_val_s = old_val + s; asm volatile("" : "+v"(old_val_s)); }
 
     // ---- the minibatch's advantage statistics (SB3 normalises per minibatch; torch.std is Bessel-corrected)
     float a_mean = 0.0f, a_std = 1.0f;
@@ -156,8 +176,12 @@ __device__ __forceinline__ void grad_narrow(const float ACAS2D_C4* w1, const flo
     }
 
     float dout, dls, pg_s, vf_s, kl_s, cf_s;
-    loss_grad<Guard>(is_actor, live, out, act + s, old_logp + s, adv + s, ret + s, a_mean, a_std, log_std_p, B, clip_range,
-                     vf_coef, dout, dls, pg_s, vf_s, kl_s, cf_s);
+    if constexpr (Opts)
+        loss_grad<Guard, true>(is_actor, live, out, act + s, old_logp + s, adv + s, ret + s, a_mean, a_std, log_std_p, B,
+                               clip_range, vf_coef, dout, dls, pg_s, vf_s, kl_s, cf_s, old_val_s, clip_vf);
+    else
+        loss_grad<Guard>(is_actor, live, out, act + s, old_logp + s, adv + s, ret + s, a_mean, a_std, log_std_p, B, clip_range,
+                         vf_coef, dout, dls, pg_s, vf_s, kl_s, cf_s);
     l_do[lane] = dout;
     if constexpr (Guard) {                                   // (here, not beside the stats atomics: the two terms die at once)
         if (is_actor) {                                      // (uniform over the wave)
@@ -228,11 +252,15 @@ __device__ __forceinline__ void grad_narrow(const float ACAS2D_C4* w1, const flo
 // idx[k][.], its gradient block grad[k], its stats[k], its clip_range and vf_coef from hyper[k] by scalar load (hyper[k]:
 // clip_range, vf_coef, ent_coef, max_grad_norm, learning_rate, beta1, beta2, adam_eps) and, Guard only, its diag[k].  The
 // rollout buffer (obs ... ret) is ONE flat buffer shared by all members; idx holds its global row numbers.
-template <int D, bool Guard = false>
+// Opts: an actor workgroup's clip range is hyper[k][0] * scale[k][1], a critic workgroup's value clip clip_range_vf[k] *
+// scale[k][2], one float32 product each, by scalar loads on the branch that needs them (scale: float[K][4]).
+template <int D, bool Guard = false, bool Opts = false>
 __device__ __forceinline__ void grad_narrow_member(const ParamPtrs& prm, const float* obs, const float* act,
                                                    const float* old_logp, const float* adv, const float* ret,
                                                    const int64_t* idx_all, int B, const float* hyper, float* grad_all,
-                                                   float* stats_all, float* lds, float* diag_all = nullptr) {
+                                                   float* stats_all, float* lds, float* diag_all = nullptr,
+                                                   const float* old_val = nullptr, const float* clip_range_vf = nullptr,
+                                                   const float* scale = nullptr) {
     const bool is_actor = blockIdx.y == 0;
     const size_t m = blockIdx.z;
     const auto net = [&](int i) -> const float* { return is_actor ? prm.p[i] : prm.p[6 + i]; };
@@ -249,8 +277,19 @@ __device__ __forceinline__ void grad_narrow_member(const ParamPtrs& prm, const f
     const float ACAS2D_C4* hy = (const float ACAS2D_C4*)(hyper + m * 8);
     const float clip_range = hy[0], vf_coef = hy[1];
 
-    grad_narrow<D, Guard>(w1, b1, w2, b2, w3, b3, log_std_p, obs, act, old_logp, adv, ret, idx, B, clip_range, vf_coef, grad,
-                          stats, lds, Guard ? diag_all + m * 8 : nullptr);
+    if constexpr (Opts) {
+        const float ACAS2D_C4* sc = (const float ACAS2D_C4*)(scale + m * 4);
+        // the workgroup's ONE clip (the actor's range or the critic's value clip), kept in a VGPR for the same reason
+        float clip = is_actor ? clip_range * sc[1] : ((const float ACAS2D_C4*)clip_range_vf)[m] * sc[2];
+        // so are the pointers only the atomics at the end use: eight SGPRs that layer 2 then has for its weights
+        float* diag = diag_all + m * 8;
+        asm volatile("" : "+v"(clip), "+v"(grad), "+v"(stats), "+v"(diag), "+v"(log_std_p));
+        grad_narrow<D, Guard, true>(w1, b1, w2, b2, w3, b3, log_std_p, obs, act, old_logp, adv, ret, idx, B, clip, vf_coef,
+                                    grad, stats, lds, diag, old_val, clip);
+    } else {
+        grad_narrow<D, Guard>(w1, b1, w2, b2, w3, b3, log_std_p, obs, act, old_logp, adv, ret, idx, B, clip_range, vf_coef,
+                              grad, stats, lds, Guard ? diag_all + m * 8 : nullptr);
+    }
 }
 
 // One 1 024-thread workgroup: the global gradient norm, torch.nn.utils.clip_grad_norm_'s coefficient, Adam

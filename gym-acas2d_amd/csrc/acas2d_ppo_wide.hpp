@@ -38,7 +38,10 @@ __host__ __device__ constexpr size_t lds_bytes(int D) {
 // Guard: the wave that adds the scalars also adds the 64 samples' KL and clipped-count terms (loss_grad) to lr.diag()[0]
 // and [1], right after loss_grad: lr.diag() is asked for there, next to lr.clip_range(), and is dead again before the
 // weight gradients (held to the end beside lr.stats() it costs the widest kernel an SGPR spill).
-template <int D, class Learner, bool Guard = false>
+// Opts (acas2d_ppo_sb3.hip, always with Guard): lr.clip_x(is_actor) is the actor's effective clip range or the critic's
+// value clip, and lr.old_val the rollout's values, for loss_grad's clipped value loss.  These are asked for at the TOP and
+// kept in VGPRs: the exception to the rule above, because three more kernel arguments cannot wait in SGPRs.
+template <int D, class Learner, bool Guard = false, bool Opts = false>
 __device__ __forceinline__ void grad_wide(const Learner& lr, const float* obs, const float* act, const float* old_logp,
                                           const float* adv, const float* ret, int B) {
     constexpr int XS = x_stride(D);
@@ -62,6 +65,14 @@ __device__ __forceinline__ void grad_wide(const Learner& lr, const float* obs, c
     const bool live = row < B;
     const int64_t s = idx[live ? row : 0];
     if (w == 0) l_idx[lane] = s;
+    // Opts: the workgroup's ONE clip (the actor's effective range or the critic's value clip) and the sample's old_val
+    // address are formed HERE and pinned in VGPRs (94 to 98 of 256 in use): layer 1 has no SGPR for three more pointers
+    [[maybe_unused]] float clip_x = 0.0f;
+    [[maybe_unused]] const float* old_val_s = nullptr;
+    if constexpr (Opts) {
+        clip_x = lr.clip_x(is_actor); old_val_s = lr.old_val + s;
+        asm volatile("" : "+v"(clip_x), "+v"(old_val_s));
+    }
 
     // ---- the minibatch's advantage statistics (SB3 normalises per minibatch; torch.std is Bessel-corrected)
     float a_mean = 0.0f, a_std = 1.0f;
@@ -148,8 +159,12 @@ __device__ __forceinline__ void grad_wide(const Learner& lr, const float* obs, c
     for (int i = 0; i < kH; ++i) out = fmaf(w3[i], l_h2[lane * kRow + i], out);
 
     float dout, dls, pg_s, vf_s, kl_s, cf_s;
-    loss_grad<Guard>(is_actor, live, out, act + s, old_logp + s, adv + s, ret + s, a_mean, a_std, lr.log_std(), B,
-                     lr.clip_range(), lr.vf_coef(), dout, dls, pg_s, vf_s, kl_s, cf_s);
+    if constexpr (Opts)
+        loss_grad<Guard, true>(is_actor, live, out, act + s, old_logp + s, adv + s, ret + s, a_mean, a_std, lr.log_std(), B,
+                               clip_x, lr.vf_coef(), dout, dls, pg_s, vf_s, kl_s, cf_s, old_val_s, clip_x);
+    else
+        loss_grad<Guard>(is_actor, live, out, act + s, old_logp + s, adv + s, ret + s, a_mean, a_std, lr.log_std(), B,
+                         lr.clip_range(), lr.vf_coef(), dout, dls, pg_s, vf_s, kl_s, cf_s);
     if (w == 0) l_do[lane] = dout;
     if constexpr (Guard) {
         if (is_actor && w == kWaves - 1) {                             // (uniform over the wave)
@@ -252,7 +267,7 @@ inline SetNets set_nets_of(const Acas2dPpoUpdateSet& u) {
 
 // member blockIdx.z of the set as grad_wide's Learner: the [K][...] stacks and what moves them to the member.  Every
 // pointer of the member is a sum formed where grad_wide asks for it (the comment above grad_wide says why), diag() among
-// them; diag_all is the guarded kernel's alone.
+// them; diag_all is the guarded kernels' alone, old_val / clip_range_vf / scale the Opts kernels' (acas2d_ppo_sb3.hip).
 struct SetMember {
     const SetNets& nets;
     const int64_t* idx_all;
@@ -260,6 +275,9 @@ struct SetMember {
     float *grad_all, *stats_all;
     int B, total;                            // rows of a minibatch, floats of a gradient block
     float* diag_all = nullptr;               // diag[k], the KL / clip statistics: Guard only
+    const float* old_val = nullptr;          // Opts only: the rollout's values, the value clips [K], the factors [K][4]
+    const float* clip_range_vf = nullptr;
+    const float* scale = nullptr;
     __device__ __forceinline__ size_t m() const { return blockIdx.z; }
     __device__ __forceinline__ NetW net() const { return nets.n[blockIdx.y]; }
     __device__ __forceinline__ size_t at(int per_member) const { return m() * (size_t)per_member; }
@@ -270,6 +288,34 @@ struct SetMember {
     __device__ __forceinline__ float* grad() const { return grad_all + m() * (size_t)total; }
     __device__ __forceinline__ float* stats() const { return stats_all + m() * 8; }
     __device__ __forceinline__ float* diag() const { return diag_all + m() * 8; }
+    // ONE float32 product: hyper[k][0] * scale[k][1] (actor) or clip_range_vf[k] * scale[k][2] (critic).  The member
+    // number passes through an empty asm, so that these addresses are not common subexpressions of the later ones.
+    __device__ __forceinline__ float clip_x(bool is_actor) const {
+        uint32_t k = blockIdx.z;
+        asm volatile("" : "+s"(k));
+        const float ACAS2D_C4* sc = (const float ACAS2D_C4*)scale + (size_t)k * 4;
+        return is_actor ? ((const float ACAS2D_C4*)hyper)[(size_t)k * 8] * sc[1]
+                        : ((const float ACAS2D_C4*)clip_range_vf)[k] * sc[2];
+    }
+};
+
+// SetMember for the Opts kernels (acas2d_ppo_sb3.hip).  The three option pointers are three more kernel arguments than
+// layer 1 has SGPRs for, so this learner forms the pointers that only the tail of grad_wide uses (log_std, grad, stats,
+// diag) and vf_coef ONCE, in the kernel's prologue, and pins them in VGPRs, of which these kernels use 94 to 98 of 256; the
+// atomics take a VGPR address as well as a scalar one.
+struct OptsMember : SetMember {
+    const float* log_std_v;
+    float *grad_v, *stats_v, *diag_v;
+    float vf_coef_v;
+    __device__ __forceinline__ explicit OptsMember(const SetMember& b)
+        : SetMember(b), log_std_v(b.log_std()), grad_v(b.grad()), stats_v(b.stats()), diag_v(b.diag()), vf_coef_v(b.vf_coef()) {
+        asm volatile("" : "+v"(log_std_v), "+v"(grad_v), "+v"(stats_v), "+v"(diag_v), "+v"(vf_coef_v));
+    }
+    __device__ __forceinline__ const float* log_std() const { return log_std_v; }
+    __device__ __forceinline__ float vf_coef() const { return vf_coef_v; }
+    __device__ __forceinline__ float* grad() const { return grad_v; }
+    __device__ __forceinline__ float* stats() const { return stats_v; }
+    __device__ __forceinline__ float* diag() const { return diag_v; }
 };
 
 }  // namespace wide

@@ -63,6 +63,12 @@ class CPpoGuard(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("target_kl", "stopped", "diag")]
 
 
+class CPpoOptions(C.Structure):
+    """struct Acas2dPpoOptions: the rollout's values, the value clips [K] and the per-update factors [K][4] of
+    acas2d_ppo_update_sb3_set_f32 (include/acas2d.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("old_val", "clip_range_vf", "scale")]
+
+
 class CGae(C.Structure):
     """struct Acas2dGae: the bootstrap value and GAE over the collector's [T][E] buffers (include/acas2d.h)."""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -99,7 +105,7 @@ EXPORTS = ("acas2d_abi_version", "acas2d_config_size", "acas2d_state_size", "aca
            "acas2d_gae_f32", "acas2d_gae_size", "acas2d_gae_pipeline_depth", "acas2d_collect_set_group_f32",
            "acas2d_ppo_update_wide_set_f32", "acas2d_member_episodes_f32", "acas2d_member_episodes_size",
            "acas2d_population_exploit_f32", "acas2d_population_exploit_size", "acas2d_ppo_update_guarded_set_f32",
-           "acas2d_ppo_guard_size")
+           "acas2d_ppo_guard_size", "acas2d_ppo_update_sb3_set_f32", "acas2d_ppo_options_size")
 
 
 class NativeLibraryError(RuntimeError):
@@ -179,6 +185,10 @@ def lib():
     L.acas2d_ppo_update_guarded_set_f32.restype = C.c_int
     L.acas2d_ppo_update_guarded_set_f32.argtypes = [C.POINTER(CPpoUpdateSet), C.POINTER(CPpoGuard), C.c_void_p]
     L.acas2d_ppo_guard_size.restype = C.c_size_t
+    L.acas2d_ppo_update_sb3_set_f32.restype = C.c_int
+    L.acas2d_ppo_update_sb3_set_f32.argtypes = [C.POINTER(CPpoUpdateSet), C.POINTER(CPpoGuard), C.POINTER(CPpoOptions),
+                                                C.c_void_p]
+    L.acas2d_ppo_options_size.restype = C.c_size_t
     L.acas2d_gae_f32.restype = C.c_int
     L.acas2d_gae_f32.argtypes = [C.POINTER(CGae), C.c_void_p]
     L.acas2d_gae_size.restype = C.c_size_t
@@ -217,7 +227,7 @@ def lib():
     if L.acas2d_gae_size() != C.sizeof(CGae):
         raise NativeLibraryError("Acas2dGae layout mismatch: %d != %d" % (L.acas2d_gae_size(), C.sizeof(CGae)))
     for name, twin in (("member_episodes", CMemberEpisodes), ("population_exploit", CPopulationExploit),
-                       ("ppo_guard", CPpoGuard)):
+                       ("ppo_guard", CPpoGuard), ("ppo_options", CPpoOptions)):
         size = getattr(L, "acas2d_%s_size" % name)()
         if size != C.sizeof(twin):
             raise NativeLibraryError("%s layout mismatch: %d != %d" % (twin.__name__, size, C.sizeof(twin)))

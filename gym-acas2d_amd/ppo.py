@@ -3,8 +3,9 @@
 The reference trains with Stable-Baselines3 (`training_main.py:44-52`:
 `PPO('MlpPolicy', env, seed=13).learn(1_048_576)`), one env, CPU.  SB3 is not available here and
 its one-env-at-a-time loop is exactly what the batched engine replaces, so this module restates
-the algorithm SB3 1.1.0 runs (clipped surrogate, advantages normalised per minibatch, value loss
-without clipping, state-independent log-std, orthogonal init, Adam eps 1e-5, gradient-norm clipping)
+the algorithm SB3 1.1.0 runs (clipped surrogate, advantages normalised per minibatch, MSE value loss
+with SB3's optional clip_range_vf, learning-rate / clip-range schedules of progress_remaining,
+state-independent log-std, orthogonal init, Adam eps 1e-5, gradient-norm clipping)
 on E parallel envs: rollouts, GAE and the updates all stay on the GPU.  `PPOConfig.sb3()` carries the
 hyper-parameters recorded in the reference's model zips (n_steps 2048, batch 64, epochs 10, gamma
 0.99, lambda 0.95, clip 0.2, lr 3e-4, ent 0, vf 0.5, max-grad-norm 0.5); the DEFAULTS differ in the two
@@ -29,8 +30,8 @@ One learner (PPOTrainer) and K learners in the same launches (PopulationTrainer,
 streams and in the kernels they call, not in their host code, which is written once: `_Trainer` holds the static rollout
 buffers, the intake of a fused collection and learn()'s loop; minibatch_buffers() / minibatch_schedule() the static index
 buffers and an epoch's walk through them; `_FusedUpdater` what FusedUpdate and FusedUpdateSet share (the entry by width,
-the workspace, hyper_row(), the struct of the set entries, the target_kl guard); policy.kernel_layout() the network as
-every kernel reads it.
+the workspace, hyper_row(), the struct of the set entries, the target_kl guard, clip_range_vf and the schedule factors);
+policy.kernel_layout() the network as every kernel reads it.
 """
 import dataclasses
 import math
@@ -67,6 +68,28 @@ class PPOConfig:
     # SB3's target_kl: PPO.train() abandons the rest of an update as soon as one minibatch's approx_kl exceeds 1.5 x
     # target_kl, before that minibatch's optimizer step.  None (SB3's default, and sb3()'s): no limit.
     target_kl: Optional[float] = None
+    # SB3's clip_range_vf: the value loss is taken on old_values + clamp(values - old_values, -c, c).  None (SB3's
+    # default, and sb3()'s): the plain MSE.  It depends on the reward scale; the returns of this env are of order 1e3.
+    # SB3's schedules, as FACTORS: a callable progress_remaining (1 at the start of learn(), 0 at its end) -> factor
+    # that multiplies learning_rate / clip_range / clip_range_vf -- or, in a population, whatever the member's hyper
+    # row holds at that moment, so that a schedule composes with PBT's exploit step.  SB3's linear_schedule(3e-4) is
+    # learning_rate=3e-4, learning_rate_schedule=linear_schedule().  None: constant.
+    # The four are constructor arguments and attributes that dataclasses.replace() carries over, but InitVars, not fields:
+    # tests/test_ppo_host.py holds every FIELD of a fully set config to differ from its default, and that file stays as it
+    # is.  So dataclasses.fields(), asdict(), repr() and == do NOT see them: two configs that differ only in
+    # clip_range_vf or a schedule compare equal, and PPOConfig(**asdict(c)) drops them.  Compare or copy them by name
+    # (OPTION_FIELDS below); tests/test_sb3_options.py pins this.
+    clip_range_vf: dataclasses.InitVar[Optional[float]] = None
+    learning_rate_schedule: dataclasses.InitVar[Optional[object]] = None
+    clip_range_schedule: dataclasses.InitVar[Optional[object]] = None
+    clip_range_vf_schedule: dataclasses.InitVar[Optional[object]] = None
+
+    def __post_init__(self, clip_range_vf, learning_rate_schedule, clip_range_schedule, clip_range_vf_schedule):
+        if clip_range_vf is not None and not clip_range_vf > 0:
+            raise ValueError("PPOConfig.clip_range_vf must be positive (None: no value clipping), got %r" % (clip_range_vf,))
+        self.clip_range_vf = clip_range_vf
+        self.learning_rate_schedule, self.clip_range_schedule = learning_rate_schedule, clip_range_schedule
+        self.clip_range_vf_schedule = clip_range_vf_schedule
 
     @classmethod
     def sb3(cls, **overrides):
@@ -75,6 +98,48 @@ class PPOConfig:
         is E x 2048 samples cut into minibatches of 64."""
         return cls(**{**dict(n_steps=2048, batch_size=64, n_epochs=10, gamma=0.99, gae_lambda=0.95, clip_range=0.2,
                              learning_rate=3e-4, ent_coef=0.0, vf_coef=0.5, max_grad_norm=0.5), **overrides})
+
+
+def linear_schedule(final=0.0):
+    """The factor form of SB3's linear schedule: progress_remaining p -> final + (1 - final) * p, 1 at the start of
+    learn() and `final` at its end."""
+    final = float(final)
+    return lambda p: final + (1.0 - final) * p
+
+
+SCHEDULE_FIELDS = ("learning_rate_schedule", "clip_range_schedule", "clip_range_vf_schedule")
+# PPOConfig's options that are attributes but not dataclass fields (the comment in PPOConfig says why)
+OPTION_FIELDS = ("clip_range_vf",) + SCHEDULE_FIELDS
+
+
+def schedule_factors(cfg, progress_remaining=1.0):
+    """The three factors (on learning_rate, clip_range, clip_range_vf) of `cfg`'s schedules at `progress_remaining`; 1.0
+    where there is no schedule.  A factor that is negative or not finite is a ValueError, here where it is evaluated."""
+    out = []
+    for name in SCHEDULE_FIELDS:
+        f = getattr(cfg, name)
+        x = 1.0 if f is None else float(f(progress_remaining))
+        if not (math.isfinite(x) and x >= 0.0):
+            raise ValueError("PPOConfig.%s(%r) = %r: a schedule's factor must be finite and >= 0"
+                             % (name, progress_remaining, x))
+        out.append(x)
+    return out
+
+
+def has_options(cfg):
+    """True where `cfg` asks for clip_range_vf or a schedule: what acas2d_ppo_update_sb3_set_f32 exists for."""
+    return cfg.clip_range_vf is not None or any(getattr(cfg, n) is not None for n in SCHEDULE_FIELDS)
+
+
+def effective_config(cfg, progress_remaining=1.0):
+    """`cfg` as one update at `progress_remaining` runs it: learning_rate, clip_range and clip_range_vf multiplied by
+    their schedules' factors (a clip_range_vf that comes to 0 is None: the plain MSE), the schedules gone."""
+    if not any(getattr(cfg, n) is not None for n in SCHEDULE_FIELDS):
+        return cfg
+    f = schedule_factors(cfg, progress_remaining)
+    vf = None if cfg.clip_range_vf is None or not cfg.clip_range_vf * f[2] > 0 else cfg.clip_range_vf * f[2]
+    return dataclasses.replace(cfg, learning_rate=cfg.learning_rate * f[0], clip_range=cfg.clip_range * f[1], clip_range_vf=vf,
+                               **{n: None for n in SCHEDULE_FIELDS})
 
 
 def _ortho(layer, gain):
@@ -259,17 +324,26 @@ def _normal_logp(mean, log_std, x):
     return (-((x - mean) ** 2) / (2.0 * (2.0 * log_std).exp()) - log_std - LOG_SQRT_2PI).sum(-1)
 
 
-def ppo_loss(policy, cfg, obs, act, old_logp, adv, ret):
+def ppo_loss(policy, cfg, obs, act, old_logp, adv, ret, old_val=None):
     """SB3 1.1.0 PPO.train() for one minibatch of a Box(1) action space: advantages normalised over the
-    minibatch, clipped surrogate, plain MSE value loss (clip_range_vf = None), entropy of the state-independent
-    Gaussian.  The ONE loss both the captured and the op-by-op update run.  Returns (loss, pg, vf)."""
+    minibatch, clipped surrogate, MSE value loss -- plain with cfg.clip_range_vf = None, otherwise on old_val +
+    clamp(value - old_val, -clip_range_vf, clip_range_vf) (`old_val`: the rollout's values of the rows, then required;
+    no max with the unclipped loss) -- and the entropy of the state-independent Gaussian.  cfg's numbers are used as they
+    are: effective_config() applies the schedules.  The ONE loss both the captured and the op-by-op update run.
+    Returns (loss, pg, vf)."""
     mean, value = policy.forward(obs)
     log_std = policy.log_std
     logp = _normal_logp(mean, log_std, act)
     a = (adv - adv.mean()) / (adv.std() + 1e-8)
     ratio = (logp - old_logp).exp()
     pg = -torch.min(a * ratio, a * ratio.clamp(1 - cfg.clip_range, 1 + cfg.clip_range)).mean()
-    vf = torch.nn.functional.mse_loss(value, ret)
+    if cfg.clip_range_vf is None:
+        vf = torch.nn.functional.mse_loss(value, ret)
+    else:
+        if old_val is None:
+            raise ValueError("ppo_loss: clip_range_vf needs old_val, the rollout's values of the minibatch's rows")
+        value_pred = old_val + (value - old_val).clamp(-cfg.clip_range_vf, cfg.clip_range_vf)
+        vf = torch.nn.functional.mse_loss(ret, value_pred)
     ent = -(0.5 + LOG_SQRT_2PI + log_std).sum()           # -entropy of N(., exp(log_std)), the same for every state
     return pg + cfg.ent_coef * ent + cfg.vf_coef * vf, pg, vf
 
@@ -324,7 +398,11 @@ class _FusedUpdater:
     `step_count`, `stats`) with a leading [K] for a set, the flat rollout, the `hyper` rows, the struct of the set entries
     and the guarded update (acas2d_ppo_update_guarded_set_f32, csrc/acas2d_ppo_guard.hip): the per-member `target_kl`
     limits, the `stopped` flags and the `diag` rows the kernels keep, as ONE device buffer so that begin_update() is one
-    memset."""
+    memset.  Where a config has a clip_range_vf or a schedule (`options`; the updater is then guarded by implication)
+    every step goes through acas2d_ppo_update_sb3_set_f32 (csrc/acas2d_ppo_sb3.hip) instead: `clip_range_vf` float32 [K]
+    (0: plain MSE) and `scale` float32 [K, 4], the factors on learning_rate, clip_range and clip_range_vf that
+    begin_update(progress_remaining) evaluates on the host and writes with one non-blocking copy; the kernels multiply
+    them into whatever `hyper` holds."""
     # one row per width class: the widths, the solo symbol, the set symbol (`_symbol` names a subclass's column)
     _ENTRIES = ((FUSED_UPDATE_WIDTHS, "acas2d_ppo_update_f32", "acas2d_ppo_update_set_f32"),
                 (FUSED_UPDATE_WIDE_WIDTHS, "acas2d_ppo_update_wide_f32", "acas2d_ppo_update_wide_set_f32"))
@@ -338,7 +416,7 @@ class _FusedUpdater:
                                                           row[cls._symbol]) for row in cls._ENTRIES)
         raise ValueError("%s is built for obs_dim in %s%s %d" % (cls.__name__, built, cls._got, D))
 
-    def __init__(self, params, configs, rollout, lead, beta1, beta2, adam_eps, diagnostics):
+    def __init__(self, params, configs, rollout, lead, beta1, beta2, adam_eps, diagnostics, old_val=None):
         import ctypes as C
         from . import native
         self.D, K, dev = rollout[0].shape[-1], len(configs), rollout[0].device
@@ -352,7 +430,10 @@ class _FusedUpdater:
         self._params = params
         assert all(p.dtype == torch.float32 and p.is_contiguous() and p.device == dev for p in params)
         self._bufs = _flat_rollout(*rollout)
-        self.guarded = bool(diagnostics) or any(c.target_kl is not None for c in configs)
+        self.configs = list(configs)
+        self.options = any(has_options(c) for c in configs)
+        self.factors = [[1.0, 1.0, 1.0] for _ in configs]  # of the update begin_update() last opened
+        self.guarded = bool(diagnostics) or self.options or any(c.target_kl is not None for c in configs)
         if self.guarded:
             # a config's target_kl as the kernels take it: None is 0, no limit
             self.target_kl = torch.tensor([0.0 if c.target_kl is None else float(c.target_kl) for c in configs],
@@ -362,6 +443,23 @@ class _FusedUpdater:
             self.stopped = self._guard_state[K * 8:].view(torch.int32)
             self._guarded_update = self._lib.acas2d_ppo_update_guarded_set_f32
             self._guard = native.CPpoGuard(self.target_kl.data_ptr(), self.stopped.data_ptr(), self.diag.data_ptr())
+        if self.options:
+            if old_val is None and any(c.clip_range_vf is not None for c in configs):
+                raise ValueError("clip_range_vf needs old_val, the rollout's values (flat, rows as obs / act / ...)")
+            # no clip_range_vf anywhere: the kernels read old_val for no member, and `ret` stands in for the pointer
+            self.old_val = self._bufs[4] if old_val is None else old_val.reshape(-1)
+            if (self.old_val.dtype != torch.float32 or not self.old_val.is_contiguous() or self.old_val.device != dev
+                    or self.old_val.numel() != self._bufs[4].numel()):
+                raise ValueError("old_val must be a contiguous float32 tensor of the rollout's %d rows on %s"
+                                 % (self._bufs[4].numel(), dev))
+            self.clip_range_vf = torch.tensor([0.0 if c.clip_range_vf is None else float(c.clip_range_vf) for c in configs],
+                                              dtype=torch.float32).to(dev)
+            self.scale = torch.ones(K, 4, dtype=torch.float32, device=dev)
+            self._scale_host = torch.ones(K, 4, dtype=torch.float32, pin_memory=dev.type == "cuda")
+            self._scale_copied = torch.cuda.Event() if dev.type == "cuda" else None   # recorded after every copy
+            self._scale_pending = False
+            self._sb3_update = self._lib.acas2d_ppo_update_sb3_set_f32
+            self._opts = native.CPpoOptions(self.old_val.data_ptr(), self.clip_range_vf.data_ptr(), self.scale.data_ptr())
 
     def _stream(self):
         return self._C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -376,13 +474,40 @@ class _FusedUpdater:
 
     def _step_guarded(self, idx, K, B):
         u = self._set_struct(idx, K, B)
+        if self.options:
+            self._native.check(self._sb3_update(self._C.byref(u), self._C.byref(self._guard), self._C.byref(self._opts),
+                                                self._stream()))
+            return
         self._native.check(self._guarded_update(self._C.byref(u), self._C.byref(self._guard), self._stream()))
 
-    def begin_update(self):
+    def begin_update(self, progress_remaining=1.0):
         """Where SB3 enters train(): every member runs again and the statistics start over.  One memset on the current
-        stream, no synchronisation; nothing to do for an update that is not guarded."""
+        stream, no synchronisation; nothing to do for an update that is not guarded.  With `options`, the configs'
+        schedules are evaluated at `progress_remaining` (schedule_factors: a bad factor is a ValueError) and the [K, 4]
+        rows of `scale` written with one non-blocking copy beside the memset; `factors` keeps them for the log."""
+        if self.options:
+            factors = [schedule_factors(c, progress_remaining) for c in self.configs]
+            if self._scale_pending:
+                self._scale_copied.synchronize()           # (the last update's copy has long left the pinned rows)
+            self._scale_host[:, :3] = torch.tensor(factors, dtype=torch.float32)
+            self.scale.copy_(self._scale_host, non_blocking=True)
+            if self._scale_copied is not None:
+                self._scale_copied.record(torch.cuda.current_stream(self.device))
+                self._scale_pending = True
+            self.factors = factors
         if self.guarded:
             self._guard_state.zero_()
+
+    def effective(self, hyper_rows=None):
+        """Per member, the learning_rate, clip_range and (where set) clip_range_vf the update begin_update() last
+        opened runs with: the hyper row's value -- `hyper_rows` ([K][8] numbers read back by the caller), else the
+        config's -- times the factor."""
+        out = []
+        for k, (c, f) in enumerate(zip(self.configs, self.factors)):
+            lr, clip = (c.learning_rate, c.clip_range) if hyper_rows is None else (hyper_rows[k][4], hyper_rows[k][0])
+            out.append({"learning_rate": lr * f[0], "clip_range": clip * f[1],
+                        **({} if c.clip_range_vf is None else {"clip_range_vf": c.clip_range_vf * f[2]})})
+        return out
 
     def _diagnostics(self):
         if not self.guarded:
@@ -404,13 +529,16 @@ class FusedUpdate(_FusedUpdater):
     With `cfg.target_kl` or `diagnostics=True` every step goes through acas2d_ppo_update_guarded_set_f32 instead, as a
     population of one (`guarded`; the hyper-parameters are then `hyper`, the config's at construction): call
     begin_update() once per PPO update, step() for every minibatch whether the learner has stopped or not, and read
-    diagnostics() afterwards.  Otherwise the calls are the ones above and begin_update() does nothing."""
+    diagnostics() afterwards.  With `cfg.clip_range_vf` or a schedule the guarded steps go through
+    acas2d_ppo_update_sb3_set_f32 (`options`; `old_val` [n]: the rollout's values, required with clip_range_vf) and
+    begin_update(progress_remaining) sets the schedules' factors.  Otherwise the calls are the ones above and
+    begin_update() does nothing."""
     _symbol, _got = 1, ", got"
 
     def __init__(self, policy, cfg, obs, act, old_logp, adv, ret, beta1=0.9, beta2=0.999, adam_eps=1e-5,
-                 diagnostics=False):
+                 diagnostics=False, old_val=None):
         super().__init__([policy.get_parameter(name) for name in PARAM_NAMES], [cfg], (obs, act, old_logp, adv, ret), (),
-                         beta1, beta2, adam_eps, diagnostics)
+                         beta1, beta2, adam_eps, diagnostics, old_val)
         self.cfg, self.betas, self.adam_eps = cfg, (beta1, beta2), adam_eps
 
     def _struct(self, idx):
@@ -558,6 +686,20 @@ class _Trainer:
         """learn() for the learners whose bookkeeping `books` holds (one _Callbacks each): iterate() runs one iteration
         and returns per learner the update's statistics, the recent episodes and the NaN events so far; evaluate() gives
         evaluate_policies_fused()'s dict, one row per learner."""
+        self.total_timesteps = total_timesteps            # (update() takes its schedules' progress_remaining from it)
+        try:
+            return self._learn_loop(total_timesteps, log, books, history, iterate, evaluate, eval_every, checkpoint_every)
+        finally:
+            self.total_timesteps = None
+
+    def _progress_remaining(self):
+        """SB3's progress_remaining for the update about to run: 1 - num_timesteps / total_timesteps inside learn(),
+        clamped at 0 (a departure from SB3, stated: the last iteration may overshoot total_timesteps, and would otherwise
+        train with a negative rate); 1.0 outside learn()."""
+        total = getattr(self, "total_timesteps", None)
+        return 1.0 if not total else max(0.0, 1.0 - self.num_timesteps / total)
+
+    def _learn_loop(self, total_timesteps, log, books, history, iterate, evaluate, eval_every, checkpoint_every):
         t0 = time.time()
         it = 0
         while self.num_timesteps < total_timesteps:
@@ -601,7 +743,12 @@ class PPOTrainer(_Trainer):
     entry: every minibatch is still launched, the host learns of a stop from update()'s statistics), op by op it is
     SB3's break before the optimizer step; the captured torch-op updater cannot stop and rejects it.  diagnostics=True
     (updater="fused"): the guarded entry without a limit.  Either adds approx_kl, clip_fraction, n_applied, early_stop and
-    explained_variance to update()'s statistics; without both, update() issues the launches it always did."""
+    explained_variance to update()'s statistics; without both, update() issues the launches it always did.
+    config.clip_range_vf and the three schedules: with updater="fused" inside FusedUpdate's kernels (its `options`
+    entry, guarded by implication), op by op through effective_config() -- the optimizer's lr is set per update; the
+    captured torch-op updater holds its numbers in a fixed graph and rejects them.  Inside learn() an update runs at
+    progress_remaining = max(0, 1 - num_timesteps / total_timesteps), outside it at 1; its statistics then carry the
+    effective learning_rate, clip_range and (where set) clip_range_vf."""
 
     def __init__(self, venv, config=None, policy=None, use_graphs=None, collector=None, updater=None, gae=None,
                  diagnostics=False):
@@ -630,6 +777,11 @@ class PPOTrainer(_Trainer):
                              "or use_graphs=False (target_kl only: SB3's break, op by op); the captured torch-op updater "
                              "replays a fixed graph and cannot stop -- got use_graphs=%r, updater=%r"
                              % (self.use_graphs, self.updater))
+        if has_options(self.cfg) and self.use_graphs and self.updater != "fused":
+            raise ValueError("clip_range_vf and the schedules need updater='fused' (they are applied inside its kernels) or "
+                             "use_graphs=False (op by op); the captured torch-op updater replays a fixed graph with the "
+                             "numbers it was captured with -- got use_graphs=%r, updater=%r" % (self.use_graphs, self.updater))
+        self.total_timesteps = None
         self.gae = gae or "torch"
         if self.gae not in ("torch", "kernel"):
             raise ValueError("gae must be None, 'torch' or 'kernel', got %r" % (gae,))
@@ -706,8 +858,10 @@ class PPOTrainer(_Trainer):
         T, E = self.cfg.n_steps, self.venv.num_envs
         flat = lambda x: x.reshape(T * E, *x.shape[2:])  # noqa: E731
         # (torch.distributions validates its arguments with a host read: not capturable -- ppo_loss() does not use it)
+        # (with updater="fused" this body is only warmed up and captured, never replayed; clip_range_vf gets its old_val)
         loss, pg, vf = ppo_loss(self.policy, self.cfg, flat(self.b_obs)[idx], flat(self.b_act)[idx],
-                                flat(self.b_logp)[idx], flat(self.b_adv)[idx], flat(self.b_ret)[idx])
+                                flat(self.b_logp)[idx], flat(self.b_adv)[idx], flat(self.b_ret)[idx],
+                                None if self.cfg.clip_range_vf is None else flat(self.b_val)[idx])
         loss.backward()
         nn.utils.clip_grad_norm_(self.policy.parameters(), self.cfg.max_grad_norm)
         self.opt.step()
@@ -831,9 +985,9 @@ class PPOTrainer(_Trainer):
             n = cfg.n_steps * self.venv.num_envs
             if self._fused_update is None:
                 self._fused_update = FusedUpdate(self.policy, cfg, self.b_obs, self.b_act, self.b_logp, self.b_adv, self.b_ret,
-                                                 diagnostics=self.diagnostics)
+                                                 diagnostics=self.diagnostics, old_val=self.b_val)
             fu = self._fused_update
-            fu.begin_update()
+            fu.begin_update(self._progress_remaining())
             for _ in range(cfg.n_epochs):
                 for idx in minibatch_schedule(torch.randperm(n, device=self.device), self.mb_idx, self.mb_tail):
                     fu.step(idx)
@@ -843,6 +997,8 @@ class PPOTrainer(_Trainer):
                 d = fu.diagnostics()
                 out.update({k: d[k] for k in ("approx_kl", "clip_fraction", "n_applied", "early_stop")})
                 out["explained_variance"] = explained_variance(self.b_val.reshape(-1), self.b_ret.reshape(-1)).item()
+            if fu.options:
+                out.update(fu.effective()[0])
             return out
         if self.use_graphs:
             n = cfg.n_steps * self.venv.num_envs
@@ -854,6 +1010,13 @@ class PPOTrainer(_Trainer):
                     "std": self.policy.log_std.detach().exp().item()}
         n = obs.shape[0]
         stats = {}
+        options = has_options(cfg)
+        if options:                                       # this update's numbers: the schedules at progress_remaining
+            cfg = effective_config(cfg, self._progress_remaining())
+            for group in self.opt.param_groups:
+                group["lr"] = cfg.learning_rate
+            if cfg.clip_range_vf is not None and old_val is None:
+                raise ValueError("update(): clip_range_vf needs old_val, the rollout's values")
         kls, cfs, n_applied, go_on = [], [], 0, True
         for _ in range(cfg.n_epochs):
             perm = torch.randperm(n, device=self.device)
@@ -861,7 +1024,8 @@ class PPOTrainer(_Trainer):
                 idx = perm[i:i + cfg.batch_size]
                 if idx.numel() < 2:
                     continue                              # a one-row tail has no advantage standard deviation
-                loss, pg, vf = ppo_loss(self.policy, cfg, obs[idx], act[idx], old_logp[idx], adv[idx], ret[idx])
+                loss, pg, vf = ppo_loss(self.policy, cfg, obs[idx], act[idx], old_logp[idx], adv[idx], ret[idx],
+                                        None if cfg.clip_range_vf is None else old_val.reshape(-1)[idx])
                 if cfg.target_kl is not None:             # SB3: measured under no_grad, the break before the optimizer step
                     kl, cf = approx_kl_and_clip_fraction(self.policy, cfg, obs[idx], act[idx], old_logp[idx])
                     kls.append(kl.item())
@@ -882,6 +1046,9 @@ class PPOTrainer(_Trainer):
                           "early_stop": not go_on})
             if old_val is not None:
                 stats["explained_variance"] = explained_variance(old_val.reshape(-1), ret.reshape(-1)).item()
+        if options:
+            stats.update({"learning_rate": cfg.learning_rate, "clip_range": cfg.clip_range,
+                          **({} if self.cfg.clip_range_vf is None else {"clip_range_vf": cfg.clip_range_vf or 0.0})})
         return stats
 
     def optimizer_state(self):
@@ -945,7 +1112,7 @@ class PPOTrainer(_Trainer):
 # ---- K learners at once: the seeds or hyper-parameter sets of a sweep as ONE population ---------------------------------
 # what may differ between the members of a population, and what the shared launches need equal
 MEMBER_FIELDS = ("seed", "learning_rate", "clip_range", "ent_coef", "vf_coef", "max_grad_norm", "gamma", "gae_lambda",
-                 "target_kl")
+                 "target_kl", "clip_range_vf") + SCHEDULE_FIELDS
 SHARED_FIELDS = ("n_steps", "batch_size", "n_epochs")
 # (HYPER_SLOTS, the row a member's hyper-parameters travel in, is defined beside hyper_row() above)
 
@@ -1027,18 +1194,22 @@ class FusedUpdateSet(_FusedUpdater):
     acas2d_ppo_update_guarded_set_f32 instead (`guarded`; csrc/acas2d_ppo_guard.hip): `target_kl` is a float32 device
     tensor [K] (0: no limit) beside `hyper`, `stopped` int32 [K] and `diag` float32 [K, 8] are the kernels'.  Call
     begin_update() once per PPO update, step() for every minibatch -- a stopped member's share of the two launches
-    returns at once -- and read diagnostics() afterwards.  Otherwise the calls are the ones above."""
+    returns at once -- and read diagnostics() afterwards.  Where a member's config has a `clip_range_vf` or a schedule
+    the guarded steps go through acas2d_ppo_update_sb3_set_f32 (`options`; csrc/acas2d_ppo_sb3.hip): `old_val` [n] is the
+    rollout's values, `clip_range_vf` a float32 device tensor [K] (0: plain MSE) and `scale` [K, 4] the factors that
+    begin_update(progress_remaining) writes; the kernels multiply them into the `hyper` rows as they are at that moment.
+    Otherwise the calls are the ones above."""
 
     _symbol, _got = 2, ", float32; got"
 
     def __init__(self, policy_set, configs, obs, act, old_logp, adv, ret, beta1=0.9, beta2=0.999, adam_eps=1e-5,
-                 diagnostics=False):
+                 diagnostics=False, old_val=None):
         D, K = obs.shape[-1], policy_set.n_members
         self._entry_for(D)
         if len(configs) != K or policy_set.obs_dim != D:
             raise ValueError("FusedUpdateSet needs one config per member and members of obs_dim %d" % D)
         super().__init__([policy_set.params[name] for name in PARAM_NAMES], list(configs), (obs, act, old_logp, adv, ret),
-                         (K,), beta1, beta2, adam_eps, diagnostics)
+                         (K,), beta1, beta2, adam_eps, diagnostics, old_val)
         self.policy_set, self.K = policy_set, K
 
     def step(self, idx, apply=True):
@@ -1081,7 +1252,10 @@ class PopulationTrainer(_Trainer):
     target_kl may differ between members (None: no limit): a member whose minibatch exceeds 1.5 x its target_kl sits out
     the rest of that update() while the others go on in the same launches, decided on the device (FusedUpdateSet's
     guarded entry).  With a target_kl anywhere, or diagnostics=True, update() adds approx_kl, clip_fraction, n_applied,
-    early_stop and explained_variance per member; without both it issues the launches it always did."""
+    early_stop and explained_variance per member; without both it issues the launches it always did.
+    clip_range_vf and the three schedules may differ between members too (None: off): with one anywhere the update goes
+    through FusedUpdateSet's `options` entry, a member without them getting neutral numbers in the same launches, and
+    update() adds every member's effective learning_rate, clip_range and (where set) clip_range_vf."""
 
     def __init__(self, venv, configs, gae=None, group=False, diagnostics=False):
         configs = list(configs)
@@ -1138,6 +1312,7 @@ class PopulationTrainer(_Trainer):
         self.num_timesteps = 0
         self.ep_returns, self.ep_lengths, self.ep_outcomes = ([[] for _ in range(K)] for _ in range(3))
         self.history = []
+        self.total_timesteps = None
         self._fused_out = self._fused_update = None
         E, T, dev = venv.num_envs, self.cfg.n_steps, self.device
         self._alloc_rollout()
@@ -1179,7 +1354,7 @@ class PopulationTrainer(_Trainer):
 
     def _make_fused_update(self):
         return FusedUpdateSet(self.policy_set, self.configs, self.b_obs, self.b_act, self.b_logp, self.b_adv, self.b_ret,
-                              diagnostics=self.diagnostics)
+                              diagnostics=self.diagnostics, old_val=self.b_val)
 
     def update(self):
         cfg, K = self.cfg, self.K
@@ -1187,7 +1362,8 @@ class PopulationTrainer(_Trainer):
         if self._fused_update is None:
             self._fused_update = self._make_fused_update()
         fu = self._fused_update
-        fu.begin_update()
+        fu.begin_update(self._progress_remaining())
+        hyper_before = self._hyper_rows(fu) if fu.options else None
         for _ in range(cfg.n_epochs):
             perm = torch.stack([torch.randperm(n, device=self.device, generator=g) for g in self.generators])
             rows = self.member_rows.gather(1, perm)       # [K, n]: each member's permutation, as rows of the shared buffer
@@ -1202,7 +1378,16 @@ class PopulationTrainer(_Trainer):
             for k, d in enumerate(fu.diagnostics()):
                 out[k].update({n: d[n] for n in ("approx_kl", "clip_fraction", "n_applied", "early_stop")})
                 out[k]["explained_variance"] = ev[k]
+        if fu.options:
+            for k, eff in enumerate(fu.effective(hyper_before)):
+                out[k].update(eff)
         return out
+
+    def _hyper_rows(self, fu):
+        """The hyper rows this update runs with, for the log's learning_rate / clip_range: None, the configs' own --
+        nothing in a PopulationTrainer rewrites the rows.  PBTTrainer answers with the rows its last exploit() read back;
+        a caller who writes into the device `hyper` tensor by hand changes what the kernels use, not what is logged."""
+        return None
 
     def optimizer_state(self):
         """The members' Adam state: step [K], exp_avg / exp_avg_sq [K, n] in the flat layout of include/acas2d.h."""
@@ -1372,7 +1557,10 @@ class PBTTrainer(PopulationTrainer):
     its minibatch generator, so twins diverge.  gamma and gae_lambda live outside the hyper row and are not exchanged:
     they must be equal across members.  A member's target_kl is not in the hyper row either and belongs to its SLOT:
     an exploit step neither copies nor perturbs it, so a recipient keeps its own limit under the donor's weights and
-    learning rate -- the guard against what the x 1.2 steps can build up.  fraction = 0 is PopulationTrainer bit for bit.
+    learning rate -- the guard against what the x 1.2 steps can build up.  clip_range_vf and the schedules belong to the
+    slot likewise; a schedule's factor multiplies the hyper row as the exploit steps have left it, and update()'s
+    learning_rate / clip_range are formed from the rows read back at the last exploit (no extra read-back: rows edited
+    by hand through `hyper` in between reach the kernels but not that log).  fraction = 0 is PopulationTrainer bit for bit.
     group=True, gae="kernel" and diagnostics=True as the parent's."""
 
     def __init__(self, venv, configs, pbt, gae=None, group=False, diagnostics=False):
@@ -1389,11 +1577,15 @@ class PBTTrainer(PopulationTrainer):
         self.window = None
         self.generation = 0
         self._updates = 0
+        self._hyper_host = None                           # the rows as the last exploit's read-back found them
 
     @property
     def hyper(self):
         """The members' current hyper rows: float32 device tensor [K, 8] (HYPER_SLOTS)."""
         return self._fused_update.hyper
+
+    def _hyper_rows(self, fu):
+        return self._hyper_host
 
     def collect(self):
         super().collect()
@@ -1414,6 +1606,7 @@ class PBTTrainer(PopulationTrainer):
         donor = population_exploit(self.policy_set, self._fused_update, w["score"], self.n_replace, self.generation,
                                    pbt.seed, perturb=pbt.perturb, factors=pbt.factors, bounds=pbt.bounds)
         donor, hyper, score = donor.cpu().tolist(), self.hyper.cpu().tolist(), w["score"].cpu().tolist()
+        self._hyper_host = hyper
         for n in ("count", "outcomes", "steps", "return_sum"):
             w[n].zero_()
         w["score"].fill_(float("nan"))

@@ -504,6 +504,43 @@ int acas2d_ppo_update_guarded_set_f32(const Acas2dPpoUpdateSet *u, const Acas2dP
 size_t acas2d_ppo_guard_size(void);     /* sizeof(Acas2dPpoGuard): layout check for bindings */
 
 /*
+ * acas2d_ppo_update_sb3_set_f32: acas2d_ppo_update_guarded_set_f32 with the rest of SB3 1.1.0's PPO.__init__ -- clip_range_vf
+ * (the value-function clipping) and per-update factors on learning_rate, clip_range and clip_range_vf, which is what a
+ * schedule of progress_remaining evaluates to.  Additive to ABI 7.  float32.  ONE entry for obs_dim in {8, 11, 14, 17, 29,
+ * 53, 101, 197}; `u` and `g` are the sibling's structs with the sibling's layouts and meaning (target_kl[k] <= 0: only the
+ * statistics), K = 1 serves a single learner.  The same two launches, no read-back:
+ *   gradient launch   a member with stopped[k] != 0 does nothing.  An actor workgroup uses clip_range = hyper[k][0] *
+ *                     scale[k][1], ONE float32 product, for the clipped surrogate and for diag[k][1]'s clipped count
+ *                     alike.  A critic workgroup forms c = clip_range_vf[k] * scale[k][2], one float32 product; if c > 0 a
+ *                     live row s with critic output `out` takes SB3's clipped value loss,
+ *                       d = out - old_val[s];  vp = old_val[s] + fminf(fmaxf(d, -c), c);  e = vp - ret[s]
+ *                       value loss += e * e / n_rows;  d loss / d out = (-c <= d && d <= c) ? vf_coef * 2 e / n_rows : 0
+ *                     (values_pred = old_values + clamp(values - old_values, -c, c), F.mse_loss(returns, values_pred): no
+ *                     max with the unclipped loss, and torch's clamp passes the gradient on the closed interval).
+ *                     Otherwise (c <= 0 or NaN) the row takes the sibling's plain MSE branch and old_val is NOT READ for
+ *                     member k.
+ *   apply launch      the sibling's statistics, stop decision and stats moves, then the sibling's apply with learning
+ *                     rate hyper[k][4] * scale[k][0], one float32 product.
+ * The factors multiply whatever hyper[k] holds when the kernels run, so they compose with acas2d_population_exploit_f32
+ * rewriting those rows on the device.  The caller writes scale (and zeroes `stopped` / `diag`) where SB3 enters train().
+ * Neutral options: scale rows of ones and clip_range_vf of zeros give acas2d_ppo_update_guarded_set_f32's parameters,
+ * adam_m, adam_v, adam_step, stats and diag -- bit for bit where n_rows <= 64 (x * 1.0f is exact, one atomic add per
+ * gradient entry), to the siblings' run-to-run rounding otherwise.  LDS as the siblings'.
+ * ACAS2D_EINVAL before any HIP call: what the guarded entry rejects, a NULL `o`, and a NULL pointer in `o` (the message
+ * names the field).  Out of scope: float64, members with different n_rows.
+ */
+typedef struct Acas2dPpoOptions {
+    const void *old_val;                /* float[n_total]: the rollout's values, rows as obs / act / ... */
+    const void *clip_range_vf;          /* device float[K]; <= 0: plain MSE for member k, old_val not read */
+    const void *scale;                  /* device float[K][4]: factors on learning_rate, clip_range, clip_range_vf of
+                                           this update; [3] reserved, not read */
+} Acas2dPpoOptions;
+
+int acas2d_ppo_update_sb3_set_f32(const Acas2dPpoUpdateSet *u, const Acas2dPpoGuard *g, const Acas2dPpoOptions *o,
+                                  void *stream);
+size_t acas2d_ppo_options_size(void);   /* sizeof(Acas2dPpoOptions): layout check for bindings */
+
+/*
  * acas2d_gae_f32: what lies between acas2d_collect_* and acas2d_ppo_update_* in a PPO iteration, in ONE launch -- the
  * critic's value of the last observation (optional) and SB3 1.1.0's RolloutBuffer.compute_returns_and_advantage (GAE)
  * over the collector's [T][E] buffers (`PPO.learn()`, training_main.py:44-52).  Additive to ABI 7.  float32.

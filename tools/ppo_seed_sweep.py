@@ -61,9 +61,19 @@ ap.add_argument("--gae", choices=("torch", "kernel"), default=None,
 ap.add_argument("--target-kl", type=float, default=None,
                 help="SB3's target_kl for every run of the sweep (decided inside the fused update's launches, DESIGN.md 4.2h): "
                      "the records then carry the last update's approx_kl, clip_fraction and n_applied")
+ap.add_argument("--clip-range-vf", type=float, default=None, metavar="X",
+                help="SB3's clip_range_vf for every run of the sweep (inside the fused update's launches, DESIGN.md 4.2j)")
+ap.add_argument("--lr-schedule", choices=("constant", "linear"), default="constant",
+                help="linear: the learning rate falls linearly to 0 over --timesteps (a factor on the rate; with --pbt on "
+                     "whatever rate the exploit steps have left a member)")
+ap.add_argument("--clip-schedule", choices=("constant", "linear"), default="constant",
+                help="linear: the clip range falls linearly to 0 over --timesteps, likewise")
 args = ap.parse_args()
 if args.pbt and not args.population:
     ap.error("--pbt needs --population")
+# the schedules as PPOConfig takes them (callables: kept out of `kw`, which goes into the records as JSON)
+SCHEDULES = dict(learning_rate_schedule=g.ppo.linear_schedule() if args.lr_schedule == "linear" else None,
+                 clip_range_schedule=g.ppo.linear_schedule() if args.clip_schedule == "linear" else None)
 # "kernel" where learn() with it beat gae="torch" by more than both variants' spreads (the fused-collector
 # PPOTrainer by 2 % at 512 steps and 13 % at 128, the population by 3 %); a trainer that were not faster would say "torch"
 GAE_DEFAULT = {"population": "kernel", "solo": "kernel"}
@@ -85,13 +95,15 @@ GROUP = N in g.ppo.GROUP_TRAFFIC                       # the group-cooperative l
 own, trf, goal = H.parity_reset_states(g.ACAS2DConfig(n_traffic=N), 13, 0, 100)
 score = dict(dtype=torch.float32, config=g.ACAS2DConfig(n_traffic=N), group=True) if GROUP else {}
 for name in args.sets:
-    kw = {**dict(n_steps=256, batch_size=4096), **SETS[name], **({} if args.target_kl is None else {"target_kl": args.target_kl})}
+    kw = {**dict(n_steps=256, batch_size=4096), **SETS[name], **({} if args.target_kl is None else {"target_kl": args.target_kl}),
+          **({} if args.clip_range_vf is None else {"clip_range_vf": args.clip_range_vf})}
+    sched = {"lr_schedule": args.lr_schedule, "clip_schedule": args.clip_schedule}
     goals = []
     if args.population:
         t0 = time.time()
         K = len(args.seeds)
         venv = g.ACAS2DVecEnv(K * args.envs, N, device="cuda:0", dtype=torch.float32, seed=13)
-        cfgs = [g.PPOConfig(seed=seed, **kw) for seed in args.seeds]
+        cfgs = [g.PPOConfig(seed=seed, **kw, **SCHEDULES) for seed in args.seeds]
         if args.pbt:
             pop = g.PBTTrainer(venv, cfgs, g.PBTConfig(ready_every=args.pbt_every, fraction=args.pbt_fraction), gae=args.gae,
                                group=GROUP)
@@ -102,7 +114,7 @@ for name in args.sets:
         wall = time.time() - t0
         for k, seed in enumerate(args.seeds):
             last = [r for r in hist if r["member"] == k and not r.get("eval") and "exploit" not in r][-1]
-            rec = {"set": name, "config": kw, "seed": seed, "population": K, "member": k, "timesteps": int(args.timesteps),
+            rec = {"set": name, "config": kw, **sched, "seed": seed, "population": K, "member": k, "timesteps": int(args.timesteps),
                    "wall_s": wall, "train_ep_rew_mean_last": last.get("ep_rew_mean"), "std": last.get("std"),
                    **{n: last[n] for n in ("approx_kl", "clip_fraction", "n_applied") if n in last},
                    "eval_mean_return": float(out["total_reward"][k].mean()), "eval_mean_steps": float(out["steps"][k].mean()),
@@ -118,10 +130,10 @@ for name in args.sets:
     for seed in ([] if args.population else args.seeds):
         t0 = time.time()
         venv = g.ACAS2DVecEnv(args.envs, N, device="cuda:0", dtype=torch.float32, seed=13)
-        tr = g.PPOTrainer(venv, g.PPOConfig(seed=seed, **kw), collector="fused", updater="fused", gae=args.gae)
+        tr = g.PPOTrainer(venv, g.PPOConfig(seed=seed, **kw, **SCHEDULES), collector="fused", updater="fused", gae=args.gae)
         hist = tr.learn(int(args.timesteps), log=None)
         out = g.evaluate_policy_fused(tr.policy, own, trf, goal, **score)
-        rec = {"set": name, "config": kw, "seed": seed, "timesteps": int(args.timesteps), "wall_s": time.time() - t0,
+        rec = {"set": name, "config": kw, **sched, "seed": seed, "timesteps": int(args.timesteps), "wall_s": time.time() - t0,
                "train_ep_rew_mean_last": hist[-1].get("ep_rew_mean"), "std": hist[-1].get("std"),
                **{n: hist[-1][n] for n in ("approx_kl", "clip_fraction", "n_applied") if n in hist[-1]},
                "eval_mean_return": float(out["total_reward"].mean()), "eval_mean_steps": float(out["steps"].mean()),

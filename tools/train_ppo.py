@@ -37,6 +37,15 @@ ap.add_argument("--target-kl", type=float, default=None,
                      "(fused updater: decided inside the update's own launches, DESIGN.md 4.2h; --collector eager: SB3's break); "
                      "the log then carries approx_kl, clip_fraction, n_applied, early_stop and explained_variance.  Not with "
                      "--updater graphs")
+ap.add_argument("--clip-range-vf", type=float, default=None, metavar="X",
+                help="SB3's clip_range_vf: the value loss on old_values + clamp(values - old_values, -X, X), inside the fused "
+                     "update's launches (DESIGN.md 4.2j) or op by op (--collector eager).  It depends on the reward scale: "
+                     "returns here are of order 1e3.  Not with --updater graphs")
+ap.add_argument("--lr-schedule", choices=("constant", "linear"), default="constant",
+                help="linear: the learning rate falls linearly to 0 over --timesteps (SB3's linear schedule, as a factor on the "
+                     "rate -- in a --pbt population on whatever rate the exploit steps have left a member)")
+ap.add_argument("--clip-schedule", choices=("constant", "linear"), default="constant",
+                help="linear: the clip range falls linearly to 0 over --timesteps, likewise")
 ap.add_argument("--population", type=int, default=0, metavar="K",
                 help="train K learners with the seeds --seed ... --seed + K - 1 side by side in one process "
                      "(ppo.PopulationTrainer: one collection launch and two launches per minibatch for all K; each member gets "
@@ -52,6 +61,10 @@ ap.add_argument("--out", default=None)
 args = ap.parse_args()
 if args.pbt and not args.population:
     ap.error("--pbt needs --population K")
+# clip_range_vf and the schedules, as PPOConfig takes them
+OPTIONS = dict(clip_range_vf=args.clip_range_vf,
+               learning_rate_schedule=g.ppo.linear_schedule() if args.lr_schedule == "linear" else None,
+               clip_range_schedule=g.ppo.linear_schedule() if args.clip_schedule == "linear" else None)
 # "kernel" where learn() with it beat gae="torch" by more than both variants' spreads (the fused-collector
 # PPOTrainer by 2 % at 512 steps and 13 % at 128, the population by 3 %); a trainer that were not faster would say "torch"
 GAE_DEFAULT = {"population": "kernel", "solo": "kernel"}
@@ -70,8 +83,8 @@ if args.population:
     import helpers as H
     K = args.population
     venv = g.ACAS2DVecEnv(K * args.envs, args.traffic, device="cuda:0", dtype=torch.float32, seed=13)
-    cfgs = [g.PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, seed=args.seed + k, target_kl=args.target_kl)
-            for k in range(K)]
+    cfgs = [g.PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, seed=args.seed + k, target_kl=args.target_kl,
+                        **OPTIONS) for k in range(K)]
     if args.pbt:
         pop = g.PBTTrainer(venv, cfgs, g.PBTConfig(ready_every=args.pbt_every, fraction=args.pbt_fraction, seed=args.seed),
                            gae=args.gae, group=args.traffic in g.ppo.GROUP_TRAFFIC)
@@ -91,7 +104,8 @@ if args.population:
     sys.exit(0)
 
 venv = g.ACAS2DVecEnv(args.envs, args.traffic, device="cuda:0", dtype=torch.float32, seed=13)
-trainer = g.PPOTrainer(venv, g.PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, seed=args.seed, target_kl=args.target_kl),
+trainer = g.PPOTrainer(venv, g.PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, seed=args.seed, target_kl=args.target_kl,
+                                         **OPTIONS),
                        collector=args.collector,
                        use_graphs=args.collector != "eager", updater=args.updater if args.collector != "eager" else "graphs", gae=args.gae)
 hist = trainer.learn(int(args.timesteps), log=lambda r: print(json.dumps(r), flush=True))
