@@ -4,9 +4,9 @@ No GPU is needed here: everything is NumPy and CPU torch.
 
 make(D, B, case, seed, K=1, clips=(0.2,)) returns an EdgeBatch: float32 rollout buffers obs [n, D], act, old_logp, adv,
 ret [n] with n = K B + 317 > K B, an int64 idx [K, B] of rows into them (member k's minibatch; the members' rows are
-disjoint), K float32 ActorCritic(D) on the CPU with the head x 40 (test_learner_kernels._Batch), and `labels`: the
+disjoint), K float32 ActorCritic(D) on the CPU with the head x 40 (learner_support.RolloutBatch), and `labels`: the
 measured quantities that make the case the case it claims to be, taken on the minibatch rows (check_labels asserts
-them).  old_logp is _Batch.set_old_logp's "mixed" mode from the case's own policy on every row of the member's pool:
+them).  old_logp is RolloutBatch.set_old_logp's "mixed" mode from the case's own policy on every row of the member's pool:
 float64 log-prob + N(0, 0.5) noise (cut at 5 sigma = 2.5: no row has logp - old_logp > 3; float32 expf overflow of the
 ratio is not a case), ratios within 1e-4 of a clip edge moved off it.
 
@@ -32,7 +32,7 @@ CASES:
                other row's advantage is -64 x the run's: the minibatch mean is an exact 0).
   underflow    max(2, B // 10) rows (1 at B < 4) have logp - old_logp = -110: the ratio is 0 in float32, 1e-48 in
                float64; they carry both signs of the normalised advantage.  The other rows are "mixed".
-"mixed" is _Batch's own minibatch (the large-B tests use it beside grid_adv)."""
+"mixed" is RolloutBatch's own minibatch (the large-B tests use it beside grid_adv)."""
 import numpy as np
 import torch
 
@@ -155,7 +155,7 @@ def dup_idx(B, pool, first, last, rng):
 
 
 def mixed_old_logp(ac_cls, D, theta, obs, act, clip, rng):
-    """_Batch.set_old_logp("mixed") for the rows given: float32 old log-probs, and how many were moved off a clip edge."""
+    """RolloutBatch.set_old_logp("mixed") for the rows given: float32 old log-probs, and how many were moved off a clip edge."""
     lp = R.logp64(ac_cls, D, theta, obs, act)
     old = (lp + np.clip(rng.normal(0, 0.5, len(lp)), -2.5, 2.5)).astype(np.float32).astype(np.float64)
     return nudge_off_edges(lp, old, clip)

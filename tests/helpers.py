@@ -1,4 +1,4 @@
-"""Shared test machinery: golden-vector loading and engine-agnostic replay loops.
+"""Shared test machinery: golden-vector loading, engine-agnostic replay loops and the one reader of kernel metadata.
 
 An "engine" here is anything with the OracleEnvs interface (oracle/oracle.py): numpy float64
 views  own_x, own_y, own_psi, trf_x, trf_y, steps, total_reward  plus
@@ -8,11 +8,19 @@ interface so that both are checked by the same code against the same fixtures.
 """
 import os
 import random
+import re
+import shlex
+import shutil
+import subprocess
 from collections import namedtuple
 
 import numpy as np
+import pytest
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "gym-acas2d_amd", "csrc")
+HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def load(name):
@@ -136,6 +144,35 @@ def assert_matches_reference_policy_eval(total_reward, steps, path_length, tol=2
     for col, want in REF_POLICY_EVAL.items():
         for k, w in want.items():
             assert abs(got[col][k] - w) <= tol * max(1.0, abs(w)), (col, k, got[col][k], w)
+
+
+# ---- code-object metadata -----------------------------------------------------------------------------------------------
+needs_hipcc = pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="needs hipcc")
+
+
+class Kernel(namedtuple("Kernel", "name entry")):
+    """One kernel of a code object: its mangled name and its whole entry of amdhsa.kernels (every field, the ones sorted
+    before .name -- group_segment_fixed_size, max_flat_workgroup_size -- included)."""
+    __slots__ = ()
+
+    def field(self, key):
+        return int(re.search(r"^    \.%s:\s+(\d+)$" % key, self.entry, re.M).group(1))
+
+
+def kernel_metadata(tmp_path, unit):
+    """csrc/<unit> (say "acas2d_ppo_set.hip") compiled to device assembly WITH THE FLAGS THE MAKEFILE GIVES IT: the compile
+    command of <unit>.o is taken from a dry run of make (nothing is built, nothing is written into the tree) and its
+    `-c <unit> -o <unit>.o` swapped for `-S --cuda-device-only -o <tmp_path>/<unit>.s`.  Returns the assembly text and one
+    Kernel per kernel of the unit."""
+    hipcc = HIPCC if os.path.exists(HIPCC) else "hipcc"
+    obj = unit[:-len(".hip")] + ".o"
+    dry = subprocess.run(["make", "-n", "-B", "HIPCC=" + hipcc, obj], cwd=CSRC, check=True, capture_output=True, text=True)
+    cmd, = [shlex.split(ln) for ln in dry.stdout.splitlines() if ln.endswith(" -c %s -o %s" % (unit, obj))]
+    asm = tmp_path / (unit + ".s")
+    subprocess.run(cmd[:-4] + ["-S", "--cuda-device-only", "-o", str(asm), unit], cwd=CSRC, check=True, capture_output=True)
+    text = asm.read_text()
+    entries = ["    .agpr_count:" + e for e in re.split(r"\n  - \.agpr_count:", text.split("amdhsa.kernels:")[1])[1:]]
+    return text, [Kernel(re.search(r"^    \.name:\s+(\S+)$", e, re.M).group(1), e) for e in entries]
 
 
 # ---- work-shape coverage ------------------------------------------------------------------------------------------

@@ -88,7 +88,7 @@ def value64(ac_cls, D, theta, obs):
 
 def place_old_val(rng, value, c, sigma=0.8):
     """float32 old values = value + N(0, sigma) with every row's | |value - old| - c | >= EDGE: rows closer are moved off,
-    as SharedBatch.set_old_logp does for ratios.  c None or <= 0: no edge to keep away from."""
+    as RolloutBatch.set_old_logp does for ratios.  c None or <= 0: no edge to keep away from."""
     old = (np.asarray(value, np.float64) + rng.normal(0, sigma, len(value))).astype(np.float32).astype(np.float64)
     if c is not None and c > 0:
         for _ in range(4):

@@ -1,6 +1,6 @@
 """The edge minibatches of tests/edge_minibatches.py on the CPU: every case is the case it claims to be (its labels), and
 every case is ADMITTED -- ppo.ppo_loss() with float32 autograd on the CPU meets the float64 reference
-(learner_ref.grad64) under the per-tensor criterion of test_learner_kernels._assert_per_tensor with tau <= TAU / 4 =
+(learner_ref.grad64) under the per-tensor criterion of learner_support.assert_per_tensor with tau <= TAU / 4 =
 5e-6, so the bound the GPU tests hold the kernels to (TAU = 2e-5) is one that plain float32 clears with room.  A case
 that misses is re-tuned in edge_minibatches.py, never given a wider bound.  Every batch tests/test_learner_edges.py runs
 is admitted here: the solo batches at D = 8, 29, 53, 197, the three-member batches of the set update at the same four
@@ -13,25 +13,15 @@ import pytest
 
 import edge_minibatches as E
 import learner_ref as R
+import learner_support as LS
 
 torch = pytest.importorskip("torch")
-import test_learner_kernels as K  # noqa: E402  (its criterion and bounds; nothing in it runs at import)
-
-ADMIT_TAU = K.TAU / 4
+ADMIT_TAU = LS.TAU / 4
 WIDTHS, ROWS = (8, 29, 53, 197), (2, 65, 130)
 SOLO = [(D, B, case) for D in WIDTHS for B in ROWS for case in E.CASES]
 SET = [(D, B, case) for D in WIDTHS for B in ROWS for case in E.CASES]
 LARGE = [(D, 8193, case) for D in (8, 197) for case in ("grid_adv", "mixed")]
 _ID = lambda c: "D%d-B%d-%s" % c  # noqa: E731
-_cache = {}
-
-
-def batch(kind, D, B, case):
-    """The batch of test_learner_edges.py for this case, built once per session and never written to."""
-    key = (kind, D, B, case)
-    if key not in _cache:
-        _cache[key] = E.make(D, B, case, E.seed_of(D, B, case), **(E.SET_LAYOUT if kind == "set" else {}))
-    return _cache[key]
 
 
 def _grad32(g, bt, k, cfg):
@@ -47,7 +37,7 @@ def _grad32(g, bt, k, cfg):
 
 def _admit(kind, D, B, case):
     import gym_acas2d_amd as g
-    bt = batch(kind, D, B, case)
+    bt = LS.edge_batch(kind, D, B, case)
     segs = R.segments(bt.pols[0])
     worst = -np.inf
     for k in range(bt.K):
@@ -55,9 +45,8 @@ def _admit(kind, D, B, case):
         ref, pg, vf, ratio = R.grad64(bt.ac_cls, cfg, D, bt.theta(k), *bt.rows(k))
         got, pg32, vf32 = _grad32(g, bt, k, cfg)
         assert np.isfinite(got).all() and np.isfinite(ref).all()
-        errs, ref_all = R.per_tensor_errors(got, ref, segs)
-        worst = max(worst, K._worst_ratio(errs, ref_all))
-        K._assert_per_tensor("admission %s %s D=%d B=%d member %d" % (kind, case, D, B, k), got, ref, segs, ADMIT_TAU)
+        worst = max(worst, LS.assert_per_tensor("admission %s %s D=%d B=%d member %d" % (kind, case, D, B, k), got, ref, segs,
+                                                ADMIT_TAU))
         assert abs(pg32 - pg) <= 1e-5 * max(1.0, abs(pg)) / 4 and abs(vf32 - vf) <= 1e-5 * max(1.0, vf) / 4, (pg32, pg, vf32, vf)
         if case == "const_adv":
             n_actor = segs[5][2]
@@ -69,13 +58,13 @@ def _admit(kind, D, B, case):
 
 @pytest.mark.parametrize("D,B,case", SOLO, ids=[_ID(c) for c in SOLO])
 def test_solo_case_is_what_it_claims_and_is_admitted(D, B, case):
-    E.check_labels(batch("solo", D, B, case))
+    E.check_labels(LS.edge_batch("solo", D, B, case))
     _admit("solo", D, B, case)
 
 
 @pytest.mark.parametrize("D,B,case", SET, ids=[_ID(c) for c in SET])
 def test_set_case_is_what_it_claims_and_is_admitted(D, B, case):
-    bt = batch("set", D, B, case)
+    bt = LS.edge_batch("set", D, B, case)
     assert bt.K == 3 and bt.clips == (0.1, 0.2, 0.3)
     E.check_labels(bt)
     _admit("set", D, B, case)
@@ -83,7 +72,7 @@ def test_set_case_is_what_it_claims_and_is_admitted(D, B, case):
 
 @pytest.mark.parametrize("D,B,case", LARGE, ids=[_ID(c) for c in LARGE])
 def test_large_minibatch_is_admitted(D, B, case):
-    bt = batch("solo", D, B, case)
+    bt = LS.edge_batch("solo", D, B, case)
     E.check_labels(bt)
     if case == "grid_adv":
         assert bt.labels["grid"][0]["c"] == 64.0
@@ -116,7 +105,7 @@ def test_grid_advantage_statistics_do_not_depend_on_the_order():
 def test_one_common_factor_cannot_place_both_layers():
     """Why `saturated` scales each hidden matrix by its own factor: at D = 8 no single factor on both hidden matrices of
     the actor puts max |z1| AND max |z2| inside [15, 30] on the case's own rows."""
-    bt = batch("solo", 8, 130, "mixed")
+    bt = LS.edge_batch("solo", 8, 130, "mixed")
     x = bt.obs[bt.idx[0]]
     ok = []
     for f in np.geomspace(1.0, 100.0, 200):

@@ -7,18 +7,16 @@ collector: the value of an observation equals what a collection started on it st
 option and the torch-free C++ host (examples/c_abi_ppo_example.cpp) are run end to end."""
 import ctypes as C
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
+import helpers as H
+
 torch = pytest.importorskip("torch")
 DEV = "cuda:0"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gym-acas2d_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+ROOT, CSRC = H.ROOT, H.CSRC
 FLT_MAX = np.finfo(np.float32).max
 
 
@@ -143,23 +141,17 @@ def test_gae_rejections_and_struct_size_without_a_device():
     assert b"wide" in L.acas2d_last_error() and b"last_value" in L.acas2d_last_error()
 
 
-@pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="needs hipcc")
+@H.needs_hipcc
 def test_gae_kernels_use_no_scratch_and_spill_nothing(tmp_path):
     """The code-object metadata of csrc/acas2d_gae.hip, read the way tests/test_build_resources.py reads it: the sweep
     keeps two blocks of 16 rows in registers, and the bootstrap variants stream a critic through SGPRs on top."""
-    asm = tmp_path / "acas2d_gae.s"
-    subprocess.run([HIPCC if os.path.exists(HIPCC) else "hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-ffp-contract=off", "-fno-slp-vectorize", "-mllvm",
-                    "-amdgpu-kernarg-preload-count=8", "-S", "--cuda-device-only", "-o", str(asm),
-                    os.path.join(CSRC, "acas2d_gae.hip")], check=True, capture_output=True)
-    kernels = re.findall(r"\.name:\s+(\S+)\n(.*?)\.wavefront_size", asm.read_text(), re.S)
+    _, kernels = H.kernel_metadata(tmp_path, "acas2d_gae.hip")
     assert len(kernels) == 6                              # last_value given + five observation widths
-    field = lambda body, k: int(re.search(r"\.%s:\s+(\d+)" % k, body).group(1))  # noqa: E731
-    for name, body in kernels:
-        assert "gae_kernel" in name
-        print(name, "vgpr", field(body, "vgpr_count"), "sgpr", field(body, "sgpr_count"))
-        assert field(body, "vgpr_spill_count") == 0 and field(body, "sgpr_spill_count") == 0, name
-        assert field(body, "private_segment_fixed_size") == 0 and field(body, "vgpr_count") <= 256, name
+    for k in kernels:
+        assert "gae_kernel" in k.name
+        print(k.name, "vgpr", k.field("vgpr_count"), "sgpr", k.field("sgpr_count"))
+        assert k.field("vgpr_spill_count") == 0 and k.field("sgpr_spill_count") == 0, k.name
+        assert k.field("private_segment_fixed_size") == 0 and k.field("vgpr_count") <= 256, k.name
 
 
 # ---- GPU: the sweep ---------------------------------------------------------------------------------------------------

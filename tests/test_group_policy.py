@@ -22,6 +22,7 @@ import pytest
 
 import helpers as H
 import learner_ref as R
+import learner_support as LS
 
 torch = pytest.importorskip("torch")
 DEV = "cuda:0"
@@ -147,47 +148,6 @@ def _envs(g, N, E, count, cfg, **kw):
     return [g.ACAS2DVecEnv(E, N, device=DEV, dtype=torch.float32, config=cfg, **kw) for _ in range(count)]
 
 
-def _parallel_flight(env, rows):
-    """Put traffic[0] of the env rows `rows` on the player's heading and speed (the reference's d_cpa is 0 / 0 there) and
-    observe.  Returns (own, trf, goal) as injected and the first observation."""
-    own = torch.stack([env.own_x, env.own_y, env.own_psi, env.own_v], 1).double().cpu().numpy()
-    trf = torch.stack([env.trf_x, env.trf_y, env.trf_psi, env.trf_v], -1).double().cpu().numpy()
-    goal = torch.stack([env.goal_x, env.goal_y], 1).double().cpu().numpy()
-    trf[rows, 0, 2], trf[rows, 0, 3] = own[rows, 2], own[rows, 3]
-    obs0 = env.set_state(own, trf, goal, np.zeros(env.num_envs, np.int32), observe=True).double().cpu().numpy()
-    return (own, trf, goal), obs0
-
-
-def _actor_critic(g, D, seed=1):
-    torch.manual_seed(seed)
-    pol = g.ActorCritic(D).to(DEV)
-    with torch.no_grad():
-        pol.action_net.weight.mul_(40.0)
-        pol.log_std.fill_(-0.7)
-    return pol
-
-
-def _scaled_actor(g, D, kind, obs0):
-    """An SB3 actor whose hidden pre-activations reach |z| = 60 on obs0 in both layers ("saturating"), stay within 0.05 of
-    0 ("small"), or are SB3's own ("plain"); the head is scaled so that |mean - b3| reaches 1.5 (0.3 for the near-zero
-    one), as tests/test_learner_kernels.py does for the thread-per-env kernels."""
-    torch.manual_seed(7)
-    pol = g.ActorCritic(D).double()
-    pn = pol.mlp_extractor.policy_net
-    x = R.obs32(obs0[np.isfinite(obs0).all(1)])
-    with torch.no_grad():
-        if kind != "plain":
-            target = 60.0 if kind == "saturating" else 0.05
-            z1, _ = R.preactivations64(R.params64(pol), x)
-            pn[0].weight.mul_(target / np.abs(z1).max())
-            _, z2 = R.preactivations64(R.params64(pol), x)
-            pn[2].weight.mul_(target / np.abs(z2).max())
-        p = R.params64(pol)
-        mean = R.mlp64(p, "mlp_extractor.policy_net", "action_net", x) - p["action_net.bias"][0]
-        pol.action_net.weight.mul_((0.3 if kind == "small" else 1.5) / np.abs(mean).max())
-    return pol.float().to(DEV)
-
-
 _STATE = ("own_x", "own_y", "own_psi", "own_v", "goal_x", "goal_y", "trf_x", "trf_y", "trf_psi", "trf_v", "steps",
           "total_reward", "episode")
 
@@ -217,13 +177,13 @@ def test_group_rollout_policy_equals_thread_per_env_bit_for_bit(gpu, cfg_name):
     env.reset()
     twin.reset()
     rows = np.arange(5, E, 13)
-    state, obs0 = _parallel_flight(env, rows)
+    state, obs0 = LS.parallel_flight(env, rows)
     twin.set_state(*state, np.zeros(E, np.int32), observe=True)
     assert np.isnan(obs0[rows]).any(1).all()
     for kind in ("plain", "saturating"):
         for v in (env, twin):
             v.set_state(*state, np.zeros(E, np.int32), observe=True)
-        pol = _scaled_actor(g, 5 + 3 * N, kind, obs0)
+        pol = LS.scaled_actor(g, 5 + 3 * N, kind, obs0)
         a = env.rollout_policy(pol, T, keep_terminal_obs=True, group=True)
         b = twin.rollout_policy(pol, T, keep_terminal_obs=True)
         torch.cuda.synchronize()
@@ -246,10 +206,10 @@ def test_group_collect_equals_thread_per_env_bit_for_bit(gpu, cfg_name):
     env.reset()
     twin.reset()
     rows = np.arange(3, E, 11)
-    state, obs0 = _parallel_flight(env, rows)
+    state, obs0 = LS.parallel_flight(env, rows)
     twin.set_state(*state, np.zeros(E, np.int32), observe=True)
     assert np.isnan(obs0[rows]).any(1).all()
-    pol = _actor_critic(g, 5 + 3 * N)
+    pol = LS.actor_critic(g, 5 + 3 * N)
     a = env.collect(pol, T, noise_seed=seed, noise_step=nstep, group=True)
     b = twin.collect(pol, T, noise_seed=seed, noise_step=nstep)
     torch.cuda.synchronize()
@@ -269,7 +229,7 @@ def test_group_policy_set_equals_thread_per_env_bit_for_bit(gpu, E, cfg_name):
     N = 8
     cfg = _config(g, N, cfg_name)
     own, trf, goal = H.parity_reset_states(cfg, 13, 0, E)
-    pols = [_actor_critic(g, 5 + 3 * N, seed=s) for s in (1, 2, 3)]
+    pols = [LS.actor_critic(g, 5 + 3 * N, seed=s) for s in (1, 2, 3)]
     a = g.evaluate_policies_fused(pols, own, trf, goal, dtype=torch.float32, config=cfg, group=True)
     b = g.evaluate_policies_fused(pols, own, trf, goal, dtype=torch.float32, config=cfg)
     for k in ("outcome", "steps", "unfinished"):
@@ -295,9 +255,9 @@ def test_group_policy_actions_vs_float64(gpu, N, E):
     for kind in ("plain", "saturating", "small"):
         env, = _envs(g, N, E, 1, _config(g, N, max_steps=12), seed=21)
         env.reset()
-        state, obs0 = _parallel_flight(env, rows)
+        state, obs0 = LS.parallel_flight(env, rows)
         assert np.isnan(obs0[rows]).any(1).all()
-        pol = _scaled_actor(g, D, kind, obs0)
+        pol = LS.scaled_actor(g, D, kind, obs0)
         out = env.rollout_policy(pol, T, group=True)
         torch.cuda.synchronize()
         obs = np.concatenate([obs0[None], out["obs"][:T - 1].double().cpu().numpy()])
@@ -330,12 +290,12 @@ def test_group_collector_vs_float64_and_twin_replay(gpu, N, E):
     g = gpu
     D, T = 5 + 3 * N, 24
     seed, nstep, off = 0x243F6A8885A308D3, 2 ** 32 - 5, 2 ** 32 - 259
-    pol = _actor_critic(g, D)
+    pol = LS.actor_critic(g, D)
     env, twin = _envs(g, N, E, 2, _config(g, N, max_steps=12), seed=21, env_offset=off)
     env.reset()
     twin.reset()
     rows = np.arange(3, E, 11)
-    state, obs0 = _parallel_flight(env, rows)
+    state, obs0 = LS.parallel_flight(env, rows)
     twin.set_state(*state, np.zeros(E, np.int32), observe=True)
     assert np.isnan(obs0[rows]).any(1).all() and not np.isnan(np.delete(obs0, rows, 0)).any()
     out = env.collect(pol, T, noise_seed=seed, noise_step=nstep, group=True)
@@ -377,7 +337,7 @@ def test_group_policy_rollout_replays_on_a_twin(gpu, N, E):
     env, twin = _envs(g, N, E, 2, cfg, seed=3, env_offset=37)
     env.reset()
     twin.reset()
-    pol = _actor_critic(g, 5 + 3 * N)
+    pol = LS.actor_critic(g, 5 + 3 * N)
     out = env.rollout_policy(pol, T, keep_terminal_obs=True, group=True)
     dones = 0
     for t in range(T):
@@ -405,7 +365,7 @@ def test_group_policy_set_rows_equal_single_policy_evaluations(gpu, E, cfg_name)
     N = 64
     cfg = _config(g, N, cfg_name)
     own, trf, goal = H.parity_reset_states(cfg, 13, 0, E)
-    pols = [_actor_critic(g, 5 + 3 * N, seed=s) for s in (1, 2, 3)]
+    pols = [LS.actor_critic(g, 5 + 3 * N, seed=s) for s in (1, 2, 3)]
     got = g.evaluate_policies_fused(pols, own, trf, goal, dtype=torch.float32, config=cfg, group=True)
     assert got["outcome"].shape == (3, E) and got["unfinished"].shape == (3,)
     for k, pol in enumerate(pols):

@@ -386,32 +386,22 @@ def test_ppo_workspace_is_the_13_parameter_tensors(g):
         assert L.acas2d_ppo_workspace_floats(D) == total == fu.grad.numel() == R.segments(pol)[-1][2], D
 
 
-def _ppo_struct(g, **over):
-    """An Acas2dPpoUpdate whose pointers are host addresses: every case built from it must be rejected before any
-    launch."""
-    buf = (C.c_char * 64)()
-    f = {n: C.addressof(buf) for n, t in g.native.CPpoUpdate._fields_ if t is C.c_void_p}
-    f.update(n_rows=64, obs_dim=8, clip_range=0.2, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, learning_rate=3e-4,
-             beta1=0.9, beta2=0.999, adam_eps=1e-5)
-    f.update(over)
-    return g.native.CPpoUpdate(**f), buf
-
-
 def test_ppo_update_validation_needs_no_gpu(g):
+    import learner_support as LS
     L = g.native.lib()
     assert L.acas2d_ppo_update_f32(None, None) == -22 and b"NULL argument" in L.acas2d_last_error()
     pointers = [n for n, t in g.native.CPpoUpdate._fields_ if t is C.c_void_p]
     assert len(pointers) == 24
     for name in pointers:
-        u, _keep = _ppo_struct(g, **{name: None})
+        u, _keep = LS.host_update(g, **{name: None})
         assert L.acas2d_ppo_update_f32(C.byref(u), None) == -22, name
         assert b"every pointer is required" in L.acas2d_last_error(), name
     for n_rows in (1, 0, -5):
-        u, _keep = _ppo_struct(g, n_rows=n_rows)
+        u, _keep = LS.host_update(g, n_rows=n_rows)
         assert L.acas2d_ppo_update_f32(C.byref(u), None) == -22
         assert (b"n_rows = %d" % n_rows) in L.acas2d_last_error()
     for D in (0, 5, 7, 9, 20, 30, -8, 53):
-        u, _keep = _ppo_struct(g, obs_dim=D)
+        u, _keep = LS.host_update(g, obs_dim=D)
         assert L.acas2d_ppo_update_f32(C.byref(u), None) == -22
         assert (b"obs_dim = %d" % D) in L.acas2d_last_error()
 

@@ -21,8 +21,6 @@ import ctypes as C
 import dataclasses
 import os
 import re
-import shutil
-import subprocess
 import types
 
 import numpy as np
@@ -31,16 +29,12 @@ import pytest
 import helpers as H
 import kl_guard_ref as KR
 import learner_ref as R
+import learner_support as LS
 
 torch = pytest.importorskip("torch")
 DEV = "cuda:0"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gym-acas2d_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 NARROW, WIDE = (8, 11, 14, 17, 29), (53, 101, 197)
 WIDTHS = NARROW + WIDE                 # every compiled guarded instantiation: what n_traffic 1, 2, 3, 4, 8, 16, 32, 64 take
-# bounds of tests/test_learner_kernels.py, unchanged
-TAU, TAU0, TAU_M, TAU_V = 2e-5, 1e-6, 2e-5, 5e-5
 GUARDED = "acas2d_ppo_update_guarded_set_f32"
 
 
@@ -63,7 +57,7 @@ def test_guarded_entry_is_exported_and_declared(g):
     for name in (GUARDED, "acas2d_ppo_guard_size"):
         assert name in g.native.EXPORTS and getattr(L, name)
     assert C.sizeof(g.native.CPpoGuard) == L.acas2d_ppo_guard_size() == 3 * 8
-    header = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "acas2d.h")).read())
+    header = re.sub(r"\s+", " ", open(os.path.join(H.ROOT, "include", "acas2d.h")).read())
     assert ("int %s(const Acas2dPpoUpdateSet *u, const Acas2dPpoGuard *g, void *stream);" % GUARDED) in header
     assert L.acas2d_abi_version() == g.native.ABI_VERSION == 7
     print("CPpoGuard: %d bytes" % C.sizeof(g.native.CPpoGuard))
@@ -79,11 +73,7 @@ def test_guarded_update_validation_needs_no_gpu(g):
     ints = dict(n_members=3, n_rows=64, obs_dim=8, apply=1)
 
     def call(guard=(a, a, a), **kw):
-        f = {n: a for n in names}
-        f.update(ints)
-        f.update(kw)
-        gd = C.byref(g.native.CPpoGuard(*guard)) if guard is not None else None
-        return L.acas2d_ppo_update_guarded_set_f32(C.byref(g.native.CPpoUpdateSet(**f)), gd, None)
+        return L.acas2d_ppo_update_guarded_set_f32(*LS.host_update_set_args(g, a, guard=guard, **{**ints, **kw}))
 
     def rejects(msg, **kw):
         assert call(**kw) == -22, kw
@@ -197,69 +187,41 @@ def test_eager_update_breaks_before_the_optimizer_step(g):
     assert st["early_stop"] and st["n_applied"] < 12 and steps == ({st["n_applied"]} if st["n_applied"] else set())
 
 
-def _device_asm(tmp_path, unit):
-    asm = tmp_path / (unit + ".s")
-    subprocess.run([HIPCC if os.path.exists(HIPCC) else "hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-S", "--cuda-device-only", "-o", str(asm),
-                    os.path.join(CSRC, unit)], check=True, capture_output=True)
-    return asm.read_text()
-
-
-_field = lambda e, k: int(re.search(r"\.%s:\s+(\d+)" % k, e).group(1))  # noqa: E731
-
-
-@pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="needs hipcc")
+@H.needs_hipcc
 def test_guarded_update_kernels_stay_in_registers_and_lds(g, tmp_path):
     """csrc/acas2d_ppo_guard.hip: five narrow gradient kernels, three wide ones and the apply kernel.  None spills either
     register file or uses scratch; the narrow ones use at most 256 VGPRs (test_ppo_update_set_kernels_stay_in_registers'
     rule); the wide ones are held to what tests/test_wide_update.py and tests/test_population_wide.py hold the unguarded
     kernel of the same width to: at most 256 VGPRs, 256 threads, acas2d_ppo_wide_lds_bytes of dynamic LDS plus the static
     LDS within gfx950's 160 KB."""
-    meta = _device_asm(tmp_path, "acas2d_ppo_guard.hip").split("amdhsa.kernels:")[1]
-    kernels = [e for e in re.split(r"\n  - \.agpr_count:", meta) if ".name:" in e]
+    _, kernels = H.kernel_metadata(tmp_path, "acas2d_ppo_guard.hip")
     assert len(kernels) == 9
     L = g.native.lib()
     seen = {"narrow": [], "wide": [], "apply": 0}
-    for e in kernels:
-        name = re.search(r"\.name:\s+(\S+)", e).group(1)
-        print(name[:70], "vgpr", _field(e, "vgpr_count"), "sgpr", _field(e, "sgpr_count"), "static LDS",
-              _field(e, "group_segment_fixed_size"))
-        assert _field(e, "vgpr_spill_count") == 0 and _field(e, "sgpr_spill_count") == 0, name
-        assert _field(e, "private_segment_fixed_size") == 0 and _field(e, "vgpr_count") <= 256, name
+    for k in kernels:
+        name = k.name
+        print(name[:70], "vgpr", k.field("vgpr_count"), "sgpr", k.field("sgpr_count"), "static LDS",
+              k.field("group_segment_fixed_size"))
+        assert k.field("vgpr_spill_count") == 0 and k.field("sgpr_spill_count") == 0, name
+        assert k.field("private_segment_fixed_size") == 0 and k.field("vgpr_count") <= 256, name
         if "ppo_apply_guarded_set_kernel" in name:
             seen["apply"] += 1
-            assert _field(e, "max_flat_workgroup_size") == 1024, name
+            assert k.field("max_flat_workgroup_size") == 1024, name
             continue
         D = int(re.search(r"kernelILi(\d+)E", name).group(1))
         if "ppo_grad_wide_guarded_set_kernel" in name:
             seen["wide"].append(D)
-            assert _field(e, "max_flat_workgroup_size") == 256, name
+            assert k.field("max_flat_workgroup_size") == 256, name
             lds = L.acas2d_ppo_wide_lds_bytes(D)
-            assert lds + _field(e, "group_segment_fixed_size") <= 160 * 1024, (D, lds)
+            assert lds + k.field("group_segment_fixed_size") <= 160 * 1024, (D, lds)
         else:
             assert "ppo_grad_guarded_set_kernel" in name
             seen["narrow"].append(D)
-            assert _field(e, "max_flat_workgroup_size") == 64, name
+            assert k.field("max_flat_workgroup_size") == 64, name
     assert sorted(seen["narrow"]) == list(NARROW) and sorted(seen["wide"]) == list(WIDE) and seen["apply"] == 1
 
 
 # ---- GPU: the kernels -------------------------------------------------------------------------------------------------
-def _cfgs(g, K, **over):
-    """K configs with different clip ranges, learning rates, ... (member 0 has the entropy term and an active norm clip)."""
-    hyper = dict(clip_range=(0.2, 0.1, 0.3), vf_coef=(0.5, 0.25, 1.0), ent_coef=(0.01, 0.0, 0.02),
-                 max_grad_norm=(0.5, 1e6, 0.5), learning_rate=(3e-4, 1e-3, 1e-4))
-    return [g.PPOConfig(**{**{f: v[k] for f, v in hyper.items()}, **over}) for k in range(K)]
-
-
-def _draw(bt, pset, cfgs, B, mode="mixed"):
-    """A fresh minibatch per member on disjoint rows, old log-probs from each member's CURRENT parameters."""
-    K = len(cfgs)
-    idx = torch.randperm(bt.n, device=DEV)[:K * B].reshape(K, B).contiguous()
-    for k in range(K):
-        bt.set_old_logp(bt.theta(pset, k), idx[k], mode, cfgs[k].clip_range)
-    return idx
-
-
 STAT_CASES = [(D, K, B) for D in WIDTHS for K in (1, 3) for B in (2, 63, 64, 65, 130)]
 
 
@@ -274,15 +236,16 @@ def test_guarded_statistics_vs_float64(gpu, D, K, B):
     Observed on an MI355X: approx_kl at most 0.081 of the bound (8.1e-7 absolute; D = 17, K = 3, B = 2), 0.055 and 0.020 at
     D = 17, K = 1 and D = 53, K = 3 (both B = 2), at most 0.006 in the other 77 cases."""
     g = gpu
-    bt = KR.SharedBatch(g, D, K, K * B + 317, seed=6000 + 7 * D + 31 * K + B, device=DEV)
-    cfgs = _cfgs(g, K)
+    bt = LS.RolloutBatch(g, D, K, K * B + 317, seed=6000 + 7 * D + 31 * K + B)
+    cfgs = LS.member_cfgs(g, K)
+    clips = [c.clip_range for c in cfgs]
     pset = bt.policy_set()
     fu = g.FusedUpdateSet(pset, cfgs, *bt.bufs, diagnostics=True)
     assert fu.guarded and float(fu.target_kl.abs().max()) == 0.0
     worst = 0.0
     for call, mode in enumerate(("mixed", "first"), 1):
-        idx = _draw(bt, pset, cfgs, B, mode)
-        theta = [bt.theta(pset, k) for k in range(K)]
+        idx = LS.draw(bt, pset, clips, B, mode)
+        theta = [LS.theta_of(pset, k) for k in range(K)]
         fu.begin_update()
         fu.step(idx)
         torch.cuda.synchronize()
@@ -312,31 +275,21 @@ def test_guarded_statistics_vs_float64(gpu, D, K, B):
     print("D=%d K=%d B=%d: worst approx_kl error %.3f of the 1e-5 bound" % (D, K, B, worst))
 
 
-def _worst_ratio(errs, ref_all, tau0=TAU0):
-    return max((e - tau0 * ref_all) / max(m, 1e-300) for e, m in errs.values())
-
-
-def _assert_per_tensor(what, got, ref, segs, tau, tau0=TAU0):
-    errs, ref_all = R.per_tensor_errors(got, ref, segs)
-    bad = {n: (e, m) for n, (e, m) in errs.items() if not e <= tau * m + tau0 * ref_all}
-    print("%s: observed tau %.2e (bound %.0e, tau0 %.0e)" % (what, _worst_ratio(errs, ref_all, tau0), tau, tau0))
-    assert not bad, (what, bad, ref_all)
-
-
 def _decision_run(g, D, B, seed):
     """Three guarded calls of K = 3 members on fresh minibatches.  None where member 1's limit does not clear its three
     minibatches by the margin the test wants (the caller re-draws the seed)."""
     K = 3
     b1, b2, eps = 0.9, 0.999, 1e-5
-    bt = KR.SharedBatch(g, D, K, K * B + 317, seed=seed, device=DEV)
-    cfgs = _cfgs(g, K)
+    bt = LS.RolloutBatch(g, D, K, K * B + 317, seed=seed)
+    cfgs = LS.member_cfgs(g, K)
+    clips = [c.clip_range for c in cfgs]
     pset = bt.policy_set()
     segs = R.segments(bt.pols[0])
     fu = g.FusedUpdateSet(pset, cfgs, *bt.bufs, diagnostics=True)
     frozen = None
     for call in (1, 2, 3):
-        idx = _draw(bt, pset, cfgs, B)
-        theta0 = [bt.theta(pset, k) for k in range(K)]
+        idx = LS.draw(bt, pset, clips, B)
+        theta0 = [LS.theta_of(pset, k) for k in range(K)]
         kl64 = [KR.approx_kl64(bt.log_ratio(theta0[k], idx[k])) for k in range(K)]
         if call == 1:
             target = [kl64[0] / 3.0, kl64[1] * 2.0, 0.0]
@@ -387,9 +340,9 @@ def _decision_run(g, D, B, seed):
             for key, got_, ref_, tol in (("norm", stats[k, 2], norm, 1e-5 * norm), ("pg", stats[k, 4], pg, 1e-5 * max(1.0, abs(pg))),
                                          ("vf", stats[k, 5], vf, 1e-5 * max(1.0, vf))):
                 assert abs(got_ - ref_) <= tol, (what, key, got_, ref_)
-            _assert_per_tensor("m " + what, m1[k], m_ref, segs, TAU_M)
-            _assert_per_tensor("v " + what, v1[k], v_ref, segs, TAU_V)
-            theta1 = bt.theta(pset, k)
+            LS.assert_per_tensor("m " + what, m1[k], m_ref, segs, LS.TAU_M)
+            LS.assert_per_tensor("v " + what, v1[k], v_ref, segs, LS.TAU_V)
+            theta1 = LS.theta_of(pset, k)
             ulp = np.spacing(np.abs(theta_ref).astype(np.float32)).astype(np.float64)
             excess = (np.abs(theta1 - theta_ref) - ulp) / c.learning_rate
             print("  %s: parameter excess %.2e lr (bound 1e-2)" % (what, float(excess.max())))
@@ -408,7 +361,7 @@ def test_guarded_decision_over_three_calls(gpu, D):
     Member 0: target_kl = kl64 / 3, stops on call 1 and stays as it was before it -- parameters, moments and step count bit
     for bit, its gradient block zero, diag[0][6] == 1, diag[0][7] == 0, diag[0][2] and the logged losses call 1's.
     Member 1: target_kl = 2 kl64 (never reached: asserted per minibatch in float64, else the seed is re-drawn); member 2:
-    no limit.  Both apply all three steps, each matching adam64(grad64(...)) at test_learner_kernels.py's bounds."""
+    no limit.  Both apply all three steps, each matching adam64(grad64(...)) at learner_support.py's bounds."""
     for seed in range(7000 + D, 7000 + D + 5000, 1000):
         if _decision_run(gpu, D, 65, seed):
             return
@@ -430,8 +383,9 @@ def test_guard_off_equals_the_unguarded_entries_bitwise(gpu, D, K, B):
     # (seeds from 8500: with the earlier 8000 the two minibatches of D = 101, K = 1, B = 2 hold four rows that the surrogate
     # clips on the side where its gradient is exactly 0 -- float64 autograd gives no actor gradient either, and the
     # `moved > 0` below, which looks at an actor matrix, cannot hold for any correct kernel; about 1 draw in 70 at B = 2)
-    bt = KR.SharedBatch(g, D, K, K * B + 317, seed=8500 + 7 * D + 31 * K + B, device=DEV)
-    cfgs = _cfgs(g, K)
+    bt = LS.RolloutBatch(g, D, K, K * B + 317, seed=8500 + 7 * D + 31 * K + B)
+    cfgs = LS.member_cfgs(g, K)
+    clips = [c.clip_range for c in cfgs]
     twins = {"plain": bt.policy_set(), "guarded": bt.policy_set()}
     fus = {"plain": g.FusedUpdateSet(twins["plain"], cfgs, *bt.bufs),
            "guarded": g.FusedUpdateSet(twins["guarded"], cfgs, *bt.bufs, diagnostics=True)}
@@ -451,7 +405,7 @@ def test_guard_off_equals_the_unguarded_entries_bitwise(gpu, D, K, B):
     if K == 1:
         solo["solo guarded"][1].begin_update()
     for call in (1, 2):
-        idx = _draw(bt, twins["plain"], cfgs, B)
+        idx = LS.draw(bt, twins["plain"], clips, B)
         for fu in fus.values():
             fu.step(idx)
         for _, fu in solo.values():
@@ -486,16 +440,17 @@ def test_begin_update_lets_a_stopped_member_run_again(gpu, D):
     member 0's limit then lets it apply too."""
     g = gpu
     K, B = 3, 65
-    bt = KR.SharedBatch(g, D, K, K * B + 317, seed=9000 + D, device=DEV)
-    cfgs = _cfgs(g, K)
+    bt = LS.RolloutBatch(g, D, K, K * B + 317, seed=9000 + D)
+    cfgs = LS.member_cfgs(g, K)
+    clips = [c.clip_range for c in cfgs]
     cfgs[0] = dataclasses.replace(cfgs[0], target_kl=1e-6)
     pset = bt.policy_set()
     fu = g.FusedUpdateSet(pset, cfgs, *bt.bufs)
     assert fu.guarded and fu.target_kl.cpu().tolist() == [np.float32(1e-6), 0.0, 0.0]
-    theta_0 = bt.theta(pset, 0)
+    theta_0 = LS.theta_of(pset, 0)
     for call in (1, 2, 3):
-        idx = _draw(bt, pset, cfgs, B)
-        kl64 = KR.approx_kl64(bt.log_ratio(bt.theta(pset, 0), idx[0]))
+        idx = LS.draw(bt, pset, clips, B)
+        kl64 = KR.approx_kl64(bt.log_ratio(LS.theta_of(pset, 0), idx[0]))
         fu.begin_update()
         torch.cuda.synchronize()
         assert fu.stopped.cpu().tolist() == [0, 0, 0] and float(fu.diag.abs().max()) == 0.0
@@ -509,44 +464,22 @@ def test_begin_update_lets_a_stopped_member_run_again(gpu, D):
         assert abs(float(diag[0, 2]) - kl64) <= 1e-5 * max(1.0, kl64) and kl64 > 1.5e-6        # this call's, not an earlier one's
         assert diag[:, 6].tolist() == [1.0, 2.0, 2.0] and diag[:, 7].tolist() == [0.0, 2.0, 2.0]
         assert fu.step_count.cpu().tolist() == [0, 2 * call, 2 * call]
-        assert np.array_equal(bt.theta(pset, 0), theta_0)
+        assert np.array_equal(LS.theta_of(pset, 0), theta_0)
     fu.target_kl[0] = 0.0
     fu.begin_update()
-    fu.step(_draw(bt, pset, cfgs, B))
+    fu.step(LS.draw(bt, pset, clips, B))
     torch.cuda.synchronize()
     assert fu.stopped.cpu().tolist() == [0, 0, 0] and fu.step_count.cpu().tolist() == [1, 7, 7]
-    assert not np.array_equal(bt.theta(pset, 0), theta_0)
+    assert not np.array_equal(LS.theta_of(pset, 0), theta_0)
 
 
 # ---- GPU: the trainers ------------------------------------------------------------------------------------------------
 T_STEPS, T_BATCH, T_EPOCHS, T_UPDATES = 4, 64, 3, 12       # 64 envs x 4 steps = 256 rows: 4 minibatches x 3 epochs
 
 
-def _count_guarded_calls(g, monkeypatch):
-    """Wrap the bound function: every call through it is counted."""
-    L = g.native.lib()
-    inner = getattr(L, GUARDED)
-    calls = []
-
-    def counted(*args):
-        calls.append(1)
-        return inner(*args)
-
-    monkeypatch.setattr(L, GUARDED, counted)
-    return calls
-
-
-def _solo_trainer(g, target_kl, seed=13, envs=64, offset=0, **kw):
-    venv = g.ACAS2DVecEnv(envs, 1, device=DEV, seed=13, env_offset=offset)
+def _solo_trainer(g, target_kl, seed=13, **kw):
     cfg = g.PPOConfig(seed=seed, n_steps=T_STEPS, batch_size=T_BATCH, n_epochs=T_EPOCHS, target_kl=target_kl)
-    return g.PPOTrainer(venv, cfg, collector="fused", updater="fused", gae="kernel", **kw)
-
-
-def _iterate(tr):
-    tr.collect()
-    st = tr.update()
-    torch.cuda.synchronize()
-    return st
+    return LS.solo_trainer(g, cfg, **kw)
 
 
 def _same_learner(a, b):
@@ -562,16 +495,16 @@ def test_trainer_without_target_kl_never_takes_the_guarded_entry(gpu, monkeypatc
     as a second such trainer.  target_kl = 1e9 (never reached; B = 64: one atomic add per gradient entry) equals it bit
     for bit, through the guarded entry, and reports all 12 minibatches applied."""
     g = gpu
-    calls = _count_guarded_calls(g, monkeypatch)
+    calls = LS.count_calls(g, monkeypatch, GUARDED)
     a = _solo_trainer(g, None)                             # (one after the other: the minibatch permutations come from
-    sa = _iterate(a)                                       # torch's global generator, seeded at construction)
+    sa = LS.iterate(a)                                       # torch's global generator, seeded at construction)
     b = _solo_trainer(g, None)
-    sb = _iterate(b)
+    sb = LS.iterate(b)
     assert calls == [] and not a._fused_update.guarded
     assert sorted(sa) == ["pg_loss", "std", "value_loss"] and sa == sb
     _same_learner(a, b)
     c = _solo_trainer(g, 1e9)
-    sc = _iterate(c)
+    sc = LS.iterate(c)
     print("target_kl=None: %s\ntarget_kl=1e9:  %s (%d guarded calls)" % (sa, sc, len(calls)))
     assert len(calls) == T_UPDATES and c._fused_update.guarded
     _same_learner(a, c)
@@ -580,7 +513,7 @@ def test_trainer_without_target_kl_never_takes_the_guarded_entry(gpu, monkeypatc
     assert sc["approx_kl"] > 0.0 and 0.0 <= sc["clip_fraction"] <= 1.0
     assert int(c._fused_update.step_count.item()) == T_UPDATES
     d = _solo_trainer(g, None, diagnostics=True)           # diagnostics alone: the same again
-    sd = _iterate(d)
+    sd = LS.iterate(d)
     _same_learner(a, d)
     assert sd["n_applied"] == T_UPDATES and sd["approx_kl"] == sc["approx_kl"]
 
@@ -590,7 +523,7 @@ def test_trainer_stops_early_on_a_tiny_target_kl(gpu):
     """target_kl = 1e-12: some minibatch exceeds it.  Which one is the device's business; the invariants are read from it."""
     g = gpu
     tr = _solo_trainer(g, 1e-12)
-    st = _iterate(tr)
+    st = LS.iterate(tr)
     fu = tr._fused_update
     d = fu.diagnostics()
     print("target_kl=1e-12:", st, d, "adam_step", int(fu.step_count.item()))
@@ -600,7 +533,7 @@ def test_trainer_stops_early_on_a_tiny_target_kl(gpu):
     assert d["last_approx_kl"] > 1.5e-12 and float(fu.diag[0, 2]) == d["last_approx_kl"]
     assert float(fu.grad.abs().max()) == 0.0
     assert np.isfinite([st["approx_kl"], st["clip_fraction"], st["explained_variance"], st["pg_loss"], st["value_loss"]]).all()
-    st2 = _iterate(tr)                                     # the next update starts afresh (begin_update)
+    st2 = LS.iterate(tr)                                     # the next update starts afresh (begin_update)
     assert int(fu.step_count.item()) == st["n_applied"] + st2["n_applied"]
 
 
@@ -619,7 +552,7 @@ def test_population_stops_one_member_and_leaves_the_other_alone(gpu, monkeypatch
                 for k in range(K)]
         return g.PopulationTrainer(venv, cfgs, gae="kernel", **kw)
 
-    calls = _count_guarded_calls(g, monkeypatch)
+    calls = LS.count_calls(g, monkeypatch, GUARDED)
     plain = population((None, None))
     plain.collect()
     s_plain = plain.update()

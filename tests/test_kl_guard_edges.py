@@ -1,7 +1,7 @@
 """acas2d_ppo_update_guarded_set_f32 (csrc/acas2d_ppo_guard.hip: target_kl early stop, approx_kl and clip_fraction on the
 device) on the hand-placed edge minibatches of tests/edge_minibatches.py and at the edges of its own decision, against the
 float64 restatements of tests/kl_guard_ref.py and tests/learner_ref.py.  Bounds and criteria are the neighbours', unchanged:
-approx_kl within 1e-5 max(1, kl64), the clipped count exact, the applied step at test_learner_edges._check_applied's bounds
+approx_kl within 1e-5 max(1, kl64), the clipped count exact, the applied step at learner_support.check_applied's bounds
 (TAU_M 2e-5, TAU_V 5e-5, parameter excess 1e-2 lr), losses and norm 1e-5.
 
   CPU  admission, per batch and member: ppo.approx_kl_and_clip_fraction on a float32 CPU copy of the member clears a
@@ -43,14 +43,10 @@ import edge_minibatches as E
 import helpers as H
 import kl_guard_ref as KR
 import learner_ref as R
+import learner_support as LS
 
 torch = pytest.importorskip("torch")
-import test_edge_minibatches as TE  # noqa: E402  (the CPU session's batches; nothing in it runs at import)
-import test_kl_guard as TK  # noqa: E402  (_cfgs, _draw)
-import test_learner_edges as LE  # noqa: E402  (the GPU session's batches, _check_applied, _check_losses, _carve, _intact)
-
-DEV = "cuda:0"
-LR = LE.LR
+LR = LS.LR
 WIDTHS, ROWS = (8, 29, 53, 197), (2, 65, 130)
 SET = [(D, B, case) for D in WIDTHS for B in ROWS for case in E.CASES]
 LARGE = [(D, 8193, case) for D in (8, 197) for case in ("mixed", "grid_adv")]
@@ -70,12 +66,6 @@ def g():
 def gpu(g):
     assert torch.cuda.is_available(), "GPU tests need a GPU"
     return g
-
-
-@pytest.fixture(scope="module")
-def K(g):
-    import test_learner_kernels as K
-    return K
 
 
 def _kl_bound(kl64):
@@ -113,7 +103,7 @@ def test_guarded_statistics_of_set_case_are_admitted(g, D, B, case):
     """Per member: float32 approx_kl within a quarter of 1e-5 max(1, kl64); float32 clip_fraction == float32(count64) /
     float32(B); edge distance >= 10 x the largest ratio error.  underflow: kl64 is about 110 x the share of underflowed
     rows, so the large-term path is the one checked."""
-    bt = TE.batch("set", D, B, case)
+    bt = LS.edge_batch("set", D, B, case)
     for k in range(bt.K):
         lr64 = _log_ratio64(bt, k)
         kl64, (count, _) = KR.approx_kl64(lr64), KR.clip_fraction64(lr64, bt.clips[k])
@@ -144,7 +134,7 @@ def test_guarded_statistics_at_8193_rows_are_admitted(g, D, B, case):
     """129 partial sums (one per 64 rows) added in float32 forwards, backwards and in both sorted orders, then / B: each
     within a quarter of the approx_kl bound.  The count: every partial is an integer <= 64, every running sum an integer
     <= 8 193 < 2^24, so float atomics in any order give float32(count); float32 and float64 count the same rows."""
-    bt = TE.batch("solo", D, B, case)
+    bt = LS.edge_batch("solo", D, B, case)
     lr64 = _log_ratio64(bt, 0)
     kl64, (count, _) = KR.approx_kl64(lr64), KR.clip_fraction64(lr64, 0.2)
     _, cf32, lr32, r32 = _forward32(g, bt, 0)
@@ -188,22 +178,22 @@ def _check_statistics(g, what, bt, k, diag_k, B, lr64, clip, calls=1.0):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("D,B,case", SET, ids=[_ID(c) for c in SET])
-def test_guarded_set_update_on_edge_minibatches_vs_float64(gpu, K, D, B, case):
+def test_guarded_set_update_on_edge_minibatches_vs_float64(gpu, D, B, case):
     """One guarded call (every limit 0) of K = 3 members with their own policy, clip_range 0.1 / 0.2 / 0.3 and vf_coef 0.5 /
     0.25 / 1.0: diag[k] against float64, then the step it applied against grad64 + adam64 from the kernel's own pre-step
     state (test_set_update_on_edge_minibatches_vs_float64's second half, through the Guard = true kernels).  const_adv:
     every actor bit kept although approx_kl and, from B = 65, the clipped count are not zero."""
     g = gpu
-    bt = LE._batch("set", D, B, case)
-    idx = LE._dev(bt.idx)
+    bt = LS.edge_batch("set", D, B, case)
+    idx = LS.dev(bt.idx)
     segs = R.segments(bt.pols[0])
-    na = LE._n_actor(segs)
+    na = LS.n_actor(segs)
     theta0 = [bt.theta(k) for k in range(bt.K)]
     ent = 0.0 if case == "const_adv" else 0.01
     cf = [g.PPOConfig(ent_coef=ent, clip_range=bt.clips[k], vf_coef=E.VF_COEFS[k], max_grad_norm=0.5, learning_rate=LR)
           for k in range(bt.K)]
-    pset = g.ActorCriticSet.from_members([LE._policy(g, bt, k) for k in range(bt.K)])
-    fu = g.FusedUpdateSet(pset, cf, *LE._bufs(bt), diagnostics=True)
+    pset = g.ActorCriticSet.from_members([LS.device_policy(g, bt, k) for k in range(bt.K)])
+    fu = g.FusedUpdateSet(pset, cf, *LS.device_bufs(bt), diagnostics=True)
     assert fu.guarded and float(fu.target_kl.abs().max()) == 0.0
     fu.begin_update()
     fu.step(idx)
@@ -218,11 +208,11 @@ def test_guarded_set_update_on_edge_minibatches_vs_float64(gpu, K, D, B, case):
         grad, pg, vf, _ = R.grad64(bt.ac_cls, cf[k], D, theta0[k], *bt.rows(k))
         theta_ref, m_ref, v_ref, norm = R.adam64(theta0[k], grad, np.zeros_like(grad), np.zeros_like(grad), 0, 0.5, LR, 0.9, 0.999, 1e-5)
         st = fu.stats[k].double().cpu().numpy()
-        theta1, m1, v1 = LE._theta_set(pset, k), fu.m[k].double().cpu().numpy(), fu.v[k].double().cpu().numpy()
+        theta1, m1, v1 = LS.theta_of(pset, k), fu.m[k].double().cpu().numpy(), fu.v[k].double().cpu().numpy()
         assert np.isfinite(theta1).all() and np.isfinite(m1).all() and np.isfinite(v1).all()
         assert abs(st[2] - norm) <= 1e-5 * norm, (what, st[2], norm)
-        LE._check_losses(what + " applied", st[4], st[5], pg, vf)
-        LE._check_applied(K, what, segs, theta1, m1, v1, theta_ref, m_ref, v_ref, LR)
+        LS.check_losses(what + " applied", st[4], st[5], pg, vf)
+        LS.check_applied(what, segs, theta1, m1, v1, theta_ref, m_ref, v_ref, LR)
         if case == "underflow":
             assert kl64 > 5.0, what
         if case == "const_adv":
@@ -239,23 +229,23 @@ def test_guarded_statistics_at_8193_rows_vs_float64(gpu, D, B, case):
     FusedUpdate(diagnostics=True) and through a FusedUpdateSet of one member: approx_kl within 1e-5 max(1, kl64), the
     clipped fraction == float32(count64) / float32(B) (every partial sum an integer below 2^24)."""
     g = gpu
-    bt = LE._batch("solo", D, B, case)
+    bt = LS.edge_batch("solo", D, B, case)
     cfg = g.PPOConfig(ent_coef=0.01, max_grad_norm=0.5, learning_rate=LR, clip_range=0.2)
     lr64 = _log_ratio64(bt, 0)
-    bufs = LE._bufs(bt)
-    pol = LE._policy(g, bt)
+    bufs = LS.device_bufs(bt)
+    pol = LS.device_policy(g, bt)
     solo = g.FusedUpdate(pol, cfg, *bufs, diagnostics=True)
-    pset = g.ActorCriticSet.from_members([LE._policy(g, bt)])
+    pset = g.ActorCriticSet.from_members([LS.device_policy(g, bt)])
     one = g.FusedUpdateSet(pset, [cfg], *bufs, diagnostics=True)
     assert solo.guarded and one.guarded
-    for name, fu, idx in (("FusedUpdate", solo, LE._dev(bt.idx[0])), ("FusedUpdateSet K=1", one, LE._dev(bt.idx))):
+    for name, fu, idx in (("FusedUpdate", solo, LS.dev(bt.idx[0])), ("FusedUpdateSet K=1", one, LS.dev(bt.idx))):
         fu.begin_update()
         fu.step(idx)
         torch.cuda.synchronize()
         assert fu.stopped.cpu().tolist() == [0] and fu.step_count.cpu().tolist() == [1]
         kl64, count = _check_statistics(g, "%s %s D=%d B=%d" % (name, case, D, B), bt, 0, fu.diag.cpu().numpy()[0], B, lr64, 0.2)
         assert 0 < count < B and kl64 > 1e-2
-    assert not np.array_equal(R.flat_params(pol), bt.theta()) and not np.array_equal(LE._theta_set(pset, 0), bt.theta())
+    assert not np.array_equal(R.flat_params(pol), bt.theta()) and not np.array_equal(LS.theta_of(pset, 0), bt.theta())
 
 
 # ---- c. the decision at its float32 boundary -----------------------------------------------------------------------------
@@ -314,9 +304,9 @@ def test_stop_decision_at_its_float32_boundary(gpu, D, B):
     -0 (never stop), +inf (never stops) and the smallest subnormal (stops a member with kl32 > 0)."""
     g = gpu
     K = 3
-    bt = KR.SharedBatch(g, D, K, K * B + 317, seed=11000 + 7 * D + B, device=DEV)
-    cfgs = TK._cfgs(g, K)
-    idx = TK._draw(bt, bt.policy_set(), cfgs, B)
+    bt = LS.RolloutBatch(g, D, K, K * B + 317, seed=11000 + 7 * D + B)
+    cfgs = LS.member_cfgs(g, K)
+    idx = LS.draw(bt, bt.policy_set(), [c.clip_range for c in cfgs], B)
     start, probe = _guarded_run(g, bt, cfgs, idx, [0.0] * K)
     assert probe["stopped"].cpu().tolist() == [0] * K and probe["step_count"].cpu().tolist() == [1] * K
     kl32 = probe["diag"][:, 2].cpu().numpy()
@@ -397,21 +387,21 @@ def test_guarded_update_writes_nothing_outside_its_rows(gpu, D):
     intact."""
     g = gpu
     B = 65
-    bt = LE._batch("set", D, B, "dup_rows")
-    bufs, idx = LE._bufs(bt), LE._dev(bt.idx)
+    bt = LS.edge_batch("set", D, B, "dup_rows")
+    bufs, idx = LS.device_bufs(bt), LS.dev(bt.idx)
     reads = [t.clone() for t in bufs] + [idx.clone()]
     cfgs, limits, kl64 = _three_kinds(g, bt, bt.idx, B)
-    pset = g.ActorCriticSet.from_members([LE._policy(g, bt, k) for k in range(bt.K)])
+    pset = g.ActorCriticSet.from_members([LS.device_policy(g, bt, k) for k in range(bt.K)])
     stacks = {}
     for n in R.PARAM_NAMES:
-        pset.params[n], stacks[n] = LE._carve(tuple(pset.params[n].shape), init=pset.params[n])
+        pset.params[n], stacks[n] = LS.carve(tuple(pset.params[n].shape), init=pset.params[n])
     fu = g.FusedUpdateSet(pset, cfgs, *bufs, diagnostics=True)
     assert fu.guarded and all(p.data_ptr() == pset.params[n].data_ptr() for p, n in zip(fu._params, R.PARAM_NAMES))
-    carved = {name: LE._carve(tuple(getattr(fu, name).shape)) for name in ("grad", "m", "v", "stats", "diag")}
-    carved["hyper"] = LE._carve(tuple(fu.hyper.shape), init=fu.hyper)
-    carved["target_kl"] = LE._carve((bt.K,), init=torch.as_tensor(np.asarray(limits, np.float32)))
-    carved["step_count"] = LE._carve((bt.K,), dtype=torch.int32, sent=-77)
-    carved["stopped"] = LE._carve((bt.K,), dtype=torch.int32, sent=-77)
+    carved = {name: LS.carve(tuple(getattr(fu, name).shape)) for name in ("grad", "m", "v", "stats", "diag")}
+    carved["hyper"] = LS.carve(tuple(fu.hyper.shape), init=fu.hyper)
+    carved["target_kl"] = LS.carve((bt.K,), init=torch.as_tensor(np.asarray(limits, np.float32)))
+    carved["step_count"] = LS.carve((bt.K,), dtype=torch.int32, sent=-77)
+    carved["stopped"] = LS.carve((bt.K,), dtype=torch.int32, sent=-77)
     for name, (view, _) in carved.items():
         setattr(fu, name, view)
     fu._guard = g.native.CPpoGuard(fu.target_kl.data_ptr(), fu.stopped.data_ptr(), fu.diag.data_ptr())
@@ -424,9 +414,9 @@ def test_guarded_update_writes_nothing_outside_its_rows(gpu, D):
     torch.cuda.synchronize()
     now = _snapshot(fu, pset)
     for name, (view, big) in carved.items():
-        LE._intact(name, big, view.numel(), -77 if name in ("step_count", "stopped") else LE.SENT)
+        LS.intact(name, big, view.numel(), -77 if name in ("step_count", "stopped") else LS.SENT)
     for n in R.PARAM_NAMES:
-        LE._intact(n, stacks[n], pset.params[n].numel())
+        LS.intact(n, stacks[n], pset.params[n].numel())
     for t, q in zip(bufs + [idx], reads):
         assert torch.equal(t, q)
     assert H.bits_equal(fu.hyper, hyper) and H.bits_equal(fu.target_kl, target)
@@ -438,7 +428,7 @@ def test_guarded_update_writes_nothing_outside_its_rows(gpu, D):
     _stopped_before_anything_moved("member 1", now, start, 1)
     assert abs(float(now["diag"][1, 2]) - kl64) <= _kl_bound(kl64)
     _, pg, vf, _ = R.grad64(bt.ac_cls, cfgs[1], D, bt.theta(1), *bt.rows(1))
-    LE._check_losses("member 1, stopping minibatch", float(now["stats"][1, 4]), float(now["stats"][1, 5]), pg, vf)
+    LS.check_losses("member 1, stopping minibatch", float(now["stats"][1, 4]), float(now["stats"][1, 5]), pg, vf)
     d2 = now["diag"][2].cpu().numpy()
     assert d2[6] == 1.0 and d2[7] == 1.0 and d2[0] == 0.0 and d2[1] == 0.0 and float(now["grad"][2].abs().max()) == 0.0
     assert float(now["m"][2].abs().max()) > 0.0 and bool(torch.isfinite(now["m"][2]).all())
@@ -454,21 +444,21 @@ def test_member_beside_stopped_members_equals_its_own_run(gpu, D):
     parameters, moments, step count, stats and diag."""
     g = gpu
     B = 64
-    bt = LE._batch("set", D, 65, "underflow")               # (dup_rows' first 64 rows can be ONE row: no actor gradient)
+    bt = LS.edge_batch("set", D, 65, "underflow")               # (dup_rows' first 64 rows can be ONE row: no actor gradient)
     rows = np.ascontiguousarray(bt.idx[:, :B])
     cfgs, limits, kl64 = _three_kinds(g, bt, rows, B)
-    bufs = LE._bufs(bt)
-    pset = g.ActorCriticSet.from_members([LE._policy(g, bt, k) for k in range(bt.K)])
+    bufs = LS.device_bufs(bt)
+    pset = g.ActorCriticSet.from_members([LS.device_policy(g, bt, k) for k in range(bt.K)])
     fu = g.FusedUpdateSet(pset, cfgs, *bufs, diagnostics=True)
     fu.begin_update()
     fu.target_kl.copy_(torch.as_tensor(np.asarray(limits, np.float32)))
     fu.stopped[0] = 1
     start = _snapshot(fu, pset)
-    fu.step(LE._dev(rows))
-    twin_set = g.ActorCriticSet.from_members([LE._policy(g, bt, 2)])
+    fu.step(LS.dev(rows))
+    twin_set = g.ActorCriticSet.from_members([LS.device_policy(g, bt, 2)])
     twin = g.FusedUpdateSet(twin_set, [cfgs[2]], *bufs, diagnostics=True)
     twin.begin_update()
-    twin.step(LE._dev(rows[2:3]))
+    twin.step(LS.dev(rows[2:3]))
     torch.cuda.synchronize()
     now, alone = _snapshot(fu, pset), _snapshot(twin, twin_set)
     assert now["stopped"].cpu().tolist() == [1, 1, 0] and alone["stopped"].cpu().tolist() == [0]
@@ -490,9 +480,9 @@ def test_member_with_a_nan_old_logp_does_not_stop_and_stays_in_its_rows(gpu, D):
     a run without the NaN bit for bit: parameters, moments, step counts, stats and diag rows."""
     g = gpu
     K, B = 3, 64
-    bt = KR.SharedBatch(g, D, K, K * B + 317, seed=12000 + D, device=DEV)
-    cfgs = TK._cfgs(g, K)
-    idx = TK._draw(bt, bt.policy_set(), cfgs, B)
+    bt = LS.RolloutBatch(g, D, K, K * B + 317, seed=12000 + D)
+    cfgs = LS.member_cfgs(g, K)
+    idx = LS.draw(bt, bt.policy_set(), [c.clip_range for c in cfgs], B)
     _, clean = _guarded_run(g, bt, cfgs, idx, [0.0] * K)
     assert clean["stopped"].cpu().tolist() == [0] * K and bool(torch.isfinite(clean["diag"]).all())
     bt.old_logp[idx[1, 37]] = float("nan")

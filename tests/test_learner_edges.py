@@ -11,7 +11,7 @@ of every bound used here), through FusedUpdate and FusedUpdateSet:
   d  set members that share rows: identical members stay bit-equal; overlapping minibatches each meet float64
   e  sentinels around every buffer the narrow and the set update write
   f  a rollout buffer of more than 2^31 floats (D = 29, D = 197)
-Criteria and bounds are test_learner_kernels.py's (TAU, TAU0, TAU_M, TAU_V, parameter excess 1e-2 lr, losses 1e-5),
+Criteria and bounds are learner_support.py's (TAU, TAU0, TAU_M, TAU_V, parameter excess 1e-2 lr, losses 1e-5),
 unchanged; every test prints what it observed.
 
 Observed on an MI355X (one run of this file: 161 passed in 8.7 s, 209 in 13.7 s with the wide set cases; the slowest test 0.39 s -- the first, which loads
@@ -59,10 +59,11 @@ import pytest
 
 import edge_minibatches as E
 import learner_ref as R
+import learner_support as LS
 
 torch = pytest.importorskip("torch")
 DEV = "cuda:0"
-LR = 3e-4
+LR = LS.LR
 
 
 @pytest.fixture(scope="module")
@@ -73,58 +74,6 @@ def g():
     return g
 
 
-@pytest.fixture(scope="module")
-def K(g):
-    """tests/test_learner_kernels.py: its bounds and per-tensor criterion are the recipe here."""
-    import test_learner_kernels as K
-    return K
-
-
-_batches = {}
-
-
-def _batch(kind, D, B, case):
-    """The batch admitted by tests/test_edge_minibatches.py, built once per session and never written to."""
-    key = (kind, D, B, case)
-    if key not in _batches:
-        _batches[key] = E.make(D, B, case, E.seed_of(D, B, case), **(E.SET_LAYOUT if kind == "set" else {}))
-    return _batches[key]
-
-
-def _dev(a):
-    return torch.as_tensor(a, device=DEV).contiguous()
-
-
-def _bufs(bt):
-    return [_dev(a) for a in (bt.obs, bt.act, bt.old_logp, bt.adv, bt.ret)]
-
-
-def _policy(g, bt, k=0):
-    """A device copy of member k's policy (the batch's own stays as admitted)."""
-    pol = g.ActorCritic(bt.D)
-    pol.load_state_dict(bt.pols[k].state_dict())
-    return pol.to(DEV)
-
-
-def _n_actor(segs):
-    return segs[5][2]                 # the 6 actor tensors come first in the flat layout
-
-
-def _check_losses(what, st0, st1, pg, vf):
-    print("  %s: pg %.6e vs %.6e, vf %.6e vs %.6e" % (what, st0, pg, st1, vf))
-    assert abs(st0 - pg) <= 1e-5 * max(1.0, abs(pg)) and abs(st1 - vf) <= 1e-5 * max(1.0, vf), (what, st0, pg, st1, vf)
-
-
-def _check_applied(K, what, segs, theta1, m1, v1, theta_ref, m_ref, v_ref, lr, tau_v=None):
-    """The bounds of test_fused_update_applied_steps_vs_float64 on one member's state after a step."""
-    K._assert_per_tensor("m " + what, m1, m_ref, segs, K.TAU_M)
-    K._assert_per_tensor("v " + what, v1, v_ref, segs, K.TAU_V if tau_v is None else tau_v)
-    ulp = np.spacing(np.abs(theta_ref).astype(np.float32)).astype(np.float64)
-    excess = float(((np.abs(theta1 - theta_ref) - ulp) / lr).max())
-    print("  %s: parameter excess %.2e lr (bound 1e-2)" % (what, excess))
-    assert excess <= 1e-2, (what, excess)
-
-
 # ---- a. every case, raw gradient and one applied step -------------------------------------------------------------------
 SOLO_CASES = [(D, B, case) for D in (8, 29, 53, 197) for B in (2, 65, 130) for case in E.CASES]
 SET_CASES = [(D, B, case) for D in (8, 29, 53, 197) for B in (2, 65, 130) for case in E.CASES]
@@ -133,17 +82,17 @@ _ID = lambda c: "D%d-B%d-%s" % c  # noqa: E731
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("D,B,case", SOLO_CASES, ids=[_ID(c) for c in SOLO_CASES])
-def test_solo_update_on_edge_minibatches_vs_float64(g, K, D, B, case):
+def test_solo_update_on_edge_minibatches_vs_float64(g, D, B, case):
     """Narrow (D = 8, 29) and wide (D = 53, 197).  Raw gradient (max_grad_norm < 0, ent_coef 0.01): each of the 13 tensors
     within TAU max |ref tensor| + TAU0 max |ref|, stats[0..1] to 1e-5.  Then one applied step (max_grad_norm 0.5, lr 3e-4)
     against grad64 + adam64 from the kernel's own state.  const_adv: the 6 actor tensors of `grad` and the log_std entry
     are exactly 0, everything is finite, and with ent_coef = 0 the applied step keeps every actor bit while the critic
     moves."""
-    bt = _batch("solo", D, B, case)
-    bufs, idx = _bufs(bt), _dev(bt.idx[0])
-    pol = _policy(g, bt)
+    bt = LS.edge_batch("solo", D, B, case)
+    bufs, idx = LS.device_bufs(bt), LS.dev(bt.idx[0])
+    pol = LS.device_policy(g, bt)
     segs = R.segments(pol)
-    na = _n_actor(segs)
+    na = LS.n_actor(segs)
     theta0 = bt.theta()
     what = "%s %s D=%d B=%d" % ("narrow" if D < 53 else "wide", case, D, B)
 
@@ -158,9 +107,9 @@ def test_solo_update_on_edge_minibatches_vs_float64(g, K, D, B, case):
     ref, pg, vf, _ = R.grad64(bt.ac_cls, cfg, D, theta0, *bt.rows())
     assert np.isfinite(raw).all() and np.array_equal(R.flat_params(pol), theta0)
     assert np.array_equal(fu.step_count.cpu().numpy(), [0])
-    K._assert_per_tensor("raw gradient " + what, got, ref, segs, K.TAU)
+    LS.assert_per_tensor("raw gradient " + what, got, ref, segs, LS.TAU)
     st = fu.stats.double().cpu().numpy()
-    _check_losses(what, st[0], st[1], pg, vf)
+    LS.check_losses(what, st[0], st[1], pg, vf)
     if case == "const_adv":
         assert not raw[:na].any() and raw[-1] == 0.0 and st[0] == 0.0, (np.abs(raw[:na]).max(), raw[-1], st[0])
         assert np.abs(raw[na:-1]).max() > 0.0
@@ -177,8 +126,8 @@ def test_solo_update_on_edge_minibatches_vs_float64(g, K, D, B, case):
     assert int(fu.step_count.item()) == 1 and float(fu.grad.abs().max()) == 0.0 and st[0] == 0.0 and st[1] == 0.0
     assert np.isfinite(theta1).all() and np.isfinite(m1).all() and np.isfinite(v1).all() and np.isfinite(st).all()
     assert abs(st[2] - norm) <= 1e-5 * norm, (what, st[2], norm)
-    _check_losses(what + " applied", st[4], st[5], pg, vf)
-    _check_applied(K, what, segs, theta1, m1, v1, theta_ref, m_ref, v_ref, LR)
+    LS.check_losses(what + " applied", st[4], st[5], pg, vf)
+    LS.check_applied(what, segs, theta1, m1, v1, theta_ref, m_ref, v_ref, LR)
     if case == "const_adv":
         assert np.array_equal(theta1[:na], theta0[:na]) and theta1[-1] == theta0[-1]           # every actor bit kept
         assert not m1[:na].any() and not v1[:na].any() and m1[-1] == 0.0 and v1[-1] == 0.0
@@ -186,24 +135,20 @@ def test_solo_update_on_edge_minibatches_vs_float64(g, K, D, B, case):
 
 
 def _set_update(g, bt, cfgs, pols=None):
-    pset = g.ActorCriticSet.from_members([_policy(g, bt, k) for k in range(bt.K)] if pols is None else pols)
-    return pset, g.FusedUpdateSet(pset, cfgs, *_bufs(bt))
-
-
-def _theta_set(pset, k):
-    return torch.cat([pset.params[n][k].reshape(-1) for n in R.PARAM_NAMES]).double().cpu().numpy()
+    pset = g.ActorCriticSet.from_members([LS.device_policy(g, bt, k) for k in range(bt.K)] if pols is None else pols)
+    return pset, g.FusedUpdateSet(pset, cfgs, *LS.device_bufs(bt))
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("D,B,case", SET_CASES, ids=[_ID(c) for c in SET_CASES])
-def test_set_update_on_edge_minibatches_vs_float64(g, K, D, B, case):
+def test_set_update_on_edge_minibatches_vs_float64(g, D, B, case):
     """The solo test for K = 3 members with their own policy, clip_range 0.1 / 0.2 / 0.3 and vf_coef 0.5 / 0.25 / 1.0 on
     disjoint rows of one buffer: apply=False for the raw gradients, then one applied step of a fresh FusedUpdateSet.
     D = 8, 29 take acas2d_ppo_update_set_f32, D = 53, 197 acas2d_ppo_update_wide_set_f32 (asserted on fu.entry)."""
-    bt = _batch("set", D, B, case)
-    idx = _dev(bt.idx)
+    bt = LS.edge_batch("set", D, B, case)
+    idx = LS.dev(bt.idx)
     segs = R.segments(bt.pols[0])
-    na = _n_actor(segs)
+    na = LS.n_actor(segs)
     theta0 = [bt.theta(k) for k in range(bt.K)]
 
     def cfgs(ent, max_norm):
@@ -218,15 +163,15 @@ def test_set_update_on_edge_minibatches_vs_float64(g, K, D, B, case):
     assert fu.step_count.cpu().tolist() == [0] * bt.K and float(fu.m.abs().max()) == 0.0 and float(fu.v.abs().max()) == 0.0
     for k in range(bt.K):
         what = "set %s D=%d B=%d member %d" % (case, D, B, k)
-        assert np.array_equal(_theta_set(pset, k), theta0[k]), what
+        assert np.array_equal(LS.theta_of(pset, k), theta0[k]), what
         raw = fu.grad[k].double().cpu().numpy()
         got = raw.copy()
         got[-1] -= 0.01
         ref, pg, vf, _ = R.grad64(bt.ac_cls, cf[k], D, theta0[k], *bt.rows(k))
         assert np.isfinite(raw).all()
-        K._assert_per_tensor("raw gradient " + what, got, ref, segs, K.TAU)
+        LS.assert_per_tensor("raw gradient " + what, got, ref, segs, LS.TAU)
         st = fu.stats[k].double().cpu().numpy()
-        _check_losses(what, st[0], st[1], pg, vf)
+        LS.check_losses(what, st[0], st[1], pg, vf)
         if case == "const_adv":
             assert not raw[:na].any() and raw[-1] == 0.0 and st[0] == 0.0, what
             assert np.abs(raw[na:-1]).max() > 0.0
@@ -242,11 +187,11 @@ def test_set_update_on_edge_minibatches_vs_float64(g, K, D, B, case):
         grad, pg, vf, _ = R.grad64(bt.ac_cls, cf[k], D, theta0[k], *bt.rows(k))
         theta_ref, m_ref, v_ref, norm = R.adam64(theta0[k], grad, np.zeros_like(grad), np.zeros_like(grad), 0, 0.5, LR, 0.9, 0.999, 1e-5)
         st = fu.stats[k].double().cpu().numpy()
-        theta1, m1, v1 = _theta_set(pset, k), fu.m[k].double().cpu().numpy(), fu.v[k].double().cpu().numpy()
+        theta1, m1, v1 = LS.theta_of(pset, k), fu.m[k].double().cpu().numpy(), fu.v[k].double().cpu().numpy()
         assert np.isfinite(theta1).all() and np.isfinite(m1).all() and np.isfinite(v1).all()
         assert abs(st[2] - norm) <= 1e-5 * norm, (what, st[2], norm)
-        _check_losses(what + " applied", st[4], st[5], pg, vf)
-        _check_applied(K, what, segs, theta1, m1, v1, theta_ref, m_ref, v_ref, LR)
+        LS.check_losses(what + " applied", st[4], st[5], pg, vf)
+        LS.check_applied(what, segs, theta1, m1, v1, theta_ref, m_ref, v_ref, LR)
         if case == "const_adv":
             assert np.array_equal(theta1[:na], theta0[k][:na]) and theta1[-1] == theta0[k][-1], what
             assert not m1[:na].any() and not v1[:na].any() and m1[-1] == 0.0 and v1[-1] == 0.0, what
@@ -259,30 +204,30 @@ LARGE = [(D, 8193, case) for D in (8, 197) for case in ("grid_adv", "mixed")]
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("D,B,case", LARGE, ids=[_ID(c) for c in LARGE])
-def test_update_raw_gradient_at_8193_rows_vs_float64(g, K, D, B, case):
+def test_update_raw_gradient_at_8193_rows_vs_float64(g, D, B, case):
     """B = 8 193: 129 workgroups per network, the last with one live row; the advantage statistics loops run 129 (narrow)
     and 33 (wide) times per lane.  grid_adv (c = 64, q <= 1 / 8: exact sums) and a "mixed" minibatch, raw gradient."""
-    bt = _batch("solo", D, B, case)
-    pol = _policy(g, bt)
+    bt = LS.edge_batch("solo", D, B, case)
+    pol = LS.device_policy(g, bt)
     cfg = g.PPOConfig(ent_coef=0.01, max_grad_norm=-1.0, clip_range=0.2)
-    fu = g.FusedUpdate(pol, cfg, *_bufs(bt))
-    fu.step(_dev(bt.idx[0]))
+    fu = g.FusedUpdate(pol, cfg, *LS.device_bufs(bt))
+    fu.step(LS.dev(bt.idx[0]))
     torch.cuda.synchronize()
     got = fu.grad.double().cpu().numpy()
     got[-1] -= cfg.ent_coef
     ref, pg, vf, _ = R.grad64(bt.ac_cls, cfg, D, bt.theta(), *bt.rows())
     what = "%s D=%d B=%d" % (case, D, B)
-    K._assert_per_tensor("raw gradient " + what, got, ref, R.segments(pol), K.TAU)
+    LS.assert_per_tensor("raw gradient " + what, got, ref, R.segments(pol), LS.TAU)
     st = fu.stats.double().cpu().numpy()
-    _check_losses(what, st[0], st[1], pg, vf)
+    LS.check_losses(what, st[0], st[1], pg, vf)
 
 
 # ---- c. Adam constants -------------------------------------------------------------------------------------------------
-def _tau_v(K, beta2):
+def _tau_v(beta2):
     """TAU_V with its allowance for the float32 beta2 recomputed: the kernel's 1 - beta2 is |beta2_f32 - beta2| /
     (1 - beta2) relative off the reference's (1.3e-5 at 0.999, the figure TAU_V = 5e-5 was set with)."""
     term = lambda b: abs(float(np.float32(b)) - b) / (1.0 - b)  # noqa: E731
-    return K.TAU_V + (term(beta2) - term(0.999))
+    return LS.TAU_V + (term(beta2) - term(0.999))
 
 
 def _moments(rng, n):
@@ -295,67 +240,67 @@ ADAM_STARTS = ((0, 2, False), (9999, 2, True), (10_000_000, 1, True))       # st
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("D", (8, 53))
-def test_solo_update_with_other_adam_constants_vs_float64(g, K, D):
+def test_solo_update_with_other_adam_constants_vs_float64(g, D):
     """FusedUpdate(beta1=0.5, beta2=0.9, adam_eps=1e-3): two steps from step count 0, two from 9 999 with non-zero moments,
     one from 10 000 000 (both bias corrections are exactly 1 in float32), each against adam64 from the kernel's own
     state.  Bounds of test_fused_update_applied_steps_vs_float64, TAU_V's float32-beta2 term recomputed for 0.9."""
     B, b1, b2, eps = 130, 0.5, 0.9, 1e-3
-    bt = _batch("solo", D, B, "mixed")
-    bufs = _bufs(bt)
-    pol = _policy(g, bt)
+    bt = LS.edge_batch("solo", D, B, "mixed")
+    bufs = LS.device_bufs(bt)
+    pol = LS.device_policy(g, bt)
     segs = R.segments(pol)
     cfg = g.PPOConfig(ent_coef=0.01, max_grad_norm=0.5, learning_rate=LR, clip_range=0.2)
     rng = np.random.default_rng(D)
-    tau_v = _tau_v(K, b2)
-    assert tau_v <= K.TAU_V
+    tau_v = _tau_v(b2)
+    assert tau_v <= LS.TAU_V
     for start, steps, moments in ADAM_STARTS:
         fu = g.FusedUpdate(pol, cfg, *bufs, beta1=b1, beta2=b2, adam_eps=eps)
         fu.step_count.fill_(start)
         if moments:
             m_pre, v_pre = _moments(rng, fu.m.numel())
-            fu.m.copy_(_dev(m_pre))
-            fu.v.copy_(_dev(v_pre))
+            fu.m.copy_(LS.dev(m_pre))
+            fu.v.copy_(LS.dev(v_pre))
         for s in range(steps):
             # (rows 0 .. B - 1 of a fresh permutation: old_logp is "mixed" on every row; a ratio that an applied step has
-            # moved onto a clip edge is moved off it as _Batch.nudge_off_edges does)
+            # moved onto a clip edge is moved off it as RolloutBatch.nudge_off_edges does)
             rows = rng.permutation(bt.n)[:B]
             theta0 = R.flat_params(pol)
             lp = R.logp64(bt.ac_cls, D, theta0, bt.obs[rows], bt.act[rows])
             old, _ = E.nudge_off_edges(lp, bt.old_logp[rows].astype(np.float64), cfg.clip_range)
-            bufs[2][_dev(rows)] = _dev(old)
+            bufs[2][LS.dev(rows)] = LS.dev(old)
             m0, v0 = fu.m.double().cpu().numpy(), fu.v.double().cpu().numpy()
             mb = [a.astype(np.float64)[rows] for a in (bt.obs, bt.act)] + [old.astype(np.float64)] + \
                  [a.astype(np.float64)[rows] for a in (bt.adv, bt.ret)]
             grad, pg, vf, _ = R.grad64(bt.ac_cls, cfg, D, theta0, *mb)
             theta_ref, m_ref, v_ref, norm = R.adam64(theta0, grad, m0, v0, start + s, 0.5, LR, b1, b2, eps)
-            fu.step(_dev(rows))
+            fu.step(LS.dev(rows))
             torch.cuda.synchronize()
             what = "adam (%g, %g, %g) D=%d step %d" % (b1, b2, eps, D, start + s + 1)
             assert int(fu.step_count.item()) == start + s + 1, what
             st = fu.stats.double().cpu().numpy()
             assert abs(st[2] - norm) <= 1e-5 * norm, (what, st[2], norm)
-            _check_applied(K, what, segs, R.flat_params(pol), fu.m.double().cpu().numpy(), fu.v.double().cpu().numpy(),
-                           theta_ref, m_ref, v_ref, LR, tau_v)
+            LS.check_applied(what, segs, R.flat_params(pol), fu.m.double().cpu().numpy(), fu.v.double().cpu().numpy(),
+                             theta_ref, m_ref, v_ref, LR, tau_v)
             assert np.median(np.abs(theta_ref - theta0) / LR) > 0.05, what           # the reference's step is a real one
     assert start == 10_000_000 and np.float32(b1) ** np.float32(start + 1) == 0.0 and np.float32(b2) ** np.float32(start + 1) == 0.0
 
 
 @pytest.mark.gpu
-def test_set_update_with_adam_constants_per_member_vs_float64(g, K):
+def test_set_update_with_adam_constants_per_member_vs_float64(g):
     """D = 8, K = 3: hyper[k][5..7] written per member -- (0.5, 0.9, 1e-3), the defaults (0.9, 0.999, 1e-5), (0.8, 0.99,
     1e-4) -- the starts and step counts of the solo test on the member's own minibatch, every member against adam64 with ITS
     constants from the kernel's own state."""
     D, B = 8, 130
     consts = ((0.5, 0.9, 1e-3), (0.9, 0.999, 1e-5), (0.8, 0.99, 1e-4))
-    bt = _batch("set", D, B, "underflow")                   # ("mixed" rows with a tenth of the ratios at 0)
+    bt = LS.edge_batch("set", D, B, "underflow")            # ("mixed" rows with a tenth of the ratios at 0)
     segs = R.segments(bt.pols[0])
     cfgs = [g.PPOConfig(ent_coef=0.01, clip_range=bt.clips[k], vf_coef=E.VF_COEFS[k], max_grad_norm=0.5, learning_rate=LR)
             for k in range(bt.K)]
     rng = np.random.default_rng(3)
-    bufs, idx = _bufs(bt), _dev(bt.idx)
+    bufs, idx = LS.device_bufs(bt), LS.dev(bt.idx)
     old = bt.old_logp.copy()
     for start, steps, moments in ADAM_STARTS:
-        pset = g.ActorCriticSet.from_members([_policy(g, bt, k) for k in range(bt.K)])
+        pset = g.ActorCriticSet.from_members([LS.device_policy(g, bt, k) for k in range(bt.K)])
         fu = g.FusedUpdateSet(pset, cfgs, *bufs)
         fu.hyper[:, 5:8] = torch.tensor(consts, dtype=torch.float32, device=DEV)
         assert fu.hyper[1].cpu().tolist() == pytest.approx([0.2, 0.25, 0.01, 0.5, LR, 0.9, 0.999, 1e-5], rel=1e-6)
@@ -363,15 +308,15 @@ def test_set_update_with_adam_constants_per_member_vs_float64(g, K):
         if moments:
             for k in range(bt.K):
                 m_pre, v_pre = _moments(rng, fu.m.shape[1])
-                fu.m[k].copy_(_dev(m_pre))
-                fu.v[k].copy_(_dev(v_pre))
+                fu.m[k].copy_(LS.dev(m_pre))
+                fu.v[k].copy_(LS.dev(v_pre))
         for s in range(steps):
-            theta0 = [_theta_set(pset, k) for k in range(bt.K)]
-            for k in range(bt.K):                           # (_Batch.nudge_off_edges for the member's CURRENT parameters)
+            theta0 = [LS.theta_of(pset, k) for k in range(bt.K)]
+            for k in range(bt.K):                           # (RolloutBatch.nudge_off_edges for the member's CURRENT parameters)
                 i = bt.idx[k]
                 lp = R.logp64(bt.ac_cls, D, theta0[k], bt.obs[i], bt.act[i])
                 old[i], _ = E.nudge_off_edges(lp, old[i].astype(np.float64), bt.clips[k])
-            bufs[2].copy_(_dev(old))
+            bufs[2].copy_(LS.dev(old))
             m0, v0 = fu.m.double().cpu().numpy(), fu.v.double().cpu().numpy()
             fu.step(idx)
             torch.cuda.synchronize()
@@ -383,10 +328,10 @@ def test_set_update_with_adam_constants_per_member_vs_float64(g, K):
                 grad, pg, vf, _ = R.grad64(bt.ac_cls, cfgs[k], D, theta0[k], *mb)
                 theta_ref, m_ref, v_ref, norm = R.adam64(theta0[k], grad, m0[k], v0[k], start + s, 0.5, LR, b1, b2, eps)
                 assert abs(float(fu.stats[k, 2]) - norm) <= 1e-5 * norm, what
-                tau_v = _tau_v(K, b2)
-                assert tau_v <= K.TAU_V
-                _check_applied(K, what, segs, _theta_set(pset, k), fu.m[k].double().cpu().numpy(),
-                               fu.v[k].double().cpu().numpy(), theta_ref, m_ref, v_ref, LR, tau_v)
+                tau_v = _tau_v(b2)
+                assert tau_v <= LS.TAU_V
+                LS.check_applied(what, segs, LS.theta_of(pset, k), fu.m[k].double().cpu().numpy(),
+                                 fu.v[k].double().cpu().numpy(), theta_ref, m_ref, v_ref, LR, tau_v)
 
 
 # ---- d. members that share rows ----------------------------------------------------------------------------------------
@@ -396,10 +341,10 @@ def test_set_members_on_the_same_rows_stay_bit_equal(g, D, B):
     """K = 3 copies of one policy, the same hyper-row, the same idx (drawn with replacement: duplicates inside): with one
     wave per network every gradient entry gets one atomic, so grad[k], the 13 parameter stacks, m, v and stats are the
     same bits for every k -- after the raw gradient and after each of two applied steps."""
-    bt = _batch("solo", D, B, "dup_rows")
+    bt = LS.edge_batch("solo", D, B, "dup_rows")
     assert bt.labels["distinct_rows"][0] < B
     cfg = g.PPOConfig(ent_coef=0.01, max_grad_norm=0.5, learning_rate=LR, clip_range=0.2)
-    idx = _dev(np.stack([bt.idx[0]] * 3))
+    idx = LS.dev(np.stack([bt.idx[0]] * 3))
 
     def all_equal(fu, pset, what):
         tensors = [("grad", fu.grad), ("m", fu.m), ("v", fu.v), ("stats", fu.stats), ("step", fu.step_count)]
@@ -409,33 +354,33 @@ def test_set_members_on_the_same_rows_stay_bit_equal(g, D, B):
             for k in (1, 2):
                 assert torch.equal(t[k], t[0]), (what, name, k)
 
-    pset, fu = _set_update(g, bt, [cfg] * 3, pols=[_policy(g, bt)] * 3)
+    pset, fu = _set_update(g, bt, [cfg] * 3, pols=[LS.device_policy(g, bt)] * 3)
     fu.step(idx, apply=False)
     torch.cuda.synchronize()
     assert float(fu.grad[0].abs().max()) > 0.0
     all_equal(fu, pset, "raw gradient")
-    before = _theta_set(pset, 2)
-    pset, fu = _set_update(g, bt, [cfg] * 3, pols=[_policy(g, bt)] * 3)
+    before = LS.theta_of(pset, 2)
+    pset, fu = _set_update(g, bt, [cfg] * 3, pols=[LS.device_policy(g, bt)] * 3)
     for step in range(2):
         fu.step(idx)
         torch.cuda.synchronize()
         all_equal(fu, pset, "applied step %d" % (step + 1))
-    assert fu.step_count.cpu().tolist() == [2, 2, 2] and np.abs(_theta_set(pset, 2) - before).max() > 0.0
+    assert fu.step_count.cpu().tolist() == [2, 2, 2] and np.abs(LS.theta_of(pset, 2) - before).max() > 0.0
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("D", (8, 29))
-def test_set_members_on_overlapping_rows_vs_float64(g, K, D):
+def test_set_members_on_overlapping_rows_vs_float64(g, D):
     """B = 130: members 0 and 2 hold different policies (member 2 is member 0 with every parameter scaled by 1 + N(0,
     0.1): a nearby policy, so its ratios on rows whose old_logp came from member 0 stay finite) and minibatches that share
     65 rows; member 1 is a copy of member 0 on rows of its own.  Raw gradient of each member against float64."""
     B = 130
-    bt = _batch("solo", D, B, "mixed")
+    bt = LS.edge_batch("solo", D, B, "mixed")
     rng = np.random.default_rng(D)
     perm = rng.permutation(bt.n)
     rows = np.stack([perm[:B], perm[200:200 + B], perm[65:65 + B]])
     assert len(np.intersect1d(rows[0], rows[2])) == 65 and len(np.intersect1d(rows[0], rows[1])) == 0
-    pols = [_policy(g, bt) for _ in range(3)]
+    pols = [LS.device_policy(g, bt) for _ in range(3)]
     gen = torch.Generator().manual_seed(D)
     with torch.no_grad():
         for p in pols[2].parameters():
@@ -452,12 +397,12 @@ def test_set_members_on_overlapping_rows_vs_float64(g, K, D):
         if not moved:
             break
     assert not moved
-    bufs = _bufs(bt)
-    bufs[2] = _dev(old)
+    bufs = LS.device_bufs(bt)
+    bufs[2] = LS.dev(old)
     cfgs = [g.PPOConfig(ent_coef=0.01, clip_range=clips[k], vf_coef=E.VF_COEFS[k], max_grad_norm=0.5) for k in range(3)]
     pset = g.ActorCriticSet.from_members(pols)
     fu = g.FusedUpdateSet(pset, cfgs, *bufs)
-    fu.step(_dev(rows), apply=False)
+    fu.step(LS.dev(rows), apply=False)
     torch.cuda.synchronize()
     segs = R.segments(pols[0])
     grads = []
@@ -467,52 +412,32 @@ def test_set_members_on_overlapping_rows_vs_float64(g, K, D):
         assert np.log(ratio).max() <= 3.0, (k, np.log(ratio).max())
         got = fu.grad[k].double().cpu().numpy()
         got[-1] -= 0.01
-        K._assert_per_tensor("overlapping rows D=%d member %d" % (D, k), got, ref, segs, K.TAU)
-        _check_losses("member %d" % k, float(fu.stats[k, 0]), float(fu.stats[k, 1]), pg, vf)
+        LS.assert_per_tensor("overlapping rows D=%d member %d" % (D, k), got, ref, segs, LS.TAU)
+        LS.check_losses("member %d" % k, float(fu.stats[k, 0]), float(fu.stats[k, 1]), pg, vf)
         grads.append(ref)
     assert np.abs(grads[0] - grads[2]).max() > 1e-3 * np.abs(grads[0]).max()          # the members really differ
 
 
 # ---- e. guard bands ----------------------------------------------------------------------------------------------------
-PAD, SENT = 4096, -7.25
-
-
-def _carve(shape, dtype=torch.float32, sent=SENT, init=None):
-    """A tensor of `shape` that is the middle of a sentinel-filled one: (view, whole)."""
-    k = int(np.prod(shape))
-    big = torch.full((k + 2 * PAD,), sent, dtype=dtype, device=DEV)
-    view = big[PAD:PAD + k].view(*shape)
-    if init is None:
-        view.zero_()
-    else:
-        view.copy_(init)
-    assert view.is_contiguous() and view.data_ptr() == big.data_ptr() + PAD * big.element_size()
-    return view, big
-
-
-def _intact(name, big, k, sent=SENT):
-    assert bool((big[:PAD] == sent).all()) and bool((big[PAD + k:] == sent).all()), name
-
-
 @pytest.mark.gpu
 def test_narrow_update_writes_nothing_outside_its_workspace(g):
     """test_wide_update_writes_nothing_outside_its_workspace for the narrow kernel: D = 29, B = 65 (a second workgroup
     with one live row); grad / m / v carved from sentinel-filled tensors, one probe and two applied steps."""
     D, B = 29, 65
-    bt = _batch("solo", D, B, "dup_rows")
-    bufs, idx = _bufs(bt), _dev(bt.idx[0])
+    bt = LS.edge_batch("solo", D, B, "dup_rows")
+    bufs, idx = LS.device_bufs(bt), LS.dev(bt.idx[0])
     reads = [t.clone() for t in bufs] + [idx.clone()]
-    pol = _policy(g, bt)
+    pol = LS.device_policy(g, bt)
     for max_norm, steps in ((-1.0, 1), (0.5, 2)):
         fu = g.FusedUpdate(pol, g.PPOConfig(max_grad_norm=max_norm), *bufs)
         k = fu.grad.numel()
-        carved = [_carve((k,)) for _ in range(3)]
+        carved = [LS.carve((k,)) for _ in range(3)]
         fu.grad, fu.m, fu.v = (c[0] for c in carved)
         for _ in range(steps):
             fu.step(idx)
             torch.cuda.synchronize()
         for name, (_, big) in zip(("grad", "m", "v"), carved):
-            _intact((max_norm, name), big, k)
+            LS.intact((max_norm, name), big, k)
         assert float(fu.grad.abs().max()) > 0.0 if max_norm < 0 else float(fu.m.abs().max()) > 0.0      # it did run
     for t, q in zip(bufs + [idx], reads):
         assert torch.equal(t, q)
@@ -524,31 +449,31 @@ def test_set_update_writes_nothing_outside_its_workspace(g):
     middle of sentinel-filled tensors (the kernels address grad + member * total, stats + member * 8, prm.p[k] + member *
     count).  After one probe and two applied steps every sentinel, every input buffer, idx and hyper are intact."""
     D, B = 8, 65
-    bt = _batch("set", D, B, "dup_rows")
-    bufs, idx = _bufs(bt), _dev(bt.idx)
+    bt = LS.edge_batch("set", D, B, "dup_rows")
+    bufs, idx = LS.device_bufs(bt), LS.dev(bt.idx)
     reads = [t.clone() for t in bufs] + [idx.clone()]
     cfgs = [g.PPOConfig(ent_coef=0.01, clip_range=bt.clips[k], vf_coef=E.VF_COEFS[k], max_grad_norm=0.5) for k in range(bt.K)]
     for apply, steps in ((False, 1), (True, 2)):
-        pset = g.ActorCriticSet.from_members([_policy(g, bt, k) for k in range(bt.K)])
+        pset = g.ActorCriticSet.from_members([LS.device_policy(g, bt, k) for k in range(bt.K)])
         stacks = {}
         for n in R.PARAM_NAMES:
-            pset.params[n], stacks[n] = _carve(tuple(pset.params[n].shape), init=pset.params[n])
+            pset.params[n], stacks[n] = LS.carve(tuple(pset.params[n].shape), init=pset.params[n])
         start = {n: pset.params[n].clone() for n in R.PARAM_NAMES}
         fu = g.FusedUpdateSet(pset, cfgs, *bufs)
         assert all(p.data_ptr() == pset.params[n].data_ptr() for p, n in zip(fu._params, R.PARAM_NAMES))
         hyper = fu.hyper.clone()
         total = fu.grad.shape[1]
-        carved = {name: _carve(tuple(getattr(fu, name).shape)) for name in ("grad", "m", "v", "stats")}
-        carved["step_count"] = _carve((bt.K,), dtype=torch.int32, sent=-77)
+        carved = {name: LS.carve(tuple(getattr(fu, name).shape)) for name in ("grad", "m", "v", "stats")}
+        carved["step_count"] = LS.carve((bt.K,), dtype=torch.int32, sent=-77)
         for name, (view, _) in carved.items():
             setattr(fu, name, view)
         for _ in range(steps):
             fu.step(idx, apply=apply)
             torch.cuda.synchronize()
         for name, (view, big) in carved.items():
-            _intact((apply, name), big, view.numel(), -77 if name == "step_count" else SENT)
+            LS.intact((apply, name), big, view.numel(), -77 if name == "step_count" else LS.SENT)
         for n in R.PARAM_NAMES:
-            _intact((apply, n), stacks[n], pset.params[n].numel())
+            LS.intact((apply, n), stacks[n], pset.params[n].numel())
             assert torch.equal(pset.params[n], start[n]) != apply, (apply, n)       # moved when applied, and only then
         assert fu.step_count.cpu().tolist() == [steps if apply else 0] * bt.K
         assert torch.equal(fu.hyper, hyper) and fu.grad.shape == (bt.K, total)
@@ -560,7 +485,7 @@ def test_set_update_writes_nothing_outside_its_workspace(g):
 # ---- f. a rollout buffer past 2^31 floats -------------------------------------------------------------------------------
 @pytest.mark.gpu
 @pytest.mark.parametrize("D", (29, 197))
-def test_update_gathers_rows_past_2_31_floats(g, K, D):
+def test_update_gathers_rows_past_2_31_floats(g, D):
     """obs is [2^31 // D + 4 096, D] zeros (8.6 GB); the B = 130 rows of the wide_obs minibatch are written at row numbers
     of which 66 lie beyond float 2^31 of obs -- one is the last row, one straddles the boundary -- so `s * D + k` must be
     taken in 64 bits.  Raw gradient against float64 on the gathered rows.  Skipped, with the reason printed, where less
@@ -570,7 +495,7 @@ def test_update_gathers_rows_past_2_31_floats(g, K, D):
     if free < 12 * 2 ** 30:
         print("skipped: %.1f GB of device memory free, the buffer needs 12" % (free / 2 ** 30))
         pytest.skip("needs 12 GB of free device memory")
-    bt = _batch("solo", D, B, "wide_obs")
+    bt = LS.edge_batch("solo", D, B, "wide_obs")
     n = 2 ** 31 // D + 4096
     edge = 2 ** 31 // D                                      # the row that holds float 2^31
     assert edge * D < 2 ** 31 < (edge + 1) * D               # ... and straddles it
@@ -580,13 +505,13 @@ def test_update_gathers_rows_past_2_31_floats(g, K, D):
     rows = rows[rng.permutation(B)].astype(np.int64)
     assert len(np.unique(rows)) == B and (rows * D + D - 1 >= 2 ** 31).sum() >= B // 2 and rows.max() == n - 1
     small = [a[bt.idx[0]] for a in (bt.obs, bt.act, bt.old_logp, bt.adv, bt.ret)]
-    idx = _dev(rows)
+    idx = LS.dev(rows)
     bufs = [torch.zeros((n, D) if i == 0 else (n,), dtype=torch.float32, device=DEV) for i in range(5)]
     fu = None
     try:
         for big, a in zip(bufs, small):
-            big[idx] = _dev(a)
-        pol = _policy(g, bt)
+            big[idx] = LS.dev(a)
+        pol = LS.device_policy(g, bt)
         cfg = g.PPOConfig(ent_coef=0.01, max_grad_norm=-1.0, clip_range=0.2)
         fu = g.FusedUpdate(pol, cfg, *bufs)
         fu.step(idx)
@@ -599,5 +524,5 @@ def test_update_gathers_rows_past_2_31_floats(g, K, D):
         torch.cuda.empty_cache()
     got[-1] -= cfg.ent_coef
     ref, pg, vf, _ = R.grad64(bt.ac_cls, cfg, D, bt.theta(), *bt.rows())
-    K._assert_per_tensor("rows past 2^31 floats D=%d" % D, got, ref, R.segments(pol), K.TAU)
-    _check_losses("D=%d" % D, st[0], st[1], pg, vf)
+    LS.assert_per_tensor("rows past 2^31 floats D=%d" % D, got, ref, R.segments(pol), LS.TAU)
+    LS.check_losses("D=%d" % D, st[0], st[1], pg, vf)

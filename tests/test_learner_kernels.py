@@ -16,6 +16,7 @@ import pytest
 
 import helpers as H
 import learner_ref as R
+import learner_support as LS
 
 torch = pytest.importorskip("torch")
 DEV = "cuda:0"
@@ -29,87 +30,9 @@ def g():
     return g
 
 
-def _parallel_flight(env, rows):
-    """Put traffic[0] of the env rows `rows` on the player's heading and speed (the NaN rows of ref_edge_n1 / n3: the
-    reference's d_cpa is 0 / 0) and observe.  Returns (own, trf, goal) as injected and the first observation."""
-    own = torch.stack([env.own_x, env.own_y, env.own_psi, env.own_v], 1).double().cpu().numpy()
-    trf = torch.stack([env.trf_x, env.trf_y, env.trf_psi, env.trf_v], -1).double().cpu().numpy()
-    goal = torch.stack([env.goal_x, env.goal_y], 1).double().cpu().numpy()
-    trf[rows, 0, 2], trf[rows, 0, 3] = own[rows, 2], own[rows, 3]
-    obs0 = env.set_state(own, trf, goal, np.zeros(env.num_envs, np.int32), observe=True).double().cpu().numpy()
-    return (own, trf, goal), obs0
-
-
 # ---- acas2d_ppo_update_f32 ------------------------------------------------------------------------------------------
 _B_ALL = (2, 3, 63, 64, 65, 127, 129, 2085, 4096)
 UPDATE_CASES = [(D, B) for D in R.UPDATE_WIDTHS for B in (_B_ALL if D in (8, 29) else (2, 65, 2085))]
-# raw gradient, per tensor: max |got - ref| <= TAU * max |ref tensor| + TAU0 * max |ref, all 13 tensors|
-# (observed at most 2.1e-6 over every case: tau 2e-5 leaves 10x headroom, and is 10x tighter than the global 2e-4 of
-# test_fused_update_against_torch_autograd_and_adam)
-TAU, TAU0 = 2e-5, 1e-6
-# moments after a step, per tensor with the same tau0: m (observed within the tau0 term) and v -- the kernel's 0.999f
-# makes its 1 - beta2 1.3e-5 relative off the reference's (observed 1.4e-5)
-TAU_M, TAU_V = 2e-5, 5e-5
-
-
-class _Batch:
-    """A rollout buffer of n rows on the device (the kernel gathers the minibatch by idx, a random subset)."""
-
-    def __init__(self, g, D, n, seed):
-        rng = np.random.default_rng(seed)
-        self.rng, self.D, self.n = rng, D, n
-        f = lambda a: torch.as_tensor(np.asarray(a, np.float32), device=DEV).contiguous()  # noqa: E731
-        self.obs = f(rng.uniform(-1, 1, (n, D)))
-        self.act = f(rng.normal(0, 0.7, n))
-        self.adv, self.ret = f(rng.normal(0, 2, n)), f(rng.normal(2, 3, n))      # (value offset: gradient norm > 0.5 at any B)
-        self.old_logp = torch.zeros(n, dtype=torch.float32, device=DEV)
-        torch.manual_seed(seed)
-        self.pol = g.ActorCritic(D).to(DEV)
-        with torch.no_grad():
-            self.pol.action_net.weight.mul_(40.0)       # away from SB3's near-zero init: ratios spread, some clip
-            self.pol.log_std.fill_(-0.7)
-        self.ac_cls = g.ActorCritic
-
-    def host(self, idx):
-        i = idx.cpu().numpy()
-        return [t.cpu().numpy().astype(np.float64)[i] for t in (self.obs, self.act, self.old_logp, self.adv, self.ret)]
-
-    def set_old_logp(self, mode, clip):
-        """mode "mixed": the current policy's float64 log-prob plus N(0, 0.5) noise -- ratios on both sides of the clip
-        range; "first": the log-prob itself (a first-epoch minibatch: ratio ~ 1, surr1 == surr2).  Ratios within 1e-4
-        of a clip edge are moved off it (float32 and float64 would take different branches there)."""
-        theta = R.flat_params(self.pol)
-        lp = R.logp64(self.ac_cls, self.D, theta, self.obs.cpu().numpy(), self.act.cpu().numpy())
-        old = lp + (self.rng.normal(0, 0.5, self.n) if mode == "mixed" else 0.0)
-        old = old.astype(np.float32).astype(np.float64)
-        r = np.exp(lp - old)
-        edge = (np.abs(r - (1 - clip)) < 1e-4) | (np.abs(r - (1 + clip)) < 1e-4)
-        old[edge] -= 1e-3
-        self.old_logp.copy_(torch.as_tensor(old.astype(np.float32), device=DEV))
-        return int(edge.sum())
-
-    def nudge_off_edges(self, clip):
-        """set_old_logp's edge rule for the CURRENT parameters (an applied step moves the ratios)."""
-        theta = R.flat_params(self.pol)
-        lp = R.logp64(self.ac_cls, self.D, theta, self.obs.cpu().numpy(), self.act.cpu().numpy())
-        old = self.old_logp.cpu().numpy().astype(np.float64)
-        r = np.exp(lp - old)
-        edge = (np.abs(r - (1 - clip)) < 1e-4) | (np.abs(r - (1 + clip)) < 1e-4)
-        if edge.any():
-            old[edge] -= 1e-3
-            self.old_logp.copy_(torch.as_tensor(old.astype(np.float32), device=DEV))
-
-
-def _worst_ratio(errs, ref_all, tau0=TAU0):
-    """max over tensors of (max |diff| - tau0 max |ref_all|) / max |ref tensor|: the per-tensor criterion's tau."""
-    return max((e - tau0 * ref_all) / max(m, 1e-300) for e, m in errs.values())
-
-
-def _assert_per_tensor(what, got, ref, segs, tau, tau0=TAU0):
-    errs, ref_all = R.per_tensor_errors(got, ref, segs)
-    bad = {n: (e, m) for n, (e, m) in errs.items() if not e <= tau * m + tau0 * ref_all}
-    print("%s: observed tau %.2e (bound %.0e, tau0 %.0e)" % (what, _worst_ratio(errs, ref_all, tau0), tau, tau0))
-    assert not bad, (what, bad, ref_all)
 
 
 @pytest.mark.gpu
@@ -119,7 +42,7 @@ def test_fused_update_raw_gradient_per_tensor_vs_float64(g, D, B):
     a minibatch that is a random subset of a larger buffer: with ratios clipped on both sides for both signs of the
     advantage (ent_coef 0.01), and a first-epoch minibatch (ratio ~ 1: ties of the two surrogates, ent_coef 0)."""
     n = max(2 * B, 300) + 17
-    bt = _Batch(g, D, n, seed=1000 + 7 * D + B)
+    bt = LS.SoloBatch(g, D, n, seed=1000 + 7 * D + B)
     segs = R.segments(bt.pol)
     for mode, ent in (("mixed", 0.01), ("first", 0.0)):
         cfg = g.PPOConfig(ent_coef=ent, max_grad_norm=-1.0, clip_range=0.2)
@@ -141,7 +64,7 @@ def test_fused_update_raw_gradient_per_tensor_vs_float64(g, D, B):
         if mode == "first":
             assert np.abs(ratio - 1).max() < 1e-5
         assert np.array_equal(fu.step_count.cpu().numpy(), [0])      # nothing applied
-        _assert_per_tensor("raw gradient D=%d B=%d %s" % (D, B, mode), got, ref, segs, TAU)
+        LS.assert_per_tensor("raw gradient D=%d B=%d %s" % (D, B, mode), got, ref, segs, LS.TAU)
         st = fu.stats.double().cpu().numpy()
         print("  pg %.3e vs %.3e, vf %.3e vs %.3e" % (st[0], pg, st[1], vf))
         assert abs(st[0] - pg) <= 1e-5 * max(1.0, abs(pg)) and abs(st[1] - vf) <= 1e-5 * max(1.0, vf)
@@ -156,7 +79,7 @@ def test_fused_update_applied_steps_vs_float64(g, D, B):
     handed beta2 as a float32 (0.999f: 1 - beta2 is 1.3e-5 relative off 1e-3); the float64 reference uses 0.999 exactly,
     and the moment bounds below absorb that."""
     n = max(2 * B, 300) + 17
-    bt = _Batch(g, D, n, seed=2000 + 7 * D + B)
+    bt = LS.SoloBatch(g, D, n, seed=2000 + 7 * D + B)
     segs = R.segments(bt.pol)
     lr, b1, b2, eps = 3e-4, 0.9, 0.999, 1e-5
     worst = {"param": 0.0, "m": 0.0, "v": 0.0, "norm": 0.0, "pg": 0.0, "vf": 0.0}
@@ -192,12 +115,8 @@ def test_fused_update_applied_steps_vs_float64(g, D, B):
                 worst[key] = max(worst[key], abs(got_ - ref_) / tol * 1.0)
                 assert abs(got_ - ref_) <= tol, (what, key, got_, ref_)
             m1, v1 = fu.m.double().cpu().numpy(), fu.v.double().cpu().numpy()
-            em, mall = R.per_tensor_errors(m1, m_ref, segs)
-            ev, vall = R.per_tensor_errors(v1, v_ref, segs)
-            worst["m"] = max(worst["m"], _worst_ratio(em, mall))
-            worst["v"] = max(worst["v"], _worst_ratio(ev, vall))
-            _assert_per_tensor("m " + what, m1, m_ref, segs, TAU_M)
-            _assert_per_tensor("v " + what, v1, v_ref, segs, TAU_V)
+            worst["m"] = max(worst["m"], LS.assert_per_tensor("m " + what, m1, m_ref, segs, LS.TAU_M))
+            worst["v"] = max(worst["v"], LS.assert_per_tensor("v " + what, v1, v_ref, segs, LS.TAU_V))
             # parameters: one float32 rounding of the stored value, plus a small fraction of an Adam step (~lr).  Adam's
             # g / (|g| + eps) turns the gradient's tau0 term into up to ~lr tau0 max|g| / eps for entries with |g| ~ eps
             # (observed at most 1.0e-3 lr; the bound is 10x that, and 2x tighter than test_ppo.py's 0.02 lr against torch)
@@ -210,7 +129,7 @@ def test_fused_update_applied_steps_vs_float64(g, D, B):
             assert np.median(moved / lr) > 0.05, what                           # the step was taken
     print("applied steps D=%d B=%d: worst param excess %.2e lr (bound 1e-2), m tau %.2e (bound %.0e), v tau %.2e (bound "
           "%.0e), norm / pg / vf at %.2f / %.2f / %.2f of their 1e-5 bounds"
-          % (D, B, worst["param"], worst["m"], TAU_M, worst["v"], TAU_V, worst["norm"], worst["pg"], worst["vf"]))
+          % (D, B, worst["param"], worst["m"], LS.TAU_M, worst["v"], LS.TAU_V, worst["norm"], worst["pg"], worst["vf"]))
 
 
 @pytest.mark.gpu
@@ -225,7 +144,7 @@ def test_narrow_and_wide_update_on_a_second_device(g):
     for dev in ("cuda:0", "cuda:1"):
         for D in (8, 53):
             n = 2 * B + 17
-            bt = _Batch(g, D, n, seed=1000 + 7 * D + B)
+            bt = LS.SoloBatch(g, D, n, seed=1000 + 7 * D + B)
             cfg = g.PPOConfig(ent_coef=0.01, max_grad_norm=-1.0, clip_range=0.2)
             bt.set_old_logp("mixed", cfg.clip_range)
             idx = torch.randperm(n, device=DEV)[:B].contiguous()
@@ -239,21 +158,12 @@ def test_narrow_and_wide_update_on_a_second_device(g):
             got = fu.grad.double().cpu().numpy()
             got[-1] -= cfg.ent_coef
             ref, pg, vf, _ = R.grad64(bt.ac_cls, cfg, D, theta, *host)
-            _assert_per_tensor("raw gradient D=%d B=%d on %s" % (D, B, dev), got, ref, R.segments(bt.pol), TAU)
+            LS.assert_per_tensor("raw gradient D=%d B=%d on %s" % (D, B, dev), got, ref, R.segments(bt.pol), LS.TAU)
             st = fu.stats.double().cpu().numpy()
             assert abs(st[0] - pg) <= 1e-5 * max(1.0, abs(pg)) and abs(st[1] - vf) <= 1e-5 * max(1.0, vf)
 
 
 # ---- acas2d_collect_* -------------------------------------------------------------------------------------------------
-def _actor_critic(g, D, seed=1):
-    torch.manual_seed(seed)
-    pol = g.ActorCritic(D).to(DEV)
-    with torch.no_grad():
-        pol.action_net.weight.mul_(40.0)
-        pol.log_std.fill_(-0.7)
-    return pol
-
-
 def _env(g, kern, E, **kw):
     dtype, fast, N = kern
     cfg = g.ACAS2DConfig(n_traffic=N, fast_math=fast, **kw.pop("cfg", {}))
@@ -270,12 +180,12 @@ def test_fused_collector_vs_float64(g, kern):
     dtype, fast, N = kern
     D, E, T = 5 + 3 * N, 512, 24
     seed, nstep, off = 0x243F6A8885A308D3, 2 ** 32 - 5, 2 ** 32 - 259
-    pol = _actor_critic(g, D)
+    pol = LS.actor_critic(g, D)
     env, twin = (_env(g, kern, E, seed=21, env_offset=off, cfg={"max_steps": 12}) for _ in range(2))
     env.reset()
     twin.reset()
     rows = np.arange(3, E, 11)
-    state, obs0 = _parallel_flight(env, rows)
+    state, obs0 = LS.parallel_flight(env, rows)
     twin.set_state(*state, np.zeros(E, np.int32), observe=True)
     assert np.isnan(obs0[rows]).any(1).all() and not np.isnan(np.delete(obs0, rows, 0)).any()     # NaN really in
     out = env.collect(pol, T, noise_seed=seed, noise_step=nstep)
@@ -318,7 +228,7 @@ def test_fused_collector_nondefault_config_replays_on_a_twin(g, kern):
     clipped actions reproduces every observation, reward and mask bit for bit (helpers.replay_collect_on_twin)."""
     dtype, fast, N = kern
     D, E, T = 5 + 3 * N, 1001, 100
-    pol = _actor_critic(g, D)
+    pol = LS.actor_critic(g, D)
     env, twin = (_env(g, kern, E, seed=3, env_offset=37, cfg=H.NONDEFAULT_CONFIGS["small"]) for _ in range(2))
     env.reset()
     twin.reset()
@@ -338,7 +248,7 @@ def test_fused_policy_rollout_nondefault_config_replays_on_a_twin(g, kern):
     reproduces every observation, reward and mask bit for bit and ends in the same state."""
     dtype, fast, N = kern
     D, E, T = 5 + 3 * N, 1001, 100
-    pol = _actor_critic(g, D)
+    pol = LS.actor_critic(g, D)
     env, twin = (_env(g, kern, E, seed=3, env_offset=37, cfg=H.NONDEFAULT_CONFIGS["small"]) for _ in range(2))
     env.reset()
     obs0 = twin.reset().double().cpu().numpy()
@@ -366,29 +276,6 @@ def test_fused_policy_rollout_nondefault_config_replays_on_a_twin(g, kern):
 
 
 # ---- acas2d_rollout_policy_* ----------------------------------------------------------------------------------------
-def _scaled_actor(g, D, kind, obs0):
-    """An SB3 actor whose hidden pre-activations reach |z| = 60 on obs0 in both layers ("saturating": v_exp_f32 in
-    tanh_hw overflows to inf / underflows to 0), stay within 0.05 of 0 ("small"), or are SB3's own ("plain"); the head
-    is scaled so that |mean - b3| reaches 1.5 (some actions clip, most do not) -- 0.3 for the near-zero one: there
-    1 - 2 / (exp(2x) + 1) cancels, tanh_hw's ~1e-7 absolute error is large relative to h ~ 0.05, and the head's weights
-    multiply it."""
-    torch.manual_seed(7)
-    pol = g.ActorCritic(D).double()
-    pn = pol.mlp_extractor.policy_net
-    x = R.obs32(obs0[np.isfinite(obs0).all(1)])
-    with torch.no_grad():
-        if kind != "plain":
-            target = 60.0 if kind == "saturating" else 0.05
-            z1, _ = R.preactivations64(R.params64(pol), x)
-            pn[0].weight.mul_(target / np.abs(z1).max())
-            _, z2 = R.preactivations64(R.params64(pol), x)
-            pn[2].weight.mul_(target / np.abs(z2).max())
-        p = R.params64(pol)
-        mean = R.mlp64(p, "mlp_extractor.policy_net", "action_net", x) - p["action_net.bias"][0]
-        pol.action_net.weight.mul_((0.3 if kind == "small" else 1.5) / np.abs(mean).max())
-    return pol.float().to(DEV)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("kern", R.POLICY_KERNELS, ids=[R.kernel_id(k) for k in R.POLICY_KERNELS])
 def test_fused_policy_actions_vs_float64(g, O, kern):
@@ -403,9 +290,9 @@ def test_fused_policy_actions_vs_float64(g, O, kern):
     for kind in ("plain", "saturating", "small"):
         env = _env(g, kern, E, seed=21)
         env.reset()
-        state, obs0 = _parallel_flight(env, rows)
+        state, obs0 = LS.parallel_flight(env, rows)
         assert np.isnan(obs0[rows]).any(1).all()
-        pol = _scaled_actor(g, D, kind, obs0)
+        pol = LS.scaled_actor(g, D, kind, obs0)
         out = env.rollout_policy(pol, T)
         torch.cuda.synchronize()
         obs = np.concatenate([obs0[None], out["obs"][:T - 1].double().cpu().numpy()])
@@ -461,7 +348,7 @@ def test_nan_observation_evaluations_agree(g, N):
     if N == 1:
         pol = g.load_sb3_policy(os.path.join(H.GOLDEN, "ref_policy_best_model.npz"), device=DEV)
     else:
-        pol = _actor_critic(g, 5 + 3 * N, seed=3)
+        pol = LS.actor_critic(g, 5 + 3 * N, seed=3)
     ev = g.ACAS2DVecEnv(E, N, device=DEV, dtype=torch.float64, auto_reset=False)
     obs0 = ev.set_state(own, trf, goal, np.zeros(E, np.int32)).cpu().numpy()
     assert np.isnan(obs0[rows]).any(1).all()
@@ -495,7 +382,7 @@ def test_fused_collector_at_wide_keys_replays_on_a_twin(g, kern):
     dtype, fast, N = kern
     E, T = H.WIDE_E, 90
     env, twin, pre = _wide_pair(g, kern, E)
-    out = env.collect(_actor_critic(g, 5 + 3 * N), T, noise_seed=H.WIDE_SEED, noise_step=0)
+    out = env.collect(LS.actor_critic(g, 5 + 3 * N), T, noise_seed=H.WIDE_SEED, noise_step=0)
     H.replay_collect_on_twin(env, twin, out)
     assert int((env.episode[pre] >= 0).sum()) >= 50                    # wrapped through 2^32 - 1 to 0
 
@@ -508,7 +395,7 @@ def test_fused_policy_rollout_at_wide_keys_replays_on_a_twin(g, kern):
     bit and ends in the same state, the preset counters wrapped."""
     dtype, fast, N = kern
     D, E, T = 5 + 3 * N, H.WIDE_E, 90
-    pol = _actor_critic(g, D)
+    pol = LS.actor_critic(g, D)
     env, twin, pre = _wide_pair(g, kern, E)
     obs0 = twin.outputs["obs"].double().cpu().numpy()
     out = env.rollout_policy(pol, T)

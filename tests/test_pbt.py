@@ -7,21 +7,15 @@ on oracle.philox4x32, and the CPU tests pin that referee on hand-computed cases 
 integers and to the worst-case bound of a double summation in any order.  PBTTrainer is held to PopulationTrainer (no
 exchange: the same bits) and to the referee applied to a snapshot (with exchange)."""
 import ctypes as C
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import helpers as H
 import pbt_ref as R
 
 torch = pytest.importorskip("torch")
 DEV = "cuda:0"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gym-acas2d_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 WIDTHS = (8, 11, 14, 17, 29, 53, 101, 197)
 INT32_MIN = np.iinfo(np.int32).min
 F32 = np.float32
@@ -227,22 +221,16 @@ def test_pbt_config_says_which_rule_it_holds():
             PBTConfig(**kw)
 
 
-@pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="needs hipcc")
+@H.needs_hipcc
 def test_pbt_kernels_use_no_scratch_and_spill_nothing(tmp_path):
     """The code-object metadata of csrc/acas2d_pbt.hip, read the way tests/test_gae_kernel.py reads its unit."""
-    asm = tmp_path / "acas2d_pbt.s"
-    subprocess.run([HIPCC if os.path.exists(HIPCC) else "hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-ffp-contract=off", "-fno-slp-vectorize", "-mllvm",
-                    "-amdgpu-kernarg-preload-count=8", "-S", "--cuda-device-only", "-o", str(asm),
-                    os.path.join(CSRC, "acas2d_pbt.hip")], check=True, capture_output=True)
-    kernels = re.findall(r"\.name:\s+(\S+)\n(.*?)\.wavefront_size", asm.read_text(), re.S)
+    _, kernels = H.kernel_metadata(tmp_path, "acas2d_pbt.hip")
     assert len(kernels) == 2
-    field = lambda body, k: int(re.search(r"\.%s:\s+(\d+)" % k, body).group(1))  # noqa: E731
-    for name, body in kernels:
-        assert "member_episodes_kernel" in name or "population_exploit_kernel" in name
-        print(name, "vgpr", field(body, "vgpr_count"), "sgpr", field(body, "sgpr_count"))
-        assert field(body, "vgpr_spill_count") == 0 and field(body, "sgpr_spill_count") == 0, name
-        assert field(body, "private_segment_fixed_size") == 0 and field(body, "vgpr_count") <= 128, name
+    for k in kernels:
+        assert "member_episodes_kernel" in k.name or "population_exploit_kernel" in k.name
+        print(k.name, "vgpr", k.field("vgpr_count"), "sgpr", k.field("sgpr_count"))
+        assert k.field("vgpr_spill_count") == 0 and k.field("sgpr_spill_count") == 0, k.name
+        assert k.field("private_segment_fixed_size") == 0 and k.field("vgpr_count") <= 128, k.name
 
 
 # ---- GPU: exploit against the referee, bit for bit -------------------------------------------------------------------------

@@ -4,7 +4,7 @@
   CPU  the two symbols and every rejection before a launch; the register guard of csrc/acas2d_ppo_set.hip; the stack /
        member round trip and the population's config rules.
   GPU  a set collection equals K solo collections bit for bit; raw gradients and applied steps per member against the
-       float64 references of tests/learner_ref.py, with the criteria and bounds of tests/test_learner_kernels.py (the set
+       float64 references of tests/learner_ref.py, with the criteria and bounds of tests/learner_support.py (the set
        kernels run the solo kernels' body per member, so the same bounds apply), and against the solo update bit for bit
        where there is one wave per network; the trainer's first iteration against K solo PPOTrainer runs; a few iterations
        with the callbacks.
@@ -13,8 +13,6 @@ import ctypes as C
 import os
 import random
 import re
-import shutil
-import subprocess
 import types
 
 import numpy as np
@@ -22,15 +20,11 @@ import pytest
 
 import helpers as H
 import learner_ref as R
+import learner_support as LS
 
 torch = pytest.importorskip("torch")
 DEV = "cuda:0"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gym-acas2d_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SET_TRAFFIC = (1, 2, 3, 4, 8)          # the five float32 thread-per-env kernels
-# bounds of tests/test_learner_kernels.py, unchanged
-TAU, TAU0, TAU_M, TAU_V = 2e-5, 1e-6, 2e-5, 5e-5
 
 
 @pytest.fixture(scope="module")
@@ -113,10 +107,7 @@ def test_update_set_validation_needs_no_gpu(g):
     ints = dict(n_members=3, n_rows=64, obs_dim=8, apply=0)
 
     def call(**kw):
-        f = {n: a for n in names}
-        f.update(ints)
-        f.update(kw)
-        return L.acas2d_ppo_update_set_f32(C.byref(g.native.CPpoUpdateSet(**f)), None)
+        return L.acas2d_ppo_update_set_f32(*LS.host_update_set_args(g, a, **{**ints, **kw}))
 
     def rejects(msg, **kw):
         assert call(**kw) == -22, kw
@@ -135,33 +126,28 @@ def test_update_set_validation_needs_no_gpu(g):
     assert L.acas2d_ppo_update_set_f32(None, None) == -22
 
 
-@pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="needs hipcc")
+@H.needs_hipcc
 def test_ppo_update_set_kernels_stay_in_registers(tmp_path):
     """csrc/acas2d_ppo_set.hip: five gradient kernels and one apply kernel, no spill of either register file, no
     scratch, at most 256 VGPRs -- test_ppo_update_kernels_stay_in_registers' guard for the new unit."""
-    asm = tmp_path / "acas2d_ppo_set.s"
-    subprocess.run([HIPCC if os.path.exists(HIPCC) else "hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-S", "--cuda-device-only", "-o", str(asm),
-                    os.path.join(CSRC, "acas2d_ppo_set.hip")], check=True, capture_output=True)
-    kernels = re.findall(r"\.name:\s+(\S+)\n(.*?)\.wavefront_size", asm.read_text(), re.S)
-    assert len([n for n, _ in kernels if "ppo_grad_set_kernel" in n]) == 5
-    assert len([n for n, _ in kernels if "ppo_apply_set_kernel" in n]) == 1
+    _, kernels = H.kernel_metadata(tmp_path, "acas2d_ppo_set.hip")
+    assert len([k for k in kernels if "ppo_grad_set_kernel" in k.name]) == 5
+    assert len([k for k in kernels if "ppo_apply_set_kernel" in k.name]) == 1
     assert len(kernels) == 6
-    field = lambda body, k: int(re.search(r"\.%s:\s+(\d+)" % k, body).group(1))  # noqa: E731
-    for name, body in kernels:
-        print(name, {k: field(body, k) for k in ("vgpr_count", "sgpr_count")})
-        assert field(body, "vgpr_spill_count") == 0 and field(body, "sgpr_spill_count") == 0, name
-        assert field(body, "private_segment_fixed_size") == 0 and field(body, "vgpr_count") <= 256, name
+    for k in kernels:
+        print(k.name, {f: k.field(f) for f in ("vgpr_count", "sgpr_count")})
+        assert k.field("vgpr_spill_count") == 0 and k.field("sgpr_spill_count") == 0, k.name
+        assert k.field("private_segment_fixed_size") == 0 and k.field("vgpr_count") <= 256, k.name
 
 
 def test_set_collector_is_five_float32_kernels(g):
     """Mode::CollectSet is value 7 and is launched for one lane per env in float32 only."""
-    src = open(os.path.join(CSRC, "acas2d_kernels.hpp")).read()
+    src = open(os.path.join(H.CSRC, "acas2d_kernels.hpp")).read()
     modes = re.search(r"enum class Mode \{(.*?)\};", src, re.S).group(1)
     names = [ln.split(",")[0].strip() for ln in modes.splitlines() if ln.strip() and not ln.strip().startswith("//")]
     assert names == ["Latch", "Step", "Arena", "Rollout", "Policy", "Collect", "Eval", "CollectSet"]
-    assert "launch_collect_set<float>" in open(os.path.join(CSRC, "acas2d_f32.hip")).read()
-    assert "launch_collect_set" not in open(os.path.join(CSRC, "acas2d_f64.hip")).read()
+    assert "launch_collect_set<float>" in open(os.path.join(H.CSRC, "acas2d_f32.hip")).read()
+    assert "launch_collect_set" not in open(os.path.join(H.CSRC, "acas2d_f64.hip")).read()
 
 
 def test_actor_critic_set_round_trip(g):
@@ -222,23 +208,6 @@ def test_population_config_rules(g):
 
 
 # ---- GPU: the collector ------------------------------------------------------------------------------------------------
-def _members(g, D, K, seed=1, scale=40.0):
-    out = []
-    for k in range(K):
-        torch.manual_seed(seed + 17 * k)
-        pol = g.ActorCritic(D).to(DEV)
-        with torch.no_grad():
-            pol.action_net.weight.mul_(scale)            # away from SB3's near-zero head: actions that steer
-            pol.log_std.fill_(-0.7 + 0.2 * k)
-        out.append(pol)
-    return out
-
-
-_STATE = ("own_x", "own_y", "own_psi", "own_v", "goal_x", "goal_y", "trf_x", "trf_y", "trf_psi", "trf_v", "steps",
-          "total_reward", "episode", "status")
-_OUTPUTS = ("actions", "values", "logp", "reward", "done", "outcome", "episode_return", "episode_steps")   # + obs = nine
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("config", ("default", "small"))
 @pytest.mark.parametrize("EM", (64, 192))
@@ -253,7 +222,7 @@ def test_collect_set_equals_solo_collections_bitwise(gpu, N, EM, config):
     cfg = g.ACAS2DConfig(n_traffic=N, **kw)
     T = cfg.max_steps + 9
     seeds = [0x243F6A8885A308D3, 11, 2 ** 63 + 5]
-    pols = _members(g, D, K)
+    pols = LS.members(g, D, K)
     pset = g.ActorCriticSet.from_members(pols)
     off = 37
     env = g.ACAS2DVecEnv(K * EM, N, device=DEV, seed=21, env_offset=off, config=cfg)
@@ -268,9 +237,9 @@ def test_collect_set_equals_solo_collections_bitwise(gpu, N, EM, config):
         torch.cuda.synchronize()
         cols = slice(k * EM, (k + 1) * EM)
         assert H.bits_equal(out["obs"][:, cols], ref["obs"]), (k, "obs")
-        for name in _OUTPUTS:
+        for name in LS.OUTPUTS:
             assert H.bits_equal(out[name][:, cols], ref[name]), (k, name)
-        for name in _STATE:
+        for name in LS.STATE:
             assert H.bits_equal(getattr(env, name)[cols], getattr(solo, name)), (k, name)
         assert H.bits_equal(env.outputs["obs"][cols], solo.outputs["obs"]), k
         resets = out["done"][:, cols].sum(0)
@@ -289,7 +258,7 @@ def test_collect_set_routes_each_member_to_its_own_rows(gpu, N):
     """One member whose actor saturates at +1, one at -1, one in between: the rows of each, and only they, show it."""
     g = gpu
     K, EM, D, T = 3, 128, 5 + 3 * N, 20
-    pols = _members(g, D, K, scale=1.0)
+    pols = LS.members(g, D, K, scale=1.0)
     with torch.no_grad():
         for pol, b in zip(pols, (50.0, -50.0, 0.0)):
             pol.action_net.weight.zero_()
@@ -315,54 +284,6 @@ def test_collect_set_routes_each_member_to_its_own_rows(gpu, N):
 
 
 # ---- GPU: the update ---------------------------------------------------------------------------------------------------
-class _SharedBatch:
-    """One flat rollout buffer of n rows shared by K members with different parameters (tests/test_learner_kernels.py's
-    _Batch with a member dimension)."""
-
-    def __init__(self, g, D, K, n, seed):
-        rng = np.random.default_rng(seed)
-        self.g, self.rng, self.D, self.K, self.n = g, rng, D, K, n
-        f = lambda a: torch.as_tensor(np.asarray(a, np.float32), device=DEV).contiguous()  # noqa: E731
-        self.obs = f(rng.uniform(-1, 1, (n, D)))
-        self.act = f(rng.normal(0, 0.7, n))
-        self.adv, self.ret = f(rng.normal(0, 2, n)), f(rng.normal(2, 3, n))
-        self.old_logp = torch.zeros(n, dtype=torch.float32, device=DEV)
-        self.pols = _members(g, D, K, seed=seed)
-        self.pset = g.ActorCriticSet.from_members(self.pols)
-
-    def theta(self, k):
-        return torch.cat([self.pset.params[n][k].reshape(-1) for n in R.PARAM_NAMES]).double().cpu().numpy()
-
-    def host(self, rows):
-        i = rows.cpu().numpy()
-        return [t.cpu().numpy().astype(np.float64)[i] for t in (self.obs, self.act, self.old_logp, self.adv, self.ret)]
-
-    def set_old_logp(self, k, rows, mode, clip):
-        """_Batch.set_old_logp for member k on ITS rows: "mixed" the member's float64 log-prob plus N(0, 0.5) noise,
-        "first" the log-prob itself; ratios within 1e-4 of a clip edge are moved off it."""
-        i = rows.cpu().numpy()
-        lp = R.logp64(self.g.ActorCritic, self.D, self.theta(k), self.obs.cpu().numpy()[i], self.act.cpu().numpy()[i])
-        old = lp + (self.rng.normal(0, 0.5, len(i)) if mode == "mixed" else 0.0)
-        old = old.astype(np.float32).astype(np.float64)
-        r = np.exp(lp - old)
-        edge = (np.abs(r - (1 - clip)) < 1e-4) | (np.abs(r - (1 + clip)) < 1e-4)
-        old[edge] -= 1e-3
-        self.old_logp[rows] = torch.as_tensor(old.astype(np.float32), device=DEV)
-
-
-def _worst_ratio(errs, ref_all, tau0=TAU0):
-    return max((e - tau0 * ref_all) / max(m, 1e-300) for e, m in errs.values())
-
-
-def _assert_per_tensor(what, got, ref, segs, tau, tau0=TAU0):
-    errs, ref_all = R.per_tensor_errors(got, ref, segs)
-    bad = {n: (e, m) for n, (e, m) in errs.items() if not e <= tau * m + tau0 * ref_all}
-    obs = _worst_ratio(errs, ref_all, tau0)
-    print("%s: observed tau %.2e (bound %.0e, tau0 %.0e)" % (what, obs, tau, tau0))
-    assert not bad, (what, bad, ref_all)
-    return obs
-
-
 GRAD_CASES = [(D, B) for D in R.UPDATE_WIDTHS for B in (2, 65, 2085, 4096)]
 
 
@@ -377,23 +298,24 @@ def test_update_set_raw_gradients_per_member_vs_float64(gpu, D, B):
     K = 3
     clips, vfs = (0.1, 0.2, 0.3), (0.5, 0.25, 1.0)
     n = K * B + 317
-    bt = _SharedBatch(g, D, K, n, seed=3000 + 7 * D + B)
+    bt = LS.RolloutBatch(g, D, K, n, seed=3000 + 7 * D + B)
+    pset = bt.policy_set()
     segs = R.segments(bt.pols[0])
     worst = 0.0
     for mode, ent in (("mixed", 0.01), ("first", 0.0)):
         cfgs = [g.PPOConfig(ent_coef=ent, clip_range=clips[k], vf_coef=vfs[k], max_grad_norm=0.5) for k in range(K)]
         idx = torch.randperm(n, device=DEV)[:K * B].reshape(K, B).contiguous()       # disjoint rows
         for k in range(K):
-            bt.set_old_logp(k, idx[k], mode, clips[k])
-        fu = g.FusedUpdateSet(bt.pset, cfgs, bt.obs, bt.act, bt.old_logp, bt.adv, bt.ret)
+            bt.set_old_logp(LS.theta_of(pset, k), idx[k], mode, clips[k])
+        fu = g.FusedUpdateSet(pset, cfgs, bt.obs, bt.act, bt.old_logp, bt.adv, bt.ret)
         fu.step_count.copy_(torch.tensor([0, 5, 9999], dtype=torch.int32))
-        before = [bt.theta(k) for k in range(K)]
+        before = [LS.theta_of(pset, k) for k in range(K)]
         fu.step(idx, apply=False)
         torch.cuda.synchronize()
         assert fu.step_count.cpu().tolist() == [0, 5, 9999]                          # adam_step untouched
         assert float(fu.m.abs().max()) == 0.0 and float(fu.v.abs().max()) == 0.0     # nothing applied
         for k in range(K):
-            assert np.array_equal(bt.theta(k), before[k]), k
+            assert np.array_equal(LS.theta_of(pset, k), before[k]), k
             got = fu.grad[k].double().cpu().numpy()
             got[-1] -= ent                                # (the entropy term is added by the apply launch)
             obs, act, old, adv, ret = bt.host(idx[k])
@@ -406,11 +328,11 @@ def test_update_set_raw_gradients_per_member_vs_float64(gpu, D, B):
                 assert ((ratio > lo) & (ratio < hi)).sum() >= 1
             if mode == "first":
                 assert np.abs(ratio - 1).max() < 1e-5
-            worst = max(worst, _assert_per_tensor("raw gradient D=%d B=%d %s member %d" % (D, B, mode, k), got, ref, segs, TAU))
+            worst = max(worst, LS.assert_per_tensor("raw gradient D=%d B=%d %s member %d" % (D, B, mode, k), got, ref, segs, LS.TAU))
             st = fu.stats[k].double().cpu().numpy()
             print("  pg %.3e vs %.3e, vf %.3e vs %.3e" % (st[0], pg, st[1], vf))
             assert abs(st[0] - pg) <= 1e-5 * max(1.0, abs(pg)) and abs(st[1] - vf) <= 1e-5 * max(1.0, vf)
-    print("raw gradients D=%d B=%d: worst observed tau %.2e (bound %.0e)" % (D, B, worst, TAU))
+    print("raw gradients D=%d B=%d: worst observed tau %.2e (bound %.0e)" % (D, B, worst, LS.TAU))
 
 
 # B is not an input of the apply launch: one partial wave and one many-wave minibatch per width
@@ -431,11 +353,12 @@ def test_update_set_applied_steps_per_member_vs_float64(gpu, D, B):
     clips, vfs = (0.2, 0.1, 0.3, 0.2), (0.5, 0.25, 1.0, 0.5)
     b1, b2, eps = 0.9, 0.999, 1e-5
     n = K * B + 317
-    bt = _SharedBatch(g, D, K, n, seed=4000 + 7 * D + B)
+    bt = LS.RolloutBatch(g, D, K, n, seed=4000 + 7 * D + B)
+    pset = bt.policy_set()
     segs = R.segments(bt.pols[0])
     cfgs = [g.PPOConfig(ent_coef=ents[k], max_grad_norm=norms[k], learning_rate=lrs[k], clip_range=clips[k], vf_coef=vfs[k])
             for k in range(K)]
-    fu = g.FusedUpdateSet(bt.pset, cfgs, bt.obs, bt.act, bt.old_logp, bt.adv, bt.ret)
+    fu = g.FusedUpdateSet(pset, cfgs, bt.obs, bt.act, bt.old_logp, bt.adv, bt.ret)
     fu.step_count.copy_(torch.tensor(starts, dtype=torch.int32))
     rng = np.random.default_rng(B)
     m_pre = rng.normal(0, 1e-2, fu.m.shape[1])                      # moments as a long run leaves them: v >= m^2
@@ -445,8 +368,8 @@ def test_update_set_applied_steps_per_member_vs_float64(gpu, D, B):
     for step in range(2):
         idx = torch.randperm(n, device=DEV)[:K * B].reshape(K, B).contiguous()
         for k in range(K):
-            bt.set_old_logp(k, idx[k], "mixed", clips[k])           # from the member's CURRENT parameters
-        theta0 = [bt.theta(k) for k in range(K)]
+            bt.set_old_logp(LS.theta_of(pset, k), idx[k], "mixed", clips[k])           # from the member's CURRENT parameters
+        theta0 = [LS.theta_of(pset, k) for k in range(K)]
         m0, v0 = fu.m.double().cpu().numpy(), fu.v.double().cpu().numpy()
         s0 = fu.step_count.cpu().tolist()
         fu.step(idx)
@@ -466,9 +389,9 @@ def test_update_set_applied_steps_per_member_vs_float64(gpu, D, B):
                                          ("vf", st[5], vf, 1e-5 * max(1.0, vf))):
                 worst[key] = max(worst[key], abs(got_ - ref_) / tol)
                 assert abs(got_ - ref_) <= tol, (what, key, got_, ref_)
-            worst["m"] = max(worst["m"], _assert_per_tensor("m " + what, m1[k], m_ref, segs, TAU_M))
-            worst["v"] = max(worst["v"], _assert_per_tensor("v " + what, v1[k], v_ref, segs, TAU_V))
-            theta1 = bt.theta(k)
+            worst["m"] = max(worst["m"], LS.assert_per_tensor("m " + what, m1[k], m_ref, segs, LS.TAU_M))
+            worst["v"] = max(worst["v"], LS.assert_per_tensor("v " + what, v1[k], v_ref, segs, LS.TAU_V))
+            theta1 = LS.theta_of(pset, k)
             if lrs[k] == 0.0:                             # isolation: a member that does not learn keeps every bit
                 assert np.array_equal(theta1, theta0[k]), what
                 assert np.abs(m1[k] - m0[k]).max() > 0
@@ -480,7 +403,7 @@ def test_update_set_applied_steps_per_member_vs_float64(gpu, D, B):
             assert np.median(np.abs(theta1 - theta0[k]) / lrs[k]) > 0.05, what         # the step was taken
     print("applied steps D=%d B=%d: worst param excess %.2e lr (bound 1e-2), m tau %.2e (bound %.0e), v tau %.2e (bound "
           "%.0e), norm / pg / vf at %.2f / %.2f / %.2f of their 1e-5 bounds"
-          % (D, B, worst["param"], worst["m"], TAU_M, worst["v"], TAU_V, worst["norm"], worst["pg"], worst["vf"]))
+          % (D, B, worst["param"], worst["m"], LS.TAU_M, worst["v"], LS.TAU_V, worst["norm"], worst["pg"], worst["vf"]))
 
 
 BITWISE_CASES = [(D, B) for D in R.UPDATE_WIDTHS for B in (2, 63, 64)]
@@ -503,17 +426,18 @@ def test_update_set_single_wave_equals_solo_bitwise(gpu, D, B):
     cfgs = [g.PPOConfig(**{f: v[k] for f, v in hyper.items()}) for k in range(K)]
     probes = [g.PPOConfig(**{**{f: v[k] for f, v in hyper.items()}, "max_grad_norm": -1.0}) for k in range(K)]
     n = K * B + 317
-    bt = _SharedBatch(g, D, K, n, seed=5000 + 7 * D + B)
+    bt = LS.RolloutBatch(g, D, K, n, seed=5000 + 7 * D + B)
+    pset = bt.policy_set()
     idx = torch.randperm(n, device=DEV)[:K * B].reshape(K, B).contiguous()           # disjoint rows
     for k in range(K):
-        bt.set_old_logp(k, idx[k], "mixed", hyper["clip_range"][k])
-    solo = [bt.pset.member(k) for k in range(K)]                                     # copies, before anything is applied
+        bt.set_old_logp(LS.theta_of(pset, k), idx[k], "mixed", hyper["clip_range"][k])
+    solo = [pset.member(k) for k in range(K)]                                     # copies, before anything is applied
     bufs = (bt.obs, bt.act, bt.old_logp, bt.adv, bt.ret)
 
     def same(what, a, b):
         assert a.shape == b.shape and torch.equal(a, b), (what, D, B, float((a.double() - b.double()).abs().max()))
 
-    fs = g.FusedUpdateSet(bt.pset, cfgs, *bufs)
+    fs = g.FusedUpdateSet(pset, cfgs, *bufs)
     fs.step(idx, apply=False)
     for k in range(K):
         fu = g.FusedUpdate(solo[k], probes[k], *bufs)
@@ -522,7 +446,7 @@ def test_update_set_single_wave_equals_solo_bitwise(gpu, D, B):
         same("raw gradient, member %d" % k, fs.grad[k], fu.grad)
         same("raw losses, member %d" % k, fs.stats[k, 0:2], fu.stats[0:2])
 
-    fs = g.FusedUpdateSet(bt.pset, cfgs, *bufs)
+    fs = g.FusedUpdateSet(pset, cfgs, *bufs)
     fus = [g.FusedUpdate(solo[k], cfgs[k], *bufs) for k in range(K)]
     starts = (0, 5, 9999)
     fs.step_count.copy_(torch.tensor(starts, dtype=torch.int32))
@@ -536,14 +460,14 @@ def test_update_set_single_wave_equals_solo_bitwise(gpu, D, B):
             what = "member %d, applied step %d: " % (k, step + 1)
             same(what + "grad", fs.grad[k], fus[k].grad)
             for name in R.PARAM_NAMES:
-                same(what + name, bt.pset.params[name][k], solo[k].get_parameter(name).detach())
+                same(what + name, pset.params[name][k], solo[k].get_parameter(name).detach())
             same(what + "m", fs.m[k], fus[k].m)
             same(what + "v", fs.v[k], fus[k].v)
             same(what + "step_count", fs.step_count[k:k + 1], fus[k].step_count)
             for slot in (2, 4, 5):
                 same(what + "stats[%d]" % slot, fs.stats[k, slot], fus[k].stats[slot])
     assert fs.step_count.cpu().tolist() == [s + 3 for s in starts]
-    moved = max(float((bt.pset.params[R.PARAM_NAMES[2]][k] - bt.pols[k].get_parameter(R.PARAM_NAMES[2]).detach()).abs().max())
+    moved = max(float((pset.params[R.PARAM_NAMES[2]][k] - bt.pols[k].get_parameter(R.PARAM_NAMES[2]).detach()).abs().max())
                 for k in range(K))
     assert moved > 0.0                                                               # the steps were taken
 

@@ -6,7 +6,7 @@ ppo.PopulationTrainer(group=True)).  The recipes are tests/test_population.py's 
        nine Mode::CollectSet kernels of the float32 unit; the host classes' choice of entry point.
   GPU  a group set collection equals K solo group collections bit for bit (and, at n_traffic = 8, the thread-per-env set
        collection); raw gradients and applied steps per member against the float64 references of tests/learner_ref.py with
-       the bounds of tests/test_learner_kernels.py (the set kernel runs the solo body per member, so the solo bounds
+       the bounds of tests/learner_support.py (the set kernel runs the solo body per member, so the solo bounds
        apply), and against the solo wide update bit for bit where there is one workgroup per network; isolation between
        members; the trainer's first iteration against K solo PPOTrainer runs; a few iterations with the callbacks.
 Every criterion prints what it observed.
@@ -18,8 +18,6 @@ import ctypes as C
 import os
 import random
 import re
-import shutil
-import subprocess
 import types
 
 import numpy as np
@@ -27,16 +25,12 @@ import pytest
 
 import helpers as H
 import learner_ref as R
-import test_population as P
+import learner_support as LS
 
 torch = pytest.importorskip("torch")
-DEV = P.DEV
-ROOT, CSRC, HIPCC = P.ROOT, P.CSRC, P.HIPCC
+DEV = "cuda:0"
 GROUP_SET_TRAFFIC = (8, 16, 32, 64)    # the four group-cooperative work shapes (4,2) (4,4) (4,8) (4,16)
 WIDE = (53, 101, 197)
-# bounds of tests/test_learner_kernels.py, unchanged
-TAU, TAU0, TAU_M, TAU_V = 2e-5, 1e-6, 2e-5, 5e-5
-needs_hipcc = pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="needs hipcc")
 
 
 @pytest.fixture(scope="module")
@@ -57,7 +51,7 @@ def test_wide_set_entry_points_are_exported_and_declared(g):
     L = g.native.lib()
     for name in ("acas2d_collect_set_group_f32", "acas2d_ppo_update_wide_set_f32"):
         assert name in g.native.EXPORTS and getattr(L, name)
-    header = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "acas2d.h")).read())
+    header = re.sub(r"\s+", " ", open(os.path.join(H.ROOT, "include", "acas2d.h")).read())
     decl = lambda name: re.search(r"int %s\(([^)]*)\);" % name, header).group(1)  # noqa: E731
     assert decl("acas2d_collect_set_group_f32") == decl("acas2d_collect_set_f32")          # the sibling's signature
     assert decl("acas2d_ppo_update_wide_set_f32") == "const Acas2dPpoUpdateSet *u, void *stream"
@@ -134,10 +128,7 @@ def test_update_wide_set_validation_needs_no_gpu(g):
     ints = dict(n_members=3, n_rows=64, obs_dim=53, apply=0)
 
     def call(**kw):
-        f = {n: a for n in names}
-        f.update(ints)
-        f.update(kw)
-        return L.acas2d_ppo_update_wide_set_f32(C.byref(g.native.CPpoUpdateSet(**f)), None)
+        return L.acas2d_ppo_update_wide_set_f32(*LS.host_update_set_args(g, a, **{**ints, **kw}))
 
     def rejects(msg, **kw):
         assert call(**kw) == -22, kw
@@ -159,66 +150,51 @@ def test_update_wide_set_validation_needs_no_gpu(g):
     assert L.acas2d_ppo_update_wide_set_f32(None, None) == -22 and b"NULL argument" in L.acas2d_last_error()
 
 
-def _device_asm(tmp_path, unit, flags=()):
-    asm = tmp_path / (unit + ".s")
-    subprocess.run([HIPCC if os.path.exists(HIPCC) else "hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, *flags, "-S", "--cuda-device-only", "-o", str(asm),
-                    os.path.join(CSRC, unit)], check=True, capture_output=True)
-    return asm.read_text()
-
-
-_field = lambda e, k: int(re.search(r"\.%s:\s+(\d+)" % k, e).group(1))  # noqa: E731
-
-
-@needs_hipcc
+@H.needs_hipcc
 def test_wide_set_update_kernels_stay_in_registers_and_lds(g, tmp_path):
     """csrc/acas2d_ppo_wide_set.hip: three gradient kernels of 256 threads (the apply kernel is acas2d_ppo_set.hip's), no
     VGPR or SGPR spill, no scratch, and acas2d_ppo_wide_lds_bytes -- the figure the launch uses -- plus the kernel's static
     LDS within gfx950's 160 KB per workgroup.  acas2d_ppo_set.hip still holds six kernels with launch_ppo_apply_set in it."""
-    meta = _device_asm(tmp_path, "acas2d_ppo_wide_set.hip").split("amdhsa.kernels:")[1]
-    kernels = [e for e in re.split(r"\n  - \.agpr_count:", meta) if ".name:" in e]
+    _, kernels = H.kernel_metadata(tmp_path, "acas2d_ppo_wide_set.hip")
     assert len(kernels) == 3
     L = g.native.lib()
     static = {}
-    for e in kernels:
-        name = re.search(r"\.name:\s+(\S+)", e).group(1)
+    for k in kernels:
+        name = k.name
         assert "ppo_grad_wide_set_kernel" in name
-        assert _field(e, "vgpr_spill_count") == 0 and _field(e, "sgpr_spill_count") == 0, name
-        assert _field(e, "private_segment_fixed_size") == 0 and _field(e, "vgpr_count") <= 256, name
-        assert _field(e, "max_flat_workgroup_size") == 256, name
-        static[int(re.search(r"kernelILi(\d+)E", name).group(1))] = _field(e, "group_segment_fixed_size")
-        print(name, "vgpr", _field(e, "vgpr_count"), "sgpr", _field(e, "sgpr_count"))
+        assert k.field("vgpr_spill_count") == 0 and k.field("sgpr_spill_count") == 0, name
+        assert k.field("private_segment_fixed_size") == 0 and k.field("vgpr_count") <= 256, name
+        assert k.field("max_flat_workgroup_size") == 256, name
+        static[int(re.search(r"kernelILi(\d+)E", name).group(1))] = k.field("group_segment_fixed_size")
+        print(name, "vgpr", k.field("vgpr_count"), "sgpr", k.field("sgpr_count"))
     assert sorted(static) == list(WIDE)
     for D in WIDE:
         lds = L.acas2d_ppo_wide_lds_bytes(D)
         assert (4 * 64 * 65 + 64 * D) * 4 <= lds and lds + static[D] <= 160 * 1024, (D, lds, static[D])
         print("D = %d: %d bytes of dynamic LDS + %d static" % (D, lds, static[D]))
-    text = _device_asm(tmp_path, "acas2d_ppo_set.hip")
-    assert len(re.findall(r"\.name:\s+(\S+)\n(.*?)\.wavefront_size", text, re.S)) == 6
+    assert len(H.kernel_metadata(tmp_path, "acas2d_ppo_set.hip")[1]) == 6
 
 
-@needs_hipcc
+@H.needs_hipcc
 def test_set_collector_is_nine_float32_kernels(tmp_path):
     """Mode::CollectSet (value 7) in the float32 unit: the five (C,1) shapes and the four group shapes, each without a VGPR
     spill or a private segment and under the unit's 400 SGPR spills; their registers beside Mode::Collect's (value 5) at
     the same shapes."""
-    text = _device_asm(tmp_path, "acas2d_f32.hip", ("-ffp-contract=off", "-fno-slp-vectorize", "-mllvm",
-                                                     "-amdgpu-kernarg-preload-count=8"))
-    kernels = re.findall(r"\.name:\s+(\S+)\n(.*?)\.wavefront_size", text, re.S)
+    _, kernels = H.kernel_metadata(tmp_path, "acas2d_f32.hip")
     by_mode = {5: {}, 7: {}}
-    for name, body in kernels:
-        m = re.match(r"_ZN6acas2d11step_kernelIfLi(\d+)ELi(\d+)ELb1ELb1ELNS_4ModeE([57])EEEv", name)
+    for k in kernels:
+        m = re.match(r"_ZN6acas2d11step_kernelIfLi(\d+)ELi(\d+)ELb1ELb1ELNS_4ModeE([57])EEEv", k.name)
         if m:
-            by_mode[int(m.group(3))][(int(m.group(1)), int(m.group(2)))] = body
-    assert len([n for n, _ in kernels if "ModeE7EEEv" in n]) == 9
+            by_mode[int(m.group(3))][(int(m.group(1)), int(m.group(2)))] = k
+    assert len([k for k in kernels if "ModeE7EEEv" in k.name]) == 9
     assert sorted(by_mode[7]) == sorted([(1, 1), (2, 1), (3, 1), (4, 1), (8, 1), (4, 2), (4, 4), (4, 8), (4, 16)])
-    for shape, body in sorted(by_mode[7].items()):
+    for shape, k in sorted(by_mode[7].items()):
         solo = by_mode[5][shape]
         print("shape %s: CollectSet vgpr %d sgpr %d sgpr spills %d | Collect vgpr %d sgpr %d sgpr spills %d"
-              % (shape, _field(body, "vgpr_count"), _field(body, "sgpr_count"), _field(body, "sgpr_spill_count"),
-                 _field(solo, "vgpr_count"), _field(solo, "sgpr_count"), _field(solo, "sgpr_spill_count")))
-        assert _field(body, "vgpr_spill_count") == 0 and _field(body, "private_segment_fixed_size") == 0, shape
-        assert _field(body, "sgpr_spill_count") < 400, shape
+              % (shape, k.field("vgpr_count"), k.field("sgpr_count"), k.field("sgpr_spill_count"),
+                 solo.field("vgpr_count"), solo.field("sgpr_count"), solo.field("sgpr_spill_count")))
+        assert k.field("vgpr_spill_count") == 0 and k.field("private_segment_fixed_size") == 0, shape
+        assert k.field("sgpr_spill_count") < 400, shape
 
 
 def test_host_classes_pick_the_wide_set_entries(g):
@@ -262,7 +238,7 @@ def test_collect_set_group_equals_solo_group_collections_bitwise(gpu, N, EM, con
     cfg = g.ACAS2DConfig(n_traffic=N, **kw)
     T = cfg.max_steps + 9
     seeds = [0x243F6A8885A308D3, 11, 2 ** 63 + 5]
-    pols = P._members(g, D, K)
+    pols = LS.members(g, D, K)
     pset = g.ActorCriticSet.from_members(pols)
     off = 37
     env = g.ACAS2DVecEnv(K * EM, N, device=DEV, seed=21, env_offset=off, config=cfg)
@@ -276,9 +252,9 @@ def test_collect_set_group_equals_solo_group_collections_bitwise(gpu, N, EM, con
         torch.cuda.synchronize()
         cols = slice(k * EM, (k + 1) * EM)
         assert H.bits_equal(out["obs"][:, cols], ref["obs"]), (k, "obs")
-        for name in P._OUTPUTS:
+        for name in LS.OUTPUTS:
             assert H.bits_equal(out[name][:, cols], ref[name]), (k, name)
-        for name in P._STATE:
+        for name in LS.STATE:
             assert H.bits_equal(getattr(env, name)[cols], getattr(solo, name)), (k, name)
         assert H.bits_equal(env.outputs["obs"][cols], solo.outputs["obs"]), k
         resets = out["done"][:, cols].sum(0)
@@ -294,7 +270,7 @@ def test_collect_set_group_equals_thread_per_env_set_at_8(gpu, EM):
     the state."""
     g = gpu
     K, N, T = 3, 8, 60
-    pols = P._members(g, 5 + 3 * N, K)
+    pols = LS.members(g, 5 + 3 * N, K)
     pset = g.ActorCriticSet.from_members(pols)
     runs = []
     for group in (True, False):
@@ -303,9 +279,9 @@ def test_collect_set_group_equals_thread_per_env_set_at_8(gpu, EM):
         runs.append((env, env.collect_set(pset, T, [5, 6, 7], noise_step=3, group=group)))
     torch.cuda.synchronize()
     (ea, a), (eb, b) = runs
-    for name in P._OUTPUTS + ("obs",):
+    for name in LS.OUTPUTS + ("obs",):
         assert H.bits_equal(a[name], b[name]), name
-    for name in P._STATE:
+    for name in LS.STATE:
         assert H.bits_equal(getattr(ea, name), getattr(eb, name)), name
     assert H.bits_equal(ea.outputs["obs"], eb.outputs["obs"])
     assert int(a["done"].sum(0).min()) >= 1
@@ -318,7 +294,7 @@ def test_collect_set_group_routes_each_member_to_its_own_rows(gpu, N):
     """One member whose actor saturates at +1, one at -1, one in between: the rows of each, and only they, show it."""
     g = gpu
     K, EM, D, T = 3, 128, 5 + 3 * N, 20
-    pols = P._members(g, D, K, scale=1.0)
+    pols = LS.members(g, D, K, scale=1.0)
     with torch.no_grad():
         for pol, b in zip(pols, (50.0, -50.0, 0.0)):
             pol.action_net.weight.zero_()
@@ -357,24 +333,25 @@ def test_update_wide_set_raw_gradients_per_member_vs_float64(gpu, D, B):
     K = 3
     clips, vfs = (0.1, 0.2, 0.3), (0.5, 0.25, 1.0)
     n = K * B + 317
-    bt = P._SharedBatch(g, D, K, n, seed=3000 + 7 * D + B)
+    bt = LS.RolloutBatch(g, D, K, n, seed=3000 + 7 * D + B)
+    pset = bt.policy_set()
     segs = R.segments(bt.pols[0])
     worst = 0.0
     for mode, ent in (("mixed", 0.01), ("first", 0.0)):
         cfgs = [g.PPOConfig(ent_coef=ent, clip_range=clips[k], vf_coef=vfs[k], max_grad_norm=0.5) for k in range(K)]
         idx = torch.randperm(n, device=DEV)[:K * B].reshape(K, B).contiguous()       # disjoint rows
         for k in range(K):
-            bt.set_old_logp(k, idx[k], mode, clips[k])
-        fu = g.FusedUpdateSet(bt.pset, cfgs, bt.obs, bt.act, bt.old_logp, bt.adv, bt.ret)
+            bt.set_old_logp(LS.theta_of(pset, k), idx[k], mode, clips[k])
+        fu = g.FusedUpdateSet(pset, cfgs, bt.obs, bt.act, bt.old_logp, bt.adv, bt.ret)
         assert fu.entry == "acas2d_ppo_update_wide_set_f32"
         fu.step_count.copy_(torch.tensor([0, 5, 9999], dtype=torch.int32))
-        before = [bt.theta(k) for k in range(K)]
+        before = [LS.theta_of(pset, k) for k in range(K)]
         fu.step(idx, apply=False)
         torch.cuda.synchronize()
         assert fu.step_count.cpu().tolist() == [0, 5, 9999]                          # adam_step untouched
         assert float(fu.m.abs().max()) == 0.0 and float(fu.v.abs().max()) == 0.0     # nothing applied
         for k in range(K):
-            assert np.array_equal(bt.theta(k), before[k]), k
+            assert np.array_equal(LS.theta_of(pset, k), before[k]), k
             got = fu.grad[k].double().cpu().numpy()
             got[-1] -= ent                                # (the entropy term is added by the apply launch)
             obs, act, old, adv, ret = bt.host(idx[k])
@@ -387,11 +364,11 @@ def test_update_wide_set_raw_gradients_per_member_vs_float64(gpu, D, B):
                 assert ((ratio > lo) & (ratio < hi)).sum() >= 1
             if mode == "first":
                 assert np.abs(ratio - 1).max() < 1e-5
-            worst = max(worst, P._assert_per_tensor("raw gradient D=%d B=%d %s member %d" % (D, B, mode, k), got, ref, segs, TAU))
+            worst = max(worst, LS.assert_per_tensor("raw gradient D=%d B=%d %s member %d" % (D, B, mode, k), got, ref, segs, LS.TAU))
             st = fu.stats[k].double().cpu().numpy()
             print("  pg %.3e vs %.3e, vf %.3e vs %.3e" % (st[0], pg, st[1], vf))
             assert abs(st[0] - pg) <= 1e-5 * max(1.0, abs(pg)) and abs(st[1] - vf) <= 1e-5 * max(1.0, vf)
-    print("raw gradients D=%d B=%d: worst observed tau %.2e (bound %.0e)" % (D, B, worst, TAU))
+    print("raw gradients D=%d B=%d: worst observed tau %.2e (bound %.0e)" % (D, B, worst, LS.TAU))
 
 
 APPLY_CASES = [(D, B) for D in WIDE for B in (65, 2085)]
@@ -409,11 +386,12 @@ def test_update_wide_set_applied_steps_per_member_vs_float64(gpu, D, B):
     clips, vfs = (0.2, 0.1, 0.3, 0.2), (0.5, 0.25, 1.0, 0.5)
     b1, b2, eps = 0.9, 0.999, 1e-5
     n = K * B + 317
-    bt = P._SharedBatch(g, D, K, n, seed=4000 + 7 * D + B)
+    bt = LS.RolloutBatch(g, D, K, n, seed=4000 + 7 * D + B)
+    pset = bt.policy_set()
     segs = R.segments(bt.pols[0])
     cfgs = [g.PPOConfig(ent_coef=ents[k], max_grad_norm=norms[k], learning_rate=lrs[k], clip_range=clips[k], vf_coef=vfs[k])
             for k in range(K)]
-    fu = g.FusedUpdateSet(bt.pset, cfgs, bt.obs, bt.act, bt.old_logp, bt.adv, bt.ret)
+    fu = g.FusedUpdateSet(pset, cfgs, bt.obs, bt.act, bt.old_logp, bt.adv, bt.ret)
     fu.step_count.copy_(torch.tensor(starts, dtype=torch.int32))
     rng = np.random.default_rng(B)
     m_pre = rng.normal(0, 1e-2, fu.m.shape[1])                      # moments as a long run leaves them: v >= m^2
@@ -423,8 +401,8 @@ def test_update_wide_set_applied_steps_per_member_vs_float64(gpu, D, B):
     for step in range(2):
         idx = torch.randperm(n, device=DEV)[:K * B].reshape(K, B).contiguous()
         for k in range(K):
-            bt.set_old_logp(k, idx[k], "mixed", clips[k])           # from the member's CURRENT parameters
-        theta0 = [bt.theta(k) for k in range(K)]
+            bt.set_old_logp(LS.theta_of(pset, k), idx[k], "mixed", clips[k])           # from the member's CURRENT parameters
+        theta0 = [LS.theta_of(pset, k) for k in range(K)]
         m0, v0 = fu.m.double().cpu().numpy(), fu.v.double().cpu().numpy()
         s0 = fu.step_count.cpu().tolist()
         fu.step(idx)
@@ -444,9 +422,9 @@ def test_update_wide_set_applied_steps_per_member_vs_float64(gpu, D, B):
                                          ("vf", st[5], vf, 1e-5 * max(1.0, vf))):
                 worst[key] = max(worst[key], abs(got_ - ref_) / tol)
                 assert abs(got_ - ref_) <= tol, (what, key, got_, ref_)
-            worst["m"] = max(worst["m"], P._assert_per_tensor("m " + what, m1[k], m_ref, segs, TAU_M))
-            worst["v"] = max(worst["v"], P._assert_per_tensor("v " + what, v1[k], v_ref, segs, TAU_V))
-            theta1 = bt.theta(k)
+            worst["m"] = max(worst["m"], LS.assert_per_tensor("m " + what, m1[k], m_ref, segs, LS.TAU_M))
+            worst["v"] = max(worst["v"], LS.assert_per_tensor("v " + what, v1[k], v_ref, segs, LS.TAU_V))
+            theta1 = LS.theta_of(pset, k)
             if lrs[k] == 0.0:                             # isolation: a member that does not learn keeps every bit
                 assert np.array_equal(theta1, theta0[k]), what
                 assert np.abs(m1[k] - m0[k]).max() > 0
@@ -458,7 +436,7 @@ def test_update_wide_set_applied_steps_per_member_vs_float64(gpu, D, B):
             assert np.median(np.abs(theta1 - theta0[k]) / lrs[k]) > 0.05, what         # the step was taken
     print("applied steps D=%d B=%d: worst param excess %.2e lr (bound 1e-2), m tau %.2e (bound %.0e), v tau %.2e (bound "
           "%.0e), norm / pg / vf at %.2f / %.2f / %.2f of their 1e-5 bounds"
-          % (D, B, worst["param"], worst["m"], TAU_M, worst["v"], TAU_V, worst["norm"], worst["pg"], worst["vf"]))
+          % (D, B, worst["param"], worst["m"], LS.TAU_M, worst["v"], LS.TAU_V, worst["norm"], worst["pg"], worst["vf"]))
 
 
 BITWISE_CASES = [(D, B) for D in WIDE for B in (2, 63, 64)]
@@ -480,17 +458,18 @@ def test_update_wide_set_single_workgroup_equals_solo_bitwise(gpu, D, B):
     cfgs = [g.PPOConfig(**{f: v[k] for f, v in hyper.items()}) for k in range(K)]
     probes = [g.PPOConfig(**{**{f: v[k] for f, v in hyper.items()}, "max_grad_norm": -1.0}) for k in range(K)]
     n = K * B + 317
-    bt = P._SharedBatch(g, D, K, n, seed=5000 + 7 * D + B)
+    bt = LS.RolloutBatch(g, D, K, n, seed=5000 + 7 * D + B)
+    pset = bt.policy_set()
     idx = torch.randperm(n, device=DEV)[:K * B].reshape(K, B).contiguous()           # disjoint rows
     for k in range(K):
-        bt.set_old_logp(k, idx[k], "mixed", hyper["clip_range"][k])
-    solo = [bt.pset.member(k) for k in range(K)]                                     # copies, before anything is applied
+        bt.set_old_logp(LS.theta_of(pset, k), idx[k], "mixed", hyper["clip_range"][k])
+    solo = [pset.member(k) for k in range(K)]                                     # copies, before anything is applied
     bufs = (bt.obs, bt.act, bt.old_logp, bt.adv, bt.ret)
 
     def same(what, a, b):
         assert a.shape == b.shape and torch.equal(a, b), (what, D, B, float((a.double() - b.double()).abs().max()))
 
-    fs = g.FusedUpdateSet(bt.pset, cfgs, *bufs)
+    fs = g.FusedUpdateSet(pset, cfgs, *bufs)
     assert fs.entry == "acas2d_ppo_update_wide_set_f32"
     fs.step(idx, apply=False)
     for k in range(K):
@@ -501,7 +480,7 @@ def test_update_wide_set_single_workgroup_equals_solo_bitwise(gpu, D, B):
         same("raw gradient, member %d" % k, fs.grad[k], fu.grad)
         same("raw losses, member %d" % k, fs.stats[k, 0:2], fu.stats[0:2])
 
-    fs = g.FusedUpdateSet(bt.pset, cfgs, *bufs)
+    fs = g.FusedUpdateSet(pset, cfgs, *bufs)
     fus = [g.FusedUpdate(solo[k], cfgs[k], *bufs) for k in range(K)]
     starts = (0, 5, 9999)
     fs.step_count.copy_(torch.tensor(starts, dtype=torch.int32))
@@ -515,14 +494,14 @@ def test_update_wide_set_single_workgroup_equals_solo_bitwise(gpu, D, B):
             what = "member %d, applied step %d: " % (k, step + 1)
             same(what + "grad", fs.grad[k], fus[k].grad)
             for name in R.PARAM_NAMES:
-                same(what + name, bt.pset.params[name][k], solo[k].get_parameter(name).detach())
+                same(what + name, pset.params[name][k], solo[k].get_parameter(name).detach())
             same(what + "m", fs.m[k], fus[k].m)
             same(what + "v", fs.v[k], fus[k].v)
             same(what + "step_count", fs.step_count[k:k + 1], fus[k].step_count)
             for slot in (2, 4, 5):
                 same(what + "stats[%d]" % slot, fs.stats[k, slot], fus[k].stats[slot])
     assert fs.step_count.cpu().tolist() == [s + 3 for s in starts]
-    moved = max(float((bt.pset.params[R.PARAM_NAMES[2]][k] - bt.pols[k].get_parameter(R.PARAM_NAMES[2]).detach()).abs().max())
+    moved = max(float((pset.params[R.PARAM_NAMES[2]][k] - bt.pols[k].get_parameter(R.PARAM_NAMES[2]).detach()).abs().max())
                 for k in range(K))
     assert moved > 0.0                                                               # the steps were taken
     print("D=%d B=%d: set and solo wide updates agree in every bit over the raw gradient and three applied steps" % (D, B))
@@ -537,13 +516,14 @@ def test_update_wide_set_writes_only_its_members_rows(gpu):
     g = gpu
     D, B, K = 197, 129, 3
     n = K * B + 317
-    bt = P._SharedBatch(g, D, K, n, seed=77)
+    bt = LS.RolloutBatch(g, D, K, n, seed=77)
+    pset = bt.policy_set()
     idx = torch.randperm(n, device=DEV)[:K * B].reshape(K, B).contiguous()
     bt.adv[idx[1]] = 2.0
     for k in range(K):
-        bt.set_old_logp(k, idx[k], "mixed", 0.2)
+        bt.set_old_logp(LS.theta_of(pset, k), idx[k], "mixed", 0.2)
     cfgs = [g.PPOConfig(ent_coef=0.0, learning_rate=(3e-4, 1e-3, 1e-4)[k]) for k in range(K)]
-    fu = g.FusedUpdateSet(bt.pset, cfgs, bt.obs, bt.act, bt.old_logp, bt.adv, bt.ret)
+    fu = g.FusedUpdateSet(pset, cfgs, bt.obs, bt.act, bt.old_logp, bt.adv, bt.ret)
     W = fu.grad.shape[1]
     SENT_F, SENT_I = -12345.5, -777
     big = {name: torch.full((K + 2, width), SENT_F, dtype=torch.float32, device=DEV)
@@ -588,16 +568,17 @@ def test_update_wide_set_hyper_row_reaches_only_what_it_enters(gpu):
     g = gpu
     D, B, K = 197, 64, 3
     n = 2 * B + 100
-    bt = P._SharedBatch(g, D, K, n, seed=91)
+    bt = LS.RolloutBatch(g, D, K, n, seed=91)
+    pset = bt.policy_set()
     for name in R.PARAM_NAMES:
-        bt.pset.params[name][2].copy_(bt.pset.params[name][0])
+        pset.params[name][2].copy_(pset.params[name][0])
     rows = torch.randperm(n, device=DEV)[:2 * B].reshape(2, B)
     idx = torch.stack([rows[0], rows[1], rows[0]]).contiguous()
-    bt.set_old_logp(0, idx[0], "mixed", 0.2)
-    bt.set_old_logp(1, idx[1], "mixed", 0.2)
+    bt.set_old_logp(LS.theta_of(pset, 0), idx[0], "mixed", 0.2)
+    bt.set_old_logp(LS.theta_of(pset, 1), idx[1], "mixed", 0.2)
     cfgs = [g.PPOConfig(clip_range=0.2, vf_coef=(0.5, 0.25, 1.0)[k], ent_coef=(0.0, 0.01, 0.02)[k],
                         max_grad_norm=(0.5, 1e6, 0.3)[k], learning_rate=(3e-4, 1e-3, 1e-4)[k]) for k in range(K)]
-    fu = g.FusedUpdateSet(bt.pset, cfgs, bt.obs, bt.act, bt.old_logp, bt.adv, bt.ret)
+    fu = g.FusedUpdateSet(pset, cfgs, bt.obs, bt.act, bt.old_logp, bt.adv, bt.ret)
     fu.step(idx, apply=False)
     torch.cuda.synchronize()
     net = 64 * D + 64 + 64 * 64 + 64 + 64 + 1

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import helpers as H
+import learner_support as LS
 
 
 bits_equal = H.bits_equal
@@ -237,15 +238,6 @@ def test_captured_update_equals_the_op_by_op_update():
     assert abs(sg["value_loss"] - se["value_loss"]) < 0.05 * abs(se["value_loss"])
 
 
-def _random_actor_critic(g, D, seed):
-    torch.manual_seed(seed)
-    pol = g.ActorCritic(D).to("cuda:0")
-    with torch.no_grad():
-        pol.action_net.weight.mul_(40.0)            # away from SB3's near-zero init: the mean depends on the observation
-        pol.log_std.fill_(-0.7)
-    return pol
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("dtype_name,N,E,T", (("float32", 1, 1024, 420), ("float32", 8, 2048, 40), ("float64", 3, 1000, 40)))
 def test_fused_collector_against_torch_and_a_twin_env(g_mod, dtype_name, N, E, T):
@@ -257,7 +249,7 @@ def test_fused_collector_against_torch_and_a_twin_env(g_mod, dtype_name, N, E, T
     g = g_mod
     dtype = getattr(torch, dtype_name)
     D = 5 + 3 * N
-    pol = _random_actor_critic(g, D, 1)
+    pol = LS.actor_critic(g, D, 1)
     mk = lambda E_, off=0: g.ACAS2DVecEnv(E_, N, device="cuda:0", dtype=dtype, seed=21, env_offset=off)  # noqa: E731
     env, twin = mk(E), mk(E)
     env.reset(); twin.reset()
@@ -301,7 +293,7 @@ def test_fused_update_against_torch_autograd_and_adam(g_mod, D, n, B):
     torch.manual_seed(11)
     dev = "cuda:0"
     cfg = g.PPOConfig(ent_coef=0.01, max_grad_norm=0.5, learning_rate=3e-4)
-    mine = _random_actor_critic(g, D, 5)
+    mine = LS.actor_critic(g, D, 5)
     ref = g.ActorCritic(D).to(dev)
     ref.load_state_dict(mine.state_dict())
     obs = torch.rand(n, D, device=dev) * 2 - 1

@@ -20,8 +20,6 @@ import ctypes as C
 import dataclasses
 import os
 import re
-import shutil
-import subprocess
 import types
 
 import numpy as np
@@ -30,17 +28,13 @@ import pytest
 import helpers as H
 import kl_guard_ref as KR
 import learner_ref as R
+import learner_support as LS
 import sb3_options_ref as S
 
 torch = pytest.importorskip("torch")
 DEV = "cuda:0"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gym-acas2d_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 NARROW, WIDE = (8, 11, 14, 17, 29), (53, 101, 197)
 WIDTHS = NARROW + WIDE
-# bounds of tests/test_learner_kernels.py and tests/test_kl_guard.py, unchanged
-TAU, TAU0, TAU_M, TAU_V = 2e-5, 1e-6, 2e-5, 5e-5
 ENTRY, GUARDED = "acas2d_ppo_update_sb3_set_f32", "acas2d_ppo_update_guarded_set_f32"
 B1, B2, EPS = 0.9, 0.999, 1e-5
 
@@ -65,7 +59,7 @@ def test_sb3_entry_is_exported_and_declared(g):
         assert name in g.native.EXPORTS and getattr(L, name)
     assert C.sizeof(g.native.CPpoOptions) == L.acas2d_ppo_options_size() == 3 * 8
     assert [n for n, _ in g.native.CPpoOptions._fields_] == ["old_val", "clip_range_vf", "scale"]
-    header = re.sub(r"\s+", " ", open(os.path.join(ROOT, "include", "acas2d.h")).read())
+    header = re.sub(r"\s+", " ", open(os.path.join(H.ROOT, "include", "acas2d.h")).read())
     assert ("int %s(const Acas2dPpoUpdateSet *u, const Acas2dPpoGuard *g, const Acas2dPpoOptions *o, void *stream);"
             % ENTRY) in header
     assert "size_t acas2d_ppo_options_size(void);" in header
@@ -84,12 +78,7 @@ def test_sb3_update_validation_needs_no_gpu(g):
     ints = dict(n_members=3, n_rows=64, obs_dim=8, apply=1)
 
     def call(guard=(a, a, a), opts=(a, a, a), **kw):
-        f = {n: a for n in names}
-        f.update(ints)
-        f.update(kw)
-        gd = C.byref(g.native.CPpoGuard(*guard)) if guard is not None else None
-        op = C.byref(g.native.CPpoOptions(*opts)) if opts is not None else None
-        return L.acas2d_ppo_update_sb3_set_f32(C.byref(g.native.CPpoUpdateSet(**f)), gd, op, None)
+        return L.acas2d_ppo_update_sb3_set_f32(*LS.host_update_set_args(g, a, guard=guard, opts=opts, **{**ints, **kw}))
 
     def rejects(msg, **kw):
         assert call(**kw) == -22, kw
@@ -286,90 +275,42 @@ def test_eager_update_honours_the_schedules_and_clip_range_vf(g):
         tr.update(*batch[:5])
 
 
-def _device_asm(tmp_path, unit):
-    asm = tmp_path / (unit + ".s")
-    subprocess.run([HIPCC if os.path.exists(HIPCC) else "hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-S", "--cuda-device-only", "-o", str(asm),
-                    os.path.join(CSRC, unit)], check=True, capture_output=True)
-    return asm.read_text()
-
-
-_field = lambda e, k: int(re.search(r"\.%s:\s+(\d+)" % k, e).group(1))  # noqa: E731
-
-
-@pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="needs hipcc")
+@H.needs_hipcc
 def test_sb3_update_kernels_stay_in_registers_and_lds(g, tmp_path):
     """csrc/acas2d_ppo_sb3.hip: five narrow gradient kernels, three wide ones and the apply kernel, held to what
     test_guarded_update_kernels_stay_in_registers_and_lds holds the guarded unit to: no spill of either register file, no
     scratch, at most 256 VGPRs, 64 / 256 / 1 024 threads, the wide kernels' dynamic plus static LDS within 160 KB.
     Observed: narrow 144 VGPRs / 87 SGPRs (90 at D = 29); wide 94 / 96 / 98 VGPRs, 104 / 104 / 105 SGPRs; apply 30 / 46."""
-    meta = _device_asm(tmp_path, "acas2d_ppo_sb3.hip").split("amdhsa.kernels:")[1]
-    kernels = [e for e in re.split(r"\n  - \.agpr_count:", meta) if ".name:" in e]
+    _, kernels = H.kernel_metadata(tmp_path, "acas2d_ppo_sb3.hip")
     assert len(kernels) == 9
     L = g.native.lib()
     seen = {"narrow": [], "wide": [], "apply": 0}
-    for e in kernels:
-        name = re.search(r"\.name:\s+(\S+)", e).group(1)
-        print(name[:70], "vgpr", _field(e, "vgpr_count"), "sgpr", _field(e, "sgpr_count"), "static LDS",
-              _field(e, "group_segment_fixed_size"))
-        assert _field(e, "vgpr_spill_count") == 0 and _field(e, "sgpr_spill_count") == 0, name
-        assert _field(e, "private_segment_fixed_size") == 0 and _field(e, "vgpr_count") <= 256, name
+    for k in kernels:
+        name = k.name
+        print(name[:70], "vgpr", k.field("vgpr_count"), "sgpr", k.field("sgpr_count"), "static LDS",
+              k.field("group_segment_fixed_size"))
+        assert k.field("vgpr_spill_count") == 0 and k.field("sgpr_spill_count") == 0, name
+        assert k.field("private_segment_fixed_size") == 0 and k.field("vgpr_count") <= 256, name
         if "ppo_apply_sb3_set_kernel" in name:
             seen["apply"] += 1
-            assert _field(e, "max_flat_workgroup_size") == 1024, name
+            assert k.field("max_flat_workgroup_size") == 1024, name
             continue
         D = int(re.search(r"kernelILi(\d+)E", name).group(1))
         if "ppo_grad_wide_sb3_set_kernel" in name:
             seen["wide"].append(D)
-            assert _field(e, "max_flat_workgroup_size") == 256, name
+            assert k.field("max_flat_workgroup_size") == 256, name
             lds = L.acas2d_ppo_wide_lds_bytes(D)
-            assert lds + _field(e, "group_segment_fixed_size") <= 160 * 1024, (D, lds)
+            assert lds + k.field("group_segment_fixed_size") <= 160 * 1024, (D, lds)
         else:
             assert "ppo_grad_sb3_set_kernel" in name
             seen["narrow"].append(D)
-            assert _field(e, "max_flat_workgroup_size") == 64, name
+            assert k.field("max_flat_workgroup_size") == 64, name
     assert sorted(seen["narrow"]) == list(NARROW) and sorted(seen["wide"]) == list(WIDE) and seen["apply"] == 1
 
 
 # ---- GPU: the kernels -------------------------------------------------------------------------------------------------
-HYPER = dict(clip_range=(0.2, 0.1, 0.3), vf_coef=(0.5, 0.25, 1.0), ent_coef=(0.01, 0.0, 0.02),
-             max_grad_norm=(0.5, 1e6, 0.5), learning_rate=(3e-4, 1e-3, 1e-4))
 CLIP_VF = (0.3, None, 1.0)             # members 0 and 2 clip, member 1 is off, in the same launch
 _ONE = lambda p: 1.0  # noqa: E731     (a schedule that turns the options entry on and changes nothing)
-
-
-def _cfgs(g, K, per_member=(), **over):
-    """K configs with different clip ranges, learning rates, ... (tests/test_kl_guard.py's); per_member[k]: member k's own."""
-    return [g.PPOConfig(**{**{f: v[k] for f, v in HYPER.items()}, **over, **(per_member[k] if per_member else {})})
-            for k in range(K)]
-
-
-def _rows(bt, K, B):
-    """K x B disjoint rows of the buffer, drawn on the host from the batch's own generator: the same on every machine."""
-    return torch.as_tensor(bt.rng.permutation(bt.n)[:K * B].reshape(K, B), device=bt.device).contiguous()
-
-
-def _draw(bt, pset, clips, B, mode="mixed"):
-    """A fresh minibatch per member on disjoint rows, old log-probs from each member's CURRENT parameters, ratios kept
-    1e-4 off the clip range given per member."""
-    K = len(clips)
-    idx = _rows(bt, K, B)
-    for k in range(K):
-        bt.set_old_logp(bt.theta(pset, k), idx[k], mode, clips[k])
-    return idx
-
-
-def _worst_ratio(errs, ref_all, tau0=TAU0):
-    return max((e - tau0 * ref_all) / max(m, 1e-300) for e, m in errs.values())
-
-
-def _assert_per_tensor(what, got, ref, segs, tau, tau0=TAU0):
-    errs, ref_all = R.per_tensor_errors(got, ref, segs)
-    bad = {n: (e, m) for n, (e, m) in errs.items() if not e <= tau * m + tau0 * ref_all}
-    obs_tau = _worst_ratio(errs, ref_all, tau0)
-    print("%s: observed tau %.2e (bound %.0e, tau0 %.0e)" % (what, obs_tau, tau, tau0))
-    assert not bad, (what, bad, ref_all)
-    return obs_tau / tau
 
 
 WORST = {}
@@ -399,10 +340,10 @@ def _check_member(g, what, bt, pset, fu, k, cfg, idx_k, theta0, pre, old_val, cl
         assert abs(got_ - ref_) <= tol, (what, key, got_, ref_)
         _note("stats " + key, abs(got_ - ref_) / tol)
     assert fu.step_count[k].item() == s0[k] + 1 and float(fu.grad[k].abs().max()) == 0.0, what
-    _note("m", _assert_per_tensor("m " + what, fu.m[k].double().cpu().numpy(), m_ref, segs, TAU_M))
-    _note("v", _assert_per_tensor("v " + what, fu.v[k].double().cpu().numpy(), v_ref, segs, TAU_V))
-    theta1 = bt.theta(pset, k)
-    _note("theta", _assert_per_tensor("theta " + what, theta1, theta_ref, segs, TAU))
+    _note("m", LS.assert_per_tensor("m " + what, fu.m[k].double().cpu().numpy(), m_ref, segs, LS.TAU_M) / LS.TAU_M)
+    _note("v", LS.assert_per_tensor("v " + what, fu.v[k].double().cpu().numpy(), v_ref, segs, LS.TAU_V) / LS.TAU_V)
+    theta1 = LS.theta_of(pset, k)
+    _note("theta", LS.assert_per_tensor("theta " + what, theta1, theta_ref, segs, LS.TAU) / LS.TAU)
     if lr > 0:
         ulp = np.spacing(np.abs(theta_ref).astype(np.float32)).astype(np.float64)
         excess = (np.abs(theta1 - theta_ref) - ulp) / lr
@@ -427,9 +368,9 @@ def test_neutral_options_equal_the_guarded_entry_bitwise(gpu, D, K, B):
     of acas2d_ppo_update_guarded_set_f32 on twin state, bit for bit (x * 1.0f is exact; B <= 64: one workgroup adds each
     gradient entry).  old_val is NaN everywhere: it is not read."""
     g = gpu
-    bt = KR.SharedBatch(g, D, K, K * B + 317, seed=8500 + 7 * D + 31 * K + B, device=DEV)
-    plain_cfgs = _cfgs(g, K)
-    opt_cfgs = _cfgs(g, K, per_member=[dict(learning_rate_schedule=_ONE)] + [{}] * (K - 1))
+    bt = LS.RolloutBatch(g, D, K, K * B + 317, seed=8500 + 7 * D + 31 * K + B)
+    plain_cfgs = LS.member_cfgs(g, K)
+    opt_cfgs = LS.member_cfgs(g, K, per_member=[dict(learning_rate_schedule=_ONE)] + [{}] * (K - 1))
     twins = {"guarded": bt.policy_set(), "sb3": bt.policy_set()}
     nan = torch.full((bt.n,), float("nan"), dtype=torch.float32, device=DEV)
     fus = {"guarded": g.FusedUpdateSet(twins["guarded"], plain_cfgs, *bt.bufs, diagnostics=True),
@@ -445,7 +386,7 @@ def test_neutral_options_equal_the_guarded_entry_bitwise(gpu, D, K, B):
         assert x.shape == y.shape and H.bits_equal(x, y), (what, D, K, B)
 
     for call in (1, 2):
-        idx = _draw(bt, twins["guarded"], [c.clip_range for c in plain_cfgs], B)
+        idx = LS.draw(bt, twins["guarded"], [c.clip_range for c in plain_cfgs], B, rows=LS.host_rows)
         for fu in fus.values():
             fu.step(idx)
         torch.cuda.synchronize()
@@ -473,7 +414,7 @@ def _place_old_val(g, bt, pset, k, idx_k, c_eff, old_val, want_sides):
     """old_val on member k's rows: its float64 value plus N(0, 0.8), admitted as the issue sets it (asserted here, on
     float64, before any launch): every row at least 1e-4 off +-c, both clipped sides and the unclipped middle present
     (want_sides), and torch float32 on the CPU on float64's side of +-c for every row."""
-    theta = bt.theta(pset, k)
+    theta = LS.theta_of(pset, k)
     obs_rows = bt.obs[idx_k]
     v64 = S.value64(g.ActorCritic, bt.D, theta, obs_rows.cpu().numpy())
     old = S.place_old_val(bt.rng, v64, c_eff)
@@ -503,8 +444,8 @@ def test_value_clipping_vs_float64(gpu, D, K, B):
     output: nothing is clipped, and the result matches the plain-MSE float64 reference at the same bounds.  B = 2 and 63
     leave dead lanes, 64 fills one workgroup, 65 and 130 add a second and a third."""
     g = gpu
-    bt = KR.SharedBatch(g, D, K, K * B + 317, seed=12000 + 7 * D + 31 * K + B, device=DEV)
-    cfgs = _cfgs(g, K, per_member=[dict(clip_range_vf=CLIP_VF[k]) for k in range(K)])
+    bt = LS.RolloutBatch(g, D, K, K * B + 317, seed=12000 + 7 * D + 31 * K + B)
+    cfgs = LS.member_cfgs(g, K, per_member=[dict(clip_range_vf=CLIP_VF[k]) for k in range(K)])
     pset = bt.policy_set()
     segs = R.segments(bt.pols[0])
     old_val = torch.full((bt.n,), float("nan"), dtype=torch.float32, device=DEV)
@@ -513,8 +454,8 @@ def test_value_clipping_vs_float64(gpu, D, K, B):
     fu.begin_update()
     c_eff = [None if CLIP_VF[k] is None else S.product32(CLIP_VF[k], 1.0) for k in range(K)]
     # ---- call 1: clipped
-    idx = _draw(bt, pset, [c.clip_range for c in cfgs], B)
-    theta0 = [bt.theta(pset, k) for k in range(K)]
+    idx = LS.draw(bt, pset, [c.clip_range for c in cfgs], B, rows=LS.host_rows)
+    theta0 = [LS.theta_of(pset, k) for k in range(K)]
     for k in range(K):
         _place_old_val(g, bt, pset, k, idx[k], c_eff[k], old_val, want_sides=B >= 63)
     pre = _pre_state(fu)
@@ -530,8 +471,8 @@ def test_value_clipping_vs_float64(gpu, D, K, B):
             plain = R.grad64(g.ActorCritic, dataclasses.replace(cfgs[k], clip_range_vf=None), D, theta0[k], obs, act, old, adv, ret)[2]
             print("  %s: value loss %.8g, the unclipped one would be %.8g" % (what, vf, plain))
     # ---- call 2: old_val = the critic's own float32 output, nothing clipped
-    idx = _draw(bt, pset, [c.clip_range for c in cfgs], B)
-    theta0 = [bt.theta(pset, k) for k in range(K)]
+    idx = LS.draw(bt, pset, [c.clip_range for c in cfgs], B, rows=LS.host_rows)
+    theta0 = [LS.theta_of(pset, k) for k in range(K)]
     for k in range(K):
         with torch.no_grad():
             own = pset.member(k).forward(bt.obs[idx[k]])[1]
@@ -557,7 +498,7 @@ def _const(x):
 
 
 def _factor_cfgs(g):
-    return _cfgs(g, 3, per_member=[dict(clip_range_vf=CLIP_VF[k], learning_rate_schedule=_const(FACTORS[k][0]),
+    return LS.member_cfgs(g, 3, per_member=[dict(clip_range_vf=CLIP_VF[k], learning_rate_schedule=_const(FACTORS[k][0]),
                                         clip_range_schedule=_const(FACTORS[k][1]),
                                         clip_range_vf_schedule=_const(FACTORS[k][2])) for k in range(3)])
 
@@ -577,7 +518,7 @@ def test_factors_scale_the_rate_and_both_clips(gpu, D, B):
     factor 0 keeps every parameter bit while adam_m, adam_v, adam_step and diag[7] advance."""
     g = gpu
     K = 3
-    bt = KR.SharedBatch(g, D, K, K * B + 317, seed=13000 + 7 * D + B, device=DEV)
+    bt = LS.RolloutBatch(g, D, K, K * B + 317, seed=13000 + 7 * D + B)
     cfgs = _factor_cfgs(g)
     pset = bt.policy_set()
     segs = R.segments(bt.pols[0])
@@ -589,8 +530,8 @@ def test_factors_scale_the_rate_and_both_clips(gpu, D, B):
     assert torch.equal(fu.scale.cpu(), want) and fu.factors == [list(f) for f in FACTORS]
     eff = [_effective(cfgs[k], FACTORS[k]) for k in range(K)]
     assert [e["learning_rate"] for e in fu.effective()] == [cfgs[k].learning_rate * FACTORS[k][0] for k in range(K)]
-    idx = _draw(bt, pset, [e[1] for e in eff], B)
-    theta0 = [bt.theta(pset, k) for k in range(K)]
+    idx = LS.draw(bt, pset, [e[1] for e in eff], B, rows=LS.host_rows)
+    theta0 = [LS.theta_of(pset, k) for k in range(K)]
     params0 = [[p[k].clone() for p in fu._params] for k in range(K)]
     for k in range(K):
         _place_old_val(g, bt, pset, k, idx[k], eff[k][2], old_val, want_sides=True)
@@ -631,7 +572,7 @@ def test_stop_with_options_on(gpu, D):
     on the third call -- with different factors -- too.  Members 1 and 2 apply every call at the float64 bounds."""
     g = gpu
     K, B = 3, 65
-    bt = KR.SharedBatch(g, D, K, K * B + 317, seed=14000 + D, device=DEV)
+    bt = LS.RolloutBatch(g, D, K, K * B + 317, seed=14000 + D)
     cfgs = _factor_cfgs(g)
     cfgs[0] = dataclasses.replace(cfgs[0], target_kl=1e-3)
     pset = bt.policy_set()
@@ -647,10 +588,10 @@ def test_stop_with_options_on(gpu, D):
             factors = [[0.7, 0.8, 0.5], [0.3, 1.0, 1.0], [2.0, 0.5, 0.25]]
         fu.scale.copy_(torch.tensor([f + [1.0] for f in factors], dtype=torch.float32))
         eff = [_effective(cfgs[k], factors[k]) for k in range(K)]
-        idx = _rows(bt, K, B)
+        idx = LS.host_rows(bt, K, B)
         for k in range(K):
-            bt.set_old_logp(bt.theta(pset, k), idx[k], "first" if (k == 0 and call == 1) else "mixed", eff[k][1])
-        theta0 = [bt.theta(pset, k) for k in range(K)]
+            bt.set_old_logp(LS.theta_of(pset, k), idx[k], "first" if (k == 0 and call == 1) else "mixed", eff[k][1])
+        theta0 = [LS.theta_of(pset, k) for k in range(K)]
         kl64 = [KR.approx_kl64(bt.log_ratio(theta0[k], idx[k])) for k in range(K)]
         if call == 1:
             assert not KR.stops(kl64[0], 1e-3) and kl64[0] < 1e-5
@@ -694,10 +635,10 @@ def test_footprint_of_the_option_pointers(gpu, D, B):
     clean buffer (at 65 equal to the atomics' rounding), and the sentinels are intact."""
     g = gpu
     K, PAD, SENT = 3, 64, -12345.5
-    bt = KR.SharedBatch(g, D, K, K * B + 317, seed=15000 + 7 * D + B, device=DEV)
+    bt = LS.RolloutBatch(g, D, K, K * B + 317, seed=15000 + 7 * D + B)
     cfgs = _factor_cfgs(g)
     eff = [_effective(cfgs[k], FACTORS[k]) for k in range(K)]
-    idx = _draw(bt, bt.policy_set(), [e[1] for e in eff], B)
+    idx = LS.draw(bt, bt.policy_set(), [e[1] for e in eff], B, rows=LS.host_rows)
     clean = torch.zeros(bt.n, dtype=torch.float32, device=DEV)
     for k in (0, 2):
         _place_old_val(g, bt, bt.policy_set(), k, idx[k], eff[k][2], clean, want_sides=False)
@@ -725,7 +666,7 @@ def test_footprint_of_the_option_pointers(gpu, D, B):
         for what, big, n in (("old_val", big_old, bt.n), ("clip_range_vf", big_vf, K), ("scale", big_sc, 4 * K)):
             assert bool((big[:PAD] == SENT).all()) and bool((big[PAD + n:] == SENT).all()), (name, what)
         assert torch.equal(fu.scale.cpu(), torch.tensor([list(f) + [1.0] for f in FACTORS], dtype=torch.float32))
-        theta = np.stack([bt.theta(pset, k) for k in range(K)])
+        theta = np.stack([LS.theta_of(pset, k) for k in range(K)])
         assert np.isfinite(theta).all() and bool(torch.isfinite(fu.m).all()) and bool(torch.isfinite(fu.v).all()), name
         assert bool(torch.isfinite(fu.stats).all()) and bool(torch.isfinite(fu.diag).all()), name
         assert fu.step_count.cpu().tolist() == [1, 1, 1]
@@ -744,31 +685,8 @@ T_STEPS, T_BATCH, T_EPOCHS = 8, 64, 2                      # 64 envs x 8 steps =
 T_UPDATES = 16
 
 
-def _count_calls(g, monkeypatch, symbol):
-    """Wrap the bound function: every call through it is counted."""
-    L = g.native.lib()
-    inner = getattr(L, symbol)
-    calls = []
-
-    def counted(*args):
-        calls.append(1)
-        return inner(*args)
-
-    monkeypatch.setattr(L, symbol, counted)
-    return calls
-
-
-def _solo_trainer(g, seed=13, envs=64, **cfg_kw):
-    venv = g.ACAS2DVecEnv(envs, 1, device=DEV, seed=13)
-    cfg = g.PPOConfig(seed=seed, n_steps=T_STEPS, batch_size=T_BATCH, n_epochs=T_EPOCHS, **cfg_kw)
-    return g.PPOTrainer(venv, cfg, collector="fused", updater="fused", gae="kernel")
-
-
-def _iterate(tr):
-    tr.collect()
-    st = tr.update()
-    torch.cuda.synchronize()
-    return st
+def _solo_trainer(g, **cfg_kw):
+    return LS.solo_trainer(g, g.PPOConfig(seed=13, n_steps=T_STEPS, batch_size=T_BATCH, n_epochs=T_EPOCHS, **cfg_kw))
 
 
 @pytest.mark.gpu
@@ -776,13 +694,13 @@ def test_trainer_takes_the_new_entry_only_with_options(gpu, monkeypatch):
     """PPOTrainer with none of the four fields: not one call of the new symbol, and the statistics it always returned.
     With clip_range_vf: one call per minibatch, the guarded statistics, and the effective numbers in the log."""
     g = gpu
-    calls = _count_calls(g, monkeypatch, ENTRY)
+    calls = LS.count_calls(g, monkeypatch, ENTRY)
     a = _solo_trainer(g)
-    sa = _iterate(a)
+    sa = LS.iterate(a)
     assert calls == [] and not a._fused_update.guarded and not a._fused_update.options
     assert sorted(sa) == ["pg_loss", "std", "value_loss"]
     b = _solo_trainer(g, clip_range_vf=0.01)
-    sb = _iterate(b)
+    sb = LS.iterate(b)
     print("no options: %s\nclip_range_vf=0.01: %s (%d calls of the new entry)" % (sa, sb, len(calls)))
     assert len(calls) == T_UPDATES and b._fused_update.options and b._fused_update.guarded
     assert sb["n_applied"] == T_UPDATES and sb["early_stop"] is False
@@ -827,7 +745,7 @@ def test_population_member_without_options_equals_its_guarded_twin(gpu, monkeypa
                 for k in range(K)]
         return g.PopulationTrainer(venv, cfgs, gae="kernel", **kw)
 
-    calls = _count_calls(g, monkeypatch, ENTRY)
+    calls = LS.count_calls(g, monkeypatch, ENTRY)
     twin = population({}, diagnostics=True)
     twin.collect()
     s_twin = twin.update()

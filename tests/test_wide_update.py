@@ -2,7 +2,7 @@
 64 traffic aircraft).
 
 CPU: the export, its argument validation, FusedUpdate's choice of entry, and the code object's registers and LDS.
-GPU: the recipe of tests/test_learner_kernels.py (its _Batch, its seeds, its criteria, unchanged) at the new widths --
+GPU: the recipe of tests/test_learner_kernels.py (learner_support.SoloBatch, its seeds, its criteria) at the new widths --
 the raw gradient tensor by tensor against float64 autograd and applied steps each started from the kernel's own state;
 the torch path the trainer otherwise runs (the shape of test_ppo.py's test, its bounds); sentinels around the workspace;
 PPOTrainer(collector="fused", updater="fused") at 16 and 64 traffic aircraft.
@@ -15,18 +15,15 @@ narrow kernel), norm / pg / vf at most 0.04 / 0.06 / 0.03 of their 1e-5 bounds."
 import ctypes as C
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import helpers as H
 import learner_ref as R
+import learner_support as LS
 
 torch = pytest.importorskip("torch")
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "gym-acas2d_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 DEV = "cuda:0"
 WIDE = (53, 101, 197)
 ENTRY = "acas2d_ppo_update_wide_f32"
@@ -38,24 +35,24 @@ def g():
     return g
 
 
+@pytest.fixture(scope="module")
+def gpu(g):
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    g.native.lib()
+    return g
+
+
 # ---- CPU ----------------------------------------------------------------------------------------------------------
 def test_library_exports_the_wide_update(g):
     L = g.native.lib()
     assert ENTRY in g.native.EXPORTS and hasattr(L, ENTRY)
-    header = open(os.path.join(ROOT, "include", "acas2d.h")).read()
+    header = open(os.path.join(H.ROOT, "include", "acas2d.h")).read()
     assert re.search(r"int %s\(const Acas2dPpoUpdate \*u, void \*stream\);" % ENTRY, header)
     assert L.acas2d_abi_version() == 7                                  # additive
 
 
 def _struct(g, **over):
-    """An Acas2dPpoUpdate whose pointers are host addresses: every case built from it must be rejected before any
-    launch."""
-    buf = (C.c_char * 64)()
-    f = {n: C.addressof(buf) for n, t in g.native.CPpoUpdate._fields_ if t is C.c_void_p}
-    f.update(n_rows=64, obs_dim=53, clip_range=0.2, vf_coef=0.5, ent_coef=0.0, max_grad_norm=0.5, learning_rate=3e-4,
-             beta1=0.9, beta2=0.999, adam_eps=1e-5)
-    f.update(over)
-    return g.native.CPpoUpdate(**f), buf
+    return LS.host_update(g, **{"obs_dim": 53, **over})
 
 
 def test_wide_update_validation_needs_no_gpu(g):
@@ -96,29 +93,23 @@ def test_fused_update_picks_the_wide_entry_on_host_tensors(g):
         g.FusedUpdate(g.ActorCritic(30), g.PPOConfig(), z(4, 30), z(4), z(4), z(4), z(4))
 
 
-@pytest.mark.skipif(not (os.path.exists(HIPCC) or shutil.which("hipcc")), reason="needs hipcc")
+@H.needs_hipcc
 def test_wide_update_kernels_stay_in_registers_and_lds(g, tmp_path):
     """csrc/acas2d_ppo_wide.hip: three gradient kernels (the apply kernel is acas2d_ppo.hip's), no VGPR or SGPR spill, no
     scratch, and the LDS the launcher asks for -- acas2d_ppo_wide_lds_bytes, the one figure the launch uses -- plus the
     kernel's static LDS within gfx950's 160 KB per workgroup."""
-    asm = tmp_path / "acas2d_ppo_wide.s"
-    subprocess.run([HIPCC if os.path.exists(HIPCC) else "hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17",
-                    "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-S", "--cuda-device-only", "-o", str(asm),
-                    os.path.join(CSRC, "acas2d_ppo_wide.hip")], check=True, capture_output=True)
-    meta = asm.read_text().split("amdhsa.kernels:")[1]
-    kernels = [e for e in re.split(r"\n  - \.agpr_count:", meta) if ".name:" in e]    # one entry per kernel, all its fields
-    field = lambda e, k: int(re.search(r"\.%s:\s+(\d+)" % k, e).group(1))  # noqa: E731
+    _, kernels = H.kernel_metadata(tmp_path, "acas2d_ppo_wide.hip")
     assert len(kernels) == 3
     L = g.native.lib()
     static = {}
-    for e in kernels:
-        name = re.search(r"\.name:\s+(\S+)", e).group(1)
+    for k in kernels:
+        name = k.name
         assert "ppo_grad_wide_kernel" in name
-        assert field(e, "vgpr_spill_count") == 0 and field(e, "sgpr_spill_count") == 0, name
-        assert field(e, "private_segment_fixed_size") == 0 and field(e, "vgpr_count") <= 256, name
-        assert field(e, "max_flat_workgroup_size") == 256, name                # four waves per workgroup
-        static[int(re.search(r"kernelILi(\d+)E", name).group(1))] = field(e, "group_segment_fixed_size")
-        print(name, "vgpr", field(e, "vgpr_count"), "sgpr", field(e, "sgpr_count"))
+        assert k.field("vgpr_spill_count") == 0 and k.field("sgpr_spill_count") == 0, name
+        assert k.field("private_segment_fixed_size") == 0 and k.field("vgpr_count") <= 256, name
+        assert k.field("max_flat_workgroup_size") == 256, name                # four waves per workgroup
+        static[int(re.search(r"kernelILi(\d+)E", name).group(1))] = k.field("group_segment_fixed_size")
+        print(name, "vgpr", k.field("vgpr_count"), "sgpr", k.field("sgpr_count"))
     assert sorted(static) == list(WIDE)
     for D in WIDE:
         lds = L.acas2d_ppo_wide_lds_bytes(D)
@@ -129,15 +120,6 @@ def test_wide_update_kernels_stay_in_registers_and_lds(g, tmp_path):
 
 
 # ---- GPU ----------------------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def K(g):
-    """tests/test_learner_kernels.py: its _Batch, bounds and per-tensor criterion are the recipe here."""
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    g.native.lib()
-    import test_learner_kernels as K
-    return K
-
-
 _B_ALL = (2, 3, 63, 64, 65, 127, 129, 2085, 4096)
 CASES = [(D, B) for D in WIDE for B in (_B_ALL if D in (53, 197) else (2, 65, 2085))]
 _IDS = ["D%d-B%d" % c for c in CASES]
@@ -145,12 +127,12 @@ _IDS = ["D%d-B%d" % c for c in CASES]
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("D,B", CASES, ids=_IDS)
-def test_wide_update_raw_gradient_per_tensor_vs_float64(g, K, D, B):
+def test_wide_update_raw_gradient_per_tensor_vs_float64(g, gpu, D, B):
     """test_fused_update_raw_gradient_per_tensor_vs_float64 at the wide widths: max_grad_norm < 0, each of the 13 tensors
     against ppo_loss() in float64 autograd, a "mixed" and a "first-epoch" minibatch; max |got - ref| <= 2e-5 max |ref
     tensor| + 1e-6 max |ref|, stats[0] / stats[1] to 1e-5."""
     n = max(2 * B, 300) + 17
-    bt = K._Batch(g, D, n, seed=1000 + 7 * D + B)
+    bt = LS.SoloBatch(g, D, n, seed=1000 + 7 * D + B)
     segs = R.segments(bt.pol)
     for mode, ent in (("mixed", 0.01), ("first", 0.0)):
         cfg = g.PPOConfig(ent_coef=ent, max_grad_norm=-1.0, clip_range=0.2)
@@ -174,7 +156,7 @@ def test_wide_update_raw_gradient_per_tensor_vs_float64(g, K, D, B):
             assert np.abs(ratio - 1).max() < 1e-5
         assert np.array_equal(fu.step_count.cpu().numpy(), [0])      # nothing applied
         assert np.array_equal(R.flat_params(bt.pol), theta)
-        K._assert_per_tensor("wide raw gradient D=%d B=%d %s" % (D, B, mode), got, ref, segs, K.TAU)
+        LS.assert_per_tensor("wide raw gradient D=%d B=%d %s" % (D, B, mode), got, ref, segs, LS.TAU)
         st = fu.stats.double().cpu().numpy()
         print("  pg %.3e vs %.3e, vf %.3e vs %.3e" % (st[0], pg, st[1], vf))
         assert abs(st[0] - pg) <= 1e-5 * max(1.0, abs(pg)) and abs(st[1] - vf) <= 1e-5 * max(1.0, vf)
@@ -182,7 +164,7 @@ def test_wide_update_raw_gradient_per_tensor_vs_float64(g, K, D, B):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("D,B", CASES, ids=_IDS)
-def test_wide_update_applied_steps_vs_float64(g, K, D, B):
+def test_wide_update_applied_steps_vs_float64(g, gpu, D, B):
     """test_fused_update_applied_steps_vs_float64 at the wide widths: the clip active (0.5) and inactive (1e6), a step
     count of 9 999 with non-zero moments, two steps each, every reference step from the kernel's own state.  Bounds: m
     2e-5, v 5e-5, parameters one float32 ulp + 1e-2 lr, norm / pg / vf 1e-5, `grad` exactly zero, step count + 1.
@@ -190,7 +172,7 @@ def test_wide_update_applied_steps_vs_float64(g, K, D, B):
     can clip, the actor's gradient is then exactly zero and the reference itself does not move half the parameters; the
     per-entry parameter bound holds the kernel to the reference's step either way."""
     n = max(2 * B, 300) + 17
-    bt = K._Batch(g, D, n, seed=2000 + 7 * D + B)
+    bt = LS.SoloBatch(g, D, n, seed=2000 + 7 * D + B)
     segs = R.segments(bt.pol)
     lr, b1, b2, eps = 3e-4, 0.9, 0.999, 1e-5
     worst = {"param": 0.0, "m": 0.0, "v": 0.0, "norm": 0.0, "pg": 0.0, "vf": 0.0}
@@ -227,12 +209,8 @@ def test_wide_update_applied_steps_vs_float64(g, K, D, B):
                 worst[key] = max(worst[key], abs(got_ - ref_) / tol * 1.0)
                 assert abs(got_ - ref_) <= tol, (what, key, got_, ref_)
             m1, v1 = fu.m.double().cpu().numpy(), fu.v.double().cpu().numpy()
-            em, mall = R.per_tensor_errors(m1, m_ref, segs)
-            ev, vall = R.per_tensor_errors(v1, v_ref, segs)
-            worst["m"] = max(worst["m"], K._worst_ratio(em, mall))
-            worst["v"] = max(worst["v"], K._worst_ratio(ev, vall))
-            K._assert_per_tensor("m " + what, m1, m_ref, segs, K.TAU_M)
-            K._assert_per_tensor("v " + what, v1, v_ref, segs, K.TAU_V)
+            worst["m"] = max(worst["m"], LS.assert_per_tensor("m " + what, m1, m_ref, segs, LS.TAU_M))
+            worst["v"] = max(worst["v"], LS.assert_per_tensor("v " + what, v1, v_ref, segs, LS.TAU_V))
             theta1 = R.flat_params(bt.pol)
             ulp = np.spacing(np.abs(theta_ref).astype(np.float32)).astype(np.float64)
             excess = (np.abs(theta1 - theta_ref) - ulp) / lr
@@ -242,28 +220,19 @@ def test_wide_update_applied_steps_vs_float64(g, K, D, B):
                 assert np.median(np.abs(theta_ref - theta0) / lr) > 0.05, what    # the reference's step is a real one
     print("wide applied steps D=%d B=%d: worst param excess %.2e lr (bound 1e-2), m tau %.2e (bound %.0e), v tau %.2e (bound "
           "%.0e), norm / pg / vf at %.2f / %.2f / %.2f of their 1e-5 bounds"
-          % (D, B, worst["param"], worst["m"], K.TAU_M, worst["v"], K.TAU_V, worst["norm"], worst["pg"], worst["vf"]))
-
-
-def _random_actor_critic(g, D, seed):
-    torch.manual_seed(seed)
-    pol = g.ActorCritic(D).to(DEV)
-    with torch.no_grad():
-        pol.action_net.weight.mul_(40.0)            # away from SB3's near-zero init: the mean depends on the observation
-        pol.log_std.fill_(-0.7)
-    return pol
+          % (D, B, worst["param"], worst["m"], LS.TAU_M, worst["v"], LS.TAU_V, worst["norm"], worst["pg"], worst["vf"]))
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("D,n,B", ((53, 6000, 2085), (197, 3000, 1000), (101, 700, 64)))
-def test_wide_update_against_torch_autograd_and_adam(g, K, D, n, B):
+def test_wide_update_against_torch_autograd_and_adam(g, gpu, D, n, B):
     """test_ppo.py's test_fused_update_against_torch_autograd_and_adam at the wide widths, its bounds: the torch path the
     trainer otherwise runs (ppo_loss(), autograd, clip_grad_norm_, torch.optim.Adam(eps = 1e-5)) on the same minibatch --
     the raw gradient, then the loss values, the gradient norm and the parameters after one and after three updates."""
     import dataclasses
     torch.manual_seed(11)
     cfg = g.PPOConfig(ent_coef=0.01, max_grad_norm=0.5, learning_rate=3e-4)
-    mine = _random_actor_critic(g, D, 5)
+    mine = LS.actor_critic(g, D, 5)
     ref = g.ActorCritic(D).to(DEV)
     ref.load_state_dict(mine.state_dict())
     obs = torch.rand(n, D, device=DEV) * 2 - 1
@@ -309,12 +278,12 @@ def test_wide_update_against_torch_autograd_and_adam(g, K, D, n, B):
 
 
 @pytest.mark.gpu
-def test_wide_update_writes_nothing_outside_its_workspace(g, K):
+def test_wide_update_writes_nothing_outside_its_workspace(g, gpu):
     """D = 197, B = 65 (a second workgroup with one live row): grad / m / v are the middle of larger tensors filled with
     a sentinel; after a probe and two applied steps every sentinel is intact, and so is every buffer the kernel reads."""
     D, B, pad, sent = 197, 65, 4096, -7.25
     n = max(2 * B, 300) + 17
-    bt = K._Batch(g, D, n, seed=5)
+    bt = LS.SoloBatch(g, D, n, seed=5)
     bt.set_old_logp("mixed", 0.2)
     reads = [t.clone() for t in (bt.obs, bt.act, bt.old_logp, bt.adv, bt.ret)]
     for max_norm, steps in ((-1.0, 1), (0.5, 2)):
@@ -339,7 +308,7 @@ def test_wide_update_writes_nothing_outside_its_workspace(g, K):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("N,iters", ((16, 3), (64, 1)))
-def test_trainer_trains_with_the_fused_update_at_wide_widths(g, K, N, iters):
+def test_trainer_trains_with_the_fused_update_at_wide_widths(g, gpu, N, iters):
     """256 envs x N traffic, collector="fused", updater="fused", n_steps 32, batch 1000, 2 epochs: 8 192 rows, so an epoch
     is eight whole minibatches and a tail of 192 rows.  Every logged loss is finite, the Adam step count is iterations x
     epochs x 9, the parameters moved, evaluate() runs.  (No learning-curve threshold: nothing says how fast PPO improves
