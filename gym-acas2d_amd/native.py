@@ -77,6 +77,13 @@ class CGae(C.Structure):
         [("n_envs", C.c_int64)] + [(n, C.c_int32) for n in ("n_steps", "n_members", "obs_dim", "_pad")]
 
 
+class CRewardNorm(C.Structure):
+    """struct Acas2dRewardNorm: VecNormalize's reward normalisation over the collector's [T][E] rewards (include/acas2d.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("reward", "done", "out", "returns", "stats", "gamma", "workspace")] + \
+        [("epsilon", C.c_double), ("clip", C.c_double), ("n_envs", C.c_int64), ("n_steps", C.c_int32),
+         ("n_members", C.c_int32)]
+
+
 class CMemberEpisodes(C.Structure):
     """struct Acas2dMemberEpisodes: per-member episode statistics of a collection (include/acas2d.h)."""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -105,7 +112,9 @@ EXPORTS = ("acas2d_abi_version", "acas2d_config_size", "acas2d_state_size", "aca
            "acas2d_gae_f32", "acas2d_gae_size", "acas2d_gae_pipeline_depth", "acas2d_collect_set_group_f32",
            "acas2d_ppo_update_wide_set_f32", "acas2d_member_episodes_f32", "acas2d_member_episodes_size",
            "acas2d_population_exploit_f32", "acas2d_population_exploit_size", "acas2d_ppo_update_guarded_set_f32",
-           "acas2d_ppo_guard_size", "acas2d_ppo_update_sb3_set_f32", "acas2d_ppo_options_size")
+           "acas2d_ppo_guard_size", "acas2d_ppo_update_sb3_set_f32", "acas2d_ppo_options_size",
+           "acas2d_reward_normalize_f32", "acas2d_reward_norm_size", "acas2d_reward_norm_workspace_bytes",
+           "acas2d_reward_norm_pipeline_depth")
 
 
 class NativeLibraryError(RuntimeError):
@@ -193,6 +202,12 @@ def lib():
     L.acas2d_gae_f32.argtypes = [C.POINTER(CGae), C.c_void_p]
     L.acas2d_gae_size.restype = C.c_size_t
     L.acas2d_gae_pipeline_depth.restype = C.c_int
+    L.acas2d_reward_normalize_f32.restype = C.c_int
+    L.acas2d_reward_normalize_f32.argtypes = [C.POINTER(CRewardNorm), C.c_void_p]
+    L.acas2d_reward_norm_size.restype = C.c_size_t
+    L.acas2d_reward_norm_workspace_bytes.restype = C.c_size_t
+    L.acas2d_reward_norm_workspace_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
+    L.acas2d_reward_norm_pipeline_depth.restype = C.c_int
     L.acas2d_member_episodes_f32.restype = C.c_int
     L.acas2d_member_episodes_f32.argtypes = [C.POINTER(CMemberEpisodes), C.c_void_p]
     L.acas2d_member_episodes_size.restype = C.c_size_t
@@ -227,7 +242,7 @@ def lib():
     if L.acas2d_gae_size() != C.sizeof(CGae):
         raise NativeLibraryError("Acas2dGae layout mismatch: %d != %d" % (L.acas2d_gae_size(), C.sizeof(CGae)))
     for name, twin in (("member_episodes", CMemberEpisodes), ("population_exploit", CPopulationExploit),
-                       ("ppo_guard", CPpoGuard), ("ppo_options", CPpoOptions)):
+                       ("ppo_guard", CPpoGuard), ("ppo_options", CPpoOptions), ("reward_norm", CRewardNorm)):
         size = getattr(L, "acas2d_%s_size" % name)()
         if size != C.sizeof(twin):
             raise NativeLibraryError("%s layout mismatch: %d != %d" % (twin.__name__, size, C.sizeof(twin)))

@@ -316,6 +316,153 @@ def gae_fused(rewards, values, dones, last_value=None, gamma=0.99, gae_lambda=0.
     return (adv, ret) if last_value is not None else (adv, ret, lv_out)
 
 
+# ---- reward normalisation: SB3's VecNormalize(norm_obs=False, norm_reward=True), on the device (csrc/acas2d_rewnorm.hip) ----
+def _reward_norm_gamma(gamma, n_members, device):
+    """The float64 [K] tensor of the members' discounts from a number or one per member."""
+    K = int(n_members)
+    g = torch.as_tensor(gamma, dtype=torch.float64).reshape(-1)
+    if g.numel() not in (1, K):
+        raise ValueError("gamma needs one element per member (%d), got %d" % (K, g.numel()))
+    return g.expand(K).contiguous().to(device)
+
+
+@torch.no_grad()
+def normalize_rewards_reference(rewards, dones, returns, stats, gamma, epsilon=1e-8, clip_reward=10.0, n_members=1, out=None):
+    """RewardNormalizer.normalize() as torch float64 operations, row by row: the documented slow path (about ten small
+    launches per row on a GPU; it runs on the CPU too) and the baseline of tools/bench_reward_norm.py.  The arithmetic is
+    include/acas2d.h's (acas2d_reward_normalize_f32), the two sums over a member's envs in torch's order.
+      rewards   [T, E] float32 (NaN counts as 0, +-inf as +-FLT_MAX); dones [T, E] bool or uint8
+      returns   float64 [E] and stats float64 [K, 3] (mean, var, count): the state, UPDATED in place
+      gamma     a number, one per member, or a float64 [K] tensor
+    Returns the normalised rewards, float32 [T, E] (`out`, which may be `rewards`, if given).  No host read."""
+    T, E = rewards.shape
+    K = int(n_members)
+    if K < 1 or E % K:
+        raise ValueError("normalize_rewards_reference needs E = K x EM, got E = %d, K = %d" % (E, K))
+    EM, dev = E // K, rewards.device
+    if returns.dtype != torch.float64 or stats.dtype != torch.float64 or tuple(returns.shape) != (E,) or tuple(stats.shape) != (K, 3):
+        raise ValueError("normalize_rewards_reference: returns float64 [%d] and stats float64 [%d, 3]" % (E, K))
+    g = _reward_norm_gamma(gamma, K, dev).view(K, 1)
+    r64 = torch.nan_to_num(rewards.to(torch.float32), nan=0.0).to(torch.float64).view(T, K, EM)
+    dones = dones.view(T, K, EM).to(torch.bool)
+    out = torch.empty(T, E, dtype=torch.float32, device=dev) if out is None else out
+    G = returns.view(K, EM)
+    mean, var, count = stats[:, 0].clone(), stats[:, 1].clone(), stats[:, 2].clone()
+    for t in range(T):
+        r = r64[t]
+        G.mul_(g).add_(r)
+        bm = G.sum(1) / EM
+        d = G - bm.unsqueeze(1)
+        bv = (d * d).sum(1) / EM
+        delta, tot = bm - mean, count + EM
+        mean_new = mean + delta * EM / tot
+        m2 = var * count + bv * EM + delta * delta * count * EM / tot
+        var, mean, count = m2 / tot, mean_new, tot
+        out[t].copy_(torch.clamp(r / torch.sqrt(var + epsilon).unsqueeze(1), -clip_reward, clip_reward).view(E))
+        G.masked_fill_(dones[t], 0.0)
+    stats.copy_(torch.stack((mean, var, count), 1))
+    return out
+
+
+class RewardNormalizer:
+    """SB3's VecNormalize(norm_obs=False, norm_reward=True) for a [T, E] buffer of collected rewards, as ONE call of
+    acas2d_reward_normalize_f32 (four small launches, no host synchronisation): every reward is divided by the running
+    standard deviation of the discounted return and clipped to +-clip_reward.  It owns the state -- `returns` float64 [E],
+    the discounted return of every env, and `stats` float64 [K, 3], member k's running mean, variance and count (SB3's
+    RunningMeanStd: 0, 1, 1e-4 at the start) -- and the kernel's workspace.  Member k owns the envs [k EM, (k + 1) EM);
+    for K > 1, EM must be a multiple of 64.  `gamma`: a number, or one per member.  The same inputs give the same bits, a
+    buffer may be passed in pieces (the state carries everything), and a member's numbers do not depend on the others."""
+
+    def __init__(self, n_envs, n_members=1, gamma=0.99, epsilon=1e-8, clip_reward=10.0, device="cuda:0"):
+        E, K = int(n_envs), int(n_members)
+        if E < 1 or K < 1 or (K > 1 and (E % K or (E // K) % 64)):
+            raise ValueError("RewardNormalizer needs n_envs = K x a multiple of 64 for K > 1 members, got n_envs = %d, K = %d"
+                             % (E, K))
+        if not (math.isfinite(epsilon) and epsilon > 0 and math.isfinite(clip_reward) and clip_reward > 0):
+            raise ValueError("RewardNormalizer: epsilon and clip_reward must be finite and positive, got %r, %r"
+                             % (epsilon, clip_reward))
+        self.n_envs, self.n_members, self.device = E, K, torch.device(device)
+        self.epsilon, self.clip_reward = float(epsilon), float(clip_reward)
+        self.gamma = _reward_norm_gamma(gamma, K, self.device)
+        self.returns = torch.zeros(E, dtype=torch.float64, device=self.device)
+        self.stats = torch.tensor([[0.0, 1.0, 1e-4]] * K, dtype=torch.float64).to(self.device)
+        self._workspace = None
+
+    def normalize(self, rewards, dones, out=None):
+        """Normalise the rows of `rewards` [T, E] (float32, on the device; NaN counts as 0, +-inf as +-FLT_MAX) in order,
+        resetting an env's discounted return where `dones` [T, E] (bool or uint8) is set; the state moves on by T steps.
+        out: a float32 [T, E] tensor, `rewards` itself for in place, or None for a new one.  One ABI call on the current
+        stream; returns `out`."""
+        import ctypes as C
+        from . import native
+        dev, E, K = self.device, self.n_envs, self.n_members
+        if dev.type != "cuda":
+            raise ValueError("RewardNormalizer.normalize runs on the GPU (normalize_rewards_reference is the torch path)")
+        if rewards.dim() != 2 or rewards.shape[1] != E or dones.shape != rewards.shape:
+            raise ValueError("normalize takes rewards and dones of one shape [T, %d]" % E)
+        if rewards.dtype != torch.float32 or dones.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("normalize takes float32 rewards and bool or uint8 dones")
+        out = torch.empty_like(rewards) if out is None else out
+        for t in (rewards, dones, out):
+            if t.device != dev or not t.is_contiguous():
+                raise ValueError("normalize takes contiguous tensors on %s" % dev)
+        if out.shape != rewards.shape or out.dtype != torch.float32:
+            raise ValueError("out must be a float32 tensor of the rewards' shape")
+        T = rewards.shape[0]
+        L = native.lib()
+        need = L.acas2d_reward_norm_workspace_bytes(E, T, K)
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        p = lambda t: t.data_ptr()  # noqa: E731
+        n = native.CRewardNorm(p(rewards), p(dones), p(out), p(self.returns), p(self.stats), p(self.gamma), p(self._workspace),
+                               self.epsilon, self.clip_reward, E, T, K)
+        with torch.cuda.device(dev):
+            native.check(L.acas2d_reward_normalize_f32(C.byref(n), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return out
+
+    def reward_std(self):
+        """sqrt(var + epsilon) per member, float64 [K] on the device: what a reward is divided by now."""
+        return torch.sqrt(self.stats[:, 1] + self.epsilon)
+
+    def inherit(self, donor):
+        """stats[k] = stats[donor[k]] for every member, as one device gather (donor: an integer device tensor [K], as
+        population_exploit returns it); `returns`, the envs' own discounted returns, stay."""
+        self.stats.copy_(self.stats.index_select(0, donor.to(device=self.device, dtype=torch.int64)))
+
+    def state_dict(self, member=None):
+        """The state and the constants (CPU copies); member=k: member k's alone, as a normaliser of one member holds it."""
+        E, K = self.n_envs, self.n_members
+        EM = E // K
+        env = slice(None) if member is None else slice(member * EM, (member + 1) * EM)
+        mem = slice(None) if member is None else slice(member, member + 1)
+        return {"returns": self.returns[env].cpu().clone(), "stats": self.stats[mem].cpu().clone(),
+                "gamma": self.gamma[mem].cpu().clone(), "epsilon": self.epsilon, "clip_reward": self.clip_reward,
+                "n_envs": E if member is None else EM, "n_members": K if member is None else 1}
+
+    def load_state_dict(self, sd):
+        if (sd["n_envs"], sd["n_members"]) != (self.n_envs, self.n_members):
+            raise ValueError("load_state_dict: the state of %d envs / %d member(s), this normaliser has %d / %d"
+                             % (sd["n_envs"], sd["n_members"], self.n_envs, self.n_members))
+        self.returns.copy_(sd["returns"])                 # in place: the addresses stay (captured graphs may hold them)
+        self.stats.copy_(sd["stats"])
+        self.gamma.copy_(sd["gamma"])
+        self.epsilon, self.clip_reward = float(sd["epsilon"]), float(sd["clip_reward"])
+
+
+def _reward_normalizer_for(reward_norm, n_envs, configs, device):
+    """A trainer's `reward_norm` argument: True (SB3's defaults, gamma from the configs) or a RewardNormalizer."""
+    K = len(configs)
+    if reward_norm is True:
+        return RewardNormalizer(n_envs, K, gamma=[c.gamma for c in configs], device=device)
+    if not isinstance(reward_norm, RewardNormalizer):
+        raise TypeError("reward_norm must be None, True or a RewardNormalizer, got %r" % (reward_norm,))
+    same = lambda a, b: a.type == b.type and (a.index or 0) == (b.index or 0)  # noqa: E731
+    if (reward_norm.n_envs, reward_norm.n_members) != (n_envs, K) or not same(reward_norm.device, torch.device(device)):
+        raise ValueError("reward_norm: a RewardNormalizer of %d envs / %d member(s) on %s, the trainer has %d / %d on %s"
+                         % (reward_norm.n_envs, reward_norm.n_members, reward_norm.device, n_envs, K, device))
+    return reward_norm
+
+
 LOG_SQRT_2PI = 0.5 * math.log(2.0 * math.pi)
 
 
@@ -583,10 +730,12 @@ def episode_summary(returns, lengths, outcomes):
 
 class _Callbacks:
     """learn()'s EvalCallback / CheckpointCallback bookkeeping for ONE learner, whose files go under `save_dir` and whose
-    ActorCritic `policy()` gives when one is saved; `head` opens every record (a population's {"member": k})."""
+    ActorCritic `policy()` gives when one is saved; `head` opens every record (a population's {"member": k}).  With
+    reward normalisation on, `reward_norm()` gives the learner's RewardNormalizer.state_dict(), saved beside every zip:
+    best_model_reward_norm.pt, checkpoints/reward_norm_<num_timesteps>_steps.pt (the zips are SB3's, untouched)."""
 
-    def __init__(self, save_dir, policy, head=()):
-        self.save_dir, self.policy, self.head = save_dir, policy, dict(head)
+    def __init__(self, save_dir, policy, head=(), reward_norm=None):
+        self.save_dir, self.policy, self.head, self.reward_norm = save_dir, policy, dict(head), reward_norm
         self.evals = {"timesteps": [], "results": [], "ep_lengths": []}
         self.best = -math.inf
 
@@ -610,11 +759,15 @@ class _Callbacks:
                      ep_lengths=np.stack(ev["ep_lengths"]))
             if new_best:
                 save_sb3_policy(self.policy(), os.path.join(self.save_dir, "best_model.zip"))
+                if self.reward_norm is not None:
+                    torch.save(self.reward_norm(), os.path.join(self.save_dir, "best_model_reward_norm.pt"))
         return rec
 
     def checkpoint(self, timesteps):
         from .policy import save_sb3_policy
         save_sb3_policy(self.policy(), os.path.join(self.save_dir, "checkpoints", "model_%d_steps.zip" % timesteps))
+        if self.reward_norm is not None:
+            torch.save(self.reward_norm(), os.path.join(self.save_dir, "checkpoints", "reward_norm_%d_steps.pt" % timesteps))
 
 
 def minibatch_buffers(n, batch_size, device, lead=()):
@@ -748,10 +901,15 @@ class PPOTrainer(_Trainer):
     entry, guarded by implication), op by op through effective_config() -- the optimizer's lr is set per update; the
     captured torch-op updater holds its numbers in a fixed graph and rejects them.  Inside learn() an update runs at
     progress_remaining = max(0, 1 - num_timesteps / total_timesteps), outside it at 1; its statistics then carry the
-    effective learning_rate, clip_range and (where set) clip_range_vf."""
+    effective learning_rate, clip_range and (where set) clip_range_vf.
+    reward_norm: None, True (SB3's VecNormalize(norm_obs=False, norm_reward=True) defaults, gamma from the config) or a
+    RewardNormalizer; with collector="fused" only.  collect() then normalises b_rew in place (one RewardNormalizer.normalize
+    call) before GAE, so GAE, the update and clip_range_vf see normalised rewards; episode returns (b_epret) and evaluate()
+    stay raw, update()'s statistics gain reward_std, and learn() saves the normaliser's state beside every zip.  It is an
+    env wrapper in SB3, not a hyper-parameter: PPOConfig has no field for it.  None: the calls issued are the same."""
 
     def __init__(self, venv, config=None, policy=None, use_graphs=None, collector=None, updater=None, gae=None,
-                 diagnostics=False):
+                 diagnostics=False, reward_norm=None):
         self.venv = venv
         self.cfg = config or PPOConfig()
         torch.manual_seed(self.cfg.seed)
@@ -790,6 +948,10 @@ class PPOTrainer(_Trainer):
                              "collector='fused' only; got use_graphs=%r, collector=%r -- use gae='torch'"
                              % (self.use_graphs, self.collector))
         self._gae_constants = None
+        self.reward_norm = None
+        if reward_norm is not None and not (self.use_graphs and self.collector == "fused"):
+            raise ValueError("reward_norm (RewardNormalizer on the static rollout buffers) is supported with use_graphs and "
+                             "collector='fused' only; got use_graphs=%r, collector=%r" % (self.use_graphs, self.collector))
         # the hand-written launches exist for the observation widths / traffic counts below: say so HERE, not at the
         # first collect() / update() of a run
         f32 = getattr(venv, "dtype", torch.float32) == torch.float32
@@ -806,6 +968,8 @@ class PPOTrainer(_Trainer):
         self.opt = torch.optim.Adam(self.policy.parameters(), lr=self.cfg.learning_rate, eps=1e-5,
                                     capturable=self.use_graphs, **({"fused": True} if self.use_graphs else {}))
         self.obs = venv.reset().to(torch.float32).clone()
+        if reward_norm is not None:
+            self.reward_norm = _reward_normalizer_for(reward_norm, venv.num_envs, [self.cfg], self.device)
         # Exact parallel flight makes the reference's d_cpa 0/0 = NaN (kinematics.py:48), and its reward
         # with it when the aircraft is traffic[0]; the engine reproduces that.  In float64 it all but
         # never happens; in float32 headings coincide bit for bit about once per 2e7 env steps, and one
@@ -931,6 +1095,8 @@ class PPOTrainer(_Trainer):
                                         out=self._fused_out, group=self._group)
                 self._fused_out = out
                 self.nan_events.add_(self._store_collection(out).sum())
+                if self.reward_norm is not None:
+                    self.reward_norm.normalize(self.b_rew, self.b_done, out=self.b_rew)
             else:
                 self.t_idx.zero_()
                 for _ in range(T):
@@ -999,6 +1165,8 @@ class PPOTrainer(_Trainer):
                 out["explained_variance"] = explained_variance(self.b_val.reshape(-1), self.b_ret.reshape(-1)).item()
             if fu.options:
                 out.update(fu.effective()[0])
+            if self.reward_norm is not None:
+                out["reward_std"] = self.reward_norm.reward_std().item()
             return out
         if self.use_graphs:
             n = cfg.n_steps * self.venv.num_envs
@@ -1007,7 +1175,8 @@ class PPOTrainer(_Trainer):
                     # whole minibatches: one static shape; the partial one SB3 also takes: its own graph
                     self._graphs[2 if idx is self.mb_idx else 3].replay()
             return {"pg_loss": self._pg.item(), "value_loss": self._vf.item(),
-                    "std": self.policy.log_std.detach().exp().item()}
+                    "std": self.policy.log_std.detach().exp().item(),
+                    **({} if self.reward_norm is None else {"reward_std": self.reward_norm.reward_std().item()})}
         n = obs.shape[0]
         stats = {}
         options = has_options(cfg)
@@ -1104,7 +1273,9 @@ class PPOTrainer(_Trainer):
             stats = self.update() if batch is None else self.update(*batch)
             return [stats], [self.recent_episodes()], [self.nan_events]
 
-        return self._learn(total_timesteps, log, [_Callbacks(save_dir, lambda: self.policy)], [], iterate,
+        books = [_Callbacks(save_dir, lambda: self.policy,
+                            reward_norm=self.reward_norm and self.reward_norm.state_dict)]
+        return self._learn(total_timesteps, log, books, [], iterate,
                            lambda: self._evaluate_rows([self.policy], self._group, eval_episodes, eval_rng), eval_every,
                            checkpoint_every)
 
@@ -1255,10 +1426,15 @@ class PopulationTrainer(_Trainer):
     early_stop and explained_variance per member; without both it issues the launches it always did.
     clip_range_vf and the three schedules may differ between members too (None: off): with one anywhere the update goes
     through FusedUpdateSet's `options` entry, a member without them getting neutral numbers in the same launches, and
-    update() adds every member's effective learning_rate, clip_range and (where set) clip_range_vf."""
+    update() adds every member's effective learning_rate, clip_range and (where set) clip_range_vf.
+    reward_norm: None, True or a RewardNormalizer of K members, as PPOTrainer's: member k's rewards are normalised by its
+    OWN running statistics (with its own gamma) in the one call after the collection, update() adds reward_std per member
+    and learn() saves member k's normaliser state under member_<k>/ beside its zips."""
 
-    def __init__(self, venv, configs, gae=None, group=False, diagnostics=False):
+    def __init__(self, venv, configs, gae=None, group=False, diagnostics=False, reward_norm=None):
         configs = list(configs)
+        if reward_norm is not None and reward_norm is not True and not isinstance(reward_norm, RewardNormalizer):
+            raise TypeError("reward_norm must be None, True or a RewardNormalizer, got %r" % (reward_norm,))
         self.group = bool(group)
         self.diagnostics = bool(diagnostics)
         self.gae = gae or "torch"
@@ -1308,6 +1484,8 @@ class PopulationTrainer(_Trainer):
                                 torch.tensor([getattr(c, f) for c in configs], dtype=torch.float32, device=self.device))
         self._gae_constants = gae_constants(per_member("gamma"), per_member("gae_lambda"), K, self.device)
         self.obs = venv.reset().to(torch.float32).clone()
+        self.reward_norm = (None if reward_norm is None else
+                            _reward_normalizer_for(reward_norm, venv.num_envs, configs, self.device))
         self.nan_events = torch.zeros(K, dtype=torch.int64, device=self.device)
         self.num_timesteps = 0
         self.ep_returns, self.ep_lengths, self.ep_outcomes = ([[] for _ in range(K)] for _ in range(3))
@@ -1332,6 +1510,8 @@ class PopulationTrainer(_Trainer):
                                     out=self._fused_out, **({"group": True} if self.group else {}))
         self._fused_out = out
         self.nan_events.add_(self._store_collection(out).view(T, K, EM).sum((0, 2)))
+        if self.reward_norm is not None:
+            self.reward_norm.normalize(self.b_rew, self.b_done, out=self.b_rew)
         self.last_value.copy_(self.policy_set.values(self.obs))
         if self.gae == "kernel":
             gae_fused(self.b_rew, self.b_val, self.b_done, self.last_value, n_members=K, constants=self._gae_constants,
@@ -1381,6 +1561,9 @@ class PopulationTrainer(_Trainer):
         if fu.options:
             for k, eff in enumerate(fu.effective(hyper_before)):
                 out[k].update(eff)
+        if self.reward_norm is not None:
+            for k, sd in enumerate(self.reward_norm.reward_std().cpu().tolist()):
+                out[k]["reward_std"] = sd
         return out
 
     def _hyper_rows(self, fu):
@@ -1418,7 +1601,9 @@ class PopulationTrainer(_Trainer):
         if checkpoint_every and not save_dir:
             raise ValueError("checkpoint_every needs save_dir")
         eval_rng = random.Random(self.configs[0].seed if eval_seed is None else eval_seed) if eval_every else None
-        books = [_Callbacks(save_dir and os.path.join(save_dir, "member_%d" % k), lambda k=k: self.member(k), {"member": k})
+        rn = self.reward_norm
+        books = [_Callbacks(save_dir and os.path.join(save_dir, "member_%d" % k), lambda k=k: self.member(k), {"member": k},
+                            reward_norm=rn and (lambda k=k: rn.state_dict(member=k)))
                  for k in range(self.K)]
 
         def iterate():
@@ -1561,9 +1746,12 @@ class PBTTrainer(PopulationTrainer):
     slot likewise; a schedule's factor multiplies the hyper row as the exploit steps have left it, and update()'s
     learning_rate / clip_range are formed from the rows read back at the last exploit (no extra read-back: rows edited
     by hand through `hyper` in between reach the kernels but not that log).  fraction = 0 is PopulationTrainer bit for bit.
-    group=True, gae="kernel" and diagnostics=True as the parent's."""
+    group=True, gae="kernel", diagnostics=True and reward_norm as the parent's.  With reward_norm a recipient also takes the
+    donor's running reward statistics (RewardNormalizer.inherit on the kernel's device `donor` vector, no host read): its
+    critic is now the donor's and lives in the donor's reward scale; the envs' discounted returns stay its own.  The score
+    of the exchange is the RAW mean episode return."""
 
-    def __init__(self, venv, configs, pbt, gae=None, group=False, diagnostics=False):
+    def __init__(self, venv, configs, pbt, gae=None, group=False, diagnostics=False, reward_norm=None):
         configs = list(configs)
         for f in ("gamma", "gae_lambda"):
             if len({getattr(c, f) for c in configs}) > 1:
@@ -1571,7 +1759,7 @@ class PBTTrainer(PopulationTrainer):
                                  "exchanged by an exploit step, got %s" % (f, [getattr(c, f) for c in configs]))
         self.pbt = pbt
         self.n_replace = pbt.n_replace(len(configs))
-        super().__init__(venv, configs, gae=gae, group=group, diagnostics=diagnostics)
+        super().__init__(venv, configs, gae=gae, group=group, diagnostics=diagnostics, reward_norm=reward_norm)
         # built now, not at the first update: an exploit before it must find the moments and the hyper row
         self._fused_update = self._make_fused_update()
         self.window = None
@@ -1605,6 +1793,8 @@ class PBTTrainer(PopulationTrainer):
         pbt, w = self.pbt, self.window
         donor = population_exploit(self.policy_set, self._fused_update, w["score"], self.n_replace, self.generation,
                                    pbt.seed, perturb=pbt.perturb, factors=pbt.factors, bounds=pbt.bounds)
+        if self.reward_norm is not None:
+            self.reward_norm.inherit(donor)
         donor, hyper, score = donor.cpu().tolist(), self.hyper.cpu().tolist(), w["score"].cpu().tolist()
         self._hyper_host = hyper
         for n in ("count", "outcomes", "steps", "return_sum"):

@@ -595,6 +595,63 @@ size_t acas2d_gae_size(void);         /* sizeof(Acas2dGae): layout check for bin
 int acas2d_gae_pipeline_depth(void);  /* rows of loads in flight per lane (16) */
 
 /*
+ * acas2d_reward_normalize_f32: SB3 1.1.0's VecNormalize(norm_obs=False, norm_reward=True) over the collector's [T][E]
+ * reward buffer, between acas2d_collect_* and acas2d_gae_f32 -- every reward divided by the running standard deviation of
+ * the discounted return (VecNormalize.step_wait + RunningMeanStd.update_from_moments).  Additive to ABI 7.  float32 rewards;
+ * the state and all arithmetic are float64, every operation its own rounding.
+ * State: per member k `stats[k]` = mean, var, count (start it at 0, 1, 1e-4); per env e the discounted return
+ * `returns[e]` = G_e (start it at 0).  Member k owns the envs [k EM, (k + 1) EM), EM = n_envs / K.  For t = 0 .. T-1, in
+ * this order:
+ *     r       = reward[t][e], NaN -> 0, +-inf -> +-FLT_MAX (acas2d_gae_f32's scrub), widened to double
+ *     G_e     = G_e * gamma_k + r
+ *     bm      = sum_e(G_e) / EM;  bv = sum_e((G_e - bm)^2) / EM                    two passes over member k's envs
+ *     delta   = bm - mean;  tot = count + EM
+ *     mean'   = mean + delta * EM / tot
+ *     m2      = var * count + bv * EM + delta * delta * count * EM / tot
+ *     var     = m2 / tot;  mean = mean';  count = tot
+ *     out[t][e] = (float)min(max(r / sqrt(var + epsilon), -clip), clip)            double division, one rounding to float32
+ *     if done[t][e]: G_e = 0
+ * The two sums over e are taken in a fixed order that depends on EM alone (lane l of one wavefront adds the columns l,
+ * l + 64, ... ascending, the wavefront adds along the xor tree 32 .. 1); there are no floating-point atomics and the merges
+ * over t are sequential.  So the same inputs give the same bits on every run; a call over T rows equals a call over the
+ * first T1 rows followed by one over the rest (the state carries everything), bit for bit in out, returns and stats; and a
+ * call with K members equals K calls with K = 1 on the column slices.
+ * The call is four launches on `stream` (per-env sweep, per-row moments, per-member merges, element-wise division) with no
+ * host synchronisation and no read-back; the sweep keeps acas2d_reward_norm_pipeline_depth() rows of loads in flight.
+ *   reward, done          the collector's float[T][E] / u8[T][E]
+ *   out                   float[T][E]; out == reward is allowed (in place: the same element by the same lane)
+ *   returns               DEVICE double[E], read and written
+ *   stats                 DEVICE double[K][3], read and written
+ *   gamma                 DEVICE double[K]: member k's discount
+ *   workspace             DEVICE scratch of acas2d_reward_norm_workspace_bytes(n_envs, n_steps, n_members) bytes (8 per
+ *                         sample and 24 per (t, k)), 8-byte aligned; holds nothing between calls
+ *   epsilon, clip         SB3's defaults are 1e-8 and 10
+ *   n_members             K >= 1; for K > 1, EM must be a multiple of 64 (a wavefront's envs belong to one member, as for
+ *                         acas2d_gae_f32); K == 1 takes any n_envs >= 1 (< 2^31)
+ * Rejected with ACAS2D_EINVAL before any HIP call: a NULL pointer; n_steps, n_envs or n_members < 1; n_envs >= 2^31; K > 1
+ * with n_envs not K x a multiple of 64; epsilon or clip not finite and positive; out, returns, stats or workspace equal to
+ * another buffer of the struct, other than out == reward; returns, stats, gamma or workspace not 8-byte aligned.
+ */
+typedef struct Acas2dRewardNorm {
+    const void *reward;              /* float[n_steps][n_envs]: the collector's reward */
+    const uint8_t *done;             /* u8[n_steps][n_envs] */
+    void *out;                       /* float[n_steps][n_envs]; may be `reward` */
+    double *returns;                 /* device double[n_envs]: read and written */
+    double *stats;                   /* device double[n_members][3]: mean, var, count; read and written */
+    const double *gamma;             /* device double[n_members] */
+    void *workspace;                 /* acas2d_reward_norm_workspace_bytes() of device scratch */
+    double epsilon, clip;
+    int64_t n_envs;
+    int32_t n_steps, n_members;
+} Acas2dRewardNorm;
+
+int acas2d_reward_normalize_f32(const Acas2dRewardNorm *n, void *stream);
+size_t acas2d_reward_norm_size(void);             /* sizeof(Acas2dRewardNorm): layout check for bindings */
+/* bytes of `workspace` for a call of this shape; 0 for a shape the entry rejects */
+size_t acas2d_reward_norm_workspace_bytes(int64_t n_envs, int32_t n_steps, int32_t n_members);
+int acas2d_reward_norm_pipeline_depth(void);      /* rows of loads in flight per lane of the sweep (16) */
+
+/*
  * acas2d_member_episodes_f32: the episodes that ended during a collection of K members, summed per member in ONE launch
  * -- the score of population-based training (Jaderberg et al. 2017).  Additive to ABI 7.  Inputs are the [T][E] outputs of
  * acas2d_collect_* as they lie, member k owning the columns [k EM, (k + 1) EM), EM = n_envs / K.  ep_return and ep_steps

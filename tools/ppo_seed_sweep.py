@@ -68,9 +68,14 @@ ap.add_argument("--lr-schedule", choices=("constant", "linear"), default="consta
                      "whatever rate the exploit steps have left a member)")
 ap.add_argument("--clip-schedule", choices=("constant", "linear"), default="constant",
                 help="linear: the clip range falls linearly to 0 over --timesteps, likewise")
+ap.add_argument("--reward-norm", action="store_true",
+                help="SB3's VecNormalize(norm_obs=False, norm_reward=True) for every run of the sweep: rewards divided by the "
+                     "running standard deviation of the discounted return before GAE (ppo.RewardNormalizer, DESIGN.md 4.2k); "
+                     "the scores stay raw returns")
 args = ap.parse_args()
 if args.pbt and not args.population:
     ap.error("--pbt needs --population")
+REWARD_NORM = True if args.reward_norm else None
 # the schedules as PPOConfig takes them (callables: kept out of `kw`, which goes into the records as JSON)
 SCHEDULES = dict(learning_rate_schedule=g.ppo.linear_schedule() if args.lr_schedule == "linear" else None,
                  clip_range_schedule=g.ppo.linear_schedule() if args.clip_schedule == "linear" else None)
@@ -97,7 +102,8 @@ score = dict(dtype=torch.float32, config=g.ACAS2DConfig(n_traffic=N), group=True
 for name in args.sets:
     kw = {**dict(n_steps=256, batch_size=4096), **SETS[name], **({} if args.target_kl is None else {"target_kl": args.target_kl}),
           **({} if args.clip_range_vf is None else {"clip_range_vf": args.clip_range_vf})}
-    sched = {"lr_schedule": args.lr_schedule, "clip_schedule": args.clip_schedule}
+    sched = {"lr_schedule": args.lr_schedule, "clip_schedule": args.clip_schedule,
+             **({"reward_norm": True} if args.reward_norm else {})}
     goals = []
     if args.population:
         t0 = time.time()
@@ -106,9 +112,9 @@ for name in args.sets:
         cfgs = [g.PPOConfig(seed=seed, **kw, **SCHEDULES) for seed in args.seeds]
         if args.pbt:
             pop = g.PBTTrainer(venv, cfgs, g.PBTConfig(ready_every=args.pbt_every, fraction=args.pbt_fraction), gae=args.gae,
-                               group=GROUP)
+                               group=GROUP, reward_norm=REWARD_NORM)
         else:
-            pop = g.PopulationTrainer(venv, cfgs, gae=args.gae, group=GROUP)
+            pop = g.PopulationTrainer(venv, cfgs, gae=args.gae, group=GROUP, reward_norm=REWARD_NORM)
         hist = pop.learn(int(args.timesteps), log=None)
         out = g.evaluate_policies_fused(pop.policy_set.actor_weights(), own, trf, goal, **score)
         wall = time.time() - t0
@@ -130,7 +136,8 @@ for name in args.sets:
     for seed in ([] if args.population else args.seeds):
         t0 = time.time()
         venv = g.ACAS2DVecEnv(args.envs, N, device="cuda:0", dtype=torch.float32, seed=13)
-        tr = g.PPOTrainer(venv, g.PPOConfig(seed=seed, **kw, **SCHEDULES), collector="fused", updater="fused", gae=args.gae)
+        tr = g.PPOTrainer(venv, g.PPOConfig(seed=seed, **kw, **SCHEDULES), collector="fused", updater="fused", gae=args.gae,
+                          reward_norm=REWARD_NORM)
         hist = tr.learn(int(args.timesteps), log=None)
         out = g.evaluate_policy_fused(tr.policy, own, trf, goal, **score)
         rec = {"set": name, "config": kw, **sched, "seed": seed, "timesteps": int(args.timesteps), "wall_s": time.time() - t0,

@@ -46,6 +46,11 @@ ap.add_argument("--lr-schedule", choices=("constant", "linear"), default="consta
                      "rate -- in a --pbt population on whatever rate the exploit steps have left a member)")
 ap.add_argument("--clip-schedule", choices=("constant", "linear"), default="constant",
                 help="linear: the clip range falls linearly to 0 over --timesteps, likewise")
+ap.add_argument("--reward-norm", action="store_true",
+                help="SB3's VecNormalize(norm_obs=False, norm_reward=True): every collected reward divided by the running standard "
+                     "deviation of the discounted return and clipped to +-10, on the device before GAE (ppo.RewardNormalizer, "
+                     "DESIGN.md 4.2k; per member in a population, inherited from the donor at a --pbt exploit step).  Episode "
+                     "returns, evaluations and PBT scores stay raw; the log gains reward_std.  Needs --collector fused")
 ap.add_argument("--population", type=int, default=0, metavar="K",
                 help="train K learners with the seeds --seed ... --seed + K - 1 side by side in one process "
                      "(ppo.PopulationTrainer: one collection launch and two launches per minibatch for all K; each member gets "
@@ -61,6 +66,7 @@ ap.add_argument("--out", default=None)
 args = ap.parse_args()
 if args.pbt and not args.population:
     ap.error("--pbt needs --population K")
+REWARD_NORM = True if args.reward_norm else None
 # clip_range_vf and the schedules, as PPOConfig takes them
 OPTIONS = dict(clip_range_vf=args.clip_range_vf,
                learning_rate_schedule=g.ppo.linear_schedule() if args.lr_schedule == "linear" else None,
@@ -87,9 +93,9 @@ if args.population:
                         **OPTIONS) for k in range(K)]
     if args.pbt:
         pop = g.PBTTrainer(venv, cfgs, g.PBTConfig(ready_every=args.pbt_every, fraction=args.pbt_fraction, seed=args.seed),
-                           gae=args.gae, group=args.traffic in g.ppo.GROUP_TRAFFIC)
+                           gae=args.gae, group=args.traffic in g.ppo.GROUP_TRAFFIC, reward_norm=REWARD_NORM)
     else:
-        pop = g.PopulationTrainer(venv, cfgs, gae=args.gae, group=args.traffic in g.ppo.GROUP_TRAFFIC)
+        pop = g.PopulationTrainer(venv, cfgs, gae=args.gae, group=args.traffic in g.ppo.GROUP_TRAFFIC, reward_norm=REWARD_NORM)
     pop.learn(int(args.timesteps), log=lambda r: print(json.dumps(r), flush=True))
     if args.traffic == 1:
         own, trf, goal = H.parity_reset_states(g.ACAS2DConfig(), 13, 0, 100)
@@ -107,7 +113,8 @@ venv = g.ACAS2DVecEnv(args.envs, args.traffic, device="cuda:0", dtype=torch.floa
 trainer = g.PPOTrainer(venv, g.PPOConfig(n_steps=args.n_steps, batch_size=args.batch_size, seed=args.seed, target_kl=args.target_kl,
                                          **OPTIONS),
                        collector=args.collector,
-                       use_graphs=args.collector != "eager", updater=args.updater if args.collector != "eager" else "graphs", gae=args.gae)
+                       use_graphs=args.collector != "eager", updater=args.updater if args.collector != "eager" else "graphs", gae=args.gae,
+                       reward_norm=REWARD_NORM)
 hist = trainer.learn(int(args.timesteps), log=lambda r: print(json.dumps(r), flush=True))
 
 if args.traffic == 1:
