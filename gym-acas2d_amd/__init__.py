@@ -9,6 +9,7 @@ from .config import ACAS2DConfig, OUTCOME_NAMES                      # noqa: F40
 from .sharding import shard_range                                    # noqa: F401
 from .spaces import Box                                              # noqa: F401
 from . import native, records, render, reset_parity, sharding        # noqa: F401
+from .records import episode_safety, safety_columns                  # noqa: F401
 from .vec_env import ACAS2DVecEnv, LazyInfos                         # noqa: F401
 from .env import ACAS2DEnv, GameView, register_with_gym              # noqa: F401
 from .policy import (SB3ActorPolicy, load_sb3_policy, save_sb3_policy, evaluate_policy, evaluate_policy_fused,  # noqa: F401

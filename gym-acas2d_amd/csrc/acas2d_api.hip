@@ -133,6 +133,29 @@ int acas2d_evaluate_policies_group_f32(const Acas2dConfig* cfg, const Acas2dStat
     return launch_evaluate_policies<float>(cfg, state, n_envs, policies, n_policies, n_episodes, obs_in, n_steps, seed, env_offset,
                                            n_traffic, outcome, steps, total_reward, (hipStream_t)stream, true);
 }
+// ... and the three evaluations with per-episode safety statistics (eval_stats_kernel)
+int acas2d_evaluate_policies_stats_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs,
+                                       const Acas2dPolicy* policies, int32_t n_policies, int32_t n_episodes, const void* obs_in,
+                                       int32_t n_steps, uint64_t seed, int64_t env_offset, int32_t n_traffic, uint8_t* outcome,
+                                       int32_t* steps, void* total_reward, const Acas2dEvalStats* stats, void* stream) {
+    return launch_evaluate_policies_stats<float>(cfg, state, n_envs, policies, n_policies, n_episodes, obs_in, n_steps, seed,
+                                                 env_offset, n_traffic, outcome, steps, total_reward, stats, (hipStream_t)stream);
+}
+int acas2d_evaluate_policies_stats_f64(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs,
+                                       const Acas2dPolicy* policies, int32_t n_policies, int32_t n_episodes, const void* obs_in,
+                                       int32_t n_steps, uint64_t seed, int64_t env_offset, int32_t n_traffic, uint8_t* outcome,
+                                       int32_t* steps, void* total_reward, const Acas2dEvalStats* stats, void* stream) {
+    return launch_evaluate_policies_stats<double>(cfg, state, n_envs, policies, n_policies, n_episodes, obs_in, n_steps, seed,
+                                                  env_offset, n_traffic, outcome, steps, total_reward, stats, (hipStream_t)stream);
+}
+int acas2d_evaluate_policies_stats_group_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs,
+                                             const Acas2dPolicy* policies, int32_t n_policies, int32_t n_episodes,
+                                             const void* obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
+                                             int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
+                                             const Acas2dEvalStats* stats, void* stream) {
+    return launch_evaluate_policies_stats<float>(cfg, state, n_envs, policies, n_policies, n_episodes, obs_in, n_steps, seed,
+                                                 env_offset, n_traffic, outcome, steps, total_reward, stats, (hipStream_t)stream, true);
+}
 int acas2d_reset_f32(const Acas2dConfig* cfg, const Acas2dState* state, const uint8_t* mask, void* obs,
                      int32_t do_init, uint64_t seed, int64_t env_offset, int64_t n_envs, int32_t n_traffic,
                      void* stream) {

@@ -7,3 +7,4 @@ using Elem = double;
 constexpr bool kFast = false;
 }
 #include "acas2d_launch.inl"
+ACAS2D_INSTANTIATE_EVAL_STATS

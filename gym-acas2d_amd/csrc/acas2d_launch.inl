@@ -336,10 +336,16 @@ static int launch_mode(const Launch<T>& L, const PW& pw) {
     dispatch(*L.cfg, L.sh, [&](auto fast, auto C, auto G, auto packed) {
         if constexpr ((M != Mode::Arena || (packed && sizeof(T) == 4)) && (!rollout_mode(M) || packed) &&
                       (!policy_mode(M) || G == 1 || (sizeof(T) == 4 && packed && group_policy_shape(C, G))) &&
-                      (M != Mode::CollectSet || sizeof(T) == 4))
-            hipLaunchKernelGGL((step_kernel<T, C, G, packed, fast, M>), dim3(L.g.grid), dim3(L.g.block), L.g.lds_bytes,
-                               L.stream, a[0], a[1], a[2], a[3], a[4], a[5], (int32_t)L.n_envs, (int32_t)L.g.tile_elems,
-                               L.p, rp, s, L.io, L.k0, L.k1, L.env_offset, L.N, L.n_steps, pw);
+                      (M != Mode::CollectSet || sizeof(T) == 4)) {
+            if constexpr (std::is_same<PW, PolicyEvalStatsW>::value)      // Mode::Eval with statistics: its own kernel
+                hipLaunchKernelGGL((eval_stats_kernel<T, C, G, fast>), dim3(L.g.grid), dim3(L.g.block), L.g.lds_bytes,
+                                   L.stream, a[0], a[1], a[2], a[3], a[4], a[5], (int32_t)L.n_envs, (int32_t)L.g.tile_elems,
+                                   L.p, rp, s, L.io, L.k0, L.k1, L.env_offset, L.N, L.n_steps, pw);
+            else
+                hipLaunchKernelGGL((step_kernel<T, C, G, packed, fast, M>), dim3(L.g.grid), dim3(L.g.block), L.g.lds_bytes,
+                                   L.stream, a[0], a[1], a[2], a[3], a[4], a[5], (int32_t)L.n_envs, (int32_t)L.g.tile_elems,
+                                   L.p, rp, s, L.io, L.k0, L.k1, L.env_offset, L.N, L.n_steps, pw);
+        }
     });
     return ACAS2D_OK;
 }
@@ -511,27 +517,34 @@ int launch_collect_set_group(const Acas2dConfig* cfg, const Acas2dState* st, con
 }
 
 // K stacked policies scored on shared episodes: policy k plays envs [k EP, (k + 1) EP) of the state, EP = n_episodes
-// rounded up to a whole wave; the launch covers those n_policies x EP envs
-template <typename T>
-int launch_evaluate_policies(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
+// rounded up to a whole wave; the launch covers those n_policies x EP envs.  STATS (the acas2d_evaluate_policies_stats_*
+// entry points) adds the per-episode safety statistics: eval_stats_kernel instead of step_kernel<..., Mode::Eval>.
+template <typename T, bool STATS>
+static int evaluate_policies(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
                              int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
                              int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
-                             hipStream_t stream, bool group) {
+                             hipStream_t stream, bool group, const Acas2dEvalStats* stats) {
     const int64_t ep = ((int64_t)n_episodes + 63) / 64 * 64, total = (int64_t)n_policies * ep;
-    Launch<T> L{group ? "acas2d_evaluate_policies_group" : "acas2d_evaluate_policies", cfg, st, nullptr, seed, env_offset, total,
-                n_traffic, n_steps, stream};
+    Launch<T> L{STATS ? (group ? "acas2d_evaluate_policies_stats_group" : "acas2d_evaluate_policies_stats")
+                      : (group ? "acas2d_evaluate_policies_group" : "acas2d_evaluate_policies"),
+                cfg, st, nullptr, seed, env_offset, total, n_traffic, n_steps, stream};
     L.group_policy = group;
     const auto inputs = [&] {
         if (!obs_in || !outcome || !steps || !total_reward)
             return fail("%s: obs_in and the outcome, steps and total_reward outputs are required", L.name);
+        if (STATS && !stats) return fail("%s: NULL stats", L.name);
+        if (STATS && (!stats->min_sep || !stats->min_sep_step || !stats->los_steps || !stats->max_a_lat || !stats->max_dev ||
+                      !stats->sum_dev))
+            return fail("%s: the min_sep, min_sep_step, los_steps, max_a_lat, max_dev and sum_dev outputs of stats are required",
+                        L.name);
         if (int rc = require_actor(L.name, pol)) return rc;
         if (n_policies < 1 || n_episodes < 1)
             return fail("%s: n_policies = %d, n_episodes = %d (at least 1 each)", L.name, n_policies, n_episodes);
         return ACAS2D_OK;
     };
     const auto shape = [&](Shape* sh) {
-        if (int rc = group ? group_shape<T>(L.name, "acas2d_evaluate_policies_f32", n_traffic, sh)
-                           : thread_per_env(L.name, n_traffic, sh)) return rc;
+        const char* sibling = STATS ? "acas2d_evaluate_policies_stats_f32" : "acas2d_evaluate_policies_f32";
+        if (int rc = group ? group_shape<T>(L.name, sibling, n_traffic, sh) : thread_per_env(L.name, n_traffic, sh)) return rc;
         if (n_envs >= total) return ACAS2D_OK;
         return fail("acas2d_evaluate_policies: the state holds n_envs = %lld envs, %d policies x %lld (n_episodes = %d rounded up "
                     "to 64) need %lld", (long long)n_envs, n_policies, (long long)ep, n_episodes, (long long)total);
@@ -539,13 +552,38 @@ int launch_evaluate_policies(const Acas2dConfig* cfg, const Acas2dState* st, int
     const auto go = [&] {
         if (group)
             if (int rc = require_aligned(L.name, {pol->w1t, pol->b1, pol->w2t, pol->b2})) return rc;
-        PolicyEvalW pw = actor<PolicyEvalW>(pol, obs_in);
+        using PW = typename std::conditional<STATS, PolicyEvalStatsW, PolicyEvalW>::type;
+        PW pw = actor<PW>(pol, obs_in);
         pw.res_outcome = outcome; pw.res_steps = steps; pw.res_return = total_reward;
         pw.n_episodes = n_episodes; pw.ep_stride = (int32_t)ep;
-        return launch_mode<Mode::Eval>(L, pw);
+        if constexpr (STATS) {
+            pw.st_min_sep = stats->min_sep; pw.st_min_sep_step = stats->min_sep_step; pw.st_los_steps = stats->los_steps;
+            pw.st_max_a_lat = stats->max_a_lat; pw.st_max_dev = stats->max_dev; pw.st_sum_dev = stats->sum_dev;
+        }
+        return launch_mode<Mode::Eval>(L, pw);             // (PW picks the kernel)
     };
     return prepare(L, Words{"cfg / policies", kSizes, "%s: negative env_offset"}, pol != nullptr, inputs, shape, go);
 }
+template <typename T>
+int launch_evaluate_policies(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
+                             int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
+                             int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
+                             hipStream_t stream, bool group) {
+    return evaluate_policies<T, false>(cfg, st, n_envs, pol, n_policies, n_episodes, obs_in, n_steps, seed, env_offset, n_traffic,
+                                       outcome, steps, total_reward, stream, group, nullptr);
+}
+// (the units instantiate this one LAST -- ACAS2D_INSTANTIATE_EVAL_STATS at their ends -- so that its kernels follow
+//  every other kernel of the unit, and those keep the local labels of their assembly too)
+template <typename T>
+int launch_evaluate_policies_stats(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
+                                   int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
+                                   int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
+                                   const Acas2dEvalStats* stats, hipStream_t stream, bool group) {
+    return evaluate_policies<T, true>(cfg, st, n_envs, pol, n_policies, n_episodes, obs_in, n_steps, seed, env_offset, n_traffic,
+                                      outcome, steps, total_reward, stream, group, stats);
+}
+#define ACAS2D_INSTANTIATE_EVAL_STATS \
+    namespace acas2d { template decltype(launch_evaluate_policies_stats<Elem>) launch_evaluate_policies_stats<Elem>; }
 
 template <typename T>
 int launch_reset(const Acas2dConfig* cfg, const Acas2dState* st, const uint8_t* mask, void* obs,

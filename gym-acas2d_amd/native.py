@@ -69,6 +69,12 @@ class CPpoOptions(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("old_val", "clip_range_vf", "scale")]
 
 
+class CEvalStats(C.Structure):
+    """struct Acas2dEvalStats: the six per-episode safety statistics [K][n_episodes] of acas2d_evaluate_policies_stats_*
+    (include/acas2d.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("min_sep", "min_sep_step", "los_steps", "max_a_lat", "max_dev", "sum_dev")]
+
+
 class CGae(C.Structure):
     """struct Acas2dGae: the bootstrap value and GAE over the collector's [T][E] buffers (include/acas2d.h)."""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -114,7 +120,8 @@ EXPORTS = ("acas2d_abi_version", "acas2d_config_size", "acas2d_state_size", "aca
            "acas2d_population_exploit_f32", "acas2d_population_exploit_size", "acas2d_ppo_update_guarded_set_f32",
            "acas2d_ppo_guard_size", "acas2d_ppo_update_sb3_set_f32", "acas2d_ppo_options_size",
            "acas2d_reward_normalize_f32", "acas2d_reward_norm_size", "acas2d_reward_norm_workspace_bytes",
-           "acas2d_reward_norm_pipeline_depth")
+           "acas2d_reward_norm_pipeline_depth", "acas2d_evaluate_policies_stats_f32", "acas2d_evaluate_policies_stats_f64",
+           "acas2d_evaluate_policies_stats_group_f32")
 
 
 class NativeLibraryError(RuntimeError):
@@ -182,6 +189,13 @@ def lib():
         f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.c_int64, C.POINTER(CPolicy), C.c_int32, C.c_int32,
                       C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                       C.c_void_p]
+    for name in ("acas2d_evaluate_policies_stats_f32", "acas2d_evaluate_policies_stats_f64",
+                 "acas2d_evaluate_policies_stats_group_f32"):                  # the plain siblings' list, stats before stream
+        f = getattr(L, name)
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.c_int64, C.POINTER(CPolicy), C.c_int32, C.c_int32,
+                      C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                      C.POINTER(CEvalStats), C.c_void_p]
     for name in ("acas2d_collect_set_f32", "acas2d_collect_set_group_f32"):
         f = getattr(L, name)
         f.restype = C.c_int

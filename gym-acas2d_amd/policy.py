@@ -158,8 +158,16 @@ def evaluate_policy_fused(policy, own, traffic, goal=None, dtype=torch.float64, 
             "path_length": step_len * (steps - 1), "unfinished": int((~fin).sum())}
 
 
+def evaluate_policies_entry(dtype, group=False, safety=False):
+    """The name of the C entry point evaluate_policies_fused() calls for (dtype, group, safety)."""
+    if group and dtype != torch.float32:
+        raise ValueError("evaluate_policies_fused(group=True) is float32 only, got %s" % (dtype,))
+    return "acas2d_evaluate_policies%s%s_%s" % ("_stats" if safety else "", "_group" if group else "",
+                                                "f32" if dtype == torch.float32 else "f64")
+
+
 def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float64, device="cuda:0", config=None,
-                            max_steps=None, group=False):
+                            max_steps=None, group=False, safety=False):
     """evaluate_policy_fused() for K policies on the SAME E episodes in ONE launch (acas2d_evaluate_policies_*):
     scoring the checkpoints of a run, or the policies of a seed sweep, together.  `policies`: `SB3ActorPolicy` /
     `ppo.ActorCritic` objects or paths of SB3 zips / .npz exports.  The episodes `own` [E,4] / `traffic` [E,N,4] /
@@ -167,13 +175,17 @@ def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float
     and is not scored).  Each env stops at the end of its first episode, and nothing per step is stored.
     Returns evaluate_policy_fused()'s keys as [K, E] numpy arrays (outcome, steps, total_reward, path_length) and
     `unfinished` [K]; row k equals evaluate_policy_fused(policies[k], ...) bit for bit.  group=True: the
-    group-cooperative float32 launch (acas2d_evaluate_policies_group_f32, N in {8, 16, 32, 64})."""
+    group-cooperative float32 launch (acas2d_evaluate_policies_group_f32, N in {8, 16, 32, 64}).
+    safety=True: the launch with per-episode safety statistics (acas2d_evaluate_policies_stats_*), over the rows of the
+    episode's step() calls (records.episode_safety(): row 0 of the reference's record lists is not among them) -- six
+    more [K, E] keys in `dtype`'s precision: min_separation, min_separation_step (1-based step row of the minimum),
+    los_steps (step rows inside the safe distance), max_abs_a_lat, max_abs_deviation and mean_abs_deviation (the sum of
+    |d_dev| over the steps - 1 rows; 0 where steps <= 1).  An unfinished episode has 0 in all of them."""
     from . import native
     from .vec_env import ACAS2DVecEnv
     if not policies:
         raise ValueError("evaluate_policies_fused needs at least one policy")
-    if group and dtype != torch.float32:
-        raise ValueError("evaluate_policies_fused(group=True) is float32 only, got %s" % (dtype,))
+    entry = evaluate_policies_entry(dtype, group, safety)
     own, traffic = np.asarray(own), np.asarray(traffic)
     E, N = own.shape[0], traffic.shape[1]
     K, EP = len(policies), (own.shape[0] + 63) // 64 * 64
@@ -200,16 +212,25 @@ def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float
     steps = torch.empty(K, E, dtype=torch.int32, device=dev)
     ret = torch.empty(K, E, dtype=dtype, device=dev)
     pw = native.CPolicy(*[t.data_ptr() for t in keep], 64, 0)
-    L = native.lib()
-    if group:
-        fn = L.acas2d_evaluate_policies_group_f32
-    else:
-        fn = L.acas2d_evaluate_policies_f32 if dtype == torch.float32 else L.acas2d_evaluate_policies_f64
+    fn = getattr(native.lib(), entry)
+    extra = ()
+    if safety:
+        st_f = torch.empty(4, K, E, dtype=dtype, device=dev)                    # min_sep, max_a_lat, max_dev, sum_dev
+        st_i = torch.empty(2, K, E, dtype=torch.int32, device=dev)              # min_sep_step, los_steps
+        cstats = native.CEvalStats(st_f[0].data_ptr(), st_i[0].data_ptr(), st_i[1].data_ptr(), st_f[1].data_ptr(),
+                                   st_f[2].data_ptr(), st_f[3].data_ptr())
+        extra = (C.byref(cstats),)
     with torch.cuda.device(dev):
         native.check(fn(C.byref(v._ccfg), C.byref(v._cstate), K * EP, C.byref(pw), K, E, v.outputs["obs"].data_ptr(), T,
                         v.seed_value, v.env_offset, N, outcome.data_ptr(), steps.data_ptr(), ret.data_ptr(),
-                        v._stream()))
+                        *extra, v._stream()))
     oc, st = outcome.cpu().numpy(), steps.cpu().numpy()
     step_len = v.config.airspeed * v.config.dt
-    return {"outcome": oc, "steps": st, "total_reward": ret.cpu().numpy().astype(np.float64),
-            "path_length": step_len * (st - 1), "unfinished": (oc == 0).sum(1)}
+    res = {"outcome": oc, "steps": st, "total_reward": ret.cpu().numpy().astype(np.float64),
+           "path_length": step_len * (st - 1), "unfinished": (oc == 0).sum(1)}
+    if safety:
+        f, i = st_f.cpu().numpy(), st_i.cpu().numpy()
+        rows = np.maximum(st - 1, 1).astype(f.dtype)
+        res.update(min_separation=f[0], min_separation_step=i[0], los_steps=i[1], max_abs_a_lat=f[1],
+                   max_abs_deviation=f[2], mean_abs_deviation=np.where(st > 1, f[3] / rows, f.dtype.type(0)))
+    return res

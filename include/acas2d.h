@@ -343,6 +343,52 @@ int acas2d_evaluate_policies_group_f32(const Acas2dConfig *cfg, const Acas2dStat
                                        void *stream);
 
 /*
+ * acas2d_evaluate_policies_stats_f32 / _f64 / _group_f32: the three evaluation entry points above with per-episode
+ * safety statistics -- how close the aircraft came to traffic, for how long it was inside the safe distance, how hard it
+ * manoeuvred and how far it left its path: the columns of testing_main.py's CSV that the fused evaluator did not give.
+ * Additive to ABI 7.  The arguments of the plain sibling with `stats` in front of `stream`; the same work shapes
+ * (thread-per-env n_traffic in {1, 2, 3, 4, 8} float32 and {1, 2, 3, 4} float64, group {8, 16, 32, 64} float32); outcome,
+ * steps and total_reward equal the sibling's bit for bit.
+ * Six more outputs, [K][n_episodes] like the other three, written with them at the episode's done.  They cover the ROWS
+ * OF THE EPISODE'S step() CALLS: rows 1 .. n-1 of the reference's record lists.  Row 0 of those lists, which
+ * ACAS2DGame.__init__ appends before the first step, is excluded.
+ *   min_sep       T      min over step rows of the minimum separation as action() logs it (game.py:236-237: the player
+ *                        has moved, the traffic not yet) -- the values of d_sep_record
+ *   min_sep_step  int32  1-based index of the FIRST step row that attains it = its position in d_sep_record
+ *   los_steps     int32  number of step rows with d_sep < safe_distance
+ *   max_a_lat     T      max over step rows of |a_lat|
+ *   max_dev       T      max over step rows of |d_dev| (d_dev is signed in the reference)
+ *   sum_dev       T      sum over step rows of |d_dev|: plain adds in step order, so a sequential host sum in T gives the
+ *                        same bits; the mean over the episode's rows is sum_dev / (steps - 1)
+ * The minimum and the maxima are kept as  x < m ? x : m  /  x > m ? x : m  from +inf / 0, so a NaN never replaces a held
+ * value and never counts as a loss of separation (min_sep_step stays 0 if no row ever compared below +inf).  An
+ * episode not done within n_steps gets 0 in all six, as in the other three.
+ * Rejected with ACAS2D_EINVAL before anything is launched: everything the sibling rejects, a NULL stats, a NULL member
+ * of it.
+ */
+typedef struct Acas2dEvalStats {
+    void *min_sep;                 /* T[K][n_episodes] */
+    int32_t *min_sep_step;         /* [K][n_episodes] */
+    int32_t *los_steps;            /* [K][n_episodes] */
+    void *max_a_lat, *max_dev, *sum_dev;   /* T[K][n_episodes] */
+} Acas2dEvalStats;
+int acas2d_evaluate_policies_stats_f32(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                                       const Acas2dPolicy *policies, int32_t n_policies, int32_t n_episodes,
+                                       const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
+                                       int32_t n_traffic, uint8_t *outcome, int32_t *steps, void *total_reward,
+                                       const Acas2dEvalStats *stats, void *stream);
+int acas2d_evaluate_policies_stats_f64(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                                       const Acas2dPolicy *policies, int32_t n_policies, int32_t n_episodes,
+                                       const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
+                                       int32_t n_traffic, uint8_t *outcome, int32_t *steps, void *total_reward,
+                                       const Acas2dEvalStats *stats, void *stream);
+int acas2d_evaluate_policies_stats_group_f32(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                                             const Acas2dPolicy *policies, int32_t n_policies, int32_t n_episodes,
+                                             const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
+                                             int32_t n_traffic, uint8_t *outcome, int32_t *steps, void *total_reward,
+                                             const Acas2dEvalStats *stats, void *stream);
+
+/*
  * acas2d_collect_set_group_f32: acas2d_collect_set_f32 for n_traffic in {8, 16, 32, 64}, float32 -- the same arguments,
  * layouts and outputs.  Additive to ABI 7.  The launch is acas2d_collect_group_f32's (the env's G lanes of the packed work
  * shapes (4,2) (4,4) (4,8) (4,16) evaluate the two networks together) with the member found per wavefront: a wavefront

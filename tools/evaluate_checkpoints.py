@@ -2,9 +2,12 @@
 """checkpoint_testing_main.py for a whole training run: every `model_<n>_steps.zip` under DIR (and DIR/checkpoints)
 plus `best_model.zip`, scored deterministically on the reference's 100 test episodes (the first 100 games of the
 seed-13 MT19937 stream, as testing_main.py and tools/train_ppo.py draw them) in ONE launch (evaluate_policies_fused).
-One JSON line per checkpoint, in timestep order, best_model.zip last.
+One JSON line per checkpoint, in timestep order, best_model.zip last.  --safety adds the per-episode safety statistics
+of the same launch (evaluate_policies_fused(safety=True)) over the finished episodes: the mean and the worst minimum
+separation, the share of episodes that lost separation (los_steps > 0), the mean of the largest |a_lat| and the mean of
+the mean |deviation| from the planned path.
 
-    python tools/evaluate_checkpoints.py DIR [--dtype float64|float32] [--episodes 100]
+    python tools/evaluate_checkpoints.py DIR [--dtype float64|float32] [--episodes 100] [--safety]
 """
 import argparse
 import glob
@@ -14,6 +17,7 @@ import random
 import re
 import sys
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,6 +28,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("dir")
 ap.add_argument("--dtype", choices=("float64", "float32"), default="float64")
 ap.add_argument("--episodes", type=int, default=100)
+ap.add_argument("--safety", action="store_true")
 args = ap.parse_args()
 
 steps_of = lambda p: int(re.search(r"model_(\d+)_steps\.zip$", p).group(1))  # noqa: E731
@@ -35,10 +40,17 @@ if not paths:
     sys.exit("no model_*_steps.zip or best_model.zip under %s" % args.dir)
 
 own, trf, goal = g.reset_parity.draw_episodes(g.ACAS2DConfig(), args.episodes, random.Random(13))
-out = g.evaluate_policies_fused(paths, own, trf, goal, dtype=getattr(torch, args.dtype))
+out = g.evaluate_policies_fused(paths, own, trf, goal, dtype=getattr(torch, args.dtype), safety=args.safety)
 for k, p in enumerate(paths):
     r, s, oc = out["total_reward"][k], out["steps"][k], out["outcome"][k]
-    print(json.dumps({"checkpoint": os.path.relpath(p, args.dir), "timesteps": steps_of(p) if p != best else None,
-                      "mean_return": float(r.mean()), "std_return": float(r.std()), "mean_steps": float(s.mean()),
-                      "goal": int((oc == 1).sum()), "collision": int((oc == 2).sum()), "timeout": int((oc == 3).sum()),
-                      "unfinished": int(out["unfinished"][k])}), flush=True)
+    row = {"checkpoint": os.path.relpath(p, args.dir), "timesteps": steps_of(p) if p != best else None,
+           "mean_return": float(r.mean()), "std_return": float(r.std()), "mean_steps": float(s.mean()),
+           "goal": int((oc == 1).sum()), "collision": int((oc == 2).sum()), "timeout": int((oc == 3).sum()),
+           "unfinished": int(out["unfinished"][k])}
+    if args.safety:
+        fin = oc != 0                                    # an unfinished episode holds zeros, not statistics
+        stat = lambda key, f: float(f(out[key][k][fin])) if fin.any() else None  # noqa: E731
+        row.update({"mean_min_separation": stat("min_separation", np.mean), "worst_min_separation": stat("min_separation", np.min),
+                    "los_share": stat("los_steps", lambda a: (a > 0).mean()), "mean_max_abs_a_lat": stat("max_abs_a_lat", np.mean),
+                    "mean_abs_deviation": stat("mean_abs_deviation", np.mean)})
+    print(json.dumps(row), flush=True)
