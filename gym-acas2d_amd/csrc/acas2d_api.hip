@@ -156,6 +156,26 @@ int acas2d_evaluate_policies_stats_group_f32(const Acas2dConfig* cfg, const Acas
     return launch_evaluate_policies_stats<float>(cfg, state, n_envs, policies, n_policies, n_episodes, obs_in, n_steps, seed,
                                                  env_offset, n_traffic, outcome, steps, total_reward, stats, (hipStream_t)stream, true);
 }
+// ... and the Monte Carlo campaign on the same three families (monte_carlo_kernel)
+size_t acas2d_monte_carlo_size(void) { return sizeof(Acas2dMonteCarlo); }
+int acas2d_monte_carlo_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs, const Acas2dPolicy* policies,
+                           int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
+                           int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc, void* stream) {
+    return launch_monte_carlo<float>(cfg, state, n_envs, policies, n_policies, n_lanes, obs_in, n_steps, seed, env_offset,
+                                     n_traffic, mc, (hipStream_t)stream);
+}
+int acas2d_monte_carlo_f64(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs, const Acas2dPolicy* policies,
+                           int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
+                           int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc, void* stream) {
+    return launch_monte_carlo<double>(cfg, state, n_envs, policies, n_policies, n_lanes, obs_in, n_steps, seed, env_offset,
+                                      n_traffic, mc, (hipStream_t)stream);
+}
+int acas2d_monte_carlo_group_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs, const Acas2dPolicy* policies,
+                                 int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
+                                 int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc, void* stream) {
+    return launch_monte_carlo<float>(cfg, state, n_envs, policies, n_policies, n_lanes, obs_in, n_steps, seed, env_offset,
+                                     n_traffic, mc, (hipStream_t)stream, true);
+}
 int acas2d_reset_f32(const Acas2dConfig* cfg, const Acas2dState* state, const uint8_t* mask, void* obs,
                      int32_t do_init, uint64_t seed, int64_t env_offset, int64_t n_envs, int32_t n_traffic,
                      void* stream) {

@@ -14,6 +14,7 @@ template decltype(launch_collect_set<float>) launch_collect_set<float>;
 template decltype(launch_collect_set_group<float>) launch_collect_set_group<float>;
 }
 ACAS2D_INSTANTIATE_EVAL_STATS
+ACAS2D_INSTANTIATE_MONTE_CARLO
 
 #ifdef ACAS2D_STAMPS
 extern "C" int acas2d_debug_set_stamps_f32(unsigned long long* buf) {

@@ -8,3 +8,4 @@ constexpr bool kFast = false;
 }
 #include "acas2d_launch.inl"
 ACAS2D_INSTANTIATE_EVAL_STATS
+ACAS2D_INSTANTIATE_MONTE_CARLO

@@ -675,6 +675,14 @@ __device__ __forceinline__ OwnCtx<T> own_context_fresh(const Params<T>& p, const
     }
 }
 
+// own_context_fresh(), or with OBSERVED own_context() as observe() calls it (a_lat = 0): the same bits as the first
+// observation of that state injected and observed (reset_kernel, do_init = 0)
+template <typename T, bool FAST, bool OBSERVED, typename R>
+__device__ __forceinline__ OwnCtx<T> fresh_context(const Params<T>& p, const R& rp, const Own<T>& o) {
+    if constexpr (OBSERVED) return own_context<T, FAST>(p, o);
+    else return own_context_fresh<T, FAST>(p, rp, o);
+}
+
 // One traffic aircraft, part 1 -- the traffic half of game.py:222-247 action(): wrap the heading,
 // sin / cos of it, Euler step when `move`.  In/out: tx, ty (moved), tpsi (wrapped); out: st, ct.
 template <typename T, bool FAST>
@@ -1099,7 +1107,9 @@ __device__ __forceinline__ Own<T> reset_env(const R& rp, const State<T>& s, uint
 // own_psi) and nothing but term_obs is stored to memory here -- the owner lanes pick the state up
 // and it leaves with the wave's ordinary, coalesced state stores and its single tile flush.  Without
 // it (generic walk) the entity lanes store the new state themselves and the caller re-flushes the row.
-template <typename T, bool FAST, int NS, bool HANDOFF, typename R>
+// OBSERVED (the Monte Carlo kernel): the player side of the first observation by own_context(), the way observe() -- and so
+// reset_kernel with do_init = 0 -- sees an injected state, instead of own_context_fresh()'s host-evaluated goal terms.
+template <typename T, bool FAST, int NS, bool HANDOFF, typename R, bool OBSERVED = false>
 __device__ __forceinline__ void wave_reset_env(const Params<T>& p, const R& rp, const State<T>& s,
                                                const StepIO<T>& io, uint32_t k0, uint32_t k1, uint64_t gid,
                                                int e, int N_dyn, int lane, T total, int32_t steps,
@@ -1155,7 +1165,7 @@ __device__ __forceinline__ void wave_reset_env(const Params<T>& p, const R& rp, 
     if constexpr (kOneTermPass) { if (io.term_obs && lane < D) (io.term_obs + e * D)[lane] = term_v; }
     psi_own = lane_value(psi_own, 0);
     const Own<T> o{(T)rp.own_x0, (T)rp.own_y0, psi_own, (T)rp.own_v, T(0), (T)rp.goal_x, (T)rp.goal_y};
-    const OwnCtx<T> c = own_context_fresh<T, FAST>(p, rp, o);
+    const OwnCtx<T> c = fresh_context<T, FAST, OBSERVED>(p, rp, o);
 
     ACAS2D_STAMP(10, wave_dbg, lane, false);
     // environment.py:44-48: the new episode's first observation (steps becomes 1)
@@ -1213,7 +1223,7 @@ template <typename T, int NS> struct SlotLayout {
 // Resets the envs named by the lowest min(SLOTS, popcount(dm)) bits of `dm` (bit = lane of the env's
 // group leader, i.e. el * G); returns the mask of those bits.  Owner lanes find their slot as the rank of
 // their bit in the returned mask.  Whole wave, wave-uniform arguments.
-template <typename T, bool FAST, int NS, int G, typename R>
+template <typename T, bool FAST, int NS, int G, typename R, bool OBSERVED = false>
 __device__ __forceinline__ unsigned long long wave_reset_slots(const Params<T>& p, const R& rp,
                                                                const StepIO<T>& io, uint32_t k0, uint32_t k1,
                                                                uint64_t gid_wave, unsigned long long dm, int lane,
@@ -1278,7 +1288,7 @@ __device__ __forceinline__ unsigned long long wave_reset_slots(const Params<T>& 
         psi_own = have ? scr[4 * N] : T(0);
     }
     const Own<T> o{(T)rp.own_x0, (T)rp.own_y0, psi_own, (T)rp.own_v, T(0), (T)rp.goal_x, (T)rp.goal_y};
-    const OwnCtx<T> c = own_context_fresh<T, FAST>(p, rp, o);
+    const OwnCtx<T> c = fresh_context<T, FAST, OBSERVED>(p, rp, o);
     // environment.py:44-48: the new episodes' first observations (steps becomes 1)
     if (mine) {
         if (ent >= 1) {
@@ -1427,6 +1437,28 @@ struct PolicyEvalStatsW : PolicyEvalW {
     int32_t *st_min_sep_step, *st_los_steps;         // [K][n_episodes]
     void *st_max_a_lat, *st_max_dev, *st_sum_dev;    // T[K][n_episodes]
 };
+
+// MC on top of STATS (acas2d_monte_carlo_*; monte_carlo_kernel): n_episodes is the lane count of a block, a lane plays
+// mc_episodes drawn episodes from counter mc_first on and folds each into these accumulators (include/acas2d.h,
+// Acas2dMonteCarlo); the res_* / st_* outputs of the bases are not written.
+struct PolicyMonteCarloW : PolicyEvalStatsW {
+    unsigned long long *mc_outcome_count, *mc_sum_steps, *mc_los_episodes, *mc_sum_los_steps, *mc_sep_hist;
+    double *mc_return_sum, *mc_return_sq;
+    void* mc_worst_sep;                              // T[K][n_lanes]
+    uint32_t* mc_worst_episode;
+    int32_t mc_n_bins, mc_episodes;
+    uint32_t mc_first;
+    float mc_inv_bin_f;                              // inv_bin_width as T: the float32 kernels read this one,
+    double mc_inv_bin_d;                             // the float64 kernels this one
+};
+
+// the body's view of them: its MC statements name these fields in every kernel that includes it and are compiled in
+// monte_carlo_kernel only (eval_stats_kernel's pw is no dependent type, so `pw.mc_...` would not parse there)
+template <typename PW>
+__device__ __forceinline__ const PolicyMonteCarloW* monte_carlo_args(const PW& pw) {
+    if constexpr (std::is_base_of<PolicyMonteCarloW, PW>::value) return &pw;
+    else return nullptr;
+}
 
 // tanh(x) = 1 - 2 / (exp(2x) + 1) on v_exp_f32 / v_rcp_f32: abs error < 2e-7 over the reals
 // (saturates cleanly: exp -> inf gives 1, exp -> 0 gives -1).
@@ -1668,7 +1700,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
                                                       Params<T> p_arg, StepResetParams<T, rollout_mode(M)> rp_arg, State<T> s_arg,
                                                       StepIO<T> io_arg, uint32_t k0, uint32_t k1,
                                                       int64_t env_offset, int N_arg, int n_steps, PolicyArg<M == Mode::Eval> pw) {
-    constexpr bool STATS = false;
+    constexpr bool STATS = false, MC = false;
 #include "acas2d_step_body.inl"
 }
 // Mode::Eval with STATS: step_kernel's arguments (and so the same preloaded ones) with PolicyEvalStatsW at the end.
@@ -1679,7 +1711,21 @@ __global__ __launch_bounds__(kBlock) void eval_stats_kernel(const T* a0, const T
                                                             Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
                                                             StepIO<T> io_arg, uint32_t k0, uint32_t k1,
                                                             int64_t env_offset, int N_arg, int n_steps, PolicyEvalStatsW pw) {
-    constexpr bool PACKED = true, STATS = true;
+    constexpr bool PACKED = true, STATS = true, MC = false;
+    constexpr Mode M = Mode::Eval;
+#include "acas2d_step_body.inl"
+}
+// Mode::Eval with STATS and MC (acas2d_monte_carlo_*): a lane plays PolicyMonteCarloW::mc_episodes drawn episodes, one
+// after another -- the in-step reset of the rollout modes draws the next one (its per-step outputs compiled out, its RNG
+// index the lane's index within its policy's block) -- and folds each finished episode into the launch's accumulators.
+// A kernel of its own for the reason eval_stats_kernel is one.
+template <typename T, int C, int G, bool FAST>
+__global__ __launch_bounds__(kBlock) void monte_carlo_kernel(const T* a0, const T* a1, const T* a2, const T* a3, const T* a4,
+                                                             const T* a5, int32_t e_n_envs, int32_t tile_elems,
+                                                             Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
+                                                             StepIO<T> io_arg, uint32_t k0, uint32_t k1,
+                                                             int64_t env_offset, int N_arg, int n_steps, PolicyMonteCarloW pw) {
+    constexpr bool PACKED = true, STATS = true, MC = true;
     constexpr Mode M = Mode::Eval;
 #include "acas2d_step_body.inl"
 }
@@ -1770,6 +1816,11 @@ int launch_evaluate_policies_stats(const Acas2dConfig* cfg, const Acas2dState* s
                                    int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
                                    int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
                                    const Acas2dEvalStats* stats, hipStream_t stream, bool group = false);
+// acas2d_monte_carlo_*: monte_carlo_kernel
+template <typename T>
+int launch_monte_carlo(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
+                       int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
+                       int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc, hipStream_t stream, bool group = false);
 // acas2d_collect_set_f32 and acas2d_collect_set_group_f32 (float32 only: acas2d_f32.hip instantiates them)
 template <typename T>
 int launch_collect_set(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,

@@ -337,7 +337,11 @@ static int launch_mode(const Launch<T>& L, const PW& pw) {
         if constexpr ((M != Mode::Arena || (packed && sizeof(T) == 4)) && (!rollout_mode(M) || packed) &&
                       (!policy_mode(M) || G == 1 || (sizeof(T) == 4 && packed && group_policy_shape(C, G))) &&
                       (M != Mode::CollectSet || sizeof(T) == 4)) {
-            if constexpr (std::is_same<PW, PolicyEvalStatsW>::value)      // Mode::Eval with statistics: its own kernel
+            if constexpr (std::is_same<PW, PolicyMonteCarloW>::value)     // ... and the Monte Carlo campaign: its own too
+                hipLaunchKernelGGL((monte_carlo_kernel<T, C, G, fast>), dim3(L.g.grid), dim3(L.g.block), L.g.lds_bytes,
+                                   L.stream, a[0], a[1], a[2], a[3], a[4], a[5], (int32_t)L.n_envs, (int32_t)L.g.tile_elems,
+                                   L.p, rp, s, L.io, L.k0, L.k1, L.env_offset, L.N, L.n_steps, pw);
+            else if constexpr (std::is_same<PW, PolicyEvalStatsW>::value) // Mode::Eval with statistics: its own kernel
                 hipLaunchKernelGGL((eval_stats_kernel<T, C, G, fast>), dim3(L.g.grid), dim3(L.g.block), L.g.lds_bytes,
                                    L.stream, a[0], a[1], a[2], a[3], a[4], a[5], (int32_t)L.n_envs, (int32_t)L.g.tile_elems,
                                    L.p, rp, s, L.io, L.k0, L.k1, L.env_offset, L.N, L.n_steps, pw);
@@ -584,6 +588,64 @@ int launch_evaluate_policies_stats(const Acas2dConfig* cfg, const Acas2dState* s
 }
 #define ACAS2D_INSTANTIATE_EVAL_STATS \
     namespace acas2d { template decltype(launch_evaluate_policies_stats<Elem>) launch_evaluate_policies_stats<Elem>; }
+
+// acas2d_monte_carlo_*: evaluate_policies()'s blocks of lanes, each lane playing mc->episodes_per_lane drawn episodes and
+// folding them into mc's accumulators (monte_carlo_kernel).  The checks and words of evaluate_policies<T, true>, then its own.
+// (Instantiated after the stats launcher -- ACAS2D_INSTANTIATE_MONTE_CARLO -- for the same reason.)
+template <typename T>
+int launch_monte_carlo(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
+                       int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
+                       int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc, hipStream_t stream, bool group) {
+    const int64_t ep = ((int64_t)n_lanes + 63) / 64 * 64, total = (int64_t)n_policies * ep;
+    Launch<T> L{group ? "acas2d_monte_carlo_group" : "acas2d_monte_carlo", cfg, st, nullptr, seed, env_offset, total, n_traffic,
+                n_steps, stream};
+    L.group_policy = group;
+    const auto inputs = [&] {
+        if (!obs_in) return fail("%s: obs_in is required", L.name);
+        if (!mc) return fail("%s: NULL mc", L.name);
+        if (!mc->outcome_count || !mc->sum_steps || !mc->los_episodes || !mc->sum_los_steps || !mc->sep_hist ||
+            !mc->lane_return_sum || !mc->lane_return_sq || !mc->lane_worst_sep || !mc->lane_worst_episode)
+            return fail("%s: the nine accumulators of mc are required", L.name);
+        if (int rc = require_actor(L.name, pol)) return rc;
+        if (n_policies < 1 || n_lanes < 1)
+            return fail("%s: n_policies = %d, n_lanes = %d (at least 1 each)", L.name, n_policies, n_lanes);
+        if (mc->episodes_per_lane < 1) return fail("%s: episodes_per_lane = %d (at least 1)", L.name, mc->episodes_per_lane);
+        if (mc->n_bins < 1) return fail("%s: n_bins = %d (at least 1)", L.name, mc->n_bins);
+        if ((uint64_t)mc->first_episode + (uint64_t)mc->episodes_per_lane > (1ull << 32))
+            return fail("%s: first_episode = %u + episodes_per_lane = %d exceeds the 32-bit episode counter", L.name,
+                        mc->first_episode, mc->episodes_per_lane);
+        const int64_t need = (int64_t)mc->episodes_per_lane * cfg->max_steps;
+        if (cfg->max_steps < 1 || need + mc->episodes_per_lane > 0x7fffffffLL || mc->episodes_per_lane > (1 << 24) || n_steps < need)
+            return fail("%s: n_steps = %d does not cover episodes_per_lane = %d episodes of max_steps = %d steps (%lld needed; "
+                        "episodes_per_lane x (max_steps + 1) must fit an int32, episodes_per_lane <= 2^24)", L.name, n_steps,
+                        mc->episodes_per_lane, cfg->max_steps, (long long)need);
+        return ACAS2D_OK;
+    };
+    const auto shape = [&](Shape* sh) {
+        if (int rc = group ? group_shape<T>(L.name, "acas2d_monte_carlo_f32", n_traffic, sh) : thread_per_env(L.name, n_traffic, sh))
+            return rc;
+        if (n_envs >= total) return ACAS2D_OK;
+        return fail("%s: the state holds n_envs = %lld envs, %d policies x %lld (n_lanes = %d rounded up to 64) need %lld", L.name,
+                    (long long)n_envs, n_policies, (long long)ep, n_lanes, (long long)total);
+    };
+    const auto go = [&] {
+        if (group)
+            if (int rc = require_aligned(L.name, {pol->w1t, pol->b1, pol->w2t, pol->b2})) return rc;
+        PolicyMonteCarloW pw = actor<PolicyMonteCarloW>(pol, obs_in);
+        pw.n_episodes = n_lanes; pw.ep_stride = (int32_t)ep;
+        const auto u64 = [](int64_t* q) { return reinterpret_cast<unsigned long long*>(q); };
+        pw.mc_outcome_count = u64(mc->outcome_count); pw.mc_sum_steps = u64(mc->sum_steps);
+        pw.mc_los_episodes = u64(mc->los_episodes); pw.mc_sum_los_steps = u64(mc->sum_los_steps); pw.mc_sep_hist = u64(mc->sep_hist);
+        pw.mc_return_sum = mc->lane_return_sum; pw.mc_return_sq = mc->lane_return_sq;
+        pw.mc_worst_sep = mc->lane_worst_sep; pw.mc_worst_episode = mc->lane_worst_episode;
+        pw.mc_n_bins = mc->n_bins; pw.mc_episodes = mc->episodes_per_lane; pw.mc_first = mc->first_episode;
+        pw.mc_inv_bin_f = (float)mc->inv_bin_width; pw.mc_inv_bin_d = mc->inv_bin_width;
+        return launch_mode<Mode::Eval>(L, pw);             // (PW picks the kernel)
+    };
+    return prepare(L, Words{"cfg / policies", kSizes, "%s: negative env_offset"}, pol != nullptr, inputs, shape, go);
+}
+#define ACAS2D_INSTANTIATE_MONTE_CARLO \
+    namespace acas2d { template decltype(launch_monte_carlo<Elem>) launch_monte_carlo<Elem>; }
 
 template <typename T>
 int launch_reset(const Acas2dConfig* cfg, const Acas2dState* st, const uint8_t* mask, void* obs,

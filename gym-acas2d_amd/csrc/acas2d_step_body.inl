@@ -1,6 +1,6 @@
-// acas2d_step_body.inl -- the body of step_kernel and eval_stats_kernel (acas2d_kernels.hpp, where the modes and what
-// each one implies are described), included inside both.  It expects the including kernel's template parameters
-// T, C, G, PACKED, FAST, M (or constants of those names), the constant STATS, and the kernel's arguments a0 .. a5,
+// acas2d_step_body.inl -- the body of step_kernel, eval_stats_kernel and monte_carlo_kernel (acas2d_kernels.hpp, where the
+// modes and what each one implies are described), included inside all three.  It expects the including kernel's template
+// parameters T, C, G, PACKED, FAST, M (or constants of those names), the constants STATS and MC, and the kernel's arguments a0 .. a5,
 // e_n_envs, tile_elems, p_arg, rp_arg, s_arg, io_arg, k0, k1, env_offset, N_arg, n_steps, pw.
     constexpr bool AUTO_RESET = M != Mode::Latch, ROLLOUT = rollout_mode(M);
     constexpr bool POLICY = policy_mode(M), SAMPLE = sample_mode(M);
@@ -192,6 +192,20 @@
         pw.w3 += (size_t)kp * kPolicyHidden; pw.b3 += kp;
     }
     (void)running; (void)res_i;
+    // MC: the lane's RNG index is its index WITHIN its policy's block (every policy meets the same encounters), its
+    // episode counter the launch's first one, and the launch's integer sums stay in registers: the four episode COUNTS
+    // per wave (ballots, scalar registers), the two sums per lane
+    uint64_t mc_gid_wave = 0;
+    int32_t mc_n1 = 0, mc_n2 = 0, mc_n3 = 0, mc_los_eps = 0;      // wave-uniform
+    int32_t mc_steps = 0, mc_los = 0;                            // per lane
+    uint32_t mc_kp = 0;
+    (void)mc_gid_wave; (void)mc_n1; (void)mc_n2; (void)mc_n3; (void)mc_steps; (void)mc_los_eps; (void)mc_los; (void)mc_kp;
+    if constexpr (MC) {
+        const PolicyMonteCarloW* const mcw = monte_carlo_args(pw);
+        mc_kp = __builtin_amdgcn_readfirstlane(e_wave32 / (uint32_t)pw.ep_stride);
+        mc_gid_wave = (uint64_t)env_offset + (uint64_t)(e_wave32 - mc_kp * (uint32_t)pw.ep_stride);
+        episode = mcw->mc_first;
+    }
     // STATS: the running statistics of the lane's episode (PolicyEvalStatsW)
     T st_min = T(1) / T(0), st_a_lat = T(0), st_dev = T(0), st_sum = T(0);
     int32_t st_min_step = 0, st_los = 0;
@@ -213,6 +227,9 @@
         pw.nk0 = (uint32_t)key; pw.nk1 = (uint32_t)(key >> 32);
     }
     for (int t = 0; t < T_steps; ++t) {
+        // (MC: the running minimum stays an ordinary register over the loop.  Left alone, the float64 FAST kernels at
+        //  N = 2, 3, 4 keep its +inf start in an accumulation register pair and count that as a spill.)
+        if constexpr (MC) asm volatile("" : "+v"(st_min));
         // outputs of step t: [t][E] / [t][E][D] slices (t == 0 for the per-step launch)
         const int64_t te = ROLLOUT ? (int64_t)t * n_envs : 0;
         const StepIO<T> io{io0.actions + te, io0.obs + te * D, io0.reward + te, io0.done + te, io0.outcome + te,
@@ -347,7 +364,37 @@
                     st_sum = st_sum + ad;
                 }
             }
-            if constexpr (EVAL) {
+            if constexpr (MC) {
+                if (!running) oc = 0;                     // a lane with no episode left finishes (and redraws) nothing
+                const bool lead = j == 0;                 // (a group finishes together: one count per env)
+                mc_n1 += __popcll(__ballot(lead && oc == 1)); mc_n2 += __popcll(__ballot(lead && oc == 2));
+                mc_n3 += __popcll(__ballot(lead && oc == 3)); mc_los_eps += __popcll(__ballot(lead && oc != 0 && st_los > 0));
+                if (oc != 0) {                            // an episode ends: fold it, restart the statistics, go on
+                    const PolicyMonteCarloW* const mcw = monte_carlo_args(pw);
+                    mc_steps += steps;
+                    mc_los += st_los;
+                    if (j == 0) {                         // (a group finishes together: its first lane holds its accumulators)
+                        const T inv_w = sizeof(T) == 4 ? (T)mcw->mc_inv_bin_f : (T)mcw->mc_inv_bin_d;
+                        const T scaled = st_min * inv_w;
+                        int b = mcw->mc_n_bins - 1;         // past the last edge, +-inf, NaN (records.separation_bin())
+                        if (m_abs(scaled) < T(2147483648.0)) {
+                            const int q = (int)scaled;
+                            if (q < mcw->mc_n_bins) b = q < 0 ? 0 : q;
+                        }
+                        atomicAdd(mcw->mc_sep_hist + (size_t)mc_kp * mcw->mc_n_bins + b, 1ull);
+                        // the lane's own slots [k][n_lanes] (recomputed here: one per ~700 steps, not a register pair)
+                        const size_t li = (size_t)mc_kp * (uint32_t)pw.n_episodes +
+                                          (e_wave32 - mc_kp * (uint32_t)pw.ep_stride + (uint32_t)el);
+                        const double r = (double)total;
+                        mcw->mc_return_sum[li] = mcw->mc_return_sum[li] + r;
+                        mcw->mc_return_sq[li] = mcw->mc_return_sq[li] + (r * r);
+                        T* worst = static_cast<T*>(mcw->mc_worst_sep) + li;
+                        if (st_min < *worst) { *worst = st_min; mcw->mc_worst_episode[li] = episode; }
+                    }
+                    st_min = T(1) / T(0); st_los = 0;
+                    if (episode == mcw->mc_first + (uint32_t)mcw->mc_episodes - 1u) { running = false; oc = 0; }   // its last one
+                }
+            } else if constexpr (EVAL) {
                 if (running && oc != 0) {                 // the first episode's result, then the lane stops for good
                     if (j == 0) {                         // (a group latches together: its first lane writes)
                         pw.res_outcome[res_i] = oc;
@@ -381,7 +428,11 @@
 
         if (t == 0) ACAS2D_STAMP(3, wave, lane, false);
         T* const obs_wave = io.obs;
-        if constexpr (HANDOFF && !EVAL) {
+        // MC: the same resets for the lanes that go on with another episode -- nothing of them is stored (no side channels:
+        // io_r's pointers are compile-time NULL; no state, no episode counter: they live in registers until the lane is done)
+        const StepIO<T> io_r = MC ? StepIO<T>{} : io;
+        const uint64_t gid_wave_r = MC ? mc_gid_wave : (uint64_t)(env_offset + e_wave);
+        if constexpr (HANDOFF && (!EVAL || MC)) {
             // ---- finished envs (one bit per env: its group's lane 0) are reset by the whole wave NOW,
             // before anything but reward / done / outcome has been stored: the new episode's state
             // reaches the owner lanes through LDS and leaves with the coalesced state stores and the
@@ -396,7 +447,7 @@
                 while (dm) {
                     wave_lds_fence();                     // every row of the tile is complete
                     const unsigned long long taken =
-                        wave_reset_slots<T, FAST, NS, G>(p, rp, io, k0, k1, (uint64_t)(env_offset + e_wave), dm, lane,
+                        wave_reset_slots<T, FAST, NS, G, decltype(rp), MC>(p, rp, io_r, k0, k1, gid_wave_r, dm, lane,
                                                          episode, tile, scratch);
                     dm &= ~taken;
                     wave_lds_fence();                     // the fresh rows and the slots are complete
@@ -404,8 +455,8 @@
                         const int k_own = __popcll(taken & ((1ull << (el * G)) - 1ull));
                         const T* scr = scratch + k_own * SL::STRIDE;
                         if (j == 0) {
-                            if (io.ep_return) io.ep_return[el] = total;
-                            if (io.ep_steps) io.ep_steps[el] = steps;
+                            if (io_r.ep_return) io_r.ep_return[el] = total;
+                            if (io_r.ep_steps) io_r.ep_steps[el] = steps;
                         }
                         using V = Vec<T, C>;              // the slot's blocks are aligned like the live traffic block
                         tr.x = *reinterpret_cast<const V*>(scr + j * C);
@@ -420,9 +471,11 @@
                         episode += 1u;
                         fresh = true;
                         trig.valid = false; trig.dirty = false;   // new headings (stored below)
-                        const int i0 = el * N + j * C;
-                        put_trf<T, C>(s, s.trf_x, i0, tr.x); put_trf<T, C>(s, s.trf_y, i0, tr.y);
-                        *reinterpret_cast<V*>(s.trf_psi + i0) = tr.psi; *reinterpret_cast<V*>(s.trf_v + i0) = tr.v;
+                        if constexpr (!MC) {
+                            const int i0 = el * N + j * C;
+                            put_trf<T, C>(s, s.trf_x, i0, tr.x); put_trf<T, C>(s, s.trf_y, i0, tr.y);
+                            *reinterpret_cast<V*>(s.trf_psi + i0) = tr.psi; *reinterpret_cast<V*>(s.trf_v + i0) = tr.v;
+                        }
                     }
                     wave_lds_fence();                     // the slots are free for the next pass
                 }
@@ -432,14 +485,14 @@
                 dm &= dm - 1;
                 const int el_d = src / G;
                 wave_lds_fence();                         // every row of the tile is complete
-                wave_reset_env<T, FAST, NS, true>(p, rp, s, io, k0, k1, (uint64_t)(env_offset + e_wave + el_d), el_d, N,
+                wave_reset_env<T, FAST, NS, true, decltype(rp), MC>(p, rp, s, io_r, k0, k1, gid_wave_r + (uint64_t)el_d, el_d, N,
                                                   lane, lane_value(total, src), lane_value(steps, src),
                                                   (uint32_t)lane_value((int)episode, src), tile + el_d * D, scratch);
                 wave_lds_fence();                         // the fresh row and the scratch are complete
                 if (el == el_d) {                         // the owner group continues with the new episode
                     if (j == 0) {
-                        if (io.ep_return) io.ep_return[el] = total;
-                        if (io.ep_steps) io.ep_steps[el] = steps;
+                        if (io_r.ep_return) io_r.ep_return[el] = total;
+                        if (io_r.ep_steps) io_r.ep_steps[el] = steps;
                     }
 #pragma unroll
                     for (int k = 0; k < C; ++k) {
@@ -455,13 +508,15 @@
                     trig.valid = false; trig.dirty = false;   // new headings (stored below)
                     // the new traffic block: whole 16-byte vectors from the owner lanes
                     using V = Vec<T, C>;
-                    const int i0 = el * N + j * C;
-                    put_trf<T, C>(s, s.trf_x, i0, tr.x); put_trf<T, C>(s, s.trf_y, i0, tr.y);
-                    *reinterpret_cast<V*>(s.trf_psi + i0) = tr.psi; *reinterpret_cast<V*>(s.trf_v + i0) = tr.v;
+                    if constexpr (!MC) {
+                        const int i0 = el * N + j * C;
+                        put_trf<T, C>(s, s.trf_x, i0, tr.x); put_trf<T, C>(s, s.trf_y, i0, tr.y);
+                        *reinterpret_cast<V*>(s.trf_psi + i0) = tr.psi; *reinterpret_cast<V*>(s.trf_v + i0) = tr.v;
+                    }
                 }
                 wave_lds_fence();                         // scratch is free for the next finished env
             }
-            if (active && j == 0) {
+            if (!MC && active && j == 0) {
                 if (fresh) {                              // per-episode constants of the new episode
                     if constexpr (ARENA) {
                         char* c = reinterpret_cast<char*>(const_cast<T*>(a1));
@@ -528,7 +583,25 @@
         // workgroup barrier, only the wave's own LDS tile and fences)
         if constexpr (EVAL) { if (__ballot(running) == 0ull) break; }
     }
-    if constexpr (EVAL) {
+    if constexpr (MC) {
+        // the wave's integer sums: the counts as they are, the group leaders' two sums (every other lane adds 0) summed
+        // across the wave, then ONE 64-bit vector atomic per counter from lane 0.  (A lane cut short by n_steps has folded the episodes it
+        // finished; the launcher refuses a budget that could cut one.)
+        const PolicyMonteCarloW* const mcw = monte_carlo_args(pw);
+        const bool mine = active && j == 0;
+        long long v[6] = {mc_n1, mc_n2, mc_n3, mine ? mc_steps : 0, mc_los_eps, mine ? mc_los : 0};   // (64-bit: 64 lanes' int32 sums)
+#pragma unroll
+        for (int q = 3; q < 6; q += 2)
+            for (int w = 1; w < 64; w <<= 1) v[q] += __shfl_xor(v[q], w, 64);
+        if (lane == 0) {
+            unsigned long long* const dst[6] = {mcw->mc_outcome_count + 4 * (size_t)mc_kp + 1, mcw->mc_outcome_count + 4 * (size_t)mc_kp + 2,
+                                                mcw->mc_outcome_count + 4 * (size_t)mc_kp + 3, mcw->mc_sum_steps + mc_kp,
+                                                mcw->mc_los_episodes + mc_kp, mcw->mc_sum_los_steps + mc_kp};
+#pragma unroll
+            for (int q = 0; q < 6; ++q)
+                if (v[q] != 0) atomicAdd(dst[q], (unsigned long long)v[q]);
+        }
+    } else if constexpr (EVAL) {
         if (running && j == 0) {                          // no done within n_steps
             pw.res_outcome[res_i] = 0;
             pw.res_steps[res_i] = 0;

@@ -75,6 +75,15 @@ class CEvalStats(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("min_sep", "min_sep_step", "los_steps", "max_a_lat", "max_dev", "sum_dev")]
 
 
+class CMonteCarlo(C.Structure):
+    """struct Acas2dMonteCarlo: the accumulators of a Monte Carlo campaign, the histogram's bin rule and the launch's episode
+    counters (acas2d_monte_carlo_*, include/acas2d.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("outcome_count", "sum_steps", "los_episodes", "sum_los_steps", "sep_hist",
+                                          "lane_return_sum", "lane_return_sq", "lane_worst_sep", "lane_worst_episode")] + \
+        [("n_bins", C.c_int32), ("episodes_per_lane", C.c_int32), ("inv_bin_width", C.c_double),
+         ("first_episode", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class CGae(C.Structure):
     """struct Acas2dGae: the bootstrap value and GAE over the collector's [T][E] buffers (include/acas2d.h)."""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -121,7 +130,8 @@ EXPORTS = ("acas2d_abi_version", "acas2d_config_size", "acas2d_state_size", "aca
            "acas2d_ppo_guard_size", "acas2d_ppo_update_sb3_set_f32", "acas2d_ppo_options_size",
            "acas2d_reward_normalize_f32", "acas2d_reward_norm_size", "acas2d_reward_norm_workspace_bytes",
            "acas2d_reward_norm_pipeline_depth", "acas2d_evaluate_policies_stats_f32", "acas2d_evaluate_policies_stats_f64",
-           "acas2d_evaluate_policies_stats_group_f32")
+           "acas2d_evaluate_policies_stats_group_f32", "acas2d_monte_carlo_f32", "acas2d_monte_carlo_f64",
+           "acas2d_monte_carlo_group_f32", "acas2d_monte_carlo_size")
 
 
 class NativeLibraryError(RuntimeError):
@@ -196,6 +206,12 @@ def lib():
         f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.c_int64, C.POINTER(CPolicy), C.c_int32, C.c_int32,
                       C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                       C.POINTER(CEvalStats), C.c_void_p]
+    for name in ("acas2d_monte_carlo_f32", "acas2d_monte_carlo_f64", "acas2d_monte_carlo_group_f32"):
+        f = getattr(L, name)                               # the stats entries' list without the three per-episode outputs
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.c_int64, C.POINTER(CPolicy), C.c_int32, C.c_int32,
+                      C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(CMonteCarlo), C.c_void_p]
+    L.acas2d_monte_carlo_size.restype = C.c_size_t
     for name in ("acas2d_collect_set_f32", "acas2d_collect_set_group_f32"):
         f = getattr(L, name)
         f.restype = C.c_int
@@ -256,7 +272,8 @@ def lib():
     if L.acas2d_gae_size() != C.sizeof(CGae):
         raise NativeLibraryError("Acas2dGae layout mismatch: %d != %d" % (L.acas2d_gae_size(), C.sizeof(CGae)))
     for name, twin in (("member_episodes", CMemberEpisodes), ("population_exploit", CPopulationExploit),
-                       ("ppo_guard", CPpoGuard), ("ppo_options", CPpoOptions), ("reward_norm", CRewardNorm)):
+                       ("ppo_guard", CPpoGuard), ("ppo_options", CPpoOptions), ("reward_norm", CRewardNorm),
+                       ("monte_carlo", CMonteCarlo)):
         size = getattr(L, "acas2d_%s_size" % name)()
         if size != C.sizeof(twin):
             raise NativeLibraryError("%s layout mismatch: %d != %d" % (twin.__name__, size, C.sizeof(twin)))

@@ -158,6 +158,22 @@ def evaluate_policy_fused(policy, own, traffic, goal=None, dtype=torch.float64, 
             "path_length": step_len * (steps - 1), "unfinished": int((~fin).sum())}
 
 
+def stack_policies(policies, obs_dim, device):
+    """K policies -- `SB3ActorPolicy` / `ppo.ActorCritic` objects, paths of SB3 zips / .npz exports, or six-tensor tuples --
+    as the six stacked float32 tensors the K-policy launches read: [K][D][64], [K][64], [K][64][64], [K][64], [K][64], [K][1]."""
+    ws = []
+    for pol in policies:
+        if isinstance(pol, (str, os.PathLike)):
+            pol = load_sb3_policy(pol)
+        w = pol.actor_weights() if hasattr(pol, "actor_weights") else pol
+        w1, b1, w2, b2, w3, b3 = (torch.as_tensor(t, dtype=torch.float32).to(device) for t in w)
+        if w1.shape != (64, obs_dim) or w2.shape != (64, 64) or w3.numel() != 64 or b3.numel() != 1:
+            raise ValueError("policy must be the SB3 MlpPolicy actor %d -> 64 -> 64 -> 1, got %s %s %s"
+                             % (obs_dim, tuple(w1.shape), tuple(w2.shape), tuple(w3.shape)))
+        ws.append(kernel_layout(w1, b1, w2, b2, w3, b3))
+    return [torch.stack(ts) for ts in zip(*ws)]                                  # [K][D][64], [K][64], ...
+
+
 def evaluate_policies_entry(dtype, group=False, safety=False):
     """The name of the C entry point evaluate_policies_fused() calls for (dtype, group, safety)."""
     if group and dtype != torch.float32:
@@ -196,17 +212,7 @@ def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float
     v = ACAS2DVecEnv(K * EP, N, device=device, dtype=dtype, auto_reset=True, config=config)
     D, dev = v.obs_dim, v.device
     v.set_state(own[idx], traffic[idx], goal, np.zeros(K * EP, np.int32), observe=True)
-    ws = []
-    for pol in policies:
-        if isinstance(pol, (str, os.PathLike)):
-            pol = load_sb3_policy(pol)
-        w = pol.actor_weights() if hasattr(pol, "actor_weights") else pol
-        w1, b1, w2, b2, w3, b3 = (torch.as_tensor(t, dtype=torch.float32).to(dev) for t in w)
-        if w1.shape != (64, D) or w2.shape != (64, 64) or w3.numel() != 64 or b3.numel() != 1:
-            raise ValueError("policy must be the SB3 MlpPolicy actor %d -> 64 -> 64 -> 1, got %s %s %s"
-                             % (D, tuple(w1.shape), tuple(w2.shape), tuple(w3.shape)))
-        ws.append(kernel_layout(w1, b1, w2, b2, w3, b3))
-    keep = [torch.stack(ts) for ts in zip(*ws)]                                  # [K][D][64], [K][64], ...
+    keep = stack_policies(policies, D, dev)
     T = (max_steps or v.config.max_steps) + 1
     outcome = torch.empty(K, E, dtype=torch.uint8, device=dev)
     steps = torch.empty(K, E, dtype=torch.int32, device=dev)
@@ -234,3 +240,159 @@ def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float
         res.update(min_separation=f[0], min_separation_step=i[0], los_steps=i[1], max_abs_a_lat=f[1],
                    max_abs_deviation=f[2], mean_abs_deviation=np.where(st > 1, f[3] / rows, f.dtype.type(0)))
     return res
+
+
+def monte_carlo_entry(dtype, group=False):
+    """The name of the C entry point MonteCarlo launches for (dtype, group)."""
+    if group and dtype != torch.float32:
+        raise ValueError("MonteCarlo(group=True) is float32 only, got %s" % (dtype,))
+    return "acas2d_monte_carlo%s_%s" % ("_group" if group else "", "f32" if dtype == torch.float32 else "f64")
+
+
+class MonteCarlo:
+    """A Monte Carlo safety campaign (acas2d_monte_carlo_*, include/acas2d.h): K policies play randomly drawn encounters,
+    `n_lanes` at a time and one after another per lane, and every finished episode is folded into accumulators that stay
+    on the device -- outcome counts, steps, losses of separation, a histogram of the minimum separation, and per lane the
+    return sums and the closest encounter.  Every policy meets the SAME encounters (common random numbers): encounter
+    (lane, counter) is episode `counter` of RNG index env_offset + lane under `seed`, whichever policy plays it and
+    however many there are, so a risk ratio between two rows is a paired comparison and any encounter can be
+    regenerated (encounter()).  An all-zero policy is the unequipped aircraft (baseline_main.py's constant action [0]).
+
+    policies   as evaluate_policies_fused(): objects with actor_weights(), paths, or six-tensor tuples
+    n_lanes    encounters in flight per policy (the launch covers K x round_up(n_lanes, 64) lanes)
+    group      the group-cooperative float32 launch (n_traffic in {8, 16, 32, 64}), else thread-per-env
+    n_bins, hist_max   the histogram of min_separation: n_bins bins of hist_max / n_bins, the last one also taking
+               everything beyond (default hist_max: 4 x the config's safe distance)
+    """
+
+    def __init__(self, policies, n_lanes, seed=13, dtype=torch.float32, group=False, config=None, n_traffic=1, n_bins=64,
+                 hist_max=None, device="cuda:0", env_offset=0):
+        from . import native, records
+        from .config import ACAS2DConfig
+        from .vec_env import ACAS2DVecEnv
+        if not policies:
+            raise ValueError("MonteCarlo needs at least one policy")
+        self.entry = monte_carlo_entry(dtype, group)
+        self.config = config if config is not None else ACAS2DConfig(n_traffic=n_traffic)
+        self.n_lanes, self.n_policies, self.dtype, self.seed = int(n_lanes), len(policies), dtype, int(seed)
+        if self.n_lanes < 1:
+            raise ValueError("MonteCarlo needs at least one lane, got %d" % self.n_lanes)
+        self.n_bins = int(n_bins)
+        self.hist_max = float(4.0 * self.config.safe_distance if hist_max is None else hist_max)
+        self.inv_bin_width = self.n_bins / self.hist_max
+        self.first_episode = 0
+        K, L = self.n_policies, self.n_lanes
+        EP = (L + 63) // 64 * 64
+        mk = lambda n, off: ACAS2DVecEnv(n, self.config.n_traffic, device=device, dtype=dtype, seed=seed, env_offset=off,  # noqa: E731
+                                         auto_reset=True, config=self.config, keep_terminal_obs=False, double_buffer=False)
+        self._src = mk(L, int(env_offset))                       # draws the first episode of a launch
+        self._all = mk(K * EP, int(env_offset))                  # ... which is replicated into its K blocks (padding: lane 0)
+        self.device = dev = self._src.device
+        self._weights = stack_policies(policies, self._src.obs_dim, dev)
+        self._idx = torch.as_tensor(np.tile(np.concatenate([np.arange(L), np.zeros(EP - L, np.int64)]), K), device=dev)
+        npdt = np.float32 if dtype == torch.float32 else np.float64
+        self._acc = {k: torch.as_tensor(v.view(np.int32) if v.dtype == np.uint32 else v).to(dev)
+                     for k, v in records.monte_carlo_empty(K, L, max(self.n_bins, 1), npdt).items()}     # (n_bins < 1: the launch refuses)
+        self._native = native
+
+    def _launch(self, episodes, events=None):
+        """One launch: `episodes` episodes per lane from counter first_episode on.  `events`: a pair of torch.cuda.Events
+        to record in front of and behind the kernel alone (tools/bench_monte_carlo.py)."""
+        C_, nat, src, dst = C, self._native, self._src, self._all
+        src.reset_to_episode(self.first_episode)
+        with torch.cuda.device(self.device):
+            # the first observation as an injected state's (set_state(observe=True)): what a replay of the encounter
+            # through evaluate_policies_fused() starts from, and what the kernel gives the episodes it draws itself
+            src.steps.zero_()
+            src._launch_reset(None, do_init=0)
+            for name in ("own_x", "own_y", "own_psi", "own_v", "goal_x", "goal_y", "trf_x", "trf_y", "trf_psi", "trf_v", "steps",
+                         "total_reward"):
+                getattr(dst, name).copy_(getattr(src, name)[self._idx])
+            dst._obs.copy_(src._obs[self._idx])
+            a = self._acc
+            mc = nat.CMonteCarlo(*[a[k].data_ptr() for k in ("outcome_count", "sum_steps", "los_episodes", "sum_los_steps",
+                                                             "sep_hist", "lane_return_sum", "lane_return_sq", "lane_worst_sep",
+                                                             "lane_worst_episode")],
+                                 self.n_bins, int(episodes), self.inv_bin_width, self.first_episode, 0)
+            pw = nat.CPolicy(*[t.data_ptr() for t in self._weights], 64, 0)
+            n_steps = max(int(episodes), 0) * self.config.max_steps
+            if events:
+                events[0].record()
+            nat.check(getattr(nat.lib(), self.entry)(
+                C_.byref(dst._ccfg), C_.byref(dst._cstate), dst.num_envs, C_.byref(pw), self.n_policies, self.n_lanes,
+                dst._obs.data_ptr(), n_steps, src.seed_value, src.env_offset, src.n_traffic, C_.byref(mc), dst._stream()))
+            if events:
+                events[1].record()
+        self.first_episode += int(episodes)
+
+    def run(self, episodes_per_lane, per_launch=8):
+        """Play `episodes_per_lane` more episodes on every lane, in launches of at most `per_launch` each (launches stay
+        short on purpose: the GPU is shared, and a wave waits for the longest SUM of its lanes' episodes).  The result
+        does not depend on per_launch, and run(a) then run(b) equals run(a + b), bit for bit."""
+        n, per_launch = int(episodes_per_lane), int(per_launch)
+        if n < 1 or per_launch < 1:
+            self._launch(n if n < 1 else per_launch)             # the library refuses it in its own words
+        while n > 0:
+            now = min(n, per_launch)
+            self._launch(now)
+            n -= now
+        return self
+
+    def accumulators(self):
+        """The accumulators as numpy arrays (records.MONTE_CARLO_KEYS): one read-back."""
+        out = {k: v.cpu().numpy() for k, v in self._acc.items()}
+        out["lane_worst_episode"] = out["lane_worst_episode"].view(np.uint32)
+        return out
+
+    def summary(self, baseline=None):
+        """records.monte_carlo_summary() of the accumulators (one read-back): per policy the episodes, the goal / collision /
+        timeout counts and rates, the collision rate's Wilson 95 % interval, the loss-of-separation rate, mean steps, mean
+        return and its standard error, the histogram and its edges; with baseline = k0 each policy's risk ratio against k0."""
+        from . import records
+        return records.monte_carlo_summary(self.accumulators(), baseline=baseline, hist_max=self.hist_max)
+
+    def worst(self, m=1):
+        """Per policy the `m` lanes with the smallest lane_worst_sep as (lane, counter, min_sep), closest first (ties: the
+        lower lane)."""
+        acc = self.accumulators()
+        out = []
+        for sep, ctr in zip(acc["lane_worst_sep"], acc["lane_worst_episode"]):
+            order = np.argsort(sep, kind="stable")[:int(m)]
+            out.append([(int(i), int(ctr[i]), sep[i]) for i in order])
+        return out
+
+    def encounter(self, lane, counter):
+        """The encounter (lane, counter) as `own` [1, 4], `traffic` [1, N, 4], `goal` [1, 2] float64 arrays -- ready for
+        evaluate_policies_fused(), for ACAS2DVecEnv.set_state() of a latching env with record_trace=True, or for render."""
+        from .vec_env import ACAS2DVecEnv
+        src = self._src
+        if not 0 <= int(lane) < self.n_lanes:
+            raise ValueError("lane %d of %d" % (lane, self.n_lanes))
+        v = ACAS2DVecEnv(1, src.n_traffic, device=self.device, dtype=self.dtype, seed=self.seed, env_offset=src.env_offset + int(lane),
+                         auto_reset=True, config=self.config, keep_terminal_obs=False, double_buffer=False)
+        v.reset_to_episode(int(counter))
+        return read_state(v)
+
+    def state_dict(self):
+        """The accumulators and first_episode (numpy / ints): a campaign survives its process."""
+        return {"accumulators": self.accumulators(), "first_episode": int(self.first_episode), "n_lanes": self.n_lanes,
+                "n_policies": self.n_policies, "n_bins": self.n_bins, "hist_max": self.hist_max, "seed": self.seed}
+
+    def load_state_dict(self, sd):
+        for k in ("n_lanes", "n_policies", "n_bins", "hist_max", "seed"):
+            if sd[k] != getattr(self, k):
+                raise ValueError("state_dict of another campaign: %s = %r, this one has %r" % (k, sd[k], getattr(self, k)))
+        for k, t in self._acc.items():
+            a = np.ascontiguousarray(sd["accumulators"][k])
+            t.copy_(torch.as_tensor(a.view(np.int32) if a.dtype == np.uint32 else a))
+        self.first_episode = int(sd["first_episode"])
+        return self
+
+
+def read_state(venv):
+    """The episodes a vec env holds as (own [E, 4], traffic [E, N, 4], goal [E, 2]) float64 arrays: set_state()'s and
+    evaluate_policies_fused()'s arguments."""
+    f = lambda t: t.detach().cpu().numpy().astype(np.float64)  # noqa: E731
+    own = np.stack([f(venv.own_x), f(venv.own_y), f(venv.own_psi), f(venv.own_v)], axis=1)
+    trf = np.stack([f(venv.trf_x), f(venv.trf_y), f(venv.trf_psi), f(venv.trf_v)], axis=2)
+    return own, trf, np.stack([f(venv.goal_x), f(venv.goal_y)], axis=1)

@@ -112,3 +112,110 @@ def safety_columns(cols, safe_distance, dtype=np.float64):
         for k in SAFETY_KEYS:
             out[k].append(row[k])
     return out
+
+
+# ---- Monte Carlo campaigns (acas2d_monte_carlo_*, policy.MonteCarlo): the accumulators' definitions, on the host -----------
+MONTE_CARLO_INT_KEYS = ("outcome_count", "sum_steps", "los_episodes", "sum_los_steps", "sep_hist")
+MONTE_CARLO_LANE_KEYS = ("lane_return_sum", "lane_return_sq", "lane_worst_sep", "lane_worst_episode")
+MONTE_CARLO_KEYS = MONTE_CARLO_INT_KEYS + MONTE_CARLO_LANE_KEYS
+
+
+def separation_bin(min_sep, n_bins, inv_bin_width, dtype=np.float64):
+    """The histogram bin of an episode's minimum separation, as the Monte Carlo kernel finds it (include/acas2d.h,
+    Acas2dMonteCarlo): b = (int)(min_sep * inv_bin_width), the product evaluated in `dtype` with inv_bin_width rounded to
+    it; a bin >= n_bins and a non-finite value (+-inf, NaN) go to bin n_bins - 1, and a negative product (no separation is)
+    to bin 0.  Scalars or arrays; returns int64."""
+    dt = np.dtype(dtype).type
+    with np.errstate(invalid="ignore", over="ignore"):
+        scaled = np.asarray(min_sep, dtype=dt) * dt(inv_bin_width)
+        ok = np.abs(scaled) < dt(2147483648.0)                       # finite and an int32 (NaN compares false)
+        q = np.where(ok, scaled, dt(0)).astype(np.int64)             # truncation toward zero, as the C cast
+    return np.where(ok & (q < n_bins), np.maximum(q, 0), n_bins - 1).astype(np.int64)
+
+
+def monte_carlo_empty(n_policies, n_lanes, n_bins, dtype=np.float64):
+    """The accumulators of a campaign before its first episode: lane_worst_sep +inf, everything else 0."""
+    K, L = int(n_policies), int(n_lanes)
+    return {"outcome_count": np.zeros((K, 4), np.int64), "sum_steps": np.zeros(K, np.int64),
+            "los_episodes": np.zeros(K, np.int64), "sum_los_steps": np.zeros(K, np.int64),
+            "sep_hist": np.zeros((K, int(n_bins)), np.int64), "lane_return_sum": np.zeros((K, L), np.float64),
+            "lane_return_sq": np.zeros((K, L), np.float64), "lane_worst_sep": np.full((K, L), np.inf, np.dtype(dtype)),
+            "lane_worst_episode": np.zeros((K, L), np.uint32)}
+
+
+def monte_carlo_reduce(per_episode_results, n_bins, inv_bin_width, dtype=np.float64, acc=None, first_episode=0):
+    """Fold a list of evaluate_policies_fused(safety=True) result dicts -- one per episode counter, in counter order, each
+    [K, n_lanes] -- into the accumulators of acas2d_monte_carlo_* (include/acas2d.h, Acas2dMonteCarlo): the
+    specification of the kernel's folding and the tests' reference.  `acc`: accumulators to go on from (a copy is
+    returned; default: monte_carlo_empty()), `first_episode`: the counter of the first dict.  total_reward is taken as
+    the float64 value of the launch's `dtype` result (evaluate_policies_fused returns it so), min_separation in `dtype`."""
+    dt = np.dtype(dtype)
+    acc = None if acc is None else {k: np.array(v, copy=True) for k, v in acc.items()}
+    for n, res in enumerate(per_episode_results):
+        oc = np.asarray(res["outcome"]).astype(np.int64)
+        K, L = oc.shape
+        if acc is None:
+            acc = monte_carlo_empty(K, L, n_bins, dt)
+        steps, los = np.asarray(res["steps"]).astype(np.int64), np.asarray(res["los_steps"]).astype(np.int64)
+        sep = np.asarray(res["min_separation"]).astype(dt, copy=False)
+        ret = np.asarray(res["total_reward"]).astype(dt).astype(np.float64)
+        b = separation_bin(sep, n_bins, inv_bin_width, dt)
+        for k in range(K):
+            acc["outcome_count"][k] += np.bincount(oc[k], minlength=4)[:4]
+            acc["sep_hist"][k] += np.bincount(b[k], minlength=n_bins)
+        acc["sum_steps"] += steps.sum(1)
+        acc["los_episodes"] += (los > 0).sum(1)
+        acc["sum_los_steps"] += los.sum(1)
+        acc["lane_return_sum"] = acc["lane_return_sum"] + ret               # plain float64 adds, counter after counter
+        acc["lane_return_sq"] = acc["lane_return_sq"] + ret * ret
+        with np.errstate(invalid="ignore"):
+            better = sep < acc["lane_worst_sep"]                          # strictly: the first occurrence keeps its place
+        acc["lane_worst_sep"] = np.where(better, sep, acc["lane_worst_sep"]).astype(dt)
+        acc["lane_worst_episode"] = np.where(better, np.uint32(first_episode + n), acc["lane_worst_episode"]).astype(np.uint32)
+    if acc is None:
+        raise ValueError("monte_carlo_reduce needs at least one result, or acc")
+    return acc
+
+
+def wilson_interval(k, n, z=1.959963984540054):
+    """Wilson score interval of a binomial rate k / n (default z: 95 %); (nan, nan) at n = 0."""
+    k, n = np.asarray(k, np.float64), np.asarray(n, np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        p = k / n
+        den = 1.0 + z * z / n
+        mid = (p + z * z / (2.0 * n)) / den
+        half = z * np.sqrt(p * (1.0 - p) / n + z * z / (4.0 * n * n)) / den
+    return mid - half, mid + half
+
+
+def monte_carlo_summary(acc, baseline=None, hist_max=None):
+    """What a campaign's accumulators say, per policy (arrays [K]): episodes, the goal / collision / timeout counts and
+    rates, the collision rate's Wilson 95 % interval (collision_rate_lo / _hi), the rate of episodes that lost separation
+    (los_rate), mean los steps per episode, mean_steps, mean_return and its standard error (return_sem) -- from the per-lane
+    sums, reduced in float64 in lane order; the standard error takes the episodes as independent -- and the histogram
+    with its n_bins + 1 edges (hist_edges; given hist_max = n_bins bin widths, else in units of a bin).
+    baseline = k0 adds risk_ratio: each policy's collision rate over policy k0's.  A baseline without collisions gives inf
+    (nan for a policy that has none either), never an exception."""
+    oc = np.asarray(acc["outcome_count"], np.int64)
+    n = oc.sum(1)
+    nf = n.astype(np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rate = lambda c: np.asarray(c, np.float64) / nf  # noqa: E731
+        s1 = np.zeros(len(n), np.float64)
+        s2 = np.zeros(len(n), np.float64)
+        for k in range(len(n)):                                           # sequential, lane after lane (cumsum adds in order)
+            s1[k] = np.cumsum(np.asarray(acc["lane_return_sum"][k], np.float64))[-1]
+            s2[k] = np.cumsum(np.asarray(acc["lane_return_sq"][k], np.float64))[-1]
+        mean = s1 / nf
+        var = np.maximum(s2 / nf - mean * mean, 0.0) * (nf / (nf - 1.0))
+        lo, hi = wilson_interval(oc[:, 2], n)
+        out = {"episodes": n, "goals": oc[:, 1], "collisions": oc[:, 2], "timeouts": oc[:, 3], "unfinished": oc[:, 0],
+               "goal_rate": rate(oc[:, 1]), "collision_rate": rate(oc[:, 2]), "timeout_rate": rate(oc[:, 3]),
+               "collision_rate_lo": lo, "collision_rate_hi": hi, "los_rate": rate(acc["los_episodes"]),
+               "mean_los_steps": rate(acc["sum_los_steps"]), "mean_steps": rate(acc["sum_steps"]), "mean_return": mean,
+               "return_sem": np.sqrt(var / nf), "sep_hist": np.asarray(acc["sep_hist"], np.int64)}
+        n_bins = out["sep_hist"].shape[1]
+        out["hist_edges"] = np.arange(n_bins + 1, dtype=np.float64) * (1.0 if hist_max is None else float(hist_max) / n_bins)
+        if baseline is not None:
+            out["risk_ratio"] = out["collision_rate"] / out["collision_rate"][int(baseline)]
+    return out

@@ -272,6 +272,25 @@ class ACAS2DVecEnv:
             self._launch_reset(None, do_init=1)
         return self._obs
 
+    def reset_to_episode(self, counter):
+        """Every env draws the episode its counter names: `counter`, an int or an [E] tensor / array of them (0 .. 2^32 - 1),
+        becomes the envs' episode counters and those episodes are drawn -- (seed, env_offset + env, counter) names the
+        same episode here, in reset() (counter 0), after `counter` reset_masked() calls and in the in-step resets, bit for
+        bit.  Returns the first observation like reset()."""
+        if torch.is_tensor(counter):
+            c = counter.detach().to("cpu", torch.int64).numpy()
+        else:
+            c = np.asarray(counter, dtype=np.int64)
+        if c.ndim > 1 or (c.ndim == 1 and c.shape[0] != self.num_envs):
+            raise ValueError("counter must be an int or %d of them, got shape %s" % (self.num_envs, tuple(c.shape)))
+        if c.size and (c.min() < 0 or c.max() > 0xFFFFFFFF):
+            raise ValueError("episode counters are 32-bit unsigned (0 .. 2^32 - 1)")
+        bits = np.broadcast_to(np.atleast_1d(c).astype(np.uint32).view(np.int32), (self.num_envs,))   # the u32's bit pattern
+        with torch.cuda.device(self.device):
+            self.episode.copy_(torch.as_tensor(np.array(bits)).to(self.device))
+            self._launch_reset(None, do_init=1)
+        return self._obs
+
     def reset_masked(self, mask):
         """Re-initialise the envs with mask != 0 (uint8/bool tensor [E]); their episode counter
         is advanced first so that they get a new episode."""

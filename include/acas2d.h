@@ -389,6 +389,67 @@ int acas2d_evaluate_policies_stats_group_f32(const Acas2dConfig *cfg, const Acas
                                              const Acas2dEvalStats *stats, void *stream);
 
 /*
+ * acas2d_monte_carlo_f32 / _f64 / _group_f32: a Monte Carlo safety campaign -- the evaluation with statistics above, but
+ * every lane plays one DRAWN encounter after another and each finished episode is folded into per-policy accumulators on
+ * the device.  Additive to ABI 7.  The arguments of acas2d_evaluate_policies_stats_* with n_lanes where that has
+ * n_episodes, without the three per-episode outputs, and `mc` where that has `stats`; the same work shapes and the same
+ * rejections in the same words.
+ *   Lane (k, i), i < n_lanes, is env k * EP + i of the state (EP = n_lanes rounded up to 64; i >= n_lanes: padding, plays
+ *   nothing, counts nothing).  It plays the episodes c = first_episode .. first_episode + episodes_per_lane - 1 of RNG index
+ *   env_offset + i: the index WITHIN the block, so the K policies meet the same encounters (common random numbers) and
+ *   (seed, env_offset + i, c) names an encounter whatever K is.  Episode first_episode arrives as `state` / `obs_in`;
+ *   every later one is drawn by the in-step reset of the rollout kernels -- the draws of acas2d_reset_* for that
+ *   (seed, index, counter), bit for bit -- and its first observation is observed from the drawn state exactly as
+ *   acas2d_reset_*(do_init = 0) observes an injected one, so that an encounter replayed through
+ *   acas2d_evaluate_policies_stats_* gives the same bits.  Every lane plays the same NUMBER OF EPISODES, not a step budget:
+ *   a budget would cut long episodes and so over-count the short ones, which are the collisions.
+ *   n_steps  the launch's step budget; it must cover every episode: n_steps >= episodes_per_lane * max_steps, and
+ *            episodes_per_lane * (max_steps + 1) must fit an int32 and episodes_per_lane be at most 2^24 (a lane's sums and a
+ *            wavefront's counts are 32-bit within a launch)
+ * Accumulators: ADDED TO, NEVER CLEARED -- launches chain, first_episode advancing by episodes_per_lane, and a campaign
+ * is as long as wanted while a launch stays short.  The host sets lane_worst_sep to +inf and everything else to 0.
+ *   outcome_count      int64 [K][4]        episodes per outcome 0 .. 3 (0 stays 0: every episode ends by timeout at the latest)
+ *   sum_steps          int64 [K]           sum of game.steps at done
+ *   los_episodes       int64 [K]           episodes with los_steps > 0
+ *   sum_los_steps      int64 [K]           sum of los_steps
+ *   sep_hist           int64 [K][n_bins]   histogram of the episodes' min_sep: bin (int)(min_sep * inv_bin_width), evaluated
+ *                                          in T; a bin >= n_bins and a non-finite value go to bin n_bins - 1
+ *   lane_return_sum    double [K][n_lanes] sum of (double)total_reward, plain adds in the lane's episode order
+ *   lane_return_sq     double [K][n_lanes] sum of (double)total_reward squared, likewise
+ *   lane_worst_sep     T [K][n_lanes]      the smallest min_sep the lane has seen (x < m ? x : m: the first occurrence wins)
+ *   lane_worst_episode uint32 [K][n_lanes] the counter of that episode
+ * The integer sums are exact and independent of any order; the per-lane ones are bitwise reproducible.  min_sep and
+ * los_steps are those of Acas2dEvalStats, restarted at every episode.
+ * Rejected with ACAS2D_EINVAL before anything is launched: everything acas2d_evaluate_policies_stats_* rejects, a NULL mc
+ * or member, episodes_per_lane < 1, n_bins < 1, first_episode + episodes_per_lane > 2^32, an n_steps that does not cover
+ * the episodes.
+ */
+typedef struct Acas2dMonteCarlo {
+    int64_t *outcome_count, *sum_steps, *los_episodes, *sum_los_steps, *sep_hist;
+    double *lane_return_sum, *lane_return_sq;
+    void *lane_worst_sep;              /* T[K][n_lanes] */
+    uint32_t *lane_worst_episode;
+    int32_t n_bins;
+    int32_t episodes_per_lane;
+    double inv_bin_width;              /* handed to the kernel as T */
+    uint32_t first_episode;
+    uint32_t _pad;
+} Acas2dMonteCarlo;
+size_t acas2d_monte_carlo_size(void);  /* sizeof(Acas2dMonteCarlo), for bindings */
+int acas2d_monte_carlo_f32(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                           const Acas2dPolicy *policies, int32_t n_policies, int32_t n_lanes, const void *obs_in,
+                           int32_t n_steps, uint64_t seed, int64_t env_offset, int32_t n_traffic,
+                           const Acas2dMonteCarlo *mc, void *stream);
+int acas2d_monte_carlo_f64(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                           const Acas2dPolicy *policies, int32_t n_policies, int32_t n_lanes, const void *obs_in,
+                           int32_t n_steps, uint64_t seed, int64_t env_offset, int32_t n_traffic,
+                           const Acas2dMonteCarlo *mc, void *stream);
+int acas2d_monte_carlo_group_f32(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                                 const Acas2dPolicy *policies, int32_t n_policies, int32_t n_lanes, const void *obs_in,
+                                 int32_t n_steps, uint64_t seed, int64_t env_offset, int32_t n_traffic,
+                                 const Acas2dMonteCarlo *mc, void *stream);
+
+/*
  * acas2d_collect_set_group_f32: acas2d_collect_set_f32 for n_traffic in {8, 16, 32, 64}, float32 -- the same arguments,
  * layouts and outputs.  Additive to ABI 7.  The launch is acas2d_collect_group_f32's (the env's G lanes of the packed work
  * shapes (4,2) (4,4) (4,8) (4,16) evaluate the two networks together) with the member found per wavefront: a wavefront

@@ -1,0 +1,264 @@
+"""Monte Carlo campaigns, host side (no GPU): the NumPy reducers of records.py that specify the accumulators of
+acas2d_monte_carlo_* -- separation_bin(), monte_carlo_reduce(), monte_carlo_summary() -- against numbers written out
+here, the three entry points in the header, the loader and the built library, and their argument validation (every
+pointer below is a host address: the calls are refused before any launch)."""
+import ctypes as C
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENTRIES = ("acas2d_monte_carlo_f32", "acas2d_monte_carlo_f64", "acas2d_monte_carlo_group_f32")
+
+
+@pytest.fixture(scope="module")
+def g():
+    import gym_acas2d_amd as g
+    return g
+
+
+# ---- separation_bin ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("dtype", (np.float32, np.float64))
+def test_separation_bin_edges(g, dtype):
+    """16 bins of 48 (hist_max = 768 = 4 x the safe distance): 0, just below / on / just above an edge, the last bin's
+    lower edge, hist_max and beyond, inf, NaN.  1 / 48 is no binary fraction, so the products are rounded in `dtype`:
+    the expected bins below are those of the rounded product, worked out per format."""
+    sb = g.records.separation_bin
+    inv = 16.0 / 768.0
+    dt = dtype
+    below, above = np.nextafter(dt(96), dt(0)), np.nextafter(dt(96), dt(1000))
+    # 96 x fl(1 / 48), exactly (rational arithmetic) and then rounded to the format:
+    #   float32  fl(1/48) > 1/48: 96 -> 2 + 6.0e-8 -> 2.0 (bin 2); its lower neighbour 95.99999 -> 2 - 9.9e-8 -> 1.9999999 (bin 1)
+    #   float64  fl(1/48) < 1/48: 96 -> 2 - 1.1e-16 -> 2.0 after rounding (bin 2, although the exact product lies below
+    #            the edge); its lower neighbour -> 2 - 4.1e-16 -> 1.9999999999999996 (bin 1)
+    want_below = 1
+    vals = [0.0, below, 96.0, above, 720.0, 767.9, 768.0, 5000.0, np.inf, -np.inf, np.nan, 47.0, 48.5]
+    want = [0, want_below, 2, 2, 15, 15, 15, 15, 15, 15, 15, 0, 1]
+    got = sb(np.array(vals, dtype), 16, inv, dtype)
+    assert got.dtype == np.int64 and got.tolist() == want
+    for v, w in zip(vals, want):                                          # scalars too
+        assert int(sb(v, 16, inv, dtype)) == w
+    # an exact bin width: every edge belongs to the bin above it
+    assert sb(np.array([127.99, 128.0, 128.01, 511.9, 512.0], dtype), 4, 1.0 / 128.0, dtype).tolist() == [0, 1, 1, 3, 3]
+    assert sb(np.array([3.0e38, 1.0e30], dtype), 4, 1.0e9, dtype).tolist() == [3, 3]       # the product overflows / is huge
+    assert sb(np.array([5.0, np.nan], dtype), 1, 1.0, dtype).tolist() == [0, 0]            # one bin takes everything
+
+
+# ---- monte_carlo_reduce -----------------------------------------------------------------------------------------------------
+INF = np.inf
+# [counter][policy][lane]; 4 bins of 128 (inv_bin_width = 1 / 128, exact)
+OUTCOME = [[[1, 2, 3, 1, 1], [1, 1, 1, 2, 3]], [[2, 1, 1, 1, 3], [1, 1, 2, 1, 1]], [[1, 1, 1, 1, 1], [3, 1, 1, 1, 2]]]
+STEPS = [[[10, 5, 100, 20, 30], [11, 12, 13, 4, 100]], [[6, 10, 10, 10, 100], [10, 10, 7, 10, 10]],
+         [[10, 10, 10, 10, 10], [100, 10, 10, 10, 3]]]
+RETURN = [[[1.5, -2.0, 0.25, 3.0, 0.5], [1.0, 2.0, 3.0, -4.0, 0.5]], [[-1.0, 1.0, 0.5, 0.5, 0.0], [1.0, 1.0, -3.0, 1.0, 1.0]],
+          [[0.25, 0.25, 0.25, 0.25, 0.25], [0.0, 1.0, 1.0, 1.0, -5.0]]]
+MIN_SEP = [[[250, 90, 300, 150, 500], [250, 150, 350, 80, INF]], [[95, 90, 310, 100, 500], [250, 120, 85, 80, 200]],
+           [[240, 300, 100, 150, 450], [400, 110, 85, 300, 70]]]
+LOS = [[[0, 3, 0, 2, 0], [0, 1, 0, 4, 0]], [[5, 2, 0, 1, 0], [0, 2, 6, 3, 0]], [[0, 0, 1, 1, 0], [0, 1, 2, 0, 3]]]
+WANT = {"outcome_count": [[0, 11, 2, 2], [0, 10, 3, 2]], "sum_steps": [351, 320], "los_episodes": [7, 8],
+        "sum_los_steps": [15, 22], "sep_hist": [[5, 4, 3, 3], [7, 4, 2, 2]],
+        "lane_return_sum": [[0.75, -0.75, 1.0, 3.75, 0.75], [2.0, 4.0, 1.0, -2.0, -3.5]],
+        "lane_return_sq": [[3.3125, 5.0625, 0.375, 9.3125, 0.3125], [2.0, 6.0, 19.0, 18.0, 26.25]],
+        # lane 1 of policy 0 (90 at counters 0 and 1), lanes 0, 2, 3 of policy 1: a tie keeps the FIRST counter
+        "lane_worst_sep": [[95, 90, 100, 100, 450], [250, 110, 85, 80, 70]],
+        "lane_worst_episode": [[1, 0, 2, 1, 2], [0, 2, 1, 0, 2]]}
+
+
+def _results(dtype, counters=(0, 1, 2)):
+    return [{"outcome": np.array(OUTCOME[c], np.uint8), "steps": np.array(STEPS[c], np.int32),
+             "total_reward": np.array(RETURN[c], np.float64), "min_separation": np.array(MIN_SEP[c], dtype),
+             "los_steps": np.array(LOS[c], np.int32)} for c in counters]
+
+
+def _same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+@pytest.mark.parametrize("dtype", (np.float32, np.float64))
+def test_monte_carlo_reduce_against_written_out_numbers(g, dtype):
+    r = g.records
+    acc = r.monte_carlo_reduce(_results(dtype), 4, 1.0 / 128.0, dtype)
+    assert tuple(acc) == r.MONTE_CARLO_KEYS
+    for k in r.MONTE_CARLO_INT_KEYS:
+        assert acc[k].dtype == np.int64 and acc[k].tolist() == WANT[k], k
+    assert acc["lane_return_sum"].dtype == acc["lane_return_sq"].dtype == np.float64
+    assert acc["lane_worst_sep"].dtype == dtype and acc["lane_worst_episode"].dtype == np.uint32
+    for k in r.MONTE_CARLO_LANE_KEYS:
+        assert acc[k].tolist() == WANT[k], k
+    assert acc["outcome_count"].sum(1).tolist() == acc["sep_hist"].sum(1).tolist() == [15, 15]
+    # chaining: [0, 1] and then [2] is [0, 1, 2], bit for bit; the inputs are left alone
+    first = r.monte_carlo_reduce(_results(dtype, (0, 1)), 4, 1.0 / 128.0, dtype)
+    keep = {k: v.copy() for k, v in first.items()}
+    both = r.monte_carlo_reduce(_results(dtype, (2,)), 4, 1.0 / 128.0, dtype, acc=first, first_episode=2)
+    for k in r.MONTE_CARLO_KEYS:
+        assert _same_bits(both[k], acc[k]), k
+        assert _same_bits(first[k], keep[k]), k
+    # first_episode names the counters; a lane that never beat +inf keeps counter 0
+    late = r.monte_carlo_reduce(_results(dtype, (0,)), 4, 1.0 / 128.0, dtype, first_episode=7)
+    assert late["lane_worst_episode"].tolist() == [[7] * 5, [7, 7, 7, 7, 0]] and late["lane_worst_sep"][1, 4] == np.inf
+    with pytest.raises(ValueError):
+        r.monte_carlo_reduce([], 4, 1.0 / 128.0, dtype)
+
+
+def test_monte_carlo_reduce_adds_the_returns_in_counter_order(g):
+    """float64 adds do not commute with regrouping: 1e16 + 1 + 1 is 1e16 counter by counter, 1e16 + 2 otherwise."""
+    def one(ret):
+        return {"outcome": np.array([[1]], np.uint8), "steps": np.array([[2]], np.int32), "total_reward": np.array([[ret]]),
+                "min_separation": np.array([[300.0]]), "los_steps": np.array([[0]], np.int32)}
+    acc = g.records.monte_carlo_reduce([one(1e16), one(1.0), one(1.0)], 4, 1.0 / 128.0)
+    assert acc["lane_return_sum"][0, 0] == 1e16 and acc["lane_return_sum"][0, 0] != 1e16 + 2.0
+    # a float32 launch's return enters as the float64 value of the float32 number
+    acc = g.records.monte_carlo_reduce([one(0.1)], 4, 1.0 / 128.0, np.float32)
+    assert acc["lane_return_sum"][0, 0] == float(np.float32(0.1)) and acc["lane_return_sq"][0, 0] == float(np.float32(0.1)) ** 2
+
+
+# ---- monte_carlo_summary ----------------------------------------------------------------------------------------------------
+def _acc(g, counts, lane_sum, lane_sq):
+    K = len(counts)
+    acc = g.records.monte_carlo_empty(K, len(lane_sum[0]), 4)
+    acc["outcome_count"][:] = counts
+    acc["lane_return_sum"][:] = lane_sum
+    acc["lane_return_sq"][:] = lane_sq
+    acc["sum_steps"][:] = [70000, 50000, 1000][:K]
+    acc["los_episodes"][:] = [25, 5, 0][:K]
+    acc["sum_los_steps"][:] = [400, 30, 0][:K]
+    acc["sep_hist"][:] = [[10, 15, 25, 50], [5, 0, 45, 50], [0, 0, 0, 100]][:K]
+    return acc
+
+
+def test_monte_carlo_summary_by_hand(g):
+    acc = _acc(g, [[0, 88, 10, 2], [0, 95, 5, 0]], [[30.0, 20.0], [60.0, 40.0]], [[500.0, 400.0], [80.0, 70.0]])
+    s = g.records.monte_carlo_summary(acc, baseline=0, hist_max=512.0)
+    assert s["episodes"].tolist() == [100, 100] and s["goals"].tolist() == [88, 95]
+    assert s["collisions"].tolist() == [10, 5] and s["timeouts"].tolist() == [2, 0]
+    assert s["goal_rate"].tolist() == [0.88, 0.95] and s["collision_rate"].tolist() == [0.1, 0.05]
+    assert s["timeout_rate"].tolist() == [0.02, 0.0] and s["los_rate"].tolist() == [0.25, 0.05]
+    assert s["mean_steps"].tolist() == [700.0, 500.0] and s["mean_los_steps"].tolist() == [4.0, 0.3]
+    # Wilson, 10 of 100 at z = 1.959964: centre (p + z^2 / 2n) / (1 + z^2 / n), half width z sqrt(p q / n + z^2 / 4n^2) / (1 + z^2 / n)
+    z, n, p = 1.959963984540054, 100.0, 0.1
+    den = 1.0 + z * z / n
+    mid, half = (p + z * z / (2 * n)) / den, z * math.sqrt(p * (1 - p) / n + z * z / (4 * n * n)) / den
+    assert s["collision_rate_lo"][0] == pytest.approx(mid - half, rel=1e-12)
+    assert s["collision_rate_hi"][0] == pytest.approx(mid + half, rel=1e-12)
+    assert abs(s["collision_rate_lo"][0] - 0.05523) < 1e-5 and abs(s["collision_rate_hi"][0] - 0.17437) < 1e-5   # the tables' values
+    assert abs(s["collision_rate_lo"][1] - 0.02154) < 2e-5 and abs(s["collision_rate_hi"][1] - 0.11175) < 1e-5   # 5 of 100
+    assert s["risk_ratio"].tolist() == [1.0, 0.5]
+    # mean 50 / 100; variance (900 / 100 - 0.25) x 100 / 99; standard error sqrt(variance / 100)
+    assert s["mean_return"].tolist() == [0.5, 1.0]
+    assert s["return_sem"][0] == pytest.approx(math.sqrt((9.0 - 0.25) * 100.0 / 99.0 / 100.0), rel=1e-12)
+    assert s["return_sem"][1] == pytest.approx(math.sqrt((1.5 - 1.0) * 100.0 / 99.0 / 100.0), rel=1e-12)
+    assert s["sep_hist"].tolist() == [[10, 15, 25, 50], [5, 0, 45, 50]] and s["hist_edges"].tolist() == [0, 128, 256, 384, 512]
+    assert g.records.monte_carlo_summary(acc, baseline=1)["risk_ratio"].tolist() == [2.0, 1.0]
+    assert "risk_ratio" not in g.records.monte_carlo_summary(acc)
+
+
+def test_monte_carlo_summary_without_collisions_in_the_baseline(g):
+    """inf against a baseline that never collided, nan for a policy that did not either (0 / 0); an empty campaign is
+    nan throughout -- no exception, no warning turned into one."""
+    acc = _acc(g, [[0, 100, 0, 0], [0, 95, 5, 0], [0, 50, 0, 50]], [[1.0, 1.0]] * 3, [[1.0, 1.0]] * 3)
+    with np.errstate(all="raise"):
+        s = g.records.monte_carlo_summary(acc, baseline=0)
+    assert math.isnan(s["risk_ratio"][0]) and s["risk_ratio"][1] == np.inf and math.isnan(s["risk_ratio"][2])
+    assert s["collision_rate_lo"][0] == pytest.approx(0.0, abs=1e-15) and 0.03 < s["collision_rate_hi"][0] < 0.04
+    with np.errstate(all="raise"):
+        e = g.records.monte_carlo_summary(g.records.monte_carlo_empty(2, 3, 4), baseline=1)
+    assert e["episodes"].tolist() == [0, 0] and np.isnan(e["collision_rate"]).all() and np.isnan(e["risk_ratio"]).all()
+    assert np.isnan(e["mean_return"]).all()
+
+
+def test_summary_sums_the_lanes_in_order(g):
+    acc = g.records.monte_carlo_empty(1, 3, 4)
+    acc["outcome_count"][0] = [0, 3, 0, 0]
+    acc["lane_return_sum"][0] = [1e16, 1.0, 1.0]                        # lane after lane: 1e16; pairwise would give 1e16 + 2
+    assert g.records.monte_carlo_summary(acc)["mean_return"][0] == 1e16 / 3.0
+
+
+# ---- header, loader, library ------------------------------------------------------------------------------------------------
+def test_entries_in_header_loader_and_library(g):
+    with open(os.path.join(ROOT, "include", "acas2d.h")) as f:
+        header = f.read()
+    L = g.native.lib()
+    for name in ENTRIES + ("acas2d_monte_carlo_size",):
+        assert (" %s(" % name) in header and name in g.native.EXPORTS and hasattr(L, name), name
+    assert "typedef struct Acas2dMonteCarlo {" in header and "#define ACAS2D_ABI_VERSION 7" in header
+    assert L.acas2d_abi_version() == g.native.ABI_VERSION == 7
+    assert C.sizeof(g.native.CMonteCarlo) == L.acas2d_monte_carlo_size() == 96
+    fields = [n for n, _ in g.native.CMonteCarlo._fields_]
+    assert fields == ["outcome_count", "sum_steps", "los_episodes", "sum_los_steps", "sep_hist", "lane_return_sum",
+                      "lane_return_sq", "lane_worst_sep", "lane_worst_episode", "n_bins", "episodes_per_lane", "inv_bin_width",
+                      "first_episode", "_pad"]
+    assert all(f in header for f in fields)
+    for name in ENTRIES:                                   # the stats siblings' arguments without the three per-episode outputs
+        stats = getattr(L, name.replace("monte_carlo", "evaluate_policies_stats")).argtypes
+        assert list(getattr(L, name).argtypes) == list(stats[:11]) + [C.POINTER(g.native.CMonteCarlo), stats[-1]]
+    me = g.policy.monte_carlo_entry
+    assert (me(torch.float32), me(torch.float64), me(torch.float32, True)) == ENTRIES
+    with pytest.raises(ValueError, match="float32 only"):
+        me(torch.float64, group=True)
+
+
+CASES = (("acas2d_monte_carlo_f32", 1, 16, "no thread-per-env shape"), ("acas2d_monte_carlo_f32", 8, 5, "no thread-per-env shape"),
+         ("acas2d_monte_carlo_f64", 4, 8, "no thread-per-env shape"),
+         ("acas2d_monte_carlo_group_f32", 16, 3, "use acas2d_monte_carlo_f32"),
+         ("acas2d_monte_carlo_group_f32", 64, 5, "has no packed work shape"))
+
+
+@pytest.mark.parametrize("entry,N,badN,bad_msg", CASES, ids=["%s-N%d" % (c[0][19:], c[1]) for c in CASES])
+def test_monte_carlo_validation_needs_no_gpu(g, entry, N, badN, bad_msg):
+    L = g.native.lib()
+    buf = (C.c_double * 8192)()
+    a = C.addressof(buf)
+    st = g.native.CState(*([a] * 14))
+    fn = getattr(L, entry)
+    cfg = g.ACAS2DConfig(n_traffic=N).to_c()                              # max_steps 1000
+    name = entry[:-4]
+    ptrs = [n for n, _ in g.native.CMonteCarlo._fields_[:9]]
+
+    def pol(hidden=64, **none):
+        f = {n: a for n, _ in g.native.CPolicy._fields_[:6]}
+        f.update(none)
+        return g.native.CPolicy(**f, hidden=hidden, _pad=0)
+
+    def mc(n_bins=16, epl=2, first=0, **none):
+        f = {n: a for n in ptrs}
+        f.update(none)
+        return g.native.CMonteCarlo(**f, n_bins=n_bins, episodes_per_lane=epl, inv_bin_width=0.02, first_episode=first, _pad=0)
+
+    def call(cfg_=C.byref(cfg), state=C.byref(st), n_envs=256, p=None, K=2, lanes=100, obs=a, T=2000, n=N, off=0, m=mc()):
+        return fn(cfg_, state, n_envs, C.byref(p or pol()), K, lanes, obs, T, 13, off, n, None if m is None else C.byref(m), None)
+
+    def rejects(msg, **kw):
+        assert call(**kw) == -22, kw
+        assert msg.encode() in L.acas2d_last_error(), (kw, L.acas2d_last_error())
+
+    rejects(name + ": NULL mc", m=None)
+    for p_ in ptrs:
+        rejects(name + ": the nine accumulators of mc are required", m=mc(**{p_: None}))
+    for epl in (0, -1):
+        rejects(name + ": episodes_per_lane = %d (at least 1)" % epl, m=mc(epl=epl))
+    for nb in (0, -4):
+        rejects(name + ": n_bins = %d (at least 1)" % nb, m=mc(n_bins=nb))
+    rejects("exceeds the 32-bit episode counter", m=mc(first=0xFFFFFFFF))           # 2^32 - 1 + 2 > 2^32
+    assert call(m=mc(first=0xFFFFFFFE), n=badN) == -22 and b"episode counter" not in L.acas2d_last_error()   # ... + 2 = 2^32: fine
+    rejects("n_steps = 1999 does not cover episodes_per_lane = 2 episodes of max_steps = 1000", T=1999)
+    rejects("does not cover", T=0)
+    rejects("must fit an int32", m=mc(epl=3000000), T=2147483647)
+    rejects(bad_msg, n=badN)
+    rejects(name + ": NULL cfg", cfg_=None)
+    rejects("NULL state", state=None)
+    rejects("obs_in is required", obs=None)
+    for w in ("w1t", "b1", "w2t", "b2", "w3", "b3"):
+        rejects("six weight buffers", p=pol(**{w: None}))
+    rejects("got hidden = 32", p=pol(32))
+    rejects("n_policies = 0", K=0)
+    rejects("n_lanes = 0", lanes=0)
+    rejects("n_traffic = 0", n=0)
+    rejects(name + ": negative env_offset", off=-1)
+    rejects("need 256", n_envs=255)
+    rejects("need 192", n_envs=191, K=3, lanes=37)
+    if "group" in entry:
+        rejects("16-byte aligned", p=pol(w2t=a + 4))

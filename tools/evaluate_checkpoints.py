@@ -6,8 +6,14 @@ One JSON line per checkpoint, in timestep order, best_model.zip last.  --safety 
 of the same launch (evaluate_policies_fused(safety=True)) over the finished episodes: the mean and the worst minimum
 separation, the share of episodes that lost separation (los_steps > 0), the mean of the largest |a_lat| and the mean of
 the mean |deviation| from the planned path.
+--monte-carlo LANESxEPISODES instead plays a Monte Carlo campaign (policy.MonteCarlo): every checkpoint meets the same
+LANES x EPISODES randomly drawn encounters of seed 13, and one JSON line per checkpoint gives its collision rate with the
+Wilson 95 % interval, the goal / timeout / loss-of-separation rates, mean steps and mean return with its standard error.
+--baseline-zero appends the all-zero policy (the unequipped aircraft: baseline_main.py's constant action [0]) and adds
+each checkpoint's risk ratio against it.
 
     python tools/evaluate_checkpoints.py DIR [--dtype float64|float32] [--episodes 100] [--safety]
+    python tools/evaluate_checkpoints.py DIR --monte-carlo 65536x64 [--baseline-zero] [--dtype float32]
 """
 import argparse
 import glob
@@ -29,6 +35,8 @@ ap.add_argument("dir")
 ap.add_argument("--dtype", choices=("float64", "float32"), default="float64")
 ap.add_argument("--episodes", type=int, default=100)
 ap.add_argument("--safety", action="store_true")
+ap.add_argument("--monte-carlo", metavar="LANESxEPISODES", default=None)
+ap.add_argument("--baseline-zero", action="store_true")
 args = ap.parse_args()
 
 steps_of = lambda p: int(re.search(r"model_(\d+)_steps\.zip$", p).group(1))  # noqa: E731
@@ -38,6 +46,24 @@ best = os.path.join(args.dir, "best_model.zip")
 paths = ckpts + ([best] if os.path.exists(best) else [])
 if not paths:
     sys.exit("no model_*_steps.zip or best_model.zip under %s" % args.dir)
+
+if args.monte_carlo:
+    lanes, episodes = (int(x) for x in args.monte_carlo.lower().split("x"))
+    pols, names = list(paths), [os.path.relpath(p, args.dir) for p in paths]
+    if args.baseline_zero:
+        D = g.ACAS2DConfig().obs_dim
+        pols.append((torch.zeros(64, D), torch.zeros(64), torch.zeros(64, 64), torch.zeros(64), torch.zeros(1, 64), torch.zeros(1)))
+        names.append("zero (unequipped)")
+    mc = g.MonteCarlo(pols, lanes, seed=13, dtype=getattr(torch, args.dtype)).run(episodes)
+    s = mc.summary(baseline=len(pols) - 1 if args.baseline_zero else None)
+    scalars = [k for k, v in s.items() if np.ndim(v) == 1 and k != "hist_edges"]
+    for k, name in enumerate(names):
+        row = {"checkpoint": name, "timesteps": steps_of(paths[k]) if k < len(ckpts) else None}
+        row.update({key: (int(s[key][k]) if s[key].dtype.kind == "i" else float(s[key][k])) for key in scalars})
+        row["sep_hist"] = [int(x) for x in s["sep_hist"][k]]
+        print(json.dumps(row), flush=True)
+    print(json.dumps({"hist_edges": [float(x) for x in s["hist_edges"]], "lanes": lanes, "episodes_per_lane": episodes}), flush=True)
+    sys.exit(0)
 
 own, trf, goal = g.reset_parity.draw_episodes(g.ACAS2DConfig(), args.episodes, random.Random(13))
 out = g.evaluate_policies_fused(paths, own, trf, goal, dtype=getattr(torch, args.dtype), safety=args.safety)
