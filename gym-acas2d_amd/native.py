@@ -84,6 +84,19 @@ class CMonteCarlo(C.Structure):
          ("first_episode", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class CEncounterSearch(C.Structure):
+    """struct Acas2dEncounterSearch: the proposal's tables, the per-candidate buffers, the stats entry's outputs, the log row,
+    the archive and the settings of one generation of an encounter search (acas2d_encounter_*, include/acas2d.h)."""
+    _fields_ = [(n, C.c_void_p) for n in ("p", "cdf", "log_ratio", "active", "bins", "log_w", "elite_w", "outcome", "min_sep",
+                                          "history", "best_score", "best_generation", "best_candidate", "best_own_psi",
+                                          "best_traffic")] + \
+        [(n, C.c_int32) for n in ("n_bins", "n_coord", "n_quantile", "weighted")] + \
+        [(n, C.c_double) for n in ("alpha", "p_floor", "level")] + [("generation", C.c_uint64)]
+
+
+SEARCH_HISTORY_WIDTH = 16
+
+
 class CGae(C.Structure):
     """struct Acas2dGae: the bootstrap value and GAE over the collector's [T][E] buffers (include/acas2d.h)."""
     _fields_ = [(n, C.c_void_p) for n in (
@@ -131,7 +144,9 @@ EXPORTS = ("acas2d_abi_version", "acas2d_config_size", "acas2d_state_size", "aca
            "acas2d_reward_normalize_f32", "acas2d_reward_norm_size", "acas2d_reward_norm_workspace_bytes",
            "acas2d_reward_norm_pipeline_depth", "acas2d_evaluate_policies_stats_f32", "acas2d_evaluate_policies_stats_f64",
            "acas2d_evaluate_policies_stats_group_f32", "acas2d_monte_carlo_f32", "acas2d_monte_carlo_f64",
-           "acas2d_monte_carlo_group_f32", "acas2d_monte_carlo_size")
+           "acas2d_monte_carlo_group_f32", "acas2d_monte_carlo_size", "acas2d_encounter_sample_f32",
+           "acas2d_encounter_sample_f64", "acas2d_encounter_select_f32", "acas2d_encounter_select_f64", "acas2d_encounter_refit",
+           "acas2d_encounter_search_size")
 
 
 class NativeLibraryError(RuntimeError):
@@ -212,6 +227,19 @@ def lib():
         f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.c_int64, C.POINTER(CPolicy), C.c_int32, C.c_int32,
                       C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(CMonteCarlo), C.c_void_p]
     L.acas2d_monte_carlo_size.restype = C.c_size_t
+    for name in ("acas2d_encounter_sample_f32", "acas2d_encounter_sample_f64"):
+        f = getattr(L, name)
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.c_int64, C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_int32,
+                      C.POINTER(CEncounterSearch), C.c_void_p]
+    for name in ("acas2d_encounter_select_f32", "acas2d_encounter_select_f64"):
+        f = getattr(L, name)
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(CConfig), C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(CEncounterSearch),
+                      C.c_void_p]
+    L.acas2d_encounter_refit.restype = C.c_int
+    L.acas2d_encounter_refit.argtypes = [C.POINTER(CEncounterSearch), C.c_int32, C.c_int32, C.c_void_p]
+    L.acas2d_encounter_search_size.restype = C.c_size_t
     for name in ("acas2d_collect_set_f32", "acas2d_collect_set_group_f32"):
         f = getattr(L, name)
         f.restype = C.c_int
@@ -273,7 +301,7 @@ def lib():
         raise NativeLibraryError("Acas2dGae layout mismatch: %d != %d" % (L.acas2d_gae_size(), C.sizeof(CGae)))
     for name, twin in (("member_episodes", CMemberEpisodes), ("population_exploit", CPopulationExploit),
                        ("ppo_guard", CPpoGuard), ("ppo_options", CPpoOptions), ("reward_norm", CRewardNorm),
-                       ("monte_carlo", CMonteCarlo)):
+                       ("monte_carlo", CMonteCarlo), ("encounter_search", CEncounterSearch)):
         size = getattr(L, "acas2d_%s_size" % name)()
         if size != C.sizeof(twin):
             raise NativeLibraryError("%s layout mismatch: %d != %d" % (twin.__name__, size, C.sizeof(twin)))

@@ -389,6 +389,231 @@ class MonteCarlo:
         return self
 
 
+def encounter_search_entries(dtype, group=False):
+    """The names of the C entry points EncounterSearch launches for (dtype, group): sample, evaluate, select (the refit is
+    dtype-free: acas2d_encounter_refit)."""
+    sfx = "f32" if dtype == torch.float32 else "f64"
+    return ("acas2d_encounter_sample_" + sfx, evaluate_policies_entry(dtype, group, safety=True), "acas2d_encounter_select_" + sfx)
+
+
+class EncounterSearch:
+    """A cross-entropy search over encounters with importance sampling (acas2d_encounter_*, include/acas2d.h; Rubinstein's
+    cross-entropy method): per generation every policy's `n_candidates` encounters are drawn from ITS proposal -- one
+    piecewise-constant density per coordinate of the reset distribution's unit cube -- played by the stats evaluator
+    (acas2d_evaluate_policies_stats_*), the closest ones (the smallest min_separation) are kept as the elite and the
+    proposal is refit to them; every candidate carries its likelihood ratio against the reset distribution, so each
+    generation also gives an unbiased estimate of the probability of min_separation <= level.  K searches run side by
+    side, one per policy; with equal proposals they meet the same candidates (common random numbers).  Five launches per
+    generation (sample, observe, evaluate, select, refit) and nothing read back in between.  records.search_*() is the
+    specification.
+
+    policies      as evaluate_policies_fused(): objects with actor_weights(), paths, or six-tensor tuples
+    n_candidates  encounters per policy and generation (the launches cover K x round_up(n_candidates, 64) envs)
+    group         the group-cooperative float32 evaluation (n_traffic in {8, 16, 32, 64}), else thread-per-env
+    n_bins        bins per coordinate: a power of two, 2 .. 64
+    rho           the elite quantile: n_quantile = max(1, ceil(rho x n_candidates)) unless n_quantile is given
+    alpha         smoothing of the refit (0: the proposal never moves); p_floor: the least bin probability before the
+                  renormalisation (default 1 / (16 n_bins))
+    level         the event: min_separation <= level (default: the config's collision distance); the elite threshold never
+                  goes below it
+    weighted      refit with the likelihood ratios as weights (the cross-entropy update for the reset distribution); False: count
+                  the elite (the estimate is then the plain event fraction of the proposal's encounters)
+    """
+
+    def __init__(self, policies, n_candidates, seed=13, dtype=torch.float32, group=False, config=None, n_traffic=1, n_bins=8,
+                 rho=0.1, alpha=0.7, p_floor=None, level=None, weighted=True, device="cuda:0", env_offset=0, n_quantile=None):
+        import math
+        from . import native, records
+        from .config import ACAS2DConfig
+        from .vec_env import ACAS2DVecEnv
+        if not policies:
+            raise ValueError("EncounterSearch needs at least one policy")
+        self.entries = encounter_search_entries(dtype, group)
+        self.config = config if config is not None else ACAS2DConfig(n_traffic=n_traffic)
+        self.n_candidates, self.n_policies, self.dtype, self.seed = int(n_candidates), len(policies), dtype, int(seed)
+        if self.n_candidates < 1:
+            raise ValueError("EncounterSearch needs at least one candidate, got %d" % self.n_candidates)
+        self.n_bins, self.alpha, self.weighted = int(n_bins), float(alpha), bool(weighted)
+        if self.n_bins < 1:
+            raise ValueError("EncounterSearch needs at least one bin, got %d" % self.n_bins)
+        self.p_floor = float(1.0 / (16 * self.n_bins) if p_floor is None else p_floor)
+        self.level = float(2 * self.config.collision_radius if level is None else level)
+        self.n_quantile = int(max(1, math.ceil(float(rho) * self.n_candidates)) if n_quantile is None else n_quantile)
+        self.generation = 0
+        K, L, N, B = self.n_policies, self.n_candidates, int(self.config.n_traffic), self.n_bins
+        self.n_coord = NC = 4 * (N + 1)
+        self._ep = EP = (L + 63) // 64 * 64
+        self._env = ACAS2DVecEnv(K * EP, N, device=device, dtype=dtype, seed=seed, env_offset=int(env_offset), auto_reset=True,
+                                 config=self.config, keep_terminal_obs=False, double_buffer=False)
+        self.device = dev = self._env.device
+        self._weights = stack_policies(policies, self._env.obs_dim, dev)
+        self.active = records.search_active_coordinates(self.config)
+        flat = np.full((K, NC, B), 1.0 / B, np.float64)
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+        z = lambda *shape, dt=torch.float64: torch.zeros(*shape, dtype=dt, device=dev)  # noqa: E731
+        self._buf = b = dict(zip(("p", "cdf", "log_ratio"), (up(t) for t in (flat,) + records.search_tables(flat))))
+        self._drawn = {k: v.clone() for k, v in b.items()}       # the tables the last generation was drawn from
+        b.update(active=up(self.active.astype(np.uint8)), bins=z(K, NC, L, dt=torch.uint8), log_w=z(K, L), elite_w=z(K, L),
+                 outcome=z(K, L, dt=torch.uint8), steps=z(K, L, dt=torch.int32), total_reward=z(K, L, dt=dtype),
+                 stats_f=z(4, K, L, dt=dtype), stats_i=z(2, K, L, dt=torch.int32),
+                 best_score=torch.full((K,), float("inf"), dtype=dtype, device=dev), best_generation=z(K, dt=torch.int32),
+                 best_candidate=torch.full((K,), -1, dtype=torch.int32, device=dev), best_own_psi=z(K, dt=dtype),
+                 best_traffic=z(K, N, 4, dt=dtype))
+        self._history = z(8, K, native.SEARCH_HISTORY_WIDTH)
+        self._native = native
+
+    def _struct(self, generation, tables=None, history=None):
+        b, t = self._buf, tables or self._buf
+        return self._native.CEncounterSearch(
+            t["p"].data_ptr(), t["cdf"].data_ptr(), t["log_ratio"].data_ptr(), b["active"].data_ptr(), b["bins"].data_ptr(),
+            b["log_w"].data_ptr(), b["elite_w"].data_ptr(), b["outcome"].data_ptr(), b["stats_f"][0].data_ptr(),
+            (self._history[0] if history is None else history).data_ptr(), b["best_score"].data_ptr(),
+            b["best_generation"].data_ptr(), b["best_candidate"].data_ptr(), b["best_own_psi"].data_ptr(),
+            b["best_traffic"].data_ptr(), self.n_bins, self.n_coord, self.n_quantile, int(self.weighted), self.alpha,
+            self.p_floor, self.level, int(generation))
+
+    def _sample(self, cs):
+        v, nat = self._env, self._native
+        nat.check(getattr(nat.lib(), self.entries[0])(
+            C.byref(v._ccfg), C.byref(v._cstate), v.num_envs, self.n_policies, self.n_candidates, v.seed_value, v.env_offset,
+            v.n_traffic, C.byref(cs), v._stream()))
+
+    def _generation(self, events=None):
+        """One generation's five launches.  `events`: four pairs of torch.cuda.Events around the sample, evaluate, select and
+        refit launches (tools/bench_encounter_search.py)."""
+        v, nat, b, g = self._env, self._native, self._buf, self.generation
+        K, L = self.n_policies, self.n_candidates
+        lib = nat.lib()
+        mark = (lambda i, j: events[i][j].record()) if events else (lambda i, j: None)
+        with torch.cuda.device(self.device):
+            if g >= self._history.shape[0]:                      # (a device copy: nothing waits for it)
+                self._history = torch.cat([self._history, torch.zeros_like(self._history)])
+            cs = self._struct(g, history=self._history[g])
+            mark(0, 0)
+            self._sample(cs)                                     # the library refuses bad settings here, before any launch
+            mark(0, 1)
+            for k, t in self._drawn.items():
+                t.copy_(b[k])
+            v._launch_reset(None, do_init=0)                     # the first observation, as of an injected state
+            sf, si = b["stats_f"], b["stats_i"]
+            cstats = nat.CEvalStats(sf[0].data_ptr(), si[0].data_ptr(), si[1].data_ptr(), sf[1].data_ptr(), sf[2].data_ptr(),
+                                    sf[3].data_ptr())
+            pw = nat.CPolicy(*[t.data_ptr() for t in self._weights], 64, 0)
+            mark(1, 0)
+            nat.check(getattr(lib, self.entries[1])(
+                C.byref(v._ccfg), C.byref(v._cstate), v.num_envs, C.byref(pw), K, L, v._obs.data_ptr(), self.config.max_steps + 1,
+                v.seed_value, v.env_offset, v.n_traffic, b["outcome"].data_ptr(), b["steps"].data_ptr(),
+                b["total_reward"].data_ptr(), C.byref(cstats), v._stream()))
+            mark(1, 1)
+            mark(2, 0)
+            nat.check(getattr(lib, self.entries[2])(C.byref(v._ccfg), K, L, v.seed_value, v.env_offset, v.n_traffic, C.byref(cs),
+                                                    v._stream()))
+            mark(2, 1)
+            mark(3, 0)
+            nat.check(lib.acas2d_encounter_refit(C.byref(cs), K, L, v._stream()))
+            mark(3, 1)
+        self.generation = g + 1
+
+    def run(self, generations):
+        """`generations` more generations, queued without a host synchronisation or read-back in between.  run(a) then run(b)
+        equals run(a + b), bit for bit."""
+        n = int(generations)
+        if n < 1:
+            raise ValueError("run() needs at least one generation, got %d" % n)
+        for _ in range(n):
+            self._generation()
+        return self
+
+    def history(self):
+        """The device log as a numpy array [generations, K, 16] (records.SEARCH_HISTORY_COLUMNS): one read-back."""
+        return self._history[:self.generation].cpu().numpy()
+
+    def estimate(self, first_generation=0):
+        """records.search_estimate() of the log: per policy the probability of min_separation <= level under the reset
+        distribution, per generation and averaged over the generations from first_generation on, with standard errors
+        and effective sample sizes."""
+        from . import records
+        return records.search_estimate(self.history(), self.n_candidates, first_generation)
+
+    def proposal(self):
+        """The proposals the NEXT generation will be drawn from: p [K, n_coord, n_bins] float64."""
+        return self._buf["p"].cpu().numpy()
+
+    def buffers(self):
+        """Every buffer of the search as numpy arrays (the tables, the last generation's bins, log_w, elite_w and evaluation
+        results, the log, the archive): what two searches are compared by."""
+        out = {k: v.cpu().numpy() for k, v in self._buf.items()}
+        out["best_generation"] = out["best_generation"].view(np.uint32)
+        out["history"] = self.history()
+        return out
+
+    def candidates(self):
+        """The last generation as it was drawn: the tables it was drawn from (p, cdf, log_ratio), and per policy the
+        candidates' states in the engine's dtype -- own [K, L, 4], traffic [K, L, N, 4], goal [K, L, 2], and the padding envs'
+        under padding_* -- their bins [K, L, n_coord], log_w [K, L], outcome and score (min_separation) [K, L].  The states are
+        drawn again from the kept tables by the sampler itself (the evaluation has stepped the arrays it wrote)."""
+        if self.generation < 1:
+            raise RuntimeError("candidates() before the first generation")
+        K, L, EP, v = self.n_policies, self.n_candidates, self._ep, self._env
+        with torch.cuda.device(self.device):
+            self._sample(self._struct(self.generation - 1, tables=self._drawn))
+        f = lambda t: t.detach().cpu().numpy()  # noqa: E731
+        own = np.stack([f(v.own_x), f(v.own_y), f(v.own_psi), f(v.own_v)], axis=1).reshape(K, EP, 4)
+        trf = np.stack([f(v.trf_x), f(v.trf_y), f(v.trf_psi), f(v.trf_v)], axis=2).reshape(K, EP, v.n_traffic, 4)
+        goal = np.stack([f(v.goal_x), f(v.goal_y)], axis=1).reshape(K, EP, 2)
+        b = self._buf
+        out = {k: f(t) for k, t in self._drawn.items()}
+        out.update(generation=self.generation - 1, own=own[:, :L], traffic=trf[:, :L], goal=goal[:, :L], padding_own=own[:, L:],
+                   padding_traffic=trf[:, L:], padding_goal=goal[:, L:], steps=f(v.steps).reshape(K, EP),
+                   total_reward=f(v.total_reward).reshape(K, EP), bins=f(b["bins"]).transpose(0, 2, 1), log_w=f(b["log_w"]),
+                   outcome=f(b["outcome"]), score=f(b["stats_f"][0]), elite_w=f(b["elite_w"]))
+        return out
+
+    def best(self):
+        """Per policy the closest encounter found so far as (generation, candidate, min_sep, own [1, 4], traffic [1, N, 4],
+        goal [1, 2]) -- float64 arrays ready for evaluate_policies_fused() -- or None where no episode has finished yet.  The
+        first occurrence wins: the lower generation, then the lower candidate."""
+        b = self.buffers()
+        cc = self.config.to_c()
+        npdt = np.float32 if self.dtype == torch.float32 else np.float64
+        out = []
+        for k in range(self.n_policies):
+            if b["best_candidate"][k] < 0:
+                out.append(None)
+                continue
+            own = np.array([[npdt(cc.own_x0), npdt(cc.own_y0), b["best_own_psi"][k], npdt(cc.own_v)]], np.float64)
+            goal = np.array([[npdt(cc.goal_x), npdt(cc.goal_y)]], np.float64)
+            out.append((int(b["best_generation"][k]), int(b["best_candidate"][k]), b["best_score"][k], own,
+                        b["best_traffic"][k][None].astype(np.float64), goal))
+        return out
+
+    _SAVED = ("p", "cdf", "log_ratio", "best_score", "best_generation", "best_candidate", "best_own_psi", "best_traffic")
+    _SETTINGS = ("n_candidates", "n_policies", "n_bins", "n_coord", "n_quantile", "alpha", "p_floor", "level", "weighted", "seed")
+
+    def state_dict(self):
+        """The proposals, the log, the archive and the generation counter (numpy / numbers): a search survives its process."""
+        b = self._buf
+        sd = {k: b[k].cpu().numpy() for k in self._SAVED}
+        sd.update(drawn={k: v.cpu().numpy() for k, v in self._drawn.items()}, history=self.history(), generation=int(self.generation))
+        sd.update({k: getattr(self, k) for k in self._SETTINGS})
+        return sd
+
+    def load_state_dict(self, sd):
+        for k in self._SETTINGS:
+            if sd[k] != getattr(self, k):
+                raise ValueError("state_dict of another search: %s = %r, this one has %r" % (k, sd[k], getattr(self, k)))
+        for k in self._SAVED:
+            self._buf[k].copy_(torch.as_tensor(np.ascontiguousarray(sd[k])))
+        for k, t in self._drawn.items():
+            t.copy_(torch.as_tensor(np.ascontiguousarray(sd["drawn"][k])))
+        h = torch.as_tensor(np.ascontiguousarray(sd["history"])).to(self.device)
+        rows = max(8, 2 * h.shape[0])
+        self._history = torch.zeros(rows, *self._history.shape[1:], dtype=torch.float64, device=self.device)
+        self._history[:h.shape[0]].copy_(h)
+        self.generation = int(sd["generation"])
+        return self
+
+
 def read_state(venv):
     """The episodes a vec env holds as (own [E, 4], traffic [E, N, 4], goal [E, 2]) float64 arrays: set_state()'s and
     evaluate_policies_fused()'s arguments."""

@@ -219,3 +219,172 @@ def monte_carlo_summary(acc, baseline=None, hist_max=None):
         if baseline is not None:
             out["risk_ratio"] = out["collision_rate"] / out["collision_rate"][int(baseline)]
     return out
+
+
+# ---- encounter search (acas2d_encounter_*, policy.EncounterSearch): the definitions of the three kernels, on the host -------
+# An encounter is a point of the unit cube with 4 (N + 1) coordinates (coordinate 4 e + j: word j of entity e's Philox block;
+# entity 0 is the player, n + 1 traffic n); the proposal is one piecewise-constant density per coordinate, p[c][b] on B equal
+# bins.  No random numbers are drawn here: the caller brings the uniforms.
+SEARCH_HISTORY_COLUMNS = ("finished", "unfinished", "n_elite", "gamma_q", "gamma", "n_event", "sum_w_event", "sum_w2_event",
+                          "sum_w", "sum_w2", "min_score", "min_candidate", "generation")
+SEARCH_HISTORY_WIDTH = 16                     # the three last columns are spare (0)
+_T_MAX = 1.0 - 2.0 ** -53
+
+
+def search_active_coordinates(config):
+    """bool [4 (N + 1)]: the coordinates that reach the state under the reset distribution -- the player's heading (word z);
+    traffic 0's x (through the starts_down bit only), z, and w iff the airspeed factor varies; traffic n >= 1's x, y, z, and w
+    under the same condition.  The others are drawn nominally, never refit, and add nothing to the likelihood ratio."""
+    N = int(config.n_traffic)
+    speed = config.airspeed_factor_min != config.airspeed_factor_max
+    act = np.zeros((N + 1, 4), bool)
+    act[0, 2] = True
+    act[1] = [True, False, True, speed]
+    act[2:] = [True, True, True, speed]
+    return act.reshape(-1)
+
+
+def search_tables(p):
+    """The tables the sampler reads beside p [..., B]: cdf [..., B + 1] (cdf[0] = 0, cdf[b + 1] = cdf[b] + p[b], added one
+    after the other in ascending b) and log_ratio [..., B] = -log(B p[b])."""
+    p = np.asarray(p, np.float64)
+    B = p.shape[-1]
+    cdf = np.zeros(p.shape[:-1] + (B + 1,), np.float64)
+    for b in range(B):
+        cdf[..., b + 1] = cdf[..., b] + p[..., b]
+    with np.errstate(divide="ignore"):
+        log_ratio = -np.log(B * p)
+    return cdf, log_ratio
+
+
+def search_sample(tables, active, u):
+    """The inverse CDF of one policy's proposal on uniforms u [L, n_coord]: tables = (p, cdf, log_ratio), each [n_coord, ...].
+    Per active coordinate: b = the largest bin with cdf[b] <= u (at most B - 1), t = (u - cdf[b]) / p[b] clamped to
+    [0, 1 - 2^-53] (a NaN to 0), c = (b + t) / B; an inactive one keeps c = u (bin min(int(u B), B - 1)).  Returns c [L, n_coord]
+    float64, bins [L, n_coord] uint8 and log_w [L]: the active coordinates' log_ratio[b], added in ascending coordinate order
+    from 0."""
+    p, cdf, log_ratio = (np.asarray(t, np.float64) for t in tables)
+    u = np.asarray(u, np.float64)
+    L, NC = u.shape
+    B = p.shape[-1]
+    c, bins, log_w = u.copy(), np.zeros((L, NC), np.uint8), np.zeros(L, np.float64)
+    for j in range(NC):
+        uj = u[:, j]
+        if not active[j]:
+            bins[:, j] = np.minimum((uj * B).astype(np.int64), B - 1)
+            continue
+        b = np.where(cdf[j, None, :B] <= uj[:, None], np.arange(B)[None, :], 0).max(1)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            t = (uj - cdf[j, b]) / p[j, b]
+            t = np.where(t > 0.0, t, 0.0)
+        t = np.where(t < _T_MAX, t, _T_MAX)
+        c[:, j] = (b.astype(np.float64) + t) / float(B)
+        bins[:, j] = b
+        log_w = log_w + log_ratio[j, b]
+    return c, bins, log_w
+
+
+def _py_mod360(a):
+    r = np.where(a >= 360.0, a - 360.0, a)
+    r = np.where(a < 0.0, a + 360.0, r)
+    out = ~((a > -360.0) & (a < 720.0))
+    if np.any(out):
+        r = np.where(out, np.mod(a, 360.0), r)
+    return r
+
+
+def encounter_from_uniforms(config, c, dtype=np.float64):
+    """The encounters of coordinates c [L, 4 (N + 1)]: the reset distribution's float64 formulas (game.py:80-116, as the
+    engine's reset evaluates them) with c in place of the uniforms and starts_down = c_x >= 0.5 for traffic 0, rounded to
+    `dtype`.  Returns own [L, 4] = (x, y, psi, v), traffic [L, N, 4], goal [L, 2]."""
+    cc = config.to_c()
+    N = int(config.n_traffic)
+    c = np.asarray(c, np.float64).reshape(-1, N + 1, 4)
+    L = c.shape[0]
+    uni = lambda a, b, u: a + (b - a) * u  # noqa: E731
+    own = np.empty((L, 4), np.float64)
+    own[:, 0], own[:, 1], own[:, 3] = cc.own_x0, cc.own_y0, cc.own_v
+    own[:, 2] = _py_mod360(cc.own_heading0 + uni(-cc.own_heading_jitter, cc.own_heading_jitter, c[:, 0, 2]))
+    trf = np.empty((L, N, 4), np.float64)
+    down = (c[:, 1, 0] >= 0.5).astype(np.float64)
+    trf[:, :, 0] = uni(0.0, cc.tn_x_max, c[:, 1:, 0])
+    trf[:, :, 1] = uni(0.0, cc.tn_y_max, c[:, 1:, 1])
+    trf[:, :, 2] = uni(0.0, 360.0, c[:, 1:, 2])
+    trf[:, :, 3] = uni(cc.speed_factor_min, cc.speed_factor_max, c[:, 1:, 3]) * cc.airspeed
+    trf[:, 0, 0] = cc.t0_x
+    trf[:, 0, 1] = cc.t0_y_base + (down * cc.t0_y_span)
+    trf[:, 0, 2] = _py_mod360((cc.t0_heading_base + (down * cc.t0_heading_step)) +
+                              uni(-cc.t0_heading_jitter, cc.t0_heading_jitter, c[:, 1, 2]))
+    goal = np.tile(np.array([cc.goal_x, cc.goal_y], np.float64), (L, 1))
+    dt = np.dtype(dtype)
+    return own.astype(dt), trf.astype(dt), goal.astype(dt)
+
+
+def search_select(score, outcome, log_w, n_quantile, level, weighted=True):
+    """One policy's selection from min_separation `score` [L] (its dtype is the engine's), `outcome` [L] and log_w [L]: a
+    candidate's score is its min_separation where the episode finished and the value is a number, else +inf; gamma_q = the
+    n_quantile-th smallest score, gamma = max(gamma_q, level rounded to the dtype); the elite: score <= gamma and finite (ties
+    at gamma are all elite); W = exp(log_w) if weighted else 1.  Returns {"score", "elite" (bool), "elite_w" (W on the elite,
+    else 0), "row"}: row is the history row of SEARCH_HISTORY_COLUMNS without its generation (math.fsum sums; the first
+    candidate of the smallest score)."""
+    import math
+    score = np.asarray(score)
+    dt = score.dtype.type
+    oc = np.asarray(outcome)
+    L = score.shape[0]
+    s = np.where((oc != 0) & ~np.isnan(score), score, dt(np.inf)).astype(score.dtype)
+    gamma_q = np.sort(s, kind="stable")[int(n_quantile) - 1]
+    gamma = max(gamma_q, dt(level))
+    elite = (s <= gamma) & np.isfinite(s)
+    event = s <= dt(level)
+    w = np.exp(np.asarray(log_w, np.float64)) if weighted else np.ones(L, np.float64)
+    row = np.zeros(SEARCH_HISTORY_WIDTH, np.float64)
+    row[:12] = [int((oc != 0).sum()), int((oc == 0).sum()), int(elite.sum()), gamma_q, gamma, int(event.sum()),
+                math.fsum(w[event]), math.fsum(w[event] * w[event]), math.fsum(w), math.fsum(w * w), s.min(), int(np.argmin(s))]
+    return {"score": s, "elite": elite, "elite_w": np.where(elite, w, 0.0), "row": row}
+
+
+def search_refit(p, active, bins, elite_w, alpha, p_floor):
+    """One policy's new proposal from p [n_coord, B], the candidates' bins [L, n_coord] and elite_w [L]: per active coordinate
+    S[b] = the elite weight in bin b (math.fsum), S_tot = their sum in ascending b; unless S_tot > 0 the row stays; else
+    p_new[b] = max((1 - alpha) p[b] + alpha (S[b] / S_tot), p_floor), divided by the sum of p_new in ascending b.  Inactive rows
+    are returned as they are."""
+    import math
+    p = np.array(p, np.float64, copy=True)
+    bins, w = np.asarray(bins), np.asarray(elite_w, np.float64)
+    B = p.shape[-1]
+    keep = 1.0 - float(alpha)
+    elite = w != 0.0                                             # (a non-elite adds nothing)
+    bins, w = bins[elite], w[elite]
+    for j in np.nonzero(np.asarray(active))[0]:
+        S = np.array([math.fsum(w[bins[:, j] == b]) for b in range(B)], np.float64)
+        s_tot = 0.0
+        for b in range(B):
+            s_tot = s_tot + S[b]
+        if not s_tot > 0.0:
+            continue
+        pn = np.maximum((keep * p[j]) + (float(alpha) * (S / s_tot)), float(p_floor))
+        norm = 0.0
+        for b in range(B):
+            norm = norm + pn[b]
+        p[j] = pn / norm
+    return p
+
+
+def search_estimate(history_rows, n_candidates, first_generation=0):
+    """The importance-sampling estimate of the event's probability from history rows [G, ..., SEARCH_HISTORY_WIDTH] (further
+    axes, e.g. policies, are kept): per generation p_g = sum_w_event / L, its standard error sqrt((sum_w2_event / L - p_g^2) /
+    (L - 1)) and the effective sample size sum_w^2 / sum_w2; and over the generations from first_generation on the mean of
+    p_g and its standard error sqrt(sum se_g^2) / G'.  A generation's proposal is fixed before the generation is drawn, so every
+    p_g is unbiased and so is their mean."""
+    h = np.asarray(history_rows, np.float64)
+    L = float(n_candidates)
+    p_g = h[..., 6] / L
+    with np.errstate(invalid="ignore", divide="ignore"):
+        se_g = np.sqrt(np.maximum(h[..., 7] / L - p_g * p_g, 0.0) / (L - 1.0))
+        ess = h[..., 8] * h[..., 8] / h[..., 9]
+    sel = slice(int(first_generation), None)
+    n = p_g[sel].shape[0]
+    return {"p_generation": p_g, "se_generation": se_g, "ess": ess, "n_event": h[..., 5], "generations": n,
+            "p": p_g[sel].mean(0) if n else np.full(p_g.shape[1:], np.nan),
+            "se": np.sqrt((se_g[sel] ** 2).sum(0)) / n if n else np.full(p_g.shape[1:], np.nan)}

@@ -450,6 +450,80 @@ int acas2d_monte_carlo_group_f32(const Acas2dConfig *cfg, const Acas2dState *sta
                                  const Acas2dMonteCarlo *mc, void *stream);
 
 /*
+ * acas2d_encounter_sample_f32 / _f64, acas2d_encounter_select_f32 / _f64, acas2d_encounter_refit: a cross-entropy search
+ * over encounters with importance sampling, around the unchanged acas2d_evaluate_policies_stats_* -- per generation:
+ * sample, acas2d_reset_* with do_init = 0 (the first observation), the stats entry, select, refit, with no host decision
+ * in between.  Additive to ABI 7.  K = n_policies searches run side by side on the blocks of EP = n_candidates rounded up
+ * to 64 envs the stats entry plays; L = n_candidates, N = n_traffic, B = n_bins.
+ *
+ * An encounter is a point of the unit cube with n_coord = 4 (N + 1) coordinates: coordinate 4 e + j takes the place of
+ * u01(word j) of the Philox block of entity e (0 = the player, n + 1 = traffic n) in the reset distribution.  The
+ * proposal is one piecewise-constant density per coordinate on B equal bins, p[k][c][b]; coordinates with active[c] == 0
+ * (they do not reach the state) keep their uniform, are never refit and add nothing to the likelihood ratio.
+ *
+ * sample.  Candidate i of block k draws reset's own blocks, counter (lane lo, lane hi, generation, e), key = seed, lane =
+ * env_offset + i, and for every active coordinate, with u = u01(word):
+ *   b = the largest bin with cdf[b] <= u (cdf[0] = 0, so at most B - 1);  t = (u - cdf[b]) / p[b], below 0 or NaN -> 0,
+ *   above 1 - 2^-53 -> 1 - 2^-53;  c = (b + t) / B;  log_w += log_ratio[b]
+ * (ascending coordinates, plain float64 adds from 0).  The state is reset's float64 formulas on c, with starts_down =
+ * c_x >= 0.5 for traffic 0, rounded to the element type and stored into `state` (own_x .. trf_v, goal, steps = 0,
+ * total_reward = 0) at env k EP + i; envs i >= L repeat candidate 0.  bins[k][c][i] is the bin (of an inactive
+ * coordinate: min((int)(u B), B - 1)).  With a flat proposal c == u bit for bit: generation g of a float64 search is
+ * episode counter g of acas2d_reset_f64.
+ *
+ * select.  One workgroup per k: score_i = min_sep[k][i] where outcome[k][i] != 0 and the value is not NaN, else +inf;
+ * gamma_q = the n_quantile-th smallest score (radix select on the order-preserving integer key); gamma = max(gamma_q,
+ * level rounded to the element type); elite: score <= gamma and finite; W_i = exp(log_w[k][i]) if weighted, else 1;
+ * elite_w[k][i] = W_i for the elite, else 0.  history[k][0 .. 15], this generation's row of the log: finished,
+ * unfinished, n_elite, gamma_q, gamma, n_event = #{score <= level}, the sums of W and W^2 over the event, the sums of W
+ * and W^2 over all candidates, the smallest score, its candidate (the lowest index), the generation, three zeros.  The
+ * archive: where that smallest score is strictly below best_score[k] (start it at +inf), best_score, best_generation
+ * and best_candidate are replaced and the encounter itself, drawn again from this generation's tables, is stored:
+ * best_own_psi[k] and best_traffic[k][n] = (x, y, psi, v).
+ *
+ * refit.  Per active coordinate c and policy k: S[b] = the sum of elite_w[k][i] over the candidates with bins[k][c][i]
+ * == b, S_tot = the sum of S[b], ascending b; unless S_tot > 0 nothing changes; else
+ *   p_new[b] = max((1 - alpha) p[b] + alpha (S[b] / S_tot), p_floor);  p[b] = p_new[b] / (the sum of p_new, ascending b)
+ *   cdf[0] = 0, cdf[b + 1] = cdf[b] + p[b];  log_ratio[b] = -log(B p[b])
+ * All sums over candidates are taken in one fixed order (thread-strided ascending, a fixed tree in the wave, the waves in
+ * order) without floating atomics: the same inputs give the same bits.
+ *
+ * Rejected with ACAS2D_EINVAL before anything is launched: a NULL cfg, state (sample) or search, a NULL buffer of either;
+ * n_bins not a power of two in 2 .. 64; n_coord != 4 (n_traffic + 1) (refit: not a multiple of 4 from 8 up); n_quantile
+ * outside 1 .. n_candidates; alpha outside [0, 1]; p_floor outside [0, 1 / n_bins); generation >= 2^32; a NaN level;
+ * n_candidates < 1; n_policies outside 1 .. 65535; a negative env_offset; a state of fewer than n_policies x EP envs.
+ */
+#define ACAS2D_SEARCH_HISTORY_WIDTH 16
+typedef struct Acas2dEncounterSearch {
+    double *p, *cdf, *log_ratio;     /* double[K][n_coord][B], [K][n_coord][B + 1], [K][n_coord][B] */
+    const uint8_t *active;           /* u8[n_coord] */
+    uint8_t *bins;                   /* u8[K][n_coord][L] */
+    double *log_w, *elite_w;         /* double[K][L] */
+    const uint8_t *outcome;          /* u8[K][L]: the stats entry's outcome */
+    const void *min_sep;             /* T[K][L]: the stats entry's Acas2dEvalStats.min_sep */
+    double *history;                 /* double[K][ACAS2D_SEARCH_HISTORY_WIDTH]: this generation's row */
+    void *best_score;                /* T[K] */
+    uint32_t *best_generation;       /* u32[K] */
+    int32_t *best_candidate;         /* int32[K] */
+    void *best_own_psi, *best_traffic;   /* T[K], T[K][N][4] */
+    int32_t n_bins, n_coord, n_quantile, weighted;
+    double alpha, p_floor, level;
+    uint64_t generation;
+} Acas2dEncounterSearch;
+size_t acas2d_encounter_search_size(void);  /* sizeof(Acas2dEncounterSearch), for bindings */
+int acas2d_encounter_sample_f32(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs, int32_t n_policies,
+                                int32_t n_candidates, uint64_t seed, int64_t env_offset, int32_t n_traffic,
+                                const Acas2dEncounterSearch *search, void *stream);
+int acas2d_encounter_sample_f64(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs, int32_t n_policies,
+                                int32_t n_candidates, uint64_t seed, int64_t env_offset, int32_t n_traffic,
+                                const Acas2dEncounterSearch *search, void *stream);
+int acas2d_encounter_select_f32(const Acas2dConfig *cfg, int32_t n_policies, int32_t n_candidates, uint64_t seed,
+                                int64_t env_offset, int32_t n_traffic, const Acas2dEncounterSearch *search, void *stream);
+int acas2d_encounter_select_f64(const Acas2dConfig *cfg, int32_t n_policies, int32_t n_candidates, uint64_t seed,
+                                int64_t env_offset, int32_t n_traffic, const Acas2dEncounterSearch *search, void *stream);
+int acas2d_encounter_refit(const Acas2dEncounterSearch *search, int32_t n_policies, int32_t n_candidates, void *stream);
+
+/*
  * acas2d_collect_set_group_f32: acas2d_collect_set_f32 for n_traffic in {8, 16, 32, 64}, float32 -- the same arguments,
  * layouts and outputs.  Additive to ABI 7.  The launch is acas2d_collect_group_f32's (the env's G lanes of the packed work
  * shapes (4,2) (4,4) (4,8) (4,16) evaluate the two networks together) with the member found per wavefront: a wavefront

@@ -11,8 +11,14 @@ LANES x EPISODES randomly drawn encounters of seed 13, and one JSON line per che
 Wilson 95 % interval, the goal / timeout / loss-of-separation rates, mean steps and mean return with its standard error.
 --baseline-zero appends the all-zero policy (the unequipped aircraft: baseline_main.py's constant action [0]) and adds
 each checkpoint's risk ratio against it.
+--search CANDIDATESxGENERATIONS instead runs an encounter search per checkpoint (policy.EncounterSearch: cross-entropy
+proposals refit on the device, importance-sampling weights): one JSON line per checkpoint gives the estimated probability of
+min_separation <= the collision distance with its standard error, beside a crude campaign of the same number of episodes
+(that campaign's share of episodes below the same separation, and its collision rate with the Wilson 95 % interval), and the
+closest encounter found.
 
     python tools/evaluate_checkpoints.py DIR [--dtype float64|float32] [--episodes 100] [--safety]
+    python tools/evaluate_checkpoints.py DIR --search 65536x8 [--dtype float32]
     python tools/evaluate_checkpoints.py DIR --monte-carlo 65536x64 [--baseline-zero] [--dtype float32]
 """
 import argparse
@@ -37,6 +43,7 @@ ap.add_argument("--episodes", type=int, default=100)
 ap.add_argument("--safety", action="store_true")
 ap.add_argument("--monte-carlo", metavar="LANESxEPISODES", default=None)
 ap.add_argument("--baseline-zero", action="store_true")
+ap.add_argument("--search", metavar="CANDIDATESxGENERATIONS", default=None)
 args = ap.parse_args()
 
 steps_of = lambda p: int(re.search(r"model_(\d+)_steps\.zip$", p).group(1))  # noqa: E731
@@ -63,6 +70,28 @@ if args.monte_carlo:
         row["sep_hist"] = [int(x) for x in s["sep_hist"][k]]
         print(json.dumps(row), flush=True)
     print(json.dumps({"hist_edges": [float(x) for x in s["hist_edges"]], "lanes": lanes, "episodes_per_lane": episodes}), flush=True)
+    sys.exit(0)
+
+if args.search:
+    cand, gens = (int(x) for x in args.search.lower().split("x"))
+    dt = getattr(torch, args.dtype)
+    es = g.EncounterSearch(paths, cand, seed=13, dtype=dt).run(gens)
+    est, hist, closest = es.estimate(first_generation=min(2, gens - 1)), es.history(), es.best()
+    mc = g.MonteCarlo(paths, cand, seed=13, dtype=dt).run(gens)
+    acc, s = mc.accumulators(), mc.summary()
+    edge = es.level * mc.inv_bin_width                       # the crude share below `level`: where a bin edge lies on it
+    below = acc["sep_hist"][:, :int(edge)].sum(1) if edge == int(edge) else None
+    for k, path in enumerate(paths):
+        b = closest[k]
+        row = {"checkpoint": os.path.relpath(path, args.dir), "timesteps": steps_of(path) if k < len(ckpts) else None,
+               "level": es.level, "episodes": cand * gens, "estimate": float(est["p"][k]), "estimate_se": float(est["se"][k]),
+               "estimate_generations": int(est["generations"]), "events_per_generation": [int(x) for x in hist[:, k, 5]],
+               "crude_below_level": None if below is None else float(below[k]) / (cand * gens),
+               "crude_collision_rate": float(s["collision_rate"][k]),
+               "crude_collision_rate_95": [float(s["collision_rate_lo"][k]), float(s["collision_rate_hi"][k])],
+               "closest": None if b is None else {"generation": b[0], "candidate": b[1], "min_separation": float(b[2]),
+                                                  "own": b[3][0].tolist(), "traffic": b[4][0].tolist()}}
+        print(json.dumps(row), flush=True)
     sys.exit(0)
 
 own, trf, goal = g.reset_parity.draw_episodes(g.ACAS2DConfig(), args.episodes, random.Random(13))
