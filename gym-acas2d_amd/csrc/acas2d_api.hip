@@ -176,6 +176,45 @@ int acas2d_monte_carlo_group_f32(const Acas2dConfig* cfg, const Acas2dState* sta
     return launch_monte_carlo<float>(cfg, state, n_envs, policies, n_policies, n_lanes, obs_in, n_steps, seed, env_offset,
                                      n_traffic, mc, (hipStream_t)stream, true);
 }
+// ... and both under sensor noise and actuator disturbance (eval_stats_disturbed_kernel, monte_carlo_disturbed_kernel; float32)
+size_t acas2d_disturbance_size(void) { return sizeof(Acas2dDisturbance); }
+int acas2d_evaluate_policies_disturbed_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs,
+                                           const Acas2dPolicy* policies, int32_t n_policies, int32_t n_episodes, const void* obs_in,
+                                           int32_t n_steps, uint64_t seed, int64_t env_offset, int32_t n_traffic, uint8_t* outcome,
+                                           int32_t* steps, void* total_reward, const Acas2dEvalStats* stats,
+                                           const Acas2dDisturbance* disturbance, void* stream) {
+    return launch_evaluate_policies_disturbed<float>(cfg, state, n_envs, policies, n_policies, n_episodes, obs_in, n_steps, seed,
+                                                     env_offset, n_traffic, outcome, steps, total_reward, stats, disturbance,
+                                                     (hipStream_t)stream);
+}
+int acas2d_evaluate_policies_disturbed_group_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs,
+                                                 const Acas2dPolicy* policies, int32_t n_policies, int32_t n_episodes,
+                                                 const void* obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
+                                                 int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
+                                                 const Acas2dEvalStats* stats, const Acas2dDisturbance* disturbance, void* stream) {
+    return launch_evaluate_policies_disturbed<float>(cfg, state, n_envs, policies, n_policies, n_episodes, obs_in, n_steps, seed,
+                                                     env_offset, n_traffic, outcome, steps, total_reward, stats, disturbance,
+                                                     (hipStream_t)stream, true);
+}
+int acas2d_monte_carlo_disturbed_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs, const Acas2dPolicy* policies,
+                                     int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
+                                     int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc,
+                                     const Acas2dDisturbance* disturbance, void* stream) {
+    return launch_monte_carlo_disturbed<float>(cfg, state, n_envs, policies, n_policies, n_lanes, obs_in, n_steps, seed, env_offset,
+                                               n_traffic, mc, disturbance, (hipStream_t)stream);
+}
+int acas2d_monte_carlo_disturbed_group_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs,
+                                           const Acas2dPolicy* policies, int32_t n_policies, int32_t n_lanes, const void* obs_in,
+                                           int32_t n_steps, uint64_t seed, int64_t env_offset, int32_t n_traffic,
+                                           const Acas2dMonteCarlo* mc, const Acas2dDisturbance* disturbance, void* stream) {
+    return launch_monte_carlo_disturbed<float>(cfg, state, n_envs, policies, n_policies, n_lanes, obs_in, n_steps, seed, env_offset,
+                                               n_traffic, mc, disturbance, (hipStream_t)stream, true);
+}
+int acas2d_disturbance_draw_f32(uint64_t noise_seed, int64_t first_lane, int32_t n_lanes, uint32_t episode, int32_t first_step,
+                                int32_t n_steps, int32_t n_slots, float* out, void* stream) {
+    return launch_disturbance_draw<float>(noise_seed, first_lane, n_lanes, episode, first_step, n_steps, n_slots, out,
+                                          (hipStream_t)stream);
+}
 int acas2d_reset_f32(const Acas2dConfig* cfg, const Acas2dState* state, const uint8_t* mask, void* obs,
                      int32_t do_init, uint64_t seed, int64_t env_offset, int64_t n_envs, int32_t n_traffic,
                      void* stream) {

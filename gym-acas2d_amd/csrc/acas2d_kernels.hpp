@@ -1460,6 +1460,47 @@ __device__ __forceinline__ const PolicyMonteCarloW* monte_carlo_args(const PW& p
     else return nullptr;
 }
 
+// DIST on top of STATS or MC (acas2d_evaluate_policies_disturbed_*, acas2d_monte_carlo_disturbed_*; float32): white Gaussian
+// noise on the three observation entries of every traffic aircraft in front of the actor and on the clipped action behind
+// it (include/acas2d.h, Acas2dDisturbance; records.disturb_observation() / disturb_action() are the arithmetic in NumPy).
+// The kernels are eval_stats_disturbed_kernel and monte_carlo_disturbed_kernel, their last arguments these derived structs.
+struct DisturbW {
+    float s_sep, s_cpa, s_closing, s_action;         // standard deviations, normalised observation units / action units
+    uint32_t k0, k1;                                 // the two halves of noise_seed (the tag is applied in the draw)
+    uint32_t episode;                                // the evaluator's episode counter (the campaign uses the lane's own)
+};
+struct PolicyEvalStatsDistW : PolicyEvalStatsW { DisturbW dist; };
+struct PolicyMonteCarloDistW : PolicyMonteCarloW { DisturbW dist; };
+// the body's view of them (as monte_carlo_args())
+template <typename PW>
+__device__ __forceinline__ const DisturbW* disturbance_args(const PW& pw) {
+    if constexpr (std::is_base_of<PolicyEvalStatsDistW, PW>::value || std::is_base_of<PolicyMonteCarloDistW, PW>::value)
+        return &pw.dist;
+    else return nullptr;
+}
+constexpr uint32_t kDisturbanceTag = 0x64697374u;    // "dist": keeps the blocks apart from the reset's under the same seed
+constexpr int kDisturbanceSlotShift = 20;            // counter word 3 = step | slot << 20
+// The normals of (lane, episode, step, slot): ONE Philox block, Box-Muller on 24-bit uniforms with the hardware's log, sqrt,
+// sin and cos (the collector's sampler).  A traffic slot (n + 1) reads z_sep, z_cpa, z_closing; the actuator slot (0) z_sep.
+// Every user -- the two kernels and acas2d_disturbance_draw_f32 -- calls this function.
+__device__ __forceinline__ void disturbance_normals(uint32_t k0, uint32_t k1, uint64_t lane, uint32_t episode, uint32_t step,
+                                                    uint32_t slot, float& z_sep, float& z_cpa, float& z_closing) {
+    const U4 w = philox4x32(U4{(uint32_t)lane, (uint32_t)(lane >> 32), episode, step | (slot << kDisturbanceSlotShift)},
+                            k0, k1 ^ kDisturbanceTag);
+    const float r1 = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u01f(w.x)));      // sqrt(-2 ln u1)
+    const float r3 = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(u01f(w.z)));
+    const float u2 = u01f(w.y);
+    z_sep = r1 * __builtin_amdgcn_cosf(u2);                                                                // cos(2 pi u2)
+    z_cpa = r1 * __builtin_amdgcn_sinf(u2);
+    z_closing = r3 * __builtin_amdgcn_cosf(u01f(w.w));
+}
+// x + s z with both roundings, then the box [lo, hi] by comparisons: a NaN stays a NaN, -0 stays -0, and s == 0 leaves x as it is
+__device__ __forceinline__ float disturbed(float x, float s, float z, float lo, float hi) {
+    if (s == 0.0f) return x;
+    const float y = __fadd_rn(x, __fmul_rn(s, z));
+    return y < lo ? lo : (y > hi ? hi : y);
+}
+
 // tanh(x) = 1 - 2 / (exp(2x) + 1) on v_exp_f32 / v_rcp_f32: abs error < 2e-7 over the reals
 // (saturates cleanly: exp -> inf gives 1, exp -> 0 gives -1).
 __device__ __forceinline__ float tanh_hw(float x) {
@@ -1700,7 +1741,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
                                                       Params<T> p_arg, StepResetParams<T, rollout_mode(M)> rp_arg, State<T> s_arg,
                                                       StepIO<T> io_arg, uint32_t k0, uint32_t k1,
                                                       int64_t env_offset, int N_arg, int n_steps, PolicyArg<M == Mode::Eval> pw) {
-    constexpr bool STATS = false, MC = false;
+    constexpr bool STATS = false, MC = false, DIST = false;
 #include "acas2d_step_body.inl"
 }
 // Mode::Eval with STATS: step_kernel's arguments (and so the same preloaded ones) with PolicyEvalStatsW at the end.
@@ -1711,7 +1752,7 @@ __global__ __launch_bounds__(kBlock) void eval_stats_kernel(const T* a0, const T
                                                             Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
                                                             StepIO<T> io_arg, uint32_t k0, uint32_t k1,
                                                             int64_t env_offset, int N_arg, int n_steps, PolicyEvalStatsW pw) {
-    constexpr bool PACKED = true, STATS = true, MC = false;
+    constexpr bool PACKED = true, STATS = true, MC = false, DIST = false;
     constexpr Mode M = Mode::Eval;
 #include "acas2d_step_body.inl"
 }
@@ -1725,9 +1766,48 @@ __global__ __launch_bounds__(kBlock) void monte_carlo_kernel(const T* a0, const 
                                                              Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
                                                              StepIO<T> io_arg, uint32_t k0, uint32_t k1,
                                                              int64_t env_offset, int N_arg, int n_steps, PolicyMonteCarloW pw) {
-    constexpr bool PACKED = true, STATS = true, MC = true;
+    constexpr bool PACKED = true, STATS = true, MC = true, DIST = false;
     constexpr Mode M = Mode::Eval;
 #include "acas2d_step_body.inl"
+}
+
+// eval_stats_kernel and monte_carlo_kernel with DIST (acas2d_evaluate_policies_disturbed_*, acas2d_monte_carlo_disturbed_*):
+// the observation the actor reads and the action it returns are disturbed (DisturbW).  Kernels of their own for the reason
+// eval_stats_kernel is one; float32 only.
+template <typename T, int C, int G, bool FAST>
+__global__ __launch_bounds__(kBlock) void eval_stats_disturbed_kernel(const T* a0, const T* a1, const T* a2, const T* a3,
+                                                                      const T* a4, const T* a5, int32_t e_n_envs, int32_t tile_elems,
+                                                                      Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
+                                                                      StepIO<T> io_arg, uint32_t k0, uint32_t k1, int64_t env_offset,
+                                                                      int N_arg, int n_steps, PolicyEvalStatsDistW pw) {
+    constexpr bool PACKED = true, STATS = true, MC = false, DIST = true;
+    constexpr Mode M = Mode::Eval;
+#include "acas2d_step_body.inl"
+}
+template <typename T, int C, int G, bool FAST>
+__global__ __launch_bounds__(kBlock) void monte_carlo_disturbed_kernel(const T* a0, const T* a1, const T* a2, const T* a3,
+                                                                       const T* a4, const T* a5, int32_t e_n_envs, int32_t tile_elems,
+                                                                       Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
+                                                                       StepIO<T> io_arg, uint32_t k0, uint32_t k1, int64_t env_offset,
+                                                                       int N_arg, int n_steps, PolicyMonteCarloDistW pw) {
+    constexpr bool PACKED = true, STATS = true, MC = true, DIST = true;
+    constexpr Mode M = Mode::Eval;
+#include "acas2d_step_body.inl"
+}
+// acas2d_disturbance_draw_f32: the normals of n_steps x n_lanes x n_slots blocks as float[n_steps][n_lanes][n_slots][3]
+// (slot 0: the actuator's normal, then two zeros), one thread each, through disturbance_normals()
+template <typename T>
+__global__ __launch_bounds__(256) void disturbance_draw_kernel(uint32_t k0, uint32_t k1, uint64_t first_lane, uint32_t n_lanes,
+                                                               uint32_t episode, uint32_t first_step, uint32_t n_slots,
+                                                               uint64_t total, T* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= total) return;
+    const uint32_t slot = (uint32_t)(i % n_slots);
+    const uint64_t r = i / n_slots;
+    const uint32_t lane = (uint32_t)(r % n_lanes), step = (uint32_t)(r / n_lanes);
+    float z0, z1, z2;
+    disturbance_normals(k0, k1, first_lane + lane, episode, first_step + step, slot, z0, z1, z2);
+    out[3 * i] = z0; out[3 * i + 1] = slot ? z1 : 0.0f; out[3 * i + 2] = slot ? z2 : 0.0f;
 }
 
 // ACAS2DEnv.reset(), environment.py:44-48 (do_init != 0: fresh episodes; == 0: keep the injected state).
@@ -1821,6 +1901,21 @@ template <typename T>
 int launch_monte_carlo(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
                        int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
                        int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc, hipStream_t stream, bool group = false);
+// acas2d_evaluate_policies_disturbed_*, acas2d_monte_carlo_disturbed_*, acas2d_disturbance_draw_f32 (float32 only)
+template <typename T>
+int launch_evaluate_policies_disturbed(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
+                                       int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
+                                       int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
+                                       const Acas2dEvalStats* stats, const Acas2dDisturbance* dist, hipStream_t stream,
+                                       bool group = false);
+template <typename T>
+int launch_monte_carlo_disturbed(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
+                                 int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
+                                 int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc, const Acas2dDisturbance* dist,
+                                 hipStream_t stream, bool group = false);
+template <typename T>
+int launch_disturbance_draw(uint64_t seed, int64_t first_lane, int32_t n_lanes, uint32_t episode, int32_t first_step,
+                            int32_t n_steps, int32_t n_slots, T* out, hipStream_t stream);
 // acas2d_collect_set_f32 and acas2d_collect_set_group_f32 (float32 only: acas2d_f32.hip instantiates them)
 template <typename T>
 int launch_collect_set(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,

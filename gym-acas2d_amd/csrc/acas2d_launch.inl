@@ -337,7 +337,15 @@ static int launch_mode(const Launch<T>& L, const PW& pw) {
         if constexpr ((M != Mode::Arena || (packed && sizeof(T) == 4)) && (!rollout_mode(M) || packed) &&
                       (!policy_mode(M) || G == 1 || (sizeof(T) == 4 && packed && group_policy_shape(C, G))) &&
                       (M != Mode::CollectSet || sizeof(T) == 4)) {
-            if constexpr (std::is_same<PW, PolicyMonteCarloW>::value)     // ... and the Monte Carlo campaign: its own too
+            if constexpr (std::is_same<PW, PolicyMonteCarloDistW>::value) // ... and the two disturbed flavours (float32)
+                hipLaunchKernelGGL((monte_carlo_disturbed_kernel<T, C, G, fast>), dim3(L.g.grid), dim3(L.g.block), L.g.lds_bytes,
+                                   L.stream, a[0], a[1], a[2], a[3], a[4], a[5], (int32_t)L.n_envs, (int32_t)L.g.tile_elems,
+                                   L.p, rp, s, L.io, L.k0, L.k1, L.env_offset, L.N, L.n_steps, pw);
+            else if constexpr (std::is_same<PW, PolicyEvalStatsDistW>::value)
+                hipLaunchKernelGGL((eval_stats_disturbed_kernel<T, C, G, fast>), dim3(L.g.grid), dim3(L.g.block), L.g.lds_bytes,
+                                   L.stream, a[0], a[1], a[2], a[3], a[4], a[5], (int32_t)L.n_envs, (int32_t)L.g.tile_elems,
+                                   L.p, rp, s, L.io, L.k0, L.k1, L.env_offset, L.N, L.n_steps, pw);
+            else if constexpr (std::is_same<PW, PolicyMonteCarloW>::value) // ... and the Monte Carlo campaign: its own too
                 hipLaunchKernelGGL((monte_carlo_kernel<T, C, G, fast>), dim3(L.g.grid), dim3(L.g.block), L.g.lds_bytes,
                                    L.stream, a[0], a[1], a[2], a[3], a[4], a[5], (int32_t)L.n_envs, (int32_t)L.g.tile_elems,
                                    L.p, rp, s, L.io, L.k0, L.k1, L.env_offset, L.N, L.n_steps, pw);
@@ -520,16 +528,35 @@ int launch_collect_set_group(const Acas2dConfig* cfg, const Acas2dState* st, con
     return collect_set<T>(cfg, st, io, ac, n_members, noise_seeds, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream, true);
 }
 
+// what the disturbed entries check on top of their siblings (after them: cfg is there), and the kernels' view of the struct
+static int check_disturbance(const char* name, const Acas2dConfig* cfg, const Acas2dDisturbance* d) {
+    if (!d) return fail("%s: NULL disturbance", name);
+    const float sd[4] = {d->s_sep, d->s_cpa, d->s_closing, d->s_action};
+    for (float v : sd)
+        if (!(v >= 0.0f) || !(v < __builtin_inff()))
+            return fail("%s: s_sep = %g, s_cpa = %g, s_closing = %g, s_action = %g (each finite and at least 0)", name,
+                        (double)sd[0], (double)sd[1], (double)sd[2], (double)sd[3]);
+    if ((int64_t)cfg->max_steps + 1 >= (1ll << kDisturbanceSlotShift))
+        return fail("%s: max_steps = %d (max_steps + 1 must stay below 2^%d, the step field of the noise counter)", name,
+                    cfg->max_steps, kDisturbanceSlotShift);
+    return ACAS2D_OK;
+}
+static DisturbW disturbance_words(const Acas2dDisturbance& d) {
+    return DisturbW{d.s_sep, d.s_cpa, d.s_closing, d.s_action, (uint32_t)d.noise_seed, (uint32_t)(d.noise_seed >> 32), d.noise_episode};
+}
+
 // K stacked policies scored on shared episodes: policy k plays envs [k EP, (k + 1) EP) of the state, EP = n_episodes
 // rounded up to a whole wave; the launch covers those n_policies x EP envs.  STATS (the acas2d_evaluate_policies_stats_*
 // entry points) adds the per-episode safety statistics: eval_stats_kernel instead of step_kernel<..., Mode::Eval>.
-template <typename T, bool STATS>
+template <typename T, bool STATS, bool DIST = false>
 static int evaluate_policies(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
                              int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
                              int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
-                             hipStream_t stream, bool group, const Acas2dEvalStats* stats) {
+                             hipStream_t stream, bool group, const Acas2dEvalStats* stats, const Acas2dDisturbance* dist = nullptr) {
+    static_assert(!DIST || (STATS && sizeof(T) == 4), "disturbed evaluation: float32, always with statistics");
     const int64_t ep = ((int64_t)n_episodes + 63) / 64 * 64, total = (int64_t)n_policies * ep;
-    Launch<T> L{STATS ? (group ? "acas2d_evaluate_policies_stats_group" : "acas2d_evaluate_policies_stats")
+    Launch<T> L{DIST ? (group ? "acas2d_evaluate_policies_disturbed_group" : "acas2d_evaluate_policies_disturbed") :
+                STATS ? (group ? "acas2d_evaluate_policies_stats_group" : "acas2d_evaluate_policies_stats")
                       : (group ? "acas2d_evaluate_policies_group" : "acas2d_evaluate_policies"),
                 cfg, st, nullptr, seed, env_offset, total, n_traffic, n_steps, stream};
     L.group_policy = group;
@@ -544,10 +571,12 @@ static int evaluate_policies(const Acas2dConfig* cfg, const Acas2dState* st, int
         if (int rc = require_actor(L.name, pol)) return rc;
         if (n_policies < 1 || n_episodes < 1)
             return fail("%s: n_policies = %d, n_episodes = %d (at least 1 each)", L.name, n_policies, n_episodes);
+        if constexpr (DIST) return check_disturbance(L.name, cfg, dist);
         return ACAS2D_OK;
     };
     const auto shape = [&](Shape* sh) {
-        const char* sibling = STATS ? "acas2d_evaluate_policies_stats_f32" : "acas2d_evaluate_policies_f32";
+        const char* sibling = DIST ? "acas2d_evaluate_policies_disturbed_f32"
+                                   : (STATS ? "acas2d_evaluate_policies_stats_f32" : "acas2d_evaluate_policies_f32");
         if (int rc = group ? group_shape<T>(L.name, sibling, n_traffic, sh) : thread_per_env(L.name, n_traffic, sh)) return rc;
         if (n_envs >= total) return ACAS2D_OK;
         return fail("acas2d_evaluate_policies: the state holds n_envs = %lld envs, %d policies x %lld (n_episodes = %d rounded up "
@@ -556,8 +585,10 @@ static int evaluate_policies(const Acas2dConfig* cfg, const Acas2dState* st, int
     const auto go = [&] {
         if (group)
             if (int rc = require_aligned(L.name, {pol->w1t, pol->b1, pol->w2t, pol->b2})) return rc;
-        using PW = typename std::conditional<STATS, PolicyEvalStatsW, PolicyEvalW>::type;
+        using PW = typename std::conditional<DIST, PolicyEvalStatsDistW,
+                                             typename std::conditional<STATS, PolicyEvalStatsW, PolicyEvalW>::type>::type;
         PW pw = actor<PW>(pol, obs_in);
+        if constexpr (DIST) pw.dist = disturbance_words(*dist);
         pw.res_outcome = outcome; pw.res_steps = steps; pw.res_return = total_reward;
         pw.n_episodes = n_episodes; pw.ep_stride = (int32_t)ep;
         if constexpr (STATS) {
@@ -592,12 +623,15 @@ int launch_evaluate_policies_stats(const Acas2dConfig* cfg, const Acas2dState* s
 // acas2d_monte_carlo_*: evaluate_policies()'s blocks of lanes, each lane playing mc->episodes_per_lane drawn episodes and
 // folding them into mc's accumulators (monte_carlo_kernel).  The checks and words of evaluate_policies<T, true>, then its own.
 // (Instantiated after the stats launcher -- ACAS2D_INSTANTIATE_MONTE_CARLO -- for the same reason.)
-template <typename T>
-int launch_monte_carlo(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
+template <typename T, bool DIST>
+static int monte_carlo(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
                        int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
-                       int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc, hipStream_t stream, bool group) {
+                       int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc, hipStream_t stream, bool group,
+                       const Acas2dDisturbance* dist) {
+    static_assert(!DIST || sizeof(T) == 4, "disturbed campaign: float32");
     const int64_t ep = ((int64_t)n_lanes + 63) / 64 * 64, total = (int64_t)n_policies * ep;
-    Launch<T> L{group ? "acas2d_monte_carlo_group" : "acas2d_monte_carlo", cfg, st, nullptr, seed, env_offset, total, n_traffic,
+    Launch<T> L{DIST ? (group ? "acas2d_monte_carlo_disturbed_group" : "acas2d_monte_carlo_disturbed")
+                     : (group ? "acas2d_monte_carlo_group" : "acas2d_monte_carlo"), cfg, st, nullptr, seed, env_offset, total, n_traffic,
                 n_steps, stream};
     L.group_policy = group;
     const auto inputs = [&] {
@@ -619,10 +653,12 @@ int launch_monte_carlo(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n
             return fail("%s: n_steps = %d does not cover episodes_per_lane = %d episodes of max_steps = %d steps (%lld needed; "
                         "episodes_per_lane x (max_steps + 1) must fit an int32, episodes_per_lane <= 2^24)", L.name, n_steps,
                         mc->episodes_per_lane, cfg->max_steps, (long long)need);
+        if constexpr (DIST) return check_disturbance(L.name, cfg, dist);
         return ACAS2D_OK;
     };
     const auto shape = [&](Shape* sh) {
-        if (int rc = group ? group_shape<T>(L.name, "acas2d_monte_carlo_f32", n_traffic, sh) : thread_per_env(L.name, n_traffic, sh))
+        if (int rc = group ? group_shape<T>(L.name, DIST ? "acas2d_monte_carlo_disturbed_f32" : "acas2d_monte_carlo_f32", n_traffic, sh)
+                           : thread_per_env(L.name, n_traffic, sh))
             return rc;
         if (n_envs >= total) return ACAS2D_OK;
         return fail("%s: the state holds n_envs = %lld envs, %d policies x %lld (n_lanes = %d rounded up to 64) need %lld", L.name,
@@ -631,7 +667,9 @@ int launch_monte_carlo(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n
     const auto go = [&] {
         if (group)
             if (int rc = require_aligned(L.name, {pol->w1t, pol->b1, pol->w2t, pol->b2})) return rc;
-        PolicyMonteCarloW pw = actor<PolicyMonteCarloW>(pol, obs_in);
+        using PW = typename std::conditional<DIST, PolicyMonteCarloDistW, PolicyMonteCarloW>::type;
+        PW pw = actor<PW>(pol, obs_in);
+        if constexpr (DIST) pw.dist = disturbance_words(*dist);
         pw.n_episodes = n_lanes; pw.ep_stride = (int32_t)ep;
         const auto u64 = [](int64_t* q) { return reinterpret_cast<unsigned long long*>(q); };
         pw.mc_outcome_count = u64(mc->outcome_count); pw.mc_sum_steps = u64(mc->sum_steps);
@@ -644,8 +682,58 @@ int launch_monte_carlo(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n
     };
     return prepare(L, Words{"cfg / policies", kSizes, "%s: negative env_offset"}, pol != nullptr, inputs, shape, go);
 }
+template <typename T>
+int launch_monte_carlo(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
+                       int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
+                       int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc, hipStream_t stream, bool group) {
+    return monte_carlo<T, false>(cfg, st, n_envs, pol, n_policies, n_lanes, obs_in, n_steps, seed, env_offset, n_traffic, mc, stream,
+                                 group, nullptr);
+}
 #define ACAS2D_INSTANTIATE_MONTE_CARLO \
     namespace acas2d { template decltype(launch_monte_carlo<Elem>) launch_monte_carlo<Elem>; }
+
+// The disturbed flavours of the two (eval_stats_disturbed_kernel, monte_carlo_disturbed_kernel) and the draw entry; float32,
+// instantiated after everything else of the unit (ACAS2D_INSTANTIATE_DISTURBED) for the reason the stats launcher is.
+template <typename T>
+int launch_evaluate_policies_disturbed(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
+                                       int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
+                                       int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
+                                       const Acas2dEvalStats* stats, const Acas2dDisturbance* dist, hipStream_t stream, bool group) {
+    return evaluate_policies<T, true, true>(cfg, st, n_envs, pol, n_policies, n_episodes, obs_in, n_steps, seed, env_offset,
+                                            n_traffic, outcome, steps, total_reward, stream, group, stats, dist);
+}
+template <typename T>
+int launch_monte_carlo_disturbed(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
+                                 int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
+                                 int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc, const Acas2dDisturbance* dist,
+                                 hipStream_t stream, bool group) {
+    return monte_carlo<T, true>(cfg, st, n_envs, pol, n_policies, n_lanes, obs_in, n_steps, seed, env_offset, n_traffic, mc, stream,
+                                group, dist);
+}
+template <typename T>
+int launch_disturbance_draw(uint64_t seed, int64_t first_lane, int32_t n_lanes, uint32_t episode, int32_t first_step,
+                            int32_t n_steps, int32_t n_slots, T* out, hipStream_t stream) {
+    const char* name = "acas2d_disturbance_draw";
+    if (!out) return fail("%s: NULL out", name);
+    if (n_lanes < 1 || n_steps < 1 || n_slots < 1)
+        return fail("%s: n_lanes = %d, n_steps = %d, n_slots = %d (at least 1 each)", name, n_lanes, n_steps, n_slots);
+    if (first_lane < 0 || first_step < 0) return fail("%s: negative first_lane / first_step", name);
+    if ((int64_t)first_step + n_steps > (1ll << kDisturbanceSlotShift))
+        return fail("%s: first_step = %d + n_steps = %d exceeds the step field of the noise counter (2^%d)", name, first_step,
+                    n_steps, kDisturbanceSlotShift);
+    if (n_slots > 65) return fail("%s: n_slots = %d (at most 65: the actuator and 64 traffic aircraft)", name, n_slots);
+    const uint64_t total = (uint64_t)n_steps * (uint64_t)n_lanes * (uint64_t)n_slots;
+    if (total > (1ull << 38)) return fail("%s: %llu blocks (at most 2^38 per call)", name, (unsigned long long)total);
+    hipLaunchKernelGGL((disturbance_draw_kernel<T>), dim3((unsigned)((total + 255u) / 256u)), dim3(256), 0, stream, (uint32_t)seed,
+                       (uint32_t)(seed >> 32), (uint64_t)first_lane, (uint32_t)n_lanes, episode, (uint32_t)first_step,
+                       (uint32_t)n_slots, total, out);
+    return check_launch(name);
+}
+#define ACAS2D_INSTANTIATE_DISTURBED \
+    namespace acas2d { \
+    template decltype(launch_evaluate_policies_disturbed<Elem>) launch_evaluate_policies_disturbed<Elem>; \
+    template decltype(launch_monte_carlo_disturbed<Elem>) launch_monte_carlo_disturbed<Elem>; \
+    template decltype(launch_disturbance_draw<Elem>) launch_disturbance_draw<Elem>; }
 
 template <typename T>
 int launch_reset(const Acas2dConfig* cfg, const Acas2dState* st, const uint8_t* mask, void* obs,

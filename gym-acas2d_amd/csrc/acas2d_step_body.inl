@@ -1,6 +1,7 @@
-// acas2d_step_body.inl -- the body of step_kernel, eval_stats_kernel and monte_carlo_kernel (acas2d_kernels.hpp, where the
-// modes and what each one implies are described), included inside all three.  It expects the including kernel's template
-// parameters T, C, G, PACKED, FAST, M (or constants of those names), the constants STATS and MC, and the kernel's arguments a0 .. a5,
+// acas2d_step_body.inl -- the body of step_kernel, eval_stats_kernel, monte_carlo_kernel and the latter two's disturbed
+// flavours (acas2d_kernels.hpp, where the modes and what each one implies are described), included inside all five.  It
+// expects the including kernel's template parameters T, C, G, PACKED, FAST, M (or constants of those names), the constants
+// STATS, MC and DIST, and the kernel's arguments a0 .. a5,
 // e_n_envs, tile_elems, p_arg, rp_arg, s_arg, io_arg, k0, k1, env_offset, N_arg, n_steps, pw.
     constexpr bool AUTO_RESET = M != Mode::Latch, ROLLOUT = rollout_mode(M);
     constexpr bool POLICY = policy_mode(M), SAMPLE = sample_mode(M);
@@ -206,6 +207,15 @@
         mc_gid_wave = (uint64_t)env_offset + (uint64_t)(e_wave32 - mc_kp * (uint32_t)pw.ep_stride);
         episode = mcw->mc_first;
     }
+    // DIST: the lane's index in the disturbance's counter -- the Monte Carlo kernel's RNG index, env_offset + the index
+    // within the policy's block (the evaluator's episode index), so K policies meet the same noise
+    uint64_t dist_lane = 0;
+    (void)dist_lane;
+    if constexpr (DIST) {
+        static_assert(EVAL && STATS && sizeof(T) == 4, "disturbances: the float32 stats evaluator and Monte Carlo kernel");
+        const uint32_t kp = __builtin_amdgcn_readfirstlane(e_wave32 / (uint32_t)pw.ep_stride);
+        dist_lane = (uint64_t)env_offset + (uint64_t)(e_wave32 - kp * (uint32_t)pw.ep_stride + (uint32_t)el);
+    }
     // STATS: the running statistics of the lane's episode (PolicyEvalStatsW)
     T st_min = T(1) / T(0), st_a_lat = T(0), st_dev = T(0), st_sum = T(0);
     int32_t st_min_step = 0, st_los = 0;
@@ -241,6 +251,29 @@
         T action = action_next;
         if constexpr (POLICY) {
             constexpr int DP = 5 + 3 * NS;                // compile-time obs width (packed shapes)
+            if constexpr (DIST) {
+                // sensor noise: slot n + 1 of (lane, episode, steps before this step) on traffic n's three entries, IN the
+                // wave's tile, by the lane that holds the aircraft in registers, fenced before the network reads the row
+                // (observe() rewrites the row below; EVAL never flushes it).  In the tile at the thread-per-env shapes too:
+                // perturbed in x[] below, the 5 + 3 N inputs are all live across the Philox chains where the network
+                // otherwise fetches them as it goes, and the N = 8 kernels need 293 and 306 VGPRs -- one wave per SIMD
+                // where their siblings (225, 252) keep two.  Through the tile they need 250 and 251.
+                const DisturbW* const dw = disturbance_args(pw);
+                if (dw->s_sep != 0.0f || dw->s_cpa != 0.0f || dw->s_closing != 0.0f) {      // (wave-uniform)
+                    const uint32_t d_ep = MC ? episode : dw->episode;
+#pragma unroll
+                    for (int k = 0; k < C; ++k) {
+                        const int n = j * C + k;
+                        float z0, z1, z2;
+                        disturbance_normals(dw->k0, dw->k1, dist_lane, d_ep, (uint32_t)steps, (uint32_t)(n + 1), z0, z1, z2);
+                        float* const e = reinterpret_cast<float*>(row) + 5 + 3 * n;
+                        e[0] = disturbed(e[0], dw->s_sep, z0, 0.0f, 1.0f);
+                        e[1] = disturbed(e[1], dw->s_cpa, z1, -1.0f, 1.0f);
+                        e[2] = disturbed(e[2], dw->s_closing, z2, -1.0f, 1.0f);
+                    }
+                    wave_lds_fence();                      // the disturbed rows are complete
+                }
+            }
             float x[G == 1 ? DP : 1];
             (void)x;
             if constexpr (G == 1) {
@@ -302,6 +335,14 @@
                     action = (T)(m != m ? m : fminf(fmaxf(m, -1.0f), 1.0f));
                 }
                 if constexpr (!EVAL) { if (active && j == 0) (static_cast<T*>(pw.actions_out) + e_wave + te)[el] = action; }
+                if constexpr (DIST) {                     // actuator noise: slot 0 on the clipped action, clipped again
+                    const DisturbW* const dw = disturbance_args(pw);
+                    if (dw->s_action != 0.0f) {           // (wave-uniform)
+                        float z0, z1, z2;
+                        disturbance_normals(dw->k0, dw->k1, dist_lane, MC ? episode : dw->episode, (uint32_t)steps, 0u, z0, z1, z2);
+                        action = (T)disturbed((float)action, dw->s_action, z0, -1.0f, 1.0f);
+                    }
+                }
             }
         } else {
             if (ROLLOUT && active && t + 1 < T_steps) action_next = io.actions[n_envs + el];

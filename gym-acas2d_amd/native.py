@@ -84,6 +84,14 @@ class CMonteCarlo(C.Structure):
          ("first_episode", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class CDisturbance(C.Structure):
+    """struct Acas2dDisturbance: the four standard deviations (normalised observation units / action units), the noise
+    seed and the evaluator's episode counter (acas2d_evaluate_policies_disturbed_*, acas2d_monte_carlo_disturbed_*,
+    include/acas2d.h)."""
+    _fields_ = [(n, C.c_float) for n in ("s_sep", "s_cpa", "s_closing", "s_action")] + \
+        [("noise_seed", C.c_uint64), ("noise_episode", C.c_uint32), ("_pad", C.c_uint32)]
+
+
 class CEncounterSearch(C.Structure):
     """struct Acas2dEncounterSearch: the proposal's tables, the per-candidate buffers, the stats entry's outputs, the log row,
     the archive and the settings of one generation of an encounter search (acas2d_encounter_*, include/acas2d.h)."""
@@ -146,7 +154,9 @@ EXPORTS = ("acas2d_abi_version", "acas2d_config_size", "acas2d_state_size", "aca
            "acas2d_evaluate_policies_stats_group_f32", "acas2d_monte_carlo_f32", "acas2d_monte_carlo_f64",
            "acas2d_monte_carlo_group_f32", "acas2d_monte_carlo_size", "acas2d_encounter_sample_f32",
            "acas2d_encounter_sample_f64", "acas2d_encounter_select_f32", "acas2d_encounter_select_f64", "acas2d_encounter_refit",
-           "acas2d_encounter_search_size")
+           "acas2d_encounter_search_size", "acas2d_disturbance_size", "acas2d_evaluate_policies_disturbed_f32",
+           "acas2d_evaluate_policies_disturbed_group_f32", "acas2d_monte_carlo_disturbed_f32",
+           "acas2d_monte_carlo_disturbed_group_f32", "acas2d_disturbance_draw_f32")
 
 
 class NativeLibraryError(RuntimeError):
@@ -227,6 +237,22 @@ def lib():
         f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.c_int64, C.POINTER(CPolicy), C.c_int32, C.c_int32,
                       C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(CMonteCarlo), C.c_void_p]
     L.acas2d_monte_carlo_size.restype = C.c_size_t
+    for name in ("acas2d_evaluate_policies_disturbed_f32", "acas2d_evaluate_policies_disturbed_group_f32"):
+        f = getattr(L, name)                               # the stats entries' list, the disturbance before stream
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.c_int64, C.POINTER(CPolicy), C.c_int32, C.c_int32,
+                      C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                      C.POINTER(CEvalStats), C.POINTER(CDisturbance), C.c_void_p]
+    for name in ("acas2d_monte_carlo_disturbed_f32", "acas2d_monte_carlo_disturbed_group_f32"):
+        f = getattr(L, name)                               # the campaign entries' list, the disturbance before stream
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.c_int64, C.POINTER(CPolicy), C.c_int32, C.c_int32,
+                      C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(CMonteCarlo),
+                      C.POINTER(CDisturbance), C.c_void_p]
+    L.acas2d_disturbance_draw_f32.restype = C.c_int
+    L.acas2d_disturbance_draw_f32.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_void_p, C.c_void_p]
+    L.acas2d_disturbance_size.restype = C.c_size_t
     for name in ("acas2d_encounter_sample_f32", "acas2d_encounter_sample_f64"):
         f = getattr(L, name)
         f.restype = C.c_int
@@ -301,7 +327,8 @@ def lib():
         raise NativeLibraryError("Acas2dGae layout mismatch: %d != %d" % (L.acas2d_gae_size(), C.sizeof(CGae)))
     for name, twin in (("member_episodes", CMemberEpisodes), ("population_exploit", CPopulationExploit),
                        ("ppo_guard", CPpoGuard), ("ppo_options", CPpoOptions), ("reward_norm", CRewardNorm),
-                       ("monte_carlo", CMonteCarlo), ("encounter_search", CEncounterSearch)):
+                       ("monte_carlo", CMonteCarlo), ("encounter_search", CEncounterSearch),
+                       ("disturbance", CDisturbance)):
         size = getattr(L, "acas2d_%s_size" % name)()
         if size != C.sizeof(twin):
             raise NativeLibraryError("%s layout mismatch: %d != %d" % (twin.__name__, size, C.sizeof(twin)))

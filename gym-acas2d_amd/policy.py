@@ -12,6 +12,7 @@ space without squashing: observation -> float32, two tanh layers of 64, linear a
 mean action clipped to [-1, 1].
 """
 import ctypes as C
+import dataclasses
 import io
 import os
 import zipfile
@@ -174,16 +175,95 @@ def stack_policies(policies, obs_dim, device):
     return [torch.stack(ts) for ts in zip(*ws)]                                  # [K][D][64], [K][64], ...
 
 
-def evaluate_policies_entry(dtype, group=False, safety=False):
-    """The name of the C entry point evaluate_policies_fused() calls for (dtype, group, safety)."""
+@dataclasses.dataclass(frozen=True, init=False)
+class Disturbance:
+    """White Gaussian sensor noise and actuator disturbance for the float32 evaluator and Monte Carlo campaign
+    (acas2d_evaluate_policies_disturbed_*, acas2d_monte_carlo_disturbed_*; records.disturb_observation() /
+    disturb_action() state the arithmetic).  Per step each traffic aircraft's normalised separation, closest-point-of-approach
+    distance and closing speed, as the actor reads them, get independent noise, and the actor's clipped action gets
+    `action` x a standard normal and is clipped again.
+
+    sep, cpa   standard deviations in pixels;  closing: in the units of v_closing.  They are divided by `config`'s d_sep_max,
+               d_cpa_max and v_closing_max in float64 and rounded to float32: the fields s_sep, s_cpa, s_closing (normalised
+               units) are what the kernels use and what two disturbances are compared by.
+    action     standard deviation in units of the action ([-1, 1]);  seed: the noise stream's 64-bit seed.
+    Disturbance.normalised(sep=, cpa=, closing=, action=, seed=) takes the three in normalised units directly."""
+    s_sep: float
+    s_cpa: float
+    s_closing: float
+    s_action: float
+    seed: int
+
+    def __init__(self, sep=0.0, cpa=0.0, closing=0.0, action=0.0, seed=0, config=None):
+        from .config import ACAS2DConfig
+        c = (config if config is not None else ACAS2DConfig()).to_c()
+        self._set(float(sep) / float(c.d_sep_max), float(cpa) / float(c.d_cpa_max), float(closing) / float(c.v_closing_max),
+                  action, seed)
+
+    def _set(self, s_sep, s_cpa, s_closing, s_action, seed):
+        for name, v in (("s_sep", s_sep), ("s_cpa", s_cpa), ("s_closing", s_closing), ("s_action", s_action)):
+            with np.errstate(over="ignore"):
+                object.__setattr__(self, name, float(np.float32(v)))         # the float32 the kernel reads
+        object.__setattr__(self, "seed", int(seed) & 0xFFFFFFFFFFFFFFFF)
+
+    @classmethod
+    def normalised(cls, sep=0.0, cpa=0.0, closing=0.0, action=0.0, seed=0):
+        d = object.__new__(cls)
+        d._set(sep, cpa, closing, action, seed)
+        return d
+
+    @property
+    def sigma(self):
+        """(s_sep, s_cpa, s_closing): records.disturb_observation()'s argument."""
+        return (self.s_sep, self.s_cpa, self.s_closing)
+
+    def is_zero(self):
+        return self.s_sep == 0 and self.s_cpa == 0 and self.s_closing == 0 and self.s_action == 0
+
+    def to_dict(self):
+        """Plain numbers (JSON, state_dict()); from_dict() gives an equal Disturbance back."""
+        return {"s_sep": self.s_sep, "s_cpa": self.s_cpa, "s_closing": self.s_closing, "s_action": self.s_action,
+                "seed": self.seed}
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls.normalised(d["s_sep"], d["s_cpa"], d["s_closing"], d["s_action"], d["seed"])
+
+    def to_c(self, noise_episode=0):
+        from . import native
+        return native.CDisturbance(self.s_sep, self.s_cpa, self.s_closing, self.s_action, self.seed, int(noise_episode), 0)
+
+
+def disturbance_draw(seed, first_lane, n_lanes, episode, first_step, n_steps, n_slots, device="cuda:0"):
+    """acas2d_disturbance_draw_f32: the standard normals the disturbed kernels draw, [n_steps, n_lanes, n_slots, 3] float32
+    (z_sep, z_cpa, z_closing; slot 0: the actuator's normal and two zeros; slot n + 1: traffic n) for lanes first_lane ..,
+    steps first_step .. (game.steps before the step) of episode counter `episode` -- computed by the device function the
+    kernels call, so a host replay that uses them reproduces a disturbed episode bit for bit."""
+    from . import native
+    dev = torch.device(device)
+    shape = (max(int(n_steps), 0), max(int(n_lanes), 0), max(int(n_slots), 0), 3)
+    out = torch.empty(shape, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        native.check(native.lib().acas2d_disturbance_draw_f32(int(seed) & 0xFFFFFFFFFFFFFFFF, int(first_lane), int(n_lanes),
+                                                              int(episode), int(first_step), int(n_steps), int(n_slots),
+                                                              out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream))
+    return out.cpu().numpy()
+
+
+def evaluate_policies_entry(dtype, group=False, safety=False, disturbed=False):
+    """The name of the C entry point evaluate_policies_fused() calls for (dtype, group, safety, disturbed)."""
     if group and dtype != torch.float32:
         raise ValueError("evaluate_policies_fused(group=True) is float32 only, got %s" % (dtype,))
+    if disturbed:
+        if dtype != torch.float32:
+            raise ValueError("evaluate_policies_fused(disturbance=...) is float32 only, got %s" % (dtype,))
+        return "acas2d_evaluate_policies_disturbed%s_f32" % ("_group" if group else "")
     return "acas2d_evaluate_policies%s%s_%s" % ("_stats" if safety else "", "_group" if group else "",
                                                 "f32" if dtype == torch.float32 else "f64")
 
 
 def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float64, device="cuda:0", config=None,
-                            max_steps=None, group=False, safety=False):
+                            max_steps=None, group=False, safety=False, disturbance=None, noise_episode=0, env_offset=0):
     """evaluate_policy_fused() for K policies on the SAME E episodes in ONE launch (acas2d_evaluate_policies_*):
     scoring the checkpoints of a run, or the policies of a seed sweep, together.  `policies`: `SB3ActorPolicy` /
     `ppo.ActorCritic` objects or paths of SB3 zips / .npz exports.  The episodes `own` [E,4] / `traffic` [E,N,4] /
@@ -196,12 +276,19 @@ def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float
     episode's step() calls (records.episode_safety(): row 0 of the reference's record lists is not among them) -- six
     more [K, E] keys in `dtype`'s precision: min_separation, min_separation_step (1-based step row of the minimum),
     los_steps (step rows inside the safe distance), max_abs_a_lat, max_abs_deviation and mean_abs_deviation (the sum of
-    |d_dev| over the steps - 1 rows; 0 where steps <= 1).  An unfinished episode has 0 in all of them."""
+    |d_dev| over the steps - 1 rows; 0 where steps <= 1).  An unfinished episode has 0 in all of them.
+    disturbance=Disturbance(...): the float32 launch under sensor noise and actuator disturbance
+    (acas2d_evaluate_policies_disturbed_*; it always computes the statistics, so the six keys are returned whatever
+    `safety` says).  Episode i draws the noise of lane env_offset + i and episode counter `noise_episode`: what lane i of a
+    MonteCarlo campaign with the same disturbance and env_offset met in its episode `noise_episode`."""
     from . import native
     from .vec_env import ACAS2DVecEnv
     if not policies:
         raise ValueError("evaluate_policies_fused needs at least one policy")
-    entry = evaluate_policies_entry(dtype, group, safety)
+    if disturbance is None:
+        entry = evaluate_policies_entry(dtype, group, safety)
+    else:
+        safety, entry = True, evaluate_policies_entry(dtype, group, True, disturbed=True)
     own, traffic = np.asarray(own), np.asarray(traffic)
     E, N = own.shape[0], traffic.shape[1]
     K, EP = len(policies), (own.shape[0] + 63) // 64 * 64
@@ -209,7 +296,7 @@ def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float
     idx = np.tile(idx, K)
     if goal is not None and np.asarray(goal).ndim == 2:
         goal = np.asarray(goal)[idx]
-    v = ACAS2DVecEnv(K * EP, N, device=device, dtype=dtype, auto_reset=True, config=config)
+    v = ACAS2DVecEnv(K * EP, N, device=device, dtype=dtype, auto_reset=True, config=config, env_offset=int(env_offset))
     D, dev = v.obs_dim, v.device
     v.set_state(own[idx], traffic[idx], goal, np.zeros(K * EP, np.int32), observe=True)
     keep = stack_policies(policies, D, dev)
@@ -226,6 +313,9 @@ def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float
         cstats = native.CEvalStats(st_f[0].data_ptr(), st_i[0].data_ptr(), st_i[1].data_ptr(), st_f[1].data_ptr(),
                                    st_f[2].data_ptr(), st_f[3].data_ptr())
         extra = (C.byref(cstats),)
+    if disturbance is not None:
+        cdist = disturbance.to_c(noise_episode)
+        extra += (C.byref(cdist),)
     with torch.cuda.device(dev):
         native.check(fn(C.byref(v._ccfg), C.byref(v._cstate), K * EP, C.byref(pw), K, E, v.outputs["obs"].data_ptr(), T,
                         v.seed_value, v.env_offset, N, outcome.data_ptr(), steps.data_ptr(), ret.data_ptr(),
@@ -242,10 +332,14 @@ def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float
     return res
 
 
-def monte_carlo_entry(dtype, group=False):
-    """The name of the C entry point MonteCarlo launches for (dtype, group)."""
+def monte_carlo_entry(dtype, group=False, disturbed=False):
+    """The name of the C entry point MonteCarlo launches for (dtype, group, disturbed)."""
     if group and dtype != torch.float32:
         raise ValueError("MonteCarlo(group=True) is float32 only, got %s" % (dtype,))
+    if disturbed:
+        if dtype != torch.float32:
+            raise ValueError("MonteCarlo(disturbance=...) is float32 only, got %s" % (dtype,))
+        return "acas2d_monte_carlo_disturbed%s_f32" % ("_group" if group else "")
     return "acas2d_monte_carlo%s_%s" % ("_group" if group else "", "f32" if dtype == torch.float32 else "f64")
 
 
@@ -263,16 +357,21 @@ class MonteCarlo:
     group      the group-cooperative float32 launch (n_traffic in {8, 16, 32, 64}), else thread-per-env
     n_bins, hist_max   the histogram of min_separation: n_bins bins of hist_max / n_bins, the last one also taking
                everything beyond (default hist_max: 4 x the config's safe distance)
+    disturbance  a Disturbance: the campaign under sensor noise and actuator disturbance (acas2d_monte_carlo_disturbed_*,
+               float32).  The noise of (lane, counter) is a function of the disturbance's seed, env_offset + lane, the counter
+               and the step alone, so the K policies meet the same noise on the same encounters, and encounter() names
+               everything a replay needs.
     """
 
     def __init__(self, policies, n_lanes, seed=13, dtype=torch.float32, group=False, config=None, n_traffic=1, n_bins=64,
-                 hist_max=None, device="cuda:0", env_offset=0):
+                 hist_max=None, device="cuda:0", env_offset=0, disturbance=None):
         from . import native, records
         from .config import ACAS2DConfig
         from .vec_env import ACAS2DVecEnv
         if not policies:
             raise ValueError("MonteCarlo needs at least one policy")
-        self.entry = monte_carlo_entry(dtype, group)
+        self.entry = monte_carlo_entry(dtype, group) if disturbance is None else monte_carlo_entry(dtype, group, disturbed=True)
+        self.disturbance = disturbance
         self.config = config if config is not None else ACAS2DConfig(n_traffic=n_traffic)
         self.n_lanes, self.n_policies, self.dtype, self.seed = int(n_lanes), len(policies), dtype, int(seed)
         if self.n_lanes < 1:
@@ -316,11 +415,15 @@ class MonteCarlo:
                                  self.n_bins, int(episodes), self.inv_bin_width, self.first_episode, 0)
             pw = nat.CPolicy(*[t.data_ptr() for t in self._weights], 64, 0)
             n_steps = max(int(episodes), 0) * self.config.max_steps
+            extra = ()
+            if self.disturbance is not None:
+                cdist = self.disturbance.to_c()
+                extra = (C_.byref(cdist),)
             if events:
                 events[0].record()
             nat.check(getattr(nat.lib(), self.entry)(
                 C_.byref(dst._ccfg), C_.byref(dst._cstate), dst.num_envs, C_.byref(pw), self.n_policies, self.n_lanes,
-                dst._obs.data_ptr(), n_steps, src.seed_value, src.env_offset, src.n_traffic, C_.byref(mc), dst._stream()))
+                dst._obs.data_ptr(), n_steps, src.seed_value, src.env_offset, src.n_traffic, C_.byref(mc), *extra, dst._stream()))
             if events:
                 events[1].record()
         self.first_episode += int(episodes)
@@ -349,7 +452,10 @@ class MonteCarlo:
         timeout counts and rates, the collision rate's Wilson 95 % interval, the loss-of-separation rate, mean steps, mean
         return and its standard error, the histogram and its edges; with baseline = k0 each policy's risk ratio against k0."""
         from . import records
-        return records.monte_carlo_summary(self.accumulators(), baseline=baseline, hist_max=self.hist_max)
+        out = records.monte_carlo_summary(self.accumulators(), baseline=baseline, hist_max=self.hist_max)
+        if self.disturbance is not None:
+            out["disturbance"] = self.disturbance.to_dict()
+        return out
 
     def worst(self, m=1):
         """Per policy the `m` lanes with the smallest lane_worst_sep as (lane, counter, min_sep), closest first (ties: the
@@ -363,7 +469,9 @@ class MonteCarlo:
 
     def encounter(self, lane, counter):
         """The encounter (lane, counter) as `own` [1, 4], `traffic` [1, N, 4], `goal` [1, 2] float64 arrays -- ready for
-        evaluate_policies_fused(), for ACAS2DVecEnv.set_state() of a latching env with record_trace=True, or for render."""
+        evaluate_policies_fused(), for ACAS2DVecEnv.set_state() of a latching env with record_trace=True, or for render.
+        A campaign with a disturbance returns a fourth item: the keyword arguments that make evaluate_policies_fused()
+        replay the DISTURBED episode (disturbance, noise_episode = counter, env_offset = the lane's RNG index)."""
         from .vec_env import ACAS2DVecEnv
         src = self._src
         if not 0 <= int(lane) < self.n_lanes:
@@ -371,17 +479,24 @@ class MonteCarlo:
         v = ACAS2DVecEnv(1, src.n_traffic, device=self.device, dtype=self.dtype, seed=self.seed, env_offset=src.env_offset + int(lane),
                          auto_reset=True, config=self.config, keep_terminal_obs=False, double_buffer=False)
         v.reset_to_episode(int(counter))
-        return read_state(v)
+        if self.disturbance is None:
+            return read_state(v)
+        return read_state(v) + ({"disturbance": self.disturbance, "noise_episode": int(counter),
+                                 "env_offset": src.env_offset + int(lane)},)
 
     def state_dict(self):
         """The accumulators and first_episode (numpy / ints): a campaign survives its process."""
         return {"accumulators": self.accumulators(), "first_episode": int(self.first_episode), "n_lanes": self.n_lanes,
-                "n_policies": self.n_policies, "n_bins": self.n_bins, "hist_max": self.hist_max, "seed": self.seed}
+                "n_policies": self.n_policies, "n_bins": self.n_bins, "hist_max": self.hist_max, "seed": self.seed,
+                **({} if self.disturbance is None else {"disturbance": self.disturbance.to_dict()})}
 
     def load_state_dict(self, sd):
         for k in ("n_lanes", "n_policies", "n_bins", "hist_max", "seed"):
             if sd[k] != getattr(self, k):
                 raise ValueError("state_dict of another campaign: %s = %r, this one has %r" % (k, sd[k], getattr(self, k)))
+        mine = None if self.disturbance is None else self.disturbance.to_dict()
+        if sd.get("disturbance") != mine:
+            raise ValueError("state_dict of another campaign: disturbance = %r, this one has %r" % (sd.get("disturbance"), mine))
         for k, t in self._acc.items():
             a = np.ascontiguousarray(sd["accumulators"][k])
             t.copy_(torch.as_tensor(a.view(np.int32) if a.dtype == np.uint32 else a))

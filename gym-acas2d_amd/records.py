@@ -388,3 +388,81 @@ def search_estimate(history_rows, n_candidates, first_generation=0):
     return {"p_generation": p_g, "se_generation": se_g, "ess": ess, "n_event": h[..., 5], "generations": n,
             "p": p_g[sel].mean(0) if n else np.full(p_g.shape[1:], np.nan),
             "se": np.sqrt((se_g[sel] ** 2).sum(0)) / n if n else np.full(p_g.shape[1:], np.nan)}
+
+
+# ---- sensor noise and actuator disturbance (acas2d_evaluate_policies_disturbed_*, acas2d_monte_carlo_disturbed_*) ----------
+DISTURBANCE_TAG = 0x64697374                   # "dist": xor-ed into the key's high word
+DISTURBANCE_SLOT_SHIFT = 20                    # counter word 3 = step | slot << 20
+DISTURBANCE_PHILOX_ROUNDS = 7                  # the reset's generator (csrc/acas2d_kernels.hpp, philox4x32)
+OBSERVATION_BOX = ((0.0, 1.0), (-1.0, 1.0), (-1.0, 1.0))      # separation, d_cpa, v_closing (environment.py:19-20)
+
+
+def philox4x32(counter, key, rounds=DISTURBANCE_PHILOX_ROUNDS):
+    """Philox4x32 on arrays: counter [..., 4] and key [..., 2] (or a pair of ints) of 32-bit words -> words [..., 4] uint32."""
+    m32 = np.uint64(0xFFFFFFFF)
+    c = [np.asarray(counter)[..., i].astype(np.uint64) & m32 for i in range(4)]
+    k = [np.asarray(key)[..., i].astype(np.uint64) & m32 for i in range(2)]
+    for _ in range(int(rounds)):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & m32]
+        k = [(k[0] + np.uint64(0x9E3779B9)) & m32, (k[1] + np.uint64(0xBB67AE85)) & m32]
+    return np.stack(np.broadcast_arrays(*c), axis=-1).astype(np.uint32)
+
+
+def disturbance_words(seed, lane, episode, step, slot):
+    """The Philox block of the disturbance at (lane, episode, step, slot), broadcast over array arguments -> [..., 4] uint32.
+    Counter (lane lo, lane hi, episode, step | slot << 20), key (seed lo, seed hi ^ DISTURBANCE_TAG).  lane: the RNG index
+    env_offset + index within the policy's block; step: game.steps before the step's increment; slot 0 the actuator,
+    slot n + 1 traffic n."""
+    lane, episode, step, slot = np.broadcast_arrays(*[np.asarray(a, np.uint64) for a in (lane, episode, step, slot)])
+    if (step >= (1 << DISTURBANCE_SLOT_SHIFT)).any() or (slot > 64).any() or (episode >= (1 << 32)).any():
+        raise ValueError("disturbance_words: step < 2^20, slot <= 64 and episode < 2^32 are required")
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    ctr = np.stack([lane & np.uint64(0xFFFFFFFF), lane >> np.uint64(32), episode,
+                    step | (slot << np.uint64(DISTURBANCE_SLOT_SHIFT))], axis=-1)
+    key = np.array([seed & 0xFFFFFFFF, (seed >> 32) ^ DISTURBANCE_TAG], np.uint64)
+    return philox4x32(ctr, key)
+
+
+def disturbance_normals(words):
+    """The three standard normals (z_sep, z_cpa, z_closing) of blocks [..., 4] in float64: u_i = ((w_i >> 8) + 0.5) / 2^24 (the
+    float32 uniforms of the kernels, exact in float64), r(u) = sqrt(-2 ln u), z_sep = r(u1) cos(2 pi u2), z_cpa = r(u1) sin(2 pi
+    u2), z_closing = r(u3) cos(2 pi u4).  The actuator slot reads z_sep.  The kernels evaluate the same formulas with the
+    hardware's approximate float32 log, sqrt, sin and cos: acas2d_disturbance_draw_f32 gives their values."""
+    w = np.asarray(words, np.uint32)
+    u = ((w >> np.uint32(8)).astype(np.float64) + 0.5) / 16777216.0
+    r1, r3 = np.sqrt(-2.0 * np.log(u[..., 0])), np.sqrt(-2.0 * np.log(u[..., 2]))
+    a2, a4 = 2.0 * np.pi * u[..., 1], 2.0 * np.pi * u[..., 3]
+    return np.stack([r1 * np.cos(a2), r1 * np.sin(a2), r3 * np.cos(a4)], axis=-1)
+
+
+def _disturbed(x, s, z, lo, hi):
+    """x + s z in float32 with both roundings, then the box by comparisons (a NaN stays, -0 stays); s == 0: x untouched."""
+    x = np.asarray(x, np.float32)
+    s = np.float32(s)
+    if s == 0:
+        return x.copy()
+    with np.errstate(invalid="ignore", over="ignore"):
+        y = (x + (s * np.asarray(z, np.float32)).astype(np.float32)).astype(np.float32)
+        return np.where(y < np.float32(lo), np.float32(lo), np.where(y > np.float32(hi), np.float32(hi), y)).astype(np.float32)
+
+
+def disturb_observation(obs, sigma, normals):
+    """The observation the actor reads: obs [..., 5 + 3 N] float32, sigma = (s_sep, s_cpa, s_closing) in normalised units,
+    normals [..., N, 3] (slot n + 1's z_sep, z_cpa, z_closing, e.g. from acas2d_disturbance_draw_f32).  Entry 5 + 3 n + c
+    becomes x + s_c z in float32 -- the product and the sum each rounded -- and is held to OBSERVATION_BOX[c]; a NaN stays
+    a NaN; a channel with s_c == 0 is neither added to nor clamped; the five own-ship entries are never touched."""
+    out = np.array(obs, np.float32, copy=True)
+    z = np.asarray(normals, np.float32)
+    n = (out.shape[-1] - 5) // 3
+    if z.shape[-2:] != (n, 3):
+        raise ValueError("disturb_observation: normals %s for %d traffic aircraft" % (z.shape, n))
+    for c, (lo, hi) in enumerate(OBSERVATION_BOX):
+        out[..., 5 + c::3] = _disturbed(out[..., 5 + c::3], sigma[c], z[..., c], lo, hi)
+    return out
+
+
+def disturb_action(action, s_action, normal):
+    """The action the aircraft flies: the actor's clipped action + s_action z in float32 (two roundings), held to [-1, 1]
+    again; a NaN stays a NaN; s_action == 0 leaves it untouched."""
+    return _disturbed(action, s_action, normal, -1.0, 1.0)

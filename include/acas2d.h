@@ -450,6 +450,67 @@ int acas2d_monte_carlo_group_f32(const Acas2dConfig *cfg, const Acas2dState *sta
                                  const Acas2dMonteCarlo *mc, void *stream);
 
 /*
+ * acas2d_evaluate_policies_disturbed_f32 / _group_f32, acas2d_monte_carlo_disturbed_f32 / _group_f32,
+ * acas2d_disturbance_draw_f32: the evaluation with statistics and the Monte Carlo campaign above under sensor noise and
+ * actuator disturbance.  Additive to ABI 7, float32 only.  The arguments of acas2d_evaluate_policies_stats_* /
+ * acas2d_monte_carlo_* with `disturbance` in front of `stream`; the same work shapes (thread-per-env n_traffic in
+ * {1, 2, 3, 4, 8}, group {8, 16, 32, 64}) and the same rejections in the same words.  With all four standard deviations 0
+ * the results equal the undisturbed entries' bit for bit.
+ *   Per step, BEFORE the actor: entry 5 + 3 n + c of the observation the actor reads (traffic n; c = 0 normalised
+ *   separation, 1 closest-point-of-approach distance, 2 closing speed) becomes  x + s_c * z  -- a float32 multiply and a
+ *   float32 add, each rounded -- and is then held to the observation box by comparisons (y < lo ? lo : y > hi ? hi : y;
+ *   [0, 1] for c = 0, [-1, 1] else; a NaN stays a NaN).  The five own-ship entries are never touched.  AFTER the actor:
+ *   the clipped action becomes  a + s_action * z, held to [-1, 1] the same way; the move, a_lat and max_a_lat see that
+ *   action.  A channel whose s is exactly 0 is neither added to nor clamped.  Only what the actor reads is disturbed:
+ *   rewards, outcomes and statistics follow from the true state.
+ *   The draws: one Philox4x32 block (the reset's generator and rounds) per (lane, episode, step, slot), counter
+ *   (lane lo, lane hi, episode, step | slot << 20), key (noise_seed lo, noise_seed hi ^ 0x64697374).  lane = env_offset +
+ *   the index within the policy's block (the RNG index of acas2d_monte_carlo_*: K policies meet the same noise); episode =
+ *   the lane's current counter in a campaign, noise_episode for every episode of an evaluation; step = game.steps BEFORE
+ *   the step's increment; slot 0 the actuator, slot n + 1 traffic n.  With u_i = ((w_i >> 8) + 0.5) / 2^24 and
+ *   r(u) = sqrt(-2 ln u): z_sep = r(u1) cos(2 pi u2), z_cpa = r(u1) sin(2 pi u2), z_closing = r(u3) cos(2 pi u4); the
+ *   actuator takes r(u1) cos(2 pi u2).  Log, sqrt, sin and cos are the hardware's approximations.  The noise depends on
+ *   nothing else: not on K, not on how a campaign is cut into launches, not on the work shape.
+ * acas2d_disturbance_draw_f32 writes those normals for lanes first_lane .. + n_lanes - 1, steps first_step .. + n_steps - 1
+ * and slots 0 .. n_slots - 1 of one episode as float[n_steps][n_lanes][n_slots][3] = (z_sep, z_cpa, z_closing); slot 0
+ * holds the actuator's normal and two zeros.  It calls the device function the two kernels call.
+ * Rejected with ACAS2D_EINVAL before anything is launched: everything the undisturbed sibling rejects, a NULL disturbance,
+ * a standard deviation that is negative or not finite, max_steps + 1 >= 2^20 (the step field); draw: a NULL out, a count
+ * < 1, a negative first_lane or first_step, first_step + n_steps > 2^20, n_slots > 65.
+ */
+typedef struct Acas2dDisturbance {
+    float s_sep, s_cpa, s_closing;     /* standard deviations in units of the NORMALISED observation */
+    float s_action;                    /* ... and of the action */
+    uint64_t noise_seed;
+    uint32_t noise_episode;            /* evaluation: the episode counter of every episode; ignored by the campaign */
+    uint32_t _pad;
+} Acas2dDisturbance;
+size_t acas2d_disturbance_size(void);  /* sizeof(Acas2dDisturbance), for bindings */
+int acas2d_evaluate_policies_disturbed_f32(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                                           const Acas2dPolicy *policies, int32_t n_policies, int32_t n_episodes,
+                                           const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
+                                           int32_t n_traffic, uint8_t *outcome, int32_t *steps, void *total_reward,
+                                           const Acas2dEvalStats *stats, const Acas2dDisturbance *disturbance,
+                                           void *stream);
+int acas2d_evaluate_policies_disturbed_group_f32(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                                                 const Acas2dPolicy *policies, int32_t n_policies, int32_t n_episodes,
+                                                 const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
+                                                 int32_t n_traffic, uint8_t *outcome, int32_t *steps, void *total_reward,
+                                                 const Acas2dEvalStats *stats, const Acas2dDisturbance *disturbance,
+                                                 void *stream);
+int acas2d_monte_carlo_disturbed_f32(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                                     const Acas2dPolicy *policies, int32_t n_policies, int32_t n_lanes, const void *obs_in,
+                                     int32_t n_steps, uint64_t seed, int64_t env_offset, int32_t n_traffic,
+                                     const Acas2dMonteCarlo *mc, const Acas2dDisturbance *disturbance, void *stream);
+int acas2d_monte_carlo_disturbed_group_f32(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                                           const Acas2dPolicy *policies, int32_t n_policies, int32_t n_lanes,
+                                           const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
+                                           int32_t n_traffic, const Acas2dMonteCarlo *mc,
+                                           const Acas2dDisturbance *disturbance, void *stream);
+int acas2d_disturbance_draw_f32(uint64_t noise_seed, int64_t first_lane, int32_t n_lanes, uint32_t episode,
+                                int32_t first_step, int32_t n_steps, int32_t n_slots, float *out, void *stream);
+
+/*
  * acas2d_encounter_sample_f32 / _f64, acas2d_encounter_select_f32 / _f64, acas2d_encounter_refit: a cross-entropy search
  * over encounters with importance sampling, around the unchanged acas2d_evaluate_policies_stats_* -- per generation:
  * sample, acas2d_reset_* with do_init = 0 (the first observation), the stats entry, select, refit, with no host decision

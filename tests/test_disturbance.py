@@ -1,0 +1,366 @@
+"""Sensor noise and actuator disturbance on the GPU (acas2d_evaluate_policies_disturbed_*, acas2d_monte_carlo_disturbed_*,
+acas2d_disturbance_draw_f32; policy.Disturbance):
+
+  1  the draws against the float64 specification of records.disturbance_normals(), and their first two moments;
+  2  all four standard deviations 0: the undisturbed entries' bits;
+  3  the disturbed evaluator against a host loop with no new arithmetic -- per step the observation of a latching env,
+     records.disturb_observation() with the normals of the draw entry, the project's in-kernel network through a one-step
+     rollout_policy() on a scratch env, records.disturb_action(), the latching step with record_trace=True, and
+     records.episode_safety() on the trace;
+  4  the disturbed campaign against reset_to_episode(c) + that evaluator folded by records.monte_carlo_reduce(), and the
+     properties a campaign is used for;
+  5  a network of zeros ignores its input: sensor noise alone leaves the all-zero policy's row as it is;
+  6  refusals.
+
+70 episodes / lanes: one full wave and a partial one thread per env, 18 waves at the (4, 16) group shape."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import eval_stats_support as ES
+import monte_carlo_support as MS
+
+pytestmark = pytest.mark.gpu
+DEV = ES.DEV
+F32 = torch.float32
+# (n_traffic, group)
+EVAL_SHAPES = ((1, False), (3, False), (8, False), (16, True), (64, True))
+ZERO_SHAPES = EVAL_SHAPES[:4]
+CAMPAIGN_SHAPES = [MS.Shape(F32, True, n, grp, max_steps) for max_steps in (1000, 150) for n, grp in ((1, False), (8, False), (16, True))]
+NOISE_EPISODE = 5
+
+# acas2d_disturbance_draw_f32 against records.disturbance_normals(): the largest absolute difference MEASURED on an MI355X
+# over the sample of test_draws_against_the_specification (printed by it), and the bound: four times that,
+# rounded up to one digit.  The difference is the hardware's approximate float32 log, sqrt, sin and cos and the float32
+# products against float64 libm; the factor covers inputs the sample does not hold.
+DRAW_MEASURED = 1.01e-5          # 1.009757e-05, at a cosine near its zero (|z| 0.0028)
+DRAW_TOL = 5e-5
+
+
+def shape_id(s):
+    return "N%d%s" % (s[0], "-group" if s[1] else "")
+
+
+EVAL_IDS = [shape_id(s) for s in EVAL_SHAPES]
+CAMPAIGN = pytest.mark.parametrize("s", CAMPAIGN_SHAPES, ids=[MS.shape_id(s) for s in CAMPAIGN_SHAPES])
+
+
+@pytest.fixture(scope="module")
+def g():
+    import gym_acas2d_amd as g
+    return g
+
+
+def the_disturbance(g):
+    return g.policy.Disturbance.normalised(sep=0.05, cpa=0.1, closing=0.1, action=0.3, seed=7)
+
+
+# ---- 1: the draws -----------------------------------------------------------------------------------------------------------------
+def test_draws_against_the_specification(g):
+    worst = 0.0
+    for first_lane in (0, (1 << 32) - 3):
+        for episode in (0, 5):
+            got = g.policy.disturbance_draw(7, first_lane, 70, episode, 0, 121, 9, device=DEV)
+            assert got.shape == (121, 70, 9, 3) and got.dtype == np.float32
+            lanes = first_lane + np.arange(70, dtype=np.uint64)
+            words = g.records.disturbance_words(7, lanes[None, :, None], episode, np.arange(121)[:, None, None],
+                                                np.arange(9)[None, None, :])
+            want = g.records.disturbance_normals(words)
+            want[:, :, 0, 1:] = 0.0                                    # the actuator slot: its normal and two zeros
+            assert (got[:, :, 0, 1:] == 0.0).all()
+            worst = max(worst, float(np.abs(got.astype(np.float64) - want).max()))
+    print("\nacas2d_disturbance_draw_f32 against the float64 specification: largest absolute difference %.3e over %d normals "
+          "(bound %r)" % (worst, 4 * 121 * 70 * (8 * 3 + 1), DRAW_TOL))
+    assert worst <= DRAW_TOL
+
+
+def test_draws_are_standard_normal(g):
+    """2^20 draws per channel (1 024 lanes x 1 024 steps): |mean| < 5 / sqrt(n), |variance - 1| < 5 sqrt(2 / n)."""
+    z = g.policy.disturbance_draw(11, 0, 1024, 0, 0, 1024, 2, device=DEV).astype(np.float64)
+    n = 1 << 20
+    for name, x in (("actuator", z[:, :, 0, 0]), ("sep", z[:, :, 1, 0]), ("cpa", z[:, :, 1, 1]), ("closing", z[:, :, 1, 2])):
+        assert x.size == n and np.isfinite(x).all(), name
+        assert abs(x.mean()) < 5 / math.sqrt(n), (name, x.mean())
+        assert abs(x.var() - 1.0) < 5 * math.sqrt(2 / n), (name, x.var())
+
+
+def test_draws_do_not_depend_on_how_they_are_asked_for(g):
+    """A block is a function of (seed, lane, episode, step, slot): windows of lanes, steps and slots cut the same values."""
+    whole = g.policy.disturbance_draw(7, 0, 70, 5, 0, 40, 9, device=DEV)
+    part = g.policy.disturbance_draw(7, 64, 6, 5, 30, 10, 3, device=DEV)
+    assert ES.bits_equal(part, whole[30:40, 64:70, :3])
+    assert not ES.bits_equal(whole, g.policy.disturbance_draw(8, 0, 70, 5, 0, 40, 9, device=DEV))
+    assert not ES.bits_equal(whole, g.policy.disturbance_draw(7, 0, 70, 4, 0, 40, 9, device=DEV))
+
+
+# ---- 2: zero is identity ------------------------------------------------------------------------------------------------------------
+def fused(g, N, group, **kw):
+    cfg = ES.config(g, N)
+    eps = ES.episodes(cfg)
+    return g.evaluate_policies_fused(ES.two_policies(g, N), eps.own, eps.trf, eps.goal, dtype=F32, device=DEV, config=cfg,
+                                     group=group, safety=True, **kw)
+
+
+@pytest.mark.parametrize("shape", ZERO_SHAPES, ids=EVAL_IDS[:4])
+def test_zero_disturbance_is_the_stats_evaluator(g, shape):
+    N, group = shape
+    plain = fused(g, N, group)
+    zero = fused(g, N, group, disturbance=g.policy.Disturbance(seed=99), noise_episode=3)
+    assert set(zero) == set(plain) and len(plain) >= 11
+    for k in plain:
+        assert ES.bits_equal(zero[k], plain[k]), k
+    assert (plain["outcome"] != 0).all()
+
+
+@pytest.mark.parametrize("shape", ZERO_SHAPES, ids=EVAL_IDS[:4])
+def test_zero_disturbance_is_the_undisturbed_campaign(g, shape):
+    s = MS.Shape(F32, True, shape[0], shape[1], 150)
+    plain = MS.campaign(g, s).run(MS.EPISODES).accumulators()
+    zero = MS.campaign(g, s, disturbance=g.policy.Disturbance(seed=99)).run(MS.EPISODES).accumulators()
+    assert not MS.mismatches(g, zero, plain)
+    assert plain["outcome_count"].sum(1).tolist() == [MS.LANES * MS.EPISODES] * 3
+
+
+# ---- 3: the evaluator against a host loop -------------------------------------------------------------------------------------------
+def host_loop(g, cfg, eps, policy, dist, noise_episode, group):
+    """One policy's reference rows [E] by the per-step path: (outcome, steps, total_reward, stats dict)."""
+    E, N = ES.E, cfg.n_traffic
+    n_steps = cfg.max_steps + 1
+    zero = np.zeros(E, np.int32)
+    # the normals of every step an episode can reach, from the draw entry: [step, lane, slot, 3]
+    normals = g.policy.disturbance_draw(dist.seed, 0, E, noise_episode, 0, cfg.max_steps + 2, N + 1, device=DEV)
+    r = g.ACAS2DVecEnv(E, N, device=DEV, dtype=F32, auto_reset=False, record_trace=True, config=cfg)
+    r.set_state(eps.own, eps.trf, eps.goal, zero, observe=True)
+    scratch = g.ACAS2DVecEnv(E, N, device=DEV, dtype=F32, auto_reset=True, config=cfg)
+    scratch.reset()
+    cols = [r.trace.clone()]
+    active = np.ones(E, bool)
+    outcome, steps, ret, t0 = np.zeros(E, np.uint8), np.zeros(E, np.int32), np.zeros(E, np.float32), np.zeros(E, np.int64)
+    lane = np.arange(E)
+    for t in range(n_steps):
+        obs = r.outputs["obs"].cpu().numpy()
+        at = r.steps.cpu().numpy()                                     # game.steps before this step
+        z = normals[np.minimum(at, normals.shape[0] - 1), lane]       # [E, N + 1, 3] (latched envs: unused)
+        noisy = g.records.disturb_observation(obs, dist.sigma, z[:, 1:])
+        scratch.outputs["obs"].copy_(torch.as_tensor(noisy, device=DEV))
+        action = scratch.rollout_policy(policy, 1, group=group)["actions"][0].cpu().numpy()
+        flown = g.records.disturb_action(action, dist.s_action, z[:, 0, 0])
+        _, _, done, infos = r.step(torch.as_tensor(flown, device=DEV))
+        cols.append(r.trace.clone())
+        fin = active & done.cpu().numpy()
+        outcome[fin] = infos.outcome.cpu().numpy()[fin]
+        steps[fin] = r.steps.cpu().numpy()[fin]
+        ret[fin] = r.total_reward.cpu().numpy()[fin]
+        t0[fin] = t
+        active &= ~fin
+        if not active.any():
+            break
+    trace = torch.stack(cols).cpu().numpy()
+    names = list(g.vec_env.TRACE_COLUMNS)
+    c_sep, c_lat, c_dev = names.index("d_sep"), names.index("a_lat"), names.index("d_dev")
+    keys = ("min_sep", "min_sep_step", "los_steps", "max_a_lat", "max_dev", "sum_dev")
+    stats = {k: np.zeros(E, np.int32 if k in ("min_sep_step", "los_steps") else np.float32) for k in keys}
+    summary = {k: np.zeros(E, np.int32 if k in ("min_separation_step", "los_steps") else np.float32) for k in g.records.SAFETY_KEYS}
+    for i in np.nonzero(~active)[0]:
+        n = t0[i] + 2
+        assert n == steps[i]
+        one = g.records.episode_safety(trace[:n, i, c_sep], trace[:n, i, c_lat], trace[:n, i, c_dev], cfg.safe_distance, np.float32)
+        for k in keys:
+            stats[k][i] = one[k]
+        for k, val in g.records.safety_summary(one, int(steps[i])).items():
+            summary[k][i] = val
+    return outcome, steps, ret, stats, summary
+
+
+_LOOP = {}
+
+
+def loop_reference(g, N, group):
+    if (N, group) not in _LOOP:
+        cfg = ES.config(g, N)
+        eps = ES.episodes(cfg)
+        rows = [host_loop(g, cfg, eps, pol, the_disturbance(g), NOISE_EPISODE, group) for pol in ES.two_policies(g, N)]
+        _LOOP[N, group] = rows
+    return _LOOP[N, group]
+
+
+@pytest.mark.parametrize("shape", EVAL_SHAPES, ids=EVAL_IDS)
+def test_disturbed_evaluator_equals_the_host_loop(g, shape):
+    N, group = shape
+    rows = loop_reference(g, N, group)
+    # teeth, on the reference alone: the disturbance moves the hardest manoeuvre of at least half of the episodes
+    plain = ES.reference(g, F32, True, N)
+    for k, row in enumerate(rows):
+        assert (row[0] != 0).all(), "an episode of the reference did not finish"
+        moved = int((ES.bits(row[3]["max_a_lat"]) != ES.bits(plain.stats["max_a_lat"][k])).sum())
+        assert 2 * moved >= ES.E, (k, moved)
+    got = fused(g, N, group, disturbance=the_disturbance(g), noise_episode=NOISE_EPISODE)
+    for k, (outcome, steps, ret, stats, summary) in enumerate(rows):
+        assert np.array_equal(got["outcome"][k], outcome) and np.array_equal(got["steps"][k], steps), k
+        assert ES.bits_equal(got["total_reward"][k].astype(np.float32), ret), k
+        for key in g.records.SAFETY_KEYS:
+            assert ES.bits_equal(got[key][k], summary[key]), (k, key)
+    # the counter and the seed are part of the noise
+    other = fused(g, N, group, disturbance=the_disturbance(g), noise_episode=NOISE_EPISODE + 1)
+    assert not ES.bits_equal(other["max_abs_a_lat"], got["max_abs_a_lat"])
+
+
+# ---- 4: the campaign against the evaluator ---------------------------------------------------------------------------------------------
+_COUNTERS, _RAN = {}, {}
+
+
+def per_counter(g, s):
+    """The disturbed evaluator's result dicts of [a, b, zero] for counters 0 .. EPISODES - 1 at shape s."""
+    if s not in _COUNTERS:
+        cfg = MS.config(g, s)
+        v = g.ACAS2DVecEnv(MS.LANES, s.N, device=DEV, dtype=F32, seed=MS.SEED, config=cfg)
+        out = []
+        for c in range(MS.EPISODES):
+            v.reset_to_episode(c)
+            own, trf, goal = g.policy.read_state(v)
+            res = g.evaluate_policies_fused(MS.policies(g, s), own, trf, goal, dtype=F32, device=DEV, config=cfg, group=s.group,
+                                            safety=True, disturbance=the_disturbance(g), noise_episode=c)
+            for a in res.values():
+                a.setflags(write=False)
+            out.append(res)
+        _COUNTERS[s] = out
+    return _COUNTERS[s]
+
+
+def reference(g, s, rows=None):
+    res = per_counter(g, s)
+    if rows is not None:
+        res = [{k: v[list(rows)] for k, v in r.items() if np.ndim(v) == 2} for r in res]
+    return g.records.monte_carlo_reduce(res, MS.N_BINS, MS.inv_bin_width(g, s), np.float32)
+
+
+def disturbed(g, s, **kw):
+    return MS.campaign(g, s, disturbance=the_disturbance(g), **kw)
+
+
+def ran(g, s):
+    if s not in _RAN:
+        acc = disturbed(g, s).run(MS.EPISODES).accumulators()
+        for a in acc.values():
+            a.setflags(write=False)
+        _RAN[s] = acc
+    return _RAN[s]
+
+
+def same(g, got, want):
+    bad = MS.mismatches(g, got, want)
+    assert not bad, {k: (np.asarray(got[k]).ravel()[:6], np.asarray(want[k]).ravel()[:6]) for k in bad}
+
+
+@CAMPAIGN
+def test_disturbed_campaign_equals_the_disturbed_evaluator(g, s):
+    ref = reference(g, s)
+    assert ref["outcome_count"].sum(1).tolist() == [MS.LANES * MS.EPISODES] * 3
+    same(g, ran(g, s), ref)
+    assert MS.mismatches(g, ran(g, s), MS.reference(g, s))           # (and it is not the undisturbed campaign)
+
+
+def test_the_campaign_reference_is_not_vacuous(g):
+    seen = np.zeros(4, np.int64)
+    for s in CAMPAIGN_SHAPES:
+        ref = reference(g, s)
+        assert ref["outcome_count"].sum(1).tolist() == ref["sep_hist"].sum(1).tolist() == [MS.LANES * MS.EPISODES] * 3, MS.shape_id(s)
+        assert ref["outcome_count"][:, 0].tolist() == [0, 0, 0]
+        assert np.isfinite(ref["lane_worst_sep"]).all()
+        seen += ref["outcome_count"].sum(0)
+        if s.max_steps == 150:
+            assert ref["outcome_count"][:, 3].sum() > 0, MS.shape_id(s)
+    assert (seen[1:] > 0).all(), seen                                  # goals, collisions and timeouts
+
+
+@CAMPAIGN
+def test_disturbed_chaining(g, s):
+    same(g, disturbed(g, s).run(2).run(1).accumulators(), ran(g, s))
+    same(g, disturbed(g, s).run(MS.EPISODES, per_launch=1).accumulators(), ran(g, s))
+
+
+@CAMPAIGN
+def test_disturbed_campaign_survives_a_state_dict(g, s):
+    first = disturbed(g, s).run(2)
+    sd = first.state_dict()
+    assert sd["first_episode"] == 2 and sd["disturbance"] == the_disturbance(g).to_dict()
+    second = disturbed(g, s).load_state_dict(sd).run(1)
+    assert second.first_episode == 3
+    same(g, second.accumulators(), ran(g, s))
+    with pytest.raises(ValueError, match="disturbance"):
+        MS.campaign(g, s).load_state_dict(sd)
+    with pytest.raises(ValueError, match="disturbance"):
+        MS.campaign(g, s, disturbance=g.policy.Disturbance.normalised(sep=0.05, cpa=0.1, closing=0.1, action=0.3, seed=8)).load_state_dict(sd)
+    with pytest.raises(ValueError, match="disturbance"):
+        disturbed(g, s).load_state_dict(MS.campaign(g, s).state_dict())
+
+
+@CAMPAIGN
+def test_disturbed_common_random_numbers(g, s):
+    """Policy b alone meets the encounters AND the noise it meets among [a, b, zero]."""
+    b = MS.policies(g, s)[1]
+    alone = disturbed(g, s, pols=[b]).run(MS.EPISODES).accumulators()
+    same(g, alone, {k: v[[1]] for k, v in ran(g, s).items()})
+
+
+@CAMPAIGN
+def test_disturbed_encounter_closes_the_loop(g, s):
+    mc = disturbed(g, s).run(MS.EPISODES)
+    acc = ran(g, s)
+    assert mc.summary()["disturbance"] == the_disturbance(g).to_dict()
+    for k, top in enumerate(mc.worst(1)):
+        (lane, counter, sep), = top
+        assert sep == acc["lane_worst_sep"][k].min() and counter == acc["lane_worst_episode"][k, lane]
+        own, trf, goal, replay = mc.encounter(lane, counter)
+        assert replay == {"disturbance": the_disturbance(g), "noise_episode": counter, "env_offset": lane}
+        res = g.evaluate_policies_fused(MS.policies(g, s), own, trf, goal, dtype=F32, device=DEV, config=MS.config(g, s),
+                                        group=s.group, safety=True, **replay)
+        assert ES.bits_equal(res["min_separation"][k, :1], np.asarray([sep], np.float32))
+
+
+# ---- 5: a network of zeros ignores its input -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("s", CAMPAIGN_SHAPES[:3], ids=[MS.shape_id(s) for s in CAMPAIGN_SHAPES[:3]])
+def test_sensor_noise_alone_leaves_the_zero_policy_alone(g, s):
+    sensors = g.policy.Disturbance.normalised(sep=0.3, cpa=0.5, closing=0.2, action=0.0, seed=21)
+    got = MS.campaign(g, s, disturbance=sensors).run(MS.EPISODES).accumulators()
+    plain = MS.reference(g, s)
+    same(g, {k: v[[2]] for k, v in got.items()}, {k: v[[2]] for k, v in plain.items()})
+    assert MS.mismatches(g, {k: v[[0]] for k, v in got.items()}, {k: v[[0]] for k, v in plain.items()})   # a real network does see it
+
+
+# ---- 6: refusals -------------------------------------------------------------------------------------------------------------------------
+def test_refusals(g):
+    D = g.policy.Disturbance
+    s = MS.Shape(F32, True, 1, False, 1000)
+    for bad in (D.normalised(sep=-0.1), D.normalised(cpa=float("nan")), D.normalised(closing=float("inf")), D.normalised(action=-1.0)):
+        mc = MS.campaign(g, s, disturbance=bad)
+        with pytest.raises(RuntimeError, match=r"acas2d_monte_carlo_disturbed: s_sep = .* \(each finite and at least 0\)"):
+            mc.run(1)
+        assert mc.first_episode == 0 and mc.accumulators()["outcome_count"].sum() == 0      # a refusal leaves the campaign alone
+        with pytest.raises(RuntimeError, match=r"acas2d_evaluate_policies_disturbed: s_sep = .* \(each finite and at least 0\)"):
+            fused(g, 1, False, disturbance=bad)
+    with pytest.raises(RuntimeError, match=r"acas2d_monte_carlo_disturbed: episodes_per_lane = 0 \(at least 1\)"):
+        disturbed(g, s).run(0)
+    long = g.ACAS2DConfig(n_traffic=1, max_steps=(1 << 20) - 1)
+    with pytest.raises(RuntimeError, match="acas2d_monte_carlo_disturbed: max_steps = 1048575 .*the step field of the noise counter"):
+        g.MonteCarlo([MS.zero_policy(1)], MS.LANES, config=long, disturbance=the_disturbance(g), device=DEV).run(1)
+    eps = ES.episodes(ES.config(g, 1))
+    with pytest.raises(RuntimeError, match="acas2d_evaluate_policies_disturbed: max_steps = 1048575 "):
+        g.evaluate_policies_fused([MS.zero_policy(1)], eps.own, eps.trf, eps.goal, dtype=F32, device=DEV, config=long,
+                                  max_steps=120, disturbance=the_disturbance(g))
+    with pytest.raises(ValueError, match="float32 only"):
+        g.MonteCarlo([MS.zero_policy(1)], MS.LANES, dtype=torch.float64, disturbance=the_disturbance(g), device=DEV)
+    with pytest.raises(ValueError, match="float32 only"):
+        g.evaluate_policies_fused([MS.zero_policy(1)], eps.own, eps.trf, eps.goal, dtype=torch.float64, device=DEV,
+                                  disturbance=the_disturbance(g))
+    with pytest.raises(RuntimeError, match="acas2d_monte_carlo_disturbed_group: n_traffic = 3 takes the thread-per-env shape C=3 G=1: "
+                                           "use acas2d_monte_carlo_disturbed_f32"):
+        g.MonteCarlo([MS.zero_policy(3)], MS.LANES, group=True, n_traffic=3, disturbance=the_disturbance(g), device=DEV).run(1)
+    with pytest.raises(RuntimeError, match="acas2d_monte_carlo_disturbed: n_traffic = 16 has no thread-per-env shape"):
+        g.MonteCarlo([MS.zero_policy(16)], MS.LANES, n_traffic=16, disturbance=the_disturbance(g), device=DEV).run(1)
+    with pytest.raises(RuntimeError, match=r"acas2d_disturbance_draw: n_slots = 66 \(at most 65"):
+        g.policy.disturbance_draw(7, 0, 4, 0, 0, 4, 66, device=DEV)
+    with pytest.raises(RuntimeError, match="acas2d_disturbance_draw: first_step = 1048575 \\+ n_steps = 2 exceeds the step field"):
+        g.policy.disturbance_draw(7, 0, 4, 0, (1 << 20) - 1, 2, 2, device=DEV)

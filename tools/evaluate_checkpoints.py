@@ -10,7 +10,10 @@ the mean |deviation| from the planned path.
 LANES x EPISODES randomly drawn encounters of seed 13, and one JSON line per checkpoint gives its collision rate with the
 Wilson 95 % interval, the goal / timeout / loss-of-separation rates, mean steps and mean return with its standard error.
 --baseline-zero appends the all-zero policy (the unequipped aircraft: baseline_main.py's constant action [0]) and adds
-each checkpoint's risk ratio against it.
+each checkpoint's risk ratio against it.  --disturbance sep=PX,cpa=PX,closing=V,action=A[,seed=S] plays the campaign under
+white sensor noise (standard deviations in pixels and in the units of v_closing, per traffic aircraft and step) and actuator
+disturbance (in units of the action) -- policy.Disturbance, float32; the flag may be repeated to sweep levels: the same
+encounters at every level, the checkpoint lines of each level carrying its disturbance, and one summary line per level.
 --search CANDIDATESxGENERATIONS instead runs an encounter search per checkpoint (policy.EncounterSearch: cross-entropy
 proposals refit on the device, importance-sampling weights): one JSON line per checkpoint gives the estimated probability of
 min_separation <= the collision distance with its standard error, beside a crude campaign of the same number of episodes
@@ -20,6 +23,8 @@ closest encounter found.
     python tools/evaluate_checkpoints.py DIR [--dtype float64|float32] [--episodes 100] [--safety]
     python tools/evaluate_checkpoints.py DIR --search 65536x8 [--dtype float32]
     python tools/evaluate_checkpoints.py DIR --monte-carlo 65536x64 [--baseline-zero] [--dtype float32]
+    python tools/evaluate_checkpoints.py DIR --monte-carlo 65536x8 --dtype float32 --baseline-zero \
+        --disturbance sep=0,cpa=0,closing=0,action=0 --disturbance sep=90,cpa=40,closing=8,action=0.1,seed=7
 """
 import argparse
 import glob
@@ -44,7 +49,22 @@ ap.add_argument("--safety", action="store_true")
 ap.add_argument("--monte-carlo", metavar="LANESxEPISODES", default=None)
 ap.add_argument("--baseline-zero", action="store_true")
 ap.add_argument("--search", metavar="CANDIDATESxGENERATIONS", default=None)
+ap.add_argument("--disturbance", metavar="sep=..,cpa=..,closing=..,action=..[,seed=..]", action="append", default=None)
 args = ap.parse_args()
+
+
+def parse_disturbance(text):
+    kw = {}
+    for item in text.split(","):
+        key, _, val = item.partition("=")
+        if key.strip() not in ("sep", "cpa", "closing", "action", "seed") or not val:
+            sys.exit("--disturbance: %r (sep=, cpa=, closing=, action= and seed= are understood)" % item)
+        kw[key.strip()] = int(val, 0) if key.strip() == "seed" else float(val)
+    return g.policy.Disturbance(**kw)
+
+
+if args.disturbance and not args.monte_carlo:
+    sys.exit("--disturbance goes with --monte-carlo")
 
 steps_of = lambda p: int(re.search(r"model_(\d+)_steps\.zip$", p).group(1))  # noqa: E731
 ckpts = sorted({p for d in (args.dir, os.path.join(args.dir, "checkpoints"))
@@ -61,15 +81,24 @@ if args.monte_carlo:
         D = g.ACAS2DConfig().obs_dim
         pols.append((torch.zeros(64, D), torch.zeros(64), torch.zeros(64, 64), torch.zeros(64), torch.zeros(1, 64), torch.zeros(1)))
         names.append("zero (unequipped)")
-    mc = g.MonteCarlo(pols, lanes, seed=13, dtype=getattr(torch, args.dtype)).run(episodes)
-    s = mc.summary(baseline=len(pols) - 1 if args.baseline_zero else None)
-    scalars = [k for k, v in s.items() if np.ndim(v) == 1 and k != "hist_edges"]
-    for k, name in enumerate(names):
-        row = {"checkpoint": name, "timesteps": steps_of(paths[k]) if k < len(ckpts) else None}
-        row.update({key: (int(s[key][k]) if s[key].dtype.kind == "i" else float(s[key][k])) for key in scalars})
-        row["sep_hist"] = [int(x) for x in s["sep_hist"][k]]
-        print(json.dumps(row), flush=True)
-    print(json.dumps({"hist_edges": [float(x) for x in s["hist_edges"]], "lanes": lanes, "episodes_per_lane": episodes}), flush=True)
+    for level in [parse_disturbance(t) for t in args.disturbance] if args.disturbance else [None]:
+        mc = g.MonteCarlo(pols, lanes, seed=13, dtype=getattr(torch, args.dtype), disturbance=level).run(episodes)
+        s = mc.summary(baseline=len(pols) - 1 if args.baseline_zero else None)
+        scalars = [k for k, v in s.items() if np.ndim(v) == 1 and k != "hist_edges"]
+        for k, name in enumerate(names):
+            row = {"checkpoint": name, "timesteps": steps_of(paths[k]) if k < len(ckpts) else None}
+            row.update({key: (int(s[key][k]) if s[key].dtype.kind == "i" else float(s[key][k])) for key in scalars})
+            row["sep_hist"] = [int(x) for x in s["sep_hist"][k]]
+            if level is not None:
+                row["disturbance"] = level.to_dict()
+            print(json.dumps(row), flush=True)
+        last = {"hist_edges": [float(x) for x in s["hist_edges"]], "lanes": lanes, "episodes_per_lane": episodes}
+        if level is not None:                            # the level's summary line: what a sweep is read by
+            last.update(disturbance=level.to_dict(), collision_rate=[float(x) for x in s["collision_rate"]],
+                        los_rate=[float(x) for x in s["los_rate"]])
+            if "risk_ratio" in s:
+                last["risk_ratio"] = [float(x) for x in s["risk_ratio"]]
+        print(json.dumps(last), flush=True)
     sys.exit(0)
 
 if args.search:
