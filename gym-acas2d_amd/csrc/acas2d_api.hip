@@ -94,20 +94,6 @@ int acas2d_collect_set_f32(const Acas2dConfig* cfg, const Acas2dState* state, co
     return launch_collect_set<float>(cfg, state, io, ac, n_members, noise_seeds, obs_in, n_steps, seed, env_offset, n_envs,
                                      n_traffic, (hipStream_t)stream);
 }
-int acas2d_evaluate_policies_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs, const Acas2dPolicy* policies,
-                                 int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
-                                 int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
-                                 void* stream) {
-    return launch_evaluate_policies<float>(cfg, state, n_envs, policies, n_policies, n_episodes, obs_in, n_steps, seed, env_offset,
-                                           n_traffic, outcome, steps, total_reward, (hipStream_t)stream);
-}
-int acas2d_evaluate_policies_f64(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs, const Acas2dPolicy* policies,
-                                 int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
-                                 int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
-                                 void* stream) {
-    return launch_evaluate_policies<double>(cfg, state, n_envs, policies, n_policies, n_episodes, obs_in, n_steps, seed, env_offset,
-                                            n_traffic, outcome, steps, total_reward, (hipStream_t)stream);
-}
 // the group-cooperative policy (float32, n_traffic in {8, 16, 32, 64}): the siblings' launches at the packed shapes
 int acas2d_rollout_policy_group_f32(const Acas2dConfig* cfg, const Acas2dState* state, const Acas2dStepIO* io,
                                     const Acas2dPolicy* policy, const void* obs_in, int32_t n_steps, uint64_t seed,
@@ -126,90 +112,70 @@ int acas2d_collect_set_group_f32(const Acas2dConfig* cfg, const Acas2dState* sta
     return launch_collect_set_group<float>(cfg, state, io, ac, n_members, noise_seeds, obs_in, n_steps, seed, env_offset, n_envs,
                                            n_traffic, (hipStream_t)stream);
 }
-int acas2d_evaluate_policies_group_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs,
-                                       const Acas2dPolicy* policies, int32_t n_policies, int32_t n_episodes, const void* obs_in,
-                                       int32_t n_steps, uint64_t seed, int64_t env_offset, int32_t n_traffic, uint8_t* outcome,
-                                       int32_t* steps, void* total_reward, void* stream) {
-    return launch_evaluate_policies<float>(cfg, state, n_envs, policies, n_policies, n_episodes, obs_in, n_steps, seed, env_offset,
-                                           n_traffic, outcome, steps, total_reward, (hipStream_t)stream, true);
+
+// The policy-scoring family: K stacked policies, policy k on block k of round_up(count, 64) envs.  Every entry takes the same
+// eleven leading arguments under the same names (include/acas2d.h spells them out), its own outputs and the stream; the
+// launchers take the shared ones as one ScoringArgs.  `count`: the evaluator's n_episodes, the campaign's n_lanes.
+#define SCORING_PARAMS(count) \
+    const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs, const Acas2dPolicy* policies, int32_t n_policies, \
+    int32_t count, const void* obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset, int32_t n_traffic
+#define SCORING_ARGS(count, group) \
+    ScoringArgs{cfg, state, n_envs, policies, n_policies, count, obs_in, n_steps, seed, env_offset, n_traffic, (hipStream_t)stream, group}
+// the evaluator, thread-per-env in both precisions and group-cooperative (float32) ...
+int acas2d_evaluate_policies_f32(SCORING_PARAMS(n_episodes), uint8_t* outcome, int32_t* steps, void* total_reward, void* stream) {
+    return launch_evaluate_policies<float, Scoring::Plain>(SCORING_ARGS(n_episodes, false), outcome, steps, total_reward, nullptr, nullptr);
 }
-// ... and the three evaluations with per-episode safety statistics (eval_stats_kernel)
-int acas2d_evaluate_policies_stats_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs,
-                                       const Acas2dPolicy* policies, int32_t n_policies, int32_t n_episodes, const void* obs_in,
-                                       int32_t n_steps, uint64_t seed, int64_t env_offset, int32_t n_traffic, uint8_t* outcome,
-                                       int32_t* steps, void* total_reward, const Acas2dEvalStats* stats, void* stream) {
-    return launch_evaluate_policies_stats<float>(cfg, state, n_envs, policies, n_policies, n_episodes, obs_in, n_steps, seed,
-                                                 env_offset, n_traffic, outcome, steps, total_reward, stats, (hipStream_t)stream);
+int acas2d_evaluate_policies_f64(SCORING_PARAMS(n_episodes), uint8_t* outcome, int32_t* steps, void* total_reward, void* stream) {
+    return launch_evaluate_policies<double, Scoring::Plain>(SCORING_ARGS(n_episodes, false), outcome, steps, total_reward,
+                                                            nullptr, nullptr);
 }
-int acas2d_evaluate_policies_stats_f64(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs,
-                                       const Acas2dPolicy* policies, int32_t n_policies, int32_t n_episodes, const void* obs_in,
-                                       int32_t n_steps, uint64_t seed, int64_t env_offset, int32_t n_traffic, uint8_t* outcome,
-                                       int32_t* steps, void* total_reward, const Acas2dEvalStats* stats, void* stream) {
-    return launch_evaluate_policies_stats<double>(cfg, state, n_envs, policies, n_policies, n_episodes, obs_in, n_steps, seed,
-                                                  env_offset, n_traffic, outcome, steps, total_reward, stats, (hipStream_t)stream);
+int acas2d_evaluate_policies_group_f32(SCORING_PARAMS(n_episodes), uint8_t* outcome, int32_t* steps, void* total_reward, void* stream) {
+    return launch_evaluate_policies<float, Scoring::Plain>(SCORING_ARGS(n_episodes, true), outcome, steps, total_reward, nullptr, nullptr);
 }
-int acas2d_evaluate_policies_stats_group_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs,
-                                             const Acas2dPolicy* policies, int32_t n_policies, int32_t n_episodes,
-                                             const void* obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
-                                             int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
+// ... with per-episode safety statistics (eval_stats_kernel) ...
+int acas2d_evaluate_policies_stats_f32(SCORING_PARAMS(n_episodes), uint8_t* outcome, int32_t* steps, void* total_reward,
+                                       const Acas2dEvalStats* stats, void* stream) {
+    return launch_evaluate_policies<float, Scoring::Stats>(SCORING_ARGS(n_episodes, false), outcome, steps, total_reward, stats, nullptr);
+}
+int acas2d_evaluate_policies_stats_f64(SCORING_PARAMS(n_episodes), uint8_t* outcome, int32_t* steps, void* total_reward,
+                                       const Acas2dEvalStats* stats, void* stream) {
+    return launch_evaluate_policies<double, Scoring::Stats>(SCORING_ARGS(n_episodes, false), outcome, steps, total_reward, stats, nullptr);
+}
+int acas2d_evaluate_policies_stats_group_f32(SCORING_PARAMS(n_episodes), uint8_t* outcome, int32_t* steps, void* total_reward,
                                              const Acas2dEvalStats* stats, void* stream) {
-    return launch_evaluate_policies_stats<float>(cfg, state, n_envs, policies, n_policies, n_episodes, obs_in, n_steps, seed,
-                                                 env_offset, n_traffic, outcome, steps, total_reward, stats, (hipStream_t)stream, true);
+    return launch_evaluate_policies<float, Scoring::Stats>(SCORING_ARGS(n_episodes, true), outcome, steps, total_reward, stats, nullptr);
 }
-// ... and the Monte Carlo campaign on the same three families (monte_carlo_kernel)
-size_t acas2d_monte_carlo_size(void) { return sizeof(Acas2dMonteCarlo); }
-int acas2d_monte_carlo_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs, const Acas2dPolicy* policies,
-                           int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
-                           int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc, void* stream) {
-    return launch_monte_carlo<float>(cfg, state, n_envs, policies, n_policies, n_lanes, obs_in, n_steps, seed, env_offset,
-                                     n_traffic, mc, (hipStream_t)stream);
+// ... and those under sensor noise and actuator disturbance (eval_stats_disturbed_kernel; float32)
+int acas2d_evaluate_policies_disturbed_f32(SCORING_PARAMS(n_episodes), uint8_t* outcome, int32_t* steps, void* total_reward,
+                                           const Acas2dEvalStats* stats, const Acas2dDisturbance* disturbance, void* stream) {
+    return launch_evaluate_policies<float, Scoring::Disturbed>(SCORING_ARGS(n_episodes, false), outcome, steps, total_reward,
+                                                               stats, disturbance);
 }
-int acas2d_monte_carlo_f64(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs, const Acas2dPolicy* policies,
-                           int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
-                           int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc, void* stream) {
-    return launch_monte_carlo<double>(cfg, state, n_envs, policies, n_policies, n_lanes, obs_in, n_steps, seed, env_offset,
-                                      n_traffic, mc, (hipStream_t)stream);
-}
-int acas2d_monte_carlo_group_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs, const Acas2dPolicy* policies,
-                                 int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
-                                 int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc, void* stream) {
-    return launch_monte_carlo<float>(cfg, state, n_envs, policies, n_policies, n_lanes, obs_in, n_steps, seed, env_offset,
-                                     n_traffic, mc, (hipStream_t)stream, true);
-}
-// ... and both under sensor noise and actuator disturbance (eval_stats_disturbed_kernel, monte_carlo_disturbed_kernel; float32)
-size_t acas2d_disturbance_size(void) { return sizeof(Acas2dDisturbance); }
-int acas2d_evaluate_policies_disturbed_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs,
-                                           const Acas2dPolicy* policies, int32_t n_policies, int32_t n_episodes, const void* obs_in,
-                                           int32_t n_steps, uint64_t seed, int64_t env_offset, int32_t n_traffic, uint8_t* outcome,
-                                           int32_t* steps, void* total_reward, const Acas2dEvalStats* stats,
-                                           const Acas2dDisturbance* disturbance, void* stream) {
-    return launch_evaluate_policies_disturbed<float>(cfg, state, n_envs, policies, n_policies, n_episodes, obs_in, n_steps, seed,
-                                                     env_offset, n_traffic, outcome, steps, total_reward, stats, disturbance,
-                                                     (hipStream_t)stream);
-}
-int acas2d_evaluate_policies_disturbed_group_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs,
-                                                 const Acas2dPolicy* policies, int32_t n_policies, int32_t n_episodes,
-                                                 const void* obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
-                                                 int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
+int acas2d_evaluate_policies_disturbed_group_f32(SCORING_PARAMS(n_episodes), uint8_t* outcome, int32_t* steps, void* total_reward,
                                                  const Acas2dEvalStats* stats, const Acas2dDisturbance* disturbance, void* stream) {
-    return launch_evaluate_policies_disturbed<float>(cfg, state, n_envs, policies, n_policies, n_episodes, obs_in, n_steps, seed,
-                                                     env_offset, n_traffic, outcome, steps, total_reward, stats, disturbance,
-                                                     (hipStream_t)stream, true);
+    return launch_evaluate_policies<float, Scoring::Disturbed>(SCORING_ARGS(n_episodes, true), outcome, steps, total_reward,
+                                                               stats, disturbance);
 }
-int acas2d_monte_carlo_disturbed_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs, const Acas2dPolicy* policies,
-                                     int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
-                                     int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc,
-                                     const Acas2dDisturbance* disturbance, void* stream) {
-    return launch_monte_carlo_disturbed<float>(cfg, state, n_envs, policies, n_policies, n_lanes, obs_in, n_steps, seed, env_offset,
-                                               n_traffic, mc, disturbance, (hipStream_t)stream);
+// the Monte Carlo campaign on the same three families (monte_carlo_kernel), and disturbed (monte_carlo_disturbed_kernel; float32)
+int acas2d_monte_carlo_f32(SCORING_PARAMS(n_lanes), const Acas2dMonteCarlo* mc, void* stream) {
+    return launch_monte_carlo<float, false>(SCORING_ARGS(n_lanes, false), mc, nullptr);
 }
-int acas2d_monte_carlo_disturbed_group_f32(const Acas2dConfig* cfg, const Acas2dState* state, int64_t n_envs,
-                                           const Acas2dPolicy* policies, int32_t n_policies, int32_t n_lanes, const void* obs_in,
-                                           int32_t n_steps, uint64_t seed, int64_t env_offset, int32_t n_traffic,
-                                           const Acas2dMonteCarlo* mc, const Acas2dDisturbance* disturbance, void* stream) {
-    return launch_monte_carlo_disturbed<float>(cfg, state, n_envs, policies, n_policies, n_lanes, obs_in, n_steps, seed, env_offset,
-                                               n_traffic, mc, disturbance, (hipStream_t)stream, true);
+int acas2d_monte_carlo_f64(SCORING_PARAMS(n_lanes), const Acas2dMonteCarlo* mc, void* stream) {
+    return launch_monte_carlo<double, false>(SCORING_ARGS(n_lanes, false), mc, nullptr);
 }
+int acas2d_monte_carlo_group_f32(SCORING_PARAMS(n_lanes), const Acas2dMonteCarlo* mc, void* stream) {
+    return launch_monte_carlo<float, false>(SCORING_ARGS(n_lanes, true), mc, nullptr);
+}
+int acas2d_monte_carlo_disturbed_f32(SCORING_PARAMS(n_lanes), const Acas2dMonteCarlo* mc, const Acas2dDisturbance* disturbance,
+                                     void* stream) {
+    return launch_monte_carlo<float, true>(SCORING_ARGS(n_lanes, false), mc, disturbance);
+}
+int acas2d_monte_carlo_disturbed_group_f32(SCORING_PARAMS(n_lanes), const Acas2dMonteCarlo* mc, const Acas2dDisturbance* disturbance,
+                                           void* stream) {
+    return launch_monte_carlo<float, true>(SCORING_ARGS(n_lanes, true), mc, disturbance);
+}
+size_t acas2d_monte_carlo_size(void) { return sizeof(Acas2dMonteCarlo); }
+size_t acas2d_disturbance_size(void) { return sizeof(Acas2dDisturbance); }
 int acas2d_disturbance_draw_f32(uint64_t noise_seed, int64_t first_lane, int32_t n_lanes, uint32_t episode, int32_t first_step,
                                 int32_t n_steps, int32_t n_slots, float* out, void* stream) {
     return launch_disturbance_draw<float>(noise_seed, first_lane, n_lanes, episode, first_step, n_steps, n_slots, out,

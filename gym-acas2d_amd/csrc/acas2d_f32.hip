@@ -13,10 +13,9 @@ namespace acas2d {
 template decltype(launch_collect_set<float>) launch_collect_set<float>;
 template decltype(launch_collect_set_group<float>) launch_collect_set_group<float>;
 }
-ACAS2D_INSTANTIATE_EVAL_STATS
-ACAS2D_INSTANTIATE_MONTE_CARLO
+ACAS2D_INSTANTIATE_SCORING
 // evaluation and campaign under sensor noise and actuator disturbance: float32 only, behind every other kernel of the unit
-ACAS2D_INSTANTIATE_DISTURBED
+ACAS2D_INSTANTIATE_SCORING_DISTURBED
 
 #ifdef ACAS2D_STAMPS
 extern "C" int acas2d_debug_set_stamps_f32(unsigned long long* buf) {

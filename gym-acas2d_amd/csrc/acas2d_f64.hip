@@ -7,5 +7,4 @@ using Elem = double;
 constexpr bool kFast = false;
 }
 #include "acas2d_launch.inl"
-ACAS2D_INSTANTIATE_EVAL_STATS
-ACAS2D_INSTANTIATE_MONTE_CARLO
+ACAS2D_INSTANTIATE_SCORING

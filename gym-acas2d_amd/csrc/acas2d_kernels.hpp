@@ -1885,34 +1885,31 @@ template <typename T>
 int launch_collect(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
                    const void* obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset, int64_t n_envs,
                    int32_t n_traffic, hipStream_t stream);
-template <typename T>
-int launch_evaluate_policies(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
-                             int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
-                             int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
-                             hipStream_t stream, bool group = false);
-// acas2d_evaluate_policies_stats_*: the same launch with eval_stats_kernel
-template <typename T>
-int launch_evaluate_policies_stats(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
-                                   int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
-                                   int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
-                                   const Acas2dEvalStats* stats, hipStream_t stream, bool group = false);
-// acas2d_monte_carlo_*: monte_carlo_kernel
-template <typename T>
-int launch_monte_carlo(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
-                       int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
-                       int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc, hipStream_t stream, bool group = false);
-// acas2d_evaluate_policies_disturbed_*, acas2d_monte_carlo_disturbed_*, acas2d_disturbance_draw_f32 (float32 only)
-template <typename T>
-int launch_evaluate_policies_disturbed(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
-                                       int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
-                                       int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
-                                       const Acas2dEvalStats* stats, const Acas2dDisturbance* dist, hipStream_t stream,
-                                       bool group = false);
-template <typename T>
-int launch_monte_carlo_disturbed(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
-                                 int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
-                                 int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc, const Acas2dDisturbance* dist,
-                                 hipStream_t stream, bool group = false);
+// The policy-scoring family, acas2d_evaluate_policies_* and acas2d_monte_carlo_*: what all of its entry points take
+// (n_per_policy: the evaluator's n_episodes, the campaign's n_lanes; group: the *_group entries), then each launcher's own.
+struct ScoringArgs {
+    const Acas2dConfig* cfg;
+    const Acas2dState* st;
+    int64_t n_envs;
+    const Acas2dPolicy* pol;
+    int32_t n_policies, n_per_policy;
+    const void* obs_in;
+    int32_t n_steps;
+    uint64_t seed;
+    int64_t env_offset;
+    int32_t n_traffic;
+    hipStream_t stream;
+    bool group;
+};
+// the evaluator: step_kernel<..., Mode::Eval> / eval_stats_kernel (stats) / eval_stats_disturbed_kernel (stats and dist; float32)
+enum class Scoring { Plain, Stats, Disturbed };
+template <typename T, Scoring V>
+int launch_evaluate_policies(const ScoringArgs& a, uint8_t* outcome, int32_t* steps, void* total_reward,
+                             const Acas2dEvalStats* stats, const Acas2dDisturbance* dist);
+// the campaign: monte_carlo_kernel / monte_carlo_disturbed_kernel (DIST: dist; float32)
+template <typename T, bool DIST>
+int launch_monte_carlo(const ScoringArgs& a, const Acas2dMonteCarlo* mc, const Acas2dDisturbance* dist);
+// acas2d_disturbance_draw_f32 (float32 only)
 template <typename T>
 int launch_disturbance_draw(uint64_t seed, int64_t first_lane, int32_t n_lanes, uint32_t episode, int32_t first_step,
                             int32_t n_steps, int32_t n_slots, T* out, hipStream_t stream);

@@ -324,7 +324,18 @@ static int require_aligned(const char* name, std::initializer_list<const void*> 
     return ACAS2D_OK;
 }
 
-// One step_kernel launch in mode M for L's shape and formulation.  The six preloaded pointers (see step_kernel): the
+// The kernel of a launch: step_kernel in mode M, unless the launch's policy argument is one of the four that have a kernel
+// of their own (Mode::Eval with statistics, the Monte Carlo campaign, and the disturbed flavour of each; packed shapes)
+template <typename PW, typename T, int C, int G, bool PACKED, bool FAST, Mode M>
+static constexpr auto kernel_for() {
+    if constexpr (std::is_same<PW, PolicyMonteCarloDistW>::value) return &monte_carlo_disturbed_kernel<T, C, G, FAST>;
+    else if constexpr (std::is_same<PW, PolicyEvalStatsDistW>::value) return &eval_stats_disturbed_kernel<T, C, G, FAST>;
+    else if constexpr (std::is_same<PW, PolicyMonteCarloW>::value) return &monte_carlo_kernel<T, C, G, FAST>;
+    else if constexpr (std::is_same<PW, PolicyEvalStatsW>::value) return &eval_stats_kernel<T, C, G, FAST>;
+    else return &step_kernel<T, C, G, PACKED, FAST, M>;
+}
+
+// One launch in mode M for L's shape and formulation.  The six preloaded pointers (see step_kernel): the
 // arena mode's four state blocks and the actions, else the traffic arrays, own_x and own_y.
 template <Mode M, typename T, typename PW>
 static int launch_mode(const Launch<T>& L, const PW& pw) {
@@ -337,26 +348,9 @@ static int launch_mode(const Launch<T>& L, const PW& pw) {
         if constexpr ((M != Mode::Arena || (packed && sizeof(T) == 4)) && (!rollout_mode(M) || packed) &&
                       (!policy_mode(M) || G == 1 || (sizeof(T) == 4 && packed && group_policy_shape(C, G))) &&
                       (M != Mode::CollectSet || sizeof(T) == 4)) {
-            if constexpr (std::is_same<PW, PolicyMonteCarloDistW>::value) // ... and the two disturbed flavours (float32)
-                hipLaunchKernelGGL((monte_carlo_disturbed_kernel<T, C, G, fast>), dim3(L.g.grid), dim3(L.g.block), L.g.lds_bytes,
-                                   L.stream, a[0], a[1], a[2], a[3], a[4], a[5], (int32_t)L.n_envs, (int32_t)L.g.tile_elems,
-                                   L.p, rp, s, L.io, L.k0, L.k1, L.env_offset, L.N, L.n_steps, pw);
-            else if constexpr (std::is_same<PW, PolicyEvalStatsDistW>::value)
-                hipLaunchKernelGGL((eval_stats_disturbed_kernel<T, C, G, fast>), dim3(L.g.grid), dim3(L.g.block), L.g.lds_bytes,
-                                   L.stream, a[0], a[1], a[2], a[3], a[4], a[5], (int32_t)L.n_envs, (int32_t)L.g.tile_elems,
-                                   L.p, rp, s, L.io, L.k0, L.k1, L.env_offset, L.N, L.n_steps, pw);
-            else if constexpr (std::is_same<PW, PolicyMonteCarloW>::value) // ... and the Monte Carlo campaign: its own too
-                hipLaunchKernelGGL((monte_carlo_kernel<T, C, G, fast>), dim3(L.g.grid), dim3(L.g.block), L.g.lds_bytes,
-                                   L.stream, a[0], a[1], a[2], a[3], a[4], a[5], (int32_t)L.n_envs, (int32_t)L.g.tile_elems,
-                                   L.p, rp, s, L.io, L.k0, L.k1, L.env_offset, L.N, L.n_steps, pw);
-            else if constexpr (std::is_same<PW, PolicyEvalStatsW>::value) // Mode::Eval with statistics: its own kernel
-                hipLaunchKernelGGL((eval_stats_kernel<T, C, G, fast>), dim3(L.g.grid), dim3(L.g.block), L.g.lds_bytes,
-                                   L.stream, a[0], a[1], a[2], a[3], a[4], a[5], (int32_t)L.n_envs, (int32_t)L.g.tile_elems,
-                                   L.p, rp, s, L.io, L.k0, L.k1, L.env_offset, L.N, L.n_steps, pw);
-            else
-                hipLaunchKernelGGL((step_kernel<T, C, G, packed, fast, M>), dim3(L.g.grid), dim3(L.g.block), L.g.lds_bytes,
-                                   L.stream, a[0], a[1], a[2], a[3], a[4], a[5], (int32_t)L.n_envs, (int32_t)L.g.tile_elems,
-                                   L.p, rp, s, L.io, L.k0, L.k1, L.env_offset, L.N, L.n_steps, pw);
+            hipLaunchKernelGGL((kernel_for<PW, T, C, G, packed, fast, M>()), dim3(L.g.grid), dim3(L.g.block), L.g.lds_bytes,
+                               L.stream, a[0], a[1], a[2], a[3], a[4], a[5], (int32_t)L.n_envs, (int32_t)L.g.tile_elems,
+                               L.p, rp, s, L.io, L.k0, L.k1, L.env_offset, L.N, L.n_steps, pw);
         }
     });
     return ACAS2D_OK;
@@ -403,6 +397,15 @@ static PW actor(const Acas2dPolicy* pol, const void* obs_in) {
     return pw;
 }
 
+// ... and what the collectors add: the value net, log_std, the per-step value / log-probability outputs and the noise stream,
+// `key` its 64-bit key (acas2d_collect_*) or the address of the members' keys (acas2d_collect_set_*)
+static void sample_with(PolicyW& pw, const Acas2dActorCritic* ac, uint64_t key) {
+    pw.v1t = (const float*)ac->v1t; pw.vb1 = (const float*)ac->vb1; pw.v2t = (const float*)ac->v2t;
+    pw.vb2 = (const float*)ac->vb2; pw.v3 = (const float*)ac->v3; pw.vb3 = (const float*)ac->vb3;
+    pw.log_std = (const float*)ac->log_std; pw.values_out = ac->values; pw.logp_out = ac->logp;
+    pw.nk0 = (uint32_t)key; pw.nk1 = (uint32_t)(key >> 32); pw.noise_step = ac->noise_step;
+}
+
 // acas2d_rollout_policy_* and, with the actor-critic, acas2d_collect_* (which words most rejections as the former)
 template <typename T>
 static int launch_policy(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dPolicy* pol,
@@ -426,10 +429,7 @@ static int launch_policy(const Acas2dConfig* cfg, const Acas2dState* st, const A
             return fail("acas2d_collect: the value net, log_std, values and logp are required");
         if (group)
             if (int rc = require_aligned(L.name, {ac->v1t, ac->vb1, ac->v2t, ac->vb2})) return rc;
-        pw.v1t = (const float*)ac->v1t; pw.vb1 = (const float*)ac->vb1; pw.v2t = (const float*)ac->v2t;
-        pw.vb2 = (const float*)ac->vb2; pw.v3 = (const float*)ac->v3; pw.vb3 = (const float*)ac->vb3;
-        pw.log_std = (const float*)ac->log_std; pw.values_out = ac->values; pw.logp_out = ac->logp;
-        pw.nk0 = (uint32_t)ac->noise_seed; pw.nk1 = (uint32_t)(ac->noise_seed >> 32); pw.noise_step = ac->noise_step;
+        sample_with(pw, ac, ac->noise_seed);
         return launch_mode<Mode::Collect>(L, pw);
     };
     const auto shape = [&](Shape* sh) {
@@ -505,11 +505,7 @@ static int collect_set(const Acas2dConfig* cfg, const Acas2dState* st, const Aca
         if (group)      // (a member's slice lies a multiple of 256 bytes behind the stack's base: the base decides)
             if (int rc = require_aligned(L.name, {ac->actor.w1t, ac->actor.b1, ac->actor.w2t, ac->actor.b2, ac->v1t, ac->vb1,
                                                   ac->v2t, ac->vb2})) return rc;
-        pw.v1t = (const float*)ac->v1t; pw.vb1 = (const float*)ac->vb1; pw.v2t = (const float*)ac->v2t;
-        pw.vb2 = (const float*)ac->vb2; pw.v3 = (const float*)ac->v3; pw.vb3 = (const float*)ac->vb3;
-        pw.log_std = (const float*)ac->log_std; pw.values_out = ac->values; pw.logp_out = ac->logp;
-        const uint64_t keys = (uint64_t)reinterpret_cast<uintptr_t>(noise_seeds);     // the kernel loads its member's key
-        pw.nk0 = (uint32_t)keys; pw.nk1 = (uint32_t)(keys >> 32); pw.noise_step = ac->noise_step;
+        sample_with(pw, ac, (uint64_t)reinterpret_cast<uintptr_t>(noise_seeds));       // the kernel loads its member's key
         pw.member_stride = (uint32_t)(n_envs / n_members);
         return launch_mode<Mode::CollectSet>(L, pw);
     };
@@ -545,132 +541,122 @@ static DisturbW disturbance_words(const Acas2dDisturbance& d) {
     return DisturbW{d.s_sep, d.s_cpa, d.s_closing, d.s_action, (uint32_t)d.noise_seed, (uint32_t)(d.noise_seed >> 32), d.noise_episode};
 }
 
-// K stacked policies scored on shared episodes: policy k plays envs [k EP, (k + 1) EP) of the state, EP = n_episodes
-// rounded up to a whole wave; the launch covers those n_policies x EP envs.  STATS (the acas2d_evaluate_policies_stats_*
-// entry points) adds the per-episode safety statistics: eval_stats_kernel instead of step_kernel<..., Mode::Eval>.
-template <typename T, bool STATS, bool DIST = false>
-static int evaluate_policies(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
-                             int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
-                             int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
-                             hipStream_t stream, bool group, const Acas2dEvalStats* stats, const Acas2dDisturbance* dist = nullptr) {
-    static_assert(!DIST || (STATS && sizeof(T) == 4), "disturbed evaluation: float32, always with statistics");
-    const int64_t ep = ((int64_t)n_episodes + 63) / 64 * 64, total = (int64_t)n_policies * ep;
-    Launch<T> L{DIST ? (group ? "acas2d_evaluate_policies_disturbed_group" : "acas2d_evaluate_policies_disturbed") :
-                STATS ? (group ? "acas2d_evaluate_policies_stats_group" : "acas2d_evaluate_policies_stats")
-                      : (group ? "acas2d_evaluate_policies_group" : "acas2d_evaluate_policies"),
-                cfg, st, nullptr, seed, env_offset, total, n_traffic, n_steps, stream};
-    L.group_policy = group;
+// ---- the policy-scoring family: acas2d_evaluate_policies_* and acas2d_monte_carlo_* ------------------------------------------
+// K stacked policies on shared work: policy k plays envs [k EP, (k + 1) EP) of the state, EP = n_per_policy (the evaluator's
+// n_episodes, the campaign's n_lanes) rounded up to a whole wave; the launch covers those n_policies x EP envs in Mode::Eval.
+// An entry's words: what its messages call it (alone / as the *_group entry), the thread-per-env entry its *_group one sends
+// the small traffic counts to, what its family calls n_per_policy, and who says "the state holds" (NULL: the entry itself;
+// the evaluator's entries have always said that one under the plain entry's name).
+struct ScoringWords { const char *name, *group_name, *sibling, *count, *holds; };
+static const ScoringWords kEvaluateWords[] = {             // [Scoring]
+    {"acas2d_evaluate_policies", "acas2d_evaluate_policies_group", "acas2d_evaluate_policies_f32", "n_episodes",
+     "acas2d_evaluate_policies"},
+    {"acas2d_evaluate_policies_stats", "acas2d_evaluate_policies_stats_group", "acas2d_evaluate_policies_stats_f32", "n_episodes",
+     "acas2d_evaluate_policies"},
+    {"acas2d_evaluate_policies_disturbed", "acas2d_evaluate_policies_disturbed_group", "acas2d_evaluate_policies_disturbed_f32",
+     "n_episodes", "acas2d_evaluate_policies"}};
+static const ScoringWords kMonteCarloWords[] = {           // [disturbed]
+    {"acas2d_monte_carlo", "acas2d_monte_carlo_group", "acas2d_monte_carlo_f32", "n_lanes", nullptr},
+    {"acas2d_monte_carlo_disturbed", "acas2d_monte_carlo_disturbed_group", "acas2d_monte_carlo_disturbed_f32", "n_lanes", nullptr}};
+
+// Everything the two share, around their own parts: nulls(name), the family's required pointers; own(name), its checks
+// behind the counts' and in front of the disturbance's; fill(pw), its fields of the kernel's last argument PW -- which
+// picks the kernel (kernel_for()).
+template <typename T, typename PW, bool DIST, typename Nulls, typename Own, typename Fill>
+static int score(const ScoringArgs& a, const ScoringWords& w, const Acas2dDisturbance* dist, Nulls nulls, Own own, Fill fill) {
+    static_assert(!DIST || sizeof(T) == 4, "the disturbed flavours: float32");
+    const int64_t ep = ((int64_t)a.n_per_policy + 63) / 64 * 64, total = (int64_t)a.n_policies * ep;
+    Launch<T> L{a.group ? w.group_name : w.name, a.cfg, a.st, nullptr, a.seed, a.env_offset, total, a.n_traffic, a.n_steps,
+                a.stream};
+    L.group_policy = a.group;
     const auto inputs = [&] {
-        if (!obs_in || !outcome || !steps || !total_reward)
-            return fail("%s: obs_in and the outcome, steps and total_reward outputs are required", L.name);
-        if (STATS && !stats) return fail("%s: NULL stats", L.name);
-        if (STATS && (!stats->min_sep || !stats->min_sep_step || !stats->los_steps || !stats->max_a_lat || !stats->max_dev ||
-                      !stats->sum_dev))
-            return fail("%s: the min_sep, min_sep_step, los_steps, max_a_lat, max_dev and sum_dev outputs of stats are required",
-                        L.name);
-        if (int rc = require_actor(L.name, pol)) return rc;
-        if (n_policies < 1 || n_episodes < 1)
-            return fail("%s: n_policies = %d, n_episodes = %d (at least 1 each)", L.name, n_policies, n_episodes);
-        if constexpr (DIST) return check_disturbance(L.name, cfg, dist);
+        if (int rc = nulls(L.name)) return rc;
+        if (int rc = require_actor(L.name, a.pol)) return rc;
+        if (a.n_policies < 1 || a.n_per_policy < 1)
+            return fail("%s: n_policies = %d, %s = %d (at least 1 each)", L.name, a.n_policies, w.count, a.n_per_policy);
+        if (int rc = own(L.name)) return rc;
+        if constexpr (DIST) return check_disturbance(L.name, a.cfg, dist);
         return ACAS2D_OK;
     };
     const auto shape = [&](Shape* sh) {
-        const char* sibling = DIST ? "acas2d_evaluate_policies_disturbed_f32"
-                                   : (STATS ? "acas2d_evaluate_policies_stats_f32" : "acas2d_evaluate_policies_f32");
-        if (int rc = group ? group_shape<T>(L.name, sibling, n_traffic, sh) : thread_per_env(L.name, n_traffic, sh)) return rc;
-        if (n_envs >= total) return ACAS2D_OK;
-        return fail("acas2d_evaluate_policies: the state holds n_envs = %lld envs, %d policies x %lld (n_episodes = %d rounded up "
-                    "to 64) need %lld", (long long)n_envs, n_policies, (long long)ep, n_episodes, (long long)total);
+        if (int rc = a.group ? group_shape<T>(L.name, w.sibling, a.n_traffic, sh) : thread_per_env(L.name, a.n_traffic, sh)) return rc;
+        if (a.n_envs >= total) return ACAS2D_OK;
+        return fail("%s: the state holds n_envs = %lld envs, %d policies x %lld (%s = %d rounded up to 64) need %lld",
+                    w.holds ? w.holds : L.name, (long long)a.n_envs, a.n_policies, (long long)ep, w.count, a.n_per_policy,
+                    (long long)total);
     };
     const auto go = [&] {
-        if (group)
-            if (int rc = require_aligned(L.name, {pol->w1t, pol->b1, pol->w2t, pol->b2})) return rc;
-        using PW = typename std::conditional<DIST, PolicyEvalStatsDistW,
-                                             typename std::conditional<STATS, PolicyEvalStatsW, PolicyEvalW>::type>::type;
-        PW pw = actor<PW>(pol, obs_in);
+        if (a.group)
+            if (int rc = require_aligned(L.name, {a.pol->w1t, a.pol->b1, a.pol->w2t, a.pol->b2})) return rc;
+        PW pw = actor<PW>(a.pol, a.obs_in);
         if constexpr (DIST) pw.dist = disturbance_words(*dist);
+        pw.n_episodes = a.n_per_policy; pw.ep_stride = (int32_t)ep;
+        fill(pw);
+        return launch_mode<Mode::Eval>(L, pw);
+    };
+    return prepare(L, Words{"cfg / policies", kSizes, "%s: negative env_offset"}, a.pol != nullptr, inputs, shape, go);
+}
+
+// acas2d_evaluate_policies_*: each lane's first episode, scored.  Scoring::Stats adds the per-episode safety statistics
+// (eval_stats_kernel instead of step_kernel<..., Mode::Eval>), Scoring::Disturbed sensor noise and actuator disturbance on
+// top (eval_stats_disturbed_kernel; float32).
+// (The units instantiate Stats and Disturbed LAST -- ACAS2D_INSTANTIATE_SCORING at their ends -- so that their kernels follow
+//  every other kernel of the unit, and those keep the local labels of their assembly too.)
+template <typename T, Scoring V>
+int launch_evaluate_policies(const ScoringArgs& a, uint8_t* outcome, int32_t* steps, void* total_reward,
+                             const Acas2dEvalStats* stats, const Acas2dDisturbance* dist) {
+    constexpr bool STATS = V != Scoring::Plain, DIST = V == Scoring::Disturbed;
+    using PW = typename std::conditional<DIST, PolicyEvalStatsDistW,
+                                         typename std::conditional<STATS, PolicyEvalStatsW, PolicyEvalW>::type>::type;
+    const auto nulls = [&](const char* name) {
+        if (!a.obs_in || !outcome || !steps || !total_reward)
+            return fail("%s: obs_in and the outcome, steps and total_reward outputs are required", name);
+        if (STATS && !stats) return fail("%s: NULL stats", name);
+        if (STATS && (!stats->min_sep || !stats->min_sep_step || !stats->los_steps || !stats->max_a_lat || !stats->max_dev ||
+                      !stats->sum_dev))
+            return fail("%s: the min_sep, min_sep_step, los_steps, max_a_lat, max_dev and sum_dev outputs of stats are required",
+                        name);
+        return ACAS2D_OK;
+    };
+    const auto fill = [&](PW& pw) {
         pw.res_outcome = outcome; pw.res_steps = steps; pw.res_return = total_reward;
-        pw.n_episodes = n_episodes; pw.ep_stride = (int32_t)ep;
         if constexpr (STATS) {
             pw.st_min_sep = stats->min_sep; pw.st_min_sep_step = stats->min_sep_step; pw.st_los_steps = stats->los_steps;
             pw.st_max_a_lat = stats->max_a_lat; pw.st_max_dev = stats->max_dev; pw.st_sum_dev = stats->sum_dev;
         }
-        return launch_mode<Mode::Eval>(L, pw);             // (PW picks the kernel)
     };
-    return prepare(L, Words{"cfg / policies", kSizes, "%s: negative env_offset"}, pol != nullptr, inputs, shape, go);
+    return score<T, PW, DIST>(a, kEvaluateWords[(int)V], dist, nulls, [](const char*) { return ACAS2D_OK; }, fill);
 }
-template <typename T>
-int launch_evaluate_policies(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
-                             int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
-                             int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
-                             hipStream_t stream, bool group) {
-    return evaluate_policies<T, false>(cfg, st, n_envs, pol, n_policies, n_episodes, obs_in, n_steps, seed, env_offset, n_traffic,
-                                       outcome, steps, total_reward, stream, group, nullptr);
-}
-// (the units instantiate this one LAST -- ACAS2D_INSTANTIATE_EVAL_STATS at their ends -- so that its kernels follow
-//  every other kernel of the unit, and those keep the local labels of their assembly too)
-template <typename T>
-int launch_evaluate_policies_stats(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
-                                   int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
-                                   int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
-                                   const Acas2dEvalStats* stats, hipStream_t stream, bool group) {
-    return evaluate_policies<T, true>(cfg, st, n_envs, pol, n_policies, n_episodes, obs_in, n_steps, seed, env_offset, n_traffic,
-                                      outcome, steps, total_reward, stream, group, stats);
-}
-#define ACAS2D_INSTANTIATE_EVAL_STATS \
-    namespace acas2d { template decltype(launch_evaluate_policies_stats<Elem>) launch_evaluate_policies_stats<Elem>; }
 
-// acas2d_monte_carlo_*: evaluate_policies()'s blocks of lanes, each lane playing mc->episodes_per_lane drawn episodes and
-// folding them into mc's accumulators (monte_carlo_kernel).  The checks and words of evaluate_policies<T, true>, then its own.
-// (Instantiated after the stats launcher -- ACAS2D_INSTANTIATE_MONTE_CARLO -- for the same reason.)
+// acas2d_monte_carlo_*: the same blocks of lanes, each lane playing mc->episodes_per_lane drawn episodes and folding them
+// into mc's accumulators (monte_carlo_kernel; DIST: monte_carlo_disturbed_kernel, float32).  Instantiated after the stats
+// evaluator, for the same reason.
 template <typename T, bool DIST>
-static int monte_carlo(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
-                       int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
-                       int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc, hipStream_t stream, bool group,
-                       const Acas2dDisturbance* dist) {
-    static_assert(!DIST || sizeof(T) == 4, "disturbed campaign: float32");
-    const int64_t ep = ((int64_t)n_lanes + 63) / 64 * 64, total = (int64_t)n_policies * ep;
-    Launch<T> L{DIST ? (group ? "acas2d_monte_carlo_disturbed_group" : "acas2d_monte_carlo_disturbed")
-                     : (group ? "acas2d_monte_carlo_group" : "acas2d_monte_carlo"), cfg, st, nullptr, seed, env_offset, total, n_traffic,
-                n_steps, stream};
-    L.group_policy = group;
-    const auto inputs = [&] {
-        if (!obs_in) return fail("%s: obs_in is required", L.name);
-        if (!mc) return fail("%s: NULL mc", L.name);
+int launch_monte_carlo(const ScoringArgs& a, const Acas2dMonteCarlo* mc, const Acas2dDisturbance* dist) {
+    using PW = typename std::conditional<DIST, PolicyMonteCarloDistW, PolicyMonteCarloW>::type;
+    const auto nulls = [&](const char* name) {
+        if (!a.obs_in) return fail("%s: obs_in is required", name);
+        if (!mc) return fail("%s: NULL mc", name);
         if (!mc->outcome_count || !mc->sum_steps || !mc->los_episodes || !mc->sum_los_steps || !mc->sep_hist ||
             !mc->lane_return_sum || !mc->lane_return_sq || !mc->lane_worst_sep || !mc->lane_worst_episode)
-            return fail("%s: the nine accumulators of mc are required", L.name);
-        if (int rc = require_actor(L.name, pol)) return rc;
-        if (n_policies < 1 || n_lanes < 1)
-            return fail("%s: n_policies = %d, n_lanes = %d (at least 1 each)", L.name, n_policies, n_lanes);
-        if (mc->episodes_per_lane < 1) return fail("%s: episodes_per_lane = %d (at least 1)", L.name, mc->episodes_per_lane);
-        if (mc->n_bins < 1) return fail("%s: n_bins = %d (at least 1)", L.name, mc->n_bins);
-        if ((uint64_t)mc->first_episode + (uint64_t)mc->episodes_per_lane > (1ull << 32))
-            return fail("%s: first_episode = %u + episodes_per_lane = %d exceeds the 32-bit episode counter", L.name,
-                        mc->first_episode, mc->episodes_per_lane);
-        const int64_t need = (int64_t)mc->episodes_per_lane * cfg->max_steps;
-        if (cfg->max_steps < 1 || need + mc->episodes_per_lane > 0x7fffffffLL || mc->episodes_per_lane > (1 << 24) || n_steps < need)
-            return fail("%s: n_steps = %d does not cover episodes_per_lane = %d episodes of max_steps = %d steps (%lld needed; "
-                        "episodes_per_lane x (max_steps + 1) must fit an int32, episodes_per_lane <= 2^24)", L.name, n_steps,
-                        mc->episodes_per_lane, cfg->max_steps, (long long)need);
-        if constexpr (DIST) return check_disturbance(L.name, cfg, dist);
+            return fail("%s: the nine accumulators of mc are required", name);
         return ACAS2D_OK;
     };
-    const auto shape = [&](Shape* sh) {
-        if (int rc = group ? group_shape<T>(L.name, DIST ? "acas2d_monte_carlo_disturbed_f32" : "acas2d_monte_carlo_f32", n_traffic, sh)
-                           : thread_per_env(L.name, n_traffic, sh))
-            return rc;
-        if (n_envs >= total) return ACAS2D_OK;
-        return fail("%s: the state holds n_envs = %lld envs, %d policies x %lld (n_lanes = %d rounded up to 64) need %lld", L.name,
-                    (long long)n_envs, n_policies, (long long)ep, n_lanes, (long long)total);
+    const auto own = [&](const char* name) {
+        if (mc->episodes_per_lane < 1) return fail("%s: episodes_per_lane = %d (at least 1)", name, mc->episodes_per_lane);
+        if (mc->n_bins < 1) return fail("%s: n_bins = %d (at least 1)", name, mc->n_bins);
+        if ((uint64_t)mc->first_episode + (uint64_t)mc->episodes_per_lane > (1ull << 32))
+            return fail("%s: first_episode = %u + episodes_per_lane = %d exceeds the 32-bit episode counter", name,
+                        mc->first_episode, mc->episodes_per_lane);
+        const int64_t need = (int64_t)mc->episodes_per_lane * a.cfg->max_steps;
+        if (a.cfg->max_steps < 1 || need + mc->episodes_per_lane > 0x7fffffffLL || mc->episodes_per_lane > (1 << 24) ||
+            a.n_steps < need)
+            return fail("%s: n_steps = %d does not cover episodes_per_lane = %d episodes of max_steps = %d steps (%lld needed; "
+                        "episodes_per_lane x (max_steps + 1) must fit an int32, episodes_per_lane <= 2^24)", name, a.n_steps,
+                        mc->episodes_per_lane, a.cfg->max_steps, (long long)need);
+        return ACAS2D_OK;
     };
-    const auto go = [&] {
-        if (group)
-            if (int rc = require_aligned(L.name, {pol->w1t, pol->b1, pol->w2t, pol->b2})) return rc;
-        using PW = typename std::conditional<DIST, PolicyMonteCarloDistW, PolicyMonteCarloW>::type;
-        PW pw = actor<PW>(pol, obs_in);
-        if constexpr (DIST) pw.dist = disturbance_words(*dist);
-        pw.n_episodes = n_lanes; pw.ep_stride = (int32_t)ep;
+    const auto fill = [&](PW& pw) {
         const auto u64 = [](int64_t* q) { return reinterpret_cast<unsigned long long*>(q); };
         pw.mc_outcome_count = u64(mc->outcome_count); pw.mc_sum_steps = u64(mc->sum_steps);
         pw.mc_los_episodes = u64(mc->los_episodes); pw.mc_sum_los_steps = u64(mc->sum_los_steps); pw.mc_sep_hist = u64(mc->sep_hist);
@@ -678,38 +664,11 @@ static int monte_carlo(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n
         pw.mc_worst_sep = mc->lane_worst_sep; pw.mc_worst_episode = mc->lane_worst_episode;
         pw.mc_n_bins = mc->n_bins; pw.mc_episodes = mc->episodes_per_lane; pw.mc_first = mc->first_episode;
         pw.mc_inv_bin_f = (float)mc->inv_bin_width; pw.mc_inv_bin_d = mc->inv_bin_width;
-        return launch_mode<Mode::Eval>(L, pw);             // (PW picks the kernel)
     };
-    return prepare(L, Words{"cfg / policies", kSizes, "%s: negative env_offset"}, pol != nullptr, inputs, shape, go);
+    return score<T, PW, DIST>(a, kMonteCarloWords[DIST], dist, nulls, own, fill);
 }
-template <typename T>
-int launch_monte_carlo(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
-                       int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
-                       int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc, hipStream_t stream, bool group) {
-    return monte_carlo<T, false>(cfg, st, n_envs, pol, n_policies, n_lanes, obs_in, n_steps, seed, env_offset, n_traffic, mc, stream,
-                                 group, nullptr);
-}
-#define ACAS2D_INSTANTIATE_MONTE_CARLO \
-    namespace acas2d { template decltype(launch_monte_carlo<Elem>) launch_monte_carlo<Elem>; }
 
-// The disturbed flavours of the two (eval_stats_disturbed_kernel, monte_carlo_disturbed_kernel) and the draw entry; float32,
-// instantiated after everything else of the unit (ACAS2D_INSTANTIATE_DISTURBED) for the reason the stats launcher is.
-template <typename T>
-int launch_evaluate_policies_disturbed(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
-                                       int32_t n_policies, int32_t n_episodes, const void* obs_in, int32_t n_steps, uint64_t seed,
-                                       int64_t env_offset, int32_t n_traffic, uint8_t* outcome, int32_t* steps, void* total_reward,
-                                       const Acas2dEvalStats* stats, const Acas2dDisturbance* dist, hipStream_t stream, bool group) {
-    return evaluate_policies<T, true, true>(cfg, st, n_envs, pol, n_policies, n_episodes, obs_in, n_steps, seed, env_offset,
-                                            n_traffic, outcome, steps, total_reward, stream, group, stats, dist);
-}
-template <typename T>
-int launch_monte_carlo_disturbed(const Acas2dConfig* cfg, const Acas2dState* st, int64_t n_envs, const Acas2dPolicy* pol,
-                                 int32_t n_policies, int32_t n_lanes, const void* obs_in, int32_t n_steps, uint64_t seed,
-                                 int64_t env_offset, int32_t n_traffic, const Acas2dMonteCarlo* mc, const Acas2dDisturbance* dist,
-                                 hipStream_t stream, bool group) {
-    return monte_carlo<T, true>(cfg, st, n_envs, pol, n_policies, n_lanes, obs_in, n_steps, seed, env_offset, n_traffic, mc, stream,
-                                group, dist);
-}
+// acas2d_disturbance_draw_f32: the normals the disturbed kernels draw (float32; instantiated with them)
 template <typename T>
 int launch_disturbance_draw(uint64_t seed, int64_t first_lane, int32_t n_lanes, uint32_t episode, int32_t first_step,
                             int32_t n_steps, int32_t n_slots, T* out, hipStream_t stream) {
@@ -729,10 +688,17 @@ int launch_disturbance_draw(uint64_t seed, int64_t first_lane, int32_t n_lanes, 
                        (uint32_t)n_slots, total, out);
     return check_launch(name);
 }
-#define ACAS2D_INSTANTIATE_DISTURBED \
+// The family's instantiations behind everything else of a unit, in the order their kernels have always been emitted: the
+// stats evaluator, the campaign, and -- the float32 unit's tail -- the disturbed evaluator, the disturbed campaign, the draw.
+// (The plain evaluator's kernels are step_kernel's: it is instantiated with the other launchers, below.)
+#define ACAS2D_INSTANTIATE_SCORING \
     namespace acas2d { \
-    template decltype(launch_evaluate_policies_disturbed<Elem>) launch_evaluate_policies_disturbed<Elem>; \
-    template decltype(launch_monte_carlo_disturbed<Elem>) launch_monte_carlo_disturbed<Elem>; \
+    template decltype(launch_evaluate_policies<Elem, Scoring::Stats>) launch_evaluate_policies<Elem, Scoring::Stats>; \
+    template decltype(launch_monte_carlo<Elem, false>) launch_monte_carlo<Elem, false>; }
+#define ACAS2D_INSTANTIATE_SCORING_DISTURBED \
+    namespace acas2d { \
+    template decltype(launch_evaluate_policies<Elem, Scoring::Disturbed>) launch_evaluate_policies<Elem, Scoring::Disturbed>; \
+    template decltype(launch_monte_carlo<Elem, true>) launch_monte_carlo<Elem, true>; \
     template decltype(launch_disturbance_draw<Elem>) launch_disturbance_draw<Elem>; }
 
 template <typename T>
@@ -780,7 +746,7 @@ template decltype(launch_rollout_policy<Elem>) launch_rollout_policy<Elem>;
 template decltype(launch_collect<Elem>) launch_collect<Elem>;
 template decltype(launch_rollout_policy_group<Elem>) launch_rollout_policy_group<Elem>;
 template decltype(launch_collect_group<Elem>) launch_collect_group<Elem>;
-template decltype(launch_evaluate_policies<Elem>) launch_evaluate_policies<Elem>;
+template decltype(launch_evaluate_policies<Elem, Scoring::Plain>) launch_evaluate_policies<Elem, Scoring::Plain>;
 template decltype(launch_reset<Elem>) launch_reset<Elem>;
 template decltype(shape_geometry<Elem>) shape_geometry<Elem>;
 template decltype(state_consecutive<Elem>) state_consecutive<Elem>;

@@ -218,37 +218,20 @@ def lib():
         f.restype = C.c_int
         f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.POINTER(CStepIO), C.POINTER(CActorCritic), C.c_void_p,
                       C.c_int32, C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
-    for name in ("acas2d_evaluate_policies_f32", "acas2d_evaluate_policies_f64", "acas2d_evaluate_policies_group_f32"):
-        f = getattr(L, name)
-        f.restype = C.c_int
-        f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.c_int64, C.POINTER(CPolicy), C.c_int32, C.c_int32,
-                      C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                      C.c_void_p]
-    for name in ("acas2d_evaluate_policies_stats_f32", "acas2d_evaluate_policies_stats_f64",
-                 "acas2d_evaluate_policies_stats_group_f32"):                  # the plain siblings' list, stats before stream
-        f = getattr(L, name)
-        f.restype = C.c_int
-        f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.c_int64, C.POINTER(CPolicy), C.c_int32, C.c_int32,
-                      C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                      C.POINTER(CEvalStats), C.c_void_p]
-    for name in ("acas2d_monte_carlo_f32", "acas2d_monte_carlo_f64", "acas2d_monte_carlo_group_f32"):
-        f = getattr(L, name)                               # the stats entries' list without the three per-episode outputs
-        f.restype = C.c_int
-        f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.c_int64, C.POINTER(CPolicy), C.c_int32, C.c_int32,
-                      C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(CMonteCarlo), C.c_void_p]
+    # the policy-scoring family (acas2d_evaluate_policies_*, acas2d_monte_carlo_*): cfg, state, n_envs, policies, n_policies,
+    # n_episodes / n_lanes, obs_in, n_steps, seed, env_offset, n_traffic -- then each entry's own outputs, then the stream
+    head = [C.POINTER(CConfig), C.POINTER(CState), C.c_int64, C.POINTER(CPolicy), C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+            C.c_uint64, C.c_int64, C.c_int32]
+    results = [C.c_void_p, C.c_void_p, C.c_void_p]          # outcome, steps, total_reward
+    for stem, tail in (("evaluate_policies", results), ("evaluate_policies_stats", results + [C.POINTER(CEvalStats)]),
+                       ("evaluate_policies_disturbed", results + [C.POINTER(CEvalStats), C.POINTER(CDisturbance)]),
+                       ("monte_carlo", [C.POINTER(CMonteCarlo)]),
+                       ("monte_carlo_disturbed", [C.POINTER(CMonteCarlo), C.POINTER(CDisturbance)])):
+        for sfx in ("f32", "group_f32") + (() if stem.endswith("disturbed") else ("f64",)):     # (disturbed: float32 only)
+            f = getattr(L, "acas2d_%s_%s" % (stem, sfx))
+            f.restype = C.c_int
+            f.argtypes = head + tail + [C.c_void_p]
     L.acas2d_monte_carlo_size.restype = C.c_size_t
-    for name in ("acas2d_evaluate_policies_disturbed_f32", "acas2d_evaluate_policies_disturbed_group_f32"):
-        f = getattr(L, name)                               # the stats entries' list, the disturbance before stream
-        f.restype = C.c_int
-        f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.c_int64, C.POINTER(CPolicy), C.c_int32, C.c_int32,
-                      C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                      C.POINTER(CEvalStats), C.POINTER(CDisturbance), C.c_void_p]
-    for name in ("acas2d_monte_carlo_disturbed_f32", "acas2d_monte_carlo_disturbed_group_f32"):
-        f = getattr(L, name)                               # the campaign entries' list, the disturbance before stream
-        f.restype = C.c_int
-        f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.c_int64, C.POINTER(CPolicy), C.c_int32, C.c_int32,
-                      C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int32, C.POINTER(CMonteCarlo),
-                      C.POINTER(CDisturbance), C.c_void_p]
     L.acas2d_disturbance_draw_f32.restype = C.c_int
     L.acas2d_disturbance_draw_f32.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
                                               C.c_void_p, C.c_void_p]

@@ -20,6 +20,9 @@ import zipfile
 import numpy as np
 import torch
 
+from . import native, records
+from .config import ACAS2DConfig
+
 _ACTOR_KEYS = ("mlp_extractor.policy_net.0.weight", "mlp_extractor.policy_net.0.bias",
                "mlp_extractor.policy_net.2.weight", "mlp_extractor.policy_net.2.bias",
                "action_net.weight", "action_net.bias")
@@ -195,7 +198,6 @@ class Disturbance:
     seed: int
 
     def __init__(self, sep=0.0, cpa=0.0, closing=0.0, action=0.0, seed=0, config=None):
-        from .config import ACAS2DConfig
         c = (config if config is not None else ACAS2DConfig()).to_c()
         self._set(float(sep) / float(c.d_sep_max), float(cpa) / float(c.d_cpa_max), float(closing) / float(c.v_closing_max),
                   action, seed)
@@ -230,7 +232,6 @@ class Disturbance:
         return cls.normalised(d["s_sep"], d["s_cpa"], d["s_closing"], d["s_action"], d["seed"])
 
     def to_c(self, noise_episode=0):
-        from . import native
         return native.CDisturbance(self.s_sep, self.s_cpa, self.s_closing, self.s_action, self.seed, int(noise_episode), 0)
 
 
@@ -239,7 +240,6 @@ def disturbance_draw(seed, first_lane, n_lanes, episode, first_step, n_steps, n_
     (z_sep, z_cpa, z_closing; slot 0: the actuator's normal and two zeros; slot n + 1: traffic n) for lanes first_lane ..,
     steps first_step .. (game.steps before the step) of episode counter `episode` -- computed by the device function the
     kernels call, so a host replay that uses them reproduces a disturbed episode bit for bit."""
-    from . import native
     dev = torch.device(device)
     shape = (max(int(n_steps), 0), max(int(n_lanes), 0), max(int(n_slots), 0), 3)
     out = torch.empty(shape, dtype=torch.float32, device=dev)
@@ -250,16 +250,54 @@ def disturbance_draw(seed, first_lane, n_lanes, episode, first_step, n_steps, n_
     return out.cpu().numpy()
 
 
+def _scoring_entry(caller, stem, dtype, group, disturbed):
+    """The scoring family's C entry for (dtype, group, disturbed); group and disturbed are float32 only, and `caller` says so."""
+    for flag, on in (("group=True", group), ("disturbance=...", disturbed)):
+        if on and dtype != torch.float32:
+            raise ValueError("%s(%s) is float32 only, got %s" % (caller, flag, dtype))
+    if disturbed:
+        stem = stem.replace("_stats", "") + "_disturbed"
+    return "acas2d_%s%s_%s" % (stem, "_group" if group else "", "f32" if dtype == torch.float32 else "f64")
+
+
+class PolicyBlocks:
+    """What the K-policy launches share (acas2d_evaluate_policies_*, acas2d_monte_carlo_*): policy k plays block k of
+    EP = round_up(n_per_policy, 64) envs -- its n_per_policy episodes or lanes, then padding that repeats the first -- and
+    the launch reads the K policies' stacked weights (stack_policies())."""
+
+    def __init__(self, policies, n_per_policy, obs_dim, device):
+        self.n_policies, self.n_per_policy = len(policies), int(n_per_policy)
+        self.EP = self.block_envs(n_per_policy)
+        self.weights = stack_policies(policies, obs_dim, device)
+        self._policy = native.CPolicy(*[t.data_ptr() for t in self.weights], 64, 0)
+
+    @staticmethod
+    def block_envs(n_per_policy):
+        return (int(n_per_policy) + 63) // 64 * 64               # EP: whole wavefronts (a wavefront's envs belong to ONE policy)
+
+    def index(self, device=None):
+        """[K x EP]: which of n_per_policy shared episodes (lanes) each env of the K blocks plays; on `device`, a tensor."""
+        idx = np.tile(np.concatenate([np.arange(self.n_per_policy), np.zeros(self.EP - self.n_per_policy, np.int64)]), self.n_policies)
+        return idx if device is None else torch.as_tensor(idx, device=device)
+
+    @staticmethod
+    def c_eval_stats(st_f, st_i):
+        """struct Acas2dEvalStats over st_f [4, K, n]: min_sep, max_a_lat, max_dev, sum_dev; st_i [2, K, n]: min_sep_step, los_steps"""
+        return native.CEvalStats(*[t.data_ptr() for t in (st_f[0], st_i[0], st_i[1], st_f[1], st_f[2], st_f[3])])
+
+    def call(self, entry, venv, obs, n_steps, *tail):
+        """`entry` on venv's K x EP envs from the observation `obs`: the family's shared arguments, the entry's own `tail`
+        (addresses, and structs to pass by reference), the stream"""
+        tail = [C.byref(t) if isinstance(t, C.Structure) else t for t in tail]
+        native.check(getattr(native.lib(), entry)(
+            C.byref(venv._ccfg), C.byref(venv._cstate), venv.num_envs, C.byref(self._policy), self.n_policies, self.n_per_policy,
+            obs.data_ptr(), n_steps, venv.seed_value, venv.env_offset, venv.n_traffic, *tail, venv._stream()))
+
+
 def evaluate_policies_entry(dtype, group=False, safety=False, disturbed=False):
     """The name of the C entry point evaluate_policies_fused() calls for (dtype, group, safety, disturbed)."""
-    if group and dtype != torch.float32:
-        raise ValueError("evaluate_policies_fused(group=True) is float32 only, got %s" % (dtype,))
-    if disturbed:
-        if dtype != torch.float32:
-            raise ValueError("evaluate_policies_fused(disturbance=...) is float32 only, got %s" % (dtype,))
-        return "acas2d_evaluate_policies_disturbed%s_f32" % ("_group" if group else "")
-    return "acas2d_evaluate_policies%s%s_%s" % ("_stats" if safety else "", "_group" if group else "",
-                                                "f32" if dtype == torch.float32 else "f64")
+    return _scoring_entry("evaluate_policies_fused", "evaluate_policies_stats" if safety else "evaluate_policies", dtype, group,
+                          disturbed)
 
 
 def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float64, device="cuda:0", config=None,
@@ -281,7 +319,6 @@ def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float
     (acas2d_evaluate_policies_disturbed_*; it always computes the statistics, so the six keys are returned whatever
     `safety` says).  Episode i draws the noise of lane env_offset + i and episode counter `noise_episode`: what lane i of a
     MonteCarlo campaign with the same disturbance and env_offset met in its episode `noise_episode`."""
-    from . import native
     from .vec_env import ACAS2DVecEnv
     if not policies:
         raise ValueError("evaluate_policies_fused needs at least one policy")
@@ -291,35 +328,28 @@ def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float
         safety, entry = True, evaluate_policies_entry(dtype, group, True, disturbed=True)
     own, traffic = np.asarray(own), np.asarray(traffic)
     E, N = own.shape[0], traffic.shape[1]
-    K, EP = len(policies), (own.shape[0] + 63) // 64 * 64
-    idx = np.concatenate([np.arange(E), np.zeros(EP - E, np.int64)])
-    idx = np.tile(idx, K)
+    if config is None:
+        config = ACAS2DConfig(n_traffic=N)
+    dev = torch.device(device)
+    blocks = PolicyBlocks(policies, E, config.obs_dim, dev)
+    K, idx = blocks.n_policies, blocks.index()
     if goal is not None and np.asarray(goal).ndim == 2:
         goal = np.asarray(goal)[idx]
-    v = ACAS2DVecEnv(K * EP, N, device=device, dtype=dtype, auto_reset=True, config=config, env_offset=int(env_offset))
-    D, dev = v.obs_dim, v.device
-    v.set_state(own[idx], traffic[idx], goal, np.zeros(K * EP, np.int32), observe=True)
-    keep = stack_policies(policies, D, dev)
+    v = ACAS2DVecEnv(len(idx), N, device=dev, dtype=dtype, auto_reset=True, config=config, env_offset=int(env_offset))
+    v.set_state(own[idx], traffic[idx], goal, np.zeros(len(idx), np.int32), observe=True)
     T = (max_steps or v.config.max_steps) + 1
     outcome = torch.empty(K, E, dtype=torch.uint8, device=dev)
     steps = torch.empty(K, E, dtype=torch.int32, device=dev)
     ret = torch.empty(K, E, dtype=dtype, device=dev)
-    pw = native.CPolicy(*[t.data_ptr() for t in keep], 64, 0)
-    fn = getattr(native.lib(), entry)
-    extra = ()
+    tail = [outcome.data_ptr(), steps.data_ptr(), ret.data_ptr()]
     if safety:
         st_f = torch.empty(4, K, E, dtype=dtype, device=dev)                    # min_sep, max_a_lat, max_dev, sum_dev
         st_i = torch.empty(2, K, E, dtype=torch.int32, device=dev)              # min_sep_step, los_steps
-        cstats = native.CEvalStats(st_f[0].data_ptr(), st_i[0].data_ptr(), st_i[1].data_ptr(), st_f[1].data_ptr(),
-                                   st_f[2].data_ptr(), st_f[3].data_ptr())
-        extra = (C.byref(cstats),)
+        tail.append(blocks.c_eval_stats(st_f, st_i))
     if disturbance is not None:
-        cdist = disturbance.to_c(noise_episode)
-        extra += (C.byref(cdist),)
+        tail.append(disturbance.to_c(noise_episode))
     with torch.cuda.device(dev):
-        native.check(fn(C.byref(v._ccfg), C.byref(v._cstate), K * EP, C.byref(pw), K, E, v.outputs["obs"].data_ptr(), T,
-                        v.seed_value, v.env_offset, N, outcome.data_ptr(), steps.data_ptr(), ret.data_ptr(),
-                        *extra, v._stream()))
+        blocks.call(entry, v, v.outputs["obs"], T, *tail)
     oc, st = outcome.cpu().numpy(), steps.cpu().numpy()
     step_len = v.config.airspeed * v.config.dt
     res = {"outcome": oc, "steps": st, "total_reward": ret.cpu().numpy().astype(np.float64),
@@ -334,13 +364,7 @@ def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float
 
 def monte_carlo_entry(dtype, group=False, disturbed=False):
     """The name of the C entry point MonteCarlo launches for (dtype, group, disturbed)."""
-    if group and dtype != torch.float32:
-        raise ValueError("MonteCarlo(group=True) is float32 only, got %s" % (dtype,))
-    if disturbed:
-        if dtype != torch.float32:
-            raise ValueError("MonteCarlo(disturbance=...) is float32 only, got %s" % (dtype,))
-        return "acas2d_monte_carlo_disturbed%s_f32" % ("_group" if group else "")
-    return "acas2d_monte_carlo%s_%s" % ("_group" if group else "", "f32" if dtype == torch.float32 else "f64")
+    return _scoring_entry("MonteCarlo", "monte_carlo", dtype, group, disturbed)
 
 
 class MonteCarlo:
@@ -365,8 +389,6 @@ class MonteCarlo:
 
     def __init__(self, policies, n_lanes, seed=13, dtype=torch.float32, group=False, config=None, n_traffic=1, n_bins=64,
                  hist_max=None, device="cuda:0", env_offset=0, disturbance=None):
-        from . import native, records
-        from .config import ACAS2DConfig
         from .vec_env import ACAS2DVecEnv
         if not policies:
             raise ValueError("MonteCarlo needs at least one policy")
@@ -381,23 +403,21 @@ class MonteCarlo:
         self.inv_bin_width = self.n_bins / self.hist_max
         self.first_episode = 0
         K, L = self.n_policies, self.n_lanes
-        EP = (L + 63) // 64 * 64
         mk = lambda n, off: ACAS2DVecEnv(n, self.config.n_traffic, device=device, dtype=dtype, seed=seed, env_offset=off,  # noqa: E731
                                          auto_reset=True, config=self.config, keep_terminal_obs=False, double_buffer=False)
         self._src = mk(L, int(env_offset))                       # draws the first episode of a launch
-        self._all = mk(K * EP, int(env_offset))                  # ... which is replicated into its K blocks (padding: lane 0)
         self.device = dev = self._src.device
-        self._weights = stack_policies(policies, self._src.obs_dim, dev)
-        self._idx = torch.as_tensor(np.tile(np.concatenate([np.arange(L), np.zeros(EP - L, np.int64)]), K), device=dev)
+        self._blocks = PolicyBlocks(policies, L, self._src.obs_dim, dev)
+        self._all = mk(K * self._blocks.EP, int(env_offset))     # ... which is replicated into its K blocks (padding: lane 0)
+        self._idx = self._blocks.index(dev)
         npdt = np.float32 if dtype == torch.float32 else np.float64
         self._acc = {k: torch.as_tensor(v.view(np.int32) if v.dtype == np.uint32 else v).to(dev)
                      for k, v in records.monte_carlo_empty(K, L, max(self.n_bins, 1), npdt).items()}     # (n_bins < 1: the launch refuses)
-        self._native = native
 
     def _launch(self, episodes, events=None):
         """One launch: `episodes` episodes per lane from counter first_episode on.  `events`: a pair of torch.cuda.Events
         to record in front of and behind the kernel alone (tools/bench_monte_carlo.py)."""
-        C_, nat, src, dst = C, self._native, self._src, self._all
+        src, dst = self._src, self._all
         src.reset_to_episode(self.first_episode)
         with torch.cuda.device(self.device):
             # the first observation as an injected state's (set_state(observe=True)): what a replay of the encounter
@@ -408,22 +428,13 @@ class MonteCarlo:
                          "total_reward"):
                 getattr(dst, name).copy_(getattr(src, name)[self._idx])
             dst._obs.copy_(src._obs[self._idx])
-            a = self._acc
-            mc = nat.CMonteCarlo(*[a[k].data_ptr() for k in ("outcome_count", "sum_steps", "los_episodes", "sum_los_steps",
-                                                             "sep_hist", "lane_return_sum", "lane_return_sq", "lane_worst_sep",
-                                                             "lane_worst_episode")],
-                                 self.n_bins, int(episodes), self.inv_bin_width, self.first_episode, 0)
-            pw = nat.CPolicy(*[t.data_ptr() for t in self._weights], 64, 0)
+            mc = native.CMonteCarlo(*[self._acc[k].data_ptr() for k in records.MONTE_CARLO_KEYS], self.n_bins, int(episodes),
+                                    self.inv_bin_width, self.first_episode, 0)
             n_steps = max(int(episodes), 0) * self.config.max_steps
-            extra = ()
-            if self.disturbance is not None:
-                cdist = self.disturbance.to_c()
-                extra = (C_.byref(cdist),)
+            tail = [mc] if self.disturbance is None else [mc, self.disturbance.to_c()]
             if events:
                 events[0].record()
-            nat.check(getattr(nat.lib(), self.entry)(
-                C_.byref(dst._ccfg), C_.byref(dst._cstate), dst.num_envs, C_.byref(pw), self.n_policies, self.n_lanes,
-                dst._obs.data_ptr(), n_steps, src.seed_value, src.env_offset, src.n_traffic, C_.byref(mc), *extra, dst._stream()))
+            self._blocks.call(self.entry, dst, dst._obs, n_steps, *tail)      # (dst has src's seed, env_offset and n_traffic)
             if events:
                 events[1].record()
         self.first_episode += int(episodes)
@@ -451,7 +462,6 @@ class MonteCarlo:
         """records.monte_carlo_summary() of the accumulators (one read-back): per policy the episodes, the goal / collision /
         timeout counts and rates, the collision rate's Wilson 95 % interval, the loss-of-separation rate, mean steps, mean
         return and its standard error, the histogram and its edges; with baseline = k0 each policy's risk ratio against k0."""
-        from . import records
         out = records.monte_carlo_summary(self.accumulators(), baseline=baseline, hist_max=self.hist_max)
         if self.disturbance is not None:
             out["disturbance"] = self.disturbance.to_dict()
@@ -538,8 +548,6 @@ class EncounterSearch:
     def __init__(self, policies, n_candidates, seed=13, dtype=torch.float32, group=False, config=None, n_traffic=1, n_bins=8,
                  rho=0.1, alpha=0.7, p_floor=None, level=None, weighted=True, device="cuda:0", env_offset=0, n_quantile=None):
         import math
-        from . import native, records
-        from .config import ACAS2DConfig
         from .vec_env import ACAS2DVecEnv
         if not policies:
             raise ValueError("EncounterSearch needs at least one policy")
@@ -557,11 +565,10 @@ class EncounterSearch:
         self.generation = 0
         K, L, N, B = self.n_policies, self.n_candidates, int(self.config.n_traffic), self.n_bins
         self.n_coord = NC = 4 * (N + 1)
-        self._ep = EP = (L + 63) // 64 * 64
-        self._env = ACAS2DVecEnv(K * EP, N, device=device, dtype=dtype, seed=seed, env_offset=int(env_offset), auto_reset=True,
+        self.device = dev = torch.device(device)
+        self._blocks = PolicyBlocks(policies, L, self.config.obs_dim, dev)
+        self._env = ACAS2DVecEnv(K * self._blocks.EP, N, device=dev, dtype=dtype, seed=seed, env_offset=int(env_offset), auto_reset=True,
                                  config=self.config, keep_terminal_obs=False, double_buffer=False)
-        self.device = dev = self._env.device
-        self._weights = stack_policies(policies, self._env.obs_dim, dev)
         self.active = records.search_active_coordinates(self.config)
         flat = np.full((K, NC, B), 1.0 / B, np.float64)
         up = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(dev)  # noqa: E731
@@ -575,11 +582,10 @@ class EncounterSearch:
                  best_candidate=torch.full((K,), -1, dtype=torch.int32, device=dev), best_own_psi=z(K, dt=dtype),
                  best_traffic=z(K, N, 4, dt=dtype))
         self._history = z(8, K, native.SEARCH_HISTORY_WIDTH)
-        self._native = native
 
     def _struct(self, generation, tables=None, history=None):
         b, t = self._buf, tables or self._buf
-        return self._native.CEncounterSearch(
+        return native.CEncounterSearch(
             t["p"].data_ptr(), t["cdf"].data_ptr(), t["log_ratio"].data_ptr(), b["active"].data_ptr(), b["bins"].data_ptr(),
             b["log_w"].data_ptr(), b["elite_w"].data_ptr(), b["outcome"].data_ptr(), b["stats_f"][0].data_ptr(),
             (self._history[0] if history is None else history).data_ptr(), b["best_score"].data_ptr(),
@@ -588,17 +594,16 @@ class EncounterSearch:
             self.p_floor, self.level, int(generation))
 
     def _sample(self, cs):
-        v, nat = self._env, self._native
-        nat.check(getattr(nat.lib(), self.entries[0])(
+        v = self._env
+        native.check(getattr(native.lib(), self.entries[0])(
             C.byref(v._ccfg), C.byref(v._cstate), v.num_envs, self.n_policies, self.n_candidates, v.seed_value, v.env_offset,
             v.n_traffic, C.byref(cs), v._stream()))
 
     def _generation(self, events=None):
         """One generation's five launches.  `events`: four pairs of torch.cuda.Events around the sample, evaluate, select and
         refit launches (tools/bench_encounter_search.py)."""
-        v, nat, b, g = self._env, self._native, self._buf, self.generation
+        v, b, g, lib = self._env, self._buf, self.generation, native.lib()
         K, L = self.n_policies, self.n_candidates
-        lib = nat.lib()
         mark = (lambda i, j: events[i][j].record()) if events else (lambda i, j: None)
         with torch.cuda.device(self.device):
             if g >= self._history.shape[0]:                      # (a device copy: nothing waits for it)
@@ -610,22 +615,17 @@ class EncounterSearch:
             for k, t in self._drawn.items():
                 t.copy_(b[k])
             v._launch_reset(None, do_init=0)                     # the first observation, as of an injected state
-            sf, si = b["stats_f"], b["stats_i"]
-            cstats = nat.CEvalStats(sf[0].data_ptr(), si[0].data_ptr(), si[1].data_ptr(), sf[1].data_ptr(), sf[2].data_ptr(),
-                                    sf[3].data_ptr())
-            pw = nat.CPolicy(*[t.data_ptr() for t in self._weights], 64, 0)
+            cstats = self._blocks.c_eval_stats(b["stats_f"], b["stats_i"])
             mark(1, 0)
-            nat.check(getattr(lib, self.entries[1])(
-                C.byref(v._ccfg), C.byref(v._cstate), v.num_envs, C.byref(pw), K, L, v._obs.data_ptr(), self.config.max_steps + 1,
-                v.seed_value, v.env_offset, v.n_traffic, b["outcome"].data_ptr(), b["steps"].data_ptr(),
-                b["total_reward"].data_ptr(), C.byref(cstats), v._stream()))
+            self._blocks.call(self.entries[1], v, v._obs, self.config.max_steps + 1, b["outcome"].data_ptr(), b["steps"].data_ptr(),
+                              b["total_reward"].data_ptr(), cstats)
             mark(1, 1)
             mark(2, 0)
-            nat.check(getattr(lib, self.entries[2])(C.byref(v._ccfg), K, L, v.seed_value, v.env_offset, v.n_traffic, C.byref(cs),
-                                                    v._stream()))
+            native.check(getattr(lib, self.entries[2])(C.byref(v._ccfg), K, L, v.seed_value, v.env_offset, v.n_traffic, C.byref(cs),
+                                                       v._stream()))
             mark(2, 1)
             mark(3, 0)
-            nat.check(lib.acas2d_encounter_refit(C.byref(cs), K, L, v._stream()))
+            native.check(lib.acas2d_encounter_refit(C.byref(cs), K, L, v._stream()))
             mark(3, 1)
         self.generation = g + 1
 
@@ -647,7 +647,6 @@ class EncounterSearch:
         """records.search_estimate() of the log: per policy the probability of min_separation <= level under the reset
         distribution, per generation and averaged over the generations from first_generation on, with standard errors
         and effective sample sizes."""
-        from . import records
         return records.search_estimate(self.history(), self.n_candidates, first_generation)
 
     def proposal(self):
@@ -669,7 +668,7 @@ class EncounterSearch:
         drawn again from the kept tables by the sampler itself (the evaluation has stepped the arrays it wrote)."""
         if self.generation < 1:
             raise RuntimeError("candidates() before the first generation")
-        K, L, EP, v = self.n_policies, self.n_candidates, self._ep, self._env
+        K, L, EP, v = self.n_policies, self.n_candidates, self._blocks.EP, self._env
         with torch.cuda.device(self.device):
             self._sample(self._struct(self.generation - 1, tables=self._drawn))
         f = lambda t: t.detach().cpu().numpy()  # noqa: E731

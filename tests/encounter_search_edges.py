@@ -605,7 +605,7 @@ class Direct:
 
     def env(self):
         if self._env is None:
-            self.EP = (self.L + 63) // 64 * 64
+            self.EP = self.g.policy.PolicyBlocks.block_envs(self.L)
             self._env = self.g.ACAS2DVecEnv(K * self.EP, self.N, device=DEV, dtype=self.tdtype, config=self.config,
                                             keep_terminal_obs=False, double_buffer=False)
         return self._env

@@ -16,7 +16,6 @@ One warm-up of every variant, then --reps repetitions, the variants alternating 
 are printed, `spread` is (max - min) / median.  The accumulators of (a) are compared with (b)'s before anything is timed.
 usage: bench_monte_carlo.py [--cases ...] [--reps 5] [--out profiles/monte_carlo_timing.jsonl]"""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -28,7 +27,6 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import gym_acas2d_amd as g  # noqa: E402
-from gym_acas2d_amd import native  # noqa: E402
 
 DEV = "cuda:0"
 N_BINS = 64
@@ -53,12 +51,11 @@ class StatsLaunch:
     """evaluate_policies_fused(safety=True)'s launch on a state staged beforehand, so that HIP events see the kernel alone."""
 
     def __init__(self, pols, lanes, N, group):
-        K, EP = len(pols), (lanes + 63) // 64 * 64
-        self.K, self.L, self.N = K, lanes, N
-        self.v = g.ACAS2DVecEnv(K * EP, N, device=DEV, dtype=torch.float32, auto_reset=True)
-        self.idx = np.tile(np.concatenate([np.arange(lanes), np.zeros(EP - lanes, np.int64)]), K)
-        self.keep = g.policy.stack_policies(pols, self.v.obs_dim, self.v.device)
-        self.fn = getattr(native.lib(), g.policy.evaluate_policies_entry(torch.float32, group, True))
+        K = len(pols)
+        self.blocks = g.policy.PolicyBlocks(pols, lanes, 5 + 3 * N, DEV)
+        self.idx = self.blocks.index()
+        self.v = g.ACAS2DVecEnv(len(self.idx), N, device=DEV, dtype=torch.float32, auto_reset=True)
+        self.entry = g.policy.evaluate_policies_entry(torch.float32, group, True)
         new = lambda dt: torch.empty(K, lanes, dtype=dt, device=DEV)  # noqa: E731
         self.out = [new(torch.uint8), new(torch.int32), new(torch.float32)]
         self.st_f, self.st_i = torch.empty(4, K, lanes, device=DEV), torch.empty(2, K, lanes, dtype=torch.int32, device=DEV)
@@ -67,12 +64,8 @@ class StatsLaunch:
         self.v.set_state(own[self.idx], trf[self.idx], goal[self.idx], np.zeros(len(self.idx), np.int32), observe=True)
 
     def launch(self):
-        v, f, i = self.v, self.st_f, self.st_i
-        stats = native.CEvalStats(f[0].data_ptr(), i[0].data_ptr(), i[1].data_ptr(), f[1].data_ptr(), f[2].data_ptr(), f[3].data_ptr())
-        pw = native.CPolicy(*[t.data_ptr() for t in self.keep], 64, 0)
-        native.check(self.fn(C.byref(v._ccfg), C.byref(v._cstate), v.num_envs, C.byref(pw), self.K, self.L, v.outputs["obs"].data_ptr(),
-                             v.config.max_steps + 1, v.seed_value, v.env_offset, self.N, *[t.data_ptr() for t in self.out],
-                             C.byref(stats), v._stream()))
+        self.blocks.call(self.entry, self.v, self.v.outputs["obs"], self.v.config.max_steps + 1,
+                         *[t.data_ptr() for t in self.out], self.blocks.c_eval_stats(self.st_f, self.st_i))
 
 
 def events(fn):

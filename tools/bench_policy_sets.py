@@ -21,7 +21,6 @@ plain and stats are `--inner` launches per timed window.
     python tools/bench_policy_sets.py --safety [--reps 9] [--inner 10]
 """
 import argparse
-import ctypes as C
 import json
 import os
 import random
@@ -42,7 +41,6 @@ ap.add_argument("--dtype", choices=("float64", "float32"), default="float64")
 ap.add_argument("--safety", action="store_true", help="time acas2d_evaluate_policies_stats_* (see the docstring)")
 ap.add_argument("--inner", type=int, default=10, help="--safety: launches per timed window of the plain and stats arms")
 args = ap.parse_args()
-
 
 
 def timed(fn):
@@ -68,26 +66,20 @@ def safety_shape(N, E, K, group, reps, inner):
         with torch.no_grad():
             p.action_net.weight.mul_(40.0)
         pols.append(p)
-    EP = (E + 63) // 64 * 64
-    idx = np.tile(np.concatenate([np.arange(E), np.zeros(EP - E, np.int64)]), K)
-    venv = g.ACAS2DVecEnv(K * EP, N, device=dev, dtype=f32, auto_reset=True, config=cfg)
-    venv.set_state(own[idx], trf[idx], goal[idx], np.zeros(K * EP, np.int32), observe=True)
-    w = [torch.stack(ts) for ts in zip(*[g.policy.kernel_layout(*p.actor_weights(), device=dev) for p in pols])]
-    pw = g.native.CPolicy(*[t.data_ptr() for t in w], 64, 0)
+    blocks = g.policy.PolicyBlocks(pols, E, D, dev)
+    idx = blocks.index()
+    venv = g.ACAS2DVecEnv(len(idx), N, device=dev, dtype=f32, auto_reset=True, config=cfg)
+    venv.set_state(own[idx], trf[idx], goal[idx], np.zeros(len(idx), np.int32), observe=True)
     res = (torch.empty(K, E, dtype=torch.uint8, device=dev), torch.empty(K, E, dtype=torch.int32, device=dev),
            torch.empty(K, E, dtype=f32, device=dev))
     st_f, st_i = torch.empty(4, K, E, dtype=f32, device=dev), torch.empty(2, K, E, dtype=torch.int32, device=dev)
-    cstats = g.native.CEvalStats(st_f[0].data_ptr(), st_i[0].data_ptr(), st_i[1].data_ptr(), st_f[1].data_ptr(),
-                                 st_f[2].data_ptr(), st_f[3].data_ptr())
-    L = g.native.lib()
-    plain_fn = getattr(L, g.policy.evaluate_policies_entry(f32, group, False))
-    stats_fn = getattr(L, g.policy.evaluate_policies_entry(f32, group, True))
+    cstats = blocks.c_eval_stats(st_f, st_i)
+    plain_fn = g.policy.evaluate_policies_entry(f32, group, False)
+    stats_fn = g.policy.evaluate_policies_entry(f32, group, True)
 
     def launch(fn, *extra):
         for _ in range(inner):
-            g.native.check(fn(C.byref(venv._ccfg), C.byref(venv._cstate), K * EP, C.byref(pw), K, E,
-                              venv.outputs["obs"].data_ptr(), T, venv.seed_value, venv.env_offset, N,
-                              *[r.data_ptr() for r in res], *extra, venv._stream()))
+            blocks.call(fn, venv, venv.outputs["obs"], T, *[r.data_ptr() for r in res], *extra)
 
     # the replay arm: one rollout env and one latching env with traces, reused by every policy
     roll = g.ACAS2DVecEnv(E, N, device=dev, dtype=f32, auto_reset=True, config=cfg)
@@ -111,9 +103,9 @@ def safety_shape(N, E, K, group, reps, inner):
                 lat.step(out["actions"][t])
                 rows[t + 1] = lat.trace[:, cols]
 
-    arms = {"plain": lambda: launch(plain_fn), "stats": lambda: launch(stats_fn, C.byref(cstats)), "replay": replay}
+    arms = {"plain": lambda: launch(plain_fn), "stats": lambda: launch(stats_fn, cstats), "replay": replay}
     launch(plain_fn)
-    launch(stats_fn, C.byref(cstats))
+    launch(stats_fn, cstats)
     replay(measure_last=True)
     torch.cuda.synchronize()
     order, t = list(arms), {a: [] for a in arms}
@@ -124,12 +116,12 @@ def safety_shape(N, E, K, group, reps, inner):
     launch(plain_fn)
     torch.cuda.synchronize()
     base = [r.clone() for r in res]
-    launch(stats_fn, C.byref(cstats))
+    launch(stats_fn, cstats)
     torch.cuda.synchronize()
     same = all(torch.equal(a.view(torch.uint8), b.view(torch.uint8)) for a, b in zip(base, res))
     steps = res[1].cpu().numpy()
     med = {a: float(np.median(v)) for a, v in t.items()}
-    row = {"bench": "eval_stats", "n_traffic": N, "episodes": E, "policies": K, "entry": stats_fn.__name__, "dtype": "float32",
+    row = {"bench": "eval_stats", "n_traffic": N, "episodes": E, "policies": K, "entry": stats_fn, "dtype": "float32",
            "steps_budget": T, "reps": reps, "launches_per_window": inner,
            "method": "HIP events, warm-up first, arms interleaved in one process with rotating order; ms per launch "
                      "(replay: per K-policy pass, host reduction excluded)",
@@ -179,25 +171,17 @@ def run_singles():
 
 
 # the set: one launch on K x EP envs
-EP = (E + 63) // 64 * 64
-idx = np.tile(np.concatenate([np.arange(E), np.zeros(EP - E, np.int64)]), K)
-venv = g.ACAS2DVecEnv(K * EP, 1, device="cuda:0", dtype=dt, auto_reset=True)
-venv.set_state(own[idx], trf[idx], goal[idx], np.zeros(K * EP, np.int32), observe=True)
-w = [torch.stack([t for t in ws]).contiguous() for ws in zip(*[(p.actor_weights()[0].t(), p.actor_weights()[1],
-                                                                p.actor_weights()[2].t(), p.actor_weights()[3],
-                                                                p.actor_weights()[4].reshape(64),
-                                                                p.actor_weights()[5].reshape(1)) for p in pols])]
-w = [t.to("cuda:0") for t in w]
+blocks = g.policy.PolicyBlocks(pols, E, 8, "cuda:0")
+idx = blocks.index()
+venv = g.ACAS2DVecEnv(len(idx), 1, device="cuda:0", dtype=dt, auto_reset=True)
+venv.set_state(own[idx], trf[idx], goal[idx], np.zeros(len(idx), np.int32), observe=True)
 res = (torch.empty(K, E, dtype=torch.uint8, device="cuda:0"), torch.empty(K, E, dtype=torch.int32, device="cuda:0"),
        torch.empty(K, E, dtype=dt, device="cuda:0"))
-L = g.native.lib()
-fn = L.acas2d_evaluate_policies_f32 if dt == torch.float32 else L.acas2d_evaluate_policies_f64
-pw = g.native.CPolicy(*[t.data_ptr() for t in w], 64, 0)
+entry = g.policy.evaluate_policies_entry(dt)
 
 
 def run_set():
-    g.native.check(fn(C.byref(venv._ccfg), C.byref(venv._cstate), K * EP, C.byref(pw), K, E, venv.outputs["obs"].data_ptr(),
-                      T, venv.seed_value, venv.env_offset, 1, *[r.data_ptr() for r in res], venv._stream()))
+    blocks.call(entry, venv, venv.outputs["obs"], T, *[r.data_ptr() for r in res])
 
 
 def run_one_single():
