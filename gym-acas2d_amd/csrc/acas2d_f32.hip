@@ -16,6 +16,7 @@ template decltype(launch_collect_set_group<float>) launch_collect_set_group<floa
 ACAS2D_INSTANTIATE_SCORING
 // evaluation and campaign under sensor noise and actuator disturbance: float32 only, behind every other kernel of the unit
 ACAS2D_INSTANTIATE_SCORING_DISTURBED
+// (training under the same noise: the disturbed set collector is acas2d_collect_disturbed.hip)
 
 #ifdef ACAS2D_STAMPS
 extern "C" int acas2d_debug_set_stamps_f32(unsigned long long* buf) {

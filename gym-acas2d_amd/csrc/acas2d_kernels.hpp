@@ -1478,6 +1478,21 @@ __device__ __forceinline__ const DisturbW* disturbance_args(const PW& pw) {
         return &pw.dist;
     else return nullptr;
 }
+// DIST on top of Mode::CollectSet (acas2d_collect_set_disturbed_f32, acas2d_collect_set_disturbed_group_f32;
+// collect_set_disturbed_kernel): the collector under the same noise.  Both networks read the disturbed row, which the launch
+// also writes out (obs_read); the standard deviations are the MEMBER's, a row of a device float[K][4] that its waves load
+// next to its noise key, the seed is the launch's.  The counter is (global env, the env's own episode, steps, slot).
+struct CollectDistW {
+    const float* sigmas;                             // float[K][4]: sep, cpa, closing, action
+    void* obs_read;                                  // T[n_steps + 1][E][D]: the rows the networks read
+    uint32_t dk0, dk1;                               // the two halves of dist_seed
+};
+struct PolicyCollectDistW : PolicyW { CollectDistW dist; };
+template <typename PW>
+__device__ __forceinline__ const CollectDistW* collect_disturbance_args(const PW& pw) {
+    if constexpr (std::is_base_of<PolicyCollectDistW, PW>::value) return &pw.dist;
+    else return nullptr;
+}
 constexpr uint32_t kDisturbanceTag = 0x64697374u;    // "dist": keeps the blocks apart from the reset's under the same seed
 constexpr int kDisturbanceSlotShift = 20;            // counter word 3 = step | slot << 20
 // The normals of (lane, episode, step, slot): ONE Philox block, Box-Muller on 24-bit uniforms with the hardware's log, sqrt,
@@ -1794,6 +1809,21 @@ __global__ __launch_bounds__(kBlock) void monte_carlo_disturbed_kernel(const T* 
     constexpr Mode M = Mode::Eval;
 #include "acas2d_step_body.inl"
 }
+// step_kernel<..., Mode::CollectSet> with DIST (acas2d_collect_set_disturbed_f32, acas2d_collect_set_disturbed_group_f32): the
+// set collector whose two networks read the disturbed row and whose env flies the disturbed action (PolicyCollectDistW).  With
+// one member it is the solo collector.  A kernel of its own for the reason eval_stats_kernel is one; float32 only.
+// (PW is always PolicyCollectDistW: as a template parameter it keeps the body's evaluator statements, which name fields
+//  that struct does not have, dependent -- and so uncompiled -- here.)
+template <typename T, int C, int G, bool FAST, typename PW = PolicyCollectDistW>
+__global__ __launch_bounds__(kBlock) void collect_set_disturbed_kernel(const T* a0, const T* a1, const T* a2, const T* a3,
+                                                                       const T* a4, const T* a5, int32_t e_n_envs, int32_t tile_elems,
+                                                                       Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
+                                                                       StepIO<T> io_arg, uint32_t k0, uint32_t k1, int64_t env_offset,
+                                                                       int N_arg, int n_steps, PW pw) {
+    constexpr bool PACKED = true, STATS = false, MC = false, DIST = true;
+    constexpr Mode M = Mode::CollectSet;
+#include "acas2d_step_body.inl"
+}
 // acas2d_disturbance_draw_f32: the normals of n_steps x n_lanes x n_slots blocks as float[n_steps][n_lanes][n_slots][3]
 // (slot 0: the actuator's normal, then two zeros), one thread each, through disturbance_normals()
 template <typename T>
@@ -1922,6 +1952,12 @@ template <typename T>
 int launch_collect_set_group(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
                              int32_t n_members, const uint64_t* noise_seeds, const void* obs_in, int32_t n_steps, uint64_t seed,
                              int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream);
+// acas2d_collect_set_disturbed_f32 and, `group`, acas2d_collect_set_disturbed_group_f32 (float32 only; instantiated last)
+template <typename T>
+int launch_collect_set_disturbed(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
+                                 int32_t n_members, const uint64_t* noise_seeds, const void* obs_in, int32_t n_steps, uint64_t seed,
+                                 int64_t env_offset, int64_t n_envs, int32_t n_traffic, const float* sigmas, uint64_t dist_seed,
+                                 void* obs_read, hipStream_t stream, bool group);
 // the *_group entry points (float32: the double instantiations reject every traffic count)
 template <typename T>
 int launch_rollout_policy_group(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io,

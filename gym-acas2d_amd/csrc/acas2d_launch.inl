@@ -324,11 +324,13 @@ static int require_aligned(const char* name, std::initializer_list<const void*> 
     return ACAS2D_OK;
 }
 
-// The kernel of a launch: step_kernel in mode M, unless the launch's policy argument is one of the four that have a kernel
-// of their own (Mode::Eval with statistics, the Monte Carlo campaign, and the disturbed flavour of each; packed shapes)
+// The kernel of a launch: step_kernel in mode M, unless the launch's policy argument is one of the five that have a kernel
+// of their own (Mode::Eval with statistics, the Monte Carlo campaign, the disturbed flavour of each and the disturbed set
+// collector; packed shapes)
 template <typename PW, typename T, int C, int G, bool PACKED, bool FAST, Mode M>
 static constexpr auto kernel_for() {
-    if constexpr (std::is_same<PW, PolicyMonteCarloDistW>::value) return &monte_carlo_disturbed_kernel<T, C, G, FAST>;
+    if constexpr (std::is_same<PW, PolicyCollectDistW>::value) return &collect_set_disturbed_kernel<T, C, G, FAST>;
+    else if constexpr (std::is_same<PW, PolicyMonteCarloDistW>::value) return &monte_carlo_disturbed_kernel<T, C, G, FAST>;
     else if constexpr (std::is_same<PW, PolicyEvalStatsDistW>::value) return &eval_stats_disturbed_kernel<T, C, G, FAST>;
     else if constexpr (std::is_same<PW, PolicyMonteCarloW>::value) return &monte_carlo_kernel<T, C, G, FAST>;
     else if constexpr (std::is_same<PW, PolicyEvalStatsW>::value) return &eval_stats_kernel<T, C, G, FAST>;
@@ -470,14 +472,19 @@ int launch_collect_group(const Acas2dConfig* cfg, const Acas2dState* st, const A
 // EM = n_envs / K a multiple of the wave, so that the member is wave-uniform.  float32, one lane per env -- or, `group`
 // (acas2d_collect_set_group_f32), the env's G lanes together at the shapes of group_shape(): a wave then holds 64 / G envs,
 // and the same rule for EM keeps them one member's.
-template <typename T>
+// DIST (acas2d_collect_set_disturbed_f32, acas2d_collect_set_disturbed_group_f32; collect_set_disturbed_kernel): the same launch
+// under sensor and actuator noise, `cd` its three arguments.  One member then takes any n_envs >= 1: it is the solo collector.
+struct CollectDisturbance { const float* sigmas; uint64_t seed; void* obs_read; };
+template <typename T, bool DIST>
 static int collect_set(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
                        int32_t n_members, const uint64_t* noise_seeds, const void* obs_in, int32_t n_steps, uint64_t seed,
-                       int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream, bool group) {
+                       int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream, bool group,
+                       const CollectDisturbance& cd = CollectDisturbance{}) {
     static_assert(sizeof(T) == 4, "acas2d_collect_set: float32 only");
     static const char kScope[] = "float32, n_traffic in {1, 2, 3, 4, 8}; n_traffic 16 / 32 / 64 is acas2d_collect_set_group_f32, "
                                  "float64 collects one learner per call";
-    Launch<T> L{group ? "acas2d_collect_set_group" : "acas2d_collect_set", cfg, st, io, seed, env_offset, n_envs, n_traffic,
+    Launch<T> L{DIST ? (group ? "acas2d_collect_set_disturbed_group" : "acas2d_collect_set_disturbed")
+                     : (group ? "acas2d_collect_set_group" : "acas2d_collect_set"), cfg, st, io, seed, env_offset, n_envs, n_traffic,
                 n_steps, stream};
     L.group_policy = group;
     const auto inputs = [&] {
@@ -488,9 +495,23 @@ static int collect_set(const Acas2dConfig* cfg, const Acas2dState* st, const Aca
             return fail("%s: the value net's stacks, log_std, values and logp are required", L.name);
         if (!noise_seeds) return fail("%s: NULL noise_seeds (one 64-bit key per member, on the device)", L.name);
         if (n_members < 1) return fail("%s: n_members = %d (at least 1)", L.name, n_members);
-        if (n_envs >= 0 && (n_envs % n_members != 0 || (n_envs / n_members) % 64 != 0))
+        if (n_envs >= 0 && !(DIST && n_members == 1) && (n_envs % n_members != 0 || (n_envs / n_members) % 64 != 0))
             return fail("%s: n_envs = %lld is not n_members = %d x a multiple of 64 (a wavefront's envs belong to ONE member)",
                         L.name, (long long)n_envs, n_members);
+        if constexpr (DIST) {
+            if (!cd.sigmas || !cd.obs_read)
+                return fail("%s: NULL sigmas (float[n_members][4], on the device) or obs_read", L.name);
+            if (n_envs > 0 && n_steps >= 1 && n_traffic >= 1) {      // (else: rejected or empty below)
+                const uint64_t row = (uint64_t)n_envs * (uint64_t)(5 + 3 * (int64_t)n_traffic) * sizeof(T);
+                const uintptr_t w0 = (uintptr_t)cd.obs_read, w1 = w0 + (uintptr_t)(row * ((uint64_t)n_steps + 1u));
+                const auto meets = [&](const void* q, uint64_t bytes) { return w0 < (uintptr_t)q + (uintptr_t)bytes && (uintptr_t)q < w1; };
+                if (meets(io->obs, row * (uint64_t)n_steps) || meets(obs_in, row))
+                    return fail("%s: obs_read overlaps io->obs or obs_in (the true observations stay what they are)", L.name);
+            }
+            if ((int64_t)cfg->max_steps + 1 >= (1ll << kDisturbanceSlotShift))
+                return fail("%s: max_steps = %d (max_steps + 1 must stay below 2^%d, the step field of the noise counter)", L.name,
+                            cfg->max_steps, kDisturbanceSlotShift);
+        }
         return ACAS2D_OK;
     };
     const auto shape = [&](Shape* sh) {
@@ -507,7 +528,14 @@ static int collect_set(const Acas2dConfig* cfg, const Acas2dState* st, const Aca
                                                   ac->v2t, ac->vb2})) return rc;
         sample_with(pw, ac, (uint64_t)reinterpret_cast<uintptr_t>(noise_seeds));       // the kernel loads its member's key
         pw.member_stride = (uint32_t)(n_envs / n_members);
-        return launch_mode<Mode::CollectSet>(L, pw);
+        if constexpr (DIST) {
+            PolicyCollectDistW pd{};
+            static_cast<PolicyW&>(pd) = pw;
+            pd.dist = CollectDistW{cd.sigmas, cd.obs_read, (uint32_t)cd.seed, (uint32_t)(cd.seed >> 32)};
+            return launch_mode<Mode::CollectSet>(L, pd);
+        } else {
+            return launch_mode<Mode::CollectSet>(L, pw);
+        }
     };
     return prepare(L, Words{"cfg / io / actor-critic", kSizes, kNegative}, io && ac, inputs, shape, go);
 }
@@ -515,13 +543,23 @@ template <typename T>
 int launch_collect_set(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
                        int32_t n_members, const uint64_t* noise_seeds, const void* obs_in, int32_t n_steps, uint64_t seed,
                        int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream) {
-    return collect_set<T>(cfg, st, io, ac, n_members, noise_seeds, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream, false);
+    return collect_set<T, false>(cfg, st, io, ac, n_members, noise_seeds, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream,
+                                 false);
 }
 template <typename T>
 int launch_collect_set_group(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
                              int32_t n_members, const uint64_t* noise_seeds, const void* obs_in, int32_t n_steps, uint64_t seed,
                              int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream) {
-    return collect_set<T>(cfg, st, io, ac, n_members, noise_seeds, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream, true);
+    return collect_set<T, false>(cfg, st, io, ac, n_members, noise_seeds, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream,
+                                 true);
+}
+template <typename T>
+int launch_collect_set_disturbed(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
+                                 int32_t n_members, const uint64_t* noise_seeds, const void* obs_in, int32_t n_steps, uint64_t seed,
+                                 int64_t env_offset, int64_t n_envs, int32_t n_traffic, const float* sigmas, uint64_t dist_seed,
+                                 void* obs_read, hipStream_t stream, bool group) {
+    return collect_set<T, true>(cfg, st, io, ac, n_members, noise_seeds, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream,
+                                group, CollectDisturbance{sigmas, dist_seed, obs_read});
 }
 
 // what the disturbed entries check on top of their siblings (after them: cfg is there), and the kernels' view of the struct
@@ -700,6 +738,10 @@ int launch_disturbance_draw(uint64_t seed, int64_t first_lane, int32_t n_lanes, 
     template decltype(launch_evaluate_policies<Elem, Scoring::Disturbed>) launch_evaluate_policies<Elem, Scoring::Disturbed>; \
     template decltype(launch_monte_carlo<Elem, true>) launch_monte_carlo<Elem, true>; \
     template decltype(launch_disturbance_draw<Elem>) launch_disturbance_draw<Elem>; }
+// the disturbed set collector: the ONE instantiation of acas2d_collect_disturbed.hip, a unit of its own -- the float32 unit
+// ends with the kernels above, and every kernel of it keeps its place, its name and the local labels of its assembly
+#define ACAS2D_INSTANTIATE_COLLECT_DISTURBED \
+    namespace acas2d { template decltype(launch_collect_set_disturbed<Elem>) launch_collect_set_disturbed<Elem>; }
 
 template <typename T>
 int launch_reset(const Acas2dConfig* cfg, const Acas2dState* st, const uint8_t* mask, void* obs,
@@ -739,7 +781,9 @@ int shape_geometry(int64_t n_envs, int32_t n_traffic, int32_t* lanes, int32_t* p
     return ACAS2D_OK;
 }
 
-// the launchers of this unit's element type (acas2d_kernels.hpp declares them, acas2d_api.hip calls them)
+// the launchers of this unit's element type (acas2d_kernels.hpp declares them, acas2d_api.hip calls them); a unit that
+// defines ACAS2D_LAUNCHERS_BY_NAME instantiates the ones it names itself (acas2d_collect_disturbed.hip)
+#ifndef ACAS2D_LAUNCHERS_BY_NAME
 template decltype(launch_step<Elem>) launch_step<Elem>;
 template decltype(launch_rollout<Elem>) launch_rollout<Elem>;
 template decltype(launch_rollout_policy<Elem>) launch_rollout_policy<Elem>;
@@ -750,5 +794,6 @@ template decltype(launch_evaluate_policies<Elem, Scoring::Plain>) launch_evaluat
 template decltype(launch_reset<Elem>) launch_reset<Elem>;
 template decltype(shape_geometry<Elem>) shape_geometry<Elem>;
 template decltype(state_consecutive<Elem>) state_consecutive<Elem>;
+#endif
 
 }  // namespace acas2d

@@ -1,11 +1,15 @@
-// acas2d_step_body.inl -- the body of step_kernel, eval_stats_kernel, monte_carlo_kernel and the latter two's disturbed
-// flavours (acas2d_kernels.hpp, where the modes and what each one implies are described), included inside all five.  It
+// acas2d_step_body.inl -- the body of step_kernel, eval_stats_kernel, monte_carlo_kernel, the latter two's disturbed
+// flavours and the disturbed set collector (acas2d_kernels.hpp, where the modes and what each one implies are described),
+// included inside all six.  It
 // expects the including kernel's template parameters T, C, G, PACKED, FAST, M (or constants of those names), the constants
 // STATS, MC and DIST, and the kernel's arguments a0 .. a5,
 // e_n_envs, tile_elems, p_arg, rp_arg, s_arg, io_arg, k0, k1, env_offset, N_arg, n_steps, pw.
     constexpr bool AUTO_RESET = M != Mode::Latch, ROLLOUT = rollout_mode(M);
     constexpr bool POLICY = policy_mode(M), SAMPLE = sample_mode(M);
     constexpr bool ARENA = M == Mode::Arena, EVAL = M == Mode::Eval, SET = M == Mode::CollectSet;
+    // the disturbed set collector is held to two waves per SIMD (256 registers) with an actor AND a critic per lane: what need not
+    // be live across the two networks is formed or fetched again behind them (LEAN, below)
+    constexpr bool LEAN = DIST && SET;
     static_assert(!SET || (PACKED && sizeof(T) == 4 && (G == 1 || group_policy_shape(C, G))),
                   "set collection: float32, one lane per env or the group-cooperative shapes");
     static_assert(!ROLLOUT || PACKED, "rollout modes: packed shapes");
@@ -212,10 +216,19 @@
     uint64_t dist_lane = 0;
     (void)dist_lane;
     if constexpr (DIST) {
-        static_assert(EVAL && STATS && sizeof(T) == 4, "disturbances: the float32 stats evaluator and Monte Carlo kernel");
-        const uint32_t kp = __builtin_amdgcn_readfirstlane(e_wave32 / (uint32_t)pw.ep_stride);
-        dist_lane = (uint64_t)env_offset + (uint64_t)(e_wave32 - kp * (uint32_t)pw.ep_stride + (uint32_t)el);
+        static_assert(((EVAL && STATS) || (SET && SAMPLE)) && sizeof(T) == 4,
+                      "disturbances: the float32 stats evaluator, Monte Carlo kernel and set collector");
+        if constexpr (SET) {                              // the collector: the sampler's gid, the GLOBAL env index
+            dist_lane = (uint64_t)env_offset + (uint64_t)(e_wave32 + (uint32_t)el);
+        } else {
+            const uint32_t kp = __builtin_amdgcn_readfirstlane(e_wave32 / (uint32_t)pw.ep_stride);
+            dist_lane = (uint64_t)env_offset + (uint64_t)(e_wave32 - kp * (uint32_t)pw.ep_stride + (uint32_t)el);
+        }
     }
+    // DIST and SET (collect_set_disturbed_kernel): the member's four sigmas and the launch's noise key as the DisturbW the
+    // evaluator takes by value -- filled in the SET prologue below; its episode field is not used (the lane's own counts)
+    DisturbW set_dw{};
+    (void)set_dw;
     // STATS: the running statistics of the lane's episode (PolicyEvalStatsW)
     T st_min = T(1) / T(0), st_a_lat = T(0), st_dev = T(0), st_sum = T(0);
     int32_t st_min_step = 0, st_los = 0;
@@ -235,8 +248,13 @@
         const uint64_t* keys = reinterpret_cast<const uint64_t*>((uintptr_t)pw.nk0 | ((uintptr_t)pw.nk1 << 32));
         const uint64_t key = ((const uint64_t ACAS2D_AS4*)keys)[km];
         pw.nk0 = (uint32_t)key; pw.nk1 = (uint32_t)(key >> 32);
+        if constexpr (DIST) {                             // the member's row of float[K][4]: sep, cpa, closing, action
+            const CollectDistW* const cw = collect_disturbance_args(pw);
+            const float ACAS2D_AS4* const sg = (const float ACAS2D_AS4*)cw->sigmas + 4 * (size_t)km;
+            set_dw = DisturbW{sg[0], sg[1], sg[2], sg[3], cw->dk0, cw->dk1, 0u};
+        }
     }
-    for (int t = 0; t < T_steps; ++t) {
+    for (int t = 0; t < T_steps + ((DIST && SET) ? 1 : 0); ++t) {      // (DIST && SET: one pass more, for obs_read[n_steps])
         // (MC: the running minimum stays an ordinary register over the loop.  Left alone, the float64 FAST kernels at
         //  N = 2, 3, 4 keep its +inf start in an accumulation register pair and count that as a spill.)
         if constexpr (MC) asm volatile("" : "+v"(st_min));
@@ -249,6 +267,7 @@
         const bool last = !ROLLOUT || t == T_steps - 1;
         uint8_t oc = 0;
         T action = action_next;
+        int el_st = el;                                   // the env index the step's STORES use
         if constexpr (POLICY) {
             constexpr int DP = 5 + 3 * NS;                // compile-time obs width (packed shapes)
             if constexpr (DIST) {
@@ -258,9 +277,9 @@
                 // perturbed in x[] below, the 5 + 3 N inputs are all live across the Philox chains where the network
                 // otherwise fetches them as it goes, and the N = 8 kernels need 293 and 306 VGPRs -- one wave per SIMD
                 // where their siblings (225, 252) keep two.  Through the tile they need 250 and 251.
-                const DisturbW* const dw = disturbance_args(pw);
+                const DisturbW* const dw = SET ? &set_dw : disturbance_args(pw);
                 if (dw->s_sep != 0.0f || dw->s_cpa != 0.0f || dw->s_closing != 0.0f) {      // (wave-uniform)
-                    const uint32_t d_ep = MC ? episode : dw->episode;
+                    const uint32_t d_ep = (MC || SET) ? episode : dw->episode;
 #pragma unroll
                     for (int k = 0; k < C; ++k) {
                         const int n = j * C + k;
@@ -272,6 +291,21 @@
                         e[2] = disturbed(e[2], dw->s_closing, z2, -1.0f, 1.0f);
                     }
                     wave_lds_fence();                      // the disturbed rows are complete
+                }
+                if constexpr (SET) {
+                    // obs_read[t]: the rows both networks read at this step, as they stand in the tile (a NaN stays one:
+                    // the scrub to 0 is the networks' own), with the coalesced flush of the step's end.  Row n_steps is the
+                    // tile the last step left, fresh rows of just-reset envs included, under the draw the NEXT launch's
+                    // first step makes from the same (episode, steps): the loop's one extra pass ends here.
+                    const CollectDistW* const cw = collect_disturbance_args(pw);
+                    wave_lds_fence();                      // every row of the tile is complete (zero sigmas: no fence above)
+                    constexpr int kChunks = (EPW * DP * (int)sizeof(T) / 16 + 63) / 64;
+                    int lane_f = lane;                     // (a fresh value: no per-lane address kept from the loop's front)
+                    asm volatile("" : "+v"(lane_f));
+                    flush_tile_unrolled<T, kChunks>(tile, static_cast<T*>(cw->obs_read) + ((int64_t)t * n_envs + e_wave) * D,
+                                                    n_rows * D, lane_f);
+                    if (t == T_steps) break;
+                    wave_lds_fence();                      // the flush's reads precede observe()'s row writes
                 }
             }
             float x[G == 1 ? DP : 1];
@@ -299,6 +333,15 @@
                     mean = policy_mlp<DP>(pw_t.w1t, pw_t.b1, pw_t.w2t, pw_t.b2, pw_t.w3, pw_t.b3, x);
                     asm volatile("" : "+s"(pw_t.v1t), "+s"(pw_t.vb1), "+s"(pw_t.v2t), "+s"(pw_t.vb2), "+s"(pw_t.v3), "+s"(pw_t.vb3),
                                       "+s"(pw_t.log_std));
+                    if constexpr (LEAN) {                 // the critic's inputs from the tile again: not live across the actor
+                        const T* row_c = row;
+                        asm volatile("" : "+v"(row_c));
+#pragma unroll
+                        for (int i = 0; i < DP; ++i) {
+                            const float xi = (float)row_c[i];
+                            x[i] = (xi == xi && fabsf(xi) < __builtin_inff()) ? xi : 0.0f;
+                        }
+                    }
                     value = policy_mlp<DP>(pw_t.v1t, pw_t.vb1, pw_t.v2t, pw_t.vb2, pw_t.v3, pw_t.vb3, x);
                 } else {
                     mean = policy_mlp_shared<DP, G, true>(pw_t.w1t, pw_t.b1, pw_t.w2t, pw_t.b2, pw_t.w3, pw_t.b3,
@@ -309,6 +352,9 @@
                                                            reinterpret_cast<const float*>(tile), hid, lane);
                     wave_lds_fence();                     // the row has been read: observe() rewrites it below
                 }
+                // DIST: the stores' index is a fresh value behind the networks.  Left alone, hipcc forms the ~13 per-lane
+                // 64-bit store addresses of a step in front of the step loop and keeps them (26 registers) across both networks.
+                if constexpr (LEAN) asm volatile("" : "+v"(el_st));
                 const float log_std = ((const float ACAS2D_AS4*)pw_t.log_std)[0];
                 // eps ~ N(0, 1): one Philox block per (global env, noise step + t), Box-Muller on two 24-bit uniforms
                 const uint64_t gid = (uint64_t)(env_offset + e_wave + el);
@@ -320,11 +366,18 @@
                 const float raw = fmaf(__builtin_amdgcn_exp2f(log_std * 1.4426950408889634f), eps, mean);
                 const float logp = fmaf(-0.5f * eps, eps, -log_std) - 0.9189385332046727f;                      // - log sqrt(2 pi)
                 if (active && j == 0) {                   // (group-uniform values: the group's first lane stores them)
-                    (static_cast<T*>(pw.actions_out) + e_wave + te)[el] = (T)raw;      // the buffer keeps the RAW action,
-                    (static_cast<T*>(pw.values_out) + e_wave + te)[el] = (T)value;     // the env sees the clipped one
-                    (static_cast<T*>(pw.logp_out) + e_wave + te)[el] = (T)logp;
+                    (static_cast<T*>(pw.actions_out) + e_wave + te)[el_st] = (T)raw;      // the buffer keeps the RAW action,
+                    (static_cast<T*>(pw.values_out) + e_wave + te)[el_st] = (T)value;     // the env sees the clipped one
+                    (static_cast<T*>(pw.logp_out) + e_wave + te)[el_st] = (T)logp;
                 }
                 action = (T)fminf(fmaxf(raw, -1.0f), 1.0f);
+                if constexpr (DIST) {                     // actuator noise: the environment's, not the policy's -- the buffer
+                    if (set_dw.s_action != 0.0f) {        // keeps raw and its logp; slot 0 on the clipped action, clipped again
+                        float z0, z1, z2;                 // (wave-uniform)
+                        disturbance_normals(set_dw.k0, set_dw.k1, dist_lane, episode, (uint32_t)steps, 0u, z0, z1, z2);
+                        action = (T)disturbed((float)action, set_dw.s_action, z0, -1.0f, 1.0f);
+                    }
+                }
             } else {
                 if constexpr (G == 1) {
                     action = (T)policy_action<DP>(pw_t, x);
@@ -349,6 +402,16 @@
         }
         if (run) {
             if (t == 0) ACAS2D_STAMP(2, wave, lane, true);
+            if constexpr (LEAN) {
+                // the traffic's headings and speeds change at a reset only, where the lane stores them: fetched again behind
+                // the networks (its own stores, in program order) instead of held across them -- 2 C registers
+                int el_r = el_l;
+                asm volatile("" : "+v"(el_r));
+                using V = Vec<T, C>;
+                const int i0 = el_r * N + j * C;
+                tr.psi = *reinterpret_cast<const V*>(s.trf_psi + i0);
+                tr.v = *reinterpret_cast<const V*>(s.trf_v + i0);
+            }
 
             // game.py:225 + aircraft.py:16-26 for the player
             o.a_lat = action * p.acc_lat_limit;
@@ -377,7 +440,7 @@
                 if constexpr (STATS) d_sep = minimum_separation<T, C, G, PACKED>(s, o, tr, el, j, N);   // every lane: it shuffles
             };
             Seen<T> r = observe<T, C, G, PACKED, FAST>(p, s, o, el, j, N, steps, !frozen, tr, row, !EVAL && last && active,
-                                                       ROLLOUT ? &trig : nullptr, before_traffic);
+                                                       (ROLLOUT && !LEAN) ? &trig : nullptr, before_traffic);
 
             // game.py:249-292 evaluate()
             T rw = step_reward_5<T, FAST>(p, r.v_closing0, o.psi, r.h_goal, r.d_cpa0, r.d_goal, r.d_dev);
@@ -453,9 +516,9 @@
                     running = false;
                 }
             } else if (j == 0 && active) {
-                io.reward[el] = rw;                       // (plain stores: non-temporal measured the same, 0.6 MB)
-                io.done[el] = (uint8_t)(oc != 0);
-                io.outcome[el] = oc;
+                io.reward[el_st] = rw;                    // (plain stores: non-temporal measured the same, 0.6 MB)
+                io.done[el_st] = (uint8_t)(oc != 0);
+                io.outcome[el_st] = oc;
                 if constexpr (!HANDOFF) {
                     if (last && (oc == 0 || !AUTO_RESET)) {
                         put_env(s, s.own_x, el, o.x); put_env(s, s.own_y, el, o.y); put_env(s, s.own_psi, el, o.psi);
@@ -496,8 +559,8 @@
                         const int k_own = __popcll(taken & ((1ull << (el * G)) - 1ull));
                         const T* scr = scratch + k_own * SL::STRIDE;
                         if (j == 0) {
-                            if (io_r.ep_return) io_r.ep_return[el] = total;
-                            if (io_r.ep_steps) io_r.ep_steps[el] = steps;
+                            if (io_r.ep_return) io_r.ep_return[el_st] = total;
+                            if (io_r.ep_steps) io_r.ep_steps[el_st] = steps;
                         }
                         using V = Vec<T, C>;              // the slot's blocks are aligned like the live traffic block
                         tr.x = *reinterpret_cast<const V*>(scr + j * C);
@@ -513,7 +576,7 @@
                         fresh = true;
                         trig.valid = false; trig.dirty = false;   // new headings (stored below)
                         if constexpr (!MC) {
-                            const int i0 = el * N + j * C;
+                            const int i0 = el_st * N + j * C;
                             put_trf<T, C>(s, s.trf_x, i0, tr.x); put_trf<T, C>(s, s.trf_y, i0, tr.y);
                             *reinterpret_cast<V*>(s.trf_psi + i0) = tr.psi; *reinterpret_cast<V*>(s.trf_v + i0) = tr.v;
                         }
@@ -532,8 +595,8 @@
                 wave_lds_fence();                         // the fresh row and the scratch are complete
                 if (el == el_d) {                         // the owner group continues with the new episode
                     if (j == 0) {
-                        if (io_r.ep_return) io_r.ep_return[el] = total;
-                        if (io_r.ep_steps) io_r.ep_steps[el] = steps;
+                        if (io_r.ep_return) io_r.ep_return[el_st] = total;
+                        if (io_r.ep_steps) io_r.ep_steps[el_st] = steps;
                     }
 #pragma unroll
                     for (int k = 0; k < C; ++k) {
@@ -550,7 +613,7 @@
                     // the new traffic block: whole 16-byte vectors from the owner lanes
                     using V = Vec<T, C>;
                     if constexpr (!MC) {
-                        const int i0 = el * N + j * C;
+                        const int i0 = el_st * N + j * C;
                         put_trf<T, C>(s, s.trf_x, i0, tr.x); put_trf<T, C>(s, s.trf_y, i0, tr.y);
                         *reinterpret_cast<V*>(s.trf_psi + i0) = tr.psi; *reinterpret_cast<V*>(s.trf_v + i0) = tr.v;
                     }
@@ -569,8 +632,8 @@
                             *reinterpret_cast<T*>(c + (size_t)((ie + 2u * E32) * 4u)) = o.gy;
                         }
                     } else {
-                        s.episode[el] = episode;
-                        if (!same_consts) { s.own_v[el] = o.v; s.goal_x[el] = o.gx; s.goal_y[el] = o.gy; }
+                        s.episode[el_st] = episode;
+                        if (!same_consts) { s.own_v[el_st] = o.v; s.goal_x[el_st] = o.gx; s.goal_y[el_st] = o.gy; }
                     }
                 }
                 if (last || fresh) {
@@ -586,9 +649,9 @@
                         __builtin_nontemporal_store(steps, reinterpret_cast<int32_t*>(mw + (size_t)((ie + 4u * E32) * 4u)));
                         __builtin_nontemporal_store(total, reinterpret_cast<T*>(mw + (size_t)((ie + 3u * E32) * 4u)));
                     } else {
-                        put_env(s, s.own_x, el, o.x); put_env(s, s.own_y, el, o.y); put_env(s, s.own_psi, el, o.psi);
-                        put_env(s, s.steps, el, steps);
-                        put_env(s, s.total_reward, el, total);
+                        put_env(s, s.own_x, el_st, o.x); put_env(s, s.own_y, el_st, o.y); put_env(s, s.own_psi, el_st, o.psi);
+                        put_env(s, s.steps, el_st, steps);
+                        put_env(s, s.total_reward, el_st, total);
                     }
                 }
             }
@@ -598,7 +661,9 @@
             wave_lds_fence();
             if constexpr (PACKED) {
                 constexpr int kChunks = (EPW * (5 + 3 * NS) * (int)sizeof(T) / 16 + 63) / 64;
-                flush_tile_unrolled<T, kChunks>(tile, obs_wave, n_rows * D, lane);
+                int lane_f = lane;
+                if constexpr (LEAN) asm volatile("" : "+v"(lane_f));
+                flush_tile_unrolled<T, kChunks>(tile, obs_wave, n_rows * D, lane_f);
             } else {
                 flush_tile<T>(tile, obs_wave, n_rows * D, lane);
             }

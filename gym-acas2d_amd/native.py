@@ -156,7 +156,8 @@ EXPORTS = ("acas2d_abi_version", "acas2d_config_size", "acas2d_state_size", "aca
            "acas2d_encounter_sample_f64", "acas2d_encounter_select_f32", "acas2d_encounter_select_f64", "acas2d_encounter_refit",
            "acas2d_encounter_search_size", "acas2d_disturbance_size", "acas2d_evaluate_policies_disturbed_f32",
            "acas2d_evaluate_policies_disturbed_group_f32", "acas2d_monte_carlo_disturbed_f32",
-           "acas2d_monte_carlo_disturbed_group_f32", "acas2d_disturbance_draw_f32")
+           "acas2d_monte_carlo_disturbed_group_f32", "acas2d_disturbance_draw_f32", "acas2d_collect_set_disturbed_f32",
+           "acas2d_collect_set_disturbed_group_f32")
 
 
 class NativeLibraryError(RuntimeError):
@@ -254,6 +255,13 @@ def lib():
         f.restype = C.c_int
         f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.POINTER(CStepIO), C.POINTER(CActorCritic), C.c_int32,
                       C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]
+    # ... under sensor noise and actuator disturbance: then sigmas (device float[K][4]), dist_seed, obs_read, the stream
+    for name in ("acas2d_collect_set_disturbed_f32", "acas2d_collect_set_disturbed_group_f32"):
+        f = getattr(L, name)
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.POINTER(CStepIO), C.POINTER(CActorCritic), C.c_int32,
+                      C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_uint64,
+                      C.c_void_p, C.c_void_p]
     for name in ("acas2d_ppo_update_set_f32", "acas2d_ppo_update_wide_set_f32"):
         f = getattr(L, name)
         f.restype = C.c_int

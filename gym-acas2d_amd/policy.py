@@ -14,6 +14,7 @@ mean action clipped to [-1, 1].
 import ctypes as C
 import dataclasses
 import io
+import math
 import os
 import zipfile
 
@@ -231,8 +232,70 @@ class Disturbance:
     def from_dict(cls, d):
         return cls.normalised(d["s_sep"], d["s_cpa"], d["s_closing"], d["s_action"], d["seed"])
 
+    @classmethod
+    def parse(cls, text, normalised=False, config=None):
+        """A Disturbance from the command-line syntax of tools/evaluate_checkpoints.py and tools/train_ppo.py,
+        "sep=..,cpa=..,closing=..,action=..[,seed=..]": every key optional (0), in the constructor's units (pixels, the units
+        of v_closing, action units) or, normalised=True, in normalised observation units.  ValueError on anything else."""
+        kw = {}
+        for item in str(text).split(","):
+            key, _, val = (part.strip() for part in item.partition("="))
+            if key not in ("sep", "cpa", "closing", "action", "seed") or not val or key in kw:
+                raise ValueError("disturbance %r: %r (sep=, cpa=, closing=, action= and seed= are understood, each once)"
+                                 % (text, item))
+            try:
+                kw[key] = int(val, 0) if key == "seed" else float(val)
+            except ValueError:
+                raise ValueError("disturbance %r: %r is no number" % (text, item)) from None
+        return cls.normalised(**kw) if normalised else cls(config=config, **kw)
+
     def to_c(self, noise_episode=0):
         return native.CDisturbance(self.s_sep, self.s_cpa, self.s_closing, self.s_action, self.seed, int(noise_episode), 0)
+
+
+class DisturbanceSet:
+    """The disturbances K learners train under (ACAS2DVecEnv.collect(disturbance=) / collect_set(disturbances=), the
+    trainers): one Disturbance for all members or K of them with EQUAL seeds -- the collector takes one noise seed per
+    launch and a row of four standard deviations per member.  The rows live on the device, where the C entry cannot look
+    at them, so they are checked HERE: each finite and at least 0.
+      rows          float32 [K, 4]: (s_sep, s_cpa, s_closing, s_action) per member;  seed: the launch's noise seed
+      members       the K Disturbances
+      state_dict()  plain numbers for a trainer's state and the file saved beside its zips; load_state_dict() refuses a
+                    state that names another disturbance: a run goes on under the noise it was started with."""
+
+    def __init__(self, disturbances, n_members=1):
+        K = int(n_members)
+        ds = [disturbances] * K if isinstance(disturbances, Disturbance) else list(disturbances)
+        if not all(isinstance(d, Disturbance) for d in ds):
+            raise TypeError("a Disturbance, or one per member, is required, got %r" % (disturbances,))
+        if len(ds) != K:
+            raise ValueError("one Disturbance, or one per member, is required: got %d for %d member(s)" % (len(ds), K))
+        for k, d in enumerate(ds):
+            for name in ("s_sep", "s_cpa", "s_closing", "s_action"):
+                v = getattr(d, name)
+                if not (v >= 0.0 and math.isfinite(v)):
+                    raise ValueError("member %d: %s = %r (every standard deviation must be finite and at least 0)" % (k, name, v))
+        if len({d.seed for d in ds}) != 1:
+            raise ValueError("the members' disturbances need EQUAL seeds (one noise seed per launch: an env's noise depends "
+                             "on its global index, not on its member), got %s" % [d.seed for d in ds])
+        self.members, self.seed = tuple(ds), ds[0].seed
+        self.rows = np.asarray([[d.s_sep, d.s_cpa, d.s_closing, d.s_action] for d in ds], np.float32)
+
+    def __len__(self):
+        return len(self.members)
+
+    def is_zero(self):
+        return all(d.is_zero() for d in self.members)
+
+    def state_dict(self):
+        return {"members": [d.to_dict() for d in self.members]}
+
+    def load_state_dict(self, sd):
+        other = None if sd is None else [Disturbance.from_dict(d) for d in sd["members"]]
+        if other is None or tuple(other) != self.members:
+            raise ValueError("load_state_dict: the state was saved under the disturbance %s, this run trains under %s -- "
+                             "a run goes on under the noise it was started with" % (
+                                 None if other is None else [d.to_dict() for d in other], [d.to_dict() for d in self.members]))
 
 
 def disturbance_draw(seed, first_lane, n_lanes, episode, first_step, n_steps, n_slots, device="cuda:0"):

@@ -34,6 +34,7 @@ the workspace, hyper_row(), the struct of the set entries, the target_kl guard, 
 policy.kernel_layout() the network as every kernel reads it.
 """
 import dataclasses
+import json
 import math
 import os
 import random
@@ -732,10 +733,13 @@ class _Callbacks:
     """learn()'s EvalCallback / CheckpointCallback bookkeeping for ONE learner, whose files go under `save_dir` and whose
     ActorCritic `policy()` gives when one is saved; `head` opens every record (a population's {"member": k}).  With
     reward normalisation on, `reward_norm()` gives the learner's RewardNormalizer.state_dict(), saved beside every zip:
-    best_model_reward_norm.pt, checkpoints/reward_norm_<num_timesteps>_steps.pt (the zips are SB3's, untouched)."""
+    best_model_reward_norm.pt, checkpoints/reward_norm_<num_timesteps>_steps.pt (the zips are SB3's, untouched).  A
+    learner that trains under a disturbance passes it as `disturbance` (Disturbance.to_dict()'s numbers): saved likewise
+    as best_model_disturbance.json, checkpoints/disturbance_<num_timesteps>_steps.json."""
 
-    def __init__(self, save_dir, policy, head=(), reward_norm=None):
+    def __init__(self, save_dir, policy, head=(), reward_norm=None, disturbance=None):
         self.save_dir, self.policy, self.head, self.reward_norm = save_dir, policy, dict(head), reward_norm
+        self.disturbance = disturbance
         self.evals = {"timesteps": [], "results": [], "ep_lengths": []}
         self.best = -math.inf
 
@@ -761,13 +765,20 @@ class _Callbacks:
                 save_sb3_policy(self.policy(), os.path.join(self.save_dir, "best_model.zip"))
                 if self.reward_norm is not None:
                     torch.save(self.reward_norm(), os.path.join(self.save_dir, "best_model_reward_norm.pt"))
+                self._save_disturbance(os.path.join(self.save_dir, "best_model_disturbance.json"))
         return rec
+
+    def _save_disturbance(self, path):
+        if self.disturbance is not None:
+            with open(path, "w") as f:
+                json.dump(self.disturbance, f)
 
     def checkpoint(self, timesteps):
         from .policy import save_sb3_policy
         save_sb3_policy(self.policy(), os.path.join(self.save_dir, "checkpoints", "model_%d_steps.zip" % timesteps))
         if self.reward_norm is not None:
             torch.save(self.reward_norm(), os.path.join(self.save_dir, "checkpoints", "reward_norm_%d_steps.pt" % timesteps))
+        self._save_disturbance(os.path.join(self.save_dir, "checkpoints", "disturbance_%d_steps.json" % timesteps))
 
 
 def minibatch_buffers(n, batch_size, device, lead=()):
@@ -810,12 +821,19 @@ class _Trainer:
 
     def _store_collection(self, out):
         """A fused collector's dict (ACAS2DVecEnv.collect / collect_set) into the buffers and `self.obs`, cast to float32
-        first and then cleaned of NaN.  Returns the NaN events per sample, int64 [T, E]."""
+        first and then cleaned of NaN.  Returns the NaN events per sample, int64 [T, E].  A disturbed collection
+        ("obs_read" in the dict): b_obs holds the rows the networks READ, `obs_boot` the row the bootstrap value is of;
+        `self.obs` stays the true observation."""
         T = self.b_obs.shape[0]
         obs_all, rew = out["obs"].to(torch.float32), out["reward"].to(torch.float32)
         nan = torch.isnan(rew).to(torch.int64) + torch.isnan(obs_all[1:]).any(-1)
         obs_all = torch.nan_to_num(obs_all, nan=0.0, posinf=0.0, neginf=0.0)    # what the kernel fed the networks
-        self.b_obs.copy_(obs_all[:T])
+        if out.get("obs_read") is not None:
+            read = torch.nan_to_num(out["obs_read"].to(torch.float32), nan=0.0, posinf=0.0, neginf=0.0)
+            self.b_obs.copy_(read[:T])
+            self.obs_boot.copy_(read[T])
+        else:
+            self.b_obs.copy_(obs_all[:T])
         self.obs.copy_(obs_all[T])
         self.b_act.copy_(out["actions"].to(torch.float32).unsqueeze(-1))
         self.b_val.copy_(out["values"].to(torch.float32))
@@ -827,13 +845,43 @@ class _Trainer:
         self.b_outcome.copy_(out["outcome"])
         return nan
 
-    def _evaluate_rows(self, policies, group, n_episodes, rng):
+    def _evaluate_rows(self, policies, group, n_episodes, rng, disturbance=None):
         """evaluate_policies_fused() of `policies` on `n_episodes` fresh episodes drawn from `rng`: rows = policies."""
         from . import reset_parity
         from .policy import evaluate_policies_fused
         own, trf, goal = reset_parity.draw_episodes(self.venv.config, n_episodes, rng)
         return evaluate_policies_fused(policies, own, trf, goal, dtype=self.venv.dtype, device=self.device,
-                                       config=self.venv.config, group=group)
+                                       config=self.venv.config, group=group,
+                                       **({} if disturbance is None else {"disturbance": disturbance}))
+
+    disturbances = None                                   # a DisturbanceSet: the trainer collects under it
+
+    def _set_disturbances(self, disturbances, n_members, who):
+        """The trainer's `disturbances` (a DisturbanceSet, or None) from its argument: checked here, before any launch."""
+        from .policy import DisturbanceSet
+        if disturbances is None:
+            return
+        if getattr(self.venv, "dtype", torch.float32) != torch.float32:
+            raise ValueError("%s: training under a disturbance is float32 only, this env is %s" % (who, self.venv.dtype))
+        self.disturbances = (disturbances if isinstance(disturbances, DisturbanceSet)
+                             else DisturbanceSet(disturbances, n_members))
+        if len(self.disturbances) != n_members:
+            raise ValueError("%s: %d disturbances for %d member(s)" % (who, len(self.disturbances), n_members))
+
+    def state_dict(self):
+        """What of a run lies neither in the policy zips nor in the reward normaliser's state: the disturbance it trains
+        under ({"disturbance": None} without one)."""
+        return {"disturbance": None if self.disturbances is None else self.disturbances.state_dict()}
+
+    def load_state_dict(self, sd):
+        """Refuses a state saved under another disturbance (or under none, or one where this run has none)."""
+        saved = sd.get("disturbance")
+        if self.disturbances is None:
+            if saved is not None:
+                raise ValueError("load_state_dict: the state was saved under the disturbance %s, this run trains under none"
+                                 % (saved,))
+            return
+        self.disturbances.load_state_dict(saved)
 
     def _learn(self, total_timesteps, log, books, history, iterate, evaluate, eval_every, checkpoint_every):
         """learn() for the learners whose bookkeeping `books` holds (one _Callbacks each): iterate() runs one iteration
@@ -906,10 +954,18 @@ class PPOTrainer(_Trainer):
     RewardNormalizer; with collector="fused" only.  collect() then normalises b_rew in place (one RewardNormalizer.normalize
     call) before GAE, so GAE, the update and clip_range_vf see normalised rewards; episode returns (b_epret) and evaluate()
     stay raw, update()'s statistics gain reward_std, and learn() saves the normaliser's state beside every zip.  It is an
-    env wrapper in SB3, not a hyper-parameter: PPOConfig has no field for it.  None: the calls issued are the same."""
+    env wrapper in SB3, not a hyper-parameter: PPOConfig has no field for it.  None: the calls issued are the same.
+    disturbance: None or a policy.Disturbance -- train under white sensor noise and actuator disturbance, with
+    collector="fused" only (ACAS2DVecEnv.collect(disturbance=): the noise is drawn inside that launch; the other collectors
+    have no such step).  The actor AND the critic read the disturbed rows, b_obs holds exactly those, b_act the raw draws
+    (actuator noise is the environment's), and the bootstrap value is the critic's on the disturbed row the next
+    collection's first step reads: torch's forward of it, or with gae="kernel" at n_traffic 1, 2, 3, 4, 8 gae_fused's own
+    critic on obs_last = that row (then the bits of the next values[0]).  It is part of the env, as reward_norm is: it goes
+    into state_dict() and beside every saved zip, and evaluate(disturbance=) scores under any other.  A zero Disturbance
+    trains the undisturbed run bit for bit (gae="kernel" aside, whose bootstrap value is then the kernel's)."""
 
     def __init__(self, venv, config=None, policy=None, use_graphs=None, collector=None, updater=None, gae=None,
-                 diagnostics=False, reward_norm=None):
+                 diagnostics=False, reward_norm=None, disturbance=None):
         self.venv = venv
         self.cfg = config or PPOConfig()
         torch.manual_seed(self.cfg.seed)
@@ -920,6 +976,12 @@ class PPOTrainer(_Trainer):
         if self.collector not in ("graphs", "fused", "eager") or (self.collector != "eager" and not self.use_graphs):
             raise ValueError("collector %r needs use_graphs" % (self.collector,))
         self._fused_out = None
+        if disturbance is not None and not (self.use_graphs and self.collector == "fused"):
+            raise ValueError("disturbance (training under sensor and actuator noise) is supported with use_graphs and "
+                             "collector='fused' only: the noise is drawn inside the fused collection launch, the captured and "
+                             "the op-by-op collectors have no such step; got use_graphs=%r, collector=%r"
+                             % (self.use_graphs, self.collector))
+        self._set_disturbances(disturbance, 1, "PPOTrainer")
         if self.collector == "graphs" and getattr(venv, "double_buffer", False):
             # ONE captured env step is replayed n_steps times: every replay must read what the previous one wrote,
             # which the double-buffered step (read generation g, write 1 - g) does not give a single-step graph
@@ -968,6 +1030,8 @@ class PPOTrainer(_Trainer):
         self.opt = torch.optim.Adam(self.policy.parameters(), lr=self.cfg.learning_rate, eps=1e-5,
                                     capturable=self.use_graphs, **({"fused": True} if self.use_graphs else {}))
         self.obs = venv.reset().to(torch.float32).clone()
+        # the row the bootstrap value is taken on: the observation itself, or (disturbed) what the critic would read of it
+        self.obs_boot = self.obs if self.disturbances is None else self.obs.clone()
         if reward_norm is not None:
             self.reward_norm = _reward_normalizer_for(reward_norm, venv.num_envs, [self.cfg], self.device)
         # Exact parallel flight makes the reference's d_cpa 0/0 = NaN (kinematics.py:48), and its reward
@@ -1012,7 +1076,7 @@ class PPOTrainer(_Trainer):
         t.add_(1)
 
     def _gae(self):
-        _, last_value = self.policy.forward(self.obs)
+        _, last_value = self.policy.forward(self.obs_boot)
         adv, ret = compute_gae(self.b_rew, self.b_val, self.b_done, last_value, self.cfg.gamma, self.cfg.gae_lambda)
         self.b_adv.copy_(adv)
         self.b_ret.copy_(ret)
@@ -1081,6 +1145,7 @@ class PPOTrainer(_Trainer):
             self.venv.load_state_dict(env_before)
             self.venv.outputs["obs"].copy_(env_obs_before)
             self.obs.copy_(obs_before)
+            self.obs_boot.copy_(obs_before)
             self.nan_events.zero_()
             self.t_idx.zero_()
 
@@ -1092,7 +1157,8 @@ class PPOTrainer(_Trainer):
             if self.collector == "fused":
                 # one launch: rows t = 0 .. T-1 of the static buffers, then the captured GAE as usual
                 out = self.venv.collect(self.policy, T, noise_seed=cfg.seed, noise_step=self.num_timesteps // E,
-                                        out=self._fused_out, group=self._group)
+                                        out=self._fused_out, group=self._group,
+                                        **({} if self.disturbances is None else {"disturbance": self.disturbances}))
                 self._fused_out = out
                 self.nan_events.add_(self._store_collection(out).sum())
                 if self.reward_norm is not None:
@@ -1104,10 +1170,15 @@ class PPOTrainer(_Trainer):
             if self.gae == "kernel":
                 if self._gae_constants is None:
                     self._gae_constants = gae_constants(cfg.gamma, cfg.gae_lambda, 1, self.device)
-                with torch.no_grad():
-                    _, last_value = self.policy.forward(self.obs)
-                gae_fused(self.b_rew, self.b_val, self.b_done, last_value, constants=self._gae_constants,
-                          out={"adv": self.b_adv, "ret": self.b_ret})
+                if self.disturbances is not None and self.venv.obs_dim in GAE_BOOTSTRAP_WIDTHS:
+                    # the kernel's own critic on the row the next collection's first step reads: the bits of its values[0]
+                    gae_fused(self.b_rew, self.b_val, self.b_done, None, critic=self.policy, obs_last=self.obs_boot,
+                              constants=self._gae_constants, out={"adv": self.b_adv, "ret": self.b_ret})
+                else:
+                    with torch.no_grad():
+                        _, last_value = self.policy.forward(self.obs_boot)
+                    gae_fused(self.b_rew, self.b_val, self.b_done, last_value, constants=self._gae_constants,
+                              out={"adv": self.b_adv, "ret": self.b_ret})
             else:
                 self._graphs[1].replay()
             done = self.b_done
@@ -1237,11 +1308,13 @@ class PPOTrainer(_Trainer):
             self.ep_returns, self.ep_lengths, self.ep_outcomes = [], [], []
         return out
 
-    def evaluate(self, n_episodes, rng):
+    def evaluate(self, n_episodes, rng, disturbance=None):
         """Score the current actor deterministically on `n_episodes` fresh episodes drawn from `rng` (a `random.Random`
         fed to reset_parity, like the reference's eval env) in one launch (policy.evaluate_policies_fused, K = 1).
-        Touches neither the training env, nor the captured graphs, nor any torch random stream."""
-        out = self._evaluate_rows([self.policy], self._group, n_episodes, rng)
+        Touches neither the training env, nor the captured graphs, nor any torch random stream.  disturbance: a
+        policy.Disturbance handed to evaluate_policies_fused (None: the nominal score, also of a learner that trains
+        under one)."""
+        out = self._evaluate_rows([self.policy], self._group, n_episodes, rng, disturbance)
         return {k: (v[0] if k != "unfinished" else int(v[0])) for k, v in out.items()}
 
     def learn(self, total_timesteps, log=print, eval_every=None, eval_episodes=10, eval_seed=None, save_dir=None,
@@ -1274,7 +1347,8 @@ class PPOTrainer(_Trainer):
             return [stats], [self.recent_episodes()], [self.nan_events]
 
         books = [_Callbacks(save_dir, lambda: self.policy,
-                            reward_norm=self.reward_norm and self.reward_norm.state_dict)]
+                            reward_norm=self.reward_norm and self.reward_norm.state_dict,
+                            disturbance=self.disturbances and self.disturbances.members[0].to_dict())]
         return self._learn(total_timesteps, log, books, [], iterate,
                            lambda: self._evaluate_rows([self.policy], self._group, eval_episodes, eval_rng), eval_every,
                            checkpoint_every)
@@ -1429,9 +1503,14 @@ class PopulationTrainer(_Trainer):
     update() adds every member's effective learning_rate, clip_range and (where set) clip_range_vf.
     reward_norm: None, True or a RewardNormalizer of K members, as PPOTrainer's: member k's rewards are normalised by its
     OWN running statistics (with its own gamma) in the one call after the collection, update() adds reward_std per member
-    and learn() saves member k's normaliser state under member_<k>/ beside its zips."""
+    and learn() saves member k's normaliser state under member_<k>/ beside its zips.
+    disturbances: None, one policy.Disturbance for all members or K of them with equal seeds (a population can sweep noise
+    levels), as PPOTrainer's `disturbance`: member k collects under its own four standard deviations
+    (ACAS2DVecEnv.collect_set(disturbances=)), b_obs holds the rows its networks read, and the bootstrap value is its
+    critic's on the disturbed row -- policy_set.values() of it, or with gae="kernel" at n_traffic 1, 2, 3, 4, 8 the
+    kernel's own.  Saved under member_<k>/ beside the zips and part of state_dict()."""
 
-    def __init__(self, venv, configs, gae=None, group=False, diagnostics=False, reward_norm=None):
+    def __init__(self, venv, configs, gae=None, group=False, diagnostics=False, reward_norm=None, disturbances=None):
         configs = list(configs)
         if reward_norm is not None and reward_norm is not True and not isinstance(reward_norm, RewardNormalizer):
             raise TypeError("reward_norm must be None, True or a RewardNormalizer, got %r" % (reward_norm,))
@@ -1483,7 +1562,9 @@ class PopulationTrainer(_Trainer):
         per_member = lambda f: (getattr(configs[0], f) if len({getattr(c, f) for c in configs}) == 1 else  # noqa: E731
                                 torch.tensor([getattr(c, f) for c in configs], dtype=torch.float32, device=self.device))
         self._gae_constants = gae_constants(per_member("gamma"), per_member("gae_lambda"), K, self.device)
+        self._set_disturbances(disturbances, K, type(self).__name__)
         self.obs = venv.reset().to(torch.float32).clone()
+        self.obs_boot = self.obs if self.disturbances is None else self.obs.clone()
         self.reward_norm = (None if reward_norm is None else
                             _reward_normalizer_for(reward_norm, venv.num_envs, configs, self.device))
         self.nan_events = torch.zeros(K, dtype=torch.int64, device=self.device)
@@ -1507,19 +1588,27 @@ class PopulationTrainer(_Trainer):
     def collect(self):
         T, E, K, EM = self.cfg.n_steps, self.venv.num_envs, self.K, self.EM
         out = self.venv.collect_set(self.policy_set, T, self.noise_seeds, noise_step=self.num_timesteps // EM,
-                                    out=self._fused_out, **({"group": True} if self.group else {}))
+                                    out=self._fused_out, **({"group": True} if self.group else {}),
+                                    **({} if self.disturbances is None else {"disturbances": self.disturbances}))
         self._fused_out = out
         self.nan_events.add_(self._store_collection(out).view(T, K, EM).sum((0, 2)))
         if self.reward_norm is not None:
             self.reward_norm.normalize(self.b_rew, self.b_done, out=self.b_rew)
-        self.last_value.copy_(self.policy_set.values(self.obs))
-        if self.gae == "kernel":
-            gae_fused(self.b_rew, self.b_val, self.b_done, self.last_value, n_members=K, constants=self._gae_constants,
-                      out={"adv": self.b_adv, "ret": self.b_ret})
+        # the kernel's own critics on the rows the next collection's first step reads (the bits of its values[0]), where
+        # a disturbed run asks for gae="kernel" and the kernel has them; else the bootstrap value is torch's
+        own_critics = self.gae == "kernel" and self.disturbances is not None and self.venv.obs_dim in GAE_BOOTSTRAP_WIDTHS
+        if own_critics:
+            gae_fused(self.b_rew, self.b_val, self.b_done, None, n_members=K, critic=self.policy_set, obs_last=self.obs_boot,
+                      constants=self._gae_constants, out={"adv": self.b_adv, "ret": self.b_ret, "last_value": self.last_value})
         else:
-            adv, ret = compute_gae(self.b_rew, self.b_val, self.b_done, self.last_value, self.gamma, self.gae_lambda)
-            self.b_adv.copy_(adv)
-            self.b_ret.copy_(ret)
+            self.last_value.copy_(self.policy_set.values(self.obs_boot))
+            if self.gae == "kernel":
+                gae_fused(self.b_rew, self.b_val, self.b_done, self.last_value, n_members=K, constants=self._gae_constants,
+                          out={"adv": self.b_adv, "ret": self.b_ret})
+            else:
+                adv, ret = compute_gae(self.b_rew, self.b_val, self.b_done, self.last_value, self.gamma, self.gae_lambda)
+                self.b_adv.copy_(adv)
+                self.b_ret.copy_(ret)
         done = self.b_done
         if bool(done.any()):                              # the iteration's one host synchronisation
             member_of = (torch.arange(E, device=self.device) // EM).expand(T, E)[done].cpu()
@@ -1586,10 +1675,11 @@ class PopulationTrainer(_Trainer):
             self.ep_returns, self.ep_lengths, self.ep_outcomes = ([[] for _ in range(self.K)] for _ in range(3))
         return out
 
-    def evaluate(self, n_episodes, rng):
+    def evaluate(self, n_episodes, rng, disturbance=None):
         """Score the K current actors deterministically on the SAME `n_episodes` fresh episodes drawn from `rng` in ONE
-        launch (policy.evaluate_policies_fused): its dict, rows = members."""
-        return self._evaluate_rows(self.policy_set.actor_weights(), self.group, n_episodes, rng)
+        launch (policy.evaluate_policies_fused): its dict, rows = members.  disturbance: one policy.Disturbance for all
+        rows, handed to evaluate_policies_fused (None: the nominal score)."""
+        return self._evaluate_rows(self.policy_set.actor_weights(), self.group, n_episodes, rng, disturbance)
 
     def learn(self, total_timesteps, log=print, eval_every=None, eval_episodes=10, eval_seed=None, save_dir=None,
               checkpoint_every=None):
@@ -1603,7 +1693,8 @@ class PopulationTrainer(_Trainer):
         eval_rng = random.Random(self.configs[0].seed if eval_seed is None else eval_seed) if eval_every else None
         rn = self.reward_norm
         books = [_Callbacks(save_dir and os.path.join(save_dir, "member_%d" % k), lambda k=k: self.member(k), {"member": k},
-                            reward_norm=rn and (lambda k=k: rn.state_dict(member=k)))
+                            reward_norm=rn and (lambda k=k: rn.state_dict(member=k)),
+                            disturbance=self.disturbances and self.disturbances.members[k].to_dict())
                  for k in range(self.K)]
 
         def iterate():
@@ -1749,9 +1840,11 @@ class PBTTrainer(PopulationTrainer):
     group=True, gae="kernel", diagnostics=True and reward_norm as the parent's.  With reward_norm a recipient also takes the
     donor's running reward statistics (RewardNormalizer.inherit on the kernel's device `donor` vector, no host read): its
     critic is now the donor's and lives in the donor's reward scale; the envs' discounted returns stay its own.  The score
-    of the exchange is the RAW mean episode return."""
+    of the exchange is the RAW mean episode return.  disturbances as the parent's: they describe a member's ENVIRONMENT, not
+    the learner, so an exploit step leaves every member's standard deviations where they were -- a recipient goes on in
+    its own noise under the donor's weights."""
 
-    def __init__(self, venv, configs, pbt, gae=None, group=False, diagnostics=False, reward_norm=None):
+    def __init__(self, venv, configs, pbt, gae=None, group=False, diagnostics=False, reward_norm=None, disturbances=None):
         configs = list(configs)
         for f in ("gamma", "gae_lambda"):
             if len({getattr(c, f) for c in configs}) > 1:
@@ -1759,7 +1852,8 @@ class PBTTrainer(PopulationTrainer):
                                  "exchanged by an exploit step, got %s" % (f, [getattr(c, f) for c in configs]))
         self.pbt = pbt
         self.n_replace = pbt.n_replace(len(configs))
-        super().__init__(venv, configs, gae=gae, group=group, diagnostics=diagnostics, reward_norm=reward_norm)
+        super().__init__(venv, configs, gae=gae, group=group, diagnostics=diagnostics, reward_norm=reward_norm,
+                         disturbances=disturbances)
         # built now, not at the first update: an exploit before it must find the moments and the hyper row
         self._fused_update = self._make_fused_update()
         self.window = None

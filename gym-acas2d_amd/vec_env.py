@@ -20,7 +20,7 @@ import torch
 
 from . import native
 from .config import ACAS2DConfig
-from .policy import kernel_layout
+from .policy import DisturbanceSet, kernel_layout
 from .spaces import Box
 
 _STATE_FIELDS = ("own_x", "own_y", "own_psi", "own_v", "goal_x", "goal_y",
@@ -377,12 +377,21 @@ class ACAS2DVecEnv:
         out["done"] = out["done_u8"].view(torch.bool)
         return out
 
-    def _launch_collect(self, fn, keep, T, out, noise_seed, noise_step, set_args=()):
+    def _launch_collect(self, fn, keep, T, out, noise_seed, noise_step, set_args=(), dist=None):
         """collect() and collect_set() from the output dict to the launch: `fn` reads the 13 weight tensors `keep`;
-        set_args is collect_set's (K, pointer to the members' noise keys)."""
+        set_args is collect_set's (K, pointer to the members' noise keys); dist, for the disturbed entries, the
+        (DisturbanceSet, its rows on the device): the launch then also writes out["obs_read"] [T + 1, E, D]."""
         if out is None:
             out = self._launch_out(T + 1, T, ("actions", "values", "logp"), new=torch.zeros)
         assert out["obs"].shape == (T + 1, self.num_envs, self.obs_dim)
+        dist_args = ()
+        if dist is not None:
+            if out.get("obs_read") is None:
+                out["obs_read"] = torch.zeros_like(out["obs"])
+            assert out["obs_read"].shape == out["obs"].shape and out["obs_read"].is_contiguous()
+            dist_args = (dist[1].data_ptr(), dist[0].seed, out["obs_read"].data_ptr())
+        else:
+            out.pop("obs_read", None)                 # (a reused dict: no stale rows under a key the trainers act on)
         ptr = lambda t: t.data_ptr()  # noqa: E731
         with torch.cuda.device(self.device):
             out["obs"][0].copy_(self._obs)
@@ -392,8 +401,8 @@ class ACAS2DVecEnv:
                                      ptr(out["values"]), ptr(out["logp"]), noise_seed, int(noise_step) & 0xFFFFFFFF, 0)
             native.check(fn(C.byref(self._ccfg), C.byref(self._cstate), C.byref(io), C.byref(ac), *set_args,
                             ptr(out["obs"][0]), T, self.seed_value, self.env_offset, self.num_envs, self.n_traffic,
-                            self._stream()))
-            self._obs.copy_(out["obs"][T])            # the observation the NEXT action(s) would be drawn on
+                            *dist_args, self._stream()))
+            self._obs.copy_(out["obs"][T])            # the (true) observation the NEXT action(s) would be drawn on
         return out
 
     def rollout(self, actions, out=None, keep_terminal_obs=False):
@@ -475,7 +484,20 @@ class ACAS2DVecEnv:
         out["_weights"] = keep       # keep the transposed copies alive until the launch ran
         return out
 
-    def collect(self, policy, n_steps, noise_seed=0, noise_step=0, out=None, group=False):
+    def _disturbed_entry(self, what, disturbances, n_members, group):
+        """The disturbed set collector's entry, the DisturbanceSet and its rows on the device (float32 only)."""
+        if self.dtype != torch.float32:
+            raise ValueError("%s under a disturbance is float32 only, this env is %s" % (what, self.dtype))
+        ds = disturbances if isinstance(disturbances, DisturbanceSet) else DisturbanceSet(disturbances, n_members)
+        if len(ds) != n_members:
+            raise ValueError("%s: %d disturbances for %d member(s)" % (what, len(ds), n_members))
+        if self.config.max_steps + 1 >= 2 ** 20:
+            raise ValueError("%s under a disturbance needs max_steps + 1 < 2^20 (the step field of the noise counter), got "
+                             "max_steps = %d" % (what, self.config.max_steps))
+        fn = self._lib.acas2d_collect_set_disturbed_group_f32 if group else self._lib.acas2d_collect_set_disturbed_f32
+        return fn, ds, torch.as_tensor(ds.rows).to(self.device).contiguous()
+
+    def collect(self, policy, n_steps, noise_seed=0, noise_step=0, out=None, group=False, disturbance=None):
         """The collector of one PPO iteration in ONE kernel launch (acas2d_collect_*; SB3 `collect_rollouts` as
         training_main.py:44-52 runs it): for n_steps steps draw `a ~ N(actor(obs), exp(log_std))`, record the raw
         action, `critic(obs)` and the draw's log-probability, step the env with `clip(a, -1, 1)`.  `policy` is a
@@ -484,9 +506,21 @@ class ACAS2DVecEnv:
         observation the next iteration starts from), actions / values / logp / reward [T, E], done [T, E] bool,
         outcome, episode_return, episode_steps [T, E].  The noise stream depends on (noise_seed, global env index,
         noise_step + t) only.  One lane per env: n_traffic in {1, 2, 3, 4, 8} (float32), {1, 2, 3, 4} (float64);
-        group=True (float32, n_traffic in {8, 16, 32, 64}: acas2d_collect_group_f32) as in rollout_policy()."""
+        group=True (float32, n_traffic in {8, 16, 32, 64}: acas2d_collect_group_f32) as in rollout_policy().
+        disturbance=Disturbance(...) (float32; acas2d_collect_set_disturbed_* with one member): the collection under
+        sensor noise and actuator disturbance.  Both networks read the disturbed rows, returned as "obs_read" [T + 1, E, D]
+        (obs_read[t]: what action t was drawn on and values[t] is the value of; obs_read[T]: the bootstrap row, whose
+        value is the next collection's values[0]); "obs" stays the true observations, "actions" the raw draws, and the
+        env flies clip(clip(a) + s_action z).  The noise depends on (disturbance.seed, global env index, the env's episode
+        counter, its step) only; a zero disturbance returns collect()'s bits and obs_read == obs."""
         if not self.auto_reset:
             raise RuntimeError("collect() has VecEnv auto-reset semantics; construct with auto_reset=True")
+        dist = None
+        if disturbance is not None:
+            if group:
+                self._group_entry("collect", "acas2d_collect_set_disturbed_group_f32")
+            fn_d, ds, rows = self._disturbed_entry("collect()", disturbance, 1, group)
+            dist = (ds, rows)
         if group:
             fn = self._group_entry("collect", "acas2d_collect_group_f32")
         else:
@@ -500,7 +534,13 @@ class ACAS2DVecEnv:
                 + [policy.log_std.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()])
         if keep[0].shape != (D, 64) or keep[2].shape != (64, 64) or keep[4].numel() != 64:
             raise ValueError("policy must be the SB3 MlpPolicy actor-critic %d -> 64 -> 64 -> 1" % D)
-        out = self._launch_collect(fn, keep, T, out, int(noise_seed) & (2 ** 64 - 1), noise_step)
+        key = int(noise_seed) & (2 ** 64 - 1)
+        if dist is not None:         # one member: its key on the device, the 13 tensors are the stacks of one
+            keys = torch.as_tensor(np.asarray([key], np.uint64).view(np.int64)).to(dev)
+            out = self._launch_collect(fn_d, keep, T, out, 0, noise_step, (1, keys.data_ptr()), dist=dist)
+            keep = keep + [keys, rows]
+        else:
+            out = self._launch_collect(fn, keep, T, out, key, noise_step)
         out["_weights"] = keep       # keep the transposed copies alive until the launch ran
         return out
 
@@ -531,7 +571,7 @@ class ACAS2DVecEnv:
                              "got num_envs = %d, K = %d" % (self.num_envs, K))
         return self.num_envs // K
 
-    def collect_set(self, policy_set, n_steps, noise_seeds, noise_step=0, out=None, group=False):
+    def collect_set(self, policy_set, n_steps, noise_seeds, noise_step=0, out=None, group=False, disturbances=None):
         """collect() for K independent actor-critics in ONE kernel launch (acas2d_collect_set_f32).  `policy_set` is a
         `ppo.ActorCriticSet` of K members; member k owns the envs [k EM, (k + 1) EM), EM = num_envs / K a multiple of 64,
         and draws its noise with the key noise_seeds[k] (K ints, or an int64 device tensor holding the keys' bit
@@ -539,7 +579,10 @@ class ACAS2DVecEnv:
         [T, E] layout: the columns of member k equal what collect(member k, noise_seed=noise_seeds[k]) returns on an env
         of EM envs at env_offset + k EM with the same seed, bit for bit.  float32, n_traffic in {1, 2, 3, 4, 8};
         group=True (n_traffic in {8, 16, 32, 64}: acas2d_collect_set_group_f32) as in collect(): the columns of member k
-        then equal collect(member k, group=True)."""
+        then equal collect(member k, group=True).
+        disturbances: one Disturbance for all members or K of them with equal seeds (acas2d_collect_set_disturbed_*), as
+        collect(disturbance=): the dict gains "obs_read"; member k's columns equal collect(member k, disturbance=its own)
+        on its envs, and a member whose four standard deviations are 0 collects what it does without."""
         if not self.auto_reset:
             raise RuntimeError("collect_set() has VecEnv auto-reset semantics; construct with auto_reset=True")
         K = int(policy_set.n_members)
@@ -556,8 +599,12 @@ class ACAS2DVecEnv:
             keys = torch.as_tensor(np.asarray([int(s) & (2 ** 64 - 1) for s in noise_seeds], np.uint64).view(np.int64)).to(dev)
         if keys.numel() != K:
             raise ValueError("collect_set() needs one noise seed per member: %d for %d members" % (keys.numel(), K))
-        out = self._launch_collect(fn, keep, T, out, 0, noise_step, (K, keys.data_ptr()))
-        out["_weights"] = keep + [keys]   # keep the transposed copies and the keys alive until the launch ran
+        dist = None
+        if disturbances is not None:
+            fn, ds, rows = self._disturbed_entry("collect_set()", disturbances, K, group)
+            dist = (ds, rows)
+        out = self._launch_collect(fn, keep, T, out, 0, noise_step, (K, keys.data_ptr()), dist=dist)
+        out["_weights"] = keep + [keys] + ([] if dist is None else [dist[1]])   # alive until the launch ran
         return out
 
     # the per-step arrays: views of the live generation

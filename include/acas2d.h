@@ -511,6 +511,42 @@ int acas2d_disturbance_draw_f32(uint64_t noise_seed, int64_t first_lane, int32_t
                                 int32_t first_step, int32_t n_steps, int32_t n_slots, float *out, void *stream);
 
 /*
+ * acas2d_collect_set_disturbed_f32 / acas2d_collect_set_disturbed_group_f32: acas2d_collect_set_f32 / _group_f32 under the
+ * sensor noise and actuator disturbance above -- the collector of a PPO iteration that TRAINS under them.  Additive to
+ * ABI 7, float32 only.  The siblings' arguments, then `sigmas`, `dist_seed` and `obs_read` in front of `stream`.
+ *   sigmas     device float[n_members][4]: member k's (s_sep, s_cpa, s_closing, s_action), Acas2dDisturbance's units.  They
+ *              live on the device, so the entry cannot look at them: the CALLER makes sure each is finite and at least 0
+ *              (the Python host does).  A member whose four are 0 draws nothing; its columns of every output of the sibling
+ *              equal the sibling's bit for bit and its rows of obs_read the true rows.
+ *   dist_seed  Acas2dDisturbance.noise_seed, one for all members.
+ *   obs_read   T[n_steps + 1][E][D], output: row t is the row BOTH networks read at step t -- the actor and the critic; the
+ *              update must be given these rows.  Stored as disturbed (a NaN stays a NaN: the scrub to 0 is the networks').
+ *              Row n_steps is the observation the last step left (fresh rows of envs that just reset included) under the
+ *              draw the next launch's first step makes, so acas2d_gae_f32 with obs_last = obs_read[n_steps] returns as
+ *              last_value_out the bits of the next collection's values[0].  io->obs keeps the TRUE observations.
+ * Per step: slot n + 1 on traffic n's three entries in front of the two networks, slot 0 on clip(raw, -1, 1), clipped again.
+ * actions keeps the RAW sampled action and logp its log-probability, as in the siblings: actuator noise belongs to the
+ * environment, not to the policy's distribution.  Rewards, outcomes and the state follow from the true state.
+ * The counter: lane = env_offset + the GLOBAL env index (the index of the sampler's noise stream), episode = the env's own
+ * counter in `state` (the in-step reset advances it), step = game.steps before the increment.  The noise is a function of
+ * (dist_seed, global env, episode, step, slot) only: not of n_members, of how training is cut into launches, or of the work
+ * shape.  The key carries the tag above, so the blocks never meet the sampler's or the reset's.
+ * With n_members == 1 the entries are the solo collector: any n_envs >= 1.
+ * Rejected with ACAS2D_EINVAL before anything is launched: everything the sibling rejects (but n_members == 1 drops the
+ * multiple-of-64 rule), a NULL sigmas or obs_read, obs_read overlapping io->obs or obs_in, max_steps + 1 >= 2^20.
+ */
+int acas2d_collect_set_disturbed_f32(const Acas2dConfig *cfg, const Acas2dState *state, const Acas2dStepIO *io,
+                                     const Acas2dActorCritic *ac, int32_t n_members, const uint64_t *noise_seeds,
+                                     const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset, int64_t n_envs,
+                                     int32_t n_traffic, const float *sigmas, uint64_t dist_seed, void *obs_read,
+                                     void *stream);
+int acas2d_collect_set_disturbed_group_f32(const Acas2dConfig *cfg, const Acas2dState *state, const Acas2dStepIO *io,
+                                           const Acas2dActorCritic *ac, int32_t n_members, const uint64_t *noise_seeds,
+                                           const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
+                                           int64_t n_envs, int32_t n_traffic, const float *sigmas, uint64_t dist_seed,
+                                           void *obs_read, void *stream);
+
+/*
  * acas2d_encounter_sample_f32 / _f64, acas2d_encounter_select_f32 / _f64, acas2d_encounter_refit: a cross-entropy search
  * over encounters with importance sampling, around the unchanged acas2d_evaluate_policies_stats_* -- per generation:
  * sample, acas2d_reset_* with do_init = 0 (the first observation), the stats entry, select, refit, with no host decision

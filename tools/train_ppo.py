@@ -62,10 +62,30 @@ ap.add_argument("--pbt", action="store_true",
                      "range and entropy coefficient, scored and decided on the device (DESIGN.md 4.2g)")
 ap.add_argument("--pbt-every", type=int, default=8, help="iterations between two exploit steps")
 ap.add_argument("--pbt-fraction", type=float, default=0.25, help="the share of members replaced at an exploit step")
+ap.add_argument("--disturbance", metavar="sep=..,cpa=..,closing=..,action=..[,seed=..]", action="append", default=None,
+                help="train under white sensor noise (standard deviations in pixels and in the units of v_closing, per traffic "
+                     "aircraft and step) and actuator disturbance (in units of the action), in the syntax of "
+                     "tools/evaluate_checkpoints.py (policy.Disturbance; DESIGN.md 4.2p): the actor and the critic read the "
+                     "disturbed observation, the update is given those rows.  Needs --collector fused.  With --population: once "
+                     "for all members, or K times, one per member, with equal seeds")
+ap.add_argument("--disturbance-normalised", action="store_true",
+                help="--disturbance's sep, cpa and closing are in units of the normalised observation instead")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 if args.pbt and not args.population:
     ap.error("--pbt needs --population K")
+DISTURBANCES = None
+if args.disturbance:
+    if len(args.disturbance) not in (1, max(args.population, 1)):
+        ap.error("--disturbance: once, or once per member of --population (got %d)" % len(args.disturbance))
+    if args.collector != "fused" and not args.population:
+        ap.error("--disturbance needs --collector fused: the noise is drawn inside the fused collection launch")
+    try:
+        DISTURBANCES = [g.Disturbance.parse(t, normalised=args.disturbance_normalised) for t in args.disturbance]
+    except ValueError as e:
+        ap.error(str(e))
+    if len(DISTURBANCES) == 1:
+        DISTURBANCES = DISTURBANCES[0]
 REWARD_NORM = True if args.reward_norm else None
 # clip_range_vf and the schedules, as PPOConfig takes them
 OPTIONS = dict(clip_range_vf=args.clip_range_vf,
@@ -93,9 +113,11 @@ if args.population:
                         **OPTIONS) for k in range(K)]
     if args.pbt:
         pop = g.PBTTrainer(venv, cfgs, g.PBTConfig(ready_every=args.pbt_every, fraction=args.pbt_fraction, seed=args.seed),
-                           gae=args.gae, group=args.traffic in g.ppo.GROUP_TRAFFIC, reward_norm=REWARD_NORM)
+                           gae=args.gae, group=args.traffic in g.ppo.GROUP_TRAFFIC, reward_norm=REWARD_NORM,
+                           disturbances=DISTURBANCES)
     else:
-        pop = g.PopulationTrainer(venv, cfgs, gae=args.gae, group=args.traffic in g.ppo.GROUP_TRAFFIC, reward_norm=REWARD_NORM)
+        pop = g.PopulationTrainer(venv, cfgs, gae=args.gae, group=args.traffic in g.ppo.GROUP_TRAFFIC, reward_norm=REWARD_NORM,
+                                  disturbances=DISTURBANCES)
     pop.learn(int(args.timesteps), log=lambda r: print(json.dumps(r), flush=True))
     if args.traffic == 1:
         own, trf, goal = H.parity_reset_states(g.ACAS2DConfig(), 13, 0, 100)
@@ -114,7 +136,7 @@ trainer = g.PPOTrainer(venv, g.PPOConfig(n_steps=args.n_steps, batch_size=args.b
                                          **OPTIONS),
                        collector=args.collector,
                        use_graphs=args.collector != "eager", updater=args.updater if args.collector != "eager" else "graphs", gae=args.gae,
-                       reward_norm=REWARD_NORM)
+                       reward_norm=REWARD_NORM, disturbance=DISTURBANCES)
 hist = trainer.learn(int(args.timesteps), log=lambda r: print(json.dumps(r), flush=True))
 
 if args.traffic == 1:
