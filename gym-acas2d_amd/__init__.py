@@ -13,7 +13,8 @@ from .records import episode_safety, safety_columns                  # noqa: F40
 from .vec_env import ACAS2DVecEnv, LazyInfos                         # noqa: F401
 from .env import ACAS2DEnv, GameView, register_with_gym              # noqa: F401
 from .policy import (SB3ActorPolicy, load_sb3_policy, save_sb3_policy, evaluate_policy, evaluate_policy_fused,  # noqa: F401
-                     evaluate_policies_fused, MonteCarlo, EncounterSearch, Disturbance, DisturbanceSet)
+                     evaluate_policies_fused, MonteCarlo, EncounterSearch, Disturbance, DisturbanceSet,
+                     CorrelatedDisturbance)
 from .ppo import (ActorCritic, ActorCriticSet, FusedUpdate, FusedUpdateSet, PBTConfig, PBTTrainer, PopulationTrainer,  # noqa: F401
                   PPOConfig, PPOTrainer, RewardNormalizer, compute_gae, gae_constants, gae_fused, member_episodes,
                   normalize_rewards_reference, population_exploit, ppo_loss)

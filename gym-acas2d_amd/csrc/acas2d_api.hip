@@ -158,22 +158,45 @@ int acas2d_evaluate_policies_disturbed_group_f32(SCORING_PARAMS(n_episodes), uin
 }
 // the Monte Carlo campaign on the same three families (monte_carlo_kernel), and disturbed (monte_carlo_disturbed_kernel; float32)
 int acas2d_monte_carlo_f32(SCORING_PARAMS(n_lanes), const Acas2dMonteCarlo* mc, void* stream) {
-    return launch_monte_carlo<float, false>(SCORING_ARGS(n_lanes, false), mc, nullptr);
+    return launch_monte_carlo<float, 0>(SCORING_ARGS(n_lanes, false), mc, nullptr);
 }
 int acas2d_monte_carlo_f64(SCORING_PARAMS(n_lanes), const Acas2dMonteCarlo* mc, void* stream) {
-    return launch_monte_carlo<double, false>(SCORING_ARGS(n_lanes, false), mc, nullptr);
+    return launch_monte_carlo<double, 0>(SCORING_ARGS(n_lanes, false), mc, nullptr);
 }
 int acas2d_monte_carlo_group_f32(SCORING_PARAMS(n_lanes), const Acas2dMonteCarlo* mc, void* stream) {
-    return launch_monte_carlo<float, false>(SCORING_ARGS(n_lanes, true), mc, nullptr);
+    return launch_monte_carlo<float, 0>(SCORING_ARGS(n_lanes, true), mc, nullptr);
 }
 int acas2d_monte_carlo_disturbed_f32(SCORING_PARAMS(n_lanes), const Acas2dMonteCarlo* mc, const Acas2dDisturbance* disturbance,
                                      void* stream) {
-    return launch_monte_carlo<float, true>(SCORING_ARGS(n_lanes, false), mc, disturbance);
+    return launch_monte_carlo<float, 1>(SCORING_ARGS(n_lanes, false), mc, disturbance);
 }
 int acas2d_monte_carlo_disturbed_group_f32(SCORING_PARAMS(n_lanes), const Acas2dMonteCarlo* mc, const Acas2dDisturbance* disturbance,
                                            void* stream) {
-    return launch_monte_carlo<float, true>(SCORING_ARGS(n_lanes, true), mc, disturbance);
+    return launch_monte_carlo<float, 1>(SCORING_ARGS(n_lanes, true), mc, disturbance);
 }
+// both under a Gauss-Markov error per channel in the white noise's place (eval_stats_correlated_kernel,
+// monte_carlo_correlated_kernel; float32)
+int acas2d_evaluate_policies_correlated_f32(SCORING_PARAMS(n_episodes), uint8_t* outcome, int32_t* steps, void* total_reward,
+                                            const Acas2dEvalStats* stats, const Acas2dDisturbance* disturbance,
+                                            const Acas2dCorrelation* correlation, void* stream) {
+    return launch_evaluate_policies<float, Scoring::Correlated>(SCORING_ARGS(n_episodes, false), outcome, steps, total_reward,
+                                                                stats, disturbance, correlation);
+}
+int acas2d_evaluate_policies_correlated_group_f32(SCORING_PARAMS(n_episodes), uint8_t* outcome, int32_t* steps, void* total_reward,
+                                                  const Acas2dEvalStats* stats, const Acas2dDisturbance* disturbance,
+                                                  const Acas2dCorrelation* correlation, void* stream) {
+    return launch_evaluate_policies<float, Scoring::Correlated>(SCORING_ARGS(n_episodes, true), outcome, steps, total_reward,
+                                                                stats, disturbance, correlation);
+}
+int acas2d_monte_carlo_correlated_f32(SCORING_PARAMS(n_lanes), const Acas2dMonteCarlo* mc, const Acas2dDisturbance* disturbance,
+                                      const Acas2dCorrelation* correlation, void* stream) {
+    return launch_monte_carlo<float, 2>(SCORING_ARGS(n_lanes, false), mc, disturbance, correlation);
+}
+int acas2d_monte_carlo_correlated_group_f32(SCORING_PARAMS(n_lanes), const Acas2dMonteCarlo* mc, const Acas2dDisturbance* disturbance,
+                                            const Acas2dCorrelation* correlation, void* stream) {
+    return launch_monte_carlo<float, 2>(SCORING_ARGS(n_lanes, true), mc, disturbance, correlation);
+}
+size_t acas2d_correlation_size(void) { return sizeof(Acas2dCorrelation); }
 size_t acas2d_monte_carlo_size(void) { return sizeof(Acas2dMonteCarlo); }
 size_t acas2d_disturbance_size(void) { return sizeof(Acas2dDisturbance); }
 int acas2d_disturbance_draw_f32(uint64_t noise_seed, int64_t first_lane, int32_t n_lanes, uint32_t episode, int32_t first_step,

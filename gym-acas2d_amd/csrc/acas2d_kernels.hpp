@@ -1478,6 +1478,35 @@ __device__ __forceinline__ const DisturbW* disturbance_args(const PW& pw) {
         return &pw.dist;
     else return nullptr;
 }
+// CORR on top of DIST (acas2d_evaluate_policies_correlated_*, acas2d_monte_carlo_correlated_*; float32): a first-order
+// Gauss-Markov error e_t per channel takes the place of the white normal z_t (include/acas2d.h, Acas2dCorrelation;
+// records.correlated_errors() is the scan in NumPy).  The kernels are eval_stats_correlated_kernel and
+// monte_carlo_correlated_kernel (acas2d_scoring_correlated.hip), their last arguments these derived structs.
+// The state -- e_{t-1} of the lane's 3 C sensor processes and of the actuator's -- lies in the wave's LDS behind the tile, the
+// reset slots and (group shapes) the hidden vectors: value i of lane l at [i * 64 + l] of the last kCorrSlots(C) * 64 elements
+// of the wave's tile_elems (geometry_for()).  Only the lane itself reads or writes its values, so nothing is fenced; every lane
+// of a group keeps a copy of the actuator's (the action is group-uniform).
+struct CorrW {
+    float rho_sep, rho_cpa, rho_closing, rho_action; // Acas2dCorrelation
+    float q_sep, q_cpa, q_closing, q_action;         // the gains (float)sqrt(1 - rho^2), formed in double on the host
+};
+struct PolicyEvalStatsCorrW : PolicyEvalStatsDistW { CorrW corr; };
+struct PolicyMonteCarloCorrW : PolicyMonteCarloDistW { CorrW corr; };
+template <typename PW>
+__device__ __forceinline__ const CorrW* correlation_args(const PW& pw) {
+    if constexpr (std::is_base_of<PolicyEvalStatsCorrW, PW>::value || std::is_base_of<PolicyMonteCarloCorrW, PW>::value)
+        return &pw.corr;
+    else return nullptr;
+}
+constexpr int kCorrSlots(int C) { return 3 * C + 1; }
+// e_t of one process from z_t and the held e_{t-1}: z_t itself where rho == 0 (wave-uniform: the channel does no arithmetic
+// and touches no state) and at the first step the lane plays of an episode; else (rho e_{t-1}) + (q z_t), three roundings
+__device__ __forceinline__ float correlated(float* held, bool first, float rho, float q, float z) {
+    if (rho == 0.0f) return z;
+    const float e = first ? z : __fadd_rn(__fmul_rn(rho, *held), __fmul_rn(q, z));
+    *held = e;
+    return e;
+}
 // DIST on top of Mode::CollectSet (acas2d_collect_set_disturbed_f32, acas2d_collect_set_disturbed_group_f32;
 // collect_set_disturbed_kernel): the collector under the same noise.  Both networks read the disturbed row, which the launch
 // also writes out (obs_read); the standard deviations are the MEMBER's, a row of a device float[K][4] that its waves load
@@ -1756,7 +1785,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
                                                       Params<T> p_arg, StepResetParams<T, rollout_mode(M)> rp_arg, State<T> s_arg,
                                                       StepIO<T> io_arg, uint32_t k0, uint32_t k1,
                                                       int64_t env_offset, int N_arg, int n_steps, PolicyArg<M == Mode::Eval> pw) {
-    constexpr bool STATS = false, MC = false, DIST = false;
+    constexpr bool STATS = false, MC = false, DIST = false, CORR = false;
 #include "acas2d_step_body.inl"
 }
 // Mode::Eval with STATS: step_kernel's arguments (and so the same preloaded ones) with PolicyEvalStatsW at the end.
@@ -1767,7 +1796,7 @@ __global__ __launch_bounds__(kBlock) void eval_stats_kernel(const T* a0, const T
                                                             Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
                                                             StepIO<T> io_arg, uint32_t k0, uint32_t k1,
                                                             int64_t env_offset, int N_arg, int n_steps, PolicyEvalStatsW pw) {
-    constexpr bool PACKED = true, STATS = true, MC = false, DIST = false;
+    constexpr bool PACKED = true, STATS = true, MC = false, DIST = false, CORR = false;
     constexpr Mode M = Mode::Eval;
 #include "acas2d_step_body.inl"
 }
@@ -1781,7 +1810,7 @@ __global__ __launch_bounds__(kBlock) void monte_carlo_kernel(const T* a0, const 
                                                              Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
                                                              StepIO<T> io_arg, uint32_t k0, uint32_t k1,
                                                              int64_t env_offset, int N_arg, int n_steps, PolicyMonteCarloW pw) {
-    constexpr bool PACKED = true, STATS = true, MC = true, DIST = false;
+    constexpr bool PACKED = true, STATS = true, MC = true, DIST = false, CORR = false;
     constexpr Mode M = Mode::Eval;
 #include "acas2d_step_body.inl"
 }
@@ -1795,7 +1824,7 @@ __global__ __launch_bounds__(kBlock) void eval_stats_disturbed_kernel(const T* a
                                                                       Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
                                                                       StepIO<T> io_arg, uint32_t k0, uint32_t k1, int64_t env_offset,
                                                                       int N_arg, int n_steps, PolicyEvalStatsDistW pw) {
-    constexpr bool PACKED = true, STATS = true, MC = false, DIST = true;
+    constexpr bool PACKED = true, STATS = true, MC = false, DIST = true, CORR = false;
     constexpr Mode M = Mode::Eval;
 #include "acas2d_step_body.inl"
 }
@@ -1805,7 +1834,7 @@ __global__ __launch_bounds__(kBlock) void monte_carlo_disturbed_kernel(const T* 
                                                                        Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
                                                                        StepIO<T> io_arg, uint32_t k0, uint32_t k1, int64_t env_offset,
                                                                        int N_arg, int n_steps, PolicyMonteCarloDistW pw) {
-    constexpr bool PACKED = true, STATS = true, MC = true, DIST = true;
+    constexpr bool PACKED = true, STATS = true, MC = true, DIST = true, CORR = false;
     constexpr Mode M = Mode::Eval;
 #include "acas2d_step_body.inl"
 }
@@ -1820,8 +1849,32 @@ __global__ __launch_bounds__(kBlock) void collect_set_disturbed_kernel(const T* 
                                                                        Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
                                                                        StepIO<T> io_arg, uint32_t k0, uint32_t k1, int64_t env_offset,
                                                                        int N_arg, int n_steps, PW pw) {
-    constexpr bool PACKED = true, STATS = false, MC = false, DIST = true;
+    constexpr bool PACKED = true, STATS = false, MC = false, DIST = true, CORR = false;
     constexpr Mode M = Mode::CollectSet;
+#include "acas2d_step_body.inl"
+}
+// eval_stats_disturbed_kernel and monte_carlo_disturbed_kernel with CORR (acas2d_evaluate_policies_correlated_*,
+// acas2d_monte_carlo_correlated_*): the disturbance is a Gauss-Markov error per channel whose state lies in the wave's LDS
+// (CorrW).  Kernels of their own for the reason eval_stats_kernel is one, instantiated in a unit of their own
+// (acas2d_scoring_correlated.hip); float32 only.
+template <typename T, int C, int G, bool FAST>
+__global__ __launch_bounds__(kBlock) void eval_stats_correlated_kernel(const T* a0, const T* a1, const T* a2, const T* a3,
+                                                                       const T* a4, const T* a5, int32_t e_n_envs, int32_t tile_elems,
+                                                                       Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
+                                                                       StepIO<T> io_arg, uint32_t k0, uint32_t k1, int64_t env_offset,
+                                                                       int N_arg, int n_steps, PolicyEvalStatsCorrW pw) {
+    constexpr bool PACKED = true, STATS = true, MC = false, DIST = true, CORR = true;
+    constexpr Mode M = Mode::Eval;
+#include "acas2d_step_body.inl"
+}
+template <typename T, int C, int G, bool FAST>
+__global__ __launch_bounds__(kBlock) void monte_carlo_correlated_kernel(const T* a0, const T* a1, const T* a2, const T* a3,
+                                                                        const T* a4, const T* a5, int32_t e_n_envs, int32_t tile_elems,
+                                                                        Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
+                                                                        StepIO<T> io_arg, uint32_t k0, uint32_t k1, int64_t env_offset,
+                                                                        int N_arg, int n_steps, PolicyMonteCarloCorrW pw) {
+    constexpr bool PACKED = true, STATS = true, MC = true, DIST = true, CORR = true;
+    constexpr Mode M = Mode::Eval;
 #include "acas2d_step_body.inl"
 }
 // acas2d_disturbance_draw_f32: the normals of n_steps x n_lanes x n_slots blocks as float[n_steps][n_lanes][n_slots][3]
@@ -1932,13 +1985,16 @@ struct ScoringArgs {
     bool group;
 };
 // the evaluator: step_kernel<..., Mode::Eval> / eval_stats_kernel (stats) / eval_stats_disturbed_kernel (stats and dist; float32)
-enum class Scoring { Plain, Stats, Disturbed };
+// / eval_stats_correlated_kernel (stats, dist and corr; float32, acas2d_scoring_correlated.hip)
+enum class Scoring { Plain, Stats, Disturbed, Correlated };
 template <typename T, Scoring V>
 int launch_evaluate_policies(const ScoringArgs& a, uint8_t* outcome, int32_t* steps, void* total_reward,
-                             const Acas2dEvalStats* stats, const Acas2dDisturbance* dist);
-// the campaign: monte_carlo_kernel / monte_carlo_disturbed_kernel (DIST: dist; float32)
-template <typename T, bool DIST>
-int launch_monte_carlo(const ScoringArgs& a, const Acas2dMonteCarlo* mc, const Acas2dDisturbance* dist);
+                             const Acas2dEvalStats* stats, const Acas2dDisturbance* dist, const Acas2dCorrelation* corr = nullptr);
+// the campaign: monte_carlo_kernel / monte_carlo_disturbed_kernel (V = 1: dist; float32) / monte_carlo_correlated_kernel
+// (V = 2: dist and corr; float32, acas2d_scoring_correlated.hip)
+template <typename T, int V>
+int launch_monte_carlo(const ScoringArgs& a, const Acas2dMonteCarlo* mc, const Acas2dDisturbance* dist,
+                       const Acas2dCorrelation* corr = nullptr);
 // acas2d_disturbance_draw_f32 (float32 only)
 template <typename T>
 int launch_disturbance_draw(uint64_t seed, int64_t first_lane, int32_t n_lanes, uint32_t episode, int32_t first_step,

@@ -134,11 +134,12 @@ static int check_launch(const char* name) {
 // Launch geometry for a shape: one env per G lanes, 64 / G envs per wavefront, 4 wavefronts per
 // workgroup, one LDS observation tile per wavefront.  `group_policy`: the launch evaluates the in-kernel policy
 // with the G lanes of an env together and keeps each env's 64 hidden activations behind the wave's tile and reset
-// slots (policy_mlp_group(); the kernel finds them at the END of the wave's tile_elems).
+// slots (policy_mlp_group(); the kernel finds them at the END of the wave's tile_elems).  `held`: values the launch keeps
+// per LANE behind all of that (the correlated flavours' error state, CorrW; the hidden vectors then end where it begins).
 struct Geometry { unsigned grid, block; int tile_elems; size_t lds_bytes; };
 
 template <typename T>
-static int geometry_for(const Shape& sh, int64_t n_envs, int n_traffic, Geometry* g, bool group_policy = false) {
+static int geometry_for(const Shape& sh, int64_t n_envs, int n_traffic, Geometry* g, bool group_policy = false, int held = 0) {
     const int64_t epw = 64 / sh.G, envs_per_block = epw * kWavesPerBlock;
     const int64_t blocks = (n_envs + envs_per_block - 1) / envs_per_block;
     if (blocks > 0x7fffffffLL || n_envs > 0x7fffffffLL) { set_error("n_envs = %lld exceeds the launch limit", (long long)n_envs); return ACAS2D_EINVAL; }
@@ -154,11 +155,11 @@ static int geometry_for(const Shape& sh, int64_t n_envs, int n_traffic, Geometry
         scratch = 4 * (int64_t)n_traffic + 1;
     }
     const int64_t hidden = group_policy ? epw * kPolicyHidden : 0;
-    const int64_t elems = ((tile + scratch + 3) / 4) * 4 + hidden;
+    const int64_t elems = ((tile + scratch + 3) / 4) * 4 + hidden + 64 * (int64_t)held;
     const int64_t bytes = elems * kWavesPerBlock * (int64_t)sizeof(T);
     if (bytes > 64 * 1024) {
-        set_error("n_traffic = %d needs a %lld-byte LDS observation tile%s per workgroup (limit 65536)", n_traffic, (long long)bytes,
-                  group_policy ? " and hidden vectors" : "");
+        set_error("n_traffic = %d needs a %lld-byte LDS observation tile%s%s per workgroup (limit 65536)", n_traffic, (long long)bytes,
+                  group_policy ? " and hidden vectors" : "", held ? " and error state" : "");
         return ACAS2D_EINVAL;
     }
     g->grid = (unsigned)blocks; g->block = (unsigned)kBlock; g->tile_elems = (int)elems; g->lds_bytes = (size_t)bytes;
@@ -256,6 +257,7 @@ struct Launch {
     StepIO<T> io;
     uint32_t k0, k1;
     bool group_policy;                        // the *_group entry points: geometry_for()'s hidden vectors
+    bool correlated;                          // the *_correlated entry points: geometry_for()'s error state, 3 C + 1 per lane
 };
 
 // The entry points' words for the rejections they share (each has always said them its own way)
@@ -278,7 +280,7 @@ static int prepare(Launch<T>& L, const Words& words, bool given, Inputs inputs, 
     if (L.n_envs < 0 || L.env_offset < 0) return fail(words.negative, L.name);
     if (L.n_envs == 0) return ACAS2D_OK;
     if (int rc = shape(&L.sh)) return rc;
-    if (int rc = geometry_for<T>(L.sh, L.n_envs, L.N, &L.g, L.group_policy)) return rc;
+    if (int rc = geometry_for<T>(L.sh, L.n_envs, L.N, &L.g, L.group_policy, L.correlated ? kCorrSlots(L.sh.C) : 0)) return rc;
     L.p = make_params<T>(*L.cfg);
     L.s = make_state<T>(*L.st);
     if (const Acas2dStepIO* io = L.step_io)
@@ -324,12 +326,14 @@ static int require_aligned(const char* name, std::initializer_list<const void*> 
     return ACAS2D_OK;
 }
 
-// The kernel of a launch: step_kernel in mode M, unless the launch's policy argument is one of the five that have a kernel
-// of their own (Mode::Eval with statistics, the Monte Carlo campaign, the disturbed flavour of each and the disturbed set
-// collector; packed shapes)
+// The kernel of a launch: step_kernel in mode M, unless the launch's policy argument is one of the seven that have a kernel
+// of their own (Mode::Eval with statistics, the Monte Carlo campaign, the disturbed and the correlated flavour of each and the
+// disturbed set collector; packed shapes)
 template <typename PW, typename T, int C, int G, bool PACKED, bool FAST, Mode M>
 static constexpr auto kernel_for() {
     if constexpr (std::is_same<PW, PolicyCollectDistW>::value) return &collect_set_disturbed_kernel<T, C, G, FAST>;
+    else if constexpr (std::is_same<PW, PolicyMonteCarloCorrW>::value) return &monte_carlo_correlated_kernel<T, C, G, FAST>;
+    else if constexpr (std::is_same<PW, PolicyEvalStatsCorrW>::value) return &eval_stats_correlated_kernel<T, C, G, FAST>;
     else if constexpr (std::is_same<PW, PolicyMonteCarloDistW>::value) return &monte_carlo_disturbed_kernel<T, C, G, FAST>;
     else if constexpr (std::is_same<PW, PolicyEvalStatsDistW>::value) return &eval_stats_disturbed_kernel<T, C, G, FAST>;
     else if constexpr (std::is_same<PW, PolicyMonteCarloW>::value) return &monte_carlo_kernel<T, C, G, FAST>;
@@ -578,6 +582,21 @@ static int check_disturbance(const char* name, const Acas2dConfig* cfg, const Ac
 static DisturbW disturbance_words(const Acas2dDisturbance& d) {
     return DisturbW{d.s_sep, d.s_cpa, d.s_closing, d.s_action, (uint32_t)d.noise_seed, (uint32_t)(d.noise_seed >> 32), d.noise_episode};
 }
+// ... and the correlated entries on top of the disturbed ones (behind EVERYTHING those reject), with the gains
+static int check_correlation(const char* name, const Acas2dCorrelation* c) {
+    if (!c) return fail("%s: NULL correlation", name);
+    const float rho[4] = {c->rho_sep, c->rho_cpa, c->rho_closing, c->rho_action};
+    for (float v : rho)
+        if (!(v >= 0.0f) || !(v <= 1.0f))
+            return fail("%s: rho_sep = %g, rho_cpa = %g, rho_closing = %g, rho_action = %g (each in [0, 1])", name,
+                        (double)rho[0], (double)rho[1], (double)rho[2], (double)rho[3]);
+    return ACAS2D_OK;
+}
+static CorrW correlation_words(const Acas2dCorrelation& c) {
+    const auto gain = [](float rho) { return (float)std::sqrt(1.0 - (double)rho * (double)rho); };
+    return CorrW{c.rho_sep, c.rho_cpa, c.rho_closing, c.rho_action,
+                 gain(c.rho_sep), gain(c.rho_cpa), gain(c.rho_closing), gain(c.rho_action)};
+}
 
 // ---- the policy-scoring family: acas2d_evaluate_policies_* and acas2d_monte_carlo_* ------------------------------------------
 // K stacked policies on shared work: policy k plays envs [k EP, (k + 1) EP) of the state, EP = n_per_policy (the evaluator's
@@ -592,21 +611,28 @@ static const ScoringWords kEvaluateWords[] = {             // [Scoring]
     {"acas2d_evaluate_policies_stats", "acas2d_evaluate_policies_stats_group", "acas2d_evaluate_policies_stats_f32", "n_episodes",
      "acas2d_evaluate_policies"},
     {"acas2d_evaluate_policies_disturbed", "acas2d_evaluate_policies_disturbed_group", "acas2d_evaluate_policies_disturbed_f32",
+     "n_episodes", "acas2d_evaluate_policies"},
+    {"acas2d_evaluate_policies_correlated", "acas2d_evaluate_policies_correlated_group", "acas2d_evaluate_policies_correlated_f32",
      "n_episodes", "acas2d_evaluate_policies"}};
-static const ScoringWords kMonteCarloWords[] = {           // [disturbed]
+static const ScoringWords kMonteCarloWords[] = {           // [plain, disturbed, correlated]
     {"acas2d_monte_carlo", "acas2d_monte_carlo_group", "acas2d_monte_carlo_f32", "n_lanes", nullptr},
-    {"acas2d_monte_carlo_disturbed", "acas2d_monte_carlo_disturbed_group", "acas2d_monte_carlo_disturbed_f32", "n_lanes", nullptr}};
+    {"acas2d_monte_carlo_disturbed", "acas2d_monte_carlo_disturbed_group", "acas2d_monte_carlo_disturbed_f32", "n_lanes", nullptr},
+    {"acas2d_monte_carlo_correlated", "acas2d_monte_carlo_correlated_group", "acas2d_monte_carlo_correlated_f32", "n_lanes", nullptr}};
 
 // Everything the two share, around their own parts: nulls(name), the family's required pointers; own(name), its checks
 // behind the counts' and in front of the disturbance's; fill(pw), its fields of the kernel's last argument PW -- which
-// picks the kernel (kernel_for()).
+// picks the kernel (kernel_for()).  A PW with a CorrW is a correlated entry's: `corr` is checked last of all.
 template <typename T, typename PW, bool DIST, typename Nulls, typename Own, typename Fill>
-static int score(const ScoringArgs& a, const ScoringWords& w, const Acas2dDisturbance* dist, Nulls nulls, Own own, Fill fill) {
+static int score(const ScoringArgs& a, const ScoringWords& w, const Acas2dDisturbance* dist, const Acas2dCorrelation* corr,
+                 Nulls nulls, Own own, Fill fill) {
     static_assert(!DIST || sizeof(T) == 4, "the disturbed flavours: float32");
+    constexpr bool CORR = std::is_base_of<PolicyEvalStatsCorrW, PW>::value || std::is_base_of<PolicyMonteCarloCorrW, PW>::value;
+    static_assert(!CORR || DIST, "the correlated flavours: on top of the disturbed ones");
     const int64_t ep = ((int64_t)a.n_per_policy + 63) / 64 * 64, total = (int64_t)a.n_policies * ep;
     Launch<T> L{a.group ? w.group_name : w.name, a.cfg, a.st, nullptr, a.seed, a.env_offset, total, a.n_traffic, a.n_steps,
                 a.stream};
     L.group_policy = a.group;
+    L.correlated = CORR;
     const auto inputs = [&] {
         if (int rc = nulls(L.name)) return rc;
         if (int rc = require_actor(L.name, a.pol)) return rc;
@@ -626,8 +652,11 @@ static int score(const ScoringArgs& a, const ScoringWords& w, const Acas2dDistur
     const auto go = [&] {
         if (a.group)
             if (int rc = require_aligned(L.name, {a.pol->w1t, a.pol->b1, a.pol->w2t, a.pol->b2})) return rc;
+        if constexpr (CORR)
+            if (int rc = check_correlation(L.name, corr)) return rc;
         PW pw = actor<PW>(a.pol, a.obs_in);
         if constexpr (DIST) pw.dist = disturbance_words(*dist);
+        if constexpr (CORR) pw.corr = correlation_words(*corr);
         pw.n_episodes = a.n_per_policy; pw.ep_stride = (int32_t)ep;
         fill(pw);
         return launch_mode<Mode::Eval>(L, pw);
@@ -637,15 +666,16 @@ static int score(const ScoringArgs& a, const ScoringWords& w, const Acas2dDistur
 
 // acas2d_evaluate_policies_*: each lane's first episode, scored.  Scoring::Stats adds the per-episode safety statistics
 // (eval_stats_kernel instead of step_kernel<..., Mode::Eval>), Scoring::Disturbed sensor noise and actuator disturbance on
-// top (eval_stats_disturbed_kernel; float32).
+// top (eval_stats_disturbed_kernel; float32), Scoring::Correlated a Gauss-Markov error in the white noise's place
+// (eval_stats_correlated_kernel; float32, instantiated by acas2d_scoring_correlated.hip).
 // (The units instantiate Stats and Disturbed LAST -- ACAS2D_INSTANTIATE_SCORING at their ends -- so that their kernels follow
 //  every other kernel of the unit, and those keep the local labels of their assembly too.)
 template <typename T, Scoring V>
 int launch_evaluate_policies(const ScoringArgs& a, uint8_t* outcome, int32_t* steps, void* total_reward,
-                             const Acas2dEvalStats* stats, const Acas2dDisturbance* dist) {
-    constexpr bool STATS = V != Scoring::Plain, DIST = V == Scoring::Disturbed;
-    using PW = typename std::conditional<DIST, PolicyEvalStatsDistW,
-                                         typename std::conditional<STATS, PolicyEvalStatsW, PolicyEvalW>::type>::type;
+                             const Acas2dEvalStats* stats, const Acas2dDisturbance* dist, const Acas2dCorrelation* corr) {
+    constexpr bool STATS = V != Scoring::Plain, CORR = V == Scoring::Correlated, DIST = V == Scoring::Disturbed || CORR;
+    using PW = typename std::conditional<CORR, PolicyEvalStatsCorrW, typename std::conditional<DIST, PolicyEvalStatsDistW,
+                                         typename std::conditional<STATS, PolicyEvalStatsW, PolicyEvalW>::type>::type>::type;
     const auto nulls = [&](const char* name) {
         if (!a.obs_in || !outcome || !steps || !total_reward)
             return fail("%s: obs_in and the outcome, steps and total_reward outputs are required", name);
@@ -663,15 +693,17 @@ int launch_evaluate_policies(const ScoringArgs& a, uint8_t* outcome, int32_t* st
             pw.st_max_a_lat = stats->max_a_lat; pw.st_max_dev = stats->max_dev; pw.st_sum_dev = stats->sum_dev;
         }
     };
-    return score<T, PW, DIST>(a, kEvaluateWords[(int)V], dist, nulls, [](const char*) { return ACAS2D_OK; }, fill);
+    return score<T, PW, DIST>(a, kEvaluateWords[(int)V], dist, corr, nulls, [](const char*) { return ACAS2D_OK; }, fill);
 }
 
 // acas2d_monte_carlo_*: the same blocks of lanes, each lane playing mc->episodes_per_lane drawn episodes and folding them
-// into mc's accumulators (monte_carlo_kernel; DIST: monte_carlo_disturbed_kernel, float32).  Instantiated after the stats
-// evaluator, for the same reason.
-template <typename T, bool DIST>
-int launch_monte_carlo(const ScoringArgs& a, const Acas2dMonteCarlo* mc, const Acas2dDisturbance* dist) {
-    using PW = typename std::conditional<DIST, PolicyMonteCarloDistW, PolicyMonteCarloW>::type;
+// into mc's accumulators (monte_carlo_kernel; V = 1: monte_carlo_disturbed_kernel, V = 2: monte_carlo_correlated_kernel, both
+// float32).  Instantiated after the stats evaluator, for the same reason.
+template <typename T, int V>
+int launch_monte_carlo(const ScoringArgs& a, const Acas2dMonteCarlo* mc, const Acas2dDisturbance* dist, const Acas2dCorrelation* corr) {
+    constexpr bool DIST = V >= 1, CORR = V == 2;
+    using PW = typename std::conditional<CORR, PolicyMonteCarloCorrW,
+                                         typename std::conditional<DIST, PolicyMonteCarloDistW, PolicyMonteCarloW>::type>::type;
     const auto nulls = [&](const char* name) {
         if (!a.obs_in) return fail("%s: obs_in is required", name);
         if (!mc) return fail("%s: NULL mc", name);
@@ -703,7 +735,7 @@ int launch_monte_carlo(const ScoringArgs& a, const Acas2dMonteCarlo* mc, const A
         pw.mc_n_bins = mc->n_bins; pw.mc_episodes = mc->episodes_per_lane; pw.mc_first = mc->first_episode;
         pw.mc_inv_bin_f = (float)mc->inv_bin_width; pw.mc_inv_bin_d = mc->inv_bin_width;
     };
-    return score<T, PW, DIST>(a, kMonteCarloWords[DIST], dist, nulls, own, fill);
+    return score<T, PW, DIST>(a, kMonteCarloWords[V], dist, corr, nulls, own, fill);
 }
 
 // acas2d_disturbance_draw_f32: the normals the disturbed kernels draw (float32; instantiated with them)
@@ -732,12 +764,18 @@ int launch_disturbance_draw(uint64_t seed, int64_t first_lane, int32_t n_lanes, 
 #define ACAS2D_INSTANTIATE_SCORING \
     namespace acas2d { \
     template decltype(launch_evaluate_policies<Elem, Scoring::Stats>) launch_evaluate_policies<Elem, Scoring::Stats>; \
-    template decltype(launch_monte_carlo<Elem, false>) launch_monte_carlo<Elem, false>; }
+    template decltype(launch_monte_carlo<Elem, 0>) launch_monte_carlo<Elem, 0>; }
 #define ACAS2D_INSTANTIATE_SCORING_DISTURBED \
     namespace acas2d { \
     template decltype(launch_evaluate_policies<Elem, Scoring::Disturbed>) launch_evaluate_policies<Elem, Scoring::Disturbed>; \
-    template decltype(launch_monte_carlo<Elem, true>) launch_monte_carlo<Elem, true>; \
+    template decltype(launch_monte_carlo<Elem, 1>) launch_monte_carlo<Elem, 1>; \
     template decltype(launch_disturbance_draw<Elem>) launch_disturbance_draw<Elem>; }
+// the correlated evaluator and campaign: the instantiations of acas2d_scoring_correlated.hip, a unit of its own for the reason
+// the disturbed set collector's is one
+#define ACAS2D_INSTANTIATE_SCORING_CORRELATED \
+    namespace acas2d { \
+    template decltype(launch_evaluate_policies<Elem, Scoring::Correlated>) launch_evaluate_policies<Elem, Scoring::Correlated>; \
+    template decltype(launch_monte_carlo<Elem, 2>) launch_monte_carlo<Elem, 2>; }
 // the disturbed set collector: the ONE instantiation of acas2d_collect_disturbed.hip, a unit of its own -- the float32 unit
 // ends with the kernels above, and every kernel of it keeps its place, its name and the local labels of its assembly
 #define ACAS2D_INSTANTIATE_COLLECT_DISTURBED \

@@ -1,8 +1,8 @@
-// acas2d_step_body.inl -- the body of step_kernel, eval_stats_kernel, monte_carlo_kernel, the latter two's disturbed
-// flavours and the disturbed set collector (acas2d_kernels.hpp, where the modes and what each one implies are described),
-// included inside all six.  It
+// acas2d_step_body.inl -- the body of step_kernel, eval_stats_kernel, monte_carlo_kernel, the latter two's disturbed and
+// correlated flavours and the disturbed set collector (acas2d_kernels.hpp, where the modes and what each one implies are
+// described), included inside all eight.  It
 // expects the including kernel's template parameters T, C, G, PACKED, FAST, M (or constants of those names), the constants
-// STATS, MC and DIST, and the kernel's arguments a0 .. a5,
+// STATS, MC, DIST and CORR, and the kernel's arguments a0 .. a5,
 // e_n_envs, tile_elems, p_arg, rp_arg, s_arg, io_arg, k0, k1, env_offset, N_arg, n_steps, pw.
     constexpr bool AUTO_RESET = M != Mode::Latch, ROLLOUT = rollout_mode(M);
     constexpr bool POLICY = policy_mode(M), SAMPLE = sample_mode(M);
@@ -229,6 +229,14 @@
     // evaluator takes by value -- filled in the SET prologue below; its episode field is not used (the lane's own counts)
     DisturbW set_dw{};
     (void)set_dw;
+    // CORR: the lane's held errors e_{t-1}, at the end of the wave's LDS (CorrW) -- value i at corr_held[i * 64]: 3 k + c for
+    // channel c of the lane's k-th aircraft, then the actuator's
+    float* corr_held = nullptr;
+    (void)corr_held;
+    if constexpr (CORR) {
+        static_assert(DIST && EVAL && STATS, "correlated errors: the disturbed stats evaluator and Monte Carlo kernel");
+        corr_held = reinterpret_cast<float*>(tile) + (tile_elems - kCorrSlots(C) * 64) + lane;
+    }
     // STATS: the running statistics of the lane's episode (PolicyEvalStatsW)
     T st_min = T(1) / T(0), st_a_lat = T(0), st_dev = T(0), st_sum = T(0);
     int32_t st_min_step = 0, st_los = 0;
@@ -280,11 +288,20 @@
                 const DisturbW* const dw = SET ? &set_dw : disturbance_args(pw);
                 if (dw->s_sep != 0.0f || dw->s_cpa != 0.0f || dw->s_closing != 0.0f) {      // (wave-uniform)
                     const uint32_t d_ep = (MC || SET) ? episode : dw->episode;
+                    // CORR: the lane's first step of an episode in this launch (an in-step reset leaves steps == 1)
+                    const bool corr_first = CORR && (t == 0 || steps == 1);
+                    (void)corr_first;
 #pragma unroll
                     for (int k = 0; k < C; ++k) {
                         const int n = j * C + k;
                         float z0, z1, z2;
                         disturbance_normals(dw->k0, dw->k1, dist_lane, d_ep, (uint32_t)steps, (uint32_t)(n + 1), z0, z1, z2);
+                        if constexpr (CORR) {             // e_t in z_t's place
+                            const CorrW* const cw = correlation_args(pw);
+                            z0 = correlated(corr_held + (3 * k) * 64, corr_first, cw->rho_sep, cw->q_sep, z0);
+                            z1 = correlated(corr_held + (3 * k + 1) * 64, corr_first, cw->rho_cpa, cw->q_cpa, z1);
+                            z2 = correlated(corr_held + (3 * k + 2) * 64, corr_first, cw->rho_closing, cw->q_closing, z2);
+                        }
                         float* const e = reinterpret_cast<float*>(row) + 5 + 3 * n;
                         e[0] = disturbed(e[0], dw->s_sep, z0, 0.0f, 1.0f);
                         e[1] = disturbed(e[1], dw->s_cpa, z1, -1.0f, 1.0f);
@@ -317,7 +334,7 @@
             // G > 1: the group evaluates the network together (policy_mlp_group()); its hidden vector lies behind
             // the wave's tile and reset slots (geometry_for())
             float* hid = nullptr;
-            if constexpr (G > 1) hid = reinterpret_cast<float*>(tile) + (tile_elems - EPW * kPolicyHidden);
+            if constexpr (G > 1) hid = reinterpret_cast<float*>(tile) + (tile_elems - (CORR ? kCorrSlots(C) * 64 : 0) - EPW * kPolicyHidden);
             (void)hid;
             // The weights must be RE-READ every step (scalar cache hits): they are loop-invariant, and
             // hoisted out of the step loop hipcc tries to keep all 4 700 of them in SGPRs, spills them
@@ -393,6 +410,10 @@
                     if (dw->s_action != 0.0f) {           // (wave-uniform)
                         float z0, z1, z2;
                         disturbance_normals(dw->k0, dw->k1, dist_lane, MC ? episode : dw->episode, (uint32_t)steps, 0u, z0, z1, z2);
+                        if constexpr (CORR) {             // e_t in z_t's place: the lane's last held value
+                            const CorrW* const cw = correlation_args(pw);
+                            z0 = correlated(corr_held + (3 * C) * 64, t == 0 || steps == 1, cw->rho_action, cw->q_action, z0);
+                        }
                         action = (T)disturbed((float)action, dw->s_action, z0, -1.0f, 1.0f);
                     }
                 }

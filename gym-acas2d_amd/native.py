@@ -92,6 +92,12 @@ class CDisturbance(C.Structure):
         [("noise_seed", C.c_uint64), ("noise_episode", C.c_uint32), ("_pad", C.c_uint32)]
 
 
+class CCorrelation(C.Structure):
+    """struct Acas2dCorrelation: the four channels' step-to-step correlation coefficients, each in [0, 1]
+    (acas2d_evaluate_policies_correlated_*, acas2d_monte_carlo_correlated_*, include/acas2d.h)."""
+    _fields_ = [(n, C.c_float) for n in ("rho_sep", "rho_cpa", "rho_closing", "rho_action")]
+
+
 class CEncounterSearch(C.Structure):
     """struct Acas2dEncounterSearch: the proposal's tables, the per-candidate buffers, the stats entry's outputs, the log row,
     the archive and the settings of one generation of an encounter search (acas2d_encounter_*, include/acas2d.h)."""
@@ -157,7 +163,9 @@ EXPORTS = ("acas2d_abi_version", "acas2d_config_size", "acas2d_state_size", "aca
            "acas2d_encounter_search_size", "acas2d_disturbance_size", "acas2d_evaluate_policies_disturbed_f32",
            "acas2d_evaluate_policies_disturbed_group_f32", "acas2d_monte_carlo_disturbed_f32",
            "acas2d_monte_carlo_disturbed_group_f32", "acas2d_disturbance_draw_f32", "acas2d_collect_set_disturbed_f32",
-           "acas2d_collect_set_disturbed_group_f32")
+           "acas2d_collect_set_disturbed_group_f32", "acas2d_correlation_size", "acas2d_evaluate_policies_correlated_f32",
+           "acas2d_evaluate_policies_correlated_group_f32", "acas2d_monte_carlo_correlated_f32",
+           "acas2d_monte_carlo_correlated_group_f32")
 
 
 class NativeLibraryError(RuntimeError):
@@ -227,8 +235,11 @@ def lib():
     for stem, tail in (("evaluate_policies", results), ("evaluate_policies_stats", results + [C.POINTER(CEvalStats)]),
                        ("evaluate_policies_disturbed", results + [C.POINTER(CEvalStats), C.POINTER(CDisturbance)]),
                        ("monte_carlo", [C.POINTER(CMonteCarlo)]),
-                       ("monte_carlo_disturbed", [C.POINTER(CMonteCarlo), C.POINTER(CDisturbance)])):
-        for sfx in ("f32", "group_f32") + (() if stem.endswith("disturbed") else ("f64",)):     # (disturbed: float32 only)
+                       ("monte_carlo_disturbed", [C.POINTER(CMonteCarlo), C.POINTER(CDisturbance)]),
+                       ("evaluate_policies_correlated", results + [C.POINTER(CEvalStats), C.POINTER(CDisturbance),
+                                                                   C.POINTER(CCorrelation)]),
+                       ("monte_carlo_correlated", [C.POINTER(CMonteCarlo), C.POINTER(CDisturbance), C.POINTER(CCorrelation)])):
+        for sfx in ("f32", "group_f32") + (() if stem.endswith(("disturbed", "correlated")) else ("f64",)):     # (those: float32 only)
             f = getattr(L, "acas2d_%s_%s" % (stem, sfx))
             f.restype = C.c_int
             f.argtypes = head + tail + [C.c_void_p]
@@ -237,6 +248,7 @@ def lib():
     L.acas2d_disturbance_draw_f32.argtypes = [C.c_uint64, C.c_int64, C.c_int32, C.c_uint32, C.c_int32, C.c_int32, C.c_int32,
                                               C.c_void_p, C.c_void_p]
     L.acas2d_disturbance_size.restype = C.c_size_t
+    L.acas2d_correlation_size.restype = C.c_size_t
     for name in ("acas2d_encounter_sample_f32", "acas2d_encounter_sample_f64"):
         f = getattr(L, name)
         f.restype = C.c_int
@@ -319,7 +331,7 @@ def lib():
     for name, twin in (("member_episodes", CMemberEpisodes), ("population_exploit", CPopulationExploit),
                        ("ppo_guard", CPpoGuard), ("ppo_options", CPpoOptions), ("reward_norm", CRewardNorm),
                        ("monte_carlo", CMonteCarlo), ("encounter_search", CEncounterSearch),
-                       ("disturbance", CDisturbance)):
+                       ("disturbance", CDisturbance), ("correlation", CCorrelation)):
         size = getattr(L, "acas2d_%s_size" % name)()
         if size != C.sizeof(twin):
             raise NativeLibraryError("%s layout mismatch: %d != %d" % (twin.__name__, size, C.sizeof(twin)))

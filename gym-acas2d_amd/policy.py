@@ -253,6 +253,95 @@ class Disturbance:
         return native.CDisturbance(self.s_sep, self.s_cpa, self.s_closing, self.s_action, self.seed, int(noise_episode), 0)
 
 
+@dataclasses.dataclass(frozen=True, init=False)
+class CorrelatedDisturbance(Disturbance):
+    """A Disturbance whose errors PERSIST: per channel a first-order Gauss-Markov process e_t = rho e_{t-1} + sqrt(1 - rho^2) z_t
+    (e_1 = z_1 at an episode's first step) takes the place of the white normal z_t, for the float32 evaluator and Monte Carlo
+    campaign (acas2d_evaluate_policies_correlated_*, acas2d_monte_carlo_correlated_*; records.correlated_errors() is the
+    scan).  The standard deviations stay what Disturbance says: e has unit variance at every step.
+
+    rho_sep, rho_cpa, rho_closing, rho_action   the step-to-step correlation of each channel's error, in [0, 1] (float32, as
+               the kernels read them; shared by all traffic aircraft).  0: the white noise of Disturbance, bit for bit;
+               1: a constant offset s z_1 per (lane, episode, channel, aircraft), a bias.
+    rho        shorthand for all four (one given by name overrides it).
+    A CorrelatedDisturbance never equals a Disturbance, not even with all four 0: to_dict() carries the rho keys.  The
+    collectors and trainers are white-noise only and refuse one (an episode spans their launches)."""
+    rho_sep: float
+    rho_cpa: float
+    rho_closing: float
+    rho_action: float
+
+    RHO = ("rho_sep", "rho_cpa", "rho_closing", "rho_action")
+
+    def __init__(self, sep=0.0, cpa=0.0, closing=0.0, action=0.0, seed=0, config=None, rho=0.0, rho_sep=None, rho_cpa=None,
+                 rho_closing=None, rho_action=None):
+        Disturbance.__init__(self, sep, cpa, closing, action, seed, config)
+        self._set_rho(rho, rho_sep, rho_cpa, rho_closing, rho_action)
+
+    def _set_rho(self, rho, *each):
+        for name, v in zip(self.RHO, each):
+            v = float(np.float32(rho if v is None else v))                   # the float32 the kernel reads
+            if not 0.0 <= v <= 1.0:                                          # (a NaN fails both comparisons)
+                raise ValueError("%s = %r (every correlation coefficient must lie in [0, 1])" % (name, v))
+            object.__setattr__(self, name, v)
+
+    @classmethod
+    def normalised(cls, sep=0.0, cpa=0.0, closing=0.0, action=0.0, seed=0, rho=0.0, rho_sep=None, rho_cpa=None, rho_closing=None,
+                   rho_action=None):
+        d = object.__new__(cls)
+        d._set(sep, cpa, closing, action, seed)
+        d._set_rho(rho, rho_sep, rho_cpa, rho_closing, rho_action)
+        return d
+
+    @property
+    def rho(self):
+        """(rho_sep, rho_cpa, rho_closing): per channel, as `sigma`."""
+        return (self.rho_sep, self.rho_cpa, self.rho_closing)
+
+    def to_dict(self):
+        return {**Disturbance.to_dict(self), **{name: getattr(self, name) for name in self.RHO}}
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls.normalised(d["s_sep"], d["s_cpa"], d["s_closing"], d["s_action"], d["seed"],
+                              **{name: d[name] for name in cls.RHO})
+
+    @classmethod
+    def parse(cls, text, normalised=False, config=None):
+        """Disturbance.parse()'s syntax with rho_sep=, rho_cpa=, rho_closing=, rho_action= and rho= (all four) on top."""
+        kw, rest = {}, []
+        for item in str(text).split(","):
+            key, _, val = (part.strip() for part in item.partition("="))
+            if key != "rho" and key not in cls.RHO:
+                rest.append(item)
+                continue
+            if not val or key in kw:
+                raise ValueError("disturbance %r: %r (rho=, rho_sep=, rho_cpa=, rho_closing= and rho_action= are understood, "
+                                 "each once)" % (text, item))
+            try:
+                kw[key] = float(val)
+            except ValueError:
+                raise ValueError("disturbance %r: %r is no number" % (text, item)) from None
+        base = Disturbance.parse(",".join(rest), normalised, config) if rest else Disturbance()
+        return cls.normalised(base.s_sep, base.s_cpa, base.s_closing, base.s_action, base.seed, **kw)
+
+    @staticmethod
+    def has_rho(text):
+        """Whether a command-line disturbance names a correlation: else it is a plain Disturbance's text."""
+        return any(item.partition("=")[0].strip().startswith("rho") for item in str(text).split(","))
+
+    def to_c(self, noise_episode=0):
+        """Both structs: (Acas2dDisturbance, Acas2dCorrelation)."""
+        return (Disturbance.to_c(self, noise_episode),
+                native.CCorrelation(self.rho_sep, self.rho_cpa, self.rho_closing, self.rho_action))
+
+
+def _c_tail(disturbance, noise_episode=0):
+    """The C structs a disturbance adds behind a scoring entry's own arguments: one, or (correlated) two."""
+    c = disturbance.to_c(noise_episode)
+    return list(c) if isinstance(c, tuple) else [c]
+
+
 class DisturbanceSet:
     """The disturbances K learners train under (ACAS2DVecEnv.collect(disturbance=) / collect_set(disturbances=), the
     trainers): one Disturbance for all members or K of them with EQUAL seeds -- the collector takes one noise seed per
@@ -268,6 +357,9 @@ class DisturbanceSet:
         ds = [disturbances] * K if isinstance(disturbances, Disturbance) else list(disturbances)
         if not all(isinstance(d, Disturbance) for d in ds):
             raise TypeError("a Disturbance, or one per member, is required, got %r" % (disturbances,))
+        if any(isinstance(d, CorrelatedDisturbance) for d in ds):
+            raise ValueError("the collectors are white-noise only: a CorrelatedDisturbance is for evaluate_policies_fused() and "
+                             "MonteCarlo (in a collector an episode spans launches, and the error state does not persist)")
         if len(ds) != K:
             raise ValueError("one Disturbance, or one per member, is required: got %d for %d member(s)" % (len(ds), K))
         for k, d in enumerate(ds):
@@ -313,13 +405,14 @@ def disturbance_draw(seed, first_lane, n_lanes, episode, first_step, n_steps, n_
     return out.cpu().numpy()
 
 
-def _scoring_entry(caller, stem, dtype, group, disturbed):
-    """The scoring family's C entry for (dtype, group, disturbed); group and disturbed are float32 only, and `caller` says so."""
-    for flag, on in (("group=True", group), ("disturbance=...", disturbed)):
+def _scoring_entry(caller, stem, dtype, group, disturbed, correlated=False):
+    """The scoring family's C entry for (dtype, group, disturbed, correlated); group, disturbed and correlated are float32 only,
+    and `caller` says so."""
+    for flag, on in (("group=True", group), ("disturbance=...", disturbed or correlated)):
         if on and dtype != torch.float32:
             raise ValueError("%s(%s) is float32 only, got %s" % (caller, flag, dtype))
-    if disturbed:
-        stem = stem.replace("_stats", "") + "_disturbed"
+    if disturbed or correlated:
+        stem = stem.replace("_stats", "") + ("_correlated" if correlated else "_disturbed")
     return "acas2d_%s%s_%s" % (stem, "_group" if group else "", "f32" if dtype == torch.float32 else "f64")
 
 
@@ -357,10 +450,10 @@ class PolicyBlocks:
             obs.data_ptr(), n_steps, venv.seed_value, venv.env_offset, venv.n_traffic, *tail, venv._stream()))
 
 
-def evaluate_policies_entry(dtype, group=False, safety=False, disturbed=False):
-    """The name of the C entry point evaluate_policies_fused() calls for (dtype, group, safety, disturbed)."""
+def evaluate_policies_entry(dtype, group=False, safety=False, disturbed=False, correlated=False):
+    """The name of the C entry point evaluate_policies_fused() calls for (dtype, group, safety, disturbed, correlated)."""
     return _scoring_entry("evaluate_policies_fused", "evaluate_policies_stats" if safety else "evaluate_policies", dtype, group,
-                          disturbed)
+                          disturbed, correlated)
 
 
 def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float64, device="cuda:0", config=None,
@@ -381,14 +474,16 @@ def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float
     disturbance=Disturbance(...): the float32 launch under sensor noise and actuator disturbance
     (acas2d_evaluate_policies_disturbed_*; it always computes the statistics, so the six keys are returned whatever
     `safety` says).  Episode i draws the noise of lane env_offset + i and episode counter `noise_episode`: what lane i of a
-    MonteCarlo campaign with the same disturbance and env_offset met in its episode `noise_episode`."""
+    MonteCarlo campaign with the same disturbance and env_offset met in its episode `noise_episode`.
+    A CorrelatedDisturbance takes the launch under time-correlated and biased errors (acas2d_evaluate_policies_correlated_*)."""
     from .vec_env import ACAS2DVecEnv
     if not policies:
         raise ValueError("evaluate_policies_fused needs at least one policy")
     if disturbance is None:
         entry = evaluate_policies_entry(dtype, group, safety)
     else:
-        safety, entry = True, evaluate_policies_entry(dtype, group, True, disturbed=True)
+        safety, entry = True, evaluate_policies_entry(dtype, group, True, disturbed=True,
+                                                      correlated=isinstance(disturbance, CorrelatedDisturbance))
     own, traffic = np.asarray(own), np.asarray(traffic)
     E, N = own.shape[0], traffic.shape[1]
     if config is None:
@@ -410,7 +505,7 @@ def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float
         st_i = torch.empty(2, K, E, dtype=torch.int32, device=dev)              # min_sep_step, los_steps
         tail.append(blocks.c_eval_stats(st_f, st_i))
     if disturbance is not None:
-        tail.append(disturbance.to_c(noise_episode))
+        tail.extend(_c_tail(disturbance, noise_episode))
     with torch.cuda.device(dev):
         blocks.call(entry, v, v.outputs["obs"], T, *tail)
     oc, st = outcome.cpu().numpy(), steps.cpu().numpy()
@@ -425,9 +520,9 @@ def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float
     return res
 
 
-def monte_carlo_entry(dtype, group=False, disturbed=False):
-    """The name of the C entry point MonteCarlo launches for (dtype, group, disturbed)."""
-    return _scoring_entry("MonteCarlo", "monte_carlo", dtype, group, disturbed)
+def monte_carlo_entry(dtype, group=False, disturbed=False, correlated=False):
+    """The name of the C entry point MonteCarlo launches for (dtype, group, disturbed, correlated)."""
+    return _scoring_entry("MonteCarlo", "monte_carlo", dtype, group, disturbed, correlated)
 
 
 class MonteCarlo:
@@ -447,7 +542,8 @@ class MonteCarlo:
     disturbance  a Disturbance: the campaign under sensor noise and actuator disturbance (acas2d_monte_carlo_disturbed_*,
                float32).  The noise of (lane, counter) is a function of the disturbance's seed, env_offset + lane, the counter
                and the step alone, so the K policies meet the same noise on the same encounters, and encounter() names
-               everything a replay needs.
+               everything a replay needs.  A CorrelatedDisturbance: the campaign under time-correlated and biased errors
+               (acas2d_monte_carlo_correlated_*); a lane's error processes restart with every episode it draws.
     """
 
     def __init__(self, policies, n_lanes, seed=13, dtype=torch.float32, group=False, config=None, n_traffic=1, n_bins=64,
@@ -455,7 +551,8 @@ class MonteCarlo:
         from .vec_env import ACAS2DVecEnv
         if not policies:
             raise ValueError("MonteCarlo needs at least one policy")
-        self.entry = monte_carlo_entry(dtype, group) if disturbance is None else monte_carlo_entry(dtype, group, disturbed=True)
+        self.entry = monte_carlo_entry(dtype, group) if disturbance is None else monte_carlo_entry(
+            dtype, group, disturbed=True, correlated=isinstance(disturbance, CorrelatedDisturbance))
         self.disturbance = disturbance
         self.config = config if config is not None else ACAS2DConfig(n_traffic=n_traffic)
         self.n_lanes, self.n_policies, self.dtype, self.seed = int(n_lanes), len(policies), dtype, int(seed)
@@ -494,7 +591,7 @@ class MonteCarlo:
             mc = native.CMonteCarlo(*[self._acc[k].data_ptr() for k in records.MONTE_CARLO_KEYS], self.n_bins, int(episodes),
                                     self.inv_bin_width, self.first_episode, 0)
             n_steps = max(int(episodes), 0) * self.config.max_steps
-            tail = [mc] if self.disturbance is None else [mc, self.disturbance.to_c()]
+            tail = [mc] if self.disturbance is None else [mc] + _c_tail(self.disturbance)
             if events:
                 events[0].record()
             self._blocks.call(self.entry, dst, dst._obs, n_steps, *tail)      # (dst has src's seed, env_offset and n_traffic)

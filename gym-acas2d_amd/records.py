@@ -466,3 +466,35 @@ def disturb_action(action, s_action, normal):
     """The action the aircraft flies: the actor's clipped action + s_action z in float32 (two roundings), held to [-1, 1]
     again; a NaN stays a NaN; s_action == 0 leaves it untouched."""
     return _disturbed(action, s_action, normal, -1.0, 1.0)
+
+
+# ---- time-correlated and biased errors (acas2d_evaluate_policies_correlated_*, acas2d_monte_carlo_correlated_*) -------------
+def correlation_gain(rho):
+    """The gain q = (float32) sqrt(1 - rho^2) of a channel's Gauss-Markov error, rho a float32 in [0, 1] (arrays: elementwise):
+    the square and the difference in float64 (both exact enough that the correctly rounded float64 root, then ONE rounding to
+    float32, is what the C entry forms with sqrt())."""
+    r = np.asarray(rho, np.float32)
+    if not ((r >= 0) & (r <= 1)).all():                                          # (a NaN fails both comparisons)
+        raise ValueError("correlation_gain: rho = %r (each in [0, 1])" % (rho,))
+    r = r.astype(np.float64)
+    return np.sqrt(1.0 - r * r).astype(np.float32)
+
+
+def correlated_errors(normals, rho):
+    """The errors e_t that take the normals' place: `normals` [steps, ...] float32 from an episode's FIRST step on (axis 0 is
+    the step), rho a float32 in [0, 1] or an array of them that broadcasts against normals[0] (e.g. one per channel of a last
+    axis).  e_0 = z_0;  e_t = (rho e_{t-1}) + (q z_t) in float32 -- two products and a sum, each rounded, no fma -- with
+    q = correlation_gain(rho).  Where rho == 0 the result is z's own bits (no arithmetic); rho == 1 repeats e_0."""
+    z = np.asarray(normals, np.float32)
+    if z.ndim < 1:
+        raise ValueError("correlated_errors: normals [steps, ...] are required")
+    rho_b = np.broadcast_to(np.asarray(rho, np.float32), z.shape[1:])
+    q = correlation_gain(rho_b)
+    white = rho_b == 0
+    e = z.copy()
+    with np.errstate(invalid="ignore", over="ignore"):
+        for t in range(1, z.shape[0]):
+            a = (rho_b * e[t - 1]).astype(np.float32)
+            b = (q * z[t]).astype(np.float32)
+            e[t] = np.where(white, z[t], (a + b).astype(np.float32))
+    return e

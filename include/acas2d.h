@@ -511,6 +511,55 @@ int acas2d_disturbance_draw_f32(uint64_t noise_seed, int64_t first_lane, int32_t
                                 int32_t first_step, int32_t n_steps, int32_t n_slots, float *out, void *stream);
 
 /*
+ * acas2d_evaluate_policies_correlated_f32 / _group_f32, acas2d_monte_carlo_correlated_f32 / _group_f32: the disturbed
+ * entries above with an error that PERSISTS -- a first-order Gauss-Markov process per channel in place of the white
+ * normals.  Additive to ABI 7, float32 only.  The arguments of the _disturbed sibling with `correlation` in front of
+ * `stream`; the same work shapes, the same rejections in the same words.
+ *   One coefficient rho in [0, 1] per channel (separation, closest-point-of-approach distance, closing speed, action),
+ *   shared by all traffic aircraft, and one process per (traffic aircraft, channel) and one for the actuator: 3 N + 1
+ *   values of state per env, local to the launch.  With z_t the sibling's normal of the step (the same block at the same
+ *   counter: nothing about the draws changes) the error that takes z_t's place everywhere is
+ *     e_t = z_t                                    at the first step a lane plays of an episode in this launch: its first
+ *                                                  step of the launch, and the first step after an in-step reset;
+ *     e_t = (rho * e_{t-1}) + (q * z_t)            otherwise: two float32 multiplies and a float32 add, each rounded, no fma,
+ *   with the gain q = (float)sqrt(1.0 - (double)rho * (double)rho) formed on the host.  e has unit variance at every step,
+ *   so s stays the standard deviation.  A channel whose rho is exactly 0 takes e_t = z_t and does no arithmetic: with all
+ *   four 0 the results equal the _disturbed entries' bit for bit.  rho = 1 gives q = 0 and e_t = e_1: a constant offset
+ *   s * z_1 per (lane, episode, channel, aircraft).  x + s * e, the box and "s == 0 leaves the channel alone" are the
+ *   sibling's.  acas2d_disturbance_draw_f32 and a scan on the host reproduce any episode.
+ * Rejected with ACAS2D_EINVAL before anything is launched: everything the _disturbed sibling rejects, in its words and its
+ * order; then a NULL correlation; then a rho that is NaN, negative or above 1.
+ */
+typedef struct Acas2dCorrelation {
+    float rho_sep, rho_cpa, rho_closing;   /* the step-to-step correlation of each observation channel's error */
+    float rho_action;                      /* ... and of the actuator's */
+} Acas2dCorrelation;
+size_t acas2d_correlation_size(void);  /* sizeof(Acas2dCorrelation), for bindings */
+int acas2d_evaluate_policies_correlated_f32(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                                            const Acas2dPolicy *policies, int32_t n_policies, int32_t n_episodes,
+                                            const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
+                                            int32_t n_traffic, uint8_t *outcome, int32_t *steps, void *total_reward,
+                                            const Acas2dEvalStats *stats, const Acas2dDisturbance *disturbance,
+                                            const Acas2dCorrelation *correlation, void *stream);
+int acas2d_evaluate_policies_correlated_group_f32(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                                                  const Acas2dPolicy *policies, int32_t n_policies, int32_t n_episodes,
+                                                  const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
+                                                  int32_t n_traffic, uint8_t *outcome, int32_t *steps, void *total_reward,
+                                                  const Acas2dEvalStats *stats, const Acas2dDisturbance *disturbance,
+                                                  const Acas2dCorrelation *correlation, void *stream);
+int acas2d_monte_carlo_correlated_f32(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                                      const Acas2dPolicy *policies, int32_t n_policies, int32_t n_lanes, const void *obs_in,
+                                      int32_t n_steps, uint64_t seed, int64_t env_offset, int32_t n_traffic,
+                                      const Acas2dMonteCarlo *mc, const Acas2dDisturbance *disturbance,
+                                      const Acas2dCorrelation *correlation, void *stream);
+int acas2d_monte_carlo_correlated_group_f32(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                                            const Acas2dPolicy *policies, int32_t n_policies, int32_t n_lanes,
+                                            const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
+                                            int32_t n_traffic, const Acas2dMonteCarlo *mc,
+                                            const Acas2dDisturbance *disturbance, const Acas2dCorrelation *correlation,
+                                            void *stream);
+
+/*
  * acas2d_collect_set_disturbed_f32 / acas2d_collect_set_disturbed_group_f32: acas2d_collect_set_f32 / _group_f32 under the
  * sensor noise and actuator disturbance above -- the collector of a PPO iteration that TRAINS under them.  Additive to
  * ABI 7, float32 only.  The siblings' arguments, then `sigmas`, `dist_seed` and `obs_read` in front of `stream`.

@@ -14,6 +14,9 @@ each checkpoint's risk ratio against it.  --disturbance sep=PX,cpa=PX,closing=V,
 white sensor noise (standard deviations in pixels and in the units of v_closing, per traffic aircraft and step) and actuator
 disturbance (in units of the action) -- policy.Disturbance, float32; the flag may be repeated to sweep levels: the same
 encounters at every level, the checkpoint lines of each level carrying its disturbance, and one summary line per level.
+With rho=R (all four channels) or rho_sep=, rho_cpa=, rho_closing=, rho_action= among the keys the errors persist: a
+first-order Gauss-Markov process per channel with step-to-step correlation R in [0, 1], 1 being a constant bias per episode
+(policy.CorrelatedDisturbance); a string without them is the white noise it has always been.
 --search CANDIDATESxGENERATIONS instead runs an encounter search per checkpoint (policy.EncounterSearch: cross-entropy
 proposals refit on the device, importance-sampling weights): one JSON line per checkpoint gives the estimated probability of
 min_separation <= the collision distance with its standard error, beside a crude campaign of the same number of episodes
@@ -25,6 +28,7 @@ closest encounter found.
     python tools/evaluate_checkpoints.py DIR --monte-carlo 65536x64 [--baseline-zero] [--dtype float32]
     python tools/evaluate_checkpoints.py DIR --monte-carlo 65536x8 --dtype float32 --baseline-zero \
         --disturbance sep=0,cpa=0,closing=0,action=0 --disturbance sep=90,cpa=40,closing=8,action=0.1,seed=7
+    python tools/evaluate_checkpoints.py DIR --monte-carlo 65536x8 --dtype float32 --disturbance sep=90,cpa=40,rho=0.99,seed=7
 """
 import argparse
 import glob
@@ -54,6 +58,11 @@ args = ap.parse_args()
 
 
 def parse_disturbance(text):
+    if g.policy.CorrelatedDisturbance.has_rho(text):     # a Gauss-Markov error per channel: policy.CorrelatedDisturbance
+        try:
+            return g.policy.CorrelatedDisturbance.parse(text)
+        except ValueError as e:
+            sys.exit("--disturbance: %s" % e)
     kw = {}
     for item in text.split(","):
         key, _, val = item.partition("=")
