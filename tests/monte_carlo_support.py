@@ -1,4 +1,5 @@
-"""Shared by tests/test_monte_carlo.py: the campaign's shapes and its reference -- the existing entries, folded on the host.
+"""Shared by tests/test_monte_carlo.py and tests/noise_scoring_support.py: the campaign's shapes and its reference -- the
+existing entries, folded on the host.
 
 Reference (no new arithmetic, no tolerance): for every episode counter c, ACAS2DVecEnv.reset_to_episode(c) on an n_lanes-env
 engine of the campaign's seed, dtype and config draws the encounters, their state is read back, and
@@ -62,22 +63,25 @@ def inv_bin_width(g, s):
 _RESULTS = {}
 
 
-def per_counter(g, s):
-    """The stats evaluator's result dicts of [a, b, zero] for counters 0 .. COUNTERS - 1 at shape s."""
-    if s not in _RESULTS:
+def per_counter(g, s, fl=None):
+    """The stats evaluator's result dicts of [a, b, zero] for counters 0 .. COUNTERS - 1 at shape s.  fl (a
+    noise_scoring_support.Flavour): the noisy evaluator's under fl.disturbance(g), counter c with the noise of episode c,
+    for counters 0 .. EPISODES - 1."""
+    key = (fl and fl.name, s)
+    if key not in _RESULTS:
         cfg = config(g, s)
         v = g.ACAS2DVecEnv(LANES, s.N, device=DEV, dtype=s.dtype, seed=SEED, config=cfg)
         out = []
-        for c in range(COUNTERS):
+        for c in range(EPISODES if fl else COUNTERS):
             v.reset_to_episode(c)
             own, trf, goal = g.policy.read_state(v)
             res = g.evaluate_policies_fused(policies(g, s), own, trf, goal, dtype=s.dtype, device=DEV, config=cfg, group=s.group,
-                                            safety=True)
+                                            safety=True, disturbance=fl and fl.disturbance(g), noise_episode=c)
             for a in res.values():
                 a.setflags(write=False)
             out.append(res)
-        _RESULTS[s] = out
-    return _RESULTS[s]
+        _RESULTS[key] = out
+    return _RESULTS[key]
 
 
 def reference(g, s, counters=EPISODES, rows=None):

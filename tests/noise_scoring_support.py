@@ -1,0 +1,209 @@
+"""Shared by tests/test_disturbance.py and tests/test_correlated.py: the shapes, the host loop the noisy evaluators are held
+to, the campaign's reference and the properties a campaign is used for -- once each, for every error model.
+
+A Flavour names an error model and builds its test disturbance; the cached helpers are keyed by its name.  The sigmas are
+the same for all of them, so the white campaign is the correlated one's at every rho 0 and both files share its run.
+
+References (no new arithmetic, no tolerance):
+  evaluator  host_loop(): per step the observation of a latching env, records.disturb_observation() with the errors of the
+             draw entry's normals, the project's in-kernel network through a one-step rollout_policy() on a scratch env,
+             records.disturb_action(), the latching step with record_trace=True, and records.episode_safety() on the trace;
+  campaign   monte_carlo_support.per_counter() under the flavour's disturbance -- reset_to_episode(c) + the noisy evaluator
+             with noise_episode = c -- folded by records.monte_carlo_reduce().
+One of each per (flavour, shape), computed once and left unchanged."""
+from collections import namedtuple
+
+import numpy as np
+import pytest
+import torch
+
+import eval_stats_support as ES
+import monte_carlo_support as MS
+
+DEV = ES.DEV
+F32 = torch.float32
+# (n_traffic, group)
+EVAL_SHAPES = ((1, False), (3, False), (8, False), (16, True), (64, True))
+ZERO_SHAPES = EVAL_SHAPES[:4]
+CAMPAIGN_SHAPES = [MS.Shape(F32, True, n, grp, max_steps) for max_steps in (1000, 150) for n, grp in ((1, False), (8, False), (16, True))]
+NOISE_EPISODE = 5
+SIGMAS = dict(sep=0.05, cpa=0.1, closing=0.1, action=0.3, seed=7)
+
+# disturbance(g): the flavour's one test disturbance; errors(g, dist, N): host_loop()'s `errors` under it, or None
+Flavour = namedtuple("Flavour", "name disturbance errors", defaults=(None,))
+WHITE = Flavour("white", lambda g: g.Disturbance.normalised(**SIGMAS))
+
+
+def shape_id(s):
+    return "N%d%s" % (s[0], "-group" if s[1] else "")
+
+
+EVAL_IDS = [shape_id(s) for s in EVAL_SHAPES]
+CAMPAIGN = pytest.mark.parametrize("s", CAMPAIGN_SHAPES, ids=[MS.shape_id(s) for s in CAMPAIGN_SHAPES])
+
+
+def fused(g, N, group, **kw):
+    cfg = ES.config(g, N)
+    eps = ES.episodes(cfg)
+    return g.evaluate_policies_fused(ES.two_policies(g, N), eps.own, eps.trf, eps.goal, dtype=F32, device=DEV, config=cfg,
+                                     group=group, safety=True, **kw)
+
+
+def same(g, got, want):
+    bad = MS.mismatches(g, got, want)
+    assert not bad, {k: (np.asarray(got[k]).ravel()[:6], np.asarray(want[k]).ravel()[:6]) for k in bad}
+
+
+# ---- the evaluator against a host loop -------------------------------------------------------------------------------------------------
+def host_loop(g, cfg, eps, policy, dist, noise_episode, group, errors=None):
+    """One policy's reference rows [E] by the per-step path: (outcome, steps, total_reward, stats dict, summary dict).
+    `errors`: from the drawn normals [step, lane, slot, 3] to the series the loop indexes; None: the normals themselves,
+    the white model."""
+    E, N = ES.E, cfg.n_traffic
+    n_steps = cfg.max_steps + 1
+    zero = np.zeros(E, np.int32)
+    # the normals of every step an episode can reach, from the draw entry: [step, lane, slot, 3] -- and the errors they drive
+    normals = g.policy.disturbance_draw(dist.seed, 0, E, noise_episode, 0, cfg.max_steps + 2, N + 1, device=DEV)
+    series = normals if errors is None else errors(normals)
+    r = g.ACAS2DVecEnv(E, N, device=DEV, dtype=F32, auto_reset=False, record_trace=True, config=cfg)
+    r.set_state(eps.own, eps.trf, eps.goal, zero, observe=True)
+    scratch = g.ACAS2DVecEnv(E, N, device=DEV, dtype=F32, auto_reset=True, config=cfg)
+    scratch.reset()
+    cols = [r.trace.clone()]
+    active = np.ones(E, bool)
+    outcome, steps, ret, t0 = np.zeros(E, np.uint8), np.zeros(E, np.int32), np.zeros(E, np.float32), np.zeros(E, np.int64)
+    lane = np.arange(E)
+    assert (r.steps.cpu().numpy() == 1).all()                          # every episode starts at game.steps == 1
+    for t in range(n_steps):
+        obs = r.outputs["obs"].cpu().numpy()
+        at = r.steps.cpu().numpy()                                     # game.steps before this step
+        z = series[np.minimum(at, series.shape[0] - 1), lane]         # [E, N + 1, 3] (latched envs: unused)
+        noisy = g.records.disturb_observation(obs, dist.sigma, z[:, 1:])
+        scratch.outputs["obs"].copy_(torch.as_tensor(noisy, device=DEV))
+        action = scratch.rollout_policy(policy, 1, group=group)["actions"][0].cpu().numpy()
+        flown = g.records.disturb_action(action, dist.s_action, z[:, 0, 0])
+        _, _, done, infos = r.step(torch.as_tensor(flown, device=DEV))
+        cols.append(r.trace.clone())
+        fin = active & done.cpu().numpy()
+        outcome[fin] = infos.outcome.cpu().numpy()[fin]
+        steps[fin] = r.steps.cpu().numpy()[fin]
+        ret[fin] = r.total_reward.cpu().numpy()[fin]
+        t0[fin] = t
+        active &= ~fin
+        if not active.any():
+            break
+    trace = torch.stack(cols).cpu().numpy()
+    names = list(g.vec_env.TRACE_COLUMNS)
+    c_sep, c_lat, c_dev = names.index("d_sep"), names.index("a_lat"), names.index("d_dev")
+    keys = ("min_sep", "min_sep_step", "los_steps", "max_a_lat", "max_dev", "sum_dev")
+    stats = {k: np.zeros(E, np.int32 if k in ("min_sep_step", "los_steps") else np.float32) for k in keys}
+    summary = {k: np.zeros(E, np.int32 if k in ("min_separation_step", "los_steps") else np.float32) for k in g.records.SAFETY_KEYS}
+    for i in np.nonzero(~active)[0]:
+        n = t0[i] + 2
+        assert n == steps[i]
+        one = g.records.episode_safety(trace[:n, i, c_sep], trace[:n, i, c_lat], trace[:n, i, c_dev], cfg.safe_distance, np.float32)
+        for k in keys:
+            stats[k][i] = one[k]
+        for k, val in g.records.safety_summary(one, int(steps[i])).items():
+            summary[k][i] = val
+    return outcome, steps, ret, stats, summary
+
+
+_LOOP, _RAN = {}, {}
+
+
+def loop_reference(g, fl, N, group):
+    """host_loop()'s rows of eval_stats_support's two policies under the flavour's disturbance at NOISE_EPISODE."""
+    if (fl.name, N, group) not in _LOOP:
+        cfg = ES.config(g, N)
+        eps = ES.episodes(cfg)
+        dist = fl.disturbance(g)
+        errors = fl.errors and fl.errors(g, dist, N)
+        _LOOP[fl.name, N, group] = [host_loop(g, cfg, eps, pol, dist, NOISE_EPISODE, group, errors) for pol in ES.two_policies(g, N)]
+    return _LOOP[fl.name, N, group]
+
+
+def evaluator_equals_the_host_loop(g, fl, shape):
+    """The fused evaluator's rows against loop_reference()'s, bit for bit."""
+    N, group = shape
+    got = fused(g, N, group, disturbance=fl.disturbance(g), noise_episode=NOISE_EPISODE)
+    for k, (outcome, steps, ret, stats, summary) in enumerate(loop_reference(g, fl, N, group)):
+        assert np.array_equal(got["outcome"][k], outcome) and np.array_equal(got["steps"][k], steps), k
+        assert ES.bits_equal(got["total_reward"][k].astype(np.float32), ret), k
+        for key in g.records.SAFETY_KEYS:
+            assert ES.bits_equal(got[key][k], summary[key]), (k, key)
+    # the counter is part of the noise
+    other = fused(g, N, group, disturbance=fl.disturbance(g), noise_episode=NOISE_EPISODE + 1)
+    assert not ES.bits_equal(other["max_abs_a_lat"], got["max_abs_a_lat"])
+
+
+# ---- the campaign against the evaluator ------------------------------------------------------------------------------------------------
+def per_counter(g, fl, s):
+    """The flavour's evaluator's result dicts of [a, b, zero] for counters 0 .. EPISODES - 1 at shape s."""
+    return MS.per_counter(g, s, fl)
+
+
+def reference(g, fl, s, rows=None):
+    res = per_counter(g, fl, s)
+    if rows is not None:
+        res = [{k: v[list(rows)] for k, v in r.items() if np.ndim(v) == 2} for r in res]
+    return g.records.monte_carlo_reduce(res, MS.N_BINS, MS.inv_bin_width(g, s), np.float32)
+
+
+def campaign(g, fl, s, **kw):
+    return MS.campaign(g, s, disturbance=fl.disturbance(g), **kw)
+
+
+def ran(g, fl, s):
+    """The accumulators of the flavour's campaign after EPISODES episodes in one launch."""
+    if (fl.name, s) not in _RAN:
+        acc = campaign(g, fl, s).run(MS.EPISODES).accumulators()
+        for a in acc.values():
+            a.setflags(write=False)
+        _RAN[fl.name, s] = acc
+    return _RAN[fl.name, s]
+
+
+# ---- the properties a campaign is used for ----------------------------------------------------------------------------------------------
+def chaining(g, fl, s):
+    same(g, campaign(g, fl, s).run(2).run(1).accumulators(), ran(g, fl, s))
+    same(g, campaign(g, fl, s).run(MS.EPISODES, per_launch=1).accumulators(), ran(g, fl, s))      # (ran: per_launch >= EPISODES)
+
+
+def survives_a_state_dict(g, fl, s, others, foreign, fields=None):
+    """... and another disturbance is another campaign: a campaign under any of `others` (None: undisturbed) refuses the
+    state, and this one refuses the state of a campaign under `foreign`.  `fields`: what the state's disturbance must say
+    beyond to_dict(), as float32."""
+    first = campaign(g, fl, s).run(2)
+    sd = first.state_dict()
+    assert sd["first_episode"] == 2 and sd["disturbance"] == fl.disturbance(g).to_dict()
+    assert all(sd["disturbance"][k] == np.float32(v) for k, v in (fields or {}).items())
+    second = campaign(g, fl, s).load_state_dict(sd).run(1)
+    assert second.first_episode == 3
+    same(g, second.accumulators(), ran(g, fl, s))
+    for other in others:
+        with pytest.raises(ValueError, match="disturbance"):
+            MS.campaign(g, s, disturbance=other).load_state_dict(sd)
+    with pytest.raises(ValueError, match="disturbance"):
+        campaign(g, fl, s).load_state_dict(MS.campaign(g, s, disturbance=foreign).state_dict())
+
+
+def common_random_numbers(g, fl, s):
+    """Policy b alone meets the encounters AND the errors it meets among [a, b, zero]."""
+    b = MS.policies(g, s)[1]
+    alone = campaign(g, fl, s, pols=[b]).run(MS.EPISODES).accumulators()
+    same(g, alone, {k: v[[1]] for k, v in ran(g, fl, s).items()})
+
+
+def encounter_closes_the_loop(g, fl, s):
+    mc = campaign(g, fl, s).run(MS.EPISODES)
+    acc = ran(g, fl, s)
+    assert mc.summary()["disturbance"] == fl.disturbance(g).to_dict()
+    for k, top in enumerate(mc.worst(1)):
+        (lane, counter, sep), = top
+        assert sep == acc["lane_worst_sep"][k].min() and counter == acc["lane_worst_episode"][k, lane]
+        own, trf, goal, replay = mc.encounter(lane, counter)
+        assert replay == {"disturbance": fl.disturbance(g), "noise_episode": counter, "env_offset": lane}
+        res = g.evaluate_policies_fused(MS.policies(g, s), own, trf, goal, dtype=F32, device=DEV, config=MS.config(g, s),
+                                        group=s.group, safety=True, **replay)
+        assert ES.bits_equal(res["min_separation"][k, :1], np.asarray([sep], np.float32))

@@ -2,14 +2,16 @@
 policy.CorrelatedDisturbance): a first-order Gauss-Markov error per channel in the white normals' place.
 
   1  all four rho 0: the disturbed entries' bits, evaluator and campaign;
-  2  the correlated evaluator against the host loop of tests/test_disturbance.py, restated here with
-     records.correlated_errors() of the draw entry's normals in the normals' place -- no other new arithmetic;
+  2  the correlated evaluator against the host loop of tests/noise_scoring_support.py with records.correlated_errors() of
+     the draw entry's normals in the normals' place -- no other new arithmetic;
   3  the correlated campaign against reset_to_episode(c) + that evaluator folded by records.monte_carlo_reduce() (a state
      carried over an in-step reset fails here), and the properties a campaign is used for;
   4  the limits: rho_action = 1 is a constant action offset, and a network of zeros ignores correlated sensors too;
   5  refusals.
 
-One test disturbance throughout: the sigmas of tests/test_disturbance.py with rho_sep = 0.9, rho_cpa = 1 (a bias),
+The shapes, the host loop, the campaign's reference and the campaign properties are tests/noise_scoring_support.py's, shared
+with tests/test_disturbance.py (whose white campaign is taken from the shared cache); CORRELATED is this file's flavour of
+them.  One test disturbance throughout: the sigmas of tests/test_disturbance.py with rho_sep = 0.9, rho_cpa = 1 (a bias),
 rho_closing = 0 (white) and rho_action = 0.5 -- all three branches in every launch.  70 episodes / lanes: one full wave and a
 partial one thread per env, 18 waves at the (4, 16) group shape: the smallest at which a lane restarts while its neighbours
 go on."""
@@ -19,25 +21,29 @@ import torch
 
 import eval_stats_support as ES
 import monte_carlo_support as MS
+import noise_scoring_support as NS
+from noise_scoring_support import (CAMPAIGN, CAMPAIGN_SHAPES, EVAL_IDS, EVAL_SHAPES, NOISE_EPISODE, SIGMAS, WHITE, ZERO_SHAPES, fused, ran,
+                                   reference, same)
 
 pytestmark = pytest.mark.gpu
 DEV = ES.DEV
 F32 = torch.float32
-# (n_traffic, group): the shapes of tests/test_disturbance.py
-EVAL_SHAPES = ((1, False), (3, False), (8, False), (16, True), (64, True))
-ZERO_SHAPES = EVAL_SHAPES[:4]
-CAMPAIGN_SHAPES = [MS.Shape(F32, True, n, grp, max_steps) for max_steps in (1000, 150) for n, grp in ((1, False), (8, False), (16, True))]
-NOISE_EPISODE = 5
-SIGMAS = dict(sep=0.05, cpa=0.1, closing=0.1, action=0.3, seed=7)
 RHO = dict(rho_sep=0.9, rho_cpa=1.0, rho_closing=0.0, rho_action=0.5)
 
 
-def shape_id(s):
-    return "N%d%s" % (s[0], "-group" if s[1] else "")
+def rho_of_slots(dist, N):
+    """[N + 1, 3]: the coefficient of every value of a lane's draw -- slot 0 the actuator's normal (and two zeros), slot n + 1
+    traffic n's three channels."""
+    return np.asarray([[dist.rho_action, 0.0, 0.0]] + [list(dist.rho)] * N, np.float32)
 
 
-EVAL_IDS = [shape_id(s) for s in EVAL_SHAPES]
-CAMPAIGN = pytest.mark.parametrize("s", CAMPAIGN_SHAPES, ids=[MS.shape_id(s) for s in CAMPAIGN_SHAPES])
+def errors(g, dist, N):
+    """The host loop's series under `dist`: the errors the normals drive, scanned from the episode's first step
+    (game.steps == 1) on."""
+    return lambda normals: np.concatenate([normals[:1], g.records.correlated_errors(normals[1:], rho_of_slots(dist, N))])
+
+
+CORRELATED = NS.Flavour("correlated", lambda g: g.CorrelatedDisturbance.normalised(**SIGMAS, **RHO), errors)
 
 
 @pytest.fixture(scope="module")
@@ -47,23 +53,11 @@ def g():
 
 
 def the_disturbance(g):
-    return g.CorrelatedDisturbance.normalised(**SIGMAS, **RHO)
+    return CORRELATED.disturbance(g)
 
 
 def the_white_disturbance(g):
-    return g.Disturbance.normalised(**SIGMAS)
-
-
-def fused(g, N, group, **kw):
-    cfg = ES.config(g, N)
-    eps = ES.episodes(cfg)
-    return g.evaluate_policies_fused(ES.two_policies(g, N), eps.own, eps.trf, eps.goal, dtype=F32, device=DEV, config=cfg,
-                                     group=group, safety=True, **kw)
-
-
-def same(g, got, want):
-    bad = MS.mismatches(g, got, want)
-    assert not bad, {k: (np.asarray(got[k]).ravel()[:6], np.asarray(want[k]).ravel()[:6]) for k in bad}
+    return WHITE.disturbance(g)
 
 
 # ---- 1: rho = 0 is the white noise ----------------------------------------------------------------------------------------------------
@@ -85,200 +79,57 @@ def test_zero_correlation_is_the_disturbed_campaign(g, shape):
     s = MS.Shape(F32, True, shape[0], shape[1], 150)
     mc = MS.campaign(g, s, disturbance=g.CorrelatedDisturbance.normalised(**SIGMAS))
     assert mc.entry == "acas2d_monte_carlo_correlated%s_f32" % ("_group" if s.group else "")
-    white = MS.campaign(g, s, disturbance=the_white_disturbance(g)).run(MS.EPISODES).accumulators()
+    white = ran(g, WHITE, s)
     same(g, mc.run(MS.EPISODES).accumulators(), white)
     assert white["outcome_count"].sum(1).tolist() == [MS.LANES * MS.EPISODES] * 3
 
 
 # ---- 2: the evaluator against a host loop ---------------------------------------------------------------------------------------------
-def rho_of_slots(dist, N):
-    """[N + 1, 3]: the coefficient of every value of a lane's draw -- slot 0 the actuator's normal (and two zeros), slot n + 1
-    traffic n's three channels."""
-    return np.asarray([[dist.rho_action, 0.0, 0.0]] + [list(dist.rho)] * N, np.float32)
-
-
-def host_loop(g, cfg, eps, policy, dist, noise_episode, group):
-    """One policy's reference rows [E] by the per-step path: (outcome, steps, total_reward, stats dict, summary dict).  The
-    loop of tests/test_disturbance.py; the one difference is `errors`."""
-    E, N = ES.E, cfg.n_traffic
-    n_steps = cfg.max_steps + 1
-    zero = np.zeros(E, np.int32)
-    # the normals of every step an episode can reach, from the draw entry: [step, lane, slot, 3] -- and the errors they drive,
-    # scanned from the episode's first step (game.steps == 1) on
-    normals = g.policy.disturbance_draw(dist.seed, 0, E, noise_episode, 0, cfg.max_steps + 2, N + 1, device=DEV)
-    errors = np.concatenate([normals[:1], g.records.correlated_errors(normals[1:], rho_of_slots(dist, N))])
-    r = g.ACAS2DVecEnv(E, N, device=DEV, dtype=F32, auto_reset=False, record_trace=True, config=cfg)
-    r.set_state(eps.own, eps.trf, eps.goal, zero, observe=True)
-    scratch = g.ACAS2DVecEnv(E, N, device=DEV, dtype=F32, auto_reset=True, config=cfg)
-    scratch.reset()
-    cols = [r.trace.clone()]
-    active = np.ones(E, bool)
-    outcome, steps, ret, t0 = np.zeros(E, np.uint8), np.zeros(E, np.int32), np.zeros(E, np.float32), np.zeros(E, np.int64)
-    lane = np.arange(E)
-    assert (r.steps.cpu().numpy() == 1).all()                          # every episode starts at game.steps == 1
-    for t in range(n_steps):
-        obs = r.outputs["obs"].cpu().numpy()
-        at = r.steps.cpu().numpy()                                     # game.steps before this step
-        z = errors[np.minimum(at, errors.shape[0] - 1), lane]         # [E, N + 1, 3] (latched envs: unused)
-        noisy = g.records.disturb_observation(obs, dist.sigma, z[:, 1:])
-        scratch.outputs["obs"].copy_(torch.as_tensor(noisy, device=DEV))
-        action = scratch.rollout_policy(policy, 1, group=group)["actions"][0].cpu().numpy()
-        flown = g.records.disturb_action(action, dist.s_action, z[:, 0, 0])
-        _, _, done, infos = r.step(torch.as_tensor(flown, device=DEV))
-        cols.append(r.trace.clone())
-        fin = active & done.cpu().numpy()
-        outcome[fin] = infos.outcome.cpu().numpy()[fin]
-        steps[fin] = r.steps.cpu().numpy()[fin]
-        ret[fin] = r.total_reward.cpu().numpy()[fin]
-        t0[fin] = t
-        active &= ~fin
-        if not active.any():
-            break
-    trace = torch.stack(cols).cpu().numpy()
-    names = list(g.vec_env.TRACE_COLUMNS)
-    c_sep, c_lat, c_dev = names.index("d_sep"), names.index("a_lat"), names.index("d_dev")
-    keys = ("min_sep", "min_sep_step", "los_steps", "max_a_lat", "max_dev", "sum_dev")
-    stats = {k: np.zeros(E, np.int32 if k in ("min_sep_step", "los_steps") else np.float32) for k in keys}
-    summary = {k: np.zeros(E, np.int32 if k in ("min_separation_step", "los_steps") else np.float32) for k in g.records.SAFETY_KEYS}
-    for i in np.nonzero(~active)[0]:
-        n = t0[i] + 2
-        assert n == steps[i]
-        one = g.records.episode_safety(trace[:n, i, c_sep], trace[:n, i, c_lat], trace[:n, i, c_dev], cfg.safe_distance, np.float32)
-        for k in keys:
-            stats[k][i] = one[k]
-        for k, val in g.records.safety_summary(one, int(steps[i])).items():
-            summary[k][i] = val
-    return outcome, steps, ret, stats, summary
-
-
-_LOOP = {}
-
-
-def loop_reference(g, N, group):
-    if (N, group) not in _LOOP:
-        cfg = ES.config(g, N)
-        eps = ES.episodes(cfg)
-        _LOOP[N, group] = [host_loop(g, cfg, eps, pol, the_disturbance(g), NOISE_EPISODE, group) for pol in ES.two_policies(g, N)]
-    return _LOOP[N, group]
-
-
 @pytest.mark.parametrize("shape", EVAL_SHAPES, ids=EVAL_IDS)
 def test_correlated_evaluator_equals_the_host_loop(g, shape):
     N, group = shape
-    rows = loop_reference(g, N, group)
+    rows = NS.loop_reference(g, CORRELATED, N, group)
     # teeth, on the reference alone: every episode finished, and against the WHITE entry (same sigmas, same seed: the parent's
     # kernel) the correlation moves the mean deviation of at least half of the episodes
     white = fused(g, N, group, disturbance=the_white_disturbance(g), noise_episode=NOISE_EPISODE)
     for k, row in enumerate(rows):
         assert (row[0] != 0).all(), "an episode of the reference did not finish"
         moved = int((ES.bits(row[4]["mean_abs_deviation"]) != ES.bits(white["mean_abs_deviation"][k])).sum())
-        print("\n%s policy %d: the correlation moves mean_abs_deviation of %d of %d episodes" % (shape_id(shape), k, moved, ES.E))
+        print("\n%s policy %d: the correlation moves mean_abs_deviation of %d of %d episodes" % (NS.shape_id(shape), k, moved, ES.E))
         assert 2 * moved >= ES.E, (k, moved)
-    got = fused(g, N, group, disturbance=the_disturbance(g), noise_episode=NOISE_EPISODE)
-    for k, (outcome, steps, ret, stats, summary) in enumerate(rows):
-        assert np.array_equal(got["outcome"][k], outcome) and np.array_equal(got["steps"][k], steps), k
-        assert ES.bits_equal(got["total_reward"][k].astype(np.float32), ret), k
-        for key in g.records.SAFETY_KEYS:
-            assert ES.bits_equal(got[key][k], summary[key]), (k, key)
-    # the counter is part of the noise
-    other = fused(g, N, group, disturbance=the_disturbance(g), noise_episode=NOISE_EPISODE + 1)
-    assert not ES.bits_equal(other["max_abs_a_lat"], got["max_abs_a_lat"])
+    NS.evaluator_equals_the_host_loop(g, CORRELATED, shape)
 
 
 # ---- 3: the campaign against the evaluator ---------------------------------------------------------------------------------------------
-_COUNTERS, _RAN = {}, {}
-
-
-def per_counter(g, s):
-    """The correlated evaluator's result dicts of [a, b, zero] for counters 0 .. EPISODES - 1 at shape s."""
-    if s not in _COUNTERS:
-        cfg = MS.config(g, s)
-        v = g.ACAS2DVecEnv(MS.LANES, s.N, device=DEV, dtype=F32, seed=MS.SEED, config=cfg)
-        out = []
-        for c in range(MS.EPISODES):
-            v.reset_to_episode(c)
-            own, trf, goal = g.policy.read_state(v)
-            res = g.evaluate_policies_fused(MS.policies(g, s), own, trf, goal, dtype=F32, device=DEV, config=cfg, group=s.group,
-                                            safety=True, disturbance=the_disturbance(g), noise_episode=c)
-            for a in res.values():
-                a.setflags(write=False)
-            out.append(res)
-        _COUNTERS[s] = out
-    return _COUNTERS[s]
-
-
-def reference(g, s):
-    return g.records.monte_carlo_reduce(per_counter(g, s), MS.N_BINS, MS.inv_bin_width(g, s), np.float32)
-
-
-def correlated(g, s, **kw):
-    return MS.campaign(g, s, disturbance=the_disturbance(g), **kw)
-
-
-def ran(g, s):
-    if s not in _RAN:
-        acc = correlated(g, s).run(MS.EPISODES).accumulators()
-        for a in acc.values():
-            a.setflags(write=False)
-        _RAN[s] = acc
-    return _RAN[s]
-
-
 @CAMPAIGN
 def test_correlated_campaign_equals_the_correlated_evaluator(g, s):
-    ref = reference(g, s)
+    ref = reference(g, CORRELATED, s)
     assert ref["outcome_count"].sum(1).tolist() == [MS.LANES * MS.EPISODES] * 3
     assert ref["outcome_count"][:, 0].tolist() == [0, 0, 0] and np.isfinite(ref["lane_worst_sep"]).all()
-    same(g, ran(g, s), ref)
-    white = MS.campaign(g, s, disturbance=the_white_disturbance(g)).run(MS.EPISODES).accumulators()
-    assert MS.mismatches(g, ran(g, s), white)                         # (and it is not the white campaign)
+    same(g, ran(g, CORRELATED, s), ref)
+    assert MS.mismatches(g, ran(g, CORRELATED, s), ran(g, WHITE, s))                       # (and it is not the white campaign)
 
 
 @CAMPAIGN
 def test_correlated_chaining(g, s):
-    same(g, correlated(g, s).run(MS.EPISODES, per_launch=1).accumulators(), ran(g, s))      # (ran: per_launch >= EPISODES)
-    same(g, correlated(g, s).run(2).run(1).accumulators(), ran(g, s))
+    NS.chaining(g, CORRELATED, s)
 
 
 @CAMPAIGN
 def test_correlated_campaign_survives_a_state_dict(g, s):
-    first = correlated(g, s).run(2)
-    sd = first.state_dict()
-    assert sd["first_episode"] == 2 and sd["disturbance"] == the_disturbance(g).to_dict()
-    assert all(sd["disturbance"][k] == np.float32(v) for k, v in RHO.items())
-    second = correlated(g, s).load_state_dict(sd).run(1)
-    assert second.first_episode == 3
-    same(g, second.accumulators(), ran(g, s))
     others = (None, the_white_disturbance(g), g.CorrelatedDisturbance.normalised(**SIGMAS, **dict(RHO, rho_cpa=0.5)),
-              g.CorrelatedDisturbance.normalised(**dict(SIGMAS, seed=8), **RHO))
-    for other in others:                                               # another correlation is another campaign
-        with pytest.raises(ValueError, match="disturbance"):
-            MS.campaign(g, s, disturbance=other).load_state_dict(sd)
-    with pytest.raises(ValueError, match="disturbance"):
-        correlated(g, s).load_state_dict(MS.campaign(g, s, disturbance=the_white_disturbance(g)).state_dict())
+              g.CorrelatedDisturbance.normalised(**dict(SIGMAS, seed=8), **RHO))          # another correlation is another campaign
+    NS.survives_a_state_dict(g, CORRELATED, s, others, foreign=the_white_disturbance(g), fields=RHO)
 
 
 @CAMPAIGN
 def test_correlated_common_random_numbers(g, s):
-    """Policy b alone meets the encounters AND the errors it meets among [a, b, zero]."""
-    b = MS.policies(g, s)[1]
-    alone = correlated(g, s, pols=[b]).run(MS.EPISODES).accumulators()
-    same(g, alone, {k: v[[1]] for k, v in ran(g, s).items()})
+    NS.common_random_numbers(g, CORRELATED, s)
 
 
 @CAMPAIGN
 def test_correlated_encounter_closes_the_loop(g, s):
-    mc = correlated(g, s).run(MS.EPISODES)
-    acc = ran(g, s)
-    assert mc.summary()["disturbance"] == the_disturbance(g).to_dict()
-    for k, top in enumerate(mc.worst(1)):
-        (lane, counter, sep), = top
-        assert sep == acc["lane_worst_sep"][k].min() and counter == acc["lane_worst_episode"][k, lane]
-        own, trf, goal, replay = mc.encounter(lane, counter)
-        assert replay == {"disturbance": the_disturbance(g), "noise_episode": counter, "env_offset": lane}
-        res = g.evaluate_policies_fused(MS.policies(g, s), own, trf, goal, dtype=F32, device=DEV, config=MS.config(g, s),
-                                        group=s.group, safety=True, **replay)
-        assert ES.bits_equal(res["min_separation"][k, :1], np.asarray([sep], np.float32))
+    NS.encounter_closes_the_loop(g, CORRELATED, s)
 
 
 # ---- 4: the limits ---------------------------------------------------------------------------------------------------------------------
@@ -339,7 +190,7 @@ def test_refusals(g):
     with pytest.raises(RuntimeError, match=r"acas2d_monte_carlo_correlated: s_sep = .* \(each finite and at least 0\)"):
         MS.campaign(g, s, disturbance=forged(g, s_cpa=-1.0, rho_sep=2.0)).run(1)
     with pytest.raises(RuntimeError, match=r"acas2d_monte_carlo_correlated: episodes_per_lane = 0 \(at least 1\)"):
-        correlated(g, s).run(0)
+        NS.campaign(g, CORRELATED, s).run(0)
     eps = ES.episodes(ES.config(g, 1))
     with pytest.raises(ValueError, match="float32 only"):
         g.MonteCarlo([MS.zero_policy(1)], MS.LANES, dtype=torch.float64, disturbance=the_disturbance(g), device=DEV)

@@ -14,7 +14,7 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
-import test_scoring_rejections_host as SR
+import scoring_rejections_support as SR
 
 f32 = np.float32
 NAN, INF = float("nan"), float("inf")
@@ -200,35 +200,6 @@ CORRELATED = {e.replace("_disturbed", "_correlated"): e for e, v in SR.ENTRIES.i
 VALID_RHO = (0.9, 1.0, 0.0, 0.5)
 
 
-def call(g, entry, N, over, corr=VALID_RHO, dist_over=None):
-    """SR.call() for a correlated entry: its sibling's call with `correlation` in front of the stream (None: NULL)."""
-    nat, L = g.native, g.native.lib()
-    kind = SR.ENTRIES[CORRELATED[entry]][0]
-    fn = getattr(L, entry)
-    A = SR.A
-    if over is None:
-        rc = fn(*([None, None, 0, None, 0, 0, None, 0, 0, 0, 0] + [None] * (len(fn.argtypes) - 11)))
-        return rc, L.acas2d_last_error().decode()
-    s = {"cfg": g.ACAS2DConfig(n_traffic=N).to_c(), "state": nat.CState(*([A] * 14)), "policies": nat.CPolicy(*([A] * 6), 64, 0),
-         "stats": nat.CEvalStats(*([A] * 6)), "mc": nat.CMonteCarlo(*([A] * 9), 16, 2, 0.02, 0, 0),
-         "dist": nat.CDisturbance(0.05, 0.1, 0.1, 0.3, 7, 5, 0)}
-    top = dict({k: True for k in s}, n_envs=256, K=2, count=100, obs=A, T=2000 if kind == "mcdist" else 10, n=N, off=0,
-               outcome=A, steps=A, ret=A)
-    for k, val in over.items():
-        if "." in k:
-            setattr(s[k.split(".")[0]], k.split(".")[1], val)
-        else:
-            assert k in top, k
-            top[k] = val
-    ref = lambda k: None if top[k] is None else C.byref(s[k])  # noqa: E731
-    tail = {"dist": ("stats", "dist"), "mcdist": ("mc", "dist")}[kind]
-    outs = [] if kind == "mcdist" else [top["outcome"], top["steps"], top["ret"]]
-    c = None if corr is None else C.byref(nat.CCorrelation(*corr))
-    rc = fn(ref("cfg"), ref("state"), top["n_envs"], ref("policies"), top["K"], top["count"], top["obs"], top["T"], 13, top["off"],
-            top["n"], *outs, *[ref(k) for k in tail], c, None)
-    return rc, L.acas2d_last_error().decode()
-
-
 def name_of(entry):
     return entry[:-len("_f32")]
 
@@ -250,15 +221,14 @@ def test_the_struct_and_the_exports(g):
 
 def test_every_rejection_of_the_disturbed_sibling(g):
     """... with a VALID correlation: the same code, the same words up to the entry's own name."""
-    with open(SR.GOLDEN) as f:
-        golden = json.load(f)
+    golden = SR.golden()
     seen = 0
     for entry, sibling in CORRELATED.items():
         kind, group, Ns, bad_n = SR.ENTRIES[sibling]
         for N in Ns:
             for vid, over in SR.violations(kind, group, bad_n):
                 if N == Ns[0] or any(tag in vid for tag in SR.N_DEPENDENT):
-                    rc, text = call(g, entry, N, over)
+                    rc, text = SR.call(g, entry, N, over, VALID_RHO)
                     assert rc == SR.EINVAL, (entry, N, vid, rc, text)          # first: nothing may get through to a launch
                     want = golden["text"][sibling][str(N)][vid]
                     assert text == want.replace("_disturbed", "_correlated"), (entry, N, vid)
@@ -273,13 +243,13 @@ def test_the_correlations_own_rejections(g):
     for entry, sibling in CORRELATED.items():
         _, group, Ns, _ = SR.ENTRIES[sibling]
         for N in Ns:
-            rc, text = call(g, entry, N, {}, corr=None)
+            rc, text = SR.call(g, entry, N, {}, None)
             assert rc == SR.EINVAL and text == "%s: NULL correlation" % name_of(entry), (entry, N, text)
             for i in range(4):
                 for bad in BAD_RHO:
                     rho = list(VALID_RHO)
                     rho[i] = bad
-                    rc, text = call(g, entry, N, {}, corr=rho)
+                    rc, text = SR.call(g, entry, N, {}, rho)
                     assert rc == SR.EINVAL, (entry, N, i, bad, rc, text)
                     shown = [float(f32(r)) for r in rho]
                     assert text == "%s: rho_sep = %g, rho_cpa = %g, rho_closing = %g, rho_action = %g (each in [0, 1])" % (
@@ -292,15 +262,14 @@ def test_every_shape_gets_past_the_launchers_lds_limit(g):
     for entry, sibling in CORRELATED.items():
         group = SR.ENTRIES[sibling][1]
         for N in ((8, 16, 32, 64) if group else (1, 2, 3, 4, 8)):
-            rc, text = call(g, entry, N, {"n_envs": 1024, "K": 1}, corr=None)
+            rc, text = SR.call(g, entry, N, {"n_envs": 1024, "K": 1}, None)
             assert rc == SR.EINVAL and text == "%s: NULL correlation" % name_of(entry), (entry, N, text)
 
 
 def test_precedence(g):
     """A bad sigma wins over a bad rho; so does everything else the sibling rejects, down to its last check (the group entries'
     alignment); a NULL correlation and a bad rho win over nothing."""
-    with open(SR.GOLDEN) as f:
-        golden = json.load(f)
+    golden = SR.golden()
     bad_rho = (0.9, NAN, 0.0, 0.5)
     for entry, sibling in CORRELATED.items():
         kind, group, Ns, bad_n = SR.ENTRIES[sibling]
@@ -311,8 +280,8 @@ def test_precedence(g):
         for vid in late:
             want = golden["text"][sibling][str(N)][vid].replace("_disturbed", "_correlated")
             for corr in (bad_rho, None):
-                rc, text = call(g, entry, N, by_id[vid], corr=corr)
+                rc, text = SR.call(g, entry, N, by_id[vid], corr)
                 assert rc == SR.EINVAL and text == want, (entry, vid, corr, text)
         # NULL in front of the values (there are none to read)
-        rc, text = call(g, entry, N, {}, corr=None)
+        rc, text = SR.call(g, entry, N, {}, None)
         assert rc == SR.EINVAL and text.endswith("NULL correlation")

@@ -12,6 +12,9 @@ acas2d_disturbance_draw_f32; policy.Disturbance):
   5  a network of zeros ignores its input: sensor noise alone leaves the all-zero policy's row as it is;
   6  refusals.
 
+The shapes, the host loop, the campaign's reference and the campaign properties are tests/noise_scoring_support.py's, shared
+with tests/test_correlated.py; WHITE is this file's flavour of them.
+
 70 episodes / lanes: one full wave and a partial one thread per env, 18 waves at the (4, 16) group shape."""
 import math
 
@@ -21,15 +24,12 @@ import torch
 
 import eval_stats_support as ES
 import monte_carlo_support as MS
+import noise_scoring_support as NS
+from noise_scoring_support import CAMPAIGN, CAMPAIGN_SHAPES, EVAL_IDS, EVAL_SHAPES, WHITE, ZERO_SHAPES, fused, ran, reference, same
 
 pytestmark = pytest.mark.gpu
 DEV = ES.DEV
 F32 = torch.float32
-# (n_traffic, group)
-EVAL_SHAPES = ((1, False), (3, False), (8, False), (16, True), (64, True))
-ZERO_SHAPES = EVAL_SHAPES[:4]
-CAMPAIGN_SHAPES = [MS.Shape(F32, True, n, grp, max_steps) for max_steps in (1000, 150) for n, grp in ((1, False), (8, False), (16, True))]
-NOISE_EPISODE = 5
 
 # acas2d_disturbance_draw_f32 against records.disturbance_normals(): the largest absolute difference MEASURED on an MI355X
 # over the sample of test_draws_against_the_specification (printed by it), and the bound: four times that,
@@ -39,14 +39,6 @@ DRAW_MEASURED = 1.01e-5          # 1.009757e-05, at a cosine near its zero (|z| 
 DRAW_TOL = 5e-5
 
 
-def shape_id(s):
-    return "N%d%s" % (s[0], "-group" if s[1] else "")
-
-
-EVAL_IDS = [shape_id(s) for s in EVAL_SHAPES]
-CAMPAIGN = pytest.mark.parametrize("s", CAMPAIGN_SHAPES, ids=[MS.shape_id(s) for s in CAMPAIGN_SHAPES])
-
-
 @pytest.fixture(scope="module")
 def g():
     import gym_acas2d_amd as g
@@ -54,7 +46,7 @@ def g():
 
 
 def the_disturbance(g):
-    return g.policy.Disturbance.normalised(sep=0.05, cpa=0.1, closing=0.1, action=0.3, seed=7)
+    return WHITE.disturbance(g)
 
 
 # ---- 1: the draws -----------------------------------------------------------------------------------------------------------------
@@ -96,13 +88,6 @@ def test_draws_do_not_depend_on_how_they_are_asked_for(g):
 
 
 # ---- 2: zero is identity ------------------------------------------------------------------------------------------------------------
-def fused(g, N, group, **kw):
-    cfg = ES.config(g, N)
-    eps = ES.episodes(cfg)
-    return g.evaluate_policies_fused(ES.two_policies(g, N), eps.own, eps.trf, eps.goal, dtype=F32, device=DEV, config=cfg,
-                                     group=group, safety=True, **kw)
-
-
 @pytest.mark.parametrize("shape", ZERO_SHAPES, ids=EVAL_IDS[:4])
 def test_zero_disturbance_is_the_stats_evaluator(g, shape):
     N, group = shape
@@ -124,148 +109,32 @@ def test_zero_disturbance_is_the_undisturbed_campaign(g, shape):
 
 
 # ---- 3: the evaluator against a host loop -------------------------------------------------------------------------------------------
-def host_loop(g, cfg, eps, policy, dist, noise_episode, group):
-    """One policy's reference rows [E] by the per-step path: (outcome, steps, total_reward, stats dict)."""
-    E, N = ES.E, cfg.n_traffic
-    n_steps = cfg.max_steps + 1
-    zero = np.zeros(E, np.int32)
-    # the normals of every step an episode can reach, from the draw entry: [step, lane, slot, 3]
-    normals = g.policy.disturbance_draw(dist.seed, 0, E, noise_episode, 0, cfg.max_steps + 2, N + 1, device=DEV)
-    r = g.ACAS2DVecEnv(E, N, device=DEV, dtype=F32, auto_reset=False, record_trace=True, config=cfg)
-    r.set_state(eps.own, eps.trf, eps.goal, zero, observe=True)
-    scratch = g.ACAS2DVecEnv(E, N, device=DEV, dtype=F32, auto_reset=True, config=cfg)
-    scratch.reset()
-    cols = [r.trace.clone()]
-    active = np.ones(E, bool)
-    outcome, steps, ret, t0 = np.zeros(E, np.uint8), np.zeros(E, np.int32), np.zeros(E, np.float32), np.zeros(E, np.int64)
-    lane = np.arange(E)
-    for t in range(n_steps):
-        obs = r.outputs["obs"].cpu().numpy()
-        at = r.steps.cpu().numpy()                                     # game.steps before this step
-        z = normals[np.minimum(at, normals.shape[0] - 1), lane]       # [E, N + 1, 3] (latched envs: unused)
-        noisy = g.records.disturb_observation(obs, dist.sigma, z[:, 1:])
-        scratch.outputs["obs"].copy_(torch.as_tensor(noisy, device=DEV))
-        action = scratch.rollout_policy(policy, 1, group=group)["actions"][0].cpu().numpy()
-        flown = g.records.disturb_action(action, dist.s_action, z[:, 0, 0])
-        _, _, done, infos = r.step(torch.as_tensor(flown, device=DEV))
-        cols.append(r.trace.clone())
-        fin = active & done.cpu().numpy()
-        outcome[fin] = infos.outcome.cpu().numpy()[fin]
-        steps[fin] = r.steps.cpu().numpy()[fin]
-        ret[fin] = r.total_reward.cpu().numpy()[fin]
-        t0[fin] = t
-        active &= ~fin
-        if not active.any():
-            break
-    trace = torch.stack(cols).cpu().numpy()
-    names = list(g.vec_env.TRACE_COLUMNS)
-    c_sep, c_lat, c_dev = names.index("d_sep"), names.index("a_lat"), names.index("d_dev")
-    keys = ("min_sep", "min_sep_step", "los_steps", "max_a_lat", "max_dev", "sum_dev")
-    stats = {k: np.zeros(E, np.int32 if k in ("min_sep_step", "los_steps") else np.float32) for k in keys}
-    summary = {k: np.zeros(E, np.int32 if k in ("min_separation_step", "los_steps") else np.float32) for k in g.records.SAFETY_KEYS}
-    for i in np.nonzero(~active)[0]:
-        n = t0[i] + 2
-        assert n == steps[i]
-        one = g.records.episode_safety(trace[:n, i, c_sep], trace[:n, i, c_lat], trace[:n, i, c_dev], cfg.safe_distance, np.float32)
-        for k in keys:
-            stats[k][i] = one[k]
-        for k, val in g.records.safety_summary(one, int(steps[i])).items():
-            summary[k][i] = val
-    return outcome, steps, ret, stats, summary
-
-
-_LOOP = {}
-
-
-def loop_reference(g, N, group):
-    if (N, group) not in _LOOP:
-        cfg = ES.config(g, N)
-        eps = ES.episodes(cfg)
-        rows = [host_loop(g, cfg, eps, pol, the_disturbance(g), NOISE_EPISODE, group) for pol in ES.two_policies(g, N)]
-        _LOOP[N, group] = rows
-    return _LOOP[N, group]
-
-
 @pytest.mark.parametrize("shape", EVAL_SHAPES, ids=EVAL_IDS)
 def test_disturbed_evaluator_equals_the_host_loop(g, shape):
     N, group = shape
-    rows = loop_reference(g, N, group)
+    rows = NS.loop_reference(g, WHITE, N, group)
     # teeth, on the reference alone: the disturbance moves the hardest manoeuvre of at least half of the episodes
     plain = ES.reference(g, F32, True, N)
     for k, row in enumerate(rows):
         assert (row[0] != 0).all(), "an episode of the reference did not finish"
         moved = int((ES.bits(row[3]["max_a_lat"]) != ES.bits(plain.stats["max_a_lat"][k])).sum())
         assert 2 * moved >= ES.E, (k, moved)
-    got = fused(g, N, group, disturbance=the_disturbance(g), noise_episode=NOISE_EPISODE)
-    for k, (outcome, steps, ret, stats, summary) in enumerate(rows):
-        assert np.array_equal(got["outcome"][k], outcome) and np.array_equal(got["steps"][k], steps), k
-        assert ES.bits_equal(got["total_reward"][k].astype(np.float32), ret), k
-        for key in g.records.SAFETY_KEYS:
-            assert ES.bits_equal(got[key][k], summary[key]), (k, key)
-    # the counter and the seed are part of the noise
-    other = fused(g, N, group, disturbance=the_disturbance(g), noise_episode=NOISE_EPISODE + 1)
-    assert not ES.bits_equal(other["max_abs_a_lat"], got["max_abs_a_lat"])
+    NS.evaluator_equals_the_host_loop(g, WHITE, shape)
 
 
 # ---- 4: the campaign against the evaluator ---------------------------------------------------------------------------------------------
-_COUNTERS, _RAN = {}, {}
-
-
-def per_counter(g, s):
-    """The disturbed evaluator's result dicts of [a, b, zero] for counters 0 .. EPISODES - 1 at shape s."""
-    if s not in _COUNTERS:
-        cfg = MS.config(g, s)
-        v = g.ACAS2DVecEnv(MS.LANES, s.N, device=DEV, dtype=F32, seed=MS.SEED, config=cfg)
-        out = []
-        for c in range(MS.EPISODES):
-            v.reset_to_episode(c)
-            own, trf, goal = g.policy.read_state(v)
-            res = g.evaluate_policies_fused(MS.policies(g, s), own, trf, goal, dtype=F32, device=DEV, config=cfg, group=s.group,
-                                            safety=True, disturbance=the_disturbance(g), noise_episode=c)
-            for a in res.values():
-                a.setflags(write=False)
-            out.append(res)
-        _COUNTERS[s] = out
-    return _COUNTERS[s]
-
-
-def reference(g, s, rows=None):
-    res = per_counter(g, s)
-    if rows is not None:
-        res = [{k: v[list(rows)] for k, v in r.items() if np.ndim(v) == 2} for r in res]
-    return g.records.monte_carlo_reduce(res, MS.N_BINS, MS.inv_bin_width(g, s), np.float32)
-
-
-def disturbed(g, s, **kw):
-    return MS.campaign(g, s, disturbance=the_disturbance(g), **kw)
-
-
-def ran(g, s):
-    if s not in _RAN:
-        acc = disturbed(g, s).run(MS.EPISODES).accumulators()
-        for a in acc.values():
-            a.setflags(write=False)
-        _RAN[s] = acc
-    return _RAN[s]
-
-
-def same(g, got, want):
-    bad = MS.mismatches(g, got, want)
-    assert not bad, {k: (np.asarray(got[k]).ravel()[:6], np.asarray(want[k]).ravel()[:6]) for k in bad}
-
-
 @CAMPAIGN
 def test_disturbed_campaign_equals_the_disturbed_evaluator(g, s):
-    ref = reference(g, s)
+    ref = reference(g, WHITE, s)
     assert ref["outcome_count"].sum(1).tolist() == [MS.LANES * MS.EPISODES] * 3
-    same(g, ran(g, s), ref)
-    assert MS.mismatches(g, ran(g, s), MS.reference(g, s))           # (and it is not the undisturbed campaign)
+    same(g, ran(g, WHITE, s), ref)
+    assert MS.mismatches(g, ran(g, WHITE, s), MS.reference(g, s))           # (and it is not the undisturbed campaign)
 
 
 def test_the_campaign_reference_is_not_vacuous(g):
     seen = np.zeros(4, np.int64)
     for s in CAMPAIGN_SHAPES:
-        ref = reference(g, s)
+        ref = reference(g, WHITE, s)
         assert ref["outcome_count"].sum(1).tolist() == ref["sep_hist"].sum(1).tolist() == [MS.LANES * MS.EPISODES] * 3, MS.shape_id(s)
         assert ref["outcome_count"][:, 0].tolist() == [0, 0, 0]
         assert np.isfinite(ref["lane_worst_sep"]).all()
@@ -277,47 +146,22 @@ def test_the_campaign_reference_is_not_vacuous(g):
 
 @CAMPAIGN
 def test_disturbed_chaining(g, s):
-    same(g, disturbed(g, s).run(2).run(1).accumulators(), ran(g, s))
-    same(g, disturbed(g, s).run(MS.EPISODES, per_launch=1).accumulators(), ran(g, s))
+    NS.chaining(g, WHITE, s)
 
 
 @CAMPAIGN
 def test_disturbed_campaign_survives_a_state_dict(g, s):
-    first = disturbed(g, s).run(2)
-    sd = first.state_dict()
-    assert sd["first_episode"] == 2 and sd["disturbance"] == the_disturbance(g).to_dict()
-    second = disturbed(g, s).load_state_dict(sd).run(1)
-    assert second.first_episode == 3
-    same(g, second.accumulators(), ran(g, s))
-    with pytest.raises(ValueError, match="disturbance"):
-        MS.campaign(g, s).load_state_dict(sd)
-    with pytest.raises(ValueError, match="disturbance"):
-        MS.campaign(g, s, disturbance=g.policy.Disturbance.normalised(sep=0.05, cpa=0.1, closing=0.1, action=0.3, seed=8)).load_state_dict(sd)
-    with pytest.raises(ValueError, match="disturbance"):
-        disturbed(g, s).load_state_dict(MS.campaign(g, s).state_dict())
+    NS.survives_a_state_dict(g, WHITE, s, others=(None, g.policy.Disturbance.normalised(**dict(NS.SIGMAS, seed=8))), foreign=None)
 
 
 @CAMPAIGN
 def test_disturbed_common_random_numbers(g, s):
-    """Policy b alone meets the encounters AND the noise it meets among [a, b, zero]."""
-    b = MS.policies(g, s)[1]
-    alone = disturbed(g, s, pols=[b]).run(MS.EPISODES).accumulators()
-    same(g, alone, {k: v[[1]] for k, v in ran(g, s).items()})
+    NS.common_random_numbers(g, WHITE, s)
 
 
 @CAMPAIGN
 def test_disturbed_encounter_closes_the_loop(g, s):
-    mc = disturbed(g, s).run(MS.EPISODES)
-    acc = ran(g, s)
-    assert mc.summary()["disturbance"] == the_disturbance(g).to_dict()
-    for k, top in enumerate(mc.worst(1)):
-        (lane, counter, sep), = top
-        assert sep == acc["lane_worst_sep"][k].min() and counter == acc["lane_worst_episode"][k, lane]
-        own, trf, goal, replay = mc.encounter(lane, counter)
-        assert replay == {"disturbance": the_disturbance(g), "noise_episode": counter, "env_offset": lane}
-        res = g.evaluate_policies_fused(MS.policies(g, s), own, trf, goal, dtype=F32, device=DEV, config=MS.config(g, s),
-                                        group=s.group, safety=True, **replay)
-        assert ES.bits_equal(res["min_separation"][k, :1], np.asarray([sep], np.float32))
+    NS.encounter_closes_the_loop(g, WHITE, s)
 
 
 # ---- 5: a network of zeros ignores its input -------------------------------------------------------------------------------------------
@@ -342,7 +186,7 @@ def test_refusals(g):
         with pytest.raises(RuntimeError, match=r"acas2d_evaluate_policies_disturbed: s_sep = .* \(each finite and at least 0\)"):
             fused(g, 1, False, disturbance=bad)
     with pytest.raises(RuntimeError, match=r"acas2d_monte_carlo_disturbed: episodes_per_lane = 0 \(at least 1\)"):
-        disturbed(g, s).run(0)
+        NS.campaign(g, WHITE, s).run(0)
     long = g.ACAS2DConfig(n_traffic=1, max_steps=(1 << 20) - 1)
     with pytest.raises(RuntimeError, match="acas2d_monte_carlo_disturbed: max_steps = 1048575 .*the step field of the noise counter"):
         g.MonteCarlo([MS.zero_policy(1)], MS.LANES, config=long, disturbance=the_disturbance(g), device=DEV).run(1)

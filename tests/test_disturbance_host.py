@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+import scoring_rejections_support as SR
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EVAL = ("acas2d_evaluate_policies_disturbed_f32", "acas2d_evaluate_policies_disturbed_group_f32")
 CAMPAIGN = ("acas2d_monte_carlo_disturbed_f32", "acas2d_monte_carlo_disturbed_group_f32")
@@ -205,95 +207,19 @@ def test_entries_in_header_loader_and_library(g):
 
 
 # ---- refusals -------------------------------------------------------------------------------------------------------------------
-CASES = ((EVAL[0], 1, 16, "no thread-per-env shape"), (EVAL[0], 8, 5, "no thread-per-env shape"),
-         (EVAL[1], 16, 3, "use acas2d_evaluate_policies_disturbed_f32"), (EVAL[1], 64, 5, "has no packed work shape"),
-         (CAMPAIGN[0], 1, 16, "no thread-per-env shape"), (CAMPAIGN[0], 8, 5, "no thread-per-env shape"),
-         (CAMPAIGN[1], 16, 3, "use acas2d_monte_carlo_disturbed_f32"), (CAMPAIGN[1], 64, 5, "has no packed work shape"))
-
-
-@pytest.mark.parametrize("entry,N,badN,bad_msg", CASES, ids=["%s-N%d" % (c[0][7:-4], c[1]) for c in CASES])
-def test_validation_needs_no_gpu(g, entry, N, badN, bad_msg):
+def test_validation_is_in_the_golden_grid(g):
     """Everything the undisturbed sibling refuses, in its words under the entry's own name; a NULL disturbance; every
-    standard deviation negative, NaN or infinite; max_steps + 1 >= 2^20."""
-    L = g.native.lib()
-    buf = (C.c_double * 8192)()
-    a = C.addressof(buf)
-    st = g.native.CState(*([a] * 14))
-    fn = getattr(L, entry)
-    cfg = g.ACAS2DConfig(n_traffic=N).to_c()                              # max_steps 1000
-    name = entry[:-4]
-    campaign = entry in CAMPAIGN
-
-    def pol(hidden=64, **none):
-        f = {n: a for n, _ in g.native.CPolicy._fields_[:6]}
-        f.update(none)
-        return g.native.CPolicy(**f, hidden=hidden, _pad=0)
-
-    def mc(**none):
-        f = {n: a for n, _ in g.native.CMonteCarlo._fields_[:9]}
-        f.update(none)
-        return g.native.CMonteCarlo(**f, n_bins=16, episodes_per_lane=2, inv_bin_width=0.02, first_episode=0, _pad=0)
-
-    def stats(**none):
-        f = {n: a for n, _ in g.native.CEvalStats._fields_}
-        f.update(none)
-        return g.native.CEvalStats(**f)
-
-    def dist(s_sep=0.05, s_cpa=0.1, s_closing=0.1, s_action=0.3):
-        return g.native.CDisturbance(s_sep, s_cpa, s_closing, s_action, 7, 5, 0)
-
-    def call(cfg_=C.byref(cfg), state=C.byref(st), n_envs=256, p=None, K=2, lanes=100, obs=a, T=2000, n=N, off=0, m=None, d=dist(),
-             out=a, null_m=False):
-        m = m or (mc() if campaign else stats())
-        tail = (None if null_m else C.byref(m), None if d is None else C.byref(d), None)
-        if campaign:
-            return fn(cfg_, state, n_envs, C.byref(p or pol()), K, lanes, obs, T, 13, off, n, *tail)
-        return fn(cfg_, state, n_envs, C.byref(p or pol()), K, lanes, obs, T, 13, off, n, out, a, a, *tail)
-
-    def rejects(msg, **kw):
-        assert call(**kw) == -22, kw
-        assert msg.encode() in L.acas2d_last_error(), (kw, L.acas2d_last_error())
-
-    # its own
-    rejects(name + ": NULL disturbance", d=None)
-    for field in ("s_sep", "s_cpa", "s_closing", "s_action"):
-        for bad in (-0.5, -1e-30, float("nan"), float("inf"), -float("inf")):
-            rejects(name + ": s_sep = ", d=dist(**{field: bad}))
-            assert b"(each finite and at least 0)" in L.acas2d_last_error()
-    # (0x7fffffff: max_steps + 1 must not wrap; the campaign's sibling check on n_steps stops that one first)
-    for max_steps, refused in (((1 << 20) - 1, True), (1 << 20, True), ((1 << 20) - 2, False)) + (() if campaign else ((0x7FFFFFFF, True),)):
-        big = g.ACAS2DConfig(n_traffic=N, max_steps=max_steps).to_c()
-        # (n = badN: the admissible max_steps passes this check and is stopped by the shape, before a launch; campaign: an
-        #  n_steps that covers two such episodes)
-        assert call(cfg_=C.byref(big), n=badN, T=0x7FFFFFFF) == -22
-        assert (b"the step field of the noise counter" in L.acas2d_last_error()) == refused, (max_steps, L.acas2d_last_error())
-        assert (("max_steps = %d " % max_steps).encode() in L.acas2d_last_error()) == refused
-    # the sibling's
-    if campaign:
-        rejects(name + ": NULL mc", null_m=True)
-        rejects(name + ": the nine accumulators of mc are required", m=mc(sep_hist=None))
-        rejects("n_steps = 1999 does not cover episodes_per_lane = 2 episodes of max_steps = 1000", T=1999)
-        rejects("n_lanes = 0", lanes=0)
-        rejects("n_lanes = 37 rounded up to 64) need 192", n_envs=191, K=3, lanes=37)
-    else:
-        rejects(name + ": NULL stats", null_m=True)
-        rejects("sum_dev outputs of stats are required", m=stats(los_steps=None))
-        rejects("the outcome, steps and total_reward outputs are required", out=None)
-        rejects("n_episodes = 0", lanes=0)
-        rejects("need 192", n_envs=191, K=3, lanes=37)
-    rejects(bad_msg, n=badN)
-    rejects(name + ": NULL cfg", cfg_=None)
-    rejects("NULL state", state=None)
-    rejects("obs_in", obs=None)
-    for w in ("w1t", "b1", "w2t", "b2", "w3", "b3"):
-        rejects("six weight buffers", p=pol(**{w: None}))
-    rejects("got hidden = 32", p=pol(32))
-    rejects("n_policies = 0", K=0)
-    rejects("n_traffic = 0", n=0)
-    rejects(name + ": negative env_offset", off=-1)
-    rejects("need 256", n_envs=255)
-    if "group" in entry:
-        rejects("16-byte aligned", p=pol(w2t=a + 4))
+    standard deviation negative, NaN or infinite; max_steps + 1 >= 2^20: tests/test_scoring_rejections_host.py holds these
+    four entries to the whole text of each.  Here: that its grid has them, and the calls it does not make."""
+    for entry in EVAL + CAMPAIGN:
+        by_n = SR.covered(entry)
+        assert "the step field of the noise counter" in by_n[str(SR.ENTRIES[entry][2][0])]["max-steps-%d" % ((1 << 20) - 1)]
+        for by_id in by_n.values():
+            # max_steps = 2^20 - 2 is admissible: the call passes the noise counter's check and is stopped by the work shape
+            assert "the step field of the noise counter" not in by_id["max-steps-admissible"]
+    # the evaluators look at n_traffic = 0 with the campaign's step budget too
+    for entry, N in zip(EVAL, (1, 16)):
+        assert SR.call(g, entry, N, {"n": 0, "T": 2000}) == (SR.EINVAL, "%s: n_traffic = 0, n_steps = 2000" % entry[:-4])
 
 
 def test_draw_validation_needs_no_gpu(g):

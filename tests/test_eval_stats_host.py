@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import helpers as H
+import scoring_rejections_support as SR
 
 SAFE = 192.0                                             # settings.py: SAFE_DISTANCE (config.safe_distance)
 
@@ -110,74 +111,16 @@ def test_safety_columns_speaks_the_fused_evaluators_keys(g):
     assert one_row["mean_abs_deviation"] == [0.0] and one_row["min_separation_step"] == [0]
 
 
-ENTRIES = (("acas2d_evaluate_policies_stats_f32", 1, 5, "no thread-per-env shape"),
-           ("acas2d_evaluate_policies_stats_f32", 8, 16, "no thread-per-env shape"),          # 16: the group sibling's
-           ("acas2d_evaluate_policies_stats_f64", 4, 8, "no thread-per-env shape"),
-           ("acas2d_evaluate_policies_stats_group_f32", 16, 4, "use acas2d_evaluate_policies_stats_f32"),   # 4: the plain one's
-           ("acas2d_evaluate_policies_stats_group_f32", 64, 5, "has no packed work shape"))
-
-
-@pytest.mark.parametrize("entry,N,badN,bad_msg", ENTRIES, ids=["%s-N%d" % (e[0][25:], e[1]) for e in ENTRIES])
-def test_evaluate_policies_stats_validation_needs_no_gpu(g, entry, N, badN, bad_msg):
-    """The three new entry points reject a NULL stats, each NULL member of it, a traffic count of the wrong sibling and
-    everything the plain entry points reject -- ACAS2D_EINVAL and a message, before any launch (every pointer here is a
-    host address: a launch would fail)."""
-    L = g.native.lib()
-    buf = (C.c_double * 8192)()
-    a = C.addressof(buf)
-    st = g.native.CState(*([a] * 14))
-    fn = getattr(L, entry)
-    cfg = g.ACAS2DConfig(n_traffic=N).to_c()
-    name = entry[:-4]
-    members = [n for n, _ in g.native.CEvalStats._fields_]
-    assert members == ["min_sep", "min_sep_step", "los_steps", "max_a_lat", "max_dev", "sum_dev"]
-
-    def pol(hidden=64, **none):
-        f = {n: a for n, _ in g.native.CPolicy._fields_[:6]}
-        f.update(none)
-        return g.native.CPolicy(**f, hidden=hidden, _pad=0)
-
-    def stats(**none):
-        f = {n: a for n in members}
-        f.update(none)
-        return g.native.CEvalStats(**f)
-
-    def call(cfg_=C.byref(cfg), state=C.byref(st), n_envs=256, p=None, K=2, E=100, obs=a, T=10, n=N, outcome=a, steps=a,
-             ret=a, off=0, s=stats()):
-        return fn(cfg_, state, n_envs, C.byref(p or pol()), K, E, obs, T, 13, off, n, outcome, steps, ret,
-                  None if s is None else C.byref(s), None)
-
-    def rejects(msg, **kw):
-        assert call(**kw) == -22, kw
-        assert msg.encode() in L.acas2d_last_error(), (kw, L.acas2d_last_error())
-
-    rejects(name + ": NULL stats", s=None)
-    for m in members:
-        rejects(name + ": the min_sep, min_sep_step, los_steps, max_a_lat, max_dev and sum_dev outputs of stats are required",
-                s=stats(**{m: None}))
-    rejects(bad_msg, n=badN)
-    # ... and the plain sibling's rejections (tests/test_policy_sets.py), under this entry point's name
-    rejects(name + ": NULL cfg", cfg_=None)
-    rejects("NULL state", state=None)
-    rejects("NULL state", state=C.byref(g.native.CState(*([a] * 5 + [None] + [a] * 8))))
-    for arg in ("obs", "outcome", "steps", "ret"):
-        rejects("are required", **{arg: None})
-    for w in ("w1t", "b1", "w2t", "b2", "w3", "b3"):
-        rejects("six weight buffers", p=pol(**{w: None}))
-    for hidden in (32, 0, 65):
-        rejects("got hidden = %d" % hidden, p=pol(hidden))
-    for K in (0, -3):
-        rejects("n_policies = %d" % K, K=K)
-    rejects("n_episodes = 0", E=0)
-    rejects("n_steps = 0", T=0)
-    rejects("n_traffic = 0", n=0)
-    rejects(name + ": negative env_offset", off=-1)
-    rejects("need 256", n_envs=255)
-    rejects("need 192", n_envs=191, K=3, E=37)
-    rejects("need 64", n_envs=0, K=1, E=1)
-    if "group" in entry:
-        rejects("16-byte aligned", p=pol(w2t=a + 4))
-    assert fn(None, None, 0, None, 0, 0, None, 0, 0, 0, 0, None, None, None, None, None) == -22
+def test_evaluate_policies_stats_validation_is_in_the_golden_grid(g):
+    """The stats entry points reject a NULL stats, each NULL member of it, a traffic count of the wrong sibling and
+    everything the plain entry points reject: tests/test_scoring_rejections_host.py holds the three entries to the whole
+    text of each.  Here: that its grid has them, and the one call it does not make."""
+    assert [n for n, _ in g.native.CEvalStats._fields_] == ["min_sep", "min_sep_step", "los_steps", "max_a_lat", "max_dev", "sum_dev"]
+    for tail in ("f32", "f64", "group_f32"):
+        SR.covered("acas2d_evaluate_policies_stats_" + tail)
+    # the widest group shape, which the grid does not call at
+    assert SR.call(g, "acas2d_evaluate_policies_stats_group_f32", 64, {"T": 0}) == (
+        SR.EINVAL, "acas2d_evaluate_policies_stats_group: n_traffic = 64, n_steps = 0")
 
 
 def test_stats_struct_and_prototypes(g):

@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 import torch
 
+import scoring_rejections_support as SR
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = ("acas2d_monte_carlo_f32", "acas2d_monte_carlo_f64", "acas2d_monte_carlo_group_f32")
 
@@ -201,64 +203,12 @@ def test_entries_in_header_loader_and_library(g):
         me(torch.float64, group=True)
 
 
-CASES = (("acas2d_monte_carlo_f32", 1, 16, "no thread-per-env shape"), ("acas2d_monte_carlo_f32", 8, 5, "no thread-per-env shape"),
-         ("acas2d_monte_carlo_f64", 4, 8, "no thread-per-env shape"),
-         ("acas2d_monte_carlo_group_f32", 16, 3, "use acas2d_monte_carlo_f32"),
-         ("acas2d_monte_carlo_group_f32", 64, 5, "has no packed work shape"))
-
-
-@pytest.mark.parametrize("entry,N,badN,bad_msg", CASES, ids=["%s-N%d" % (c[0][19:], c[1]) for c in CASES])
-def test_monte_carlo_validation_needs_no_gpu(g, entry, N, badN, bad_msg):
-    L = g.native.lib()
-    buf = (C.c_double * 8192)()
-    a = C.addressof(buf)
-    st = g.native.CState(*([a] * 14))
-    fn = getattr(L, entry)
-    cfg = g.ACAS2DConfig(n_traffic=N).to_c()                              # max_steps 1000
-    name = entry[:-4]
-    ptrs = [n for n, _ in g.native.CMonteCarlo._fields_[:9]]
-
-    def pol(hidden=64, **none):
-        f = {n: a for n, _ in g.native.CPolicy._fields_[:6]}
-        f.update(none)
-        return g.native.CPolicy(**f, hidden=hidden, _pad=0)
-
-    def mc(n_bins=16, epl=2, first=0, **none):
-        f = {n: a for n in ptrs}
-        f.update(none)
-        return g.native.CMonteCarlo(**f, n_bins=n_bins, episodes_per_lane=epl, inv_bin_width=0.02, first_episode=first, _pad=0)
-
-    def call(cfg_=C.byref(cfg), state=C.byref(st), n_envs=256, p=None, K=2, lanes=100, obs=a, T=2000, n=N, off=0, m=mc()):
-        return fn(cfg_, state, n_envs, C.byref(p or pol()), K, lanes, obs, T, 13, off, n, None if m is None else C.byref(m), None)
-
-    def rejects(msg, **kw):
-        assert call(**kw) == -22, kw
-        assert msg.encode() in L.acas2d_last_error(), (kw, L.acas2d_last_error())
-
-    rejects(name + ": NULL mc", m=None)
-    for p_ in ptrs:
-        rejects(name + ": the nine accumulators of mc are required", m=mc(**{p_: None}))
-    for epl in (0, -1):
-        rejects(name + ": episodes_per_lane = %d (at least 1)" % epl, m=mc(epl=epl))
-    for nb in (0, -4):
-        rejects(name + ": n_bins = %d (at least 1)" % nb, m=mc(n_bins=nb))
-    rejects("exceeds the 32-bit episode counter", m=mc(first=0xFFFFFFFF))           # 2^32 - 1 + 2 > 2^32
-    assert call(m=mc(first=0xFFFFFFFE), n=badN) == -22 and b"episode counter" not in L.acas2d_last_error()   # ... + 2 = 2^32: fine
-    rejects("n_steps = 1999 does not cover episodes_per_lane = 2 episodes of max_steps = 1000", T=1999)
-    rejects("does not cover", T=0)
-    rejects("must fit an int32", m=mc(epl=3000000), T=2147483647)
-    rejects(bad_msg, n=badN)
-    rejects(name + ": NULL cfg", cfg_=None)
-    rejects("NULL state", state=None)
-    rejects("obs_in is required", obs=None)
-    for w in ("w1t", "b1", "w2t", "b2", "w3", "b3"):
-        rejects("six weight buffers", p=pol(**{w: None}))
-    rejects("got hidden = 32", p=pol(32))
-    rejects("n_policies = 0", K=0)
-    rejects("n_lanes = 0", lanes=0)
-    rejects("n_traffic = 0", n=0)
-    rejects(name + ": negative env_offset", off=-1)
-    rejects("need 256", n_envs=255)
-    rejects("need 192", n_envs=191, K=3, lanes=37)
-    if "group" in entry:
-        rejects("16-byte aligned", p=pol(w2t=a + 4))
+def test_monte_carlo_validation_is_in_the_golden_grid():
+    """The campaign's rejections -- a NULL mc, each NULL accumulator, episodes_per_lane, n_bins, the 32-bit episode counter,
+    the step budget, the work shapes and everything the evaluators refuse: tests/test_scoring_rejections_host.py holds the
+    three entries to the whole text of each.  Here: that its grid has them."""
+    for entry in ENTRIES:
+        for by_id in SR.covered(entry).values():
+            # first_episode + episodes_per_lane = 2^32 exactly fits the counter: the work shape stops that call
+            assert "episode counter" not in by_id["counter-fits"]
+    assert "exceeds the 32-bit episode counter" in SR.covered(ENTRIES[0])["1"]["counter-wraps"]

@@ -5,7 +5,6 @@ the reference's training_main.py:28-52 (EvalCallback + CheckpointCallback) and c
 CPU: the zip round trip and the argument validation of the two new entry points.  GPU (-m gpu): every row of a K-policy
 launch equals evaluate_policy_fused() of that policy bit for bit, at every thread-per-env instantiation; the reference's
 recorded score; routing of many policies; NaN episodes; the step budget; the trainer callbacks."""
-import ctypes as C
 import io
 import os
 import random
@@ -17,6 +16,7 @@ import torch
 
 import helpers as H
 import learner_ref as R
+import scoring_rejections_support as SR
 
 DEV = "cuda:0"
 FIXTURE = os.path.join(H.GOLDEN, "ref_policy_best_model.npz")
@@ -62,52 +62,15 @@ def test_save_sb3_policy_round_trip(g, tmp_path):
         assert torch.equal(a.view(torch.int32), b.view(torch.int32)), k
 
 
-def test_evaluate_policies_validation_needs_no_gpu(g):
-    """acas2d_evaluate_policies_* reject every bad argument with ACAS2D_EINVAL and a message, before any launch (the
-    pointers are host addresses: a launch would fail otherwise)."""
-    L = g.native.lib()
-    buf = (C.c_double * 8192)()
-    a = C.addressof(buf)
-    st = g.native.CState(*([a] * 14))
-
-    def pol(hidden=64, **none):
-        f = {n: a for n, _ in g.native.CPolicy._fields_[:6]}
-        f.update(none)
-        return g.native.CPolicy(**f, hidden=hidden, _pad=0)
-
-    for dt, N, badN in (("f32", 1, 5), ("f64", 4, 8), ("f32", 8, 6), ("f64", 1, 8)):
-        fn = getattr(L, "acas2d_evaluate_policies_" + dt)
-        cfg = g.ACAS2DConfig(n_traffic=N).to_c()
-
-        def call(cfg_=C.byref(cfg), state=C.byref(st), n_envs=256, p=None, K=2, E=100, obs=a, T=10, n=N,
-                 outcome=a, steps=a, ret=a, off=0):
-            return fn(cfg_, state, n_envs, C.byref(p or pol()), K, E, obs, T, 13, off, n, outcome, steps, ret, None)
-
-        def rejects(msg, **kw):
-            assert call(**kw) == -22, (dt, kw)
-            assert msg.encode() in L.acas2d_last_error(), (dt, kw, L.acas2d_last_error())
-
-        rejects("NULL cfg", cfg_=None)
-        rejects("NULL state", state=None)
-        rejects("NULL state", state=C.byref(g.native.CState(*([a] * 5 + [None] + [a] * 8))))
-        for name in ("obs", "outcome", "steps", "ret"):
-            rejects("are required", **{name: None})
-        for name in ("w1t", "b1", "w2t", "b2", "w3", "b3"):
-            rejects("six weight buffers", p=pol(**{name: None}))
-        for hidden in (32, 0, 65):
-            rejects("got hidden = %d" % hidden, p=pol(hidden))
-        for K in (0, -3):
-            rejects("n_policies = %d" % K, K=K)
-        rejects("n_episodes = 0", E=0)
-        rejects("n_steps = 0", T=0)
-        rejects("n_traffic = 0", n=0)
-        rejects("acas2d_evaluate_policies: negative env_offset", off=-1)
-        rejects("no thread-per-env shape", n=badN)
-        # K x round_up(E, 64) envs: 2 x 128 = 256 fit, 255 do not; 3 x 64 = 192 at E = 37
-        rejects("need 256", n_envs=255)
-        rejects("need 192", n_envs=191, K=3, E=37)
-        rejects("need 64", n_envs=0, K=1, E=1)
-    assert L.acas2d_evaluate_policies_f32(None, None, 0, None, 0, 0, None, 0, 0, 0, 0, None, None, None, None) == -22
+def test_evaluate_policies_validation_is_in_the_golden_grid(g):
+    """acas2d_evaluate_policies_* reject every bad argument with ACAS2D_EINVAL and a message, before any launch:
+    tests/test_scoring_rejections_host.py holds them to the whole text of each.  Here: that its grid has them, and the one
+    call it does not make."""
+    for dt in ("f32", "f64"):
+        SR.covered("acas2d_evaluate_policies_" + dt)
+    # a traffic count between two thread-per-env shapes
+    assert SR.call(g, "acas2d_evaluate_policies_f32", 8, {"n": 6}) == (
+        SR.EINVAL, "acas2d_evaluate_policies: n_traffic = 6 has no thread-per-env shape for this element type")
 
 
 # ---- GPU ------------------------------------------------------------------------------------------------------------
