@@ -219,6 +219,23 @@ int acas2d_collect_set_disturbed_group_f32(const Acas2dConfig* cfg, const Acas2d
     return launch_collect_set_disturbed<float>(cfg, state, io, ac, n_members, noise_seeds, obs_in, n_steps, seed, env_offset, n_envs,
                                                n_traffic, sigmas, dist_seed, obs_read, (hipStream_t)stream, true);
 }
+// ... and under time-correlated and biased errors whose state outlives the launch (collect_set_correlated_kernel; float32)
+int acas2d_collect_set_correlated_f32(const Acas2dConfig* cfg, const Acas2dState* state, const Acas2dStepIO* io,
+                                      const Acas2dActorCritic* ac, int32_t n_members, const uint64_t* noise_seeds, const void* obs_in,
+                                      int32_t n_steps, uint64_t seed, int64_t env_offset, int64_t n_envs, int32_t n_traffic,
+                                      const float* sigmas, uint64_t dist_seed, void* obs_read, const float* correlations, float* held,
+                                      void* stream) {
+    return launch_collect_set_correlated<float>(cfg, state, io, ac, n_members, noise_seeds, obs_in, n_steps, seed, env_offset, n_envs,
+                                                n_traffic, sigmas, dist_seed, obs_read, correlations, held, (hipStream_t)stream, false);
+}
+int acas2d_collect_set_correlated_group_f32(const Acas2dConfig* cfg, const Acas2dState* state, const Acas2dStepIO* io,
+                                            const Acas2dActorCritic* ac, int32_t n_members, const uint64_t* noise_seeds,
+                                            const void* obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset, int64_t n_envs,
+                                            int32_t n_traffic, const float* sigmas, uint64_t dist_seed, void* obs_read,
+                                            const float* correlations, float* held, void* stream) {
+    return launch_collect_set_correlated<float>(cfg, state, io, ac, n_members, noise_seeds, obs_in, n_steps, seed, env_offset, n_envs,
+                                                n_traffic, sigmas, dist_seed, obs_read, correlations, held, (hipStream_t)stream, true);
+}
 int acas2d_reset_f32(const Acas2dConfig* cfg, const Acas2dState* state, const uint8_t* mask, void* obs,
                      int32_t do_init, uint64_t seed, int64_t env_offset, int64_t n_envs, int32_t n_traffic,
                      void* stream) {

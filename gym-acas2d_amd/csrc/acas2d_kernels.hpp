@@ -1501,10 +1501,11 @@ __device__ __forceinline__ const CorrW* correlation_args(const PW& pw) {
 constexpr int kCorrSlots(int C) { return 3 * C + 1; }
 // e_t of one process from z_t and the held e_{t-1}: z_t itself where rho == 0 (wave-uniform: the channel does no arithmetic
 // and touches no state) and at the first step the lane plays of an episode; else (rho e_{t-1}) + (q z_t), three roundings
-__device__ __forceinline__ float correlated(float* held, bool first, float rho, float q, float z) {
+// (`commit`: the set collector's extra pass for obs_read[n_steps] forms e_T and leaves the held e_{T-1} alone)
+__device__ __forceinline__ float correlated(float* held, bool first, float rho, float q, float z, bool commit = true) {
     if (rho == 0.0f) return z;
     const float e = first ? z : __fadd_rn(__fmul_rn(rho, *held), __fmul_rn(q, z));
-    *held = e;
+    if (commit) *held = e;
     return e;
 }
 // DIST on top of Mode::CollectSet (acas2d_collect_set_disturbed_f32, acas2d_collect_set_disturbed_group_f32;
@@ -1520,6 +1521,21 @@ struct PolicyCollectDistW : PolicyW { CollectDistW dist; };
 template <typename PW>
 __device__ __forceinline__ const CollectDistW* collect_disturbance_args(const PW& pw) {
     if constexpr (std::is_base_of<PolicyCollectDistW, PW>::value) return &pw.dist;
+    else return nullptr;
+}
+// CORR on top of that (acas2d_collect_set_correlated_f32, acas2d_collect_set_correlated_group_f32; collect_set_correlated_kernel,
+// acas2d_collect_correlated.hip): the collector under the Gauss-Markov error.  An episode spans launches, so the state outlives
+// them: `held`, float[3 N + 1][E] in device memory (row 3 n + c: traffic n's channel c; row 3 N: the actuator's), which a lane
+// loads into its LDS slots (CorrW's layout) at the launch's start and stores behind the last played step.  The coefficients are
+// the MEMBER's, a row of a device float[K][8] (four rho, four gains) that its waves load next to its sigmas.
+struct CollectCorrW {
+    const float* correlations;                       // float[K][8]: CorrW's fields in its order
+    float* held;                                     // float[3 N + 1][E]: e_{t-1} of every process, in and out
+};
+struct PolicyCollectCorrW : PolicyCollectDistW { CollectCorrW corr; };
+template <typename PW>
+__device__ __forceinline__ const CollectCorrW* collect_correlation_args(const PW& pw) {
+    if constexpr (std::is_base_of<PolicyCollectCorrW, PW>::value) return &pw.corr;
     else return nullptr;
 }
 constexpr uint32_t kDisturbanceTag = 0x64697374u;    // "dist": keeps the blocks apart from the reset's under the same seed
@@ -1877,6 +1893,19 @@ __global__ __launch_bounds__(kBlock) void monte_carlo_correlated_kernel(const T*
     constexpr Mode M = Mode::Eval;
 #include "acas2d_step_body.inl"
 }
+// collect_set_disturbed_kernel with CORR (acas2d_collect_set_correlated_f32, acas2d_collect_set_correlated_group_f32): the error
+// state lies in the wave's LDS during the launch and in device memory between launches (CollectCorrW).  Instantiated in a unit
+// of its own (acas2d_collect_correlated.hip); float32 only.
+template <typename T, int C, int G, bool FAST, typename PW = PolicyCollectCorrW>
+__global__ __launch_bounds__(kBlock) void collect_set_correlated_kernel(const T* a0, const T* a1, const T* a2, const T* a3,
+                                                                        const T* a4, const T* a5, int32_t e_n_envs, int32_t tile_elems,
+                                                                        Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
+                                                                        StepIO<T> io_arg, uint32_t k0, uint32_t k1, int64_t env_offset,
+                                                                        int N_arg, int n_steps, PW pw) {
+    constexpr bool PACKED = true, STATS = false, MC = false, DIST = true, CORR = true;
+    constexpr Mode M = Mode::CollectSet;
+#include "acas2d_step_body.inl"
+}
 // acas2d_disturbance_draw_f32: the normals of n_steps x n_lanes x n_slots blocks as float[n_steps][n_lanes][n_slots][3]
 // (slot 0: the actuator's normal, then two zeros), one thread each, through disturbance_normals()
 template <typename T>
@@ -2014,6 +2043,13 @@ int launch_collect_set_disturbed(const Acas2dConfig* cfg, const Acas2dState* st,
                                  int32_t n_members, const uint64_t* noise_seeds, const void* obs_in, int32_t n_steps, uint64_t seed,
                                  int64_t env_offset, int64_t n_envs, int32_t n_traffic, const float* sigmas, uint64_t dist_seed,
                                  void* obs_read, hipStream_t stream, bool group);
+// acas2d_collect_set_correlated_f32 and, `group`, acas2d_collect_set_correlated_group_f32 (float32 only;
+// acas2d_collect_correlated.hip)
+template <typename T>
+int launch_collect_set_correlated(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
+                                  int32_t n_members, const uint64_t* noise_seeds, const void* obs_in, int32_t n_steps, uint64_t seed,
+                                  int64_t env_offset, int64_t n_envs, int32_t n_traffic, const float* sigmas, uint64_t dist_seed,
+                                  void* obs_read, const float* correlations, float* held, hipStream_t stream, bool group);
 // the *_group entry points (float32: the double instantiations reject every traffic count)
 template <typename T>
 int launch_rollout_policy_group(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io,

@@ -326,12 +326,13 @@ static int require_aligned(const char* name, std::initializer_list<const void*> 
     return ACAS2D_OK;
 }
 
-// The kernel of a launch: step_kernel in mode M, unless the launch's policy argument is one of the seven that have a kernel
-// of their own (Mode::Eval with statistics, the Monte Carlo campaign, the disturbed and the correlated flavour of each and the
-// disturbed set collector; packed shapes)
+// The kernel of a launch: step_kernel in mode M, unless the launch's policy argument is one of the eight that have a kernel
+// of their own (Mode::Eval with statistics, the Monte Carlo campaign, the disturbed and the correlated flavour of each, the
+// disturbed and the correlated set collector; packed shapes)
 template <typename PW, typename T, int C, int G, bool PACKED, bool FAST, Mode M>
 static constexpr auto kernel_for() {
-    if constexpr (std::is_same<PW, PolicyCollectDistW>::value) return &collect_set_disturbed_kernel<T, C, G, FAST>;
+    if constexpr (std::is_same<PW, PolicyCollectCorrW>::value) return &collect_set_correlated_kernel<T, C, G, FAST>;
+    else if constexpr (std::is_same<PW, PolicyCollectDistW>::value) return &collect_set_disturbed_kernel<T, C, G, FAST>;
     else if constexpr (std::is_same<PW, PolicyMonteCarloCorrW>::value) return &monte_carlo_correlated_kernel<T, C, G, FAST>;
     else if constexpr (std::is_same<PW, PolicyEvalStatsCorrW>::value) return &eval_stats_correlated_kernel<T, C, G, FAST>;
     else if constexpr (std::is_same<PW, PolicyMonteCarloDistW>::value) return &monte_carlo_disturbed_kernel<T, C, G, FAST>;
@@ -478,19 +479,25 @@ int launch_collect_group(const Acas2dConfig* cfg, const Acas2dState* st, const A
 // and the same rule for EM keeps them one member's.
 // DIST (acas2d_collect_set_disturbed_f32, acas2d_collect_set_disturbed_group_f32; collect_set_disturbed_kernel): the same launch
 // under sensor and actuator noise, `cd` its three arguments.  One member then takes any n_envs >= 1: it is the solo collector.
-struct CollectDisturbance { const float* sigmas; uint64_t seed; void* obs_read; };
-template <typename T, bool DIST>
+// CORR on top (acas2d_collect_set_correlated_f32, acas2d_collect_set_correlated_group_f32; collect_set_correlated_kernel): the
+// noise a Gauss-Markov error whose state lives in `held` between launches, `cd`'s last two arguments; its rejections stand
+// behind everything the disturbed entry rejects: in go(), after the shape, geometry_for() and the alignment.
+struct CollectDisturbance { const float* sigmas; uint64_t seed; void* obs_read; const float* correlations; float* held; };
+template <typename T, bool DIST, bool CORR = false>
 static int collect_set(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
                        int32_t n_members, const uint64_t* noise_seeds, const void* obs_in, int32_t n_steps, uint64_t seed,
                        int64_t env_offset, int64_t n_envs, int32_t n_traffic, hipStream_t stream, bool group,
                        const CollectDisturbance& cd = CollectDisturbance{}) {
     static_assert(sizeof(T) == 4, "acas2d_collect_set: float32 only");
+    static_assert(!CORR || DIST, "the correlated collector: on top of the disturbed one");
     static const char kScope[] = "float32, n_traffic in {1, 2, 3, 4, 8}; n_traffic 16 / 32 / 64 is acas2d_collect_set_group_f32, "
                                  "float64 collects one learner per call";
-    Launch<T> L{DIST ? (group ? "acas2d_collect_set_disturbed_group" : "acas2d_collect_set_disturbed")
-                     : (group ? "acas2d_collect_set_group" : "acas2d_collect_set"), cfg, st, io, seed, env_offset, n_envs, n_traffic,
+    Launch<T> L{CORR ? (group ? "acas2d_collect_set_correlated_group" : "acas2d_collect_set_correlated")
+                : DIST ? (group ? "acas2d_collect_set_disturbed_group" : "acas2d_collect_set_disturbed")
+                       : (group ? "acas2d_collect_set_group" : "acas2d_collect_set"), cfg, st, io, seed, env_offset, n_envs, n_traffic,
                 n_steps, stream};
     L.group_policy = group;
+    L.correlated = CORR;
     const auto inputs = [&] {
         if (!io->actions || !io->obs || !io->reward || !io->done || !io->outcome || !obs_in)
             return fail("%s: obs_in, actions (output), obs, reward, done and outcome are required", L.name);
@@ -530,9 +537,27 @@ static int collect_set(const Acas2dConfig* cfg, const Acas2dState* st, const Aca
         if (group)      // (a member's slice lies a multiple of 256 bytes behind the stack's base: the base decides)
             if (int rc = require_aligned(L.name, {ac->actor.w1t, ac->actor.b1, ac->actor.w2t, ac->actor.b2, ac->v1t, ac->vb1,
                                                   ac->v2t, ac->vb2})) return rc;
+        if constexpr (CORR) {
+            // its own rejections, behind EVERYTHING the disturbed sibling rejects (the work shape, the launch and LDS limits and
+            // the group entries' alignment included), as the correlated evaluator checks its correlation last of all
+            if (!cd.correlations) return fail("%s: NULL correlations (float[n_members][8], on the device)", L.name);
+            if (!cd.held) return fail("%s: NULL held (float[3 n_traffic + 1][n_envs], on the device)", L.name);
+            const uint64_t row = (uint64_t)n_envs * (uint64_t)(5 + 3 * (int64_t)n_traffic) * sizeof(T);
+            const uintptr_t w0 = (uintptr_t)cd.held,
+                            w1 = w0 + (uintptr_t)((uint64_t)n_envs * (uint64_t)(3 * (int64_t)n_traffic + 1) * sizeof(float));
+            const auto meets = [&](const void* q, uint64_t bytes) { return w0 < (uintptr_t)q + (uintptr_t)bytes && (uintptr_t)q < w1; };
+            if (meets(cd.obs_read, row * ((uint64_t)n_steps + 1u)) || meets(io->obs, row * (uint64_t)n_steps) || meets(obs_in, row))
+                return fail("%s: held overlaps obs_read, io->obs or obs_in", L.name);
+        }
         sample_with(pw, ac, (uint64_t)reinterpret_cast<uintptr_t>(noise_seeds));       // the kernel loads its member's key
         pw.member_stride = (uint32_t)(n_envs / n_members);
-        if constexpr (DIST) {
+        if constexpr (CORR) {
+            PolicyCollectCorrW pc{};
+            static_cast<PolicyW&>(pc) = pw;
+            pc.dist = CollectDistW{cd.sigmas, cd.obs_read, (uint32_t)cd.seed, (uint32_t)(cd.seed >> 32)};
+            pc.corr = CollectCorrW{cd.correlations, cd.held};
+            return launch_mode<Mode::CollectSet>(L, pc);
+        } else if constexpr (DIST) {
             PolicyCollectDistW pd{};
             static_cast<PolicyW&>(pd) = pw;
             pd.dist = CollectDistW{cd.sigmas, cd.obs_read, (uint32_t)cd.seed, (uint32_t)(cd.seed >> 32)};
@@ -564,6 +589,14 @@ int launch_collect_set_disturbed(const Acas2dConfig* cfg, const Acas2dState* st,
                                  void* obs_read, hipStream_t stream, bool group) {
     return collect_set<T, true>(cfg, st, io, ac, n_members, noise_seeds, obs_in, n_steps, seed, env_offset, n_envs, n_traffic, stream,
                                 group, CollectDisturbance{sigmas, dist_seed, obs_read});
+}
+template <typename T>
+int launch_collect_set_correlated(const Acas2dConfig* cfg, const Acas2dState* st, const Acas2dStepIO* io, const Acas2dActorCritic* ac,
+                                  int32_t n_members, const uint64_t* noise_seeds, const void* obs_in, int32_t n_steps, uint64_t seed,
+                                  int64_t env_offset, int64_t n_envs, int32_t n_traffic, const float* sigmas, uint64_t dist_seed,
+                                  void* obs_read, const float* correlations, float* held, hipStream_t stream, bool group) {
+    return collect_set<T, true, true>(cfg, st, io, ac, n_members, noise_seeds, obs_in, n_steps, seed, env_offset, n_envs, n_traffic,
+                                      stream, group, CollectDisturbance{sigmas, dist_seed, obs_read, correlations, held});
 }
 
 // what the disturbed entries check on top of their siblings (after them: cfg is there), and the kernels' view of the struct
@@ -780,6 +813,9 @@ int launch_disturbance_draw(uint64_t seed, int64_t first_lane, int32_t n_lanes, 
 // ends with the kernels above, and every kernel of it keeps its place, its name and the local labels of its assembly
 #define ACAS2D_INSTANTIATE_COLLECT_DISTURBED \
     namespace acas2d { template decltype(launch_collect_set_disturbed<Elem>) launch_collect_set_disturbed<Elem>; }
+// ... and the correlated one: the ONE instantiation of acas2d_collect_correlated.hip, a unit of its own likewise
+#define ACAS2D_INSTANTIATE_COLLECT_CORRELATED \
+    namespace acas2d { template decltype(launch_collect_set_correlated<Elem>) launch_collect_set_correlated<Elem>; }
 
 template <typename T>
 int launch_reset(const Acas2dConfig* cfg, const Acas2dState* st, const uint8_t* mask, void* obs,
@@ -820,7 +856,7 @@ int shape_geometry(int64_t n_envs, int32_t n_traffic, int32_t* lanes, int32_t* p
 }
 
 // the launchers of this unit's element type (acas2d_kernels.hpp declares them, acas2d_api.hip calls them); a unit that
-// defines ACAS2D_LAUNCHERS_BY_NAME instantiates the ones it names itself (acas2d_collect_disturbed.hip)
+// defines ACAS2D_LAUNCHERS_BY_NAME instantiates the ones it names itself (acas2d_collect_disturbed.hip and its kin)
 #ifndef ACAS2D_LAUNCHERS_BY_NAME
 template decltype(launch_step<Elem>) launch_step<Elem>;
 template decltype(launch_rollout<Elem>) launch_rollout<Elem>;

@@ -1,6 +1,6 @@
 // acas2d_step_body.inl -- the body of step_kernel, eval_stats_kernel, monte_carlo_kernel, the latter two's disturbed and
-// correlated flavours and the disturbed set collector (acas2d_kernels.hpp, where the modes and what each one implies are
-// described), included inside all eight.  It
+// correlated flavours and the disturbed and the correlated set collector (acas2d_kernels.hpp, where the modes and what each one
+// implies are described), included inside all nine.  It
 // expects the including kernel's template parameters T, C, G, PACKED, FAST, M (or constants of those names), the constants
 // STATS, MC, DIST and CORR, and the kernel's arguments a0 .. a5,
 // e_n_envs, tile_elems, p_arg, rp_arg, s_arg, io_arg, k0, k1, env_offset, N_arg, n_steps, pw.
@@ -233,9 +233,25 @@
     // channel c of the lane's k-th aircraft, then the actuator's
     float* corr_held = nullptr;
     (void)corr_held;
+    // CORR and SET (collect_set_correlated_kernel): the member's four rho and four gains as the CorrW the evaluator takes by
+    // value -- filled in the SET prologue below, scalar registers, so that `rho == 0` stays a wave-uniform branch
+    CorrW set_cw{};
+    (void)set_cw;
     if constexpr (CORR) {
-        static_assert(DIST && EVAL && STATS, "correlated errors: the disturbed stats evaluator and Monte Carlo kernel");
+        static_assert(DIST && ((EVAL && STATS) || SET),
+                      "correlated errors: the disturbed stats evaluator, Monte Carlo kernel and set collector");
         corr_held = reinterpret_cast<float*>(tile) + (tile_elems - kCorrSlots(C) * 64) + lane;
+        if constexpr (SET) {
+            // the state the previous launch left (CollectCorrW::held, rows of E): every process of the lane, whatever its rho --
+            // a value nobody advances goes back as it came.  Lanes past the last env load nothing: they play a copy of the
+            // wave's first env on whatever their slots hold, and store nothing.
+            if (active) {
+                const float* const hp = collect_correlation_args(pw)->held + (e_wave + el);
+#pragma unroll
+                for (int i = 0; i < 3 * C; ++i) corr_held[i * 64] = hp[(int64_t)(3 * (j * C) + i) * n_envs];
+                corr_held[(3 * C) * 64] = hp[(int64_t)(3 * N) * n_envs];
+            }
+        }
     }
     // STATS: the running statistics of the lane's episode (PolicyEvalStatsW)
     T st_min = T(1) / T(0), st_a_lat = T(0), st_dev = T(0), st_sum = T(0);
@@ -260,6 +276,10 @@
             const CollectDistW* const cw = collect_disturbance_args(pw);
             const float ACAS2D_AS4* const sg = (const float ACAS2D_AS4*)cw->sigmas + 4 * (size_t)km;
             set_dw = DisturbW{sg[0], sg[1], sg[2], sg[3], cw->dk0, cw->dk1, 0u};
+        }
+        if constexpr (CORR) {                             // ... and of float[K][8]: four rho, four gains
+            const float ACAS2D_AS4* const cr = (const float ACAS2D_AS4*)collect_correlation_args(pw)->correlations + 8 * (size_t)km;
+            set_cw = CorrW{cr[0], cr[1], cr[2], cr[3], cr[4], cr[5], cr[6], cr[7]};
         }
     }
     for (int t = 0; t < T_steps + ((DIST && SET) ? 1 : 0); ++t) {      // (DIST && SET: one pass more, for obs_read[n_steps])
@@ -288,19 +308,23 @@
                 const DisturbW* const dw = SET ? &set_dw : disturbance_args(pw);
                 if (dw->s_sep != 0.0f || dw->s_cpa != 0.0f || dw->s_closing != 0.0f) {      // (wave-uniform)
                     const uint32_t d_ep = (MC || SET) ? episode : dw->episode;
-                    // CORR: the lane's first step of an episode in this launch (an in-step reset leaves steps == 1)
-                    const bool corr_first = CORR && (t == 0 || steps == 1);
-                    (void)corr_first;
+                    // CORR: the lane's first step of an episode in this launch (an in-step reset leaves steps == 1) -- SET: of
+                    // an episode, reset()'s or an in-step reset's: a launch boundary is no episode boundary, the held value came
+                    // in from memory.  The collector's extra pass forms e_T without committing it: what goes back to memory is
+                    // the state after the last played step, and the next launch's first step forms the same e_T again.
+                    const bool corr_first = CORR && (SET ? steps == 1 : (t == 0 || steps == 1));
+                    const bool corr_commit = !SET || t != T_steps;         // (wave-uniform)
+                    (void)corr_first; (void)corr_commit;
 #pragma unroll
                     for (int k = 0; k < C; ++k) {
                         const int n = j * C + k;
                         float z0, z1, z2;
                         disturbance_normals(dw->k0, dw->k1, dist_lane, d_ep, (uint32_t)steps, (uint32_t)(n + 1), z0, z1, z2);
                         if constexpr (CORR) {             // e_t in z_t's place
-                            const CorrW* const cw = correlation_args(pw);
-                            z0 = correlated(corr_held + (3 * k) * 64, corr_first, cw->rho_sep, cw->q_sep, z0);
-                            z1 = correlated(corr_held + (3 * k + 1) * 64, corr_first, cw->rho_cpa, cw->q_cpa, z1);
-                            z2 = correlated(corr_held + (3 * k + 2) * 64, corr_first, cw->rho_closing, cw->q_closing, z2);
+                            const CorrW* const cw = SET ? &set_cw : correlation_args(pw);
+                            z0 = correlated(corr_held + (3 * k) * 64, corr_first, cw->rho_sep, cw->q_sep, z0, corr_commit);
+                            z1 = correlated(corr_held + (3 * k + 1) * 64, corr_first, cw->rho_cpa, cw->q_cpa, z1, corr_commit);
+                            z2 = correlated(corr_held + (3 * k + 2) * 64, corr_first, cw->rho_closing, cw->q_closing, z2, corr_commit);
                         }
                         float* const e = reinterpret_cast<float*>(row) + 5 + 3 * n;
                         e[0] = disturbed(e[0], dw->s_sep, z0, 0.0f, 1.0f);
@@ -392,6 +416,11 @@
                     if (set_dw.s_action != 0.0f) {        // keeps raw and its logp; slot 0 on the clipped action, clipped again
                         float z0, z1, z2;                 // (wave-uniform)
                         disturbance_normals(set_dw.k0, set_dw.k1, dist_lane, episode, (uint32_t)steps, 0u, z0, z1, z2);
+                        // e_t in z_t's place: the lane's last held value.  It commits: the extra pass (t == T_steps) never gets
+                        // here -- it leaves the loop at the `break` behind the obs_read flush above.  A draw moved in front of
+                        // that break must pass corr_commit, or the state stored behind the loop is one step ahead.
+                        if constexpr (CORR)
+                            z0 = correlated(corr_held + (3 * C) * 64, steps == 1, set_cw.rho_action, set_cw.q_action, z0);
                         action = (T)disturbed((float)action, set_dw.s_action, z0, -1.0f, 1.0f);
                     }
                 }
@@ -709,6 +738,19 @@
         // EVAL: the wave is done once every lane has latched its result (a wave-uniform exit: the loop body has no
         // workgroup barrier, only the wave's own LDS tile and fences)
         if constexpr (EVAL) { if (__ballot(running) == 0ull) break; }
+    }
+    if constexpr (CORR && SET) {
+        // The state after the last played step goes back to memory (the extra pass above committed nothing, so these are the
+        // values the last step left), through addresses formed here: none of them is live across the networks.  Every lane of
+        // a group holds the actuator's value; its first lane stores it.
+        int el_h = el;
+        asm volatile("" : "+v"(el_h));
+        if (active) {
+            float* const hp = collect_correlation_args(pw)->held + (e_wave + el_h);
+#pragma unroll
+            for (int i = 0; i < 3 * C; ++i) hp[(int64_t)(3 * (j * C) + i) * n_envs] = corr_held[i * 64];
+            if (j == 0) hp[(int64_t)(3 * N) * n_envs] = corr_held[(3 * C) * 64];
+        }
     }
     if constexpr (MC) {
         // the wave's integer sums: the counts as they are, the group leaders' two sums (every other lane adds 0) summed

@@ -165,7 +165,8 @@ EXPORTS = ("acas2d_abi_version", "acas2d_config_size", "acas2d_state_size", "aca
            "acas2d_monte_carlo_disturbed_group_f32", "acas2d_disturbance_draw_f32", "acas2d_collect_set_disturbed_f32",
            "acas2d_collect_set_disturbed_group_f32", "acas2d_correlation_size", "acas2d_evaluate_policies_correlated_f32",
            "acas2d_evaluate_policies_correlated_group_f32", "acas2d_monte_carlo_correlated_f32",
-           "acas2d_monte_carlo_correlated_group_f32")
+           "acas2d_monte_carlo_correlated_group_f32", "acas2d_collect_set_correlated_f32",
+           "acas2d_collect_set_correlated_group_f32")
 
 
 class NativeLibraryError(RuntimeError):
@@ -274,6 +275,13 @@ def lib():
         f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.POINTER(CStepIO), C.POINTER(CActorCritic), C.c_int32,
                       C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_uint64,
                       C.c_void_p, C.c_void_p]
+    # ... under time-correlated errors: then correlations (device float[K][8]) and held (device float[3 N + 1][E]) in front of it
+    for name in ("acas2d_collect_set_correlated_f32", "acas2d_collect_set_correlated_group_f32"):
+        f = getattr(L, name)
+        f.restype = C.c_int
+        f.argtypes = [C.POINTER(CConfig), C.POINTER(CState), C.POINTER(CStepIO), C.POINTER(CActorCritic), C.c_int32,
+                      C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_uint64,
+                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     for name in ("acas2d_ppo_update_set_f32", "acas2d_ppo_update_wide_set_f32"):
         f = getattr(L, name)
         f.restype = C.c_int

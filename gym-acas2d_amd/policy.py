@@ -16,6 +16,7 @@ import dataclasses
 import io
 import math
 import os
+import weakref
 import zipfile
 
 import numpy as np
@@ -265,7 +266,8 @@ class CorrelatedDisturbance(Disturbance):
                1: a constant offset s z_1 per (lane, episode, channel, aircraft), a bias.
     rho        shorthand for all four (one given by name overrides it).
     A CorrelatedDisturbance never equals a Disturbance, not even with all four 0: to_dict() carries the rho keys.  The
-    collectors and trainers are white-noise only and refuse one (an episode spans their launches)."""
+    collectors and trainers refuse a bare one -- an episode spans their launches, and a frozen value cannot hold the error
+    state between them: a CorrelatedDisturbanceSet does, and is what they take."""
     rho_sep: float
     rho_cpa: float
     rho_closing: float
@@ -353,13 +355,22 @@ class DisturbanceSet:
                     state that names another disturbance: a run goes on under the noise it was started with."""
 
     def __init__(self, disturbances, n_members=1):
-        K = int(n_members)
-        ds = [disturbances] * K if isinstance(disturbances, Disturbance) else list(disturbances)
-        if not all(isinstance(d, Disturbance) for d in ds):
-            raise TypeError("a Disturbance, or one per member, is required, got %r" % (disturbances,))
+        ds = self._as_members(disturbances, n_members)
         if any(isinstance(d, CorrelatedDisturbance) for d in ds):
             raise ValueError("the collectors are white-noise only: a CorrelatedDisturbance is for evaluate_policies_fused() and "
-                             "MonteCarlo (in a collector an episode spans launches, and the error state does not persist)")
+                             "MonteCarlo (in a collector an episode spans launches, and the error state does not persist) -- "
+                             "a CorrelatedDisturbanceSet holds that state and trains under one")
+        self._set_members(ds, n_members)
+
+    @staticmethod
+    def _as_members(disturbances, n_members):
+        ds = [disturbances] * int(n_members) if isinstance(disturbances, Disturbance) else list(disturbances)
+        if not all(isinstance(d, Disturbance) for d in ds):
+            raise TypeError("a Disturbance, or one per member, is required, got %r" % (disturbances,))
+        return ds
+
+    def _set_members(self, ds, n_members):
+        K = int(n_members)
         if len(ds) != K:
             raise ValueError("one Disturbance, or one per member, is required: got %d for %d member(s)" % (len(ds), K))
         for k, d in enumerate(ds):
@@ -384,6 +395,82 @@ class DisturbanceSet:
 
     def load_state_dict(self, sd):
         other = None if sd is None else [Disturbance.from_dict(d) for d in sd["members"]]
+        if other is None or tuple(other) != self.members:
+            raise ValueError("load_state_dict: the state was saved under the disturbance %s, this run trains under %s -- "
+                             "a run goes on under the noise it was started with" % (
+                                 None if other is None else [d.to_dict() for d in other], [d.to_dict() for d in self.members]))
+
+
+class CorrelatedDisturbanceSet(DisturbanceSet):
+    """A DisturbanceSet whose members' errors may PERSIST (acas2d_collect_set_correlated_*): one disturbance for all members
+    or K with equal seeds, each a Disturbance (white: rho 0) or a CorrelatedDisturbance.  An episode spans collection
+    launches, so the set OWNS the error state between them -- mutable per-env data, which is why the way in is this object
+    and not a CorrelatedDisturbance handed to a collector.
+      rows, seed, members   as DisturbanceSet's, with the same checks
+      corr_rows     float32 [K, 8]: (rho_sep, rho_cpa, rho_closing, rho_action, then their gains records.correlation_gain())
+                    per member; the rho were checked when the members were made
+      held          None, then the device tensor float32 [3 N + 1, E] of e_{t-1} (row 3 n + c: traffic n's channel c; the last
+                    row: the actuator's), zeroed and bound to the env that first collects under the set: a second env, or a
+                    state of another E or N, is a ValueError.  reset_held() zeroes it; held_numpy() / load_held(array) carry
+                    it across a process restart, next to the env's own state_dict().
+      state_dict()  the members' to_dict(), rho keys included where a member has them; load_state_dict() refuses another
+                    disturbance or another correlation, in DisturbanceSet's words.
+    An env's held value is used where its steps > 1: after the env's reset() the first step of every episode starts the
+    processes afresh, so the state needs no reset of its own then."""
+
+    def __init__(self, disturbances, n_members=1):
+        self._set_members(self._as_members(disturbances, n_members), n_members)
+        rho = np.asarray([[getattr(d, name, 0.0) for name in CorrelatedDisturbance.RHO] for d in self.members], np.float32)
+        self.corr_rows = np.concatenate([rho, records.correlation_gain(rho)], axis=1).astype(np.float32)
+        self.held, self._env, self._pending = None, None, None
+
+    def bind(self, venv):
+        """The held state for a collection on `venv`: allocated (zeroed, or from load_held()'s array) at the first call,
+        the same tensor at every later one of the same env."""
+        shape = (3 * int(venv.n_traffic) + 1, int(venv.num_envs))
+        if self._env is not None and self._env() is not venv:
+            raise ValueError("this CorrelatedDisturbanceSet holds the error state of another env (the state is per env: one "
+                             "set per env)")
+        if self.held is None:
+            if self._pending is not None and self._pending.shape != shape:
+                raise ValueError("load_held: the state is %s, this env needs [3 N + 1, E] = %s"
+                                 % (list(self._pending.shape), list(shape)))
+            self.held = torch.zeros(shape, dtype=torch.float32, device=venv.device)
+            if self._pending is not None:
+                self.held.copy_(torch.as_tensor(self._pending))
+            self._pending = None
+        elif tuple(self.held.shape) != shape:
+            raise ValueError("the held state is %s, this env needs [3 N + 1, E] = %s" % (list(self.held.shape), list(shape)))
+        self._env = weakref.ref(venv)
+        return self.held
+
+    def reset_held(self):
+        """Zero the state: every process restarts as q z_t at its next step (as z_t where that step is an episode's first)."""
+        self._pending = None
+        if self.held is not None:
+            self.held.zero_()
+
+    def held_numpy(self):
+        """The state as a float32 array [3 N + 1, E] (None before the first collection and without load_held())."""
+        if self.held is None:
+            return None if self._pending is None else self._pending.copy()
+        return self.held.detach().cpu().numpy().copy()
+
+    def load_held(self, array):
+        """Put back what held_numpy() gave: at once where the state exists (same shape), else at the first collection."""
+        a = np.array(array, np.float32, copy=True)
+        if a.ndim != 2:
+            raise ValueError("load_held: a [3 N + 1, E] array is required, got %s" % (list(a.shape),))
+        if self.held is None:
+            self._pending = a
+        elif tuple(self.held.shape) != a.shape:
+            raise ValueError("load_held: the state is %s, this set holds %s" % (list(a.shape), list(self.held.shape)))
+        else:
+            self.held.copy_(torch.as_tensor(a))
+
+    def load_state_dict(self, sd):
+        make = lambda d: (CorrelatedDisturbance if any(k in d for k in CorrelatedDisturbance.RHO) else Disturbance).from_dict(d)  # noqa: E731
+        other = None if sd is None else [make(d) for d in sd["members"]]
         if other is None or tuple(other) != self.members:
             raise ValueError("load_state_dict: the state was saved under the disturbance %s, this run trains under %s -- "
                              "a run goes on under the noise it was started with" % (

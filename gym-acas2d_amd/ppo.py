@@ -962,7 +962,10 @@ class PPOTrainer(_Trainer):
     collection's first step reads: torch's forward of it, or with gae="kernel" at n_traffic 1, 2, 3, 4, 8 gae_fused's own
     critic on obs_last = that row (then the bits of the next values[0]).  It is part of the env, as reward_norm is: it goes
     into state_dict() and beside every saved zip, and evaluate(disturbance=) scores under any other.  A zero Disturbance
-    trains the undisturbed run bit for bit (gae="kernel" aside, whose bootstrap value is then the kernel's)."""
+    trains the undisturbed run bit for bit (gae="kernel" aside, whose bootstrap value is then the kernel's).
+    A policy.CorrelatedDisturbanceSet of one member in its place trains under time-correlated and biased errors
+    (acas2d_collect_set_correlated_*): the set holds the per-env error state between the collection launches, everything
+    above stays as said, and with every rho 0 it trains the white run's bits.  A bare CorrelatedDisturbance is refused."""
 
     def __init__(self, venv, config=None, policy=None, use_graphs=None, collector=None, updater=None, gae=None,
                  diagnostics=False, reward_norm=None, disturbance=None):
@@ -1508,7 +1511,9 @@ class PopulationTrainer(_Trainer):
     levels), as PPOTrainer's `disturbance`: member k collects under its own four standard deviations
     (ACAS2DVecEnv.collect_set(disturbances=)), b_obs holds the rows its networks read, and the bootstrap value is its
     critic's on the disturbed row -- policy_set.values() of it, or with gae="kernel" at n_traffic 1, 2, 3, 4, 8 the
-    kernel's own.  Saved under member_<k>/ beside the zips and part of state_dict()."""
+    kernel's own.  Saved under member_<k>/ beside the zips and part of state_dict().  A policy.CorrelatedDisturbanceSet
+    of K members in their place: member k under its own correlations too (rho keys in the saved numbers), the error state of
+    all envs held by the set between launches -- it belongs to the envs, so a PBT exploit step copies none of it."""
 
     def __init__(self, venv, configs, gae=None, group=False, diagnostics=False, reward_norm=None, disturbances=None):
         configs = list(configs)

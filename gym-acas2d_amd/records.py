@@ -498,3 +498,19 @@ def correlated_errors(normals, rho):
             b = (q * z[t]).astype(np.float32)
             e[t] = np.where(white, z[t], (a + b).astype(np.float32))
     return e
+
+
+def correlated_step(held, normals, rho, first):
+    """ONE step of that scan, for a state that outlives the call (acas2d_collect_set_correlated_*, whose episodes span launches):
+    the new errors e_t from `held` = e_{t-1}, `normals` = z_t (float32 arrays of one shape), rho as in correlated_errors()
+    (broadcast against them) and `first`, a bool or bool array: where the step is an episode's first.  e_t = z_t where rho == 0
+    or first;  else (rho held) + (q z_t) in float32, two products and a sum, each rounded, no fma, q = correlation_gain(rho).
+    Returns e_t: the caller keeps it as the next step's `held` where rho != 0 (a channel with rho == 0 holds nothing)."""
+    z = np.asarray(normals, np.float32)
+    h = np.broadcast_to(np.asarray(held, np.float32), z.shape)
+    rho_b = np.broadcast_to(np.asarray(rho, np.float32), z.shape)
+    q = correlation_gain(rho_b)
+    with np.errstate(invalid="ignore", over="ignore"):
+        a = (rho_b * h).astype(np.float32)
+        b = (q * z).astype(np.float32)
+        return np.where((rho_b == 0) | np.broadcast_to(np.asarray(first, bool), z.shape), z, (a + b).astype(np.float32))

@@ -20,7 +20,7 @@ import torch
 
 from . import native
 from .config import ACAS2DConfig
-from .policy import DisturbanceSet, kernel_layout
+from .policy import CorrelatedDisturbanceSet, DisturbanceSet, kernel_layout
 from .spaces import Box
 
 _STATE_FIELDS = ("own_x", "own_y", "own_psi", "own_v", "goal_x", "goal_y",
@@ -380,7 +380,8 @@ class ACAS2DVecEnv:
     def _launch_collect(self, fn, keep, T, out, noise_seed, noise_step, set_args=(), dist=None):
         """collect() and collect_set() from the output dict to the launch: `fn` reads the 13 weight tensors `keep`;
         set_args is collect_set's (K, pointer to the members' noise keys); dist, for the disturbed entries, the
-        (DisturbanceSet, its rows on the device): the launch then also writes out["obs_read"] [T + 1, E, D]."""
+        (DisturbanceSet, its rows on the device) -- a CorrelatedDisturbanceSet's entries: then its corr_rows on the device and
+        its held state too: the launch then also writes out["obs_read"] [T + 1, E, D]."""
         if out is None:
             out = self._launch_out(T + 1, T, ("actions", "values", "logp"), new=torch.zeros)
         assert out["obs"].shape == (T + 1, self.num_envs, self.obs_dim)
@@ -389,7 +390,7 @@ class ACAS2DVecEnv:
             if out.get("obs_read") is None:
                 out["obs_read"] = torch.zeros_like(out["obs"])
             assert out["obs_read"].shape == out["obs"].shape and out["obs_read"].is_contiguous()
-            dist_args = (dist[1].data_ptr(), dist[0].seed, out["obs_read"].data_ptr())
+            dist_args = (dist[1].data_ptr(), dist[0].seed, out["obs_read"].data_ptr()) + tuple(t.data_ptr() for t in dist[2:])
         else:
             out.pop("obs_read", None)                 # (a reused dict: no stale rows under a key the trainers act on)
         ptr = lambda t: t.data_ptr()  # noqa: E731
@@ -485,7 +486,9 @@ class ACAS2DVecEnv:
         return out
 
     def _disturbed_entry(self, what, disturbances, n_members, group):
-        """The disturbed set collector's entry, the DisturbanceSet and its rows on the device (float32 only)."""
+        """The disturbed set collector's entry and _launch_collect()'s `dist`: the DisturbanceSet and its rows on the device
+        (float32 only).  A CorrelatedDisturbanceSet: the correlated collector's entry, and `dist` also carries its
+        coefficient rows on the device and the held state it keeps for THIS env."""
         if self.dtype != torch.float32:
             raise ValueError("%s under a disturbance is float32 only, this env is %s" % (what, self.dtype))
         ds = disturbances if isinstance(disturbances, DisturbanceSet) else DisturbanceSet(disturbances, n_members)
@@ -494,8 +497,12 @@ class ACAS2DVecEnv:
         if self.config.max_steps + 1 >= 2 ** 20:
             raise ValueError("%s under a disturbance needs max_steps + 1 < 2^20 (the step field of the noise counter), got "
                              "max_steps = %d" % (what, self.config.max_steps))
+        rows = torch.as_tensor(ds.rows).to(self.device).contiguous()
+        if isinstance(ds, CorrelatedDisturbanceSet):
+            fn = self._lib.acas2d_collect_set_correlated_group_f32 if group else self._lib.acas2d_collect_set_correlated_f32
+            return fn, (ds, rows, torch.as_tensor(ds.corr_rows).to(self.device).contiguous(), ds.bind(self))
         fn = self._lib.acas2d_collect_set_disturbed_group_f32 if group else self._lib.acas2d_collect_set_disturbed_f32
-        return fn, ds, torch.as_tensor(ds.rows).to(self.device).contiguous()
+        return fn, (ds, rows)
 
     def collect(self, policy, n_steps, noise_seed=0, noise_step=0, out=None, group=False, disturbance=None):
         """The collector of one PPO iteration in ONE kernel launch (acas2d_collect_*; SB3 `collect_rollouts` as
@@ -512,15 +519,19 @@ class ACAS2DVecEnv:
         (obs_read[t]: what action t was drawn on and values[t] is the value of; obs_read[T]: the bootstrap row, whose
         value is the next collection's values[0]); "obs" stays the true observations, "actions" the raw draws, and the
         env flies clip(clip(a) + s_action z).  The noise depends on (disturbance.seed, global env index, the env's episode
-        counter, its step) only; a zero disturbance returns collect()'s bits and obs_read == obs."""
+        counter, its step) only; a zero disturbance returns collect()'s bits and obs_read == obs.
+        disturbance=CorrelatedDisturbanceSet(...) (acas2d_collect_set_correlated_* with one member): the same under
+        time-correlated and biased errors.  The set holds the per-env error state between launches, so the errors do not
+        depend on how training is cut into collections; obs_read[T] is formed without committing its error, and equals the
+        next collection's obs_read[0].  A bare CorrelatedDisturbance is refused: it has nowhere to keep that state."""
         if not self.auto_reset:
             raise RuntimeError("collect() has VecEnv auto-reset semantics; construct with auto_reset=True")
         dist = None
         if disturbance is not None:
             if group:
-                self._group_entry("collect", "acas2d_collect_set_disturbed_group_f32")
-            fn_d, ds, rows = self._disturbed_entry("collect()", disturbance, 1, group)
-            dist = (ds, rows)
+                self._group_entry("collect", "acas2d_collect_set_correlated_group_f32" if isinstance(
+                    disturbance, CorrelatedDisturbanceSet) else "acas2d_collect_set_disturbed_group_f32")
+            fn_d, dist = self._disturbed_entry("collect()", disturbance, 1, group)
         if group:
             fn = self._group_entry("collect", "acas2d_collect_group_f32")
         else:
@@ -538,7 +549,7 @@ class ACAS2DVecEnv:
         if dist is not None:         # one member: its key on the device, the 13 tensors are the stacks of one
             keys = torch.as_tensor(np.asarray([key], np.uint64).view(np.int64)).to(dev)
             out = self._launch_collect(fn_d, keep, T, out, 0, noise_step, (1, keys.data_ptr()), dist=dist)
-            keep = keep + [keys, rows]
+            keep = keep + [keys] + list(dist[1:])
         else:
             out = self._launch_collect(fn, keep, T, out, key, noise_step)
         out["_weights"] = keep       # keep the transposed copies alive until the launch ran
@@ -582,7 +593,9 @@ class ACAS2DVecEnv:
         then equal collect(member k, group=True).
         disturbances: one Disturbance for all members or K of them with equal seeds (acas2d_collect_set_disturbed_*), as
         collect(disturbance=): the dict gains "obs_read"; member k's columns equal collect(member k, disturbance=its own)
-        on its envs, and a member whose four standard deviations are 0 collects what it does without."""
+        on its envs, and a member whose four standard deviations are 0 collects what it does without.  A
+        CorrelatedDisturbanceSet of K members (acas2d_collect_set_correlated_*): each member under its own correlations, the
+        error state of all envs held by the set between launches; a member whose four rho are 0 collects the white bits."""
         if not self.auto_reset:
             raise RuntimeError("collect_set() has VecEnv auto-reset semantics; construct with auto_reset=True")
         K = int(policy_set.n_members)
@@ -601,10 +614,9 @@ class ACAS2DVecEnv:
             raise ValueError("collect_set() needs one noise seed per member: %d for %d members" % (keys.numel(), K))
         dist = None
         if disturbances is not None:
-            fn, ds, rows = self._disturbed_entry("collect_set()", disturbances, K, group)
-            dist = (ds, rows)
+            fn, dist = self._disturbed_entry("collect_set()", disturbances, K, group)
         out = self._launch_collect(fn, keep, T, out, 0, noise_step, (K, keys.data_ptr()), dist=dist)
-        out["_weights"] = keep + [keys] + ([] if dist is None else [dist[1]])   # alive until the launch ran
+        out["_weights"] = keep + [keys] + ([] if dist is None else list(dist[1:]))   # alive until the launch ran
         return out
 
     # the per-step arrays: views of the live generation

@@ -596,6 +596,45 @@ int acas2d_collect_set_disturbed_group_f32(const Acas2dConfig *cfg, const Acas2d
                                            void *obs_read, void *stream);
 
 /*
+ * acas2d_collect_set_correlated_f32 / acas2d_collect_set_correlated_group_f32: the disturbed collectors above under the
+ * time-correlated and biased errors of Acas2dCorrelation -- the collector of a PPO iteration that TRAINS under them.  An
+ * episode spans collection launches, so the error state lives in device memory between them.  Additive to ABI 7, float32
+ * only.  The disturbed sibling's arguments, then `correlations` and `held` in front of `stream`.
+ *   correlations  device float[n_members][8]: member k's rho_sep, rho_cpa, rho_closing, rho_action, then the four gains
+ *                 q = (float)sqrt(1 - (double)rho * rho) in the same order.  Like sigmas it lives on the device, so the entry
+ *                 cannot look at it: the CALLER makes sure each rho is in [0, 1] and each gain is the one that belongs to it
+ *                 (the Python host does).
+ *   held          device float[3 * n_traffic + 1][n_envs], in and out: row 3 n + c is traffic n's channel c (sep, cpa,
+ *                 closing), row 3 * n_traffic the actuator's, column i env i of THIS launch.  The caller zeroes it once and
+ *                 hands the same buffer to every launch on these envs.
+ * With z_t the white model's normal of (dist_seed, global env, episode, step, slot), a channel's error is
+ *   e_t = z_t                                  where the env's game.steps is 1 before the step's increment: the first step
+ *                                              of an episode, after acas2d_reset_* and after an in-step reset alike;
+ *   e_t = fadd(fmul(rho, e_{t-1}), fmul(q, z_t))  otherwise, three roundings, no fma, e_{t-1} the value the env held after the
+ *                                              previous step it played -- in this launch or an earlier one.
+ * A launch boundary is no episode boundary: the errors are a function of (dist_seed, global env, episode, step, slot, rho)
+ * only, not of how training is cut into launches, of n_members or of the work shape.  A channel whose rho is 0 takes z_t
+ * and leaves its held value alone; so does a channel where nothing is drawn (the member's three sensor sigmas all 0; its
+ * action sigma 0).  A member whose four rho are 0 gives the disturbed sibling's outputs bit for bit.  rho == 1 is a
+ * constant bias s z_1 per (env, episode, channel, aircraft).  A held value of 0 under steps > 1 -- a state set by hand, a
+ * buffer zeroed in mid-episode -- gives e_t = q z_t.
+ * obs_read[n_steps] is formed from the held e_{n_steps - 1} WITHOUT committing it: `held` returns as the last played step
+ * left it, and the next launch's first step forms the same row again.
+ * Rejected with ACAS2D_EINVAL before anything is launched: everything the disturbed sibling rejects, in its words and its
+ * order; then a NULL correlations; then a NULL held; then held overlapping obs_read, io->obs or obs_in.
+ */
+int acas2d_collect_set_correlated_f32(const Acas2dConfig *cfg, const Acas2dState *state, const Acas2dStepIO *io,
+                                      const Acas2dActorCritic *ac, int32_t n_members, const uint64_t *noise_seeds,
+                                      const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset, int64_t n_envs,
+                                      int32_t n_traffic, const float *sigmas, uint64_t dist_seed, void *obs_read,
+                                      const float *correlations, float *held, void *stream);
+int acas2d_collect_set_correlated_group_f32(const Acas2dConfig *cfg, const Acas2dState *state, const Acas2dStepIO *io,
+                                            const Acas2dActorCritic *ac, int32_t n_members, const uint64_t *noise_seeds,
+                                            const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
+                                            int64_t n_envs, int32_t n_traffic, const float *sigmas, uint64_t dist_seed,
+                                            void *obs_read, const float *correlations, float *held, void *stream);
+
+/*
  * acas2d_encounter_sample_f32 / _f64, acas2d_encounter_select_f32 / _f64, acas2d_encounter_refit: a cross-entropy search
  * over encounters with importance sampling, around the unchanged acas2d_evaluate_policies_stats_* -- per generation:
  * sample, acas2d_reset_* with do_init = 0 (the first observation), the stats entry, select, refit, with no host decision

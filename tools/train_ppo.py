@@ -67,10 +67,26 @@ ap.add_argument("--disturbance", metavar="sep=..,cpa=..,closing=..,action=..[,se
                      "aircraft and step) and actuator disturbance (in units of the action), in the syntax of "
                      "tools/evaluate_checkpoints.py (policy.Disturbance; DESIGN.md 4.2p): the actor and the critic read the "
                      "disturbed observation, the update is given those rows.  Needs --collector fused.  With --population: once "
-                     "for all members, or K times, one per member, with equal seeds")
+                     "for all members, or K times, one per member, with equal seeds.  With rho=.. (all four channels) or "
+                     "rho_sep=, rho_cpa=, rho_closing=, rho_action= the errors persist from step to step (policy."
+                     "CorrelatedDisturbance in a CorrelatedDisturbanceSet, which holds the per-env error state between the "
+                     "collection launches; DESIGN.md 4.2r): rho 1 is a constant bias per episode")
 ap.add_argument("--disturbance-normalised", action="store_true",
                 help="--disturbance's sep, cpa and closing are in units of the normalised observation instead")
 ap.add_argument("--out", default=None)
+
+
+def training_disturbances(texts, n_members, normalised):
+    """--disturbance's texts as the trainers take them: a text that names a correlation makes the set a
+    CorrelatedDisturbanceSet (its other members white: rho 0), else one Disturbance or one per member as before."""
+    if any(g.CorrelatedDisturbance.has_rho(t) for t in texts):
+        ds = [g.CorrelatedDisturbance.parse(t, normalised=normalised) if g.CorrelatedDisturbance.has_rho(t)
+              else g.Disturbance.parse(t, normalised=normalised) for t in texts]
+        return g.CorrelatedDisturbanceSet(ds[0] if len(ds) == 1 else ds, n_members)
+    ds = [g.Disturbance.parse(t, normalised=normalised) for t in texts]
+    return ds[0] if len(ds) == 1 else ds
+
+
 args = ap.parse_args()
 if args.pbt and not args.population:
     ap.error("--pbt needs --population K")
@@ -81,11 +97,9 @@ if args.disturbance:
     if args.collector != "fused" and not args.population:
         ap.error("--disturbance needs --collector fused: the noise is drawn inside the fused collection launch")
     try:
-        DISTURBANCES = [g.Disturbance.parse(t, normalised=args.disturbance_normalised) for t in args.disturbance]
+        DISTURBANCES = training_disturbances(args.disturbance, max(args.population, 1), args.disturbance_normalised)
     except ValueError as e:
         ap.error(str(e))
-    if len(DISTURBANCES) == 1:
-        DISTURBANCES = DISTURBANCES[0]
 REWARD_NORM = True if args.reward_norm else None
 # clip_range_vf and the schedules, as PPOConfig takes them
 OPTIONS = dict(clip_range_vf=args.clip_range_vf,
