@@ -1,8 +1,9 @@
 """Shared by tests/test_disturbance.py and tests/test_correlated.py: the shapes, the host loop the noisy evaluators are held
 to, the campaign's reference and the properties a campaign is used for -- once each, for every error model.
 
-A Flavour names an error model and builds its test disturbance; the cached helpers are keyed by its name.  The sigmas are
-the same for all of them, so the white campaign is the correlated one's at every rho 0 and both files share its run.
+A Flavour names an error model and builds its test disturbance; the cached helpers are keyed by its name.  WHITE and
+CORRELATED have the same sigmas, so the white campaign is the correlated one's at every rho 0 and both files share its run;
+SATURATING and SATURATING_CORRELATED are their twins under sigmas of two box widths, where the clamps decide every step.
 
 References (no new arithmetic, no tolerance):
   evaluator  host_loop(): per step the observation of a latching env, records.disturb_observation() with the errors of the
@@ -17,21 +18,46 @@ import numpy as np
 import pytest
 import torch
 
+import edge_observations as EO
 import eval_stats_support as ES
 import monte_carlo_support as MS
 
 DEV = ES.DEV
 F32 = torch.float32
 # (n_traffic, group)
-EVAL_SHAPES = ((1, False), (3, False), (8, False), (16, True), (64, True))
-ZERO_SHAPES = EVAL_SHAPES[:4]
+# all nine compiled work shapes (C, G): (1,1) (3,1) (8,1) (4,4) (4,16) (2,1) (4,1) (4,2) (4,8)
+EVAL_SHAPES = ((1, False), (3, False), (8, False), (16, True), (64, True), (2, False), (4, False), (8, True), (32, True))
 CAMPAIGN_SHAPES = [MS.Shape(F32, True, n, grp, max_steps) for max_steps in (1000, 150) for n, grp in ((1, False), (8, False), (16, True))]
+# the other six work shapes, for the equality with the evaluator alone, under the short config
+CAMPAIGN_MORE = [MS.Shape(F32, True, n, grp, 150) for n, grp in ((2, False), (3, False), (4, False), (8, True), (32, True), (64, True))]
 NOISE_EPISODE = 5
 SIGMAS = dict(sep=0.05, cpa=0.1, closing=0.1, action=0.3, seed=7)
+# most of what the actor reads lies at an end of its box, and most of what is flown is +-1: the clamps decide every step
+SATURATING_SIGMAS = dict(sep=2.0, cpa=4.0, closing=4.0, action=4.0, seed=7)
+SATURATING_EVAL_SHAPES = ((3, False), (16, True))
+SATURATING_CAMPAIGN_SHAPE = MS.Shape(F32, True, 8, False, 150)
+RHO = dict(rho_sep=0.9, rho_cpa=1.0, rho_closing=0.0, rho_action=0.5)
+
+
+def rho_of_slots(dist, N):
+    """[N + 1, 3]: the coefficient of every value of a lane's draw -- slot 0 the actuator's normal (and two zeros), slot n + 1
+    traffic n's three channels."""
+    return np.asarray([[dist.rho_action, 0.0, 0.0]] + [list(dist.rho)] * N, np.float32)
+
+
+def correlated_series(g, dist, N):
+    """The host loop's series under `dist`: the errors the normals drive, scanned from the episode's first step
+    (game.steps == 1) on."""
+    return lambda normals: np.concatenate([normals[:1], g.records.correlated_errors(normals[1:], rho_of_slots(dist, N))])
+
 
 # disturbance(g): the flavour's one test disturbance; errors(g, dist, N): host_loop()'s `errors` under it, or None
 Flavour = namedtuple("Flavour", "name disturbance errors", defaults=(None,))
 WHITE = Flavour("white", lambda g: g.Disturbance.normalised(**SIGMAS))
+CORRELATED = Flavour("correlated", lambda g: g.CorrelatedDisturbance.normalised(**SIGMAS, **RHO), correlated_series)
+SATURATING = Flavour("saturating", lambda g: g.Disturbance.normalised(**SATURATING_SIGMAS))
+SATURATING_CORRELATED = Flavour("saturating-correlated", lambda g: g.CorrelatedDisturbance.normalised(**SATURATING_SIGMAS, **RHO),
+                                correlated_series)
 
 
 def shape_id(s):
@@ -40,6 +66,9 @@ def shape_id(s):
 
 EVAL_IDS = [shape_id(s) for s in EVAL_SHAPES]
 CAMPAIGN = pytest.mark.parametrize("s", CAMPAIGN_SHAPES, ids=[MS.shape_id(s) for s in CAMPAIGN_SHAPES])
+CAMPAIGN_EVERY_SHAPE = pytest.mark.parametrize("s", CAMPAIGN_SHAPES + CAMPAIGN_MORE,
+                                               ids=[MS.shape_id(s) for s in CAMPAIGN_SHAPES + CAMPAIGN_MORE])
+SATURATING_EVAL = pytest.mark.parametrize("shape", SATURATING_EVAL_SHAPES, ids=[shape_id(s) for s in SATURATING_EVAL_SHAPES])
 
 
 def fused(g, N, group, **kw):
@@ -55,10 +84,11 @@ def same(g, got, want):
 
 
 # ---- the evaluator against a host loop -------------------------------------------------------------------------------------------------
-def host_loop(g, cfg, eps, policy, dist, noise_episode, group, errors=None):
+def host_loop(g, cfg, eps, policy, dist, noise_episode, group, errors=None, seen=None):
     """One policy's reference rows [E] by the per-step path: (outcome, steps, total_reward, stats dict, summary dict).
     `errors`: from the drawn normals [step, lane, slot, 3] to the series the loop indexes; None: the normals themselves,
-    the white model."""
+    the white model.  `seen`: a list that takes, per step, (the rows the actor read, the actions flown) of the envs still
+    playing."""
     E, N = ES.E, cfg.n_traffic
     n_steps = cfg.max_steps + 1
     zero = np.zeros(E, np.int32)
@@ -82,6 +112,8 @@ def host_loop(g, cfg, eps, policy, dist, noise_episode, group, errors=None):
         scratch.outputs["obs"].copy_(torch.as_tensor(noisy, device=DEV))
         action = scratch.rollout_policy(policy, 1, group=group)["actions"][0].cpu().numpy()
         flown = g.records.disturb_action(action, dist.s_action, z[:, 0, 0])
+        if seen is not None:
+            seen.append((noisy[active], flown[active]))
         _, _, done, infos = r.step(torch.as_tensor(flown, device=DEV))
         cols.append(r.trace.clone())
         fin = active & done.cpu().numpy()
@@ -109,7 +141,7 @@ def host_loop(g, cfg, eps, policy, dist, noise_episode, group, errors=None):
     return outcome, steps, ret, stats, summary
 
 
-_LOOP, _RAN = {}, {}
+_LOOP, _RAN, _SEEN = {}, {}, {}
 
 
 def loop_reference(g, fl, N, group):
@@ -119,12 +151,34 @@ def loop_reference(g, fl, N, group):
         eps = ES.episodes(cfg)
         dist = fl.disturbance(g)
         errors = fl.errors and fl.errors(g, dist, N)
-        _LOOP[fl.name, N, group] = [host_loop(g, cfg, eps, pol, dist, NOISE_EPISODE, group, errors) for pol in ES.two_policies(g, N)]
+        seen = _SEEN[fl.name, N, group] = []
+        _LOOP[fl.name, N, group] = [host_loop(g, cfg, eps, pol, dist, NOISE_EPISODE, group, errors, seen) for pol in ES.two_policies(g, N)]
     return _LOOP[fl.name, N, group]
 
 
-def evaluator_equals_the_host_loop(g, fl, shape):
-    """The fused evaluator's rows against loop_reference()'s, bit for bit."""
+def loop_seen(g, fl, N, group):
+    """(rows read [n, 5 + 3 N], actions flown [n]) over every step either policy played in loop_reference()."""
+    loop_reference(g, fl, N, group)
+    seen = _SEEN[fl.name, N, group]
+    return np.concatenate([s[0] for s in seen]), np.concatenate([s[1] for s in seen])
+
+
+def saturating_evaluator_equals_the_host_loop(g, fl, shape):
+    """Under the saturating sigmas -- asserted first, on the reference alone: every episode finished and the clamps decide
+    (edge_observations.check_saturated).  Every episode flies a +-1 at some step, so max_abs_a_lat is the limit under every
+    noise counter: the counter shows in the mean deviation, which the whole flown path makes."""
+    N, group = shape
+    limit = np.float32(ES.config(g, N).to_c().acc_lat_limit)
+    for row in loop_reference(g, fl, N, group):
+        assert (row[0] != 0).all(), "an episode of the reference did not finish"
+        assert (row[4]["max_abs_a_lat"] == limit).all()
+    EO.check_saturated(*loop_seen(g, fl, N, group), g.records.OBSERVATION_BOX)
+    evaluator_equals_the_host_loop(g, fl, shape, counter_shows_in="mean_abs_deviation")
+
+
+def evaluator_equals_the_host_loop(g, fl, shape, counter_shows_in="max_abs_a_lat"):
+    """The fused evaluator's rows against loop_reference()'s, bit for bit; another noise counter gives another
+    `counter_shows_in`."""
     N, group = shape
     got = fused(g, N, group, disturbance=fl.disturbance(g), noise_episode=NOISE_EPISODE)
     for k, (outcome, steps, ret, stats, summary) in enumerate(loop_reference(g, fl, N, group)):
@@ -134,7 +188,7 @@ def evaluator_equals_the_host_loop(g, fl, shape):
             assert ES.bits_equal(got[key][k], summary[key]), (k, key)
     # the counter is part of the noise
     other = fused(g, N, group, disturbance=fl.disturbance(g), noise_episode=NOISE_EPISODE + 1)
-    assert not ES.bits_equal(other["max_abs_a_lat"], got["max_abs_a_lat"])
+    assert not ES.bits_equal(other[counter_shows_in], got[counter_shows_in])
 
 
 # ---- the campaign against the evaluator ------------------------------------------------------------------------------------------------

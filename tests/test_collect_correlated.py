@@ -4,7 +4,8 @@ ACAS2DVecEnv.collect(disturbance=) / collect_set(disturbances=) with a policy.Co
   1  every rho 0: the white disturbed collector's bits, and the held state stays zero;
   2  correlated, against the white collector's host loop (test_collect_disturbed.host_loop) with the errors in the normals' place:
      per-env held arrays advanced by records.correlated_step() with first = (steps == 1) -- no other new arithmetic; the final
-     held state too;
+     held state too -- also under sigmas of two box widths, and (2b) on test_collect_disturbed's injected rows in two
+     consecutive one-step launches, the second of which reads the state: what is held is the error, not the clamped entry;
   3  one launch of 16 steps is two of 8 and sixteen of 1: a launch boundary is no episode boundary, and the extra pass for
      obs_read[T] commits nothing;
   4  member k of two with different rho is the one-member launch on its envs; a white member beside a correlated one is the
@@ -26,6 +27,7 @@ import numpy as np
 import pytest
 import torch
 
+import edge_observations as EO
 import eval_stats_support as ES
 import test_collect_disturbed as CD
 
@@ -85,7 +87,7 @@ ALL = ("obs_read",) + CD.KEYS + tuple("state." + n for n in CD.STATE)
 
 
 # ---- 1: every rho 0 ---------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", CD.ZERO_SHAPES, ids=[CD.shape_id(s) for s in CD.ZERO_SHAPES])
+@pytest.mark.parametrize("shape", CD.ALL_SHAPES, ids=[CD.shape_id(s) for s in CD.ALL_SHAPES])
 def test_zero_rho_is_the_white_collector(g, shape):
     N, group = shape
     white = CD.solo(g, N, group, "noisy")
@@ -149,6 +151,11 @@ def correlated_host_loop(g, monkeypatch, N, group, dist):
     return ref, err
 
 
+def held_rows_of(N):
+    """Which rows of the final held state are not all +0.0 under RHO: rho_closing = 0 holds nothing."""
+    return [True, True, False] * N + [True]
+
+
 @pytest.mark.parametrize("shape", CD.LOOP_SHAPES, ids=[CD.shape_id(s) for s in CD.LOOP_SHAPES])
 def test_correlated_collector_equals_the_host_loop(g, monkeypatch, shape):
     N, group = shape
@@ -163,7 +170,7 @@ def test_correlated_collector_equals_the_host_loop(g, monkeypatch, shape):
     moved = (ES.bits(white_rows) != ES.bits(ref["obs_read"])).any(-1)
     assert int(later.sum()) >= E1 and 2 * int((moved & later).sum()) > int(later.sum()), (int(moved.sum()), int(later.sum()))
     assert not moved[~later].any()                                                    # an episode's first step: z itself
-    assert ES.bits(ref["held"]).any(1).tolist() == ([True, True, False] * N + [True])   # rho_closing = 0 holds nothing
+    assert ES.bits(ref["held"]).any(1).tolist() == held_rows_of(N)                    # rho_closing = 0 holds nothing
     got = csolo(g, N, group, dist)
     for k in ALL + ("held",):
         assert ES.bits_equal(got[k], ref[k]), k
@@ -171,9 +178,49 @@ def test_correlated_collector_equals_the_host_loop(g, monkeypatch, shape):
     assert not ES.bits_equal(got["obs_read"], CD.solo(g, N, group, "noisy")["obs_read"])
 
 
+@pytest.mark.parametrize("shape", CD.SATURATING_SHAPES, ids=[CD.shape_id(s) for s in CD.SATURATING_SHAPES])
+def test_saturating_correlated_collector_equals_the_host_loop(g, monkeypatch, shape):
+    """Sigmas of two box widths: the clamps decide most entries and most actions, and the state is the error, not the entry."""
+    N, group = shape
+    dist = corr(g, **EO.SATURATING)
+    ref, err = correlated_host_loop(g, monkeypatch, N, group, dist)
+    CD.every_env_was_reset(ref, E1)
+    EO.check_saturated(ref["obs_read"], ref["flown"], g.records.OBSERVATION_BOX)      # teeth, on the reference alone
+    assert ES.bits(ref["held"]).any(1).tolist() == held_rows_of(N)
+    got = csolo(g, N, group, dist)
+    for k in ALL + ("held",):
+        assert ES.bits_equal(got[k], ref[k]), k
+
+
+# ---- 2b: hand-placed entries in the row the launch reads ---------------------------------------------------------------------------
+@pytest.mark.parametrize("case", CD.INJECTED, ids=[CD.injected_id(c) for c in CD.INJECTED])
+def test_injected_rows_meet_the_reference(g, case):
+    """test_collect_disturbed's injected rows through a CorrelatedDisturbanceSet with RHO, in two consecutive one-step
+    collections, each with a freshly injected row: the second reads the held state.  The state is compared after each."""
+    (N, group), name = case
+    dist = corr(g, **EO.DISTURBANCES[name])
+    ds = g.CorrelatedDisturbanceSet(dist, 1)
+    err = Errors(g, dist, E1, N, 2)
+    CD.injected_rows_meet_the_reference(g, (N, group), dist, launches=2, draw=err, dset=ds, vanishing=name == "vanishing",
+                                        held=lambda: (ds.held_numpy(), err.held()))
+    # (an env the first step finished -- a fresh draw can start inside a collision -- starts afresh, steps == 1 again: the
+    #  others, at least a tenth of the envs, read the state)
+    assert err.calls == 2 and (err.steps[0] == 1).all() and set(err.steps[1].tolist()) <= {1, 2}
+    assert 10 * int((err.steps[1] == 2).sum()) >= E1
+    sensors, held = any(dist.sigma), err.held()
+    assert ES.bits(held).any(1).tolist() == [sensors, sensors, False] * N + [dist.s_action != 0]
+    if name == "saturating":
+        # what is held is the unclamped error e_t, not what the clamp left of the entry
+        assert 10 * int((np.abs(held[:-1]) > 1).sum()) >= held[:-1].size
+
+
 # ---- 3: cuts ------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", ((3, False), (16, True)), ids=["N3", "N16-group"])
-@pytest.mark.parametrize("pieces", (2, 16))
+# (the pieces of one step also at (4,1) and at (4,8): eight envs per wave there, so the last wave of the 70 holds six -- lanes
+#  past the last env neither load nor store held state)
+CUTS = [(2, (3, False)), (2, (16, True)), (16, (3, False)), (16, (16, True)), (16, (4, False)), (16, (32, True))]
+
+
+@pytest.mark.parametrize("pieces,shape", CUTS, ids=["%d-%s" % (p, CD.shape_id(s)) for p, s in CUTS])
 def test_one_launch_is_its_pieces(g, shape, pieces):
     N, group = shape
     whole = csolo(g, N, group, corr(g))

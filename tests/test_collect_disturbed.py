@@ -4,7 +4,10 @@ ACAS2DVecEnv.collect(disturbance=), collect_set(disturbances=), the trainers' di
   1  all four standard deviations 0: the plain collectors' bits, and obs_read is the true observation;
   2  disturbed, against a host loop with no new arithmetic -- per step the true observation and (episode, steps) of a
      per-step env, records.disturb_observation() on the draw entry's normals (= obs_read[t], bit for bit), the project's own
-     networks and sampler through a one-step undisturbed collect() on that row, records.disturb_action(), the env step;
+     networks and sampler through a one-step undisturbed collect() on that row, records.disturb_action(), the env step --
+     also under sigmas of two box widths, and (2b) on rows whose traffic entries are tests/edge_observations.py's table: the
+     ends of the boxes and their neighbours, both zeros, denormals, +-FLT_MAX, +-inf and NaN under one channel at a time, a
+     saturating, a vanishing and an overflowing disturbance -- the handle on the device function disturbed();
   3  member k of two with different sigmas is the one-member launch on its envs; a zero member beside a noisy one is the
      plain collector;  4  thread-per-env and group shape agree at eight aircraft;  5  one launch of 16 steps is two of 8;
   6  gae_fused on obs_read[T] returns the bits of the next collection's values[0];
@@ -14,11 +17,13 @@ ACAS2DVecEnv.collect(disturbance=), collect_set(disturbances=), the trainers' di
      leaves the members' sigmas where they were.
 
 70 envs for one member (two waves thread per env, one of them partial), 2 x 64 for two, 16 steps, and max_steps = 5: every env
-times out and is reset inside every launch, three times in 16 steps."""
+times out and is reset inside every launch, three times in 16 steps.  1 and 2b run at all nine compiled work shapes, 2 at
+every one but (4,2), which 4 holds to (8,1)."""
 import numpy as np
 import pytest
 import torch
 
+import edge_observations as EO
 import eval_stats_support as ES
 
 pytestmark = pytest.mark.gpu
@@ -30,8 +35,14 @@ NOISE_SEED, NOISE_STEP = 21, 3
 KEYS = ("obs", "actions", "values", "logp", "reward", "done_u8", "outcome", "episode_return", "episode_steps")
 STATE = ("own_x", "own_y", "own_psi", "trf_x", "trf_y", "trf_psi", "trf_v", "steps", "total_reward", "episode")
 # (n_traffic, group)
-ZERO_SHAPES = ((1, False), (3, False), (8, False), (16, True))
-LOOP_SHAPES = ZERO_SHAPES + ((64, True),)
+# the host loop: every compiled work shape but (4,2), which test_work_shape_does_not_matter holds to (8,1)
+LOOP_SHAPES = ((1, False), (3, False), (8, False), (16, True), (64, True), (2, False), (4, False), (32, True))
+# all nine compiled work shapes (C, G): (1,1) (3,1) (8,1) (4,4) (4,16) (2,1) (4,1) (4,8) (4,2)
+ALL_SHAPES = LOOP_SHAPES + ((8, True),)
+SATURATING_SHAPES = ((3, False), (16, True))
+# the injected rows: every disturbance of edge_observations at three shapes, the saturating one at all nine
+INJECTED = ([(s, name) for s in ((1, False), (3, False), (16, True)) for name in EO.DISTURBANCES] +
+            [(s, "saturating") for s in ALL_SHAPES if s not in ((1, False), (3, False), (16, True))])
 # torch's log-probability against the collector's: the bound of the fused-collector test (test_ppo.py: largest and mean
 # absolute difference)
 LOGP_MAX, LOGP_MEAN = 2e-3, 2e-5
@@ -49,6 +60,14 @@ def g():
 
 def noisy(g, seed=7):
     return g.Disturbance.normalised(sep=0.05, cpa=0.1, closing=0.1, action=0.3, seed=seed)
+
+
+def saturating(g):
+    return g.Disturbance.normalised(**EO.SATURATING, seed=EO.SEED)
+
+
+def injected_id(case):
+    return "%s-%s" % (shape_id(case[0]), case[1])
 
 
 def make_env(g, E, N, offset=0):
@@ -94,7 +113,8 @@ def solo(g, N, group, dist="noisy", E=E1, offset=0, seed=1, key=NOISE_SEED, cuts
     name = (N, group, dist, E, offset, seed, key, cuts)
     if name not in _RUNS:
         env, pol = make_env(g, E, N, offset), policy(g, N, seed)
-        d = {"noisy": noisy(g), "zero": g.Disturbance(seed=99), None: None}[dist] if isinstance(dist, (str, type(None))) else dist
+        d = ({"noisy": noisy(g), "zero": g.Disturbance(seed=99), "saturating": saturating(g), None: None}[dist]
+             if isinstance(dist, (str, type(None))) else dist)
         outs, at = [], NOISE_STEP
         for n in cuts:
             outs.append(host(env.collect(pol, n, noise_seed=key, noise_step=at, group=group,
@@ -117,7 +137,7 @@ def pair(g, N, group, dists):
 
 
 # ---- 1: zero is identity ------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", ZERO_SHAPES, ids=[shape_id(s) for s in ZERO_SHAPES])
+@pytest.mark.parametrize("shape", ALL_SHAPES, ids=[shape_id(s) for s in ALL_SHAPES])
 def test_zero_sigmas_are_the_plain_collectors(g, shape):
     N, group = shape
     plain, zero = solo(g, N, group, None), solo(g, N, group, "zero")
@@ -192,6 +212,65 @@ def test_disturbed_collector_equals_the_host_loop(g, shape):
     # the seed is part of the noise
     other = solo(g, N, group, noisy(g, seed=8))
     assert not ES.bits_equal(other["obs_read"], got["obs_read"]) and not ES.bits_equal(other["reward"], got["reward"])
+
+
+@pytest.mark.parametrize("shape", SATURATING_SHAPES, ids=[shape_id(s) for s in SATURATING_SHAPES])
+def test_saturating_collector_equals_the_host_loop(g, shape):
+    """Sigmas of two box widths: the clamps of disturbed() decide most entries of every row and most actions."""
+    N, group = shape
+    ref = host_loop(g, N, group, saturating(g))
+    every_env_was_reset(ref, E1)
+    EO.check_saturated(ref["obs_read"], ref["flown"], g.records.OBSERVATION_BOX)      # teeth, on the reference alone
+    got = solo(g, N, group, "saturating")
+    for k in ("obs_read",) + KEYS + tuple("state." + n for n in STATE):
+        assert ES.bits_equal(got[k], ref[k]), k
+
+
+# ---- 2b: hand-placed entries in the row the launch reads ---------------------------------------------------------------------------
+def injected_rows_meet_the_reference(g, shape, dist, launches=1, draw=None, dset=None, held=None, vanishing=False):
+    """One-step collections whose first row carries edge_observations' table in its traffic columns, written into
+    env.outputs["obs"] where the collector reads it.  Per launch, no new arithmetic: obs_read[0] is
+    records.disturb_observation() of that row under `draw` (normals_for's signature: the normals, or the errors in their
+    place) at the env's (global lane, episode, steps); actions / values / logp [0] are the undisturbed one-step collect() on
+    the reference's row (the host loop's own step: the networks' NaN scrub is theirs); the env is sent
+    records.disturb_action() of the clipped action, so obs[1], reward and done are a per-step env's.  Bit for bit, but a NaN
+    of the reference may be any NaN.  dset: what collect() takes as disturbance= (default dist); held(): (the launch's,
+    the reference's) error state after each launch."""
+    N, group = shape
+    boxes = g.records.OBSERVATION_BOX
+    env, r, scratch, pol = make_env(g, E1, N), make_env(g, E1, N), make_env(g, E1, N), policy(g, N)
+    draw = draw or normals_for
+    for at in range(launches):
+        row = EO.inject(r.outputs["obs"].cpu().numpy(), boxes, shift=3 * at)
+        assert ES.bits_equal(row[:, :5], env.outputs["obs"].cpu().numpy()[:, :5])     # the own-ship five: as the env left them
+        z = draw(g, dist.seed, 0, r.episode.cpu().numpy().view(np.uint32), r.steps.cpu().numpy(), N)
+        read = g.records.disturb_observation(row, dist.sigma, z[:, 1:])
+        EO.check_reference(row, read, dist.sigma, boxes, vanishing)               # on the reference alone
+        scratch.outputs["obs"].copy_(torch.as_tensor(read, device=DEV))
+        one = scratch.collect(pol, 1, noise_seed=NOISE_SEED, noise_step=NOISE_STEP + at, group=group)
+        raw = one["actions"][0].cpu().numpy()
+        flown = g.records.disturb_action(np.clip(raw, np.float32(-1), np.float32(1)), dist.s_action, z[:, 0, 0])
+        assert np.isfinite(raw).all() and (np.abs(flown) <= 1).all()
+        env.outputs["obs"].copy_(torch.as_tensor(row, device=DEV))
+        got = host(env.collect(pol, 1, noise_seed=NOISE_SEED, noise_step=NOISE_STEP + at, group=group,
+                               disturbance=dist if dset is None else dset))
+        assert EO.same_but_for_nan_bits(got["obs_read"][0], read), at
+        assert ES.bits_equal(got["obs"][0], row), at                              # the true row: as it was written
+        for k in ("actions", "values", "logp"):
+            assert ES.bits_equal(got[k][0], one[k][0].cpu().numpy()), (at, k)
+        obs, rew, done, _ = r.step(torch.as_tensor(flown, device=DEV))
+        assert ES.bits_equal(got["obs"][1], obs.cpu().numpy()) and ES.bits_equal(got["reward"][0], rew.cpu().numpy()), at
+        assert np.array_equal(got["done_u8"][0], done.cpu().numpy().astype(np.uint8)), at
+        if held is not None:
+            ours, theirs = held()
+            assert ES.bits_equal(ours, theirs), at
+
+
+@pytest.mark.parametrize("case", INJECTED, ids=[injected_id(c) for c in INJECTED])
+def test_injected_rows_meet_the_reference(g, case):
+    shape, name = case
+    dist = g.Disturbance.normalised(**EO.DISTURBANCES[name], seed=EO.SEED)
+    injected_rows_meet_the_reference(g, shape, dist, vanishing=name == "vanishing")
 
 
 # ---- 3: members -------------------------------------------------------------------------------------------------------------------

@@ -11,7 +11,8 @@ policy.CorrelatedDisturbance): a first-order Gauss-Markov error per channel in t
 
 The shapes, the host loop, the campaign's reference and the campaign properties are tests/noise_scoring_support.py's, shared
 with tests/test_disturbance.py (whose white campaign is taken from the shared cache); CORRELATED is this file's flavour of
-them.  One test disturbance throughout: the sigmas of tests/test_disturbance.py with rho_sep = 0.9, rho_cpa = 1 (a bias),
+them.  1, 2 and the campaign's equality with the evaluator run at all nine compiled work shapes; 2 and that equality also
+under SATURATING_CORRELATED, where the clamps decide every step.  One test disturbance otherwise: the sigmas of tests/test_disturbance.py with rho_sep = 0.9, rho_cpa = 1 (a bias),
 rho_closing = 0 (white) and rho_action = 0.5 -- all three branches in every launch.  70 episodes / lanes: one full wave and a
 partial one thread per env, 18 waves at the (4, 16) group shape: the smallest at which a lane restarts while its neighbours
 go on."""
@@ -22,28 +23,12 @@ import torch
 import eval_stats_support as ES
 import monte_carlo_support as MS
 import noise_scoring_support as NS
-from noise_scoring_support import (CAMPAIGN, CAMPAIGN_SHAPES, EVAL_IDS, EVAL_SHAPES, NOISE_EPISODE, SIGMAS, WHITE, ZERO_SHAPES, fused, ran,
-                                   reference, same)
+from noise_scoring_support import (CAMPAIGN, CAMPAIGN_SHAPES, CORRELATED, EVAL_IDS, EVAL_SHAPES, NOISE_EPISODE, RHO, SIGMAS, WHITE, fused,
+                                   ran, reference, same)
 
 pytestmark = pytest.mark.gpu
 DEV = ES.DEV
 F32 = torch.float32
-RHO = dict(rho_sep=0.9, rho_cpa=1.0, rho_closing=0.0, rho_action=0.5)
-
-
-def rho_of_slots(dist, N):
-    """[N + 1, 3]: the coefficient of every value of a lane's draw -- slot 0 the actuator's normal (and two zeros), slot n + 1
-    traffic n's three channels."""
-    return np.asarray([[dist.rho_action, 0.0, 0.0]] + [list(dist.rho)] * N, np.float32)
-
-
-def errors(g, dist, N):
-    """The host loop's series under `dist`: the errors the normals drive, scanned from the episode's first step
-    (game.steps == 1) on."""
-    return lambda normals: np.concatenate([normals[:1], g.records.correlated_errors(normals[1:], rho_of_slots(dist, N))])
-
-
-CORRELATED = NS.Flavour("correlated", lambda g: g.CorrelatedDisturbance.normalised(**SIGMAS, **RHO), errors)
 
 
 @pytest.fixture(scope="module")
@@ -61,7 +46,7 @@ def the_white_disturbance(g):
 
 
 # ---- 1: rho = 0 is the white noise ----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", ZERO_SHAPES, ids=EVAL_IDS[:4])
+@pytest.mark.parametrize("shape", EVAL_SHAPES, ids=EVAL_IDS)
 def test_zero_correlation_is_the_disturbed_evaluator(g, shape):
     N, group = shape
     assert g.policy.evaluate_policies_entry(F32, group, True, correlated=True) == \
@@ -74,7 +59,7 @@ def test_zero_correlation_is_the_disturbed_evaluator(g, shape):
     assert (white["outcome"] != 0).all()
 
 
-@pytest.mark.parametrize("shape", ZERO_SHAPES, ids=EVAL_IDS[:4])
+@pytest.mark.parametrize("shape", EVAL_SHAPES, ids=EVAL_IDS)
 def test_zero_correlation_is_the_disturbed_campaign(g, shape):
     s = MS.Shape(F32, True, shape[0], shape[1], 150)
     mc = MS.campaign(g, s, disturbance=g.CorrelatedDisturbance.normalised(**SIGMAS))
@@ -100,14 +85,28 @@ def test_correlated_evaluator_equals_the_host_loop(g, shape):
     NS.evaluator_equals_the_host_loop(g, CORRELATED, shape)
 
 
+@NS.SATURATING_EVAL
+def test_saturating_correlated_evaluator_equals_the_host_loop(g, shape):
+    NS.saturating_evaluator_equals_the_host_loop(g, NS.SATURATING_CORRELATED, shape)
+
+
 # ---- 3: the campaign against the evaluator ---------------------------------------------------------------------------------------------
-@CAMPAIGN
+@NS.CAMPAIGN_EVERY_SHAPE
 def test_correlated_campaign_equals_the_correlated_evaluator(g, s):
     ref = reference(g, CORRELATED, s)
     assert ref["outcome_count"].sum(1).tolist() == [MS.LANES * MS.EPISODES] * 3
     assert ref["outcome_count"][:, 0].tolist() == [0, 0, 0] and np.isfinite(ref["lane_worst_sep"]).all()
     same(g, ran(g, CORRELATED, s), ref)
     assert MS.mismatches(g, ran(g, CORRELATED, s), ran(g, WHITE, s))                       # (and it is not the white campaign)
+
+
+def test_saturating_correlated_campaign_equals_the_evaluator(g):
+    s, fl = NS.SATURATING_CAMPAIGN_SHAPE, NS.SATURATING_CORRELATED
+    ref = reference(g, fl, s)
+    assert ref["outcome_count"].sum(1).tolist() == [MS.LANES * MS.EPISODES] * 3
+    assert ref["outcome_count"][:, 0].tolist() == [0, 0, 0] and np.isfinite(ref["lane_worst_sep"]).all()
+    same(g, ran(g, fl, s), ref)
+    assert MS.mismatches(g, ran(g, fl, s), ran(g, NS.SATURATING, s))                       # (and it is not its white twin)
 
 
 @CAMPAIGN

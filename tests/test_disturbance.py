@@ -13,7 +13,9 @@ acas2d_disturbance_draw_f32; policy.Disturbance):
   6  refusals.
 
 The shapes, the host loop, the campaign's reference and the campaign properties are tests/noise_scoring_support.py's, shared
-with tests/test_correlated.py; WHITE is this file's flavour of them.
+with tests/test_correlated.py; WHITE is this file's flavour of them.  2, 3 and the campaign's equality with the evaluator run
+at all nine compiled work shapes; 3 and that equality also under SATURATING, where the clamps of disturbed() decide every
+step.
 
 70 episodes / lanes: one full wave and a partial one thread per env, 18 waves at the (4, 16) group shape."""
 import math
@@ -25,7 +27,7 @@ import torch
 import eval_stats_support as ES
 import monte_carlo_support as MS
 import noise_scoring_support as NS
-from noise_scoring_support import CAMPAIGN, CAMPAIGN_SHAPES, EVAL_IDS, EVAL_SHAPES, WHITE, ZERO_SHAPES, fused, ran, reference, same
+from noise_scoring_support import CAMPAIGN, CAMPAIGN_SHAPES, EVAL_IDS, EVAL_SHAPES, WHITE, fused, ran, reference, same
 
 pytestmark = pytest.mark.gpu
 DEV = ES.DEV
@@ -88,7 +90,7 @@ def test_draws_do_not_depend_on_how_they_are_asked_for(g):
 
 
 # ---- 2: zero is identity ------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("shape", ZERO_SHAPES, ids=EVAL_IDS[:4])
+@pytest.mark.parametrize("shape", EVAL_SHAPES, ids=EVAL_IDS)
 def test_zero_disturbance_is_the_stats_evaluator(g, shape):
     N, group = shape
     plain = fused(g, N, group)
@@ -99,7 +101,7 @@ def test_zero_disturbance_is_the_stats_evaluator(g, shape):
     assert (plain["outcome"] != 0).all()
 
 
-@pytest.mark.parametrize("shape", ZERO_SHAPES, ids=EVAL_IDS[:4])
+@pytest.mark.parametrize("shape", EVAL_SHAPES, ids=EVAL_IDS)
 def test_zero_disturbance_is_the_undisturbed_campaign(g, shape):
     s = MS.Shape(F32, True, shape[0], shape[1], 150)
     plain = MS.campaign(g, s).run(MS.EPISODES).accumulators()
@@ -122,13 +124,26 @@ def test_disturbed_evaluator_equals_the_host_loop(g, shape):
     NS.evaluator_equals_the_host_loop(g, WHITE, shape)
 
 
+@NS.SATURATING_EVAL
+def test_saturating_evaluator_equals_the_host_loop(g, shape):
+    NS.saturating_evaluator_equals_the_host_loop(g, NS.SATURATING, shape)
+
+
 # ---- 4: the campaign against the evaluator ---------------------------------------------------------------------------------------------
-@CAMPAIGN
+@NS.CAMPAIGN_EVERY_SHAPE
 def test_disturbed_campaign_equals_the_disturbed_evaluator(g, s):
     ref = reference(g, WHITE, s)
     assert ref["outcome_count"].sum(1).tolist() == [MS.LANES * MS.EPISODES] * 3
     same(g, ran(g, WHITE, s), ref)
     assert MS.mismatches(g, ran(g, WHITE, s), MS.reference(g, s))           # (and it is not the undisturbed campaign)
+
+
+def test_saturating_campaign_equals_the_saturating_evaluator(g):
+    s = NS.SATURATING_CAMPAIGN_SHAPE
+    ref = reference(g, NS.SATURATING, s)
+    assert ref["outcome_count"].sum(1).tolist() == [MS.LANES * MS.EPISODES] * 3
+    same(g, ran(g, NS.SATURATING, s), ref)
+    assert MS.mismatches(g, ran(g, NS.SATURATING, s), ran(g, WHITE, s))     # (and it is not the campaign under the small sigmas)
 
 
 def test_the_campaign_reference_is_not_vacuous(g):

@@ -11,6 +11,7 @@ import monte_carlo_support as S
 
 pytestmark = pytest.mark.gpu
 SHAPES = pytest.mark.parametrize("s", S.SHAPES, ids=[S.shape_id(s) for s in S.SHAPES])
+EVERY_SHAPE = pytest.mark.parametrize("s", S.SHAPES + S.MORE_SHAPES, ids=[S.shape_id(s) for s in S.SHAPES + S.MORE_SHAPES])
 
 
 @pytest.fixture(scope="module")
@@ -37,10 +38,11 @@ def same(g, got, want):
     assert not bad, {k: (np.asarray(got[k]).ravel()[:6], np.asarray(want[k]).ravel()[:6]) for k in bad}
 
 
-@SHAPES
+@EVERY_SHAPE
 def test_equals_the_existing_entries_bit_for_bit(g, s):
     """reset_to_episode(c) + evaluate_policies_fused(safety=True) for c = 0, 1, 2, folded by records.monte_carlo_reduce():
-    the in-kernel redraw, the restart of the statistics and the folding, all at once."""
+    the in-kernel redraw, the restart of the statistics and the folding, all at once -- at every compiled float32 work shape
+    (S.MORE_SHAPES: the three the property tests below leave out)."""
     ref = S.reference(g, s)
     assert ref["outcome_count"].sum(1).tolist() == [S.LANES * S.EPISODES] * 3       # (the reference itself: test below)
     same(g, ran(g, s), ref)
@@ -51,7 +53,7 @@ def test_the_reference_is_not_vacuous(g):
     nothing unfinished; across the parametrisation: every outcome, losses of separation, a histogram that spreads."""
     seen = np.zeros(4, np.int64)
     los = bins = 0
-    for s in S.SHAPES:
+    for s in S.SHAPES + S.MORE_SHAPES:
         ref = S.reference(g, s)
         assert ref["outcome_count"].sum(1).tolist() == ref["sep_hist"].sum(1).tolist() == [S.LANES * S.EPISODES] * 3, S.shape_id(s)
         assert ref["outcome_count"][:, 0].tolist() == [0, 0, 0]
