@@ -425,12 +425,16 @@ def disturbance_words(seed, lane, episode, step, slot):
 
 
 def disturbance_normals(words):
-    """The three standard normals (z_sep, z_cpa, z_closing) of blocks [..., 4] in float64: u_i = ((w_i >> 8) + 0.5) / 2^24 (the
+    """The three standard normals (z_sep, z_cpa, z_closing) of blocks [..., 4] in float64: u_i = fl32((w_i >> 8) + 0.5) / 2^24 (the
     float32 uniforms of the kernels, exact in float64), r(u) = sqrt(-2 ln u), z_sep = r(u1) cos(2 pi u2), z_cpa = r(u1) sin(2 pi
     u2), z_closing = r(u3) cos(2 pi u4).  The actuator slot reads z_sep.  The kernels evaluate the same formulas with the
-    hardware's approximate float32 log, sqrt, sin and cos: acas2d_disturbance_draw_f32 gives their values."""
+    hardware's approximate float32 log, sqrt, sin and cos: acas2d_disturbance_draw_f32 gives their values.
+    fl32: the kernels form k + 0.5 in float32 (u01f()), which holds it only for k < 2^23; from there on it is a tie and goes
+    to the even neighbour -- k for an even k, k + 1 for an odd one.  Nothing of that shows but next to u = 1, where ln u is all
+    rounding: k = 2^24 - 1 gives u = 1 and the normal 0 (not 2.4e-4 times the cosine), k = 2^24 - 2 and 2^24 - 3 give
+    r = 4.9e-4 (not 4.2e-4 and 5.5e-4)."""
     w = np.asarray(words, np.uint32)
-    u = ((w >> np.uint32(8)).astype(np.float64) + 0.5) / 16777216.0
+    u = ((w >> np.uint32(8)).astype(np.float32) + np.float32(0.5)).astype(np.float64) / 16777216.0
     r1, r3 = np.sqrt(-2.0 * np.log(u[..., 0])), np.sqrt(-2.0 * np.log(u[..., 2]))
     a2, a4 = 2.0 * np.pi * u[..., 1], 2.0 * np.pi * u[..., 3]
     return np.stack([r1 * np.cos(a2), r1 * np.sin(a2), r3 * np.cos(a4)], axis=-1)

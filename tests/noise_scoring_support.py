@@ -60,12 +60,32 @@ SATURATING_CORRELATED = Flavour("saturating-correlated", lambda g: g.CorrelatedD
                                 correlated_series)
 
 
+def reseeded(dist, seed):
+    """`dist` under another noise seed."""
+    return type(dist).from_dict(dict(dist.to_dict(), seed=seed))
+
+
+def at_wide_seed(fl):
+    """The flavour under monte_carlo_support.WIDE_SEED (both halves of the noise key non-zero and distinct)."""
+    return Flavour(fl.name + "@wide-seed", lambda g: reseeded(fl.disturbance(g), MS.WIDE_SEED), fl.errors)
+
+
+# the noisy evaluators' wide keys: the noise lane crosses 2^32 at episode 37 of the 70 (monte_carlo_support.WIDE_LANE_OFFSET),
+# the seed is WIDE_SEED and the counter the last one
+WIDE_NOISE_EPISODE = 2 ** 32 - 1
+WIDE_EVAL = dict(env_offset=MS.WIDE_LANE_OFFSET, seed=MS.WIDE_SEED, noise_episode=WIDE_NOISE_EPISODE)
+WIDE_EVAL_SHAPES = ((1, False), (8, False), (16, True))
+WIDE_CAMPAIGN_SHAPES = [MS.Shape(F32, True, n, grp, 150) for n, grp in ((1, False), (16, True))]
+
+
 def shape_id(s):
     return "N%d%s" % (s[0], "-group" if s[1] else "")
 
 
 EVAL_IDS = [shape_id(s) for s in EVAL_SHAPES]
 CAMPAIGN = pytest.mark.parametrize("s", CAMPAIGN_SHAPES, ids=[MS.shape_id(s) for s in CAMPAIGN_SHAPES])
+WIDE_EVAL_PARAMS = pytest.mark.parametrize("shape", WIDE_EVAL_SHAPES, ids=[shape_id(s) for s in WIDE_EVAL_SHAPES])
+WIDE_CAMPAIGN = pytest.mark.parametrize("s", WIDE_CAMPAIGN_SHAPES, ids=[MS.shape_id(s) for s in WIDE_CAMPAIGN_SHAPES])
 CAMPAIGN_EVERY_SHAPE = pytest.mark.parametrize("s", CAMPAIGN_SHAPES + CAMPAIGN_MORE,
                                                ids=[MS.shape_id(s) for s in CAMPAIGN_SHAPES + CAMPAIGN_MORE])
 SATURATING_EVAL = pytest.mark.parametrize("shape", SATURATING_EVAL_SHAPES, ids=[shape_id(s) for s in SATURATING_EVAL_SHAPES])
@@ -84,8 +104,9 @@ def same(g, got, want):
 
 
 # ---- the evaluator against a host loop -------------------------------------------------------------------------------------------------
-def host_loop(g, cfg, eps, policy, dist, noise_episode, group, errors=None, seen=None):
+def host_loop(g, cfg, eps, policy, dist, noise_episode, group, errors=None, seen=None, env_offset=0):
     """One policy's reference rows [E] by the per-step path: (outcome, steps, total_reward, stats dict, summary dict).
+    Episode i reads the noise of lane env_offset + i.
     `errors`: from the drawn normals [step, lane, slot, 3] to the series the loop indexes; None: the normals themselves,
     the white model.  `seen`: a list that takes, per step, (the rows the actor read, the actions flown) of the envs still
     playing."""
@@ -93,7 +114,7 @@ def host_loop(g, cfg, eps, policy, dist, noise_episode, group, errors=None, seen
     n_steps = cfg.max_steps + 1
     zero = np.zeros(E, np.int32)
     # the normals of every step an episode can reach, from the draw entry: [step, lane, slot, 3] -- and the errors they drive
-    normals = g.policy.disturbance_draw(dist.seed, 0, E, noise_episode, 0, cfg.max_steps + 2, N + 1, device=DEV)
+    normals = g.policy.disturbance_draw(dist.seed, env_offset, E, noise_episode, 0, cfg.max_steps + 2, N + 1, device=DEV)
     series = normals if errors is None else errors(normals)
     r = g.ACAS2DVecEnv(E, N, device=DEV, dtype=F32, auto_reset=False, record_trace=True, config=cfg)
     r.set_state(eps.own, eps.trf, eps.goal, zero, observe=True)
@@ -144,16 +165,23 @@ def host_loop(g, cfg, eps, policy, dist, noise_episode, group, errors=None, seen
 _LOOP, _RAN, _SEEN = {}, {}, {}
 
 
-def loop_reference(g, fl, N, group):
-    """host_loop()'s rows of eval_stats_support's two policies under the flavour's disturbance at NOISE_EPISODE."""
-    if (fl.name, N, group) not in _LOOP:
+def disturbance_of(g, fl, seed=None):
+    """The flavour's disturbance, under its own seed or `seed`."""
+    return fl.disturbance(g) if seed is None else reseeded(fl.disturbance(g), seed)
+
+
+def loop_reference(g, fl, N, group, env_offset=0, seed=None, noise_episode=NOISE_EPISODE):
+    """host_loop()'s rows of eval_stats_support's two policies under the flavour's disturbance at NOISE_EPISODE -- or at the
+    keys given: the first noise lane, the noise seed, the counter."""
+    key = (fl.name, N, group) + (() if (env_offset, seed, noise_episode) == (0, None, NOISE_EPISODE) else (env_offset, seed, noise_episode))
+    if key not in _LOOP:
         cfg = ES.config(g, N)
         eps = ES.episodes(cfg)
-        dist = fl.disturbance(g)
+        dist = disturbance_of(g, fl, seed)
         errors = fl.errors and fl.errors(g, dist, N)
-        seen = _SEEN[fl.name, N, group] = []
-        _LOOP[fl.name, N, group] = [host_loop(g, cfg, eps, pol, dist, NOISE_EPISODE, group, errors, seen) for pol in ES.two_policies(g, N)]
-    return _LOOP[fl.name, N, group]
+        seen = _SEEN[key] = []
+        _LOOP[key] = [host_loop(g, cfg, eps, pol, dist, noise_episode, group, errors, seen, env_offset) for pol in ES.two_policies(g, N)]
+    return _LOOP[key]
 
 
 def loop_seen(g, fl, N, group):
@@ -176,19 +204,34 @@ def saturating_evaluator_equals_the_host_loop(g, fl, shape):
     evaluator_equals_the_host_loop(g, fl, shape, counter_shows_in="mean_abs_deviation")
 
 
-def evaluator_equals_the_host_loop(g, fl, shape, counter_shows_in="max_abs_a_lat"):
+def evaluator_equals_the_host_loop(g, fl, shape, counter_shows_in="max_abs_a_lat", env_offset=0, seed=None, noise_episode=NOISE_EPISODE):
     """The fused evaluator's rows against loop_reference()'s, bit for bit; another noise counter gives another
     `counter_shows_in`."""
     N, group = shape
-    got = fused(g, N, group, disturbance=fl.disturbance(g), noise_episode=NOISE_EPISODE)
-    for k, (outcome, steps, ret, stats, summary) in enumerate(loop_reference(g, fl, N, group)):
+    dist = disturbance_of(g, fl, seed)
+    got = fused(g, N, group, disturbance=dist, noise_episode=noise_episode, env_offset=env_offset)
+    for k, (outcome, steps, ret, stats, summary) in enumerate(loop_reference(g, fl, N, group, env_offset, seed, noise_episode)):
         assert np.array_equal(got["outcome"][k], outcome) and np.array_equal(got["steps"][k], steps), k
         assert ES.bits_equal(got["total_reward"][k].astype(np.float32), ret), k
         for key in g.records.SAFETY_KEYS:
             assert ES.bits_equal(got[key][k], summary[key]), (k, key)
     # the counter is part of the noise
-    other = fused(g, N, group, disturbance=fl.disturbance(g), noise_episode=NOISE_EPISODE + 1)
+    other = fused(g, N, group, disturbance=dist, noise_episode=(noise_episode + 1) % 2 ** 32, env_offset=env_offset)
     assert not ES.bits_equal(other[counter_shows_in], got[counter_shows_in])
+
+
+def evaluator_at_wide_keys(g, fl, shape):
+    """The evaluator against the host loop at WIDE_EVAL.  Teeth first, on the reference alone: against the host loop at the
+    default keys a float statistic moves in at least half of the episodes, on both sides of the crossing."""
+    N, group = shape
+    floats = [k for k in g.records.SAFETY_KEYS if k not in ("min_separation_step", "los_steps")]
+    for k, (wide, plain) in enumerate(zip(loop_reference(g, fl, N, group, **WIDE_EVAL), loop_reference(g, fl, N, group))):
+        assert (wide[0] != 0).all(), "an episode of the reference did not finish"
+        moved = np.zeros(ES.E, bool)
+        for key in floats:
+            moved |= ES.bits(wide[4][key]) != ES.bits(plain[4][key])
+        assert 2 * int(moved.sum()) >= ES.E and moved[:MS.WIDE_CROSSING].any() and moved[MS.WIDE_CROSSING:].any(), (k, int(moved.sum()))
+    evaluator_equals_the_host_loop(g, fl, shape, **WIDE_EVAL)
 
 
 # ---- the campaign against the evaluator ------------------------------------------------------------------------------------------------
@@ -198,10 +241,27 @@ def per_counter(g, fl, s):
 
 
 def reference(g, fl, s, rows=None):
-    res = per_counter(g, fl, s)
-    if rows is not None:
-        res = [{k: v[list(rows)] for k, v in r.items() if np.ndim(v) == 2} for r in res]
-    return g.records.monte_carlo_reduce(res, MS.N_BINS, MS.inv_bin_width(g, s), np.float32)
+    return MS.reference(g, s, rows=rows, fl=fl)
+
+
+def campaign_at_wide_keys(g, fl, s):
+    """monte_carlo_support.campaign_at_wide_keys() under the flavour at WIDE_SEED: the campaign's seed is the noise seed too.
+    The campaign and its reference, the noisy evaluator, form the noise lane with the same code, so the reference is anchored
+    first: policy a's row of the last counter, 2^32 - 1, against host_loop() on the encounters drawn for it, whose normals
+    come from the draw entry at the 64-bit lanes."""
+    wide, last = at_wide_seed(fl), 2 ** 32 - 1
+    cfg, dist = MS.config(g, s), at_wide_seed(fl).disturbance(g)
+    v = g.ACAS2DVecEnv(MS.LANES, s.N, device=DEV, dtype=F32, seed=MS.WIDE_SEED, env_offset=MS.WIDE_LANE_OFFSET, config=cfg)
+    v.reset_to_episode(last)
+    assert MS.LANES == ES.E                                       # host_loop() plays eval_stats_support's number of episodes
+    outcome, steps, ret, _, summary = host_loop(g, cfg, ES.Episodes(*g.policy.read_state(v), None), MS.policies(g, s)[0], dist, last,
+                                                s.group, wide.errors and wide.errors(g, dist, s.N), env_offset=MS.WIDE_LANE_OFFSET)
+    res = MS.per_counter(g, s, wide, **MS.WIDE)[-1]
+    assert (outcome != 0).all() and np.array_equal(res["outcome"][0], outcome) and np.array_equal(res["steps"][0], steps)
+    assert ES.bits_equal(res["total_reward"][0].astype(np.float32), ret)
+    for key in g.records.SAFETY_KEYS:
+        assert ES.bits_equal(res[key][0], summary[key]), key
+    MS.campaign_at_wide_keys(g, s, fl=wide, default=fl)
 
 
 def campaign(g, fl, s, **kw):

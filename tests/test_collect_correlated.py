@@ -52,12 +52,12 @@ def corr(g, **kw):
 _RUNS = {}
 
 
-def csolo(g, N, group, dist, E=E1, offset=0, seed=1, key=NOISE_SEED, cuts=(T,)):
+def csolo(g, N, group, dist, E=E1, offset=0, seed=1, key=NOISE_SEED, cuts=(T,), episodes=False):
     """collect() of `cuts` steps in a row on a fresh env under a fresh one-member CorrelatedDisturbanceSet of `dist`: one
     host dict per piece (test_collect_disturbed.host's, plus "held": the state after the piece).  Cached, left alone."""
-    name = (N, group, dist, E, offset, seed, key, cuts)
+    name = (N, group, dist, E, offset, seed, key, cuts) + ((episodes,) if episodes else ())
     if name not in _RUNS:
-        env, pol = CD.make_env(g, E, N, offset), CD.policy(g, N, seed)
+        env, pol = CD.make_env(g, E, N, offset, episodes), CD.policy(g, N, seed)
         ds = g.CorrelatedDisturbanceSet(dist, 1)
         outs, at = [], NOISE_STEP
         for n in cuts:
@@ -141,10 +141,10 @@ class Errors:
 CD_NORMALS = CD.normals_for
 
 
-def correlated_host_loop(g, monkeypatch, N, group, dist):
+def correlated_host_loop(g, monkeypatch, N, group, dist, **keys):
     err = Errors(g, dist, E1, N, T)
     monkeypatch.setattr(CD, "normals_for", err)
-    ref = CD.host_loop(g, N, group, dist)
+    ref = CD.host_loop(g, N, group, dist, **keys)
     monkeypatch.undo()
     assert err.calls == T + 1
     ref["held"] = err.held()
@@ -176,6 +176,34 @@ def test_correlated_collector_equals_the_host_loop(g, monkeypatch, shape):
         assert ES.bits_equal(got[k], ref[k]), k
     # ... which the white collector does not give
     assert not ES.bits_equal(got["obs_read"], CD.solo(g, N, group, "noisy")["obs_read"])
+
+
+@pytest.mark.parametrize("shape", CD.WIDE_SHAPES, ids=[CD.shape_id(s) for s in CD.WIDE_SHAPES])
+def test_correlated_collector_equals_the_host_loop_at_wide_keys(g, monkeypatch, shape):
+    """test_collect_disturbed's wide keys -- the global env index crossing 2^32 at env 37, the noise seed helpers.WIDE_SEED,
+    the even envs' counters preset to 2^32 - 2 -- in one launch of 16 steps and in two of 8: at the cut the preset envs play
+    the episode 2^32 - 1, so the held state crosses a launch inside the episode after which the counter wraps."""
+    N, group = shape
+    dist = corr(g, seed=CD.MS.WIDE_SEED)
+    ref, err = correlated_host_loop(g, monkeypatch, N, group, dist, **CD.WIDE)
+    CD.preset_counters_wrapped(ref, E1)
+    assert ES.bits(ref["held"]).any(1).tolist() == held_rows_of(N)
+    assert ES.bits(ref["held"])[:, :CD.MS.WIDE_CROSSING].any() and ES.bits(ref["held"])[:, CD.MS.WIDE_CROSSING:].any()
+    got = csolo(g, N, group, dist, **CD.WIDE)
+    for k in ALL + ("held",):
+        assert ES.bits_equal(got[k], ref[k]), k
+    h = T // 2
+    first, second = csolo(g, N, group, dist, cuts=(h, h), **CD.WIDE)
+    pre = CD.H.wide_preset(E1)
+    top = pre & (first["state.episode"].view(np.uint32) == 2 ** 32 - 1) & (first["state.steps"] > 1)
+    assert top.any()                                                      # mid-episode at the last counter, with state to carry
+    assert ES.bits(first["held"])[:, top].any(0).all()
+    for k in CD.KEYS[1:]:
+        assert ES.bits_equal(np.concatenate([first[k], second[k]]), ref[k]), k
+    assert ES.bits_equal(first["obs"], ref["obs"][:h + 1]) and ES.bits_equal(second["obs"], ref["obs"][h:])
+    assert ES.bits_equal(first["obs_read"], ref["obs_read"][:h + 1]) and ES.bits_equal(second["obs_read"], ref["obs_read"][h:])
+    for k in tuple("state." + n for n in CD.STATE) + ("held",):
+        assert ES.bits_equal(second[k], ref[k]), k
 
 
 @pytest.mark.parametrize("shape", CD.SATURATING_SHAPES, ids=[CD.shape_id(s) for s in CD.SATURATING_SHAPES])

@@ -25,6 +25,8 @@ import torch
 
 import edge_observations as EO
 import eval_stats_support as ES
+import helpers as H
+import monte_carlo_support as MS
 
 pytestmark = pytest.mark.gpu
 DEV = ES.DEV
@@ -70,10 +72,15 @@ def injected_id(case):
     return "%s-%s" % (shape_id(case[0]), case[1])
 
 
-def make_env(g, E, N, offset=0):
+def make_env(g, E, N, offset=0, episodes=False):
+    """episodes: the even envs' episode counters start at helpers.WIDE_EPISODE = 2^32 - 2, so that their second reset wraps
+    the counter to 0 inside a launch."""
     cfg = g.ACAS2DConfig(n_traffic=N, max_steps=MAX_STEPS)
     env = g.ACAS2DVecEnv(E, N, device=DEV, dtype=F32, seed=13, env_offset=offset, config=cfg)
-    env.reset()
+    if episodes:
+        env.reset_to_episode(np.where(H.wide_preset(E), H.WIDE_EPISODE, 0))
+    else:
+        env.reset()
     return env
 
 
@@ -108,11 +115,11 @@ def same(a, b, keys=None, cols=slice(None)):
 _RUNS = {}
 
 
-def solo(g, N, group, dist="noisy", E=E1, offset=0, seed=1, key=NOISE_SEED, cuts=(T,)):
+def solo(g, N, group, dist="noisy", E=E1, offset=0, seed=1, key=NOISE_SEED, cuts=(T,), episodes=False):
     """collect() of `cuts` steps in a row on a fresh env (cached: a reference is computed once and left alone)."""
-    name = (N, group, dist, E, offset, seed, key, cuts)
+    name = (N, group, dist, E, offset, seed, key, cuts) + ((episodes,) if episodes else ())
     if name not in _RUNS:
-        env, pol = make_env(g, E, N, offset), policy(g, N, seed)
+        env, pol = make_env(g, E, N, offset, episodes), policy(g, N, seed)
         d = ({"noisy": noisy(g), "zero": g.Disturbance(seed=99), "saturating": saturating(g), None: None}[dist]
              if isinstance(dist, (str, type(None))) else dist)
         outs, at = [], NOISE_STEP
@@ -163,8 +170,8 @@ def normals_for(g, seed, offset, episode, steps, N):
     return z
 
 
-def host_loop(g, N, group, dist, E=E1, offset=0):
-    r, scratch, pol = make_env(g, E, N, offset), make_env(g, E, N, offset), policy(g, N)
+def host_loop(g, N, group, dist, E=E1, offset=0, episodes=False):
+    r, scratch, pol = make_env(g, E, N, offset, episodes), make_env(g, E, N, offset), policy(g, N)
     rows = {k: [] for k in ("obs_read", "actions", "values", "logp", "flown", "reward", "done_u8", "outcome", "obs",
                             "episode_return", "episode_steps")}
     rows["obs"].append(r.outputs["obs"].cpu().numpy().copy())
@@ -212,6 +219,33 @@ def test_disturbed_collector_equals_the_host_loop(g, shape):
     # the seed is part of the noise
     other = solo(g, N, group, noisy(g, seed=8))
     assert not ES.bits_equal(other["obs_read"], got["obs_read"]) and not ES.bits_equal(other["reward"], got["reward"])
+
+
+# the collectors' wide keys: the noise lane -- here the global env index -- crosses 2^32 at env 37 of the 70
+# (monte_carlo_support.WIDE_LANE_OFFSET), the noise seed is helpers.WIDE_SEED, and the even envs' counters are preset
+WIDE_SHAPES = ((1, False), (16, True))
+WIDE = dict(offset=MS.WIDE_LANE_OFFSET, episodes=True)
+
+
+def preset_counters_wrapped(ref, E):
+    """On the reference alone: every env was reset at least three times inside the launch, so every preset counter went
+    through 2^32 - 1 to 0 -- the counters end at the number of resets, the preset ones two below it."""
+    pre, dones = H.wide_preset(E), ref["done_u8"].astype(np.int64).sum(0)
+    end = ref["state.episode"].view(np.uint32).astype(np.int64)
+    assert ref["done_u8"].shape == (T, E) and (dones >= 3).all()
+    assert np.array_equal(end[pre], dones[pre] - 2) and np.array_equal(end[~pre], dones[~pre])
+
+
+@pytest.mark.parametrize("shape", WIDE_SHAPES, ids=[shape_id(s) for s in WIDE_SHAPES])
+def test_disturbed_collector_equals_the_host_loop_at_wide_keys(g, shape):
+    N, group = shape
+    dist = noisy(g, seed=MS.WIDE_SEED)
+    ref = host_loop(g, N, group, dist, **WIDE)
+    preset_counters_wrapped(ref, E1)
+    assert (ES.bits(ref["obs_read"]) != ES.bits(ref["obs"])).any(-1).any(0).all()     # every env reads noise, on both sides of the crossing
+    got = solo(g, N, group, dist, **WIDE)
+    for k in ("obs_read",) + KEYS + tuple("state." + n for n in STATE):
+        assert ES.bits_equal(got[k], ref[k]), k
 
 
 @pytest.mark.parametrize("shape", SATURATING_SHAPES, ids=[shape_id(s) for s in SATURATING_SHAPES])

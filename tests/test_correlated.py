@@ -85,6 +85,12 @@ def test_correlated_evaluator_equals_the_host_loop(g, shape):
     NS.evaluator_equals_the_host_loop(g, CORRELATED, shape)
 
 
+@NS.WIDE_EVAL_PARAMS
+def test_correlated_evaluator_equals_the_host_loop_at_wide_keys(g, shape):
+    """The noise lane crossing 2^32 at episode 37 of the 70, the noise seed helpers.WIDE_SEED, the counter 2^32 - 1."""
+    NS.evaluator_at_wide_keys(g, CORRELATED, shape)
+
+
 @NS.SATURATING_EVAL
 def test_saturating_correlated_evaluator_equals_the_host_loop(g, shape):
     NS.saturating_evaluator_equals_the_host_loop(g, NS.SATURATING_CORRELATED, shape)
@@ -107,6 +113,12 @@ def test_saturating_correlated_campaign_equals_the_evaluator(g):
     assert ref["outcome_count"][:, 0].tolist() == [0, 0, 0] and np.isfinite(ref["lane_worst_sep"]).all()
     same(g, ran(g, fl, s), ref)
     assert MS.mismatches(g, ran(g, fl, s), ran(g, NS.SATURATING, s))                       # (and it is not its white twin)
+
+
+@NS.WIDE_CAMPAIGN
+def test_correlated_campaign_at_wide_keys(g, s):
+    """monte_carlo_support.WIDE with the noise seed WIDE_SEED too (tests/test_disturbance.py's, under the correlation)."""
+    NS.campaign_at_wide_keys(g, CORRELATED, s)
 
 
 @CAMPAIGN

@@ -25,6 +25,7 @@ import pytest
 import torch
 
 import eval_stats_support as ES
+import helpers as H
 import monte_carlo_support as MS
 import noise_scoring_support as NS
 from noise_scoring_support import CAMPAIGN, CAMPAIGN_SHAPES, EVAL_IDS, EVAL_SHAPES, WHITE, fused, ran, reference, same
@@ -39,6 +40,11 @@ F32 = torch.float32
 # products against float64 libm; the factor covers inputs the sample does not hold.
 DRAW_MEASURED = 1.01e-5          # 1.009757e-05, at a cosine near its zero (|z| 0.0028)
 DRAW_TOL = 5e-5
+# That figure was taken against uniforms (k + 0.5) / 2^24 in float64.  The kernels form k + 0.5 in float32, where from k = 2^23
+# on it is a tie that goes to the even neighbour; next to u = 1 the radius sqrt(-2 ln u) is all rounding, and k = 2^24 - 1
+# gives u = 1 and the normal 0.  The wider sample of the test below met such a block (seed 7, lane 2^32 + 2, episode 2^32 - 1,
+# step 45, slot 4: 0 against 1.95e-4), beyond the bound.  records.disturbance_normals() now rounds the uniform as the kernels
+# do; against it the largest difference over the sample is 6.95e-7.  The bound stays where it was.
 
 
 @pytest.fixture(scope="module")
@@ -53,20 +59,24 @@ def the_disturbance(g):
 
 # ---- 1: the draws -----------------------------------------------------------------------------------------------------------------
 def test_draws_against_the_specification(g):
-    worst = 0.0
-    for first_lane in (0, (1 << 32) - 3):
-        for episode in (0, 5):
-            got = g.policy.disturbance_draw(7, first_lane, 70, episode, 0, 121, 9, device=DEV)
-            assert got.shape == (121, 70, 9, 3) and got.dtype == np.float32
-            lanes = first_lane + np.arange(70, dtype=np.uint64)
-            words = g.records.disturbance_words(7, lanes[None, :, None], episode, np.arange(121)[:, None, None],
-                                                np.arange(9)[None, None, :])
-            want = g.records.disturbance_normals(words)
-            want[:, :, 0, 1:] = 0.0                                    # the actuator slot: its normal and two zeros
-            assert (got[:, :, 0, 1:] == 0.0).all()
-            worst = max(worst, float(np.abs(got.astype(np.float64) - want).max()))
+    """... at both first lanes (the second crosses 2^32 inside the block), and -- the root of everything the noisy kernels
+    are held to at wide keys -- also under a seed whose high word is not 0 and at the last episode counter."""
+    worst, blocks = 0.0, 0
+    for seed in (7, H.WIDE_SEED):
+        for first_lane in (0, (1 << 32) - 3):
+            for episode in (0, 5, (1 << 32) - 1):
+                got = g.policy.disturbance_draw(seed, first_lane, 70, episode, 0, 121, 9, device=DEV)
+                assert got.shape == (121, 70, 9, 3) and got.dtype == np.float32
+                lanes = first_lane + np.arange(70, dtype=np.uint64)
+                words = g.records.disturbance_words(seed, lanes[None, :, None], episode, np.arange(121)[:, None, None],
+                                                    np.arange(9)[None, None, :])
+                want = g.records.disturbance_normals(words)
+                want[:, :, 0, 1:] = 0.0                                # the actuator slot: its normal and two zeros
+                assert (got[:, :, 0, 1:] == 0.0).all()
+                worst = max(worst, float(np.abs(got.astype(np.float64) - want).max()))
+                blocks += 1
     print("\nacas2d_disturbance_draw_f32 against the float64 specification: largest absolute difference %.3e over %d normals "
-          "(bound %r)" % (worst, 4 * 121 * 70 * (8 * 3 + 1), DRAW_TOL))
+          "(bound %r)" % (worst, blocks * 121 * 70 * (8 * 3 + 1), DRAW_TOL))
     assert worst <= DRAW_TOL
 
 
@@ -124,6 +134,12 @@ def test_disturbed_evaluator_equals_the_host_loop(g, shape):
     NS.evaluator_equals_the_host_loop(g, WHITE, shape)
 
 
+@NS.WIDE_EVAL_PARAMS
+def test_disturbed_evaluator_equals_the_host_loop_at_wide_keys(g, shape):
+    """The noise lane crossing 2^32 at episode 37 of the 70, the noise seed helpers.WIDE_SEED, the counter 2^32 - 1."""
+    NS.evaluator_at_wide_keys(g, WHITE, shape)
+
+
 @NS.SATURATING_EVAL
 def test_saturating_evaluator_equals_the_host_loop(g, shape):
     NS.saturating_evaluator_equals_the_host_loop(g, NS.SATURATING, shape)
@@ -157,6 +173,13 @@ def test_the_campaign_reference_is_not_vacuous(g):
         if s.max_steps == 150:
             assert ref["outcome_count"][:, 3].sum() > 0, MS.shape_id(s)
     assert (seen[1:] > 0).all(), seen                                  # goals, collisions and timeouts
+
+
+@NS.WIDE_CAMPAIGN
+def test_disturbed_campaign_at_wide_keys(g, s):
+    """monte_carlo_support.WIDE with the noise seed WIDE_SEED too: the lane's OWN counter names its noise (the reference
+    plays counter c under noise_episode = c, up to 2^32 - 1), and the replay keywords of encounter() name the 64-bit lane."""
+    NS.campaign_at_wide_keys(g, WHITE, s)
 
 
 @CAMPAIGN

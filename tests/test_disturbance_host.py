@@ -80,13 +80,25 @@ def test_blocks_differ_from_the_resets_under_the_same_seed(g):
 
 
 def test_normals_from_words(g):
-    w = np.array([[0x80000000, 0x00000000, 0xFFFFFFFF, 0x40000000]], np.uint32)
-    u = [(0x800000 + 0.5) / 2 ** 24, 0.5 / 2 ** 24, (0xFFFFFF + 0.5) / 2 ** 24, (0x400000 + 0.5) / 2 ** 24]
-    r1, r3 = math.sqrt(-2.0 * math.log(u[0])), math.sqrt(-2.0 * math.log(u[2]))
-    want = [r1 * math.cos(2 * math.pi * u[1]), r1 * math.sin(2 * math.pi * u[1]), r3 * math.cos(2 * math.pi * u[3])]
+    """The uniforms are the kernels' float32 ones: k + 0.5 as it is below k = 2^23, and from there on -- a tie in float32 --
+    the even neighbour: k = 0x800000 stays, k = 0x800001 and 0xFFFFFD go up by one, 0xFFFFFE stays, and k = 0xFFFFFF gives
+    u = 1, whose normal is 0."""
+    w = np.array([[0x80000000, 0x00000000, 0xFFFFFFFF, 0x40000000], [0x80000100, 0x3FFFFF00, 0xFFFFFE00, 0x00000000],
+                  [0xFFFFFD00, 0x7FFFFF00, 0x7FFFFFFF, 0x80000000]], np.uint32)
+    us = [[0x800000 / 2 ** 24, 0.5 / 2 ** 24, 1.0, (0x400000 + 0.5) / 2 ** 24],
+          [0x800002 / 2 ** 24, (0x3FFFFF + 0.5) / 2 ** 24, 0xFFFFFE / 2 ** 24, 0.5 / 2 ** 24],
+          [0xFFFFFE / 2 ** 24, (0x7FFFFF + 0.5) / 2 ** 24, (0x7FFFFF + 0.5) / 2 ** 24, 0x800000 / 2 ** 24]]
     got = g.records.disturbance_normals(w)
-    assert got.shape == (1, 3) and got.dtype == np.float64
-    assert np.allclose(got[0], want, rtol=1e-14, atol=1e-300)
+    assert got.shape == (3, 3) and got.dtype == np.float64
+    for row, u in zip(got, us):
+        r1, r3 = math.sqrt(-2.0 * math.log(u[0])), math.sqrt(-2.0 * math.log(u[2]))
+        want = [r1 * math.cos(2 * math.pi * u[1]), r1 * math.sin(2 * math.pi * u[1]), r3 * math.cos(2 * math.pi * u[3])]
+        assert np.allclose(row, want, rtol=1e-14, atol=1e-300)
+    assert got[0, 2] == 0.0 and got[1, 2] == pytest.approx(2.0 ** -11, rel=1e-6)        # r(1 - 2^-23) = sqrt(2^-22 (1 + ...))
+    # ... and what float32 makes of k + 0.5, worked out here in integers: exact below 2^23, then ties to even
+    k = np.array([0, 1, 0x7FFFFF, 0x800000, 0x800001, 0xFFFFFC, 0xFFFFFD, 0xFFFFFE, 0xFFFFFF], np.uint32)
+    twice = np.where(k < 0x800000, 2 * k.astype(np.int64) + 1, 2 * (k.astype(np.int64) + (k & 1)))
+    assert ((k.astype(np.float32) + np.float32(0.5)).astype(np.float64) * 2 == twice).all()
     # a quarter of a million blocks: three standard normals, uncorrelated (5 standard errors)
     z = g.records.disturbance_normals(g.records.disturbance_words(3, np.arange(1 << 18), 0, 0, 1))
     n = z.shape[0]

@@ -1940,6 +1940,33 @@ def test_every_f64_shape_reset_masked_at_wide_keys_vs_oracle(g, O, monkeypatch, 
             assert (env.episode[pre] == 0).all()
 
 
+def test_reset_to_episode_at_the_campaign_wide_keys_vs_oracle(g, O, monkeypatch):
+    """The encounters the Monte Carlo tests draw at THEIR wide keys (tests/monte_carlo_support.py: helpers.WIDE_SEED, the lane
+    crossing 2^32 at local lane 37 of 70, counters 2^32 - 3 .. 2^32 - 1), by the route of the test above at the float64
+    reference formulation with one aircraft: reset_to_episode(c) bit for bit against the oracle's draw of counter c, first
+    observations 1e-9.  The campaign's reference and the campaign share the GPU reset; this holds what both drew to the CPU."""
+    import monte_carlo_support as MS
+    shape = next(s for s in _F64_EXACT if s.n_traffic == 1)
+    E, N = MS.LANES, shape.n_traffic
+    _use_shape(g, monkeypatch, shape, E)
+    v = _shape_env(g, shape, E, seed=MS.WIDE_SEED, env_offset=MS.WIDE_LANE_OFFSET, config=dict(max_steps=150))
+    ref = O.OracleEnvs(E, N, seed=MS.WIDE_SEED, env_offset=MS.WIDE_LANE_OFFSET, auto_reset=True, config=_oracle_config_from(O, v.config))
+    env = _engine(v)
+    ref.reset()
+    every = np.ones(E, np.uint8)
+    drawn = []
+    for c in range(MS.WIDE_FIRST_EPISODE, MS.WIDE_FIRST_EPISODE + MS.EPISODES):
+        obs = env._np(v.reset_to_episode(c))
+        ref.episode[:] = np.uint32(c)
+        ref.reset_philox(every)
+        for name in _STATE:
+            assert np.array_equal(getattr(env, name), getattr(ref, name)), (c, name)
+        assert np.array_equal(env.episode, ref.episode) and (env.episode == c).all(), c
+        np.testing.assert_allclose(obs, ref.observe(), rtol=0, atol=1e-9)
+        drawn.append(env.trf_psi.copy())
+    assert c == 2 ** 32 - 1 and not np.array_equal(drawn[0], drawn[1]) and not np.array_equal(drawn[1], drawn[2])
+
+
 @pytest.mark.parametrize("key", tuple(H.WIDE_OFFSET))
 @pytest.mark.parametrize("shape", _F32_SHAPES, ids=_ids(_F32_SHAPES))
 def test_every_f32_shape_at_wide_keys_vs_f64_oracle(g, O, monkeypatch, shape, key):

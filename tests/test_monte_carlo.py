@@ -2,7 +2,9 @@
 existing entries folded on the host (tests/monte_carlo_support.py) -- integers exactly, the per-lane arrays bit for bit --
 and the properties a campaign is used for: chaining, resuming, common random numbers, reproducibility, regenerating an
 encounter.  70 lanes x 3 episodes, K = 3 (two policies and the all-zero one), 16 bins, at every shape family and under
-two configs."""
+two configs.  Further down: the campaign at wide keys (a 64-bit seed, the lane crossing 2^32 inside a wave, counters up to
+2^32 - 1), the histogram rule on a rounding edge, with one bin, past the last edge and at 4 096 bins, and 1, 64 and 129
+lanes."""
 import numpy as np
 import pytest
 import torch
@@ -172,6 +174,125 @@ def test_encounter_closes_the_loop(g, s):
         assert S.bits_equal(res["min_separation"][k, :1], np.asarray([sep], S.npdt(s)))
     three = mc.worst(3)
     assert [len(t) for t in three] == [3, 3, 3] and all(t[0][2] <= t[1][2] <= t[2][2] for t in three)
+
+
+# ---- wide keys ---------------------------------------------------------------------------------------------------------------------------
+WIDE_SHAPES = [S.Shape(S.F32, True, 1, False, 150), S.Shape(S.F32, True, 8, False, 150), S.Shape(S.F32, True, 16, True, 150),
+               S.Shape(S.F64, False, 1, False, 150)]
+
+
+@pytest.mark.parametrize("s", WIDE_SHAPES, ids=[S.shape_id(s) for s in WIDE_SHAPES])
+def test_campaign_at_wide_keys(g, s):
+    """monte_carlo_support.WIDE: the seed's halves non-zero and distinct, the lane crossing 2^32 at local lane 37, the
+    launch's last counter 2^32 - 1 -- every accumulator against the reference at those keys, the counters in
+    lane_worst_episode, chaining, the closest encounters and the two lanes at the crossing regenerated and replayed, and
+    the refusal of counter 2^32 (monte_carlo_support.campaign_at_wide_keys)."""
+    S.campaign_at_wide_keys(g, s)
+
+
+# ---- the histogram rule and the lane count -----------------------------------------------------------------------------------------------
+HIST_SHAPES = [S.Shape(S.F32, True, 1, False, 150), S.Shape(S.F32, True, 16, True, 150), S.Shape(S.F64, False, 1, False, 150)]
+HIST = pytest.mark.parametrize("s", HIST_SHAPES, ids=[S.shape_id(s) for s in HIST_SHAPES])
+
+
+def histogram(g, s, n_bins, hist_max=None):
+    """(the campaign's accumulators, the reference's) under the histogram (n_bins, hist_max): the cached per-counter results
+    folded with the id's own bin rule."""
+    kw = {} if hist_max is None else {"hist_max": hist_max}
+    got = S.campaign(g, s, n_bins=n_bins, **kw).run(S.EPISODES).accumulators()
+    assert got["sep_hist"].shape == (3, n_bins)
+    return got, S.reference(g, s, n_bins=n_bins, hist_max=hist_max)
+
+
+def separations(g, s):
+    """[EPISODES, K, LANES]: the reference's minimum separations."""
+    return np.stack([r["min_separation"] for r in S.per_counter(g, s)[:S.EPISODES]])
+
+
+@HIST
+def test_histogram_on_a_rounding_edge(g, s):
+    """16 bins of a width at which the median separation's product with the inverse width is, rounded to the kernel's
+    format, exactly a bin edge while the exact product lies below it (monte_carlo_support.edge_hist_max): a kernel that
+    formed the product in another precision, or divided by the width, bins that episode one lower."""
+    dt = S.npdt(s)
+    m, hist_max = S.edge_separation(g, s, 16)
+    inv = S.inv_bin_width(g, s, 16, hist_max)
+    sep = separations(g, s)
+    assert np.isfinite(sep).all() and (sep[:, 0] == m).any()
+    moved = int((g.records.separation_bin(sep, 16, inv, dt) != S.exact_bins(sep, 16, inv, dt)).sum())
+    print("\n%s: separation %r, hist_max %r, %d of %d episodes change their bin with the precision of the product"
+          % (S.shape_id(s), float(m), hist_max, moved, sep.size))
+    assert moved >= 1
+    got, ref = histogram(g, s, 16, hist_max)
+    same(g, got, ref)
+
+
+@HIST
+def test_histogram_of_one_bin(g, s):
+    got, ref = histogram(g, s, 1)
+    assert got["sep_hist"][:, 0].tolist() == [S.LANES * S.EPISODES] * 3
+    same(g, got, ref)
+
+
+@HIST
+def test_histogram_past_the_last_edge(g, s):
+    """hist_max = safe_distance / 64: most episodes lie beyond it and take the last bin through `q >= n_bins`;
+    hist_max = 1e-30: every product is >= 2^31 (float32: some 1e33; none overflows to inf), so every episode takes it
+    through the branch that never casts.  A non-finite minimum separation cannot be produced by a drawn campaign -- every
+    episode has a step row with a finite d_sep -- so the NaN / inf side of that branch stays held on the CPU alone
+    (tests/test_monte_carlo_host.py)."""
+    dt = S.npdt(s)
+    sep = separations(g, s)
+    assert np.isfinite(sep).all() and (sep > 0).all()
+    near = S.config(g, s).safe_distance / 64.0
+    got, ref = histogram(g, s, S.N_BINS, near)
+    assert (2 * ref["sep_hist"][:, -1] > S.LANES * S.EPISODES).all()
+    same(g, got, ref)
+    got, ref = histogram(g, s, S.N_BINS, 1e-30)
+    with np.errstate(over="ignore"):
+        scaled = sep.astype(dt) * dt(S.inv_bin_width(g, s, S.N_BINS, 1e-30))
+    assert (scaled >= dt(2147483648.0)).all()
+    assert ref["sep_hist"][:, -1].tolist() == [S.LANES * S.EPISODES] * 3
+    same(g, got, ref)
+
+
+@HIST
+def test_fine_histogram(g, s):
+    """4096 bins: at least 32 occupied bins per policy row, rows that differ, and all K x 4096 counters -- the row
+    addressing k * n_bins + b.  At the default hist_max (4 x the safe distance) that holds with 16 aircraft.  A single
+    aircraft never comes that close in these 210 encounters -- asserted: every separation lies past the default hist_max
+    and the whole fine histogram is its last bin, which is compared too -- so those shapes are held to the spread under
+    hist_max = d_sep_max, the bound of the observation's separation entry, which no separation exceeds."""
+    got, ref = histogram(g, s, 4096)
+    same(g, got, ref)
+    hist_max = None
+    if s.N == 1:
+        sep, hist_max = separations(g, s), float(S.config(g, s).to_c().d_sep_max)
+        assert ref["sep_hist"][:, -1].tolist() == [S.LANES * S.EPISODES] * 3 and (sep < hist_max).all()
+        got, ref = histogram(g, s, 4096, hist_max)
+    occupied = (ref["sep_hist"] > 0).sum(1)
+    print("\n%s: hist_max %r, %s of 4096 bins occupied" % (S.shape_id(s), hist_max, occupied.tolist()))
+    assert (occupied >= 32).all(), occupied
+    assert all(not np.array_equal(ref["sep_hist"][a], ref["sep_hist"][b]) for a, b in ((0, 1), (0, 2), (1, 2)))
+    same(g, got, ref)
+
+
+LANE_COUNTS = [(s, n) for s in HIST_SHAPES[:2] for n in (1, 64, 129)]
+
+
+@pytest.mark.parametrize("s,lanes", LANE_COUNTS, ids=["%s-L%d" % (S.shape_id(s), n) for s, n in LANE_COUNTS])
+def test_lane_counts(g, s, lanes):
+    """1 lane (63 padding lanes thread per env, 15 padding envs in the group shape's wave), exactly 64 (none) and 129 (more
+    than two waves) against a reference computed for that lane count: padding lanes play nothing and count nothing, and the
+    lane, not the launch, names the encounter."""
+    ref = S.reference(g, s, lanes=lanes)
+    got = S.campaign(g, s, lanes=lanes).run(S.EPISODES).accumulators()
+    assert got["outcome_count"].sum(1).tolist() == got["sep_hist"].sum(1).tolist() == [lanes * S.EPISODES] * 3
+    assert all(got[k].shape == (3, lanes) for k in g.records.MONTE_CARLO_LANE_KEYS)
+    same(g, got, ref)
+    n = min(lanes, S.LANES)
+    for k in g.records.MONTE_CARLO_LANE_KEYS:
+        assert S.bits_equal(got[k][:, :n], ran(g, s)[k][:, :n]), k
 
 
 def test_summary_of_a_campaign(g):

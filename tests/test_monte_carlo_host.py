@@ -49,6 +49,76 @@ def test_separation_bin_edges(g, dtype):
     assert sb(np.array([5.0, np.nan], dtype), 1, 1.0, dtype).tolist() == [0, 0]            # one bin takes everything
 
 
+# ---- the GPU tests' support: wide keys and the rounding edge ------------------------------------------------------------------
+def test_wide_keys_cross_2_to_the_32_where_the_gpu_tests_claim():
+    """monte_carlo_support.WIDE_*: the seed's halves are non-zero and distinct; the launch's last counter is 2^32 - 1; the
+    lane crosses 2^32 at local lane 37, strictly inside the 70 lanes / episodes / envs, and that lane is neither the first
+    nor the last env of its wave at 64, 32, 16, 8 or 4 envs per wave -- so at every shape the campaigns, evaluators and
+    collectors run at those keys."""
+    import eval_stats_support as ES
+    import helpers as H
+    import monte_carlo_support as MS
+    import noise_scoring_support as NS
+    import test_collect_disturbed as CD
+    import test_monte_carlo as TM
+    lo, hi = MS.WIDE_SEED & 0xFFFFFFFF, MS.WIDE_SEED >> 32
+    assert MS.WIDE_SEED == H.WIDE_SEED and 0 < lo != hi > 0 and hi < 2 ** 32
+    assert MS.WIDE_FIRST_EPISODE + MS.EPISODES - 1 == 2 ** 32 - 1 == NS.WIDE_NOISE_EPISODE
+    c = MS.WIDE_CROSSING
+    assert MS.WIDE_LANE_OFFSET + c == 2 ** 32 and (MS.WIDE_LANE_OFFSET + c - 1) >> 32 == 0
+    assert 0 < c < min(MS.LANES, ES.E, CD.E1) - 1
+    assert MS.TRUNCATED["env_offset"] == (MS.WIDE_LANE_OFFSET + c) & 0xFFFFFFFF == 0          # lane 37's low word: lane 0 of offset 0
+    shapes = ([(s.N, s.group) for s in TM.WIDE_SHAPES + NS.WIDE_CAMPAIGN_SHAPES] + list(NS.WIDE_EVAL_SHAPES) + list(CD.WIDE_SHAPES))
+    assert {(1, False), (8, False), (16, True)} == set(shapes)
+    for N, group in shapes:
+        wave = MS.envs_per_wave((N, group))
+        if group:                                             # the table of work shapes has it: (4, N / 4), the default choice at N
+            assert any(s.dtype == "float32" and s.n_traffic == N and s.override is None and (s.C, s.G) == (4, N // 4) and
+                       s.envs_per_wave == wave for s in H.SHAPES), (N, group)
+        assert 0 < c % wave < wave - 1, (N, group, wave)
+    for wave in (64, 32, 16, 8, 4):
+        assert 0 < c % wave < wave - 1, wave
+
+
+# (format, min_sep, the hist_max found, the bin edge the rounded product lands on)
+EDGES = ((np.float32, 137.25, 2196.0000135493465, 1), (np.float32, 201.7, 1075.7333425837921, 3), (np.float32, 58.9, 104.71111691895858, 9),
+         (np.float64, 137.25, 2196.0, 1), (np.float64, 333.3333, 1777.7776000000001, 3), (np.float64, 58.9, 188.48000000000002, 5))
+
+
+@pytest.mark.parametrize("dtype,min_sep,want,edge", EDGES, ids=["%s-%r" % (np.dtype(e[0]).name, e[1]) for e in EDGES])
+def test_edge_hist_max_meets_its_three_conditions(g, dtype, min_sep, want, edge):
+    """monte_carlo_support.edge_hist_max() on written-out values: the double it returns, and -- in rational arithmetic, not
+    through the function's own expressions -- that the kernel's inverse width is dtype(16 / hist_max), that min_sep lies
+    inside the histogram, and that the product is `edge` exactly once rounded to the format while the exact one is below."""
+    import fractions
+
+    import monte_carlo_support as MS
+    F = fractions.Fraction
+    m = dtype(min_sep)
+    hist_max = MS.edge_hist_max(m, 16, dtype)
+    assert isinstance(hist_max, float) and hist_max == want
+    inv = dtype(16 / hist_max)                                   # what policy.MonteCarlo hands the kernel, rounded as it reads it
+    exact = F(float(m)) * F(float(inv))
+    assert float(m) < hist_max
+    assert exact < edge and float(dtype(m * inv)) == float(edge)
+    # the format's rounding of the exact product, worked out here: the distance to the edge is at most half a unit in the
+    # last place below it (units below a power of two are half those above; `edge` may be one)
+    bits = 24 if dtype == np.float32 else 53
+    ulp_below = F(2) ** (math.floor(math.log2(edge - 0.5 if edge > 1 else 0.75)) - bits + 1)
+    assert 0 < edge - exact <= ulp_below / 2
+    # ... so the bins differ: the kernel's rule says `edge`, exact arithmetic the bin below
+    assert int(g.records.separation_bin(m, 16, 16 / hist_max, dtype)) == edge
+    assert int(MS.exact_bins(m, 16, 16 / hist_max, dtype)) == edge - 1
+
+
+@pytest.mark.parametrize("dtype", (np.float32, np.float64))
+def test_edge_hist_max_raises_where_there_is_no_edge(dtype):
+    """A power of two times an inverse width is exact: no rounding, no such width -- an error, never a fallback."""
+    import monte_carlo_support as MS
+    with pytest.raises(ValueError, match="no bin width"):
+        MS.edge_hist_max(dtype(128.0), 16, dtype)
+
+
 # ---- monte_carlo_reduce -----------------------------------------------------------------------------------------------------
 INF = np.inf
 # [counter][policy][lane]; 4 bins of 128 (inv_bin_width = 1 / 128, exact)
