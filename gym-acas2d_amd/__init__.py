@@ -14,7 +14,7 @@ from .vec_env import ACAS2DVecEnv, LazyInfos                         # noqa: F40
 from .env import ACAS2DEnv, GameView, register_with_gym              # noqa: F401
 from .policy import (SB3ActorPolicy, load_sb3_policy, save_sb3_policy, evaluate_policy, evaluate_policy_fused,  # noqa: F401
                      evaluate_policies_fused, MonteCarlo, EncounterSearch, Disturbance, DisturbanceSet,
-                     CorrelatedDisturbance, CorrelatedDisturbanceSet)
+                     CorrelatedDisturbance, CorrelatedDisturbanceSet, DelayedDisturbance)
 from .ppo import (ActorCritic, ActorCriticSet, FusedUpdate, FusedUpdateSet, PBTConfig, PBTTrainer, PopulationTrainer,  # noqa: F401
                   PPOConfig, PPOTrainer, RewardNormalizer, compute_gae, gae_constants, gae_fused, member_episodes,
                   normalize_rewards_reference, population_exploit, ppo_loss)

@@ -196,6 +196,29 @@ int acas2d_monte_carlo_correlated_group_f32(SCORING_PARAMS(n_lanes), const Acas2
                                             const Acas2dCorrelation* correlation, void* stream) {
     return launch_monte_carlo<float, 2>(SCORING_ARGS(n_lanes, true), mc, disturbance, correlation);
 }
+// ... and under a dead time and a lag between the actor and the aircraft on top of that (eval_stats_delayed_kernel,
+// monte_carlo_delayed_kernel; float32)
+int acas2d_evaluate_policies_delayed_f32(SCORING_PARAMS(n_episodes), uint8_t* outcome, int32_t* steps, void* total_reward,
+                                         const Acas2dEvalStats* stats, const Acas2dDisturbance* disturbance,
+                                         const Acas2dCorrelation* correlation, const Acas2dResponse* response, void* stream) {
+    return launch_evaluate_policies<float, Scoring::Delayed>(SCORING_ARGS(n_episodes, false), outcome, steps, total_reward,
+                                                             stats, disturbance, correlation, response);
+}
+int acas2d_evaluate_policies_delayed_group_f32(SCORING_PARAMS(n_episodes), uint8_t* outcome, int32_t* steps, void* total_reward,
+                                               const Acas2dEvalStats* stats, const Acas2dDisturbance* disturbance,
+                                               const Acas2dCorrelation* correlation, const Acas2dResponse* response, void* stream) {
+    return launch_evaluate_policies<float, Scoring::Delayed>(SCORING_ARGS(n_episodes, true), outcome, steps, total_reward,
+                                                             stats, disturbance, correlation, response);
+}
+int acas2d_monte_carlo_delayed_f32(SCORING_PARAMS(n_lanes), const Acas2dMonteCarlo* mc, const Acas2dDisturbance* disturbance,
+                                   const Acas2dCorrelation* correlation, const Acas2dResponse* response, void* stream) {
+    return launch_monte_carlo<float, 3>(SCORING_ARGS(n_lanes, false), mc, disturbance, correlation, response);
+}
+int acas2d_monte_carlo_delayed_group_f32(SCORING_PARAMS(n_lanes), const Acas2dMonteCarlo* mc, const Acas2dDisturbance* disturbance,
+                                         const Acas2dCorrelation* correlation, const Acas2dResponse* response, void* stream) {
+    return launch_monte_carlo<float, 3>(SCORING_ARGS(n_lanes, true), mc, disturbance, correlation, response);
+}
+size_t acas2d_response_size(void) { return sizeof(Acas2dResponse); }
 size_t acas2d_correlation_size(void) { return sizeof(Acas2dCorrelation); }
 size_t acas2d_monte_carlo_size(void) { return sizeof(Acas2dMonteCarlo); }
 size_t acas2d_disturbance_size(void) { return sizeof(Acas2dDisturbance); }

@@ -1508,6 +1508,28 @@ __device__ __forceinline__ float correlated(float* held, bool first, float rho, 
     if (commit) *held = e;
     return e;
 }
+// RESP on top of CORR (acas2d_evaluate_policies_delayed_*, acas2d_monte_carlo_delayed_*; float32): the clipped action reaches
+// the aircraft late and through a lag -- first-order plus dead time (include/acas2d.h, Acas2dResponse; records.response_delay()
+// and records.response_lag() are the two steps in NumPy).  The kernels are eval_stats_delayed_kernel and
+// monte_carlo_delayed_kernel (acas2d_scoring_delayed.hip), their last arguments these derived structs.
+// The lag's state u_{s-1} is one more per-lane LDS slot behind CorrW's (every lane of a group keeps a copy, as of the
+// actuator's error).  The dead time's line is `ring`, float[delay][ring_envs] in device memory, slot steps % delay of the
+// launch's env: an env's step loads the action written there `delay` steps ago and stores its own in its place, both by the
+// env's first lane.  What the ring holds on entry means nothing: an episode younger than `delay` steps reads no slot.
+struct RespW {
+    int32_t delay;                                   // Acas2dResponse::delay_steps
+    float lam, gain;                                 // Acas2dResponse::lag and (float)(1 - (double)lag), formed on the host
+    float* ring;                                     // float[delay][ring_envs]
+    int64_t ring_envs;
+};
+struct PolicyEvalStatsRespW : PolicyEvalStatsCorrW { RespW resp; };
+struct PolicyMonteCarloRespW : PolicyMonteCarloCorrW { RespW resp; };
+template <typename PW>
+__device__ __forceinline__ const RespW* response_args(const PW& pw) {
+    if constexpr (std::is_base_of<PolicyEvalStatsRespW, PW>::value || std::is_base_of<PolicyMonteCarloRespW, PW>::value)
+        return &pw.resp;
+    else return nullptr;
+}
 // DIST on top of Mode::CollectSet (acas2d_collect_set_disturbed_f32, acas2d_collect_set_disturbed_group_f32;
 // collect_set_disturbed_kernel): the collector under the same noise.  Both networks read the disturbed row, which the launch
 // also writes out (obs_read); the standard deviations are the MEMBER's, a row of a device float[K][4] that its waves load
@@ -1801,7 +1823,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const T* a0, const T* a1, 
                                                       Params<T> p_arg, StepResetParams<T, rollout_mode(M)> rp_arg, State<T> s_arg,
                                                       StepIO<T> io_arg, uint32_t k0, uint32_t k1,
                                                       int64_t env_offset, int N_arg, int n_steps, PolicyArg<M == Mode::Eval> pw) {
-    constexpr bool STATS = false, MC = false, DIST = false, CORR = false;
+    constexpr bool STATS = false, MC = false, DIST = false, CORR = false, RESP = false;
 #include "acas2d_step_body.inl"
 }
 // Mode::Eval with STATS: step_kernel's arguments (and so the same preloaded ones) with PolicyEvalStatsW at the end.
@@ -1812,7 +1834,7 @@ __global__ __launch_bounds__(kBlock) void eval_stats_kernel(const T* a0, const T
                                                             Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
                                                             StepIO<T> io_arg, uint32_t k0, uint32_t k1,
                                                             int64_t env_offset, int N_arg, int n_steps, PolicyEvalStatsW pw) {
-    constexpr bool PACKED = true, STATS = true, MC = false, DIST = false, CORR = false;
+    constexpr bool PACKED = true, STATS = true, MC = false, DIST = false, CORR = false, RESP = false;
     constexpr Mode M = Mode::Eval;
 #include "acas2d_step_body.inl"
 }
@@ -1826,7 +1848,7 @@ __global__ __launch_bounds__(kBlock) void monte_carlo_kernel(const T* a0, const 
                                                              Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
                                                              StepIO<T> io_arg, uint32_t k0, uint32_t k1,
                                                              int64_t env_offset, int N_arg, int n_steps, PolicyMonteCarloW pw) {
-    constexpr bool PACKED = true, STATS = true, MC = true, DIST = false, CORR = false;
+    constexpr bool PACKED = true, STATS = true, MC = true, DIST = false, CORR = false, RESP = false;
     constexpr Mode M = Mode::Eval;
 #include "acas2d_step_body.inl"
 }
@@ -1840,7 +1862,7 @@ __global__ __launch_bounds__(kBlock) void eval_stats_disturbed_kernel(const T* a
                                                                       Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
                                                                       StepIO<T> io_arg, uint32_t k0, uint32_t k1, int64_t env_offset,
                                                                       int N_arg, int n_steps, PolicyEvalStatsDistW pw) {
-    constexpr bool PACKED = true, STATS = true, MC = false, DIST = true, CORR = false;
+    constexpr bool PACKED = true, STATS = true, MC = false, DIST = true, CORR = false, RESP = false;
     constexpr Mode M = Mode::Eval;
 #include "acas2d_step_body.inl"
 }
@@ -1850,7 +1872,7 @@ __global__ __launch_bounds__(kBlock) void monte_carlo_disturbed_kernel(const T* 
                                                                        Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
                                                                        StepIO<T> io_arg, uint32_t k0, uint32_t k1, int64_t env_offset,
                                                                        int N_arg, int n_steps, PolicyMonteCarloDistW pw) {
-    constexpr bool PACKED = true, STATS = true, MC = true, DIST = true, CORR = false;
+    constexpr bool PACKED = true, STATS = true, MC = true, DIST = true, CORR = false, RESP = false;
     constexpr Mode M = Mode::Eval;
 #include "acas2d_step_body.inl"
 }
@@ -1865,7 +1887,7 @@ __global__ __launch_bounds__(kBlock) void collect_set_disturbed_kernel(const T* 
                                                                        Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
                                                                        StepIO<T> io_arg, uint32_t k0, uint32_t k1, int64_t env_offset,
                                                                        int N_arg, int n_steps, PW pw) {
-    constexpr bool PACKED = true, STATS = false, MC = false, DIST = true, CORR = false;
+    constexpr bool PACKED = true, STATS = false, MC = false, DIST = true, CORR = false, RESP = false;
     constexpr Mode M = Mode::CollectSet;
 #include "acas2d_step_body.inl"
 }
@@ -1879,7 +1901,7 @@ __global__ __launch_bounds__(kBlock) void eval_stats_correlated_kernel(const T* 
                                                                        Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
                                                                        StepIO<T> io_arg, uint32_t k0, uint32_t k1, int64_t env_offset,
                                                                        int N_arg, int n_steps, PolicyEvalStatsCorrW pw) {
-    constexpr bool PACKED = true, STATS = true, MC = false, DIST = true, CORR = true;
+    constexpr bool PACKED = true, STATS = true, MC = false, DIST = true, CORR = true, RESP = false;
     constexpr Mode M = Mode::Eval;
 #include "acas2d_step_body.inl"
 }
@@ -1889,7 +1911,31 @@ __global__ __launch_bounds__(kBlock) void monte_carlo_correlated_kernel(const T*
                                                                         Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
                                                                         StepIO<T> io_arg, uint32_t k0, uint32_t k1, int64_t env_offset,
                                                                         int N_arg, int n_steps, PolicyMonteCarloCorrW pw) {
-    constexpr bool PACKED = true, STATS = true, MC = true, DIST = true, CORR = true;
+    constexpr bool PACKED = true, STATS = true, MC = true, DIST = true, CORR = true, RESP = false;
+    constexpr Mode M = Mode::Eval;
+#include "acas2d_step_body.inl"
+}
+// eval_stats_correlated_kernel and monte_carlo_correlated_kernel with RESP (acas2d_evaluate_policies_delayed_*,
+// acas2d_monte_carlo_delayed_*): the clipped action passes a dead time and a first-order lag in front of the actuator's error
+// (RespW).  Kernels of their own for the reason eval_stats_kernel is one, instantiated in a unit of their own
+// (acas2d_scoring_delayed.hip); float32 only.
+template <typename T, int C, int G, bool FAST>
+__global__ __launch_bounds__(kBlock) void eval_stats_delayed_kernel(const T* a0, const T* a1, const T* a2, const T* a3,
+                                                                    const T* a4, const T* a5, int32_t e_n_envs, int32_t tile_elems,
+                                                                    Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
+                                                                    StepIO<T> io_arg, uint32_t k0, uint32_t k1, int64_t env_offset,
+                                                                    int N_arg, int n_steps, PolicyEvalStatsRespW pw) {
+    constexpr bool PACKED = true, STATS = true, MC = false, DIST = true, CORR = true, RESP = true;
+    constexpr Mode M = Mode::Eval;
+#include "acas2d_step_body.inl"
+}
+template <typename T, int C, int G, bool FAST>
+__global__ __launch_bounds__(kBlock) void monte_carlo_delayed_kernel(const T* a0, const T* a1, const T* a2, const T* a3,
+                                                                     const T* a4, const T* a5, int32_t e_n_envs, int32_t tile_elems,
+                                                                     Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
+                                                                     StepIO<T> io_arg, uint32_t k0, uint32_t k1, int64_t env_offset,
+                                                                     int N_arg, int n_steps, PolicyMonteCarloRespW pw) {
+    constexpr bool PACKED = true, STATS = true, MC = true, DIST = true, CORR = true, RESP = true;
     constexpr Mode M = Mode::Eval;
 #include "acas2d_step_body.inl"
 }
@@ -1902,7 +1948,7 @@ __global__ __launch_bounds__(kBlock) void collect_set_correlated_kernel(const T*
                                                                         Params<T> p_arg, StepResetParams<T, true> rp_arg, State<T> s_arg,
                                                                         StepIO<T> io_arg, uint32_t k0, uint32_t k1, int64_t env_offset,
                                                                         int N_arg, int n_steps, PW pw) {
-    constexpr bool PACKED = true, STATS = false, MC = false, DIST = true, CORR = true;
+    constexpr bool PACKED = true, STATS = false, MC = false, DIST = true, CORR = true, RESP = false;
     constexpr Mode M = Mode::CollectSet;
 #include "acas2d_step_body.inl"
 }
@@ -2015,15 +2061,18 @@ struct ScoringArgs {
 };
 // the evaluator: step_kernel<..., Mode::Eval> / eval_stats_kernel (stats) / eval_stats_disturbed_kernel (stats and dist; float32)
 // / eval_stats_correlated_kernel (stats, dist and corr; float32, acas2d_scoring_correlated.hip)
-enum class Scoring { Plain, Stats, Disturbed, Correlated };
+// / eval_stats_delayed_kernel (stats, dist, corr and resp; float32, acas2d_scoring_delayed.hip)
+enum class Scoring { Plain, Stats, Disturbed, Correlated, Delayed };
 template <typename T, Scoring V>
 int launch_evaluate_policies(const ScoringArgs& a, uint8_t* outcome, int32_t* steps, void* total_reward,
-                             const Acas2dEvalStats* stats, const Acas2dDisturbance* dist, const Acas2dCorrelation* corr = nullptr);
+                             const Acas2dEvalStats* stats, const Acas2dDisturbance* dist, const Acas2dCorrelation* corr = nullptr,
+                             const Acas2dResponse* resp = nullptr);
 // the campaign: monte_carlo_kernel / monte_carlo_disturbed_kernel (V = 1: dist; float32) / monte_carlo_correlated_kernel
-// (V = 2: dist and corr; float32, acas2d_scoring_correlated.hip)
+// (V = 2: dist and corr; float32, acas2d_scoring_correlated.hip) / monte_carlo_delayed_kernel (V = 3: dist, corr and resp;
+// float32, acas2d_scoring_delayed.hip)
 template <typename T, int V>
 int launch_monte_carlo(const ScoringArgs& a, const Acas2dMonteCarlo* mc, const Acas2dDisturbance* dist,
-                       const Acas2dCorrelation* corr = nullptr);
+                       const Acas2dCorrelation* corr = nullptr, const Acas2dResponse* resp = nullptr);
 // acas2d_disturbance_draw_f32 (float32 only)
 template <typename T>
 int launch_disturbance_draw(uint64_t seed, int64_t first_lane, int32_t n_lanes, uint32_t episode, int32_t first_step,

@@ -135,7 +135,8 @@ static int check_launch(const char* name) {
 // workgroup, one LDS observation tile per wavefront.  `group_policy`: the launch evaluates the in-kernel policy
 // with the G lanes of an env together and keeps each env's 64 hidden activations behind the wave's tile and reset
 // slots (policy_mlp_group(); the kernel finds them at the END of the wave's tile_elems).  `held`: values the launch keeps
-// per LANE behind all of that (the correlated flavours' error state, CorrW; the hidden vectors then end where it begins).
+// per LANE behind all of that (the correlated flavours' error state, CorrW, and the delayed flavours' lag state behind it, RespW;
+// the hidden vectors then end where it begins).
 struct Geometry { unsigned grid, block; int tile_elems; size_t lds_bytes; };
 
 template <typename T>
@@ -258,6 +259,7 @@ struct Launch {
     uint32_t k0, k1;
     bool group_policy;                        // the *_group entry points: geometry_for()'s hidden vectors
     bool correlated;                          // the *_correlated entry points: geometry_for()'s error state, 3 C + 1 per lane
+    bool delayed;                             // the *_delayed entry points: one value more per lane, the lag's state
 };
 
 // The entry points' words for the rejections they share (each has always said them its own way)
@@ -280,7 +282,7 @@ static int prepare(Launch<T>& L, const Words& words, bool given, Inputs inputs, 
     if (L.n_envs < 0 || L.env_offset < 0) return fail(words.negative, L.name);
     if (L.n_envs == 0) return ACAS2D_OK;
     if (int rc = shape(&L.sh)) return rc;
-    if (int rc = geometry_for<T>(L.sh, L.n_envs, L.N, &L.g, L.group_policy, L.correlated ? kCorrSlots(L.sh.C) : 0)) return rc;
+    if (int rc = geometry_for<T>(L.sh, L.n_envs, L.N, &L.g, L.group_policy, L.correlated ? kCorrSlots(L.sh.C) + (L.delayed ? 1 : 0) : 0)) return rc;
     L.p = make_params<T>(*L.cfg);
     L.s = make_state<T>(*L.st);
     if (const Acas2dStepIO* io = L.step_io)
@@ -326,13 +328,15 @@ static int require_aligned(const char* name, std::initializer_list<const void*> 
     return ACAS2D_OK;
 }
 
-// The kernel of a launch: step_kernel in mode M, unless the launch's policy argument is one of the eight that have a kernel
-// of their own (Mode::Eval with statistics, the Monte Carlo campaign, the disturbed and the correlated flavour of each, the
-// disturbed and the correlated set collector; packed shapes)
+// The kernel of a launch: step_kernel in mode M, unless the launch's policy argument is one of the ten that have a kernel
+// of their own (Mode::Eval with statistics, the Monte Carlo campaign, the disturbed, the correlated and the delayed flavour of
+// each, the disturbed and the correlated set collector; packed shapes)
 template <typename PW, typename T, int C, int G, bool PACKED, bool FAST, Mode M>
 static constexpr auto kernel_for() {
     if constexpr (std::is_same<PW, PolicyCollectCorrW>::value) return &collect_set_correlated_kernel<T, C, G, FAST>;
     else if constexpr (std::is_same<PW, PolicyCollectDistW>::value) return &collect_set_disturbed_kernel<T, C, G, FAST>;
+    else if constexpr (std::is_same<PW, PolicyMonteCarloRespW>::value) return &monte_carlo_delayed_kernel<T, C, G, FAST>;
+    else if constexpr (std::is_same<PW, PolicyEvalStatsRespW>::value) return &eval_stats_delayed_kernel<T, C, G, FAST>;
     else if constexpr (std::is_same<PW, PolicyMonteCarloCorrW>::value) return &monte_carlo_correlated_kernel<T, C, G, FAST>;
     else if constexpr (std::is_same<PW, PolicyEvalStatsCorrW>::value) return &eval_stats_correlated_kernel<T, C, G, FAST>;
     else if constexpr (std::is_same<PW, PolicyMonteCarloDistW>::value) return &monte_carlo_disturbed_kernel<T, C, G, FAST>;
@@ -625,6 +629,21 @@ static int check_correlation(const char* name, const Acas2dCorrelation* c) {
                         (double)rho[0], (double)rho[1], (double)rho[2], (double)rho[3]);
     return ACAS2D_OK;
 }
+// ... and the delayed entries on top of the correlated ones, last of all: `total` is the launch's env count, n_policies x EP
+static int check_response(const char* name, const Acas2dResponse* r, int64_t total) {
+    if (!r) return fail("%s: NULL response", name);
+    if (r->delay_steps < 0 || r->delay_steps > 32767)
+        return fail("%s: delay_steps = %d (0 to 32767)", name, r->delay_steps);
+    if (!(r->lag >= 0.0f) || !(r->lag <= 1.0f)) return fail("%s: lag = %g (in [0, 1])", name, (double)r->lag);
+    if (r->delay_steps > 0 && !r->ring)
+        return fail("%s: NULL ring with delay_steps = %d (float[delay_steps][ring_envs], on the device)", name, r->delay_steps);
+    if (r->delay_steps > 0 && r->ring_envs < total)
+        return fail("%s: ring_envs = %lld, the launch covers %lld envs", name, (long long)r->ring_envs, (long long)total);
+    return ACAS2D_OK;
+}
+static RespW response_words(const Acas2dResponse& r) {
+    return RespW{r.delay_steps, r.lag, (float)(1.0 - (double)r.lag), r.ring, r.ring_envs};
+}
 static CorrW correlation_words(const Acas2dCorrelation& c) {
     const auto gain = [](float rho) { return (float)std::sqrt(1.0 - (double)rho * (double)rho); };
     return CorrW{c.rho_sep, c.rho_cpa, c.rho_closing, c.rho_action,
@@ -646,26 +665,32 @@ static const ScoringWords kEvaluateWords[] = {             // [Scoring]
     {"acas2d_evaluate_policies_disturbed", "acas2d_evaluate_policies_disturbed_group", "acas2d_evaluate_policies_disturbed_f32",
      "n_episodes", "acas2d_evaluate_policies"},
     {"acas2d_evaluate_policies_correlated", "acas2d_evaluate_policies_correlated_group", "acas2d_evaluate_policies_correlated_f32",
+     "n_episodes", "acas2d_evaluate_policies"},
+    {"acas2d_evaluate_policies_delayed", "acas2d_evaluate_policies_delayed_group", "acas2d_evaluate_policies_delayed_f32",
      "n_episodes", "acas2d_evaluate_policies"}};
-static const ScoringWords kMonteCarloWords[] = {           // [plain, disturbed, correlated]
+static const ScoringWords kMonteCarloWords[] = {           // [plain, disturbed, correlated, delayed]
     {"acas2d_monte_carlo", "acas2d_monte_carlo_group", "acas2d_monte_carlo_f32", "n_lanes", nullptr},
     {"acas2d_monte_carlo_disturbed", "acas2d_monte_carlo_disturbed_group", "acas2d_monte_carlo_disturbed_f32", "n_lanes", nullptr},
-    {"acas2d_monte_carlo_correlated", "acas2d_monte_carlo_correlated_group", "acas2d_monte_carlo_correlated_f32", "n_lanes", nullptr}};
+    {"acas2d_monte_carlo_correlated", "acas2d_monte_carlo_correlated_group", "acas2d_monte_carlo_correlated_f32", "n_lanes", nullptr},
+    {"acas2d_monte_carlo_delayed", "acas2d_monte_carlo_delayed_group", "acas2d_monte_carlo_delayed_f32", "n_lanes", nullptr}};
 
 // Everything the two share, around their own parts: nulls(name), the family's required pointers; own(name), its checks
 // behind the counts' and in front of the disturbance's; fill(pw), its fields of the kernel's last argument PW -- which
-// picks the kernel (kernel_for()).  A PW with a CorrW is a correlated entry's: `corr` is checked last of all.
+// picks the kernel (kernel_for()).  A PW with a CorrW is a correlated entry's: `corr` is checked last of all -- but for `resp`,
+// which a PW with a RespW (a delayed entry's) checks behind it.
 template <typename T, typename PW, bool DIST, typename Nulls, typename Own, typename Fill>
 static int score(const ScoringArgs& a, const ScoringWords& w, const Acas2dDisturbance* dist, const Acas2dCorrelation* corr,
-                 Nulls nulls, Own own, Fill fill) {
+                 const Acas2dResponse* resp, Nulls nulls, Own own, Fill fill) {
     static_assert(!DIST || sizeof(T) == 4, "the disturbed flavours: float32");
     constexpr bool CORR = std::is_base_of<PolicyEvalStatsCorrW, PW>::value || std::is_base_of<PolicyMonteCarloCorrW, PW>::value;
     static_assert(!CORR || DIST, "the correlated flavours: on top of the disturbed ones");
+    constexpr bool RESP = std::is_base_of<PolicyEvalStatsRespW, PW>::value || std::is_base_of<PolicyMonteCarloRespW, PW>::value;
     const int64_t ep = ((int64_t)a.n_per_policy + 63) / 64 * 64, total = (int64_t)a.n_policies * ep;
     Launch<T> L{a.group ? w.group_name : w.name, a.cfg, a.st, nullptr, a.seed, a.env_offset, total, a.n_traffic, a.n_steps,
                 a.stream};
     L.group_policy = a.group;
     L.correlated = CORR;
+    L.delayed = RESP;
     const auto inputs = [&] {
         if (int rc = nulls(L.name)) return rc;
         if (int rc = require_actor(L.name, a.pol)) return rc;
@@ -687,9 +712,12 @@ static int score(const ScoringArgs& a, const ScoringWords& w, const Acas2dDistur
             if (int rc = require_aligned(L.name, {a.pol->w1t, a.pol->b1, a.pol->w2t, a.pol->b2})) return rc;
         if constexpr (CORR)
             if (int rc = check_correlation(L.name, corr)) return rc;
+        if constexpr (RESP)
+            if (int rc = check_response(L.name, resp, total)) return rc;
         PW pw = actor<PW>(a.pol, a.obs_in);
         if constexpr (DIST) pw.dist = disturbance_words(*dist);
         if constexpr (CORR) pw.corr = correlation_words(*corr);
+        if constexpr (RESP) pw.resp = response_words(*resp);
         pw.n_episodes = a.n_per_policy; pw.ep_stride = (int32_t)ep;
         fill(pw);
         return launch_mode<Mode::Eval>(L, pw);
@@ -700,15 +728,18 @@ static int score(const ScoringArgs& a, const ScoringWords& w, const Acas2dDistur
 // acas2d_evaluate_policies_*: each lane's first episode, scored.  Scoring::Stats adds the per-episode safety statistics
 // (eval_stats_kernel instead of step_kernel<..., Mode::Eval>), Scoring::Disturbed sensor noise and actuator disturbance on
 // top (eval_stats_disturbed_kernel; float32), Scoring::Correlated a Gauss-Markov error in the white noise's place
-// (eval_stats_correlated_kernel; float32, instantiated by acas2d_scoring_correlated.hip).
+// (eval_stats_correlated_kernel; float32, instantiated by acas2d_scoring_correlated.hip), Scoring::Delayed a dead time and a lag
+// between the actor and the actuator on top of that (eval_stats_delayed_kernel; float32, acas2d_scoring_delayed.hip).
 // (The units instantiate Stats and Disturbed LAST -- ACAS2D_INSTANTIATE_SCORING at their ends -- so that their kernels follow
 //  every other kernel of the unit, and those keep the local labels of their assembly too.)
 template <typename T, Scoring V>
 int launch_evaluate_policies(const ScoringArgs& a, uint8_t* outcome, int32_t* steps, void* total_reward,
-                             const Acas2dEvalStats* stats, const Acas2dDisturbance* dist, const Acas2dCorrelation* corr) {
-    constexpr bool STATS = V != Scoring::Plain, CORR = V == Scoring::Correlated, DIST = V == Scoring::Disturbed || CORR;
-    using PW = typename std::conditional<CORR, PolicyEvalStatsCorrW, typename std::conditional<DIST, PolicyEvalStatsDistW,
-                                         typename std::conditional<STATS, PolicyEvalStatsW, PolicyEvalW>::type>::type>::type;
+                             const Acas2dEvalStats* stats, const Acas2dDisturbance* dist, const Acas2dCorrelation* corr,
+                             const Acas2dResponse* resp) {
+    constexpr bool STATS = V != Scoring::Plain, RESP = V == Scoring::Delayed, CORR = V == Scoring::Correlated || RESP;
+    constexpr bool DIST = V == Scoring::Disturbed || CORR;
+    using PW = typename std::conditional<RESP, PolicyEvalStatsRespW, typename std::conditional<CORR, PolicyEvalStatsCorrW, typename std::conditional<DIST, PolicyEvalStatsDistW,
+                                         typename std::conditional<STATS, PolicyEvalStatsW, PolicyEvalW>::type>::type>::type>::type;
     const auto nulls = [&](const char* name) {
         if (!a.obs_in || !outcome || !steps || !total_reward)
             return fail("%s: obs_in and the outcome, steps and total_reward outputs are required", name);
@@ -726,17 +757,18 @@ int launch_evaluate_policies(const ScoringArgs& a, uint8_t* outcome, int32_t* st
             pw.st_max_a_lat = stats->max_a_lat; pw.st_max_dev = stats->max_dev; pw.st_sum_dev = stats->sum_dev;
         }
     };
-    return score<T, PW, DIST>(a, kEvaluateWords[(int)V], dist, corr, nulls, [](const char*) { return ACAS2D_OK; }, fill);
+    return score<T, PW, DIST>(a, kEvaluateWords[(int)V], dist, corr, resp, nulls, [](const char*) { return ACAS2D_OK; }, fill);
 }
 
 // acas2d_monte_carlo_*: the same blocks of lanes, each lane playing mc->episodes_per_lane drawn episodes and folding them
-// into mc's accumulators (monte_carlo_kernel; V = 1: monte_carlo_disturbed_kernel, V = 2: monte_carlo_correlated_kernel, both
-// float32).  Instantiated after the stats evaluator, for the same reason.
+// into mc's accumulators (monte_carlo_kernel; V = 1: monte_carlo_disturbed_kernel, V = 2: monte_carlo_correlated_kernel, V = 3:
+// monte_carlo_delayed_kernel, all three float32).  Instantiated after the stats evaluator, for the same reason.
 template <typename T, int V>
-int launch_monte_carlo(const ScoringArgs& a, const Acas2dMonteCarlo* mc, const Acas2dDisturbance* dist, const Acas2dCorrelation* corr) {
-    constexpr bool DIST = V >= 1, CORR = V == 2;
-    using PW = typename std::conditional<CORR, PolicyMonteCarloCorrW,
-                                         typename std::conditional<DIST, PolicyMonteCarloDistW, PolicyMonteCarloW>::type>::type;
+int launch_monte_carlo(const ScoringArgs& a, const Acas2dMonteCarlo* mc, const Acas2dDisturbance* dist, const Acas2dCorrelation* corr,
+                       const Acas2dResponse* resp) {
+    constexpr bool DIST = V >= 1, CORR = V >= 2, RESP = V == 3;
+    using PW = typename std::conditional<RESP, PolicyMonteCarloRespW, typename std::conditional<CORR, PolicyMonteCarloCorrW,
+                                         typename std::conditional<DIST, PolicyMonteCarloDistW, PolicyMonteCarloW>::type>::type>::type;
     const auto nulls = [&](const char* name) {
         if (!a.obs_in) return fail("%s: obs_in is required", name);
         if (!mc) return fail("%s: NULL mc", name);
@@ -768,7 +800,7 @@ int launch_monte_carlo(const ScoringArgs& a, const Acas2dMonteCarlo* mc, const A
         pw.mc_n_bins = mc->n_bins; pw.mc_episodes = mc->episodes_per_lane; pw.mc_first = mc->first_episode;
         pw.mc_inv_bin_f = (float)mc->inv_bin_width; pw.mc_inv_bin_d = mc->inv_bin_width;
     };
-    return score<T, PW, DIST>(a, kMonteCarloWords[V], dist, corr, nulls, own, fill);
+    return score<T, PW, DIST>(a, kMonteCarloWords[V], dist, corr, resp, nulls, own, fill);
 }
 
 // acas2d_disturbance_draw_f32: the normals the disturbed kernels draw (float32; instantiated with them)
@@ -809,6 +841,11 @@ int launch_disturbance_draw(uint64_t seed, int64_t first_lane, int32_t n_lanes, 
     namespace acas2d { \
     template decltype(launch_evaluate_policies<Elem, Scoring::Correlated>) launch_evaluate_policies<Elem, Scoring::Correlated>; \
     template decltype(launch_monte_carlo<Elem, 2>) launch_monte_carlo<Elem, 2>; }
+// the delayed evaluator and campaign: the instantiations of acas2d_scoring_delayed.hip, a unit of its own likewise
+#define ACAS2D_INSTANTIATE_SCORING_DELAYED \
+    namespace acas2d { \
+    template decltype(launch_evaluate_policies<Elem, Scoring::Delayed>) launch_evaluate_policies<Elem, Scoring::Delayed>; \
+    template decltype(launch_monte_carlo<Elem, 3>) launch_monte_carlo<Elem, 3>; }
 // the disturbed set collector: the ONE instantiation of acas2d_collect_disturbed.hip, a unit of its own -- the float32 unit
 // ends with the kernels above, and every kernel of it keeps its place, its name and the local labels of its assembly
 #define ACAS2D_INSTANTIATE_COLLECT_DISTURBED \

@@ -1,8 +1,8 @@
-// acas2d_step_body.inl -- the body of step_kernel, eval_stats_kernel, monte_carlo_kernel, the latter two's disturbed and
-// correlated flavours and the disturbed and the correlated set collector (acas2d_kernels.hpp, where the modes and what each one
-// implies are described), included inside all nine.  It
+// acas2d_step_body.inl -- the body of step_kernel, eval_stats_kernel, monte_carlo_kernel, the latter two's disturbed,
+// correlated and delayed flavours and the disturbed and the correlated set collector (acas2d_kernels.hpp, where the modes and what
+// each one implies are described), included inside all eleven.  It
 // expects the including kernel's template parameters T, C, G, PACKED, FAST, M (or constants of those names), the constants
-// STATS, MC, DIST and CORR, and the kernel's arguments a0 .. a5,
+// STATS, MC, DIST, CORR and RESP, and the kernel's arguments a0 .. a5,
 // e_n_envs, tile_elems, p_arg, rp_arg, s_arg, io_arg, k0, k1, env_offset, N_arg, n_steps, pw.
     constexpr bool AUTO_RESET = M != Mode::Latch, ROLLOUT = rollout_mode(M);
     constexpr bool POLICY = policy_mode(M), SAMPLE = sample_mode(M);
@@ -231,6 +231,8 @@
     (void)set_dw;
     // CORR: the lane's held errors e_{t-1}, at the end of the wave's LDS (CorrW) -- value i at corr_held[i * 64]: 3 k + c for
     // channel c of the lane's k-th aircraft, then the actuator's
+    // (RESP: one slot more behind them, the lag's u_{s-1} -- RespW)
+    constexpr int kHeldSlots = CORR ? kCorrSlots(C) + (RESP ? 1 : 0) : 0;
     float* corr_held = nullptr;
     (void)corr_held;
     // CORR and SET (collect_set_correlated_kernel): the member's four rho and four gains as the CorrW the evaluator takes by
@@ -240,7 +242,7 @@
     if constexpr (CORR) {
         static_assert(DIST && ((EVAL && STATS) || SET),
                       "correlated errors: the disturbed stats evaluator, Monte Carlo kernel and set collector");
-        corr_held = reinterpret_cast<float*>(tile) + (tile_elems - kCorrSlots(C) * 64) + lane;
+        corr_held = reinterpret_cast<float*>(tile) + (tile_elems - kHeldSlots * 64) + lane;
         if constexpr (SET) {
             // the state the previous launch left (CollectCorrW::held, rows of E): every process of the lane, whatever its rho --
             // a value nobody advances goes back as it came.  Lanes past the last env load nothing: they play a copy of the
@@ -358,7 +360,7 @@
             // G > 1: the group evaluates the network together (policy_mlp_group()); its hidden vector lies behind
             // the wave's tile and reset slots (geometry_for())
             float* hid = nullptr;
-            if constexpr (G > 1) hid = reinterpret_cast<float*>(tile) + (tile_elems - (CORR ? kCorrSlots(C) * 64 : 0) - EPW * kPolicyHidden);
+            if constexpr (G > 1) hid = reinterpret_cast<float*>(tile) + (tile_elems - kHeldSlots * 64 - EPW * kPolicyHidden);
             (void)hid;
             // The weights must be RE-READ every step (scalar cache hits): they are loop-invariant, and
             // hoisted out of the step loop hipcc tries to keep all 4 700 of them in SGPRs, spills them
@@ -434,6 +436,37 @@
                     action = (T)(m != m ? m : fminf(fmaxf(m, -1.0f), 1.0f));
                 }
                 if constexpr (!EVAL) { if (active && j == 0) (static_cast<T*>(pw.actions_out) + e_wave + te)[el] = action; }
+                if constexpr (RESP) {
+                    // the response (RespW): the clipped action a_s becomes the command c_s = a_{s - delay} of the same episode
+                    // (0 while the episode is younger than that), then u_s = clamp((lam u_{s-1}) + (g c_s)) with u = 0 in front
+                    // of the episode's first step; the actuator's error below acts on u_s.  Both off: wave-uniform, nothing done.
+                    static_assert(CORR && EVAL && STATS, "response delay and lag: the correlated stats evaluator and Monte Carlo kernel");
+                    const RespW* const rs = response_args(pw);
+                    float cmd = (float)action;
+                    if (rs->delay != 0) {                 // (wave-uniform)
+                        // the episode's age in steps, this one not counted: t until the launch's first in-step reset (whatever
+                        // `steps` the state came in with), steps - 1 from then on.  Slot steps % delay holds a_{s - delay} once the
+                        // episode is `delay` steps old and is never read before.  The address is a fresh value behind the network.
+                        const uint32_t age = (uint32_t)t < (uint32_t)(steps - 1) ? (uint32_t)t : (uint32_t)(steps - 1);
+                        const uint32_t slot = (uint32_t)steps % (uint32_t)rs->delay;
+                        int el_r = el;
+                        asm volatile("" : "+v"(el_r));
+                        float* const q = rs->ring + ((int64_t)slot * rs->ring_envs + (e_wave + el_r));
+                        float late = 0.0f;
+                        if (active && j == 0) {           // (the env's first lane: every access to an address in program order)
+                            if (age >= (uint32_t)rs->delay) late = *q;
+                            *q = cmd;
+                        }
+                        cmd = group_bcast0<G>(late);
+                    }
+                    if (rs->lam != 0.0f) {                // (wave-uniform)
+                        float* const held = corr_held + kCorrSlots(C) * 64;
+                        const float prev = (t == 0 || steps == 1) ? 0.0f : *held;
+                        cmd = fminf(fmaxf(__fadd_rn(__fmul_rn(rs->lam, prev), __fmul_rn(rs->gain, cmd)), -1.0f), 1.0f);
+                        *held = cmd;
+                    }
+                    action = (T)cmd;
+                }
                 if constexpr (DIST) {                     // actuator noise: slot 0 on the clipped action, clipped again
                     const DisturbW* const dw = disturbance_args(pw);
                     if (dw->s_action != 0.0f) {           // (wave-uniform)

@@ -98,6 +98,12 @@ class CCorrelation(C.Structure):
     _fields_ = [(n, C.c_float) for n in ("rho_sep", "rho_cpa", "rho_closing", "rho_action")]
 
 
+class CResponse(C.Structure):
+    """struct Acas2dResponse: the dead time in steps, the lag's pole in [0, 1], and the dead time's device scratch
+    float[delay_steps][ring_envs] (acas2d_evaluate_policies_delayed_*, acas2d_monte_carlo_delayed_*, include/acas2d.h)."""
+    _fields_ = [("delay_steps", C.c_int32), ("lag", C.c_float), ("ring", C.c_void_p), ("ring_envs", C.c_int64)]
+
+
 class CEncounterSearch(C.Structure):
     """struct Acas2dEncounterSearch: the proposal's tables, the per-candidate buffers, the stats entry's outputs, the log row,
     the archive and the settings of one generation of an encounter search (acas2d_encounter_*, include/acas2d.h)."""
@@ -166,7 +172,8 @@ EXPORTS = ("acas2d_abi_version", "acas2d_config_size", "acas2d_state_size", "aca
            "acas2d_collect_set_disturbed_group_f32", "acas2d_correlation_size", "acas2d_evaluate_policies_correlated_f32",
            "acas2d_evaluate_policies_correlated_group_f32", "acas2d_monte_carlo_correlated_f32",
            "acas2d_monte_carlo_correlated_group_f32", "acas2d_collect_set_correlated_f32",
-           "acas2d_collect_set_correlated_group_f32")
+           "acas2d_collect_set_correlated_group_f32", "acas2d_response_size", "acas2d_evaluate_policies_delayed_f32",
+           "acas2d_evaluate_policies_delayed_group_f32", "acas2d_monte_carlo_delayed_f32", "acas2d_monte_carlo_delayed_group_f32")
 
 
 class NativeLibraryError(RuntimeError):
@@ -239,8 +246,12 @@ def lib():
                        ("monte_carlo_disturbed", [C.POINTER(CMonteCarlo), C.POINTER(CDisturbance)]),
                        ("evaluate_policies_correlated", results + [C.POINTER(CEvalStats), C.POINTER(CDisturbance),
                                                                    C.POINTER(CCorrelation)]),
-                       ("monte_carlo_correlated", [C.POINTER(CMonteCarlo), C.POINTER(CDisturbance), C.POINTER(CCorrelation)])):
-        for sfx in ("f32", "group_f32") + (() if stem.endswith(("disturbed", "correlated")) else ("f64",)):     # (those: float32 only)
+                       ("monte_carlo_correlated", [C.POINTER(CMonteCarlo), C.POINTER(CDisturbance), C.POINTER(CCorrelation)]),
+                       ("evaluate_policies_delayed", results + [C.POINTER(CEvalStats), C.POINTER(CDisturbance),
+                                                                C.POINTER(CCorrelation), C.POINTER(CResponse)]),
+                       ("monte_carlo_delayed", [C.POINTER(CMonteCarlo), C.POINTER(CDisturbance), C.POINTER(CCorrelation),
+                                                C.POINTER(CResponse)])):
+        for sfx in ("f32", "group_f32") + (() if stem.endswith(("disturbed", "correlated", "delayed")) else ("f64",)):     # (those: float32 only)
             f = getattr(L, "acas2d_%s_%s" % (stem, sfx))
             f.restype = C.c_int
             f.argtypes = head + tail + [C.c_void_p]
@@ -250,6 +261,7 @@ def lib():
                                               C.c_void_p, C.c_void_p]
     L.acas2d_disturbance_size.restype = C.c_size_t
     L.acas2d_correlation_size.restype = C.c_size_t
+    L.acas2d_response_size.restype = C.c_size_t
     for name in ("acas2d_encounter_sample_f32", "acas2d_encounter_sample_f64"):
         f = getattr(L, name)
         f.restype = C.c_int
@@ -339,7 +351,7 @@ def lib():
     for name, twin in (("member_episodes", CMemberEpisodes), ("population_exploit", CPopulationExploit),
                        ("ppo_guard", CPpoGuard), ("ppo_options", CPpoOptions), ("reward_norm", CRewardNorm),
                        ("monte_carlo", CMonteCarlo), ("encounter_search", CEncounterSearch),
-                       ("disturbance", CDisturbance), ("correlation", CCorrelation)):
+                       ("disturbance", CDisturbance), ("correlation", CCorrelation), ("response", CResponse)):
         size = getattr(L, "acas2d_%s_size" % name)()
         if size != C.sizeof(twin):
             raise NativeLibraryError("%s layout mismatch: %d != %d" % (twin.__name__, size, C.sizeof(twin)))

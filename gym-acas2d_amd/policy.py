@@ -338,9 +338,96 @@ class CorrelatedDisturbance(Disturbance):
                 native.CCorrelation(self.rho_sep, self.rho_cpa, self.rho_closing, self.rho_action))
 
 
-def _c_tail(disturbance, noise_episode=0):
-    """The C structs a disturbance adds behind a scoring entry's own arguments: one, or (correlated) two."""
-    c = disturbance.to_c(noise_episode)
+@dataclasses.dataclass(frozen=True, init=False)
+class DelayedDisturbance(CorrelatedDisturbance):
+    """A CorrelatedDisturbance with a RESPONSE between the policy and the aircraft, for the float32 evaluator and Monte Carlo
+    campaign (acas2d_evaluate_policies_delayed_*, acas2d_monte_carlo_delayed_*; records.response_delay() and
+    records.response_lag() state the two steps): first-order plus dead time.
+
+    delay      the dead time in steps (0 .. 32767; at dt = 0.01 s a pilot's half second is 50): the aircraft flies the action the
+               actor produced `delay` steps earlier in the same episode, and 0 -- straight ahead -- until the first one arrives
+    lag        the pole of the first-order lag behind it, in [0, 1] (float32, as the kernels read it):
+               u_s = clamp(lag u_{s-1} + (1 - lag) c_s), u = 0 in front of an episode's first step; 1: the aircraft never responds
+    The actuator's error acts on u_s; the sensor errors are untouched.  With delay 0 and lag 0 the results are the
+    CorrelatedDisturbance's bit for bit, but the two never compare equal: to_dict() carries the delay and lag keys.  The
+    collectors, the trainers and both kinds of DisturbanceSet refuse one."""
+    delay: int
+    lag: float
+
+    MAX_DELAY = 32767
+
+    def __init__(self, sep=0.0, cpa=0.0, closing=0.0, action=0.0, seed=0, config=None, rho=0.0, rho_sep=None, rho_cpa=None,
+                 rho_closing=None, rho_action=None, delay=0, lag=0.0):
+        CorrelatedDisturbance.__init__(self, sep, cpa, closing, action, seed, config, rho, rho_sep, rho_cpa, rho_closing, rho_action)
+        self._set_response(delay, lag)
+
+    def _set_response(self, delay, lag):
+        if isinstance(delay, bool) or not 0 <= delay <= self.MAX_DELAY or int(delay) != delay:       # (a NaN fails the range)
+            raise ValueError("delay = %r (whole steps, 0 to %d)" % (delay, self.MAX_DELAY))
+        lag = float(np.float32(lag))                                         # the float32 the kernel reads
+        if not 0.0 <= lag <= 1.0:                                            # (a NaN fails both comparisons)
+            raise ValueError("lag = %r (the lag must lie in [0, 1])" % (lag,))
+        object.__setattr__(self, "delay", int(delay))
+        object.__setattr__(self, "lag", lag)
+
+    @classmethod
+    def normalised(cls, sep=0.0, cpa=0.0, closing=0.0, action=0.0, seed=0, rho=0.0, rho_sep=None, rho_cpa=None, rho_closing=None,
+                   rho_action=None, delay=0, lag=0.0):
+        d = object.__new__(cls)
+        d._set(sep, cpa, closing, action, seed)
+        d._set_rho(rho, rho_sep, rho_cpa, rho_closing, rho_action)
+        d._set_response(delay, lag)
+        return d
+
+    def to_dict(self):
+        return {**CorrelatedDisturbance.to_dict(self), "delay": self.delay, "lag": self.lag}
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls.normalised(d["s_sep"], d["s_cpa"], d["s_closing"], d["s_action"], d["seed"],
+                              **{name: d[name] for name in cls.RHO}, delay=d["delay"], lag=d["lag"])
+
+    @classmethod
+    def parse(cls, text, normalised=False, config=None):
+        """CorrelatedDisturbance.parse()'s syntax with delay= (whole steps) and lag= on top."""
+        kw, rest = {}, []
+        for item in str(text).split(","):
+            key, _, val = (part.strip() for part in item.partition("="))
+            if key not in ("delay", "lag"):
+                rest.append(item)
+                continue
+            if not val or key in kw:
+                raise ValueError("disturbance %r: %r (delay= and lag= are understood, each once)" % (text, item))
+            try:
+                kw[key] = int(val, 0) if key == "delay" else float(val)
+            except ValueError:
+                raise ValueError("disturbance %r: %r is no number" % (text, item)) from None
+        base = CorrelatedDisturbance.parse(",".join(rest), normalised, config) if rest else CorrelatedDisturbance()
+        return cls.normalised(base.s_sep, base.s_cpa, base.s_closing, base.s_action, base.seed,
+                              **{name: getattr(base, name) for name in cls.RHO}, **kw)
+
+    @staticmethod
+    def has_response(text):
+        """Whether a command-line disturbance names a delay or a lag: else it is a (Correlated)Disturbance's text."""
+        return any(item.partition("=")[0].strip() in ("delay", "lag") for item in str(text).split(","))
+
+    def ring(self, n_envs, device):
+        """The dead time's scratch for launches over `n_envs` envs (Acas2dResponse::ring): float32 [max(delay, 1), n_envs] on
+        `device`, filled with NaN -- the kernels never read a slot the episode at hand has not written, and a NaN flown would
+        show in every statistic."""
+        return torch.full((max(self.delay, 1), int(n_envs)), float("nan"), dtype=torch.float32, device=device)
+
+    def to_c(self, noise_episode=0, ring=None):
+        """All three structs: (Acas2dDisturbance, Acas2dCorrelation, Acas2dResponse); `ring`: the tensor of ring(), which the
+        caller keeps alive across the launch (None: no ring -- the library then refuses a delay above 0)."""
+        return CorrelatedDisturbance.to_c(self, noise_episode) + (
+            native.CResponse(self.delay, self.lag, 0 if ring is None else ring.data_ptr(), 0 if ring is None else ring.shape[1]),)
+
+
+def _c_tail(disturbance, noise_episode=0, ring=None):
+    """The C structs a disturbance adds behind a scoring entry's own arguments: one, (correlated) two or (delayed, with the
+    caller's `ring`) three."""
+    c = disturbance.to_c(noise_episode, ring) if isinstance(disturbance, DelayedDisturbance) else disturbance.to_c(noise_episode)
     return list(c) if isinstance(c, tuple) else [c]
 
 
@@ -419,7 +506,11 @@ class CorrelatedDisturbanceSet(DisturbanceSet):
     processes afresh, so the state needs no reset of its own then."""
 
     def __init__(self, disturbances, n_members=1):
-        self._set_members(self._as_members(disturbances, n_members), n_members)
+        ds = self._as_members(disturbances, n_members)
+        if any(isinstance(d, DelayedDisturbance) for d in ds):
+            raise ValueError("the collectors know no response delay or lag: a DelayedDisturbance is for evaluate_policies_fused() "
+                             "and MonteCarlo")
+        self._set_members(ds, n_members)
         rho = np.asarray([[getattr(d, name, 0.0) for name in CorrelatedDisturbance.RHO] for d in self.members], np.float32)
         self.corr_rows = np.concatenate([rho, records.correlation_gain(rho)], axis=1).astype(np.float32)
         self.held, self._env, self._pending = None, None, None
@@ -492,14 +583,15 @@ def disturbance_draw(seed, first_lane, n_lanes, episode, first_step, n_steps, n_
     return out.cpu().numpy()
 
 
-def _scoring_entry(caller, stem, dtype, group, disturbed, correlated=False):
-    """The scoring family's C entry for (dtype, group, disturbed, correlated); group, disturbed and correlated are float32 only,
-    and `caller` says so."""
-    for flag, on in (("group=True", group), ("disturbance=...", disturbed or correlated)):
+def _scoring_entry(caller, stem, dtype, group, disturbed, correlated=False, delayed=False):
+    """The scoring family's C entry for (dtype, group, disturbed, correlated, delayed); group and the three disturbed flavours are
+    float32 only, and `caller` says so."""
+    disturbed, correlated = disturbed or correlated or delayed, correlated or delayed
+    for flag, on in (("group=True", group), ("disturbance=...", disturbed)):
         if on and dtype != torch.float32:
             raise ValueError("%s(%s) is float32 only, got %s" % (caller, flag, dtype))
-    if disturbed or correlated:
-        stem = stem.replace("_stats", "") + ("_correlated" if correlated else "_disturbed")
+    if disturbed:
+        stem = stem.replace("_stats", "") + ("_delayed" if delayed else "_correlated" if correlated else "_disturbed")
     return "acas2d_%s%s_%s" % (stem, "_group" if group else "", "f32" if dtype == torch.float32 else "f64")
 
 
@@ -537,10 +629,10 @@ class PolicyBlocks:
             obs.data_ptr(), n_steps, venv.seed_value, venv.env_offset, venv.n_traffic, *tail, venv._stream()))
 
 
-def evaluate_policies_entry(dtype, group=False, safety=False, disturbed=False, correlated=False):
-    """The name of the C entry point evaluate_policies_fused() calls for (dtype, group, safety, disturbed, correlated)."""
+def evaluate_policies_entry(dtype, group=False, safety=False, disturbed=False, correlated=False, delayed=False):
+    """The name of the C entry point evaluate_policies_fused() calls for (dtype, group, safety, disturbed, correlated, delayed)."""
     return _scoring_entry("evaluate_policies_fused", "evaluate_policies_stats" if safety else "evaluate_policies", dtype, group,
-                          disturbed, correlated)
+                          disturbed, correlated, delayed)
 
 
 def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float64, device="cuda:0", config=None,
@@ -562,15 +654,17 @@ def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float
     (acas2d_evaluate_policies_disturbed_*; it always computes the statistics, so the six keys are returned whatever
     `safety` says).  Episode i draws the noise of lane env_offset + i and episode counter `noise_episode`: what lane i of a
     MonteCarlo campaign with the same disturbance and env_offset met in its episode `noise_episode`.
-    A CorrelatedDisturbance takes the launch under time-correlated and biased errors (acas2d_evaluate_policies_correlated_*)."""
+    A CorrelatedDisturbance takes the launch under time-correlated and biased errors (acas2d_evaluate_policies_correlated_*), a
+    DelayedDisturbance the one with a response delay and an actuation lag on top (acas2d_evaluate_policies_delayed_*)."""
     from .vec_env import ACAS2DVecEnv
     if not policies:
         raise ValueError("evaluate_policies_fused needs at least one policy")
     if disturbance is None:
         entry = evaluate_policies_entry(dtype, group, safety)
     else:
-        safety, entry = True, evaluate_policies_entry(dtype, group, True, disturbed=True,
-                                                      correlated=isinstance(disturbance, CorrelatedDisturbance))
+        delayed = isinstance(disturbance, DelayedDisturbance)         # (the subclass first)
+        safety, entry = True, evaluate_policies_entry(dtype, group, True, disturbed=True, delayed=delayed,
+                                                      correlated=not delayed and isinstance(disturbance, CorrelatedDisturbance))
     own, traffic = np.asarray(own), np.asarray(traffic)
     E, N = own.shape[0], traffic.shape[1]
     if config is None:
@@ -592,7 +686,9 @@ def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float
         st_i = torch.empty(2, K, E, dtype=torch.int32, device=dev)              # min_sep_step, los_steps
         tail.append(blocks.c_eval_stats(st_f, st_i))
     if disturbance is not None:
-        tail.extend(_c_tail(disturbance, noise_episode))
+        # (a DelayedDisturbance: the dead time's ring over the launch's K x EP envs, alive until the results are read back)
+        ring = disturbance.ring(len(idx), dev) if isinstance(disturbance, DelayedDisturbance) else None
+        tail.extend(_c_tail(disturbance, noise_episode, ring))
     with torch.cuda.device(dev):
         blocks.call(entry, v, v.outputs["obs"], T, *tail)
     oc, st = outcome.cpu().numpy(), steps.cpu().numpy()
@@ -607,9 +703,9 @@ def evaluate_policies_fused(policies, own, traffic, goal=None, dtype=torch.float
     return res
 
 
-def monte_carlo_entry(dtype, group=False, disturbed=False, correlated=False):
-    """The name of the C entry point MonteCarlo launches for (dtype, group, disturbed, correlated)."""
-    return _scoring_entry("MonteCarlo", "monte_carlo", dtype, group, disturbed, correlated)
+def monte_carlo_entry(dtype, group=False, disturbed=False, correlated=False, delayed=False):
+    """The name of the C entry point MonteCarlo launches for (dtype, group, disturbed, correlated, delayed)."""
+    return _scoring_entry("MonteCarlo", "monte_carlo", dtype, group, disturbed, correlated, delayed)
 
 
 class MonteCarlo:
@@ -630,7 +726,9 @@ class MonteCarlo:
                float32).  The noise of (lane, counter) is a function of the disturbance's seed, env_offset + lane, the counter
                and the step alone, so the K policies meet the same noise on the same encounters, and encounter() names
                everything a replay needs.  A CorrelatedDisturbance: the campaign under time-correlated and biased errors
-               (acas2d_monte_carlo_correlated_*); a lane's error processes restart with every episode it draws.
+               (acas2d_monte_carlo_correlated_*); a lane's error processes restart with every episode it draws.  A
+               DelayedDisturbance: with a response delay and an actuation lag on top (acas2d_monte_carlo_delayed_*); the delay
+               line and the lag restart with every episode too, and the campaign owns the delay line's ring on the device.
     """
 
     def __init__(self, policies, n_lanes, seed=13, dtype=torch.float32, group=False, config=None, n_traffic=1, n_bins=64,
@@ -638,8 +736,9 @@ class MonteCarlo:
         from .vec_env import ACAS2DVecEnv
         if not policies:
             raise ValueError("MonteCarlo needs at least one policy")
+        delayed = isinstance(disturbance, DelayedDisturbance)         # (the subclass first)
         self.entry = monte_carlo_entry(dtype, group) if disturbance is None else monte_carlo_entry(
-            dtype, group, disturbed=True, correlated=isinstance(disturbance, CorrelatedDisturbance))
+            dtype, group, disturbed=True, delayed=delayed, correlated=not delayed and isinstance(disturbance, CorrelatedDisturbance))
         self.disturbance = disturbance
         self.config = config if config is not None else ACAS2DConfig(n_traffic=n_traffic)
         self.n_lanes, self.n_policies, self.dtype, self.seed = int(n_lanes), len(policies), dtype, int(seed)
@@ -657,6 +756,7 @@ class MonteCarlo:
         self._blocks = PolicyBlocks(policies, L, self._src.obs_dim, dev)
         self._all = mk(K * self._blocks.EP, int(env_offset))     # ... which is replicated into its K blocks (padding: lane 0)
         self._idx = self._blocks.index(dev)
+        self._ring = disturbance.ring(K * self._blocks.EP, dev) if delayed else None     # the dead time's scratch, for every launch
         npdt = np.float32 if dtype == torch.float32 else np.float64
         self._acc = {k: torch.as_tensor(v.view(np.int32) if v.dtype == np.uint32 else v).to(dev)
                      for k, v in records.monte_carlo_empty(K, L, max(self.n_bins, 1), npdt).items()}     # (n_bins < 1: the launch refuses)
@@ -678,7 +778,7 @@ class MonteCarlo:
             mc = native.CMonteCarlo(*[self._acc[k].data_ptr() for k in records.MONTE_CARLO_KEYS], self.n_bins, int(episodes),
                                     self.inv_bin_width, self.first_episode, 0)
             n_steps = max(int(episodes), 0) * self.config.max_steps
-            tail = [mc] if self.disturbance is None else [mc] + _c_tail(self.disturbance)
+            tail = [mc] if self.disturbance is None else [mc] + _c_tail(self.disturbance, ring=self._ring)
             if events:
                 events[0].record()
             self._blocks.call(self.entry, dst, dst._obs, n_steps, *tail)      # (dst has src's seed, env_offset and n_traffic)

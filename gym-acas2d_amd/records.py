@@ -518,3 +518,57 @@ def correlated_step(held, normals, rho, first):
         a = (rho_b * h).astype(np.float32)
         b = (q * z).astype(np.float32)
         return np.where((rho_b == 0) | np.broadcast_to(np.asarray(first, bool), z.shape), z, (a + b).astype(np.float32))
+
+
+# ---- response delay and actuation lag (acas2d_evaluate_policies_delayed_*, acas2d_monte_carlo_delayed_*) --------------------
+def response_gain(lag):
+    """The gain g = (float32)(1 - lag) of the first-order lag, `lag` a float32 in [0, 1]: the difference in float64 (exact),
+    then ONE rounding to float32, as the C entry forms it."""
+    lam = np.float32(lag)
+    if not 0 <= lam <= 1:                                                        # (a NaN fails both comparisons)
+        raise ValueError("response_gain: lag = %r (in [0, 1])" % (lag,))
+    return np.float32(1.0 - np.float64(lam))
+
+
+def response_delay(actions, delay):
+    """The dead time: `actions` [steps, ...] from an episode's FIRST step on (axis 0 is the step), the actor's clipped actions;
+    returns the commands c of the same shape, c_s = a_{s - delay} and 0 for the first `delay` steps (nothing has arrived: the
+    aircraft flies straight).  delay == 0 gives the actions' own bits; delay >= steps gives all zeros."""
+    a = np.asarray(actions)
+    d = int(delay)
+    if a.ndim < 1 or d != delay or d < 0:
+        raise ValueError("response_delay: actions [steps, ...] and a whole delay of at least 0 are required")
+    out = np.zeros_like(a)
+    if d < a.shape[0]:
+        out[d:] = a[:a.shape[0] - d]
+    return out
+
+
+def response_lag_step(held, commands, lag, first, dtype=np.float32):
+    """ONE step of the lag: u_s = clamp((lag u_{s-1}) + (g c_s)) from `held` = u_{s-1} and `commands` = c_s (arrays of one
+    shape), with 0 in u_{s-1}'s place where `first` (a bool or bool array: the step is an episode's first); two products and a
+    sum in `dtype`, each rounded, no fma, g = response_gain(lag), then fmin(fmax(., -1), 1) -- which sends a NaN to -1, as
+    fminf(fmaxf()) does.  lag == 0: the commands' own bits (no arithmetic)."""
+    c = np.asarray(commands, dtype)
+    lam = np.float32(lag)
+    g = response_gain(lam)
+    if lam == 0:
+        return c.copy()
+    prev = np.where(np.broadcast_to(np.asarray(first, bool), c.shape), dtype(0), np.broadcast_to(np.asarray(held, dtype), c.shape))
+    with np.errstate(invalid="ignore", over="ignore"):
+        a = (dtype(lam) * prev).astype(dtype)
+        b = (dtype(g) * c).astype(dtype)
+        return np.fmin(np.fmax((a + b).astype(dtype), dtype(-1)), dtype(1)).astype(dtype)
+
+
+def response_lag(commands, lag, dtype=np.float32):
+    """The first-order lag behind the dead time: `commands` [steps, ...] from an episode's FIRST step on; returns u of the same
+    shape, u_s = clamp((lag u_{s-1}) + (g c_s)) with u = 0 in front of the first step (response_lag_step() is one step of it).
+    lag == 0 gives the commands' own bits; lag == 1 (g = 0) gives zeros: the aircraft never responds."""
+    c = np.asarray(commands, dtype)
+    if c.ndim < 1:
+        raise ValueError("response_lag: commands [steps, ...] are required")
+    u = np.empty_like(c)
+    for s in range(c.shape[0]):
+        u[s] = response_lag_step(u[s - 1] if s else np.zeros_like(c[0]), c[s], lag, s == 0, dtype)
+    return u

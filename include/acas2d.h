@@ -560,6 +560,64 @@ int acas2d_monte_carlo_correlated_group_f32(const Acas2dConfig *cfg, const Acas2
                                             void *stream);
 
 /*
+ * acas2d_evaluate_policies_delayed_f32 / _group_f32, acas2d_monte_carlo_delayed_f32 / _group_f32: the correlated entries
+ * above with a RESPONSE between the policy and the aircraft -- a dead time (the pilot's response delay) and a first-order
+ * lag (the aircraft's).  Additive to ABI 7, float32 only.  The arguments of the _correlated sibling with `response` in
+ * front of `stream`; the same work shapes, the same rejections in the same words.
+ *   With a_s the actor's clipped action at a step (a NaN mean passes through), the step flies
+ *     c_s = a_{s - delay_steps}                    the action the same lane's actor produced delay_steps steps earlier in the
+ *                                                  same episode, played in the same launch; 0.0f while the episode is younger
+ *                                                  than that (the aircraft flies straight until the first command arrives);
+ *                                                  delay_steps == 0: c_s = a_s, and `ring` is not touched;
+ *     u_s = clamp((lag * u_{s-1}) + (g * c_s))     to [-1, 1] by fminf(fmaxf(., -1), 1): two float32 multiplies and a float32
+ *                                                  add, each rounded, no fma, with u = 0 in front of the episode's first step
+ *                                                  and g = (float)(1.0 - (double)lag) formed on the host; lag == 0: u_s = c_s,
+ *                                                  no arithmetic; lag == 1: the aircraft never responds;
+ *   and the actuator's error acts on u_s as it acts on the clipped action in the sibling.  An episode's first step is the
+ *   sibling's: the lane's first step of the launch, and the first step after an in-step reset.  Sensor noise is untouched.
+ *   With delay_steps == 0 and lag == 0 the results equal the _correlated entries' bit for bit.
+ *   ring       device float[delay_steps][ring_envs], scratch for the dead time: row steps % delay_steps holds the actions the
+ *              envs of the launch (n_policies x n_episodes or n_lanes rounded up to 64) wrote delay_steps steps ago.  Its
+ *              contents on entry mean nothing and need no clearing: no row is read before the episode at hand has written
+ *              it.  An env's step costs one 4-byte load and one 4-byte store.  Launches that run at the same time need rings
+ *              of their own.
+ * Rejected with ACAS2D_EINVAL before anything is launched: everything the _correlated sibling rejects, in its words and its
+ * order; then a NULL response; delay_steps below 0 or above 32767; a lag that is NaN, negative or above 1; delay_steps > 0
+ * with a NULL ring, or with ring_envs below the launch's env count.
+ */
+typedef struct Acas2dResponse {
+    int32_t delay_steps;                   /* dead time between the actor and the aircraft, in steps */
+    float lag;                             /* the first-order lag's pole, in [0, 1] */
+    float *ring;                           /* device float[delay_steps][ring_envs]; may be NULL when delay_steps == 0 */
+    int64_t ring_envs;
+} Acas2dResponse;
+size_t acas2d_response_size(void);     /* sizeof(Acas2dResponse), for bindings */
+int acas2d_evaluate_policies_delayed_f32(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                                         const Acas2dPolicy *policies, int32_t n_policies, int32_t n_episodes,
+                                         const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
+                                         int32_t n_traffic, uint8_t *outcome, int32_t *steps, void *total_reward,
+                                         const Acas2dEvalStats *stats, const Acas2dDisturbance *disturbance,
+                                         const Acas2dCorrelation *correlation, const Acas2dResponse *response, void *stream);
+int acas2d_evaluate_policies_delayed_group_f32(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                                               const Acas2dPolicy *policies, int32_t n_policies, int32_t n_episodes,
+                                               const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
+                                               int32_t n_traffic, uint8_t *outcome, int32_t *steps, void *total_reward,
+                                               const Acas2dEvalStats *stats, const Acas2dDisturbance *disturbance,
+                                               const Acas2dCorrelation *correlation, const Acas2dResponse *response,
+                                               void *stream);
+int acas2d_monte_carlo_delayed_f32(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                                   const Acas2dPolicy *policies, int32_t n_policies, int32_t n_lanes, const void *obs_in,
+                                   int32_t n_steps, uint64_t seed, int64_t env_offset, int32_t n_traffic,
+                                   const Acas2dMonteCarlo *mc, const Acas2dDisturbance *disturbance,
+                                   const Acas2dCorrelation *correlation, const Acas2dResponse *response, void *stream);
+int acas2d_monte_carlo_delayed_group_f32(const Acas2dConfig *cfg, const Acas2dState *state, int64_t n_envs,
+                                         const Acas2dPolicy *policies, int32_t n_policies, int32_t n_lanes,
+                                         const void *obs_in, int32_t n_steps, uint64_t seed, int64_t env_offset,
+                                         int32_t n_traffic, const Acas2dMonteCarlo *mc,
+                                         const Acas2dDisturbance *disturbance, const Acas2dCorrelation *correlation,
+                                         const Acas2dResponse *response, void *stream);
+
+/*
  * acas2d_collect_set_disturbed_f32 / acas2d_collect_set_disturbed_group_f32: acas2d_collect_set_f32 / _group_f32 under the
  * sensor noise and actuator disturbance above -- the collector of a PPO iteration that TRAINS under them.  Additive to
  * ABI 7, float32 only.  The siblings' arguments, then `sigmas`, `dist_seed` and `obs_read` in front of `stream`.

@@ -17,6 +17,9 @@ encounters at every level, the checkpoint lines of each level carrying its distu
 With rho=R (all four channels) or rho_sep=, rho_cpa=, rho_closing=, rho_action= among the keys the errors persist: a
 first-order Gauss-Markov process per channel with step-to-step correlation R in [0, 1], 1 being a constant bias per episode
 (policy.CorrelatedDisturbance); a string without them is the white noise it has always been.
+With delay=STEPS and / or lag=L among the keys the aircraft flies the action the policy gave STEPS steps earlier (0 until the
+first one arrives: a pilot's response delay, 50 steps being half a second) through a first-order lag with pole L in [0, 1]
+(policy.DelayedDisturbance; the rho keys go with it as before).
 --search CANDIDATESxGENERATIONS instead runs an encounter search per checkpoint (policy.EncounterSearch: cross-entropy
 proposals refit on the device, importance-sampling weights): one JSON line per checkpoint gives the estimated probability of
 min_separation <= the collision distance with its standard error, beside a crude campaign of the same number of episodes
@@ -29,6 +32,7 @@ closest encounter found.
     python tools/evaluate_checkpoints.py DIR --monte-carlo 65536x8 --dtype float32 --baseline-zero \
         --disturbance sep=0,cpa=0,closing=0,action=0 --disturbance sep=90,cpa=40,closing=8,action=0.1,seed=7
     python tools/evaluate_checkpoints.py DIR --monte-carlo 65536x8 --dtype float32 --disturbance sep=90,cpa=40,rho=0.99,seed=7
+    python tools/evaluate_checkpoints.py DIR --monte-carlo 65536x8 --dtype float32 --disturbance delay=50,lag=0.5
 """
 import argparse
 import glob
@@ -58,6 +62,11 @@ args = ap.parse_args()
 
 
 def parse_disturbance(text):
+    if g.policy.DelayedDisturbance.has_response(text):   # a response delay and / or a lag: policy.DelayedDisturbance
+        try:
+            return g.policy.DelayedDisturbance.parse(text)
+        except ValueError as e:
+            sys.exit("--disturbance: %s" % e)
     if g.policy.CorrelatedDisturbance.has_rho(text):     # a Gauss-Markov error per channel: policy.CorrelatedDisturbance
         try:
             return g.policy.CorrelatedDisturbance.parse(text)

@@ -78,7 +78,13 @@ ap.add_argument("--out", default=None)
 
 def training_disturbances(texts, n_members, normalised):
     """--disturbance's texts as the trainers take them: a text that names a correlation makes the set a
-    CorrelatedDisturbanceSet (its other members white: rho 0), else one Disturbance or one per member as before."""
+    CorrelatedDisturbanceSet (its other members white: rho 0), else one Disturbance or one per member as before.  A text with
+    delay= or lag= is a DelayedDisturbance, which the trainers refuse in their own words (it is for the evaluator and the
+    campaign)."""
+    if any(g.DelayedDisturbance.has_response(t) for t in texts):
+        ds = [g.DelayedDisturbance.parse(t, normalised=normalised) if g.DelayedDisturbance.has_response(t)
+              else g.Disturbance.parse(t, normalised=normalised) for t in texts]
+        return g.CorrelatedDisturbanceSet(ds[0] if len(ds) == 1 else ds, n_members)         # raises: no response in a collector
     if any(g.CorrelatedDisturbance.has_rho(t) for t in texts):
         ds = [g.CorrelatedDisturbance.parse(t, normalised=normalised) if g.CorrelatedDisturbance.has_rho(t)
               else g.Disturbance.parse(t, normalised=normalised) for t in texts]
